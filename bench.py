@@ -37,8 +37,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
-# the stream lanes of a step must land on different hardware queues to overlap (new_streams); the ROCm runtime reads this once
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
@@ -218,9 +216,9 @@ def new_streams(torch, dev, n):
     """n HIP streams of their own (hipStreamCreateWithFlags, non-blocking -- what the library creates for itself), wrapped for
     torch.  Explicit handles: torch's DEFAULT stream has handle 0, which the ABI reads as "the searcher's own stream", so the
     torch ops that follow a call on the default stream (the exchange's pack above all) would not be ordered behind it.
-    Whether two streams overlap at all depends on the hardware queues the runtime maps them to: with its default of 4 queues
-    (GPU_MAX_HW_QUEUES) the same two lanes measured 465 k or 515 k q/s on C3 depending on how many other streams the process
-    had created before them; bench.py therefore asks for 8 queues (set below, before the runtime starts; recorded in the line)."""
+    Whether two streams overlap at all depends on the hardware queues the runtime maps them to: the same two lanes measured
+    465 k or 515 k q/s on C3 depending on how many other streams the process had created before them.  bench.py leaves the
+    runtime's queue count to the environment and records it in the line."""
     global _HIP
     import ctypes
     if _HIP is None:
@@ -268,6 +266,30 @@ def new_streams(torch, dev, n):
                 out.append(c)
     _LANES[str(dev)] = out
     return out
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap_bytes=DUMP_CAP_BYTES, seed=0):
+    """Write `arrays` (name -> array whose first axis is the query) as out_dir/<name>.npy: float32 arrays as they are, every
+    other dtype as float64 (exact for the u32 / i32 / i64 ids and counts here).  Over cap_bytes in all, the same fixed,
+    seeded sample of queries is kept in every array and its query indices are written as query_index.npy."""
+    conv = {name: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+            for name, a in arrays.items()}
+    n = len(next(iter(conv.values())))
+    total = sum(a.nbytes for a in conv.values())
+    sample = None
+    if total > cap_bytes:
+        m = max(1, int((cap_bytes - 4096 * (len(conv) + 1)) // (total / n + 8)))       # 4 KB per file for the .npy header
+        sample = np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False))
+        conv = {name: a[sample] for name, a in conv.items()}
+        conv["query_index"] = sample.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": {name: [str(a.dtype)] + list(a.shape) for name, a in conv.items()},
+            "bytes": int(sum(a.nbytes for a in conv.values())), "sampled_queries": None if sample is None else int(len(sample))}
 
 
 def spread(nq, m):
@@ -1056,7 +1078,12 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the c2 / refbench / c4-shard / c5 passes that follow the default C3 run")
     ap.add_argument("--parity-queries", type=int, default=64, help="queries of the step checked bit for bit against the CPU oracle")
     ap.add_argument("--recall", type=int, default=32, help="queries checked against an exact brute force (0 disables)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (distances, rows, and per-query counts "
+                         "where the step returns them) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.dump_outputs and args.from_parquet:
+        raise SystemExit("--dump-outputs covers the timed top-k step; --from-parquet times an index build")
     global K
     K = args.k
 
@@ -1221,31 +1248,36 @@ def main():
             dist.all_reduce(cal, op=dist.ReduceOp.MAX)
         steps = int(max(20, math.ceil(1.2 / max(float(cal.item()), 1e-6))))
     barrier()
-    # The timed block is EXACTLY `steps` steps between barrier + synchronize on both sides.  A short block (the driver's
-    # --steps 20 is 40 ms on C3) is repeated until the blocks add up to >= 1 s, and the MEDIAN block is reported
-    # (`repeats`; every rank runs the same count: the decision is taken on the all-reduced time of the first block).
+    # The timed region is ONE block of EXACTLY `steps` steps between barrier + synchronize on both sides: `--steps K` times K
+    # steps, and ms_per_step is that block's time / K.
     searcher.set_timing(not args.no_timing)
-    block_s = []
-    rank_block_s = []          # per block: every rank's own wall time (the line reports the spread)
-    repeats = 1
-    while len(block_s) < repeats:
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            out_d, out_r = step()
-        barrier()
-        el_b = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-        if use_dist:
-            mine = el_b.clone()
-            every = [torch.zeros_like(mine) for _ in range(world)]
-            dist.all_gather(every, mine)
-            rank_block_s.append([float(x.item()) for x in every])
-            dist.all_reduce(el_b, op=dist.ReduceOp.MAX)
-        block_s.append(float(el_b.item()))
-        if len(block_s) == 1 and args.steps > 0:
-            repeats = int(min(200, max(1, math.ceil(1.0 / max(block_s[0], 1e-6)))))
-    elapsed = float(np.median(block_s))
+    rank_block_s = []          # every rank's own wall time of the block (the line reports the spread)
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        out_d, out_r = step()
+    barrier()
+    el_b = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+    if use_dist:
+        mine = el_b.clone()
+        every = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(every, mine)
+        rank_block_s.append([float(x.item()) for x in every])
+        dist.all_reduce(el_b, op=dist.ReduceOp.MAX)
+    block_s = [float(el_b.item())]
+    elapsed = block_s[0]
     searcher.set_timing(False)
     rerank_ms, total_ms, ncalls = searcher.timing_read()
+    # what the last timed step handed its caller, copied out before anything below reuses the lanes' buffers
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outs = {"distances": out_d.cpu().numpy(), "rows": out_r.cpu().numpy()}
+        if outs["rows"].dtype == np.int32:
+            outs["rows"] = outs["rows"].view(np.uint32)          # row ids are u32 (pqv.h)
+        if not exchange:
+            last = (step_no[0] - 1) % n_lanes
+            outs["n_found"] = nf_l[last].cpu().numpy()
+            outs["n_candidates"] = nc_l[last].cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, outs)
     # A serial pass (outside the timed region): steps issued one at a time on one stream -- the step time
     # without the overlap between consecutive steps, and the isolated per-launch kernel durations.
     serial_ms, serial_rr_ms, serial_hot_ms = None, None, None
@@ -1339,8 +1371,8 @@ def main():
                    else "single GPU"},
         "timed_region_s": float(sum(block_s)),
         "repeats": len(block_s),
-        "repeats_note": "blocks of exactly `steps` steps (barrier + synchronize on both sides, max over ranks); ms_per_step and value "
-                        "are the MEDIAN block; min / max block ms_per_step: %.4f / %.4f" % (min(block_s) / steps * 1e3, max(block_s) / steps * 1e3),
+        "repeats_note": "one timed block of exactly `steps` steps (barrier + synchronize on both sides, max over ranks); ms_per_step "
+                        "and value are that block's",
         "pipelining": {"streams": n_lanes, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
                        "note": "steps alternate between %d HIP streams, so consecutive steps overlap on the GPU and ms_per_step "
                                "(throughput) is below one step's own latency; ms_per_step_serial is the same step issued "
@@ -1396,11 +1428,12 @@ def main():
                       "frac": (mf / (k_ms * 1e-3) / 1e12 / (3944.0 if i8 else 2500.0 if f16 else 157.3)) if k_ms else 0.0} if screened else None,
     }
     result["counters"] = ctr
+    if dumped:
+        result["dump_outputs"] = dumped
     if rank_block_s:
-        med = int(np.argsort(block_s)[len(block_s) // 2])
-        per = [t / steps * 1e3 for t in rank_block_s[med]]
+        per = [t / steps * 1e3 for t in rank_block_s[0]]
         result["per_rank_ms_per_step"] = {"min": min(per), "max": max(per), "ranks": per,
-                                          "note": "every rank's own wall time of the median block / steps; the line's ms_per_step is the maximum"}
+                                          "note": "every rank's own wall time of the timed block / steps; the line's ms_per_step is the maximum"}
     if exchange and xchg.fast:
         # the library merge kernel against the torch stable-sort merge of the same gathered lists
         lane = (step_no[0] - 1) % n_lanes if step_no[0] else 0
@@ -1666,9 +1699,10 @@ def brute_f64_check(torch, corpus_t, queries_t, rows, dist, sel, k):
             "ok": bool(err <= 1e-4 and missed == 0)}
 
 
-def brute_measure(args, pqv, torch, dev, local_rank, name, k, steps=5, corpus_t=None, queries_t=None):
+def brute_measure(args, pqv, torch, dev, local_rank, name, k, steps=5, corpus_t=None, queries_t=None, outputs=None):
     """BASELINE config 5: exhaustive cosine top-k of nq queries per step as a Q.V^T contraction on the matrix cores
-    (pqv_brute_topk; an extension -- the reference has no cosine).  The 32 checked queries are answers of the timed run."""
+    (pqv_brute_topk; an extension -- the reference has no cosine).  The 32 checked queries are answers of the timed run.
+    `outputs` (a dict), if given, receives the last timed step's rows / distances / n_found."""
     n, dim, _, _, nq = WORKLOADS[name]
     t_all = time.perf_counter()
     if corpus_t is None:
@@ -1687,6 +1721,8 @@ def brute_measure(args, pqv, torch, dev, local_rank, name, k, steps=5, corpus_t=
         rows, dist, nf = corpus.brute_topk(q_host, k, pqv.PQV_COSINE)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(distances=dist, rows=rows, n_found=nf)
     ms = elapsed / steps * 1e3
     flops = 2.0 * nq * n * dim
     f32_only = os.environ.get("PQV_BRUTE_F16", "1") == "0"
@@ -1723,8 +1759,9 @@ def bench_brute(args, pqv, torch, corpus, corpus_t, queries_t, n, dim, nq, rank,
     if world != 1:
         raise SystemExit("the c5 workload is single-GPU")
     steps = args.steps if args.steps > 0 else 5
+    outs = {}
     rec = brute_measure(args, pqv, torch, corpus_t.device, corpus_t.device.index or 0, args.workload, K, steps=steps,
-                        corpus_t=corpus_t, queries_t=queries_t)
+                        corpus_t=corpus_t, queries_t=queries_t, outputs=outs)
     result = {
         "metric": "topk_queries_per_s_k10", "value": rec["value"], "unit": "queries/s",
         "n_gpus": 1, "steps": steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"],
@@ -1734,6 +1771,8 @@ def bench_brute(args, pqv, torch, corpus, corpus_t, queries_t, n, dim, nq, rank,
         "timed_region_s": rec["ms_per_step"] * steps * 1e-3,
         "roofline": rec["roofline"], "parity": rec["parity"],
     }
+    if args.dump_outputs:
+        result["dump_outputs"] = dump_outputs(args.dump_outputs, outs)
     rc = 0 if rec["parity"]["ok"] else 3
     if not args.no_cpu:
         # CPU column: f64 numpy brute force on a row slice (multithreaded BLAS), extrapolated linearly in rows

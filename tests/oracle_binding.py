@@ -3,9 +3,12 @@
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg.  The product package (pq_vector_amd) never imports this module.
 """
+import atexit
 import ctypes as C
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -29,13 +32,29 @@ class PqoIndex(C.Structure):
                 ("list_off", u64p), ("list_rows", u32p)]
 
 
+_HOST_DIR = None
+
+
+def _host_dir():
+    """Private directory of this process for the host-tuned flavours ("native", "fast"): they are built on the host that runs
+    them, never in the tree, which may be read-only for whoever runs the benchmark."""
+    global _HOST_DIR
+    if _HOST_DIR is None:
+        _HOST_DIR = tempfile.mkdtemp(prefix="pqv_oracle_")
+        atexit.register(shutil.rmtree, _HOST_DIR, True)
+    return _HOST_DIR
+
+
 def build_oracle(target="all"):
-    subprocess.check_call(["make", "-s", "-C", ORACLE_DIR, target])
+    cmd = ["make", "-s", "-C", ORACLE_DIR, target]
+    if target in ("native", "fast"):
+        cmd.append("OUT=" + _host_dir())
+    subprocess.check_call(cmd)
 
 
 def load(native=False, fast=False):
     name = "libpqv_oracle_fast.so" if fast else "libpqv_oracle_native.so" if native else "libpqv_oracle.so"
-    path = os.path.join(ORACLE_DIR, name)
+    path = os.path.join(_host_dir() if (native or fast) else ORACLE_DIR, name)
     if not os.path.exists(path):
         build_oracle("fast" if fast else "native" if native else "all")
     lib = C.CDLL(path)
