@@ -322,6 +322,37 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// Range search (no counterpart in the reference): for every query (`queries.len() == nq * dim`) each candidate
+    /// of `nprobe` lists whose distance (sqrt of the `PQV_L2SQ_REF4` d2, as [`Searcher::topk`]) is `<= radius`, ascending
+    /// by (distance, candidate position); `max_results > 0` keeps the first that many per query.  A NaN radius is an error.
+    pub fn range_search(&self, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64)
+        -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (mut lims, mut rows, mut dist) = (ptr::null_mut::<u64>(), ptr::null_mut::<u32>(), ptr::null_mut::<f32>());
+        check(unsafe {
+            sys::pqv_range_search(self.raw, queries.as_ptr(), nq as u32, dim as u32, radius, nprobe.get() as u32, 0, max_results,
+                                  sys::PQV_L2SQ_REF4, 1, &mut lims, &mut rows, &mut dist, ptr::null_mut(), ptr::null_mut())
+        })?;
+        if lims.is_null() || rows.is_null() || dist.is_null() {
+            unsafe { sys::pqv_range_free(lims, rows, dist) };
+            return Err("pqv_range_search returned a NULL buffer".into());
+        }
+        let out = {
+            let l = unsafe { std::slice::from_raw_parts(lims, nq + 1) };
+            let total = l[nq] as usize;
+            let (r, d) = if total == 0 {
+                (&[][..], &[][..])
+            } else {
+                unsafe { (std::slice::from_raw_parts(rows, total), std::slice::from_raw_parts(dist, total)) }
+            };
+            (0..nq)
+                .map(|q| (l[q] as usize..l[q + 1] as usize).map(|i| SearchResult { row_idx: r[i], distance: d[i] }).collect())
+                .collect()
+        };
+        unsafe { sys::pqv_range_free(lims, rows, dist) };
+        Ok(out)
+    }
+
     /// Plan metrics (`src/df_vector/index_exec.rs:289-299`, `exec.rs:411-427`).
     pub fn counters(&self) -> Result<sys::PqvCounters> {
         let mut c = sys::PqvCounters::default();

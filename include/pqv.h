@@ -312,6 +312,27 @@ int pqv_topk_device_flags(const pqv_searcher *searcher, const void *d_queries, u
                           uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, void *d_row_idx,
                           void *d_dist, void *d_n_found, void *d_n_candidates, void *d_tie_flags, void *hip_stream);
 
+/* Range search: EVERY candidate within `radius` of each query, for nq queries in one call.
+ *   candidates   candidate_rows(q, nprobe) (probe-rank order, list order inside a list), the first max_candidates of them
+ *                when max_candidates > 0 (as pqv_topk); a candidate's position is its index in that sequence.  nprobe is
+ *                clamped to n_clusters and may exceed 1024.
+ *   distance     d2 of `metric` (bit-identical to pqv_topk's); out = sqrt_out ? sqrt(d2) (correctly rounded) : d2.
+ *   hit          out <= radius (inclusive, on the output scale).  A NaN distance is never a hit; radius = +inf keeps every
+ *                other candidate, a negative radius none; a NaN radius is PQV_ERR_INVALID ("radius must not be NaN").
+ *   order        ascending by (d2, position): unique per query, independent of scheduling.
+ *   max_results  > 0: only the first max_results hits in that order are returned.  Where the cut falls inside a group of
+ *                equal distances the kept rows follow (d2, position) -- pqv_topk, which follows the reference's heap
+ *                history on ties, may keep others.
+ * Output (CSR): query q's hits are row_idx / dist [lims[q], lims[q+1]); *lims [nq + 1] (lims[0] = 0, allocated also for
+ * nq = 0), *row_idx and *dist [lims[nq]] are library buffers released with pqv_range_free.  n_within host [nq] (may be
+ * NULL): the full hit count (before max_results); n_candidates host [nq] (may be NULL): sum of the probed lists' lengths,
+ * before the cap.  Counters advance as for a pqv_topk call of the same shape; the searcher's other state is untouched. */
+int  pqv_range_search(const pqv_searcher *searcher, const float *queries, uint32_t nq, uint32_t query_len,
+                      float radius, uint32_t nprobe, uint64_t max_candidates, uint64_t max_results,
+                      int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
+                      uint64_t *n_within, uint64_t *n_candidates);
+void pqv_range_free(uint64_t *lims, uint32_t *row_idx, float *dist);
+
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`
  * baseline does row by row (benches/query.rs:76-98), for the metrics above.  Results are

@@ -440,6 +440,37 @@ class Searcher:
                                    nc.ctypes.data_as(u64p)))
         return rows, dist, nf, nc
 
+    def range_search(self, queries, radius, nprobe, max_candidates=0, max_results=0, metric=_ffi.PQV_L2SQ_REF4,
+                     sqrt_out=True):
+        """Every candidate within `radius` of each query (pqv.h: pqv_range_search), ascending by (d2, candidate position).
+        Returns (lims u64 [nq+1], rows u32, dist f32, n_within u64 [nq], n_candidates u64 [nq]): query q's hits are
+        rows / dist [lims[q]:lims[q+1]]; n_within is the hit count before max_results."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        radius = float(radius)
+        if nprobe == 0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be > 0")
+        if radius != radius:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "radius must not be NaN")
+        nq, qlen = q.shape
+        if qlen != self.dim:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"Query dimension mismatch: expected {self.dim}, got {qlen}")
+        nw = np.zeros(nq, dtype=np.uint64)
+        nc = np.zeros(nq, dtype=np.uint64)
+        lims_p, rows_p, dist_p = u64p(), u32p(), f32p()
+        _check(_ffi.lib().pqv_range_search(self._h, q.ctypes.data_as(f32p), nq, qlen, radius, nprobe, max_candidates,
+                                           max_results, metric, 1 if sqrt_out else 0, C.byref(lims_p), C.byref(rows_p),
+                                           C.byref(dist_p), nw.ctypes.data_as(u64p), nc.ctypes.data_as(u64p)))
+        try:
+            lims = np.ctypeslib.as_array(lims_p, shape=(nq + 1,)).copy()
+            total = int(lims[-1])
+            rows = (np.ctypeslib.as_array(rows_p, shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32))
+            dist = (np.ctypeslib.as_array(dist_p, shape=(total,)).copy() if total else np.zeros(0, dtype=np.float32))
+        finally:
+            _ffi.lib().pqv_range_free(lims_p, rows_p, dist_p)
+        return lims, rows, dist, nw, nc
+
     def topk_device(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0,
                     max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0):
         """Device-pointer form (ints from tensor.data_ptr()); asynchronous on `stream` -- a hipStream_t handle; 0 means the
@@ -567,6 +598,52 @@ class TopkBuilder:
         rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe)
         n = int(nf[0])
         return [SearchResult(r, d) for r, d in zip(rows[0, :n].tolist(), dist[0, :n].tolist())]
+
+
+class RangeBuilder:
+    """Range counterpart of TopkBuilder: every row within `radius` of the query, nearest first (ties by candidate
+    position).  radius and nprobe must be set; max_results (optional, > 0) keeps the first that many.  `source` is an
+    indexed Parquet path or an existing Searcher."""
+
+    def __init__(self, source, query, device=0):
+        import os
+        if isinstance(source, (str, bytes, os.PathLike)):
+            self._path, self._searcher = source, None
+        else:
+            self._path, self._searcher = None, source
+        self._device = device
+        self._query = query
+        self._radius = None
+        self._nprobe = None
+        self._max_results = 0
+
+    def radius(self, radius):
+        radius = float(radius)
+        if radius != radius:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "radius must not be NaN")
+        self._radius = radius
+        return self
+
+    def nprobe(self, nprobe):
+        if nprobe == 0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be > 0")
+        self._nprobe = nprobe
+        return self
+
+    def max_results(self, max_results):
+        self._max_results = int(max_results)
+        return self
+
+    def search(self):
+        if self._radius is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "radius must be set")
+        if self._nprobe is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
+        if self._searcher is None:
+            self._searcher = searcher_for_parquet(self._path, self._device)
+        _, rows, dist, _, _ = self._searcher.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
+                                                          max_results=self._max_results)
+        return [SearchResult(r, d) for r, d in zip(rows.tolist(), dist.tolist())]
 
 
 # ---------------------------------------------------------------------------------------

@@ -111,7 +111,7 @@ int use_device(int device) {
     if (!lazy && device < 64)
         std::call_once(warmed[device], [] {
             (void)pqv::touch_probe(nullptr); (void)pqv::touch_screen(nullptr); (void)pqv::touch_brute(nullptr); (void)pqv::touch_build(nullptr);
-            (void)pqv::touch_layout(nullptr); (void)pqv::touch_list(nullptr); (void)pqv::touch_kpp(nullptr);
+            (void)pqv::touch_layout(nullptr); (void)pqv::touch_list(nullptr); (void)pqv::touch_kpp(nullptr); (void)pqv::touch_range(nullptr);
             (void)hipStreamSynchronize(nullptr);
             // ... and the runtime's staging buffers for copies from / to pageable host memory are made by the first such copies
             void *d = nullptr;
@@ -315,7 +315,8 @@ constexpr int PQV_LANES = 4;
 struct Scratch {
     DevBuf s_probe_keys, s_probe_vals, s_probe, s_cand_base, s_ncand, s_part_keys, s_part_vals, s_queries, s_rows,
         s_dist, s_nfound, s_pair_u32, s_pairs, s_groups, s_quads, s_items, s_ticket, s_ticket2, s_cand_keys, s_cand_vals, s_cand_cnt, s_spilled,
-        s_seed_ub, s_qblk, s_gthr, s_tie, s_replay, s_qnorm, s_qmax, s_thr_hist, s_thr_bins, s_qi8, s_qn2i, s_qres, s_qresu, s_pair_lb, s_part_flags, s_qpad, s_cand_lb, s_pendv, s_work, s_nwork, s_out;
+        s_seed_ub, s_qblk, s_gthr, s_tie, s_replay, s_qnorm, s_qmax, s_thr_hist, s_thr_bins, s_qi8, s_qn2i, s_qres, s_qresu, s_pair_lb, s_part_flags, s_qpad, s_cand_lb, s_pendv, s_work, s_nwork, s_out,
+        s_hit_cnt, s_hit_keys, s_hit_vals, s_alt_keys, s_alt_vals, s_rsegs, s_rout_off, s_rout_rows, s_rout_dist;   // s_hit_* .. s_rout_*: pqv_range_search
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -3781,6 +3782,261 @@ extern "C" int pqv_topk(const pqv_searcher *s, const float *queries, uint32_t nq
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                         uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] { return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates); });
+}
+
+// ---- range search ----------------------------------------------------------------------------------------------------
+// Every candidate within `radius` of each query (pqv.h: pqv_range_search).  Per sub-batch of queries: the batched probe
+// (probe_rows_kernel or stream_kernel over the centroids, then merge_kernel PROBE; beyond the kernels' 1024-entry lists
+// find_closest_centroids per query through centroid_order_host), ONE stream_kernel STREAM_RANGE pass that appends every hit
+// to its query's segment, ONE synchronisation for the hit counts (the output is sized from them), then the segments sorted
+// by (d2, candidate position) and written out on the device (kernels_range.hip) and copied back.
+namespace {
+struct HostFree { void operator()(void *p) const { std::free(p); } };
+
+template <class T>
+int grow_host(std::unique_ptr<T, HostFree> &buf, uint64_t &cap, uint64_t need) {
+    if (need <= cap) return PQV_OK;
+    const uint64_t n = std::max<uint64_t>(need, cap + cap / 2);
+    void *p = std::realloc(buf.get(), static_cast<size_t>(n) * sizeof(T));
+    if (!p) return fail(PQV_ERR_OOM, "host allocation failed");
+    (void)buf.release();
+    buf.reset(static_cast<T *>(p));
+    cap = n;
+    return PQV_OK;
+}
+
+int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, float radius, uint32_t nprobe,
+               uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t *lims,
+               std::unique_ptr<uint32_t, HostFree> &rows, std::unique_ptr<float, HostFree> &dist, uint64_t *n_within,
+               uint64_t *n_candidates) {
+    using namespace pqv;
+    hipStream_t st = s->stream;
+    const uint32_t kc = s->n_clusters, np = std::min<uint32_t>(nprobe, kc);
+    const bool wide_probe = np > 1024;              // (merge_kernel's lists hold up to 1024 probed clusters)
+    const uint64_t max_pos = max_candidates ? max_candidates : ~0ull;
+    // a query's segment holds its capped candidates: at most the np longest lists, at most max_candidates
+    uint64_t bound = 0;
+    {
+        std::vector<uint64_t> len(kc);
+        for (uint32_t c = 0; c < kc; ++c) len[c] = s->h_list_off[c + 1] - s->h_list_off[c];
+        std::sort(len.begin(), len.end(), std::greater<uint64_t>());
+        for (uint32_t j = 0; j < np; ++j) bound += len[j];
+        if (max_candidates) bound = std::min(bound, max_candidates);
+    }
+    const uint64_t stride = std::max<uint64_t>(1, bound);
+    // sub-batches: the segments (12 B per entry) and the probe's scratch within ~1 GiB, at most 65535 queries (gridDim.z);
+    // a query whose segment alone is larger still runs, alone
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), nprobe, 1, metric);
+    const uint64_t per_query = stride * 12 + static_cast<uint64_t>(p1.n_part_probe) * std::max<uint32_t>(64, np) * 12 +
+                               static_cast<uint64_t>(np) * 12 + static_cast<uint64_t>(s->dim + s->sdim) * 4 + 32;
+    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>({nq, 65535ull, (1ull << 30) / per_query})));
+    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
+    if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(batch) * s->sdim * sizeof(float)));
+    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(batch) * np * sizeof(uint32_t)));
+    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(batch) * np * sizeof(uint64_t)));
+    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_hit_cnt.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_hit_keys.ensure(static_cast<size_t>(batch) * stride * sizeof(uint64_t)));
+    HIP_TRY(sc.s_hit_vals.ensure(static_cast<size_t>(batch) * stride * sizeof(uint32_t)));
+    HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
+    std::vector<uint32_t> h_cnt(batch), h_probe, order;
+    std::vector<uint64_t> h_ncand(batch), h_off(batch), h_base;
+    std::vector<RangeSeg> segs;
+    uint64_t cap_rows = 1, cap_dist = 1;      // entries the library buffers have room for
+    const uint64_t max_len = std::max<uint64_t>(1, s->max_list_len);
+    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
+        const uint32_t b = std::min<uint32_t>(batch, nq - q0);
+        uint32_t launches = 0;
+        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+        if (s->timing) {     // pqv_timing_read: the STREAM_RANGE pass as the "re-rank", probe .. write-out as the total
+            HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+            HIP_TRY(hipEventCreate(&e2)); HIP_TRY(hipEventCreate(&e3));
+            s->ev.push_back(e0); s->ev.push_back(e1); s->ev.push_back(e2); s->ev.push_back(e3);
+        }
+        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
+                               hipMemcpyHostToDevice, st));
+        if (e0) HIP_TRY(hipEventRecord(e0, st));
+        const float *d_q = sc.s_queries.as<float>(), *d_q_s = d_q;
+        if (s->sdim != s->dim) {
+            HIP_TRY(launch_pad_rows(d_q, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), st));
+            d_q_s = sc.s_qpad.as<float>();
+            ++launches;
+        }
+        if (!wide_probe) {
+            const TopkPlan p = plan_topk(s, b, nprobe, 1, metric);
+            HIP_TRY(sc.s_probe_keys.ensure(static_cast<size_t>(b) * p.n_part_probe * p.probe_kpart * sizeof(uint64_t)));
+            HIP_TRY(sc.s_probe_vals.ensure(static_cast<size_t>(b) * p.n_part_probe * p.probe_kpart * sizeof(uint32_t)));
+            if (p.probe_rows) {
+                ProbeRowsArgs pr{};
+                pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_q;
+                pr.nq = b; pr.kc = kc; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
+                pr.part_keys = sc.s_probe_keys.as<uint64_t>(); pr.part_vals = sc.s_probe_vals.as<uint32_t>();
+                HIP_TRY(launch_probe_rows(pr, st));
+            } else {
+                StreamArgs pa{};
+                pa.mat = s->d_centroids.as<float>();
+                pa.single_begin = 0; pa.single_end = kc;
+                pa.queries = d_q; pa.nq = b; pa.nprobe = 1; pa.dim = s->dim; pa.k = p.np;
+                pa.rows_per_block = 256; pa.blocks_per_list = p.probe_bpl;
+                pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;   // find_closest_centroids always uses index.rs:461
+                pa.part_keys = sc.s_probe_keys.as<uint64_t>(); pa.part_vals = sc.s_probe_vals.as<uint32_t>();
+                HIP_TRY(launch_stream(pa, STREAM_TOPK, st));
+            }
+            MergeArgs pm{};
+            pm.part_keys = sc.s_probe_keys.as<uint64_t>(); pm.part_vals = sc.s_probe_vals.as<uint32_t>();
+            pm.nq = b; pm.n_part = p.n_part_probe; pm.k_part = p.probe_kpart; pm.k = p.np;
+            pm.list_off = s->d_list_off.as<uint64_t>();
+            pm.probe = sc.s_probe.as<uint32_t>(); pm.cand_base = sc.s_cand_base.as<uint64_t>();
+            pm.n_cand = sc.s_ncand.as<uint64_t>(); pm.max_pos = max_pos;
+            pm.stats = s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
+            HIP_TRY(launch_merge_probe(pm, st));
+            launches += 2;
+        } else {
+            // find_closest_centroids without the kernels' list limit (as topk_unbounded): the order of every centroid per query
+            h_probe.resize(static_cast<size_t>(b) * np);
+            h_base.resize(static_cast<size_t>(b) * np);
+            for (uint32_t i = 0; i < b; ++i) {
+                if (int rc = centroid_order_host(s, sc, d_q + static_cast<uint64_t>(i) * s->dim, order)) return rc;
+                uint64_t total = 0;
+                for (uint32_t j = 0; j < np; ++j) {
+                    h_probe[static_cast<size_t>(i) * np + j] = order[j];
+                    h_base[static_cast<size_t>(i) * np + j] = total;
+                    total += s->h_list_off[order[j] + 1] - s->h_list_off[order[j]];
+                }
+                h_ncand[i] = total;
+                s->counters.candidate_rows += total;                              // index_exec.rs:289-299
+                s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(total, max_candidates) : total;
+            }
+            HIP_TRY(hipMemcpyAsync(sc.s_probe.p, h_probe.data(), h_probe.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(sc.s_cand_base.p, h_base.data(), h_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        }
+
+        // the hits: one pass over every (query, probed list), rows through d_mat / d_row_of (every layout)
+        HIP_TRY(hipMemsetAsync(sc.s_hit_cnt.p, 0, static_cast<size_t>(b) * sizeof(uint32_t), st));
+        StreamArgs ra{};
+        ra.mat = s->d_mat; ra.row_of = s->d_row_of; ra.list_off = s->d_list_off.as<uint64_t>();
+        ra.probe = sc.s_probe.as<uint32_t>(); ra.cand_base = sc.s_cand_base.as<uint64_t>();
+        ra.queries = d_q_s; ra.nq = b; ra.nprobe = np; ra.dim = s->sdim; ra.k = 1;
+        {   // (the split of stream_kernel's top-k form: enough blocks to fill the chip, lists cut into 256-row multiples)
+            const uint64_t pairs = std::max<uint64_t>(1, static_cast<uint64_t>(b) * np);
+            const uint64_t max_bpl = (max_len + 255) / 256;
+            const uint64_t bpl = std::max<uint64_t>(1, std::min<uint64_t>((8192 + pairs - 1) / pairs, max_bpl));
+            const uint64_t rpb = ((max_len + bpl - 1) / bpl + 255) / 256 * 256;
+            ra.rows_per_block = static_cast<uint32_t>(rpb);
+            ra.blocks_per_list = static_cast<uint32_t>((max_len + rpb - 1) / rpb);
+        }
+        ra.max_pos = max_pos; ra.metric = metric;
+        ra.radius = radius; ra.sqrt_out = sqrt_out ? 1 : 0;
+        ra.hit_cnt = sc.s_hit_cnt.as<uint32_t>(); ra.hit_keys = sc.s_hit_keys.as<uint64_t>(); ra.hit_vals = sc.s_hit_vals.as<uint32_t>();
+        ra.seg_stride = stride;
+        if (e1) HIP_TRY(hipEventRecord(e1, st));
+        for (uint32_t j0 = 0; j0 < np; j0 += 32768) {                    // gridDim.y <= 65535
+            ra.j0 = j0; ra.nj = std::min<uint32_t>(32768, np - j0);
+            HIP_TRY(launch_stream(ra, STREAM_RANGE, st));
+            ++launches;
+        }
+        if (e2) HIP_TRY(hipEventRecord(e2, st));
+        HIP_TRY(hipMemcpyAsync(h_cnt.data(), sc.s_hit_cnt.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (!wide_probe)
+            HIP_TRY(hipMemcpyAsync(h_ncand.data(), sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+
+        // output offsets from the counts; segments longer than one block's sort go to the multi-pass path
+        segs.clear();
+        uint64_t tot = 0, alt = 0;
+        uint32_t max_n = 0;
+        bool any_small = false;
+        for (uint32_t i = 0; i < b; ++i) {
+            const uint32_t n = h_cnt[i];
+            if (n > stride) return fail(PQV_ERR_HIP, "range search: a segment overflowed");     // (cannot happen: n <= capped candidates)
+            const uint64_t kept = max_results ? std::min<uint64_t>(n, max_results) : n;
+            h_off[i] = tot;
+            tot += kept;
+            lims[q0 + i + 1] = lims[q0 + i] + kept;
+            if (n_within) n_within[q0 + i] = n;
+            if (n_candidates) n_candidates[q0 + i] = h_ncand[i];
+            if (n > RANGE_SMALL) { segs.push_back(RangeSeg{i, n, alt}); alt += n; max_n = std::max(max_n, n); }
+            else if (n) any_small = true;
+        }
+        if (int rc = grow_host(rows, cap_rows, lims[q0 + b])) return rc;
+        if (int rc = grow_host(dist, cap_dist, lims[q0 + b])) return rc;
+        if (tot) {
+            HIP_TRY(sc.s_rout_rows.ensure(tot * sizeof(uint32_t)));
+            HIP_TRY(sc.s_rout_dist.ensure(tot * sizeof(float)));
+            HIP_TRY(hipMemcpyAsync(sc.s_rout_off.p, h_off.data(), static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            RangeSortArgs sa{};
+            sa.nq = b; sa.hit_cnt = sc.s_hit_cnt.as<uint32_t>();
+            sa.keys = sc.s_hit_keys.as<uint64_t>(); sa.vals = sc.s_hit_vals.as<uint32_t>(); sa.seg_stride = stride;
+            sa.max_results = max_results; sa.out_off = sc.s_rout_off.as<uint64_t>();
+            sa.ids = s->d_final_ids; sa.sqrt_out = sqrt_out ? 1 : 0;
+            sa.out_rows = sc.s_rout_rows.as<uint32_t>(); sa.out_dist = sc.s_rout_dist.as<float>();
+            if (any_small) { HIP_TRY(launch_range_sort_small(sa, st)); ++launches; }
+            if (!segs.empty()) {
+                HIP_TRY(sc.s_alt_keys.ensure(alt * sizeof(uint64_t)));
+                HIP_TRY(sc.s_alt_vals.ensure(alt * sizeof(uint32_t)));
+                HIP_TRY(sc.s_rsegs.ensure(segs.size() * sizeof(RangeSeg)));
+                HIP_TRY(hipMemcpyAsync(sc.s_rsegs.p, segs.data(), segs.size() * sizeof(RangeSeg), hipMemcpyHostToDevice, st));
+                sa.alt_keys = sc.s_alt_keys.as<uint64_t>(); sa.alt_vals = sc.s_alt_vals.as<uint32_t>();
+                sa.segs = sc.s_rsegs.as<RangeSeg>(); sa.n_segs = static_cast<uint32_t>(segs.size());
+                uint32_t nl = 0;
+                HIP_TRY(launch_range_sort_large(sa, max_n, &nl, st));
+                launches += nl;
+            }
+            if (e3) HIP_TRY(hipEventRecord(e3, st));
+            HIP_TRY(hipMemcpyAsync(rows.get() + lims[q0], sc.s_rout_rows.p, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dist.get() + lims[q0], sc.s_rout_dist.p, tot * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        } else if (e3) {
+            HIP_TRY(hipEventRecord(e3, st));
+        }
+        s->counters.queries += b;
+        s->counters.kernel_launches += launches;
+    }
+    return PQV_OK;
+}
+}  // namespace
+
+static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len, float radius,
+                                 uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
+                                 uint64_t **lims_out, uint32_t **rows_out, float **dist_out, uint64_t *n_within,
+                                 uint64_t *n_candidates) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (nprobe == 0) return fail(PQV_ERR_INVALID, "nprobe must be > 0");                          // search.rs:72
+    if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ) return fail(PQV_ERR_INVALID, "unknown metric");
+    if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
+    if (query_len != s->dim)                                                                      // search.rs:91-98
+        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) +
+                                         ", got " + std::to_string(query_len));
+    if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
+    if (nq && !queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
+    *lims_out = nullptr; *rows_out = nullptr; *dist_out = nullptr;
+    std::unique_ptr<uint64_t, HostFree> lims(static_cast<uint64_t *>(std::malloc((static_cast<size_t>(nq) + 1) * sizeof(uint64_t))));
+    std::unique_ptr<uint32_t, HostFree> rows(static_cast<uint32_t *>(std::malloc(sizeof(uint32_t))));
+    std::unique_ptr<float, HostFree> dist(static_cast<float *>(std::malloc(sizeof(float))));
+    if (!lims || !rows || !dist) return fail(PQV_ERR_OOM, "host allocation failed");
+    lims.get()[0] = 0;
+    if (nq) {
+        if (int rc = use_device(s->device)) return rc;
+        std::lock_guard<std::mutex> lock(s->mu);
+        Scratch *lane = nullptr;
+        if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
+        LaneGuard lane_guard{*lane, s->stream};
+        if (int rc = range_body(s, *lane, queries, nq, radius, nprobe, max_candidates, max_results, metric, sqrt_out, lims.get(), rows,
+                                dist, n_within, n_candidates))
+            return rc;
+        if (int rc = lane_release(*lane, s->stream)) return rc;
+    }
+    *lims_out = lims.release(); *rows_out = rows.release(); *dist_out = dist.release();
+    return PQV_OK;
+}
+extern "C" int pqv_range_search(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len, float radius,
+                                uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
+                                uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
+    return guard([&] { return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric,
+                                                    sqrt_out, lims, row_idx, dist, n_within, n_candidates); });
+}
+extern "C" void pqv_range_free(uint64_t *lims, uint32_t *row_idx, float *dist) {
+    std::free(lims); std::free(row_idx); std::free(dist);
 }
 
 static int pqv_searcher_set_option_impl(pqv_searcher *s, const char *name, int64_t value) {

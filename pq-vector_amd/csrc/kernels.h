@@ -14,6 +14,7 @@ enum StreamMode : int {
     STREAM_TOPK   = 0,  // fold into per-wave top-k lists
     STREAM_DIST   = 1,  // out_f32[pos] = d2
     STREAM_MINUPD = 2,  // out_f32[pos] = min(out_f32[pos], d2)   (k-means++ round)
+    STREAM_RANGE  = 3,  // out <= radius: append (d2, pos) key + storage row to the query's hit segment (range search)
 };
 
 struct StreamArgs {
@@ -48,6 +49,17 @@ struct StreamArgs {
     // optional: zero_u32[0 .. zero_n) = 0 (scratch of the kernels that follow in the stream)
     uint32_t       *zero_u32;
     uint32_t        zero_n;
+    // RANGE: probe ranks [j0, j0 + nj) of every query (gridDim.y = nj; probe / cand_base keep the row stride nprobe).  A
+    // candidate is a hit iff out = (sqrt_out ? sqrt(d2) : d2) <= radius; each wave appends its hits to query q's segment
+    // hit_keys / hit_vals [q * seg_stride + slot) (slot from one atomicAdd per wave on hit_cnt[q]).  seg_stride must be at
+    // least the query's capped candidate count, so a segment cannot overflow.
+    uint32_t        j0, nj;
+    float           radius;
+    int             sqrt_out;
+    uint32_t       *hit_cnt;     // [nq], zeroed by the caller
+    uint64_t       *hit_keys;    // (d2 bits << 32) | candidate position
+    uint32_t       *hit_vals;    // storage row
+    uint64_t        seg_stride;
 };
 
 // Streaming exact-order squared-L2 pass (the re-rank kernel).  Returns hipError_t.
@@ -647,6 +659,37 @@ hipError_t launch_lloyd_update(const float *rows, uint32_t dim, const uint32_t *
                                const uint64_t *list_off, uint32_t k, float *centroids,
                                hipStream_t s);
 
+// ---- range search: per-query segments of hits, sorted by (d2, position) and written out (kernels_range.hip) ----------
+// Segments of up to RANGE_SMALL hits are sorted by one block in LDS and written out by it; longer ones are sorted in
+// RANGE_SMALL-key tiles, merged pairwise (merge path) between the segment buffer and a compact second buffer, and written out.
+constexpr uint32_t RANGE_SMALL = 4096;
+struct RangeSeg {                 // a segment of the long-segment path
+    uint32_t q;                   // query of the sub-batch
+    uint32_t n;                   // hits
+    uint64_t alt_off;             // its offset in the second buffer
+};
+struct RangeSortArgs {
+    uint32_t        nq;
+    const uint32_t *hit_cnt;      // [nq]
+    uint64_t       *keys;         // [nq * seg_stride] (StreamArgs::hit_keys)
+    uint32_t       *vals;
+    uint64_t        seg_stride;
+    uint64_t       *alt_keys;     // second buffer of the long segments, RangeSeg::alt_off
+    uint32_t       *alt_vals;
+    const RangeSeg *segs;         // [n_segs] long segments
+    uint32_t        n_segs;
+    uint64_t        max_results;  // 0: every hit
+    const uint64_t *out_off;      // [nq] first output entry of each query
+    const uint32_t *ids;          // storage row -> file row id (nullptr => identity)
+    int             sqrt_out;
+    uint32_t       *out_rows;
+    float          *out_dist;
+};
+// segments with 0 < n <= RANGE_SMALL: sort and write out (one block per query)
+hipError_t launch_range_sort_small(const RangeSortArgs &a, hipStream_t s);
+// long segments: sort, merge and write out; max_n = the longest of them (several launches)
+hipError_t launch_range_sort_large(const RangeSortArgs &a, uint32_t max_n, uint32_t *launches, hipStream_t s);
+
 // number of per-wave partial lists per (query, probed list)
 inline uint32_t waves_per_block() { return 4; }
 
@@ -662,5 +705,6 @@ hipError_t touch_build(hipStream_t s);
 hipError_t touch_layout(hipStream_t s);
 hipError_t touch_list(hipStream_t s);
 hipError_t touch_kpp(hipStream_t s);
+hipError_t touch_range(hipStream_t s);
 
 }  // namespace pqv

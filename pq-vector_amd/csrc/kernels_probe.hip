@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void stream_kernel(const StreamArgs a) {
     float *lds = lds_all + wave * (LROWS * 64);
 #define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
 
-    const uint32_t q = blockIdx.z, j = blockIdx.y;
+    const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
     uint64_t lbeg, lend, cbase;
     if (a.probe) {
         const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
@@ -153,6 +153,22 @@ __global__ __launch_bounds__(256) void stream_kernel(const StreamArgs a) {
                     if (a.mirror_t) a.mirror_t[(pos % a.mirror_chunk) * a.mirror_stride + pos / a.mirror_chunk] = sum;
                 }
             }
+        } else if constexpr (MODE == STREAM_RANGE) {
+            // the wave's hits go to the query's segment in one block: ballot, rank from mbcnt, one atomicAdd per wave
+            const float outv = a.sqrt_out ? sqrt_f32_ieee(sum) : sum;
+            const bool hit = valid && outv <= a.radius;                // (a NaN distance never compares true)
+            const uint64_t m = __ballot(hit);
+            if (m) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(a.hit_cnt + q, (uint32_t)__popcll(m));
+                base = (uint32_t)__shfl((int)base, 0, 64);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                if (hit) {
+                    const uint64_t o = (uint64_t)q * a.seg_stride + base + rank;
+                    a.hit_keys[o] = ((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos;
+                    a.hit_vals[o] = my_srow;
+                }
+            }
         } else {
             if (valid) a.out_f32[pos] = sum;
         }
@@ -195,8 +211,24 @@ static hipError_t launch_stream_topk_s(const StreamArgs &a, hipStream_t s) {
     return launch_stream_t<32, S, STREAM_TOPK, false, true>(a, s);
 }
 
+template <int CG, bool SEQ, bool ALIGNED>
+static hipError_t launch_stream_range_t(const StreamArgs &a, hipStream_t s) {
+    dim3 grid(a.blocks_per_list, a.nj, a.nq);
+    hipLaunchKernelGGL((stream_kernel<CG, 1, STREAM_RANGE, SEQ, ALIGNED>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_stream(const StreamArgs &a, StreamMode mode, hipStream_t s) {
     if (a.nq == 0 || a.blocks_per_list == 0) return hipSuccess;
+    if (mode == STREAM_RANGE) {          // (the chunk choice of STREAM_TOPK: the chain order does not depend on it)
+        if (a.nj == 0 || !a.probe) return a.nj == 0 ? hipSuccess : hipErrorInvalidValue;
+        const bool aligned = (a.dim % 4) == 0;
+        const uint32_t G = a.dim / 4;
+        if (a.metric == 1) return aligned ? launch_stream_range_t<16, true, true>(a, s) : launch_stream_range_t<16, true, false>(a, s);
+        if (!aligned) return launch_stream_range_t<32, false, false>(a, s);
+        if (G >= 64 && G % 64 == 0) return launch_stream_range_t<64, false, true>(a, s);
+        return launch_stream_range_t<32, false, true>(a, s);
+    }
     if (mode == STREAM_TOPK) {
         if (a.k <= 64) return launch_stream_topk_s<1>(a, s);
         if (a.k <= 256) return launch_stream_topk_s<4>(a, s);
