@@ -367,6 +367,47 @@ impl Drop for Searcher<'_> {
     }
 }
 
+/// A table of indexed files on one GPU (`src/df_vector/index_exec.rs:85-164`, one heap over the files' candidates as
+/// `exec.rs:264-267`): file `f`'s rows are corpus rows `row_base[f] ..` (its index' row ids are local to the file).  It
+/// derefs to a [`Searcher`] on which `nprobe` counts per file and rows come back as corpus rows; [`TableSearcher::split_row`]
+/// maps one back to (file, row in that file).
+pub struct TableSearcher<'c> {
+    inner: Searcher<'c>,
+    row_base: Vec<u64>,
+    n_rows: Vec<u64>,
+}
+
+impl<'c> TableSearcher<'c> {
+    pub fn new(indexes: &[&Index], row_base: &[u64], corpus: &'c mut Corpus) -> Result<Self> {
+        if indexes.len() != row_base.len() {
+            return Err("row_base needs one entry per indexed file".into());
+        }
+        let mut ptrs: Vec<*const sys::PqvIndex> = indexes.iter().map(|i| i.raw as *const sys::PqvIndex).collect();
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            sys::pqv_table_searcher_create(ptrs.as_mut_ptr(), ptrs.len() as u32, row_base.as_ptr(), corpus.raw,
+                                           sys::PQV_LAYOUT_IVF_ORDERED, &mut raw)
+        })?;
+        let n_rows = indexes.iter().map(|i| unsafe { sys::pqv_index_n_rows(i.raw) }).collect();
+        Ok(Self { inner: Searcher { raw, _corpus: std::marker::PhantomData }, row_base: row_base.to_vec(), n_rows })
+    }
+
+    /// A corpus row of this table -> (file, row in that file); `None` outside every file.
+    pub fn split_row(&self, row: u32) -> Option<(usize, u32)> {
+        let r = row as u64;
+        let f = self.row_base.partition_point(|&b| b <= r).checked_sub(1)?;
+        let local = r - self.row_base[f];
+        if row == u32::MAX || local >= self.n_rows[f] { None } else { Some((f, local as u32)) }
+    }
+}
+
+impl<'c> std::ops::Deref for TableSearcher<'c> {
+    type Target = Searcher<'c>;
+    fn deref(&self) -> &Searcher<'c> {
+        &self.inner
+    }
+}
+
 /// `TopkBuilder` (`src/ivf/search.rs:49-81`) over a cached [`Searcher`] instead of a path.
 pub struct TopkBuilder<'a, 'c> {
     searcher: &'a Searcher<'c>,

@@ -197,6 +197,18 @@ void pqv_index_free(pqv_index *index);
 int  pqv_searcher_create(const pqv_index *index, pqv_corpus *corpus, uint32_t flags,
                          pqv_searcher **out);
 void pqv_searcher_free(pqv_searcher *searcher);
+/* A table of indexed files on one GPU (src/df_vector/index_exec.rs:85-164 on one device): file f's rows are corpus rows
+ * [row_base[f], row_base[f] + pqv_index_n_rows(indexes[f])), its index' row ids are local to the file.  Returns an ordinary
+ * pqv_searcher on which nprobe means "per file": a query probes the first min(nprobe, kc_f) centroids of each file's
+ * find_closest_centroids, reported as global list ids cluster_base[f] + c, file after file (P = the sum of those counts).  The
+ * candidate sequence is file 0's candidate_rows, then file 1's, ... with rows shifted by row_base; top-k orders by (distance,
+ * position in that sequence), as per-file searches merged with pqv_merge_topk.  Row ranges must increase without overlapping
+ * and lie inside the corpus; all dims are equal.  max_candidates > 0 returns PQV_ERR_UNSUPPORTED on a table (per-file caps:
+ * pqv_candidate_cursor over per-file searchers, then pqv_merge_topk); P > 1024: as min(nprobe, n_clusters) > 1024 today. */
+int pqv_table_searcher_create(const pqv_index *const *indexes, uint32_t n_files, const uint64_t *row_base,
+                              pqv_corpus *corpus, uint32_t flags, pqv_searcher **out);
+/* 1 for ordinary searchers; row_base / cluster_base (each [n_files], may be NULL) for tables. */
+int pqv_searcher_files(const pqv_searcher *searcher, uint32_t *n_files, uint64_t *row_base, uint32_t *cluster_base);
 
 /* Tunables of one searcher (all optional; the defaults are the measured dispatch rules of DESIGN.md 5 / DESIGN_HISTORY.md 5.1c-f).
  * The reference has no such knobs -- its topk() is one fixed loop (src/ivf/search.rs:112-127) -- so nothing here

@@ -105,6 +105,8 @@ SIGNATURES = {
     "pqv_index_free": (None, [vp]),
     "pqv_searcher_create": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(vp)]),
     "pqv_searcher_free": (None, [vp]),
+    "pqv_table_searcher_create": (C.c_int, [C.POINTER(vp), C.c_uint32, u64p, vp, C.c_uint32, C.POINTER(vp)]),
+    "pqv_searcher_files": (C.c_int, [vp, u32p, u64p, u32p]),
     "pqv_probe": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, u32p, u32p]),
     "pqv_candidate_rows": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, C.POINTER(u32p), u64p]),
     "pqv_rows_free": (None, [u32p]),

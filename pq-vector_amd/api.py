@@ -63,7 +63,14 @@ class Corpus:
     def create(cls, capacity_rows, dim, device=0):
         h = vp()
         _check(_ffi.lib().pqv_corpus_create(device, capacity_rows, dim, C.byref(h)))
-        return cls(h)
+        c = cls(h)
+        c._capacity = int(capacity_rows)
+        return c
+
+    @property
+    def capacity(self):
+        """Rows the corpus has room for (Corpus.create's capacity_rows; else its row count)."""
+        return getattr(self, "_capacity", None) or self.rows
 
     def append(self, rows):
         rows = np.asarray(rows)
@@ -644,6 +651,197 @@ class RangeBuilder:
         _, rows, dist, _, _ = self._searcher.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
                                                           max_results=self._max_results)
         return [SearchResult(r, d) for r, d in zip(rows.tolist(), dist.tolist())]
+
+
+# ---------------------------------------------------------------------------------------
+# A table of indexed files on one GPU (pqv.h: pqv_table_searcher_create; src/df_vector/index_exec.rs:85-164, exec.rs:264-267)
+@dataclass
+class TableSearchResult:
+    """One row of the reference's index scan over a table: the file it came from, its row id in that file, the distance."""
+    path: str
+    row_idx: int
+    distance: float
+
+
+def _table_args(indexes, corpus, row_base):
+    """Host-side checks of a table (the library repeats them): returned as (indexes, row_base u64 array)."""
+    indexes = list(indexes)
+    if not indexes:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "a table needs at least one indexed file")
+    if corpus is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "indexes/row_base/corpus must not be NULL")
+    rb = np.ascontiguousarray(row_base, dtype=np.uint64).reshape(-1)
+    if rb.size != len(indexes):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"row_base has {rb.size} entries for {len(indexes)} files")
+    dim0, end = indexes[0].dim, 0
+    for f, ix in enumerate(indexes):
+        if ix.dim != dim0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"index dimension {ix.dim} of file {f} does not match dimension {dim0} of file 0")
+        if ix.dim != corpus.dim:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"index dimension {ix.dim} of file {f} does not match corpus dimension {corpus.dim}")
+        b, n = int(rb[f]), ix.n_rows
+        if f > 0 and b < end:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"row range of file {f} starts at {b}, inside the rows of the files before it "
+                                                 "(ranges must be increasing and disjoint)")
+        if b + n > corpus.rows:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"row range [{b}, {b + n}) of file {f} lies outside the corpus of {corpus.rows} rows")
+        end = b + n
+    if end >= 0xFFFFFFFF:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "a table's rows must stay below 2^32 - 1 (0xFFFFFFFF marks an empty slot)")
+    return indexes, rb
+
+
+class TableSearcher(Searcher):
+    """Several indexed files searched as ONE table on one GPU: file f's rows are corpus rows [row_base[f], row_base[f] + its
+    rows).  nprobe counts per file; probe() returns the P = sum_f min(nprobe, kc_f) global list ids, file after file; rows
+    come back as corpus rows (split_rows maps them to (file, local row)).  max_candidates > 0 is not supported: cap per file
+    with CandidateCursor over per-file Searchers and merge_topk."""
+
+    def __init__(self, indexes, corpus, row_base, flags=_ffi.PQV_LAYOUT_IVF_ORDERED):
+        indexes, rb = _table_args(indexes, corpus, row_base)
+        arr = (vp * len(indexes))(*[ix._h for ix in indexes])
+        h = vp()
+        _check(_ffi.lib().pqv_table_searcher_create(arr, len(indexes), rb.ctypes.data_as(u64p), corpus._h, flags, C.byref(h)))
+        self._h = h
+        self._corpus = corpus
+        self.dim = indexes[0].dim
+        self.n_clusters = sum(ix.n_clusters for ix in indexes)
+        self.n_files = len(indexes)
+        self.row_base = rb.copy()
+        self.n_rows = np.array([ix.n_rows for ix in indexes], dtype=np.uint64)
+        self.cluster_base = np.concatenate([[0], np.cumsum([ix.n_clusters for ix in indexes])]).astype(np.uint32)
+
+    def probe_count(self, nprobe):
+        """P: the lists one query probes (the sum over the files of min(nprobe, kc_f))."""
+        return int(np.minimum(np.diff(self.cluster_base.astype(np.int64)), int(nprobe)).sum())
+
+    def probe(self, query, nprobe):
+        q = _f32(query).reshape(-1)
+        out = np.zeros(max(1, self.probe_count(nprobe)), dtype=np.uint32)
+        n = C.c_uint32(0)
+        _check(_ffi.lib().pqv_probe(self._h, q.ctypes.data_as(f32p), q.size, nprobe,
+                                    out.ctypes.data_as(u32p), C.byref(n)))
+        return out[:n.value].copy()
+
+    def split_rows(self, rows):
+        """Corpus rows -> (file, local row) arrays (0xFFFFFFFF, an empty slot, maps to file -1)."""
+        return split_table_rows(rows, self.row_base, self.n_rows)
+
+
+def split_table_rows(rows, row_base, n_rows=None):
+    """Corpus rows of a table -> (file index int64, row in that file u32); rows outside every file (and 0xFFFFFFFF) give file
+    -1.  row_base: increasing first rows of the files; n_rows: their row counts (default: up to the next file's base)."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    rb = np.asarray(row_base, dtype=np.uint64).reshape(-1)
+    f = np.searchsorted(rb, rows, side="right").astype(np.int64) - 1
+    fi = np.clip(f, 0, max(0, rb.size - 1))
+    local = rows - rb[fi] if rb.size else rows
+    ok = (f >= 0) & (rows != 0xFFFFFFFF)
+    if n_rows is not None:
+        ok &= local < np.asarray(n_rows, dtype=np.uint64).reshape(-1)[fi]
+    return np.where(ok, f, -1), np.where(ok, local, 0xFFFFFFFF).astype(np.uint32)
+
+
+_TABLE_SEARCHERS = {}
+
+
+def searcher_for_parquet_files(paths, device=0):
+    """A TableSearcher over indexed Parquet files: every file's index blob and embedding column, the columns loaded one after
+    the other into ONE resident corpus.  Cached per (files, sizes, mtimes, device) as searcher_for_parquet is."""
+    import os
+    from . import parquet_io
+    if isinstance(paths, (str, bytes, os.PathLike)):
+        paths = [paths]
+    paths = list(paths)
+    if not paths:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "a table needs at least one indexed file")
+    key = []
+    for p in paths:
+        st = os.stat(p)
+        real = _REALPATHS.get(p)
+        if real is None:
+            real = _REALPATHS.setdefault(p, os.path.realpath(p))
+        key.append((real, st.st_size, st.st_mtime_ns))
+    key = (tuple(key), device)
+    hit = _TABLE_SEARCHERS.get(key)
+    if hit is None:
+        import pyarrow.parquet as pq
+        parts = [parquet_io.read_index_from_parquet(p) for p in paths]
+        indexes = [ix for ix, _ in parts]
+        dim0 = indexes[0].dim
+        for f, ix in enumerate(indexes):
+            if ix.dim != dim0:
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"index dimension {ix.dim} of file {f} does not match dimension {dim0} of file 0")
+        counts = [pq.ParquetFile(p).metadata.num_rows for p in paths]
+        row_base = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint64)
+        total = int(sum(counts))
+        if total >= 0xFFFFFFFF:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "a table's rows must stay below 2^32 - 1 (0xFFFFFFFF marks an empty slot)")
+        corpus = Corpus.create(total, dim0, device)
+        try:
+            for p, (_, column), b in zip(paths, parts, row_base):
+                parquet_io.load_embedding_column(p, column, device, into=corpus, row_offset=int(b))
+            corpus.finish(total)
+            hit = TableSearcher(indexes, corpus, row_base, _ffi.PQV_LAYOUT_IVF_ORDERED | _ffi.PQV_RELEASE_IF_COPIED)
+        except Exception:
+            corpus.close()
+            raise
+        hit.paths = [str(p) for p in paths]
+        _TABLE_SEARCHERS.clear()
+        _TABLE_SEARCHERS[key] = hit
+    return hit
+
+
+def _table_paths(paths):
+    import os
+    if isinstance(paths, (str, bytes, os.PathLike)):
+        paths = [paths]
+    paths = list(paths)
+    if not paths:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "a table needs at least one indexed file")
+    return paths
+
+
+def _table_results(searcher, paths, rows, dist):
+    f, local = searcher.split_rows(rows)
+    return [TableSearchResult(str(paths[int(i)]), int(r), float(d)) for i, r, d in zip(f.tolist(), local.tolist(), dist.tolist())]
+
+
+class TableTopkBuilder(TopkBuilder):
+    """TopkBuilder over a table of indexed Parquet files (searched as one TableSearcher; nprobe per file).  search() returns
+    [TableSearchResult(path, row_idx, distance)] -- the (path, row id, distance) columns of the reference's index scan."""
+
+    def __init__(self, paths, query, device=0):
+        self._paths = _table_paths(paths)
+        super().__init__(None, query, device)
+
+    def search(self):
+        if self._k is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "k must be set")
+        if self._nprobe is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
+        s = searcher_for_parquet_files(self._paths, self._device)
+        rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe)
+        n = int(nf[0])
+        return _table_results(s, self._paths, rows[0, :n], dist[0, :n])
+
+
+class TableRangeBuilder(RangeBuilder):
+    """RangeBuilder over a table of indexed Parquet files; search() returns [TableSearchResult], nearest first."""
+
+    def __init__(self, paths, query, device=0):
+        self._paths = _table_paths(paths)
+        super().__init__(None, query, device)
+
+    def search(self):
+        if self._radius is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "radius must be set")
+        if self._nprobe is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
+        s = searcher_for_parquet_files(self._paths, self._device)
+        _, rows, dist, _, _ = s.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
+                                             max_results=self._max_results)
+        return _table_results(s, self._paths, rows, dist)
 
 
 # ---------------------------------------------------------------------------------------

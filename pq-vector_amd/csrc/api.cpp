@@ -430,6 +430,13 @@ struct pqv_searcher {
                                            // against 2.1; DESIGN 5.4d has the counters); 0 (default) = the wide-quad instance
     };
     mutable Opts opt;
+    // table searchers (pqv_table_searcher_create): n_files > 0, the index is the files' indexes concatenated -- file f owns the
+    // global centroids [seg_off[f], seg_off[f + 1]) and the corpus rows [row_base[f], row_base[f] + its rows); nprobe counts per file
+    uint32_t n_files = 0;                  // 0: an ordinary searcher
+    std::vector<uint32_t> seg_off;         // [n_files + 1]
+    std::vector<uint64_t> row_base;        // [n_files]
+    uint32_t seg_max_kc = 0;               // largest file centroid count
+    DevBuf d_seg_off, d_seg_off64;         // seg_off on the device: u32 (merge_probe_seg_kernel), u64 (the per-file stream_kernel probe)
     mutable pqv_counters_t counters{};
     // timing
     mutable bool timing = false;
@@ -2783,6 +2790,95 @@ extern "C" int pqv_searcher_create(const pqv_index *index, pqv_corpus *corpus, u
     return guard([&] { return pqv_searcher_create_impl(index, corpus, flags, out); });
 }
 
+// A table of indexed files (pqv.h: pqv_table_searcher_create): the files' indexes concatenated into ONE index -- centroid tables
+// and inverted lists appended file after file, each file's rows shifted by its row_base -- and an ordinary searcher over it (the
+// IVF-ordered layout, operand images and norms exactly as for one index); the per-file centroid segments make the probe count
+// nprobe per file.
+static int pqv_table_searcher_create_impl(const pqv_index *const *indexes, uint32_t n_files, const uint64_t *row_base,
+                                          pqv_corpus *corpus, uint32_t flags, pqv_searcher **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!indexes || !row_base || !corpus) return fail(PQV_ERR_INVALID, "indexes/row_base/corpus must not be NULL");
+    if (n_files == 0) return fail(PQV_ERR_INVALID, "a table needs at least one indexed file");
+    uint64_t kc_total = 0, rows_end = 0;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        const pqv_index *ix = indexes[f];
+        const std::string fs = std::to_string(f);
+        if (!ix) return fail(PQV_ERR_INVALID, "index of file " + fs + " must not be NULL");
+        if (ix->dim != indexes[0]->dim)
+            return fail(PQV_ERR_INVALID, "index dimension " + std::to_string(ix->dim) + " of file " + fs +
+                                             " does not match dimension " + std::to_string(indexes[0]->dim) + " of file 0");
+        if (ix->dim != corpus->dim)
+            return fail(PQV_ERR_INVALID, "index dimension " + std::to_string(ix->dim) + " of file " + fs +
+                                             " does not match corpus dimension " + std::to_string(corpus->dim));
+        const uint64_t n_f = ix->n_rows();
+        if (f > 0 && row_base[f] < rows_end)
+            return fail(PQV_ERR_INVALID, "row range of file " + fs + " starts at " + std::to_string(row_base[f]) +
+                                             ", inside the rows of the files before it (ranges must be increasing and disjoint)");
+        if (row_base[f] > corpus->n || n_f > corpus->n - row_base[f])
+            return fail(PQV_ERR_INVALID, "row range [" + std::to_string(row_base[f]) + ", " + std::to_string(row_base[f] + n_f) +
+                                             ") of file " + fs + " lies outside the corpus of " + std::to_string(corpus->n) + " rows");
+        rows_end = row_base[f] + n_f;
+        kc_total += ix->n_clusters;
+    }
+    if (rows_end >= 0xFFFFFFFFull) return fail(PQV_ERR_INVALID, "a table's rows must stay below 2^32 - 1 (0xFFFFFFFF marks an empty slot)");
+    if (kc_total > 0xFFFFFFFFull) return fail(PQV_ERR_INVALID, "a table's clusters must stay below 2^32");
+    pqv_index all;
+    all.dim = indexes[0]->dim;
+    all.n_clusters = static_cast<uint32_t>(kc_total);
+    std::vector<uint32_t> seg_off(n_files + 1, 0);
+    uint32_t seg_max = 0;
+    all.list_off.reserve(kc_total + 1);
+    all.list_off.push_back(0);
+    for (uint32_t f = 0; f < n_files; ++f) {
+        const pqv_index *ix = indexes[f];
+        const std::vector<uint32_t> *rv = ix->rows->get();
+        if (!rv) return PQV_ERR_HIP;
+        const uint64_t n_f = ix->n_rows(), o = all.list_off.back();
+        all.centroids.insert(all.centroids.end(), ix->centroids.begin(), ix->centroids.end());
+        for (uint32_t c = 0; c < ix->n_clusters; ++c) all.list_off.push_back(o + ix->list_off[c + 1]);
+        const uint32_t rb = static_cast<uint32_t>(row_base[f]);
+        for (uint32_t r : *rv) {
+            if (r >= n_f) return fail(PQV_ERR_INVALID, "index row id out of range for file " + std::to_string(f));
+            all.list_rows.push_back(rb + r);
+        }
+        seg_off[f + 1] = seg_off[f] + ix->n_clusters;
+        seg_max = std::max(seg_max, ix->n_clusters);
+    }
+    all.rows->n = all.list_rows.size();
+    pqv_searcher *s = nullptr;
+    if (int rc = pqv_searcher_create_impl(&all, corpus, flags, &s)) return rc;
+    s->n_files = n_files;
+    s->seg_off = std::move(seg_off);
+    s->row_base.assign(row_base, row_base + n_files);
+    s->seg_max_kc = seg_max;
+    const std::vector<uint64_t> seg_off64(s->seg_off.begin(), s->seg_off.end());
+    hipError_t e = s->d_seg_off.alloc(s->seg_off.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = s->d_seg_off64.alloc(seg_off64.size() * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemcpy(s->d_seg_off.p, s->seg_off.data(), s->seg_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s->d_seg_off64.p, seg_off64.data(), seg_off64.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete s;
+        return fail(e == hipErrorOutOfMemory ? PQV_ERR_OOM : PQV_ERR_HIP, std::string("segment table upload: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return PQV_OK;
+}
+extern "C" int pqv_table_searcher_create(const pqv_index *const *indexes, uint32_t n_files, const uint64_t *row_base,
+                                         pqv_corpus *corpus, uint32_t flags, pqv_searcher **out) {
+    return guard([&] { return pqv_table_searcher_create_impl(indexes, n_files, row_base, corpus, flags, out); });
+}
+extern "C" int pqv_searcher_files(const pqv_searcher *s, uint32_t *n_files, uint64_t *row_base, uint32_t *cluster_base) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    const uint32_t n = s->n_files ? s->n_files : 1;
+    if (n_files) *n_files = n;
+    for (uint32_t f = 0; f < n; ++f) {
+        if (row_base) row_base[f] = s->n_files ? s->row_base[f] : 0;
+        if (cluster_base) cluster_base[f] = s->n_files ? s->seg_off[f] : 0;
+    }
+    return PQV_OK;
+}
+
 extern "C" void pqv_searcher_free(pqv_searcher *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -2790,6 +2886,14 @@ extern "C" void pqv_searcher_free(pqv_searcher *s) {
 }
 
 namespace {
+
+// probed lists per query: min(nprobe, n_clusters), on a table searcher the sum of min(nprobe, kc_f) over its files
+uint32_t probe_count(const pqv_searcher *s, uint32_t nprobe) {
+    if (!s->n_files) return std::min<uint32_t>(nprobe, s->n_clusters);
+    uint64_t P = 0;
+    for (uint32_t f = 0; f < s->n_files; ++f) P += std::min<uint32_t>(nprobe, s->seg_off[f + 1] - s->seg_off[f]);
+    return static_cast<uint32_t>(std::min<uint64_t>(P, 0xFFFFFFFFull));
+}
 
 struct TopkPlan {
     uint32_t np;            // effective nprobe
@@ -2850,7 +2954,7 @@ static bool seed_refine_on(const pqv_searcher *s, uint32_t nq, uint32_t k) {
 TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t k = 1, int metric = 0) {
     TopkPlan p{};
     const pqv_searcher::Opts &o = s->opt;
-    p.np = std::min<uint32_t>(nprobe, s->n_clusters);
+    p.np = probe_count(s, nprobe);
     // probe pass: every block scans 256 centroids (64 per wave)
     p.probe_bpl = (s->n_clusters + 255) / 256;
     p.n_part_probe = p.probe_bpl * pqv::waves_per_block();
@@ -2860,6 +2964,12 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     p.probe_rows = s->opt.probe_rows && s->kc_pad != 0 && (nq >= 8 || s->opt.probe_rows > 1) &&
                    static_cast<uint64_t>(nq) * s->kc_pad * 12 <= (2ull << 30);
     p.probe_kpart = p.probe_rows ? 64u : p.np;
+    if (s->n_files && !p.probe_rows) {
+        // table, stream_kernel probe: one list per file (no block straddles two files), the nprobe nearest of a file kept per partial list
+        p.probe_bpl = (s->seg_max_kc + 255) / 256;
+        p.n_part_probe = s->n_files * p.probe_bpl * pqv::waves_per_block();
+        p.probe_kpart = std::min<uint32_t>(nprobe, s->seg_max_kc);
+    }
     // re-rank: enough blocks to fill 256 CUs several times over, few enough partial lists
     const uint64_t max_len = std::max<uint64_t>(1, s->max_list_len);
     const uint64_t max_bpl = (max_len + 255) / 256;
@@ -3020,6 +3130,47 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     return p;
 }
 
+// tables: the per-file cap of the reference (access.rs:214-242) is not one prefix of the file-major candidate sequence
+int table_max_candidates(const pqv_searcher *s, uint64_t max_candidates) {
+    if (s->n_files && max_candidates)
+        return fail(PQV_ERR_UNSUPPORTED, "max_candidates > 0 is not supported on a table searcher: cap per file with "
+                                         "pqv_candidate_cursor over per-file searchers and merge their results");
+    return PQV_OK;
+}
+// Table searchers: the batched probe over the combined centroid table (probe_rows_kernel, or stream_kernel with one list per
+// file) and the probe merge per file segment (merge_probe_seg_kernel).  pm: the probe merge's arguments as the caller fills them
+// for launch_merge_probe (k = p.np = P); pm.part_keys / part_vals are the probe scratch.  sc.s_probe / s_cand_base must hold
+// nq * max(P, n_files) entries (the stream route reads its per-file arguments from them before the merge overwrites them).
+int enqueue_table_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, const float *d_queries, uint32_t nq, uint32_t nprobe,
+                        uint32_t *zero_u32, uint32_t zero_n, const pqv::MergeArgs &pm, hipStream_t stream) {
+    using namespace pqv;
+    if (p.probe_rows) {
+        ProbeRowsArgs pr{};
+        pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_queries;
+        pr.nq = nq; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
+        pr.part_keys = const_cast<uint64_t *>(pm.part_keys); pr.part_vals = const_cast<uint32_t *>(pm.part_vals);
+        pr.zero_u32 = zero_u32; pr.zero_n = zero_n;
+        HIP_TRY(launch_probe_rows(pr, stream));
+    } else {
+        HIP_TRY(launch_seg_probe_fill(s->d_seg_off.as<uint32_t>(), s->n_files, nq, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(), stream));
+        StreamArgs pa{};
+        pa.mat = s->d_centroids.as<float>(); pa.row_of = nullptr; pa.list_off = s->d_seg_off64.as<uint64_t>();
+        pa.probe = sc.s_probe.as<uint32_t>(); pa.cand_base = sc.s_cand_base.as<uint64_t>();
+        pa.queries = d_queries; pa.nq = nq; pa.nprobe = s->n_files; pa.dim = s->dim; pa.k = p.probe_kpart;
+        pa.rows_per_block = 256; pa.blocks_per_list = p.probe_bpl;
+        pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;   // find_closest_centroids always uses index.rs:461
+        pa.part_keys = const_cast<uint64_t *>(pm.part_keys); pa.part_vals = const_cast<uint32_t *>(pm.part_vals);
+        pa.zero_u32 = zero_u32; pa.zero_n = zero_n;
+        HIP_TRY(launch_stream(pa, STREAM_TOPK, stream));
+        s->counters.kernel_launches += 2;
+    }
+    SegProbeArgs g{};
+    g.seg_off = s->d_seg_off.as<uint32_t>(); g.n_files = s->n_files; g.nprobe = nprobe;
+    g.kmax = std::min<uint32_t>(nprobe, s->seg_max_kc);
+    g.stream_parts = p.probe_rows ? 0u : p.probe_bpl * waves_per_block();
+    HIP_TRY(launch_merge_probe_seg(pm, g, stream));
+    return PQV_OK;
+}
 // Enqueue probe -> probe-merge -> re-rank -> final merge for one batch on `stream`.
 // `k` is the list length the kernels work with; the first k_out entries are written out.
 // With k == k_out + 1 the merge can also flag queries whose output distances tie (d_tie).
@@ -3041,8 +3192,9 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
 
     HIP_TRY(sc.s_probe_keys.ensure(static_cast<size_t>(nq) * p.n_part_probe * p.probe_kpart * sizeof(uint64_t)));
     HIP_TRY(sc.s_probe_vals.ensure(static_cast<size_t>(nq) * p.n_part_probe * p.probe_kpart * sizeof(uint32_t)));
-    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
-    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint64_t)));
+    const uint32_t np_slots = std::max<uint32_t>(p.np, s->n_files);     // (a table's stream probe reads its per-file arguments from them)
+    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(nq) * np_slots * sizeof(uint32_t)));
+    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(nq) * np_slots * sizeof(uint64_t)));
     HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(nq) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint32_t)));
@@ -3078,9 +3230,10 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         if (p.filter) { HIP_TRY(sc.s_qnorm.ensure(static_cast<size_t>(nq) * sizeof(float))); HIP_TRY(sc.s_qmax.ensure(static_cast<size_t>(nq) * sizeof(float))); }
     }
     // one query on the wide screened path: probe, probe merge, bucketing and quantisation in ONE block (probe_single_kernel)
+    // (table searchers: never -- the batched probe and the pair sort, see enqueue_table_probe)
     const bool fused_probe = nq == 1 && p.np <= 64 && p.tile && p.filter && p.quad && s->opt.single_bucket > 0 &&
-                             s->opt.single_bucket != 2 && s->kc_pad != 0 && s->kc_pad <= 4096;
-    if (fused_probe) {
+                             s->opt.single_bucket != 2 && s->kc_pad != 0 && s->kc_pad <= 4096 && !s->n_files;
+    if (fused_probe || s->n_files) {
         // (launched below, once the merge arguments are complete)
     } else if (p.probe_rows) {     // a batch: a lane per centroid, the chains of up to 8 queries in registers
         pqv::ProbeRowsArgs pr{};
@@ -3115,7 +3268,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         if (p.filter) { pm.qnorm_out = sc.s_qnorm.as<float>(); pm.qmax_out = sc.s_qmax.as<float>(); pm.queries = d_queries; pm.dim = s->dim; }
     }
     // one query: the probe merge writes the bucketing itself (MergeArgs::sq_*), no pair sort
-    const bool single_bucket = nq == 1 && p.np <= 64 && p.tile && p.filter && p.quad && s->opt.single_bucket;
+    const bool single_bucket = nq == 1 && p.np <= 64 && p.tile && p.filter && p.quad && s->opt.single_bucket && !s->n_files;
     // (a work-item table of more than 2^24 entries -- batches of hundreds of thousands of queries -- keeps the 2-D grid)
     const bool items = p.tile && p.filter && p.quad && (s->opt.item_grid > 1 || (s->opt.item_grid == 1 && p.block_waves == 4)) &&
                        static_cast<uint64_t>(p.max_quads) * p.filter_bpl <= (1ull << 24);
@@ -3166,6 +3319,8 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         // (the image(s) of a one-query call are made inside the probe launch)
         quant_done = pq_args.n_pairs != 0;
         HIP_TRY(pqv::launch_probe_single(pr, pm, sc.s_ticket.as<uint32_t>(), quant_done ? &pq_args : nullptr, stream));
+    } else if (s->n_files) {
+        if (int rc = enqueue_table_probe(s, sc, p, d_queries, nq, nprobe, pa.zero_u32, pa.zero_n, pm, stream)) return rc;
     } else {
         HIP_TRY(launch_merge_probe(pm, stream));
     }
@@ -3431,7 +3586,7 @@ int validate_topk(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric
 // the kernels' sorted lists hold up to 1024 entries (k, and the probe's min(nprobe, n_clusters)); pqv_topk goes around
 // that limit (topk_unbounded), the asynchronous device entry points report it
 bool beyond_kernel_lists(const pqv_searcher *s, uint32_t k_lists, uint32_t nprobe) {
-    return k_lists > 1024 || std::min<uint32_t>(nprobe, s->n_clusters) > 1024;
+    return k_lists > 1024 || probe_count(s, nprobe) > 1024;
 }
 
 }  // namespace
@@ -3555,7 +3710,8 @@ int replay_query_exact(const pqv_searcher *s, Scratch &sc, const float *d_query,
 // candidate distance on the GPU, the reference's heap on the host.  Correct for any k / nprobe; not a fast path.
 // find_closest_centroids (index.rs:130-149) without the kernels' list limit: every centroid distance on the GPU
 // (STREAM_DIST over the centroid table), the stable sort on the host.  d_query: device [dim]; order: all clusters, nearest first.
-int centroid_order_host(const pqv_searcher *s, Scratch &sc, const float *d_query, std::vector<uint32_t> &order) {
+// (a table searcher: the probed lists only -- see below; `nprobe` is read on tables only)
+int centroid_order_host(const pqv_searcher *s, Scratch &sc, const float *d_query, std::vector<uint32_t> &order, uint32_t nprobe) {
     using namespace pqv;
     const uint32_t kc = s->n_clusters;
     HIP_TRY(sc.s_replay.ensure(std::max<size_t>(1, kc) * sizeof(float)));
@@ -3572,7 +3728,20 @@ int centroid_order_host(const pqv_searcher *s, Scratch &sc, const float *d_query
     HIP_TRY(hipStreamSynchronize(s->stream));
     order.resize(kc);
     for (uint32_t c = 0; c < kc; ++c) order[c] = c;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cd[a] < cd[b]; });   // index.rs:143-147
+    if (!s->n_files) {
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cd[a] < cd[b]; });   // index.rs:143-147
+    } else {
+        // a table: each file's centroids in their own order, file after file, and only the first nprobe of each are probed --
+        // order becomes the probed lists, P = probe_count(s, nprobe) of them
+        uint32_t o = 0;
+        for (uint32_t f = 0; f < s->n_files; ++f) {
+            const uint32_t lo = s->seg_off[f], hi = s->seg_off[f + 1], kf = std::min<uint32_t>(nprobe, hi - lo);
+            std::stable_sort(order.begin() + lo, order.begin() + hi, [&](uint32_t a, uint32_t b) { return cd[a] < cd[b]; });
+            std::copy(order.begin() + lo, order.begin() + lo + kf, order.begin() + o);
+            o += kf;
+        }
+        order.resize(o);
+    }
     s->counters.kernel_launches += 1;
     return PQV_OK;
 }
@@ -3581,7 +3750,7 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
                    uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found,
                    uint64_t *n_candidates) {
     using namespace pqv;
-    const uint32_t kc = s->n_clusters, np = std::min<uint32_t>(nprobe, kc);
+    const uint32_t np = probe_count(s, nprobe);
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
     HIP_TRY(sc.s_probe.ensure(std::max<size_t>(1, np) * sizeof(uint32_t)));
     HIP_TRY(sc.s_cand_base.ensure(std::max<size_t>(1, np) * sizeof(uint64_t)));
@@ -3590,7 +3759,7 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
     for (uint32_t q = 0; q < nq; ++q) {
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q) * s->dim, static_cast<size_t>(s->dim) * sizeof(float),
                                hipMemcpyHostToDevice, s->stream));
-        if (int rc = centroid_order_host(s, sc, sc.s_queries.as<float>(), order)) return rc;
+        if (int rc = centroid_order_host(s, sc, sc.s_queries.as<float>(), order, nprobe)) return rc;
         const float *d_q_s = sc.s_queries.as<float>();
         if (s->sdim != s->dim) {
             HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(s->sdim) * sizeof(float)));
@@ -3626,9 +3795,12 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
                                void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                void *d_tie_flags, void *hip_stream) {
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (int rc = table_max_candidates(s, max_candidates)) return rc;
     if (d_tie_flags && k > 1023) return fail(PQV_ERR_UNSUPPORTED, "tie flags need a runner-up entry: k <= 1023");
     if (beyond_kernel_lists(s, k, nprobe))
-        return fail(PQV_ERR_UNSUPPORTED, "the device entry points take k <= 1024 and min(nprobe, n_clusters) <= 1024 (pqv_topk has no such limit)");
+        return fail(PQV_ERR_UNSUPPORTED, s->n_files ? "the device entry points take k <= 1024 and at most 1024 probed lists per query (the sum of "
+                                                      "min(nprobe, n_clusters) over the table's files; pqv_topk has no such limit)"
+                                                    : "the device entry points take k <= 1024 and min(nprobe, n_clusters) <= 1024 (pqv_topk has no such limit)");
     if (nq == 0) return PQV_OK;
     if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
     if (int rc = use_device(s->device)) return rc;
@@ -3663,6 +3835,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                         uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (int rc = table_max_candidates(s, max_candidates)) return rc;
     if (query_len != s->dim)                                                           // search.rs:91-98
         return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) +
                                          ", got " + std::to_string(query_len));
@@ -3698,7 +3871,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     HIP_TRY(sc.s_tie.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     std::vector<uint64_t> h_ncand(batch);
     std::vector<uint32_t> h_tie(batch), h_nf(batch);
-    const uint32_t np = std::min<uint32_t>(nprobe, s->n_clusters);
+    const uint32_t np = probe_count(s, nprobe);
     // A call of a few queries (TopkBuilder::search is ONE) is six small pageable copies otherwise -- the query in, rows, distances,
     // counts and tie flags out, each staged and waited for by the runtime: 60-80 us around 180 us of kernels.  Small calls go
     // through ONE pinned buffer instead: the results are laid out as one device block {candidates u64 | rows | dist | found |
@@ -3811,7 +3984,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
                uint64_t *n_candidates) {
     using namespace pqv;
     hipStream_t st = s->stream;
-    const uint32_t kc = s->n_clusters, np = std::min<uint32_t>(nprobe, kc);
+    const uint32_t kc = s->n_clusters, np = probe_count(s, nprobe);
     const bool wide_probe = np > 1024;              // (merge_kernel's lists hold up to 1024 probed clusters)
     const uint64_t max_pos = max_candidates ? max_candidates : ~0ull;
     // a query's segment holds its capped candidates: at most the np longest lists, at most max_candidates
@@ -3832,8 +4005,8 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
     const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>({nq, 65535ull, (1ull << 30) / per_query})));
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
     if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(batch) * s->sdim * sizeof(float)));
-    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(batch) * np * sizeof(uint32_t)));
-    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(batch) * np * sizeof(uint64_t)));
+    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(batch) * std::max<uint32_t>(np, s->n_files) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(batch) * std::max<uint32_t>(np, s->n_files) * sizeof(uint64_t)));
     HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
     HIP_TRY(sc.s_hit_cnt.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     HIP_TRY(sc.s_hit_keys.ensure(static_cast<size_t>(batch) * stride * sizeof(uint64_t)));
@@ -3866,7 +4039,9 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             const TopkPlan p = plan_topk(s, b, nprobe, 1, metric);
             HIP_TRY(sc.s_probe_keys.ensure(static_cast<size_t>(b) * p.n_part_probe * p.probe_kpart * sizeof(uint64_t)));
             HIP_TRY(sc.s_probe_vals.ensure(static_cast<size_t>(b) * p.n_part_probe * p.probe_kpart * sizeof(uint32_t)));
-            if (p.probe_rows) {
+            if (s->n_files) {
+                // (a table: launched with the merge, enqueue_table_probe)
+            } else if (p.probe_rows) {
                 ProbeRowsArgs pr{};
                 pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_q;
                 pr.nq = b; pr.kc = kc; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
@@ -3889,6 +4064,9 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             pm.probe = sc.s_probe.as<uint32_t>(); pm.cand_base = sc.s_cand_base.as<uint64_t>();
             pm.n_cand = sc.s_ncand.as<uint64_t>(); pm.max_pos = max_pos;
             pm.stats = s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
+            if (s->n_files) {
+                if (int rc = enqueue_table_probe(s, sc, p, d_q, b, nprobe, nullptr, 0, pm, st)) return rc;
+            } else
             HIP_TRY(launch_merge_probe(pm, st));
             launches += 2;
         } else {
@@ -3896,7 +4074,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             h_probe.resize(static_cast<size_t>(b) * np);
             h_base.resize(static_cast<size_t>(b) * np);
             for (uint32_t i = 0; i < b; ++i) {
-                if (int rc = centroid_order_host(s, sc, d_q + static_cast<uint64_t>(i) * s->dim, order)) return rc;
+                if (int rc = centroid_order_host(s, sc, d_q + static_cast<uint64_t>(i) * s->dim, order, nprobe)) return rc;
                 uint64_t total = 0;
                 for (uint32_t j = 0; j < np; ++j) {
                     h_probe[static_cast<size_t>(i) * np + j] = order[j];
@@ -4002,6 +4180,7 @@ static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, ui
                                  uint64_t *n_candidates) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (nprobe == 0) return fail(PQV_ERR_INVALID, "nprobe must be > 0");                          // search.rs:72
+    if (int rc = table_max_candidates(s, max_candidates)) return rc;
     if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ) return fail(PQV_ERR_INVALID, "unknown metric");
     if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
     if (query_len != s->dim)                                                                      // search.rs:91-98
@@ -4090,9 +4269,18 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
     if (!s || !buf || !len) return fail(PQV_ERR_INVALID, "searcher/buf must not be NULL");
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
+    // a table names itself first: its files, the lists a query probes, and the probe route
+    char tb[256] = "";
+    if (s->n_files) {
+        const TopkPlan pt = plan_topk(s, std::max<uint32_t>(1, nq), nprobe, k, metric);
+        std::snprintf(tb, sizeof tb, "table of %u files, %u lists per query (nprobe %u per file); probe: %s + merge_probe_seg_kernel (per file), "
+                      "no fused single-query probe (pair sort instead); ", s->n_files, probe_count(s, nprobe), nprobe,
+                      beyond_kernel_lists(s, k, nprobe) ? "stream_kernel (STREAM_DIST) + a stable sort per file on the host"
+                      : pt.probe_rows ? "probe_rows_kernel" : "stream_kernel with one list per file");
+    }
     if (beyond_kernel_lists(s, k, nprobe)) {
-        std::snprintf(buf, len, "pqv_topk only: stream_kernel (STREAM_DIST) for every centroid and candidate distance, selection by the "
-                                "reference's heap on the host (k > 1024 or min(nprobe, n_clusters) > 1024)");
+        std::snprintf(buf, len, "%spqv_topk only: stream_kernel (STREAM_DIST) for every centroid and candidate distance, selection by the "
+                                "reference's heap on the host (k > 1024 or min(nprobe, n_clusters) > 1024)", tb);
         return PQV_OK;
     }
     const TopkPlan p = plan_topk(s, std::max<uint32_t>(1, nq), nprobe, k, metric);
@@ -4152,7 +4340,7 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
                           defp ? "true" : "false");
         }
     }
-    std::snprintf(buf, len, "%s; centroid probe: %s%s", t, p.probe_rows ? "probe_rows_kernel (a lane per centroid)" : "stream_kernel", kn);
+    std::snprintf(buf, len, "%s%s; centroid probe: %s%s", tb, t, p.probe_rows ? "probe_rows_kernel (a lane per centroid)" : "stream_kernel", kn);
     return PQV_OK;
 }
 extern "C" int pqv_searcher_describe(const pqv_searcher *s, uint32_t nq, uint32_t k, uint32_t nprobe, int metric,
@@ -4193,7 +4381,7 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
         return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) +
                                          ", got " + std::to_string(query_len));
     if (!query || !clusters_out) return fail(PQV_ERR_INVALID, "query/clusters_out must not be NULL");
-    const uint32_t np = std::min<uint32_t>(nprobe, s->n_clusters);
+    const uint32_t np = probe_count(s, nprobe);
     if (int rc = use_device(s->device)) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     using namespace pqv;
@@ -4205,7 +4393,7 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
         HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, query, static_cast<size_t>(s->dim) * sizeof(float), hipMemcpyHostToDevice, s->stream));
         std::vector<uint32_t> order;
-        if (int rc = centroid_order_host(s, sc, sc.s_queries.as<float>(), order)) return rc;
+        if (int rc = centroid_order_host(s, sc, sc.s_queries.as<float>(), order, nprobe)) return rc;
         std::memcpy(clusters_out, order.data(), static_cast<size_t>(np) * sizeof(uint32_t));
         if (n_out) *n_out = np;
         return lane_release(sc, s->stream);
@@ -4214,8 +4402,8 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
     HIP_TRY(sc.s_probe_keys.ensure(static_cast<size_t>(p.n_part_probe) * p.probe_kpart * sizeof(uint64_t)));
     HIP_TRY(sc.s_probe_vals.ensure(static_cast<size_t>(p.n_part_probe) * p.probe_kpart * sizeof(uint32_t)));
-    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(np) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(np) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(std::max<uint32_t>(np, s->n_files)) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(std::max<uint32_t>(np, s->n_files)) * sizeof(uint64_t)));
     HIP_TRY(sc.s_ncand.ensure(sizeof(uint64_t)));
     HIP_TRY(hipMemcpyAsync(sc.s_queries.p, query, static_cast<size_t>(s->dim) * sizeof(float),
                            hipMemcpyHostToDevice, s->stream));
@@ -4224,7 +4412,9 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
     pa.queries = sc.s_queries.as<float>(); pa.nq = 1; pa.nprobe = 1; pa.dim = s->dim; pa.k = np;
     pa.rows_per_block = 256; pa.blocks_per_list = p.probe_bpl; pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;
     pa.part_keys = sc.s_probe_keys.as<uint64_t>(); pa.part_vals = sc.s_probe_vals.as<uint32_t>();
-    if (p.probe_rows) {
+    if (s->n_files) {
+        // (a table: launched with the merge, enqueue_table_probe)
+    } else if (p.probe_rows) {
         pqv::ProbeRowsArgs pr{};
         pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = pa.queries;
         pr.nq = 1; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
@@ -4238,6 +4428,9 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
     pm.k_part = p.probe_kpart; pm.k = np; pm.list_off = s->d_list_off.as<uint64_t>();
     pm.probe = sc.s_probe.as<uint32_t>(); pm.cand_base = sc.s_cand_base.as<uint64_t>();
     pm.n_cand = sc.s_ncand.as<uint64_t>(); pm.max_pos = ~0ull;
+    if (s->n_files) {
+        if (int rc = enqueue_table_probe(s, sc, p, pa.queries, 1, nprobe, nullptr, 0, pm, s->stream)) return rc;
+    } else
     HIP_TRY(launch_merge_probe(pm, s->stream));
     HIP_TRY(hipMemcpyAsync(clusters_out, sc.s_probe.p, static_cast<size_t>(np) * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, s->stream));
@@ -4257,7 +4450,7 @@ static int pqv_candidate_rows_impl(const pqv_searcher *s, const float *query, ui
     if (!rows || !n_rows) return fail(PQV_ERR_INVALID, "rows/n_rows must not be NULL");
     *rows = nullptr; *n_rows = 0;
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
-    const uint32_t np = std::min<uint32_t>(nprobe, s->n_clusters);
+    const uint32_t np = probe_count(s, nprobe);
     std::vector<uint32_t> clusters(std::max<uint32_t>(np, 1));
     uint32_t got = 0;
     if (int rc = pqv_probe(s, query, query_len, nprobe, clusters.data(), &got)) return rc;

@@ -172,6 +172,16 @@ hipError_t launch_merge_final(const MergeArgs &a, hipStream_t s);
 // deferred evaluations of a BATCH, ahead of launch_merge_final (which then gets cand_lb = nullptr): work = nq * cand_cap uint2 of scratch
 hipError_t launch_resolve(const MergeArgs &a, void *work, uint32_t *n_work, bool n_work_is_zero, hipStream_t s);
 hipError_t launch_merge_probe(const MergeArgs &a, hipStream_t s);
+// table searchers: the probe merge per file segment of the centroid table (kernels_probe.hip: merge_probe_seg_kernel)
+struct SegProbeArgs {
+    const uint32_t *seg_off;      // [n_files + 1] first global centroid of each file (device)
+    uint32_t        n_files, nprobe;
+    uint32_t        kmax;         // max over the files of min(nprobe, kc_f) (<= 1024)
+    uint32_t        stream_parts; // 0: probe_rows_kernel partials (entry c = centroid c); else stream_kernel partial lists per file
+};
+hipError_t launch_merge_probe_seg(const MergeArgs &a, const SegProbeArgs &g, hipStream_t s);
+// stream_kernel arguments of the per-file centroid pass: probe[q * n_files + f] = f, cand_base[...] = seg_off[f]
+hipError_t launch_seg_probe_fill(const uint32_t *seg_off, uint32_t n_files, uint32_t nq, uint32_t *probe, uint64_t *cand_base, hipStream_t s);
 
 // ---- batched re-rank: cluster-major tiles ------------------------------------------------
 // The (query, probe-rank) pairs of a batch are bucketed by cluster; a "group" is up to

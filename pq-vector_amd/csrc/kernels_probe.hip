@@ -1139,6 +1139,117 @@ hipError_t launch_merge_final(const MergeArgs &a, hipStream_t s) { return launch
 hipError_t launch_merge_probe(const MergeArgs &a, hipStream_t s) { return launch_merge_t<true>(a, s); }
 
 // ------------------------------------------------------------------------------------
+// Table searchers (pqv_table_searcher_create): the centroid table is the files' tables concatenated, file f owning the global
+// centroids [seg_off[f], seg_off[f + 1]).  find_closest_centroids runs per FILE (index_exec.rs:85-164): the probe merge keeps, per
+// (query, file), the first min(nprobe, kc_f) keys by (distance bits, global centroid) -- within a file the order by local index --
+// and writes them file-major, the candidate bases running on across the files (file 0's candidate_rows, then file 1's, ...).
+// Everything else is the PROBE merge's: histogram, presets, admission thresholds, norms, statistics.  The plain merge_kernel
+// instantiations are untouched.
+//   probe_rows_kernel input: partial list entry c of a query is centroid c, so file f's keys are entries [seg_off[f], seg_off[f+1]).
+//   stream_kernel input (one "list" per file, SegProbeArgs::stream_parts partial lists of k_part entries each): file f's are the
+//   partial lists [f * stream_parts, (f + 1) * stream_parts) -- no block of that pass straddles two files.
+// ------------------------------------------------------------------------------------
+template <int S>
+__device__ __forceinline__ void probe_merge_tail_seg(const MergeArgs &a, uint32_t q, int lane, const WaveTopk<S> &tk, uint32_t kf,
+                                                     uint32_t out0, uint64_t &carry) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const uint32_t e = s * 64 + lane;
+        const bool have = e < kf && tk.key[s] != KEY_EMPTY;
+        const uint32_t c = have ? tk.val[s] : 0;
+        const uint64_t len = have ? (a.list_off[c + 1] - a.list_off[c]) : 0;
+        uint64_t incl = len;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, off, 64);
+            const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), off, 64);
+            const uint64_t o = ((uint64_t)hi << 32) | lo;
+            if (lane >= off) incl += o;
+        }
+        if (e < kf) {
+            a.probe[(uint64_t)q * a.k + out0 + e] = c;
+            a.cand_base[(uint64_t)q * a.k + out0 + e] = carry + incl - len;
+            if (a.hist && have) atomicAdd(&a.hist[(uint64_t)(q % HIST_REPLICAS) * a.hist_stride + c], 1u);
+        }
+        carry += readlane_u64(incl, 63);
+    }
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void merge_probe_seg_kernel(const MergeArgs a, const SegProbeArgs g) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t q = blockIdx.x;
+    if (threadIdx.x >= 64) {
+        probe_merge_helpers(a, q);
+        return;
+    }
+    const uint64_t total = (uint64_t)a.n_part * a.k_part;
+    const uint64_t *pk = a.part_keys + (uint64_t)q * total;
+    const uint32_t *pv = a.part_vals + (uint64_t)q * total;
+    uint64_t carry = 0;
+    uint32_t out0 = 0;
+    for (uint32_t f = 0; f < g.n_files; ++f) {
+        const uint32_t lo = g.seg_off[f], hi = g.seg_off[f + 1];
+        const uint32_t kf = hi - lo < g.nprobe ? hi - lo : g.nprobe;
+        if (kf == 0) continue;
+        uint64_t b, e;
+        if (g.stream_parts) { b = (uint64_t)f * g.stream_parts * a.k_part; e = b + (uint64_t)g.stream_parts * a.k_part; }
+        else { b = lo; e = hi; }
+        WaveTopk<S> tk;
+        tk.init();
+        for (uint64_t i = b; i < e; i += 64) {
+            const uint64_t idx = i + lane;
+            uint64_t key = KEY_EMPTY;
+            uint32_t val = 0xFFFFFFFFu;
+            if (idx < e) { key = pk[idx]; val = pv[idx]; }
+            if (__ballot(key != KEY_EMPTY) != 0ull) tk.offer(key, val, kf, lane);
+        }
+        probe_merge_tail_seg<S>(a, q, lane, tk, kf, out0, carry);
+        out0 += kf;
+    }
+    if (a.n_cand && lane == 0) a.n_cand[q] = carry;
+    if (a.stats && lane == 0) {
+#ifdef PQV_PROFILE_PHASES
+        unsigned long long *st = a.stats;
+#else
+        unsigned long long *st = a.stats + 8 + 16 * (q % STATS_SLOTS);
+#endif
+        atomicAdd(&st[2], (unsigned long long)carry);
+        atomicAdd(&st[3], (unsigned long long)(carry < a.max_pos ? carry : a.max_pos));
+    }
+    if (a.gthr_init && lane == 0) a.gthr_init[q] = ~0ull;
+    probe_query_norms(a, q, lane);
+}
+hipError_t launch_merge_probe_seg(const MergeArgs &a, const SegProbeArgs &g, hipStream_t s) {
+    if (a.nq == 0) return hipSuccess;
+    if (a.sq_quads || g.n_files == 0) return hipErrorInvalidValue;     // (no single-query bucketing on tables)
+    dim3 grid(a.nq), block((a.preset_keys || a.preset_flags) ? 256 : 64);
+    if (g.kmax <= 64) hipLaunchKernelGGL((merge_probe_seg_kernel<1>), grid, block, 0, s, a, g);
+    else if (g.kmax <= 256) hipLaunchKernelGGL((merge_probe_seg_kernel<4>), grid, block, 0, s, a, g);
+    else if (g.kmax <= 1024) hipLaunchKernelGGL((merge_probe_seg_kernel<16>), grid, block, 0, s, a, g);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// stream_kernel's arguments for the per-file centroid pass: list j of query q is file j (probe = j, candidate base = its first
+// global centroid, so positions and values are global centroid ids)
+__global__ __launch_bounds__(256) void seg_probe_fill_kernel(const uint32_t *seg_off, uint32_t n_files, uint32_t nq, uint32_t *probe,
+                                                             uint64_t *cand_base) {
+    const uint64_t n = (uint64_t)nq * n_files;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t f = (uint32_t)(i % n_files);
+        probe[i] = f;
+        cand_base[i] = seg_off[f];
+    }
+}
+hipError_t launch_seg_probe_fill(const uint32_t *seg_off, uint32_t n_files, uint32_t nq, uint32_t *probe, uint64_t *cand_base, hipStream_t s) {
+    const uint64_t n = (uint64_t)nq * n_files;
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(seg_probe_fill_kernel, dim3(blocks), dim3(256), 0, s, seg_off, n_files, nq, probe, cand_base);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // pair bucketing for the batched re-rank: counting sort of (query, probe-rank) pairs by
 // cluster + the group table.  Order inside a bucket is arbitrary (atomics) and does not
 // matter: every pair writes its partial lists to slots fixed by (q, j, chunk, wave).

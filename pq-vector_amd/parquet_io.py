@@ -668,7 +668,31 @@ def _load_pages(path, column, corpus, dim, rg_off, n_threads, counters, row_grou
         return False
 
 
-def load_embedding_column(path, column, device=0, readers=None, stats=None, row_groups=None):
+class _RowOffsetCorpus:
+    """A caller's corpus seen from one file of a table: rows land at `row_offset` onward; finishing and closing stay with the
+    caller (load_embedding_column(..., into=corpus, row_offset=...))."""
+
+    def __init__(self, corpus, row_offset):
+        self._c, self._off = corpus, int(row_offset)
+
+    def write_rows(self, row_offset, rows):
+        return self._c.write_rows(self._off + row_offset, rows)
+
+    def write_rows_ptr(self, row_offset, address, n_rows, f64=False):
+        return self._c.write_rows_ptr(self._off + row_offset, address, n_rows, f64)
+
+    def write_plain_pages(self, file_base, body_off, body_len, first_value, n_values, dim, max_def, f64=False):
+        first = np.ascontiguousarray(first_value, dtype=np.uint64) + np.uint64(self._off * dim)
+        return self._c.write_plain_pages(file_base, body_off, body_len, first, n_values, dim, max_def, f64)
+
+    def finish(self, n_rows):
+        pass
+
+    def close(self):
+        pass
+
+
+def load_embedding_column(path, column, device=0, readers=None, stats=None, row_groups=None, into=None, row_offset=0):
     """The column -> one resident [n, dim] f32 matrix (src/ivf/parquet.rs:216-305; Float64 values are narrowed on the device,
     :246-256).  Row groups are decoded by `readers` threads (pyarrow releases the GIL while it decodes), each with its own file
     handle; every decoded batch goes through the corpus' pinned staging buffers as an asynchronous DMA (pqv_corpus_write_rows)
@@ -678,7 +702,11 @@ def load_embedding_column(path, column, device=0, readers=None, stats=None, row_
 
     `row_groups` = (lo, hi): only that half-open range of the file's row groups -- ONE shard of a file that several GPUs share
     (sharding.shard_row_groups cuts at row-group boundaries; the shard's row 0 is the range's first row, its file-global row
-    base the prefix sum of the row groups before it, src/df_vector/access.rs:128-144)."""
+    base the prefix sum of the row groups before it, src/df_vector/access.rs:128-144).
+
+    `into` (a Corpus.create of the whole table) + `row_offset`: the column's rows are written to rows [row_offset, row_offset + n)
+    of that corpus instead of a corpus of their own -- N files load into one resident corpus (TableSearcher); the caller
+    finishes it.  Returns `into`."""
     import os
     import threading
     import time
@@ -694,6 +722,16 @@ def load_embedding_column(path, column, device=0, readers=None, stats=None, row_
         rg_off[i + 1] = rg_off[i] + meta.row_group(rg_lo + i).num_rows
     if n_rows == 0:
         raise _err("Embedding column has no rows")
+    if into is not None and (row_offset < 0 or row_offset + n_rows > into.capacity):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"rows [{row_offset}, {row_offset + n_rows}) of {path} do not fit the target corpus "
+                                             f"of {into.capacity} rows")
+
+    def make_corpus(n, dim):
+        if into is None:
+            return Corpus.create(n, dim, device)
+        if dim != into.dim:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"embedding dimension {dim} of {path} does not match the target corpus dimension {into.dim}")
+        return _RowOffsetCorpus(into, row_offset)
     nthr_pages = max(1, readers or int(os.environ.get("PQV_LOADER_THREADS", "0")) or min(8, os.cpu_count() or 1))
     # the page-level walk first (PQV_PARQUET_PAGES=0: the Arrow reader only).  Its first data page fixes the dimension and is
     # checked before any device is touched; from then on every page is handed to the upload threads while the walk goes on.
@@ -717,7 +755,7 @@ def load_embedding_column(path, column, device=0, readers=None, stats=None, row_
             nonlocal corpus, ex, t_first, t_create
             if corpus is None:
                 t_first = time.perf_counter() - t0
-                corpus = Corpus.create(n_rows, pl.dim, device)
+                corpus = make_corpus(n_rows, pl.dim)
                 t_create = time.perf_counter() - t0 - t_first
                 state["do"] = _page_uploader(pl, corpus)
                 state["run"] = _plain_run_uploader(pl, corpus)
@@ -775,7 +813,7 @@ def load_embedding_column(path, column, device=0, readers=None, stats=None, row_
             if corpus is not None:
                 corpus.close()
             t_first = time.perf_counter() - t0
-            corpus = Corpus.create(n_rows, dim, device)
+            corpus = make_corpus(n_rows, dim)
             t_create = time.perf_counter() - t0 - t_first
     else:
         dim = plan.dim
@@ -791,7 +829,7 @@ def load_embedding_column(path, column, device=0, readers=None, stats=None, row_
             stats.update({"rows": int(n_rows), "dim": int(dim), "bytes": int(pages[0]), "seconds": el, "GBps": pages[0] / el / 1e9,
                           "row_groups": int(n_rg), "reader_threads": nthr_pages, "path": "data pages walked in the mapped file", "pages": pages[1],
                           "first_page_s": t_first, "corpus_create_s": t_create})
-        return corpus
+        return into if into is not None else corpus
 
     def work(t):
         rg = t
@@ -828,4 +866,4 @@ def load_embedding_column(path, column, device=0, readers=None, stats=None, row_
         el = time.perf_counter() - t0
         stats.update({"rows": int(n_rows), "dim": int(dim), "bytes": int(nbytes[0]), "seconds": el, "GBps": nbytes[0] / el / 1e9,
                       "row_groups": int(n_rg), "reader_threads": nthr, "path": "pyarrow record batches"})
-    return corpus
+    return into if into is not None else corpus
