@@ -22,9 +22,14 @@ queries/s over an N times larger corpus.  `--multi replica` instead replicates a
 fits one GPU and shards the QUERIES (no data-path collective); it is also timed as a
 secondary object on every N > 1 run.
 
-Prints ONE JSON line on rank 0 (contract in the task brief) with `roofline` and
-`cpu_baseline` objects; exits non-zero if the parity check inside the CPU leg fails.
-torch is plumbing here: device tensors, streams, RCCL.
+A plain run does only what the headline needs: it sets up (data, index, searcher, stream lanes),
+warms up, times the steps, writes --dump-outputs if asked, and prints ONE JSON line on rank 0
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  `--full` also measures and
+checks everything else, after the timed steps: the serial pass and `roofline`, single-query
+latency, recall, the `cpu_baseline` with its oracle parity leg, the exchange checks of multi-rank
+runs and, on the default C3 line, the Gaussian-mixture pass and the other configurations; it then
+exits non-zero if a parity check fails.  `--from-parquet` is a benchmark of its own and keeps its
+legs either way.  torch is plumbing here: device tensors, streams, RCCL.
 """
 import argparse
 import json
@@ -1081,6 +1086,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (distances, rows, and per-query counts "
                          "where the step returns them) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check: serial pass and roofline, single-query "
+                         "latency, recall, CPU baseline and oracle parity, multi-rank exchange checks and replicas, and on the default "
+                         "C3 line the mixture pass and the other configurations (--no-cpu, --single, --recall, --no-secondary, "
+                         "--no-configs, --parity-queries, --cabi-check shape this part).  Without it a run prints the headline only")
     args = ap.parse_args()
     if args.dump_outputs and args.from_parquet:
         raise SystemExit("--dump-outputs covers the timed top-k step; --from-parquet times an index build")
@@ -1278,6 +1288,61 @@ def main():
             outs["n_found"] = nf_l[last].cpu().numpy()
             outs["n_candidates"] = nc_l[last].cpu().numpy()
         dumped = dump_outputs(args.dump_outputs, outs)
+    # ---- the record of the set-up and the timed block: all a plain run prints ----------------------------------------
+    result = {
+        "metric": f"topk_queries_per_s_k{K}",
+        "value": (world if replica else 1) * nq * steps / elapsed,
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak" if (weak or replica or world == 1) else "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic" if args.data == "uniform" else "synthetic (gaussian mixture, sigma 0.1)",
+        "config": {"workload": f"{args.workload}: {n_total}x{dim} {'uniform' if args.data == 'uniform' else 'gaussian-mixture'} f32, n_clusters {index.n_clusters}"
+                               f"{' per shard' if world > 1 and not replica else ''}, k {K}, nprobe {nprobe}, "
+                               f"{nq} queries/step, layout {args.layout}",
+                   "rows": n_total, "rows_per_gpu": n_shard, "dim": dim, "n_clusters": int(index.n_clusters), "k": K,
+                   "nprobe": nprobe, "queries_per_step": nq, "shards": 1 if replica else world,
+                   "parallelism": ("replicas x%d: corpus replicated, query batches sharded (%d queries per step over "
+                                   "the job), no data-path collective" % (world, world * nq)) if replica
+                   else ("corpus sharded x%d (%d rows per rank, one IVF index per shard), every rank searches the same batch, one RCCL "
+                         "all-gather of the per-shard top-k + device merge per step" % (world, n_shard)) if world > 1
+                   else "single GPU"},
+        "timed_region_s": float(sum(block_s)),
+        "repeats": len(block_s),
+        "repeats_note": "one timed block of exactly `steps` steps (barrier + synchronize on both sides, max over ranks); ms_per_step "
+                        "and value are that block's",
+        "pipelining": {"streams": n_lanes, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
+                       "note": "steps alternate between %d HIP streams, so consecutive steps overlap on the GPU and ms_per_step "
+                               "(throughput) is below one step's own latency; ms_per_step_serial (--full) is the same step issued "
+                               "alone and host-synchronised" % n_lanes if n_lanes > 1 else "steps are serial on one stream"},
+        "index_build_vectors_per_s": n_shard / build_s,
+        "index_build_s": build_s,
+        "library_init_and_corpus_attach_s": attach_s,
+        "index_build": build_info,
+        "searcher_create_s": layout_s,
+        "time_to_first_query_s": build_s + layout_s,
+        "corpus_row_scans_per_s": n_total * nq * steps / elapsed if not replica else world * n_total * nq * steps / elapsed,
+        "dispatch": plan_text,
+    }
+    if dumped:
+        result["dump_outputs"] = dumped
+    if rank_block_s:
+        per = [t / steps * 1e3 for t in rank_block_s[0]]
+        result["per_rank_ms_per_step"] = {"min": min(per), "max": max(per), "ranks": per,
+                                          "note": "every rank's own wall time of the timed block / steps; the line's ms_per_step is the maximum"}
+    if not args.full:
+        if rank == 0:
+            emit(real_stdout, result)
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: every other measurement and check, all after the timed block ------------------------------------------
     # A serial pass (outside the timed region): steps issued one at a time on one stream -- the step time
     # without the overlap between consecutive steps, and the isolated per-launch kernel durations.
     serial_ms, serial_rr_ms, serial_hot_ms = None, None, None
@@ -1346,50 +1411,12 @@ def main():
     achieved = min_bytes / (k_ms * 1e-3) / 1e9 if k_ms and k_ms > 0 else 0.0
     fabric = traffic / (k_ms * 1e-3) / 1e9 if traffic and k_ms and k_ms > 0 else None
     mf = 2.0 * dim * cand_rows                         # the Q.X^T contraction of the screen
-    result = {
-        "metric": f"topk_queries_per_s_k{K}",
-        "value": (world if replica else 1) * nq * steps / elapsed,
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak" if (weak or replica or world == 1) else "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic" if args.data == "uniform" else "synthetic (gaussian mixture, sigma 0.1)",
-        "config": {"workload": f"{args.workload}: {n_total}x{dim} {'uniform' if args.data == 'uniform' else 'gaussian-mixture'} f32, n_clusters {index.n_clusters}"
-                               f"{' per shard' if world > 1 and not replica else ''}, k {K}, nprobe {nprobe}, "
-                               f"{nq} queries/step, layout {args.layout}",
-                   "rows": n_total, "rows_per_gpu": n_shard, "dim": dim, "n_clusters": int(index.n_clusters), "k": K,
-                   "nprobe": nprobe, "queries_per_step": nq, "shards": 1 if replica else world,
-                   "parallelism": ("replicas x%d: corpus replicated, query batches sharded (%d queries per step over "
-                                   "the job), no data-path collective" % (world, world * nq)) if replica
-                   else ("corpus sharded x%d (%d rows per rank, one IVF index per shard), every rank searches the same batch, one RCCL "
-                         "all-gather of the per-shard top-k + device merge per step" % (world, n_shard)) if world > 1
-                   else "single GPU"},
-        "timed_region_s": float(sum(block_s)),
-        "repeats": len(block_s),
-        "repeats_note": "one timed block of exactly `steps` steps (barrier + synchronize on both sides, max over ranks); ms_per_step "
-                        "and value are that block's",
-        "pipelining": {"streams": n_lanes, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
-                       "note": "steps alternate between %d HIP streams, so consecutive steps overlap on the GPU and ms_per_step "
-                               "(throughput) is below one step's own latency; ms_per_step_serial is the same step issued "
-                               "alone and host-synchronised" % n_lanes if n_lanes > 1 else "steps are serial on one stream"},
+    result.update({
         "ms_per_step_serial": serial_ms,
         "hot_path_ms_per_step_serial": serial_hot_ms,
-        "index_build_vectors_per_s": n_shard / build_s,
-        "index_build_s": build_s,
-        "library_init_and_corpus_attach_s": attach_s,
-        "index_build": build_info,
-        "searcher_create_s": layout_s,
-        "time_to_first_query_s": build_s + layout_s,
         "candidates_per_query": cand_rows / nq,
-        "corpus_row_scans_per_s": n_total * nq * steps / elapsed if not replica else world * n_total * nq * steps / elapsed,
         "hbm_footprint": fp,
-        "dispatch": plan_text,
-    }
+    })
     result["roofline"] = {
         "bound": "hbm", "kernel": " + ".join(k.split("@")[0] for k in kernels),
         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
@@ -1428,12 +1455,6 @@ def main():
                       "frac": (mf / (k_ms * 1e-3) / 1e12 / (3944.0 if i8 else 2500.0 if f16 else 157.3)) if k_ms else 0.0} if screened else None,
     }
     result["counters"] = ctr
-    if dumped:
-        result["dump_outputs"] = dumped
-    if rank_block_s:
-        per = [t / steps * 1e3 for t in rank_block_s[0]]
-        result["per_rank_ms_per_step"] = {"min": min(per), "max": max(per), "ranks": per,
-                                          "note": "every rank's own wall time of the timed block / steps; the line's ms_per_step is the maximum"}
     if exchange and xchg.fast:
         # the library merge kernel against the torch stable-sort merge of the same gathered lists
         lane = (step_no[0] - 1) % n_lanes if step_no[0] else 0
@@ -1699,10 +1720,10 @@ def brute_f64_check(torch, corpus_t, queries_t, rows, dist, sel, k):
             "ok": bool(err <= 1e-4 and missed == 0)}
 
 
-def brute_measure(args, pqv, torch, dev, local_rank, name, k, steps=5, corpus_t=None, queries_t=None, outputs=None):
+def brute_measure(args, pqv, torch, dev, local_rank, name, k, steps=5, corpus_t=None, queries_t=None, outputs=None, check=True):
     """BASELINE config 5: exhaustive cosine top-k of nq queries per step as a Q.V^T contraction on the matrix cores
-    (pqv_brute_topk; an extension -- the reference has no cosine).  The 32 checked queries are answers of the timed run.
-    `outputs` (a dict), if given, receives the last timed step's rows / distances / n_found."""
+    (pqv_brute_topk; an extension -- the reference has no cosine).  With `check`, 32 answers of the timed run are checked
+    against an f64 brute force (`parity`).  `outputs` (a dict), if given, receives the last timed step's rows / distances / n_found."""
     n, dim, _, _, nq = WORKLOADS[name]
     t_all = time.perf_counter()
     if corpus_t is None:
@@ -1748,7 +1769,8 @@ def brute_measure(args, pqv, torch, dev, local_rank, name, k, steps=5, corpus_t=
                                 "peak = the dense MFMA rate of the screen's operand form: int8 3944 TOPS (default), f16 2.5 PF "
                                 "(PQV_BRUTE_OP=f16), f32 157.3 TF (PQV_BRUTE_F16=0)",
                         "unit_note": "TFLOP/s reads Tera-op/s for the int8 form"}}
-    rec["parity"] = brute_f64_check(torch, corpus_t, queries_t, rows, dist, spread(nq, 32), k)
+    if check:
+        rec["parity"] = brute_f64_check(torch, corpus_t, queries_t, rows, dist, spread(nq, 32), k)
     rec["seconds"] = time.perf_counter() - t_all
     corpus.close()
     return rec
@@ -1761,7 +1783,7 @@ def bench_brute(args, pqv, torch, corpus, corpus_t, queries_t, n, dim, nq, rank,
     steps = args.steps if args.steps > 0 else 5
     outs = {}
     rec = brute_measure(args, pqv, torch, corpus_t.device, corpus_t.device.index or 0, args.workload, K, steps=steps,
-                        corpus_t=corpus_t, queries_t=queries_t, outputs=outs)
+                        corpus_t=corpus_t, queries_t=queries_t, outputs=outs, check=args.full)
     result = {
         "metric": "topk_queries_per_s_k10", "value": rec["value"], "unit": "queries/s",
         "n_gpus": 1, "steps": steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"],
@@ -1769,12 +1791,15 @@ def bench_brute(args, pqv, torch, corpus, corpus_t, queries_t, n, dim, nq, rank,
         "dtype": rec["dtype"], "data": "synthetic",
         "config": {"workload": rec["config"], "rows": n, "dim": dim, "k": K, "queries_per_step": nq, "shards": 1},
         "timed_region_s": rec["ms_per_step"] * steps * 1e-3,
-        "roofline": rec["roofline"], "parity": rec["parity"],
+        "roofline": rec["roofline"],
     }
     if args.dump_outputs:
         result["dump_outputs"] = dump_outputs(args.dump_outputs, outs)
-    rc = 0 if rec["parity"]["ok"] else 3
-    if not args.no_cpu:
+    rc = 0
+    if "parity" in rec:
+        result["parity"] = rec["parity"]
+        rc = 0 if rec["parity"]["ok"] else 3
+    if args.full and not args.no_cpu:
         # CPU column: f64 numpy brute force on a row slice (multithreaded BLAS), extrapolated linearly in rows
         q_host = queries_t.cpu().numpy()
         m = min(n, 200_000)

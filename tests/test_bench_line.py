@@ -131,3 +131,23 @@ def test_a_line_always_comes_out(bench, monkeypatch):
     monkeypatch.setattr(bench, "compact_line", lambda r: {"x": "y" * 20000})
     text = bench.line_text(full)
     assert len(text) < bench.LINE_CAP and json.loads(text)["config"]["workload"].startswith("c3")
+
+
+def test_plain_run_line_keeps_the_contract_without_the_full_sections(bench, monkeypatch):
+    """A run without --full records the set-up and the timed block only: its line still carries every contract key, and the
+    sections only --full measures are absent rather than empty -- also in the fallback line."""
+    full = _canned()
+    plain = {k: v for k, v in full.items() if k not in (
+        "roofline", "cpu_baseline", "single_query", "recall_at_k", "secondary_mixture", "configs", "configs_note", "counters",
+        "ms_per_step_serial", "hot_path_ms_per_step_serial", "candidates_per_query", "hbm_footprint")}
+    texts = [_dump(bench, plain)]
+    monkeypatch.setattr(bench, "compact_line", lambda r: (_ for _ in ()).throw(KeyError("boom")))
+    texts.append(bench.line_text(plain))
+    for text in texts:
+        line = json.loads(text)
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                    "dtype", "data", "config"):
+            assert key in line, key
+        assert line["value"] == pytest.approx(full["value"], rel=1e-5) and line["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+        for key in ("roofline", "cpu_baseline", "single_query", "recall_at_k", "configs", "secondary_mixture", "survivors_per_query"):
+            assert key not in line, key

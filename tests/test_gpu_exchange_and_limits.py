@@ -118,6 +118,32 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["config"]["shards"] == 2 and rec["value"] > 0
 
 
+@pytest.mark.timeout(600)
+def test_plain_bench_run_prints_the_headline_and_full_adds_the_rest(tmp_path):
+    """A plain run sets up, warms up, times the steps, dumps and prints the headline; roofline, single-query latency, recall
+    and the CPU baseline with its oracle parity leg come only with --full, and neither changes what the timed step returns."""
+    lines, dumps = {}, {}
+    for mode in ("plain", "full"):
+        out = tmp_path / mode
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "5",
+                            "--warmup", "2", "--dump-outputs", str(out)] + (["--full"] if mode == "full" else []),
+                           capture_output=True, text=True, cwd=ROOT, timeout=280)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines[mode] = _one_compact_line(p)
+        dumps[mode] = {name: np.load(out / (name + ".npy")) for name in ("distances", "rows", "n_found", "n_candidates")}
+    plain, full = lines["plain"], lines["full"]
+    for rec in (plain, full):
+        assert rec["metric"] == "topk_queries_per_s_k10" and rec["unit"] == "queries/s" and rec["higher_is_better"] is True
+        assert rec["dtype"] == "f32" and rec["steps"] == 5 and rec["warmup"] == 2 and rec["value"] > 0
+        assert rec["value"] == pytest.approx(64 * 1e3 / rec["ms_per_step"], rel=1e-4)
+    for key in ("roofline", "cpu_baseline", "single_query", "recall_at_k", "ms_per_step_serial"):
+        assert key not in plain, key
+        assert key in full, key
+    assert full["cpu_baseline"]["parity_ok"] is True and full["roofline"]["bound"] == "hbm"
+    for name, a in dumps["plain"].items():
+        assert np.array_equal(a.view(np.uint8), dumps["full"][name].view(np.uint8)), name
+
+
 def test_cpp_host_mirror_example_matches_the_oracle(oracle, tmp_path):
     """pq-vector_amd/host/pqv.hpp (the header-only C++ mirror of IndexBuilder / TopkBuilder over the C ABI) through its example
     program: the index it builds and the answers it prints must be the oracle's on the same data."""
@@ -147,7 +173,7 @@ def test_bench_c4_two_ranks_with_a_small_shard():
     exchange's share.  (No multi-GPU hardware has run this yet: the 1 -> 8 curve is the driver's to measure.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "c4",
-                        "--rows-per-rank", "1000000", "--steps", "5", "--warmup", "1", "--no-cpu"],
+                        "--rows-per-rank", "1000000", "--steps", "5", "--warmup", "1", "--no-cpu", "--full"],
                        capture_output=True, text=True, env=env, cwd=ROOT, timeout=570)
     assert p.returncode == 0, p.stderr[-2000:]
     rec = _one_compact_line(p)
@@ -215,7 +241,7 @@ def test_bench_c4_many_ranks_with_small_shards():
     w = SHARED_GPU_RANKS
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(w), "--backend", "gloo", "--workload", "c4",
-                        "--rows-per-rank", "250000", "--steps", "5", "--warmup", "1"],
+                        "--rows-per-rank", "250000", "--steps", "5", "--warmup", "1", "--full"],
                        capture_output=True, text=True, env=env, cwd=ROOT, timeout=870)
     assert p.returncode == 0, p.stderr[-3000:]
     rec = _one_compact_line(p)

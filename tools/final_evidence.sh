@@ -6,8 +6,8 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 tag=${1:-r03}; M=$R/gpurun_out/${tag}_multi; mkdir -p $M
 cd $R
-timeout 600 python bench.py --gpus 2 --backend gloo --workload c2 --no-cpu --steps 20 > $M/bench_c2_gpus2_gloo.json 2> $M/bench_c2_gpus2_gloo.err; echo "gpus2 gloo rc=$?"
-timeout 600 python bench.py --force-dist --workload c2 --no-cpu --steps 20 > $M/bench_c2_rccl_1rank.json 2> $M/bench_c2_rccl_1rank.err; echo "force-dist rc=$?"
+timeout 600 python bench.py --full --gpus 2 --backend gloo --workload c2 --no-cpu --steps 20 > $M/bench_c2_gpus2_gloo.json 2> $M/bench_c2_gpus2_gloo.err; echo "gpus2 gloo rc=$?"
+timeout 600 python bench.py --full --force-dist --workload c2 --no-cpu --steps 20 > $M/bench_c2_rccl_1rank.json 2> $M/bench_c2_rccl_1rank.err; echo "force-dist rc=$?"
 for f in $M/*.json; do python - $f <<'PY'
 import json, sys
 try:

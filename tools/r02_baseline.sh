@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 tag=${1:-r02a}; O=$R/gpurun_out/$tag; mkdir -p $O
 cd $R
-python bench.py --workload c3 --steps 20 --no-cpu 2>$O/c3.err | tail -1 > $O/bench_c3.json
-python bench.py --workload c3 --steps 20 --no-cpu --streams 1 2>$O/c3s.err | tail -1 > $O/bench_c3_serial.json
+python bench.py --full --workload c3 --steps 20 --no-cpu 2>$O/c3.err | tail -1 > $O/bench_c3.json
+python bench.py --full --workload c3 --steps 20 --no-cpu --streams 1 2>$O/c3s.err | tail -1 > $O/bench_c3_serial.json
 PQV_LIB_PATH=$R/pq-vector_amd/libpqv_hip_phases.so PQV_PHASES_OUT=$O/phases_c3.bin python bench.py --workload c3 --steps 1 --warmup 1 --no-cpu --streams 1 --no-timing > /dev/null 2>$O/ph.err
 python tools/phase_timeline.py $O/phases_c3.bin > $O/phases_c3.txt 2>&1; rm -f $O/phases_c3.bin
 cd /tmp

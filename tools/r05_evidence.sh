@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; E=$R/gpurun_out/r05_ev; mkdir -p $E; cd $R
 tag=${1:-a}
 python -m pytest tests -q -m gpu > $E/gpu_tests_$tag.log 2>&1; tail -2 $E/gpu_tests_$tag.log
-python bench.py > $E/bench_default_line_$tag.json 2> $E/bench_default_line_$tag.err; echo "bench rc=$?"
+python bench.py --full > $E/bench_default_line_$tag.json 2> $E/bench_default_line_$tag.err; echo "bench rc=$?"
 python bench.py --from-parquet > $E/bench_from_parquet_$tag.json 2>/dev/null; echo "from-parquet rc=$?"
 python bench.py --gpus 2 --backend gloo --from-parquet --rows-per-rank 1000000 --steps 10 --warmup 2 --parity-queries 64 > $E/bench_from_parquet_2ranks_$tag.json 2>/dev/null; echo "sharded from-parquet rc=$?"
 bash tools/profile_round.sh r05 c3 > /dev/null 2>&1

@@ -5,12 +5,12 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; E=$R/gpurun_out/r06_ev; mkdir -p $E; cd $R
 tag=${1:-a}
 python -m pytest tests -q -m gpu > $E/gpu_tests_$tag.log 2>&1; tail -2 $E/gpu_tests_$tag.log
-python bench.py > $E/bench_default_line_$tag.json 2> $E/bench_default_line_$tag.err; echo "bench rc=$? bytes=$(wc -c < $E/bench_default_line_$tag.json)"
+python bench.py --full > $E/bench_default_line_$tag.json 2> $E/bench_default_line_$tag.err; echo "bench rc=$? bytes=$(wc -c < $E/bench_default_line_$tag.json)"
 cp bench_full.json $E/bench_default_full_$tag.json
 python bench.py --from-parquet > $E/bench_from_parquet_$tag.json 2>/dev/null; echo "from-parquet rc=$?"
 python bench.py --gpus 2 --backend gloo --from-parquet --rows-per-rank 1000000 --steps 10 --warmup 2 --parity-queries 64 > $E/bench_from_parquet_2ranks_$tag.json 2>/dev/null; echo "2-rank from-parquet rc=$?"
 python bench.py --gpus 8 --backend gloo --from-parquet --rows-per-rank 250000 --steps 5 --warmup 1 --parity-queries 64 > $E/bench_from_parquet_8ranks_$tag.json 2>/dev/null; echo "8-rank from-parquet rc=$?"
-python bench.py --gpus 8 --backend gloo --workload c4 --rows-per-rank 500000 --steps 5 --warmup 1 > $E/bench_c4_8ranks_small_$tag.json 2>/dev/null; echo "8-rank c4 rc=$?"
+python bench.py --full --gpus 8 --backend gloo --workload c4 --rows-per-rank 500000 --steps 5 --warmup 1 > $E/bench_c4_8ranks_small_$tag.json 2>/dev/null; echo "8-rank c4 rc=$?"
 bash tools/profile_round.sh r06 c3 > /dev/null 2>&1
 bash tools/profile_round.sh r06mix c3 --data mixture > /dev/null 2>&1
 bash tools/profile_round.sh r06 c5 > /dev/null 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/single_sweep.sh "ENV=VAL ..."...: C3 single-query p50 / p99 per environment setting (one searcher per run)
 for envs in "$@"; do
-  env $envs python bench.py --no-cpu --no-secondary --no-configs --recall 0 --parity-queries 0 --steps 5 --single 300 > /dev/null 2>&1
+  env $envs python bench.py --full --no-cpu --no-secondary --no-configs --recall 0 --parity-queries 0 --steps 5 --single 300 > /dev/null 2>&1
   python -c "
 import json
 s = json.load(open('bench_full.json'))['single_query']

@@ -5,7 +5,7 @@ out=$1; shift
 args=(); while [ "$1" != "--" ] && [ $# -gt 0 ]; do args+=("$1"); shift; done; shift
 : > $out
 for e in "$@"; do
-  line=$(env $e python bench.py "${args[@]}" --no-cpu 2>/dev/null | tail -1)
+  line=$(env $e python bench.py --full "${args[@]}" --no-cpu 2>/dev/null | tail -1)
   python - "$e" "$line" >> $out <<'PY'
 import json, sys
 e, line = sys.argv[1], sys.argv[2]
