@@ -379,14 +379,19 @@ pub struct TableSearcher<'c> {
 
 impl<'c> TableSearcher<'c> {
     pub fn new(indexes: &[&Index], row_base: &[u64], corpus: &'c mut Corpus) -> Result<Self> {
+        Self::with_flags(indexes, row_base, corpus, sys::PQV_LAYOUT_IVF_ORDERED)
+    }
+
+    /// As [`TableSearcher::new`] with creation flags: `sys::PQV_TABLE_CAP_ROUND_ROBIN` makes `max_candidates` the reference's
+    /// round-robin cap over the files (`VectorTopKOptions::max_candidates`, exec.rs:207-245) instead of an error.
+    pub fn with_flags(indexes: &[&Index], row_base: &[u64], corpus: &'c mut Corpus, flags: u32) -> Result<Self> {
         if indexes.len() != row_base.len() {
             return Err("row_base needs one entry per indexed file".into());
         }
         let mut ptrs: Vec<*const sys::PqvIndex> = indexes.iter().map(|i| i.raw as *const sys::PqvIndex).collect();
         let mut raw = ptr::null_mut();
         check(unsafe {
-            sys::pqv_table_searcher_create(ptrs.as_mut_ptr(), ptrs.len() as u32, row_base.as_ptr(), corpus.raw,
-                                           sys::PQV_LAYOUT_IVF_ORDERED, &mut raw)
+            sys::pqv_table_searcher_create(ptrs.as_mut_ptr(), ptrs.len() as u32, row_base.as_ptr(), corpus.raw, flags, &mut raw)
         })?;
         let n_rows = indexes.iter().map(|i| unsafe { sys::pqv_index_n_rows(i.raw) }).collect();
         Ok(Self { inner: Searcher { raw, _corpus: std::marker::PhantomData }, row_base: row_base.to_vec(), n_rows })
@@ -399,6 +404,14 @@ impl<'c> TableSearcher<'c> {
         let local = r - self.row_base[f];
         if row == u32::MAX || local >= self.n_rows[f] { None } else { Some((f, local as u32)) }
     }
+}
+
+/// What `CandidateCursor::next_batch(max_candidates)` of a fresh cursor takes from each file (access.rs:214-242), from the
+/// files' candidate counts alone; `max_candidates == 0`: no cap.  The quotas of a round-robin capped [`TableSearcher`].
+pub fn round_robin_quota(counts: &[u64], max_candidates: u64) -> Result<Vec<u64>> {
+    let mut quota = vec![0u64; counts.len()];
+    check(unsafe { sys::pqv_round_robin_quota(counts.as_ptr(), u32::try_from(counts.len())?, max_candidates, quota.as_mut_ptr()) })?;
+    Ok(quota)
 }
 
 impl<'c> std::ops::Deref for TableSearcher<'c> {

@@ -64,6 +64,8 @@ typedef enum pqv_metric {
 #define PQV_RELEASE_IF_COPIED    0x4u /* with IVF_ORDERED: drop the row-order copy only where the searcher made a list-ordered
                                          f32 copy of its own (the images-only layout keeps reading the caller's rows): one f32
                                          copy of the column resident either way                                              */
+#define PQV_TABLE_CAP_ROUND_ROBIN 0x8u /* pqv_table_searcher_create: max_candidates is dealt out round robin over the files
+                                          (see there); ignored by pqv_searcher_create                                         */
 
 typedef struct pqv_index    pqv_index;    /* IvfIndex: dim, n_clusters, centroids, inverted lists */
 typedef struct pqv_corpus   pqv_corpus;   /* the embedding column, resident in one GPU's HBM     */
@@ -203,12 +205,21 @@ void pqv_searcher_free(pqv_searcher *searcher);
  * find_closest_centroids, reported as global list ids cluster_base[f] + c, file after file (P = the sum of those counts).  The
  * candidate sequence is file 0's candidate_rows, then file 1's, ... with rows shifted by row_base; top-k orders by (distance,
  * position in that sequence), as per-file searches merged with pqv_merge_topk.  Row ranges must increase without overlapping
- * and lie inside the corpus; all dims are equal.  max_candidates > 0 returns PQV_ERR_UNSUPPORTED on a table (per-file caps:
- * pqv_candidate_cursor over per-file searchers, then pqv_merge_topk); P > 1024: as min(nprobe, n_clusters) > 1024 today. */
+ * and lie inside the corpus; all dims are equal.  P > 1024: as min(nprobe, n_clusters) > 1024 today.
+ * max_candidates > 0 returns PQV_ERR_UNSUPPORTED on a table created without PQV_TABLE_CAP_ROUND_ROBIN.  With that flag the cap is
+ * the reference's (exec.rs:207-245): file f of a query considers the first t_f of its c_f candidates, t_f being what
+ * CandidateCursor::next_batch(max_candidates) of a fresh cursor over the files (access.rs:214-242, file 0 first) takes from it --
+ * pqv_round_robin_quota.  Positions in the file-major sequence and the (distance, position) order stay as they are; only the
+ * considered set shrinks.  n_candidates stays the count before the cap; embeddings_fetched advances by min(max_candidates, total).
+ * On a one-file table the cap is a prefix, as on an ordinary searcher. */
 int pqv_table_searcher_create(const pqv_index *const *indexes, uint32_t n_files, const uint64_t *row_base,
                               pqv_corpus *corpus, uint32_t flags, pqv_searcher **out);
 /* 1 for ordinary searchers; row_base / cluster_base (each [n_files], may be NULL) for tables. */
 int pqv_searcher_files(const pqv_searcher *searcher, uint32_t *n_files, uint64_t *row_base, uint32_t *cluster_base);
+/* Host only: quota[f] = the candidates CandidateCursor::next_batch(max_candidates) of a fresh cursor takes from file f, whose
+ * candidate count is counts[f] (access.rs:214-242); max_candidates == 0: no cap (quota = counts).  The per-file quotas of a
+ * PQV_TABLE_CAP_ROUND_ROBIN table, for hosts that build their own access plans. */
+int pqv_round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max_candidates, uint64_t *quota);
 
 /* Tunables of one searcher (all optional; the defaults are the measured dispatch rules of DESIGN.md 5 / DESIGN_HISTORY.md 5.1c-f).
  * The reference has no such knobs -- its topk() is one fixed loop (src/ivf/search.rs:112-127) -- so nothing here

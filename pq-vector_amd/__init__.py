@@ -13,20 +13,21 @@ Host-side mirror of the reference's Rust API over the C ABI of include/pqv.h:
     (no counterpart: range search)           RangeBuilder(searcher, query).radius(r).nprobe(n).search()
     index scan over a table of files         TableTopkBuilder(paths, query).k(k).nprobe(n).search()
       (df_vector/index_exec.rs:85-164)         -> [TableSearchResult(path, row_idx, distance)]
+    VectorTopKOptions{max_candidates: Some(m)} TableTopkBuilder(...).max_candidates(m) (round robin over the files)
 
 (src/ivf/parquet.rs:23-103, src/ivf/search.rs:41-81).  All compute runs in the HIP kernels
 behind libpqv_hip.so; importing this package without the built library fails loudly.
 """
 from .api import (CandidateCursor, Corpus, Index, IndexBuilder, PqvError, RangeBuilder, Searcher, SearchResult, TopkBuilder,
                   TableRangeBuilder, TableSearcher, TableSearchResult, TableTopkBuilder, device_count, merge_topk, rerank_batch,
-                  rerank_finish, searcher_for_parquet, searcher_for_parquet_files, split_table_rows)
+                  rerank_finish, round_robin_quota, searcher_for_parquet, searcher_for_parquet_files, split_table_rows)
 from .parquet_io import has_pq_vector_index, read_index_from_parquet
 from ._ffi import (PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE, PQV_L2SQ_MFMA, PQV_LAYOUT_IVF_ORDERED, PQV_LAYOUT_ROW_ORDER,
-                   PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, LIB_PATH)
+                   PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, LIB_PATH)
 
 __all__ = ["CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
            "TopkBuilder", "TableRangeBuilder", "TableSearcher", "TableSearchResult", "TableTopkBuilder", "searcher_for_parquet_files",
            "split_table_rows", "device_count", "merge_topk", "rerank_batch", "rerank_finish", "searcher_for_parquet", "PQV_COSINE", "PQV_L2SQ_MFMA",
            "has_pq_vector_index", "read_index_from_parquet", "PQV_L2SQ_REF4",
            "PQV_L2SQ_SEQ", "PQV_LAYOUT_IVF_ORDERED", "PQV_LAYOUT_ROW_ORDER",
-           "PQV_RELEASE_ROW_ORDER", "PQV_RELEASE_IF_COPIED", "LIB_PATH"]
+           "PQV_RELEASE_ROW_ORDER", "PQV_RELEASE_IF_COPIED", "PQV_TABLE_CAP_ROUND_ROBIN", "round_robin_quota", "LIB_PATH"]

@@ -34,6 +34,7 @@ PQV_LAYOUT_IVF_ORDERED = 0x0
 PQV_LAYOUT_ROW_ORDER = 0x1
 PQV_RELEASE_ROW_ORDER = 0x2
 PQV_RELEASE_IF_COPIED = 0x4
+PQV_TABLE_CAP_ROUND_ROBIN = 0x8      # pqv_table_searcher_create: max_candidates dealt out round robin over the files
 
 
 class Counters(C.Structure):
@@ -107,6 +108,7 @@ SIGNATURES = {
     "pqv_searcher_free": (None, [vp]),
     "pqv_table_searcher_create": (C.c_int, [C.POINTER(vp), C.c_uint32, u64p, vp, C.c_uint32, C.POINTER(vp)]),
     "pqv_searcher_files": (C.c_int, [vp, u32p, u64p, u32p]),
+    "pqv_round_robin_quota": (C.c_int, [u64p, C.c_uint32, C.c_uint64, u64p]),
     "pqv_probe": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, u32p, u32p]),
     "pqv_candidate_rows": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, C.POINTER(u32p), u64p]),
     "pqv_rows_free": (None, [u32p]),

@@ -694,8 +694,9 @@ def _table_args(indexes, corpus, row_base):
 class TableSearcher(Searcher):
     """Several indexed files searched as ONE table on one GPU: file f's rows are corpus rows [row_base[f], row_base[f] + its
     rows).  nprobe counts per file; probe() returns the P = sum_f min(nprobe, kc_f) global list ids, file after file; rows
-    come back as corpus rows (split_rows maps them to (file, local row)).  max_candidates > 0 is not supported: cap per file
-    with CandidateCursor over per-file Searchers and merge_topk."""
+    come back as corpus rows (split_rows maps them to (file, local row)).  max_candidates > 0 needs
+    flags |= PQV_TABLE_CAP_ROUND_ROBIN: file f then considers the first round_robin_quota(its candidate counts, max_candidates)[f]
+    of its candidates, as the reference's CandidateCursor deals them; without the flag it is refused (PQV_ERR_UNSUPPORTED)."""
 
     def __init__(self, indexes, corpus, row_base, flags=_ffi.PQV_LAYOUT_IVF_ORDERED):
         indexes, rb = _table_args(indexes, corpus, row_base)
@@ -742,12 +743,31 @@ def split_table_rows(rows, row_base, n_rows=None):
     return np.where(ok, f, -1), np.where(ok, local, 0xFFFFFFFF).astype(np.uint32)
 
 
+def round_robin_quota(counts, max_candidates):
+    """What CandidateCursor::next_batch(max_candidates) of a fresh cursor takes from each file (access.rs:214-242), given the
+    files' candidate counts: u64 [n_files].  max_candidates == 0: no cap (the counts themselves)."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    out = np.zeros(max(1, c.size), dtype=np.uint64)
+    _check(_ffi.lib().pqv_round_robin_quota(c.ctypes.data_as(u64p), c.size, int(max_candidates), out.ctypes.data_as(u64p)))
+    return out[:c.size]
+
+
+def _max_candidates_arg(n):
+    """A builder's max_candidates: an integer in [1, 2^64) (VectorTopKOptions::max_candidates; None there = no cap)."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"max_candidates must be an integer, got {type(n).__name__}")
+    if not 0 < int(n) < (1 << 64):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"max_candidates must be in [1, 2^64), got {int(n)}")
+    return int(n)
+
+
 _TABLE_SEARCHERS = {}
 
 
-def searcher_for_parquet_files(paths, device=0):
+def searcher_for_parquet_files(paths, device=0, round_robin_cap=False):
     """A TableSearcher over indexed Parquet files: every file's index blob and embedding column, the columns loaded one after
-    the other into ONE resident corpus.  Cached per (files, sizes, mtimes, device) as searcher_for_parquet is."""
+    the other into ONE resident corpus.  Cached per (files, sizes, mtimes, device, round_robin_cap) as searcher_for_parquet is.
+    round_robin_cap: created with PQV_TABLE_CAP_ROUND_ROBIN (max_candidates allowed, dealt out round robin over the files)."""
     import os
     from . import parquet_io
     if isinstance(paths, (str, bytes, os.PathLike)):
@@ -762,7 +782,7 @@ def searcher_for_parquet_files(paths, device=0):
         if real is None:
             real = _REALPATHS.setdefault(p, os.path.realpath(p))
         key.append((real, st.st_size, st.st_mtime_ns))
-    key = (tuple(key), device)
+    key = (tuple(key), device, bool(round_robin_cap))
     hit = _TABLE_SEARCHERS.get(key)
     if hit is None:
         import pyarrow.parquet as pq
@@ -782,7 +802,10 @@ def searcher_for_parquet_files(paths, device=0):
             for p, (_, column), b in zip(paths, parts, row_base):
                 parquet_io.load_embedding_column(p, column, device, into=corpus, row_offset=int(b))
             corpus.finish(total)
-            hit = TableSearcher(indexes, corpus, row_base, _ffi.PQV_LAYOUT_IVF_ORDERED | _ffi.PQV_RELEASE_IF_COPIED)
+            flags = _ffi.PQV_LAYOUT_IVF_ORDERED | _ffi.PQV_RELEASE_IF_COPIED
+            if round_robin_cap:
+                flags |= _ffi.PQV_TABLE_CAP_ROUND_ROBIN
+            hit = TableSearcher(indexes, corpus, row_base, flags)
         except Exception:
             corpus.close()
             raise
@@ -809,38 +832,50 @@ def _table_results(searcher, paths, rows, dist):
 
 class TableTopkBuilder(TopkBuilder):
     """TopkBuilder over a table of indexed Parquet files (searched as one TableSearcher; nprobe per file).  search() returns
-    [TableSearchResult(path, row_idx, distance)] -- the (path, row id, distance) columns of the reference's index scan."""
+    [TableSearchResult(path, row_idx, distance)] -- the (path, row id, distance) columns of the reference's index scan.
+    max_candidates(n): VectorTopKOptions::max_candidates -- n candidates dealt out round robin over the files (exec.rs:207-245)."""
 
     def __init__(self, paths, query, device=0):
         self._paths = _table_paths(paths)
+        self._max_candidates = 0
         super().__init__(None, query, device)
+
+    def max_candidates(self, n):
+        self._max_candidates = _max_candidates_arg(n)
+        return self
 
     def search(self):
         if self._k is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "k must be set")
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
-        s = searcher_for_parquet_files(self._paths, self._device)
-        rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe)
+        s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
+        rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, max_candidates=self._max_candidates)
         n = int(nf[0])
         return _table_results(s, self._paths, rows[0, :n], dist[0, :n])
 
 
 class TableRangeBuilder(RangeBuilder):
-    """RangeBuilder over a table of indexed Parquet files; search() returns [TableSearchResult], nearest first."""
+    """RangeBuilder over a table of indexed Parquet files; search() returns [TableSearchResult], nearest first.
+    max_candidates(n): as TableTopkBuilder's."""
 
     def __init__(self, paths, query, device=0):
         self._paths = _table_paths(paths)
+        self._max_candidates = 0
         super().__init__(None, query, device)
+
+    def max_candidates(self, n):
+        self._max_candidates = _max_candidates_arg(n)
+        return self
 
     def search(self):
         if self._radius is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "radius must be set")
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
-        s = searcher_for_parquet_files(self._paths, self._device)
+        s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
         _, rows, dist, _, _ = s.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
-                                             max_results=self._max_results)
+                                             max_candidates=self._max_candidates, max_results=self._max_results)
         return _table_results(s, self._paths, rows, dist)
 
 

@@ -316,7 +316,8 @@ struct Scratch {
     DevBuf s_probe_keys, s_probe_vals, s_probe, s_cand_base, s_ncand, s_part_keys, s_part_vals, s_queries, s_rows,
         s_dist, s_nfound, s_pair_u32, s_pairs, s_groups, s_quads, s_items, s_ticket, s_ticket2, s_cand_keys, s_cand_vals, s_cand_cnt, s_spilled,
         s_seed_ub, s_qblk, s_gthr, s_tie, s_replay, s_qnorm, s_qmax, s_thr_hist, s_thr_bins, s_qi8, s_qn2i, s_qres, s_qresu, s_pair_lb, s_part_flags, s_qpad, s_cand_lb, s_pendv, s_work, s_nwork, s_out,
-        s_hit_cnt, s_hit_keys, s_hit_vals, s_alt_keys, s_alt_vals, s_rsegs, s_rout_off, s_rout_rows, s_rout_dist;   // s_hit_* .. s_rout_*: pqv_range_search
+        s_hit_cnt, s_hit_keys, s_hit_vals, s_alt_keys, s_alt_vals, s_rsegs, s_rout_off, s_rout_rows, s_rout_dist,   // s_hit_* .. s_rout_*: pqv_range_search
+        s_pair_end, s_file_cnt;     // round-robin capped tables: per-pair candidate ends, per-file counts (SegProbeArgs)
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -436,6 +437,7 @@ struct pqv_searcher {
     std::vector<uint32_t> seg_off;         // [n_files + 1]
     std::vector<uint64_t> row_base;        // [n_files]
     uint32_t seg_max_kc = 0;               // largest file centroid count
+    bool rr_cap = false;                   // PQV_TABLE_CAP_ROUND_ROBIN: max_candidates is dealt out round robin over the files
     DevBuf d_seg_off, d_seg_off64;         // seg_off on the device: u32 (merge_probe_seg_kernel), u64 (the per-file stream_kernel probe)
     mutable pqv_counters_t counters{};
     // timing
@@ -2852,6 +2854,7 @@ static int pqv_table_searcher_create_impl(const pqv_index *const *indexes, uint3
     s->seg_off = std::move(seg_off);
     s->row_base.assign(row_base, row_base + n_files);
     s->seg_max_kc = seg_max;
+    s->rr_cap = (flags & PQV_TABLE_CAP_ROUND_ROBIN) != 0;
     const std::vector<uint64_t> seg_off64(s->seg_off.begin(), s->seg_off.end());
     hipError_t e = s->d_seg_off.alloc(s->seg_off.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = s->d_seg_off64.alloc(seg_off64.size() * sizeof(uint64_t));
@@ -2879,6 +2882,42 @@ extern "C" int pqv_searcher_files(const pqv_searcher *s, uint32_t *n_files, uint
     return PQV_OK;
 }
 
+// CandidateCursor::next_batch(max_candidates) of a fresh cursor over files with counts[f] candidates (access.rs:214-242), as
+// per-file tallies in closed form: L = the largest level with S(L) = sum_f min(counts[f], L) <= max_candidates, every file keeps
+// min(counts[f], L), and the first max_candidates - S(L) files with more than L candidates one more.  max_candidates == 0 or
+// >= the total: no cap.  merge_probe_seg_kernel (table_quota) computes the same numbers on the device.
+static void round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max_candidates, uint64_t *quota) {
+    // S(L), saturating at 2^64 - 1 (it is only compared with max_candidates)
+    auto level_sum = [&](uint64_t L) {
+        uint64_t sum = 0;
+        for (uint32_t f = 0; f < n_files; ++f) {
+            const uint64_t v = std::min(counts[f], L);
+            sum = sum + v < sum ? ~0ull : sum + v;
+        }
+        return sum;
+    };
+    const uint64_t max_c = n_files ? *std::max_element(counts, counts + n_files) : 0;
+    if (max_candidates == 0 || level_sum(max_c) <= max_candidates) {
+        std::copy(counts, counts + n_files, quota);
+        return;
+    }
+    uint64_t lo = 0, hi = max_c, s_lo = 0;      // S(lo) <= M < S(hi)
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2, sm = level_sum(mid);
+        if (sm <= max_candidates) { lo = mid; s_lo = sm; } else hi = mid;
+    }
+    uint64_t rem = max_candidates - s_lo;
+    for (uint32_t f = 0; f < n_files; ++f) {
+        quota[f] = std::min(counts[f], lo);
+        if (counts[f] > lo && rem) { quota[f] += 1; --rem; }
+    }
+}
+extern "C" int pqv_round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max_candidates, uint64_t *quota) {
+    if (n_files == 0) return PQV_OK;
+    if (!counts || !quota) return fail(PQV_ERR_INVALID, "counts/quota must not be NULL");
+    return guard([&] { round_robin_quota(counts, n_files, max_candidates, quota); return PQV_OK; });
+}
+
 extern "C" void pqv_searcher_free(pqv_searcher *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -2893,6 +2932,28 @@ uint32_t probe_count(const pqv_searcher *s, uint32_t nprobe) {
     uint64_t P = 0;
     for (uint32_t f = 0; f < s->n_files; ++f) P += std::min<uint32_t>(nprobe, s->seg_off[f + 1] - s->seg_off[f]);
     return static_cast<uint32_t>(std::min<uint64_t>(P, 0xFFFFFFFFull));
+}
+
+// a round-robin capped table on the host: the end of candidates of each of a query's P probed lists (clusters, file after file:
+// min(nprobe, kc_f) of file f), as merge_probe_seg_kernel writes them to SegProbeArgs::pair_end
+void table_pair_ends(const pqv_searcher *s, const std::vector<uint32_t> &clusters, uint32_t nprobe, uint64_t max_candidates,
+                     std::vector<uint64_t> &end) {
+    const uint32_t F = s->n_files;
+    std::vector<uint64_t> cnt(F, 0), quota(F);
+    size_t j = 0;
+    for (uint32_t f = 0; f < F; ++f) {
+        const uint32_t kf = std::min<uint32_t>(nprobe, s->seg_off[f + 1] - s->seg_off[f]);
+        for (uint32_t i = 0; i < kf && j < clusters.size(); ++i, ++j) cnt[f] += s->h_list_off[clusters[j] + 1] - s->h_list_off[clusters[j]];
+    }
+    round_robin_quota(cnt.data(), F, max_candidates, quota.data());
+    end.assign(clusters.size(), 0);
+    uint64_t fb = 0;
+    j = 0;
+    for (uint32_t f = 0; f < F; ++f) {
+        const uint32_t kf = std::min<uint32_t>(nprobe, s->seg_off[f + 1] - s->seg_off[f]);
+        for (uint32_t i = 0; i < kf && j < clusters.size(); ++i, ++j) end[j] = fb + quota[f];
+        fb += cnt[f];
+    }
 }
 
 struct TopkPlan {
@@ -3130,19 +3191,24 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     return p;
 }
 
-// tables: the per-file cap of the reference (access.rs:214-242) is not one prefix of the file-major candidate sequence
+// tables: the per-file cap of the reference (access.rs:214-242) is not one prefix of the file-major candidate sequence -- a
+// table applies it only when created with PQV_TABLE_CAP_ROUND_ROBIN
 int table_max_candidates(const pqv_searcher *s, uint64_t max_candidates) {
-    if (s->n_files && max_candidates)
+    if (s->n_files && max_candidates && !s->rr_cap)
         return fail(PQV_ERR_UNSUPPORTED, "max_candidates > 0 is not supported on a table searcher: cap per file with "
                                          "pqv_candidate_cursor over per-file searchers and merge their results");
     return PQV_OK;
 }
+// the kernels take per-pair candidate ends (SegProbeArgs::pair_end) instead of one cap
+bool table_rr(const pqv_searcher *s, uint64_t max_candidates) { return s->n_files && s->rr_cap && max_candidates; }
+
 // Table searchers: the batched probe over the combined centroid table (probe_rows_kernel, or stream_kernel with one list per
 // file) and the probe merge per file segment (merge_probe_seg_kernel).  pm: the probe merge's arguments as the caller fills them
 // for launch_merge_probe (k = p.np = P); pm.part_keys / part_vals are the probe scratch.  sc.s_probe / s_cand_base must hold
 // nq * max(P, n_files) entries (the stream route reads its per-file arguments from them before the merge overwrites them).
+// With the round-robin cap (table_rr) the merge also writes sc.s_pair_end [nq * P]: every list's end of candidates, its file's quota.
 int enqueue_table_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, const float *d_queries, uint32_t nq, uint32_t nprobe,
-                        uint32_t *zero_u32, uint32_t zero_n, const pqv::MergeArgs &pm, hipStream_t stream) {
+                        uint32_t *zero_u32, uint32_t zero_n, const pqv::MergeArgs &pm, hipStream_t stream, uint64_t max_candidates = 0) {
     using namespace pqv;
     if (p.probe_rows) {
         ProbeRowsArgs pr{};
@@ -3168,6 +3234,11 @@ int enqueue_table_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, c
     g.seg_off = s->d_seg_off.as<uint32_t>(); g.n_files = s->n_files; g.nprobe = nprobe;
     g.kmax = std::min<uint32_t>(nprobe, s->seg_max_kc);
     g.stream_parts = p.probe_rows ? 0u : p.probe_bpl * waves_per_block();
+    if (table_rr(s, max_candidates)) {
+        HIP_TRY(sc.s_pair_end.ensure(std::max<size_t>(1, static_cast<size_t>(nq) * p.np) * sizeof(uint64_t)));
+        HIP_TRY(sc.s_file_cnt.ensure(static_cast<size_t>(nq) * s->n_files * sizeof(uint32_t)));
+        g.max_cand = max_candidates; g.pair_end = sc.s_pair_end.as<uint64_t>(); g.file_cnt = sc.s_file_cnt.as<uint32_t>();
+    }
     HIP_TRY(launch_merge_probe_seg(pm, g, stream));
     return PQV_OK;
 }
@@ -3320,10 +3391,11 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         quant_done = pq_args.n_pairs != 0;
         HIP_TRY(pqv::launch_probe_single(pr, pm, sc.s_ticket.as<uint32_t>(), quant_done ? &pq_args : nullptr, stream));
     } else if (s->n_files) {
-        if (int rc = enqueue_table_probe(s, sc, p, d_queries, nq, nprobe, pa.zero_u32, pa.zero_n, pm, stream)) return rc;
+        if (int rc = enqueue_table_probe(s, sc, p, d_queries, nq, nprobe, pa.zero_u32, pa.zero_n, pm, stream, max_candidates)) return rc;
     } else {
         HIP_TRY(launch_merge_probe(pm, stream));
     }
+    const uint64_t *pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
 
     // 2. candidate re-rank + per-wave top-k
     bool use_cand = false;     // wide screened path: the final merge also reads the candidate buffers
@@ -3380,7 +3452,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         ta.pairs = ps.pairs; ta.groups = ps.groups; ta.n_groups = ps.n_groups; ta.max_groups = p.max_groups;
         ta.nq = nq; ta.nprobe = p.np; ta.dim = s->sdim; ta.k = k;
         ta.quads = ps.quads; ta.n_quads = ps.n_quads; ta.max_quads = p.max_quads; ta.quad_width = p.quad_width;
-        ta.rows_per_block = p.rr_rows_per_block; ta.blocks_per_list = p.rr_bpl; ta.max_pos = max_pos;
+        ta.rows_per_block = p.rr_rows_per_block; ta.blocks_per_list = p.rr_bpl; ta.max_pos = max_pos; ta.pair_end = pair_end;
         ta.slots_per_pair = p.slots_per_pair; ta.slot_base = 0; ta.n_part = p.n_part_rr;
         ta.gthr = sc.s_gthr.as<unsigned long long>();
         ta.part_keys = sc.s_part_keys.as<uint64_t>(); ta.part_vals = sc.s_part_vals.as<uint32_t>();
@@ -3467,6 +3539,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
                 rf.mat = s->d_mat; rf.row_of = s->d_row_of; rf.queries = d_queries_s; rf.list_off = s->d_list_off.as<uint64_t>();
                 rf.probe = sc.s_probe.as<uint32_t>(); rf.cand_base = sc.s_cand_base.as<uint64_t>();
                 rf.dim = s->sdim; rf.nprobe = p.np; rf.seed_sw = seed.seed_sw; rf.seed_rows = p.seed_rows; rf.max_pos = max_pos;
+                rf.pair_end = pair_end;
             }
             // one query: the seed kernel's last block selects (SeedTail); otherwise a launch of its own
             const bool seed_tail = nq == 1 && k <= 256 && s->opt.single_bucket > 0;
@@ -3548,7 +3621,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     ra.probe = sc.s_probe.as<uint32_t>(); ra.cand_base = sc.s_cand_base.as<uint64_t>();
     ra.queries = d_queries_s; ra.nq = nq; ra.nprobe = p.np; ra.dim = s->sdim; ra.k = k;
     ra.rows_per_block = p.rr_rows_per_block; ra.blocks_per_list = p.rr_bpl;
-    ra.max_pos = max_pos; ra.metric = metric;
+    ra.max_pos = max_pos; ra.pair_end = pair_end; ra.metric = metric;
     ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
     if (!p.tile) {
         if (timing) HIP_TRY(hipEventRecord(e1, stream));
@@ -3642,10 +3715,11 @@ inline void heap_pop(std::vector<HeapEnt> &h) {
 // Recompute one query's candidate distances on the device (STREAM_DIST), then replay them
 // through the heap in candidate order.  d_probe / d_cand_base: the query's probe list on the device; `clusters` the
 // same list on the host.  Any k (the selection is the heap's), any nprobe (the grid is cut into slices of probed lists).
+// A round-robin capped table (table_rr) replays each list up to its file's quota (table_pair_ends; `nprobe` is read there only).
 int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_query, const uint32_t *d_probe,
                          const uint64_t *d_cand_base, const std::vector<uint32_t> &clusters, uint32_t k,
                          uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                         uint32_t *n_found) {
+                         uint32_t *n_found, uint32_t nprobe = 0) {
     using namespace pqv;
     const uint32_t np = static_cast<uint32_t>(clusters.size());
     uint64_t total = 0;
@@ -3670,12 +3744,17 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
     }
     std::vector<HeapEnt> heap;
     heap.reserve(static_cast<size_t>(std::min<uint64_t>(k, use)) + 1);
-    uint64_t pos = 0;
+    std::vector<uint64_t> pair_end;
+    if (table_rr(s, max_candidates)) table_pair_ends(s, clusters, nprobe, max_candidates, pair_end);
+    uint64_t base = 0;
     const std::vector<uint32_t> *h_rows = s->h_rows->get();             // (the index' host lists: downloaded by the first call that reads them)
     if (!h_rows) return PQV_ERR_HIP;
-    for (uint32_t c : clusters) {                                        // candidate_rows order
-        const uint64_t b = s->h_list_off[c], e = s->h_list_off[c + 1];
-        for (uint64_t i = b; i < e && pos < use; ++i, ++pos) {
+    for (size_t j = 0; j < clusters.size(); ++j) {                      // candidate_rows order
+        const uint32_t c = clusters[j];
+        const uint64_t b = s->h_list_off[c], e = s->h_list_off[c + 1], lim = pair_end.empty() ? use : pair_end[j];
+        uint64_t pos = base;
+        base += e - b;
+        for (uint64_t i = b; i < e && pos < lim; ++i, ++pos) {
             const HeapEnt ent{d[pos], (*h_rows)[i]};
             if (heap.size() < k) heap_push(heap, ent);                   // search.rs:119-120
             else if (ent.d < heap[0].d) { heap_pop(heap); heap_push(heap, ent); }   // :121-125
@@ -3694,14 +3773,14 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
 // qi indexes the current sub-batch's probe scratch (written by the probe merge).
 int replay_query_exact(const pqv_searcher *s, Scratch &sc, const float *d_query, uint32_t qi, uint32_t np, uint32_t k,
                        uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                       uint32_t *n_found) {
+                       uint32_t *n_found, uint32_t nprobe) {
     std::vector<uint32_t> clusters(np);
     HIP_TRY(hipMemcpyAsync(clusters.data(), sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * np,
                            np * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return replay_with_clusters(s, sc, d_query, sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * np,
                                 sc.s_cand_base.as<uint64_t>() + static_cast<size_t>(qi) * np, clusters, k, max_candidates,
-                                metric, sqrt_out, row_idx, dist, n_found);
+                                metric, sqrt_out, row_idx, dist, n_found, nprobe);
 }
 
 // topk() beyond the kernels' list capacity (k >= 1024: no runner-up slot left; min(nprobe, n_clusters) > 1024): the
@@ -3776,7 +3855,7 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
         uint32_t nf = 0;
         if (int rc = replay_with_clusters(s, sc, d_q_s, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(),
                                           clusters, k, max_candidates, metric, sqrt_out, row_idx + static_cast<uint64_t>(q) * k,
-                                          dist + static_cast<uint64_t>(q) * k, &nf))
+                                          dist + static_cast<uint64_t>(q) * k, &nf, nprobe))
             return rc;
         if (n_found) n_found[q] = nf;
         if (n_candidates) n_candidates[q] = total;
@@ -3941,7 +4020,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
                                                                           : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i, np,
                                                 k, max_candidates, metric, sqrt_out,
                                                 row_idx + static_cast<uint64_t>(q0 + i) * k,
-                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i]))
+                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe))
                     return rc;
                 s->counters.exact_replays++;
             }
@@ -4013,7 +4092,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
     HIP_TRY(sc.s_hit_vals.ensure(static_cast<size_t>(batch) * stride * sizeof(uint32_t)));
     HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
     std::vector<uint32_t> h_cnt(batch), h_probe, order;
-    std::vector<uint64_t> h_ncand(batch), h_off(batch), h_base;
+    std::vector<uint64_t> h_ncand(batch), h_off(batch), h_base, h_end, pair_end_q;
     std::vector<RangeSeg> segs;
     uint64_t cap_rows = 1, cap_dist = 1;      // entries the library buffers have room for
     const uint64_t max_len = std::max<uint64_t>(1, s->max_list_len);
@@ -4065,7 +4144,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             pm.n_cand = sc.s_ncand.as<uint64_t>(); pm.max_pos = max_pos;
             pm.stats = s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
             if (s->n_files) {
-                if (int rc = enqueue_table_probe(s, sc, p, d_q, b, nprobe, nullptr, 0, pm, st)) return rc;
+                if (int rc = enqueue_table_probe(s, sc, p, d_q, b, nprobe, nullptr, 0, pm, st, max_candidates)) return rc;
             } else
             HIP_TRY(launch_merge_probe(pm, st));
             launches += 2;
@@ -4073,6 +4152,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             // find_closest_centroids without the kernels' list limit (as topk_unbounded): the order of every centroid per query
             h_probe.resize(static_cast<size_t>(b) * np);
             h_base.resize(static_cast<size_t>(b) * np);
+            if (table_rr(s, max_candidates)) h_end.resize(static_cast<size_t>(b) * np);
             for (uint32_t i = 0; i < b; ++i) {
                 if (int rc = centroid_order_host(s, sc, d_q + static_cast<uint64_t>(i) * s->dim, order, nprobe)) return rc;
                 uint64_t total = 0;
@@ -4081,12 +4161,21 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
                     h_base[static_cast<size_t>(i) * np + j] = total;
                     total += s->h_list_off[order[j] + 1] - s->h_list_off[order[j]];
                 }
+                if (!h_end.empty()) {
+                    order.resize(np);
+                    table_pair_ends(s, order, nprobe, max_candidates, pair_end_q);
+                    std::copy(pair_end_q.begin(), pair_end_q.end(), h_end.begin() + static_cast<size_t>(i) * np);
+                }
                 h_ncand[i] = total;
                 s->counters.candidate_rows += total;                              // index_exec.rs:289-299
                 s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(total, max_candidates) : total;
             }
             HIP_TRY(hipMemcpyAsync(sc.s_probe.p, h_probe.data(), h_probe.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(sc.s_cand_base.p, h_base.data(), h_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            if (!h_end.empty()) {
+                HIP_TRY(sc.s_pair_end.ensure(h_end.size() * sizeof(uint64_t)));
+                HIP_TRY(hipMemcpyAsync(sc.s_pair_end.p, h_end.data(), h_end.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            }
         }
 
         // the hits: one pass over every (query, probed list), rows through d_mat / d_row_of (every layout)
@@ -4104,6 +4193,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             ra.blocks_per_list = static_cast<uint32_t>((max_len + rpb - 1) / rpb);
         }
         ra.max_pos = max_pos; ra.metric = metric;
+        ra.pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
         ra.radius = radius; ra.sqrt_out = sqrt_out ? 1 : 0;
         ra.hit_cnt = sc.s_hit_cnt.as<uint32_t>(); ra.hit_keys = sc.s_hit_keys.as<uint64_t>(); ra.hit_vals = sc.s_hit_vals.as<uint32_t>();
         ra.seg_stride = stride;

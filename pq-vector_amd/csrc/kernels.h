@@ -32,6 +32,8 @@ struct StreamArgs {
     uint32_t        rows_per_block;   // multiple of 256
     uint32_t        blocks_per_list;  // gridDim.x
     uint64_t        max_pos;          // candidates at position >= max_pos are ignored
+    const uint64_t *pair_end;         // [nq, nprobe] or nullptr: list j of query q counts positions < pair_end[q * nprobe + j]
+                                      // instead (a round-robin capped table, SegProbeArgs::pair_end)
     int             metric;           // pqv_metric
     // TOPK outputs: [nq][nprobe*blocks_per_list*4][k]
     uint64_t       *part_keys;
@@ -178,6 +180,12 @@ struct SegProbeArgs {
     uint32_t        n_files, nprobe;
     uint32_t        kmax;         // max over the files of min(nprobe, kc_f) (<= 1024)
     uint32_t        stream_parts; // 0: probe_rows_kernel partials (entry c = centroid c); else stream_kernel partial lists per file
+    // round-robin cap (PQV_TABLE_CAP_ROUND_ROBIN, max_cand > 0): file f of query q keeps the first t_f of its c_f candidates, t_f
+    // as CandidateCursor::next_batch(max_cand) deals them (access.rs:214-242); pair_end[q * k + j] = the end position of list j's
+    // file (its first position + t_f).  file_cnt: [nq * n_files] scratch.  pair_end == nullptr: no cap here.
+    uint64_t        max_cand;
+    uint32_t       *file_cnt;
+    uint64_t       *pair_end;
 };
 hipError_t launch_merge_probe_seg(const MergeArgs &a, const SegProbeArgs &g, hipStream_t s);
 // stream_kernel arguments of the per-file centroid pass: probe[q * n_files + f] = f, cand_base[...] = seg_off[f]
@@ -264,6 +272,7 @@ struct SeedRefine {
     const uint64_t *cand_base;  // [nq, nprobe]
     uint32_t        dim, nprobe, seed_sw, seed_rows;
     uint64_t        max_pos;
+    const uint64_t *pair_end;   // [nq, nprobe] or nullptr (StreamArgs::pair_end)
 };
 // One-query calls: wide_seed_kernel's LAST block to finish (a ticket counter) runs seed_select_kernel's body itself.
 struct SeedTail {
@@ -293,6 +302,7 @@ struct TileArgs {
     uint32_t        nq, nprobe, dim, k;
     uint32_t        rows_per_block, blocks_per_list;
     uint64_t        max_pos;
+    const uint64_t *pair_end;    // [nq * nprobe] or nullptr: the pair's candidates end there instead (StreamArgs::pair_end)
     unsigned long long *gthr;    // [nq] per-query global admission threshold, preset to KEY_EMPTY
     // row window of this launch inside every list: rows [row_offset, row_offset + gridDim.x *
     // rows_per_block).  Partial-list slots: a (query, probe rank j) pair owns slots_per_pair

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void list_filter_kernel(const TileArgs a) {
         const uint32_t qrow = pk >> 10, pair = qrow * nprobe + (pk & 1023u);
         const float *x = a.mat + (uint64_t)srow * DIM;
         const float4 *qg = reinterpret_cast<const float4 *>(a.queries + (uint64_t)qrow * DIM);
-        const uint64_t cbase = a.cand_base[pair];
+        const uint64_t cbase = a.cand_base[pair], lim = a.pair_end ? a.pair_end[pair] : a.max_pos;
         const uint32_t thr_now = buf_ld4<16>(rt_thr, qrow * 8u + 4u, 0u);
         float sum = 0.0f;
         const uint32_t first = (uint32_t)lane & ~(L - 1u);
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void list_filter_kernel(const TileArgs a) {
             }
         }
         const uint64_t pos = cbase + roff;
-        const uint64_t mykey_all = (have && pos < a.max_pos) ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos) : KEY_EMPTY;
+        const uint64_t mykey_all = (have && pos < lim) ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos) : KEY_EMPTY;
         const bool pass = mykey_all < widen(thr_now);
         const bool spill = !append_pair(pass, qrow, sum, mykey_all, srow);
         unsigned long long todo = __ballot(spill);

@@ -44,12 +44,13 @@ __global__ __launch_bounds__(256) void stream_kernel(const StreamArgs a) {
 #define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
 
     const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
-    uint64_t lbeg, lend, cbase;
+    uint64_t lbeg, lend, cbase, lim = a.max_pos;
     if (a.probe) {
         const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
         lbeg = a.list_off[c];
         lend = a.list_off[c + 1];
         cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
+        if (a.pair_end) lim = a.pair_end[(uint64_t)q * a.nprobe + j];
     } else {
         lbeg = a.single_begin;
         lend = a.single_end;
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(256) void stream_kernel(const StreamArgs a) {
         }
 
         const uint64_t pos = cbase + t0 + (uint64_t)lane;
-        const bool valid = (uint32_t)lane < nvalid && pos < a.max_pos;
+        const bool valid = (uint32_t)lane < nvalid && pos < lim;
         if constexpr (MODE == STREAM_TOPK) {
             const uint64_t mykey =
                 valid ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos)
@@ -1175,6 +1176,54 @@ __device__ __forceinline__ void probe_merge_tail_seg(const MergeArgs &a, uint32_
     }
 }
 
+// The round-robin cap of a table (SegProbeArgs::pair_end): CandidateCursor::next_batch(M) of a fresh cursor over the files
+// (access.rs:214-242) in closed form.  Whole rounds first: L = the largest level with S(L) = sum_f min(c_f, L) <= M (a binary
+// search, one wave sum per step); then the first M - S(L) files with c_f > L take one more (ballot, rank from mbcnt).  Counts are
+// u32: a query's candidates are distinct table rows, fewer than 2^32 - 1.  file_cnt[f] was written by lane f % 64, and only that
+// lane reads it back.  total: the query's uncapped candidate count.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return readlane_u32(wave_incl_scan_u32(v), 63); }
+__device__ void table_quota(const MergeArgs &a, const SegProbeArgs &g, uint32_t q, int lane, uint64_t total) {
+    const uint32_t F = g.n_files;
+    const uint32_t *cnt = g.file_cnt + (uint64_t)q * F;
+    uint32_t L = 0xFFFFFFFFu, rem = 0;            // no cap (M >= total): every file keeps all of its candidates
+    if (g.max_cand < total) {
+        const uint32_t M = (uint32_t)g.max_cand;
+        uint32_t lo = 0, hi = M + 1, s_lo = 0;     // S(lo) <= M < S(hi)  (S(M + 1) >= min(total, M + 1))
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            uint32_t part = 0;
+            for (uint32_t f0 = 0; f0 < F; f0 += 64) {
+                const uint32_t f = f0 + (uint32_t)lane;
+                const uint32_t c = f < F ? cnt[f] : 0u;
+                part += c < mid ? c : mid;
+            }
+            const uint32_t sm = wave_sum_u32(part);
+            if (sm <= M) { lo = mid; s_lo = sm; } else hi = mid;
+        }
+        L = lo;
+        rem = M - s_lo;
+    }
+    uint32_t fb = 0, o = 0, rank0 = 0;            // running: the file's first position, its first pair, files above L so far
+    for (uint32_t f0 = 0; f0 < F; f0 += 64) {
+        const uint32_t f = f0 + (uint32_t)lane;
+        const bool in = f < F;
+        const uint32_t c = in ? cnt[f] : 0u;
+        const uint32_t kc = in ? g.seg_off[f + 1] - g.seg_off[f] : 0u;
+        const uint32_t kf = kc < g.nprobe ? kc : g.nprobe;
+        const bool above = c > L;
+        const uint64_t m = __ballot(above);
+        const uint32_t rank = rank0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint32_t t = (c < L ? c : L) + ((above && rank < rem) ? 1u : 0u);
+        const uint32_t ci = wave_incl_scan_u32(c), ki = wave_incl_scan_u32(kf);
+        const uint64_t end = (uint64_t)(fb + ci - c) + t;
+        uint64_t *pe = g.pair_end + (uint64_t)q * a.k + (o + ki - kf);
+        for (uint32_t i = 0; i < kf; ++i) pe[i] = end;
+        fb += readlane_u32(ci, 63);
+        o += readlane_u32(ki, 63);
+        rank0 += (uint32_t)__popcll(m);
+    }
+}
+
 template <int S>
 __global__ __launch_bounds__(256) void merge_probe_seg_kernel(const MergeArgs a, const SegProbeArgs g) {
     const int lane = threadIdx.x & 63;
@@ -1191,7 +1240,11 @@ __global__ __launch_bounds__(256) void merge_probe_seg_kernel(const MergeArgs a,
     for (uint32_t f = 0; f < g.n_files; ++f) {
         const uint32_t lo = g.seg_off[f], hi = g.seg_off[f + 1];
         const uint32_t kf = hi - lo < g.nprobe ? hi - lo : g.nprobe;
-        if (kf == 0) continue;
+        const uint64_t carry0 = carry;
+        if (kf == 0) {
+            if (g.pair_end && lane == (int)(f & 63u)) g.file_cnt[(uint64_t)q * g.n_files + f] = 0u;
+            continue;
+        }
         uint64_t b, e;
         if (g.stream_parts) { b = (uint64_t)f * g.stream_parts * a.k_part; e = b + (uint64_t)g.stream_parts * a.k_part; }
         else { b = lo; e = hi; }
@@ -1206,7 +1259,9 @@ __global__ __launch_bounds__(256) void merge_probe_seg_kernel(const MergeArgs a,
         }
         probe_merge_tail_seg<S>(a, q, lane, tk, kf, out0, carry);
         out0 += kf;
+        if (g.pair_end && lane == (int)(f & 63u)) g.file_cnt[(uint64_t)q * g.n_files + f] = (uint32_t)(carry - carry0);
     }
+    if (g.pair_end) table_quota(a, g, q, lane, carry);
     if (a.n_cand && lane == 0) a.n_cand[q] = carry;
     if (a.stats && lane == 0) {
 #ifdef PQV_PROFILE_PHASES

@@ -57,6 +57,7 @@ __global__ __launch_bounds__(256) void tile_rerank_kernel(const TileArgs a) {
     const uint32_t my_pair = a.pairs[my_slot];
     const uint32_t my_qrow = my_pair / a.nprobe;
     const uint64_t my_cbase = a.cand_base[my_pair];
+    const uint64_t my_lim = a.pair_end ? a.pair_end[my_pair] : a.max_pos;     // candidates of this pair end there
     uint64_t my_lkth = KEY_EMPTY;          // k-th key of this wave's list of query `lane`
     bool my_touched = false;               // this wave has folded into its list of query `lane`
     // this wave's list of query `lane`: slot (q, j, chunk, wave) of the partial-list buffer
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256) void tile_rerank_kernel(const TileArgs a) {
         for (uint32_t qq = 0; qq < cnt; ++qq) {
             const uint64_t thr = readlane_u64(my_thr, (int)qq);
             const uint64_t pos = readlane_u64(my_cbase, (int)qq) + posl;
-            const bool valid = (uint32_t)lane < nvalid && pos < a.max_pos;
+            const bool valid = (uint32_t)lane < nvalid && pos < readlane_u64(my_lim, (int)qq);
             const float sv = lsums[qq * 64 + lane];
             const uint64_t mykey =
                 valid ? (((uint64_t)__float_as_uint(sv) << 32) | (uint64_t)(uint32_t)pos) : KEY_EMPTY;
@@ -259,6 +260,7 @@ __global__ __launch_bounds__(256) void tile_filter_kernel(const TileArgs a) {
     const uint32_t my_pair = a.pairs[my_slot];
     const uint32_t my_qrow = my_pair / a.nprobe;
     const uint64_t my_cbase = a.cand_base[my_pair];
+    const uint64_t my_lim = a.pair_end ? a.pair_end[my_pair] : a.max_pos;
     const float my_qn = a.query_norm2[my_qrow];
     uint64_t my_lkth = KEY_EMPTY;
     const uint32_t n_part = a.n_part;
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256) void tile_filter_kernel(const TileArgs a) {
 #pragma unroll 1
         for (uint32_t qq = 0; qq < cnt; ++qq) {
             const uint64_t pos = readlane_u64(my_cbase, (int)qq) + roff;
-            const bool mine = have && qs == qq && pos < a.max_pos;
+            const bool mine = have && qs == qq && pos < readlane_u64(my_lim, (int)qq);
             const uint64_t mykey =
                 mine ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos) : KEY_EMPTY;
             const uint64_t thr = readlane_u64(my_thr, (int)qq);
@@ -600,7 +602,8 @@ __global__ __launch_bounds__(256) void wide_seed_kernel(const TileArgs a) {
     const uint32_t my_qrow = my_pair / a.nprobe;
     const uint64_t my_cbase = a.cand_base[my_pair];
     // list offsets below my_lim are candidates of this query (max_candidates cap)
-    const uint64_t room = a.max_pos > my_cbase ? a.max_pos - my_cbase : 0;
+    const uint64_t my_lim = a.pair_end ? a.pair_end[my_pair] : a.max_pos;
+    const uint64_t room = my_lim > my_cbase ? my_lim - my_cbase : 0;
     qnl[lane] = a.query_norm2[my_qrow];
     const float my_qn0 = a.query_norm2[my_qrow];
     bool my_bad16 = F16 && (a.query_maxabs[my_qrow] * a.scale > 32768.0f || my_qn0 * a.scale2 < 1.0f);   // no valid f16 bound
@@ -969,12 +972,14 @@ __device__ __forceinline__ void seed_select_body(const uint32_t q, const float *
                 if (valid && pre_lists) {
                     lbeg = s_lbeg[j];
                     pos = s_cbase[j] + row;
-                    valid = row < rf.seed_rows && lbeg + row < s_lend[j] && pos < rf.max_pos;
+                    valid = row < rf.seed_rows && lbeg + row < s_lend[j] &&
+                            pos < (rf.pair_end ? rf.pair_end[(uint64_t)q * rf.nprobe + j] : rf.max_pos);
                 } else if (valid) {
                     const uint32_t c = rf.probe[(uint64_t)q * rf.nprobe + j];
                     lbeg = rf.list_off[c];
                     pos = rf.cand_base[(uint64_t)q * rf.nprobe + j] + row;
-                    valid = row < rf.seed_rows && lbeg + row < rf.list_off[c + 1] && pos < rf.max_pos;
+                    valid = row < rf.seed_rows && lbeg + row < rf.list_off[c + 1] &&
+                            pos < (rf.pair_end ? rf.pair_end[(uint64_t)q * rf.nprobe + j] : rf.max_pos);
                 }
                 s_rowoff[lane] = valid ? (uint64_t)(rf.row_of ? rf.row_of[lbeg + row] : lbeg + row) * rf.dim : 0ull;
             }
@@ -1065,7 +1070,8 @@ __device__ __forceinline__ void seed_select_body(const uint32_t q, const float *
             const uint32_t c = rf.probe[(uint64_t)q * rf.nprobe + j];
             lbeg = rf.list_off[c];
             pos = rf.cand_base[(uint64_t)q * rf.nprobe + j] + row;
-            valid = row < rf.seed_rows && lbeg + row < rf.list_off[c + 1] && pos < rf.max_pos;
+            valid = row < rf.seed_rows && lbeg + row < rf.list_off[c + 1] &&
+                    pos < (rf.pair_end ? rf.pair_end[(uint64_t)q * rf.nprobe + j] : rf.max_pos);
         }
         const float *x = rf.mat + (valid ? (uint64_t)(rf.row_of ? rf.row_of[lbeg + row] : lbeg + row) : 0ull) * rf.dim;
         const float4 *qg = reinterpret_cast<const float4 *>(rf.queries + (uint64_t)q * rf.dim);
@@ -1409,6 +1415,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
     // top of every tile.  LDS reads count on lgkmcnt and leave the operand stream alone.
     constexpr bool LST = NW == 8 || I8 || NG == 6;
     __shared__ uint64_t qst_cbase[LST ? NQ : 1];
+    __shared__ uint32_t qst_room[LST ? NQ : 1];       // list offsets below it are candidates of the pair (max_candidates cap)
     __shared__ uint32_t qst_pair[LST ? NQ : 1];
     __shared__ float qst_qn[LST && !I8 ? NQ : 1];     // |q|^2; NaN = never skip this query (float operand forms)
     // (the two the screen reads by LANE index are padded to 64 QS entries: slot s of lane l reads entry 64 s + l without a clamp --
@@ -1420,6 +1427,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
     [[maybe_unused]] uint32_t my_pairi[I8 ? QS : 1];         // int8: the pair (its image is per (query, list))
     [[maybe_unused]] uint32_t my_pair[LST ? 1 : QS];
     [[maybe_unused]] uint64_t my_cbase[LST ? 1 : QS], my_base[LST ? 1 : QS];
+    [[maybe_unused]] uint32_t my_room[LST ? 1 : QS];
     [[maybe_unused]] float my_qn[LST ? 1 : QS];
     [[maybe_unused]] bool my_noskip[LST ? 1 : QS];
     const uint32_t n_part = a.n_part;
@@ -1433,16 +1441,22 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
         const float qn = a.query_norm2[my_qrow[s]];
         // F16: a query whose scaled image overflows f16 or whose scaled norm is below 1 is never skipped
         const bool noskip = F16 && (!(a.query_maxabs[my_qrow[s]] * a.scale <= 32768.0f) || !(qn * a.scale2 >= 1.0f) || !(qn <= 3.0e38f));
+        // (positions and list offsets stay below 2^32: the room, clamped to 32 bits, decides exactly as pos < limit)
+        const uint64_t cb = a.cand_base[pair], lim = a.pair_end ? a.pair_end[pair] : a.max_pos;
+        const uint64_t room64 = lim > cb ? lim - cb : 0;
+        const uint32_t room = room64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)room64;
         if constexpr (LST) {
             if (qi < NQ) {
                 qst_pair[qi] = pair;
-                qst_cbase[qi] = a.cand_base[pair];
+                qst_cbase[qi] = cb;
+                qst_room[qi] = room;
                 if constexpr (!I8) qst_qn[qi] = noskip ? __uint_as_float(0x7FC00000u) : qn;
                 if constexpr (I8) { qst_n2i[qi] = a.q_n2i[my_pairi[s]]; qst_res[qi] = a.q_res[my_pairi[s]]; }   // +inf: non-finite query
             }
         } else {
             my_pair[s] = pair;
-            my_cbase[s] = a.cand_base[pair];
+            my_cbase[s] = cb;
+            my_room[s] = room;
             my_qn[s] = qn;
             my_base[s] = ((uint64_t)my_qrow[s] * n_part + (pair % a.nprobe) * a.slots_per_pair + a.slot_base + bx * NW + wave) * k;
             my_noskip[s] = noskip;
@@ -1594,7 +1608,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
         const uint32_t qrow = qsel_u32<QS>(my_qrow, qsl);
         const float thr_d = __uint_as_float(qsel_u32<QS>(cur_gthr, qsl));
         uint64_t pos;
-        if constexpr (LST) pos = qst_cbase[qsl] + roff; else pos = qsel_u64<QS>(my_cbase, qsl) + roff;
+        uint32_t room;
+        if constexpr (LST) { pos = qst_cbase[qsl] + roff; room = qst_room[qsl]; }
+        else { pos = qsel_u64<QS>(my_cbase, qsl) + roff; room = qsel_u32<QS>(my_room, qsl); }
         float lb = 0.0f, ub = INFINITY;
         bool ok = valid && raw != NOVAL && raw != NOVAL_NOHIST;
         if constexpr (I8) {
@@ -1629,7 +1645,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
             ok = ok && !noskip && sv == sv && nn <= 3.0e38f;
         }
         ok = ok && ub >= 0.0f && ub <= 3.0e38f && lb <= ub;
-        const bool in_cap = valid && pos < a.max_pos;
+        const bool in_cap = valid && roff < room;
         // (the threshold may have tightened since the screen; an unset one is NaN: never dropped)
         const bool dpass = ok && in_cap && !(lb > thr_d);
         const uint64_t dkey = ((uint64_t)__float_as_uint(ub) << 32) | (uint64_t)(uint32_t)pos;
@@ -1731,9 +1747,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
 #endif
         // the wave's view of the thresholds (refreshed every tile)
         uint64_t pos;
-        if constexpr (LST) pos = qst_cbase[qsl] + roff; else pos = qsel_u64<QS>(my_cbase, qsl) + roff;
+        uint32_t room;
+        if constexpr (LST) { pos = qst_cbase[qsl] + roff; room = qst_room[qsl]; }
+        else { pos = qsel_u64<QS>(my_cbase, qsl) + roff; room = qsel_u32<QS>(my_room, qsl); }
         const uint64_t mykey_all =
-            (have && pos < a.max_pos) ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos) : KEY_EMPTY;
+            (have && roff < room) ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos) : KEY_EMPTY;
         // A pair that beats its query's threshold is APPENDED to the query's candidate buffer: one
         // atomic per lane, all lanes in parallel (a sorted per-wave list would cost one global
         // read-modify-write round trip per query, serially -- measured: half of the kernel).

@@ -13,7 +13,14 @@ k = 10, sqrt_out = 0.  Reported per route: queries/s (host clock around synchron
 bytes-over-HBM-peak computed as bench.py's roofline does (the int8 image of every distinct probed row + 8 bytes, plus the f32
 row of every screen survivor) over the CALL time, and whether (a) and (b) agree.  Kernel times: run this under
 `rocprofv3 --kernel-trace --stats` in a run of its own.  Prints one JSON line.
-usage: python tools/bench_table.py [--reps N] [--shapes t8,t64] [--out PATH]"""
+--max-candidates M[,M...] adds the capped leg per shape and M (VectorTopKOptions::max_candidates, dealt out round robin
+over the files as the reference's CandidateCursor does):
+  (a) capped   -- a TableSearcher created with PQV_TABLE_CAP_ROUND_ROBIN, one pqv_topk_device call
+  (b) perfile  -- the route without it: per query, the per-file candidate counts (pqv_probe + list lengths), the quotas
+                  (pqv_round_robin_quota), one capped pqv_topk_device call per (query, file), pqv_merge_topk; timed on the first
+                  --cap-subset queries of a batch and scaled to the batch
+  (c) uncapped -- the uncapped table at the same nprobe
+usage: python tools/bench_table.py [--reps N] [--shapes t8,t64] [--max-candidates 2048,32768] [--cap-subset 16] [--out PATH]"""
 import argparse
 import json
 import os
@@ -46,6 +53,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="t8,t64")
     ap.add_argument("--out", default="")
+    ap.add_argument("--max-candidates", default="")
+    ap.add_argument("--cap-subset", type=int, default=16)
     args = ap.parse_args()
     import torch
     import bench
@@ -63,12 +72,13 @@ def main():
     single_lens = np.diff(np.asarray(single_index.list_offsets, dtype=np.int64))
     out = {"rows": n, "dim": dim, "k": K, "batch": nq, "single_index_build_s": time.perf_counter() - t0, "shapes": {}}
 
-    def run(s, queries, k, nprobe):
+    def run(s, queries, k, nprobe, max_candidates=0):
         m = len(queries)
         rows = torch.empty((m, k), dtype=torch.int32, device=dev)
         dist = torch.empty((m, k), dtype=torch.float32, device=dev)
         nf = torch.empty(m, dtype=torch.int32, device=dev)
-        s.topk_device(queries.data_ptr(), m, k, nprobe, rows.data_ptr(), dist.data_ptr(), nf.data_ptr(), 0, sqrt_out=False)
+        s.topk_device(queries.data_ptr(), m, k, nprobe, rows.data_ptr(), dist.data_ptr(), nf.data_ptr(), 0,
+                      max_candidates=max_candidates, sqrt_out=False)
         return rows, dist, nf
 
     def roofline(s, queries, nprobe, sec, probe_lists):
@@ -142,6 +152,53 @@ def main():
             rec["by_nq"][str(m)] = r
         rec["describe_table_1024"] = table.describe(nq, K, nprobe_f)
         rec["describe_table_1"] = table.describe(1, K, nprobe_f)
+        caps = [int(x) for x in args.max_candidates.split(",") if x]
+        if caps:
+            capped = pqv.TableSearcher(idx, corpus, row_base, pqv.PQV_TABLE_CAP_ROUND_ROBIN)
+            lens_f = [np.diff(np.asarray(ix.list_offsets, dtype=np.int64)) for ix in idx]
+
+            def perfile_capped(queries, mc):
+                """(b): rows u32 [m, K], dist [m, K], counts [m] -- per query and file one capped call, then the merge"""
+                qs = queries.cpu().numpy()
+                rows_o, dist_o, cnt_o = [], [], []
+                for i, q in enumerate(qs):
+                    counts = np.array([int(lens_f[f][s_f.probe(q, nprobe_f)].sum()) for f, s_f in enumerate(perfile)], np.uint64)
+                    quota = pqv.round_robin_quota(counts, mc)
+                    outs = [(f, run(s_f, queries[i:i + 1], K, nprobe_f, int(quota[f]))) for f, s_f in enumerate(perfile) if quota[f]]
+                    torch.cuda.synchronize()
+                    r = np.full((F, 1, K), 0xFFFFFFFF, np.uint32)
+                    d = np.full((F, 1, K), np.inf, np.float32)
+                    c = np.zeros((F, 1), np.uint32)
+                    for f, o in outs:
+                        rf = o[0].cpu().numpy().view(np.uint32)
+                        r[f] = np.where(rf == 0xFFFFFFFF, rf, rf.astype(np.int64) + row_base[f]).astype(np.uint32)
+                        d[f] = o[1].cpu().numpy()
+                        c[f] = o[2].cpu().numpy().astype(np.uint32)
+                    md, mr, _, mcnt = pqv.merge_topk(d, r, c)
+                    rows_o.append(mr[0]); dist_o.append(md[0]); cnt_o.append(mcnt[0])
+                return np.stack(rows_o), np.stack(dist_o), np.array(cnt_o)
+
+            rec["capped"] = {}
+            for mc in caps:
+                by = {}
+                for m in (nq, 1):
+                    qb = q_t[:m].contiguous()
+                    sub = qb[:min(m, args.cap_subset)].contiguous()
+                    ta = timed(torch, lambda: run(capped, qb, K, nprobe_f, mc), args.reps)
+                    tb_sub = timed(torch, lambda: perfile_capped(sub, mc), max(1, args.reps // 2))
+                    tb = tb_sub * m / len(sub)
+                    tc = timed(torch, lambda: run(table, qb, K, nprobe_f), args.reps)
+                    ra, da, fa = run(capped, sub, K, nprobe_f, mc)
+                    torch.cuda.synchronize()
+                    br, bd, bc = perfile_capped(sub, mc)
+                    same = bool((fa.cpu().numpy().astype(np.uint32) == bc).all() and (ra.cpu().numpy().view(np.uint32) == br).all() and
+                                (da.cpu().numpy().view(np.uint32) == bd.view(np.uint32)).all())
+                    by[str(m)] = {"capped": {"s": ta, "qps": m / ta}, "perfile_capped": {"s": tb, "qps": m / tb, "timed_queries": len(sub)},
+                                  "uncapped": {"s": tc, "qps": m / tc}, "capped_equals_perfile": same,
+                                  "capped_over_uncapped_time": ta / tc, "perfile_over_capped_time": tb / ta}
+                rec["capped"][str(mc)] = by
+            rec["describe_capped_1024"] = capped.describe(nq, K, nprobe_f)
+            del capped
         out["shapes"][shape] = rec
         del table, perfile
         torch.cuda.synchronize()
