@@ -11,11 +11,12 @@ REF4, SEQ = 0, 1
 
 
 def l2_chain(rows, query, metric):
-    """d2 [m] f32 of rows [m, dim] against query [dim] in the metric's summation order."""
+    """d2 [m] f32 of rows [m, dim] against query [dim] (or row by row against queries [m, dim]) in the metric's
+    summation order."""
     x = np.ascontiguousarray(rows, dtype=np.float32)
-    q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)
+    q = np.ascontiguousarray(query, dtype=np.float32)
     m, dim = x.shape
-    d = q[None, :] - x
+    d = (q.reshape(1, -1) if q.ndim < 2 else q) - x
     sq = d * d
     s = np.zeros(m, dtype=np.float32)
     if metric == SEQ:

@@ -211,27 +211,21 @@ def test_rejection_branch_sample_build_blob_equals_oracle(pqv, oracle):
 
 
 @pytest.mark.timeout(1800)
-def test_c3_shape_screened_final_assignment_matches_oracle_on_a_slice(pqv, oracle, c3_shape):
-    """C3's parameters (dim 768, 1024 centroids): the final assignment of the build runs through the MFMA screen
-    (ScreenedAssign) -- bounds, survivors, exact re-evaluation.  For 100 000 rows spread over the corpus the cluster the
-    GPU put a row into must be the oracle's nearest_centroid (index.rs:244-257: strict '<', lowest index wins) under
-    the GPU-built centroids."""
-    from concurrent.futures import ThreadPoolExecutor
+def test_c3_shape_build_centroids_and_every_row_match_reference(pqv, oracle, c3_shape):
+    """C3's parameters (dim 768, 1024 centroids) on 1 M rows: the final assignment of the build runs through the MFMA
+    screen (ScreenedAssign) -- bounds, survivors, exact re-evaluation.  The centroids must equal oracle.kmeans over the
+    build's 50 000-row sample (index::sample's INPLACE branch at this size) with the same workers, bit for bit, and the
+    cluster of EVERY row must be the reference's nearest_centroid (index.rs:244-257: strict '<', lowest index wins) under
+    those centroids, decided exactly by tests/assign_exact.py; the lists and the blob follow from them."""
+    from build_reference import check_build_against_reference
     data, corpus, index, _ = c3_shape
     n = data.shape[0]
-    off, rows = index.list_offsets.astype(np.int64), index.list_rows
-    cluster_of = np.empty(n, dtype=np.uint32)
-    for c in range(index.n_clusters):
-        cluster_of[rows[off[c]:off[c + 1]]] = c
-    oidx = oracle.index_from_bytes(index.to_bytes())
-    sel = np.arange(0, n, 10)[:100_000]
-
-    def nearest(lo):
-        return [int(oidx.find_closest_centroids(data[r], 1)[0]) for r in sel[lo:lo + 500]]
-    with ThreadPoolExecutor(max_workers=32) as ex:
-        want = np.array([c for part in ex.map(nearest, range(0, len(sel), 500)) for c in part], dtype=np.uint32)
-    bad = np.nonzero(cluster_of[sel] != want)[0]
-    assert len(bad) == 0, (len(bad), sel[bad[:5]], cluster_of[sel][bad[:5]], want[bad[:5]])
+    sample_idx, branch = oracle.index_sample(oracle.rng(42), n, 50_000)
+    assert branch == 1                                           # inplace
+    problems, rec = check_build_against_reference(oracle, data, index.to_bytes(), index.centroids, index.list_offsets,
+                                                  index.list_rows, sample_idx, index.n_clusters, 8)
+    print(f"\nc3 shape, 1 M rows: {rec}")
+    assert not problems, problems
 
 
 def test_c1_vldb_standin_through_the_path_builders(pqv, tmp_path):
