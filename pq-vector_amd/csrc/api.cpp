@@ -325,6 +325,14 @@ struct Scratch {
     // the lane's side stream for the wide-quad launch of a batch (TileArgs::side_stream), created on first use
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // every DevBuf above, for pqv_searcher_footprint (a buffer added to the declaration belongs here too)
+    std::vector<const DevBuf *> bufs() const {
+        return {&s_probe_keys, &s_probe_vals, &s_probe, &s_cand_base, &s_ncand, &s_part_keys, &s_part_vals, &s_queries, &s_rows,
+                &s_dist, &s_nfound, &s_pair_u32, &s_pairs, &s_groups, &s_quads, &s_items, &s_ticket, &s_ticket2, &s_cand_keys, &s_cand_vals, &s_cand_cnt, &s_spilled,
+                &s_seed_ub, &s_qblk, &s_gthr, &s_tie, &s_replay, &s_qnorm, &s_qmax, &s_thr_hist, &s_thr_bins, &s_qi8, &s_qn2i, &s_qres, &s_qresu, &s_pair_lb, &s_part_flags, &s_qpad, &s_cand_lb, &s_pendv, &s_work, &s_nwork, &s_out,
+                &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
+                &s_pair_end, &s_file_cnt};
+    }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -2956,6 +2964,14 @@ void table_pair_ends(const pqv_searcher *s, const std::vector<uint32_t> &cluster
     }
 }
 
+// stream_kernel's split of a pass over (query, list) pairs: enough blocks to fill the chip (~8192), lists cut into 256-row multiples
+void stream_split(uint64_t max_len, uint64_t pairs, uint32_t &rows_per_block, uint32_t &blocks_per_list) {
+    const uint64_t bpl = std::max<uint64_t>(1, std::min<uint64_t>((8192 + pairs - 1) / pairs, (max_len + 255) / 256));
+    const uint64_t rpb = ((max_len + bpl - 1) / bpl + 255) / 256 * 256;
+    rows_per_block = static_cast<uint32_t>(rpb);
+    blocks_per_list = static_cast<uint32_t>((max_len + rpb - 1) / rpb);
+}
+
 struct TopkPlan {
     uint32_t np;            // effective nprobe
     uint32_t probe_bpl;     // blocks over the centroid matrix
@@ -3033,7 +3049,6 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     }
     // re-rank: enough blocks to fill 256 CUs several times over, few enough partial lists
     const uint64_t max_len = std::max<uint64_t>(1, s->max_list_len);
-    const uint64_t max_bpl = (max_len + 255) / 256;
     const uint64_t pairs = std::max<uint64_t>(1, static_cast<uint64_t>(nq) * p.np);
     // Tile path: worth it once several queries share a cluster (each streamed row is then
     // reused by up to TILE_QB queries).  k <= 256; REF4 order only.
@@ -3057,7 +3072,6 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
         const uint64_t tile_rows = o.tile_rows ? o.tile_rows : 1536;
         uint64_t rpb = std::min<uint64_t>(tile_rows, (max_len + 255) / 256 * 256);
         while (rpb > 256 && est_groups * ((max_len + rpb - 1) / rpb) < 2048) rpb -= 256;
-        (void)max_bpl;
         p.rr_rows_per_block = static_cast<uint32_t>(rpb);
         // threshold sample: 256 rows per probed list, 512 for lists of >= 4096 rows (survivors per query halve,
         // the sampling pass doubles: C2 0.246 -> 0.226 ms, C3 7.99 -> 7.58 ms)
@@ -3181,12 +3195,7 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
         p.max_groups = static_cast<uint32_t>(pairs / pqv::TILE_QB + std::min<uint64_t>(s->n_clusters, pairs));
         return p;
     }
-    uint64_t bpl = (8192 + pairs - 1) / pairs;
-    bpl = std::max<uint64_t>(1, std::min<uint64_t>(bpl, max_bpl));
-    uint64_t rpb = (max_len + bpl - 1) / bpl;
-    rpb = (rpb + 255) / 256 * 256;
-    p.rr_rows_per_block = static_cast<uint32_t>(rpb);
-    p.rr_bpl = static_cast<uint32_t>((max_len + rpb - 1) / rpb);
+    stream_split(max_len, pairs, p.rr_rows_per_block, p.rr_bpl);
     p.n_part_rr = p.np * p.rr_bpl * pqv::waves_per_block();
     return p;
 }
@@ -3202,33 +3211,71 @@ int table_max_candidates(const pqv_searcher *s, uint64_t max_candidates) {
 // the kernels take per-pair candidate ends (SegProbeArgs::pair_end) instead of one cap
 bool table_rr(const pqv_searcher *s, uint64_t max_candidates) { return s->n_files && s->rr_cap && max_candidates; }
 
-// Table searchers: the batched probe over the combined centroid table (probe_rows_kernel, or stream_kernel with one list per
-// file) and the probe merge per file segment (merge_probe_seg_kernel).  pm: the probe merge's arguments as the caller fills them
-// for launch_merge_probe (k = p.np = P); pm.part_keys / part_vals are the probe scratch.  sc.s_probe / s_cand_base must hold
-// nq * max(P, n_files) entries (the stream route reads its per-file arguments from them before the merge overwrites them).
-// With the round-robin cap (table_rr) the merge also writes sc.s_pair_end [nq * P]: every list's end of candidates, its file's quota.
-int enqueue_table_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, const float *d_queries, uint32_t nq, uint32_t nprobe,
-                        uint32_t *zero_u32, uint32_t zero_n, const pqv::MergeArgs &pm, hipStream_t stream, uint64_t max_candidates = 0) {
+// The probe's outputs, P lists per query: sc.s_probe / s_cand_base [nq * P] (probed lists nearest first, a table's file after file;
+// their first candidate positions), sized nq * max(P, n_files): a table's stream probe first reads its per-file arguments there.
+int ensure_probe_slots(const pqv_searcher *s, Scratch &sc, uint32_t nq, uint32_t np) {
+    const size_t slots = static_cast<size_t>(nq) * std::max<uint32_t>(np, s->n_files);
+    HIP_TRY(sc.s_probe.ensure(slots * sizeof(uint32_t)));
+    HIP_TRY(sc.s_cand_base.ensure(slots * sizeof(uint64_t)));
+    return PQV_OK;
+}
+
+// The device probe's scratch and the probe merge's common arguments (k = P, totals to s_ncand, positions below max_candidates).
+// Made first: the caller's own fields may point into that scratch (and the fused one-query probe takes the same arguments).
+// pm.stats stays unset: a call that counts its candidates sets it.
+int probe_merge_args(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, uint32_t nq, uint64_t max_candidates, pqv::MergeArgs &pm) {
+    const size_t n_keys = static_cast<size_t>(nq) * p.n_part_probe * p.probe_kpart;
+    HIP_TRY(sc.s_probe_keys.ensure(n_keys * sizeof(uint64_t)));
+    HIP_TRY(sc.s_probe_vals.ensure(n_keys * sizeof(uint32_t)));
+    if (int rc = ensure_probe_slots(s, sc, nq, p.np)) return rc;
+    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(nq) * sizeof(uint64_t)));
+    pm.part_keys = sc.s_probe_keys.as<uint64_t>(); pm.part_vals = sc.s_probe_vals.as<uint32_t>();
+    pm.nq = nq; pm.n_part = p.n_part_probe; pm.k_part = p.probe_kpart; pm.k = p.np;
+    pm.list_off = s->d_list_off.as<uint64_t>();
+    pm.probe = sc.s_probe.as<uint32_t>(); pm.cand_base = sc.s_cand_base.as<uint64_t>();
+    pm.n_cand = sc.s_ncand.as<uint64_t>();
+    pm.max_pos = max_candidates ? max_candidates : ~0ull;
+    return PQV_OK;
+}
+
+// The centroid probe on the device (P <= 1024: the kernels' sorted lists): the distance pass, then the probe merge (a table: per
+// file segment, merge_probe_seg_kernel).  pm: from probe_merge_args plus the caller's fields; zero_u32 / zero_n: scratch the
+// distance pass zeroes on the way (the tile path's histogram).  With the round-robin cap (table_rr) the merge also writes
+// sc.s_pair_end [nq * P]: every list's end of candidates, its file's quota.
+int enqueue_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, const float *d_queries, uint32_t nq, uint32_t nprobe,
+                  uint64_t max_candidates, const pqv::MergeArgs &pm, uint32_t *zero_u32, uint32_t zero_n, hipStream_t stream) {
     using namespace pqv;
-    if (p.probe_rows) {
+    uint64_t *keys = const_cast<uint64_t *>(pm.part_keys);
+    uint32_t *vals = const_cast<uint32_t *>(pm.part_vals);
+    if (p.probe_rows) {     // a batch: a lane per centroid, the chains of up to 8 queries in registers
         ProbeRowsArgs pr{};
         pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_queries;
         pr.nq = nq; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
-        pr.part_keys = const_cast<uint64_t *>(pm.part_keys); pr.part_vals = const_cast<uint32_t *>(pm.part_vals);
+        pr.part_keys = keys; pr.part_vals = vals;
         pr.zero_u32 = zero_u32; pr.zero_n = zero_n;
         HIP_TRY(launch_probe_rows(pr, stream));
-    } else {
-        HIP_TRY(launch_seg_probe_fill(s->d_seg_off.as<uint32_t>(), s->n_files, nq, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(), stream));
+    } else {                // the re-rank kernel over the centroid matrix, k = P (a table: min(nprobe, kc_f) per file)
         StreamArgs pa{};
-        pa.mat = s->d_centroids.as<float>(); pa.row_of = nullptr; pa.list_off = s->d_seg_off64.as<uint64_t>();
-        pa.probe = sc.s_probe.as<uint32_t>(); pa.cand_base = sc.s_cand_base.as<uint64_t>();
-        pa.queries = d_queries; pa.nq = nq; pa.nprobe = s->n_files; pa.dim = s->dim; pa.k = p.probe_kpart;
+        pa.mat = s->d_centroids.as<float>();
+        if (s->n_files) {
+            HIP_TRY(launch_seg_probe_fill(s->d_seg_off.as<uint32_t>(), s->n_files, nq, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(), stream));
+            pa.list_off = s->d_seg_off64.as<uint64_t>(); pa.probe = sc.s_probe.as<uint32_t>(); pa.cand_base = sc.s_cand_base.as<uint64_t>();
+            pa.nprobe = s->n_files;
+        } else {
+            pa.single_begin = 0; pa.single_end = s->n_clusters;
+            pa.nprobe = 1;
+        }
+        pa.queries = d_queries; pa.nq = nq; pa.dim = s->dim; pa.k = p.probe_kpart;
         pa.rows_per_block = 256; pa.blocks_per_list = p.probe_bpl;
         pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;   // find_closest_centroids always uses index.rs:461
-        pa.part_keys = const_cast<uint64_t *>(pm.part_keys); pa.part_vals = const_cast<uint32_t *>(pm.part_vals);
+        pa.part_keys = keys; pa.part_vals = vals;
         pa.zero_u32 = zero_u32; pa.zero_n = zero_n;
         HIP_TRY(launch_stream(pa, STREAM_TOPK, stream));
-        s->counters.kernel_launches += 2;
+        if (s->n_files) s->counters.kernel_launches += 2;
+    }
+    if (!s->n_files) {
+        HIP_TRY(launch_merge_probe(pm, stream));
+        return PQV_OK;
     }
     SegProbeArgs g{};
     g.seg_off = s->d_seg_off.as<uint32_t>(); g.n_files = s->n_files; g.nprobe = nprobe;
@@ -3242,6 +3289,17 @@ int enqueue_table_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, c
     HIP_TRY(launch_merge_probe_seg(pm, g, stream));
     return PQV_OK;
 }
+
+// pqv_timing_read's four events of one call (probe start, re-rank start, re-rank stop, end), kept in s->ev; all null when
+// timing is off
+int timing_events(const pqv_searcher *s, hipEvent_t (&e)[4]) {
+    for (hipEvent_t &x : e) x = nullptr;
+    if (!s->timing) return PQV_OK;
+    for (hipEvent_t &x : e) HIP_TRY(hipEventCreate(&x));
+    s->ev.insert(s->ev.end(), e, e + 4);
+    return PQV_OK;
+}
+
 // Enqueue probe -> probe-merge -> re-rank -> final merge for one batch on `stream`.
 // `k` is the list length the kernels work with; the first k_out entries are written out.
 // With k == k_out + 1 the merge can also flag queries whose output distances tie (d_tie).
@@ -3261,70 +3319,34 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         d_queries_s = sc.s_qpad.as<float>();
     }
 
-    HIP_TRY(sc.s_probe_keys.ensure(static_cast<size_t>(nq) * p.n_part_probe * p.probe_kpart * sizeof(uint64_t)));
-    HIP_TRY(sc.s_probe_vals.ensure(static_cast<size_t>(nq) * p.n_part_probe * p.probe_kpart * sizeof(uint32_t)));
-    const uint32_t np_slots = std::max<uint32_t>(p.np, s->n_files);     // (a table's stream probe reads its per-file arguments from them)
-    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(nq) * np_slots * sizeof(uint32_t)));
-    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(nq) * np_slots * sizeof(uint64_t)));
-    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(nq) * sizeof(uint64_t)));
+    // 1. centroid probe (its scratch first: the arguments below point into it)
+    MergeArgs pm{};
+    if (int rc = probe_merge_args(s, sc, p, nq, max_candidates, pm)) return rc;
+    if (d_n_cand) pm.n_cand = d_n_cand;
+    pm.stats = s->d_stats.as<unsigned long long>();
     HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint32_t)));
 
-    const bool timing = s->timing;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    if (timing) {
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventCreate(&e2)); HIP_TRY(hipEventCreate(&e3));
-        s->ev.push_back(e0); s->ev.push_back(e1); s->ev.push_back(e2); s->ev.push_back(e3);
-        HIP_TRY(hipEventRecord(e0, stream));
-    }
+    hipEvent_t ev[4];
+    if (int rc = timing_events(s, ev)) return rc;
+    if (ev[0]) HIP_TRY(hipEventRecord(ev[0], stream));
 
-    // 1. centroid probe: the re-rank kernel over the centroid matrix, k = nprobe
-    StreamArgs pa{};
-    pa.mat = s->d_centroids.as<float>(); pa.row_of = nullptr; pa.list_off = nullptr;
-    pa.probe = nullptr; pa.cand_base = nullptr;
-    pa.single_begin = 0; pa.single_end = s->n_clusters;
-    pa.queries = d_queries; pa.nq = nq; pa.nprobe = 1; pa.dim = s->dim; pa.k = p.np;
-    pa.rows_per_block = 256; pa.blocks_per_list = p.probe_bpl;
-    pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;   // find_closest_centroids always uses index.rs:461
-    pa.part_keys = sc.s_probe_keys.as<uint64_t>(); pa.part_vals = sc.s_probe_vals.as<uint32_t>();
     const uint32_t kc_pairs = s->n_clusters;
-    uint32_t *pair_u32 = nullptr;
+    uint32_t *pair_u32 = nullptr, zero_n = 0;
     if (p.tile) {
         // u32 scratch: hist[R][kc] cursor[R][kc] pair_off[kc+1] group_off[kc+1] n_groups[1] quad_off[kc+1] n_quads[1]
         // (R = HIST_REPLICAS partial copies); the probe kernel zeroes hist, the probe merge fills it, the scan sets cursor
         constexpr uint64_t R = pqv::HIST_REPLICAS;
         HIP_TRY(sc.s_pair_u32.ensure(((2 * R + 5) * kc_pairs + 10) * sizeof(uint32_t)));      // + item_off[kc+1] n_items[1] wide_item_off[kc+1] wide_n_items[1]
         pair_u32 = sc.s_pair_u32.as<uint32_t>();
-        pa.zero_u32 = pair_u32; pa.zero_n = static_cast<uint32_t>(R * kc_pairs);
+        zero_n = static_cast<uint32_t>(R * kc_pairs);
         HIP_TRY(sc.s_gthr.ensure(static_cast<size_t>(nq) * sizeof(unsigned long long)));
         if (p.filter) { HIP_TRY(sc.s_qnorm.ensure(static_cast<size_t>(nq) * sizeof(float))); HIP_TRY(sc.s_qmax.ensure(static_cast<size_t>(nq) * sizeof(float))); }
     }
     // one query on the wide screened path: probe, probe merge, bucketing and quantisation in ONE block (probe_single_kernel)
-    // (table searchers: never -- the batched probe and the pair sort, see enqueue_table_probe)
+    // (table searchers: never -- the batched probe and the pair sort)
     const bool fused_probe = nq == 1 && p.np <= 64 && p.tile && p.filter && p.quad && s->opt.single_bucket > 0 &&
                              s->opt.single_bucket != 2 && s->kc_pad != 0 && s->kc_pad <= 4096 && !s->n_files;
-    if (fused_probe || s->n_files) {
-        // (launched below, once the merge arguments are complete)
-    } else if (p.probe_rows) {     // a batch: a lane per centroid, the chains of up to 8 queries in registers
-        pqv::ProbeRowsArgs pr{};
-        pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_queries;
-        pr.nq = nq; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
-        pr.part_keys = pa.part_keys; pr.part_vals = pa.part_vals;
-        pr.zero_u32 = pa.zero_u32; pr.zero_n = pa.zero_n;
-        HIP_TRY(pqv::launch_probe_rows(pr, stream));
-    } else {
-        HIP_TRY(launch_stream(pa, STREAM_TOPK, stream));
-    }
-
-    MergeArgs pm{};
-    pm.part_keys = pa.part_keys; pm.part_vals = pa.part_vals;
-    pm.nq = nq; pm.n_part = p.n_part_probe; pm.k_part = p.probe_kpart; pm.k = p.np;
-    pm.list_off = s->d_list_off.as<uint64_t>();
-    pm.probe = sc.s_probe.as<uint32_t>(); pm.cand_base = sc.s_cand_base.as<uint64_t>();
-    pm.n_cand = d_n_cand ? d_n_cand : sc.s_ncand.as<uint64_t>();
-    pm.max_pos = max_pos;
-    pm.stats = s->d_stats.as<unsigned long long>();
     if (p.tile) {
         pm.hist = pair_u32; pm.hist_stride = kc_pairs; pm.gthr_init = sc.s_gthr.as<unsigned long long>();
         // every partial list of the re-rank starts EMPTY: preset by the probe merge (one wave per query)
@@ -3390,10 +3412,8 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         // (the image(s) of a one-query call are made inside the probe launch)
         quant_done = pq_args.n_pairs != 0;
         HIP_TRY(pqv::launch_probe_single(pr, pm, sc.s_ticket.as<uint32_t>(), quant_done ? &pq_args : nullptr, stream));
-    } else if (s->n_files) {
-        if (int rc = enqueue_table_probe(s, sc, p, d_queries, nq, nprobe, pa.zero_u32, pa.zero_n, pm, stream, max_candidates)) return rc;
     } else {
-        HIP_TRY(launch_merge_probe(pm, stream));
+        if (int rc = enqueue_probe(s, sc, p, d_queries, nq, nprobe, max_candidates, pm, pair_u32, zero_n, stream)) return rc;
     }
     const uint64_t *pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
 
@@ -3500,7 +3520,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
             }
         }
         if (p.filter) ta.query_norm2 = sc.s_qnorm.as<float>();     // filled by the probe merge
-        if (timing) HIP_TRY(hipEventRecord(e1, stream));
+        if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
         if (p.filter && p.quad) {
             const uint32_t ccap = cand_cap_for(s, k);
             HIP_TRY(sc.s_cand_keys.ensure(static_cast<size_t>(nq) * ccap * sizeof(uint64_t)));
@@ -3613,7 +3633,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
             ta.row_offset = 0; ta.slot_base = 0; ta.grid_x = p.rr_bpl;
             HIP_TRY(launch_tile_rerank(ta, stream));
         }
-        if (timing) HIP_TRY(hipEventRecord(e2, stream));
+        if (ev[2]) HIP_TRY(hipEventRecord(ev[2], stream));
         s->counters.kernel_launches += 3;
     }
     StreamArgs ra{};
@@ -3624,9 +3644,9 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     ra.max_pos = max_pos; ra.pair_end = pair_end; ra.metric = metric;
     ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
     if (!p.tile) {
-        if (timing) HIP_TRY(hipEventRecord(e1, stream));
+        if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
         HIP_TRY(launch_stream(ra, STREAM_TOPK, stream));
-        if (timing) HIP_TRY(hipEventRecord(e2, stream));
+        if (ev[2]) HIP_TRY(hipEventRecord(ev[2], stream));
     }
 
     // 3. fold the per-wave lists
@@ -3643,7 +3663,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     }
     if (use_defer) fm.zero_after = sc.s_nwork.as<uint32_t>();
     HIP_TRY(launch_merge_final(fm, stream));
-    if (timing) HIP_TRY(hipEventRecord(e3, stream));
+    if (ev[3]) HIP_TRY(hipEventRecord(ev[3], stream));
     if (int rc = lane_release(sc, stream)) return rc;
     s->counters.kernel_launches += 4;
     return PQV_OK;
@@ -3654,6 +3674,16 @@ int validate_topk(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric
     if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");                         // search.rs:67
     if (nprobe == 0) return fail(PQV_ERR_INVALID, "nprobe must be > 0");               // search.rs:72
     if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ) return fail(PQV_ERR_INVALID, "unknown metric");
+    return PQV_OK;
+}
+// ... and of the entry points that take queries from the host (pqv_topk, pqv_range_search with k = 1, pqv_probe with k = 1 and
+// PQV_L2SQ_REF4: neither takes a k, pqv_probe no metric)
+int validate_query(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric, uint64_t max_candidates, uint32_t query_len) {
+    if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (int rc = table_max_candidates(s, max_candidates)) return rc;
+    if (query_len != s->dim)                                                           // search.rs:91-98
+        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) +
+                                         ", got " + std::to_string(query_len));
     return PQV_OK;
 }
 // the kernels' sorted lists hold up to 1024 entries (k, and the probe's min(nprobe, n_clusters)); pqv_topk goes around
@@ -3783,10 +3813,6 @@ int replay_query_exact(const pqv_searcher *s, Scratch &sc, const float *d_query,
                                 metric, sqrt_out, row_idx, dist, n_found, nprobe);
 }
 
-// topk() beyond the kernels' list capacity (k >= 1024: no runner-up slot left; min(nprobe, n_clusters) > 1024): the
-// reference accepts any NonZeroUsize (search.rs:56-81).  Per query: every centroid distance on the GPU (STREAM_DIST over
-// the centroid table), find_closest_centroids' stable sort + take(nprobe) on the host (index.rs:143-148), every
-// candidate distance on the GPU, the reference's heap on the host.  Correct for any k / nprobe; not a fast path.
 // find_closest_centroids (index.rs:130-149) without the kernels' list limit: every centroid distance on the GPU
 // (STREAM_DIST over the centroid table), the stable sort on the host.  d_query: device [dim]; order: all clusters, nearest first.
 // (a table searcher: the probed lists only -- see below; `nprobe` is read on tables only)
@@ -3825,33 +3851,64 @@ int centroid_order_host(const pqv_searcher *s, Scratch &sc, const float *d_query
     return PQV_OK;
 }
 
+// The centroid probe on the host (P > 1024; topk_unbounded): per query (device, dim wide) centroid_order_host -> its P probed lists
+// in clusters [nq * P], its candidate total in totals[q].  With `upload` also what enqueue_probe leaves: sc.s_probe / s_cand_base
+// and, on a round-robin capped table (table_rr), sc.s_pair_end (table_pair_ends).
+int host_probe(const pqv_searcher *s, Scratch &sc, const float *d_queries, uint32_t nq, uint32_t nprobe, uint64_t max_candidates,
+               bool upload, std::vector<uint32_t> &clusters, uint64_t *totals) {
+    const uint32_t np = probe_count(s, nprobe);
+    const size_t n = static_cast<size_t>(nq) * np;
+    const bool rr = upload && table_rr(s, max_candidates);
+    std::vector<uint32_t> order;
+    std::vector<uint64_t> base(upload ? n : 0), end(rr ? n : 0), end_q;
+    clusters.resize(n);
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (int rc = centroid_order_host(s, sc, d_queries + static_cast<uint64_t>(q) * s->dim, order, nprobe)) return rc;
+        order.resize(np);
+        uint64_t total = 0;
+        for (uint32_t j = 0; j < np; ++j) {
+            clusters[static_cast<size_t>(q) * np + j] = order[j];
+            if (upload) base[static_cast<size_t>(q) * np + j] = total;
+            total += s->h_list_off[order[j] + 1] - s->h_list_off[order[j]];
+        }
+        if (rr) {
+            table_pair_ends(s, order, nprobe, max_candidates, end_q);
+            std::copy(end_q.begin(), end_q.end(), end.begin() + static_cast<size_t>(q) * np);
+        }
+        totals[q] = total;
+    }
+    if (!upload) return PQV_OK;
+    if (int rc = ensure_probe_slots(s, sc, nq, np)) return rc;
+    HIP_TRY(hipMemcpyAsync(sc.s_probe.p, clusters.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(sc.s_cand_base.p, base.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+    if (rr) {
+        HIP_TRY(sc.s_pair_end.ensure(n * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpyAsync(sc.s_pair_end.p, end.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+    }
+    return PQV_OK;
+}
+
+// topk() beyond the kernels' list capacity (k >= 1024: no runner-up slot left; min(nprobe, n_clusters) > 1024): the
+// reference accepts any NonZeroUsize (search.rs:56-81).  Per query: host_probe, every
+// candidate distance on the GPU, the reference's heap on the host.  Correct for any k / nprobe; not a fast path.
 int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                    uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found,
                    uint64_t *n_candidates) {
     using namespace pqv;
-    const uint32_t np = probe_count(s, nprobe);
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
-    HIP_TRY(sc.s_probe.ensure(std::max<size_t>(1, np) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_cand_base.ensure(std::max<size_t>(1, np) * sizeof(uint64_t)));
-    std::vector<uint32_t> order, clusters(np);
-    std::vector<uint64_t> base(np);
+    std::vector<uint32_t> clusters;
     for (uint32_t q = 0; q < nq; ++q) {
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q) * s->dim, static_cast<size_t>(s->dim) * sizeof(float),
                                hipMemcpyHostToDevice, s->stream));
-        if (int rc = centroid_order_host(s, sc, sc.s_queries.as<float>(), order, nprobe)) return rc;
+        uint64_t total = 0;
+        // (no pair ends: the replay applies a table's round-robin cap on the host)
+        if (int rc = host_probe(s, sc, sc.s_queries.as<float>(), 1, nprobe, 0, true, clusters, &total)) return rc;
         const float *d_q_s = sc.s_queries.as<float>();
         if (s->sdim != s->dim) {
             HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(s->sdim) * sizeof(float)));
             HIP_TRY(launch_pad_rows(sc.s_queries.as<float>(), nullptr, 1, s->dim, s->sdim, sc.s_qpad.as<float>(), s->stream));
             d_q_s = sc.s_qpad.as<float>();
         }
-        uint64_t total = 0;
-        for (uint32_t j = 0; j < np; ++j) {
-            clusters[j] = order[j]; base[j] = total;
-            total += s->h_list_off[order[j] + 1] - s->h_list_off[order[j]];
-        }
-        HIP_TRY(hipMemcpyAsync(sc.s_probe.p, clusters.data(), static_cast<size_t>(np) * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(sc.s_cand_base.p, base.data(), static_cast<size_t>(np) * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
         uint32_t nf = 0;
         if (int rc = replay_with_clusters(s, sc, d_q_s, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(),
                                           clusters, k, max_candidates, metric, sqrt_out, row_idx + static_cast<uint64_t>(q) * k,
@@ -3913,11 +3970,7 @@ extern "C" int pqv_topk_device_flags(const pqv_searcher *s, const void *d_querie
 static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len,
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                         uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
-    if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
-    if (int rc = table_max_candidates(s, max_candidates)) return rc;
-    if (query_len != s->dim)                                                           // search.rs:91-98
-        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) +
-                                         ", got " + std::to_string(query_len));
+    if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
     if (int rc = use_device(s->device)) return rc;
@@ -4037,9 +4090,8 @@ extern "C" int pqv_topk(const pqv_searcher *s, const float *queries, uint32_t nq
 }
 
 // ---- range search ----------------------------------------------------------------------------------------------------
-// Every candidate within `radius` of each query (pqv.h: pqv_range_search).  Per sub-batch of queries: the batched probe
-// (probe_rows_kernel or stream_kernel over the centroids, then merge_kernel PROBE; beyond the kernels' 1024-entry lists
-// find_closest_centroids per query through centroid_order_host), ONE stream_kernel STREAM_RANGE pass that appends every hit
+// Every candidate within `radius` of each query (pqv.h: pqv_range_search).  Per sub-batch of queries: the probe (enqueue_probe;
+// beyond the kernels' 1024-entry lists host_probe), ONE stream_kernel STREAM_RANGE pass that appends every hit
 // to its query's segment, ONE synchronisation for the hit counts (the output is sized from them), then the segments sorted
 // by (d2, candidate position) and written out on the device (kernels_range.hip) and copied back.
 namespace {
@@ -4084,30 +4136,24 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
     const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>({nq, 65535ull, (1ull << 30) / per_query})));
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
     if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(batch) * s->sdim * sizeof(float)));
-    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(batch) * std::max<uint32_t>(np, s->n_files) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(batch) * std::max<uint32_t>(np, s->n_files) * sizeof(uint64_t)));
     HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
     HIP_TRY(sc.s_hit_cnt.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     HIP_TRY(sc.s_hit_keys.ensure(static_cast<size_t>(batch) * stride * sizeof(uint64_t)));
     HIP_TRY(sc.s_hit_vals.ensure(static_cast<size_t>(batch) * stride * sizeof(uint32_t)));
     HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
-    std::vector<uint32_t> h_cnt(batch), h_probe, order;
-    std::vector<uint64_t> h_ncand(batch), h_off(batch), h_base, h_end, pair_end_q;
+    std::vector<uint32_t> h_cnt(batch), h_probe;
+    std::vector<uint64_t> h_ncand(batch), h_off(batch);
     std::vector<RangeSeg> segs;
     uint64_t cap_rows = 1, cap_dist = 1;      // entries the library buffers have room for
     const uint64_t max_len = std::max<uint64_t>(1, s->max_list_len);
     for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
         const uint32_t b = std::min<uint32_t>(batch, nq - q0);
         uint32_t launches = 0;
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-        if (s->timing) {     // pqv_timing_read: the STREAM_RANGE pass as the "re-rank", probe .. write-out as the total
-            HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-            HIP_TRY(hipEventCreate(&e2)); HIP_TRY(hipEventCreate(&e3));
-            s->ev.push_back(e0); s->ev.push_back(e1); s->ev.push_back(e2); s->ev.push_back(e3);
-        }
+        hipEvent_t e[4];     // pqv_timing_read: the STREAM_RANGE pass as the "re-rank", probe .. write-out as the total
+        if (int rc = timing_events(s, e)) return rc;
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
                                hipMemcpyHostToDevice, st));
-        if (e0) HIP_TRY(hipEventRecord(e0, st));
+        if (e[0]) HIP_TRY(hipEventRecord(e[0], st));
         const float *d_q = sc.s_queries.as<float>(), *d_q_s = d_q;
         if (s->sdim != s->dim) {
             HIP_TRY(launch_pad_rows(d_q, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), st));
@@ -4116,65 +4162,17 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         }
         if (!wide_probe) {
             const TopkPlan p = plan_topk(s, b, nprobe, 1, metric);
-            HIP_TRY(sc.s_probe_keys.ensure(static_cast<size_t>(b) * p.n_part_probe * p.probe_kpart * sizeof(uint64_t)));
-            HIP_TRY(sc.s_probe_vals.ensure(static_cast<size_t>(b) * p.n_part_probe * p.probe_kpart * sizeof(uint32_t)));
-            if (s->n_files) {
-                // (a table: launched with the merge, enqueue_table_probe)
-            } else if (p.probe_rows) {
-                ProbeRowsArgs pr{};
-                pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_q;
-                pr.nq = b; pr.kc = kc; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
-                pr.part_keys = sc.s_probe_keys.as<uint64_t>(); pr.part_vals = sc.s_probe_vals.as<uint32_t>();
-                HIP_TRY(launch_probe_rows(pr, st));
-            } else {
-                StreamArgs pa{};
-                pa.mat = s->d_centroids.as<float>();
-                pa.single_begin = 0; pa.single_end = kc;
-                pa.queries = d_q; pa.nq = b; pa.nprobe = 1; pa.dim = s->dim; pa.k = p.np;
-                pa.rows_per_block = 256; pa.blocks_per_list = p.probe_bpl;
-                pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;   // find_closest_centroids always uses index.rs:461
-                pa.part_keys = sc.s_probe_keys.as<uint64_t>(); pa.part_vals = sc.s_probe_vals.as<uint32_t>();
-                HIP_TRY(launch_stream(pa, STREAM_TOPK, st));
-            }
             MergeArgs pm{};
-            pm.part_keys = sc.s_probe_keys.as<uint64_t>(); pm.part_vals = sc.s_probe_vals.as<uint32_t>();
-            pm.nq = b; pm.n_part = p.n_part_probe; pm.k_part = p.probe_kpart; pm.k = p.np;
-            pm.list_off = s->d_list_off.as<uint64_t>();
-            pm.probe = sc.s_probe.as<uint32_t>(); pm.cand_base = sc.s_cand_base.as<uint64_t>();
-            pm.n_cand = sc.s_ncand.as<uint64_t>(); pm.max_pos = max_pos;
+            if (int rc = probe_merge_args(s, sc, p, b, max_candidates, pm)) return rc;
             pm.stats = s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
-            if (s->n_files) {
-                if (int rc = enqueue_table_probe(s, sc, p, d_q, b, nprobe, nullptr, 0, pm, st, max_candidates)) return rc;
-            } else
-            HIP_TRY(launch_merge_probe(pm, st));
+            if (int rc = enqueue_probe(s, sc, p, d_q, b, nprobe, max_candidates, pm, nullptr, 0, st)) return rc;
             launches += 2;
         } else {
-            // find_closest_centroids without the kernels' list limit (as topk_unbounded): the order of every centroid per query
-            h_probe.resize(static_cast<size_t>(b) * np);
-            h_base.resize(static_cast<size_t>(b) * np);
-            if (table_rr(s, max_candidates)) h_end.resize(static_cast<size_t>(b) * np);
+            // find_closest_centroids without the kernels' list limit (as topk_unbounded)
+            if (int rc = host_probe(s, sc, d_q, b, nprobe, max_candidates, true, h_probe, h_ncand.data())) return rc;
             for (uint32_t i = 0; i < b; ++i) {
-                if (int rc = centroid_order_host(s, sc, d_q + static_cast<uint64_t>(i) * s->dim, order, nprobe)) return rc;
-                uint64_t total = 0;
-                for (uint32_t j = 0; j < np; ++j) {
-                    h_probe[static_cast<size_t>(i) * np + j] = order[j];
-                    h_base[static_cast<size_t>(i) * np + j] = total;
-                    total += s->h_list_off[order[j] + 1] - s->h_list_off[order[j]];
-                }
-                if (!h_end.empty()) {
-                    order.resize(np);
-                    table_pair_ends(s, order, nprobe, max_candidates, pair_end_q);
-                    std::copy(pair_end_q.begin(), pair_end_q.end(), h_end.begin() + static_cast<size_t>(i) * np);
-                }
-                h_ncand[i] = total;
-                s->counters.candidate_rows += total;                              // index_exec.rs:289-299
-                s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(total, max_candidates) : total;
-            }
-            HIP_TRY(hipMemcpyAsync(sc.s_probe.p, h_probe.data(), h_probe.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(sc.s_cand_base.p, h_base.data(), h_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            if (!h_end.empty()) {
-                HIP_TRY(sc.s_pair_end.ensure(h_end.size() * sizeof(uint64_t)));
-                HIP_TRY(hipMemcpyAsync(sc.s_pair_end.p, h_end.data(), h_end.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+                s->counters.candidate_rows += h_ncand[i];                         // index_exec.rs:289-299
+                s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(h_ncand[i], max_candidates) : h_ncand[i];
             }
         }
 
@@ -4184,26 +4182,19 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         ra.mat = s->d_mat; ra.row_of = s->d_row_of; ra.list_off = s->d_list_off.as<uint64_t>();
         ra.probe = sc.s_probe.as<uint32_t>(); ra.cand_base = sc.s_cand_base.as<uint64_t>();
         ra.queries = d_q_s; ra.nq = b; ra.nprobe = np; ra.dim = s->sdim; ra.k = 1;
-        {   // (the split of stream_kernel's top-k form: enough blocks to fill the chip, lists cut into 256-row multiples)
-            const uint64_t pairs = std::max<uint64_t>(1, static_cast<uint64_t>(b) * np);
-            const uint64_t max_bpl = (max_len + 255) / 256;
-            const uint64_t bpl = std::max<uint64_t>(1, std::min<uint64_t>((8192 + pairs - 1) / pairs, max_bpl));
-            const uint64_t rpb = ((max_len + bpl - 1) / bpl + 255) / 256 * 256;
-            ra.rows_per_block = static_cast<uint32_t>(rpb);
-            ra.blocks_per_list = static_cast<uint32_t>((max_len + rpb - 1) / rpb);
-        }
+        stream_split(max_len, std::max<uint64_t>(1, static_cast<uint64_t>(b) * np), ra.rows_per_block, ra.blocks_per_list);   // (as the top-k form)
         ra.max_pos = max_pos; ra.metric = metric;
         ra.pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
         ra.radius = radius; ra.sqrt_out = sqrt_out ? 1 : 0;
         ra.hit_cnt = sc.s_hit_cnt.as<uint32_t>(); ra.hit_keys = sc.s_hit_keys.as<uint64_t>(); ra.hit_vals = sc.s_hit_vals.as<uint32_t>();
         ra.seg_stride = stride;
-        if (e1) HIP_TRY(hipEventRecord(e1, st));
+        if (e[1]) HIP_TRY(hipEventRecord(e[1], st));
         for (uint32_t j0 = 0; j0 < np; j0 += 32768) {                    // gridDim.y <= 65535
             ra.j0 = j0; ra.nj = std::min<uint32_t>(32768, np - j0);
             HIP_TRY(launch_stream(ra, STREAM_RANGE, st));
             ++launches;
         }
-        if (e2) HIP_TRY(hipEventRecord(e2, st));
+        if (e[2]) HIP_TRY(hipEventRecord(e[2], st));
         HIP_TRY(hipMemcpyAsync(h_cnt.data(), sc.s_hit_cnt.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         if (!wide_probe)
             HIP_TRY(hipMemcpyAsync(h_ncand.data(), sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -4250,12 +4241,12 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
                 HIP_TRY(launch_range_sort_large(sa, max_n, &nl, st));
                 launches += nl;
             }
-            if (e3) HIP_TRY(hipEventRecord(e3, st));
+            if (e[3]) HIP_TRY(hipEventRecord(e[3], st));
             HIP_TRY(hipMemcpyAsync(rows.get() + lims[q0], sc.s_rout_rows.p, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(dist.get() + lims[q0], sc.s_rout_dist.p, tot * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-        } else if (e3) {
-            HIP_TRY(hipEventRecord(e3, st));
+        } else if (e[3]) {
+            HIP_TRY(hipEventRecord(e[3], st));
         }
         s->counters.queries += b;
         s->counters.kernel_launches += launches;
@@ -4268,14 +4259,8 @@ static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, ui
                                  uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                                  uint64_t **lims_out, uint32_t **rows_out, float **dist_out, uint64_t *n_within,
                                  uint64_t *n_candidates) {
-    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
-    if (nprobe == 0) return fail(PQV_ERR_INVALID, "nprobe must be > 0");                          // search.rs:72
-    if (int rc = table_max_candidates(s, max_candidates)) return rc;
-    if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ) return fail(PQV_ERR_INVALID, "unknown metric");
+    if (int rc = validate_query(s, 1, nprobe, metric, max_candidates, query_len)) return rc;
     if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
-    if (query_len != s->dim)                                                                      // search.rs:91-98
-        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) +
-                                         ", got " + std::to_string(query_len));
     if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
     if (nq && !queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
     *lims_out = nullptr; *rows_out = nullptr; *dist_out = nullptr;
@@ -4449,12 +4434,7 @@ static int pqv_searcher_footprint_impl(const pqv_searcher *s, uint64_t *row_orde
     uint64_t other = s->d_centroids.bytes + s->d_cent_t.bytes + s->d_list_off.bytes + s->d_ids.bytes + s->d_stats.bytes + s->d_row_norm2.bytes + s->d_blk_off.bytes +
                      s->d_center.bytes + s->d_list_scale.bytes + s->d_list_half.bytes + s->d_list_radius.bytes + s->d_row_n2i.bytes + s->d_row_res.bytes;
     for (const Scratch &l : s->lanes)
-        for (const DevBuf *b : {&l.s_probe_keys, &l.s_probe_vals, &l.s_probe, &l.s_cand_base, &l.s_ncand, &l.s_part_keys, &l.s_part_vals,
-                                &l.s_queries, &l.s_rows, &l.s_dist, &l.s_nfound, &l.s_pair_u32, &l.s_pairs, &l.s_groups, &l.s_quads, &l.s_items, &l.s_ticket, &l.s_ticket2,
-                                &l.s_cand_keys, &l.s_cand_vals, &l.s_cand_cnt, &l.s_spilled, &l.s_seed_ub, &l.s_qblk, &l.s_gthr, &l.s_tie,
-                                &l.s_replay, &l.s_qnorm, &l.s_qmax, &l.s_thr_hist, &l.s_thr_bins, &l.s_qi8, &l.s_qn2i, &l.s_qres, &l.s_part_flags,
-                                &l.s_qresu, &l.s_pair_lb, &l.s_qpad, &l.s_cand_lb, &l.s_pendv, &l.s_work, &l.s_nwork, &l.s_out})
-            other += b->p ? b->bytes : 0;
+        for (const DevBuf *b : l.bufs()) other += b->p ? b->bytes : 0;
     if (other_bytes) *other_bytes = other;
     return PQV_OK;
 }
@@ -4465,63 +4445,29 @@ extern "C" int pqv_searcher_footprint(const pqv_searcher *s, uint64_t *row_order
 
 static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t query_len, uint32_t nprobe,
                          uint32_t *clusters_out, uint32_t *n_out) {
-    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
-    if (nprobe == 0) return fail(PQV_ERR_INVALID, "nprobe must be > 0");
-    if (query_len != s->dim)
-        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) +
-                                         ", got " + std::to_string(query_len));
+    if (int rc = validate_query(s, 1, nprobe, PQV_L2SQ_REF4, 0, query_len)) return rc;
     if (!query || !clusters_out) return fail(PQV_ERR_INVALID, "query/clusters_out must not be NULL");
     const uint32_t np = probe_count(s, nprobe);
     if (int rc = use_device(s->device)) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
-    using namespace pqv;
     Scratch *lane = nullptr;
     if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
     Scratch &sc = *lane;
     LaneGuard lane_guard{sc, s->stream};
+    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(sc.s_queries.p, query, static_cast<size_t>(s->dim) * sizeof(float), hipMemcpyHostToDevice, s->stream));
     if (np > 1024) {            // beyond the kernels' sorted lists: distances on the GPU, the stable sort on the host
-        HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
-        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, query, static_cast<size_t>(s->dim) * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        std::vector<uint32_t> order;
-        if (int rc = centroid_order_host(s, sc, sc.s_queries.as<float>(), order, nprobe)) return rc;
-        std::memcpy(clusters_out, order.data(), static_cast<size_t>(np) * sizeof(uint32_t));
+        std::vector<uint32_t> clusters;
+        uint64_t total = 0;
+        if (int rc = host_probe(s, sc, sc.s_queries.as<float>(), 1, nprobe, 0, false, clusters, &total)) return rc;
+        std::memcpy(clusters_out, clusters.data(), static_cast<size_t>(np) * sizeof(uint32_t));
         if (n_out) *n_out = np;
         return lane_release(sc, s->stream);
     }
     const TopkPlan p = plan_topk(s, 1, nprobe);
-    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
-    HIP_TRY(sc.s_probe_keys.ensure(static_cast<size_t>(p.n_part_probe) * p.probe_kpart * sizeof(uint64_t)));
-    HIP_TRY(sc.s_probe_vals.ensure(static_cast<size_t>(p.n_part_probe) * p.probe_kpart * sizeof(uint32_t)));
-    HIP_TRY(sc.s_probe.ensure(static_cast<size_t>(std::max<uint32_t>(np, s->n_files)) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_cand_base.ensure(static_cast<size_t>(std::max<uint32_t>(np, s->n_files)) * sizeof(uint64_t)));
-    HIP_TRY(sc.s_ncand.ensure(sizeof(uint64_t)));
-    HIP_TRY(hipMemcpyAsync(sc.s_queries.p, query, static_cast<size_t>(s->dim) * sizeof(float),
-                           hipMemcpyHostToDevice, s->stream));
-    StreamArgs pa{};
-    pa.mat = s->d_centroids.as<float>(); pa.single_begin = 0; pa.single_end = s->n_clusters;
-    pa.queries = sc.s_queries.as<float>(); pa.nq = 1; pa.nprobe = 1; pa.dim = s->dim; pa.k = np;
-    pa.rows_per_block = 256; pa.blocks_per_list = p.probe_bpl; pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;
-    pa.part_keys = sc.s_probe_keys.as<uint64_t>(); pa.part_vals = sc.s_probe_vals.as<uint32_t>();
-    if (s->n_files) {
-        // (a table: launched with the merge, enqueue_table_probe)
-    } else if (p.probe_rows) {
-        pqv::ProbeRowsArgs pr{};
-        pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = pa.queries;
-        pr.nq = 1; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
-        pr.part_keys = pa.part_keys; pr.part_vals = pa.part_vals;
-        HIP_TRY(pqv::launch_probe_rows(pr, s->stream));
-    } else {
-        HIP_TRY(launch_stream(pa, STREAM_TOPK, s->stream));
-    }
-    MergeArgs pm{};
-    pm.part_keys = pa.part_keys; pm.part_vals = pa.part_vals; pm.nq = 1; pm.n_part = p.n_part_probe;
-    pm.k_part = p.probe_kpart; pm.k = np; pm.list_off = s->d_list_off.as<uint64_t>();
-    pm.probe = sc.s_probe.as<uint32_t>(); pm.cand_base = sc.s_cand_base.as<uint64_t>();
-    pm.n_cand = sc.s_ncand.as<uint64_t>(); pm.max_pos = ~0ull;
-    if (s->n_files) {
-        if (int rc = enqueue_table_probe(s, sc, p, pa.queries, 1, nprobe, nullptr, 0, pm, s->stream)) return rc;
-    } else
-    HIP_TRY(launch_merge_probe(pm, s->stream));
+    pqv::MergeArgs pm{};        // (no pm.stats: a probe counts no candidates)
+    if (int rc = probe_merge_args(s, sc, p, 1, 0, pm)) return rc;
+    if (int rc = enqueue_probe(s, sc, p, sc.s_queries.as<float>(), 1, nprobe, 0, pm, nullptr, 0, s->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(clusters_out, sc.s_probe.p, static_cast<size_t>(np) * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, s->stream));
     if (int rc = lane_release(sc, s->stream)) return rc;
