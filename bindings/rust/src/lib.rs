@@ -308,13 +308,24 @@ impl<'c> Searcher<'c> {
     /// `topk()` (`src/ivf/search.rs:83-142`) for a batch of queries (`queries.len() == nq * dim`): identical
     /// results to the reference, ties included (flagged queries are replayed through the reference's heap).
     pub fn topk(&self, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
+        self.topk_metric(queries, dim, k, nprobe, sys::PQV_L2SQ_REF4)
+    }
+
+    /// [`Searcher::topk`] by cosine distance (an extension; `include/pqv.h`: `PQV_COSINE`): the distance is `0.5 * d2` of the
+    /// normalised query and row, `1 - cos` in exact arithmetic.  The first such call builds the searcher's cosine layout.
+    pub fn topk_cosine(&self, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
+        self.topk_metric(queries, dim, k, nprobe, sys::PQV_COSINE)
+    }
+
+    fn topk_metric(&self, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize, metric: c_int)
+        -> Result<Vec<Vec<SearchResult>>> {
         let nq = if dim == 0 { 0 } else { queries.len() / dim };
         let (k, np) = (k.get(), nprobe.get());
         let mut rows = vec![0u32; nq * k];
         let mut dist = vec![0f32; nq * k];
         let mut found = vec![0u32; nq];
         check(unsafe {
-            sys::pqv_topk(self.raw, queries.as_ptr(), nq as u32, dim as u32, k as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1,
+            sys::pqv_topk(self.raw, queries.as_ptr(), nq as u32, dim as u32, k as u32, np as u32, 0, metric, 1,
                           rows.as_mut_ptr(), dist.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((0..nq)
@@ -327,11 +338,23 @@ impl<'c> Searcher<'c> {
     /// by (distance, candidate position); `max_results > 0` keeps the first that many per query.  A NaN radius is an error.
     pub fn range_search(&self, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64)
         -> Result<Vec<Vec<SearchResult>>> {
+        self.range_search_metric(queries, dim, radius, nprobe, max_results, sys::PQV_L2SQ_REF4)
+    }
+
+    /// [`Searcher::range_search`] by cosine distance (`include/pqv.h`: `PQV_COSINE`): hits are the candidates with
+    /// `0.5 * d2 <= radius` (d2 of the normalised vectors), and that is the distance returned.
+    pub fn range_search_cosine(&self, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64)
+        -> Result<Vec<Vec<SearchResult>>> {
+        self.range_search_metric(queries, dim, radius, nprobe, max_results, sys::PQV_COSINE)
+    }
+
+    fn range_search_metric(&self, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64, metric: c_int)
+        -> Result<Vec<Vec<SearchResult>>> {
         let nq = if dim == 0 { 0 } else { queries.len() / dim };
         let (mut lims, mut rows, mut dist) = (ptr::null_mut::<u64>(), ptr::null_mut::<u32>(), ptr::null_mut::<f32>());
         check(unsafe {
             sys::pqv_range_search(self.raw, queries.as_ptr(), nq as u32, dim as u32, radius, nprobe.get() as u32, 0, max_results,
-                                  sys::PQV_L2SQ_REF4, 1, &mut lims, &mut rows, &mut dist, ptr::null_mut(), ptr::null_mut())
+                                  metric, 1, &mut lims, &mut rows, &mut dist, ptr::null_mut(), ptr::null_mut())
         })?;
         if lims.is_null() || rows.is_null() || dist.is_null() {
             unsafe { sys::pqv_range_free(lims, rows, dist) };

@@ -56,6 +56,26 @@ typedef enum pqv_metric {
  * screen's image of the corpus (+ 1 byte per value; PQV_BRUTE_OP=f16: + 2). */
 #define PQV_COSINE      2   /* 1 - q.v / (|q| |v|); zero-norm vectors get distance 1            */
 #define PQV_L2SQ_MFMA   3   /* |q|^2 + |v|^2 - 2 q.v (norm-expansion form, clamped at 0)        */
+/* PQV_COSINE through the index (pqv_topk, pqv_topk_device(_flags), pqv_range_search, pqv_searcher_describe, plain and table
+ * searchers; an EXTENSION like the above, with arithmetic of its own).  With
+ *   sq(v) = the PQV_L2SQ_REF4 chain of v against 0 (index.rs:461-480: 4-grouped, the tail element by element),
+ *   r(v)  = 1.0f / sqrtf(sq(v)) (correctly rounded sqrt and division), 0 where sq(v) == 0,
+ *   n(v)  = v_i * r(v) (one f32 multiply per value),
+ * a cosine call returns exactly what the same call with PQV_L2SQ_REF4 and sqrt_out = 0 returns on a searcher over
+ * Index.from_parts(dim, n(centroids) row by row, the same lists) and a corpus of n(x) for every row x, with the queries replaced by
+ * n(q) -- row ids, n_found, n_candidates, counters, the tie rules (pqv_topk replays the heap on tied d2, pqv_topk_device orders by
+ * (d2, position)), max_candidates (a table's round-robin cap too), a table's per-file nprobe, the device entry points' limits and the
+ * range order included -- except that every distance is the f32 product 0.5f * d2: half the squared distance of the unit vectors,
+ * 1 - cos(q, x) in exact arithmetic without the cancellation of 1 - q.x / (|q||x|) near 0.  So the probe ranks centroids by cosine
+ * (ties by centroid id) and scaling q by a power of two changes no bit.  sqrt_out is ignored (the output is always this distance);
+ * pqv_range_search's hit test is 0.5f * d2 <= radius.  ZERO vectors: a zero row or centroid normalises to 0 (distance
+ * 0.5 * sq(n(q)) from a query), a zero query to 0 (every row at 0.5 * sq(n(x))) -- unlike pqv_brute_topk, which gives them 1.
+ * The first cosine call on a searcher (or PQV_PREPARE_COSINE at creation) builds its cosine layout under the searcher's lock,
+ * synchronously: the normalised centroid table and rows (one more f32 copy of the column, counted by pqv_searcher_footprint) and
+ * the screen operands made from them; until then no L2 call or buffer is touched.  A failed build (PQV_ERR_OOM, ...) leaves the
+ * searcher as it was.  Cosine queries are normalised on the device (one extra launch on the call's stream; pqv_topk_device stays
+ * asynchronous after the first call); the halving is part of the final write-out.  pqv_rerank* and PQV_L2SQ_MFMA stay as they are:
+ * no cosine through the index for the first, brute force only for the second. */
 
 /* pqv_searcher_create flags */
 #define PQV_LAYOUT_IVF_ORDERED   0x0u /* copy rows into cluster-contiguous order in HBM (default) */
@@ -66,6 +86,8 @@ typedef enum pqv_metric {
                                          copy of the column resident either way                                              */
 #define PQV_TABLE_CAP_ROUND_ROBIN 0x8u /* pqv_table_searcher_create: max_candidates is dealt out round robin over the files
                                           (see there); ignored by pqv_searcher_create                                         */
+#define PQV_PREPARE_COSINE      0x10u  /* build the PQV_COSINE layout at creation (see PQV_COSINE), so that no query pays for it; the
+                                          searcher is not returned when that fails                                             */
 
 typedef struct pqv_index    pqv_index;    /* IvfIndex: dim, n_clusters, centroids, inverted lists */
 typedef struct pqv_corpus   pqv_corpus;   /* the embedding column, resident in one GPU's HBM     */
@@ -273,11 +295,13 @@ int pqv_round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max
  * (profiling scripts). */
 int pqv_searcher_set_option(pqv_searcher *searcher, const char *name, int64_t value);
 /* Which kernels a pqv_topk_device call of this shape would run on this searcher (one line of text, for bench
- * records): written NUL-terminated into buf (truncated to len). */
+ * records): written NUL-terminated into buf (truncated to len).  PQV_COSINE: the query normalisation, then the dispatch of the
+ * searcher's cosine layout (of this searcher's L2 dispatch while that layout is not built). */
 int pqv_searcher_describe(const pqv_searcher *searcher, uint32_t nq, uint32_t k, uint32_t nprobe, int metric,
                           char *buf, size_t len);
 /* Device memory held for this searcher, in bytes: the corpus' row-order copy (0 once released), the IVF-ordered
- * f32 rows, the blocked screen-operand copy, and everything else (centroids, lists, norms, scratch lanes). */
+ * f32 rows, the blocked screen-operand copy, and everything else (centroids, lists, norms, scratch lanes).  Once the PQV_COSINE
+ * layout is built its buffers are added to the same four classes (its normalised rows to the first or the second). */
 int pqv_searcher_footprint(const pqv_searcher *searcher, uint64_t *row_order_bytes, uint64_t *ivf_rows_bytes,
                            uint64_t *blocked_bytes, uint64_t *other_bytes);
 
@@ -296,8 +320,9 @@ void pqv_rows_free(uint32_t *rows);
  *   max_candidates  0 => none; else the CandidateCursor cap (src/df_vector/access.rs:
  *                   214-242, single file): only the first max_candidates candidates in
  *                   probe-rank order are considered
- *   metric       PQV_L2SQ_REF4 (TopkBuilder) or PQV_L2SQ_SEQ (VectorTopKExec)
- *   sqrt_out     nonzero => dist = sqrt(d2) as TopkBuilder returns (:133); 0 => d2
+ *   metric       PQV_L2SQ_REF4 (TopkBuilder), PQV_L2SQ_SEQ (VectorTopKExec) or PQV_COSINE (0.5f * d2 of the normalised
+ *                vectors: see PQV_COSINE)
+ *   sqrt_out     nonzero => dist = sqrt(d2) as TopkBuilder returns (:133); 0 => d2 (ignored for PQV_COSINE)
  *   row_idx/dist host [nq*k]; entries past n_found[q] are 0xFFFFFFFF / +inf
  * Ties: when two of a query's k results (or the k-th and the runner-up) have EQUAL output
  * distance, which rows survive and in what order is an artefact of Rust's BinaryHeap sift
@@ -320,7 +345,9 @@ int pqv_topk(const pqv_searcher *searcher, const float *queries, uint32_t nq,
  * whose next operation runs on the default stream (torch.cuda.current_stream() outside a stream
  * context) must pass an explicit stream -- hipStreamLegacy, ((hipStream_t)1), names the default stream itself -- or
  * synchronise) and the call returns without
- * synchronising.  d_n_found / d_n_candidates may be NULL.  This is what bench.py times. */
+ * synchronising.  d_n_found / d_n_candidates may be NULL.  This is what bench.py times.  PQV_COSINE (see there): n(q) is computed
+ * on `hip_stream` into the searcher's scratch, the halving happens in the final merge; the first cosine call on a searcher builds
+ * its cosine layout and synchronises once. */
 int pqv_topk_device(const pqv_searcher *searcher, const void *d_queries, uint32_t nq,
                     uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric,
                     int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found,
@@ -339,7 +366,8 @@ int pqv_topk_device_flags(const pqv_searcher *searcher, const void *d_queries, u
  *   candidates   candidate_rows(q, nprobe) (probe-rank order, list order inside a list), the first max_candidates of them
  *                when max_candidates > 0 (as pqv_topk); a candidate's position is its index in that sequence.  nprobe is
  *                clamped to n_clusters and may exceed 1024.
- *   distance     d2 of `metric` (bit-identical to pqv_topk's); out = sqrt_out ? sqrt(d2) (correctly rounded) : d2.
+ *   distance     d2 of `metric` (bit-identical to pqv_topk's); out = sqrt_out ? sqrt(d2) (correctly rounded) : d2.  PQV_COSINE:
+ *                d2 of the normalised vectors, out = 0.5f * d2 whatever sqrt_out (see PQV_COSINE).
  *   hit          out <= radius (inclusive, on the output scale).  A NaN distance is never a hit; radius = +inf keeps every
  *                other candidate, a negative radius none; a NaN radius is PQV_ERR_INVALID ("radius must not be NaN").
  *   order        ascending by (d2, position): unique per query, independent of scheduling.

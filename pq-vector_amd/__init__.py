@@ -23,11 +23,11 @@ from .api import (CandidateCursor, Corpus, Index, IndexBuilder, PqvError, RangeB
                   rerank_finish, round_robin_quota, searcher_for_parquet, searcher_for_parquet_files, split_table_rows)
 from .parquet_io import has_pq_vector_index, read_index_from_parquet
 from ._ffi import (PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE, PQV_L2SQ_MFMA, PQV_LAYOUT_IVF_ORDERED, PQV_LAYOUT_ROW_ORDER,
-                   PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, LIB_PATH)
+                   PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, PQV_PREPARE_COSINE, LIB_PATH)
 
 __all__ = ["CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
            "TopkBuilder", "TableRangeBuilder", "TableSearcher", "TableSearchResult", "TableTopkBuilder", "searcher_for_parquet_files",
            "split_table_rows", "device_count", "merge_topk", "rerank_batch", "rerank_finish", "searcher_for_parquet", "PQV_COSINE", "PQV_L2SQ_MFMA",
            "has_pq_vector_index", "read_index_from_parquet", "PQV_L2SQ_REF4",
            "PQV_L2SQ_SEQ", "PQV_LAYOUT_IVF_ORDERED", "PQV_LAYOUT_ROW_ORDER",
-           "PQV_RELEASE_ROW_ORDER", "PQV_RELEASE_IF_COPIED", "PQV_TABLE_CAP_ROUND_ROBIN", "round_robin_quota", "LIB_PATH"]
+           "PQV_RELEASE_ROW_ORDER", "PQV_RELEASE_IF_COPIED", "PQV_TABLE_CAP_ROUND_ROBIN", "PQV_PREPARE_COSINE", "round_robin_quota", "LIB_PATH"]

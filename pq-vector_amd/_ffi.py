@@ -35,6 +35,7 @@ PQV_LAYOUT_ROW_ORDER = 0x1
 PQV_RELEASE_ROW_ORDER = 0x2
 PQV_RELEASE_IF_COPIED = 0x4
 PQV_TABLE_CAP_ROUND_ROBIN = 0x8      # pqv_table_searcher_create: max_candidates dealt out round robin over the files
+PQV_PREPARE_COSINE = 0x10            # build the PQV_COSINE layout at creation (pqv.h: PQV_COSINE)
 
 
 class Counters(C.Structure):

@@ -568,9 +568,17 @@ def searcher_for_parquet(path, device=0):
     return hit
 
 
+def _metric_arg(m):
+    """The metric of a builder: PQV_L2SQ_REF4 (the default) or PQV_COSINE (pqv.h: PQV_COSINE)."""
+    if isinstance(m, bool) or not isinstance(m, int) or m not in (_ffi.PQV_L2SQ_REF4, _ffi.PQV_COSINE):
+        raise PqvError(_ffi.PQV_ERR_INVALID, "unknown metric")
+    return int(m)
+
+
 class TopkBuilder:
     """src/ivf/search.rs:49-81: k and nprobe must be set and > 0.  `source` is an indexed
-    Parquet path (as in the reference) or an existing Searcher."""
+    Parquet path (as in the reference) or an existing Searcher.  metric(m): PQV_L2SQ_REF4 (default, distances
+    sqrt(d2) as the reference returns them) or PQV_COSINE (0.5 * d2 of the normalised vectors, pqv.h: PQV_COSINE)."""
 
     def __init__(self, source, query, device=0):
         import os
@@ -582,6 +590,11 @@ class TopkBuilder:
         self._query = query
         self._k = None
         self._nprobe = None
+        self._metric = _ffi.PQV_L2SQ_REF4
+
+    def metric(self, m):
+        self._metric = _metric_arg(m)
+        return self
 
     def k(self, k):
         if k == 0:
@@ -602,7 +615,7 @@ class TopkBuilder:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
-        rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe)
+        rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric)
         n = int(nf[0])
         return [SearchResult(r, d) for r, d in zip(rows[0, :n].tolist(), dist[0, :n].tolist())]
 
@@ -610,7 +623,7 @@ class TopkBuilder:
 class RangeBuilder:
     """Range counterpart of TopkBuilder: every row within `radius` of the query, nearest first (ties by candidate
     position).  radius and nprobe must be set; max_results (optional, > 0) keeps the first that many.  `source` is an
-    indexed Parquet path or an existing Searcher."""
+    indexed Parquet path or an existing Searcher.  metric(m): as TopkBuilder's (PQV_COSINE: radius on the 0.5 * d2 scale)."""
 
     def __init__(self, source, query, device=0):
         import os
@@ -623,6 +636,11 @@ class RangeBuilder:
         self._radius = None
         self._nprobe = None
         self._max_results = 0
+        self._metric = _ffi.PQV_L2SQ_REF4
+
+    def metric(self, m):
+        self._metric = _metric_arg(m)
+        return self
 
     def radius(self, radius):
         radius = float(radius)
@@ -649,7 +667,7 @@ class RangeBuilder:
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
         _, rows, dist, _, _ = self._searcher.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
-                                                          max_results=self._max_results)
+                                                          max_results=self._max_results, metric=self._metric)
         return [SearchResult(r, d) for r, d in zip(rows.tolist(), dist.tolist())]
 
 
@@ -850,7 +868,8 @@ class TableTopkBuilder(TopkBuilder):
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
-        rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, max_candidates=self._max_candidates)
+        rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, max_candidates=self._max_candidates,
+                                   metric=self._metric)
         n = int(nf[0])
         return _table_results(s, self._paths, rows[0, :n], dist[0, :n])
 
@@ -875,7 +894,7 @@ class TableRangeBuilder(RangeBuilder):
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
         _, rows, dist, _, _ = s.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
-                                             max_candidates=self._max_candidates, max_results=self._max_results)
+                                             max_candidates=self._max_candidates, max_results=self._max_results, metric=self._metric)
         return _table_results(s, self._paths, rows, dist)
 
 

@@ -317,7 +317,8 @@ struct Scratch {
         s_dist, s_nfound, s_pair_u32, s_pairs, s_groups, s_quads, s_items, s_ticket, s_ticket2, s_cand_keys, s_cand_vals, s_cand_cnt, s_spilled,
         s_seed_ub, s_qblk, s_gthr, s_tie, s_replay, s_qnorm, s_qmax, s_thr_hist, s_thr_bins, s_qi8, s_qn2i, s_qres, s_qresu, s_pair_lb, s_part_flags, s_qpad, s_cand_lb, s_pendv, s_work, s_nwork, s_out,
         s_hit_cnt, s_hit_keys, s_hit_vals, s_alt_keys, s_alt_vals, s_rsegs, s_rout_off, s_rout_rows, s_rout_dist,   // s_hit_* .. s_rout_*: pqv_range_search
-        s_pair_end, s_file_cnt;     // round-robin capped tables: per-pair candidate ends, per-file counts (SegProbeArgs)
+        s_pair_end, s_file_cnt,     // round-robin capped tables: per-pair candidate ends, per-file counts (SegProbeArgs)
+        s_qcos;                     // PQV_COSINE: the call's normalised queries n(q), read by the cosine searcher's kernels
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -331,7 +332,7 @@ struct Scratch {
                 &s_dist, &s_nfound, &s_pair_u32, &s_pairs, &s_groups, &s_quads, &s_items, &s_ticket, &s_ticket2, &s_cand_keys, &s_cand_vals, &s_cand_cnt, &s_spilled,
                 &s_seed_ub, &s_qblk, &s_gthr, &s_tie, &s_replay, &s_qnorm, &s_qmax, &s_thr_hist, &s_thr_bins, &s_qi8, &s_qn2i, &s_qres, &s_qresu, &s_pair_lb, &s_part_flags, &s_qpad, &s_cand_lb, &s_pendv, &s_work, &s_nwork, &s_out,
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
-                &s_pair_end, &s_file_cnt};
+                &s_pair_end, &s_file_cnt, &s_qcos};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -451,6 +452,12 @@ struct pqv_searcher {
     // timing
     mutable bool timing = false;
     mutable std::vector<hipEvent_t> ev;    // triples: probe-start, rerank-start, rerank-stop, end
+    // PQV_COSINE (pqv.h): an ordinary searcher of the same layout over the normalised column -- n(c) centroids, the same lists, n(x)
+    // rows in cos_corpus -- made under `mu` by the first cosine call or at creation (PQV_PREPARE_COSINE; ensure_cosine).  Cosine calls
+    // normalise their queries and run the L2 path on it with the distances halved at the write-out.  Declared in this order: the
+    // searcher goes before the corpus it borrows.
+    mutable std::unique_ptr<pqv_corpus> cos_corpus;    // row-order n(x) (its rows released where `cos` keeps an IVF-ordered copy)
+    mutable std::unique_ptr<pqv_searcher> cos;
     ~pqv_searcher();
 };
 pqv_searcher::~pqv_searcher() {
@@ -2795,9 +2802,24 @@ static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, 
     *out = s;
     return PQV_OK;
 }
+static int ensure_cosine(const pqv_searcher *s);
+// PQV_PREPARE_COSINE: the cosine layout now; a searcher whose layout cannot be built is not returned
+static int prepare_cosine(uint32_t flags, pqv_searcher **out) {
+    if (!(flags & PQV_PREPARE_COSINE) || !*out) return PQV_OK;
+    int rc;
+    {
+        std::lock_guard<std::mutex> lock((*out)->mu);
+        rc = ensure_cosine(*out);
+    }
+    if (rc) { pqv_searcher_free(*out); *out = nullptr; }
+    return rc;
+}
 extern "C" int pqv_searcher_create(const pqv_index *index, pqv_corpus *corpus, uint32_t flags,
                                    pqv_searcher **out) {
-    return guard([&] { return pqv_searcher_create_impl(index, corpus, flags, out); });
+    return guard([&] {
+        if (int rc = pqv_searcher_create_impl(index, corpus, flags, out)) return rc;
+        return prepare_cosine(flags, out);
+    });
 }
 
 // A table of indexed files (pqv.h: pqv_table_searcher_create): the files' indexes concatenated into ONE index -- centroid tables
@@ -2877,7 +2899,10 @@ static int pqv_table_searcher_create_impl(const pqv_index *const *indexes, uint3
 }
 extern "C" int pqv_table_searcher_create(const pqv_index *const *indexes, uint32_t n_files, const uint64_t *row_base,
                                          pqv_corpus *corpus, uint32_t flags, pqv_searcher **out) {
-    return guard([&] { return pqv_table_searcher_create_impl(indexes, n_files, row_base, corpus, flags, out); });
+    return guard([&] {
+        if (int rc = pqv_table_searcher_create_impl(indexes, n_files, row_base, corpus, flags, out)) return rc;
+        return prepare_cosine(flags, out);
+    });
 }
 extern "C" int pqv_searcher_files(const pqv_searcher *s, uint32_t *n_files, uint64_t *row_base, uint32_t *cluster_base) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
@@ -2887,6 +2912,57 @@ extern "C" int pqv_searcher_files(const pqv_searcher *s, uint32_t *n_files, uint
         if (row_base) row_base[f] = s->n_files ? s->row_base[f] : 0;
         if (cluster_base) cluster_base[f] = s->n_files ? s->seg_off[f] : 0;
     }
+    return PQV_OK;
+}
+
+// The cosine layout of a searcher (pqv.h: PQV_COSINE), under s->mu: the centroid table and the column normalised on the device
+// (normalize_rows_kernel), then an ordinary searcher over them that shares the index' lists and takes the layout `s` has -- rows
+// read through the list order from the normalised row-order copy (images-only IVF, ROW_ORDER), or an IVF-ordered copy of its own,
+// after which its row-order copy is released: one more f32 copy of the column either way -- with the images, norms and per-list
+// centres its creation builds from those rows.  A table's file segments are copied over.  Any failure leaves `s` as it was.
+static int ensure_cosine(const pqv_searcher *s) {
+    if (s->cos) return PQV_OK;
+    if (int rc = use_device(s->device)) return rc;
+    const uint32_t kc = s->n_clusters, dim = s->dim;
+    pqv_index ni;
+    ni.dim = dim; ni.n_clusters = kc; ni.list_off = s->h_list_off; ni.rows = s->h_rows;
+    try { ni.centroids.resize(static_cast<size_t>(kc) * dim); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+    std::unique_ptr<pqv_corpus> nc(new (std::nothrow) pqv_corpus());
+    if (!nc) return fail(PQV_ERR_OOM, "host allocation failed");
+    const pqv_corpus *src = s->corpus;
+    nc->device = s->device; nc->dim = dim; nc->n = nc->capacity = src->n; nc->owned = true;
+    {
+        DevBuf d_nc;
+        HIP_TRY(d_nc.alloc(std::max<size_t>(1, ni.centroids.size()) * sizeof(float)));
+        HIP_TRY(pqv::launch_normalize_rows(s->d_centroids.as<float>(), dim, nullptr, kc, dim, d_nc.as<float>(), s->stream));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&nc->d_rows), std::max<size_t>(1, src->n) * dim * sizeof(float)));
+        if (src->d_rows) {
+            HIP_TRY(pqv::launch_normalize_rows(src->d_rows, dim, nullptr, src->n, dim, nc->d_rows, s->stream));
+        } else {
+            // the caller's row-order copy was released (PQV_RELEASE_ROW_ORDER): the searcher's own IVF-ordered copy is the source, its
+            // storage rows go back to their file rows (zero padding adds nothing to the chain); rows of no list stay zero
+            HIP_TRY(hipMemsetAsync(nc->d_rows, 0, std::max<size_t>(1, src->n) * dim * sizeof(float), s->stream));
+            HIP_TRY(pqv::launch_normalize_rows(s->d_mat, s->sdim, s->d_final_ids, s->n, dim, nc->d_rows, s->stream));
+        }
+        if (!ni.centroids.empty())
+            HIP_TRY(hipMemcpyAsync(ni.centroids.data(), d_nc.p, ni.centroids.size() * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    const uint32_t flags = s->images_only ? 0u : s->d_row_of ? PQV_LAYOUT_ROW_ORDER : PQV_RELEASE_ROW_ORDER;
+    pqv_searcher *c = nullptr;
+    if (int rc = pqv_searcher_create_impl(&ni, nc.get(), flags, &c)) return rc;
+    std::unique_ptr<pqv_searcher> cu(c);
+    c->opt = s->opt;
+    c->timing = s->timing;
+    if (s->n_files) {
+        c->n_files = s->n_files; c->seg_off = s->seg_off; c->row_base = s->row_base; c->seg_max_kc = s->seg_max_kc; c->rr_cap = s->rr_cap;
+        HIP_TRY(c->d_seg_off.alloc(s->d_seg_off.bytes));
+        HIP_TRY(c->d_seg_off64.alloc(s->d_seg_off64.bytes));
+        HIP_TRY(hipMemcpy(c->d_seg_off.p, s->d_seg_off.p, s->d_seg_off.bytes, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(c->d_seg_off64.p, s->d_seg_off64.p, s->d_seg_off64.bytes, hipMemcpyDeviceToDevice));
+    }
+    s->cos_corpus = std::move(nc);
+    s->cos = std::move(cu);
     return PQV_OK;
 }
 
@@ -3673,7 +3749,7 @@ int validate_topk(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");                         // search.rs:67
     if (nprobe == 0) return fail(PQV_ERR_INVALID, "nprobe must be > 0");               // search.rs:72
-    if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ) return fail(PQV_ERR_INVALID, "unknown metric");
+    if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ && metric != PQV_COSINE) return fail(PQV_ERR_INVALID, "unknown metric");
     return PQV_OK;
 }
 // ... and of the entry points that take queries from the host (pqv_topk, pqv_range_search with k = 1, pqv_probe with k = 1 and
@@ -3790,8 +3866,9 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
             else if (ent.d < heap[0].d) { heap_pop(heap); heap_push(heap, ent); }   // :121-125
         }
     }
-    if (sqrt_out) for (auto &h : heap) h.d = std::sqrt(h.d);             // :133 (IEEE sqrtf)
+    if (sqrt_out == 1) for (auto &h : heap) h.d = std::sqrt(h.d);        // :133 (IEEE sqrtf)
     std::stable_sort(heap.begin(), heap.end(), [](const HeapEnt &a, const HeapEnt &b) { return a.d < b.d; });
+    if (sqrt_out == 2) for (auto &h : heap) h.d = 0.5f * h.d;            // PQV_COSINE: sorted on d2, halved on the way out
     for (uint32_t i = 0; i < k; ++i) {
         if (i < heap.size()) { row_idx[i] = heap[i].row; dist[i] = heap[i].d; }
         else { row_idx[i] = 0xFFFFFFFFu; dist[i] = INFINITY; }
@@ -3926,6 +4003,25 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
 
 }  // namespace
 
+// The host entry points' PQV_COSINE queries: the cosine layout (ensure_cosine), then n(q) of host queries [nq, dim] computed on the device
+// (one normalize_rows_kernel launch on the searcher's stream) and brought back for the cosine searcher's own host entry point.
+static int cosine_queries_host(const pqv_searcher *s, const float *queries, uint32_t nq, std::vector<float> &out) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = ensure_cosine(s)) return rc;
+    const size_t n = static_cast<size_t>(nq) * s->dim;
+    try { out.resize(n); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+    Scratch *lane = nullptr;
+    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
+    LaneGuard lane_guard{*lane, s->stream};
+    HIP_TRY(lane->s_queries.ensure(n * sizeof(float)));
+    HIP_TRY(lane->s_qcos.ensure(n * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(lane->s_queries.p, queries, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(pqv::launch_normalize_rows(lane->s_queries.as<float>(), s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), s->stream));
+    HIP_TRY(hipMemcpyAsync(out.data(), lane->s_qcos.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return lane_release(*lane, s->stream);
+}
+
 static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, uint32_t nq, uint32_t k,
                                uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
@@ -3943,6 +4039,19 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
     std::lock_guard<std::mutex> lock(s->mu);
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
     Scratch *lane = nullptr;
+    if (metric == PQV_COSINE) {
+        // n(q) into this searcher's lane on the caller's stream, then the L2 call of the cosine searcher on the same stream, its
+        // write-out halving d2 (sqrt_out 2); the lane's `done` event follows that call's kernels
+        if (int rc = ensure_cosine(s)) return rc;
+        if (int rc = lane_acquire(s, stream, &lane)) return rc;
+        LaneGuard lane_guard{*lane, stream};
+        HIP_TRY(lane->s_qcos.ensure(static_cast<size_t>(nq) * s->dim * sizeof(float)));
+        HIP_TRY(pqv::launch_normalize_rows(static_cast<const float *>(d_queries), s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), stream));
+        if (int rc = pqv_topk_device_impl(s->cos.get(), lane->s_qcos.p, nq, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
+                                          d_n_found, d_n_candidates, d_tie_flags, stream))
+            return rc;
+        return lane_release(*lane, stream);
+    }
     if (int rc = lane_acquire(s, stream, &lane)) return rc;
     LaneGuard lane_guard{*lane, stream};
     // with flags the kernels carry one extra merged entry (the runner-up), exactly as pqv_topk does
@@ -3957,14 +4066,14 @@ extern "C" int pqv_topk_device(const pqv_searcher *s, const void *d_queries, uin
                                uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                void *hip_stream) {
-    return guard([&] { return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out, d_row_idx, d_dist, d_n_found, d_n_candidates, nullptr, hip_stream); });
+    return guard([&] { return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates, nullptr, hip_stream); });
 }
 extern "C" int pqv_topk_device_flags(const pqv_searcher *s, const void *d_queries, uint32_t nq, uint32_t k,
                                      uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                      void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                      void *d_tie_flags, void *hip_stream) {
     if (!d_tie_flags) return fail(PQV_ERR_INVALID, "d_tie_flags must not be NULL");
-    return guard([&] { return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out, d_row_idx, d_dist, d_n_found, d_n_candidates, d_tie_flags, hip_stream); });
+    return guard([&] { return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates, d_tie_flags, hip_stream); });
 }
 
 static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len,
@@ -3974,6 +4083,12 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
     if (int rc = use_device(s->device)) return rc;
+    if (metric == PQV_COSINE) {
+        std::vector<float> nq_host;
+        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
+        return pqv_topk_impl(s->cos.get(), nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist, n_found,
+                             n_candidates);
+    }
     std::lock_guard<std::mutex> lock(s->mu);
     // One extra merged entry (the runner-up) lets the merge kernel see ties at the k-th
     // distance; queries it flags are replayed through the exact heap (replay_query_exact).
@@ -4086,7 +4201,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
 extern "C" int pqv_topk(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len,
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                         uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
-    return guard([&] { return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates); });
+    return guard([&] { return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates); });
 }
 
 // ---- range search ----------------------------------------------------------------------------------------------------
@@ -4185,7 +4300,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         stream_split(max_len, std::max<uint64_t>(1, static_cast<uint64_t>(b) * np), ra.rows_per_block, ra.blocks_per_list);   // (as the top-k form)
         ra.max_pos = max_pos; ra.metric = metric;
         ra.pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
-        ra.radius = radius; ra.sqrt_out = sqrt_out ? 1 : 0;
+        ra.radius = radius; ra.sqrt_out = sqrt_out;
         ra.hit_cnt = sc.s_hit_cnt.as<uint32_t>(); ra.hit_keys = sc.s_hit_keys.as<uint64_t>(); ra.hit_vals = sc.s_hit_vals.as<uint32_t>();
         ra.seg_stride = stride;
         if (e[1]) HIP_TRY(hipEventRecord(e[1], st));
@@ -4227,7 +4342,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             sa.nq = b; sa.hit_cnt = sc.s_hit_cnt.as<uint32_t>();
             sa.keys = sc.s_hit_keys.as<uint64_t>(); sa.vals = sc.s_hit_vals.as<uint32_t>(); sa.seg_stride = stride;
             sa.max_results = max_results; sa.out_off = sc.s_rout_off.as<uint64_t>();
-            sa.ids = s->d_final_ids; sa.sqrt_out = sqrt_out ? 1 : 0;
+            sa.ids = s->d_final_ids; sa.sqrt_out = sqrt_out;
             sa.out_rows = sc.s_rout_rows.as<uint32_t>(); sa.out_dist = sc.s_rout_dist.as<float>();
             if (any_small) { HIP_TRY(launch_range_sort_small(sa, st)); ++launches; }
             if (!segs.empty()) {
@@ -4269,6 +4384,14 @@ static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, ui
     std::unique_ptr<float, HostFree> dist(static_cast<float *>(std::malloc(sizeof(float))));
     if (!lims || !rows || !dist) return fail(PQV_ERR_OOM, "host allocation failed");
     lims.get()[0] = 0;
+    std::vector<float> nq_host;
+    if (nq && metric == PQV_COSINE) {
+        // the cosine searcher's range search over n(q): hits 0.5 d2 <= radius, written out halved (sqrt_out 2)
+        if (int rc = use_device(s->device)) return rc;
+        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
+        queries = nq_host.data();
+        s = s->cos.get(); metric = PQV_L2SQ_REF4; sqrt_out = 2;
+    }
     if (nq) {
         if (int rc = use_device(s->device)) return rc;
         std::lock_guard<std::mutex> lock(s->mu);
@@ -4287,7 +4410,7 @@ extern "C" int pqv_range_search(const pqv_searcher *s, const float *queries, uin
                                 uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                                 uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
     return guard([&] { return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric,
-                                                    sqrt_out, lims, row_idx, dist, n_within, n_candidates); });
+                                                    sqrt_out ? 1 : 0, lims, row_idx, dist, n_within, n_candidates); });
 }
 extern "C" void pqv_range_free(uint64_t *lims, uint32_t *row_idx, float *dist) {
     std::free(lims); std::free(row_idx); std::free(dist);
@@ -4333,6 +4456,7 @@ static int pqv_searcher_set_option_impl(pqv_searcher *s, const char *name, int64
         s->d_mat_blk_op[2].release();
     }
     else return fail(PQV_ERR_INVALID, "unknown searcher option: " + n);
+    if (s->cos) return pqv_searcher_set_option_impl(s->cos.get(), name, value);      // (the cosine searcher follows)
     return PQV_OK;
 }
 extern "C" int pqv_searcher_set_option(pqv_searcher *s, const char *name, int64_t value) {
@@ -4343,6 +4467,21 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
                                       char *buf, size_t len) {
     if (!s || !buf || !len) return fail(PQV_ERR_INVALID, "searcher/buf must not be NULL");
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (metric == PQV_COSINE) {
+        // the L2 dispatch of the cosine searcher (before the first cosine call: of this one, over the raw rows)
+        const pqv_searcher *c;
+        {
+            std::lock_guard<std::mutex> lock(s->mu);
+            c = s->cos ? s->cos.get() : s;
+        }
+        const int l = std::snprintf(buf, len, "PQV_COSINE%s: normalize_rows_kernel (n(q), one launch on the call's stream), then ",
+                                    c == s ? " (layout not built yet)" : "");
+        const size_t used = l < 0 ? 0 : std::min<size_t>(static_cast<size_t>(l), len - 1);
+        if (int rc = pqv_searcher_describe_impl(c, nq, k, nprobe, PQV_L2SQ_REF4, buf + used, len - used)) return rc;
+        const size_t end = std::strlen(buf);
+        std::snprintf(buf + end, len - end, "; distances halved in the final write-out (merge_kernel / range write-out)");
+        return PQV_OK;
+    }
     std::lock_guard<std::mutex> lock(s->mu);
     // a table names itself first: its files, the lists a query probes, and the probe route
     char tb[256] = "";
@@ -4436,6 +4575,14 @@ static int pqv_searcher_footprint_impl(const pqv_searcher *s, uint64_t *row_orde
     for (const Scratch &l : s->lanes)
         for (const DevBuf *b : l.bufs()) other += b->p ? b->bytes : 0;
     if (other_bytes) *other_bytes = other;
+    if (s->cos) {       // the cosine layout: its searcher's buffers, its normalised row-order copy included, in the same four classes
+        uint64_t f[4] = {0, 0, 0, 0};
+        if (int rc = pqv_searcher_footprint_impl(s->cos.get(), f, f + 1, f + 2, f + 3)) return rc;
+        if (row_order_bytes) *row_order_bytes += f[0];
+        if (ivf_rows_bytes) *ivf_rows_bytes += f[1];
+        if (blocked_bytes) *blocked_bytes += f[2];
+        if (other_bytes) *other_bytes += f[3];
+    }
     return PQV_OK;
 }
 extern "C" int pqv_searcher_footprint(const pqv_searcher *s, uint64_t *row_order_bytes, uint64_t *ivf_rows_bytes,
@@ -4543,6 +4690,13 @@ static int pqv_counters_impl(const pqv_searcher *s, pqv_counters_t *out) {
     out->screen_survivors = st[1];
     out->candidate_rows += st[2];         // top-k calls (device counters) + pqv_candidate_rows (host counter)
     out->embeddings_fetched += st[3];
+    if (s->cos) {                         // PQV_COSINE calls count on the cosine searcher
+        pqv_counters_t c{};
+        if (int rc = pqv_counters_impl(s->cos.get(), &c)) return rc;
+        out->queries += c.queries; out->candidate_rows += c.candidate_rows; out->embeddings_fetched += c.embeddings_fetched;
+        out->kernel_launches += c.kernel_launches; out->exact_replays += c.exact_replays; out->screened_pairs += c.screened_pairs;
+        out->screen_survivors += c.screen_survivors;
+    }
     return PQV_OK;
 }
 extern "C" int pqv_counters(const pqv_searcher *s, pqv_counters_t *out) {
@@ -4553,6 +4707,7 @@ static int pqv_set_timing_impl(pqv_searcher *s, int enabled) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     s->timing = enabled != 0;
+    if (s->cos) return pqv_set_timing_impl(s->cos.get(), enabled);
     return PQV_OK;
 }
 extern "C" int pqv_set_timing(pqv_searcher *s, int enabled) {
@@ -4575,6 +4730,12 @@ static int pqv_timing_read_impl(const pqv_searcher *s, double *rerank_ms, double
     }
     for (auto e : s->ev) (void)hipEventDestroy(e);
     s->ev.clear();
+    if (s->cos) {                         // PQV_COSINE calls record on the cosine searcher
+        double r2 = 0.0, t2 = 0.0;
+        uint32_t c2 = 0;
+        if (int rc = pqv_timing_read_impl(s->cos.get(), &r2, &t2, &c2)) return rc;
+        rr += r2; tot += t2; calls += c2;
+    }
     if (rerank_ms) *rerank_ms = rr;
     if (total_ms) *total_ms = tot;
     if (n_calls) *n_calls = calls;

@@ -52,7 +52,7 @@ struct StreamArgs {
     uint32_t       *zero_u32;
     uint32_t        zero_n;
     // RANGE: probe ranks [j0, j0 + nj) of every query (gridDim.y = nj; probe / cand_base keep the row stride nprobe).  A
-    // candidate is a hit iff out = (sqrt_out ? sqrt(d2) : d2) <= radius; each wave appends its hits to query q's segment
+    // candidate is a hit iff out = (sqrt_out 1 ? sqrt(d2) : 2 ? 0.5 d2 (PQV_COSINE) : d2) <= radius; each wave appends its hits to query q's segment
     // hit_keys / hit_vals [q * seg_stride + slot) (slot from one atomicAdd per wave on hit_cnt[q]).  seg_stride must be at
     // least the query's capped candidate count, so a segment cannot overflow.
     uint32_t        j0, nj;
@@ -108,7 +108,7 @@ struct MergeArgs {
     uint32_t       *row_idx;     // [nq, k]
     float          *dist;        // [nq, k]
     uint32_t       *n_found;     // [nq] or nullptr
-    int             sqrt_out;
+    int             sqrt_out;    // 0 d2, 1 sqrt(d2), 2 0.5 d2 (PQV_COSINE; tie flags still compare d2)
     uint32_t        k_out;       // results written per query (<= k); 0 => k
     // optional extra source (wide screened path): per-query candidate buffers; with `spilled` the partial
     // lists of a query are read only if spilled[q] != 0
@@ -662,6 +662,10 @@ hipError_t launch_gather_rows(const float *src, const uint32_t *idx32, const uin
                               uint64_t m, uint32_t dim, float *out, hipStream_t s);
 // out[i, :dim_p] = src[idx32 ? idx32[i] : i, :dim] zero-padded (dim, dim_p multiples of 4): see pad_rows_kernel
 hipError_t launch_pad_rows(const float *src, const uint32_t *idx32, uint64_t m, uint32_t dim, uint32_t dim_p, float *out, hipStream_t s);
+// PQV_COSINE: dst[dst_row ? dst_row[i] : i, :dim] = n(src[i * src_stride, :dim]) (every value times 1 / sqrt of the row's 4-grouped
+// squared-norm chain; 0 for a zero row): see normalize_rows_kernel.  dst rows are dim wide.
+hipError_t launch_normalize_rows(const float *src, uint32_t src_stride, const uint32_t *dst_row, uint64_t m, uint32_t dim, float *dst,
+                                 hipStream_t s);
 // f64 -> f32 narrowing of a staged column chunk
 hipError_t launch_narrow_f64(const double *src, uint64_t count, float *out, hipStream_t s);
 
@@ -701,7 +705,7 @@ struct RangeSortArgs {
     uint64_t        max_results;  // 0: every hit
     const uint64_t *out_off;      // [nq] first output entry of each query
     const uint32_t *ids;          // storage row -> file row id (nullptr => identity)
-    int             sqrt_out;
+    int             sqrt_out;     // as MergeArgs::sqrt_out
     uint32_t       *out_rows;
     float          *out_dist;
 };

@@ -685,6 +685,70 @@ hipError_t launch_narrow_f64(const double *src, uint64_t count, float *out, hipS
 }
 
 
+// PQV_COSINE (pqv.h): dst[dst_row ? dst_row[i] : i, :dim] = n(src[i]) -- every value times r = 1 / sqrt(sq), sq the
+// reference's 4-grouped chain of the row against zero (index.rs:461-480, as stream_kernel adds d2), r = 0 where sq == 0.  One wave
+// per row: lane l squares the groups l, l + 64, ... ((v0^2 + v1^2) + v2^2) + v3^2, the wave adds them to the running sum in group
+// order (readlane: the chain stays sequential), the tail element by element; the scaling pass re-reads the row the wave has just
+// read (cache hits: the column leaves HBM once).  Correctly rounded sqrt and division (double rounding from f64 is exact for both).
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void normalize_rows_kernel(const float *__restrict__ src, uint32_t src_stride,
+                                                             const uint32_t *__restrict__ dst_row, uint64_t m, uint32_t dim,
+                                                             float *__restrict__ dst) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * 4;
+    const uint32_t G = dim >> 2;
+    for (uint64_t i = wave; i < m; i += nwaves) {
+        const float *s = src + i * src_stride;
+        float sum = 0.0f;
+        for (uint32_t g0 = 0; g0 < G; g0 += 64) {
+            const uint32_t g = g0 + lane;
+            float t = 0.0f;
+            if (g < G) {
+                float v0, v1, v2, v3;
+                if constexpr (ALIGNED) {
+                    const float4 v = reinterpret_cast<const float4 *>(s)[g];
+                    v0 = v.x; v1 = v.y; v2 = v.z; v3 = v.w;
+                } else {
+                    v0 = s[4 * g]; v1 = s[4 * g + 1]; v2 = s[4 * g + 2]; v3 = s[4 * g + 3];
+                }
+                t = v0 * v0 + v1 * v1;
+                t = t + v2 * v2;
+                t = t + v3 * v3;
+            }
+            const uint32_t n = G - g0 < 64 ? G - g0 : 64;
+            for (uint32_t j = 0; j < n; ++j) sum = sum + __uint_as_float(readlane_u32(__float_as_uint(t), (int)j));
+        }
+        for (uint32_t e = G * 4; e < dim; ++e) {
+            const float v = s[e];
+            sum = sum + v * v;
+        }
+        const float r = sum == 0.0f ? 0.0f : (float)(1.0 / (double)sqrt_f32_ieee(sum));
+        float *d = dst + (dst_row ? (uint64_t)dst_row[i] : i) * dim;
+        if constexpr (ALIGNED) {
+            for (uint32_t g = lane; g < G; g += 64) {
+                float4 v = reinterpret_cast<const float4 *>(s)[g];
+                v.x = v.x * r; v.y = v.y * r; v.z = v.z * r; v.w = v.w * r;
+                reinterpret_cast<float4 *>(d)[g] = v;
+            }
+        } else {
+            for (uint32_t e = lane; e < dim; e += 64) d[e] = s[e] * r;
+        }
+    }
+}
+
+hipError_t launch_normalize_rows(const float *src, uint32_t src_stride, const uint32_t *dst_row, uint64_t m, uint32_t dim, float *dst,
+                                 hipStream_t s) {
+    if (m == 0 || dim == 0) return hipSuccess;
+    uint64_t blocks = (m + 3) / 4;
+    if (blocks > 65536) blocks = 65536;
+    if (dim % 4 == 0 && src_stride % 4 == 0)
+        hipLaunchKernelGGL(normalize_rows_kernel<true>, dim3((uint32_t)blocks), dim3(256), 0, s, src, src_stride, dst_row, m, dim, dst);
+    else
+        hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((uint32_t)blocks), dim3(256), 0, s, src, src_stride, dst_row, m, dim, dst);
+    return hipGetLastError();
+}
+
 
 // an empty kernel the library launches at the first call for a device (and on a new stream): the runtime loads this unit's code
 // object and sets up the stream's hardware queue then, not inside the first build or the first query

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void stream_kernel(const StreamArgs a) {
             }
         } else if constexpr (MODE == STREAM_RANGE) {
             // the wave's hits go to the query's segment in one block: ballot, rank from mbcnt, one atomicAdd per wave
-            const float outv = a.sqrt_out ? sqrt_f32_ieee(sum) : sum;
+            const float outv = a.sqrt_out == 1 ? sqrt_f32_ieee(sum) : a.sqrt_out == 2 ? 0.5f * sum : sum;     // (2: PQV_COSINE)
             const bool hit = valid && outv <= a.radius;                // (a NaN distance never compares true)
             const uint64_t m = __ballot(hit);
             if (m) {
@@ -921,7 +921,7 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
         for (int s = 0; s < S; ++s) {
             const bool have = tk.key[s] != KEY_EMPTY;
             const float d2 = __uint_as_float((uint32_t)(tk.key[s] >> 32));
-            outd[s] = have ? (a.sqrt_out ? sqrt_f32_ieee(d2) : d2) : INFINITY;
+            outd[s] = have ? (a.sqrt_out == 1 ? sqrt_f32_ieee(d2) : d2) : INFINITY;     // (sqrt_out 2: halved at the store, ties on d2)
         }
 #pragma unroll
         for (int s = 0; s < S; ++s) {
@@ -947,7 +947,7 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
                 float d = INFINITY;
                 if (have) {
                     row = a.ids ? a.ids[tk.val[s]] : tk.val[s];
-                    d = outd[s];
+                    d = a.sqrt_out == 2 ? 0.5f * outd[s] : outd[s];
                 }
                 a.row_idx[(uint64_t)q * k_out + e] = row;
                 a.dist[(uint64_t)q * k_out + e] = d;

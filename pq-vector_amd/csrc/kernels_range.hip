@@ -44,7 +44,7 @@ __device__ __forceinline__ uint32_t pow2_at_least(uint32_t n) {
 __device__ __forceinline__ void write_hit(const RangeSortArgs &a, uint64_t o, uint64_t key, uint32_t val) {
     const float d2 = __uint_as_float((uint32_t)(key >> 32));
     a.out_rows[o] = a.ids ? a.ids[val] : val;
-    a.out_dist[o] = a.sqrt_out ? sqrt_f32_ieee(d2) : d2;     // search.rs:133
+    a.out_dist[o] = a.sqrt_out == 1 ? sqrt_f32_ieee(d2) : a.sqrt_out == 2 ? 0.5f * d2 : d2;     // search.rs:133; 2: PQV_COSINE
 }
 
 __device__ __forceinline__ uint64_t kept_of(const RangeSortArgs &a, uint32_t n) {
