@@ -376,6 +376,62 @@ impl<'c> Searcher<'c> {
         Ok(out)
     }
 
+    /// A row mask for this searcher (`include/pqv.h`: `pqv_row_mask`): `allowed[r]` says whether the row reported as `row_idx == r`
+    /// may be returned; `allowed.len()` must be the corpus' row count.  What a DataFusion host gets from its `FilterExec`.
+    pub fn row_mask(&self, allowed: &[bool]) -> Result<RowMask> {
+        let bytes: Vec<u8> = allowed.iter().map(|&b| b as u8).collect();
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_row_mask_create(self.raw, bytes.as_ptr(), bytes.len() as u64, &mut raw) })?;
+        Ok(RowMask { raw })
+    }
+
+    /// [`Searcher::topk`] over the allowed rows only (the reference's predicate inside the scan, `src/df_vector/exec.rs:207-277`):
+    /// fewer than `k` results may come back.
+    pub fn topk_masked(&self, mask: &RowMask, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize)
+        -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (k, np) = (k.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_masked(self.raw, mask.raw, queries.as_ptr(), nq as u32, dim as u32, k as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1,
+                                 rows.as_mut_ptr(), dist.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
+    /// [`Searcher::range_search`] over the allowed rows only.
+    pub fn range_search_masked(&self, mask: &RowMask, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64)
+        -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (mut lims, mut rows, mut dist) = (ptr::null_mut::<u64>(), ptr::null_mut::<u32>(), ptr::null_mut::<f32>());
+        check(unsafe {
+            sys::pqv_range_search_masked(self.raw, mask.raw, queries.as_ptr(), nq as u32, dim as u32, radius, nprobe.get() as u32, 0,
+                                         max_results, sys::PQV_L2SQ_REF4, 1, &mut lims, &mut rows, &mut dist, ptr::null_mut(), ptr::null_mut())
+        })?;
+        if lims.is_null() || rows.is_null() || dist.is_null() {
+            unsafe { sys::pqv_range_free(lims, rows, dist) };
+            return Err("pqv_range_search_masked returned a NULL buffer".into());
+        }
+        let out = {
+            let l = unsafe { std::slice::from_raw_parts(lims, nq + 1) };
+            let total = l[nq] as usize;
+            let (r, d) = if total == 0 {
+                (&[][..], &[][..])
+            } else {
+                unsafe { (std::slice::from_raw_parts(rows, total), std::slice::from_raw_parts(dist, total)) }
+            };
+            (0..nq)
+                .map(|q| (l[q] as usize..l[q + 1] as usize).map(|i| SearchResult { row_idx: r[i], distance: d[i] }).collect())
+                .collect()
+        };
+        unsafe { sys::pqv_range_free(lims, rows, dist) };
+        Ok(out)
+    }
+
     /// Plan metrics (`src/df_vector/index_exec.rs:289-299`, `exec.rs:411-427`).
     pub fn counters(&self) -> Result<sys::PqvCounters> {
         let mut c = sys::PqvCounters::default();
@@ -387,6 +443,26 @@ impl<'c> Searcher<'c> {
 impl Drop for Searcher<'_> {
     fn drop(&mut self) {
         unsafe { sys::pqv_searcher_free(self.raw) }
+    }
+}
+
+/// One allow bit per row of a searcher's corpus ([`Searcher::row_mask`]); immutable, usable from any thread, and safe to drop
+/// before or after its searcher.
+pub struct RowMask {
+    raw: *mut sys::PqvRowMask,
+}
+unsafe impl Send for RowMask {}
+unsafe impl Sync for RowMask {}
+
+impl RowMask {
+    pub fn rows(&self) -> u64 { unsafe { sys::pqv_row_mask_rows(self.raw) } }
+    /// allowed rows (that belong to an inverted list)
+    pub fn count(&self) -> u64 { unsafe { sys::pqv_row_mask_count(self.raw) } }
+}
+
+impl Drop for RowMask {
+    fn drop(&mut self) {
+        unsafe { sys::pqv_row_mask_free(self.raw) }
     }
 }
 

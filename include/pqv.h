@@ -384,6 +384,53 @@ int  pqv_range_search(const pqv_searcher *searcher, const float *queries, uint32
                       uint64_t *n_within, uint64_t *n_candidates);
 void pqv_range_free(uint64_t *lims, uint32_t *row_idx, float *dist);
 
+/* Row-masked search: top-k and range search restricted to a set of rows -- the `WHERE <predicate>` of
+ * `SELECT .. WHERE <predicate> ORDER BY array_distance(col, q) LIMIT k`, which the reference evaluates inside the scan, after
+ * candidate pruning and before the heap (src/df_vector/exec.rs:207-277) -- and equally deleted rows or a tenant's rows.
+ *
+ * A row mask is one bit per row of the searcher's corpus: bit r belongs to the row a call reports as row_idx == r (a file row
+ * of a plain searcher, a corpus row of a table searcher).  It is made for ONE searcher, from `allowed` [n_rows] bytes (nonzero =
+ * allowed; n_rows must equal pqv_corpus_rows of the searcher's corpus, else PQV_ERR_INVALID "row mask has N rows, the corpus has
+ * M"), and is immutable.  Rows that belong to no inverted list are ignored; pqv_row_mask_count is the number of allowed rows
+ * that belong to one.  pqv_row_mask_from_device reads device bytes (u8 [n_rows], e.g. a torch.bool tensor) on hip_stream (NULL:
+ * the searcher's) and is complete on return.  Any thread may use a mask; mask and searcher may be freed in either order; the
+ * caller keeps a mask alive until the work enqueued with it has completed, as with its query buffers.
+ *
+ * A masked call behaves as the unmasked call of the same arguments, except:
+ *   candidates   the unmasked call's sequence (candidate_rows order; file-major on a table), cut by max_candidates / the table's
+ *                round-robin quotas exactly as there, BEFORE the mask is looked at; the considered rows are the allowed rows
+ *                among the capped candidates, at their UNMASKED positions.  Top-k and range order by (d2, position); tie rules
+ *                (the host form replays the reference's heap over the considered rows in arrival order; the device form flags),
+ *                sqrt_out, max_results and the PQV_COSINE halving are unchanged.
+ *   counts       n_candidates and the candidate_rows counter stay the counts before cap and mask; embeddings_fetched advances
+ *                by the considered rows (the reference's counter after the filter); n_found may be below k, or 0 (rows
+ *                0xFFFFFFFF, distance +inf); n_within counts masked hits.
+ *   equivalence  with max_candidates == 0 on a plain searcher the call returns, bit for bit, what the unmasked call returns on a
+ *                searcher over pqv_index_from_parts(dim, centroids, [list intersected with the allowed rows, for each list])
+ *                and the same corpus -- rows, distances, n_found, tie flags -- n_candidates excepted.
+ *   path         always the exact streaming pass (masked_stream_kernel): no searcher option changes a masked result, and rows the
+ *                mask excludes are never read.  k > 1024 or more than 1024 probed lists: pqv_topk_masked goes through the host heap
+ *                like pqv_topk; the device form reports PQV_ERR_UNSUPPORTED like pqv_topk_device.
+ * Errors (PQV_ERR_INVALID): "row mask must not be NULL", "row mask belongs to another searcher".
+ * pqv_topk_masked_device: d_tie_flags may be NULL (then k <= 1024, else k <= 1023). */
+typedef struct pqv_row_mask pqv_row_mask;
+int      pqv_row_mask_create(const pqv_searcher *searcher, const uint8_t *allowed, uint64_t n_rows, pqv_row_mask **out);
+int      pqv_row_mask_from_device(const pqv_searcher *searcher, const void *d_allowed, uint64_t n_rows, void *hip_stream,
+                                  pqv_row_mask **out);
+uint64_t pqv_row_mask_rows(const pqv_row_mask *mask);
+uint64_t pqv_row_mask_count(const pqv_row_mask *mask);
+void     pqv_row_mask_free(pqv_row_mask *mask);
+int pqv_topk_masked(const pqv_searcher *searcher, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                    uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                    uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_masked_device(const pqv_searcher *searcher, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                           uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, void *d_row_idx,
+                           void *d_dist, void *d_n_found, void *d_n_candidates, void *d_tie_flags, void *hip_stream);
+int pqv_range_search_masked(const pqv_searcher *searcher, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                            uint32_t query_len, float radius, uint32_t nprobe, uint64_t max_candidates, uint64_t max_results,
+                            int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
+                            uint64_t *n_within, uint64_t *n_candidates);
+
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`
  * baseline does row by row (benches/query.rs:76-98), for the metrics above.  Results are

@@ -120,6 +120,17 @@ SIGNATURES = {
     "pqv_range_search": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64,
                                    C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_range_free": (None, [u64p, u32p, f32p]),
+    "pqv_row_mask_create": (C.c_int, [vp, u8p, C.c_uint64, C.POINTER(vp)]),
+    "pqv_row_mask_from_device": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(vp)]),
+    "pqv_row_mask_rows": (C.c_uint64, [vp]),
+    "pqv_row_mask_count": (C.c_uint64, [vp]),
+    "pqv_row_mask_free": (None, [vp]),
+    "pqv_topk_masked": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                  C.c_int, C.c_int, u32p, f32p, u32p, u64p]),
+    "pqv_topk_masked_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                         vp, vp, vp, vp, vp, vp]),
+    "pqv_range_search_masked": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64,
+                                          C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_brute_topk": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, u32p]),
     "pqv_rerank": (C.c_int, [C.c_int, f32p, f32p, u32p, u8p, C.c_uint64, C.c_uint32, C.c_uint32,
                              C.c_int, u32p, f32p, u32p]),

@@ -400,6 +400,57 @@ class SearchResult:
     distance: float
 
 
+class RowMask:
+    """One allow bit per row of a searcher's corpus (pqv.h: pqv_row_mask): made by Searcher.row_mask / row_mask_from_rows /
+    row_mask_device, passed as mask= to that searcher's topk / range_search / topk_device.  Immutable; close() releases it."""
+
+    def __init__(self, handle, searcher):
+        self._h = handle
+        self._searcher = searcher
+
+    @property
+    def rows(self):
+        return int(_ffi.lib().pqv_row_mask_rows(self._h)) if self._h else 0
+
+    @property
+    def count(self):
+        """allowed rows (that belong to an inverted list)"""
+        return int(_ffi.lib().pqv_row_mask_count(self._h)) if self._h else 0
+
+    def close(self):
+        if self._h:
+            _ffi.lib().pqv_row_mask_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _allow_array(allowed, n_rows, what="row mask"):
+    """A caller's allow array -> contiguous uint8 [n_rows]: bool or uint8, one entry per row; anything else is refused."""
+    if allowed is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} must not be None")
+    a = np.asarray(allowed)
+    if a.dtype != np.bool_ and a.dtype != np.uint8:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} must be a bool or uint8 array, got {a.dtype}")
+    if a.ndim != 1:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} must be one-dimensional, got {a.ndim} dimensions")
+    if n_rows is not None and a.size != n_rows:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"row mask has {a.size} rows, the corpus has {n_rows}")
+    return np.ascontiguousarray(a).view(np.uint8) if a.dtype == np.bool_ else np.ascontiguousarray(a)
+
+
+def _mask_handle(searcher, mask):
+    if not isinstance(mask, RowMask):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"mask must be a RowMask, got {type(mask).__name__}")
+    if mask._h is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "row mask must not be NULL")
+    return mask._h
+
+
 class Searcher:
     """An index bound to a resident corpus on that corpus' GPU."""
 
@@ -431,8 +482,35 @@ class Searcher:
         finally:
             _ffi.lib().pqv_rows_free(rows)
 
-    def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
-        """Batched topk(); returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq], n_candidates [nq])."""
+    def row_mask(self, allowed):
+        """RowMask from a bool / uint8 array [corpus rows] (nonzero = allowed)."""
+        a = _allow_array(allowed, self._corpus.rows)
+        h = vp()
+        _check(_ffi.lib().pqv_row_mask_create(self._h, a.ctypes.data_as(_ffi.u8p), a.size, C.byref(h)))
+        return RowMask(h, self)
+
+    def row_mask_from_rows(self, row_ids, allow=True):
+        """RowMask that allows exactly `row_ids` -- or, with allow=False, every row BUT these (deletions)."""
+        n = self._corpus.rows
+        ids = np.asarray(row_ids)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"row ids must be integers, got {ids.dtype}")
+        ids = ids.reshape(-1).astype(np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"row id out of range for a corpus of {n} rows")
+        a = np.zeros(n, dtype=np.uint8) if allow else np.ones(n, dtype=np.uint8)
+        a[ids] = 1 if allow else 0
+        return self.row_mask(a)
+
+    def row_mask_device(self, ptr, n_rows, stream=0):
+        """RowMask from device bytes u8 [n_rows] (e.g. a torch.bool tensor's data_ptr()); complete on return."""
+        h = vp()
+        _check(_ffi.lib().pqv_row_mask_from_device(self._h, vp(ptr or None), int(n_rows), vp(stream or None), C.byref(h)))
+        return RowMask(h, self)
+
+    def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None):
+        """Batched topk(); returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq], n_candidates [nq]).
+        mask (a RowMask of this searcher): only allowed rows are considered (pqv.h: pqv_topk_masked)."""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -441,6 +519,11 @@ class Searcher:
         dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
+        if mask is not None:
+            _check(_ffi.lib().pqv_topk_masked(self._h, _mask_handle(self, mask), q.ctypes.data_as(f32p), nq, qlen, k, nprobe,
+                                              max_candidates, metric, 1 if sqrt_out else 0, rows.ctypes.data_as(u32p),
+                                              dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p)))
+            return rows, dist, nf, nc
         _check(_ffi.lib().pqv_topk(self._h, q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_candidates,
                                    metric, 1 if sqrt_out else 0, rows.ctypes.data_as(u32p),
                                    dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
@@ -448,7 +531,7 @@ class Searcher:
         return rows, dist, nf, nc
 
     def range_search(self, queries, radius, nprobe, max_candidates=0, max_results=0, metric=_ffi.PQV_L2SQ_REF4,
-                     sqrt_out=True):
+                     sqrt_out=True, mask=None):
         """Every candidate within `radius` of each query (pqv.h: pqv_range_search), ascending by (d2, candidate position).
         Returns (lims u64 [nq+1], rows u32, dist f32, n_within u64 [nq], n_candidates u64 [nq]): query q's hits are
         rows / dist [lims[q]:lims[q+1]]; n_within is the hit count before max_results."""
@@ -466,9 +549,14 @@ class Searcher:
         nw = np.zeros(nq, dtype=np.uint64)
         nc = np.zeros(nq, dtype=np.uint64)
         lims_p, rows_p, dist_p = u64p(), u32p(), f32p()
-        _check(_ffi.lib().pqv_range_search(self._h, q.ctypes.data_as(f32p), nq, qlen, radius, nprobe, max_candidates,
-                                           max_results, metric, 1 if sqrt_out else 0, C.byref(lims_p), C.byref(rows_p),
-                                           C.byref(dist_p), nw.ctypes.data_as(u64p), nc.ctypes.data_as(u64p)))
+        if mask is not None:       # (pqv.h: pqv_range_search_masked)
+            _check(_ffi.lib().pqv_range_search_masked(self._h, _mask_handle(self, mask), q.ctypes.data_as(f32p), nq, qlen, radius, nprobe,
+                                                      max_candidates, max_results, metric, 1 if sqrt_out else 0, C.byref(lims_p),
+                                                      C.byref(rows_p), C.byref(dist_p), nw.ctypes.data_as(u64p), nc.ctypes.data_as(u64p)))
+        else:
+            _check(_ffi.lib().pqv_range_search(self._h, q.ctypes.data_as(f32p), nq, qlen, radius, nprobe, max_candidates,
+                                               max_results, metric, 1 if sqrt_out else 0, C.byref(lims_p), C.byref(rows_p),
+                                               C.byref(dist_p), nw.ctypes.data_as(u64p), nc.ctypes.data_as(u64p)))
         try:
             lims = np.ctypeslib.as_array(lims_p, shape=(nq + 1,)).copy()
             total = int(lims[-1])
@@ -479,12 +567,19 @@ class Searcher:
         return lims, rows, dist, nw, nc
 
     def topk_device(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0,
-                    max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0):
+                    max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0, mask=None):
         """Device-pointer form (ints from tensor.data_ptr()); asynchronous on `stream` -- a hipStream_t handle; 0 means the
         searcher's OWN non-blocking stream, not HIP's / torch's default stream (whose handle is 0 too): work that must follow
         the call on the default stream is NOT ordered behind it, so pass an explicit stream (1 = hipStreamLegacy names the default
         stream itself).  d_tie_flags (u32 [nq]):
-        also flag the queries whose answer depends on the reference's heap history (re-submit those to topk())."""
+        also flag the queries whose answer depends on the reference's heap history (re-submit those to topk()).
+        mask (a RowMask of this searcher, alive until the enqueued work has completed): pqv.h: pqv_topk_masked_device."""
+        if mask is not None:
+            _check(_ffi.lib().pqv_topk_masked_device(self._h, _mask_handle(self, mask), vp(d_queries), nq, k, nprobe, max_candidates,
+                                                     metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
+                                                     vp(d_n_found or None), vp(d_n_candidates or None), vp(d_tie_flags or None),
+                                                     vp(stream or None)))
+            return
         if d_tie_flags:
             _check(_ffi.lib().pqv_topk_device_flags(self._h, vp(d_queries), nq, k, nprobe, max_candidates, metric,
                                                     1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
@@ -575,6 +670,77 @@ def _metric_arg(m):
     return int(m)
 
 
+
+def _is_expression(x):
+    try:
+        import pyarrow.compute as pc
+    except ImportError:
+        return False
+    return isinstance(x, pc.Expression)
+
+
+def _where_arg(x, path, searcher):
+    """What .where(x) of a one-file builder accepts: a bool array over the file's rows, a RowMask (searcher sources), or a
+    pyarrow.compute.Expression over the file's other columns (path sources).  Returns x checked; anything else is refused."""
+    if x is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "where() needs a bool array, a RowMask or a pyarrow expression, got None")
+    if isinstance(x, RowMask):
+        if searcher is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "where(RowMask) needs a Searcher source: a row mask belongs to one searcher")
+        if x._searcher is not searcher:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "row mask belongs to another searcher")
+        return x
+    if _is_expression(x):
+        if path is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "where(expression) needs a Parquet path source: the expression is evaluated over the file's columns")
+        return x
+    a = np.asarray(x)
+    if a.dtype != np.bool_:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"where() needs a bool array, a RowMask or a pyarrow expression, got {a.dtype if a.dtype != object else type(x).__name__}")
+    n_rows = searcher._corpus.rows if searcher is not None else _parquet_rows(path)
+    return _allow_array(a, n_rows, "where()")
+
+
+def _parquet_rows(path):
+    import pyarrow.parquet as pq
+    return pq.ParquetFile(path).metadata.num_rows
+
+
+def _resolve_where(x, path, searcher):
+    """-> (RowMask, owned): the mask of a checked where() argument on `searcher`; owned masks are closed after the search."""
+    if isinstance(x, RowMask):
+        return x, False
+    if _is_expression(x):
+        from . import parquet_io
+        x = parquet_io.row_mask_from_expression(path, x)
+    return searcher.row_mask(x), True
+
+
+def _table_where_arg(x, paths):
+    """What .where(x) of a table builder accepts: ONE expression for all files, or one entry per file (bool array or expression)."""
+    if x is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "where() needs a pyarrow expression or one bool array / expression per file, got None")
+    if isinstance(x, RowMask):
+        raise PqvError(_ffi.PQV_ERR_INVALID, "where(RowMask) needs a Searcher source: a row mask belongs to one searcher")
+    if _is_expression(x):
+        return [x] * len(paths)
+    if isinstance(x, np.ndarray) or not isinstance(x, (list, tuple)):
+        raise PqvError(_ffi.PQV_ERR_INVALID, "a table's where() needs one pyarrow expression, or a list with one bool array / expression per file")
+    if len(x) != len(paths):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"where() has {len(x)} entries for {len(paths)} files")
+    return [_where_arg(xf, p, None) for xf, p in zip(x, paths)]
+
+
+def _resolve_table_where(per_file, paths, searcher):
+    from . import parquet_io
+    allowed = np.zeros(searcher._corpus.rows, dtype=np.uint8)
+    for xf, p, b, n in zip(per_file, paths, searcher.row_base.tolist(), searcher.n_rows.tolist()):
+        a = parquet_io.row_mask_from_expression(p, xf) if _is_expression(xf) else xf
+        a = _allow_array(a, int(n), "where()")
+        allowed[int(b):int(b) + int(n)] = a
+    return searcher.row_mask(allowed)
+
+
 class TopkBuilder:
     """src/ivf/search.rs:49-81: k and nprobe must be set and > 0.  `source` is an indexed
     Parquet path (as in the reference) or an existing Searcher.  metric(m): PQV_L2SQ_REF4 (default, distances
@@ -591,9 +757,17 @@ class TopkBuilder:
         self._k = None
         self._nprobe = None
         self._metric = _ffi.PQV_L2SQ_REF4
+        self._where = None
 
     def metric(self, m):
         self._metric = _metric_arg(m)
+        return self
+
+    def where(self, x):
+        """Restrict the search to rows (the reference's `WHERE <predicate>` inside the scan, exec.rs:207-277): a bool array over
+        the file's rows, a RowMask (Searcher sources), or a pyarrow.compute.Expression over the file's other columns, e.g.
+        pc.field("id") >= 2 (path sources; nulls count as False).  Fewer than k rows may come back."""
+        self._where = _where_arg(x, self._path, self._searcher)
         return self
 
     def k(self, k):
@@ -615,7 +789,16 @@ class TopkBuilder:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
-        rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric)
+        if self._where is not None:
+            mask, owned = _resolve_where(self._where, self._path, self._searcher)
+            try:
+                rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric,
+                                                        mask=mask)
+            finally:
+                if owned:
+                    mask.close()
+        else:
+            rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric)
         n = int(nf[0])
         return [SearchResult(r, d) for r, d in zip(rows[0, :n].tolist(), dist[0, :n].tolist())]
 
@@ -637,9 +820,15 @@ class RangeBuilder:
         self._nprobe = None
         self._max_results = 0
         self._metric = _ffi.PQV_L2SQ_REF4
+        self._where = None
 
     def metric(self, m):
         self._metric = _metric_arg(m)
+        return self
+
+    def where(self, x):
+        """As TopkBuilder.where: only rows that pass are hits."""
+        self._where = _where_arg(x, self._path, self._searcher)
         return self
 
     def radius(self, radius):
@@ -666,8 +855,17 @@ class RangeBuilder:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
-        _, rows, dist, _, _ = self._searcher.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
-                                                          max_results=self._max_results, metric=self._metric)
+        if self._where is not None:
+            mask, owned = _resolve_where(self._where, self._path, self._searcher)
+            try:
+                _, rows, dist, _, _ = self._searcher.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
+                                                                  max_results=self._max_results, metric=self._metric, mask=mask)
+            finally:
+                if owned:
+                    mask.close()
+        else:
+            _, rows, dist, _, _ = self._searcher.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
+                                                              max_results=self._max_results, metric=self._metric)
         return [SearchResult(r, d) for r, d in zip(rows.tolist(), dist.tolist())]
 
 
@@ -862,14 +1060,27 @@ class TableTopkBuilder(TopkBuilder):
         self._max_candidates = _max_candidates_arg(n)
         return self
 
+    def where(self, x):
+        """One pyarrow expression for all files, or a list with one bool array / expression per file (TopkBuilder.where)."""
+        self._where = _table_where_arg(x, self._paths)
+        return self
+
     def search(self):
         if self._k is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "k must be set")
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
-        rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, max_candidates=self._max_candidates,
-                                   metric=self._metric)
+        if self._where is not None:
+            mask = _resolve_table_where(self._where, self._paths, s)
+            try:
+                rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, max_candidates=self._max_candidates,
+                                           metric=self._metric, mask=mask)
+            finally:
+                mask.close()
+        else:
+            rows, dist, nf, _ = s.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, max_candidates=self._max_candidates,
+                                       metric=self._metric)
         n = int(nf[0])
         return _table_results(s, self._paths, rows[0, :n], dist[0, :n])
 
@@ -887,14 +1098,28 @@ class TableRangeBuilder(RangeBuilder):
         self._max_candidates = _max_candidates_arg(n)
         return self
 
+    def where(self, x):
+        """As TableTopkBuilder.where."""
+        self._where = _table_where_arg(x, self._paths)
+        return self
+
     def search(self):
         if self._radius is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "radius must be set")
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
-        _, rows, dist, _, _ = s.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
-                                             max_candidates=self._max_candidates, max_results=self._max_results, metric=self._metric)
+        if self._where is not None:
+            mask = _resolve_table_where(self._where, self._paths, s)
+            try:
+                _, rows, dist, _, _ = s.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
+                                                     max_candidates=self._max_candidates, max_results=self._max_results,
+                                                     metric=self._metric, mask=mask)
+            finally:
+                mask.close()
+        else:
+            _, rows, dist, _, _ = s.range_search(_f32(self._query).reshape(1, -1), self._radius, self._nprobe,
+                                                 max_candidates=self._max_candidates, max_results=self._max_results, metric=self._metric)
         return _table_results(s, self._paths, rows, dist)
 
 

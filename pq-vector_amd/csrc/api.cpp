@@ -111,7 +111,7 @@ int use_device(int device) {
     if (!lazy && device < 64)
         std::call_once(warmed[device], [] {
             (void)pqv::touch_probe(nullptr); (void)pqv::touch_screen(nullptr); (void)pqv::touch_brute(nullptr); (void)pqv::touch_build(nullptr);
-            (void)pqv::touch_layout(nullptr); (void)pqv::touch_list(nullptr); (void)pqv::touch_kpp(nullptr); (void)pqv::touch_range(nullptr);
+            (void)pqv::touch_layout(nullptr); (void)pqv::touch_list(nullptr); (void)pqv::touch_kpp(nullptr); (void)pqv::touch_range(nullptr); (void)pqv::touch_mask(nullptr);
             (void)hipStreamSynchronize(nullptr);
             // ... and the runtime's staging buffers for copies from / to pageable host memory are made by the first such copies
             void *d = nullptr;
@@ -344,6 +344,7 @@ struct Scratch {
 
 struct pqv_searcher {
     int device = 0;
+    uint64_t uid = 0;                      // unique per searcher made in this process (a pqv_row_mask remembers its searcher by it)
     uint32_t dim = 0, n_clusters = 0;
     // storage dimension of the IVF-ordered rows: dim, or dim zero-padded to a multiple of 64 / 128 / 256 where the MFMA
     // screen has no tiling for dim itself (dim % 4 == 0; kernels_layout.hip: pad_rows_kernel -- distances stay bit-identical).
@@ -491,6 +492,26 @@ static int lane_release(Scratch &sc, hipStream_t stream) {
 struct LaneGuard {
     Scratch &sc; hipStream_t stream;
     ~LaneGuard() { if (sc.done) (void)hipEventRecord(sc.done, stream); }
+};
+
+// A row mask (pqv.h: pqv_row_mask): one allow bit per row of the searcher's corpus, kept as the device bitset over LIST POSITIONS
+// that masked_stream_kernel reads (kernels_mask.hip) and as the caller's bytes in row order for the host replays.  The bitset is
+// indexed through d_ids -- list position -> the row a call reports, the same table in every layout -- and the cosine searcher
+// (ensure_cosine) shares its searcher's lists, so ONE image serves the row-order, IVF-ordered, images-only and cosine layouts.
+// Immutable after creation; it holds no pointer into its searcher that it follows (owner / owner_uid are compared, never read
+// through), so mask and searcher may be freed in either order.
+struct pqv_row_mask {
+    const pqv_searcher *owner = nullptr;
+    uint64_t owner_uid = 0;
+    int device = 0;
+    uint64_t n_rows = 0, count = 0;
+    DevBuf d_bits;                     // [ceil(n / 64) + 1] u64 image, then one u64: the allowed total
+    std::vector<uint8_t> host;         // [n_rows] allow bytes in row order
+};
+// what a masked call hands down (nullptr: the unmasked call)
+struct MaskView {
+    const uint64_t *bits;              // device image
+    const uint8_t *host;               // row-order bytes
 };
 
 // ---------------------------------------------------------------------------------------
@@ -2668,6 +2689,7 @@ static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, 
     if (int rc = use_device(corpus->device)) return rc;
     pqv_searcher *s = new (std::nothrow) pqv_searcher();
     if (!s) return fail(PQV_ERR_OOM, "host allocation failed");
+    { static std::atomic<uint64_t> next_uid{1}; s->uid = next_uid.fetch_add(1, std::memory_order_relaxed); }
     s->device = corpus->device; s->dim = index->dim; s->sdim = index->dim; s->n_clusters = index->n_clusters;
     if (!(flags & PQV_LAYOUT_ROW_ORDER) && (s->dim % 4) == 0 && (s->dim % 64) != 0) {
         // zero-padded storage: the cheapest tiling whose padding stays within a third of the row -- int8 images (a multiple
@@ -3104,7 +3126,9 @@ static bool seed_refine_on(const pqv_searcher *s, uint32_t nq, uint32_t k) {
     (void)nq;
     return s->opt.seed_refine && (!s->d_row_of || s->images_only) && (s->sdim % 32) == 0 && k <= 16 && (s->opt.seed_refine > 1 || s->sdim >= 256);
 }
-TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t k = 1, int metric = 0) {
+// exact_stream: a masked call -- the per-(query, list) stream whatever the options say (the screened paths' thresholds come from
+// sampled rows the mask may exclude)
+TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t k = 1, int metric = 0, bool exact_stream = false) {
     TopkPlan p{};
     const pqv_searcher::Opts &o = s->opt;
     p.np = probe_count(s, nprobe);
@@ -3140,6 +3164,7 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     if (wide_any_batch) p.tile = true;
     if (o.rerank_mode == 1) p.tile = false;
     if (o.rerank_mode == 2) p.tile = metric == PQV_L2SQ_REF4 && k <= 256;
+    if (exact_stream) p.tile = false;
     if (p.tile) {
         const uint64_t est_groups = std::max<uint64_t>(1, pairs / pqv::TILE_QB);
         // Rows per block: long enough to amortise a block's setup and top-k warm-up, short
@@ -3382,9 +3407,9 @@ int timing_events(const pqv_searcher *s, hipEvent_t (&e)[4]) {
 int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uint32_t k,
                  uint32_t k_out, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                  uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand,
-                 uint32_t *d_tie, hipStream_t stream, Scratch &sc) {
+                 uint32_t *d_tie, hipStream_t stream, Scratch &sc, const MaskView *mask = nullptr) {
     using namespace pqv;
-    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric);
+    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, mask != nullptr);
     const uint64_t max_pos = max_candidates ? max_candidates : ~0ull;
     // the probe works on the queries as given; everything that meets the (possibly zero-padded) stored rows gets the
     // batch's queries padded the same way
@@ -3399,7 +3424,8 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     MergeArgs pm{};
     if (int rc = probe_merge_args(s, sc, p, nq, max_candidates, pm)) return rc;
     if (d_n_cand) pm.n_cand = d_n_cand;
-    pm.stats = s->d_stats.as<unsigned long long>();
+    // (a masked call: candidate_rows and embeddings_fetched -- the considered rows -- are counted by masked_stream_kernel)
+    pm.stats = mask ? nullptr : s->d_stats.as<unsigned long long>();
     HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint32_t)));
 
@@ -3721,7 +3747,12 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
     if (!p.tile) {
         if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
-        HIP_TRY(launch_stream(ra, STREAM_TOPK, stream));
+        if (mask) {
+            const MaskedArgs ma{mask->bits, s->d_stats.as<unsigned long long>(), pm.n_cand};
+            HIP_TRY(launch_masked_stream(ra, ma, STREAM_TOPK, stream));
+        } else {
+            HIP_TRY(launch_stream(ra, STREAM_TOPK, stream));
+        }
         if (ev[2]) HIP_TRY(hipEventRecord(ev[2], stream));
     }
 
@@ -3822,10 +3853,12 @@ inline void heap_pop(std::vector<HeapEnt> &h) {
 // through the heap in candidate order.  d_probe / d_cand_base: the query's probe list on the device; `clusters` the
 // same list on the host.  Any k (the selection is the heap's), any nprobe (the grid is cut into slices of probed lists).
 // A round-robin capped table (table_rr) replays each list up to its file's quota (table_pair_ends; `nprobe` is read there only).
+// allow (a masked call: row-order allow bytes): a capped candidate whose row is not allowed is skipped in arrival order -- it never
+// meets the heap; *considered = the rows that did.
 int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_query, const uint32_t *d_probe,
                          const uint64_t *d_cand_base, const std::vector<uint32_t> &clusters, uint32_t k,
                          uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                         uint32_t *n_found, uint32_t nprobe = 0) {
+                         uint32_t *n_found, uint32_t nprobe = 0, const uint8_t *allow = nullptr, uint64_t *considered = nullptr) {
     using namespace pqv;
     const uint32_t np = static_cast<uint32_t>(clusters.size());
     uint64_t total = 0;
@@ -3852,7 +3885,7 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
     heap.reserve(static_cast<size_t>(std::min<uint64_t>(k, use)) + 1);
     std::vector<uint64_t> pair_end;
     if (table_rr(s, max_candidates)) table_pair_ends(s, clusters, nprobe, max_candidates, pair_end);
-    uint64_t base = 0;
+    uint64_t base = 0, n_considered = 0;
     const std::vector<uint32_t> *h_rows = s->h_rows->get();             // (the index' host lists: downloaded by the first call that reads them)
     if (!h_rows) return PQV_ERR_HIP;
     for (size_t j = 0; j < clusters.size(); ++j) {                      // candidate_rows order
@@ -3862,6 +3895,8 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
         base += e - b;
         for (uint64_t i = b; i < e && pos < lim; ++i, ++pos) {
             const HeapEnt ent{d[pos], (*h_rows)[i]};
+            if (allow && !allow[ent.row]) continue;
+            ++n_considered;
             if (heap.size() < k) heap_push(heap, ent);                   // search.rs:119-120
             else if (ent.d < heap[0].d) { heap_pop(heap); heap_push(heap, ent); }   // :121-125
         }
@@ -3874,20 +3909,21 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
         else { row_idx[i] = 0xFFFFFFFFu; dist[i] = INFINITY; }
     }
     if (n_found) *n_found = static_cast<uint32_t>(heap.size());
+    if (considered) *considered = n_considered;
     return PQV_OK;
 }
 
 // qi indexes the current sub-batch's probe scratch (written by the probe merge).
 int replay_query_exact(const pqv_searcher *s, Scratch &sc, const float *d_query, uint32_t qi, uint32_t np, uint32_t k,
                        uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                       uint32_t *n_found, uint32_t nprobe) {
+                       uint32_t *n_found, uint32_t nprobe, const uint8_t *allow = nullptr) {
     std::vector<uint32_t> clusters(np);
     HIP_TRY(hipMemcpyAsync(clusters.data(), sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * np,
                            np * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return replay_with_clusters(s, sc, d_query, sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * np,
                                 sc.s_cand_base.as<uint64_t>() + static_cast<size_t>(qi) * np, clusters, k, max_candidates,
-                                metric, sqrt_out, row_idx, dist, n_found, nprobe);
+                                metric, sqrt_out, row_idx, dist, n_found, nprobe, allow);
 }
 
 // find_closest_centroids (index.rs:130-149) without the kernels' list limit: every centroid distance on the GPU
@@ -3970,7 +4006,7 @@ int host_probe(const pqv_searcher *s, Scratch &sc, const float *d_queries, uint3
 // candidate distance on the GPU, the reference's heap on the host.  Correct for any k / nprobe; not a fast path.
 int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                    uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found,
-                   uint64_t *n_candidates) {
+                   uint64_t *n_candidates, const MaskView *mask = nullptr) {
     using namespace pqv;
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
     std::vector<uint32_t> clusters;
@@ -3987,14 +4023,15 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
             d_q_s = sc.s_qpad.as<float>();
         }
         uint32_t nf = 0;
+        uint64_t considered = 0;
         if (int rc = replay_with_clusters(s, sc, d_q_s, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(),
                                           clusters, k, max_candidates, metric, sqrt_out, row_idx + static_cast<uint64_t>(q) * k,
-                                          dist + static_cast<uint64_t>(q) * k, &nf, nprobe))
+                                          dist + static_cast<uint64_t>(q) * k, &nf, nprobe, mask ? mask->host : nullptr, &considered))
             return rc;
         if (n_found) n_found[q] = nf;
         if (n_candidates) n_candidates[q] = total;
         s->counters.candidate_rows += total;                             // index_exec.rs:289-299
-        s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(total, max_candidates) : total;   // exec.rs:411-427
+        s->counters.embeddings_fetched += considered;                    // exec.rs:411-427 (unmasked: min(total, max_candidates))
         s->counters.queries += 1;
         s->counters.exact_replays += 1;
     }
@@ -4025,7 +4062,7 @@ static int cosine_queries_host(const pqv_searcher *s, const float *queries, uint
 static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, uint32_t nq, uint32_t k,
                                uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
-                               void *d_tie_flags, void *hip_stream) {
+                               void *d_tie_flags, void *hip_stream, const MaskView *mask = nullptr) {
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
     if (int rc = table_max_candidates(s, max_candidates)) return rc;
     if (d_tie_flags && k > 1023) return fail(PQV_ERR_UNSUPPORTED, "tie flags need a runner-up entry: k <= 1023");
@@ -4048,7 +4085,7 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
         HIP_TRY(lane->s_qcos.ensure(static_cast<size_t>(nq) * s->dim * sizeof(float)));
         HIP_TRY(pqv::launch_normalize_rows(static_cast<const float *>(d_queries), s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), stream));
         if (int rc = pqv_topk_device_impl(s->cos.get(), lane->s_qcos.p, nq, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
-                                          d_n_found, d_n_candidates, d_tie_flags, stream))
+                                          d_n_found, d_n_candidates, d_tie_flags, stream, mask))
             return rc;
         return lane_release(*lane, stream);
     }
@@ -4058,7 +4095,7 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
     const int rc = enqueue_topk(s, static_cast<const float *>(d_queries), nq, d_tie_flags ? k + 1 : k, k, nprobe, max_candidates,
                                 metric, sqrt_out, static_cast<uint32_t *>(d_row_idx),
                                 static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
-                                static_cast<uint64_t *>(d_n_candidates), static_cast<uint32_t *>(d_tie_flags), stream, *lane);
+                                static_cast<uint64_t *>(d_n_candidates), static_cast<uint32_t *>(d_tie_flags), stream, *lane, mask);
     if (rc == PQV_OK) s->counters.queries += nq;
     return rc;
 }
@@ -4078,7 +4115,7 @@ extern "C" int pqv_topk_device_flags(const pqv_searcher *s, const void *d_querie
 
 static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len,
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
-                        uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
+                        uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates, const MaskView *mask = nullptr) {
     if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
@@ -4087,7 +4124,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         std::vector<float> nq_host;
         if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
         return pqv_topk_impl(s->cos.get(), nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist, n_found,
-                             n_candidates);
+                             n_candidates, mask);
     }
     std::lock_guard<std::mutex> lock(s->mu);
     // One extra merged entry (the runner-up) lets the merge kernel see ties at the k-th
@@ -4099,13 +4136,13 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     Scratch &sc = *lane;
     LaneGuard lane_guard{sc, s->stream};
     if (k >= 1024u || beyond_kernel_lists(s, k_int, nprobe)) {
-        const int rc = topk_unbounded(s, sc, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates);
+        const int rc = topk_unbounded(s, sc, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates, mask);
         const int rc2 = lane_release(sc, s->stream);
         return rc ? rc : rc2;
     }
     // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
     // (per query: partial lists, probe partial lists, candidate buffer, the int8 images of its probed pairs)
-    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), nprobe, k_int, metric);
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), nprobe, k_int, metric, mask != nullptr);
     const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * k_int * 12 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
                                static_cast<uint64_t>(cand_cap_for(s, k_int)) * 12 + static_cast<uint64_t>(p1.np) * (s->sdim + 32) +
                                static_cast<uint64_t>(s->sdim) * 4 + 1;
@@ -4155,7 +4192,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         if (int rc = enqueue_topk(s, sc.s_queries.as<float>(), b, k_int, k, nprobe, max_candidates, metric,
                                   sqrt_out, o_rows, o_dist, o_nf,
                                   small_io ? reinterpret_cast<uint64_t *>(direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p)) : nullptr,
-                                  o_tie, s->stream, sc))
+                                  o_tie, s->stream, sc, mask))
             return rc;
         if (small_io) {
             char *hb = static_cast<char *>(sc.h_io.p) + out_off;
@@ -4188,7 +4225,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
                                                                           : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i, np,
                                                 k, max_candidates, metric, sqrt_out,
                                                 row_idx + static_cast<uint64_t>(q0 + i) * k,
-                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe))
+                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, mask ? mask->host : nullptr))
                     return rc;
                 s->counters.exact_replays++;
             }
@@ -4227,7 +4264,7 @@ int grow_host(std::unique_ptr<T, HostFree> &buf, uint64_t &cap, uint64_t need) {
 int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, float radius, uint32_t nprobe,
                uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t *lims,
                std::unique_ptr<uint32_t, HostFree> &rows, std::unique_ptr<float, HostFree> &dist, uint64_t *n_within,
-               uint64_t *n_candidates) {
+               uint64_t *n_candidates, const MaskView *mask = nullptr) {
     using namespace pqv;
     hipStream_t st = s->stream;
     const uint32_t kc = s->n_clusters, np = probe_count(s, nprobe);
@@ -4279,7 +4316,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             const TopkPlan p = plan_topk(s, b, nprobe, 1, metric);
             MergeArgs pm{};
             if (int rc = probe_merge_args(s, sc, p, b, max_candidates, pm)) return rc;
-            pm.stats = s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
+            pm.stats = mask ? nullptr : s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
             if (int rc = enqueue_probe(s, sc, p, d_q, b, nprobe, max_candidates, pm, nullptr, 0, st)) return rc;
             launches += 2;
         } else {
@@ -4287,7 +4324,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             if (int rc = host_probe(s, sc, d_q, b, nprobe, max_candidates, true, h_probe, h_ncand.data())) return rc;
             for (uint32_t i = 0; i < b; ++i) {
                 s->counters.candidate_rows += h_ncand[i];                         // index_exec.rs:289-299
-                s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(h_ncand[i], max_candidates) : h_ncand[i];
+                if (!mask) s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(h_ncand[i], max_candidates) : h_ncand[i];
             }
         }
 
@@ -4306,6 +4343,10 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         if (e[1]) HIP_TRY(hipEventRecord(e[1], st));
         for (uint32_t j0 = 0; j0 < np; j0 += 32768) {                    // gridDim.y <= 65535
             ra.j0 = j0; ra.nj = std::min<uint32_t>(32768, np - j0);
+            if (mask) {      // (the considered rows are counted by the kernel; candidate_rows too unless the host probe counted it above)
+                const MaskedArgs ma{mask->bits, s->d_stats.as<unsigned long long>(), wide_probe ? nullptr : sc.s_ncand.as<uint64_t>()};
+                HIP_TRY(launch_masked_stream(ra, ma, STREAM_RANGE, st));
+            } else
             HIP_TRY(launch_stream(ra, STREAM_RANGE, st));
             ++launches;
         }
@@ -4373,7 +4414,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
 static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len, float radius,
                                  uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                                  uint64_t **lims_out, uint32_t **rows_out, float **dist_out, uint64_t *n_within,
-                                 uint64_t *n_candidates) {
+                                 uint64_t *n_candidates, const MaskView *mask = nullptr) {
     if (int rc = validate_query(s, 1, nprobe, metric, max_candidates, query_len)) return rc;
     if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
     if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
@@ -4399,7 +4440,7 @@ static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, ui
         if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
         LaneGuard lane_guard{*lane, s->stream};
         if (int rc = range_body(s, *lane, queries, nq, radius, nprobe, max_candidates, max_results, metric, sqrt_out, lims.get(), rows,
-                                dist, n_within, n_candidates))
+                                dist, n_within, n_candidates, mask))
             return rc;
         if (int rc = lane_release(*lane, s->stream)) return rc;
     }
@@ -4414,6 +4455,104 @@ extern "C" int pqv_range_search(const pqv_searcher *s, const float *queries, uin
 }
 extern "C" void pqv_range_free(uint64_t *lims, uint32_t *row_idx, float *dist) {
     std::free(lims); std::free(row_idx); std::free(dist);
+}
+
+// ---- row masks (pqv.h: pqv_row_mask) -----------------------------------------------------------------------------------
+// Creation: the allow bytes (host: through a temporary device copy; device: as given) -> mask_layout_kernel -> the position image
+// and the allowed total, and the row-order bytes kept on the host for the replays.  Complete on return.
+static int row_mask_create_impl(const pqv_searcher *s, const uint8_t *h_allowed, const void *d_allowed, uint64_t n_rows, void *hip_stream,
+                                pqv_row_mask **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    const uint64_t corpus_rows = s->corpus ? s->corpus->n : 0;
+    if (n_rows != corpus_rows)
+        return fail(PQV_ERR_INVALID, "row mask has " + std::to_string(n_rows) + " rows, the corpus has " + std::to_string(corpus_rows));
+    if (n_rows && !h_allowed && !d_allowed) return fail(PQV_ERR_INVALID, "allowed must not be NULL");
+    if (int rc = use_device(s->device)) return rc;
+    std::unique_ptr<pqv_row_mask> m(new (std::nothrow) pqv_row_mask());
+    if (!m) return fail(PQV_ERR_OOM, "host allocation failed");
+    m->owner = s; m->owner_uid = s->uid; m->device = s->device; m->n_rows = n_rows;
+    m->host.resize(n_rows);
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+    const uint64_t n_words = (s->n + 63) / 64 + 1;
+    HIP_TRY(m->d_bits.alloc((n_words + 1) * sizeof(uint64_t)));
+    unsigned long long *d_count = m->d_bits.as<unsigned long long>() + n_words;
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
+    DevBuf d_tmp;
+    const uint8_t *d_src = static_cast<const uint8_t *>(d_allowed);
+    if (h_allowed) {
+        if (n_rows) std::memcpy(m->host.data(), h_allowed, n_rows);
+        HIP_TRY(d_tmp.alloc(n_rows));
+        if (n_rows) HIP_TRY(hipMemcpyAsync(d_tmp.p, h_allowed, n_rows, hipMemcpyHostToDevice, stream));
+        d_src = d_tmp.as<uint8_t>();
+    } else if (n_rows) {
+        HIP_TRY(hipMemcpyAsync(m->host.data(), d_allowed, n_rows, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(pqv::launch_mask_layout(d_src, n_rows, s->d_ids.as<uint32_t>(), s->n, m->d_bits.as<uint64_t>(), n_words, d_count, stream));
+    unsigned long long h_count = 0;
+    HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof h_count, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));       // (d_tmp is released at scope exit)
+    m->count = h_count;
+    *out = m.release();
+    return PQV_OK;
+}
+extern "C" int pqv_row_mask_create(const pqv_searcher *s, const uint8_t *allowed, uint64_t n_rows, pqv_row_mask **out) {
+    return guard([&] {
+        if (out) *out = nullptr;
+        if (s && out && n_rows && !allowed) return fail(PQV_ERR_INVALID, "allowed must not be NULL");
+        static const uint8_t none = 0;
+        return row_mask_create_impl(s, allowed ? allowed : &none, nullptr, n_rows, nullptr, out);
+    });
+}
+extern "C" int pqv_row_mask_from_device(const pqv_searcher *s, const void *d_allowed, uint64_t n_rows, void *hip_stream, pqv_row_mask **out) {
+    return guard([&] { return row_mask_create_impl(s, nullptr, d_allowed, n_rows, hip_stream, out); });
+}
+extern "C" uint64_t pqv_row_mask_rows(const pqv_row_mask *m) { return m ? m->n_rows : 0; }
+extern "C" uint64_t pqv_row_mask_count(const pqv_row_mask *m) { return m ? m->count : 0; }
+extern "C" void pqv_row_mask_free(pqv_row_mask *m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    delete m;
+}
+
+// the checks every masked entry point makes before anything else (after the searcher's own NULL check)
+static int mask_view(const pqv_searcher *s, const pqv_row_mask *mask, MaskView &mv) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!mask) return fail(PQV_ERR_INVALID, "row mask must not be NULL");
+    if (mask->owner != s || mask->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+    mv.bits = mask->d_bits.as<uint64_t>(); mv.host = mask->host.data();
+    return PQV_OK;
+}
+extern "C" int pqv_topk_masked(const pqv_searcher *s, const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len,
+                               uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                               uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = mask_view(s, mask, mv)) return rc;
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
+    });
+}
+extern "C" int pqv_topk_masked_device(const pqv_searcher *s, const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k,
+                                      uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                      void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
+                                      void *d_tie_flags, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = mask_view(s, mask, mv)) return rc;
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, d_tie_flags, hip_stream, &mv);
+    });
+}
+extern "C" int pqv_range_search_masked(const pqv_searcher *s, const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len,
+                                       float radius, uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
+                                       uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = mask_view(s, mask, mv)) return rc;
+        return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
+                                     row_idx, dist, n_within, n_candidates, &mv);
+    });
 }
 
 static int pqv_searcher_set_option_impl(pqv_searcher *s, const char *name, int64_t value) {

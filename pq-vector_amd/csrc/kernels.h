@@ -67,6 +67,22 @@ struct StreamArgs {
 // Streaming exact-order squared-L2 pass (the re-rank kernel).  Returns hipError_t.
 hipError_t launch_stream(const StreamArgs &a, StreamMode mode, hipStream_t s);
 
+// ---- row-masked searches (kernels_mask.hip) ------------------------------------------------------------------------------
+// A row mask on the device is a bitset over LIST POSITIONS: bit p = the caller's allow byte of the row position p reports.
+// launch_mask_layout writes it from allow bytes in row order (ids: list position -> reported row, a searcher's d_ids) -- all
+// n_words words, n_words >= ceil(n_pos / 64) + 1, bits of positions >= n_pos zero -- and adds the allowed total to *count.
+hipError_t launch_mask_layout(const uint8_t *allowed, uint64_t n_rows, const uint32_t *ids, uint64_t n_pos, uint64_t *bits,
+                              uint64_t n_words, unsigned long long *count, hipStream_t s);
+struct MaskedArgs {
+    const uint64_t     *bits;     // the image above
+    unsigned long long *stats;    // optional: the searcher's statistics block -- every wave adds the rows it evaluated to the
+                                  // embeddings_fetched word of its query's slot (the probe merge of a masked call gets no MergeArgs::stats)
+    const uint64_t     *n_cand;   // optional [nq] (with stats): the probe merge's uncapped totals, added to candidate_rows once per query
+};
+// launch_stream's STREAM_TOPK / STREAM_RANGE pass over the allowed positions only (masked_stream_kernel): the same grid, chain
+// arithmetic, keys and output formats; a.probe / a.list_off / a.cand_base are required.
+hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s);
+
 // Batched centroid probe (probe_rows_kernel): every query against every centroid, exact reference order.
 struct ProbeRowsArgs {
     const float4   *cent_t;      // [dim/4][kc_pad] float4 transpose of the centroid table (launch_transpose_rows4)
@@ -730,5 +746,6 @@ hipError_t touch_layout(hipStream_t s);
 hipError_t touch_list(hipStream_t s);
 hipError_t touch_kpp(hipStream_t s);
 hipError_t touch_range(hipStream_t s);
+hipError_t touch_mask(hipStream_t s);
 
 }  // namespace pqv

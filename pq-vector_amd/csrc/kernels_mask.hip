@@ -1,0 +1,293 @@
+// kernels_mask.hip -- gfx950 kernels of the row-masked searches (pqv.h: pqv_row_mask): mask_layout_kernel (allow bytes in row
+// order -> a bitset indexed by LIST POSITION) and masked_stream_kernel (stream_kernel's exact distance pass over the allowed
+// positions only).  The screened paths take their thresholds from sampled rows; a threshold from a row the mask excludes is no
+// bound on the masked answer, so masked calls always run this exact pass.
+#include "device_common.hpp"
+
+namespace pqv {
+
+// ------------------------------------------------------------------------------------
+// mask_layout_kernel: bit p of `bits` = allowed[ids[p]] for list position p (ids: list position -> the row a call reports, a
+// searcher's d_ids in every layout).  One thread per position; a wave's 64 answers are one __ballot word, stored by lane 0
+// (positions start at a multiple of 64 per wave, so the word index is p / 64); positions >= n_pos give zero bits.  The allowed
+// total: a popcount and one atomicAdd per wave.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mask_layout_kernel(const uint8_t *allowed, uint64_t n_rows, const uint32_t *ids, uint64_t n_pos,
+                                                          uint64_t *bits, uint64_t n_words, unsigned long long *count) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool on = false;
+    if (p < n_pos) {
+        const uint64_t r = ids ? ids[p] : p;
+        on = r < n_rows && allowed[r] != 0;
+    }
+    const uint64_t m = __ballot(on);
+    if ((threadIdx.x & 63) == 0) {
+        const uint64_t w = p >> 6;
+        if (w < n_words) bits[w] = m;
+        if (m) atomicAdd(count, (unsigned long long)__popcll(m));
+    }
+}
+
+hipError_t launch_mask_layout(const uint8_t *allowed, uint64_t n_rows, const uint32_t *ids, uint64_t n_pos, uint64_t *bits,
+                              uint64_t n_words, unsigned long long *count, hipStream_t s) {
+    // every word of the image is written: one wave per word, n_words >= ceil(n_pos / 64) + 1 (masked_stream_kernel reads two words)
+    const uint64_t blocks = (n_words * 64 + 255) / 256;
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_layout_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, allowed, n_rows, ids, n_pos, bits, n_words, count);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// masked_stream_kernel
+//
+// stream_kernel's grid (row block, probe rank, query), its 4 independent waves per block and its chain arithmetic, element for
+// element (REF4 groups / SEQ squares, dim % 4 tails, unaligned rows; the unit is built with -ffp-contract=off like the others).
+// What differs is WHICH rows fill a 64-row tile: a wave walks its position range [r0, r1) of the list in 64-position windows,
+// reads the window's mask word (lbeg + r0 is not 64-aligned: two words, funnel-shifted), drops the bits at or beyond the
+// candidate cap (max_pos / pair_end) and compacts the set positions into a queue, rank from mbcnt.  A chain tile runs whenever 64
+// positions are queued, and once more at the end of the range -- so the f32 bytes read are (considered rows) x 4 dim and a row
+// the mask excludes is never loaded.  Keys stay (d2 bits << 32) | (u32)(cbase + position in list): the unmasked positions.
+//
+// The queue: its first 64 entries live in a register (lane i holds entry i), at most 63 of them between two windows.  A window's
+// compaction goes through the first 128 words of the wave's tile area in LDS, which is idle between two chain tiles -- no LDS
+// beside the tile, so an instantiation's occupancy is its stream_kernel twin's (CG = 32: 32 KiB per block; a queue of its own
+// would take the fifth block per CU away).
+//
+// Outputs: stream_kernel's (per-wave partial lists / hit segments).  Each wave adds the rows it evaluated to the
+// embeddings_fetched word of the query's statistics slot; the (0, 0) block of a query adds n_cand[q] to candidate_rows.
+// ------------------------------------------------------------------------------------
+template <int CG, int S, int MODE, bool SEQ, bool ALIGNED>
+__global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, const MaskedArgs ma) {
+    constexpr int RPI = 64 / CG;        // rows per load instruction
+    constexpr int NI = CG;              // load instructions per 64-row tile
+    constexpr int EPL = SEQ ? 4 : 1;    // LDS values per lane item
+    constexpr int LROWS = CG * EPL;     // chain length per chunk
+    constexpr int NB = 8;               // loads in flight per lane
+    static_assert(NI % NB == 0, "NI must be a multiple of NB");
+    static_assert(LROWS * 64 >= 128, "the compaction needs 128 words of the tile area");
+
+    __shared__ float lds_all[4 * LROWS * 64];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    float *lds = lds_all + wave * (LROWS * 64);
+    uint32_t *cq = reinterpret_cast<uint32_t *>(lds);          // compaction scratch: 128 entries
+#define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
+
+    const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
+    const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
+    const uint64_t lbeg = a.list_off[c], lend = a.list_off[c + 1];
+    const uint64_t cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
+    const uint64_t lim = a.pair_end ? a.pair_end[(uint64_t)q * a.nprobe + j] : a.max_pos;
+    uint64_t len = lend - lbeg;
+    // positions at or beyond the cap are no candidates: the walk ends there (their bits are never looked at)
+    const uint64_t room = lim > cbase ? lim - cbase : 0;
+    if (len > room) len = room;
+    const uint64_t wrows = a.rows_per_block / 4;
+    const uint64_t r0 = (uint64_t)blockIdx.x * a.rows_per_block + (uint64_t)wave * wrows;
+    uint64_t r1 = r0 + wrows;
+    if (r1 > len) r1 = len;
+
+#ifdef PQV_PROFILE_PHASES
+    unsigned long long *st = ma.stats;
+#else
+    unsigned long long *st = ma.stats ? ma.stats + 8 + 16 * (q % STATS_SLOTS) : nullptr;
+#endif
+    if (ma.n_cand && st && blockIdx.x == 0 && j == 0 && threadIdx.x == 0) atomicAdd(&st[2], (unsigned long long)ma.n_cand[q]);
+
+    const uint32_t dim = a.dim;
+    const uint32_t G = dim >> 2;
+    const uint32_t tail = dim & 3u;
+    const float *qv = a.queries + (uint64_t)q * dim;
+    const int g_in = lane % CG;      // my float4 group inside a chunk
+    const int row_in = lane / CG;    // my row inside a load instruction
+
+    WaveTopk<S> tk;
+    if constexpr (MODE == STREAM_TOPK) tk.init();
+
+    uint32_t pend = 0;      // queue entry `lane` (a list offset, < 2^32 as every candidate position), meaningful for lane < qn
+    uint32_t qn = 0;        // queued entries, < 64 between two windows (wave-uniform)
+    uint32_t n_eval = 0;    // rows this wave evaluated (wave-uniform)
+    for (uint64_t w0 = r0;; w0 += 64) {
+        const bool flush = w0 >= r1;        // past the range: what is left in the queue is the last tile
+        uint32_t nvalid = 0;                // rows of the chain tile this turn runs (0: none)
+        uint32_t my_r = 0;                  // list offset of tile row `lane`
+        if (!flush) {
+            const uint64_t p = lbeg + w0;
+            const uint64_t wi = p >> 6;
+            const uint32_t sh = (uint32_t)(p & 63u);
+            // (the image has one word of padding behind the last position: wi + 1 is always in range)
+            const uint64_t lo = ma.bits[wi], hi = ma.bits[wi + 1];
+            uint64_t win = sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
+            if (r1 - w0 < 64) win &= (1ull << (r1 - w0)) - 1ull;
+            const uint32_t cnt = (uint32_t)__popcll(win);
+            if (cnt == 0) continue;
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(win >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)win, 0u));
+            if ((uint32_t)lane < qn) cq[lane] = pend;
+            if ((win >> lane) & 1ull) cq[qn + rank] = (uint32_t)(w0 + (uint64_t)lane);
+            wave_lds_fence();
+            const uint32_t total = qn + cnt;                   // <= 127
+            const uint32_t first = cq[lane];
+            const uint32_t over = cq[64 + lane];
+            wave_lds_fence();
+            if (total >= 64) {
+                my_r = first; nvalid = 64u;
+                pend = over; qn = total - 64;
+            } else {
+                pend = first; qn = total;
+            }
+        } else if (qn) {
+            const uint32_t last = (uint32_t)__shfl((int)pend, (int)(qn - 1), 64);
+            my_r = (uint32_t)lane < qn ? pend : last;         // (clamped: every address in range)
+            nvalid = qn; qn = 0;
+        }
+        if (nvalid) {
+            n_eval += nvalid;
+            const uint64_t lpos = lbeg + my_r;
+            const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
+
+            float sum = 0.0f;
+            for (uint32_t c0 = 0; c0 < G; c0 += CG) {
+                const uint32_t ng = (G - c0 < (uint32_t)CG) ? (G - c0) : (uint32_t)CG;
+                const bool gvalid = (uint32_t)g_in < ng;
+                const uint32_t goff = (c0 + (gvalid ? g_in : 0)) * 4;
+                const float4 qq = load4<ALIGNED>(qv + goff);
+
+#pragma unroll 1
+                for (int ib = 0; ib < NI; ib += NB) {
+                    float4 x[NB];
+#pragma unroll
+                    for (int u = 0; u < NB; ++u) {
+                        uint32_t rr = (uint32_t)((ib + u) * RPI + row_in);
+                        if (rr >= nvalid) rr = nvalid - 1;
+                        const uint32_t srow = (uint32_t)__shfl((int)my_srow, (int)rr, 64);
+                        x[u] = load4<ALIGNED>(a.mat + (uint64_t)srow * dim + goff);
+                    }
+#pragma unroll
+                    for (int u = 0; u < NB; ++u) {
+                        const int rr = (ib + u) * RPI + row_in;
+                        const float d0 = qq.x - x[u].x, d1 = qq.y - x[u].y;
+                        const float d2 = qq.z - x[u].z, d3 = qq.w - x[u].w;
+                        if constexpr (SEQ) {
+                            if (gvalid) {
+                                LDS_AT(g_in * 4 + 0, rr) = d0 * d0;
+                                LDS_AT(g_in * 4 + 1, rr) = d1 * d1;
+                                LDS_AT(g_in * 4 + 2, rr) = d2 * d2;
+                                LDS_AT(g_in * 4 + 3, rr) = d3 * d3;
+                            }
+                        } else {
+                            float t = d0 * d0 + d1 * d1;
+                            t = t + d2 * d2;
+                            t = t + d3 * d3;
+                            if (gvalid) LDS_AT(g_in, rr) = t;
+                        }
+                    }
+                }
+                wave_lds_fence();
+                const uint32_t nchain = ng * EPL;
+                uint32_t e = 0;
+                for (; e + 8 <= nchain; e += 8) {
+                    float v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = LDS_AT(e + u, lane);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) sum = sum + v[u];
+                }
+                for (; e < nchain; ++e) sum = sum + LDS_AT(e, lane);
+                wave_lds_fence();
+            }
+            if (tail) {  // scalar tail of squared_l2_distance (index.rs:474-478)
+                const float *xr = a.mat + (uint64_t)my_srow * dim + (uint64_t)G * 4;
+                const float *qt = qv + (uint64_t)G * 4;
+                for (uint32_t e = 0; e < tail; ++e) {
+                    const float d = qt[e] - xr[e];
+                    sum = sum + d * d;
+                }
+            }
+
+            const uint64_t pos = cbase + my_r;
+            const bool valid = (uint32_t)lane < nvalid;           // (pos < lim by the clamp of the walk)
+            if constexpr (MODE == STREAM_TOPK) {
+                const uint64_t mykey =
+                    valid ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos)
+                          : KEY_EMPTY;
+                tk.offer(mykey, my_srow, a.k, lane);
+            } else {
+                // the wave's hits go to the query's segment in one block: ballot, rank from mbcnt, one atomicAdd per wave
+                const float outv = a.sqrt_out == 1 ? sqrt_f32_ieee(sum) : a.sqrt_out == 2 ? 0.5f * sum : sum;     // (2: PQV_COSINE)
+                const bool hit = valid && outv <= a.radius;                // (a NaN distance never compares true)
+                const uint64_t m = __ballot(hit);
+                if (m) {
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(a.hit_cnt + q, (uint32_t)__popcll(m));
+                    base = (uint32_t)__shfl((int)base, 0, 64);
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (hit) {
+                        const uint64_t o = (uint64_t)q * a.seg_stride + base + rank;
+                        a.hit_keys[o] = ((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos;
+                        a.hit_vals[o] = my_srow;
+                    }
+                }
+            }
+        }
+        if (flush) break;
+    }
+    if (st && n_eval && lane == 0) atomicAdd(&st[3], (unsigned long long)n_eval);
+
+    if constexpr (MODE == STREAM_TOPK) {
+        const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
+        const uint32_t pi = (j * a.blocks_per_list + blockIdx.x) * 4 + wave;
+        const uint64_t base = ((uint64_t)q * n_part + pi) * a.k;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const uint32_t e = s * 64 + lane;
+            if (e < a.k) {
+                a.part_keys[base + e] = tk.key[s];
+                a.part_vals[base + e] = tk.val[s];
+            }
+        }
+    }
+}
+
+#undef LDS_AT
+
+template <int CG, int S, int MODE, bool SEQ, bool ALIGNED>
+static hipError_t launch_masked_t(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
+    dim3 grid(a.blocks_per_list, MODE == STREAM_RANGE ? a.nj : a.nprobe, a.nq);
+    hipLaunchKernelGGL((masked_stream_kernel<CG, S, MODE, SEQ, ALIGNED>), grid, dim3(256), 0, s, a, ma);
+    return hipGetLastError();
+}
+
+// the chunk choice of launch_stream (the chain order does not depend on it)
+template <int S, int MODE>
+static hipError_t launch_masked_s(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
+    const bool aligned = (a.dim % 4) == 0;
+    const uint32_t G = a.dim / 4;
+    if (a.metric == 1) {
+        return aligned ? launch_masked_t<16, S, MODE, true, true>(a, ma, s)
+                       : launch_masked_t<16, S, MODE, true, false>(a, ma, s);
+    }
+    if (!aligned) return launch_masked_t<32, S, MODE, false, false>(a, ma, s);
+    if (G >= 64 && G % 64 == 0) return launch_masked_t<64, S, MODE, false, true>(a, ma, s);
+    return launch_masked_t<32, S, MODE, false, true>(a, ma, s);
+}
+
+hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s) {
+    if (!a.probe || !a.list_off || !a.cand_base || !ma.bits) return hipErrorInvalidValue;
+    if (a.nq == 0 || a.blocks_per_list == 0) return hipSuccess;
+    if (mode == STREAM_RANGE) return a.nj == 0 ? hipSuccess : launch_masked_s<1, STREAM_RANGE>(a, ma, s);
+    if (mode != STREAM_TOPK) return hipErrorInvalidValue;
+    if (a.nprobe == 0) return hipSuccess;
+    if (a.k <= 64) return launch_masked_s<1, STREAM_TOPK>(a, ma, s);
+    if (a.k <= 256) return launch_masked_s<4, STREAM_TOPK>(a, ma, s);
+    if (a.k <= 1024) return launch_masked_s<16, STREAM_TOPK>(a, ma, s);
+    return hipErrorInvalidValue;
+}
+
+__global__ void touch_mask_kernel() {}
+hipError_t touch_mask(hipStream_t s) {
+    hipLaunchKernelGGL(touch_mask_kernel, dim3(1), dim3(64), 0, s);
+    return hipGetLastError();
+}
+
+}  // namespace pqv

@@ -99,9 +99,27 @@ private:
     uint32_t dim_ = 0;
 };
 
+// One allow bit per row of a searcher's corpus (pqv.h: pqv_row_mask); may outlive its searcher or be released before it.
+class RowMask {
+public:
+    RowMask(const Searcher &s, const std::vector<uint8_t> &allowed) {
+        pqv_row_mask *h = nullptr;
+        check(pqv_row_mask_create(s.get(), allowed.data(), allowed.size(), &h));
+        h_.reset(h);
+    }
+    const pqv_row_mask *get() const { return h_.get(); }
+    uint64_t rows() const { return pqv_row_mask_rows(h_.get()); }
+    uint64_t count() const { return pqv_row_mask_count(h_.get()); }
+private:
+    struct Del { void operator()(pqv_row_mask *p) const { pqv_row_mask_free(p); } };
+    std::unique_ptr<pqv_row_mask, Del> h_;
+};
+
 class TopkBuilder {
 public:
     TopkBuilder(const Searcher &s, const std::vector<float> &query) : s_(s), query_(query) {}
+    // only rows the mask allows are considered (the reference's predicate inside the scan, exec.rs:207-277)
+    TopkBuilder &where(const RowMask &m) { mask_ = &m; return *this; }
     TopkBuilder &k(uint32_t v) { if (!v) throw Error(PQV_ERR_INVALID, "k must be > 0"); k_ = v; return *this; }
     TopkBuilder &nprobe(uint32_t v) { if (!v) throw Error(PQV_ERR_INVALID, "nprobe must be > 0"); nprobe_ = v; return *this; }
     std::vector<SearchResult> search() const {
@@ -110,6 +128,10 @@ public:
         std::vector<uint32_t> rows(*k_);
         std::vector<float> dist(*k_);
         uint32_t found = 0;
+        if (mask_)
+            check(pqv_topk_masked(s_.get(), mask_->get(), query_.data(), 1, static_cast<uint32_t>(query_.size()), *k_, *nprobe_, 0,
+                                  PQV_L2SQ_REF4, 1, rows.data(), dist.data(), &found, nullptr));
+        else
         check(pqv_topk(s_.get(), query_.data(), 1, static_cast<uint32_t>(query_.size()), *k_, *nprobe_, 0,
                        PQV_L2SQ_REF4, 1, rows.data(), dist.data(), &found, nullptr));
         std::vector<SearchResult> out;
@@ -120,6 +142,7 @@ private:
     const Searcher &s_;
     const std::vector<float> &query_;
     std::optional<uint32_t> k_, nprobe_;
+    const RowMask *mask_ = nullptr;
 };
 
 }  // namespace pqv

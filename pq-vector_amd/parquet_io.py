@@ -867,3 +867,22 @@ def load_embedding_column(path, column, device=0, readers=None, stats=None, row_
         stats.update({"rows": int(n_rows), "dim": int(dim), "bytes": int(nbytes[0]), "seconds": el, "GBps": nbytes[0] / el / 1e9,
                       "row_groups": int(n_rg), "reader_threads": nthr, "path": "pyarrow record batches"})
     return into if into is not None else corpus
+
+
+def row_mask_from_expression(path, expr):
+    """The rows of a Parquet file that pass a predicate over its columns: `expr` (a pyarrow.compute.Expression, e.g.
+    pc.field("id") >= 2) evaluated for every row -> bool array in FILE ROW ORDER, a null result counting as False (SQL WHERE).
+    The input of TopkBuilder.where / Searcher.row_mask."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    import pyarrow.dataset as ds
+    if not isinstance(expr, pc.Expression):
+        raise _err(f"row_mask_from_expression needs a pyarrow.compute.Expression, got {type(expr).__name__}")
+    try:
+        # (one file, one fragment: the scanner yields its row groups in file order; projecting the expression keeps one bool per row)
+        col = ds.dataset(path, format="parquet").to_table(columns={"m": expr}).column("m")
+    except (pa.ArrowInvalid, pa.ArrowNotImplementedError, KeyError) as e:
+        raise _err(f"cannot evaluate the predicate over {path}: {e}")
+    if not pa.types.is_boolean(col.type):
+        raise _err(f"the predicate must be boolean, it evaluates to {col.type}")
+    return pc.fill_null(col, False).combine_chunks().to_numpy(zero_copy_only=False).astype(np.bool_)
