@@ -458,6 +458,74 @@ impl RowMask {
     pub fn rows(&self) -> u64 { unsafe { sys::pqv_row_mask_rows(self.raw) } }
     /// allowed rows (that belong to an inverted list)
     pub fn count(&self) -> u64 { unsafe { sys::pqv_row_mask_count(self.raw) } }
+
+    /// The mask of a predicate evaluated on the GPU over resident columns (`include/pqv.h`: `pqv_row_mask_from_predicates`).
+    /// Leaf `i` is `(columns[i], ops[i], operands[2 i], operands[2 i + 1])` -- `masks[i]` instead of a column for a
+    /// `PQV_OP_MASK` leaf -- and `program` the postfix bytes over the leaves.  Only the leaf table crosses PCIe.
+    pub fn from_predicates(searcher: &Searcher, columns: &[Option<&Column>], masks: &[Option<&RowMask>], ops: &[u32],
+                           operands: &[u64], program: &[u8]) -> Result<RowMask> {
+        let n = ops.len();
+        if columns.len() != n || masks.len() != n || operands.len() != 2 * n {
+            return Err("one column slot, one mask slot and two operands per leaf".into());
+        }
+        let mut cols: Vec<*const sys::PqvColumn> = columns.iter().map(|c| c.map_or(ptr::null(), |c| c.raw as *const _)).collect();
+        let mut ms: Vec<*const sys::PqvRowMask> = masks.iter().map(|m| m.map_or(ptr::null(), |m| m.raw as *const _)).collect();
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            sys::pqv_row_mask_from_predicates(searcher.raw, n as u32, cols.as_mut_ptr(), ms.as_mut_ptr(), ops.as_ptr(), operands.as_ptr(),
+                                              program.as_ptr(), program.len() as u32, ptr::null_mut(), &mut raw)
+        })?;
+        Ok(RowMask { raw })
+    }
+
+    /// One byte per corpus row: 1 where the row is allowed.
+    pub fn to_bytes(&self) -> Result<Vec<u8>> {
+        let mut out = vec![0u8; self.rows() as usize];
+        check(unsafe { sys::pqv_row_mask_to_bytes(self.raw, out.as_mut_ptr(), out.len() as u64) })?;
+        Ok(out)
+    }
+}
+
+/// A scalar column resident on one GPU beside the embedding column (`include/pqv.h`: `pqv_column`): what predicate leaves read.
+pub struct Column {
+    raw: *mut sys::PqvColumn,
+}
+unsafe impl Send for Column {}
+unsafe impl Sync for Column {}
+
+impl Column {
+    fn upload(device: i32, dtype: i32, values: *const c_void, valid: Option<&[u8]>, n: usize) -> Result<Column> {
+        if let Some(v) = valid {
+            if v.len() != n {
+                return Err("one validity byte per value".into());
+            }
+        }
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_column_upload(device, dtype, values, valid.map_or(ptr::null(), |v| v.as_ptr()), n as u64, &mut raw) })?;
+        Ok(Column { raw })
+    }
+    /// `valid[r] == 0` marks row `r` NULL.
+    pub fn from_i32(device: i32, values: &[i32], valid: Option<&[u8]>) -> Result<Column> {
+        Self::upload(device, sys::PQV_COL_I32, values.as_ptr() as *const _, valid, values.len())
+    }
+    pub fn from_i64(device: i32, values: &[i64], valid: Option<&[u8]>) -> Result<Column> {
+        Self::upload(device, sys::PQV_COL_I64, values.as_ptr() as *const _, valid, values.len())
+    }
+    pub fn from_f32(device: i32, values: &[f32], valid: Option<&[u8]>) -> Result<Column> {
+        Self::upload(device, sys::PQV_COL_F32, values.as_ptr() as *const _, valid, values.len())
+    }
+    pub fn from_f64(device: i32, values: &[f64], valid: Option<&[u8]>) -> Result<Column> {
+        Self::upload(device, sys::PQV_COL_F64, values.as_ptr() as *const _, valid, values.len())
+    }
+    pub fn rows(&self) -> u64 { unsafe { sys::pqv_column_rows(self.raw) } }
+    pub fn dtype(&self) -> i32 { unsafe { sys::pqv_column_dtype(self.raw) } }
+    pub fn device(&self) -> i32 { unsafe { sys::pqv_column_device(self.raw) } }
+}
+
+impl Drop for Column {
+    fn drop(&mut self) {
+        unsafe { sys::pqv_column_free(self.raw) }
+    }
 }
 
 impl Drop for RowMask {

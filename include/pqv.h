@@ -431,6 +431,68 @@ int pqv_range_search_masked(const pqv_searcher *searcher, const pqv_row_mask *ma
                             int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
                             uint64_t *n_within, uint64_t *n_candidates);
 
+/* Predicate masks: the WHERE clause evaluated on the GPU.  A pqv_column is one scalar column resident on one GPU beside the
+ * embedding column: one value per corpus row (PQV_COL_*), optionally validity bytes (u8 [n_rows], 0 = NULL).
+ * pqv_column_upload copies host arrays; pqv_column_from_device borrows device arrays, as pqv_corpus_from_device does (the caller
+ * keeps them alive and unchanged).  pqv_row_mask_from_predicates evaluates a predicate over such columns into an ordinary
+ * immutable pqv_row_mask, good for every masked entry point (plain and table searchers, every layout, every metric).  Nothing
+ * of size O(n_rows) crosses PCIe: the leaf table and the program go in, the 8-byte allowed total comes out.
+ *
+ * A predicate is n_leaves <= 32 leaves and a postfix program over them (program_len <= 63 bytes: 0..31 pushes leaf i,
+ * PQV_PRED_AND / PQV_PRED_OR replace the two top values; stack depth <= 32; exactly one value is left).  Leaf i is
+ * (columns[i], ops[i], operands[2 i], operands[2 i + 1]):
+ *   truth      true on a row iff  valid && (cmp(x) != negate),  negate = ops[i] & PQV_OP_NOT.  PQV_OP_IS_NULL is
+ *              (!valid) != negate; a column without validity bytes is never NULL.  PQV_OP_MASK is  bit != negate  of masks[i],
+ *              an existing row mask of THIS searcher (columns[i] is ignored and may be NULL).
+ *   operands   slot 0 (and slot 1 for PQV_OP_BETWEEN: lo <= x && x <= hi) holds the bits of an int64_t for I32 / I64 columns
+ *              and of a double for F32 / F64 columns.  Integer columns compare in i64 (never through floating point: 2^53
+ *              and 2^53 + 1 stay distinct); float columns compare in f64 (an f32 value is widened, which is exact) with IEEE
+ *              rules: NaN makes every op false except NE -- so a negated LT is true on NaN -- and -0.0 == 0.0.
+ *   combining  AND / OR are two-valued and there is no NOT operator: negation exists on leaves only (push NOT down with De
+ *              Morgan).  With `valid` gating every leaf this equals SQL's three-valued logic followed by "NULL counts as
+ *              false"; a negated membership test (an AND of negated EQ leaves) drops NULL rows, as SQL's NOT IN does.
+ *   columns    have pqv_corpus_rows rows and live on the searcher's device; row r is the row a call reports (a corpus row of a
+ *              table searcher).  Rows outside every file or list are evaluated -- pqv_row_mask_to_bytes shows them -- and
+ *              ignored by searches and pqv_row_mask_count, as for every mask.
+ *   completion work is enqueued on hip_stream (NULL: the searcher's) and complete on return; columns and MASK leaves are only
+ *              read during the call.
+ * pqv_predicate_check validates a program on the host (no device) and reports its deepest stack in *max_depth (may be NULL).
+ * pqv_row_mask_to_bytes writes allowed[r] = 1 where row r is allowed, else 0, for every corpus row, from any mask: it downloads
+ * the mask's row-order device bitset (n_rows / 8 bytes) and expands it, for a byte-made mask too.
+ * Errors (PQV_ERR_INVALID, before any device use where the arguments allow it): "predicate program is empty", "predicate
+ * program is malformed" (unknown byte, leaf index >= n_leaves, underflow, overflow, more than one value left), "predicate has N
+ * leaves, at most 32", "unknown column type", "unknown predicate op", "column has N rows, the corpus has M", "column is on device
+ * D, the searcher on device E", "predicate leaf I has no column", "row mask belongs to another searcher" (MASK leaves). */
+#define PQV_COL_I32 0
+#define PQV_COL_I64 1
+#define PQV_COL_F32 2
+#define PQV_COL_F64 3
+typedef struct pqv_column pqv_column;
+int      pqv_column_upload(int device, int dtype, const void *values, const uint8_t *valid, uint64_t n_rows, pqv_column **out);
+int      pqv_column_from_device(int device, int dtype, const void *d_values, const void *d_valid, uint64_t n_rows,
+                                pqv_column **out);
+uint64_t pqv_column_rows(const pqv_column *column);
+int      pqv_column_dtype(const pqv_column *column);
+int      pqv_column_device(const pqv_column *column);
+void     pqv_column_free(pqv_column *column);
+#define PQV_OP_EQ 0
+#define PQV_OP_NE 1
+#define PQV_OP_LT 2
+#define PQV_OP_LE 3
+#define PQV_OP_GT 4
+#define PQV_OP_GE 5
+#define PQV_OP_BETWEEN 6
+#define PQV_OP_IS_NULL 7
+#define PQV_OP_MASK 8
+#define PQV_OP_NOT 0x100
+#define PQV_PRED_AND 0x80
+#define PQV_PRED_OR  0x81
+int pqv_predicate_check(const uint8_t *program, uint32_t program_len, uint32_t n_leaves, uint32_t *max_depth);
+int pqv_row_mask_from_predicates(const pqv_searcher *searcher, uint32_t n_leaves, const pqv_column *const *columns,
+                                 const pqv_row_mask *const *masks, const uint32_t *ops, const uint64_t *operands,
+                                 const uint8_t *program, uint32_t program_len, void *hip_stream, pqv_row_mask **out);
+int pqv_row_mask_to_bytes(const pqv_row_mask *mask, uint8_t *allowed, uint64_t n_rows);
+
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`
  * baseline does row by row (benches/query.rs:76-98), for the metrics above.  Results are

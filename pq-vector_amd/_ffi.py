@@ -37,6 +37,13 @@ PQV_RELEASE_IF_COPIED = 0x4
 PQV_TABLE_CAP_ROUND_ROBIN = 0x8      # pqv_table_searcher_create: max_candidates dealt out round robin over the files
 PQV_PREPARE_COSINE = 0x10            # build the PQV_COSINE layout at creation (pqv.h: PQV_COSINE)
 
+# resident scalar columns and predicate leaves (pqv.h: pqv_column, pqv_row_mask_from_predicates)
+PQV_COL_I32, PQV_COL_I64, PQV_COL_F32, PQV_COL_F64 = 0, 1, 2, 3
+PQV_OP_EQ, PQV_OP_NE, PQV_OP_LT, PQV_OP_LE, PQV_OP_GT, PQV_OP_GE, PQV_OP_BETWEEN, PQV_OP_IS_NULL, PQV_OP_MASK = range(9)
+PQV_OP_NOT = 0x100
+PQV_PRED_AND = 0x80
+PQV_PRED_OR = 0x81
+
 
 class Counters(C.Structure):
     _fields_ = [("queries", C.c_uint64), ("candidate_rows", C.c_uint64),
@@ -125,6 +132,16 @@ SIGNATURES = {
     "pqv_row_mask_rows": (C.c_uint64, [vp]),
     "pqv_row_mask_count": (C.c_uint64, [vp]),
     "pqv_row_mask_free": (None, [vp]),
+    "pqv_row_mask_to_bytes": (C.c_int, [vp, u8p, C.c_uint64]),
+    "pqv_column_upload": (C.c_int, [C.c_int, C.c_int, vp, u8p, C.c_uint64, C.POINTER(vp)]),
+    "pqv_column_from_device": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_uint64, C.POINTER(vp)]),
+    "pqv_column_rows": (C.c_uint64, [vp]),
+    "pqv_column_dtype": (C.c_int, [vp]),
+    "pqv_column_device": (C.c_int, [vp]),
+    "pqv_column_free": (None, [vp]),
+    "pqv_predicate_check": (C.c_int, [u8p, C.c_uint32, C.c_uint32, u32p]),
+    "pqv_row_mask_from_predicates": (C.c_int, [vp, C.c_uint32, C.POINTER(vp), C.POINTER(vp), u32p, u64p, u8p, C.c_uint32, vp,
+                                               C.POINTER(vp)]),
     "pqv_topk_masked": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                   C.c_int, C.c_int, u32p, f32p, u32p, u64p]),
     "pqv_topk_masked_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,

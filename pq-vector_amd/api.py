@@ -8,7 +8,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, predicate
 from ._ffi import f32p, f64p, u8p, u32p, u64p, vp
 
 
@@ -400,6 +400,120 @@ class SearchResult:
     distance: float
 
 
+_COLUMN_DTYPES = {np.dtype(np.int32): _ffi.PQV_COL_I32, np.dtype(np.int64): _ffi.PQV_COL_I64,
+                  np.dtype(np.float32): _ffi.PQV_COL_F32, np.dtype(np.float64): _ffi.PQV_COL_F64}
+_RESIDENT_TYPES = "int8..int64, uint8..uint32, bool, date, timestamp, time64, float, double"
+
+
+def _arrow_scalar_target(typ):
+    """The resident type (a pyarrow type) of an Arrow column type, or None where the column cannot be resident."""
+    import pyarrow as pa
+    ty = pa.types
+    if ty.is_boolean(typ) or ty.is_int8(typ) or ty.is_int16(typ) or ty.is_int32(typ) or ty.is_uint8(typ) or ty.is_uint16(typ) \
+            or ty.is_date32(typ):
+        return pa.int32()
+    if ty.is_int64(typ) or ty.is_uint32(typ) or ty.is_date64(typ) or ty.is_timestamp(typ) or ty.is_time64(typ):
+        return pa.int64()
+    if ty.is_float32(typ):
+        return pa.float32()
+    if ty.is_float64(typ):
+        return pa.float64()
+    return None
+
+
+def scalar_arrays(values, valid=None, name=None):
+    """-> (values, valid or None, PQV_COL_*): contiguous numpy values of a resident type and validity bytes (0 = NULL) from a
+    numpy array (int32 / int64 / float32 / float64, plus an optional bool / uint8 `valid`) or a pyarrow Array / ChunkedArray, whose
+    nulls become validity bytes (int8 / int16 / uint8 / uint16 / bool / date32 -> int32; uint32 / date64 / timestamp / time64 ->
+    int64).  Anything else is refused."""
+    what = f"column {name!r}" if name else "the column"
+    if not isinstance(values, np.ndarray) and hasattr(values, "type") and hasattr(values, "null_count"):
+        import pyarrow as pa
+        import pyarrow.compute as pc
+        arr = values.combine_chunks() if isinstance(values, pa.ChunkedArray) else values
+        target = _arrow_scalar_target(arr.type)
+        if target is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} has type {arr.type}: not a resident scalar type ({_RESIDENT_TYPES}); "
+                                                 "filter on it on the host with a pyarrow expression (pyarrow.compute.field(...))")
+        if valid is not None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "valid= goes with numpy values; a pyarrow array carries its own nulls")
+        if arr.null_count:
+            valid = pc.is_valid(arr).to_numpy(zero_copy_only=False).astype(np.uint8)
+        if pa.types.is_boolean(arr.type):
+            arr = arr.cast(pa.int8())
+        elif pa.types.is_date64(arr.type) or pa.types.is_timestamp(arr.type) or pa.types.is_time64(arr.type):
+            arr = arr.cast(pa.int64())
+        elif pa.types.is_date32(arr.type):
+            arr = arr.cast(pa.int32())
+        arr = arr.cast(target)
+        if arr.null_count:
+            arr = pc.fill_null(arr, pa.scalar(0, type=target))
+        values = arr.to_numpy(zero_copy_only=False)
+    a = np.asarray(values)
+    if a.ndim != 1:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} must be one-dimensional, got {a.ndim} dimensions")
+    if a.dtype not in _COLUMN_DTYPES:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} has dtype {a.dtype}: a resident column is int32, int64, float32 or float64")
+    a = np.ascontiguousarray(a)
+    if valid is not None:
+        v = np.asarray(valid)
+        if v.dtype != np.bool_ and v.dtype != np.uint8:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"valid must be a bool or uint8 array, got {v.dtype}")
+        if v.shape != a.shape:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"valid has {v.size} entries for {a.size} values")
+        valid = np.ascontiguousarray(v).view(np.uint8) if v.dtype == np.bool_ else np.ascontiguousarray(v)
+    return a, valid, _COLUMN_DTYPES[a.dtype]
+
+
+class Column:
+    """A scalar column resident on one GPU (pqv.h: pqv_column): one value per corpus row, optional validity bytes (0 = NULL).
+    What predicates (pqv.col(name) >= 2 ...) read; attach it to a searcher with Searcher.attach_column(name, column)."""
+
+    def __init__(self, handle, keepalive=None):
+        self._h = handle
+        self._keepalive = keepalive
+
+    @classmethod
+    def upload(cls, values, valid=None, device=0):
+        a, v, dtype = scalar_arrays(values, valid)
+        h = vp()
+        _check(_ffi.lib().pqv_column_upload(device, dtype, vp(a.ctypes.data), v.ctypes.data_as(_ffi.u8p) if v is not None else None,
+                                            a.size, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_device_ptr(cls, dtype, ptr, n_rows, valid_ptr=0, device=0, keepalive=None):
+        """Borrow device arrays (dtype: PQV_COL_*; valid_ptr: optional u8 [n_rows]); keepalive keeps their owner alive."""
+        h = vp()
+        _check(_ffi.lib().pqv_column_from_device(device, int(dtype), vp(ptr or None), vp(valid_ptr or None), int(n_rows), C.byref(h)))
+        return cls(h, keepalive)
+
+    @property
+    def rows(self):
+        return int(_ffi.lib().pqv_column_rows(self._h)) if self._h else 0
+
+    @property
+    def dtype(self):
+        """PQV_COL_I32 / I64 / F32 / F64"""
+        return int(_ffi.lib().pqv_column_dtype(self._h)) if self._h else -1
+
+    @property
+    def device(self):
+        return int(_ffi.lib().pqv_column_device(self._h)) if self._h else -1
+
+    def close(self):
+        if self._h:
+            _ffi.lib().pqv_column_free(self._h)
+            self._h = None
+            self._keepalive = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class RowMask:
     """One allow bit per row of a searcher's corpus (pqv.h: pqv_row_mask): made by Searcher.row_mask / row_mask_from_rows /
     row_mask_device, passed as mask= to that searcher's topk / range_search / topk_device.  Immutable; close() releases it."""
@@ -416,6 +530,14 @@ class RowMask:
     def count(self):
         """allowed rows (that belong to an inverted list)"""
         return int(_ffi.lib().pqv_row_mask_count(self._h)) if self._h else 0
+
+    def to_bytes(self):
+        """uint8 [corpus rows]: 1 where the row is allowed -- every corpus row, whether or not it belongs to a list."""
+        if self._h is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "row mask must not be NULL")
+        out = np.zeros(self.rows, dtype=np.uint8)
+        _check(_ffi.lib().pqv_row_mask_to_bytes(self._h, out.ctypes.data_as(_ffi.u8p), out.size))
+        return out
 
     def close(self):
         if self._h:
@@ -459,6 +581,8 @@ class Searcher:
         _check(_ffi.lib().pqv_searcher_create(index._h, corpus._h, flags, C.byref(h)))
         self._h = h
         self._corpus = corpus
+        self._columns = {}           # name -> Column (attach_column)
+        self._owned_columns = []     # the attached columns that close() closes
         self.dim = index.dim
         self.n_clusters = index.n_clusters
 
@@ -482,8 +606,53 @@ class Searcher:
         finally:
             _ffi.lib().pqv_rows_free(rows)
 
+    @property
+    def columns(self):
+        """{name: Column}: the scalar columns attached to this searcher (what predicates' names resolve against)."""
+        return self._columns
+
+    def attach_column(self, name, column, own=False):
+        """Make a resident scalar column known to predicates as `name`: a Column, or a numpy / pyarrow array that is uploaded to
+        the searcher's device.  One value per corpus row.  Returns the Column.  close() closes the columns the searcher uploaded
+        itself and those attached with own=True; any other Column stays its caller's (it may serve several searchers)."""
+        if not isinstance(name, str) or not name:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "attach_column needs a column name")
+        if not isinstance(column, Column):
+            a, v, _ = scalar_arrays(column, name=name)
+            if a.size != self._corpus.rows:
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"column has {a.size} rows, the corpus has {self._corpus.rows}")
+            column = Column.upload(a, v, device=self._corpus.device)
+            own = True
+        elif column._h is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "column must not be NULL")
+        self._columns[name] = column
+        if own:
+            self._owned_columns.append(column)
+        return column
+
+    def row_mask_predicate(self, pred, stream=0):
+        """RowMask of a predicate over the attached columns (pqv.h: pqv_row_mask_from_predicates): evaluated on the device; the
+        only host traffic is the leaf table in and the allowed count out.  Complete on return."""
+        cols = self.columns
+        for name in pred.columns():
+            if name not in cols:
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"no column named {name!r} is attached to this searcher")
+        comp = predicate.compile(pred, {name: c.dtype for name, c in cols.items()})
+        n = len(comp.leaves)
+        col_h = (vp * n)(*[cols[x]._h if isinstance(x, str) else None for x in comp.leaves])
+        mask_h = (vp * n)(*[None if isinstance(x, str) else _mask_handle(self, x) for x in comp.leaves])
+        prog = np.frombuffer(comp.program, dtype=np.uint8)
+        h = vp()
+        _check(_ffi.lib().pqv_row_mask_from_predicates(self._h, n, col_h, mask_h, comp.ops.ctypes.data_as(u32p),
+                                                       comp.operands.ctypes.data_as(u64p), prog.ctypes.data_as(_ffi.u8p), prog.size,
+                                                       vp(stream or None), C.byref(h)))
+        return RowMask(h, self)
+
     def row_mask(self, allowed):
-        """RowMask from a bool / uint8 array [corpus rows] (nonzero = allowed)."""
+        """RowMask from a bool / uint8 array [corpus rows] (nonzero = allowed), or from a predicate over the attached columns
+        (pqv.col(name) >= 2 ...: row_mask_predicate)."""
+        if isinstance(allowed, predicate.Predicate):
+            return self.row_mask_predicate(allowed)
         a = _allow_array(allowed, self._corpus.rows)
         h = vp()
         _check(_ffi.lib().pqv_row_mask_create(self._h, a.ctypes.data_as(_ffi.u8p), a.size, C.byref(h)))
@@ -627,6 +796,10 @@ class Searcher:
         if self._h:
             _ffi.lib().pqv_searcher_free(self._h)
             self._h = None
+        for column in self._owned_columns:
+            column.close()
+        self._owned_columns = []
+        self._columns = {}
 
     def __del__(self):
         try:
@@ -694,6 +867,8 @@ def _where_arg(x, path, searcher):
         if path is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "where(expression) needs a Parquet path source: the expression is evaluated over the file's columns")
         return x
+    if isinstance(x, predicate.Predicate):       # (names resolve at search(): attached columns, or the file's, loaded once)
+        return x
     a = np.asarray(x)
     if a.dtype != np.bool_:
         raise PqvError(_ffi.PQV_ERR_INVALID, f"where() needs a bool array, a RowMask or a pyarrow expression, got {a.dtype if a.dtype != object else type(x).__name__}")
@@ -710,10 +885,48 @@ def _resolve_where(x, path, searcher):
     """-> (RowMask, owned): the mask of a checked where() argument on `searcher`; owned masks are closed after the search."""
     if isinstance(x, RowMask):
         return x, False
+    if isinstance(x, predicate.Predicate):
+        if path is not None:
+            _attach_file_columns(searcher, path, x.columns())
+        return searcher.row_mask_predicate(x), True
     if _is_expression(x):
         from . import parquet_io
         x = parquet_io.row_mask_from_expression(path, x)
     return searcher.row_mask(x), True
+
+
+def _attach_file_columns(searcher, path, names):
+    """The named columns of the searcher's file, resident: loaded on first use and kept with the (cached) searcher, so every later
+    predicate over them is device-only."""
+    from . import parquet_io
+    for name in names:
+        if name not in searcher.columns:
+            searcher.attach_column(name, parquet_io.load_scalar_column(path, name, searcher._corpus.device), own=True)
+
+
+def _attach_table_columns(searcher, paths, names):
+    """As _attach_file_columns for a table: ONE corpus-row-aligned column per name -- file f's values at its corpus rows, rows
+    outside the files NULL; the files must agree on the column's resident type."""
+    from . import parquet_io
+    for name in names:
+        if name in searcher.columns:
+            continue
+        values = valid = None
+        dtype0 = None
+        for f, (p, b, n) in enumerate(zip(paths, searcher.row_base.tolist(), searcher.n_rows.tolist())):
+            a, v, dtype = parquet_io.read_scalar_column(p, name)
+            if a.size != int(n):
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"column {name!r} of file {f} has {a.size} rows, its index has {int(n)}")
+            if values is None:
+                dtype0 = dtype
+                values = np.zeros(searcher._corpus.rows, dtype=a.dtype)
+                valid = np.zeros(searcher._corpus.rows, dtype=np.uint8)
+            elif dtype != dtype0:
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"column {name!r} is {a.dtype} in file {f} and {values.dtype} in file 0: "
+                                                     "a table's predicate columns must have one type")
+            values[int(b):int(b) + int(n)] = a
+            valid[int(b):int(b) + int(n)] = 1 if v is None else v
+        searcher.attach_column(name, Column.upload(values, valid, device=searcher._corpus.device), own=True)
 
 
 def _table_where_arg(x, paths):
@@ -724,6 +937,8 @@ def _table_where_arg(x, paths):
         raise PqvError(_ffi.PQV_ERR_INVALID, "where(RowMask) needs a Searcher source: a row mask belongs to one searcher")
     if _is_expression(x):
         return [x] * len(paths)
+    if isinstance(x, predicate.Predicate):       # (ONE predicate for the table: evaluated over corpus-row-aligned columns)
+        return x
     if isinstance(x, np.ndarray) or not isinstance(x, (list, tuple)):
         raise PqvError(_ffi.PQV_ERR_INVALID, "a table's where() needs one pyarrow expression, or a list with one bool array / expression per file")
     if len(x) != len(paths):
@@ -733,6 +948,9 @@ def _table_where_arg(x, paths):
 
 def _resolve_table_where(per_file, paths, searcher):
     from . import parquet_io
+    if isinstance(per_file, predicate.Predicate):
+        _attach_table_columns(searcher, paths, per_file.columns())
+        return searcher.row_mask_predicate(per_file)
     allowed = np.zeros(searcher._corpus.rows, dtype=np.uint8)
     for xf, p, b, n in zip(per_file, paths, searcher.row_base.tolist(), searcher.n_rows.tolist()):
         a = parquet_io.row_mask_from_expression(p, xf) if _is_expression(xf) else xf
@@ -765,8 +983,10 @@ class TopkBuilder:
 
     def where(self, x):
         """Restrict the search to rows (the reference's `WHERE <predicate>` inside the scan, exec.rs:207-277): a bool array over
-        the file's rows, a RowMask (Searcher sources), or a pyarrow.compute.Expression over the file's other columns, e.g.
-        pc.field("id") >= 2 (path sources; nulls count as False).  Fewer than k rows may come back."""
+        the file's rows, a RowMask (Searcher sources), a pyarrow.compute.Expression over the file's other columns, e.g.
+        pc.field("id") >= 2 (path sources; evaluated on the host; nulls count as False), or a predicate, e.g. pqv.col("id") >= 2,
+        evaluated on the GPU over resident columns: the searcher's attached columns, or with a path source the file's columns,
+        loaded once per resident file.  Fewer than k rows may come back."""
         self._where = _where_arg(x, self._path, self._searcher)
         return self
 
@@ -921,6 +1141,8 @@ class TableSearcher(Searcher):
         _check(_ffi.lib().pqv_table_searcher_create(arr, len(indexes), rb.ctypes.data_as(u64p), corpus._h, flags, C.byref(h)))
         self._h = h
         self._corpus = corpus
+        self._columns = {}
+        self._owned_columns = []
         self.dim = indexes[0].dim
         self.n_clusters = sum(ix.n_clusters for ix in indexes)
         self.n_files = len(indexes)
@@ -1061,7 +1283,8 @@ class TableTopkBuilder(TopkBuilder):
         return self
 
     def where(self, x):
-        """One pyarrow expression for all files, or a list with one bool array / expression per file (TopkBuilder.where)."""
+        """One pyarrow expression or one predicate (pqv.col(...), evaluated on the GPU) for all files, or a list with one bool array /
+        expression per file (TopkBuilder.where)."""
         self._where = _table_where_arg(x, self._paths)
         return self
 

@@ -111,7 +111,7 @@ int use_device(int device) {
     if (!lazy && device < 64)
         std::call_once(warmed[device], [] {
             (void)pqv::touch_probe(nullptr); (void)pqv::touch_screen(nullptr); (void)pqv::touch_brute(nullptr); (void)pqv::touch_build(nullptr);
-            (void)pqv::touch_layout(nullptr); (void)pqv::touch_list(nullptr); (void)pqv::touch_kpp(nullptr); (void)pqv::touch_range(nullptr); (void)pqv::touch_mask(nullptr);
+            (void)pqv::touch_layout(nullptr); (void)pqv::touch_list(nullptr); (void)pqv::touch_kpp(nullptr); (void)pqv::touch_range(nullptr); (void)pqv::touch_mask(nullptr); (void)pqv::touch_predicate(nullptr);
             (void)hipStreamSynchronize(nullptr);
             // ... and the runtime's staging buffers for copies from / to pageable host memory are made by the first such copies
             void *d = nullptr;
@@ -506,13 +506,46 @@ struct pqv_row_mask {
     int device = 0;
     uint64_t n_rows = 0, count = 0;
     DevBuf d_bits;                     // [ceil(n / 64) + 1] u64 image, then one u64: the allowed total
-    std::vector<uint8_t> host;         // [n_rows] allow bytes in row order
+    DevBuf d_rowbits;                  // [ceil(n_rows / 64)] u64 ROW IMAGE (kernels.h): what a MASK leaf and pqv_row_mask_to_bytes read
+    // [n_rows] allow bytes in row order for the host replays: a byte-made mask's are the caller's, copied at creation; a predicate
+    // mask's are made from the row image by the first replay that needs them (mask_host_bytes), under host_mu
+    mutable std::mutex host_mu;
+    mutable std::vector<uint8_t> host;
+    mutable std::atomic<bool> host_ready{false};
 };
 // what a masked call hands down (nullptr: the unmasked call)
 struct MaskView {
     const uint64_t *bits;              // device image
-    const uint8_t *host;               // row-order bytes
+    const pqv_row_mask *mask;          // (the row-order bytes are fetched at the replay site: mask_host_bytes)
 };
+// a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
+static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
+    const uint64_t n_words = (m->n_rows + 63) / 64;
+    std::vector<uint64_t> words;
+    try { words.resize(n_words); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+    HIP_TRY(hipSetDevice(m->device));
+    if (n_words) HIP_TRY(hipMemcpy(words.data(), m->d_rowbits.p, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint64_t r = 0; r < m->n_rows; ++r) dst[r] = static_cast<uint8_t>((words[r >> 6] >> (r & 63u)) & 1ull);
+    return PQV_OK;
+}
+// The row-order allow bytes of a masked call's mask (nullptr for an unmasked call).  A predicate mask downloads its row image
+// (n_rows / 8 bytes) once and expands it on the host; threads that arrive together wait for the first.  The row image was complete
+// when the mask's creation returned, so the copy orders behind nothing.
+static int mask_host_bytes(const MaskView *mv, const uint8_t **out) {
+    *out = nullptr;
+    if (!mv) return PQV_OK;
+    const pqv_row_mask *m = mv->mask;
+    if (!m->host_ready.load(std::memory_order_acquire)) {
+        std::lock_guard<std::mutex> lock(m->host_mu);
+        if (!m->host_ready.load(std::memory_order_relaxed)) {
+            try { m->host.resize(m->n_rows); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+            if (int rc = row_image_to_bytes(m, m->host.data())) return rc;
+            m->host_ready.store(true, std::memory_order_release);
+        }
+    }
+    *out = m->host.data();
+    return PQV_OK;
+}
 
 // ---------------------------------------------------------------------------------------
 // misc
@@ -4010,6 +4043,8 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
     using namespace pqv;
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
     std::vector<uint32_t> clusters;
+    const uint8_t *allow = nullptr;
+    if (int rc = mask_host_bytes(mask, &allow)) return rc;
     for (uint32_t q = 0; q < nq; ++q) {
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q) * s->dim, static_cast<size_t>(s->dim) * sizeof(float),
                                hipMemcpyHostToDevice, s->stream));
@@ -4026,7 +4061,7 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
         uint64_t considered = 0;
         if (int rc = replay_with_clusters(s, sc, d_q_s, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(),
                                           clusters, k, max_candidates, metric, sqrt_out, row_idx + static_cast<uint64_t>(q) * k,
-                                          dist + static_cast<uint64_t>(q) * k, &nf, nprobe, mask ? mask->host : nullptr, &considered))
+                                          dist + static_cast<uint64_t>(q) * k, &nf, nprobe, allow, &considered))
             return rc;
         if (n_found) n_found[q] = nf;
         if (n_candidates) n_candidates[q] = total;
@@ -4221,11 +4256,13 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
             if (n_candidates) n_candidates[q0 + i] = h_ncand[i];
             if (h_tie[i]) {
                 // tied output distances: survivors / order follow Rust's heap mechanics exactly
+                const uint8_t *allow = nullptr;
+                if (int rc = mask_host_bytes(mask, &allow)) return rc;
                 if (int rc = replay_query_exact(s, sc, s->sdim != s->dim ? sc.s_qpad.as<float>() + static_cast<size_t>(i) * s->sdim
                                                                           : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i, np,
                                                 k, max_candidates, metric, sqrt_out,
                                                 row_idx + static_cast<uint64_t>(q0 + i) * k,
-                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, mask ? mask->host : nullptr))
+                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, allow))
                     return rc;
                 s->counters.exact_replays++;
             }
@@ -4459,7 +4496,8 @@ extern "C" void pqv_range_free(uint64_t *lims, uint32_t *row_idx, float *dist) {
 
 // ---- row masks (pqv.h: pqv_row_mask) -----------------------------------------------------------------------------------
 // Creation: the allow bytes (host: through a temporary device copy; device: as given) -> mask_layout_kernel -> the position image
-// and the allowed total, and the row-order bytes kept on the host for the replays.  Complete on return.
+// and the allowed total, mask_pack_kernel -> the row image, and the row-order bytes kept on the host for the replays.  Complete
+// on return.
 static int row_mask_create_impl(const pqv_searcher *s, const uint8_t *h_allowed, const void *d_allowed, uint64_t n_rows, void *hip_stream,
                                 pqv_row_mask **out) {
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
@@ -4476,7 +4514,9 @@ static int row_mask_create_impl(const pqv_searcher *s, const uint8_t *h_allowed,
     m->host.resize(n_rows);
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
     const uint64_t n_words = (s->n + 63) / 64 + 1;
+    const uint64_t row_words = (n_rows + 63) / 64;
     HIP_TRY(m->d_bits.alloc((n_words + 1) * sizeof(uint64_t)));
+    HIP_TRY(m->d_rowbits.alloc(row_words * sizeof(uint64_t)));
     unsigned long long *d_count = m->d_bits.as<unsigned long long>() + n_words;
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
     DevBuf d_tmp;
@@ -4490,10 +4530,12 @@ static int row_mask_create_impl(const pqv_searcher *s, const uint8_t *h_allowed,
         HIP_TRY(hipMemcpyAsync(m->host.data(), d_allowed, n_rows, hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(pqv::launch_mask_layout(d_src, n_rows, s->d_ids.as<uint32_t>(), s->n, m->d_bits.as<uint64_t>(), n_words, d_count, stream));
+    HIP_TRY(pqv::launch_mask_pack(d_src, n_rows, m->d_rowbits.as<uint64_t>(), row_words, stream));
     unsigned long long h_count = 0;
     HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof h_count, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));       // (d_tmp is released at scope exit)
     m->count = h_count;
+    m->host_ready.store(true, std::memory_order_release);
     *out = m.release();
     return PQV_OK;
 }
@@ -4515,13 +4557,184 @@ extern "C" void pqv_row_mask_free(pqv_row_mask *m) {
     (void)hipSetDevice(m->device);
     delete m;
 }
+static int pqv_row_mask_to_bytes_impl(const pqv_row_mask *m, uint8_t *allowed, uint64_t n_rows) {
+    if (!m) return fail(PQV_ERR_INVALID, "row mask must not be NULL");
+    if (n_rows != m->n_rows)
+        return fail(PQV_ERR_INVALID, "row mask has " + std::to_string(m->n_rows) + " rows, the buffer has " + std::to_string(n_rows));
+    if (n_rows && !allowed) return fail(PQV_ERR_INVALID, "allowed must not be NULL");
+    return row_image_to_bytes(m, allowed);       // (the row image of every mask, byte-made ones included; never the cached bytes)
+}
+extern "C" int pqv_row_mask_to_bytes(const pqv_row_mask *m, uint8_t *allowed, uint64_t n_rows) {
+    return guard([&] { return pqv_row_mask_to_bytes_impl(m, allowed, n_rows); });
+}
+
+// ---- resident scalar columns and predicate masks (pqv.h: pqv_column, pqv_row_mask_from_predicates) ----------------------
+struct pqv_column {
+    int device = 0;
+    int dtype = 0;
+    uint64_t n = 0;
+    void *d_values = nullptr;          // [n] of dtype
+    uint8_t *d_valid = nullptr;        // optional [n] validity bytes (0 = NULL)
+    bool owned = true;
+    ~pqv_column() {
+        if (owned) {
+            if (d_values) (void)hipFree(d_values);
+            if (d_valid) (void)hipFree(d_valid);
+        }
+    }
+};
+static size_t column_value_size(int dtype) { return (dtype == PQV_COL_I32 || dtype == PQV_COL_F32) ? 4 : 8; }
+
+static int pqv_column_make(int device, int dtype, const void *values, const void *valid, uint64_t n_rows, bool upload, pqv_column **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (dtype != PQV_COL_I32 && dtype != PQV_COL_I64 && dtype != PQV_COL_F32 && dtype != PQV_COL_F64)
+        return fail(PQV_ERR_INVALID, "unknown column type");
+    if (n_rows > 0xFFFFFFFFull) return fail(PQV_ERR_UNSUPPORTED, "row ids are u32: at most 4294967295 rows per corpus");
+    if (n_rows && !values) return fail(PQV_ERR_INVALID, upload ? "values must not be NULL" : "d_values must not be NULL");
+    if (int rc = use_device(device)) return rc;
+    std::unique_ptr<pqv_column> c(new (std::nothrow) pqv_column());
+    if (!c) return fail(PQV_ERR_OOM, "host allocation failed");
+    c->device = device; c->dtype = dtype; c->n = n_rows;
+    if (!upload) {
+        c->owned = false;
+        c->d_values = const_cast<void *>(values);
+        c->d_valid = static_cast<uint8_t *>(const_cast<void *>(valid));
+    } else {
+        const size_t vb = static_cast<size_t>(n_rows) * column_value_size(dtype);
+        HIP_TRY(hipMalloc(&c->d_values, vb ? vb : 16));
+        if (vb) HIP_TRY(hipMemcpy(c->d_values, values, vb, hipMemcpyHostToDevice));
+        if (valid) {
+            void *dv = nullptr;
+            HIP_TRY(hipMalloc(&dv, n_rows ? n_rows : 16));
+            c->d_valid = static_cast<uint8_t *>(dv);
+            if (n_rows) HIP_TRY(hipMemcpy(c->d_valid, valid, n_rows, hipMemcpyHostToDevice));
+        }
+    }
+    *out = c.release();
+    return PQV_OK;
+}
+extern "C" int pqv_column_upload(int device, int dtype, const void *values, const uint8_t *valid, uint64_t n_rows, pqv_column **out) {
+    return guard([&] { return pqv_column_make(device, dtype, values, valid, n_rows, true, out); });
+}
+extern "C" int pqv_column_from_device(int device, int dtype, const void *d_values, const void *d_valid, uint64_t n_rows, pqv_column **out) {
+    return guard([&] { return pqv_column_make(device, dtype, d_values, d_valid, n_rows, false, out); });
+}
+extern "C" uint64_t pqv_column_rows(const pqv_column *c) { return c ? c->n : 0; }
+extern "C" int pqv_column_dtype(const pqv_column *c) { return c ? c->dtype : -1; }
+extern "C" int pqv_column_device(const pqv_column *c) { return c ? c->device : -1; }
+extern "C" void pqv_column_free(pqv_column *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    delete c;
+}
+
+// the postfix program of a predicate: 0..31 push leaf i, PQV_PRED_AND / PQV_PRED_OR fold the two top values
+static int predicate_check(const uint8_t *program, uint32_t program_len, uint32_t n_leaves, uint32_t *max_depth) {
+    if (max_depth) *max_depth = 0;
+    if (program_len == 0) return fail(PQV_ERR_INVALID, "predicate program is empty");
+    if (!program) return fail(PQV_ERR_INVALID, "program must not be NULL");
+    if (n_leaves > 32) return fail(PQV_ERR_INVALID, "predicate has " + std::to_string(n_leaves) + " leaves, at most 32");
+    uint32_t depth = 0, deepest = 0;
+    bool ok = program_len <= 63;
+    for (uint32_t i = 0; ok && i < program_len; ++i) {
+        const uint8_t c = program[i];
+        if (c == PQV_PRED_AND || c == PQV_PRED_OR) {
+            if (depth < 2) ok = false; else --depth;
+        } else if (c < 32 && c < n_leaves) {
+            if (++depth > 32) ok = false;
+            deepest = std::max(deepest, depth);
+        } else {
+            ok = false;
+        }
+    }
+    if (!ok || depth != 1) return fail(PQV_ERR_INVALID, "predicate program is malformed");
+    if (max_depth) *max_depth = deepest;
+    return PQV_OK;
+}
+extern "C" int pqv_predicate_check(const uint8_t *program, uint32_t program_len, uint32_t n_leaves, uint32_t *max_depth) {
+    return guard([&] { return predicate_check(program, program_len, n_leaves, max_depth); });
+}
+
+// (the kernels' leaf table takes ops and column types as the header numbers them)
+static_assert(pqv::PRED_COL_I32 == PQV_COL_I32 && pqv::PRED_COL_I64 == PQV_COL_I64 && pqv::PRED_COL_F32 == PQV_COL_F32 &&
+              pqv::PRED_COL_F64 == PQV_COL_F64, "kernels.h PRED_COL_* must equal pqv.h PQV_COL_*");
+static_assert(pqv::PRED_EQ == PQV_OP_EQ && pqv::PRED_NE == PQV_OP_NE && pqv::PRED_LT == PQV_OP_LT && pqv::PRED_LE == PQV_OP_LE &&
+              pqv::PRED_GT == PQV_OP_GT && pqv::PRED_GE == PQV_OP_GE && pqv::PRED_BETWEEN == PQV_OP_BETWEEN &&
+              pqv::PRED_IS_NULL == PQV_OP_IS_NULL && pqv::PRED_MASK == PQV_OP_MASK && pqv::PRED_NOT == PQV_OP_NOT,
+              "kernels.h PRED_* ops must equal pqv.h PQV_OP_*");
+static_assert(pqv::PRED_PROG_AND == PQV_PRED_AND && pqv::PRED_PROG_OR == PQV_PRED_OR, "kernels.h PRED_PROG_* must equal pqv.h PQV_PRED_*");
+static_assert(sizeof(pqv::PredArgs::program) == 64, "the program field holds 64 bytes");
+
+// predicate_rows_kernel -> the row image, mask_gather_kernel -> the position image and the allowed total.  Host traffic: the
+// kernel arguments in, the 8-byte total out; the row-order host bytes of the replays are made on first need (mask_host_bytes).
+static int row_mask_from_predicates_impl(const pqv_searcher *s, uint32_t n_leaves, const pqv_column *const *columns,
+                                         const pqv_row_mask *const *masks, const uint32_t *ops, const uint64_t *operands,
+                                         const uint8_t *program, uint32_t program_len, void *hip_stream, pqv_row_mask **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (int rc = predicate_check(program, program_len, n_leaves, nullptr)) return rc;
+    if (!ops) return fail(PQV_ERR_INVALID, "ops must not be NULL");
+    if (!operands) return fail(PQV_ERR_INVALID, "operands must not be NULL");
+    const uint64_t corpus_rows = s->corpus ? s->corpus->n : 0;
+    pqv::PredArgs pa{};
+    for (uint32_t i = 0; i < n_leaves; ++i) {
+        const uint32_t op = ops[i] & ~static_cast<uint32_t>(PQV_OP_NOT);
+        if (op > PQV_OP_MASK) return fail(PQV_ERR_INVALID, "unknown predicate op");
+        pqv::PredLeaf &L = pa.leaf[i];
+        L.op = ops[i]; L.a = operands[2 * i]; L.b = operands[2 * i + 1];
+        if (op == PQV_OP_MASK) {
+            const pqv_row_mask *lm = masks ? masks[i] : nullptr;
+            if (!lm) return fail(PQV_ERR_INVALID, "row mask must not be NULL");
+            if (lm->owner != s || lm->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+            L.values = lm->d_rowbits.p; L.valid = nullptr; L.dtype = 0;
+            continue;
+        }
+        const pqv_column *c = columns ? columns[i] : nullptr;
+        if (!c) return fail(PQV_ERR_INVALID, "predicate leaf " + std::to_string(i) + " has no column");
+        if (c->n != corpus_rows)
+            return fail(PQV_ERR_INVALID, "column has " + std::to_string(c->n) + " rows, the corpus has " + std::to_string(corpus_rows));
+        if (c->device != s->device)
+            return fail(PQV_ERR_INVALID, "column is on device " + std::to_string(c->device) + ", the searcher on device " + std::to_string(s->device));
+        L.values = c->d_values; L.valid = c->d_valid; L.dtype = static_cast<uint32_t>(c->dtype);
+    }
+    std::memcpy(pa.program, program, program_len);
+    pa.program_len = program_len; pa.n_leaves = n_leaves; pa.n_rows = corpus_rows;
+    if (int rc = use_device(s->device)) return rc;
+    std::unique_ptr<pqv_row_mask> m(new (std::nothrow) pqv_row_mask());
+    if (!m) return fail(PQV_ERR_OOM, "host allocation failed");
+    m->owner = s; m->owner_uid = s->uid; m->device = s->device; m->n_rows = corpus_rows;
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+    const uint64_t n_words = (s->n + 63) / 64 + 1;
+    const uint64_t row_words = (corpus_rows + 63) / 64;
+    HIP_TRY(m->d_bits.alloc((n_words + 1) * sizeof(uint64_t)));
+    HIP_TRY(m->d_rowbits.alloc(row_words * sizeof(uint64_t)));
+    pa.rowbits = m->d_rowbits.as<uint64_t>(); pa.n_words = row_words;
+    unsigned long long *d_count = m->d_bits.as<unsigned long long>() + n_words;
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
+    if (row_words) HIP_TRY(pqv::launch_predicate_rows(pa, stream));
+    HIP_TRY(pqv::launch_mask_gather(m->d_rowbits.as<uint64_t>(), corpus_rows, s->d_ids.as<uint32_t>(), s->n, m->d_bits.as<uint64_t>(), n_words,
+                                    d_count, stream));
+    unsigned long long h_count = 0;
+    HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof h_count, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    m->count = h_count;
+    *out = m.release();
+    return PQV_OK;
+}
+extern "C" int pqv_row_mask_from_predicates(const pqv_searcher *s, uint32_t n_leaves, const pqv_column *const *columns,
+                                            const pqv_row_mask *const *masks, const uint32_t *ops, const uint64_t *operands,
+                                            const uint8_t *program, uint32_t program_len, void *hip_stream, pqv_row_mask **out) {
+    return guard([&] { return row_mask_from_predicates_impl(s, n_leaves, columns, masks, ops, operands, program, program_len, hip_stream, out); });
+}
 
 // the checks every masked entry point makes before anything else (after the searcher's own NULL check)
 static int mask_view(const pqv_searcher *s, const pqv_row_mask *mask, MaskView &mv) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!mask) return fail(PQV_ERR_INVALID, "row mask must not be NULL");
     if (mask->owner != s || mask->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
-    mv.bits = mask->d_bits.as<uint64_t>(); mv.host = mask->host.data();
+    mv.bits = mask->d_bits.as<uint64_t>(); mv.mask = mask;
     return PQV_OK;
 }
 extern "C" int pqv_topk_masked(const pqv_searcher *s, const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len,

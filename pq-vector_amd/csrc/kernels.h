@@ -83,6 +83,36 @@ struct MaskedArgs {
 // arithmetic, keys and output formats; a.probe / a.list_off / a.cand_base are required.
 hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s);
 
+// ---- predicate masks (kernels_predicate.hip) -----------------------------------------------------------------------------
+// A mask's ROW IMAGE is the bitset in row order: bit r of word r / 64 = row r is allowed, ceil(n_rows / 64) words, bits of rows
+// >= n_rows zero.  predicate_rows_kernel writes it from resident columns and a postfix program (pqv.h:
+// pqv_row_mask_from_predicates; the values below are the header's PQV_COL_* / PQV_OP_* / PQV_PRED_*), mask_pack_kernel from allow
+// bytes; mask_gather_kernel turns it into the list-position image and the allowed total, as launch_mask_layout does from bytes.
+enum : uint32_t { PRED_COL_I32 = 0, PRED_COL_I64 = 1, PRED_COL_F32 = 2, PRED_COL_F64 = 3 };
+enum : uint32_t { PRED_EQ = 0, PRED_NE = 1, PRED_LT = 2, PRED_LE = 3, PRED_GT = 4, PRED_GE = 5, PRED_BETWEEN = 6, PRED_IS_NULL = 7,
+                  PRED_MASK = 8, PRED_NOT = 0x100, PRED_PROG_AND = 0x80, PRED_PROG_OR = 0x81 };
+struct PredLeaf {
+    const void    *values;   // the column's values [n_rows] of dtype; PRED_MASK: the row image of the leaf's mask
+    const uint8_t *valid;    // optional validity bytes [n_rows] (0 = NULL)
+    uint64_t       a, b;     // operand bits: int64_t (integer columns) / double (float columns)
+    uint32_t       op;       // PRED_* | PRED_NOT
+    uint32_t       dtype;    // PRED_COL_*
+};
+struct PredArgs {
+    PredLeaf  leaf[32];
+    uint32_t  program[16];   // 64 postfix bytes, byte i in bits 8 (i % 4) .. of word i / 4 (a memcpy of the byte program; words, so
+                             // that the kernel reads them as scalars): 0..31 push leaf i, PRED_PROG_AND, PRED_PROG_OR (host-checked)
+    uint32_t  program_len;
+    uint32_t  n_leaves;
+    uint64_t  n_rows;
+    uint64_t *rowbits;       // [n_words]
+    uint64_t  n_words;       // ceil(n_rows / 64)
+};
+hipError_t launch_predicate_rows(const PredArgs &a, hipStream_t s);
+hipError_t launch_mask_gather(const uint64_t *rowbits, uint64_t n_rows, const uint32_t *ids, uint64_t n_pos, uint64_t *bits,
+                              uint64_t n_words, unsigned long long *count, hipStream_t s);
+hipError_t launch_mask_pack(const uint8_t *allowed, uint64_t n_rows, uint64_t *rowbits, uint64_t n_words, hipStream_t s);
+
 // Batched centroid probe (probe_rows_kernel): every query against every centroid, exact reference order.
 struct ProbeRowsArgs {
     const float4   *cent_t;      // [dim/4][kc_pad] float4 transpose of the centroid table (launch_transpose_rows4)
@@ -747,5 +777,6 @@ hipError_t touch_list(hipStream_t s);
 hipError_t touch_kpp(hipStream_t s);
 hipError_t touch_range(hipStream_t s);
 hipError_t touch_mask(hipStream_t s);
+hipError_t touch_predicate(hipStream_t s);
 
 }  // namespace pqv

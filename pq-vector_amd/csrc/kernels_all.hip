@@ -1,5 +1,5 @@
 // kernels_all.hip -- every kernel translation unit in ONE (diagnostic builds only: `make phases`, `make stamps` -- the stamps
-// build keeps its device-side stamp table in one place).  The product build compiles the nine units separately.
+// build keeps its device-side stamp table in one place).  The product build compiles the units separately.
 #include "kernels_probe.hip"
 #include "kernels_screen.hip"
 #include "kernels_brute.hip"
@@ -9,3 +9,4 @@
 #include "kernels_kpp.hip"
 #include "kernels_range.hip"
 #include "kernels_mask.hip"
+#include "kernels_predicate.hip"

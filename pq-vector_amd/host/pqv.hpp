@@ -99,9 +99,46 @@ private:
     uint32_t dim_ = 0;
 };
 
+// A scalar column resident on one GPU beside the embedding column (pqv.h: pqv_column): what predicate leaves read.
+class Column {
+public:
+    // dtype: PQV_COL_*; values: one per corpus row; valid: empty, or one byte per row (0 = NULL)
+    Column(int device, int dtype, const void *values, const std::vector<uint8_t> &valid, uint64_t n_rows) {
+        if (!valid.empty() && valid.size() != n_rows) throw Error(PQV_ERR_INVALID, "one validity byte per value");
+        pqv_column *h = nullptr;
+        check(pqv_column_upload(device, dtype, values, valid.empty() ? nullptr : valid.data(), n_rows, &h));
+        h_.reset(h);
+    }
+    const pqv_column *get() const { return h_.get(); }
+    uint64_t rows() const { return pqv_column_rows(h_.get()); }
+    int dtype() const { return pqv_column_dtype(h_.get()); }
+private:
+    struct Del { void operator()(pqv_column *p) const { pqv_column_free(p); } };
+    std::unique_ptr<pqv_column, Del> h_;
+};
+
 // One allow bit per row of a searcher's corpus (pqv.h: pqv_row_mask); may outlive its searcher or be released before it.
 class RowMask {
 public:
+    // the mask of a predicate evaluated on the GPU (pqv.h: pqv_row_mask_from_predicates): leaf i is (columns[i], ops[i],
+    // operands[2 i], operands[2 i + 1]), masks[i] instead of a column for a PQV_OP_MASK leaf (masks may be empty without one)
+    static RowMask from_predicates(const Searcher &s, const std::vector<const pqv_column *> &columns,
+                                   const std::vector<const pqv_row_mask *> &masks, const std::vector<uint32_t> &ops,
+                                   const std::vector<uint64_t> &operands, const std::vector<uint8_t> &program) {
+        if (columns.size() != ops.size() || operands.size() != 2 * ops.size() || (!masks.empty() && masks.size() != ops.size()))
+            throw Error(PQV_ERR_INVALID, "one column slot and two operands per leaf");
+        pqv_row_mask *h = nullptr;
+        check(pqv_row_mask_from_predicates(s.get(), static_cast<uint32_t>(ops.size()), columns.data(), masks.empty() ? nullptr : masks.data(),
+                                           ops.data(), operands.data(), program.data(), static_cast<uint32_t>(program.size()), nullptr, &h));
+        RowMask m;
+        m.h_.reset(h);
+        return m;
+    }
+    std::vector<uint8_t> to_bytes() const {
+        std::vector<uint8_t> out(rows());
+        check(pqv_row_mask_to_bytes(h_.get(), out.data(), out.size()));
+        return out;
+    }
     RowMask(const Searcher &s, const std::vector<uint8_t> &allowed) {
         pqv_row_mask *h = nullptr;
         check(pqv_row_mask_create(s.get(), allowed.data(), allowed.size(), &h));
@@ -111,6 +148,7 @@ public:
     uint64_t rows() const { return pqv_row_mask_rows(h_.get()); }
     uint64_t count() const { return pqv_row_mask_count(h_.get()); }
 private:
+    RowMask() = default;
     struct Del { void operator()(pqv_row_mask *p) const { pqv_row_mask_free(p); } };
     std::unique_ptr<pqv_row_mask, Del> h_;
 };

@@ -24,7 +24,7 @@ import struct
 import numpy as np
 
 from . import _ffi
-from .api import Corpus, Index, PqvError
+from .api import Column, Corpus, Index, PqvError, scalar_arrays
 
 MAGIC = b"PQ_VECTOR1"                                   # src/ivf/parquet.rs:106
 OFFSET_KEY = "pq_vector_index_offset"                   # :109
@@ -886,3 +886,24 @@ def row_mask_from_expression(path, expr):
     if not pa.types.is_boolean(col.type):
         raise _err(f"the predicate must be boolean, it evaluates to {col.type}")
     return pc.fill_null(col, False).combine_chunks().to_numpy(zero_copy_only=False).astype(np.bool_)
+
+
+def read_scalar_column(path, name, row_groups=None):
+    """One scalar column of a Parquet file as host arrays in FILE ROW ORDER -> (values, valid or None, PQV_COL_*), with the type
+    map of api.scalar_arrays.  A column that cannot be resident (strings, uint64, decimals, nested, ...) is refused with an error
+    that names it, its type and the host route (pyarrow expressions)."""
+    import pyarrow.parquet as pq
+    pf = pq.ParquetFile(path)
+    if name not in pf.schema_arrow.names:
+        raise _err(f"{path} has no column named {name!r}")
+    if row_groups is None:
+        table = pf.read(columns=[name])
+    else:
+        table = pf.read_row_groups(list(row_groups), columns=[name])
+    return scalar_arrays(table.column(name), name=name)
+
+
+def load_scalar_column(path, name, device=0, row_groups=None):
+    """One scalar column of a Parquet file resident on `device` (api.Column): what a predicate (pqv.col(name) ...) reads."""
+    values, valid, _ = read_scalar_column(path, name, row_groups)
+    return Column.upload(values, valid, device=device)
