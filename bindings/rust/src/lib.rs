@@ -432,6 +432,35 @@ impl<'c> Searcher<'c> {
         Ok(out)
     }
 
+    /// The keys of an integer column laid out for this searcher (`include/pqv.h`: `pqv_row_keys`); the column is copied.
+    pub fn row_keys(&self, column: &Column) -> Result<RowKeys> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_row_keys_create(self.raw, column.raw, ptr::null_mut(), &mut raw) })?;
+        Ok(RowKeys { raw })
+    }
+
+    /// [`Searcher::topk_masked`] with one filter PER QUERY: query `q` considers the rows whose key equals `query_keys[q]` -- and
+    /// that `mask` allows, where one is given (`include/pqv.h`: `pqv_topk_keyed`).
+    pub fn topk_keyed(&self, keys: &RowKeys, query_keys: &[i64], mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,
+                      nprobe: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        if query_keys.len() != nq {
+            return Err("one query key per query".into());
+        }
+        let (k, np) = (k.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_keyed(self.raw, keys.raw, query_keys.as_ptr(), mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(),
+                                nq as u32, dim as u32, k as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(),
+                                dist.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
     /// Plan metrics (`src/df_vector/index_exec.rs:289-299`, `exec.rs:411-427`).
     pub fn counters(&self) -> Result<sys::PqvCounters> {
         let mut c = sys::PqvCounters::default();
@@ -531,6 +560,26 @@ impl Drop for Column {
 impl Drop for RowMask {
     fn drop(&mut self) {
         unsafe { sys::pqv_row_mask_free(self.raw) }
+    }
+}
+
+/// A key column laid out for one searcher ([`Searcher::row_keys`]): what [`Searcher::topk_keyed`] compares each query's key
+/// against.  Immutable, usable from any thread, and safe to drop before or after its searcher.
+pub struct RowKeys {
+    raw: *mut sys::PqvRowKeys,
+}
+unsafe impl Send for RowKeys {}
+unsafe impl Sync for RowKeys {}
+
+impl RowKeys {
+    pub fn rows(&self) -> u64 { unsafe { sys::pqv_row_keys_rows(self.raw) } }
+    /// `PQV_COL_I32` or `PQV_COL_I64`
+    pub fn dtype(&self) -> i32 { unsafe { sys::pqv_row_keys_dtype(self.raw) } }
+}
+
+impl Drop for RowKeys {
+    fn drop(&mut self) {
+        unsafe { sys::pqv_row_keys_free(self.raw) }
     }
 }
 

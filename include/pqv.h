@@ -493,6 +493,54 @@ int pqv_row_mask_from_predicates(const pqv_searcher *searcher, uint32_t n_leaves
                                  const uint8_t *program, uint32_t program_len, void *hip_stream, pqv_row_mask **out);
 int pqv_row_mask_to_bytes(const pqv_row_mask *mask, uint8_t *allowed, uint64_t n_rows);
 
+/* Per-query key filters: one batched search in which every query has its own `key_column = ?` -- a tenant, a user, a
+ * collection -- where a row mask is ONE filter for the whole batch.
+ *
+ * A pqv_row_keys is a resident INTEGER column (PQV_COL_I32 or PQV_COL_I64, one value per corpus row, optional validity bytes)
+ * laid out for ONE searcher, plain or table: key_pos[p] = column[row that list position p reports] at the column's own width,
+ * beside a validity bitset in a mask's format where the column has validity bytes.  pqv_row_keys_create copies what it needs
+ * (the column may be freed or changed afterwards), runs on hip_stream (NULL: the searcher's) and is complete on return; the
+ * result is immutable, serves every layout, every metric and every keyed entry point, may be used by any thread, and may be
+ * freed before or after its searcher.  Nothing of size O(n_rows) crosses PCIe, except once for the first call that replays a
+ * query on the host (tied distances, k > 1024, more than 1024 probed lists).
+ *
+ * A keyed call is its masked twin with `keys`, `qkeys` (int64_t [nq], one key per query; the device form reads a device array
+ * on hip_stream, inside the enqueued work) and `mask` (an optional shared row mask, NULL: none) inserted behind `searcher`.  With
+ *     M_q[r] = valid[r] && (int64_t) column[r] == qkeys[q] && (mask ? mask[r] : 1)
+ * query q of a keyed call returns, bit for bit, what the masked twin returns for that one query under the mask M_q:
+ *   candidates   the unmasked sequence, cut by max_candidates / a table's round-robin quotas BEFORE the filter; the considered
+ *                rows are the rows of M_q among the capped candidates, at their UNMASKED positions; order, tie rules (host heap
+ *                replay, device tie flags), sqrt_out, max_results and the PQV_COSINE halving are the masked call's.
+ *   counts       n_candidates and candidate_rows stay the counts before cap and filter; embeddings_fetched advances by the
+ *                considered rows, summed over the batch; n_found may be below k, or 0 (rows 0xFFFFFFFF, distance +inf); n_within
+ *                counts the hits in M_q.
+ *   comparison   in i64: an I32 column's values are widened, so a query key outside the i32 range matches nothing on an I32
+ *                column (it is never truncated).  A NULL row never matches.  Two queries may carry the same key; a key no row
+ *                has gives n_found == 0 or an empty range.
+ *   path         always the exact streaming pass, as for masks: no searcher option changes a keyed result, and rows the filter
+ *                excludes are never read.  k > 1024 or more than 1024 probed lists: pqv_topk_keyed goes through the host heap like
+ *                pqv_topk_masked; the device form reports PQV_ERR_UNSUPPORTED like pqv_topk_masked_device.
+ * Errors (PQV_ERR_INVALID; NULL handles are checked before any device use): "searcher must not be NULL", "out must not be NULL",
+ * "column must not be NULL", "key column must be PQV_COL_I32 or PQV_COL_I64", "column has N rows, the corpus has M", "column is
+ * on device D, the searcher on device E", "row keys must not be NULL", "query keys must not be NULL", "row keys belong to
+ * another searcher", and the masked calls' own ("row mask belongs to another searcher"). */
+typedef struct pqv_row_keys pqv_row_keys;
+int      pqv_row_keys_create(const pqv_searcher *searcher, const pqv_column *column, void *hip_stream, pqv_row_keys **out);
+uint64_t pqv_row_keys_rows(const pqv_row_keys *keys);
+int      pqv_row_keys_dtype(const pqv_row_keys *keys);
+void     pqv_row_keys_free(pqv_row_keys *keys);
+int pqv_topk_keyed(const pqv_searcher *searcher, const pqv_row_keys *keys, const int64_t *qkeys, const pqv_row_mask *mask,
+                   const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates,
+                   int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_keyed_device(const pqv_searcher *searcher, const pqv_row_keys *keys, const void *d_qkeys, const pqv_row_mask *mask,
+                          const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric,
+                          int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates, void *d_tie_flags,
+                          void *hip_stream);
+int pqv_range_search_keyed(const pqv_searcher *searcher, const pqv_row_keys *keys, const int64_t *qkeys,
+                           const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len, float radius,
+                           uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
+                           uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates);
+
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`
  * baseline does row by row (benches/query.rs:76-98), for the metrics above.  Results are

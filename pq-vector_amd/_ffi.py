@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("PQV_LIB_PATH") or os.path.join(_HERE, "libpqv_hip.so"
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
+i64p = C.POINTER(C.c_int64)
 f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)
 vp = C.c_void_p
@@ -148,6 +149,16 @@ SIGNATURES = {
                                          vp, vp, vp, vp, vp, vp]),
     "pqv_range_search_masked": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64,
                                           C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
+    "pqv_row_keys_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
+    "pqv_row_keys_rows": (C.c_uint64, [vp]),
+    "pqv_row_keys_dtype": (C.c_int, [vp]),
+    "pqv_row_keys_free": (None, [vp]),
+    "pqv_topk_keyed": (C.c_int, [vp, vp, i64p, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                 C.c_int, C.c_int, u32p, f32p, u32p, u64p]),
+    "pqv_topk_keyed_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                        vp, vp, vp, vp, vp, vp]),
+    "pqv_range_search_keyed": (C.c_int, [vp, vp, i64p, vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64,
+                                         C.c_uint64, C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_brute_topk": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, u32p]),
     "pqv_rerank": (C.c_int, [C.c_int, f32p, f32p, u32p, u8p, C.c_uint64, C.c_uint32, C.c_uint32,
                              C.c_int, u32p, f32p, u32p]),

@@ -551,6 +551,59 @@ class RowMask:
             pass
 
 
+class RowKeys:
+    """A key column laid out for one searcher (pqv.h: pqv_row_keys): made by Searcher.row_keys, passed as keys= with one
+    query_keys entry per query to that searcher's topk / range_search / topk_device -- every query is filtered by ITS OWN
+    `column == key`.  Immutable; close() releases it."""
+
+    def __init__(self, handle, searcher):
+        self._h = handle
+        self._searcher = searcher
+
+    @property
+    def rows(self):
+        return int(_ffi.lib().pqv_row_keys_rows(self._h)) if self._h else 0
+
+    @property
+    def dtype(self):
+        """PQV_COL_I32 or PQV_COL_I64"""
+        return int(_ffi.lib().pqv_row_keys_dtype(self._h)) if self._h else -1
+
+    def close(self):
+        if self._h:
+            _ffi.lib().pqv_row_keys_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _keys_handle(keys, query_keys):
+    if not isinstance(keys, RowKeys):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"keys must be a RowKeys, got {type(keys).__name__}")
+    if keys._h is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "row keys must not be NULL")
+    if query_keys is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "query keys must not be NULL")
+    return keys._h
+
+
+def _query_keys(query_keys, nq):
+    """A host call's query keys -> contiguous int64 [nq]; integers only, each within i64."""
+    a = np.asarray(query_keys)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"query keys must be integers, got {a.dtype}")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > 0x7FFFFFFFFFFFFFFF:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "query keys must fit int64")
+    a = np.ascontiguousarray(a.reshape(-1), dtype=np.int64)
+    if a.size != nq:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{a.size} query keys for {nq} queries")
+    return a
+
+
 def _allow_array(allowed, n_rows, what="row mask"):
     """A caller's allow array -> contiguous uint8 [n_rows]: bool or uint8, one entry per row; anything else is refused."""
     if allowed is None:
@@ -677,9 +730,25 @@ class Searcher:
         _check(_ffi.lib().pqv_row_mask_from_device(self._h, vp(ptr or None), int(n_rows), vp(stream or None), C.byref(h)))
         return RowMask(h, self)
 
-    def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None):
+    def row_keys(self, column, stream=0):
+        """RowKeys of an integer column (a Column, or the name of an attached one): pqv.h: pqv_row_keys_create.  The column is
+        copied, so it may be closed afterwards.  Complete on return."""
+        if isinstance(column, str):
+            if column not in self._columns:
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"no column named {column!r} is attached to this searcher")
+            column = self._columns[column]
+        if not isinstance(column, Column) or column._h is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "column must not be NULL")
+        h = vp()
+        _check(_ffi.lib().pqv_row_keys_create(self._h, column._h, vp(stream or None), C.byref(h)))
+        return RowKeys(h, self)
+
+    def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None, keys=None,
+             query_keys=None):
         """Batched topk(); returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq], n_candidates [nq]).
-        mask (a RowMask of this searcher): only allowed rows are considered (pqv.h: pqv_topk_masked)."""
+        mask (a RowMask of this searcher): only allowed rows are considered (pqv.h: pqv_topk_masked).
+        keys (a RowKeys of this searcher) with query_keys (int [nq]): query q considers only the rows whose key equals
+        query_keys[q], within mask if one is given too (pqv.h: pqv_topk_keyed)."""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -688,6 +757,14 @@ class Searcher:
         dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
+        if keys is not None or query_keys is not None:
+            kh = _keys_handle(keys, query_keys)
+            qk = _query_keys(query_keys, nq)
+            _check(_ffi.lib().pqv_topk_keyed(self._h, kh, qk.ctypes.data_as(_ffi.i64p), _mask_handle(self, mask) if mask is not None else None,
+                                             q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                             rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
+                                             nc.ctypes.data_as(u64p)))
+            return rows, dist, nf, nc
         if mask is not None:
             _check(_ffi.lib().pqv_topk_masked(self._h, _mask_handle(self, mask), q.ctypes.data_as(f32p), nq, qlen, k, nprobe,
                                               max_candidates, metric, 1 if sqrt_out else 0, rows.ctypes.data_as(u32p),
@@ -700,8 +777,9 @@ class Searcher:
         return rows, dist, nf, nc
 
     def range_search(self, queries, radius, nprobe, max_candidates=0, max_results=0, metric=_ffi.PQV_L2SQ_REF4,
-                     sqrt_out=True, mask=None):
+                     sqrt_out=True, mask=None, keys=None, query_keys=None):
         """Every candidate within `radius` of each query (pqv.h: pqv_range_search), ascending by (d2, candidate position).
+        mask / keys + query_keys: as topk (pqv.h: pqv_range_search_masked, pqv_range_search_keyed).
         Returns (lims u64 [nq+1], rows u32, dist f32, n_within u64 [nq], n_candidates u64 [nq]): query q's hits are
         rows / dist [lims[q]:lims[q+1]]; n_within is the hit count before max_results."""
         q = _f32(queries)
@@ -718,7 +796,15 @@ class Searcher:
         nw = np.zeros(nq, dtype=np.uint64)
         nc = np.zeros(nq, dtype=np.uint64)
         lims_p, rows_p, dist_p = u64p(), u32p(), f32p()
-        if mask is not None:       # (pqv.h: pqv_range_search_masked)
+        if keys is not None or query_keys is not None:       # (pqv.h: pqv_range_search_keyed)
+            kh = _keys_handle(keys, query_keys)
+            qk = _query_keys(query_keys, nq)
+            _check(_ffi.lib().pqv_range_search_keyed(self._h, kh, qk.ctypes.data_as(_ffi.i64p),
+                                                     _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
+                                                     qlen, radius, nprobe, max_candidates, max_results, metric, 1 if sqrt_out else 0,
+                                                     C.byref(lims_p), C.byref(rows_p), C.byref(dist_p), nw.ctypes.data_as(u64p),
+                                                     nc.ctypes.data_as(u64p)))
+        elif mask is not None:       # (pqv.h: pqv_range_search_masked)
             _check(_ffi.lib().pqv_range_search_masked(self._h, _mask_handle(self, mask), q.ctypes.data_as(f32p), nq, qlen, radius, nprobe,
                                                       max_candidates, max_results, metric, 1 if sqrt_out else 0, C.byref(lims_p),
                                                       C.byref(rows_p), C.byref(dist_p), nw.ctypes.data_as(u64p), nc.ctypes.data_as(u64p)))
@@ -736,13 +822,23 @@ class Searcher:
         return lims, rows, dist, nw, nc
 
     def topk_device(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0,
-                    max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0, mask=None):
+                    max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0, mask=None, keys=None,
+                    query_keys=None):
         """Device-pointer form (ints from tensor.data_ptr()); asynchronous on `stream` -- a hipStream_t handle; 0 means the
         searcher's OWN non-blocking stream, not HIP's / torch's default stream (whose handle is 0 too): work that must follow
         the call on the default stream is NOT ordered behind it, so pass an explicit stream (1 = hipStreamLegacy names the default
         stream itself).  d_tie_flags (u32 [nq]):
         also flag the queries whose answer depends on the reference's heap history (re-submit those to topk()).
-        mask (a RowMask of this searcher, alive until the enqueued work has completed): pqv.h: pqv_topk_masked_device."""
+        mask (a RowMask of this searcher, alive until the enqueued work has completed): pqv.h: pqv_topk_masked_device.
+        keys (a RowKeys of this searcher) with query_keys (the device pointer of int64 [nq], read on `stream` inside the enqueued
+        work): pqv.h: pqv_topk_keyed_device; combinable with mask."""
+        if keys is not None or query_keys is not None:
+            kh = _keys_handle(keys, query_keys)
+            _check(_ffi.lib().pqv_topk_keyed_device(self._h, kh, vp(query_keys or None), _mask_handle(self, mask) if mask is not None else None,
+                                                    vp(d_queries), nq, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                    vp(d_row_idx), vp(d_dist), vp(d_n_found or None), vp(d_n_candidates or None),
+                                                    vp(d_tie_flags or None), vp(stream or None)))
+            return
         if mask is not None:
             _check(_ffi.lib().pqv_topk_masked_device(self._h, _mask_handle(self, mask), vp(d_queries), nq, k, nprobe, max_candidates,
                                                      metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),

@@ -318,7 +318,8 @@ struct Scratch {
         s_seed_ub, s_qblk, s_gthr, s_tie, s_replay, s_qnorm, s_qmax, s_thr_hist, s_thr_bins, s_qi8, s_qn2i, s_qres, s_qresu, s_pair_lb, s_part_flags, s_qpad, s_cand_lb, s_pendv, s_work, s_nwork, s_out,
         s_hit_cnt, s_hit_keys, s_hit_vals, s_alt_keys, s_alt_vals, s_rsegs, s_rout_off, s_rout_rows, s_rout_dist,   // s_hit_* .. s_rout_*: pqv_range_search
         s_pair_end, s_file_cnt,     // round-robin capped tables: per-pair candidate ends, per-file counts (SegProbeArgs)
-        s_qcos;                     // PQV_COSINE: the call's normalised queries n(q), read by the cosine searcher's kernels
+        s_qcos,                     // PQV_COSINE: the call's normalised queries n(q), read by the cosine searcher's kernels
+        s_qkeys;                    // keyed host calls (pqv_row_keys): the sub-batch's query keys, i64 [b]
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -332,7 +333,7 @@ struct Scratch {
                 &s_dist, &s_nfound, &s_pair_u32, &s_pairs, &s_groups, &s_quads, &s_items, &s_ticket, &s_ticket2, &s_cand_keys, &s_cand_vals, &s_cand_cnt, &s_spilled,
                 &s_seed_ub, &s_qblk, &s_gthr, &s_tie, &s_replay, &s_qnorm, &s_qmax, &s_thr_hist, &s_thr_bins, &s_qi8, &s_qn2i, &s_qres, &s_qresu, &s_pair_lb, &s_part_flags, &s_qpad, &s_cand_lb, &s_pendv, &s_work, &s_nwork, &s_out,
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
-                &s_pair_end, &s_file_cnt, &s_qcos};
+                &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -513,10 +514,33 @@ struct pqv_row_mask {
     mutable std::vector<uint8_t> host;
     mutable std::atomic<bool> host_ready{false};
 };
-// what a masked call hands down (nullptr: the unmasked call)
+// A key column laid out for one searcher (pqv.h: pqv_row_keys): the column's values in LIST POSITION order at their own width,
+// padded by a whole 64-position window, and -- where the column has validity bytes -- a position bitset in a mask's format
+// (kernels.h: launch_key_layout).  Indexed through d_ids like a mask's image, so one image serves every layout, the cosine
+// searcher and table searchers.  Immutable; owner / owner_uid are compared, never read through.
+struct pqv_row_keys {
+    const pqv_searcher *owner = nullptr;
+    uint64_t owner_uid = 0;
+    int device = 0;
+    int dtype = 0;                     // PQV_COL_I32 / PQV_COL_I64
+    uint64_t n_rows = 0, n_pos = 0;
+    bool has_valid = false;
+    DevBuf d_key_pos;                  // [n_words * 64] i32 / i64, n_words = ceil(n_pos / 64) + 1
+    DevBuf d_valid_pos;                // [n_words] u64 (has_valid)
+    // the keys in ROW order for the host replays: made from the position image by the first replay that needs them
+    // (keys_host_rows), under host_mu
+    mutable std::mutex host_mu;
+    mutable std::vector<int64_t> host_vals;      // [n_rows], widened
+    mutable std::vector<uint8_t> host_valid;     // [n_rows] (has_valid)
+    mutable std::atomic<bool> host_ready{false};
+};
+// what a masked or keyed call hands down (nullptr: the unfiltered call)
 struct MaskView {
-    const uint64_t *bits;              // device image
+    const uint64_t *bits;              // device image of the call's row mask (a keyed call: of its shared mask, or nullptr)
     const pqv_row_mask *mask;          // (the row-order bytes are fetched at the replay site: mask_host_bytes)
+    const pqv_row_keys *keys;          // a keyed call's key column, else nullptr
+    const int64_t *h_qkeys;            // host forms: [nq] query keys, indexed like the call's queries
+    const int64_t *d_qkeys;            // device: the keys of the queries the kernels see (the current sub-batch's)
 };
 // a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
 static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
@@ -533,7 +557,7 @@ static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
 // when the mask's creation returned, so the copy orders behind nothing.
 static int mask_host_bytes(const MaskView *mv, const uint8_t **out) {
     *out = nullptr;
-    if (!mv) return PQV_OK;
+    if (!mv || !mv->mask) return PQV_OK;
     const pqv_row_mask *m = mv->mask;
     if (!m->host_ready.load(std::memory_order_acquire)) {
         std::lock_guard<std::mutex> lock(m->host_mu);
@@ -545,6 +569,76 @@ static int mask_host_bytes(const MaskView *mv, const uint8_t **out) {
     }
     *out = m->host.data();
     return PQV_OK;
+}
+// The row-order keys of a keyed call: the position image downloaded once (4 or 8 bytes per list position, n / 8 of validity) and
+// scattered back through the searcher's host lists; threads that arrive together wait for the first.  The image was complete
+// when pqv_row_keys_create returned.  `s`: the call's searcher (the keys' owner, or its cosine searcher -- the same lists).
+static int keys_host_rows(const pqv_searcher *s, const pqv_row_keys *kk) {
+    if (kk->host_ready.load(std::memory_order_acquire)) return PQV_OK;
+    std::lock_guard<std::mutex> lock(kk->host_mu);
+    if (kk->host_ready.load(std::memory_order_relaxed)) return PQV_OK;
+    const std::vector<uint32_t> *h_rows = s->h_rows->get();
+    if (!h_rows) return PQV_ERR_HIP;
+    const uint64_t n_pos = std::min<uint64_t>(kk->n_pos, h_rows->size());
+    const size_t es = kk->dtype == PQV_COL_I32 ? 4 : 8;
+    std::vector<uint8_t> pos_vals;
+    std::vector<uint64_t> pos_valid;
+    try {
+        pos_vals.resize(n_pos * es);
+        if (kk->has_valid) pos_valid.resize((n_pos + 63) / 64);
+        kk->host_vals.assign(kk->n_rows, 0);
+        if (kk->has_valid) kk->host_valid.assign(kk->n_rows, 0);
+    } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+    HIP_TRY(hipSetDevice(kk->device));
+    if (n_pos) HIP_TRY(hipMemcpy(pos_vals.data(), kk->d_key_pos.p, n_pos * es, hipMemcpyDeviceToHost));
+    if (!pos_valid.empty()) HIP_TRY(hipMemcpy(pos_valid.data(), kk->d_valid_pos.p, pos_valid.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint64_t p = 0; p < n_pos; ++p) {
+        const uint32_t r = (*h_rows)[p];
+        if (r >= kk->n_rows) continue;
+        if (es == 4) { int32_t v; std::memcpy(&v, pos_vals.data() + p * 4, 4); kk->host_vals[r] = v; }
+        else std::memcpy(&kk->host_vals[r], pos_vals.data() + p * 8, 8);
+        if (kk->has_valid) kk->host_valid[r] = static_cast<uint8_t>((pos_valid[p >> 6] >> (p & 63u)) & 1ull);
+    }
+    kk->host_ready.store(true, std::memory_order_release);
+    return PQV_OK;
+}
+// The allow test of a host replay: the mask's row-order bytes and / or a keyed call's M_q (pqv.h) for the query at index `q` of
+// the call's batch.  Unset (an unfiltered call): every row passes.
+struct RowFilter {
+    const uint8_t *allow = nullptr;
+    const int64_t *key_vals = nullptr;
+    const uint8_t *key_valid = nullptr;
+    int64_t qkey = 0;
+    bool active() const { return allow || key_vals; }
+    bool pass(uint32_t row) const {
+        if (allow && !allow[row]) return false;
+        if (key_vals && ((key_valid && !key_valid[row]) || key_vals[row] != qkey)) return false;
+        return true;
+    }
+};
+static int row_filter(const pqv_searcher *s, const MaskView *mv, uint64_t q, RowFilter &f) {
+    f = RowFilter{};
+    if (!mv) return PQV_OK;
+    if (int rc = mask_host_bytes(mv, &f.allow)) return rc;
+    if (mv->keys) {
+        if (int rc = keys_host_rows(s, mv->keys)) return rc;
+        f.key_vals = mv->keys->host_vals.data();
+        f.key_valid = mv->keys->has_valid ? mv->keys->host_valid.data() : nullptr;
+        f.qkey = mv->h_qkeys[q];
+    }
+    return PQV_OK;
+}
+// the STREAM_TOPK / STREAM_RANGE pass of a masked or keyed call
+static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskView *mv, unsigned long long *stats, const uint64_t *n_cand,
+                                         pqv::StreamMode mode, hipStream_t stream) {
+    if (mv->keys) {
+        const pqv_row_keys *kk = mv->keys;
+        const pqv::KeyedArgs ka{mv->bits, stats, n_cand, kk->d_key_pos.p, kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr,
+                                mv->d_qkeys, kk->dtype == PQV_COL_I32 ? 4u : 8u};
+        return pqv::launch_keyed_stream(ra, ka, mode, stream);
+    }
+    const pqv::MaskedArgs ma{mv->bits, stats, n_cand};
+    return pqv::launch_masked_stream(ra, ma, mode, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3781,8 +3875,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     if (!p.tile) {
         if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
         if (mask) {
-            const MaskedArgs ma{mask->bits, s->d_stats.as<unsigned long long>(), pm.n_cand};
-            HIP_TRY(launch_masked_stream(ra, ma, STREAM_TOPK, stream));
+            HIP_TRY(launch_filtered_stream(ra, mask, s->d_stats.as<unsigned long long>(), pm.n_cand, STREAM_TOPK, stream));
         } else {
             HIP_TRY(launch_stream(ra, STREAM_TOPK, stream));
         }
@@ -3886,12 +3979,12 @@ inline void heap_pop(std::vector<HeapEnt> &h) {
 // through the heap in candidate order.  d_probe / d_cand_base: the query's probe list on the device; `clusters` the
 // same list on the host.  Any k (the selection is the heap's), any nprobe (the grid is cut into slices of probed lists).
 // A round-robin capped table (table_rr) replays each list up to its file's quota (table_pair_ends; `nprobe` is read there only).
-// allow (a masked call: row-order allow bytes): a capped candidate whose row is not allowed is skipped in arrival order -- it never
+// allow (a masked or keyed call: its RowFilter): a capped candidate whose row does not pass is skipped in arrival order -- it never
 // meets the heap; *considered = the rows that did.
 int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_query, const uint32_t *d_probe,
                          const uint64_t *d_cand_base, const std::vector<uint32_t> &clusters, uint32_t k,
                          uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                         uint32_t *n_found, uint32_t nprobe = 0, const uint8_t *allow = nullptr, uint64_t *considered = nullptr) {
+                         uint32_t *n_found, uint32_t nprobe = 0, const RowFilter *allow = nullptr, uint64_t *considered = nullptr) {
     using namespace pqv;
     const uint32_t np = static_cast<uint32_t>(clusters.size());
     uint64_t total = 0;
@@ -3928,7 +4021,7 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
         base += e - b;
         for (uint64_t i = b; i < e && pos < lim; ++i, ++pos) {
             const HeapEnt ent{d[pos], (*h_rows)[i]};
-            if (allow && !allow[ent.row]) continue;
+            if (allow && !allow->pass(ent.row)) continue;
             ++n_considered;
             if (heap.size() < k) heap_push(heap, ent);                   // search.rs:119-120
             else if (ent.d < heap[0].d) { heap_pop(heap); heap_push(heap, ent); }   // :121-125
@@ -3949,7 +4042,7 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
 // qi indexes the current sub-batch's probe scratch (written by the probe merge).
 int replay_query_exact(const pqv_searcher *s, Scratch &sc, const float *d_query, uint32_t qi, uint32_t np, uint32_t k,
                        uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                       uint32_t *n_found, uint32_t nprobe, const uint8_t *allow = nullptr) {
+                       uint32_t *n_found, uint32_t nprobe, const RowFilter *allow = nullptr) {
     std::vector<uint32_t> clusters(np);
     HIP_TRY(hipMemcpyAsync(clusters.data(), sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * np,
                            np * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
@@ -4043,9 +4136,9 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
     using namespace pqv;
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
     std::vector<uint32_t> clusters;
-    const uint8_t *allow = nullptr;
-    if (int rc = mask_host_bytes(mask, &allow)) return rc;
+    RowFilter allow;
     for (uint32_t q = 0; q < nq; ++q) {
+        if (int rc = row_filter(s, mask, q, allow)) return rc;
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q) * s->dim, static_cast<size_t>(s->dim) * sizeof(float),
                                hipMemcpyHostToDevice, s->stream));
         uint64_t total = 0;
@@ -4061,7 +4154,7 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
         uint64_t considered = 0;
         if (int rc = replay_with_clusters(s, sc, d_q_s, sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(),
                                           clusters, k, max_candidates, metric, sqrt_out, row_idx + static_cast<uint64_t>(q) * k,
-                                          dist + static_cast<uint64_t>(q) * k, &nf, nprobe, allow, &considered))
+                                          dist + static_cast<uint64_t>(q) * k, &nf, nprobe, allow.active() ? &allow : nullptr, &considered))
             return rc;
         if (n_found) n_found[q] = nf;
         if (n_candidates) n_candidates[q] = total;
@@ -4191,6 +4284,11 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     std::vector<uint64_t> h_ncand(batch);
     std::vector<uint32_t> h_tie(batch), h_nf(batch);
     const uint32_t np = probe_count(s, nprobe);
+    // a keyed call: the kernels of a sub-batch read its own slice of the query keys (the same q0 as its queries)
+    MaskView sub{};
+    if (mask) sub = *mask;
+    const MaskView *bmask = mask ? &sub : nullptr;
+    if (mask && mask->keys) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     // A call of a few queries (TopkBuilder::search is ONE) is six small pageable copies otherwise -- the query in, rows, distances,
     // counts and tie flags out, each staged and waited for by the runtime: 60-80 us around 180 us of kernels.  Small calls go
     // through ONE pinned buffer instead: the results are laid out as one device block {candidates u64 | rows | dist | found |
@@ -4212,6 +4310,10 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         // (round 5: the result block of a small call is WRITTEN by the kernels straight into the pinned buffer -- host memory the
         //  device can address -- so there is no device-to-host copy behind them, only the synchronise: PQV_SMALL_IO_DIRECT=0 keeps the copy)
         static const bool direct_out = [] { const char *e = std::getenv("PQV_SMALL_IO_DIRECT"); return !(e && *e == '0'); }();
+        if (mask && mask->keys) {
+            HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, mask->h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+            sub.d_qkeys = sc.s_qkeys.as<int64_t>();
+        }
         if (small_io) {
             char *ob = direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p);           // (laid out for THIS sub-batch's b)
             o_rows = reinterpret_cast<uint32_t *>(ob + 8ull * b);
@@ -4227,7 +4329,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         if (int rc = enqueue_topk(s, sc.s_queries.as<float>(), b, k_int, k, nprobe, max_candidates, metric,
                                   sqrt_out, o_rows, o_dist, o_nf,
                                   small_io ? reinterpret_cast<uint64_t *>(direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p)) : nullptr,
-                                  o_tie, s->stream, sc, mask))
+                                  o_tie, s->stream, sc, bmask))
             return rc;
         if (small_io) {
             char *hb = static_cast<char *>(sc.h_io.p) + out_off;
@@ -4256,13 +4358,13 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
             if (n_candidates) n_candidates[q0 + i] = h_ncand[i];
             if (h_tie[i]) {
                 // tied output distances: survivors / order follow Rust's heap mechanics exactly
-                const uint8_t *allow = nullptr;
-                if (int rc = mask_host_bytes(mask, &allow)) return rc;
+                RowFilter allow;
+                if (int rc = row_filter(s, mask, static_cast<uint64_t>(q0) + i, allow)) return rc;
                 if (int rc = replay_query_exact(s, sc, s->sdim != s->dim ? sc.s_qpad.as<float>() + static_cast<size_t>(i) * s->sdim
                                                                           : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i, np,
                                                 k, max_candidates, metric, sqrt_out,
                                                 row_idx + static_cast<uint64_t>(q0 + i) * k,
-                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, allow))
+                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, allow.active() ? &allow : nullptr))
                     return rc;
                 s->counters.exact_replays++;
             }
@@ -4330,6 +4432,9 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
     HIP_TRY(sc.s_hit_keys.ensure(static_cast<size_t>(batch) * stride * sizeof(uint64_t)));
     HIP_TRY(sc.s_hit_vals.ensure(static_cast<size_t>(batch) * stride * sizeof(uint32_t)));
     HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
+    MaskView sub{};      // (a keyed call: each sub-batch's kernels read its own slice of the query keys)
+    if (mask) sub = *mask;
+    if (mask && mask->keys) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     std::vector<uint32_t> h_cnt(batch), h_probe;
     std::vector<uint64_t> h_ncand(batch), h_off(batch);
     std::vector<RangeSeg> segs;
@@ -4342,6 +4447,10 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         if (int rc = timing_events(s, e)) return rc;
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
                                hipMemcpyHostToDevice, st));
+        if (mask && mask->keys) {
+            HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, mask->h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            sub.d_qkeys = sc.s_qkeys.as<int64_t>();
+        }
         if (e[0]) HIP_TRY(hipEventRecord(e[0], st));
         const float *d_q = sc.s_queries.as<float>(), *d_q_s = d_q;
         if (s->sdim != s->dim) {
@@ -4381,8 +4490,8 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         for (uint32_t j0 = 0; j0 < np; j0 += 32768) {                    // gridDim.y <= 65535
             ra.j0 = j0; ra.nj = std::min<uint32_t>(32768, np - j0);
             if (mask) {      // (the considered rows are counted by the kernel; candidate_rows too unless the host probe counted it above)
-                const MaskedArgs ma{mask->bits, s->d_stats.as<unsigned long long>(), wide_probe ? nullptr : sc.s_ncand.as<uint64_t>()};
-                HIP_TRY(launch_masked_stream(ra, ma, STREAM_RANGE, st));
+                HIP_TRY(launch_filtered_stream(ra, &sub, s->d_stats.as<unsigned long long>(), wide_probe ? nullptr : sc.s_ncand.as<uint64_t>(),
+                                               STREAM_RANGE, st));
             } else
             HIP_TRY(launch_stream(ra, STREAM_RANGE, st));
             ++launches;
@@ -4734,6 +4843,7 @@ static int mask_view(const pqv_searcher *s, const pqv_row_mask *mask, MaskView &
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!mask) return fail(PQV_ERR_INVALID, "row mask must not be NULL");
     if (mask->owner != s || mask->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+    mv = MaskView{};
     mv.bits = mask->d_bits.as<uint64_t>(); mv.mask = mask;
     return PQV_OK;
 }
@@ -4763,6 +4873,94 @@ extern "C" int pqv_range_search_masked(const pqv_searcher *s, const pqv_row_mask
     return guard([&] {
         MaskView mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
+        return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
+                                     row_idx, dist, n_within, n_candidates, &mv);
+    });
+}
+
+// ---- per-query key filters (pqv.h: pqv_row_keys) ------------------------------------------------------------------------
+// Creation: ONE key_layout_kernel pass, a gather of the column through d_ids into the position image.  Complete on return.
+static int row_keys_create_impl(const pqv_searcher *s, const pqv_column *c, void *hip_stream, pqv_row_keys **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!c) return fail(PQV_ERR_INVALID, "column must not be NULL");
+    if (c->dtype != PQV_COL_I32 && c->dtype != PQV_COL_I64) return fail(PQV_ERR_INVALID, "key column must be PQV_COL_I32 or PQV_COL_I64");
+    const uint64_t corpus_rows = s->corpus ? s->corpus->n : 0;
+    if (c->n != corpus_rows)
+        return fail(PQV_ERR_INVALID, "column has " + std::to_string(c->n) + " rows, the corpus has " + std::to_string(corpus_rows));
+    if (c->device != s->device)
+        return fail(PQV_ERR_INVALID, "column is on device " + std::to_string(c->device) + ", the searcher on device " + std::to_string(s->device));
+    if (int rc = use_device(s->device)) return rc;
+    std::unique_ptr<pqv_row_keys> kk(new (std::nothrow) pqv_row_keys());
+    if (!kk) return fail(PQV_ERR_OOM, "host allocation failed");
+    kk->owner = s; kk->owner_uid = s->uid; kk->device = s->device; kk->dtype = c->dtype;
+    kk->n_rows = corpus_rows; kk->n_pos = s->n; kk->has_valid = c->d_valid != nullptr;
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+    const uint32_t es = static_cast<uint32_t>(column_value_size(c->dtype));
+    const uint64_t n_words = (s->n + 63) / 64 + 1;
+    HIP_TRY(kk->d_key_pos.alloc(n_words * 64 * es));
+    if (kk->has_valid) HIP_TRY(kk->d_valid_pos.alloc(n_words * sizeof(uint64_t)));
+    HIP_TRY(pqv::launch_key_layout(c->d_values, c->d_valid, es, corpus_rows, s->d_ids.as<uint32_t>(), s->n, kk->d_key_pos.p,
+                                   kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr, n_words, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *out = kk.release();
+    return PQV_OK;
+}
+extern "C" int pqv_row_keys_create(const pqv_searcher *s, const pqv_column *column, void *hip_stream, pqv_row_keys **out) {
+    return guard([&] { return row_keys_create_impl(s, column, hip_stream, out); });
+}
+extern "C" uint64_t pqv_row_keys_rows(const pqv_row_keys *k) { return k ? k->n_rows : 0; }
+extern "C" int pqv_row_keys_dtype(const pqv_row_keys *k) { return k ? k->dtype : -1; }
+extern "C" void pqv_row_keys_free(pqv_row_keys *k) {
+    if (!k) return;
+    (void)hipSetDevice(k->device);
+    delete k;
+}
+
+// the checks every keyed entry point makes before anything else: NULL handles first, nothing dereferenced before them
+static int keyed_view(const pqv_searcher *s, const pqv_row_keys *keys, const void *qkeys, uint32_t nq, const pqv_row_mask *mask, MaskView &mv) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
+    if (nq && !qkeys) return fail(PQV_ERR_INVALID, "query keys must not be NULL");
+    if (keys->owner != s || keys->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
+    mv = MaskView{};
+    if (mask) {
+        if (int rc = mask_view(s, mask, mv)) return rc;
+    }
+    mv.keys = keys;
+    return PQV_OK;
+}
+extern "C" int pqv_topk_keyed(const pqv_searcher *s, const pqv_row_keys *keys, const int64_t *qkeys, const pqv_row_mask *mask,
+                              const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates,
+                              int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = keyed_view(s, keys, qkeys, nq, mask, mv)) return rc;
+        mv.h_qkeys = qkeys;
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
+    });
+}
+extern "C" int pqv_topk_keyed_device(const pqv_searcher *s, const pqv_row_keys *keys, const void *d_qkeys, const pqv_row_mask *mask,
+                                     const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric,
+                                     int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
+                                     void *d_tie_flags, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = keyed_view(s, keys, d_qkeys, nq, mask, mv)) return rc;
+        mv.d_qkeys = static_cast<const int64_t *>(d_qkeys);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, d_tie_flags, hip_stream, &mv);
+    });
+}
+extern "C" int pqv_range_search_keyed(const pqv_searcher *s, const pqv_row_keys *keys, const int64_t *qkeys, const pqv_row_mask *mask,
+                                      const float *queries, uint32_t nq, uint32_t query_len, float radius, uint32_t nprobe,
+                                      uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t **lims,
+                                      uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = keyed_view(s, keys, qkeys, nq, mask, mv)) return rc;
+        mv.h_qkeys = qkeys;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
     });

@@ -83,6 +83,25 @@ struct MaskedArgs {
 // arithmetic, keys and output formats; a.probe / a.list_off / a.cand_base are required.
 hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s);
 
+// ---- per-query key filters (kernels_mask.hip; pqv.h: pqv_row_keys) ------------------------------------------------------
+// A key column on the device is laid out by LIST POSITION like a mask: key_pos[p] = column[ids[p]] at the column's own width
+// (elem_size 4 or 8), and -- where the column has validity bytes -- valid_pos, a bitset in exactly the mask image's format.
+// launch_key_layout writes all n_words * 64 entries of key_pos (zero behind n_pos: a whole 64-position window behind the last
+// position is readable) and, with `valid`, all n_words words of valid_pos; n_words >= ceil(n_pos / 64) + 1.
+hipError_t launch_key_layout(const void *values, const uint8_t *valid, uint32_t elem_size, uint64_t n_rows, const uint32_t *ids,
+                             uint64_t n_pos, void *key_pos, uint64_t *valid_pos, uint64_t n_words, hipStream_t s);
+struct KeyedArgs {
+    const uint64_t     *bits;       // optional: a shared row mask's image (MaskedArgs::bits), ANDed into every window
+    unsigned long long *stats;      // as MaskedArgs::stats
+    const uint64_t     *n_cand;     // as MaskedArgs::n_cand
+    const void         *key_pos;    // i32 / i64 [n_words * 64]
+    const uint64_t     *valid_pos;  // optional [n_words]
+    const int64_t      *qkeys;      // [nq]: query q's key; an i32 column's values are widened for the comparison
+    uint32_t            elem_size;  // 4 or 8
+};
+// launch_masked_stream with a window's bits taken from key_pos[p] == qkeys[q] (masked_stream_kernel, WIN = 1 / 2)
+hipError_t launch_keyed_stream(const StreamArgs &a, const KeyedArgs &ka, StreamMode mode, hipStream_t s);
+
 // ---- predicate masks (kernels_predicate.hip) -----------------------------------------------------------------------------
 // A mask's ROW IMAGE is the bitset in row order: bit r of word r / 64 = row r is allowed, ceil(n_rows / 64) words, bits of rows
 // >= n_rows zero.  predicate_rows_kernel writes it from resident columns and a postfix program (pqv.h:

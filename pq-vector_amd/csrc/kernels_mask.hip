@@ -1,6 +1,7 @@
 // kernels_mask.hip -- gfx950 kernels of the row-masked searches (pqv.h: pqv_row_mask): mask_layout_kernel (allow bytes in row
 // order -> a bitset indexed by LIST POSITION) and masked_stream_kernel (stream_kernel's exact distance pass over the allowed
-// positions only).  The screened paths take their thresholds from sampled rows; a threshold from a row the mask excludes is no
+// positions only) -- and of the per-query key filters (pqv.h: pqv_row_keys): key_layout_kernel (a key column in row order -> list
+// position order) and masked_stream_kernel's keyed instantiations, whose windows come from comparing keys.  The screened paths take their thresholds from sampled rows; a threshold from a row the mask excludes is no
 // bound on the masked answer, so masked calls always run this exact pass.
 #include "device_common.hpp"
 
@@ -39,6 +40,49 @@ hipError_t launch_mask_layout(const uint8_t *allowed, uint64_t n_rows, const uin
 }
 
 // ------------------------------------------------------------------------------------
+// key_layout_kernel: key_pos[p] = values[ids[p]] for list position p (T: the column's width as an unsigned word -- the values are
+// copied, never interpreted), zero for positions >= n_pos; one thread per entry of the padded image, so the stores of a wave are
+// one coalesced 256- / 512-byte line.  With validity bytes: bit p of valid_pos = valid[ids[p]] != 0, a wave's __ballot word
+// stored by lane 0, exactly as mask_layout_kernel writes a mask's image.
+// ------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(256) void key_layout_kernel(const T *values, const uint8_t *valid, uint64_t n_rows, const uint32_t *ids,
+                                                         uint64_t n_pos, T *key_pos, uint64_t *valid_pos, uint64_t n_words) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    T v = 0;
+    bool on = false;
+    if (p < n_pos) {
+        const uint64_t r = ids ? ids[p] : p;
+        if (r < n_rows) {
+            v = values[r];
+            on = !valid || valid[r] != 0;
+        }
+    }
+    if (p < n_words * 64) key_pos[p] = v;
+    if (valid_pos) {
+        const uint64_t m = __ballot(on);
+        const uint64_t w = p >> 6;
+        if ((threadIdx.x & 63) == 0 && w < n_words) valid_pos[w] = m;
+    }
+}
+
+hipError_t launch_key_layout(const void *values, const uint8_t *valid, uint32_t elem_size, uint64_t n_rows, const uint32_t *ids,
+                             uint64_t n_pos, void *key_pos, uint64_t *valid_pos, uint64_t n_words, hipStream_t s) {
+    if (elem_size != 4 && elem_size != 8) return hipErrorInvalidValue;
+    const uint64_t blocks = (n_words * 64 + 255) / 256;
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    uint64_t *vp = valid ? valid_pos : nullptr;
+    if (elem_size == 4)
+        hipLaunchKernelGGL(key_layout_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint32_t *>(values),
+                           valid, n_rows, ids, n_pos, static_cast<uint32_t *>(key_pos), vp, n_words);
+    else
+        hipLaunchKernelGGL(key_layout_kernel<uint64_t>, dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint64_t *>(values),
+                           valid, n_rows, ids, n_pos, static_cast<uint64_t *>(key_pos), vp, n_words);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // masked_stream_kernel
 //
 // stream_kernel's grid (row block, probe rank, query), its 4 independent waves per block and its chain arithmetic, element for
@@ -54,11 +98,27 @@ hipError_t launch_mask_layout(const uint8_t *allowed, uint64_t n_rows, const uin
 // beside the tile, so an instantiation's occupancy is its stream_kernel twin's (CG = 32: 32 KiB per block; a queue of its own
 // would take the fifth block per CU away).
 //
+// WIN, the source of a window's 64 bits: 0 the mask's image as above; 1 / 2 a key column (i32 / i64) in list-position order -- lane
+// l loads key_pos[lbeg + w0 + l] (one coalesced 256- / 512-byte read per window), compares it as an i64 against the query's key
+// (wave-uniform, loaded once) and the __ballot of the comparison is the window, ANDed with the funnel-shifted words of valid_pos
+// and of a shared mask where the call has them, and clipped like a mask's.  Everything behind the window is shared.
+//
 // Outputs: stream_kernel's (per-wave partial lists / hit segments).  Each wave adds the rows it evaluated to the
 // embeddings_fetched word of the query's statistics slot; the (0, 0) block of a query adds n_cand[q] to candidate_rows.
 // ------------------------------------------------------------------------------------
-template <int CG, int S, int MODE, bool SEQ, bool ALIGNED>
-__global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, const MaskedArgs ma) {
+template <int WIN> struct WinArgs { using type = KeyedArgs; };
+template <> struct WinArgs<0> { using type = MaskedArgs; };
+
+// the 64 bits of a position image from position p on (the image has one word of padding behind the last position: wi + 1 is always in range)
+__device__ __forceinline__ uint64_t image_window(const uint64_t *bits, uint64_t p) {
+    const uint64_t wi = p >> 6;
+    const uint32_t sh = (uint32_t)(p & 63u);
+    const uint64_t lo = bits[wi], hi = bits[wi + 1];
+    return sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
+}
+
+template <int CG, int S, int MODE, bool SEQ, bool ALIGNED, int WIN = 0>
+__global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, const typename WinArgs<WIN>::type ma) {
     constexpr int RPI = 64 / CG;        // rows per load instruction
     constexpr int NI = CG;              // load instructions per 64-row tile
     constexpr int EPL = SEQ ? 4 : 1;    // LDS values per lane item
@@ -95,6 +155,9 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
 #endif
     if (ma.n_cand && st && blockIdx.x == 0 && j == 0 && threadIdx.x == 0) atomicAdd(&st[2], (unsigned long long)ma.n_cand[q]);
 
+    int64_t qkey = 0;
+    if constexpr (WIN != 0) qkey = ma.qkeys[q];
+
     const uint32_t dim = a.dim;
     const uint32_t G = dim >> 2;
     const uint32_t tail = dim & 3u;
@@ -114,11 +177,18 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
         uint32_t my_r = 0;                  // list offset of tile row `lane`
         if (!flush) {
             const uint64_t p = lbeg + w0;
-            const uint64_t wi = p >> 6;
-            const uint32_t sh = (uint32_t)(p & 63u);
-            // (the image has one word of padding behind the last position: wi + 1 is always in range)
-            const uint64_t lo = ma.bits[wi], hi = ma.bits[wi + 1];
-            uint64_t win = sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
+            uint64_t win;
+            if constexpr (WIN == 0) {
+                win = image_window(ma.bits, p);
+            } else {
+                // (key_pos is padded by a whole window: p + lane is always in range; positions >= r1 are clipped below)
+                int64_t kv;
+                if constexpr (WIN == 1) kv = (int64_t) static_cast<const int32_t *>(ma.key_pos)[p + (uint64_t)lane];
+                else kv = static_cast<const int64_t *>(ma.key_pos)[p + (uint64_t)lane];
+                win = __ballot(kv == qkey);
+                if (ma.valid_pos) win &= image_window(ma.valid_pos, p);
+                if (ma.bits) win &= image_window(ma.bits, p);
+            }
             if (r1 - w0 < 64) win &= (1ull << (r1 - w0)) - 1ull;
             const uint32_t cnt = (uint32_t)__popcll(win);
             if (cnt == 0) continue;
@@ -251,36 +321,49 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
 
 #undef LDS_AT
 
-template <int CG, int S, int MODE, bool SEQ, bool ALIGNED>
-static hipError_t launch_masked_t(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
+template <int CG, int S, int MODE, bool SEQ, bool ALIGNED, int WIN>
+static hipError_t launch_masked_t(const StreamArgs &a, const typename WinArgs<WIN>::type &ma, hipStream_t s) {
     dim3 grid(a.blocks_per_list, MODE == STREAM_RANGE ? a.nj : a.nprobe, a.nq);
-    hipLaunchKernelGGL((masked_stream_kernel<CG, S, MODE, SEQ, ALIGNED>), grid, dim3(256), 0, s, a, ma);
+    hipLaunchKernelGGL((masked_stream_kernel<CG, S, MODE, SEQ, ALIGNED, WIN>), grid, dim3(256), 0, s, a, ma);
     return hipGetLastError();
 }
 
 // the chunk choice of launch_stream (the chain order does not depend on it)
-template <int S, int MODE>
-static hipError_t launch_masked_s(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
+template <int S, int MODE, int WIN>
+static hipError_t launch_masked_s(const StreamArgs &a, const typename WinArgs<WIN>::type &ma, hipStream_t s) {
     const bool aligned = (a.dim % 4) == 0;
     const uint32_t G = a.dim / 4;
     if (a.metric == 1) {
-        return aligned ? launch_masked_t<16, S, MODE, true, true>(a, ma, s)
-                       : launch_masked_t<16, S, MODE, true, false>(a, ma, s);
+        return aligned ? launch_masked_t<16, S, MODE, true, true, WIN>(a, ma, s)
+                       : launch_masked_t<16, S, MODE, true, false, WIN>(a, ma, s);
     }
-    if (!aligned) return launch_masked_t<32, S, MODE, false, false>(a, ma, s);
-    if (G >= 64 && G % 64 == 0) return launch_masked_t<64, S, MODE, false, true>(a, ma, s);
-    return launch_masked_t<32, S, MODE, false, true>(a, ma, s);
+    if (!aligned) return launch_masked_t<32, S, MODE, false, false, WIN>(a, ma, s);
+    if (G >= 64 && G % 64 == 0) return launch_masked_t<64, S, MODE, false, true, WIN>(a, ma, s);
+    return launch_masked_t<32, S, MODE, false, true, WIN>(a, ma, s);
+}
+
+template <int WIN>
+static hipError_t launch_masked_w(const StreamArgs &a, const typename WinArgs<WIN>::type &ma, StreamMode mode, hipStream_t s) {
+    if (!a.probe || !a.list_off || !a.cand_base) return hipErrorInvalidValue;
+    if (a.nq == 0 || a.blocks_per_list == 0) return hipSuccess;
+    if (mode == STREAM_RANGE) return a.nj == 0 ? hipSuccess : launch_masked_s<1, STREAM_RANGE, WIN>(a, ma, s);
+    if (mode != STREAM_TOPK) return hipErrorInvalidValue;
+    if (a.nprobe == 0) return hipSuccess;
+    if (a.k <= 64) return launch_masked_s<1, STREAM_TOPK, WIN>(a, ma, s);
+    if (a.k <= 256) return launch_masked_s<4, STREAM_TOPK, WIN>(a, ma, s);
+    if (a.k <= 1024) return launch_masked_s<16, STREAM_TOPK, WIN>(a, ma, s);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s) {
-    if (!a.probe || !a.list_off || !a.cand_base || !ma.bits) return hipErrorInvalidValue;
-    if (a.nq == 0 || a.blocks_per_list == 0) return hipSuccess;
-    if (mode == STREAM_RANGE) return a.nj == 0 ? hipSuccess : launch_masked_s<1, STREAM_RANGE>(a, ma, s);
-    if (mode != STREAM_TOPK) return hipErrorInvalidValue;
-    if (a.nprobe == 0) return hipSuccess;
-    if (a.k <= 64) return launch_masked_s<1, STREAM_TOPK>(a, ma, s);
-    if (a.k <= 256) return launch_masked_s<4, STREAM_TOPK>(a, ma, s);
-    if (a.k <= 1024) return launch_masked_s<16, STREAM_TOPK>(a, ma, s);
+    if (!ma.bits) return hipErrorInvalidValue;
+    return launch_masked_w<0>(a, ma, mode, s);
+}
+
+hipError_t launch_keyed_stream(const StreamArgs &a, const KeyedArgs &ka, StreamMode mode, hipStream_t s) {
+    if (!ka.key_pos || !ka.qkeys) return hipErrorInvalidValue;
+    if (ka.elem_size == 4) return launch_masked_w<1>(a, ka, mode, s);
+    if (ka.elem_size == 8) return launch_masked_w<2>(a, ka, mode, s);
     return hipErrorInvalidValue;
 }
 

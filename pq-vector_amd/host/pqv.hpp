@@ -153,6 +153,34 @@ private:
     std::unique_ptr<pqv_row_mask, Del> h_;
 };
 
+// A key column laid out for one searcher (pqv.h: pqv_row_keys): every query of a keyed call is filtered by ITS OWN
+// `column == key`.  The column is copied; keys may outlive their searcher or be released before it.
+class RowKeys {
+public:
+    RowKeys(const Searcher &s, const Column &column) {
+        pqv_row_keys *h = nullptr;
+        check(pqv_row_keys_create(s.get(), column.get(), nullptr, &h));
+        h_.reset(h);
+    }
+    const pqv_row_keys *get() const { return h_.get(); }
+    uint64_t rows() const { return pqv_row_keys_rows(h_.get()); }
+    int dtype() const { return pqv_row_keys_dtype(h_.get()); }
+    // top-k of nq = qkeys.size() queries (queries: [nq, dim]), query q over the rows whose key equals qkeys[q] -- and, with `mask`,
+    // that the mask allows (pqv.h: pqv_topk_keyed); found[q] results per query, k slots each
+    void topk(const Searcher &s, const std::vector<int64_t> &qkeys, const std::vector<float> &queries, uint32_t k, uint32_t nprobe,
+              std::vector<uint32_t> &rows, std::vector<float> &dist, std::vector<uint32_t> &found, const RowMask *mask = nullptr) const {
+        const uint32_t nq = static_cast<uint32_t>(qkeys.size());
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, 0.0f);
+        found.assign(nq, 0);
+        check(pqv_topk_keyed(s.get(), h_.get(), qkeys.data(), mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, nprobe, 0,
+                             PQV_L2SQ_REF4, 1, rows.data(), dist.data(), found.data(), nullptr));
+    }
+private:
+    struct Del { void operator()(pqv_row_keys *p) const { pqv_row_keys_free(p); } };
+    std::unique_ptr<pqv_row_keys, Del> h_;
+};
+
 class TopkBuilder {
 public:
     TopkBuilder(const Searcher &s, const std::vector<float> &query) : s_(s), query_(query) {}
