@@ -277,6 +277,14 @@ pub struct SearchResult {
     pub distance: f32,
 }
 
+/// One group of a distinct top-k ([`Searcher::topk_distinct`]): the group's nearest row, its distance and the group's key value.
+#[derive(Debug, Clone, PartialEq)]
+pub struct DistinctSearchResult {
+    pub row_idx: u32,
+    pub distance: f32,
+    pub key: i64,
+}
+
 /// An index bound to its column on one GPU.  What `topk()` re-creates per query from the file
 /// (`read_index_from_parquet` + `read_embeddings_for_rows`, `src/ivf/search.rs:89-110`) is kept resident here:
 /// cache one per indexed Parquet file.
@@ -459,6 +467,45 @@ impl<'c> Searcher<'c> {
         Ok((0..nq)
             .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
             .collect())
+    }
+
+    /// The nearest row of each of the `k` nearest groups -- a group is the considered rows of one value of `keys` (NULL-key rows
+    /// belong to none), under `mask` where one is given (`include/pqv.h`: `pqv_topk_distinct`).  Ascending by (distance, position).
+    pub fn topk_distinct(&self, keys: &RowKeys, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,
+                         nprobe: NonZeroUsize) -> Result<Vec<Vec<DistinctSearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (k, np) = (k.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut group = vec![0i64; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_distinct(self.raw, keys.raw, mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(), nq as u32,
+                                   dim as u32, k as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(), dist.as_mut_ptr(),
+                                   group.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| {
+                (0..found[q] as usize)
+                    .map(|i| DistinctSearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i], key: group[q * k + i] })
+                    .collect()
+            })
+            .collect())
+    }
+
+    /// [`Searcher::topk_distinct`] on device buffers, enqueued on `hip_stream` (NULL: the searcher's): `d_queries` f32 `[nq, dim]`,
+    /// `d_row_idx` u32 / `d_dist` f32 / `d_group_key` i64 `[nq, k]`, `d_n_found` u32 / `d_n_candidates` u64 `[nq]`; the last three may
+    /// be NULL.
+    ///
+    /// # Safety
+    /// Every non-NULL pointer must be a device allocation of at least the size above, valid until the stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn topk_distinct_device(&self, keys: &RowKeys, mask: Option<&RowMask>, d_queries: *const c_void, nq: u32, k: NonZeroUsize,
+                                       nprobe: NonZeroUsize, d_row_idx: *mut c_void, d_dist: *mut c_void, d_group_key: *mut c_void,
+                                       d_n_found: *mut c_void, d_n_candidates: *mut c_void, hip_stream: *mut c_void) -> Result<()> {
+        check(sys::pqv_topk_distinct_device(self.raw, keys.raw, mask.map_or(ptr::null(), |m| m.raw as *const _), d_queries, nq,
+                                            k.get() as u32, nprobe.get() as u32, 0, sys::PQV_L2SQ_REF4, 1, d_row_idx, d_dist,
+                                            d_group_key, d_n_found, d_n_candidates, hip_stream))
     }
 
     /// Plan metrics (`src/df_vector/index_exec.rs:289-299`, `exec.rs:411-427`).

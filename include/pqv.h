@@ -541,6 +541,47 @@ int pqv_range_search_keyed(const pqv_searcher *searcher, const pqv_row_keys *key
                            uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                            uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates);
 
+/* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
+ * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.
+ *
+ * A distinct call is the masked call of the same arguments plus a group column `keys`: a pqv_row_keys of this searcher (I32 or
+ * I64, optional validity).  `mask` is an optional shared row mask, NULL: none.
+ *   considered rows  the unmasked candidate sequence, cut by max_candidates / a table's round-robin quotas BEFORE any filter; of
+ *                    the capped candidates, those whose key is valid (not NULL) and which the mask allows, at their UNMASKED
+ *                    positions.  A NULL-key row belongs to no group and is never returned (as a NULL row never matches a keyed call).
+ *   group            all considered rows of equal key value, compared in i64 (an I32 column is widened); its representative is
+ *                    its considered row with the smallest (d2, position).
+ *   result           query q: the k representatives with the smallest (d2, position), ascending by that pair -- always: the
+ *                    reference has no grouping, so there is no heap history to replay and there are no tie flags; the host and
+ *                    the device form return the same thing.  NaN distances follow the key's bit order, as in
+ *                    pqv_topk_masked_device (unpinned, as everywhere).
+ *   outputs          row_idx, dist and group_key (int64_t [nq * k]: the representatives' key values), n_found (groups found, at
+ *                    most k) and n_candidates; entries past n_found[q] are 0xFFFFFFFF, +inf and 0.  sqrt_out and the PQV_COSINE
+ *                    halving are the masked call's.  group_key / d_group_key, n_found and n_candidates may be NULL.
+ *   counts           n_candidates and candidate_rows are the counts before cap and filter; embeddings_fetched advances by the
+ *                    considered rows.
+ *   equivalence      query q's result is the (d2, position)-sorted sequence of its considered rows with only the FIRST row of
+ *                    every key value kept, cut to k; that sorted sequence is what pqv_range_search_masked returns with radius =
+ *                    +inf, sqrt_out = 0 and the same mask ANDed with the key validity.  Hence with all keys distinct the call
+ *                    returns, bit for bit, what pqv_topk_masked_device returns (rows, distances, n_found).
+ *   path             always the exact streaming pass with lists that hold at most one entry per group: no searcher option
+ *                    changes a result, and excluded rows are never read.  Plain and table searchers, every layout, PQV_COSINE
+ *                    through the cosine layout.  The kernels serve k <= 1024 and at most 1024 probed lists; beyond that
+ *                    pqv_topk_distinct computes the sorted considered sequence with the masked range machinery (radius = +inf)
+ *                    and keeps the first row per key on the host, and pqv_topk_distinct_device reports PQV_ERR_UNSUPPORTED, as
+ *                    pqv_topk_masked_device does.
+ *   out of scope     more than one row per group; a per-query key filter combined with a group column in one call; distinct
+ *                    range search.
+ * Errors (PQV_ERR_INVALID; NULL handles are checked before any device use): "searcher must not be NULL", "row keys must not be
+ * NULL", "row keys belong to another searcher", "row mask belongs to another searcher", and pqv_topk's own ("k must be > 0", ...). */
+int pqv_topk_distinct(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries,
+                      uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric,
+                      int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_distinct_device(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask,
+                             const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric,
+                             int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_n_found,
+                             void *d_n_candidates, void *hip_stream);
+
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`
  * baseline does row by row (benches/query.rs:76-98), for the metrics above.  Results are

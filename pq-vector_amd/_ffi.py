@@ -159,6 +159,10 @@ SIGNATURES = {
                                         vp, vp, vp, vp, vp, vp]),
     "pqv_range_search_keyed": (C.c_int, [vp, vp, i64p, vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64,
                                          C.c_uint64, C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
+    "pqv_topk_distinct": (C.c_int, [vp, vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                    u32p, f32p, i64p, u32p, u64p]),
+    "pqv_topk_distinct_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                           vp, vp, vp, vp, vp, vp]),
     "pqv_brute_topk": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, u32p]),
     "pqv_rerank": (C.c_int, [C.c_int, f32p, f32p, u32p, u8p, C.c_uint64, C.c_uint32, C.c_uint32,
                              C.c_int, u32p, f32p, u32p]),

@@ -400,6 +400,14 @@ class SearchResult:
     distance: float
 
 
+@dataclass
+class DistinctSearchResult:
+    """One group of a distinct top-k (TopkBuilder.distinct_on): the group's nearest row, its distance, the group's key value."""
+    row_idx: int
+    distance: float
+    key: int
+
+
 _COLUMN_DTYPES = {np.dtype(np.int32): _ffi.PQV_COL_I32, np.dtype(np.int64): _ffi.PQV_COL_I64,
                   np.dtype(np.float32): _ffi.PQV_COL_F32, np.dtype(np.float64): _ffi.PQV_COL_F64}
 _RESIDENT_TYPES = "int8..int64, uint8..uint32, bool, date, timestamp, time64, float, double"
@@ -591,6 +599,14 @@ def _keys_handle(keys, query_keys):
     return keys._h
 
 
+def _group_handle(keys):
+    if not isinstance(keys, RowKeys):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"keys must be a RowKeys, got {type(keys).__name__}")
+    if keys._h is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "row keys must not be NULL")
+    return keys._h
+
+
 def _query_keys(query_keys, nq):
     """A host call's query keys -> contiguous int64 [nq]; integers only, each within i64."""
     a = np.asarray(query_keys)
@@ -775,6 +791,36 @@ class Searcher:
                                    dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
                                    nc.ctypes.data_as(u64p)))
         return rows, dist, nf, nc
+
+    def topk_distinct(self, queries, k, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """Distinct top-k (pqv.h: pqv_topk_distinct): per query the nearest row of each of the k nearest groups, a group being the
+        considered rows of one value of `keys` (a RowKeys of this searcher; NULL-key rows belong to no group), under `mask` if one
+        is given.  Returns (row_idx [nq,k] u32, dist [nq,k] f32, group_keys [nq,k] i64, n_found [nq], n_candidates [nq]), ascending
+        by (d2, candidate position); entries past n_found are 0xFFFFFFFF, +inf and 0."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        rows = np.full((nq, max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        grp = np.zeros((nq, max(k, 1)), dtype=np.int64)
+        nf = np.zeros(nq, dtype=np.uint32)
+        nc = np.zeros(nq, dtype=np.uint64)
+        _check(_ffi.lib().pqv_topk_distinct(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
+                                            q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                            rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), grp.ctypes.data_as(_ffi.i64p),
+                                            nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p)))
+        return rows, dist, grp, nf, nc
+
+    def topk_distinct_device(self, d_queries, nq, k, nprobe, keys, d_row_idx, d_dist, d_group_key=0, d_n_found=0, d_n_candidates=0,
+                             mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of topk_distinct (pqv.h: pqv_topk_distinct_device), asynchronous on `stream` as topk_device is:
+        d_row_idx u32 / d_dist f32 / d_group_key i64 [nq, k], d_n_found u32 / d_n_candidates u64 [nq]; the last three are optional.
+        keys and mask must stay alive until the enqueued work has completed."""
+        _check(_ffi.lib().pqv_topk_distinct_device(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
+                                                   vp(d_queries), nq, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                   vp(d_row_idx), vp(d_dist), vp(d_group_key or None), vp(d_n_found or None),
+                                                   vp(d_n_candidates or None), vp(stream or None)))
 
     def range_search(self, queries, radius, nprobe, max_candidates=0, max_results=0, metric=_ffi.PQV_L2SQ_REF4,
                      sqrt_out=True, mask=None, keys=None, query_keys=None):
@@ -1072,10 +1118,44 @@ class TopkBuilder:
         self._nprobe = None
         self._metric = _ffi.PQV_L2SQ_REF4
         self._where = None
+        self._distinct = None
 
     def metric(self, m):
         self._metric = _metric_arg(m)
         return self
+
+    def distinct_on(self, x):
+        """`SELECT DISTINCT ON (x) .. ORDER BY distance LIMIT k`: the nearest row of each of the k nearest values of an integer
+        column -- the k nearest documents, not k chunks of one (pqv.h: pqv_topk_distinct).  x: the name of an integer column (with a
+        path source the file's, loaded once per resident file; with a Searcher source an attached one), or a RowKeys of the
+        searcher.  Rows whose value is NULL belong to no group.  search() then returns [DistinctSearchResult(row_idx, distance,
+        key)]; composes with where() and metric()."""
+        if isinstance(x, RowKeys):
+            if self._searcher is None:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "distinct_on(RowKeys) needs a Searcher source: row keys belong to one searcher")
+        elif not isinstance(x, str):
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"distinct_on() needs a column name or a RowKeys, got {type(x).__name__}")
+        self._distinct = x
+        return self
+
+    def _group_keys(self, searcher):
+        """-> (RowKeys, owned) of the distinct_on() argument on `searcher`."""
+        if isinstance(self._distinct, RowKeys):
+            return self._distinct, False
+        if self._path is not None:
+            _attach_file_columns(searcher, self._path, [self._distinct])
+        return searcher.row_keys(self._distinct), True
+
+    def _search_distinct(self, searcher, mask, max_candidates=0):
+        keys, owned = self._group_keys(searcher)
+        try:
+            rows, dist, grp, nf, _ = searcher.topk_distinct(_f32(self._query).reshape(1, -1), self._k, self._nprobe, keys, mask=mask,
+                                                            max_candidates=max_candidates, metric=self._metric)
+        finally:
+            if owned:
+                keys.close()
+        n = int(nf[0])
+        return rows[0, :n], dist[0, :n], grp[0, :n]
 
     def where(self, x):
         """Restrict the search to rows (the reference's `WHERE <predicate>` inside the scan, exec.rs:207-277): a bool array over
@@ -1105,6 +1185,14 @@ class TopkBuilder:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
+        if self._distinct is not None:
+            mask, owned = _resolve_where(self._where, self._path, self._searcher) if self._where is not None else (None, False)
+            try:
+                rows, dist, grp = self._search_distinct(self._searcher, mask)
+            finally:
+                if owned:
+                    mask.close()
+            return [DistinctSearchResult(r, d, g) for r, d, g in zip(rows.tolist(), dist.tolist(), grp.tolist())]
         if self._where is not None:
             mask, owned = _resolve_where(self._where, self._path, self._searcher)
             try:
@@ -1193,6 +1281,15 @@ class TableSearchResult:
     path: str
     row_idx: int
     distance: float
+
+
+@dataclass
+class TableDistinctSearchResult:
+    """TableSearchResult of a distinct top-k (TableTopkBuilder.distinct_on), with the group's key value."""
+    path: str
+    row_idx: int
+    distance: float
+    key: int
 
 
 def _table_args(indexes, corpus, row_base):
@@ -1384,12 +1481,33 @@ class TableTopkBuilder(TopkBuilder):
         self._where = _table_where_arg(x, self._paths)
         return self
 
+    def distinct_on(self, x):
+        """TopkBuilder.distinct_on over the table: x names an integer column that every file has (one resident type); search()
+        returns [TableDistinctSearchResult(path, row_idx, distance, key)]."""
+        if not isinstance(x, str):
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"a table's distinct_on() needs a column name, got {type(x).__name__}")
+        self._distinct = x
+        return self
+
+    def _group_keys(self, searcher):
+        _attach_table_columns(searcher, self._paths, [self._distinct])
+        return searcher.row_keys(self._distinct), True
+
     def search(self):
         if self._k is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "k must be set")
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
+        if self._distinct is not None:
+            mask = _resolve_table_where(self._where, self._paths, s) if self._where is not None else None
+            try:
+                rows, dist, grp = self._search_distinct(s, mask, self._max_candidates)
+            finally:
+                if mask is not None:
+                    mask.close()
+            return [TableDistinctSearchResult(r.path, r.row_idx, r.distance, int(g))
+                    for r, g in zip(_table_results(s, self._paths, rows, dist), grp.tolist())]
         if self._where is not None:
             mask = _resolve_table_where(self._where, self._paths, s)
             try:

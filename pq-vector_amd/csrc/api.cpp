@@ -29,6 +29,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <unordered_set>
 #include <vector>
 
 #include "internal.h"
@@ -319,7 +320,8 @@ struct Scratch {
         s_hit_cnt, s_hit_keys, s_hit_vals, s_alt_keys, s_alt_vals, s_rsegs, s_rout_off, s_rout_rows, s_rout_dist,   // s_hit_* .. s_rout_*: pqv_range_search
         s_pair_end, s_file_cnt,     // round-robin capped tables: per-pair candidate ends, per-file counts (SegProbeArgs)
         s_qcos,                     // PQV_COSINE: the call's normalised queries n(q), read by the cosine searcher's kernels
-        s_qkeys;                    // keyed host calls (pqv_row_keys): the sub-batch's query keys, i64 [b]
+        s_qkeys,                    // keyed host calls (pqv_row_keys): the sub-batch's query keys, i64 [b]
+        s_part_grp, s_grp_out;      // distinct calls: the partial lists' group values i64 [nq][n_part][k]; the host form's group_key block
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -333,7 +335,7 @@ struct Scratch {
                 &s_dist, &s_nfound, &s_pair_u32, &s_pairs, &s_groups, &s_quads, &s_items, &s_ticket, &s_ticket2, &s_cand_keys, &s_cand_vals, &s_cand_cnt, &s_spilled,
                 &s_seed_ub, &s_qblk, &s_gthr, &s_tie, &s_replay, &s_qnorm, &s_qmax, &s_thr_hist, &s_thr_bins, &s_qi8, &s_qn2i, &s_qres, &s_qresu, &s_pair_lb, &s_part_flags, &s_qpad, &s_cand_lb, &s_pendv, &s_work, &s_nwork, &s_out,
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
-                &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys};
+                &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_part_grp, &s_grp_out};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -541,6 +543,8 @@ struct MaskView {
     const pqv_row_keys *keys;          // a keyed call's key column, else nullptr
     const int64_t *h_qkeys;            // host forms: [nq] query keys, indexed like the call's queries
     const int64_t *d_qkeys;            // device: the keys of the queries the kernels see (the current sub-batch's)
+    const pqv_row_keys *group;         // a distinct call's group column, else nullptr (bits / mask: its shared mask, or nullptr)
+    int64_t *d_group_out;              // distinct: where the fold writes the group values [nq * k] (device), or nullptr
 };
 // a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
 static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
@@ -629,8 +633,16 @@ static int row_filter(const pqv_searcher *s, const MaskView *mv, uint64_t q, Row
     return PQV_OK;
 }
 // the STREAM_TOPK / STREAM_RANGE pass of a masked or keyed call
+// (a distinct call: STREAM_TOPK only, the per-wave lists' group values go to part_grp)
 static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskView *mv, unsigned long long *stats, const uint64_t *n_cand,
-                                         pqv::StreamMode mode, hipStream_t stream) {
+                                         pqv::StreamMode mode, hipStream_t stream, int64_t *part_grp = nullptr) {
+    if (mv->group) {
+        if (mode != pqv::STREAM_TOPK) return hipErrorInvalidValue;
+        const pqv_row_keys *gk = mv->group;
+        const pqv::DistinctArgs da{mv->bits, stats, n_cand, gk->d_key_pos.p, gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr,
+                                   gk->dtype == PQV_COL_I32 ? 4u : 8u, part_grp};
+        return pqv::launch_distinct_stream(ra, da, stream);
+    }
     if (mv->keys) {
         const pqv_row_keys *kk = mv->keys;
         const pqv::KeyedArgs ka{mv->bits, stats, n_cand, kk->d_key_pos.p, kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr,
@@ -3555,6 +3567,8 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     pm.stats = mask ? nullptr : s->d_stats.as<unsigned long long>();
     HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint32_t)));
+    const bool distinct = mask && mask->group;
+    if (distinct) HIP_TRY(sc.s_part_grp.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(int64_t)));
 
     hipEvent_t ev[4];
     if (int rc = timing_events(s, ev)) return rc;
@@ -3875,7 +3889,8 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     if (!p.tile) {
         if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
         if (mask) {
-            HIP_TRY(launch_filtered_stream(ra, mask, s->d_stats.as<unsigned long long>(), pm.n_cand, STREAM_TOPK, stream));
+            HIP_TRY(launch_filtered_stream(ra, mask, s->d_stats.as<unsigned long long>(), pm.n_cand, STREAM_TOPK, stream,
+                                           distinct ? sc.s_part_grp.as<int64_t>() : nullptr));
         } else {
             HIP_TRY(launch_stream(ra, STREAM_TOPK, stream));
         }
@@ -3883,6 +3898,19 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     }
 
     // 3. fold the per-wave lists
+    if (distinct) {      // (at most one entry per group: distinct_merge_kernel -- no tie flag, k_out == k)
+        if (p.tile || k_out != k || d_tie) return fail(PQV_ERR_INVALID, "distinct call on a non-distinct plan");
+        DistinctMergeArgs dm{};
+        dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = sc.s_part_grp.as<int64_t>();
+        dm.nq = nq; dm.n_part = p.n_part_rr; dm.k = k; dm.elem_size = mask->group->dtype == PQV_COL_I32 ? 4u : 8u;
+        dm.ids = s->d_final_ids; dm.row_idx = d_row_idx; dm.dist = d_dist; dm.group_key = mask->d_group_out; dm.n_found = d_n_found;
+        dm.sqrt_out = sqrt_out;
+        HIP_TRY(launch_distinct_merge(dm, stream));
+        if (ev[3]) HIP_TRY(hipEventRecord(ev[3], stream));
+        if (int rc = lane_release(sc, stream)) return rc;
+        s->counters.kernel_launches += 4;
+        return PQV_OK;
+    }
     MergeArgs fm{};
     fm.part_keys = ra.part_keys; fm.part_vals = ra.part_vals;
     fm.nq = nq; fm.n_part = p.n_part_rr; fm.k_part = k; fm.k = k;
@@ -4963,6 +4991,155 @@ extern "C" int pqv_range_search_keyed(const pqv_searcher *s, const pqv_row_keys 
         mv.h_qkeys = qkeys;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
+    });
+}
+
+// ---- distinct top-k (pqv.h: pqv_topk_distinct) -----------------------------------------------------------------------------
+// the checks both entry points make before anything else: NULL handles first, nothing dereferenced before them
+static int distinct_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, MaskView &mv) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
+    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");       // (validate_topk's, ahead of everything that reads a handle)
+    if (keys->owner != s || keys->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
+    mv = MaskView{};
+    if (mask) {
+        if (int rc = mask_view(s, mask, mv)) return rc;
+    }
+    mv.group = keys;
+    return PQV_OK;
+}
+namespace {
+// Beyond the kernels' lists (k > 1024 or more than 1024 probed lists): the (d2, position)-sorted considered rows of every query from
+// the masked range machinery -- radius +inf, d2 out, under the position image (key validity AND shared mask) -- and the first row
+// of every key value kept on the host.  Correct for any k / nprobe; not a fast path.
+int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const MaskView *mv, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                       uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key,
+                       uint32_t *n_found, uint64_t *n_candidates) {
+    const pqv_row_keys *gk = mv->group;
+    if (int rc = keys_host_rows(s, gk)) return rc;
+    // the image of the considered positions, made on the host from the two images (n / 8 bytes each)
+    const uint64_t n_words = (s->n + 63) / 64 + 1;
+    std::vector<uint64_t> img, other;
+    try { img.assign(n_words, ~0ull); other.resize(n_words); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+    for (const void *src : {gk->has_valid ? gk->d_valid_pos.p : nullptr, static_cast<void *>(const_cast<uint64_t *>(mv->bits))}) {
+        if (!src) continue;
+        HIP_TRY(hipMemcpy(other.data(), src, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t w = 0; w < n_words; ++w) img[w] &= other[w];
+    }
+    for (uint64_t pz = s->n; pz < n_words * 64; ++pz) img[pz >> 6] &= ~(1ull << (pz & 63u));     // (bits of positions >= n are zero)
+    DevBuf d_img;
+    HIP_TRY(d_img.alloc(n_words * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(d_img.p, img.data(), n_words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    MaskView rv{};
+    rv.bits = d_img.as<uint64_t>();
+    std::unique_ptr<uint64_t, HostFree> lims(static_cast<uint64_t *>(std::malloc((static_cast<size_t>(nq) + 1) * sizeof(uint64_t))));
+    std::unique_ptr<uint32_t, HostFree> rows(static_cast<uint32_t *>(std::malloc(sizeof(uint32_t))));
+    std::unique_ptr<float, HostFree> d2(static_cast<float *>(std::malloc(sizeof(float))));
+    if (!lims || !rows || !d2) return fail(PQV_ERR_OOM, "host allocation failed");
+    lims.get()[0] = 0;
+    if (int rc = range_body(s, sc, queries, nq, INFINITY, nprobe, max_candidates, 0, metric, 0, lims.get(), rows, d2, nullptr, n_candidates, &rv))
+        return rc;
+    std::unordered_set<int64_t> seen;
+    for (uint32_t q = 0; q < nq; ++q) {
+        seen.clear();
+        uint32_t found = 0;
+        uint32_t *orow = row_idx + static_cast<uint64_t>(q) * k;
+        float *od = dist + static_cast<uint64_t>(q) * k;
+        int64_t *og = group_key ? group_key + static_cast<uint64_t>(q) * k : nullptr;
+        for (uint64_t i = lims.get()[q]; i < lims.get()[q + 1] && found < k; ++i) {
+            const uint32_t r = rows.get()[i];
+            if (r >= gk->n_rows) continue;
+            const int64_t g = gk->host_vals[r];
+            if (!seen.insert(g).second) continue;
+            const float v = d2.get()[i];
+            orow[found] = r;
+            od[found] = sqrt_out == 1 ? std::sqrt(v) : sqrt_out == 2 ? 0.5f * v : v;
+            if (og) og[found] = g;
+            ++found;
+        }
+        // (k may be huge -- "keep everything": the caller's buffers are [nq * k] all the same)
+        for (uint64_t e = found; e < k; ++e) { orow[e] = 0xFFFFFFFFu; od[e] = INFINITY; if (og) og[e] = 0; }
+        if (n_found) n_found[q] = found;
+    }
+    return PQV_OK;
+}
+}  // namespace
+static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                                  uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
+                                  int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
+    if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
+    if (nq == 0) return PQV_OK;
+    if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+    if (int rc = use_device(s->device)) return rc;
+    if (metric == PQV_COSINE) {
+        std::vector<float> nq_host;
+        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
+        return pqv_topk_distinct_impl(s->cos.get(), mv, nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist,
+                                      group_key, n_found, n_candidates);
+    }
+    std::lock_guard<std::mutex> lock(s->mu);
+    Scratch *lane = nullptr;
+    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
+    Scratch &sc = *lane;
+    LaneGuard lane_guard{sc, s->stream};
+    if (beyond_kernel_lists(s, k, nprobe)) {
+        const int rc = distinct_unbounded(s, sc, mv, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, group_key, n_found,
+                                          n_candidates);
+        const int rc2 = lane_release(sc, s->stream);
+        return rc ? rc : rc2;
+    }
+    // sub-batches as the keyed form slices them: the per-wave partial lists (20 B per entry here) stay under ~1 GiB
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), nprobe, k, metric, true);
+    const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * k * 20 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
+                               static_cast<uint64_t>(p1.np) * 32 + static_cast<uint64_t>(s->sdim + s->dim) * 4 + 20ull * k + 16;
+    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 30) / per_query)));
+    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
+    HIP_TRY(sc.s_rows.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
+    HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(batch) * k * sizeof(float)));
+    HIP_TRY(sc.s_grp_out.ensure(static_cast<size_t>(batch) * k * sizeof(int64_t)));
+    HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
+    MaskView sub = *mv;
+    sub.d_group_out = sc.s_grp_out.as<int64_t>();
+    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
+        const uint32_t b = std::min<uint32_t>(batch, nq - q0);
+        const uint64_t o = static_cast<uint64_t>(q0) * k;
+        const size_t nk = static_cast<size_t>(b) * k;
+        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
+                               hipMemcpyHostToDevice, s->stream));
+        if (int rc = enqueue_topk(s, sc.s_queries.as<float>(), b, k, k, nprobe, max_candidates, metric, sqrt_out, sc.s_rows.as<uint32_t>(),
+                                  sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_ncand.as<uint64_t>(), nullptr, s->stream, sc, &sub))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(row_idx + o, sc.s_rows.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(dist + o, sc.s_dist.p, nk * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        if (group_key) HIP_TRY(hipMemcpyAsync(group_key + o, sc.s_grp_out.p, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+        if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        if (n_candidates)
+            HIP_TRY(hipMemcpyAsync(n_candidates + q0, sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        s->counters.queries += b;
+    }
+    return PQV_OK;
+}
+extern "C" int pqv_topk_distinct(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                 uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                 uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
+        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
+                                      n_found, n_candidates);
+    });
+}
+extern "C" int pqv_topk_distinct_device(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const void *d_queries,
+                                        uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                        void *d_row_idx, void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
+        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, nullptr, hip_stream, &mv);
     });
 }
 

@@ -102,6 +102,37 @@ struct KeyedArgs {
 // launch_masked_stream with a window's bits taken from key_pos[p] == qkeys[q] (masked_stream_kernel, WIN = 1 / 2)
 hipError_t launch_keyed_stream(const StreamArgs &a, const KeyedArgs &ka, StreamMode mode, hipStream_t s);
 
+// ---- distinct top-k (kernels_distinct.hip; pqv.h: pqv_topk_distinct) -----------------------------------------------------
+// The group column is a key column's position image (launch_key_layout).  launch_distinct_stream is launch_masked_stream's
+// STREAM_TOPK pass over the positions whose key is valid and which the shared mask allows, with per-wave lists that hold at most
+// one entry per group value: part_keys / part_vals as there, plus part_grp [nq][nprobe * blocks_per_list * 4][k], the entries'
+// group values widened to i64.
+struct DistinctArgs {
+    const uint64_t     *bits;       // optional: a shared row mask's image (MaskedArgs::bits)
+    unsigned long long *stats;      // as MaskedArgs::stats
+    const uint64_t     *n_cand;     // as MaskedArgs::n_cand
+    const void         *key_pos;    // i32 / i64 [n_words * 64]: the group value of every list position
+    const uint64_t     *valid_pos;  // optional [n_words]: positions whose key is not NULL
+    uint32_t            elem_size;  // 4 or 8
+    int64_t            *part_grp;
+};
+hipError_t launch_distinct_stream(const StreamArgs &a, const DistinctArgs &da, hipStream_t s);
+// the fold of those lists, one wave per query (distinct_merge_kernel): k <= 1024
+struct DistinctMergeArgs {
+    const uint64_t *part_keys;   // [nq][n_part][k]
+    const uint32_t *part_vals;
+    const int64_t  *part_grp;
+    uint32_t        nq, n_part, k;
+    uint32_t        elem_size;   // the group column's width, 4 or 8 (an i32 column's values are compared in 32 bits)
+    const uint32_t *ids;         // storage row -> reported row (nullptr => identity)
+    uint32_t       *row_idx;     // [nq, k]
+    float          *dist;        // [nq, k]
+    int64_t        *group_key;   // [nq, k] or nullptr
+    uint32_t       *n_found;     // [nq] or nullptr
+    int             sqrt_out;    // 0 d2, 1 sqrt(d2), 2 0.5 d2 (PQV_COSINE)
+};
+hipError_t launch_distinct_merge(const DistinctMergeArgs &a, hipStream_t s);
+
 // ---- predicate masks (kernels_predicate.hip) -----------------------------------------------------------------------------
 // A mask's ROW IMAGE is the bitset in row order: bit r of word r / 64 = row r is allowed, ceil(n_rows / 64) words, bits of rows
 // >= n_rows zero.  predicate_rows_kernel writes it from resident columns and a postfix program (pqv.h:

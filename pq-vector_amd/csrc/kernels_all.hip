@@ -10,3 +10,4 @@
 #include "kernels_range.hip"
 #include "kernels_mask.hip"
 #include "kernels_predicate.hip"
+#include "kernels_distinct.hip"

@@ -176,6 +176,19 @@ public:
         check(pqv_topk_keyed(s.get(), h_.get(), qkeys.data(), mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, nprobe, 0,
                              PQV_L2SQ_REF4, 1, rows.data(), dist.data(), found.data(), nullptr));
     }
+    // distinct top-k with this column as the GROUP column (pqv.h: pqv_topk_distinct): per query the nearest row of each of the k
+    // nearest key values; found[q] groups per query, k slots each, group_keys the representatives' key values
+    void topk_distinct(const Searcher &s, const std::vector<float> &queries, uint32_t k, uint32_t nprobe, std::vector<uint32_t> &rows,
+                       std::vector<float> &dist, std::vector<int64_t> &group_keys, std::vector<uint32_t> &found,
+                       const RowMask *mask = nullptr) const {
+        const uint32_t nq = s.dim() ? static_cast<uint32_t>(queries.size() / s.dim()) : 0;
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, 0.0f);
+        group_keys.assign(static_cast<size_t>(nq) * k, 0);
+        found.assign(nq, 0);
+        check(pqv_topk_distinct(s.get(), h_.get(), mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, nprobe, 0, PQV_L2SQ_REF4, 1,
+                                rows.data(), dist.data(), group_keys.data(), found.data(), nullptr));
+    }
 private:
     struct Del { void operator()(pqv_row_keys *p) const { pqv_row_keys_free(p); } };
     std::unique_ptr<pqv_row_keys, Del> h_;
