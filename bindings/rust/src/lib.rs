@@ -325,6 +325,13 @@ impl<'c> Searcher<'c> {
         self.topk_metric(queries, dim, k, nprobe, sys::PQV_COSINE)
     }
 
+    /// [`Searcher::topk`] by inner product (an extension; `include/pqv.h`: `PQV_DOT`): the distance is `-(q.x)`, the negated
+    /// similarity in the 4-grouped f32 chain, smallest first; ties by candidate position, no heap replay.  `k <= 1024` and at most
+    /// 1024 probed lists per query.
+    pub fn topk_dot(&self, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
+        self.topk_metric(queries, dim, k, nprobe, sys::PQV_DOT)
+    }
+
     fn topk_metric(&self, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize, metric: c_int)
         -> Result<Vec<Vec<SearchResult>>> {
         let nq = if dim == 0 { 0 } else { queries.len() / dim };
@@ -354,6 +361,13 @@ impl<'c> Searcher<'c> {
     pub fn range_search_cosine(&self, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64)
         -> Result<Vec<Vec<SearchResult>>> {
         self.range_search_metric(queries, dim, radius, nprobe, max_results, sys::PQV_COSINE)
+    }
+
+    /// [`Searcher::range_search`] by inner product (`include/pqv.h`: `PQV_DOT`): hits are the candidates with `-(q.x) <= radius`
+    /// (`radius = -0.8` keeps `q.x >= 0.8`), and that is the distance returned.
+    pub fn range_search_dot(&self, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64)
+        -> Result<Vec<Vec<SearchResult>>> {
+        self.range_search_metric(queries, dim, radius, nprobe, max_results, sys::PQV_DOT)
     }
 
     fn range_search_metric(&self, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64, metric: c_int)

@@ -76,6 +76,38 @@ typedef enum pqv_metric {
  * searcher as it was.  Cosine queries are normalised on the device (one extra launch on the call's stream; pqv_topk_device stays
  * asynchronous after the first call); the halving is part of the final write-out.  pqv_rerank* and PQV_L2SQ_MFMA stay as they are:
  * no cosine through the index for the first, brute force only for the second. */
+#define PQV_DOT         4   /* inner product: dist = -(q.x), the negated similarity (pgvector's <#>)  */
+/* PQV_DOT through the index (pqv_topk, pqv_topk_device(_flags), pqv_range_search, the three masked forms, pqv_searcher_describe,
+ * plain and table searchers; an EXTENSION like cosine: the reference has no inner product).  All operations are f32, each rounded
+ * on its own:
+ *   s(q, x):  sum = 0.0f
+ *             per full group of four dims:  t = q0*x0 + q1*x1;  t = t + q2*x2;  t = t + q3*x3;  sum = sum + t
+ *             tail (dim % 4 values), element by element:  sum = sum + qe*xe
+ *   dist(q, x) = 0.0f - sum      (a zero result is always +0.0f, never -0.0f)
+ * -- index.rs:461-480's grouping with products in place of squared differences, so s(x, x) is bit-equal to the PQV_L2SQ_REF4 chain
+ * of x against 0.  Candidates are ordered by (dist, candidate position); NaN distances follow the order of
+ * ord(b) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000) on their f32 bits and are unpinned, as everywhere.
+ * A PQV_DOT call behaves as the PQV_L2SQ_REF4 call of the same arguments, except:
+ *   probe        centroids are ranked ascending by (dist(q, centroid), centroid id), the first min(nprobe, n_clusters) are probed; a
+ *                table searcher does so per file.  The candidate order, positions, max_candidates, a table's round-robin quotas
+ *                and n_candidates follow from that probe, unchanged.  pqv_probe and pqv_candidate_rows take no metric: L2.
+ *   result       the k candidates with the smallest (dist, position), ascending.  There is no reference heap to replay: pqv_topk
+ *                and pqv_topk_device return the same thing, exact_replays never advances and d_tie_flags (where given) is written
+ *                with zeros.  Entries past n_found[q] are 0xFFFFFFFF / +inf.  sqrt_out is ignored.
+ *   range        a hit iff dist <= radius, any non-NaN radius: a negative one is ordinary (radius = -0.8 keeps s >= 0.8), +inf
+ *                keeps every non-NaN candidate.  Order, max_results, n_within and the CSR output are unchanged.
+ *   masks        pqv_topk_masked, pqv_topk_masked_device and pqv_range_search_masked take PQV_DOT under the masked contract as
+ *                written (cap before mask, unmasked positions, excluded rows never read): bit-equal to the unmasked DOT call
+ *                over pqv_index_from_parts(dim, centroids, [each list's allowed rows]), n_candidates excepted.
+ *   path         always the exact stream per (query, probed list) over the centroids and the f32 rows in place, in every layout;
+ *                no searcher option changes a DOT result and no layout is built lazily.
+ *   limits       k <= 1024 (1023 with tie flags) and at most 1024 probed lists per query for EVERY DOT entry point, host and
+ *                range forms included: beyond that PQV_ERR_UNSUPPORTED "PQV_DOT takes k <= 1024 and at most 1024 probed lists
+ *                per query".
+ *   counters     queries, candidate_rows and embeddings_fetched advance as for the L2 (masked L2) call of the same shape;
+ *                screened_pairs and screen_survivors do not advance.
+ * pqv_topk_keyed*, pqv_range_search_keyed and pqv_topk_distinct* with PQV_DOT return PQV_ERR_UNSUPPORTED "PQV_DOT is not supported
+ * by keyed and distinct calls"; pqv_rerank* and pqv_brute_topk keep their metric checks. */
 
 /* pqv_searcher_create flags */
 #define PQV_LAYOUT_IVF_ORDERED   0x0u /* copy rows into cluster-contiguous order in HBM (default) */

@@ -28,12 +28,12 @@ from .api import (CandidateCursor, Column, Corpus, DistinctSearchResult, TableDi
                   rerank_finish, round_robin_quota, searcher_for_parquet, searcher_for_parquet_files, split_table_rows)
 from .parquet_io import has_pq_vector_index, load_scalar_column, read_index_from_parquet, row_mask_from_expression
 from .predicate import allowed, col
-from ._ffi import (PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE, PQV_L2SQ_MFMA, PQV_LAYOUT_IVF_ORDERED, PQV_LAYOUT_ROW_ORDER,
+from ._ffi import (PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE, PQV_L2SQ_MFMA, PQV_DOT, PQV_LAYOUT_IVF_ORDERED, PQV_LAYOUT_ROW_ORDER,
                    PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, PQV_PREPARE_COSINE, LIB_PATH)
 
 __all__ = ["RowMask", "RowKeys", "DistinctSearchResult", "TableDistinctSearchResult", "Column", "col", "allowed", "load_scalar_column", "row_mask_from_expression", "CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
            "TopkBuilder", "TableRangeBuilder", "TableSearcher", "TableSearchResult", "TableTopkBuilder", "searcher_for_parquet_files",
-           "split_table_rows", "device_count", "merge_topk", "rerank_batch", "rerank_finish", "searcher_for_parquet", "PQV_COSINE", "PQV_L2SQ_MFMA",
+           "split_table_rows", "device_count", "merge_topk", "rerank_batch", "rerank_finish", "searcher_for_parquet", "PQV_COSINE", "PQV_L2SQ_MFMA", "PQV_DOT",
            "has_pq_vector_index", "read_index_from_parquet", "PQV_L2SQ_REF4",
            "PQV_L2SQ_SEQ", "PQV_LAYOUT_IVF_ORDERED", "PQV_LAYOUT_ROW_ORDER",
            "PQV_RELEASE_ROW_ORDER", "PQV_RELEASE_IF_COPIED", "PQV_TABLE_CAP_ROUND_ROBIN", "PQV_PREPARE_COSINE", "round_robin_quota", "LIB_PATH"]

@@ -30,6 +30,7 @@ PQV_L2SQ_REF4 = 0
 PQV_L2SQ_SEQ = 1
 PQV_COSINE = 2
 PQV_L2SQ_MFMA = 3
+PQV_DOT = 4                           # inner product through the index: dist = -(q.x) (pqv.h: PQV_DOT)
 
 PQV_LAYOUT_IVF_ORDERED = 0x0
 PQV_LAYOUT_ROW_ORDER = 0x1

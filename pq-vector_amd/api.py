@@ -979,8 +979,8 @@ def searcher_for_parquet(path, device=0):
 
 
 def _metric_arg(m):
-    """The metric of a builder: PQV_L2SQ_REF4 (the default) or PQV_COSINE (pqv.h: PQV_COSINE)."""
-    if isinstance(m, bool) or not isinstance(m, int) or m not in (_ffi.PQV_L2SQ_REF4, _ffi.PQV_COSINE):
+    """The metric of a builder: PQV_L2SQ_REF4 (the default), PQV_COSINE or PQV_DOT (pqv.h: PQV_COSINE, PQV_DOT)."""
+    if isinstance(m, bool) or not isinstance(m, int) or m not in (_ffi.PQV_L2SQ_REF4, _ffi.PQV_COSINE, _ffi.PQV_DOT):
         raise PqvError(_ffi.PQV_ERR_INVALID, "unknown metric")
     return int(m)
 
@@ -1104,7 +1104,8 @@ def _resolve_table_where(per_file, paths, searcher):
 class TopkBuilder:
     """src/ivf/search.rs:49-81: k and nprobe must be set and > 0.  `source` is an indexed
     Parquet path (as in the reference) or an existing Searcher.  metric(m): PQV_L2SQ_REF4 (default, distances
-    sqrt(d2) as the reference returns them) or PQV_COSINE (0.5 * d2 of the normalised vectors, pqv.h: PQV_COSINE)."""
+    sqrt(d2) as the reference returns them), PQV_COSINE (0.5 * d2 of the normalised vectors, pqv.h: PQV_COSINE) or PQV_DOT (the negated
+    inner product -(q.x), smallest first, pqv.h: PQV_DOT; not with distinct_on)."""
 
     def __init__(self, source, query, device=0):
         import os
@@ -1210,7 +1211,8 @@ class TopkBuilder:
 class RangeBuilder:
     """Range counterpart of TopkBuilder: every row within `radius` of the query, nearest first (ties by candidate
     position).  radius and nprobe must be set; max_results (optional, > 0) keeps the first that many.  `source` is an
-    indexed Parquet path or an existing Searcher.  metric(m): as TopkBuilder's (PQV_COSINE: radius on the 0.5 * d2 scale)."""
+    indexed Parquet path or an existing Searcher.  metric(m): as TopkBuilder's (PQV_COSINE: radius on the 0.5 * d2 scale; PQV_DOT: hits have
+    -(q.x) <= radius, so radius = -0.8 keeps q.x >= 0.8)."""
 
     def __init__(self, source, query, device=0):
         import os

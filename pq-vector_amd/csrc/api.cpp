@@ -650,6 +650,7 @@ static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskVi
         return pqv::launch_keyed_stream(ra, ka, mode, stream);
     }
     const pqv::MaskedArgs ma{mv->bits, stats, n_cand};
+    if (ra.metric == PQV_DOT) return pqv::launch_dot_stream(ra, &ma, mode, stream);
     return pqv::launch_masked_stream(ra, ma, mode, stream);
 }
 
@@ -3270,6 +3271,7 @@ static bool seed_refine_on(const pqv_searcher *s, uint32_t nq, uint32_t k) {
 TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t k = 1, int metric = 0, bool exact_stream = false) {
     TopkPlan p{};
     const pqv_searcher::Opts &o = s->opt;
+    if (metric == PQV_DOT) exact_stream = true;     // (pqv.h: always the exact stream, whatever the options say)
     p.np = probe_count(s, nprobe);
     // probe pass: every block scans 256 centroids (64 per wave)
     p.probe_bpl = (s->n_clusters + 255) / 256;
@@ -3279,6 +3281,7 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     //  times tens of thousands of queries in one device call -- the per-query stream probe takes over)
     p.probe_rows = s->opt.probe_rows && s->kc_pad != 0 && (nq >= 8 || s->opt.probe_rows > 1) &&
                    static_cast<uint64_t>(nq) * s->kc_pad * 12 <= (2ull << 30);
+    if (metric == PQV_DOT) p.probe_rows = false;    // (probe_rows_kernel is L2 arithmetic: dot_stream_kernel over the centroid matrix)
     p.probe_kpart = p.probe_rows ? 64u : p.np;
     if (s->n_files && !p.probe_rows) {
         // table, stream_kernel probe: one list per file (no block straddles two files), the nprobe nearest of a file kept per partial list
@@ -3483,7 +3486,8 @@ int probe_merge_args(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, uint
 // distance pass zeroes on the way (the tile path's histogram).  With the round-robin cap (table_rr) the merge also writes
 // sc.s_pair_end [nq * P]: every list's end of candidates, its file's quota.
 int enqueue_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, const float *d_queries, uint32_t nq, uint32_t nprobe,
-                  uint64_t max_candidates, const pqv::MergeArgs &pm, uint32_t *zero_u32, uint32_t zero_n, hipStream_t stream) {
+                  uint64_t max_candidates, const pqv::MergeArgs &pm, uint32_t *zero_u32, uint32_t zero_n, hipStream_t stream,
+                  int metric = PQV_L2SQ_REF4) {
     using namespace pqv;
     uint64_t *keys = const_cast<uint64_t *>(pm.part_keys);
     uint32_t *vals = const_cast<uint32_t *>(pm.part_vals);
@@ -3510,6 +3514,10 @@ int enqueue_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, const f
         pa.max_pos = ~0ull; pa.metric = PQV_L2SQ_REF4;   // find_closest_centroids always uses index.rs:461
         pa.part_keys = keys; pa.part_vals = vals;
         pa.zero_u32 = zero_u32; pa.zero_n = zero_n;
+        if (metric == PQV_DOT) {     // centroids ranked by (dist, id): the merges below use the keys for their order only
+            pa.metric = PQV_DOT;
+            HIP_TRY(launch_dot_stream(pa, nullptr, STREAM_TOPK, stream));
+        } else
         HIP_TRY(launch_stream(pa, STREAM_TOPK, stream));
         if (s->n_files) s->counters.kernel_launches += 2;
     }
@@ -3656,7 +3664,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         quant_done = pq_args.n_pairs != 0;
         HIP_TRY(pqv::launch_probe_single(pr, pm, sc.s_ticket.as<uint32_t>(), quant_done ? &pq_args : nullptr, stream));
     } else {
-        if (int rc = enqueue_probe(s, sc, p, d_queries, nq, nprobe, max_candidates, pm, pair_u32, zero_n, stream)) return rc;
+        if (int rc = enqueue_probe(s, sc, p, d_queries, nq, nprobe, max_candidates, pm, pair_u32, zero_n, stream, metric)) return rc;
     }
     const uint64_t *pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
 
@@ -3891,6 +3899,8 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         if (mask) {
             HIP_TRY(launch_filtered_stream(ra, mask, s->d_stats.as<unsigned long long>(), pm.n_cand, STREAM_TOPK, stream,
                                            distinct ? sc.s_part_grp.as<int64_t>() : nullptr));
+        } else if (metric == PQV_DOT) {
+            HIP_TRY(launch_dot_stream(ra, nullptr, STREAM_TOPK, stream));
         } else {
             HIP_TRY(launch_stream(ra, STREAM_TOPK, stream));
         }
@@ -3923,6 +3933,10 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         fm.part_flags = sc.s_part_flags.as<uint8_t>();       // row stride: (n_part + 3) / 4 * 4 == n_part (a multiple of 4 waves)
     }
     if (use_defer) fm.zero_after = sc.s_nwork.as<uint32_t>();
+    if (metric == PQV_DOT) {     // (keys carry ord(dist): dot_merge_kernel undoes it; no tie flags to raise)
+        if (p.tile) return fail(PQV_ERR_INVALID, "PQV_DOT call on a screened plan");
+        HIP_TRY(launch_dot_merge(fm, stream));
+    } else
     HIP_TRY(launch_merge_final(fm, stream));
     if (ev[3]) HIP_TRY(hipEventRecord(ev[3], stream));
     if (int rc = lane_release(sc, stream)) return rc;
@@ -3934,7 +3948,7 @@ int validate_topk(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");                         // search.rs:67
     if (nprobe == 0) return fail(PQV_ERR_INVALID, "nprobe must be > 0");               // search.rs:72
-    if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ && metric != PQV_COSINE) return fail(PQV_ERR_INVALID, "unknown metric");
+    if (metric != PQV_L2SQ_REF4 && metric != PQV_L2SQ_SEQ && metric != PQV_COSINE && metric != PQV_DOT) return fail(PQV_ERR_INVALID, "unknown metric");
     return PQV_OK;
 }
 // ... and of the entry points that take queries from the host (pqv_topk, pqv_range_search with k = 1, pqv_probe with k = 1 and
@@ -3951,6 +3965,14 @@ int validate_query(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metri
 // that limit (topk_unbounded), the asynchronous device entry points report it
 bool beyond_kernel_lists(const pqv_searcher *s, uint32_t k_lists, uint32_t nprobe) {
     return k_lists > 1024 || probe_count(s, nprobe) > 1024;
+}
+// PQV_DOT (pqv.h): every entry point works within the kernels' lists, and keyed / distinct calls do not take it.  Checked behind
+// validate_topk, before any device work.
+int dot_checks(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric, const MaskView *mask) {
+    if (metric != PQV_DOT) return PQV_OK;
+    if (mask && (mask->keys || mask->group)) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
+    if (beyond_kernel_lists(s, k, nprobe)) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT takes k <= 1024 and at most 1024 probed lists per query");
+    return PQV_OK;
 }
 
 }  // namespace
@@ -4220,6 +4242,7 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
                                void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                void *d_tie_flags, void *hip_stream, const MaskView *mask = nullptr) {
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (int rc = dot_checks(s, k, nprobe, metric, mask)) return rc;
     if (int rc = table_max_candidates(s, max_candidates)) return rc;
     if (d_tie_flags && k > 1023) return fail(PQV_ERR_UNSUPPORTED, "tie flags need a runner-up entry: k <= 1023");
     if (beyond_kernel_lists(s, k, nprobe))
@@ -4248,7 +4271,8 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
     if (int rc = lane_acquire(s, stream, &lane)) return rc;
     LaneGuard lane_guard{*lane, stream};
     // with flags the kernels carry one extra merged entry (the runner-up), exactly as pqv_topk does
-    const int rc = enqueue_topk(s, static_cast<const float *>(d_queries), nq, d_tie_flags ? k + 1 : k, k, nprobe, max_candidates,
+    // (PQV_DOT: no runner-up -- dot_merge_kernel writes the flags with zeros)
+    const int rc = enqueue_topk(s, static_cast<const float *>(d_queries), nq, (d_tie_flags && metric != PQV_DOT) ? k + 1 : k, k, nprobe, max_candidates,
                                 metric, sqrt_out, static_cast<uint32_t *>(d_row_idx),
                                 static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
                                 static_cast<uint64_t *>(d_n_candidates), static_cast<uint32_t *>(d_tie_flags), stream, *lane, mask);
@@ -4273,6 +4297,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                         uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates, const MaskView *mask = nullptr) {
     if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
+    if (int rc = dot_checks(s, k, nprobe, metric, mask)) return rc;
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
     if (int rc = use_device(s->device)) return rc;
@@ -4286,12 +4311,14 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     // One extra merged entry (the runner-up) lets the merge kernel see ties at the k-th
     // distance; queries it flags are replayed through the exact heap (replay_query_exact).
     // (k == UINT32_MAX -- "keep everything": the reference takes any NonZeroUsize -- must not wrap to a plan with k = 0)
-    const uint32_t k_int = k >= 1024u ? k : k + 1;
+    // (PQV_DOT: no runner-up, no replay -- the order is (dist, position) and the flags come back zero; its limits were checked above)
+    const bool dot = metric == PQV_DOT;
+    const uint32_t k_int = (dot || k >= 1024u) ? k : k + 1;
     Scratch *lane = nullptr;
     if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
     Scratch &sc = *lane;
     LaneGuard lane_guard{sc, s->stream};
-    if (k >= 1024u || beyond_kernel_lists(s, k_int, nprobe)) {
+    if (!dot && (k >= 1024u || beyond_kernel_lists(s, k_int, nprobe))) {
         const int rc = topk_unbounded(s, sc, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates, mask);
         const int rc2 = lane_release(sc, s->stream);
         return rc ? rc : rc2;
@@ -4491,7 +4518,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             MergeArgs pm{};
             if (int rc = probe_merge_args(s, sc, p, b, max_candidates, pm)) return rc;
             pm.stats = mask ? nullptr : s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
-            if (int rc = enqueue_probe(s, sc, p, d_q, b, nprobe, max_candidates, pm, nullptr, 0, st)) return rc;
+            if (int rc = enqueue_probe(s, sc, p, d_q, b, nprobe, max_candidates, pm, nullptr, 0, st, metric)) return rc;
             launches += 2;
         } else {
             // find_closest_centroids without the kernels' list limit (as topk_unbounded)
@@ -4520,6 +4547,8 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             if (mask) {      // (the considered rows are counted by the kernel; candidate_rows too unless the host probe counted it above)
                 HIP_TRY(launch_filtered_stream(ra, &sub, s->d_stats.as<unsigned long long>(), wide_probe ? nullptr : sc.s_ncand.as<uint64_t>(),
                                                STREAM_RANGE, st));
+            } else if (metric == PQV_DOT) {
+                HIP_TRY(launch_dot_stream(ra, nullptr, STREAM_RANGE, st));
             } else
             HIP_TRY(launch_stream(ra, STREAM_RANGE, st));
             ++launches;
@@ -4571,6 +4600,10 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
                 HIP_TRY(launch_range_sort_large(sa, max_n, &nl, st));
                 launches += nl;
             }
+            if (metric == PQV_DOT) {     // (the sort kernels wrote the keys' ord halves: back to dist in place)
+                HIP_TRY(launch_dot_finish(sc.s_rout_dist.as<float>(), tot, st));
+                ++launches;
+            }
             if (e[3]) HIP_TRY(hipEventRecord(e[3], st));
             HIP_TRY(hipMemcpyAsync(rows.get() + lims[q0], sc.s_rout_rows.p, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(dist.get() + lims[q0], sc.s_rout_dist.p, tot * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -4590,6 +4623,8 @@ static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, ui
                                  uint64_t **lims_out, uint32_t **rows_out, float **dist_out, uint64_t *n_within,
                                  uint64_t *n_candidates, const MaskView *mask = nullptr) {
     if (int rc = validate_query(s, 1, nprobe, metric, max_candidates, query_len)) return rc;
+    if (int rc = dot_checks(s, 1, nprobe, metric, mask)) return rc;
+    if (metric == PQV_DOT) sqrt_out = 0;      // (ignored: the range_* kernels run as order-only machinery)
     if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
     if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
     if (nq && !queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
@@ -5068,6 +5103,7 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
                                   uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
                                   int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
     if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
+    if (int rc = dot_checks(s, k, nprobe, metric, mv)) return rc;
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
     if (int rc = use_device(s->device)) return rc;
@@ -5194,6 +5230,7 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
                                       char *buf, size_t len) {
     if (!s || !buf || !len) return fail(PQV_ERR_INVALID, "searcher/buf must not be NULL");
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (int rc = dot_checks(s, k, nprobe, metric, nullptr)) return rc;
     if (metric == PQV_COSINE) {
         // the L2 dispatch of the cosine searcher (before the first cosine call: of this one, over the raw rows)
         const pqv_searcher *c;
@@ -5217,7 +5254,7 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
         std::snprintf(tb, sizeof tb, "table of %u files, %u lists per query (nprobe %u per file); probe: %s + merge_probe_seg_kernel (per file), "
                       "no fused single-query probe (pair sort instead); ", s->n_files, probe_count(s, nprobe), nprobe,
                       beyond_kernel_lists(s, k, nprobe) ? "stream_kernel (STREAM_DIST) + a stable sort per file on the host"
-                      : pt.probe_rows ? "probe_rows_kernel" : "stream_kernel with one list per file");
+                      : pt.probe_rows ? "probe_rows_kernel" : metric == PQV_DOT ? "dot_stream_kernel with one list per file" : "stream_kernel with one list per file");
     }
     if (beyond_kernel_lists(s, k, nprobe)) {
         std::snprintf(buf, len, "%spqv_topk only: stream_kernel (STREAM_DIST) for every centroid and candidate distance, selection by the "
@@ -5239,6 +5276,10 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
                       "%u rows per block", p.seed_rows, p.filter_rows_per_block);
     else if (p.tile)
         std::snprintf(t, sizeof t, "tile_rerank_kernel: exact arithmetic, 16-query groups, %u rows per block", p.rr_rows_per_block);
+    else if (metric == PQV_DOT)
+        std::snprintf(t, sizeof t, "PQV_DOT: dot_stream_kernel (a masked call: its WIN = 1 form over the mask's set positions): one candidate "
+                      "stream per (query, probed list), %u rows per block, keys (ord(dist) << 32) | position; dot_merge_kernel (range search: "
+                      "range_* sort kernels + dot_finish_kernel)", p.rr_rows_per_block);
     else
         std::snprintf(t, sizeof t, "stream_kernel: one candidate stream per (query, probed list), %u rows per block", p.rr_rows_per_block);
     if (p.tile && p.filter && p.quad && p.wide_width) {
@@ -5281,7 +5322,12 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
                           defp ? "true" : "false");
         }
     }
-    std::snprintf(buf, len, "%s%s; centroid probe: %s%s", tb, t, p.probe_rows ? "probe_rows_kernel (a lane per centroid)" : "stream_kernel", kn);
+    if (metric == PQV_DOT) {
+        const bool al = (s->sdim % 4) == 0;
+        std::snprintf(kn, sizeof kn, " | kernels: dot_stream_kernel<%d, %d, 0, %s, 0>; dot_merge_kernel<%d>",
+                      (al && (s->sdim / 4) % 64 == 0) ? 64 : 32, k <= 64 ? 1 : k <= 256 ? 4 : 16, al ? "true" : "false", k <= 64 ? 1 : k <= 256 ? 4 : 16);
+    }
+    std::snprintf(buf, len, "%s%s; centroid probe: %s%s", tb, t, p.probe_rows ? "probe_rows_kernel (a lane per centroid)" : metric == PQV_DOT ? "dot_stream_kernel" : "stream_kernel", kn);
     return PQV_OK;
 }
 extern "C" int pqv_searcher_describe(const pqv_searcher *s, uint32_t nq, uint32_t k, uint32_t nprobe, int metric,

@@ -298,6 +298,15 @@ __device__ __forceinline__ uint32_t block_kth_u32(F get, uint32_t n, uint32_t k,
     return prefix;
 }
 
+// Row masks (kernels_mask.hip, kernels_dot.hip): a position image is a bitset over LIST POSITIONS.
+// the 64 bits of a position image from position p on (the image has one word of padding behind the last position: wi + 1 is always in range)
+__device__ __forceinline__ uint64_t image_window(const uint64_t *bits, uint64_t p) {
+    const uint64_t wi = p >> 6;
+    const uint32_t sh = (uint32_t)(p & 63u);
+    const uint64_t lo = bits[wi], hi = bits[wi + 1];
+    return sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
+}
+
 // ------------------------------------------------------------------------------------
 // 16-byte row loads.  ALIGNED: dim % 4 == 0 so every row starts 16-B aligned.
 // ------------------------------------------------------------------------------------

@@ -83,6 +83,19 @@ struct MaskedArgs {
 // arithmetic, keys and output formats; a.probe / a.list_off / a.cand_base are required.
 hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s);
 
+// ---- inner-product search (kernels_dot.hip; pqv.h: PQV_DOT) ----------------------------------------------------------------
+// launch_stream's / launch_masked_stream's STREAM_TOPK / STREAM_RANGE pass with dist = 0.0f - s(q, x), s the 4-grouped chain over
+// products, and keys (ord(dist) << 32) | candidate position (ord: the order-preserving map of signed f32 bits to u32).  ma ==
+// nullptr: every position (a.probe == nullptr: the single list, the centroid probe of a DOT call); else the mask's set positions.
+// A hit of STREAM_RANGE: dist <= radius (sqrt_out is not read).  zero_u32 must be unset.
+hipError_t launch_dot_stream(const StreamArgs &a, const MaskedArgs *ma, StreamMode mode, hipStream_t s);
+struct MergeArgs;
+// the fold of those per-wave lists, one wave per query (dot_merge_kernel): part_keys / part_vals / nq / n_part / k_part / k / k_out /
+// ids / row_idx / dist / n_found as launch_merge_final reads them; dist = ord undone, tie_flag (where given) written with zeros
+hipError_t launch_dot_merge(const MergeArgs &a, hipStream_t s);
+// range write-out: dist[i] held ord bits (the range_* kernels with sqrt_out 0), now the distance; i < n
+hipError_t launch_dot_finish(float *dist, uint64_t n, hipStream_t s);
+
 // ---- per-query key filters (kernels_mask.hip; pqv.h: pqv_row_keys) ------------------------------------------------------
 // A key column on the device is laid out by LIST POSITION like a mask: key_pos[p] = column[ids[p]] at the column's own width
 // (elem_size 4 or 8), and -- where the column has validity bytes -- valid_pos, a bitset in exactly the mask image's format.

@@ -11,3 +11,4 @@
 #include "kernels_mask.hip"
 #include "kernels_predicate.hip"
 #include "kernels_distinct.hip"
+#include "kernels_dot.hip"

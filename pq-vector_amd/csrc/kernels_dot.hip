@@ -1,0 +1,366 @@
+// kernels_dot.hip -- gfx950 kernels of PQV_DOT (pqv.h): inner-product search.  The distance of a candidate is the negated
+// similarity, dist = 0.0f - s(q, x), with s the reference's 4-grouped chain (index.rs:461-480) over PRODUCTS instead of squared
+// differences:
+//     t_g = ((q0 x0 + q1 x1) + q2 x2) + q3 x3 per full group of four dims, sum += t_g in ascending g, then the dim % 4 tail element
+//     by element -- every operation a rounded f32 one (the unit is built with -ffp-contract=off like the others).
+// sum starts at +0.0f and x + y is -0.0f only when both are, so sum is never -0.0f and a zero dist is always +0.0f.
+// Distances are signed, so the keys are (ord(dist) << 32) | candidate position with ord the usual order-preserving map of f32 bits
+// to u32 (negative: all bits flipped; else: the sign bit set): ascending keys = ascending (dist, position).
+//   dot_stream_kernel   stream_kernel's grid, tile and chain structure (kernels_probe.hip) with that partial and that key;
+//                       WIN = 0 walks every position of the wave's range, WIN = 1 the set bits of a row mask's image exactly as
+//                       masked_stream_kernel does (kernels_mask.hip).  Also the centroid probe of a DOT call (the centroid matrix as
+//                       one list, or a table's per-file segments): merge_kernel<S, true> / merge_probe_seg_kernel use keys for
+//                       their order only.
+//   dot_merge_kernel    the fold of the per-wave lists, one wave per query: rows, dist (ord undone), n_found; tie flags zeroed
+//   dot_finish_kernel   range search: the range_* sort kernels run as order-only machinery (sqrt_out 0) and write the keys' high
+//                       halves; this turns them back into dist in place
+#include "device_common.hpp"
+
+namespace pqv {
+
+namespace {
+
+__device__ __forceinline__ uint32_t dot_ord(float d) {
+    const uint32_t b = __float_as_uint(d);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float dot_unord(uint32_t o) {
+    return __uint_as_float((o >> 31) ? o ^ 0x80000000u : ~o);
+}
+
+#define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
+
+// The similarity chain of one 64-row tile: lane r returns s(q, row r) for r < nvalid (my_srow: storage row of tile row `lane`,
+// clamped so that every address is in range).  stream_kernel's chunk loop with products in place of squared differences.
+template <int CG, bool ALIGNED>
+__device__ __forceinline__ float dot_tile(const StreamArgs &a, float *lds, const float *qv, uint32_t my_srow, uint32_t nvalid, int lane) {
+    constexpr int RPI = 64 / CG;        // rows per load instruction
+    constexpr int NI = CG;              // load instructions per 64-row tile
+    constexpr int NB = 8;               // loads in flight per lane
+    static_assert(NI % NB == 0, "NI must be a multiple of NB");
+    const uint32_t dim = a.dim;
+    const uint32_t G = dim >> 2;
+    const uint32_t tail = dim & 3u;
+    const int g_in = lane % CG;      // my float4 group inside a chunk
+    const int row_in = lane / CG;    // my row inside a load instruction
+
+    float sum = 0.0f;
+    for (uint32_t c0 = 0; c0 < G; c0 += CG) {
+        const uint32_t ng = (G - c0 < (uint32_t)CG) ? (G - c0) : (uint32_t)CG;
+        const bool gvalid = (uint32_t)g_in < ng;
+        const uint32_t goff = (c0 + (gvalid ? g_in : 0)) * 4;
+        const float4 qq = load4<ALIGNED>(qv + goff);
+
+#pragma unroll 1
+        for (int ib = 0; ib < NI; ib += NB) {
+            float4 x[NB];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                uint32_t rr = (uint32_t)((ib + u) * RPI + row_in);
+                if (rr >= nvalid) rr = nvalid - 1;
+                const uint32_t srow = (uint32_t)__shfl((int)my_srow, (int)rr, 64);
+                x[u] = load4<ALIGNED>(a.mat + (uint64_t)srow * dim + goff);
+            }
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                const int rr = (ib + u) * RPI + row_in;
+                float t = qq.x * x[u].x + qq.y * x[u].y;
+                t = t + qq.z * x[u].z;
+                t = t + qq.w * x[u].w;
+                if (gvalid) LDS_AT(g_in, rr) = t;
+            }
+        }
+        wave_lds_fence();
+        uint32_t e = 0;
+        for (; e + 8 <= ng; e += 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = LDS_AT(e + u, lane);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) sum = sum + v[u];
+        }
+        for (; e < ng; ++e) sum = sum + LDS_AT(e, lane);
+        wave_lds_fence();
+    }
+    if (tail) {
+        const float *xr = a.mat + (uint64_t)my_srow * dim + (uint64_t)G * 4;
+        const float *qt = qv + (uint64_t)G * 4;
+        for (uint32_t e = 0; e < tail; ++e) sum = sum + qt[e] * xr[e];
+    }
+    return sum;
+}
+
+#undef LDS_AT
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------
+// dot_stream_kernel
+//
+// grid = (blocks_per_list, nprobe | nj | 1, nq); block = 256 threads = 4 independent waves, each owning a contiguous run of
+// positions of one inverted list (probe == nullptr, WIN = 0 only: of the single list [single_begin, single_end)).
+// WIN = 0: the run is walked in 64-row tiles.  WIN = 1: in 64-position windows of the mask's image (two words, funnel-shifted),
+// clipped at the candidate cap; the set positions are compacted through the first 128 words of the wave's idle tile area into a
+// queue whose first 64 entries live in one register, and a tile runs whenever 64 are queued and once more at the end -- a row the
+// mask excludes is never loaded, positions stay the unmasked ones, and the waves add what they evaluated to embeddings_fetched
+// (the (0, 0) block of a query adds n_cand[q] to candidate_rows), as masked_stream_kernel does.
+// Outputs: stream_kernel's per-wave partial lists (STREAM_TOPK) / hit segments (STREAM_RANGE: hit iff dist <= radius).
+// ------------------------------------------------------------------------------------
+template <int CG, int S, int MODE, bool ALIGNED, int WIN>
+__global__ __launch_bounds__(256) void dot_stream_kernel(const StreamArgs a, const MaskedArgs ma) {
+    static_assert(MODE == STREAM_TOPK || MODE == STREAM_RANGE, "top-k lists or range hits");
+    static_assert(CG * 64 >= 128, "the compaction needs 128 words of the tile area");
+    __shared__ float lds_all[4 * CG * 64];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    float *lds = lds_all + wave * (CG * 64);
+
+    const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
+    uint64_t lbeg, lend, cbase, lim = a.max_pos;
+    if (WIN != 0 || a.probe) {
+        const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
+        lbeg = a.list_off[c];
+        lend = a.list_off[c + 1];
+        cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
+        if (a.pair_end) lim = a.pair_end[(uint64_t)q * a.nprobe + j];
+    } else {
+        lbeg = a.single_begin;
+        lend = a.single_end;
+        cbase = 0;
+    }
+    uint64_t len = lend - lbeg;
+    if constexpr (WIN != 0) {
+        // positions at or beyond the cap are no candidates: the walk ends there (their bits are never looked at)
+        const uint64_t room = lim > cbase ? lim - cbase : 0;
+        if (len > room) len = room;
+    }
+    const uint64_t wrows = a.rows_per_block / 4;
+    const uint64_t r0 = (uint64_t)blockIdx.x * a.rows_per_block + (uint64_t)wave * wrows;
+    uint64_t r1 = r0 + wrows;
+    if (r1 > len) r1 = len;
+
+    const float *qv = a.queries + (uint64_t)q * a.dim;
+
+    WaveTopk<S> tk;
+    if constexpr (MODE == STREAM_TOPK) tk.init();
+
+    // what a tile's rows become: lane `lane` holds row my_srow at candidate position pos
+    auto emit = [&](float sum, bool valid, uint64_t pos, uint32_t my_srow) {
+        const float dist = 0.0f - sum;
+        const uint64_t key = ((uint64_t)dot_ord(dist) << 32) | (uint64_t)(uint32_t)pos;
+        if constexpr (MODE == STREAM_TOPK) {
+            tk.offer(valid ? key : KEY_EMPTY, my_srow, a.k, lane);
+        } else {
+            // the wave's hits go to the query's segment in one block: ballot, rank from mbcnt, one atomicAdd per wave
+            const bool hit = valid && dist <= a.radius;                // (a NaN distance never compares true)
+            const uint64_t m = __ballot(hit);
+            if (m) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(a.hit_cnt + q, (uint32_t)__popcll(m));
+                base = (uint32_t)__shfl((int)base, 0, 64);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                if (hit) {
+                    const uint64_t o = (uint64_t)q * a.seg_stride + base + rank;
+                    a.hit_keys[o] = key;
+                    a.hit_vals[o] = my_srow;
+                }
+            }
+        }
+    };
+
+    if constexpr (WIN == 0) {
+        for (uint64_t t0 = r0; t0 < r1; t0 += 64) {
+            const uint32_t nvalid = (r1 - t0 < 64) ? (uint32_t)(r1 - t0) : 64u;
+            const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
+            const uint64_t lpos = lbeg + t0 + lrow;
+            const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
+            const float sum = dot_tile<CG, ALIGNED>(a, lds, qv, my_srow, nvalid, lane);
+            const uint64_t pos = cbase + t0 + (uint64_t)lane;
+            emit(sum, (uint32_t)lane < nvalid && pos < lim, pos, my_srow);
+        }
+    } else {
+        uint32_t *cq = reinterpret_cast<uint32_t *>(lds);          // compaction scratch: 128 entries
+#ifdef PQV_PROFILE_PHASES
+        unsigned long long *st = ma.stats;
+#else
+        unsigned long long *st = ma.stats ? ma.stats + 8 + 16 * (q % STATS_SLOTS) : nullptr;
+#endif
+        if (ma.n_cand && st && blockIdx.x == 0 && j == 0 && threadIdx.x == 0) atomicAdd(&st[2], (unsigned long long)ma.n_cand[q]);
+
+        uint32_t pend = 0;      // queue entry `lane` (a list offset, < 2^32 as every candidate position), meaningful for lane < qn
+        uint32_t qn = 0;        // queued entries, < 64 between two windows (wave-uniform)
+        uint32_t n_eval = 0;    // rows this wave evaluated (wave-uniform)
+        for (uint64_t w0 = r0;; w0 += 64) {
+            const bool flush = w0 >= r1;        // past the range: what is left in the queue is the last tile
+            uint32_t nvalid = 0;                // rows of the chain tile this turn runs (0: none)
+            uint32_t my_r = 0;                  // list offset of tile row `lane`
+            if (!flush) {
+                uint64_t win = image_window(ma.bits, lbeg + w0);
+                if (r1 - w0 < 64) win &= (1ull << (r1 - w0)) - 1ull;
+                const uint32_t cnt = (uint32_t)__popcll(win);
+                if (cnt == 0) continue;
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(win >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)win, 0u));
+                if ((uint32_t)lane < qn) cq[lane] = pend;
+                if ((win >> lane) & 1ull) cq[qn + rank] = (uint32_t)(w0 + (uint64_t)lane);
+                wave_lds_fence();
+                const uint32_t total = qn + cnt;                   // <= 127
+                const uint32_t first = cq[lane];
+                const uint32_t over = cq[64 + lane];
+                wave_lds_fence();
+                if (total >= 64) {
+                    my_r = first; nvalid = 64u;
+                    pend = over; qn = total - 64;
+                } else {
+                    pend = first; qn = total;
+                }
+            } else if (qn) {
+                const uint32_t last = (uint32_t)__shfl((int)pend, (int)(qn - 1), 64);
+                my_r = (uint32_t)lane < qn ? pend : last;         // (clamped: every address in range)
+                nvalid = qn; qn = 0;
+            }
+            if (nvalid) {
+                n_eval += nvalid;
+                const uint64_t lpos = lbeg + my_r;
+                const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
+                const float sum = dot_tile<CG, ALIGNED>(a, lds, qv, my_srow, nvalid, lane);
+                emit(sum, (uint32_t)lane < nvalid, cbase + my_r, my_srow);           // (pos < lim by the clamp of the walk)
+            }
+            if (flush) break;
+        }
+        if (st && n_eval && lane == 0) atomicAdd(&st[3], (unsigned long long)n_eval);
+    }
+
+    if constexpr (MODE == STREAM_TOPK) {
+        const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
+        const uint32_t pi = (j * a.blocks_per_list + blockIdx.x) * 4 + wave;
+        const uint64_t base = ((uint64_t)q * n_part + pi) * a.k;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const uint32_t e = s * 64 + lane;
+            if (e < a.k) {
+                a.part_keys[base + e] = tk.key[s];
+                a.part_vals[base + e] = tk.val[s];
+            }
+        }
+    }
+}
+
+template <int CG, int S, int MODE, bool ALIGNED, int WIN>
+static hipError_t launch_dot_t(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
+    dim3 grid(a.blocks_per_list, !a.probe ? 1u : MODE == STREAM_RANGE ? a.nj : a.nprobe, a.nq);
+    hipLaunchKernelGGL((dot_stream_kernel<CG, S, MODE, ALIGNED, WIN>), grid, dim3(256), 0, s, a, ma);
+    return hipGetLastError();
+}
+
+// the chunk choice of launch_stream (the chain order does not depend on it)
+template <int S, int MODE, int WIN>
+static hipError_t launch_dot_s(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
+    const bool aligned = (a.dim % 4) == 0;
+    const uint32_t G = a.dim / 4;
+    if (!aligned) return launch_dot_t<32, S, MODE, false, WIN>(a, ma, s);
+    if (G >= 64 && G % 64 == 0) return launch_dot_t<64, S, MODE, true, WIN>(a, ma, s);
+    return launch_dot_t<32, S, MODE, true, WIN>(a, ma, s);
+}
+
+template <int WIN>
+static hipError_t launch_dot_w(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s) {
+    if (a.nq == 0 || a.blocks_per_list == 0) return hipSuccess;
+    if (mode == STREAM_RANGE) {
+        if (a.nj == 0) return hipSuccess;
+        if (!a.probe) return hipErrorInvalidValue;
+        return launch_dot_s<1, STREAM_RANGE, WIN>(a, ma, s);
+    }
+    if (mode != STREAM_TOPK) return hipErrorInvalidValue;
+    if (a.probe && a.nprobe == 0) return hipSuccess;
+    if (a.k <= 64) return launch_dot_s<1, STREAM_TOPK, WIN>(a, ma, s);
+    if (a.k <= 256) return launch_dot_s<4, STREAM_TOPK, WIN>(a, ma, s);
+    if (a.k <= 1024) return launch_dot_s<16, STREAM_TOPK, WIN>(a, ma, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_dot_stream(const StreamArgs &a, const MaskedArgs *ma, StreamMode mode, hipStream_t s) {
+    if (a.zero_u32 || (a.rows_per_block % 256) != 0 || a.rows_per_block == 0) return hipErrorInvalidValue;
+    if (a.probe && (!a.list_off || !a.cand_base)) return hipErrorInvalidValue;
+    if (!ma) return launch_dot_w<0>(a, MaskedArgs{}, mode, s);
+    if (!ma->bits || !a.probe) return hipErrorInvalidValue;
+    return launch_dot_w<1>(a, *ma, mode, s);
+}
+
+// ------------------------------------------------------------------------------------
+// dot_merge_kernel: one wave per query folds the per-wave lists [n_part][k_part] into the k smallest keys and writes the first
+// k_out: reported rows, dist = the key's high half with ord undone, 0xFFFFFFFF / +inf past n_found; tie_flag[q] = 0 (there is
+// no reference heap whose history a tie could depend on).
+// ------------------------------------------------------------------------------------
+template <int S>
+__global__ __launch_bounds__(64) void dot_merge_kernel(const MergeArgs a) {
+    const int lane = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    WaveTopk<S> tk;
+    tk.init();
+    const uint64_t total = (uint64_t)a.n_part * a.k_part;
+    const uint64_t *pk = a.part_keys + (uint64_t)q * total;
+    const uint32_t *pv = a.part_vals + (uint64_t)q * total;
+    // pre-filter (k <= 64): the k-th smallest of the 64 lane minima bounds the k-th smallest overall, so only keys at or below it
+    // reach the serial insertion (merge_kernel's cut)
+    uint64_t cut = KEY_EMPTY;
+    if (S == 1 && total > 128) {
+        uint64_t lmin = KEY_EMPTY;
+        for (uint64_t i = lane; i < total; i += 64) { const uint64_t key = pk[i]; lmin = key < lmin ? key : lmin; }
+        uint32_t dummy = 0;
+        bitonic_sort64(lmin, dummy, lane);
+        cut = readlane_u64(lmin, (int)a.k - 1);
+    }
+    for (uint64_t i = 0; i < total; i += 64) {
+        const uint64_t idx = i + lane;
+        uint64_t key = KEY_EMPTY;
+        uint32_t val = 0xFFFFFFFFu;
+        if (idx < total) { key = pk[idx]; val = pv[idx]; }
+        if (key > cut) key = KEY_EMPTY;
+        if (__ballot(key != KEY_EMPTY) != 0ull) tk.offer(key, val, a.k, lane);
+    }
+    const uint32_t k_out = a.k_out ? a.k_out : a.k;
+    uint32_t found = 0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const uint32_t e = s * 64 + lane;
+        const bool have = e < a.k && tk.key[s] != KEY_EMPTY;
+        found += (uint32_t)__popcll(__ballot(have && e < k_out));
+        if (e < k_out) {
+            uint32_t row = 0xFFFFFFFFu;
+            float d = INFINITY;
+            if (have) {
+                row = a.ids ? a.ids[tk.val[s]] : tk.val[s];
+                d = dot_unord((uint32_t)(tk.key[s] >> 32));
+            }
+            a.row_idx[(uint64_t)q * k_out + e] = row;
+            a.dist[(uint64_t)q * k_out + e] = d;
+        }
+    }
+    if (a.n_found && lane == 0) a.n_found[q] = found;
+    if (a.tie_flag && lane == 0) a.tie_flag[q] = 0u;
+}
+
+hipError_t launch_dot_merge(const MergeArgs &a, hipStream_t s) {
+    if (a.nq == 0) return hipSuccess;
+    if (a.cand_keys || a.cand_lb || a.part_flags || a.k == 0 || (a.k_out ? a.k_out : a.k) > a.k) return hipErrorInvalidValue;
+    if (a.k <= 64) hipLaunchKernelGGL(dot_merge_kernel<1>, dim3(a.nq), dim3(64), 0, s, a);
+    else if (a.k <= 256) hipLaunchKernelGGL(dot_merge_kernel<4>, dim3(a.nq), dim3(64), 0, s, a);
+    else if (a.k <= 1024) hipLaunchKernelGGL(dot_merge_kernel<16>, dim3(a.nq), dim3(64), 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// dist[i] = the distance whose ord bits dist[i] holds (range search write-out), i < n
+__global__ __launch_bounds__(256) void dot_finish_kernel(float *dist, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+        dist[i] = dot_unord(reinterpret_cast<const uint32_t *>(dist)[i]);
+}
+
+hipError_t launch_dot_finish(float *dist, uint64_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(dot_finish_kernel, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, dist, n);
+    return hipGetLastError();
+}
+
+}  // namespace pqv

@@ -109,14 +109,6 @@ hipError_t launch_key_layout(const void *values, const uint8_t *valid, uint32_t 
 template <int WIN> struct WinArgs { using type = KeyedArgs; };
 template <> struct WinArgs<0> { using type = MaskedArgs; };
 
-// the 64 bits of a position image from position p on (the image has one word of padding behind the last position: wi + 1 is always in range)
-__device__ __forceinline__ uint64_t image_window(const uint64_t *bits, uint64_t p) {
-    const uint64_t wi = p >> 6;
-    const uint32_t sh = (uint32_t)(p & 63u);
-    const uint64_t lo = bits[wi], hi = bits[wi + 1];
-    return sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
-}
-
 template <int CG, int S, int MODE, bool SEQ, bool ALIGNED, int WIN = 0>
 __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, const typename WinArgs<WIN>::type ma) {
     constexpr int RPI = 64 / CG;        // rows per load instruction

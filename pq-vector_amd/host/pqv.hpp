@@ -201,6 +201,12 @@ public:
     TopkBuilder &where(const RowMask &m) { mask_ = &m; return *this; }
     TopkBuilder &k(uint32_t v) { if (!v) throw Error(PQV_ERR_INVALID, "k must be > 0"); k_ = v; return *this; }
     TopkBuilder &nprobe(uint32_t v) { if (!v) throw Error(PQV_ERR_INVALID, "nprobe must be > 0"); nprobe_ = v; return *this; }
+    // PQV_L2SQ_REF4 (default: sqrt(d2) as the reference returns it), PQV_COSINE (0.5 d2 of the normalised vectors) or PQV_DOT
+    // (-(q.x), smallest first); see include/pqv.h
+    TopkBuilder &metric(int m) {
+        if (m != PQV_L2SQ_REF4 && m != PQV_COSINE && m != PQV_DOT) throw Error(PQV_ERR_INVALID, "unknown metric");
+        metric_ = m; return *this;
+    }
     std::vector<SearchResult> search() const {
         if (!k_) throw Error(PQV_ERR_INVALID, "k must be set");              // search.rs:77
         if (!nprobe_) throw Error(PQV_ERR_INVALID, "nprobe must be set");    // search.rs:78
@@ -209,10 +215,10 @@ public:
         uint32_t found = 0;
         if (mask_)
             check(pqv_topk_masked(s_.get(), mask_->get(), query_.data(), 1, static_cast<uint32_t>(query_.size()), *k_, *nprobe_, 0,
-                                  PQV_L2SQ_REF4, 1, rows.data(), dist.data(), &found, nullptr));
+                                  metric_, 1, rows.data(), dist.data(), &found, nullptr));
         else
         check(pqv_topk(s_.get(), query_.data(), 1, static_cast<uint32_t>(query_.size()), *k_, *nprobe_, 0,
-                       PQV_L2SQ_REF4, 1, rows.data(), dist.data(), &found, nullptr));
+                       metric_, 1, rows.data(), dist.data(), &found, nullptr));
         std::vector<SearchResult> out;
         for (uint32_t i = 0; i < found; ++i) out.push_back({rows[i], dist[i]});
         return out;
@@ -221,6 +227,7 @@ private:
     const Searcher &s_;
     const std::vector<float> &query_;
     std::optional<uint32_t> k_, nprobe_;
+    int metric_ = PQV_L2SQ_REF4;
     const RowMask *mask_ = nullptr;
 };
 
