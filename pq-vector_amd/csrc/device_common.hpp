@@ -110,7 +110,8 @@ __device__ __forceinline__ uint32_t buf_ld4(__amdgpu_buffer_rsrc_t r, uint32_t l
 #define PQV_REPF 1             // wide_filter_kernel: the operand prefetch is issued again behind exact evaluations in mid-wave (stages dead across them)
 #endif
 #ifndef PQV_NA_REG
-#define PQV_NA_REG 0           // regular int8 instance: branch-free K loop bodies for quads of 3 / 4 / 5 groups too (124 bytes of spills: off)
+#define PQV_NA_REG 0           // regular int8 instance: branch-free K loop bodies for quads of 3 / 4 / 5 groups too (spilled 124 bytes while every
+                               // accumulator had two register homes; fits since -- 245 VGPRs, no scratch -- and is not measured yet: off)
 #endif
 #ifndef PQV_THR_EVERY
 #define PQV_THR_EVERY 1        // 64-row-tile instances: thresholds re-read behind every n-th tile
@@ -147,6 +148,19 @@ template <int OP>
 __device__ __forceinline__ void mfma_step(i32x4_acc &acc, const float4 q, const float4 x) {
     static_assert(OP == OP_I8, "integer accumulators belong to the int8 form");
     acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_acc, q), __builtin_bit_cast(i32x4_acc, x), acc, 0, 0, 0);
+}
+// The FIRST K step of an accumulator: its start value c0 enters through the C operand, so the accumulator needs no register
+// moves of its own before the loop.  The same operands in the same order as acc = c0 followed by mfma_step: the same bits.
+// (wide_filter_kernel uses the int8 form only; the float form keeps its generic K loop lambdas well-formed)
+template <int OP>
+__device__ __forceinline__ void mfma_step_c(f32x4_acc &acc, const float4 q, const float4 x, const f32x4_acc c0) {
+    acc = c0;
+    mfma_step<OP>(acc, q, x);
+}
+template <int OP>
+__device__ __forceinline__ void mfma_step_c(i32x4_acc &acc, const float4 q, const float4 x, const i32x4_acc c0) {
+    static_assert(OP == OP_I8, "integer accumulators belong to the int8 form");
+    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_acc, q), __builtin_bit_cast(i32x4_acc, x), c0, 0, 0, 0);
 }
 // eight f32 values scaled by a power of two and rounded to f16 (round to nearest even), packed as 16 bytes
 __device__ __forceinline__ float4 pack_f16x8(const float4 lo, const float4 hi, float scale) {

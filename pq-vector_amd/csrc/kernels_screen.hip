@@ -1970,27 +1970,32 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
 
         using acc_t = std::conditional_t<I8, i32x4_acc, f32x4_acc>;
         acc_t acc[NG][TS];
-        if constexpr (I8) {
-            // int8 operands.  x = c + xi / S + e_x and q = c + qi / S + e_q (c = per-dimension mid-range, S one global
-            // scale, xi / qi the int8 images, |e_x| <= rx and |e_q| <= rq stored upper bounds of the residual norms), so
-            //     |q - x| >= |qi - xi| / S - rq - rx        (triangle inequality; |qi - xi|^2 = Nq + Nx - 2 qi.xi EXACTLY)
-            // and a pair whose reference distance could still pass the threshold thr has
-            //     |qi - xi| <= S (sqrt(thr (1 + c)) + rq + R),  R = the largest rx of the tile's rows
-            //     =>  Nq + Nx - 2 dot <= T2 = S^2 (sqrt(thr (1 + c)) + rq + R)^2.
-            // skip  <=>  dot + ceil(-Nx / 2) + ceil((T2 - Nq) / 2) < 0: the row term is the accumulator's START value
-            // (known before the K loop, no threshold in it), the query term one integer add per pair after the loop,
-            // the sign bit the answer.  All roundings go up (never skip wrongly); the contraction itself is exact.
+        // start values, one vector c0[t] per row sub-tile.
+        // int8 operands.  x = c + xi / S + e_x and q = c + qi / S + e_q (c = per-dimension mid-range, S one global
+        // scale, xi / qi the int8 images, |e_x| <= rx and |e_q| <= rq stored upper bounds of the residual norms), so
+        //     |q - x| >= |qi - xi| / S - rq - rx        (triangle inequality; |qi - xi|^2 = Nq + Nx - 2 qi.xi EXACTLY)
+        // and a pair whose reference distance could still pass the threshold thr has
+        //     |qi - xi| <= S (sqrt(thr (1 + c)) + rq + R),  R = the largest rx of the tile's rows
+        //     =>  Nq + Nx - 2 dot <= T2 = S^2 (sqrt(thr (1 + c)) + rq + R)^2.
+        // skip  <=>  dot + ceil(-Nx / 2) + ceil((T2 - Nq) / 2) < 0: the row term is the accumulator's START value
+        // (known before the K loop, no threshold in it), the query term one integer add per pair after the loop,
+        // the sign bit the answer.  All roundings go up (never skip wrongly); the contraction itself is exact.
+        acc_t c0[TS];
 #pragma unroll
-            for (int t = 0; t < TS; ++t) {
-                const int init = -(xn2i[t] >> 1);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g][t] = (i32x4_acc){init, init, init, init};
-            }
-        } else {
+        for (int t = 0; t < TS; ++t) {
+            if constexpr (I8) { const int init = -(xn2i[t] >> 1); c0[t] = (i32x4_acc){init, init, init, init}; }
+            else c0[t] = (f32x4_acc){0.f, 0.f, 0.f, 0.f};
+        }
+        // C0 (the int8 instances): the start value is the C operand of the accumulator's FIRST MFMA (kloop peels the first K
+        // steps) -- TS vectors per tile instead of a register move per accumulator register (4 NG TS).  The float forms copy it:
+        // with the peeled steps their k > 64 instances -- the deferred form reads the accumulators again behind the screen -- do
+        // not fit the register file (f16: 0 -> 80 .. 316 bytes of scratch), and they keep the loop they had.
+        constexpr bool C0 = I8;
+        if constexpr (!C0) {
 #pragma unroll
             for (int g = 0; g < NG; ++g)
 #pragma unroll
-                for (int t = 0; t < TS; ++t) acc[g][t] = (f32x4_acc){0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < TS; ++t) acc[g][t] = c0[t];
         }
 
 #ifdef PQV_PROFILE_PHASES
@@ -2010,17 +2015,30 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
         constexpr int APD = TS == 2 ? PQV_APD_TS2 : PQV_APD;
         // `full`: std::integral_constant<int, NA> -- NA > 0: exactly the first NA groups, branch-free (NA = NG: a full quad);
         // NA = 0: the quad's ng groups behind per-group branches
-        auto mma = [&](const float4 (&x)[TS], uint32_t ks, auto full) {
+        // `first`: std::bool_constant -- the accumulators' first K step: they START here, from c0 (groups that are not
+        // contracted still get the start value: the screen reads every accumulator and masks what does not count)
+        auto mma = [&](const float4 (&x)[TS], uint32_t ks, auto full, auto first) {
             constexpr int NA = decltype(full)::value, NGL = NA ? NA : NG;
+            constexpr bool FIRST = decltype(first)::value;
+            auto step = [&](int g, const float4 qc) {
+#pragma unroll
+                for (int t = 0; t < TS; ++t) {
+                    if constexpr (FIRST) mfma_step_c<OP>(acc[g][t], qc, x[t], c0[t]);
+                    else mfma_step<OP>(acc[g][t], qc, x[t]);
+                }
+            };
+            auto idle = [&](int g) {
+                if constexpr (FIRST) {
+#pragma unroll
+                    for (int t = 0; t < TS; ++t) acc[g][t] = c0[t];
+                }
+            };
             const uint32_t chq = ks * 4 + (uint32_t)kk;
             if constexpr (APD == 0) {
 #pragma unroll
                 for (int g = 0; g < NGL; ++g) {
-                    if (NA || (uint32_t)g < ng) {
-                        const float4 qc = qs[(16 * g + l15) * G + (chq ^ (uint32_t)l15)];
-#pragma unroll
-                        for (int t = 0; t < TS; ++t) mfma_step<OP>(acc[g][t], qc, x[t]);
-                    }
+                    if (NA || (uint32_t)g < ng) step(g, qs[(16 * g + l15) * G + (chq ^ (uint32_t)l15)]);
+                    else idle(g);
                 }
             } else {
                 const float4 *qb0 = qs + (uint32_t)l15 * G + (chq ^ (uint32_t)l15);
@@ -2038,14 +2056,19 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
                             const uint32_t gi = NA || (uint32_t)(g + APD) < ng ? (uint32_t)(g + APD) : ng - 1u;
                             qb[(g + APD) % (APD + 1)] = qb0[gi * gstride];
                         }
-#pragma unroll
-                        for (int t = 0; t < TS; ++t) mfma_step<OP>(acc[g][t], qb[g % (APD + 1)], x[t]);
+                        step(g, qb[g % (APD + 1)]);
                         // (the machine scheduler otherwise sinks every read back in front of its use to save the registers)
                         __builtin_amdgcn_sched_barrier(0);
-                    }
+                    } else idle(g);
                 }
             }
+#pragma unroll
+            for (int g = NGL; g < NG; ++g) idle(g);
         };
+        // C0: the first NS steps are peeled -- they start the accumulators (step 0) and give the loop and the tail behind it values
+        // that were WRITTEN by an MFMA.  (With start values moved into the registers in front of a loop that may run zero
+        // times, every accumulator had two register homes -- the loop's and the tail's -- and was copied from one to the other
+        // at the loop's exit and again in the tail: a quarter of the kernel's VALU instructions.)
         auto kloop = [&](auto full) {
             if constexpr (!(XT && XPF)) {
 #pragma unroll
@@ -2053,18 +2076,33 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
 #pragma unroll
                     for (int t = 0; t < TS; ++t) xs[j][t] = buf_ld16<ROW_AUX>(xr, lane_b, xso[t] + j * 1024);
             }
-            // on entry xs[j] holds (or awaits) K step j of this tile; nks is a multiple of 4 >= NS
+            // on entry xs[j] holds (or awaits) K step j of this tile; nks is a multiple of NS
+            auto refill = [&](int j, uint32_t ks) {
+#pragma unroll
+                for (int t = 0; t < TS; ++t) xs[j][t] = buf_ld16<ROW_AUX>(xr, lane_b, xso[t] + (ks + NS) * 1024);
+            };
             uint32_t ks = 0;
+            if constexpr (C0) {
+                const bool more = (uint32_t)NS < nks;       // wave-uniform
+                mma(xs[0], 0u, full, std::true_type{});
+                if (more) refill(0, 0u);
+#pragma unroll
+                for (int j = 1; j < NS; ++j) {
+                    mma(xs[j], (uint32_t)j, full, std::false_type{});
+                    if (more) refill(j, (uint32_t)j);
+                }
+                if (!more) return;
+                ks = NS;
+            }
             for (; ks + NS < nks; ks += NS) {
 #pragma unroll
                 for (int j = 0; j < NS; ++j) {
-                    mma(xs[j], ks + j, full);
-#pragma unroll
-                    for (int t = 0; t < TS; ++t) xs[j][t] = buf_ld16<ROW_AUX>(xr, lane_b, xso[t] + (ks + j + NS) * 1024);
+                    mma(xs[j], ks + j, full, std::false_type{});
+                    refill(j, ks + j);
                 }
             }
 #pragma unroll
-            for (int j = 0; j < NS; ++j) mma(xs[j], ks + j, full);
+            for (int j = 0; j < NS; ++j) mma(xs[j], ks + j, full, std::false_type{});
         };
         // !QLDS: both operands stream from global memory through THREE rotating register stages, so the
         // loads of K step s + 2 are issued before the MFMAs of step s (HBM latency is ~2 K steps of a
@@ -2104,7 +2142,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
         else if constexpr (PF) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
-                if ((uint32_t)ks < nks) mma(xt[ks], (uint32_t)ks, std::integral_constant<int, 0>{});
+                if ((uint32_t)ks < nks) mma(xt[ks], (uint32_t)ks, std::integral_constant<int, 0>{}, std::false_type{});
         }
         // (32-row tiles: a branch-free body per group count -- a wide quad has 7..10 of its 10 groups; per-group branches would
         //  cost the exact wait counts of the A-operand pipeline, and running all ten always (round 3 / 4) costs up to 30 % of the
@@ -2302,9 +2340,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
         }
         // (a last word that holds fewer than GPW groups: its fields move up to where a full word has them)
         if constexpr ((NG % (int)GPW) != 0) bits[NWD - 1] <<= FW * (GPW - (uint32_t)(NG % (int)GPW));
-        uint32_t rowmask = 0;                          // bit TS - 1 - t: row 16 t + l15 of the tile belongs to this wave
+        // Validity of this lane's pairs.  Rows: bit TS - 1 - t of an (r) field says that row 16 t + l15 of the tile belongs to
+        // this wave -- rowrep carries it in EVERY field of a word (all ones on a full tile).
+        constexpr uint32_t REPW = TS == 4 ? 0x11111111u : 0x55555555u;      // bit 0 of every TS-bit field
+        uint32_t rowrep = 0;
 #pragma unroll
-        for (int t = 0; t < TS; ++t) rowmask |= ((uint32_t)(16 * t + l15) < nvalid) ? ((1u << (TS - 1)) >> t) : 0u;
+        for (int t = 0; t < TS; ++t) rowrep |= ((uint32_t)(16 * t + l15) < nvalid) ? (REPW << (TS - 1 - t)) : 0u;
         // the accumulators are dead from here on: the next tile's operands can take their registers
         if constexpr (PF) { if (pf && t0 + 64 < r1) issue_tile(t0 + 64); }
         const uint32_t rowbase = (uint32_t)(t0 - r0) + (uint32_t)l15;
@@ -2314,23 +2355,45 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
         // Explicit validity (rows past the wave's range, queries past the quad's count): the compare above keeps
         // a pair whenever its operands are NaN -- an unset threshold, non-finite data -- and an out-of-range row
         // must never reach the exact evaluation.
+        // Queries: ng = ceil(cnt / 16), so every query of the groups below the quad's last one exists and none of the groups
+        // behind it does -- whole fields, the same in every lane: a wave-uniform word mask.  Only the LAST group is partial,
+        // and there a lane's four queries 16 (ng - 1) + 4 kk + r are a prefix r < nvr (r = 0 in the field's highest bits).
+        // (A compare and a select per lane query and tile said the same: a tenth of the int8 instances' VALU instructions.
+        //  The f32 forms keep that: built for three waves per SIMD, they spill 8 .. 12 bytes more with the masks.)
         uint32_t vw[NWD];
         uint32_t tot = 0;
+        if constexpr (OP != OP_F32) {
+            const int glast = (int)ng - 1;
+            const int nvr = min(max((int)cnt - 16 * glast - 4 * kk, 0), 4);
+            const uint32_t vm_last = (rowrep & ((1u << FW) - 1u)) & (0xFFFFFFFFu << (FW - (uint32_t)TS * (uint32_t)nvr));
 #pragma unroll
-        for (int ww = 0; ww < NWD; ++ww) {
-            uint32_t vmw = 0;
-#pragma unroll
-            for (int gl = 0; gl < (int)GPW; ++gl) {
-                const uint32_t g = GPW * (uint32_t)ww + (uint32_t)gl;
-                if (g < (uint32_t)NG) {
-                    uint32_t vm = 0;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) vm |= (16 * g + 4 * (uint32_t)kk + (uint32_t)r < cnt) ? rowmask << (FW - TS * (r + 1)) : 0u;
-                    vmw |= g < ng ? vm << (FW * (GPW - 1u - (uint32_t)gl)) : 0u;
-                }
+            for (int ww = 0; ww < NWD; ++ww) {
+                const int nf = min(max(glast - (int)GPW * ww, 0), (int)GPW);          // whole groups of this word (wave-uniform)
+                const uint32_t mfull = nf ? 0xFFFFFFFFu << (32u - FW * (uint32_t)nf) : 0u;
+                const int li = glast - (int)GPW * ww;                                 // the last group's place in this word, if here
+                const bool here = li >= 0 && li < (int)GPW;
+                const uint32_t vmw = (rowrep & mfull) | ((vm_last << (here ? FW * (GPW - 1u - (uint32_t)li) : 0u)) & (here ? 0xFFFFFFFFu : 0u));
+                vw[ww] = bits[ww] & vmw;
+                tot += (uint32_t)__popc(vw[ww]);
             }
-            vw[ww] = bits[ww] & vmw;
-            tot += (uint32_t)__popc(vw[ww]);
+        } else {
+            const uint32_t rowmask = rowrep & ((1u << TS) - 1u);
+#pragma unroll
+            for (int ww = 0; ww < NWD; ++ww) {
+                uint32_t vmw = 0;
+#pragma unroll
+                for (int gl = 0; gl < (int)GPW; ++gl) {
+                    const uint32_t g = GPW * (uint32_t)ww + (uint32_t)gl;
+                    if (g < (uint32_t)NG) {
+                        uint32_t vm = 0;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) vm |= (16 * g + 4 * (uint32_t)kk + (uint32_t)r < cnt) ? rowmask << (FW - TS * (r + 1)) : 0u;
+                        vmw |= g < ng ? vm << (FW * (GPW - 1u - (uint32_t)gl)) : 0u;
+                    }
+                }
+                vw[ww] = bits[ww] & vmw;
+                tot += (uint32_t)__popc(vw[ww]);
+            }
         }
         const uint32_t incl_all = wave_incl_scan_u32(tot);
         const bool one_pass = readlane_u32(incl_all, 63) <= (uint32_t)PASS - 64u;
