@@ -285,6 +285,13 @@ pub struct DistinctSearchResult {
     pub key: i64,
 }
 
+/// One group of a grouped top-k ([`Searcher::topk_grouped`]): the group's key value and its nearest rows, nearest first.
+#[derive(Debug, Clone, PartialEq)]
+pub struct GroupSearchResult {
+    pub key: i64,
+    pub hits: Vec<SearchResult>,
+}
+
 /// An index bound to its column on one GPU.  What `topk()` re-creates per query from the file
 /// (`read_index_from_parquet` + `read_embeddings_for_rows`, `src/ivf/search.rs:89-110`) is kept resident here:
 /// cache one per indexed Parquet file.
@@ -505,6 +512,55 @@ impl<'c> Searcher<'c> {
                     .collect()
             })
             .collect())
+    }
+
+    /// Up to `group_size` rows of each of the `k` nearest groups of `keys`, groups as [`Searcher::topk_distinct`] defines them
+    /// (`include/pqv.h`: `pqv_topk_grouped`).  Groups ascending by their nearest row, a group's hits by (distance, position).
+    pub fn topk_grouped(&self, keys: &RowKeys, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,
+                        group_size: NonZeroUsize, nprobe: NonZeroUsize) -> Result<Vec<Vec<GroupSearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (k, m, np) = (k.get(), group_size.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k * m];
+        let mut dist = vec![0f32; nq * k * m];
+        let mut group = vec![0i64; nq * k];
+        let mut group_rows = vec![0u32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_grouped(self.raw, keys.raw, mask.map_or(ptr::null(), |x| x.raw as *const _), queries.as_ptr(), nq as u32,
+                                  dim as u32, k as u32, m as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(),
+                                  dist.as_mut_ptr(), group.as_mut_ptr(), group_rows.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| {
+                (0..found[q] as usize)
+                    .map(|g| {
+                        let o = (q * k + g) * m;
+                        GroupSearchResult {
+                            key: group[q * k + g],
+                            hits: (0..group_rows[q * k + g] as usize)
+                                .map(|i| SearchResult { row_idx: rows[o + i], distance: dist[o + i] })
+                                .collect(),
+                        }
+                    })
+                    .collect()
+            })
+            .collect())
+    }
+
+    /// [`Searcher::topk_grouped`] on device buffers, enqueued on `hip_stream` (NULL: the searcher's): `d_row_idx` u32 / `d_dist` f32
+    /// `[nq, k, group_size]`, `d_group_key` i64 / `d_group_rows` u32 `[nq, k]`, `d_n_found` u32 / `d_n_candidates` u64 `[nq]`; the last
+    /// four may be NULL.  Serves `k * group_size <= 1024`.
+    ///
+    /// # Safety
+    /// Every non-NULL pointer must be a device allocation of at least the size above, valid until the stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn topk_grouped_device(&self, keys: &RowKeys, mask: Option<&RowMask>, d_queries: *const c_void, nq: u32, k: NonZeroUsize,
+                                      group_size: NonZeroUsize, nprobe: NonZeroUsize, d_row_idx: *mut c_void, d_dist: *mut c_void,
+                                      d_group_key: *mut c_void, d_group_rows: *mut c_void, d_n_found: *mut c_void,
+                                      d_n_candidates: *mut c_void, hip_stream: *mut c_void) -> Result<()> {
+        check(sys::pqv_topk_grouped_device(self.raw, keys.raw, mask.map_or(ptr::null(), |x| x.raw as *const _), d_queries, nq,
+                                           k.get() as u32, group_size.get() as u32, nprobe.get() as u32, 0, sys::PQV_L2SQ_REF4, 1,
+                                           d_row_idx, d_dist, d_group_key, d_group_rows, d_n_found, d_n_candidates, hip_stream))
     }
 
     /// [`Searcher::topk_distinct`] on device buffers, enqueued on `hip_stream` (NULL: the searcher's): `d_queries` f32 `[nq, dim]`,

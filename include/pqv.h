@@ -602,8 +602,8 @@ int pqv_range_search_keyed(const pqv_searcher *searcher, const pqv_row_keys *key
  *                    pqv_topk_distinct computes the sorted considered sequence with the masked range machinery (radius = +inf)
  *                    and keeps the first row per key on the host, and pqv_topk_distinct_device reports PQV_ERR_UNSUPPORTED, as
  *                    pqv_topk_masked_device does.
- *   out of scope     more than one row per group; a per-query key filter combined with a group column in one call; distinct
- *                    range search.
+ *   out of scope     a per-query key filter combined with a group column in one call; distinct range search.  (More than one
+ *                    row per group: pqv_topk_grouped below.)
  * Errors (PQV_ERR_INVALID; NULL handles are checked before any device use): "searcher must not be NULL", "row keys must not be
  * NULL", "row keys belong to another searcher", "row mask belongs to another searcher", and pqv_topk's own ("k must be > 0", ...). */
 int pqv_topk_distinct(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries,
@@ -613,6 +613,46 @@ int pqv_topk_distinct_device(const pqv_searcher *searcher, const pqv_row_keys *k
                              const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric,
                              int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_n_found,
                              void *d_n_candidates, void *hip_stream);
+
+/* Grouped top-k: up to group_size rows of each of the k nearest GROUPS -- "the 10 nearest documents and the 3 best chunks of each";
+ * `ROW_NUMBER() OVER (PARTITION BY doc_id ORDER BY distance) <= group_size` on the k nearest doc_ids; elsewhere search_groups,
+ * group_by_field + group_size, collapse + inner_hits.
+ *
+ * A grouped call is the distinct call of the same arguments plus group_size.  Considered rows, groups and representatives are
+ * exactly pqv_topk_distinct's: the cap cuts the candidate sequence before any filter, a row is considered when its key is valid
+ * and the optional shared mask allows it, positions are the unmasked ones, keys are compared in i64.
+ *   result           let S be query q's considered rows sorted by (d2, position).  Groups are ranked by their first row in S and
+ *                    the first k groups are kept; group g returns its first min(group_size, rows it has in S) rows, in S order.
+ *                    No heap to replay and no tie flags: the host and the device form return the same thing.
+ *   outputs          row_idx and dist [nq, k, group_size]: group g's i-th row at [q][g][i]; group_key (int64_t [nq, k]): the
+ *                    group's key value; group_rows (uint32_t [nq, k]): the rows returned for the group; n_found [nq]: the groups
+ *                    found, at most k; n_candidates.  Empty row slots hold 0xFFFFFFFF / +inf, empty group slots key 0 and count
+ *                    0.  sqrt_out and the PQV_COSINE halving are the distinct call's.  group_key, group_rows, n_found and
+ *                    n_candidates (and their d_ forms) may be NULL.
+ *   equivalence      each bit for bit: group_size == 1 returns what pqv_topk_distinct returns and takes that path unchanged (one
+ *                    pass); with all keys distinct, slot i = 0 holds pqv_topk_masked_device's result; in general S is what
+ *                    pqv_range_search_masked returns with radius = +inf, sqrt_out = 0 and the mask ANDed with the key validity.
+ *   path             group_size > 1 is two exact streaming passes over the same candidates: the distinct pass names the k groups,
+ *                    the second pass reads only the rows of those groups and keeps at most group_size per group.  No searcher
+ *                    option changes a result.  The kernels serve k * group_size <= 1024 (computed in 64 bits) and at most 1024
+ *                    probed lists; beyond that pqv_topk_grouped computes S with the masked range machinery and groups on the
+ *                    host, and pqv_topk_grouped_device reports PQV_ERR_UNSUPPORTED "pqv_topk_grouped_device takes k *
+ *                    group_size <= 1024 and at most 1024 probed lists per query".
+ *   counts           group_size > 1: queries and candidate_rows advance once per query, not once per pass; embeddings_fetched
+ *                    advances by the considered rows plus the rows the second pass evaluates, the considered rows of the selected
+ *                    groups.  group_size == 1: the distinct call's counts.
+ *   out of scope     a per-query key filter combined with grouping; grouped range search; PQV_DOT; probing further lists when
+ *                    fewer than k groups are found.
+ * Errors: pqv_topk_distinct's, in the same order, NULL handles checked before any device use; behind "k must be > 0":
+ * "group_size must be > 0".  PQV_DOT: PQV_ERR_UNSUPPORTED "PQV_DOT is not supported by keyed and distinct calls". */
+int pqv_topk_grouped(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries,
+                     uint32_t nq, uint32_t query_len, uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates,
+                     int metric, int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows,
+                     uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_grouped_device(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask, const void *d_queries,
+                            uint32_t nq, uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric,
+                            int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
+                            void *d_n_candidates, void *hip_stream);
 
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`

@@ -19,11 +19,13 @@ Host-side mirror of the reference's Rust API over the C ABI of include/pqv.h:
                                                predicates (col("id") >= 2, & | ~) run on the GPU over resident Columns
     SELECT DISTINCT ON (doc) .. LIMIT k      TopkBuilder / TableTopkBuilder: .distinct_on("doc") -> [DistinctSearchResult(row_idx,
       (no counterpart: grouping)               distance, key)]; Searcher.topk_distinct / topk_distinct_device (keys=RowKeys)
+    ROW_NUMBER() OVER (PARTITION BY doc      .distinct_on("doc").group_size(m) -> [GroupSearchResult(key, hits=[SearchResult])]: up to m
+      ORDER BY distance) <= m, k docs          rows of each of the k nearest groups; Searcher.topk_grouped / topk_grouped_device
 
 (src/ivf/parquet.rs:23-103, src/ivf/search.rs:41-81).  All compute runs in the HIP kernels
 behind libpqv_hip.so; importing this package without the built library fails loudly.
 """
-from .api import (CandidateCursor, Column, Corpus, DistinctSearchResult, TableDistinctSearchResult, Index, IndexBuilder, PqvError, RangeBuilder, RowKeys, RowMask, Searcher, SearchResult, TopkBuilder,
+from .api import (CandidateCursor, Column, Corpus, DistinctSearchResult, GroupSearchResult, TableDistinctSearchResult, Index, IndexBuilder, PqvError, RangeBuilder, RowKeys, RowMask, Searcher, SearchResult, TopkBuilder,
                   TableRangeBuilder, TableSearcher, TableSearchResult, TableTopkBuilder, device_count, merge_topk, rerank_batch,
                   rerank_finish, round_robin_quota, searcher_for_parquet, searcher_for_parquet_files, split_table_rows)
 from .parquet_io import has_pq_vector_index, load_scalar_column, read_index_from_parquet, row_mask_from_expression
@@ -31,7 +33,7 @@ from .predicate import allowed, col
 from ._ffi import (PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE, PQV_L2SQ_MFMA, PQV_DOT, PQV_LAYOUT_IVF_ORDERED, PQV_LAYOUT_ROW_ORDER,
                    PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, PQV_PREPARE_COSINE, LIB_PATH)
 
-__all__ = ["RowMask", "RowKeys", "DistinctSearchResult", "TableDistinctSearchResult", "Column", "col", "allowed", "load_scalar_column", "row_mask_from_expression", "CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
+__all__ = ["RowMask", "RowKeys", "DistinctSearchResult", "GroupSearchResult", "TableDistinctSearchResult", "Column", "col", "allowed", "load_scalar_column", "row_mask_from_expression", "CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
            "TopkBuilder", "TableRangeBuilder", "TableSearcher", "TableSearchResult", "TableTopkBuilder", "searcher_for_parquet_files",
            "split_table_rows", "device_count", "merge_topk", "rerank_batch", "rerank_finish", "searcher_for_parquet", "PQV_COSINE", "PQV_L2SQ_MFMA", "PQV_DOT",
            "has_pq_vector_index", "read_index_from_parquet", "PQV_L2SQ_REF4",

@@ -408,6 +408,14 @@ class DistinctSearchResult:
     key: int
 
 
+@dataclass
+class GroupSearchResult:
+    """One group of a grouped top-k (TopkBuilder.distinct_on(..).group_size(m)): the group's key value and its up to m nearest rows,
+    nearest first -- [SearchResult], or [TableSearchResult] from a TableTopkBuilder."""
+    key: int
+    hits: list
+
+
 _COLUMN_DTYPES = {np.dtype(np.int32): _ffi.PQV_COL_I32, np.dtype(np.int64): _ffi.PQV_COL_I64,
                   np.dtype(np.float32): _ffi.PQV_COL_F32, np.dtype(np.float64): _ffi.PQV_COL_F64}
 _RESIDENT_TYPES = "int8..int64, uint8..uint32, bool, date, timestamp, time64, float, double"
@@ -822,6 +830,39 @@ class Searcher:
                                                    vp(d_row_idx), vp(d_dist), vp(d_group_key or None), vp(d_n_found or None),
                                                    vp(d_n_candidates or None), vp(stream or None)))
 
+    def topk_grouped(self, queries, k, group_size, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """Grouped top-k (pqv.h: pqv_topk_grouped): per query up to group_size rows of each of the k nearest groups of `keys` (as
+        topk_distinct defines groups), under `mask` if one is given.  Returns (row_idx [nq,k,group_size] u32, dist [nq,k,group_size]
+        f32, group_keys [nq,k] i64, group_rows [nq,k] u32, n_found [nq], n_candidates [nq]): groups ascending by their nearest row,
+        a group's rows ascending by (d2, candidate position); empty row slots are 0xFFFFFFFF / +inf, empty groups key 0, count 0."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        shape = (nq, max(k, 1), max(group_size, 1))
+        rows = np.full(shape, 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full(shape, np.inf, dtype=np.float32)
+        grp = np.zeros(shape[:2], dtype=np.int64)
+        grows = np.zeros(shape[:2], dtype=np.uint32)
+        nf = np.zeros(nq, dtype=np.uint32)
+        nc = np.zeros(nq, dtype=np.uint64)
+        _check(_ffi.lib().pqv_topk_grouped(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
+                                           q.ctypes.data_as(f32p), nq, qlen, k, group_size, nprobe, max_candidates, metric,
+                                           1 if sqrt_out else 0, rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p),
+                                           grp.ctypes.data_as(_ffi.i64p), grows.ctypes.data_as(u32p), nf.ctypes.data_as(u32p),
+                                           nc.ctypes.data_as(u64p)))
+        return rows, dist, grp, grows, nf, nc
+
+    def topk_grouped_device(self, d_queries, nq, k, group_size, nprobe, keys, d_row_idx, d_dist, d_group_key=0, d_group_rows=0, d_n_found=0,
+                            d_n_candidates=0, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of topk_grouped (pqv.h: pqv_topk_grouped_device), asynchronous on `stream` as topk_device is:
+        d_row_idx u32 / d_dist f32 [nq, k, group_size], d_group_key i64 / d_group_rows u32 [nq, k], d_n_found u32 / d_n_candidates u64
+        [nq]; the last four are optional.  Serves k * group_size <= 1024.  keys and mask must stay alive until the work has completed."""
+        _check(_ffi.lib().pqv_topk_grouped_device(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
+                                                  vp(d_queries), nq, k, group_size, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                  vp(d_row_idx), vp(d_dist), vp(d_group_key or None), vp(d_group_rows or None),
+                                                  vp(d_n_found or None), vp(d_n_candidates or None), vp(stream or None)))
+
     def range_search(self, queries, radius, nprobe, max_candidates=0, max_results=0, metric=_ffi.PQV_L2SQ_REF4,
                      sqrt_out=True, mask=None, keys=None, query_keys=None):
         """Every candidate within `radius` of each query (pqv.h: pqv_range_search), ascending by (d2, candidate position).
@@ -1120,6 +1161,7 @@ class TopkBuilder:
         self._metric = _ffi.PQV_L2SQ_REF4
         self._where = None
         self._distinct = None
+        self._group_size = None
 
     def metric(self, m):
         self._metric = _metric_arg(m)
@@ -1138,6 +1180,30 @@ class TopkBuilder:
             raise PqvError(_ffi.PQV_ERR_INVALID, f"distinct_on() needs a column name or a RowKeys, got {type(x).__name__}")
         self._distinct = x
         return self
+
+    def group_size(self, m):
+        """With distinct_on(x): up to m rows of each of the k nearest values of x -- the k nearest documents and the m best chunks of
+        each (pqv.h: pqv_topk_grouped).  search() then returns [GroupSearchResult(key, hits=[SearchResult])], groups nearest first,
+        a group's hits nearest first.  Without distinct_on() search() raises."""
+        if m == 0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "group_size must be > 0")
+        self._group_size = m
+        return self
+
+    def _search_grouped(self, searcher, mask, max_candidates=0):
+        """-> [(key, rows, dist)] of the found groups."""
+        keys, owned = self._group_keys(searcher)
+        try:
+            rows, dist, grp, grows, nf, _ = searcher.topk_grouped(_f32(self._query).reshape(1, -1), self._k, self._group_size, self._nprobe,
+                                                                  keys, mask=mask, max_candidates=max_candidates, metric=self._metric)
+        finally:
+            if owned:
+                keys.close()
+        return [(int(grp[0, g]), rows[0, g, :int(grows[0, g])], dist[0, g, :int(grows[0, g])]) for g in range(int(nf[0]))]
+
+    def _check_grouping(self):
+        if self._group_size is not None and self._distinct is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "group_size() needs distinct_on(): the column whose values are the groups")
 
     def _group_keys(self, searcher):
         """-> (RowKeys, owned) of the distinct_on() argument on `searcher`."""
@@ -1184,11 +1250,15 @@ class TopkBuilder:
             raise PqvError(_ffi.PQV_ERR_INVALID, "k must be set")
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
+        self._check_grouping()
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
         if self._distinct is not None:
             mask, owned = _resolve_where(self._where, self._path, self._searcher) if self._where is not None else (None, False)
             try:
+                if self._group_size is not None:
+                    return [GroupSearchResult(g, [SearchResult(r, d) for r, d in zip(rows.tolist(), dist.tolist())])
+                            for g, rows, dist in self._search_grouped(self._searcher, mask)]
                 rows, dist, grp = self._search_distinct(self._searcher, mask)
             finally:
                 if owned:
@@ -1485,7 +1555,8 @@ class TableTopkBuilder(TopkBuilder):
 
     def distinct_on(self, x):
         """TopkBuilder.distinct_on over the table: x names an integer column that every file has (one resident type); search()
-        returns [TableDistinctSearchResult(path, row_idx, distance, key)]."""
+        returns [TableDistinctSearchResult(path, row_idx, distance, key)], with group_size(m) [GroupSearchResult(key,
+        hits=[TableSearchResult])]."""
         if not isinstance(x, str):
             raise PqvError(_ffi.PQV_ERR_INVALID, f"a table's distinct_on() needs a column name, got {type(x).__name__}")
         self._distinct = x
@@ -1500,10 +1571,14 @@ class TableTopkBuilder(TopkBuilder):
             raise PqvError(_ffi.PQV_ERR_INVALID, "k must be set")
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
+        self._check_grouping()
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
         if self._distinct is not None:
             mask = _resolve_table_where(self._where, self._paths, s) if self._where is not None else None
             try:
+                if self._group_size is not None:
+                    return [GroupSearchResult(g, _table_results(s, self._paths, rows, dist))
+                            for g, rows, dist in self._search_grouped(s, mask, self._max_candidates)]
                 rows, dist, grp = self._search_distinct(s, mask, self._max_candidates)
             finally:
                 if mask is not None:

@@ -29,6 +29,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -321,7 +322,11 @@ struct Scratch {
         s_pair_end, s_file_cnt,     // round-robin capped tables: per-pair candidate ends, per-file counts (SegProbeArgs)
         s_qcos,                     // PQV_COSINE: the call's normalised queries n(q), read by the cosine searcher's kernels
         s_qkeys,                    // keyed host calls (pqv_row_keys): the sub-batch's query keys, i64 [b]
-        s_part_grp, s_grp_out;      // distinct calls: the partial lists' group values i64 [nq][n_part][k]; the host form's group_key block
+        s_part_grp, s_grp_out,      // distinct calls: the partial lists' group values i64 [nq][n_part][k]; the host form's group_key block
+        // grouped calls (pqv_topk_grouped): pass 1's rows / distances [nq][k] (not reported), its group values and n_found where the caller
+        // takes none, the sorted sets [nq][k], the partial lists' slots [nq][n_part][k * group_size] and lengths [nq][n_part], and the
+        // host form's group_rows block
+        s_g1_rows, s_g1_dist, s_g1_keys, s_g1_nfound, s_gset_keys, s_gset_slot, s_gpart_slot, s_gpart_cnt, s_grows_out;
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -335,7 +340,8 @@ struct Scratch {
                 &s_dist, &s_nfound, &s_pair_u32, &s_pairs, &s_groups, &s_quads, &s_items, &s_ticket, &s_ticket2, &s_cand_keys, &s_cand_vals, &s_cand_cnt, &s_spilled,
                 &s_seed_ub, &s_qblk, &s_gthr, &s_tie, &s_replay, &s_qnorm, &s_qmax, &s_thr_hist, &s_thr_bins, &s_qi8, &s_qn2i, &s_qres, &s_qresu, &s_pair_lb, &s_part_flags, &s_qpad, &s_cand_lb, &s_pendv, &s_work, &s_nwork, &s_out,
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
-                &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_part_grp, &s_grp_out};
+                &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_part_grp, &s_grp_out,
+                &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -545,6 +551,9 @@ struct MaskView {
     const int64_t *d_qkeys;            // device: the keys of the queries the kernels see (the current sub-batch's)
     const pqv_row_keys *group;         // a distinct call's group column, else nullptr (bits / mask: its shared mask, or nullptr)
     int64_t *d_group_out;              // distinct: where the fold writes the group values [nq * k] (device), or nullptr
+    uint32_t group_size;               // a grouped call (pqv_topk_grouped; `group` set): rows per group, >= 1; 0: not grouped.  The call's row_idx / dist are
+                                       // [nq, k, group_size]
+    uint32_t *d_group_rows;            // grouped: where the rows per group go [nq * k] (device), or nullptr
 };
 // a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
 static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
@@ -3577,6 +3586,31 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint32_t)));
     const bool distinct = mask && mask->group;
     if (distinct) HIP_TRY(sc.s_part_grp.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(int64_t)));
+    // a grouped call (pqv.h: pqv_topk_grouped) with more than one row per group: pass 1 below is the distinct call with its rows and
+    // distances going to the lane, pass 2 behind its fold fills the caller's [nq, k, group_size] blocks.  Every buffer of both passes is
+    // sized here, before the first kernel: the partial lists of pass 2 take over those of pass 1.
+    const uint32_t gm = distinct ? mask->group_size : 0u;
+    const bool two_pass = gm > 1;
+    const size_t km = static_cast<size_t>(k) * std::max<uint32_t>(1, gm);
+    uint32_t *g_n_found = d_n_found;          // pass 1's n_found: the caller's block, or the lane's where pass 2 / group_rows need one
+    int64_t *g_keys = distinct ? mask->d_group_out : nullptr;
+    if (two_pass) {
+        if (km > 1024 || k > pqv::GROUPED_SET_MAX) return fail(PQV_ERR_INVALID, "grouped call beyond the kernels' lists");
+        const size_t n_lists = static_cast<size_t>(nq) * p.n_part_rr;
+        HIP_TRY(sc.s_part_keys.ensure((n_lists * km + 4) * sizeof(uint64_t)));
+        HIP_TRY(sc.s_part_vals.ensure((n_lists * km + 4) * sizeof(uint32_t)));
+        HIP_TRY(sc.s_gpart_slot.ensure((n_lists * km + 4) * sizeof(uint32_t)));
+        HIP_TRY(sc.s_gpart_cnt.ensure((n_lists + 4) * sizeof(uint32_t)));
+        HIP_TRY(sc.s_g1_rows.ensure(static_cast<size_t>(nq) * k * sizeof(uint32_t)));
+        HIP_TRY(sc.s_g1_dist.ensure(static_cast<size_t>(nq) * k * sizeof(float)));
+        HIP_TRY(sc.s_gset_keys.ensure(static_cast<size_t>(nq) * k * sizeof(int64_t)));
+        HIP_TRY(sc.s_gset_slot.ensure(static_cast<size_t>(nq) * k * sizeof(uint32_t)));
+        if (!g_keys) { HIP_TRY(sc.s_g1_keys.ensure(static_cast<size_t>(nq) * k * sizeof(int64_t))); g_keys = sc.s_g1_keys.as<int64_t>(); }
+    }
+    if ((two_pass || (gm == 1 && mask->d_group_rows)) && !g_n_found) {
+        HIP_TRY(sc.s_g1_nfound.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
+        g_n_found = sc.s_g1_nfound.as<uint32_t>();
+    }
 
     hipEvent_t ev[4];
     if (int rc = timing_events(s, ev)) return rc;
@@ -3913,9 +3947,32 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         DistinctMergeArgs dm{};
         dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = sc.s_part_grp.as<int64_t>();
         dm.nq = nq; dm.n_part = p.n_part_rr; dm.k = k; dm.elem_size = mask->group->dtype == PQV_COL_I32 ? 4u : 8u;
-        dm.ids = s->d_final_ids; dm.row_idx = d_row_idx; dm.dist = d_dist; dm.group_key = mask->d_group_out; dm.n_found = d_n_found;
+        dm.ids = s->d_final_ids; dm.row_idx = d_row_idx; dm.dist = d_dist; dm.group_key = g_keys; dm.n_found = g_n_found;
         dm.sqrt_out = sqrt_out;
+        if (two_pass) { dm.row_idx = sc.s_g1_rows.as<uint32_t>(); dm.dist = sc.s_g1_dist.as<float>(); }
         HIP_TRY(launch_distinct_merge(dm, stream));
+        if (two_pass) {
+            // pass 2: the k groups as a sorted set per query, the walk again over their rows only, and the fold (no host step between)
+            const pqv_row_keys *gk = mask->group;
+            HIP_TRY(launch_group_set(g_keys, g_n_found, nq, k, sc.s_gset_keys.as<int64_t>(), sc.s_gset_slot.as<uint32_t>(), stream));
+            GroupedArgs ga{};
+            ga.bits = mask->bits; ga.stats = s->d_stats.as<unsigned long long>(); ga.key_pos = gk->d_key_pos.p;
+            ga.valid_pos = gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr; ga.elem_size = dm.elem_size;
+            ga.set_keys = sc.s_gset_keys.as<int64_t>(); ga.set_slot = sc.s_gset_slot.as<uint32_t>(); ga.n_found = g_n_found;
+            ga.k = k; ga.group_size = gm; ga.km = static_cast<uint32_t>(km);
+            ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
+            ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
+            HIP_TRY(launch_grouped_stream(ra, ga, stream));
+            GroupedMergeArgs gma{};
+            gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
+            gma.nq = nq; gma.n_part = p.n_part_rr; gma.k = k; gma.group_size = gm; gma.km = ga.km;
+            gma.ids = s->d_final_ids; gma.row_idx = d_row_idx; gma.dist = d_dist; gma.group_rows = mask->d_group_rows; gma.sqrt_out = sqrt_out;
+            HIP_TRY(launch_grouped_merge(gma, stream));
+            s->counters.kernel_launches += 3;
+        } else if (gm == 1 && mask->d_group_rows) {
+            HIP_TRY(launch_group_rows_fill(g_n_found, nq, k, mask->d_group_rows, stream));
+            s->counters.kernel_launches += 1;
+        }
         if (ev[3]) HIP_TRY(hipEventRecord(ev[3], stream));
         if (int rc = lane_release(sc, stream)) return rc;
         s->counters.kernel_launches += 4;
@@ -3965,6 +4022,10 @@ int validate_query(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metri
 // that limit (topk_unbounded), the asynchronous device entry points report it
 bool beyond_kernel_lists(const pqv_searcher *s, uint32_t k_lists, uint32_t nprobe) {
     return k_lists > 1024 || probe_count(s, nprobe) > 1024;
+}
+// a grouped call's lists hold k * group_size entries (64-bit: no wrap)
+bool grouped_beyond_kernel_lists(const pqv_searcher *s, uint32_t k, uint32_t group_size, uint32_t nprobe) {
+    return static_cast<uint64_t>(k) * group_size > 1024 || probe_count(s, nprobe) > 1024;
 }
 // PQV_DOT (pqv.h): every entry point works within the kernels' lists, and keyed / distinct calls do not take it.  Checked behind
 // validate_topk, before any device work.
@@ -4245,6 +4306,8 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
     if (int rc = dot_checks(s, k, nprobe, metric, mask)) return rc;
     if (int rc = table_max_candidates(s, max_candidates)) return rc;
     if (d_tie_flags && k > 1023) return fail(PQV_ERR_UNSUPPORTED, "tie flags need a runner-up entry: k <= 1023");
+    if (mask && mask->group_size && grouped_beyond_kernel_lists(s, k, mask->group_size, nprobe))
+        return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_grouped_device takes k * group_size <= 1024 and at most 1024 probed lists per query");
     if (beyond_kernel_lists(s, k, nprobe))
         return fail(PQV_ERR_UNSUPPORTED, s->n_files ? "the device entry points take k <= 1024 and at most 1024 probed lists per query (the sum of "
                                                       "min(nprobe, n_clusters) over the table's files; pqv_topk has no such limit)"
@@ -5047,9 +5110,10 @@ namespace {
 // Beyond the kernels' lists (k > 1024 or more than 1024 probed lists): the (d2, position)-sorted considered rows of every query from
 // the masked range machinery -- radius +inf, d2 out, under the position image (key validity AND shared mask) -- and the first row
 // of every key value kept on the host.  Correct for any k / nprobe; not a fast path.
+// m (a grouped call, pqv.h: pqv_topk_grouped): the first m rows of each of those key values, row_idx / dist [nq, k, m], group_rows [nq, k].
 int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const MaskView *mv, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                        uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key,
-                       uint32_t *n_found, uint64_t *n_candidates) {
+                       uint32_t *n_found, uint64_t *n_candidates, uint32_t m = 1, uint32_t *group_rows = nullptr) {
     const pqv_row_keys *gk = mv->group;
     if (int rc = keys_host_rows(s, gk)) return rc;
     // the image of the considered positions, made on the host from the two images (n / 8 bytes each)
@@ -5074,34 +5138,57 @@ int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const MaskView *mv, c
     lims.get()[0] = 0;
     if (int rc = range_body(s, sc, queries, nq, INFINITY, nprobe, max_candidates, 0, metric, 0, lims.get(), rows, d2, nullptr, n_candidates, &rv))
         return rc;
-    std::unordered_set<int64_t> seen;
+    std::unordered_map<int64_t, uint32_t> slot_of;       // key value -> its group's rank
+    std::vector<uint32_t> have;                          // rows kept per group
     for (uint32_t q = 0; q < nq; ++q) {
-        seen.clear();
+        slot_of.clear();
+        have.clear();
         uint32_t found = 0;
-        uint32_t *orow = row_idx + static_cast<uint64_t>(q) * k;
-        float *od = dist + static_cast<uint64_t>(q) * k;
-        int64_t *og = group_key ? group_key + static_cast<uint64_t>(q) * k : nullptr;
-        for (uint64_t i = lims.get()[q]; i < lims.get()[q + 1] && found < k; ++i) {
+        uint64_t open = 0;                               // groups that still take rows
+        const uint64_t qo = static_cast<uint64_t>(q) * k;
+        uint32_t *orow = row_idx + qo * m;
+        float *od = dist + qo * m;
+        int64_t *og = group_key ? group_key + qo : nullptr;
+        uint32_t *ogr = group_rows ? group_rows + qo : nullptr;
+        for (uint64_t i = lims.get()[q]; i < lims.get()[q + 1] && (found < k || open); ++i) {
             const uint32_t r = rows.get()[i];
             if (r >= gk->n_rows) continue;
             const int64_t g = gk->host_vals[r];
-            if (!seen.insert(g).second) continue;
+            uint32_t slot;
+            const auto it = slot_of.find(g);
+            if (it != slot_of.end()) {
+                slot = it->second;
+                if (have[slot] >= m) continue;
+            } else {
+                if (found >= k) continue;
+                slot = found++;
+                slot_of.emplace(g, slot);
+                have.push_back(0);
+                if (og) og[slot] = g;
+                ++open;
+            }
             const float v = d2.get()[i];
-            orow[found] = r;
-            od[found] = sqrt_out == 1 ? std::sqrt(v) : sqrt_out == 2 ? 0.5f * v : v;
-            if (og) og[found] = g;
-            ++found;
+            const uint64_t o = static_cast<uint64_t>(slot) * m + have[slot];
+            orow[o] = r;
+            od[o] = sqrt_out == 1 ? std::sqrt(v) : sqrt_out == 2 ? 0.5f * v : v;
+            if (++have[slot] == m) --open;
         }
-        // (k may be huge -- "keep everything": the caller's buffers are [nq * k] all the same)
-        for (uint64_t e = found; e < k; ++e) { orow[e] = 0xFFFFFFFFu; od[e] = INFINITY; if (og) og[e] = 0; }
+        // (k may be huge -- "keep everything": the caller's buffers are [nq * k * m] all the same)
+        for (uint64_t e = 0; e < k; ++e) {
+            const uint32_t h = e < found ? have[e] : 0u;
+            for (uint64_t i = h; i < m; ++i) { orow[e * m + i] = 0xFFFFFFFFu; od[e * m + i] = INFINITY; }
+            if (og && e >= found) og[e] = 0;
+            if (ogr) ogr[e] = h;
+        }
         if (n_found) n_found[q] = found;
     }
     return PQV_OK;
 }
 }  // namespace
+// (a grouped call: mv->group_size = m >= 1, row_idx / dist [nq, k, m] and group_rows [nq, k]; m == 1 is the distinct call plus group_rows)
 static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
                                   uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                                  int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
+                                  int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates, uint32_t *group_rows = nullptr) {
     if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
     if (int rc = dot_checks(s, k, nprobe, metric, mv)) return rc;
     if (nq == 0) return PQV_OK;
@@ -5111,44 +5198,53 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
         std::vector<float> nq_host;
         if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
         return pqv_topk_distinct_impl(s->cos.get(), mv, nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist,
-                                      group_key, n_found, n_candidates);
+                                      group_key, n_found, n_candidates, group_rows);
     }
+    const uint32_t m = std::max<uint32_t>(1, mv->group_size);
     std::lock_guard<std::mutex> lock(s->mu);
     Scratch *lane = nullptr;
     if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
     Scratch &sc = *lane;
     LaneGuard lane_guard{sc, s->stream};
-    if (beyond_kernel_lists(s, k, nprobe)) {
+    if (grouped_beyond_kernel_lists(s, k, m, nprobe)) {
         const int rc = distinct_unbounded(s, sc, mv, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, group_key, n_found,
-                                          n_candidates);
+                                          n_candidates, m, group_rows);
         const int rc2 = lane_release(sc, s->stream);
         return rc ? rc : rc2;
     }
     // sub-batches as the keyed form slices them: the per-wave partial lists (20 B per entry here) stay under ~1 GiB
     const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), nprobe, k, metric, true);
-    const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * k * 20 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
-                               static_cast<uint64_t>(p1.np) * 32 + static_cast<uint64_t>(s->sdim + s->dim) * 4 + 20ull * k + 16;
+    // (a grouped call's second pass: 16 B per entry of k * m, in the same buffers)
+    const uint64_t km = static_cast<uint64_t>(k) * m;
+    const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * std::max<uint64_t>(k * 20ull, m > 1 ? km * 16 + 4 : 0) +
+                               static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
+                               static_cast<uint64_t>(p1.np) * 32 + static_cast<uint64_t>(s->sdim + s->dim) * 4 + 20ull * k + (m > 1 ? 8ull * km : 0) + 16;
     const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 30) / per_query)));
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
-    HIP_TRY(sc.s_rows.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
-    HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(batch) * k * sizeof(float)));
+    HIP_TRY(sc.s_rows.ensure(static_cast<size_t>(batch) * km * sizeof(uint32_t)));
+    HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(batch) * km * sizeof(float)));
     HIP_TRY(sc.s_grp_out.ensure(static_cast<size_t>(batch) * k * sizeof(int64_t)));
+    if (group_rows) HIP_TRY(sc.s_grows_out.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
     HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
     MaskView sub = *mv;
     sub.d_group_out = sc.s_grp_out.as<int64_t>();
+    sub.d_group_rows = group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr;
     for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
         const uint32_t b = std::min<uint32_t>(batch, nq - q0);
         const uint64_t o = static_cast<uint64_t>(q0) * k;
         const size_t nk = static_cast<size_t>(b) * k;
+        const uint64_t om = o * m;
+        const size_t nkm = nk * m;
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
                                hipMemcpyHostToDevice, s->stream));
         if (int rc = enqueue_topk(s, sc.s_queries.as<float>(), b, k, k, nprobe, max_candidates, metric, sqrt_out, sc.s_rows.as<uint32_t>(),
                                   sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_ncand.as<uint64_t>(), nullptr, s->stream, sc, &sub))
             return rc;
-        HIP_TRY(hipMemcpyAsync(row_idx + o, sc.s_rows.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(dist + o, sc.s_dist.p, nk * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(row_idx + om, sc.s_rows.p, nkm * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(dist + om, sc.s_dist.p, nkm * sizeof(float), hipMemcpyDeviceToHost, s->stream));
         if (group_key) HIP_TRY(hipMemcpyAsync(group_key + o, sc.s_grp_out.p, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+        if (group_rows) HIP_TRY(hipMemcpyAsync(group_rows + o, sc.s_grows_out.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         if (n_candidates)
             HIP_TRY(hipMemcpyAsync(n_candidates + q0, sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
@@ -5174,6 +5270,42 @@ extern "C" int pqv_topk_distinct_device(const pqv_searcher *s, const pqv_row_key
         MaskView mv{};
         if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
         mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, nullptr, hip_stream, &mv);
+    });
+}
+
+// ---- grouped top-k (pqv.h: pqv_topk_grouped) ---------------------------------------------------------------------------------
+// distinct_view's checks with "group_size must be > 0" behind "k must be > 0" (both ahead of everything that reads a handle)
+static int grouped_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, uint32_t group_size, MaskView &mv) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
+    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (group_size == 0) return fail(PQV_ERR_INVALID, "group_size must be > 0");
+    if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
+    mv.group_size = group_size;
+    return PQV_OK;
+}
+extern "C" int pqv_topk_grouped(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                uint32_t query_len, uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric,
+                                int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found,
+                                uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
+        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
+                                      n_found, n_candidates, group_rows);
+    });
+}
+extern "C" int pqv_topk_grouped_device(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const void *d_queries,
+                                       uint32_t nq, uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric,
+                                       int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
+                                       void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
+        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
     });

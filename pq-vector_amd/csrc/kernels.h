@@ -146,6 +146,49 @@ struct DistinctMergeArgs {
 };
 hipError_t launch_distinct_merge(const DistinctMergeArgs &a, hipStream_t s);
 
+// ---- grouped top-k (kernels_grouped.hip; pqv.h: pqv_topk_grouped) --------------------------------------------------------
+// Pass 2 of the call: pass 1 (the distinct stream and fold above) has written the k nearest groups' values and n_found.  Every
+// launcher takes k * group_size == km <= 1024 with group_size >= 2, hence k <= GROUPED_SET_MAX.
+constexpr uint32_t GROUPED_SET_MAX = 512;
+// the first n_found[q] values of group_key [nq][k], ascending, to set_keys [nq][k], and each value's rank in pass 1 (its slot) to
+// set_slot [nq][k] (group_set_kernel; the padding of group_key is not read)
+hipError_t launch_group_set(const int64_t *group_key, const uint32_t *n_found, uint32_t nq, uint32_t k, int64_t *set_keys, uint32_t *set_slot,
+                            hipStream_t s);
+struct GroupedArgs {
+    const uint64_t     *bits;       // optional: a shared row mask's image (MaskedArgs::bits)
+    unsigned long long *stats;      // as MaskedArgs::stats: the rows evaluated are added to embeddings_fetched (candidate_rows is pass 1's)
+    const void         *key_pos;    // i32 / i64 [n_words * 64]: the group value of every list position
+    const uint64_t     *valid_pos;  // optional [n_words]: positions whose key is not NULL
+    uint32_t            elem_size;  // 4 or 8
+    const int64_t      *set_keys;   // launch_group_set's outputs
+    const uint32_t     *set_slot;
+    const uint32_t     *n_found;    // [nq]: the sets' sizes
+    uint32_t            k, group_size, km;
+    uint64_t           *part_keys;  // [nq][n_part][km], n_part = nprobe * blocks_per_list * 4: the first part_cnt entries of a list are written
+    uint32_t           *part_vals;
+    uint32_t           *part_slot;
+    uint32_t           *part_cnt;   // [nq][n_part]
+};
+// launch_distinct_stream's walk over the positions whose group value is in the query's set, per-wave lists of at most group_size
+// entries per slot (grouped_stream_kernel); StreamArgs::k / part_keys / part_vals are not read
+hipError_t launch_grouped_stream(const StreamArgs &a, const GroupedArgs &ga, hipStream_t s);
+// the fold of those lists, one wave per query (grouped_merge_kernel)
+struct GroupedMergeArgs {
+    const uint64_t *part_keys;
+    const uint32_t *part_vals;
+    const uint32_t *part_slot;
+    const uint32_t *part_cnt;
+    uint32_t        nq, n_part, k, group_size, km;
+    const uint32_t *ids;         // storage row -> reported row (nullptr => identity)
+    uint32_t       *row_idx;     // [nq, k, group_size]
+    float          *dist;        // [nq, k, group_size]
+    uint32_t       *group_rows;  // [nq, k] or nullptr
+    int             sqrt_out;    // 0 d2, 1 sqrt(d2), 2 0.5 d2 (PQV_COSINE)
+};
+hipError_t launch_grouped_merge(const GroupedMergeArgs &a, hipStream_t s);
+// group_size == 1 (the distinct call, one row per group): group_rows[q][g] = g < n_found[q] ? 1 : 0
+hipError_t launch_group_rows_fill(const uint32_t *n_found, uint32_t nq, uint32_t k, uint32_t *group_rows, hipStream_t s);
+
 // ---- predicate masks (kernels_predicate.hip) -----------------------------------------------------------------------------
 // A mask's ROW IMAGE is the bitset in row order: bit r of word r / 64 = row r is allowed, ceil(n_rows / 64) words, bits of rows
 // >= n_rows zero.  predicate_rows_kernel writes it from resident columns and a postfix program (pqv.h:

@@ -5,6 +5,7 @@
 // Header-only RAII wrappers; errors become pqv::Error carrying the reference's message text.
 #pragma once
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -188,6 +189,20 @@ public:
         found.assign(nq, 0);
         check(pqv_topk_distinct(s.get(), h_.get(), mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, nprobe, 0, PQV_L2SQ_REF4, 1,
                                 rows.data(), dist.data(), group_keys.data(), found.data(), nullptr));
+    }
+    // grouped top-k (pqv.h: pqv_topk_grouped): up to group_size rows of each of the k nearest key values; rows / dist are [nq, k,
+    // group_size], group_keys / group_rows [nq, k] (the rows returned per group), found[q] groups per query
+    void topk_grouped(const Searcher &s, const std::vector<float> &queries, uint32_t k, uint32_t group_size, uint32_t nprobe,
+                      std::vector<uint32_t> &rows, std::vector<float> &dist, std::vector<int64_t> &group_keys,
+                      std::vector<uint32_t> &group_rows, std::vector<uint32_t> &found, const RowMask *mask = nullptr) const {
+        const uint32_t nq = s.dim() ? static_cast<uint32_t>(queries.size() / s.dim()) : 0;
+        rows.assign(static_cast<size_t>(nq) * k * group_size, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k * group_size, std::numeric_limits<float>::infinity());
+        group_keys.assign(static_cast<size_t>(nq) * k, 0);
+        group_rows.assign(static_cast<size_t>(nq) * k, 0);
+        found.assign(nq, 0);
+        check(pqv_topk_grouped(s.get(), h_.get(), mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, group_size, nprobe, 0,
+                               PQV_L2SQ_REF4, 1, rows.data(), dist.data(), group_keys.data(), group_rows.data(), found.data(), nullptr));
     }
 private:
     struct Del { void operator()(pqv_row_keys *p) const { pqv_row_keys_free(p); } };
