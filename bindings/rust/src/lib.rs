@@ -490,6 +490,65 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// [`Searcher::topk_keyed`] under any per-query filter: a key, an inclusive range or a set per query (`include/pqv.h`:
+    /// `pqv_topk_filtered`).  Sets are sorted and de-duplicated here; one beyond `PQV_KEY_SET_MAX` values is refused.
+    pub fn topk_filtered(&self, keys: &RowKeys, filter: &KeyFilter, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,
+                         nprobe: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        // (the arrays the descriptor points at live until the call has returned)
+        let lims: Vec<u64>;
+        let vals: Vec<i64>;
+        let desc = match filter {
+            KeyFilter::Eq(a) => {
+                if a.len() != nq {
+                    return Err("one query key per query".into());
+                }
+                sys::PqvKeyFilter { kind: sys::PQV_KEY_EQ, reserved: 0, a: a.as_ptr() as *const c_void, b: ptr::null() }
+            }
+            KeyFilter::Range(lo, hi) => {
+                if lo.len() != nq || hi.len() != nq {
+                    return Err("one lower and one upper bound per query".into());
+                }
+                sys::PqvKeyFilter { kind: sys::PQV_KEY_RANGE, reserved: 0, a: lo.as_ptr() as *const c_void, b: hi.as_ptr() as *const c_void }
+            }
+            KeyFilter::In(sets) => {
+                if sets.len() != nq {
+                    return Err("one query key set per query".into());
+                }
+                let mut l = vec![0u64; nq + 1];
+                let mut v: Vec<i64> = Vec::new();
+                for (q, set) in sets.iter().enumerate() {
+                    let mut s = set.clone();
+                    s.sort_unstable();
+                    s.dedup();
+                    if s.len() > sys::PQV_KEY_SET_MAX {
+                        return Err("a query key set takes at most 1024 values".into());
+                    }
+                    v.extend_from_slice(&s);
+                    l[q + 1] = v.len() as u64;
+                }
+                if v.is_empty() {
+                    v.push(0); // (never read: a readable address for the descriptor)
+                }
+                lims = l;
+                vals = v;
+                sys::PqvKeyFilter { kind: sys::PQV_KEY_IN, reserved: 0, a: lims.as_ptr() as *const c_void, b: vals.as_ptr() as *const c_void }
+            }
+        };
+        let (k, np) = (k.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_filtered(self.raw, keys.raw, &desc, mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(),
+                                   nq as u32, dim as u32, k as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(),
+                                   dist.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
     /// The nearest row of each of the `k` nearest groups -- a group is the considered rows of one value of `keys` (NULL-key rows
     /// belong to none), under `mask` where one is given (`include/pqv.h`: `pqv_topk_distinct`).  Ascending by (distance, position).
     pub fn topk_distinct(&self, keys: &RowKeys, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,
@@ -692,6 +751,14 @@ impl RowKeys {
     pub fn rows(&self) -> u64 { unsafe { sys::pqv_row_keys_rows(self.raw) } }
     /// `PQV_COL_I32` or `PQV_COL_I64`
     pub fn dtype(&self) -> i32 { unsafe { sys::pqv_row_keys_dtype(self.raw) } }
+}
+
+/// One filter per query of a [`Searcher::topk_filtered`] call, compared in i64 against the key column (`include/pqv.h`:
+/// `pqv_key_filter`): a key, an inclusive range (`lo > hi` matches nothing), or a set (empty: matches nothing).
+pub enum KeyFilter {
+    Eq(Vec<i64>),
+    Range(Vec<i64>, Vec<i64>),
+    In(Vec<Vec<i64>>),
 }
 
 impl Drop for RowKeys {

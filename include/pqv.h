@@ -573,6 +573,50 @@ int pqv_range_search_keyed(const pqv_searcher *searcher, const pqv_row_keys *key
                            uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                            uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates);
 
+/* Per-query filters beyond equality: `key IN (...)` (the groups a user belongs to) and `key BETWEEN ? AND ?` (a window of
+ * timestamps, prices, versions) per query of one batch.  A filtered call is its keyed twin with a filter descriptor where the
+ * twin has `qkeys`: with F_q(v) the descriptor's test for query q on an i64 value and
+ *     M_q[r] = valid[r] && F_q((int64_t) column[r]) && (mask ? mask[r] : 1)
+ * query q returns, bit for bit, what the masked twin returns for that one query under the mask M_q -- candidates, counts, path,
+ * ties, sqrt_out, max_results, the PQV_COSINE halving, the limits beyond the kernels' lists and the PQV_DOT refusal are the keyed
+ * contract above, word for word.
+ *   PQV_KEY_EQ     a: int64_t [nq].  key == a[q]: pqv_topk_keyed* exactly.  b is not read.
+ *   PQV_KEY_RANGE  a, b: int64_t [nq].  a[q] <= key && key <= b[q], both ends inclusive; a[q] > b[q] matches nothing and is no
+ *                  error; [INT64_MIN, INT64_MAX] matches every valid row.
+ *   PQV_KEY_IN     a: uint64_t lims [nq + 1], b: int64_t values.  key is one of b[a[q] .. a[q + 1]).  lims[0] == 0, lims does not
+ *                  decrease, every query's slice is strictly ascending (sorted, no duplicates) and holds at most PQV_KEY_SET_MAX
+ *                  values; an empty slice matches nothing.
+ * Comparisons are in i64: an I32 column is widened, never truncated, so a range or a set beyond the i32 values matches nothing
+ * there.  A NULL row never matches.  `reserved` must be 0.
+ * The host forms validate the descriptor before any device use, ahead of the keyed calls' own checks and in this order
+ * (PQV_ERR_INVALID): "filter must not be NULL", "unknown key filter kind N", "query keys must not be NULL" (a, and b where the
+ * kind reads it), "query key sets must start at 0 and not decrease", "a query key set takes at most 1024 values", "query key
+ * sets must be strictly ascending".  The device form takes a and b as DEVICE arrays read on hip_stream inside the enqueued work,
+ * so the call stays asynchronous and a set cannot be validated: the kernels read at most PQV_KEY_SET_MAX values of a slice and
+ * never anything outside b[a[q] .. a[q + 1]); for a slice that is longer or not strictly ascending that query's result is
+ * unspecified, and every access stays inside the slice. */
+#define PQV_KEY_EQ     0
+#define PQV_KEY_RANGE  1
+#define PQV_KEY_IN     2
+#define PQV_KEY_SET_MAX 1024
+typedef struct pqv_key_filter {
+    uint32_t    kind;      /* PQV_KEY_* */
+    uint32_t    reserved;  /* 0 */
+    const void *a;
+    const void *b;
+} pqv_key_filter;
+int pqv_topk_filtered(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                      const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates,
+                      int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_filtered_device(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_key_filter *filter,
+                             const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                             uint64_t max_candidates, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found,
+                             void *d_n_candidates, void *d_tie_flags, void *hip_stream);
+int pqv_range_search_filtered(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_key_filter *filter,
+                              const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len, float radius,
+                              uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
+                              uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates);
+
 /* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
  * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.
  *

@@ -14,6 +14,8 @@ Host-side mirror of the reference's Rust API over the C ABI of include/pqv.h:
     index scan over a table of files         TableTopkBuilder(paths, query).k(k).nprobe(n).search()
       (df_vector/index_exec.rs:85-164)         -> [TableSearchResult(path, row_idx, distance)]
     VectorTopKOptions{max_candidates: Some(m)} TableTopkBuilder(...).max_candidates(m) (round robin over the files)
+    WHERE tenant = ? / ts BETWEEN ? AND ? /  Searcher.row_keys(column) + topk / range_search / topk_device (keys=..., and one of
+      grp IN (...), one filter PER QUERY       query_keys= / query_key_ranges=(lo, hi) / query_key_sets=[...])
     WHERE <predicate> inside the scan        every builder: .where(bool array | RowMask | pyarrow expression | predicate);
       (df_vector/exec.rs:207-277)              Searcher.row_mask(allowed) + topk / range_search / topk_device (mask=...)
                                                predicates (col("id") >= 2, & | ~) run on the GPU over resident Columns
@@ -31,11 +33,13 @@ from .api import (CandidateCursor, Column, Corpus, DistinctSearchResult, GroupSe
 from .parquet_io import has_pq_vector_index, load_scalar_column, read_index_from_parquet, row_mask_from_expression
 from .predicate import allowed, col
 from ._ffi import (PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE, PQV_L2SQ_MFMA, PQV_DOT, PQV_LAYOUT_IVF_ORDERED, PQV_LAYOUT_ROW_ORDER,
-                   PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, PQV_PREPARE_COSINE, LIB_PATH)
+                   PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, PQV_PREPARE_COSINE, PQV_KEY_EQ, PQV_KEY_RANGE, PQV_KEY_IN,
+                   PQV_KEY_SET_MAX, LIB_PATH)
 
 __all__ = ["RowMask", "RowKeys", "DistinctSearchResult", "GroupSearchResult", "TableDistinctSearchResult", "Column", "col", "allowed", "load_scalar_column", "row_mask_from_expression", "CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
            "TopkBuilder", "TableRangeBuilder", "TableSearcher", "TableSearchResult", "TableTopkBuilder", "searcher_for_parquet_files",
            "split_table_rows", "device_count", "merge_topk", "rerank_batch", "rerank_finish", "searcher_for_parquet", "PQV_COSINE", "PQV_L2SQ_MFMA", "PQV_DOT",
            "has_pq_vector_index", "read_index_from_parquet", "PQV_L2SQ_REF4",
            "PQV_L2SQ_SEQ", "PQV_LAYOUT_IVF_ORDERED", "PQV_LAYOUT_ROW_ORDER",
-           "PQV_RELEASE_ROW_ORDER", "PQV_RELEASE_IF_COPIED", "PQV_TABLE_CAP_ROUND_ROBIN", "PQV_PREPARE_COSINE", "round_robin_quota", "LIB_PATH"]
+           "PQV_RELEASE_ROW_ORDER", "PQV_RELEASE_IF_COPIED", "PQV_TABLE_CAP_ROUND_ROBIN", "PQV_PREPARE_COSINE", "round_robin_quota", "LIB_PATH",
+           "PQV_KEY_EQ", "PQV_KEY_RANGE", "PQV_KEY_IN", "PQV_KEY_SET_MAX"]

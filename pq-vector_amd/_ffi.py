@@ -46,6 +46,14 @@ PQV_OP_NOT = 0x100
 PQV_PRED_AND = 0x80
 PQV_PRED_OR = 0x81
 
+# per-query key filters (pqv.h: pqv_key_filter)
+PQV_KEY_EQ, PQV_KEY_RANGE, PQV_KEY_IN = 0, 1, 2
+PQV_KEY_SET_MAX = 1024
+
+
+class KeyFilter(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("a", C.c_void_p), ("b", C.c_void_p)]
+
 
 class Counters(C.Structure):
     _fields_ = [("queries", C.c_uint64), ("candidate_rows", C.c_uint64),
@@ -160,6 +168,12 @@ SIGNATURES = {
                                         vp, vp, vp, vp, vp, vp]),
     "pqv_range_search_keyed": (C.c_int, [vp, vp, i64p, vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64,
                                          C.c_uint64, C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
+    "pqv_topk_filtered": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                    C.c_int, C.c_int, u32p, f32p, u32p, u64p]),
+    "pqv_topk_filtered_device": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int,
+                                           C.c_int, vp, vp, vp, vp, vp, vp]),
+    "pqv_range_search_filtered": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64,
+                                            C.c_uint64, C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_topk_distinct": (C.c_int, [vp, vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
                                     u32p, f32p, i64p, u32p, u64p]),
     "pqv_topk_distinct_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,

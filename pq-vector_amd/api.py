@@ -628,6 +628,64 @@ def _query_keys(query_keys, nq):
     return a
 
 
+def key_sets_to_csr(query_key_sets, nq):
+    """A host call's query key sets (a sequence of nq iterables of integers) -> (lims uint64 [nq + 1], vals int64): every set
+    sorted with duplicates removed, as pqv.h: PQV_KEY_IN wants it.  ValueError beyond PQV_KEY_SET_MAX distinct values in a set."""
+    sets = list(query_key_sets)
+    if len(sets) != nq:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{len(sets)} query key sets for {nq} queries")
+    parts = []
+    lims = np.zeros(nq + 1, dtype=np.uint64)
+    for i, one in enumerate(sets):
+        a = np.asarray(one if isinstance(one, np.ndarray) else list(one))
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"query keys must be integers, got {a.dtype}")
+        if a.dtype == np.uint64 and a.size and int(a.max()) > 0x7FFFFFFFFFFFFFFF:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "query keys must fit int64")
+        a = np.unique(a.reshape(-1).astype(np.int64))
+        if a.size > _ffi.PQV_KEY_SET_MAX:
+            raise ValueError(f"a query key set takes at most {_ffi.PQV_KEY_SET_MAX} values, query {i} has {a.size}")
+        parts.append(a)
+        lims[i + 1] = lims[i] + np.uint64(a.size)
+    vals = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64), dtype=np.int64)
+    if vals.size == 0:
+        vals = np.zeros(1, dtype=np.int64)      # (never read: a readable address for the descriptor)
+    return lims, vals
+
+
+def _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq, device=False):
+    """The per-query filter of a call: None (no keys= argument), ("keyed", handle, int64 array or device pointer) for query_keys=, or
+    ("filtered", handle, KeyFilter, the arrays it points at) for query_key_ranges= / query_key_sets=.  Exactly one of the three goes
+    with keys=."""
+    given = [n for n, v in (("query_keys", query_keys), ("query_key_ranges", query_key_ranges), ("query_key_sets", query_key_sets))
+             if v is not None]
+    if keys is None and not given:
+        return None
+    if len(given) > 1:
+        raise PqvError(_ffi.PQV_ERR_INVALID, " and ".join(given) + " are mutually exclusive")
+    if query_key_ranges is None and query_key_sets is None:
+        kh = _keys_handle(keys, query_keys)
+        return ("keyed", kh, query_keys if device else _query_keys(query_keys, nq))
+    kh = _keys_handle(keys, True)
+    if query_key_ranges is not None:
+        try:
+            lo, hi = query_key_ranges
+        except (TypeError, ValueError):
+            raise PqvError(_ffi.PQV_ERR_INVALID, "query_key_ranges must be a pair (lo, hi)") from None
+        if device:
+            return ("filtered", kh, _ffi.KeyFilter(_ffi.PQV_KEY_RANGE, 0, int(lo) or None, int(hi) or None), ())
+        lo, hi = _query_keys(lo, nq), _query_keys(hi, nq)
+        return ("filtered", kh, _ffi.KeyFilter(_ffi.PQV_KEY_RANGE, 0, lo.ctypes.data, hi.ctypes.data), (lo, hi))
+    if device:
+        try:
+            d_lims, d_vals = query_key_sets
+        except (TypeError, ValueError):
+            raise PqvError(_ffi.PQV_ERR_INVALID, "query_key_sets of a device call must be a pair (ptr_lims, ptr_vals)") from None
+        return ("filtered", kh, _ffi.KeyFilter(_ffi.PQV_KEY_IN, 0, int(d_lims) or None, int(d_vals) or None), ())
+    lims, vals = key_sets_to_csr(query_key_sets, nq)
+    return ("filtered", kh, _ffi.KeyFilter(_ffi.PQV_KEY_IN, 0, lims.ctypes.data, vals.ctypes.data), (lims, vals))
+
+
 def _allow_array(allowed, n_rows, what="row mask"):
     """A caller's allow array -> contiguous uint8 [n_rows]: bool or uint8, one entry per row; anything else is refused."""
     if allowed is None:
@@ -768,11 +826,14 @@ class Searcher:
         return RowKeys(h, self)
 
     def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None, keys=None,
-             query_keys=None):
+             query_keys=None, query_key_ranges=None, query_key_sets=None):
         """Batched topk(); returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq], n_candidates [nq]).
         mask (a RowMask of this searcher): only allowed rows are considered (pqv.h: pqv_topk_masked).
         keys (a RowKeys of this searcher) with query_keys (int [nq]): query q considers only the rows whose key equals
-        query_keys[q], within mask if one is given too (pqv.h: pqv_topk_keyed)."""
+        query_keys[q], within mask if one is given too (pqv.h: pqv_topk_keyed).  Instead of query_keys:
+        query_key_ranges=(lo, hi) (int [nq] each): lo[q] <= key <= hi[q], both inclusive; or query_key_sets (nq iterables of
+        integers, at most PQV_KEY_SET_MAX distinct values each; sorted and de-duplicated here): key in the query's set
+        (pqv.h: pqv_topk_filtered)."""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -781,9 +842,15 @@ class Searcher:
         dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
-        if keys is not None or query_keys is not None:
-            kh = _keys_handle(keys, query_keys)
-            qk = _query_keys(query_keys, nq)
+        kf = _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if kf is not None and kf[0] == "filtered":
+            _check(_ffi.lib().pqv_topk_filtered(self._h, kf[1], C.byref(kf[2]), _mask_handle(self, mask) if mask is not None else None,
+                                                q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
+                                                nc.ctypes.data_as(u64p)))
+            return rows, dist, nf, nc
+        if kf is not None:
+            kh, qk = kf[1], kf[2]
             _check(_ffi.lib().pqv_topk_keyed(self._h, kh, qk.ctypes.data_as(_ffi.i64p), _mask_handle(self, mask) if mask is not None else None,
                                              q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
                                              rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
@@ -864,9 +931,10 @@ class Searcher:
                                                   vp(d_n_found or None), vp(d_n_candidates or None), vp(stream or None)))
 
     def range_search(self, queries, radius, nprobe, max_candidates=0, max_results=0, metric=_ffi.PQV_L2SQ_REF4,
-                     sqrt_out=True, mask=None, keys=None, query_keys=None):
+                     sqrt_out=True, mask=None, keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None):
         """Every candidate within `radius` of each query (pqv.h: pqv_range_search), ascending by (d2, candidate position).
-        mask / keys + query_keys: as topk (pqv.h: pqv_range_search_masked, pqv_range_search_keyed).
+        mask / keys + query_keys / query_key_ranges / query_key_sets: as topk (pqv.h: pqv_range_search_masked,
+        pqv_range_search_keyed, pqv_range_search_filtered).
         Returns (lims u64 [nq+1], rows u32, dist f32, n_within u64 [nq], n_candidates u64 [nq]): query q's hits are
         rows / dist [lims[q]:lims[q+1]]; n_within is the hit count before max_results."""
         q = _f32(queries)
@@ -883,9 +951,15 @@ class Searcher:
         nw = np.zeros(nq, dtype=np.uint64)
         nc = np.zeros(nq, dtype=np.uint64)
         lims_p, rows_p, dist_p = u64p(), u32p(), f32p()
-        if keys is not None or query_keys is not None:       # (pqv.h: pqv_range_search_keyed)
-            kh = _keys_handle(keys, query_keys)
-            qk = _query_keys(query_keys, nq)
+        kf = _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if kf is not None and kf[0] == "filtered":       # (pqv.h: pqv_range_search_filtered)
+            _check(_ffi.lib().pqv_range_search_filtered(self._h, kf[1], C.byref(kf[2]),
+                                                        _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
+                                                        qlen, radius, nprobe, max_candidates, max_results, metric, 1 if sqrt_out else 0,
+                                                        C.byref(lims_p), C.byref(rows_p), C.byref(dist_p), nw.ctypes.data_as(u64p),
+                                                        nc.ctypes.data_as(u64p)))
+        elif kf is not None:       # (pqv.h: pqv_range_search_keyed)
+            kh, qk = kf[1], kf[2]
             _check(_ffi.lib().pqv_range_search_keyed(self._h, kh, qk.ctypes.data_as(_ffi.i64p),
                                                      _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
                                                      qlen, radius, nprobe, max_candidates, max_results, metric, 1 if sqrt_out else 0,
@@ -910,7 +984,7 @@ class Searcher:
 
     def topk_device(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0,
                     max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0, mask=None, keys=None,
-                    query_keys=None):
+                    query_keys=None, query_key_ranges=None, query_key_sets=None):
         """Device-pointer form (ints from tensor.data_ptr()); asynchronous on `stream` -- a hipStream_t handle; 0 means the
         searcher's OWN non-blocking stream, not HIP's / torch's default stream (whose handle is 0 too): work that must follow
         the call on the default stream is NOT ordered behind it, so pass an explicit stream (1 = hipStreamLegacy names the default
@@ -918,9 +992,19 @@ class Searcher:
         also flag the queries whose answer depends on the reference's heap history (re-submit those to topk()).
         mask (a RowMask of this searcher, alive until the enqueued work has completed): pqv.h: pqv_topk_masked_device.
         keys (a RowKeys of this searcher) with query_keys (the device pointer of int64 [nq], read on `stream` inside the enqueued
-        work): pqv.h: pqv_topk_keyed_device; combinable with mask."""
-        if keys is not None or query_keys is not None:
-            kh = _keys_handle(keys, query_keys)
+        work): pqv.h: pqv_topk_keyed_device; combinable with mask.  Instead of query_keys: query_key_ranges=(ptr_lo, ptr_hi), device
+        pointers of int64 [nq] each, or query_key_sets=(ptr_lims, ptr_vals), device pointers of uint64 [nq + 1] offsets and of the
+        int64 values, every query's slice strictly ascending and at most PQV_KEY_SET_MAX long -- not validated, the call stays
+        asynchronous (pqv.h: pqv_topk_filtered_device)."""
+        kf = _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        if kf is not None and kf[0] == "filtered":
+            _check(_ffi.lib().pqv_topk_filtered_device(self._h, kf[1], C.byref(kf[2]), _mask_handle(self, mask) if mask is not None else None,
+                                                       vp(d_queries), nq, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                       vp(d_row_idx), vp(d_dist), vp(d_n_found or None), vp(d_n_candidates or None),
+                                                       vp(d_tie_flags or None), vp(stream or None)))
+            return
+        if kf is not None:
+            kh = kf[1]
             _check(_ffi.lib().pqv_topk_keyed_device(self._h, kh, vp(query_keys or None), _mask_handle(self, mask) if mask is not None else None,
                                                     vp(d_queries), nq, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
                                                     vp(d_row_idx), vp(d_dist), vp(d_n_found or None), vp(d_n_candidates or None),

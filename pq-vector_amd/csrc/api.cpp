@@ -322,6 +322,8 @@ struct Scratch {
         s_pair_end, s_file_cnt,     // round-robin capped tables: per-pair candidate ends, per-file counts (SegProbeArgs)
         s_qcos,                     // PQV_COSINE: the call's normalised queries n(q), read by the cosine searcher's kernels
         s_qkeys,                    // keyed host calls (pqv_row_keys): the sub-batch's query keys, i64 [b]
+        s_qfilt_a, s_qfilt_b,       // filtered host calls (pqv_key_filter): the sub-batch's a / b -- RANGE: lo, hi i64 [b]; IN: lims rebased to the
+                                    // sub-batch u64 [b + 1], its slice of the values
         s_part_grp, s_grp_out,      // distinct calls: the partial lists' group values i64 [nq][n_part][k]; the host form's group_key block
         // grouped calls (pqv_topk_grouped): pass 1's rows / distances [nq][k] (not reported), its group values and n_found where the caller
         // takes none, the sorted sets [nq][k], the partial lists' slots [nq][n_part][k * group_size] and lengths [nq][n_part], and the
@@ -340,7 +342,7 @@ struct Scratch {
                 &s_dist, &s_nfound, &s_pair_u32, &s_pairs, &s_groups, &s_quads, &s_items, &s_ticket, &s_ticket2, &s_cand_keys, &s_cand_vals, &s_cand_cnt, &s_spilled,
                 &s_seed_ub, &s_qblk, &s_gthr, &s_tie, &s_replay, &s_qnorm, &s_qmax, &s_thr_hist, &s_thr_bins, &s_qi8, &s_qn2i, &s_qres, &s_qresu, &s_pair_lb, &s_part_flags, &s_qpad, &s_cand_lb, &s_pendv, &s_work, &s_nwork, &s_out,
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
-                &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_part_grp, &s_grp_out,
+                &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
                 &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out};
     }
     ~Scratch() {
@@ -549,6 +551,9 @@ struct MaskView {
     const pqv_row_keys *keys;          // a keyed call's key column, else nullptr
     const int64_t *h_qkeys;            // host forms: [nq] query keys, indexed like the call's queries
     const int64_t *d_qkeys;            // device: the keys of the queries the kernels see (the current sub-batch's)
+    uint32_t fkind;                    // a filtered call (pqv_key_filter) of kind PQV_KEY_RANGE / PQV_KEY_IN, else 0 (PQV_KEY_EQ travels as h_qkeys / d_qkeys)
+    const void *h_fa, *h_fb;           // its host a / b, indexed like the call's queries (IN: lims [nq + 1] and the values)
+    const void *d_fa, *d_fb;           // device: a / b of the queries the kernels see (IN: lims rebased to the current sub-batch)
     const pqv_row_keys *group;         // a distinct call's group column, else nullptr (bits / mask: its shared mask, or nullptr)
     int64_t *d_group_out;              // distinct: where the fold writes the group values [nq * k] (device), or nullptr
     uint32_t group_size;               // a grouped call (pqv_topk_grouped; `group` set): rows per group, >= 1; 0: not grouped.  The call's row_idx / dist are
@@ -621,11 +626,20 @@ struct RowFilter {
     const uint8_t *allow = nullptr;
     const int64_t *key_vals = nullptr;
     const uint8_t *key_valid = nullptr;
-    int64_t qkey = 0;
+    int64_t qkey = 0;                              // EQ: the key; RANGE: the lower bound
+    uint32_t kind = PQV_KEY_EQ;
+    int64_t qhi = 0;                               // RANGE: the upper bound
+    const int64_t *set_beg = nullptr, *set_end = nullptr;      // IN: the query's slice, strictly ascending
     bool active() const { return allow || key_vals; }
     bool pass(uint32_t row) const {
         if (allow && !allow[row]) return false;
-        if (key_vals && ((key_valid && !key_valid[row]) || key_vals[row] != qkey)) return false;
+        if (key_vals) {
+            if (key_valid && !key_valid[row]) return false;
+            const int64_t v = key_vals[row];
+            if (kind == PQV_KEY_EQ) return v == qkey;
+            if (kind == PQV_KEY_RANGE) return qkey <= v && v <= qhi;
+            return std::binary_search(set_beg, set_end, v);
+        }
         return true;
     }
 };
@@ -637,7 +651,45 @@ static int row_filter(const pqv_searcher *s, const MaskView *mv, uint64_t q, Row
         if (int rc = keys_host_rows(s, mv->keys)) return rc;
         f.key_vals = mv->keys->host_vals.data();
         f.key_valid = mv->keys->has_valid ? mv->keys->host_valid.data() : nullptr;
-        f.qkey = mv->h_qkeys[q];
+        f.kind = mv->fkind;
+        if (mv->fkind == PQV_KEY_RANGE) {
+            f.qkey = static_cast<const int64_t *>(mv->h_fa)[q];
+            f.qhi = static_cast<const int64_t *>(mv->h_fb)[q];
+        } else if (mv->fkind == PQV_KEY_IN) {
+            const uint64_t *lims = static_cast<const uint64_t *>(mv->h_fa);
+            f.set_beg = static_cast<const int64_t *>(mv->h_fb) + lims[q];
+            f.set_end = static_cast<const int64_t *>(mv->h_fb) + lims[q + 1];
+        } else {
+            f.qkey = mv->h_qkeys[q];
+        }
+    }
+    return PQV_OK;
+}
+// A keyed or filtered host call's per-query arguments for the sub-batch [q0, q0 + b): uploaded on `st` into the lane's scratch,
+// `sub` pointed at them.  `lims` keeps an IN filter's rebased offsets alive until the sub-batch's synchronisation.
+static int upload_query_filter(Scratch &sc, const MaskView *mask, MaskView &sub, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
+                               hipStream_t st) {
+    if (!mask || !mask->keys) return PQV_OK;
+    if (mask->fkind == PQV_KEY_RANGE) {
+        HIP_TRY(sc.s_qfilt_a.ensure(static_cast<size_t>(b) * sizeof(int64_t)));
+        HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(b) * sizeof(int64_t)));
+        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, static_cast<const int64_t *>(mask->h_fa) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(mask->h_fb) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        sub.d_fa = sc.s_qfilt_a.p; sub.d_fb = sc.s_qfilt_b.p;
+    } else if (mask->fkind == PQV_KEY_IN) {
+        const uint64_t *hl = static_cast<const uint64_t *>(mask->h_fa);
+        const uint64_t base = hl[q0], n_vals = hl[q0 + b] - base;
+        try { lims.resize(static_cast<size_t>(b) + 1); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+        for (uint32_t i = 0; i <= b; ++i) lims[i] = hl[q0 + i] - base;
+        HIP_TRY(sc.s_qfilt_a.ensure((static_cast<size_t>(b) + 1) * sizeof(uint64_t)));
+        HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(n_vals) * sizeof(int64_t)));
+        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, lims.data(), (static_cast<size_t>(b) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (n_vals)
+            HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(mask->h_fb) + base, static_cast<size_t>(n_vals) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        sub.d_fa = sc.s_qfilt_a.p; sub.d_fb = sc.s_qfilt_b.p;
+    } else {
+        HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, mask->h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        sub.d_qkeys = sc.s_qkeys.as<int64_t>();
     }
     return PQV_OK;
 }
@@ -656,6 +708,12 @@ static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskVi
         const pqv_row_keys *kk = mv->keys;
         const pqv::KeyedArgs ka{mv->bits, stats, n_cand, kk->d_key_pos.p, kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr,
                                 mv->d_qkeys, kk->dtype == PQV_COL_I32 ? 4u : 8u};
+        if (mv->fkind) {
+            pqv::KeyFilterArgs fa{};
+            static_cast<pqv::KeyedArgs &>(fa) = ka;
+            fa.kind = mv->fkind; fa.a = mv->d_fa; fa.b = mv->d_fb;
+            return pqv::launch_key_filter_stream(ra, fa, mode, stream);
+        }
         return pqv::launch_keyed_stream(ra, ka, mode, stream);
     }
     const pqv::MaskedArgs ma{mv->bits, stats, n_cand};
@@ -4406,7 +4464,8 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     MaskView sub{};
     if (mask) sub = *mask;
     const MaskView *bmask = mask ? &sub : nullptr;
-    if (mask && mask->keys) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    if (mask && mask->keys && !mask->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    std::vector<uint64_t> sub_lims;
     // A call of a few queries (TopkBuilder::search is ONE) is six small pageable copies otherwise -- the query in, rows, distances,
     // counts and tie flags out, each staged and waited for by the runtime: 60-80 us around 180 us of kernels.  Small calls go
     // through ONE pinned buffer instead: the results are laid out as one device block {candidates u64 | rows | dist | found |
@@ -4428,10 +4487,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         // (round 5: the result block of a small call is WRITTEN by the kernels straight into the pinned buffer -- host memory the
         //  device can address -- so there is no device-to-host copy behind them, only the synchronise: PQV_SMALL_IO_DIRECT=0 keeps the copy)
         static const bool direct_out = [] { const char *e = std::getenv("PQV_SMALL_IO_DIRECT"); return !(e && *e == '0'); }();
-        if (mask && mask->keys) {
-            HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, mask->h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
-            sub.d_qkeys = sc.s_qkeys.as<int64_t>();
-        }
+        if (int rc = upload_query_filter(sc, mask, sub, q0, b, sub_lims, s->stream)) return rc;
         if (small_io) {
             char *ob = direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p);           // (laid out for THIS sub-batch's b)
             o_rows = reinterpret_cast<uint32_t *>(ob + 8ull * b);
@@ -4552,7 +4608,8 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
     HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
     MaskView sub{};      // (a keyed call: each sub-batch's kernels read its own slice of the query keys)
     if (mask) sub = *mask;
-    if (mask && mask->keys) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    if (mask && mask->keys && !mask->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    std::vector<uint64_t> sub_lims;
     std::vector<uint32_t> h_cnt(batch), h_probe;
     std::vector<uint64_t> h_ncand(batch), h_off(batch);
     std::vector<RangeSeg> segs;
@@ -4565,10 +4622,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         if (int rc = timing_events(s, e)) return rc;
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
                                hipMemcpyHostToDevice, st));
-        if (mask && mask->keys) {
-            HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, mask->h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            sub.d_qkeys = sc.s_qkeys.as<int64_t>();
-        }
+        if (int rc = upload_query_filter(sc, mask, sub, q0, b, sub_lims, st)) return rc;
         if (e[0]) HIP_TRY(hipEventRecord(e[0], st));
         const float *d_q = sc.s_queries.as<float>(), *d_q_s = d_q;
         if (s->sdim != s->dim) {
@@ -5087,6 +5141,69 @@ extern "C" int pqv_range_search_keyed(const pqv_searcher *s, const pqv_row_keys 
         MaskView mv{};
         if (int rc = keyed_view(s, keys, qkeys, nq, mask, mv)) return rc;
         mv.h_qkeys = qkeys;
+        return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
+                                     row_idx, dist, n_within, n_candidates, &mv);
+    });
+}
+
+// ---- per-query filters beyond equality (pqv.h: pqv_key_filter) ---------------------------------------------------------------
+// The descriptor's checks, ahead of keyed_view's; `host`: a and b are host arrays and a set filter is validated in full.  On
+// success the view carries the filter: PQV_KEY_EQ as the keyed calls' query keys, the other kinds in fkind / h_f* / d_f*.
+static int filtered_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *f, uint32_t nq, const pqv_row_mask *mask,
+                         bool host, MaskView &mv) {
+    if (!f) return fail(PQV_ERR_INVALID, "filter must not be NULL");
+    if (f->kind > PQV_KEY_IN) return fail(PQV_ERR_INVALID, "unknown key filter kind " + std::to_string(f->kind));
+    const bool reads_b = f->kind != PQV_KEY_EQ;
+    if (nq && (!f->a || (reads_b && !f->b))) return fail(PQV_ERR_INVALID, "query keys must not be NULL");
+    if (host && nq && f->kind == PQV_KEY_IN) {
+        const uint64_t *lims = static_cast<const uint64_t *>(f->a);
+        const int64_t *vals = static_cast<const int64_t *>(f->b);
+        if (lims[0] != 0) return fail(PQV_ERR_INVALID, "query key sets must start at 0 and not decrease");
+        for (uint32_t q = 0; q < nq; ++q)
+            if (lims[q + 1] < lims[q]) return fail(PQV_ERR_INVALID, "query key sets must start at 0 and not decrease");
+        for (uint32_t q = 0; q < nq; ++q)
+            if (lims[q + 1] - lims[q] > PQV_KEY_SET_MAX) return fail(PQV_ERR_INVALID, "a query key set takes at most 1024 values");
+        for (uint32_t q = 0; q < nq; ++q)
+            for (uint64_t i = lims[q] + 1; i < lims[q + 1]; ++i)
+                if (!(vals[i - 1] < vals[i])) return fail(PQV_ERR_INVALID, "query key sets must be strictly ascending");
+    }
+    if (int rc = keyed_view(s, keys, f->a, nq, mask, mv)) return rc;
+    if (f->kind == PQV_KEY_EQ) {
+        (host ? mv.h_qkeys : mv.d_qkeys) = static_cast<const int64_t *>(f->a);
+    } else {
+        mv.fkind = f->kind;
+        if (host) { mv.h_fa = f->a; mv.h_fb = f->b; }
+        else { mv.d_fa = f->a; mv.d_fb = f->b; }
+    }
+    return PQV_OK;
+}
+extern "C" int pqv_topk_filtered(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                                 const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates,
+                                 int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = filtered_view(s, keys, filter, nq, mask, true, mv)) return rc;
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
+    });
+}
+extern "C" int pqv_topk_filtered_device(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                                        const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric,
+                                        int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
+                                        void *d_tie_flags, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = filtered_view(s, keys, filter, nq, mask, false, mv)) return rc;
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, d_tie_flags, hip_stream, &mv);
+    });
+}
+extern "C" int pqv_range_search_filtered(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                                         const float *queries, uint32_t nq, uint32_t query_len, float radius, uint32_t nprobe,
+                                         uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t **lims,
+                                         uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = filtered_view(s, keys, filter, nq, mask, true, mv)) return rc;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
     });

@@ -114,6 +114,17 @@ struct KeyedArgs {
 };
 // launch_masked_stream with a window's bits taken from key_pos[p] == qkeys[q] (masked_stream_kernel, WIN = 1 / 2)
 hipError_t launch_keyed_stream(const StreamArgs &a, const KeyedArgs &ka, StreamMode mode, hipStream_t s);
+// A per-query filter descriptor (pqv.h: pqv_key_filter) on the device.  kind 0 (PQV_KEY_EQ): a = qkeys, the call above.  kind 1
+// (PQV_KEY_RANGE): a / b = i64 [nq] inclusive bounds, the window is the ballot of a[q] <= key && key <= b[q] (WIN = 3 / 4).  kind 2
+// (PQV_KEY_IN): a = u64 lims [nq + 1], b = i64 values; the block copies b[a[q] .. a[q + 1]) -- at most KEY_SET_MAX values of it --
+// into LDS and a lane's key is looked up there (WIN = 5 / 6).  KeyedArgs::qkeys is not read for kinds 1 and 2.
+constexpr uint32_t KEY_SET_MAX = 1024;
+struct KeyFilterArgs : KeyedArgs {
+    uint32_t    kind;
+    const void *a;
+    const void *b;
+};
+hipError_t launch_key_filter_stream(const StreamArgs &a, const KeyFilterArgs &fa, StreamMode mode, hipStream_t s);
 
 // ---- distinct top-k (kernels_distinct.hip; pqv.h: pqv_topk_distinct) -----------------------------------------------------
 // The group column is a key column's position image (launch_key_layout).  launch_distinct_stream is launch_masked_stream's

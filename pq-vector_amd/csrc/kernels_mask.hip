@@ -103,11 +103,21 @@ hipError_t launch_key_layout(const void *values, const uint8_t *valid, uint32_t 
 // (wave-uniform, loaded once) and the __ballot of the comparison is the window, ANDed with the funnel-shifted words of valid_pos
 // and of a shared mask where the call has them, and clipped like a mask's.  Everything behind the window is shared.
 //
+// WIN 3 / 4 (i32 / i64), a per-query RANGE (pqv.h: PQV_KEY_RANGE): the same load, the bounds lo / hi wave-uniform and loaded once,
+// the window the __ballot of lo <= kv && kv <= hi.  WIN 5 / 6, a per-query set (PQV_KEY_IN): the block copies its query's slice
+// vals[lims[q] .. lims[q + 1]) -- never more than KEY_SET_MAX values, never anything outside the slice -- into 8 KiB of LDS behind
+// the tile area before the first window (the kernel's one __syncthreads: every wave reaches it, the waves are independent behind
+// it) and a lane's key is looked up by a halving search whose trip count depends on the slice length only; the window is the
+// __ballot of "found".  An empty slice walks nothing.  A slice that is not ascending finds some keys and misses others; every
+// index the search forms stays below the slice length.
+//
 // Outputs: stream_kernel's (per-wave partial lists / hit segments).  Each wave adds the rows it evaluated to the
 // embeddings_fetched word of the query's statistics slot; the (0, 0) block of a query adds n_cand[q] to candidate_rows.
 // ------------------------------------------------------------------------------------
-template <int WIN> struct WinArgs { using type = KeyedArgs; };
+template <int WIN> struct WinArgs { using type = KeyFilterArgs; };
 template <> struct WinArgs<0> { using type = MaskedArgs; };
+template <> struct WinArgs<1> { using type = KeyedArgs; };
+template <> struct WinArgs<2> { using type = KeyedArgs; };
 
 template <int CG, int S, int MODE, bool SEQ, bool ALIGNED, int WIN = 0>
 __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, const typename WinArgs<WIN>::type ma) {
@@ -148,7 +158,23 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
     if (ma.n_cand && st && blockIdx.x == 0 && j == 0 && threadIdx.x == 0) atomicAdd(&st[2], (unsigned long long)ma.n_cand[q]);
 
     int64_t qkey = 0;
-    if constexpr (WIN != 0) qkey = ma.qkeys[q];
+    if constexpr (WIN == 1 || WIN == 2) qkey = ma.qkeys[q];
+    int64_t qhi = 0;            // WIN 3 / 4: the window is qkey <= kv && kv <= qhi
+    if constexpr (WIN == 3 || WIN == 4) {
+        qkey = static_cast<const int64_t *>(ma.a)[q];
+        qhi = static_cast<const int64_t *>(ma.b)[q];
+    }
+    const int64_t *kset = nullptr;
+    uint32_t kset_n = 0;        // WIN 5 / 6: the values of the query's set held in kset (block-uniform)
+    if constexpr (WIN >= 5) {
+        __shared__ int64_t set_lds[KEY_SET_MAX];
+        const uint64_t s0 = static_cast<const uint64_t *>(ma.a)[q], s1 = static_cast<const uint64_t *>(ma.a)[q + 1];
+        if (s1 > s0) kset_n = s1 - s0 > (uint64_t)KEY_SET_MAX ? KEY_SET_MAX : (uint32_t)(s1 - s0);
+        for (uint32_t i = threadIdx.x; i < kset_n; i += 256) set_lds[i] = static_cast<const int64_t *>(ma.b)[s0 + i];
+        __syncthreads();
+        kset = set_lds;
+        if (kset_n == 0) r1 = r0;      // (nothing matches: no window is read)
+    }
 
     const uint32_t dim = a.dim;
     const uint32_t G = dim >> 2;
@@ -175,9 +201,21 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
             } else {
                 // (key_pos is padded by a whole window: p + lane is always in range; positions >= r1 are clipped below)
                 int64_t kv;
-                if constexpr (WIN == 1) kv = (int64_t) static_cast<const int32_t *>(ma.key_pos)[p + (uint64_t)lane];
+                if constexpr (WIN & 1) kv = (int64_t) static_cast<const int32_t *>(ma.key_pos)[p + (uint64_t)lane];
                 else kv = static_cast<const int64_t *>(ma.key_pos)[p + (uint64_t)lane];
-                win = __ballot(kv == qkey);
+                if constexpr (WIN <= 2) {
+                    win = __ballot(kv == qkey);
+                } else if constexpr (WIN <= 4) {
+                    win = __ballot(qkey <= kv && kv <= qhi);
+                } else {
+                    uint32_t at = 0;
+                    for (uint32_t span = kset_n; span > 1;) {           // (wave-uniform trip count; at + half < kset_n)
+                        const uint32_t half = span >> 1;
+                        if (kset[at + half] <= kv) at += half;
+                        span -= half;
+                    }
+                    win = __ballot(kset[at] == kv);                     // (kset_n >= 1 here)
+                }
                 if (ma.valid_pos) win &= image_window(ma.valid_pos, p);
                 if (ma.bits) win &= image_window(ma.bits, p);
             }
@@ -356,6 +394,18 @@ hipError_t launch_keyed_stream(const StreamArgs &a, const KeyedArgs &ka, StreamM
     if (!ka.key_pos || !ka.qkeys) return hipErrorInvalidValue;
     if (ka.elem_size == 4) return launch_masked_w<1>(a, ka, mode, s);
     if (ka.elem_size == 8) return launch_masked_w<2>(a, ka, mode, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_key_filter_stream(const StreamArgs &a, const KeyFilterArgs &fa, StreamMode mode, hipStream_t s) {
+    if (fa.kind == 0) {       // PQV_KEY_EQ: the keyed call, unchanged
+        KeyedArgs ka = fa;
+        ka.qkeys = static_cast<const int64_t *>(fa.a);
+        return launch_keyed_stream(a, ka, mode, s);
+    }
+    if (!fa.key_pos || !fa.a || !fa.b || (fa.elem_size != 4 && fa.elem_size != 8)) return hipErrorInvalidValue;
+    if (fa.kind == 1) return fa.elem_size == 4 ? launch_masked_w<3>(a, fa, mode, s) : launch_masked_w<4>(a, fa, mode, s);
+    if (fa.kind == 2) return fa.elem_size == 4 ? launch_masked_w<5>(a, fa, mode, s) : launch_masked_w<6>(a, fa, mode, s);
     return hipErrorInvalidValue;
 }
 

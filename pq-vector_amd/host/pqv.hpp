@@ -4,6 +4,7 @@
 //   pqv::SearchResult   src/ivf/search.rs:41-45
 // Header-only RAII wrappers; errors become pqv::Error carrying the reference's message text.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <limits>
 #include <memory>
@@ -154,6 +155,42 @@ private:
     std::unique_ptr<pqv_row_mask, Del> h_;
 };
 
+// A per-query filter on a key column (pqv.h: pqv_key_filter): equals(keys), between(lo, hi) -- both ends inclusive -- or in_sets(sets),
+// one entry per query.  It owns copies of its arrays, a set filter sorts and de-duplicates every set; descriptor() stays valid
+// as long as the filter does.
+class KeyFilter {
+public:
+    static KeyFilter equals(std::vector<int64_t> keys) {
+        KeyFilter f; f.kind_ = PQV_KEY_EQ; f.a_ = std::move(keys); return f;
+    }
+    static KeyFilter between(std::vector<int64_t> lo, std::vector<int64_t> hi) {
+        if (lo.size() != hi.size()) throw std::invalid_argument("one lower and one upper bound per query");
+        KeyFilter f; f.kind_ = PQV_KEY_RANGE; f.a_ = std::move(lo); f.b_ = std::move(hi); return f;
+    }
+    static KeyFilter in_sets(const std::vector<std::vector<int64_t>> &sets) {
+        KeyFilter f; f.kind_ = PQV_KEY_IN; f.lims_.assign(1, 0);
+        for (std::vector<int64_t> s : sets) {
+            std::sort(s.begin(), s.end());
+            s.erase(std::unique(s.begin(), s.end()), s.end());
+            if (s.size() > PQV_KEY_SET_MAX) throw std::invalid_argument("a query key set takes at most 1024 values");
+            f.b_.insert(f.b_.end(), s.begin(), s.end());
+            f.lims_.push_back(f.b_.size());
+        }
+        if (f.b_.empty()) f.b_.push_back(0);      // (never read: a readable address for the descriptor)
+        return f;
+    }
+    uint32_t queries() const { return static_cast<uint32_t>(kind_ == PQV_KEY_IN ? lims_.size() - 1 : a_.size()); }
+    pqv_key_filter descriptor() const {
+        return pqv_key_filter{kind_, 0, kind_ == PQV_KEY_IN ? static_cast<const void *>(lims_.data()) : static_cast<const void *>(a_.data()),
+                              kind_ == PQV_KEY_EQ ? nullptr : static_cast<const void *>(b_.data())};
+    }
+private:
+    KeyFilter() = default;
+    uint32_t kind_ = PQV_KEY_EQ;
+    std::vector<int64_t> a_, b_;
+    std::vector<uint64_t> lims_;
+};
+
 // A key column laid out for one searcher (pqv.h: pqv_row_keys): every query of a keyed call is filtered by ITS OWN
 // `column == key`.  The column is copied; keys may outlive their searcher or be released before it.
 class RowKeys {
@@ -176,6 +213,17 @@ public:
         found.assign(nq, 0);
         check(pqv_topk_keyed(s.get(), h_.get(), qkeys.data(), mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, nprobe, 0,
                              PQV_L2SQ_REF4, 1, rows.data(), dist.data(), found.data(), nullptr));
+    }
+    // the same under any per-query filter -- a key, a range, a set (pqv.h: pqv_topk_filtered); nq = filter.queries()
+    void topk(const Searcher &s, const KeyFilter &filter, const std::vector<float> &queries, uint32_t k, uint32_t nprobe,
+              std::vector<uint32_t> &rows, std::vector<float> &dist, std::vector<uint32_t> &found, const RowMask *mask = nullptr) const {
+        const uint32_t nq = filter.queries();
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, 0.0f);
+        found.assign(nq, 0);
+        const pqv_key_filter d = filter.descriptor();
+        check(pqv_topk_filtered(s.get(), h_.get(), &d, mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, nprobe, 0,
+                                PQV_L2SQ_REF4, 1, rows.data(), dist.data(), found.data(), nullptr));
     }
     // distinct top-k with this column as the GROUP column (pqv.h: pqv_topk_distinct): per query the nearest row of each of the k
     // nearest key values; found[q] groups per query, k slots each, group_keys the representatives' key values
