@@ -496,45 +496,7 @@ impl<'c> Searcher<'c> {
                          nprobe: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
         let nq = if dim == 0 { 0 } else { queries.len() / dim };
         // (the arrays the descriptor points at live until the call has returned)
-        let lims: Vec<u64>;
-        let vals: Vec<i64>;
-        let desc = match filter {
-            KeyFilter::Eq(a) => {
-                if a.len() != nq {
-                    return Err("one query key per query".into());
-                }
-                sys::PqvKeyFilter { kind: sys::PQV_KEY_EQ, reserved: 0, a: a.as_ptr() as *const c_void, b: ptr::null() }
-            }
-            KeyFilter::Range(lo, hi) => {
-                if lo.len() != nq || hi.len() != nq {
-                    return Err("one lower and one upper bound per query".into());
-                }
-                sys::PqvKeyFilter { kind: sys::PQV_KEY_RANGE, reserved: 0, a: lo.as_ptr() as *const c_void, b: hi.as_ptr() as *const c_void }
-            }
-            KeyFilter::In(sets) => {
-                if sets.len() != nq {
-                    return Err("one query key set per query".into());
-                }
-                let mut l = vec![0u64; nq + 1];
-                let mut v: Vec<i64> = Vec::new();
-                for (q, set) in sets.iter().enumerate() {
-                    let mut s = set.clone();
-                    s.sort_unstable();
-                    s.dedup();
-                    if s.len() > sys::PQV_KEY_SET_MAX {
-                        return Err("a query key set takes at most 1024 values".into());
-                    }
-                    v.extend_from_slice(&s);
-                    l[q + 1] = v.len() as u64;
-                }
-                if v.is_empty() {
-                    v.push(0); // (never read: a readable address for the descriptor)
-                }
-                lims = l;
-                vals = v;
-                sys::PqvKeyFilter { kind: sys::PQV_KEY_IN, reserved: 0, a: lims.as_ptr() as *const c_void, b: vals.as_ptr() as *const c_void }
-            }
-        };
+        let (desc, _lims, _vals) = key_filter_desc(filter, nq)?;
         let (k, np) = (k.get(), nprobe.get());
         let mut rows = vec![0u32; nq * k];
         let mut dist = vec![0f32; nq * k];
@@ -547,6 +509,36 @@ impl<'c> Searcher<'c> {
         Ok((0..nq)
             .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
             .collect())
+    }
+
+    /// Keep probing until `k` rows pass the filter (`include/pqv.h`: `pqv_topk_expand`): every query probes the fewest lists, at
+    /// least `nprobe` and at most `max_nprobe`, whose passing rows number `k`, and gets what [`Searcher::topk_masked`] (`filter`
+    /// `None`: `mask` is required) or [`Searcher::topk_filtered`] returns for that many lists.  Returns the hits and the lists
+    /// each query probed.
+    pub fn topk_expand(&self, filter: Option<(&RowKeys, &KeyFilter)>, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,
+                       nprobe: NonZeroUsize, max_nprobe: NonZeroUsize) -> Result<(Vec<Vec<SearchResult>>, Vec<u32>)> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        // (the arrays the descriptor points at live until the call has returned)
+        let held = match filter {
+            Some((_, f)) => Some(key_filter_desc(f, nq)?),
+            None => None,
+        };
+        let keys_raw = filter.map_or(ptr::null(), |(kk, _)| kk.raw as *const _);
+        let desc_ptr = held.as_ref().map_or(ptr::null(), |h| &h.0 as *const sys::PqvKeyFilter);
+        let (k, np, max_np) = (k.get(), nprobe.get(), max_nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        let mut used = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_expand(self.raw, keys_raw, desc_ptr, mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(),
+                                 nq as u32, dim as u32, k as u32, np as u32, max_np as u32, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(),
+                                 dist.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut(), used.as_mut_ptr())
+        })?;
+        let hits = (0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect();
+        Ok((hits, used))
     }
 
     /// The nearest row of each of the `k` nearest groups -- a group is the considered rows of one value of `keys` (NULL-key rows
@@ -979,5 +971,48 @@ impl CandidateCursor {
 impl Drop for CandidateCursor {
     fn drop(&mut self) {
         unsafe { sys::pqv_candidate_cursor_free(self.raw) }
+    }
+}
+
+/// The C descriptor of a [`KeyFilter`] for `nq` queries, with the arrays it points at (a set filter's offsets and sorted,
+/// de-duplicated values): they must outlive the call that reads the descriptor.
+fn key_filter_desc(filter: &KeyFilter, nq: usize) -> Result<(sys::PqvKeyFilter, Vec<u64>, Vec<i64>)> {
+    match filter {
+        KeyFilter::Eq(a) => {
+            if a.len() != nq {
+                return Err("one query key per query".into());
+            }
+            Ok((sys::PqvKeyFilter { kind: sys::PQV_KEY_EQ, reserved: 0, a: a.as_ptr() as *const c_void, b: ptr::null() }, Vec::new(), Vec::new()))
+        }
+        KeyFilter::Range(lo, hi) => {
+            if lo.len() != nq || hi.len() != nq {
+                return Err("one lower and one upper bound per query".into());
+            }
+            Ok((sys::PqvKeyFilter { kind: sys::PQV_KEY_RANGE, reserved: 0, a: lo.as_ptr() as *const c_void, b: hi.as_ptr() as *const c_void },
+                Vec::new(), Vec::new()))
+        }
+        KeyFilter::In(sets) => {
+            if sets.len() != nq {
+                return Err("one query key set per query".into());
+            }
+            let mut lims = vec![0u64; nq + 1];
+            let mut vals: Vec<i64> = Vec::new();
+            for (q, set) in sets.iter().enumerate() {
+                let mut s = set.clone();
+                s.sort_unstable();
+                s.dedup();
+                if s.len() > sys::PQV_KEY_SET_MAX {
+                    return Err("a query key set takes at most 1024 values".into());
+                }
+                vals.extend_from_slice(&s);
+                lims[q + 1] = vals.len() as u64;
+            }
+            if vals.is_empty() {
+                vals.push(0); // (never read: a readable address for the descriptor)
+            }
+            // (moving the vectors out does not move their heap buffers: the descriptor's pointers stay valid)
+            let desc = sys::PqvKeyFilter { kind: sys::PQV_KEY_IN, reserved: 0, a: lims.as_ptr() as *const c_void, b: vals.as_ptr() as *const c_void };
+            Ok((desc, lims, vals))
+        }
     }
 }

@@ -617,6 +617,49 @@ int pqv_range_search_filtered(const pqv_searcher *searcher, const pqv_row_keys *
                               uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                               uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates);
 
+/* Expanding filtered top-k: keep probing until k rows pass the filter.  A selective mask or key filter often leaves fewer than k
+ * passing rows in a query's `nprobe` nearest lists; raising nprobe for the whole batch makes every query pay for the worst one.
+ * An expanding call lets each query probe further on its own, up to `max_nprobe` lists, decided on the device in one submission.
+ *
+ * Which filter the call takes:
+ *   keys == NULL   filter must be NULL and mask non-NULL: the twin is pqv_topk_masked / pqv_topk_masked_device.
+ *   keys != NULL   filter must be non-NULL (PQV_KEY_EQ is the keyed call); mask is the optional shared mask: the twin is
+ *                  pqv_topk_filtered / pqv_topk_filtered_device.
+ * With M_q the row set of the twin for query q (the mask, or M_q[r] of the keyed / filtered contract above) and
+ *     kc = n_clusters, p0 = min(nprobe, kc), P = min(max_nprobe, kc),
+ *     cnt_q(p) = the rows of M_q in the first p lists of q's probe order (a row counts whatever its distance is, NaN included),
+ *     nprobe_used[q] = the smallest p in [p0, P] with cnt_q(p) >= k, or P if there is none,
+ * query q's row_idx, dist, n_found and tie flag are, bit for bit, what the twin returns for that one query with the same arguments,
+ * nprobe = nprobe_used[q] and max_candidates = 0 (the probe order is prefix-consistent: the nearest P centroids by (d2, id) begin
+ * with the nearest p).  The host form replays flagged queries through the reference heap over that query's first nprobe_used[q]
+ * lists, as its twin does.  n_candidates[q] is the summed length of those lists.  max_nprobe == nprobe is the twin call itself.
+ * No searcher option changes a result.
+ *   counts     as for those nq twin calls: queries advances by nq, candidate_rows by the sum of n_candidates, embeddings_fetched
+ *              by the considered rows in the used lists.  The counting pass reads no embedding and counts nothing.
+ *   scope      plain searchers, both layouts, PQV_L2SQ_REF4, PQV_L2SQ_SEQ and PQV_COSINE (through the cosine layout, as the
+ *              twins).  nprobe_used / d_nprobe_used, n_found, n_candidates and d_tie_flags may be NULL.  The device form is
+ *              asynchronous on hip_stream like its twin, with no host synchronisation; device filter arrays are read inside
+ *              the enqueued work.
+ *   path       the probe ranks P lists per query; a counting pass over the filter's images (1 bit per row of a mask, 4 or 8
+ *              bytes per row of a key column) and a select write nprobe_used; ONE exact streaming pass then walks each query's
+ *              lists below its own limit.
+ *   out of scope  table searchers, PQV_DOT, max_candidates, distinct / grouped expansion, range search, and -- for the host form
+ *              too -- k or P beyond the kernels' lists.
+ * Errors, checked in this order, NULL handles before any device use -- PQV_ERR_INVALID: "searcher must not be NULL",
+ * "pqv_topk_expand needs a row mask or row keys", "a key filter needs row keys" (filter without keys), "filter must not be NULL"
+ * (keys without filter), the filter-descriptor checks of the filtered host form, "max_nprobe must be >= nprobe", then the twin's
+ * own ("row mask belongs to another searcher", "k must be > 0", ...).  PQV_ERR_UNSUPPORTED: "pqv_topk_expand does not take table
+ * searchers", "PQV_DOT is not supported by pqv_topk_expand", "pqv_topk_expand takes k <= 1024 (1023 with tie flags) and at most
+ * 1024 probed lists per query" (both forms; the host form always carries tie flags and does not fall back to the host heap path). */
+int pqv_topk_expand(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                    const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t max_nprobe,
+                    int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates,
+                    uint32_t *nprobe_used);
+int pqv_topk_expand_device(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_key_filter *filter,
+                           const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                           uint32_t max_nprobe, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found,
+                           void *d_n_candidates, void *d_nprobe_used, void *d_tie_flags, void *hip_stream);
+
 /* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
  * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.
  *

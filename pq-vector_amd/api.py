@@ -686,6 +686,18 @@ def _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq, device=F
     return ("filtered", kh, _ffi.KeyFilter(_ffi.PQV_KEY_IN, 0, lims.ctypes.data, vals.ctypes.data), (lims, vals))
 
 
+def _expand_filter(kf, device=False):
+    """An expanding call's (keys handle, KeyFilter pointer, what must stay alive) from _key_filter's answer: query_keys= travels as a
+    PQV_KEY_EQ descriptor (pqv.h: pqv_topk_expand); no keys= gives (None, None, ())."""
+    if kf is None:
+        return None, None, ()
+    if kf[0] == "filtered":
+        return kf[1], C.byref(kf[2]), kf
+    qk = kf[2]
+    f = _ffi.KeyFilter(_ffi.PQV_KEY_EQ, 0, (int(qk) or None) if device else qk.ctypes.data, None)
+    return kf[1], C.byref(f), (kf, f)
+
+
 def _allow_array(allowed, n_rows, what="row mask"):
     """A caller's allow array -> contiguous uint8 [n_rows]: bool or uint8, one entry per row; anything else is refused."""
     if allowed is None:
@@ -826,8 +838,11 @@ class Searcher:
         return RowKeys(h, self)
 
     def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None, keys=None,
-             query_keys=None, query_key_ranges=None, query_key_sets=None):
+             query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=None):
         """Batched topk(); returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq], n_candidates [nq]).
+        max_nprobe (with mask= or keys=; not with max_candidates): keep probing until k rows pass the filter -- query q probes the
+        fewest lists, at least nprobe and at most max_nprobe, whose passing rows number k, and gets what the call without
+        max_nprobe returns for that many lists; a fifth array nprobe_used [nq] u32 comes back (pqv.h: pqv_topk_expand).
         mask (a RowMask of this searcher): only allowed rows are considered (pqv.h: pqv_topk_masked).
         keys (a RowKeys of this searcher) with query_keys (int [nq]): query q considers only the rows whose key equals
         query_keys[q], within mask if one is given too (pqv.h: pqv_topk_keyed).  Instead of query_keys:
@@ -843,6 +858,16 @@ class Searcher:
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
         kf = _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if max_nprobe is not None:
+            if max_candidates:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
+            used = np.zeros(nq, dtype=np.uint32)
+            kh, fp, _alive = _expand_filter(kf)
+            _check(_ffi.lib().pqv_topk_expand(self._h, kh, fp, _mask_handle(self, mask) if mask is not None else None,
+                                              q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_nprobe, metric, 1 if sqrt_out else 0,
+                                              rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
+                                              nc.ctypes.data_as(u64p), used.ctypes.data_as(u32p)))
+            return rows, dist, nf, nc, used
         if kf is not None and kf[0] == "filtered":
             _check(_ffi.lib().pqv_topk_filtered(self._h, kf[1], C.byref(kf[2]), _mask_handle(self, mask) if mask is not None else None,
                                                 q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
@@ -984,7 +1009,7 @@ class Searcher:
 
     def topk_device(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0,
                     max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0, mask=None, keys=None,
-                    query_keys=None, query_key_ranges=None, query_key_sets=None):
+                    query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=0, d_nprobe_used=0):
         """Device-pointer form (ints from tensor.data_ptr()); asynchronous on `stream` -- a hipStream_t handle; 0 means the
         searcher's OWN non-blocking stream, not HIP's / torch's default stream (whose handle is 0 too): work that must follow
         the call on the default stream is NOT ordered behind it, so pass an explicit stream (1 = hipStreamLegacy names the default
@@ -995,8 +1020,19 @@ class Searcher:
         work): pqv.h: pqv_topk_keyed_device; combinable with mask.  Instead of query_keys: query_key_ranges=(ptr_lo, ptr_hi), device
         pointers of int64 [nq] each, or query_key_sets=(ptr_lims, ptr_vals), device pointers of uint64 [nq + 1] offsets and of the
         int64 values, every query's slice strictly ascending and at most PQV_KEY_SET_MAX long -- not validated, the call stays
-        asynchronous (pqv.h: pqv_topk_filtered_device)."""
+        asynchronous (pqv.h: pqv_topk_filtered_device).
+        max_nprobe (> 0, with mask= or keys=; not with max_candidates): the expanding call, as topk's; d_nprobe_used (u32 [nq],
+        optional) takes the lists each query probed (pqv.h: pqv_topk_expand_device)."""
         kf = _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        if max_nprobe:
+            if max_candidates:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
+            kh, fp, _alive = _expand_filter(kf, device=True)
+            _check(_ffi.lib().pqv_topk_expand_device(self._h, kh, fp, _mask_handle(self, mask) if mask is not None else None,
+                                                     vp(d_queries), nq, k, nprobe, max_nprobe, metric, 1 if sqrt_out else 0,
+                                                     vp(d_row_idx), vp(d_dist), vp(d_n_found or None), vp(d_n_candidates or None),
+                                                     vp(d_nprobe_used or None), vp(d_tie_flags or None), vp(stream or None)))
+            return
         if kf is not None and kf[0] == "filtered":
             _check(_ffi.lib().pqv_topk_filtered_device(self._h, kf[1], C.byref(kf[2]), _mask_handle(self, mask) if mask is not None else None,
                                                        vp(d_queries), nq, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
@@ -1246,6 +1282,15 @@ class TopkBuilder:
         self._where = None
         self._distinct = None
         self._group_size = None
+        self._max_nprobe = None
+
+    def max_nprobe(self, n):
+        """With where(): keep probing, up to n lists, until k rows pass the filter (pqv.h: pqv_topk_expand); nprobe() stays the
+        fewest lists probed.  Not with distinct_on(); table builders do not take it."""
+        if n == 0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe must be > 0")
+        self._max_nprobe = n
+        return self
 
     def metric(self, m):
         self._metric = _metric_arg(m)
@@ -1335,6 +1380,11 @@ class TopkBuilder:
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         self._check_grouping()
+        if self._max_nprobe is not None:
+            if self._where is None:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "pqv_topk_expand needs a row mask or row keys")
+            if self._distinct is not None:
+                raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "max_nprobe() does not combine with distinct_on()")
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
         if self._distinct is not None:
@@ -1351,8 +1401,8 @@ class TopkBuilder:
         if self._where is not None:
             mask, owned = _resolve_where(self._where, self._path, self._searcher)
             try:
-                rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric,
-                                                        mask=mask)
+                rows, dist, nf = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric,
+                                                     mask=mask, max_nprobe=self._max_nprobe)[:3]
             finally:
                 if owned:
                     mask.close()
@@ -1656,6 +1706,8 @@ class TableTopkBuilder(TopkBuilder):
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         self._check_grouping()
+        if self._max_nprobe is not None:
+            raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "pqv_topk_expand does not take table searchers")
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
         if self._distinct is not None:
             mask = _resolve_table_where(self._where, self._paths, s) if self._where is not None else None

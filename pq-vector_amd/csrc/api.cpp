@@ -328,7 +328,8 @@ struct Scratch {
         // grouped calls (pqv_topk_grouped): pass 1's rows / distances [nq][k] (not reported), its group values and n_found where the caller
         // takes none, the sorted sets [nq][k], the partial lists' slots [nq][n_part][k * group_size] and lengths [nq][n_part], and the
         // host form's group_rows block
-        s_g1_rows, s_g1_dist, s_g1_keys, s_g1_nfound, s_gset_keys, s_gset_slot, s_gpart_slot, s_gpart_cnt, s_grows_out;
+        s_g1_rows, s_g1_dist, s_g1_keys, s_g1_nfound, s_gset_keys, s_gset_slot, s_gpart_slot, s_gpart_cnt, s_grows_out,
+        s_expand_cnt, s_expand_used;    // pqv_topk_expand: the passing rows per probed list u32 [nq][P]; nprobe_used u32 [nq] where the caller takes none
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -343,7 +344,8 @@ struct Scratch {
                 &s_seed_ub, &s_qblk, &s_gthr, &s_tie, &s_replay, &s_qnorm, &s_qmax, &s_thr_hist, &s_thr_bins, &s_qi8, &s_qn2i, &s_qres, &s_qresu, &s_pair_lb, &s_part_flags, &s_qpad, &s_cand_lb, &s_pendv, &s_work, &s_nwork, &s_out,
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
                 &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
-                &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out};
+                &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out,
+                &s_expand_cnt, &s_expand_used};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -559,7 +561,12 @@ struct MaskView {
     uint32_t group_size;               // a grouped call (pqv_topk_grouped; `group` set): rows per group, >= 1; 0: not grouped.  The call's row_idx / dist are
                                        // [nq, k, group_size]
     uint32_t *d_group_rows;            // grouped: where the rows per group go [nq * k] (device), or nullptr
+    uint32_t max_nprobe;               // an expanding call (pqv_topk_expand): the lists the probe ranks per query, >= the call's nprobe; 0: not expanding
+    uint32_t *d_nprobe_used;           // expanding: where the lists each query used go [nq] (device), or nullptr (the lane's scratch)
+    uint32_t *h_nprobe_used;           // expanding host form: the caller's [nq], or nullptr
 };
+// the lists the probe of a call ranks per query: an expanding call's max_nprobe, else its nprobe
+static inline uint32_t probe_arg(const MaskView *mv, uint32_t nprobe) { return mv && mv->max_nprobe ? mv->max_nprobe : nprobe; }
 // a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
 static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
     const uint64_t n_words = (m->n_rows + 63) / 64;
@@ -696,7 +703,8 @@ static int upload_query_filter(Scratch &sc, const MaskView *mask, MaskView &sub,
 // the STREAM_TOPK / STREAM_RANGE pass of a masked or keyed call
 // (a distinct call: STREAM_TOPK only, the per-wave lists' group values go to part_grp)
 static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskView *mv, unsigned long long *stats, const uint64_t *n_cand,
-                                         pqv::StreamMode mode, hipStream_t stream, int64_t *part_grp = nullptr) {
+                                         pqv::StreamMode mode, hipStream_t stream, int64_t *part_grp = nullptr,
+                                         const uint32_t *rank_limit = nullptr) {
     if (mv->group) {
         if (mode != pqv::STREAM_TOPK) return hipErrorInvalidValue;
         const pqv_row_keys *gk = mv->group;
@@ -707,7 +715,7 @@ static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskVi
     if (mv->keys) {
         const pqv_row_keys *kk = mv->keys;
         const pqv::KeyedArgs ka{mv->bits, stats, n_cand, kk->d_key_pos.p, kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr,
-                                mv->d_qkeys, kk->dtype == PQV_COL_I32 ? 4u : 8u};
+                                mv->d_qkeys, kk->dtype == PQV_COL_I32 ? 4u : 8u, rank_limit};
         if (mv->fkind) {
             pqv::KeyFilterArgs fa{};
             static_cast<pqv::KeyedArgs &>(fa) = ka;
@@ -716,7 +724,7 @@ static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskVi
         }
         return pqv::launch_keyed_stream(ra, ka, mode, stream);
     }
-    const pqv::MaskedArgs ma{mv->bits, stats, n_cand};
+    const pqv::MaskedArgs ma{mv->bits, stats, n_cand, rank_limit};
     if (ra.metric == PQV_DOT) return pqv::launch_dot_stream(ra, &ma, mode, stream);
     return pqv::launch_masked_stream(ra, ma, mode, stream);
 }
@@ -3623,7 +3631,14 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
                  uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand,
                  uint32_t *d_tie, hipStream_t stream, Scratch &sc, const MaskView *mask = nullptr) {
     using namespace pqv;
+    // an expanding call (pqv_topk_expand): the probe ranks P = min(max_nprobe, n_clusters) lists per query, a counting pass and a
+    // select decide per query how many of them it walks (>= p0), and the stream pass below runs under those rank limits
+    const bool expand = mask && mask->max_nprobe;
+    const uint32_t p0 = probe_count(s, nprobe);
+    nprobe = probe_arg(mask, nprobe);
     const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, mask != nullptr);
+    if (expand && (s->n_files || mask->group || p.tile || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
+        return fail(PQV_ERR_INVALID, "expanding call on a plan that cannot expand");
     const uint64_t max_pos = max_candidates ? max_candidates : ~0ull;
     // the probe works on the queries as given; everything that meets the (possibly zero-padded) stored rows gets the
     // batch's queries padded the same way
@@ -3759,6 +3774,27 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         if (int rc = enqueue_probe(s, sc, p, d_queries, nq, nprobe, max_candidates, pm, pair_u32, zero_n, stream, metric)) return rc;
     }
     const uint64_t *pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
+    const uint32_t *rank_limit = nullptr;
+    if (expand) {
+        HIP_TRY(sc.s_expand_cnt.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
+        uint32_t *used = mask->d_nprobe_used;
+        if (!used) { HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(nq) * sizeof(uint32_t))); used = sc.s_expand_used.as<uint32_t>(); }
+        ExpandCountArgs ca{};
+        ca.probe = sc.s_probe.as<uint32_t>(); ca.list_off = s->d_list_off.as<uint64_t>(); ca.nq = nq; ca.P = p.np;
+        ca.bits = mask->bits; ca.cnt = sc.s_expand_cnt.as<uint32_t>();
+        if (const pqv_row_keys *kk = mask->keys) {
+            const uint32_t wide = kk->dtype == PQV_COL_I32 ? 0u : 1u;
+            ca.win = 1u + 2u * mask->fkind + wide;
+            ca.key_pos = kk->d_key_pos.p; ca.valid_pos = kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr;
+            ca.a = mask->fkind ? mask->d_fa : mask->d_qkeys; ca.b = mask->fkind ? mask->d_fb : nullptr;
+        }
+        HIP_TRY(launch_filter_count(ca, stream));
+        // (before the stream pass: that pass adds n_cand[q] to candidate_rows)
+        const ExpandSelectArgs sa{ca.cnt, ca.probe, sc.s_cand_base.as<uint64_t>(), ca.list_off, nq, p.np, p0, k_out, used, pm.n_cand};
+        HIP_TRY(launch_expand_select(sa, stream));
+        rank_limit = used;
+        s->counters.kernel_launches += 2;
+    }
 
     // 2. candidate re-rank + per-wave top-k
     bool use_cand = false;     // wide screened path: the final merge also reads the candidate buffers
@@ -3990,7 +4026,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
         if (mask) {
             HIP_TRY(launch_filtered_stream(ra, mask, s->d_stats.as<unsigned long long>(), pm.n_cand, STREAM_TOPK, stream,
-                                           distinct ? sc.s_part_grp.as<int64_t>() : nullptr));
+                                           distinct ? sc.s_part_grp.as<int64_t>() : nullptr, rank_limit));
         } else if (metric == PQV_DOT) {
             HIP_TRY(launch_dot_stream(ra, nullptr, STREAM_TOPK, stream));
         } else {
@@ -4211,13 +4247,15 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
 // qi indexes the current sub-batch's probe scratch (written by the probe merge).
 int replay_query_exact(const pqv_searcher *s, Scratch &sc, const float *d_query, uint32_t qi, uint32_t np, uint32_t k,
                        uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                       uint32_t *n_found, uint32_t nprobe, const RowFilter *allow = nullptr) {
+                       uint32_t *n_found, uint32_t nprobe, const RowFilter *allow = nullptr, uint32_t stride = 0) {
+    // (stride: the probe table's lists per query where the replay takes the first np of them only -- an expanding call)
+    if (!stride) stride = np;
     std::vector<uint32_t> clusters(np);
-    HIP_TRY(hipMemcpyAsync(clusters.data(), sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * np,
+    HIP_TRY(hipMemcpyAsync(clusters.data(), sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * stride,
                            np * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    return replay_with_clusters(s, sc, d_query, sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * np,
-                                sc.s_cand_base.as<uint64_t>() + static_cast<size_t>(qi) * np, clusters, k, max_candidates,
+    return replay_with_clusters(s, sc, d_query, sc.s_probe.as<uint32_t>() + static_cast<size_t>(qi) * stride,
+                                sc.s_cand_base.as<uint64_t>() + static_cast<size_t>(qi) * stride, clusters, k, max_candidates,
                                 metric, sqrt_out, row_idx, dist, n_found, nprobe, allow);
 }
 
@@ -4446,7 +4484,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     }
     // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
     // (per query: partial lists, probe partial lists, candidate buffer, the int8 images of its probed pairs)
-    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), nprobe, k_int, metric, mask != nullptr);
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(mask, nprobe), k_int, metric, mask != nullptr);
     const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * k_int * 12 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
                                static_cast<uint64_t>(cand_cap_for(s, k_int)) * 12 + static_cast<uint64_t>(p1.np) * (s->sdim + 32) +
                                static_cast<uint64_t>(s->sdim) * 4 + 1;
@@ -4459,10 +4497,15 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     HIP_TRY(sc.s_tie.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     std::vector<uint64_t> h_ncand(batch);
     std::vector<uint32_t> h_tie(batch), h_nf(batch);
-    const uint32_t np = probe_count(s, nprobe);
+    const uint32_t np = probe_count(s, probe_arg(mask, nprobe));
+    // an expanding call: the lists each query of the sub-batch used come back with its results
+    const bool expand = mask && mask->max_nprobe;
+    std::vector<uint32_t> h_used(expand ? batch : 0);
+    if (expand) HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     // a keyed call: the kernels of a sub-batch read its own slice of the query keys (the same q0 as its queries)
     MaskView sub{};
     if (mask) sub = *mask;
+    if (expand) sub.d_nprobe_used = sc.s_expand_used.as<uint32_t>();
     const MaskView *bmask = mask ? &sub : nullptr;
     if (mask && mask->keys && !mask->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     std::vector<uint64_t> sub_lims;
@@ -4505,6 +4548,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
                                   small_io ? reinterpret_cast<uint64_t *>(direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p)) : nullptr,
                                   o_tie, s->stream, sc, bmask))
             return rc;
+        if (expand) HIP_TRY(hipMemcpyAsync(h_used.data(), sc.s_expand_used.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         if (small_io) {
             char *hb = static_cast<char *>(sc.h_io.p) + out_off;
             const size_t ob_bytes = static_cast<size_t>(b) * (16 + 8 * static_cast<size_t>(k));
@@ -4535,14 +4579,16 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
                 RowFilter allow;
                 if (int rc = row_filter(s, mask, static_cast<uint64_t>(q0) + i, allow)) return rc;
                 if (int rc = replay_query_exact(s, sc, s->sdim != s->dim ? sc.s_qpad.as<float>() + static_cast<size_t>(i) * s->sdim
-                                                                          : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i, np,
+                                                                          : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i,
+                                                expand ? std::min<uint32_t>(std::max<uint32_t>(1, h_used[i]), np) : np,
                                                 k, max_candidates, metric, sqrt_out,
                                                 row_idx + static_cast<uint64_t>(q0 + i) * k,
-                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, allow.active() ? &allow : nullptr))
+                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, allow.active() ? &allow : nullptr, np))
                     return rc;
                 s->counters.exact_replays++;
             }
             if (n_found) n_found[q0 + i] = h_nf[i];
+            if (expand && mask->h_nprobe_used) mask->h_nprobe_used[q0 + i] = h_used[i];
         }
         s->counters.queries += b;
     }
@@ -5149,8 +5195,7 @@ extern "C" int pqv_range_search_keyed(const pqv_searcher *s, const pqv_row_keys 
 // ---- per-query filters beyond equality (pqv.h: pqv_key_filter) ---------------------------------------------------------------
 // The descriptor's checks, ahead of keyed_view's; `host`: a and b are host arrays and a set filter is validated in full.  On
 // success the view carries the filter: PQV_KEY_EQ as the keyed calls' query keys, the other kinds in fkind / h_f* / d_f*.
-static int filtered_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *f, uint32_t nq, const pqv_row_mask *mask,
-                         bool host, MaskView &mv) {
+static int filter_descriptor_checks(const pqv_key_filter *f, uint32_t nq, bool host) {
     if (!f) return fail(PQV_ERR_INVALID, "filter must not be NULL");
     if (f->kind > PQV_KEY_IN) return fail(PQV_ERR_INVALID, "unknown key filter kind " + std::to_string(f->kind));
     const bool reads_b = f->kind != PQV_KEY_EQ;
@@ -5167,6 +5212,12 @@ static int filtered_view(const pqv_searcher *s, const pqv_row_keys *keys, const 
             for (uint64_t i = lims[q] + 1; i < lims[q + 1]; ++i)
                 if (!(vals[i - 1] < vals[i])) return fail(PQV_ERR_INVALID, "query key sets must be strictly ascending");
     }
+    return PQV_OK;
+}
+// (descriptor_checked: the caller made filter_descriptor_checks itself, with checks of its own behind them)
+static int filtered_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *f, uint32_t nq, const pqv_row_mask *mask,
+                         bool host, MaskView &mv, bool descriptor_checked = false) {
+    if (!descriptor_checked) { if (int rc = filter_descriptor_checks(f, nq, host)) return rc; }
     if (int rc = keyed_view(s, keys, f->a, nq, mask, mv)) return rc;
     if (f->kind == PQV_KEY_EQ) {
         (host ? mv.h_qkeys : mv.d_qkeys) = static_cast<const int64_t *>(f->a);
@@ -5194,6 +5245,50 @@ extern "C" int pqv_topk_filtered_device(const pqv_searcher *s, const pqv_row_key
         MaskView mv{};
         if (int rc = filtered_view(s, keys, filter, nq, mask, false, mv)) return rc;
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, d_tie_flags, hip_stream, &mv);
+    });
+}
+// ---- expanding filtered top-k (pqv.h: pqv_topk_expand) ---------------------------------------------------------------------
+// The checks of both forms up to the view, in the contract's order; nothing is dereferenced before the NULL checks.
+static int expand_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask, uint32_t nq,
+                       uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric, bool host, bool flags, MaskView &mv) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!keys && !mask) return fail(PQV_ERR_INVALID, "pqv_topk_expand needs a row mask or row keys");
+    if (!keys && filter) return fail(PQV_ERR_INVALID, "a key filter needs row keys");
+    if (keys && !filter) return fail(PQV_ERR_INVALID, "filter must not be NULL");
+    if (keys) { if (int rc = filter_descriptor_checks(filter, nq, host)) return rc; }
+    if (max_nprobe < nprobe) return fail(PQV_ERR_INVALID, "max_nprobe must be >= nprobe");
+    if (keys) { if (int rc = filtered_view(s, keys, filter, nq, mask, host, mv, true)) return rc; }
+    else if (int rc = mask_view(s, mask, mv)) return rc;
+    if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (s->n_files) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_expand does not take table searchers");
+    if (metric == PQV_DOT) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by pqv_topk_expand");
+    // (the host form always carries the runner-up entry its tie replay needs)
+    if (k > (flags ? 1023u : 1024u) || probe_count(s, max_nprobe) > 1024)
+        return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_expand takes k <= 1024 (1023 with tie flags) and at most 1024 probed lists per query");
+    mv.max_nprobe = max_nprobe;
+    return PQV_OK;
+}
+extern "C" int pqv_topk_expand(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                               const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t max_nprobe,
+                               int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates,
+                               uint32_t *nprobe_used) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = expand_view(s, keys, filter, mask, nq, k, nprobe, max_nprobe, metric, true, true, mv)) return rc;
+        mv.h_nprobe_used = nprobe_used;
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
+    });
+}
+extern "C" int pqv_topk_expand_device(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                                      const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric,
+                                      int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
+                                      void *d_nprobe_used, void *d_tie_flags, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = expand_view(s, keys, filter, mask, nq, k, nprobe, max_nprobe, metric, false, d_tie_flags != nullptr, mv)) return rc;
+        mv.d_nprobe_used = static_cast<uint32_t *>(d_nprobe_used);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
     });
 }

@@ -78,6 +78,8 @@ struct MaskedArgs {
     unsigned long long *stats;    // optional: the searcher's statistics block -- every wave adds the rows it evaluated to the
                                   // embeddings_fetched word of its query's slot (the probe merge of a masked call gets no MergeArgs::stats)
     const uint64_t     *n_cand;   // optional [nq] (with stats): the probe merge's uncapped totals, added to candidate_rows once per query
+    const uint32_t     *rank_limit;   // optional [nq] (STREAM_TOPK; pqv_topk_expand): query q walks its probe ranks below rank_limit[q] only -- a
+                                      // block of a rank at or beyond it reads that word, stores its four EMPTY lists and ends.  nullptr: every rank
 };
 // launch_stream's STREAM_TOPK / STREAM_RANGE pass over the allowed positions only (masked_stream_kernel): the same grid, chain
 // arithmetic, keys and output formats; a.probe / a.list_off / a.cand_base are required.
@@ -111,6 +113,7 @@ struct KeyedArgs {
     const uint64_t     *valid_pos;  // optional [n_words]
     const int64_t      *qkeys;      // [nq]: query q's key; an i32 column's values are widened for the comparison
     uint32_t            elem_size;  // 4 or 8
+    const uint32_t     *rank_limit; // as MaskedArgs::rank_limit
 };
 // launch_masked_stream with a window's bits taken from key_pos[p] == qkeys[q] (masked_stream_kernel, WIN = 1 / 2)
 hipError_t launch_keyed_stream(const StreamArgs &a, const KeyedArgs &ka, StreamMode mode, hipStream_t s);
@@ -125,6 +128,37 @@ struct KeyFilterArgs : KeyedArgs {
     const void *b;
 };
 hipError_t launch_key_filter_stream(const StreamArgs &a, const KeyFilterArgs &fa, StreamMode mode, hipStream_t s);
+
+// ---- expanding filtered top-k (kernels_expand.hip; pqv.h: pqv_topk_expand) ------------------------------------------------
+// filter_count_kernel: cnt[q * P + j] = the positions of list probe[q * P + j] that pass the call's filter -- the set bits of
+// the windows masked_stream_kernel forms for the same `win` (0: the mask image `bits`; 1 / 2: key_pos == a[q], i32 / i64; 3 / 4:
+// a[q] <= key_pos <= b[q]; 5 / 6: key_pos in b[a[q] .. a[q + 1]); valid_pos and a shared mask's bits ANDed in), no candidate cap.
+// One block per (rank, query), one plain store each: deterministic.  No embedding is read.
+struct ExpandCountArgs {
+    const uint32_t *probe;       // [nq, P]
+    const uint64_t *list_off;
+    uint32_t        nq, P;
+    uint32_t        win;         // masked_stream_kernel's WIN
+    const uint64_t *bits;        // win 0: the mask's image; else an optional shared mask's
+    const void     *key_pos;     // win >= 1
+    const uint64_t *valid_pos;   // optional
+    const void     *a, *b;       // KeyFilterArgs::a / b (win 1 / 2: a = the query keys)
+    uint32_t       *cnt;         // [nq, P]
+};
+hipError_t launch_filter_count(const ExpandCountArgs &a, hipStream_t s);
+// expand_select_kernel, one wave per query: nprobe_used[q] = the smallest p in [p0, P] whose first p lists hold >= k passing
+// positions (64-bit prefix sums of cnt in probe order), P where there is none; n_cand[q] is overwritten with the summed length of
+// those lists.  1 <= p0 <= P.
+struct ExpandSelectArgs {
+    const uint32_t *cnt;         // [nq, P]
+    const uint32_t *probe;       // [nq, P]
+    const uint64_t *cand_base;   // [nq, P]
+    const uint64_t *list_off;
+    uint32_t        nq, P, p0, k;
+    uint32_t       *nprobe_used; // [nq]
+    uint64_t       *n_cand;      // [nq]
+};
+hipError_t launch_expand_select(const ExpandSelectArgs &a, hipStream_t s);
 
 // ---- distinct top-k (kernels_distinct.hip; pqv.h: pqv_topk_distinct) -----------------------------------------------------
 // The group column is a key column's position image (launch_key_layout).  launch_distinct_stream is launch_masked_stream's

@@ -111,6 +111,9 @@ hipError_t launch_key_layout(const void *values, const uint8_t *valid, uint32_t 
 // __ballot of "found".  An empty slice walks nothing.  A slice that is not ascending finds some keys and misses others; every
 // index the search forms stays below the slice length.
 //
+// rank_limit (STREAM_TOPK, optional; pqv_topk_expand): the blocks of probe ranks j >= rank_limit[q] store empty lists and end.
+// j == 0 is below every limit (>= 1), so the candidate_rows word is still added once per query.
+//
 // Outputs: stream_kernel's (per-wave partial lists / hit segments).  Each wave adds the rows it evaluated to the
 // embeddings_fetched word of the query's statistics slot; the (0, 0) block of a query adds n_cand[q] to candidate_rows.
 // ------------------------------------------------------------------------------------
@@ -137,6 +140,19 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
 #define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
 
     const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
+    if constexpr (MODE == STREAM_TOPK) {
+        // a rank at or beyond the query's limit (pqv_topk_expand) walks nothing: that one word is all the block loads, its four
+        // waves' lists go out EMPTY for the final merge (block-uniform: nobody is left waiting at the IN forms' barrier)
+        if (ma.rank_limit && j >= ma.rank_limit[q]) {
+            const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
+            const uint64_t base = ((uint64_t)q * n_part + (j * a.blocks_per_list + blockIdx.x) * 4 + wave) * a.k;
+            for (uint32_t e = lane; e < a.k; e += 64) {
+                a.part_keys[base + e] = KEY_EMPTY;
+                a.part_vals[base + e] = 0xFFFFFFFFu;
+            }
+            return;
+        }
+    }
     const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
     const uint64_t lbeg = a.list_off[c], lend = a.list_off[c + 1];
     const uint64_t cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
