@@ -565,6 +565,68 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// [`Searcher::topk_distinct`] with one filter PER QUERY on `filter_keys` (which may be `group_keys`), applied before a group's
+    /// representative is chosen: the nearest documents of every query's own tenant (`include/pqv.h`: `pqv_topk_distinct_filtered`).
+    pub fn topk_distinct_filtered(&self, group_keys: &RowKeys, filter_keys: &RowKeys, filter: &KeyFilter, mask: Option<&RowMask>,
+                                  queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize) -> Result<Vec<Vec<DistinctSearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        // (the arrays the descriptor points at live until the call has returned)
+        let (desc, _lims, _vals) = key_filter_desc(filter, nq)?;
+        let (k, np) = (k.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut group = vec![0i64; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_distinct_filtered(self.raw, group_keys.raw, filter_keys.raw, &desc, mask.map_or(ptr::null(), |m| m.raw as *const _),
+                                            queries.as_ptr(), nq as u32, dim as u32, k as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1,
+                                            rows.as_mut_ptr(), dist.as_mut_ptr(), group.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| {
+                (0..found[q] as usize)
+                    .map(|i| DistinctSearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i], key: group[q * k + i] })
+                    .collect()
+            })
+            .collect())
+    }
+
+    /// [`Searcher::topk_grouped`] under a per-query filter, as [`Searcher::topk_distinct_filtered`] takes it (`include/pqv.h`:
+    /// `pqv_topk_grouped_filtered`).
+    pub fn topk_grouped_filtered(&self, group_keys: &RowKeys, filter_keys: &RowKeys, filter: &KeyFilter, mask: Option<&RowMask>,
+                                 queries: &[f32], dim: usize, k: NonZeroUsize, group_size: NonZeroUsize, nprobe: NonZeroUsize)
+                                 -> Result<Vec<Vec<GroupSearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (desc, _lims, _vals) = key_filter_desc(filter, nq)?;
+        let (k, m, np) = (k.get(), group_size.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k * m];
+        let mut dist = vec![0f32; nq * k * m];
+        let mut group = vec![0i64; nq * k];
+        let mut group_rows = vec![0u32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_grouped_filtered(self.raw, group_keys.raw, filter_keys.raw, &desc, mask.map_or(ptr::null(), |x| x.raw as *const _),
+                                           queries.as_ptr(), nq as u32, dim as u32, k as u32, m as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1,
+                                           rows.as_mut_ptr(), dist.as_mut_ptr(), group.as_mut_ptr(), group_rows.as_mut_ptr(),
+                                           found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| {
+                (0..found[q] as usize)
+                    .map(|g| {
+                        let o = (q * k + g) * m;
+                        GroupSearchResult {
+                            key: group[q * k + g],
+                            hits: (0..group_rows[q * k + g] as usize)
+                                .map(|i| SearchResult { row_idx: rows[o + i], distance: dist[o + i] })
+                                .collect(),
+                        }
+                    })
+                    .collect()
+            })
+            .collect())
+    }
+
     /// Up to `group_size` rows of each of the `k` nearest groups of `keys`, groups as [`Searcher::topk_distinct`] defines them
     /// (`include/pqv.h`: `pqv_topk_grouped`).  Groups ascending by their nearest row, a group's hits by (distance, position).
     pub fn topk_grouped(&self, keys: &RowKeys, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,

@@ -689,8 +689,8 @@ int pqv_topk_expand_device(const pqv_searcher *searcher, const pqv_row_keys *key
  *                    pqv_topk_distinct computes the sorted considered sequence with the masked range machinery (radius = +inf)
  *                    and keeps the first row per key on the host, and pqv_topk_distinct_device reports PQV_ERR_UNSUPPORTED, as
  *                    pqv_topk_masked_device does.
- *   out of scope     a per-query key filter combined with a group column in one call; distinct range search.  (More than one
- *                    row per group: pqv_topk_grouped below.)
+ *   out of scope     distinct range search.  (A per-query key filter together with the group column: pqv_topk_distinct_filtered
+ *                    below.  More than one row per group: pqv_topk_grouped below.)
  * Errors (PQV_ERR_INVALID; NULL handles are checked before any device use): "searcher must not be NULL", "row keys must not be
  * NULL", "row keys belong to another searcher", "row mask belongs to another searcher", and pqv_topk's own ("k must be > 0", ...). */
 int pqv_topk_distinct(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries,
@@ -728,8 +728,8 @@ int pqv_topk_distinct_device(const pqv_searcher *searcher, const pqv_row_keys *k
  *   counts           group_size > 1: queries and candidate_rows advance once per query, not once per pass; embeddings_fetched
  *                    advances by the considered rows plus the rows the second pass evaluates, the considered rows of the selected
  *                    groups.  group_size == 1: the distinct call's counts.
- *   out of scope     a per-query key filter combined with grouping; grouped range search; PQV_DOT; probing further lists when
- *                    fewer than k groups are found.
+ *   out of scope     grouped range search; PQV_DOT; probing further lists when fewer than k groups are found.  (A per-query key
+ *                    filter together with grouping: pqv_topk_grouped_filtered below.)
  * Errors: pqv_topk_distinct's, in the same order, NULL handles checked before any device use; behind "k must be > 0":
  * "group_size must be > 0".  PQV_DOT: PQV_ERR_UNSUPPORTED "PQV_DOT is not supported by keyed and distinct calls". */
 int pqv_topk_grouped(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries,
@@ -740,6 +740,59 @@ int pqv_topk_grouped_device(const pqv_searcher *searcher, const pqv_row_keys *ke
                             uint32_t nq, uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric,
                             int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
                             void *d_n_candidates, void *hip_stream);
+
+/* Distinct and grouped top-k under a PER-QUERY key filter: every query of a batch has its own `tenant = ?`, `group_id IN (...)`
+ * or `ts BETWEEN ? AND ?` and gets the k nearest DOCUMENTS back -- multi-tenant retrieval over chunked documents in one call.
+ *
+ * Each call is its twin (pqv_topk_distinct*, pqv_topk_grouped*) with `filter_keys, filter` behind the group column `group_keys`:
+ * filter_keys is a second pqv_row_keys of this searcher (it may be the same object as group_keys) and filter the descriptor of
+ * pqv_topk_filtered, read as that call reads it -- host arrays in the host forms; in the device forms DEVICE arrays read on
+ * hip_stream inside the enqueued work, the calls stay asynchronous, and an unvalidated PQV_KEY_IN slice has the unspecified but
+ * in-bounds behaviour pqv_topk_filtered_device documents.  `mask` is an optional shared row mask, NULL: none.
+ *   contract         let F_q be the descriptor's test for query q, exactly as pqv_topk_filtered defines it, and
+ *                      M_q[r] = filter_valid[r] && F_q((int64_t) filter_column[r]) && (mask ? mask[r] : 1).
+ *                    Query q returns, bit for bit, what pqv_topk_distinct / pqv_topk_grouped returns for that one query with the
+ *                    shared mask M_q: rows, distances, group keys, group_rows, n_found and n_candidates.
+ *   the twin's       everything else, word for word: the cap cuts the candidate sequence BEFORE any filter and positions stay the
+ *                    unmasked ones; a row is considered iff M_q holds AND its group key is valid; groups are compared in i64; the
+ *                    order is (d2, position) always -- no heap replay, no tie flags; sqrt_out and the PQV_COSINE halving;
+ *                    group_size == 1 is the distinct call; the counters (embeddings_fetched advances by the considered rows summed
+ *                    over the batch, plus the second pass's rows of a grouped call).  Plain and table searchers, every layout,
+ *                    PQV_L2SQ_REF4 / PQV_L2SQ_SEQ / PQV_COSINE.
+ *   consequences     the filter applies BEFORE the representative is chosen: a group whose nearest row fails F_q is represented by
+ *                    its nearest PASSING row, or absent if none passes.  PQV_KEY_RANGE over [INT64_MIN, INT64_MAX] on a column
+ *                    without NULLs is the unfiltered twin.  With all group keys distinct, slot 0 holds pqv_topk_filtered_device's
+ *                    result.
+ *   path             the twins' exact streaming passes, a window's positions also tested against the query's filter: a row the
+ *                    filter excludes is never read.  Beyond the kernels' lists (k * group_size > 1024, or more than 1024 probed
+ *                    lists) the host forms compute the sorted considered sequence with the filtered range machinery (radius =
+ *                    +inf, the group validity AND the shared mask as the image, the per-query filter beside it) and group on the
+ *                    host; the device forms report the twins' PQV_ERR_UNSUPPORTED.
+ *   out of scope     expansion (max_nprobe) with a group column; PQV_DOT: PQV_ERR_UNSUPPORTED "PQV_DOT is not supported by keyed
+ *                    and distinct calls".
+ * Errors (PQV_ERR_INVALID), in this order, every NULL and zero check before a handle is dereferenced or a device used: "searcher
+ * must not be NULL", "row keys must not be NULL" (group_keys), "a key filter needs row keys" (filter_keys), "filter must not be
+ * NULL", the descriptor checks of pqv_topk_filtered, "k must be > 0", "group_size must be > 0" (grouped), "row keys belong to
+ * another searcher" (either column), "row mask belongs to another searcher", and the rest of pqv_topk's. */
+int pqv_topk_distinct_filtered(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                               const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                               uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                               uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_distinct_filtered_device(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                      const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                      uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                      void *d_row_idx, void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates,
+                                      void *hip_stream);
+int pqv_topk_grouped_filtered(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                              const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                              uint32_t query_len, uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates,
+                              int metric, int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows,
+                              uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_grouped_filtered_device(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                     const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                     uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric,
+                                     int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows,
+                                     void *d_n_found, void *d_n_candidates, void *hip_stream);
 
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`

@@ -698,6 +698,20 @@ def _expand_filter(kf, device=False):
     return kf[1], C.byref(f), (kf, f)
 
 
+def _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq, device=False):
+    """A distinct / grouped call's per-query filter: None without any of the four keywords (the unfiltered symbols are called), else
+    _expand_filter's triple.  filter_keys= goes with exactly one of the three query keywords."""
+    given = [n for n, v in (("query_keys", query_keys), ("query_key_ranges", query_key_ranges), ("query_key_sets", query_key_sets))
+             if v is not None]
+    if filter_keys is None and not given:
+        return None
+    if filter_keys is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, given[0] + " needs filter_keys=")
+    if not given:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "filter_keys= needs query_keys=, query_key_ranges= or query_key_sets=")
+    return _expand_filter(_key_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq, device=device), device=device)
+
+
 def _allow_array(allowed, n_rows, what="row mask"):
     """A caller's allow array -> contiguous uint8 [n_rows]: bool or uint8, one entry per row; anything else is refused."""
     if allowed is None:
@@ -892,11 +906,15 @@ class Searcher:
                                    nc.ctypes.data_as(u64p)))
         return rows, dist, nf, nc
 
-    def topk_distinct(self, queries, k, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+    def topk_distinct(self, queries, k, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True,
+                      filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None):
         """Distinct top-k (pqv.h: pqv_topk_distinct): per query the nearest row of each of the k nearest groups, a group being the
         considered rows of one value of `keys` (a RowKeys of this searcher; NULL-key rows belong to no group), under `mask` if one
         is given.  Returns (row_idx [nq,k] u32, dist [nq,k] f32, group_keys [nq,k] i64, n_found [nq], n_candidates [nq]), ascending
-        by (d2, candidate position); entries past n_found are 0xFFFFFFFF, +inf and 0."""
+        by (d2, candidate position); entries past n_found are 0xFFFFFFFF, +inf and 0.
+        filter_keys (a RowKeys of this searcher; it may be `keys`) with one of query_keys / query_key_ranges / query_key_sets, as
+        topk takes them: query q considers only the rows whose filter key passes ITS test -- the filter applies before a group's
+        representative is chosen (pqv.h: pqv_topk_distinct_filtered)."""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -906,6 +924,14 @@ class Searcher:
         grp = np.zeros((nq, max(k, 1)), dtype=np.int64)
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
+        gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if gf is not None:
+            _check(_ffi.lib().pqv_topk_distinct_filtered(self._h, _group_handle(keys), gf[0], gf[1],
+                                                         _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
+                                                         qlen, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                         rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), grp.ctypes.data_as(_ffi.i64p),
+                                                         nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p)))
+            return rows, dist, grp, nf, nc
         _check(_ffi.lib().pqv_topk_distinct(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
                                             q.ctypes.data_as(f32p), nq, qlen, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
                                             rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), grp.ctypes.data_as(_ffi.i64p),
@@ -913,20 +939,34 @@ class Searcher:
         return rows, dist, grp, nf, nc
 
     def topk_distinct_device(self, d_queries, nq, k, nprobe, keys, d_row_idx, d_dist, d_group_key=0, d_n_found=0, d_n_candidates=0,
-                             mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+                             mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, filter_keys=None,
+                             query_keys=None, query_key_ranges=None, query_key_sets=None):
         """Device-pointer form of topk_distinct (pqv.h: pqv_topk_distinct_device), asynchronous on `stream` as topk_device is:
         d_row_idx u32 / d_dist f32 / d_group_key i64 [nq, k], d_n_found u32 / d_n_candidates u64 [nq]; the last three are optional.
-        keys and mask must stay alive until the enqueued work has completed."""
+        keys and mask must stay alive until the enqueued work has completed.
+        filter_keys with query_keys / query_key_ranges / query_key_sets as DEVICE pointers, as topk_device takes them, read on
+        `stream` inside the enqueued work (pqv.h: pqv_topk_distinct_filtered_device)."""
+        gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        if gf is not None:
+            _check(_ffi.lib().pqv_topk_distinct_filtered_device(self._h, _group_handle(keys), gf[0], gf[1],
+                                                                _mask_handle(self, mask) if mask is not None else None, vp(d_queries), nq, k,
+                                                                nprobe, max_candidates, metric, 1 if sqrt_out else 0, vp(d_row_idx),
+                                                                vp(d_dist), vp(d_group_key or None), vp(d_n_found or None),
+                                                                vp(d_n_candidates or None), vp(stream or None)))
+            return
         _check(_ffi.lib().pqv_topk_distinct_device(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
                                                    vp(d_queries), nq, k, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
                                                    vp(d_row_idx), vp(d_dist), vp(d_group_key or None), vp(d_n_found or None),
                                                    vp(d_n_candidates or None), vp(stream or None)))
 
-    def topk_grouped(self, queries, k, group_size, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+    def topk_grouped(self, queries, k, group_size, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True,
+                     filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None):
         """Grouped top-k (pqv.h: pqv_topk_grouped): per query up to group_size rows of each of the k nearest groups of `keys` (as
         topk_distinct defines groups), under `mask` if one is given.  Returns (row_idx [nq,k,group_size] u32, dist [nq,k,group_size]
         f32, group_keys [nq,k] i64, group_rows [nq,k] u32, n_found [nq], n_candidates [nq]): groups ascending by their nearest row,
-        a group's rows ascending by (d2, candidate position); empty row slots are 0xFFFFFFFF / +inf, empty groups key 0, count 0."""
+        a group's rows ascending by (d2, candidate position); empty row slots are 0xFFFFFFFF / +inf, empty groups key 0, count 0.
+        filter_keys with query_keys / query_key_ranges / query_key_sets: a per-query filter, as topk_distinct takes it (pqv.h:
+        pqv_topk_grouped_filtered)."""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -938,6 +978,14 @@ class Searcher:
         grows = np.zeros(shape[:2], dtype=np.uint32)
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
+        gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if gf is not None:
+            _check(_ffi.lib().pqv_topk_grouped_filtered(self._h, _group_handle(keys), gf[0], gf[1],
+                                                        _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
+                                                        qlen, k, group_size, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                        rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), grp.ctypes.data_as(_ffi.i64p),
+                                                        grows.ctypes.data_as(u32p), nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p)))
+            return rows, dist, grp, grows, nf, nc
         _check(_ffi.lib().pqv_topk_grouped(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
                                            q.ctypes.data_as(f32p), nq, qlen, k, group_size, nprobe, max_candidates, metric,
                                            1 if sqrt_out else 0, rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p),
@@ -946,10 +994,21 @@ class Searcher:
         return rows, dist, grp, grows, nf, nc
 
     def topk_grouped_device(self, d_queries, nq, k, group_size, nprobe, keys, d_row_idx, d_dist, d_group_key=0, d_group_rows=0, d_n_found=0,
-                            d_n_candidates=0, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+                            d_n_candidates=0, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0,
+                            filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None):
         """Device-pointer form of topk_grouped (pqv.h: pqv_topk_grouped_device), asynchronous on `stream` as topk_device is:
         d_row_idx u32 / d_dist f32 [nq, k, group_size], d_group_key i64 / d_group_rows u32 [nq, k], d_n_found u32 / d_n_candidates u64
-        [nq]; the last four are optional.  Serves k * group_size <= 1024.  keys and mask must stay alive until the work has completed."""
+        [nq]; the last four are optional.  Serves k * group_size <= 1024.  keys and mask must stay alive until the work has completed.
+        filter_keys with device-pointer query_keys / query_key_ranges / query_key_sets: as topk_distinct_device (pqv.h:
+        pqv_topk_grouped_filtered_device)."""
+        gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        if gf is not None:
+            _check(_ffi.lib().pqv_topk_grouped_filtered_device(self._h, _group_handle(keys), gf[0], gf[1],
+                                                               _mask_handle(self, mask) if mask is not None else None, vp(d_queries), nq, k,
+                                                               group_size, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                                               vp(d_row_idx), vp(d_dist), vp(d_group_key or None), vp(d_group_rows or None),
+                                                               vp(d_n_found or None), vp(d_n_candidates or None), vp(stream or None)))
+            return
         _check(_ffi.lib().pqv_topk_grouped_device(self._h, _group_handle(keys), _mask_handle(self, mask) if mask is not None else None,
                                                   vp(d_queries), nq, k, group_size, nprobe, max_candidates, metric, 1 if sqrt_out else 0,
                                                   vp(d_row_idx), vp(d_dist), vp(d_group_key or None), vp(d_group_rows or None),

@@ -700,6 +700,12 @@ static int upload_query_filter(Scratch &sc, const MaskView *mask, MaskView &sub,
     }
     return PQV_OK;
 }
+// the per-query filter of a distinct / grouped call that has one (mv->keys beside mv->group), as its kernels read it
+static pqv::GroupFilterArgs group_filter_args(const MaskView *mv) {
+    const pqv_row_keys *kk = mv->keys;
+    return pqv::GroupFilterArgs{kk->d_key_pos.p, kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr, kk->dtype == PQV_COL_I32 ? 4u : 8u,
+                                mv->fkind, mv->fkind ? mv->d_fa : mv->d_qkeys, mv->fkind ? mv->d_fb : nullptr};
+}
 // the STREAM_TOPK / STREAM_RANGE pass of a masked or keyed call
 // (a distinct call: STREAM_TOPK only, the per-wave lists' group values go to part_grp)
 static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskView *mv, unsigned long long *stats, const uint64_t *n_cand,
@@ -710,6 +716,7 @@ static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskVi
         const pqv_row_keys *gk = mv->group;
         const pqv::DistinctArgs da{mv->bits, stats, n_cand, gk->d_key_pos.p, gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr,
                                    gk->dtype == PQV_COL_I32 ? 4u : 8u, part_grp};
+        if (mv->keys) return pqv::launch_distinct_filter_stream(ra, da, group_filter_args(mv), stream);
         return pqv::launch_distinct_stream(ra, da, stream);
     }
     if (mv->keys) {
@@ -4056,7 +4063,8 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
             ga.k = k; ga.group_size = gm; ga.km = static_cast<uint32_t>(km);
             ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
             ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
-            HIP_TRY(launch_grouped_stream(ra, ga, stream));
+            if (mask->keys) HIP_TRY(launch_grouped_filter_stream(ra, ga, group_filter_args(mask), stream));
+            else HIP_TRY(launch_grouped_stream(ra, ga, stream));
             GroupedMergeArgs gma{};
             gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
             gma.nq = nq; gma.n_part = p.n_part_rr; gma.k = k; gma.group_size = gm; gma.km = ga.km;
@@ -5343,6 +5351,8 @@ int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const MaskView *mv, c
     HIP_TRY(hipMemcpy(d_img.p, img.data(), n_words * sizeof(uint64_t), hipMemcpyHostToDevice));
     MaskView rv{};
     rv.bits = d_img.as<uint64_t>();
+    // (a filtered call: the per-query filter travels beside the image, as in pqv_range_search_filtered)
+    rv.keys = mv->keys; rv.h_qkeys = mv->h_qkeys; rv.fkind = mv->fkind; rv.h_fa = mv->h_fa; rv.h_fb = mv->h_fb;
     std::unique_ptr<uint64_t, HostFree> lims(static_cast<uint64_t *>(std::malloc((static_cast<size_t>(nq) + 1) * sizeof(uint64_t))));
     std::unique_ptr<uint32_t, HostFree> rows(static_cast<uint32_t *>(std::malloc(sizeof(uint32_t))));
     std::unique_ptr<float, HostFree> d2(static_cast<float *>(std::malloc(sizeof(float))));
@@ -5439,12 +5449,15 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
     if (group_rows) HIP_TRY(sc.s_grows_out.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
     HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
+    if (mv->keys && !mv->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     MaskView sub = *mv;
     sub.d_group_out = sc.s_grp_out.as<int64_t>();
     sub.d_group_rows = group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr;
+    std::vector<uint64_t> sub_lims;      // (a filtered call: each sub-batch's kernels read its own slice of the filter, IN lims rebased)
     for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
         const uint32_t b = std::min<uint32_t>(batch, nq - q0);
         const uint64_t o = static_cast<uint64_t>(q0) * k;
+        if (int rc = upload_query_filter(sc, mv, sub, q0, b, sub_lims, s->stream)) return rc;
         const size_t nk = static_cast<size_t>(b) * k;
         const uint64_t om = o * m;
         const size_t nkm = nk * m;
@@ -5516,6 +5529,75 @@ extern "C" int pqv_topk_grouped_device(const pqv_searcher *s, const pqv_row_keys
     return guard([&] {
         MaskView mv{};
         if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
+        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, nullptr, hip_stream, &mv);
+    });
+}
+
+// ---- distinct / grouped top-k under a per-query key filter (pqv.h: pqv_topk_distinct_filtered) ---------------------------------
+// Both halves of the view in the contract's order: every NULL and zero check, the descriptor's included, before a handle is read.
+// group_size: nullptr for the distinct forms.
+static int group_filtered_view(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys, const pqv_key_filter *filter,
+                               const pqv_row_mask *mask, uint32_t nq, uint32_t k, const uint32_t *group_size, bool host, MaskView &mv) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!group_keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
+    if (!filter_keys) return fail(PQV_ERR_INVALID, "a key filter needs row keys");
+    if (!filter) return fail(PQV_ERR_INVALID, "filter must not be NULL");
+    if (int rc = filter_descriptor_checks(filter, nq, host)) return rc;
+    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (group_size && *group_size == 0) return fail(PQV_ERR_INVALID, "group_size must be > 0");
+    if (group_keys->owner != s || group_keys->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
+    // (the filter column's owner and the mask's: filtered_view)
+    if (int rc = filtered_view(s, filter_keys, filter, nq, mask, host, mv, true)) return rc;
+    mv.group = group_keys;
+    mv.group_size = group_size ? *group_size : 0u;
+    return PQV_OK;
+}
+extern "C" int pqv_topk_distinct_filtered(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                          const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                          uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                          uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, true, mv)) return rc;
+        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
+                                      n_found, n_candidates);
+    });
+}
+extern "C" int pqv_topk_distinct_filtered_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                                 const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                                 uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, void *d_row_idx,
+                                                 void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, false, mv)) return rc;
+        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, nullptr, hip_stream, &mv);
+    });
+}
+extern "C" int pqv_topk_grouped_filtered(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                         const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                         uint32_t query_len, uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric,
+                                         int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found,
+                                         uint64_t *n_candidates) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, true, mv)) return rc;
+        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
+                                      n_found, n_candidates, group_rows);
+    });
+}
+extern "C" int pqv_topk_grouped_filtered_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                                const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                                uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                                void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
+                                                void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, false, mv)) return rc;
         mv.d_group_out = static_cast<int64_t *>(d_group_key);
         mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,

@@ -234,6 +234,23 @@ hipError_t launch_grouped_merge(const GroupedMergeArgs &a, hipStream_t s);
 // group_size == 1 (the distinct call, one row per group): group_rows[q][g] = g < n_found[q] ? 1 : 0
 hipError_t launch_group_rows_fill(const uint32_t *n_found, uint32_t nq, uint32_t k, uint32_t *group_rows, hipStream_t s);
 
+// ---- distinct / grouped top-k under a per-query key filter (kernels_distinct_filter.hip; pqv.h: pqv_topk_distinct_filtered) ----
+// The filter of such a call: a second key column's position image and the descriptor's device arrays.  kind 0 (PQV_KEY_EQ): a = i64
+// [nq] query keys; 1 (PQV_KEY_RANGE): a / b = i64 [nq] inclusive bounds; 2 (PQV_KEY_IN): a = u64 lims [nq + 1], b = i64 values, at
+// most KEY_SET_MAX of a query's slice are read.  A position passes iff its filter key is valid and meets the query's test.
+struct GroupFilterArgs {
+    const void     *key_pos;    // i32 / i64 [n_words * 64]: the filter key of every list position
+    const uint64_t *valid_pos;  // optional [n_words]: positions whose filter key is not NULL
+    uint32_t        elem_size;  // 4 or 8
+    uint32_t        kind;
+    const void     *a;
+    const void     *b;
+};
+// launch_distinct_stream / launch_grouped_stream over the positions that also pass fa (distinct_filter_stream_kernel,
+// grouped_filter_stream_kernel): the same arguments, outputs and folds
+hipError_t launch_distinct_filter_stream(const StreamArgs &a, const DistinctArgs &da, const GroupFilterArgs &fa, hipStream_t s);
+hipError_t launch_grouped_filter_stream(const StreamArgs &a, const GroupedArgs &ga, const GroupFilterArgs &fa, hipStream_t s);
+
 // ---- predicate masks (kernels_predicate.hip) -----------------------------------------------------------------------------
 // A mask's ROW IMAGE is the bitset in row order: bit r of word r / 64 = row r is allowed, ceil(n_rows / 64) words, bits of rows
 // >= n_rows zero.  predicate_rows_kernel writes it from resident columns and a postfix program (pqv.h:

@@ -19,113 +19,11 @@
 // in the global top k is, with its global representative r, in the top k of the partition P that holds r -- every group that
 // precedes it in P's list has a representative in P smaller than r, hence a global representative smaller than r, and fewer than
 // k groups have one.  So r reaches the fold, where the same offer keeps the smallest entry per group.
-#include "device_common.hpp"
+#include "wave_group_lists.hpp"
 
 namespace pqv {
 
-// ------------------------------------------------------------------------------------
-// Element e lives in slot e / 64, lane e % 64; ascending by key = (d2 bits << 32) | candidate position; grp[s][0 .. GW) are the
-// 32-bit words of the entry's group value (GW = 1: an i32 column's value, GW = 2: the halves of an i64).  Entries at or beyond k
-// are spill room, as in WaveTopk: they stay sorted and distinct but are never read out.
-// ------------------------------------------------------------------------------------
-template <int S, int GW>
-struct WaveDistinctTopk {
-    uint64_t key[S];
-    uint32_t val[S];
-    uint32_t grp[S][GW];
-
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            key[s] = KEY_EMPTY; val[s] = 0xFFFFFFFFu;
-#pragma unroll
-            for (int w = 0; w < GW; ++w) grp[s][w] = 0u;
-        }
-    }
-    // key of element k-1 (the admission threshold); k is wave-uniform
-    __device__ __forceinline__ uint64_t kth(uint32_t k) const {
-        const uint32_t e = k - 1;
-        uint64_t r = KEY_EMPTY;
-#pragma unroll
-        for (int s = 0; s < S; ++s)
-            if ((int)(e >> 6) == s) r = readlane_u64(key[s], (int)(e & 63));
-        return r;
-    }
-    // insert (x, xv, g), all wave-uniform, x < KEY_EMPTY
-    __device__ __forceinline__ void insert(uint64_t x, uint32_t xv, const uint32_t (&g)[GW], int lane) {
-        // the one filled slot of g's group, if any: a ballot per slot register, both halves of an i64 compared
-        int e_old = -1;
-        uint64_t old_key = KEY_EMPTY;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            bool same = key[s] != KEY_EMPTY;
-#pragma unroll
-            for (int w = 0; w < GW; ++w) same = same && grp[s][w] == g[w];
-            const unsigned long long m = __ballot(same);
-            if (m) {
-                const int l = __builtin_ctzll(m);
-                e_old = s * 64 + l;
-                old_key = readlane_u64(key[s], l);
-            }
-        }
-        if (e_old >= 0 && old_key < x) return;          // the group's entry is nearer: drop the candidate
-        int p = 0;                                      // rank of x
-#pragma unroll
-        for (int s = 0; s < S; ++s) p += __popcll(__ballot(key[s] < x));
-        // elements (p, hi] move up by one and x goes to p: hi = the group's old entry (p <= e_old: nothing falls off the end), or
-        // the end of the list (WaveTopk::insert: the largest element is dropped)
-        const int hi = e_old >= 0 ? e_old : S * 64 - 1;
-#pragma unroll
-        for (int s = S - 1; s >= 0; --s) {
-            if (s * 64 > hi || s * 64 + 63 < p) continue;          // (wave-uniform) no element of this slot changes
-            uint64_t up = shfl_up1_u64(key[s]);
-            uint32_t upv = (uint32_t)__shfl_up((int)val[s], 1, 64);
-            uint32_t upg[GW];
-#pragma unroll
-            for (int w = 0; w < GW; ++w) upg[w] = (uint32_t)__shfl_up((int)grp[s][w], 1, 64);
-            if (s > 0) {
-                const uint64_t pk = readlane_u64(key[s - 1], 63);
-                const uint32_t pv = readlane_u32(val[s - 1], 63);
-                uint32_t pg[GW];
-#pragma unroll
-                for (int w = 0; w < GW; ++w) pg[w] = readlane_u32(grp[s - 1][w], 63);
-                if (lane == 0) {
-                    up = pk; upv = pv;
-#pragma unroll
-                    for (int w = 0; w < GW; ++w) upg[w] = pg[w];
-                }
-            }
-            const int e = s * 64 + lane;
-            if (e > p && e <= hi) {
-                key[s] = up; val[s] = upv;
-#pragma unroll
-                for (int w = 0; w < GW; ++w) grp[s][w] = upg[w];
-            } else if (e == p) {
-                key[s] = x; val[s] = xv;
-#pragma unroll
-                for (int w = 0; w < GW; ++w) grp[s][w] = g[w];
-            }
-        }
-    }
-    // offer one candidate per lane (mykey == KEY_EMPTY for lanes with none).  mykey < kth(k) stays the admission test: a candidate
-    // at or above the k-th entry cannot improve a group that is in the first k, and cannot enter them otherwise.
-    __device__ __forceinline__ void offer(uint64_t mykey, uint32_t myval, const uint32_t (&mygrp)[GW], uint32_t k, int lane) {
-        uint64_t thr = kth(k);
-        unsigned long long m = __ballot(mykey < thr);
-        while (m) {
-            const int L = __builtin_ctzll(m);
-            const uint64_t x = readlane_u64(mykey, L);
-            const uint32_t xv = readlane_u32(myval, L);
-            uint32_t g[GW];
-#pragma unroll
-            for (int w = 0; w < GW; ++w) g[w] = readlane_u32(mygrp[w], L);
-            insert(x, xv, g, lane);
-            thr = kth(k);
-            m &= m - 1;
-            m &= __ballot(mykey < thr);
-        }
-    }
-};
+// WaveDistinctTopk<S, GW>: wave_group_lists.hpp
 
 // the 64 bits of a position image from position p on (one word of padding behind the last position: wi + 1 is always in range)
 __device__ __forceinline__ uint64_t distinct_image_window(const uint64_t *bits, uint64_t p) {

@@ -19,79 +19,11 @@
 //
 // The fold is exact for the plain reason: each of slot g's global group_size smallest keys is among the group_size smallest of
 // the partition that holds it, so it reaches the fold, where the same offer keeps the smallest per slot.
-#include "device_common.hpp"
+#include "wave_group_lists.hpp"
 
 namespace pqv {
 
-constexpr uint32_t GROUPED_SLOT_EMPTY = 0xFFFFFFFFu;
-
-// ------------------------------------------------------------------------------------
-// Element e lives in slot register e / 64, lane e % 64; ascending by (slot, key), key = (d2 bits << 32) | candidate position; the
-// n filled elements are [0, n), everything behind them is (GROUPED_SLOT_EMPTY, KEY_EMPTY).  A group's entries are contiguous:
-// group g's i-th nearest row is element (entries of slots < g) + i.
-// ------------------------------------------------------------------------------------
-template <int S>
-struct WaveGroupedTopk {
-    uint64_t key[S];
-    uint32_t val[S];
-    uint32_t slot[S];
-    uint32_t n;         // filled elements (wave-uniform)
-
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int s = 0; s < S; ++s) { key[s] = KEY_EMPTY; val[s] = 0xFFFFFFFFu; slot[s] = GROUPED_SLOT_EMPTY; }
-        n = 0;
-    }
-    // insert (x, xv, sl), all wave-uniform, x < KEY_EMPTY, sl < k; m = group_size
-    __device__ __forceinline__ void insert(uint64_t x, uint32_t xv, uint32_t sl, uint32_t m, int lane) {
-        // slot sl's segment [lo, lo + cnt) and the rank of x inside it: three ballots per slot register
-        int lo = 0, cnt = 0, below = 0;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            lo += __popcll(__ballot(slot[s] < sl));
-            cnt += __popcll(__ballot(slot[s] == sl));
-            below += __popcll(__ballot(slot[s] == sl && key[s] < x));
-        }
-        const int p = lo + below;                       // rank of (sl, x)
-        // elements (p, hi] move up by one and x goes to p.  The segment has room: hi = n, the first empty element (n < k * m <= S * 64
-        // while some slot is short).  It is full: x replaces the segment's largest entry lo + cnt - 1, or is dropped when it is
-        // not smaller than that (below == cnt).
-        int hi;
-        if ((uint32_t)cnt < m) {
-            hi = (int)n;
-            if (hi >= S * 64) return;                   // (never: only members are offered)
-            ++n;
-        } else {
-            if (below == cnt) return;
-            hi = lo + cnt - 1;
-        }
-#pragma unroll
-        for (int s = S - 1; s >= 0; --s) {
-            if (s * 64 > hi || s * 64 + 63 < p) continue;          // (wave-uniform) no element of this slot register changes
-            uint64_t up = shfl_up1_u64(key[s]);
-            uint32_t upv = (uint32_t)__shfl_up((int)val[s], 1, 64);
-            uint32_t ups = (uint32_t)__shfl_up((int)slot[s], 1, 64);
-            if (s > 0) {
-                const uint64_t pk = readlane_u64(key[s - 1], 63);
-                const uint32_t pv = readlane_u32(val[s - 1], 63);
-                const uint32_t ps = readlane_u32(slot[s - 1], 63);
-                if (lane == 0) { up = pk; upv = pv; ups = ps; }
-            }
-            const int e = s * 64 + lane;
-            if (e > p && e <= hi) { key[s] = up; val[s] = upv; slot[s] = ups; }
-            else if (e == p) { key[s] = x; val[s] = xv; slot[s] = sl; }
-        }
-    }
-    // offer one candidate per lane (mykey == KEY_EMPTY for lanes with none)
-    __device__ __forceinline__ void offer(uint64_t mykey, uint32_t myval, uint32_t myslot, uint32_t m, int lane) {
-        unsigned long long todo = __ballot(mykey != KEY_EMPTY);
-        while (todo) {
-            const int L = __builtin_ctzll(todo);
-            insert(readlane_u64(mykey, L), readlane_u32(myval, L), readlane_u32(myslot, L), m, lane);
-            todo &= todo - 1;
-        }
-    }
-};
+// GROUPED_SLOT_EMPTY, WaveGroupedTopk<S>: wave_group_lists.hpp
 
 // the 64 bits of a position image from position p on (distinct_image_window: one word of padding behind the last position)
 __device__ __forceinline__ uint64_t grouped_image_window(const uint64_t *bits, uint64_t p) {

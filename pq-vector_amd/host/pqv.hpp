@@ -252,6 +252,35 @@ public:
         check(pqv_topk_grouped(s.get(), h_.get(), mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, group_size, nprobe, 0,
                                PQV_L2SQ_REF4, 1, rows.data(), dist.data(), group_keys.data(), group_rows.data(), found.data(), nullptr));
     }
+    // topk_distinct / topk_grouped with one filter PER QUERY on `filter_keys` (it may be this column), applied before a group's
+    // representative is chosen (pqv.h: pqv_topk_distinct_filtered, pqv_topk_grouped_filtered); nq = filter.queries()
+    void topk_distinct_filtered(const Searcher &s, const RowKeys &filter_keys, const KeyFilter &filter, const std::vector<float> &queries,
+                                uint32_t k, uint32_t nprobe, std::vector<uint32_t> &rows, std::vector<float> &dist,
+                                std::vector<int64_t> &group_keys, std::vector<uint32_t> &found, const RowMask *mask = nullptr) const {
+        const uint32_t nq = filter.queries();
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, 0.0f);
+        group_keys.assign(static_cast<size_t>(nq) * k, 0);
+        found.assign(nq, 0);
+        const pqv_key_filter d = filter.descriptor();
+        check(pqv_topk_distinct_filtered(s.get(), h_.get(), filter_keys.get(), &d, mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k,
+                                         nprobe, 0, PQV_L2SQ_REF4, 1, rows.data(), dist.data(), group_keys.data(), found.data(), nullptr));
+    }
+    void topk_grouped_filtered(const Searcher &s, const RowKeys &filter_keys, const KeyFilter &filter, const std::vector<float> &queries,
+                               uint32_t k, uint32_t group_size, uint32_t nprobe, std::vector<uint32_t> &rows, std::vector<float> &dist,
+                               std::vector<int64_t> &group_keys, std::vector<uint32_t> &group_rows, std::vector<uint32_t> &found,
+                               const RowMask *mask = nullptr) const {
+        const uint32_t nq = filter.queries();
+        rows.assign(static_cast<size_t>(nq) * k * group_size, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k * group_size, std::numeric_limits<float>::infinity());
+        group_keys.assign(static_cast<size_t>(nq) * k, 0);
+        group_rows.assign(static_cast<size_t>(nq) * k, 0);
+        found.assign(nq, 0);
+        const pqv_key_filter d = filter.descriptor();
+        check(pqv_topk_grouped_filtered(s.get(), h_.get(), filter_keys.get(), &d, mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k,
+                                        group_size, nprobe, 0, PQV_L2SQ_REF4, 1, rows.data(), dist.data(), group_keys.data(), group_rows.data(),
+                                        found.data(), nullptr));
+    }
 private:
     struct Del { void operator()(pqv_row_keys *p) const { pqv_row_keys_free(p); } };
     std::unique_ptr<pqv_row_keys, Del> h_;
