@@ -19,26 +19,19 @@
 // in the global top k is, with its global representative r, in the top k of the partition P that holds r -- every group that
 // precedes it in P's list has a representative in P smaller than r, hence a global representative smaller than r, and fewer than
 // k groups have one.  So r reaches the fold, where the same offer keeps the smallest entry per group.
+#include "stream_walk.hpp"
 #include "wave_group_lists.hpp"
 
 namespace pqv {
 
 // WaveDistinctTopk<S, GW>: wave_group_lists.hpp
 
-// the 64 bits of a position image from position p on (one word of padding behind the last position: wi + 1 is always in range)
-__device__ __forceinline__ uint64_t distinct_image_window(const uint64_t *bits, uint64_t p) {
-    const uint64_t wi = p >> 6;
-    const uint32_t sh = (uint32_t)(p & 63u);
-    const uint64_t lo = bits[wi], hi = bits[wi + 1];
-    return sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
-}
-
 // ------------------------------------------------------------------------------------
 // distinct_stream_kernel
 //
-// masked_stream_kernel's STREAM_TOPK pass, restated: its grid (row block, probe rank, query), its 4 independent waves per block,
-// its walk over 64-position windows with the queue in a register and the compaction through the idle tile area, its chain
-// arithmetic element for element, its keys (d2 bits << 32) | (u32)(cbase + position) and its statistics words.  A window's 64
+// masked_stream_kernel's STREAM_TOPK pass, composed of the same pieces (stream_walk.hpp): its grid (row block, probe rank, query),
+// its 4 independent waves per block, its clamped walk range, its filtered walk, its chain tile, its keys
+// (d2 bits << 32) | (u32)(cbase + position) and its statistics words.  A window's 64
 // bits are the funnel-shifted words of the group column's validity image ANDed with those of the shared mask -- all ones where the
 // call has neither -- clipped to the range and the cap exactly as there: a NULL-key row belongs to no group and is never read.
 // What is new: lane l loads its row's group value key_pos[lbeg + my_r] (one gathered 4- / 8-byte load per evaluated row, issued
@@ -47,202 +40,36 @@ __device__ __forceinline__ uint64_t distinct_image_window(const uint64_t *bits, 
 // ------------------------------------------------------------------------------------
 template <int CG, int S, bool SEQ, bool ALIGNED, int GW>
 __global__ __launch_bounds__(256) void distinct_stream_kernel(const StreamArgs a, const DistinctArgs da) {
-    constexpr int RPI = 64 / CG;        // rows per load instruction
-    constexpr int NI = CG;              // load instructions per 64-row tile
-    constexpr int EPL = SEQ ? 4 : 1;    // LDS values per lane item
-    constexpr int LROWS = CG * EPL;     // chain length per chunk
-    constexpr int NB = 8;               // loads in flight per lane
-    static_assert(NI % NB == 0, "NI must be a multiple of NB");
-    static_assert(LROWS * 64 >= 128, "the compaction needs 128 words of the tile area");
-
-    __shared__ float lds_all[4 * LROWS * 64];
+    static_assert(tile_words<CG, SEQ>() >= WindowQueue<false>::SCRATCH, "the compaction needs 128 words of the tile area");
+    __shared__ float lds_all[4 * tile_words<CG, SEQ>()];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    float *lds = lds_all + wave * (LROWS * 64);
-    uint32_t *cq = reinterpret_cast<uint32_t *>(lds);          // compaction scratch: 128 entries
-#define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
+    float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y;
-    const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
-    const uint64_t lbeg = a.list_off[c], lend = a.list_off[c + 1];
-    const uint64_t cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
-    const uint64_t lim = a.pair_end ? a.pair_end[(uint64_t)q * a.nprobe + j] : a.max_pos;
-    uint64_t len = lend - lbeg;
-    // positions at or beyond the cap are no candidates: the walk ends there (their bits are never looked at)
-    const uint64_t room = lim > cbase ? lim - cbase : 0;
-    if (len > room) len = room;
-    const uint64_t wrows = a.rows_per_block / 4;
-    const uint64_t r0 = (uint64_t)blockIdx.x * a.rows_per_block + (uint64_t)wave * wrows;
-    uint64_t r1 = r0 + wrows;
-    if (r1 > len) r1 = len;
+    const WalkRange w = walk_range<true>(a, q, j, wave);
+    unsigned long long *st = stats_slot(da.stats, q);
+    stats_add_candidates(st, da.n_cand, q, j);
 
-#ifdef PQV_PROFILE_PHASES
-    unsigned long long *st = da.stats;
-#else
-    unsigned long long *st = da.stats ? da.stats + 8 + 16 * (q % STATS_SLOTS) : nullptr;
-#endif
-    if (da.n_cand && st && blockIdx.x == 0 && j == 0 && threadIdx.x == 0) atomicAdd(&st[2], (unsigned long long)da.n_cand[q]);
-
-    const uint32_t dim = a.dim;
-    const uint32_t G = dim >> 2;
-    const uint32_t tail = dim & 3u;
-    const float *qv = a.queries + (uint64_t)q * dim;
-    const int g_in = lane % CG;      // my float4 group inside a chunk
-    const int row_in = lane / CG;    // my row inside a load instruction
-
+    const float *qv = a.queries + (uint64_t)q * a.dim;
     WaveDistinctTopk<S, GW> tk;
     tk.init();
 
-    uint32_t pend = 0;      // queue entry `lane` (a list offset, < 2^32 as every candidate position), meaningful for lane < qn
-    uint32_t qn = 0;        // queued entries, < 64 between two windows (wave-uniform)
-    uint32_t n_eval = 0;    // rows this wave evaluated (wave-uniform)
-    for (uint64_t w0 = r0;; w0 += 64) {
-        const bool flush = w0 >= r1;        // past the range: what is left in the queue is the last tile
-        uint32_t nvalid = 0;                // rows of the chain tile this turn runs (0: none)
-        uint32_t my_r = 0;                  // list offset of tile row `lane`
-        if (!flush) {
-            const uint64_t p = lbeg + w0;
-            uint64_t win = ~0ull;
-            if (da.valid_pos) win &= distinct_image_window(da.valid_pos, p);
-            if (da.bits) win &= distinct_image_window(da.bits, p);
-            if (r1 - w0 < 64) win &= (1ull << (r1 - w0)) - 1ull;
-            const uint32_t cnt = (uint32_t)__popcll(win);
-            if (cnt == 0) continue;
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(win >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)win, 0u));
-            if ((uint32_t)lane < qn) cq[lane] = pend;
-            if ((win >> lane) & 1ull) cq[qn + rank] = (uint32_t)(w0 + (uint64_t)lane);
-            wave_lds_fence();
-            const uint32_t total = qn + cnt;                   // <= 127
-            const uint32_t first = cq[lane];
-            const uint32_t over = cq[64 + lane];
-            wave_lds_fence();
-            if (total >= 64) {
-                my_r = first; nvalid = 64u;
-                pend = over; qn = total - 64;
-            } else {
-                pend = first; qn = total;
-            }
-        } else if (qn) {
-            const uint32_t last = (uint32_t)__shfl((int)pend, (int)(qn - 1), 64);
-            my_r = (uint32_t)lane < qn ? pend : last;         // (clamped: every address in range)
-            nvalid = qn; qn = 0;
-        }
-        if (nvalid) {
-            n_eval += nvalid;
-            const uint64_t lpos = lbeg + my_r;
-            const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
-            // my row's group value (lpos < the image's n_pos: a candidate position), back by the end of the chain
-            uint32_t mygrp[GW];
-            if constexpr (GW == 1) {
-                mygrp[0] = static_cast<const uint32_t *>(da.key_pos)[lpos];
-            } else {
-                const uint64_t gv = static_cast<const uint64_t *>(da.key_pos)[lpos];
-                mygrp[0] = (uint32_t)gv; mygrp[1] = (uint32_t)(gv >> 32);
-            }
-
-            float sum = 0.0f;
-            for (uint32_t c0 = 0; c0 < G; c0 += CG) {
-                const uint32_t ng = (G - c0 < (uint32_t)CG) ? (G - c0) : (uint32_t)CG;
-                const bool gvalid = (uint32_t)g_in < ng;
-                const uint32_t goff = (c0 + (gvalid ? g_in : 0)) * 4;
-                const float4 qq = load4<ALIGNED>(qv + goff);
-
-#pragma unroll 1
-                for (int ib = 0; ib < NI; ib += NB) {
-                    float4 x[NB];
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) {
-                        uint32_t rr = (uint32_t)((ib + u) * RPI + row_in);
-                        if (rr >= nvalid) rr = nvalid - 1;
-                        const uint32_t srow = (uint32_t)__shfl((int)my_srow, (int)rr, 64);
-                        x[u] = load4<ALIGNED>(a.mat + (uint64_t)srow * dim + goff);
-                    }
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) {
-                        const int rr = (ib + u) * RPI + row_in;
-                        const float d0 = qq.x - x[u].x, d1 = qq.y - x[u].y;
-                        const float d2 = qq.z - x[u].z, d3 = qq.w - x[u].w;
-                        if constexpr (SEQ) {
-                            if (gvalid) {
-                                LDS_AT(g_in * 4 + 0, rr) = d0 * d0;
-                                LDS_AT(g_in * 4 + 1, rr) = d1 * d1;
-                                LDS_AT(g_in * 4 + 2, rr) = d2 * d2;
-                                LDS_AT(g_in * 4 + 3, rr) = d3 * d3;
-                            }
-                        } else {
-                            float t = d0 * d0 + d1 * d1;
-                            t = t + d2 * d2;
-                            t = t + d3 * d3;
-                            if (gvalid) LDS_AT(g_in, rr) = t;
-                        }
-                    }
-                }
-                wave_lds_fence();
-                const uint32_t nchain = ng * EPL;
-                uint32_t e = 0;
-                for (; e + 8 <= nchain; e += 8) {
-                    float v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = LDS_AT(e + u, lane);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) sum = sum + v[u];
-                }
-                for (; e < nchain; ++e) sum = sum + LDS_AT(e, lane);
-                wave_lds_fence();
-            }
-            if (tail) {  // scalar tail of squared_l2_distance
-                const float *xr = a.mat + (uint64_t)my_srow * dim + (uint64_t)G * 4;
-                const float *qt = qv + (uint64_t)G * 4;
-                for (uint32_t e = 0; e < tail; ++e) {
-                    const float d = qt[e] - xr[e];
-                    sum = sum + d * d;
-                }
-            }
-
-            const uint64_t pos = cbase + my_r;
-            const bool valid = (uint32_t)lane < nvalid;           // (pos < lim by the clamp of the walk)
-            const uint64_t mykey = valid ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos) : KEY_EMPTY;
-            tk.offer(mykey, my_srow, mygrp, a.k, lane);
-        }
-        if (flush) break;
-    }
+    const uint32_t n_eval = filtered_walk<false>(
+        w.lbeg, w.r0, w.r1, lds, lane,
+        [&](uint64_t p, uint64_t, uint64_t clip, uint32_t &) { return group_images_window(da.valid_pos, da.bits, p, clip); },
+        [&](const QueueTile &t) { distinct_tile<CG, SEQ, ALIGNED, GW>(a, da.key_pos, w, t, lds, qv, lane, tk); });
     if (st && n_eval && lane == 0) atomicAdd(&st[3], (unsigned long long)n_eval);
-
-    const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
-    const uint32_t pi = (j * a.blocks_per_list + blockIdx.x) * 4 + wave;
-    const uint64_t base = ((uint64_t)q * n_part + pi) * a.k;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const uint32_t e = s * 64 + lane;
-        if (e < a.k) {
-            a.part_keys[base + e] = tk.key[s];
-            a.part_vals[base + e] = tk.val[s];
-            if constexpr (GW == 1) da.part_grp[base + e] = (int64_t)(int32_t)tk.grp[s][0];
-            else da.part_grp[base + e] = (int64_t)(((uint64_t)tk.grp[s][1] << 32) | (uint64_t)tk.grp[s][0]);
-        }
-    }
+    write_distinct_lists<S, GW>(a, da.part_grp, partial_base(a, q, j, wave, a.k), lane, tk);
 }
 
-#undef LDS_AT
-
-template <int CG, int S, bool SEQ, bool ALIGNED, int GW>
-static hipError_t launch_distinct_t(const StreamArgs &a, const DistinctArgs &da, hipStream_t s) {
-    dim3 grid(a.blocks_per_list, a.nprobe, a.nq);
-    hipLaunchKernelGGL((distinct_stream_kernel<CG, S, SEQ, ALIGNED, GW>), grid, dim3(256), 0, s, a, da);
-    return hipGetLastError();
-}
-
-// the chunk choice of launch_stream (the chain order does not depend on it)
 template <int S, int GW>
 static hipError_t launch_distinct_s(const StreamArgs &a, const DistinctArgs &da, hipStream_t s) {
-    const bool aligned = (a.dim % 4) == 0;
-    const uint32_t G = a.dim / 4;
-    if (a.metric == 1) {
-        return aligned ? launch_distinct_t<16, S, true, true, GW>(a, da, s) : launch_distinct_t<16, S, true, false, GW>(a, da, s);
-    }
-    if (!aligned) return launch_distinct_t<32, S, false, false, GW>(a, da, s);
-    if (G >= 64 && G % 64 == 0) return launch_distinct_t<64, S, false, true, GW>(a, da, s);
-    return launch_distinct_t<32, S, false, true, GW>(a, da, s);
+    return dispatch_chunk(a.dim, a.metric, [&](auto cg, auto seq, auto aligned) {
+        dim3 grid(a.blocks_per_list, a.nprobe, a.nq);
+        hipLaunchKernelGGL((distinct_stream_kernel<cg.value, S, seq.value, aligned.value, GW>), grid, dim3(256), 0, s, a, da);
+        return hipGetLastError();
+    });
 }
 
 template <int GW>

@@ -6,7 +6,8 @@
 // sum starts at +0.0f and x + y is -0.0f only when both are, so sum is never -0.0f and a zero dist is always +0.0f.
 // Distances are signed, so the keys are (ord(dist) << 32) | candidate position with ord the usual order-preserving map of f32 bits
 // to u32 (negative: all bits flipped; else: the sign bit set): ascending keys = ascending (dist, position).
-//   dot_stream_kernel   stream_kernel's grid, tile and chain structure (kernels_probe.hip) with that partial and that key;
+//   dot_stream_kernel   stream_kernel's grid, tile and chain structure (stream_walk.hpp: dot_tile is chain_tile's products form)
+//                       with that key;
 //                       WIN = 0 walks every position of the wave's range, WIN = 1 the set bits of a row mask's image exactly as
 //                       masked_stream_kernel does (kernels_mask.hip).  Also the centroid probe of a DOT call (the centroid matrix as
 //                       one list, or a table's per-file segments): merge_kernel<S, true> / merge_probe_seg_kernel use keys for
@@ -14,7 +15,7 @@
 //   dot_merge_kernel    the fold of the per-wave lists, one wave per query: rows, dist (ord undone), n_found; tie flags zeroed
 //   dot_finish_kernel   range search: the range_* sort kernels run as order-only machinery (sqrt_out 0) and write the keys' high
 //                       halves; this turns them back into dist in place
-#include "device_common.hpp"
+#include "stream_walk.hpp"
 
 namespace pqv {
 
@@ -27,70 +28,6 @@ __device__ __forceinline__ uint32_t dot_ord(float d) {
 __device__ __forceinline__ float dot_unord(uint32_t o) {
     return __uint_as_float((o >> 31) ? o ^ 0x80000000u : ~o);
 }
-
-#define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
-
-// The similarity chain of one 64-row tile: lane r returns s(q, row r) for r < nvalid (my_srow: storage row of tile row `lane`,
-// clamped so that every address is in range).  stream_kernel's chunk loop with products in place of squared differences.
-template <int CG, bool ALIGNED>
-__device__ __forceinline__ float dot_tile(const StreamArgs &a, float *lds, const float *qv, uint32_t my_srow, uint32_t nvalid, int lane) {
-    constexpr int RPI = 64 / CG;        // rows per load instruction
-    constexpr int NI = CG;              // load instructions per 64-row tile
-    constexpr int NB = 8;               // loads in flight per lane
-    static_assert(NI % NB == 0, "NI must be a multiple of NB");
-    const uint32_t dim = a.dim;
-    const uint32_t G = dim >> 2;
-    const uint32_t tail = dim & 3u;
-    const int g_in = lane % CG;      // my float4 group inside a chunk
-    const int row_in = lane / CG;    // my row inside a load instruction
-
-    float sum = 0.0f;
-    for (uint32_t c0 = 0; c0 < G; c0 += CG) {
-        const uint32_t ng = (G - c0 < (uint32_t)CG) ? (G - c0) : (uint32_t)CG;
-        const bool gvalid = (uint32_t)g_in < ng;
-        const uint32_t goff = (c0 + (gvalid ? g_in : 0)) * 4;
-        const float4 qq = load4<ALIGNED>(qv + goff);
-
-#pragma unroll 1
-        for (int ib = 0; ib < NI; ib += NB) {
-            float4 x[NB];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-                uint32_t rr = (uint32_t)((ib + u) * RPI + row_in);
-                if (rr >= nvalid) rr = nvalid - 1;
-                const uint32_t srow = (uint32_t)__shfl((int)my_srow, (int)rr, 64);
-                x[u] = load4<ALIGNED>(a.mat + (uint64_t)srow * dim + goff);
-            }
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-                const int rr = (ib + u) * RPI + row_in;
-                float t = qq.x * x[u].x + qq.y * x[u].y;
-                t = t + qq.z * x[u].z;
-                t = t + qq.w * x[u].w;
-                if (gvalid) LDS_AT(g_in, rr) = t;
-            }
-        }
-        wave_lds_fence();
-        uint32_t e = 0;
-        for (; e + 8 <= ng; e += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = LDS_AT(e + u, lane);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum = sum + v[u];
-        }
-        for (; e < ng; ++e) sum = sum + LDS_AT(e, lane);
-        wave_lds_fence();
-    }
-    if (tail) {
-        const float *xr = a.mat + (uint64_t)my_srow * dim + (uint64_t)G * 4;
-        const float *qt = qv + (uint64_t)G * 4;
-        for (uint32_t e = 0; e < tail; ++e) sum = sum + qt[e] * xr[e];
-    }
-    return sum;
-}
-
-#undef LDS_AT
 
 }  // namespace
 
@@ -109,36 +46,14 @@ __device__ __forceinline__ float dot_tile(const StreamArgs &a, float *lds, const
 template <int CG, int S, int MODE, bool ALIGNED, int WIN>
 __global__ __launch_bounds__(256) void dot_stream_kernel(const StreamArgs a, const MaskedArgs ma) {
     static_assert(MODE == STREAM_TOPK || MODE == STREAM_RANGE, "top-k lists or range hits");
-    static_assert(CG * 64 >= 128, "the compaction needs 128 words of the tile area");
-    __shared__ float lds_all[4 * CG * 64];
+    static_assert(tile_words<CG, false>() >= WindowQueue<false>::SCRATCH, "the compaction needs 128 words of the tile area");
+    __shared__ float lds_all[4 * tile_words<CG, false>()];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    float *lds = lds_all + wave * (CG * 64);
+    float *lds = lds_all + wave * tile_words<CG, false>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
-    uint64_t lbeg, lend, cbase, lim = a.max_pos;
-    if (WIN != 0 || a.probe) {
-        const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
-        lbeg = a.list_off[c];
-        lend = a.list_off[c + 1];
-        cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
-        if (a.pair_end) lim = a.pair_end[(uint64_t)q * a.nprobe + j];
-    } else {
-        lbeg = a.single_begin;
-        lend = a.single_end;
-        cbase = 0;
-    }
-    uint64_t len = lend - lbeg;
-    if constexpr (WIN != 0) {
-        // positions at or beyond the cap are no candidates: the walk ends there (their bits are never looked at)
-        const uint64_t room = lim > cbase ? lim - cbase : 0;
-        if (len > room) len = room;
-    }
-    const uint64_t wrows = a.rows_per_block / 4;
-    const uint64_t r0 = (uint64_t)blockIdx.x * a.rows_per_block + (uint64_t)wave * wrows;
-    uint64_t r1 = r0 + wrows;
-    if (r1 > len) r1 = len;
-
+    const WalkRange w = walk_range<WIN != 0>(a, q, j, wave);
     const float *qv = a.queries + (uint64_t)q * a.dim;
 
     WaveTopk<S> tk;
@@ -148,118 +63,43 @@ __global__ __launch_bounds__(256) void dot_stream_kernel(const StreamArgs a, con
     auto emit = [&](float sum, bool valid, uint64_t pos, uint32_t my_srow) {
         const float dist = 0.0f - sum;
         const uint64_t key = ((uint64_t)dot_ord(dist) << 32) | (uint64_t)(uint32_t)pos;
-        if constexpr (MODE == STREAM_TOPK) {
-            tk.offer(valid ? key : KEY_EMPTY, my_srow, a.k, lane);
-        } else {
-            // the wave's hits go to the query's segment in one block: ballot, rank from mbcnt, one atomicAdd per wave
-            const bool hit = valid && dist <= a.radius;                // (a NaN distance never compares true)
-            const uint64_t m = __ballot(hit);
-            if (m) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(a.hit_cnt + q, (uint32_t)__popcll(m));
-                base = (uint32_t)__shfl((int)base, 0, 64);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (hit) {
-                    const uint64_t o = (uint64_t)q * a.seg_stride + base + rank;
-                    a.hit_keys[o] = key;
-                    a.hit_vals[o] = my_srow;
-                }
-            }
-        }
+        if constexpr (MODE == STREAM_TOPK) tk.offer(valid ? key : KEY_EMPTY, my_srow, a.k, lane);
+        else emit_range_hit(a, q, valid && dist <= a.radius, key, my_srow, lane);     // (a NaN distance never compares true)
     };
 
     if constexpr (WIN == 0) {
-        for (uint64_t t0 = r0; t0 < r1; t0 += 64) {
-            const uint32_t nvalid = (r1 - t0 < 64) ? (uint32_t)(r1 - t0) : 64u;
+        for (uint64_t t0 = w.r0; t0 < w.r1; t0 += 64) {
+            const uint32_t nvalid = (w.r1 - t0 < 64) ? (uint32_t)(w.r1 - t0) : 64u;
             const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
-            const uint64_t lpos = lbeg + t0 + lrow;
-            const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
+            const uint32_t my_srow = storage_row(a, w.lbeg + t0 + lrow);
             const float sum = dot_tile<CG, ALIGNED>(a, lds, qv, my_srow, nvalid, lane);
-            const uint64_t pos = cbase + t0 + (uint64_t)lane;
-            emit(sum, (uint32_t)lane < nvalid && pos < lim, pos, my_srow);
+            const uint64_t pos = w.cbase + t0 + (uint64_t)lane;
+            emit(sum, (uint32_t)lane < nvalid && pos < w.lim, pos, my_srow);
         }
     } else {
-        uint32_t *cq = reinterpret_cast<uint32_t *>(lds);          // compaction scratch: 128 entries
-#ifdef PQV_PROFILE_PHASES
-        unsigned long long *st = ma.stats;
-#else
-        unsigned long long *st = ma.stats ? ma.stats + 8 + 16 * (q % STATS_SLOTS) : nullptr;
-#endif
-        if (ma.n_cand && st && blockIdx.x == 0 && j == 0 && threadIdx.x == 0) atomicAdd(&st[2], (unsigned long long)ma.n_cand[q]);
-
-        uint32_t pend = 0;      // queue entry `lane` (a list offset, < 2^32 as every candidate position), meaningful for lane < qn
-        uint32_t qn = 0;        // queued entries, < 64 between two windows (wave-uniform)
-        uint32_t n_eval = 0;    // rows this wave evaluated (wave-uniform)
-        for (uint64_t w0 = r0;; w0 += 64) {
-            const bool flush = w0 >= r1;        // past the range: what is left in the queue is the last tile
-            uint32_t nvalid = 0;                // rows of the chain tile this turn runs (0: none)
-            uint32_t my_r = 0;                  // list offset of tile row `lane`
-            if (!flush) {
-                uint64_t win = image_window(ma.bits, lbeg + w0);
-                if (r1 - w0 < 64) win &= (1ull << (r1 - w0)) - 1ull;
-                const uint32_t cnt = (uint32_t)__popcll(win);
-                if (cnt == 0) continue;
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(win >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)win, 0u));
-                if ((uint32_t)lane < qn) cq[lane] = pend;
-                if ((win >> lane) & 1ull) cq[qn + rank] = (uint32_t)(w0 + (uint64_t)lane);
-                wave_lds_fence();
-                const uint32_t total = qn + cnt;                   // <= 127
-                const uint32_t first = cq[lane];
-                const uint32_t over = cq[64 + lane];
-                wave_lds_fence();
-                if (total >= 64) {
-                    my_r = first; nvalid = 64u;
-                    pend = over; qn = total - 64;
-                } else {
-                    pend = first; qn = total;
-                }
-            } else if (qn) {
-                const uint32_t last = (uint32_t)__shfl((int)pend, (int)(qn - 1), 64);
-                my_r = (uint32_t)lane < qn ? pend : last;         // (clamped: every address in range)
-                nvalid = qn; qn = 0;
-            }
-            if (nvalid) {
-                n_eval += nvalid;
-                const uint64_t lpos = lbeg + my_r;
-                const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
-                const float sum = dot_tile<CG, ALIGNED>(a, lds, qv, my_srow, nvalid, lane);
-                emit(sum, (uint32_t)lane < nvalid, cbase + my_r, my_srow);           // (pos < lim by the clamp of the walk)
-            }
-            if (flush) break;
-        }
+        unsigned long long *st = stats_slot(ma.stats, q);
+        stats_add_candidates(st, ma.n_cand, q, j);
+        const uint32_t n_eval = filtered_walk<false>(
+            w.lbeg, w.r0, w.r1, lds, lane, [&](uint64_t p, uint64_t, uint64_t, uint32_t &) { return image_window(ma.bits, p); },
+            [&](const QueueTile &t) {
+                const uint32_t my_srow = storage_row(a, w.lbeg + t.my_r);
+                const float sum = dot_tile<CG, ALIGNED>(a, lds, qv, my_srow, t.nvalid, lane);
+                emit(sum, (uint32_t)lane < t.nvalid, w.cbase + t.my_r, my_srow);           // (pos < lim by the clamp of the walk)
+            });
         if (st && n_eval && lane == 0) atomicAdd(&st[3], (unsigned long long)n_eval);
     }
 
-    if constexpr (MODE == STREAM_TOPK) {
-        const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
-        const uint32_t pi = (j * a.blocks_per_list + blockIdx.x) * 4 + wave;
-        const uint64_t base = ((uint64_t)q * n_part + pi) * a.k;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const uint32_t e = s * 64 + lane;
-            if (e < a.k) {
-                a.part_keys[base + e] = tk.key[s];
-                a.part_vals[base + e] = tk.val[s];
-            }
-        }
-    }
+    if constexpr (MODE == STREAM_TOPK) write_partial_lists<S>(a.part_keys, a.part_vals, partial_base(a, q, j, wave, a.k), a.k, lane, tk.key, tk.val);
 }
 
-template <int CG, int S, int MODE, bool ALIGNED, int WIN>
-static hipError_t launch_dot_t(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
-    dim3 grid(a.blocks_per_list, !a.probe ? 1u : MODE == STREAM_RANGE ? a.nj : a.nprobe, a.nq);
-    hipLaunchKernelGGL((dot_stream_kernel<CG, S, MODE, ALIGNED, WIN>), grid, dim3(256), 0, s, a, ma);
-    return hipGetLastError();
-}
-
-// the chunk choice of launch_stream (the chain order does not depend on it)
+// (no SEQ chain: PQV_DOT has the 4-grouped form only)
 template <int S, int MODE, int WIN>
 static hipError_t launch_dot_s(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
-    const bool aligned = (a.dim % 4) == 0;
-    const uint32_t G = a.dim / 4;
-    if (!aligned) return launch_dot_t<32, S, MODE, false, WIN>(a, ma, s);
-    if (G >= 64 && G % 64 == 0) return launch_dot_t<64, S, MODE, true, WIN>(a, ma, s);
-    return launch_dot_t<32, S, MODE, true, WIN>(a, ma, s);
+    return dispatch_chunk<false>(a.dim, a.metric, [&](auto cg, auto, auto aligned) {
+        dim3 grid(a.blocks_per_list, !a.probe ? 1u : MODE == STREAM_RANGE ? a.nj : a.nprobe, a.nq);
+        hipLaunchKernelGGL((dot_stream_kernel<cg.value, S, MODE, aligned.value, WIN>), grid, dim3(256), 0, s, a, ma);
+        return hipGetLastError();
+    });
 }
 
 template <int WIN>

@@ -2,7 +2,7 @@
 // positions of each probed list pass the call's filter -- no embedding is read) and expand_select_kernel (per query: the prefix
 // sums of those counts in probe order, the first rank at which k rows have passed, the candidate total of the lists up to it).
 // masked_stream_kernel (kernels_mask.hip) then walks each query's lists below its own rank limit.
-#include "device_common.hpp"
+#include "stream_walk.hpp"
 
 namespace pqv {
 
@@ -10,9 +10,9 @@ namespace pqv {
 // filter_count_kernel<WIN>: grid (probe rank j < P, query), one 256-thread block per probed list; cnt[q * P + j] = the set bits of
 // the list's windows, ONE plain store per block, no atomics.
 //
-// A window's 64 bits are masked_stream_kernel's for the same WIN, restated here (the stream kernel's instantiations stay as they
-// are): positions lbeg + w0 .. + 63 of the list, w0 a multiple of 64 -- the stream's waves start their ranges at multiples of 64
-// inside the list and clip at min(range end, list end), so the union of their windows is exactly these, clipped at the list's end.
+// A window's 64 bits are masked_stream_kernel's for the same WIN, from the same KeyTest (stream_walk.hpp): positions
+// lbeg + w0 .. + 63 of the list, w0 a multiple of 64 -- the stream's waves start their ranges at multiples of 64 inside the
+// list and clip at min(range end, list end), so the union of their windows is exactly these, clipped at the list's end.
 // WIN 0: the mask's image through image_window.  WIN 1 .. 6: lane l loads key_pos[lbeg + w0 + l], compares in i64 (equality /
 // inclusive range / a halving search in the query's set, copied into LDS first) and the __ballot is the window, ANDed with the
 // windows of valid_pos and of the shared mask where the call has them.  No candidate cap: an expanding call takes none.
@@ -40,45 +40,18 @@ __global__ __launch_bounds__(256) void filter_count_kernel(const ExpandCountArgs
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, 64);
     } else {
-        int64_t qkey = 0, qhi = 0;
-        if constexpr (WIN == 1 || WIN == 2) qkey = static_cast<const int64_t *>(a.a)[q];
-        if constexpr (WIN == 3 || WIN == 4) {
-            qkey = static_cast<const int64_t *>(a.a)[q];
-            qhi = static_cast<const int64_t *>(a.b)[q];
-        }
-        const int64_t *kset = nullptr;
-        uint32_t kset_n = 0;
+        KeyTest<(WIN - 1) / 2> kt;          // WIN 1 / 2: EQ, 3 / 4: RANGE, 5 / 6: IN
+        if constexpr (WIN <= 4) kt.lo = static_cast<const int64_t *>(a.a)[q];
+        if constexpr (WIN == 3 || WIN == 4) kt.hi = static_cast<const int64_t *>(a.b)[q];
         uint64_t end = len;
         if constexpr (WIN >= 5) {
             __shared__ int64_t set_lds[KEY_SET_MAX];
-            const uint64_t s0 = static_cast<const uint64_t *>(a.a)[q], s1 = static_cast<const uint64_t *>(a.a)[q + 1];
-            if (s1 > s0) kset_n = s1 - s0 > (uint64_t)KEY_SET_MAX ? KEY_SET_MAX : (uint32_t)(s1 - s0);
-            for (uint32_t i = threadIdx.x; i < kset_n; i += 256) set_lds[i] = static_cast<const int64_t *>(a.b)[s0 + i];
-            __syncthreads();
-            kset = set_lds;
-            if (kset_n == 0) end = 0;      // (nothing matches: no window is read)
+            kt.setup_in(a.a, a.b, q, set_lds);
+            if (kt.empty()) end = 0;       // (nothing matches: no window is read)
         }
         for (uint64_t w0 = (uint64_t)wave * 64; w0 < end; w0 += 256) {
             const uint64_t p = lbeg + w0;
-            // (key_pos is padded by a whole window: p + lane is always in range; positions >= len are clipped below)
-            int64_t kv;
-            if constexpr (WIN & 1) kv = (int64_t) static_cast<const int32_t *>(a.key_pos)[p + (uint64_t)lane];
-            else kv = static_cast<const int64_t *>(a.key_pos)[p + (uint64_t)lane];
-            uint64_t win;
-            if constexpr (WIN <= 2) {
-                win = __ballot(kv == qkey);
-            } else if constexpr (WIN <= 4) {
-                win = __ballot(qkey <= kv && kv <= qhi);
-            } else {
-                uint32_t at = 0;
-                for (uint32_t span = kset_n; span > 1;) {           // (wave-uniform trip count; at + half < kset_n)
-                    const uint32_t half = span >> 1;
-                    if (kset[at + half] <= kv) at += half;
-                    span -= half;
-                }
-                win = __ballot(kset[at] == kv);                     // (kset_n >= 1 here)
-            }
-            if (a.valid_pos) win &= image_window(a.valid_pos, p);
+            uint64_t win = kt.window(a.key_pos, (WIN & 1) != 0, a.valid_pos, p, lane);      // (positions >= len are clipped below)
             if (a.bits) win &= image_window(a.bits, p);
             if (len - w0 < 64) win &= (1ull << (len - w0)) - 1ull;
             sum += (uint32_t)__popcll(win);

@@ -3,7 +3,7 @@
 // positions only) -- and of the per-query key filters (pqv.h: pqv_row_keys): key_layout_kernel (a key column in row order -> list
 // position order) and masked_stream_kernel's keyed instantiations, whose windows come from comparing keys.  The screened paths take their thresholds from sampled rows; a threshold from a row the mask excludes is no
 // bound on the masked answer, so masked calls always run this exact pass.
-#include "device_common.hpp"
+#include "stream_walk.hpp"
 
 namespace pqv {
 
@@ -85,8 +85,9 @@ hipError_t launch_key_layout(const void *values, const uint8_t *valid, uint32_t 
 // ------------------------------------------------------------------------------------
 // masked_stream_kernel
 //
-// stream_kernel's grid (row block, probe rank, query), its 4 independent waves per block and its chain arithmetic, element for
-// element (REF4 groups / SEQ squares, dim % 4 tails, unaligned rows; the unit is built with -ffp-contract=off like the others).
+// stream_kernel's grid (row block, probe rank, query), its 4 independent waves per block and its chain tile (l2_tile: REF4 groups
+// / SEQ squares, dim % 4 tails, unaligned rows).  The walk, the queue, the key test and the outputs are stream_walk.hpp's pieces,
+// which every other filtered form composes too; what follows describes them as this kernel uses them.
 // What differs is WHICH rows fill a 64-row tile: a wave walks its position range [r0, r1) of the list in 64-position windows,
 // reads the window's mask word (lbeg + r0 is not 64-aligned: two words, funnel-shifted), drops the bits at or beyond the
 // candidate cap (max_pos / pair_end) and compacts the set positions into a queue, rank from mbcnt.  A chain tile runs whenever 64
@@ -124,28 +125,18 @@ template <> struct WinArgs<2> { using type = KeyedArgs; };
 
 template <int CG, int S, int MODE, bool SEQ, bool ALIGNED, int WIN = 0>
 __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, const typename WinArgs<WIN>::type ma) {
-    constexpr int RPI = 64 / CG;        // rows per load instruction
-    constexpr int NI = CG;              // load instructions per 64-row tile
-    constexpr int EPL = SEQ ? 4 : 1;    // LDS values per lane item
-    constexpr int LROWS = CG * EPL;     // chain length per chunk
-    constexpr int NB = 8;               // loads in flight per lane
-    static_assert(NI % NB == 0, "NI must be a multiple of NB");
-    static_assert(LROWS * 64 >= 128, "the compaction needs 128 words of the tile area");
-
-    __shared__ float lds_all[4 * LROWS * 64];
+    static_assert(tile_words<CG, SEQ>() >= WindowQueue<false>::SCRATCH, "the compaction needs 128 words of the tile area");
+    __shared__ float lds_all[4 * tile_words<CG, SEQ>()];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    float *lds = lds_all + wave * (LROWS * 64);
-    uint32_t *cq = reinterpret_cast<uint32_t *>(lds);          // compaction scratch: 128 entries
-#define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
+    float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
     if constexpr (MODE == STREAM_TOPK) {
         // a rank at or beyond the query's limit (pqv_topk_expand) walks nothing: that one word is all the block loads, its four
         // waves' lists go out EMPTY for the final merge (block-uniform: nobody is left waiting at the IN forms' barrier)
         if (ma.rank_limit && j >= ma.rank_limit[q]) {
-            const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
-            const uint64_t base = ((uint64_t)q * n_part + (j * a.blocks_per_list + blockIdx.x) * 4 + wave) * a.k;
+            const uint64_t base = partial_base(a, q, j, wave, a.k);
             for (uint32_t e = lane; e < a.k; e += 64) {
                 a.part_keys[base + e] = KEY_EMPTY;
                 a.part_vals[base + e] = 0xFFFFFFFFu;
@@ -153,239 +144,57 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
             return;
         }
     }
-    const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
-    const uint64_t lbeg = a.list_off[c], lend = a.list_off[c + 1];
-    const uint64_t cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
-    const uint64_t lim = a.pair_end ? a.pair_end[(uint64_t)q * a.nprobe + j] : a.max_pos;
-    uint64_t len = lend - lbeg;
-    // positions at or beyond the cap are no candidates: the walk ends there (their bits are never looked at)
-    const uint64_t room = lim > cbase ? lim - cbase : 0;
-    if (len > room) len = room;
-    const uint64_t wrows = a.rows_per_block / 4;
-    const uint64_t r0 = (uint64_t)blockIdx.x * a.rows_per_block + (uint64_t)wave * wrows;
-    uint64_t r1 = r0 + wrows;
-    if (r1 > len) r1 = len;
+    WalkRange w = walk_range<true>(a, q, j, wave);
+    unsigned long long *st = stats_slot(ma.stats, q);
+    stats_add_candidates(st, ma.n_cand, q, j);
 
-#ifdef PQV_PROFILE_PHASES
-    unsigned long long *st = ma.stats;
-#else
-    unsigned long long *st = ma.stats ? ma.stats + 8 + 16 * (q % STATS_SLOTS) : nullptr;
-#endif
-    if (ma.n_cand && st && blockIdx.x == 0 && j == 0 && threadIdx.x == 0) atomicAdd(&st[2], (unsigned long long)ma.n_cand[q]);
-
-    int64_t qkey = 0;
-    if constexpr (WIN == 1 || WIN == 2) qkey = ma.qkeys[q];
-    int64_t qhi = 0;            // WIN 3 / 4: the window is qkey <= kv && kv <= qhi
+    KeyTest<WIN == 0 ? 0 : (WIN - 1) / 2> kt;       // WIN 1 / 2: EQ, 3 / 4: RANGE, 5 / 6: IN
+    if constexpr (WIN == 1 || WIN == 2) kt.lo = ma.qkeys[q];
     if constexpr (WIN == 3 || WIN == 4) {
-        qkey = static_cast<const int64_t *>(ma.a)[q];
-        qhi = static_cast<const int64_t *>(ma.b)[q];
+        kt.lo = static_cast<const int64_t *>(ma.a)[q];
+        kt.hi = static_cast<const int64_t *>(ma.b)[q];
     }
-    const int64_t *kset = nullptr;
-    uint32_t kset_n = 0;        // WIN 5 / 6: the values of the query's set held in kset (block-uniform)
     if constexpr (WIN >= 5) {
         __shared__ int64_t set_lds[KEY_SET_MAX];
-        const uint64_t s0 = static_cast<const uint64_t *>(ma.a)[q], s1 = static_cast<const uint64_t *>(ma.a)[q + 1];
-        if (s1 > s0) kset_n = s1 - s0 > (uint64_t)KEY_SET_MAX ? KEY_SET_MAX : (uint32_t)(s1 - s0);
-        for (uint32_t i = threadIdx.x; i < kset_n; i += 256) set_lds[i] = static_cast<const int64_t *>(ma.b)[s0 + i];
-        __syncthreads();
-        kset = set_lds;
-        if (kset_n == 0) r1 = r0;      // (nothing matches: no window is read)
+        kt.setup_in(ma.a, ma.b, q, set_lds);
+        if (kt.empty()) w.r1 = w.r0;      // (nothing matches: no window is read)
     }
 
-    const uint32_t dim = a.dim;
-    const uint32_t G = dim >> 2;
-    const uint32_t tail = dim & 3u;
-    const float *qv = a.queries + (uint64_t)q * dim;
-    const int g_in = lane % CG;      // my float4 group inside a chunk
-    const int row_in = lane / CG;    // my row inside a load instruction
-
+    const float *qv = a.queries + (uint64_t)q * a.dim;
     WaveTopk<S> tk;
     if constexpr (MODE == STREAM_TOPK) tk.init();
 
-    uint32_t pend = 0;      // queue entry `lane` (a list offset, < 2^32 as every candidate position), meaningful for lane < qn
-    uint32_t qn = 0;        // queued entries, < 64 between two windows (wave-uniform)
-    uint32_t n_eval = 0;    // rows this wave evaluated (wave-uniform)
-    for (uint64_t w0 = r0;; w0 += 64) {
-        const bool flush = w0 >= r1;        // past the range: what is left in the queue is the last tile
-        uint32_t nvalid = 0;                // rows of the chain tile this turn runs (0: none)
-        uint32_t my_r = 0;                  // list offset of tile row `lane`
-        if (!flush) {
-            const uint64_t p = lbeg + w0;
-            uint64_t win;
+    const uint32_t n_eval = filtered_walk<false>(
+        w.lbeg, w.r0, w.r1, lds, lane,
+        [&](uint64_t p, uint64_t, uint64_t, uint32_t &) {
             if constexpr (WIN == 0) {
-                win = image_window(ma.bits, p);
+                return image_window(ma.bits, p);
             } else {
-                // (key_pos is padded by a whole window: p + lane is always in range; positions >= r1 are clipped below)
-                int64_t kv;
-                if constexpr (WIN & 1) kv = (int64_t) static_cast<const int32_t *>(ma.key_pos)[p + (uint64_t)lane];
-                else kv = static_cast<const int64_t *>(ma.key_pos)[p + (uint64_t)lane];
-                if constexpr (WIN <= 2) {
-                    win = __ballot(kv == qkey);
-                } else if constexpr (WIN <= 4) {
-                    win = __ballot(qkey <= kv && kv <= qhi);
-                } else {
-                    uint32_t at = 0;
-                    for (uint32_t span = kset_n; span > 1;) {           // (wave-uniform trip count; at + half < kset_n)
-                        const uint32_t half = span >> 1;
-                        if (kset[at + half] <= kv) at += half;
-                        span -= half;
-                    }
-                    win = __ballot(kset[at] == kv);                     // (kset_n >= 1 here)
-                }
-                if (ma.valid_pos) win &= image_window(ma.valid_pos, p);
+                uint64_t win = kt.window(ma.key_pos, (WIN & 1) != 0, ma.valid_pos, p, lane);
                 if (ma.bits) win &= image_window(ma.bits, p);
+                return win;
             }
-            if (r1 - w0 < 64) win &= (1ull << (r1 - w0)) - 1ull;
-            const uint32_t cnt = (uint32_t)__popcll(win);
-            if (cnt == 0) continue;
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(win >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)win, 0u));
-            if ((uint32_t)lane < qn) cq[lane] = pend;
-            if ((win >> lane) & 1ull) cq[qn + rank] = (uint32_t)(w0 + (uint64_t)lane);
-            wave_lds_fence();
-            const uint32_t total = qn + cnt;                   // <= 127
-            const uint32_t first = cq[lane];
-            const uint32_t over = cq[64 + lane];
-            wave_lds_fence();
-            if (total >= 64) {
-                my_r = first; nvalid = 64u;
-                pend = over; qn = total - 64;
-            } else {
-                pend = first; qn = total;
-            }
-        } else if (qn) {
-            const uint32_t last = (uint32_t)__shfl((int)pend, (int)(qn - 1), 64);
-            my_r = (uint32_t)lane < qn ? pend : last;         // (clamped: every address in range)
-            nvalid = qn; qn = 0;
-        }
-        if (nvalid) {
-            n_eval += nvalid;
-            const uint64_t lpos = lbeg + my_r;
-            const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
-
-            float sum = 0.0f;
-            for (uint32_t c0 = 0; c0 < G; c0 += CG) {
-                const uint32_t ng = (G - c0 < (uint32_t)CG) ? (G - c0) : (uint32_t)CG;
-                const bool gvalid = (uint32_t)g_in < ng;
-                const uint32_t goff = (c0 + (gvalid ? g_in : 0)) * 4;
-                const float4 qq = load4<ALIGNED>(qv + goff);
-
-#pragma unroll 1
-                for (int ib = 0; ib < NI; ib += NB) {
-                    float4 x[NB];
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) {
-                        uint32_t rr = (uint32_t)((ib + u) * RPI + row_in);
-                        if (rr >= nvalid) rr = nvalid - 1;
-                        const uint32_t srow = (uint32_t)__shfl((int)my_srow, (int)rr, 64);
-                        x[u] = load4<ALIGNED>(a.mat + (uint64_t)srow * dim + goff);
-                    }
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) {
-                        const int rr = (ib + u) * RPI + row_in;
-                        const float d0 = qq.x - x[u].x, d1 = qq.y - x[u].y;
-                        const float d2 = qq.z - x[u].z, d3 = qq.w - x[u].w;
-                        if constexpr (SEQ) {
-                            if (gvalid) {
-                                LDS_AT(g_in * 4 + 0, rr) = d0 * d0;
-                                LDS_AT(g_in * 4 + 1, rr) = d1 * d1;
-                                LDS_AT(g_in * 4 + 2, rr) = d2 * d2;
-                                LDS_AT(g_in * 4 + 3, rr) = d3 * d3;
-                            }
-                        } else {
-                            float t = d0 * d0 + d1 * d1;
-                            t = t + d2 * d2;
-                            t = t + d3 * d3;
-                            if (gvalid) LDS_AT(g_in, rr) = t;
-                        }
-                    }
-                }
-                wave_lds_fence();
-                const uint32_t nchain = ng * EPL;
-                uint32_t e = 0;
-                for (; e + 8 <= nchain; e += 8) {
-                    float v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = LDS_AT(e + u, lane);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) sum = sum + v[u];
-                }
-                for (; e < nchain; ++e) sum = sum + LDS_AT(e, lane);
-                wave_lds_fence();
-            }
-            if (tail) {  // scalar tail of squared_l2_distance (index.rs:474-478)
-                const float *xr = a.mat + (uint64_t)my_srow * dim + (uint64_t)G * 4;
-                const float *qt = qv + (uint64_t)G * 4;
-                for (uint32_t e = 0; e < tail; ++e) {
-                    const float d = qt[e] - xr[e];
-                    sum = sum + d * d;
-                }
-            }
-
-            const uint64_t pos = cbase + my_r;
-            const bool valid = (uint32_t)lane < nvalid;           // (pos < lim by the clamp of the walk)
-            if constexpr (MODE == STREAM_TOPK) {
-                const uint64_t mykey =
-                    valid ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos)
-                          : KEY_EMPTY;
-                tk.offer(mykey, my_srow, a.k, lane);
-            } else {
-                // the wave's hits go to the query's segment in one block: ballot, rank from mbcnt, one atomicAdd per wave
-                const float outv = a.sqrt_out == 1 ? sqrt_f32_ieee(sum) : a.sqrt_out == 2 ? 0.5f * sum : sum;     // (2: PQV_COSINE)
-                const bool hit = valid && outv <= a.radius;                // (a NaN distance never compares true)
-                const uint64_t m = __ballot(hit);
-                if (m) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(a.hit_cnt + q, (uint32_t)__popcll(m));
-                    base = (uint32_t)__shfl((int)base, 0, 64);
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (hit) {
-                        const uint64_t o = (uint64_t)q * a.seg_stride + base + rank;
-                        a.hit_keys[o] = ((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos;
-                        a.hit_vals[o] = my_srow;
-                    }
-                }
-            }
-        }
-        if (flush) break;
-    }
+        },
+        [&](const QueueTile &t) {
+            const uint32_t my_srow = storage_row(a, w.lbeg + t.my_r);
+            const float sum = l2_tile<CG, SEQ, ALIGNED>(a, lds, qv, my_srow, t.nvalid, lane);
+            const uint64_t pos = w.cbase + t.my_r;
+            const bool valid = (uint32_t)lane < t.nvalid;           // (pos < lim by the clamp of the walk)
+            if constexpr (MODE == STREAM_TOPK) tk.offer(valid ? l2_key(sum, pos) : KEY_EMPTY, my_srow, a.k, lane);
+            else emit_l2_range_hit(a, q, valid, sum, pos, my_srow, lane);
+        });
     if (st && n_eval && lane == 0) atomicAdd(&st[3], (unsigned long long)n_eval);
 
-    if constexpr (MODE == STREAM_TOPK) {
-        const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
-        const uint32_t pi = (j * a.blocks_per_list + blockIdx.x) * 4 + wave;
-        const uint64_t base = ((uint64_t)q * n_part + pi) * a.k;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const uint32_t e = s * 64 + lane;
-            if (e < a.k) {
-                a.part_keys[base + e] = tk.key[s];
-                a.part_vals[base + e] = tk.val[s];
-            }
-        }
-    }
+    if constexpr (MODE == STREAM_TOPK) write_partial_lists<S>(a.part_keys, a.part_vals, partial_base(a, q, j, wave, a.k), a.k, lane, tk.key, tk.val);
 }
 
-#undef LDS_AT
-
-template <int CG, int S, int MODE, bool SEQ, bool ALIGNED, int WIN>
-static hipError_t launch_masked_t(const StreamArgs &a, const typename WinArgs<WIN>::type &ma, hipStream_t s) {
-    dim3 grid(a.blocks_per_list, MODE == STREAM_RANGE ? a.nj : a.nprobe, a.nq);
-    hipLaunchKernelGGL((masked_stream_kernel<CG, S, MODE, SEQ, ALIGNED, WIN>), grid, dim3(256), 0, s, a, ma);
-    return hipGetLastError();
-}
-
-// the chunk choice of launch_stream (the chain order does not depend on it)
 template <int S, int MODE, int WIN>
 static hipError_t launch_masked_s(const StreamArgs &a, const typename WinArgs<WIN>::type &ma, hipStream_t s) {
-    const bool aligned = (a.dim % 4) == 0;
-    const uint32_t G = a.dim / 4;
-    if (a.metric == 1) {
-        return aligned ? launch_masked_t<16, S, MODE, true, true, WIN>(a, ma, s)
-                       : launch_masked_t<16, S, MODE, true, false, WIN>(a, ma, s);
-    }
-    if (!aligned) return launch_masked_t<32, S, MODE, false, false, WIN>(a, ma, s);
-    if (G >= 64 && G % 64 == 0) return launch_masked_t<64, S, MODE, false, true, WIN>(a, ma, s);
-    return launch_masked_t<32, S, MODE, false, true, WIN>(a, ma, s);
+    return dispatch_chunk(a.dim, a.metric, [&](auto cg, auto seq, auto aligned) {
+        dim3 grid(a.blocks_per_list, MODE == STREAM_RANGE ? a.nj : a.nprobe, a.nq);
+        hipLaunchKernelGGL((masked_stream_kernel<cg.value, S, MODE, seq.value, aligned.value, WIN>), grid, dim3(256), 0, s, a, ma);
+        return hipGetLastError();
+    });
 }
 
 template <int WIN>

@@ -2,7 +2,7 @@
 // re-rank src/ivf/search.rs:112-127, centroid probe index.rs:130-149, k-means++ rounds index.rs:344-369), probe_rows_kernel /
 // probe_single_kernel (find_closest_centroids for a batch / one query), quantize_pairs_i8_kernel, merge_kernel (heap semantics of
 // search.rs:119-126 == k smallest by (d2, candidate position)) and the pair bucketing (pair_scan / pair_scatter).
-#include "device_common.hpp"
+#include "stream_walk.hpp"
 
 namespace pqv {
 
@@ -10,15 +10,10 @@ namespace pqv {
 // stream_kernel
 //
 // grid = (blocks_per_list, nprobe | 1, nq); block = 256 threads = 4 independent waves.
-// A wave owns a contiguous run of rows of one inverted list and walks it in 64-row tiles.
-// For a tile and a chunk of CG float4 groups of the dimension:
-//   1. every load instruction reads 64 x 16 B, fully coalesced (CG = 64: one 1 KiB row
-//      segment; CG = 32: two 512 B segments), NB instructions in flight;
-//   2. each lane turns its float4 into the reference's per-group partial
-//      t = ((d0^2 + d1^2) + d2^2) + d3^2  (PQV_L2SQ_REF4) or four squares (PQV_L2SQ_SEQ)
-//      and parks it in a [group][row] LDS tile (XOR-swizzled: conflict-free both ways);
-//   3. lane r then replays row r's serial chain  sum += t_g  in ascending g -- the one
-//      part of the reference arithmetic that cannot be re-associated.
+// A wave owns a contiguous run of rows of one inverted list (walk_range, stream_walk.hpp) and
+// walks it in 64-row tiles; a tile's distances are l2_tile's (stream_walk.hpp: coalesced 16 B
+// loads, the reference's per-group partials parked in a swizzled LDS tile, row r's serial chain
+// replayed by lane r), shared with every filtered form of this pass.
 // LDS traffic is 1/4 of the streamed bytes (REF4), VALU ~12 ops per 16 B: the kernel is
 // bound by the HBM/L2 stream.
 // ------------------------------------------------------------------------------------
@@ -27,124 +22,29 @@ __global__ __launch_bounds__(256) void stream_kernel(const StreamArgs a) {
     if (a.zero_u32 && blockIdx.x == 0 && blockIdx.y == 0) {     // scratch the NEXT kernels expect zeroed
         for (uint32_t i = blockIdx.z * 256 + threadIdx.x; i < a.zero_n; i += gridDim.z * 256) a.zero_u32[i] = 0u;
     }
-    constexpr int RPI = 64 / CG;        // rows per load instruction
-    constexpr int NI = CG;              // load instructions per 64-row tile
-    constexpr int EPL = SEQ ? 4 : 1;    // LDS values per lane item
-    constexpr int LROWS = CG * EPL;     // chain length per chunk
-    constexpr int NB = 8;               // loads in flight per lane
-    static_assert(NI % NB == 0, "NI must be a multiple of NB");
-
-    // [chain element e][row r] tile per wave, XOR-swizzled (column r ^ (e & 63)) so that
-    // both the group-major writes and the row-major chain reads are bank-conflict-free
-    // without padding: CG = 64 uses exactly 64 KiB per block.
-    __shared__ float lds_all[4 * LROWS * 64];
+    __shared__ float lds_all[4 * tile_words<CG, SEQ>()];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    float *lds = lds_all + wave * (LROWS * 64);
-#define LDS_AT(e, r) lds[(e) * 64 + ((r) ^ ((e) & 63))]
+    float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y + (MODE == STREAM_RANGE ? a.j0 : 0u);
-    uint64_t lbeg, lend, cbase, lim = a.max_pos;
-    if (a.probe) {
-        const uint32_t c = a.probe[(uint64_t)q * a.nprobe + j];
-        lbeg = a.list_off[c];
-        lend = a.list_off[c + 1];
-        cbase = a.cand_base[(uint64_t)q * a.nprobe + j];
-        if (a.pair_end) lim = a.pair_end[(uint64_t)q * a.nprobe + j];
-    } else {
-        lbeg = a.single_begin;
-        lend = a.single_end;
-        cbase = 0;
-    }
-    const uint64_t len = lend - lbeg;
-    const uint64_t wrows = a.rows_per_block / 4;
-    const uint64_t r0 = (uint64_t)blockIdx.x * a.rows_per_block + (uint64_t)wave * wrows;
-    uint64_t r1 = r0 + wrows;
-    if (r1 > len) r1 = len;
-
-    const uint32_t dim = a.dim;
-    const uint32_t G = dim >> 2;
-    const uint32_t tail = dim & 3u;
-    const float *qv = a.queries + (uint64_t)q * dim;
-    const int g_in = lane % CG;      // my float4 group inside a chunk
-    const int row_in = lane / CG;    // my row inside a load instruction
+    const WalkRange w = walk_range<false>(a, q, j, wave);
+    const float *qv = a.queries + (uint64_t)q * a.dim;
 
     WaveTopk<S> tk;
     if constexpr (MODE == STREAM_TOPK) tk.init();
 
-    for (uint64_t t0 = r0; t0 < r1; t0 += 64) {
-        const uint32_t nvalid = (r1 - t0 < 64) ? (uint32_t)(r1 - t0) : 64u;
+    for (uint64_t t0 = w.r0; t0 < w.r1; t0 += 64) {
+        const uint32_t nvalid = (w.r1 - t0 < 64) ? (uint32_t)(w.r1 - t0) : 64u;
         // storage row of tile row `lane` (clamped so every address is in range)
         const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
-        const uint64_t lpos = lbeg + t0 + lrow;
-        const uint32_t my_srow = a.row_of ? a.row_of[lpos] : (uint32_t)lpos;
+        const uint32_t my_srow = storage_row(a, w.lbeg + t0 + lrow);
+        const float sum = l2_tile<CG, SEQ, ALIGNED>(a, lds, qv, my_srow, nvalid, lane);
 
-        float sum = 0.0f;
-        for (uint32_t c0 = 0; c0 < G; c0 += CG) {
-            const uint32_t ng = (G - c0 < (uint32_t)CG) ? (G - c0) : (uint32_t)CG;
-            const bool gvalid = (uint32_t)g_in < ng;
-            const uint32_t goff = (c0 + (gvalid ? g_in : 0)) * 4;
-            const float4 qq = load4<ALIGNED>(qv + goff);
-
-#pragma unroll 1
-            for (int ib = 0; ib < NI; ib += NB) {
-                float4 x[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    uint32_t rr = (uint32_t)((ib + u) * RPI + row_in);
-                    if (rr >= nvalid) rr = nvalid - 1;
-                    const uint32_t srow = (uint32_t)__shfl((int)my_srow, (int)rr, 64);
-                    x[u] = load4<ALIGNED>(a.mat + (uint64_t)srow * dim + goff);
-                }
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    const int rr = (ib + u) * RPI + row_in;
-                    const float d0 = qq.x - x[u].x, d1 = qq.y - x[u].y;
-                    const float d2 = qq.z - x[u].z, d3 = qq.w - x[u].w;
-                    if constexpr (SEQ) {
-                        if (gvalid) {
-                            LDS_AT(g_in * 4 + 0, rr) = d0 * d0;
-                            LDS_AT(g_in * 4 + 1, rr) = d1 * d1;
-                            LDS_AT(g_in * 4 + 2, rr) = d2 * d2;
-                            LDS_AT(g_in * 4 + 3, rr) = d3 * d3;
-                        }
-                    } else {
-                        float t = d0 * d0 + d1 * d1;
-                        t = t + d2 * d2;
-                        t = t + d3 * d3;
-                        if (gvalid) LDS_AT(g_in, rr) = t;
-                    }
-                }
-            }
-            wave_lds_fence();
-            const uint32_t nchain = ng * EPL;
-            uint32_t e = 0;
-            for (; e + 8 <= nchain; e += 8) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = LDS_AT(e + u, lane);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) sum = sum + v[u];
-            }
-            for (; e < nchain; ++e) sum = sum + LDS_AT(e, lane);
-            wave_lds_fence();
-        }
-        if (tail) {  // scalar tail of squared_l2_distance (index.rs:474-478)
-            const float *xr = a.mat + (uint64_t)my_srow * dim + (uint64_t)G * 4;
-            const float *qt = qv + (uint64_t)G * 4;
-            for (uint32_t e = 0; e < tail; ++e) {
-                const float d = qt[e] - xr[e];
-                sum = sum + d * d;
-            }
-        }
-
-        const uint64_t pos = cbase + t0 + (uint64_t)lane;
-        const bool valid = (uint32_t)lane < nvalid && pos < lim;
+        const uint64_t pos = w.cbase + t0 + (uint64_t)lane;
+        const bool valid = (uint32_t)lane < nvalid && pos < w.lim;
         if constexpr (MODE == STREAM_TOPK) {
-            const uint64_t mykey =
-                valid ? (((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos)
-                      : KEY_EMPTY;
-            tk.offer(mykey, my_srow, a.k, lane);
+            tk.offer(valid ? l2_key(sum, pos) : KEY_EMPTY, my_srow, a.k, lane);
         } else if constexpr (MODE == STREAM_MINUPD) {
             if (valid) {
                 const float old = a.out_f32[pos];
@@ -155,106 +55,39 @@ __global__ __launch_bounds__(256) void stream_kernel(const StreamArgs a) {
                 }
             }
         } else if constexpr (MODE == STREAM_RANGE) {
-            // the wave's hits go to the query's segment in one block: ballot, rank from mbcnt, one atomicAdd per wave
-            const float outv = a.sqrt_out == 1 ? sqrt_f32_ieee(sum) : a.sqrt_out == 2 ? 0.5f * sum : sum;     // (2: PQV_COSINE)
-            const bool hit = valid && outv <= a.radius;                // (a NaN distance never compares true)
-            const uint64_t m = __ballot(hit);
-            if (m) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(a.hit_cnt + q, (uint32_t)__popcll(m));
-                base = (uint32_t)__shfl((int)base, 0, 64);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (hit) {
-                    const uint64_t o = (uint64_t)q * a.seg_stride + base + rank;
-                    a.hit_keys[o] = ((uint64_t)__float_as_uint(sum) << 32) | (uint64_t)(uint32_t)pos;
-                    a.hit_vals[o] = my_srow;
-                }
-            }
+            emit_l2_range_hit(a, q, valid, sum, pos, my_srow, lane);
         } else {
             if (valid) a.out_f32[pos] = sum;
         }
     }
 
-    if constexpr (MODE == STREAM_TOPK) {
-        const uint32_t n_part = a.nprobe * a.blocks_per_list * 4;
-        const uint32_t pi = (j * a.blocks_per_list + blockIdx.x) * 4 + wave;
-        const uint64_t base = ((uint64_t)q * n_part + pi) * a.k;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const uint32_t e = s * 64 + lane;
-            if (e < a.k) {
-                a.part_keys[base + e] = tk.key[s];
-                a.part_vals[base + e] = tk.val[s];
-            }
-        }
-    }
+    if constexpr (MODE == STREAM_TOPK) write_partial_lists<S>(a.part_keys, a.part_vals, partial_base(a, q, j, wave, a.k), a.k, lane, tk.key, tk.val);
 }
 
-#undef LDS_AT
-
-template <int CG, int S, int MODE, bool SEQ, bool ALIGNED>
-static hipError_t launch_stream_t(const StreamArgs &a, hipStream_t s) {
-    dim3 grid(a.blocks_per_list, a.probe ? a.nprobe : 1, a.nq);
-    hipLaunchKernelGGL((stream_kernel<CG, S, MODE, SEQ, ALIGNED>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int S>
-static hipError_t launch_stream_topk_s(const StreamArgs &a, hipStream_t s) {
-    const bool aligned = (a.dim % 4) == 0;
-    const uint32_t G = a.dim / 4;
-    if (a.metric == 1) {
-        return aligned ? launch_stream_t<16, S, STREAM_TOPK, true, true>(a, s)
-                       : launch_stream_t<16, S, STREAM_TOPK, true, false>(a, s);
-    }
-    if (!aligned) return launch_stream_t<32, S, STREAM_TOPK, false, false>(a, s);
-    if (G >= 64 && G % 64 == 0) return launch_stream_t<64, S, STREAM_TOPK, false, true>(a, s);
-    return launch_stream_t<32, S, STREAM_TOPK, false, true>(a, s);
-}
-
-template <int CG, bool SEQ, bool ALIGNED>
-static hipError_t launch_stream_range_t(const StreamArgs &a, hipStream_t s) {
-    dim3 grid(a.blocks_per_list, a.nj, a.nq);
-    hipLaunchKernelGGL((stream_kernel<CG, 1, STREAM_RANGE, SEQ, ALIGNED>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+// the chunk choice is dispatch_chunk's (stream_walk.hpp); STREAM_DIST has no CG 64 form
+template <int S, int MODE, bool WIDE_OK = true>
+static hipError_t launch_stream_s(const StreamArgs &a, hipStream_t s) {
+    return dispatch_chunk<true, WIDE_OK>(a.dim, a.metric, [&](auto cg, auto seq, auto aligned) {
+        dim3 grid(a.blocks_per_list, MODE == STREAM_RANGE ? a.nj : a.probe ? a.nprobe : 1, a.nq);
+        hipLaunchKernelGGL((stream_kernel<cg.value, S, MODE, seq.value, aligned.value>), grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_stream(const StreamArgs &a, StreamMode mode, hipStream_t s) {
     if (a.nq == 0 || a.blocks_per_list == 0) return hipSuccess;
-    if (mode == STREAM_RANGE) {          // (the chunk choice of STREAM_TOPK: the chain order does not depend on it)
+    if (mode == STREAM_RANGE) {
         if (a.nj == 0 || !a.probe) return a.nj == 0 ? hipSuccess : hipErrorInvalidValue;
-        const bool aligned = (a.dim % 4) == 0;
-        const uint32_t G = a.dim / 4;
-        if (a.metric == 1) return aligned ? launch_stream_range_t<16, true, true>(a, s) : launch_stream_range_t<16, true, false>(a, s);
-        if (!aligned) return launch_stream_range_t<32, false, false>(a, s);
-        if (G >= 64 && G % 64 == 0) return launch_stream_range_t<64, false, true>(a, s);
-        return launch_stream_range_t<32, false, true>(a, s);
+        return launch_stream_s<1, STREAM_RANGE>(a, s);
     }
     if (mode == STREAM_TOPK) {
-        if (a.k <= 64) return launch_stream_topk_s<1>(a, s);
-        if (a.k <= 256) return launch_stream_topk_s<4>(a, s);
-        if (a.k <= 1024) return launch_stream_topk_s<16>(a, s);
+        if (a.k <= 64) return launch_stream_s<1, STREAM_TOPK>(a, s);
+        if (a.k <= 256) return launch_stream_s<4, STREAM_TOPK>(a, s);
+        if (a.k <= 1024) return launch_stream_s<16, STREAM_TOPK>(a, s);
         return hipErrorInvalidValue;
     }
-    const bool aligned = (a.dim % 4) == 0;
-    const uint32_t G = a.dim / 4;
-    if (a.metric == 1) {
-        if (mode == STREAM_MINUPD)
-            return aligned ? launch_stream_t<16, 1, STREAM_MINUPD, true, true>(a, s)
-                           : launch_stream_t<16, 1, STREAM_MINUPD, true, false>(a, s);
-        if (mode == STREAM_DIST)
-            return aligned ? launch_stream_t<16, 1, STREAM_DIST, true, true>(a, s)
-                           : launch_stream_t<16, 1, STREAM_DIST, true, false>(a, s);
-        return hipErrorInvalidValue;
-    }
-    if (mode == STREAM_MINUPD) {
-        if (!aligned) return launch_stream_t<32, 1, STREAM_MINUPD, false, false>(a, s);
-        if (G >= 64 && G % 64 == 0) return launch_stream_t<64, 1, STREAM_MINUPD, false, true>(a, s);
-        return launch_stream_t<32, 1, STREAM_MINUPD, false, true>(a, s);
-    }
-    if (mode == STREAM_DIST)
-        return aligned ? launch_stream_t<32, 1, STREAM_DIST, false, true>(a, s)
-                       : launch_stream_t<32, 1, STREAM_DIST, false, false>(a, s);
+    if (mode == STREAM_MINUPD) return launch_stream_s<1, STREAM_MINUPD>(a, s);
+    if (mode == STREAM_DIST) return launch_stream_s<1, STREAM_DIST, false>(a, s);
     return hipErrorInvalidValue;
 }
 
