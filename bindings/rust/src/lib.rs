@@ -591,6 +591,86 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// Keep probing until `k` GROUPS are found (`include/pqv.h`: `pqv_topk_distinct_expand`): every query probes the fewest lists, at
+    /// least `nprobe` and at most `max_nprobe`, that hold `k` distinct values of `group_keys` among the rows it considers, and gets
+    /// what [`Searcher::topk_distinct`] (`filter` `None`) or [`Searcher::topk_distinct_filtered`] returns for that many lists.
+    /// Returns the hits and the lists each query probed.
+    pub fn topk_distinct_expand(&self, group_keys: &RowKeys, filter: Option<(&RowKeys, &KeyFilter)>, mask: Option<&RowMask>, queries: &[f32],
+                                dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize, max_nprobe: NonZeroUsize)
+                                -> Result<(Vec<Vec<DistinctSearchResult>>, Vec<u32>)> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        // (the arrays the descriptor points at live until the call has returned)
+        let held = match filter {
+            Some((_, f)) => Some(key_filter_desc(f, nq)?),
+            None => None,
+        };
+        let keys_raw = filter.map_or(ptr::null(), |(kk, _)| kk.raw as *const _);
+        let desc_ptr = held.as_ref().map_or(ptr::null(), |h| &h.0 as *const sys::PqvKeyFilter);
+        let (k, np, max_np) = (k.get(), nprobe.get(), max_nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut group = vec![0i64; nq * k];
+        let mut found = vec![0u32; nq];
+        let mut used = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_distinct_expand(self.raw, group_keys.raw, keys_raw, desc_ptr, mask.map_or(ptr::null(), |m| m.raw as *const _),
+                                          queries.as_ptr(), nq as u32, dim as u32, k as u32, np as u32, max_np as u32, sys::PQV_L2SQ_REF4, 1,
+                                          rows.as_mut_ptr(), dist.as_mut_ptr(), group.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut(),
+                                          used.as_mut_ptr())
+        })?;
+        let hits = (0..nq)
+            .map(|q| {
+                (0..found[q] as usize)
+                    .map(|i| DistinctSearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i], key: group[q * k + i] })
+                    .collect()
+            })
+            .collect();
+        Ok((hits, used))
+    }
+
+    /// [`Searcher::topk_distinct_expand`] with up to `group_size` rows per group (`include/pqv.h`: `pqv_topk_grouped_expand`): the
+    /// target stays `k` groups.
+    pub fn topk_grouped_expand(&self, group_keys: &RowKeys, filter: Option<(&RowKeys, &KeyFilter)>, mask: Option<&RowMask>, queries: &[f32],
+                               dim: usize, k: NonZeroUsize, group_size: NonZeroUsize, nprobe: NonZeroUsize, max_nprobe: NonZeroUsize)
+                               -> Result<(Vec<Vec<GroupSearchResult>>, Vec<u32>)> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let held = match filter {
+            Some((_, f)) => Some(key_filter_desc(f, nq)?),
+            None => None,
+        };
+        let keys_raw = filter.map_or(ptr::null(), |(kk, _)| kk.raw as *const _);
+        let desc_ptr = held.as_ref().map_or(ptr::null(), |h| &h.0 as *const sys::PqvKeyFilter);
+        let (k, m, np, max_np) = (k.get(), group_size.get(), nprobe.get(), max_nprobe.get());
+        let mut rows = vec![0u32; nq * k * m];
+        let mut dist = vec![0f32; nq * k * m];
+        let mut group = vec![0i64; nq * k];
+        let mut group_rows = vec![0u32; nq * k];
+        let mut found = vec![0u32; nq];
+        let mut used = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_grouped_expand(self.raw, group_keys.raw, keys_raw, desc_ptr, mask.map_or(ptr::null(), |x| x.raw as *const _),
+                                         queries.as_ptr(), nq as u32, dim as u32, k as u32, m as u32, np as u32, max_np as u32,
+                                         sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(), dist.as_mut_ptr(), group.as_mut_ptr(),
+                                         group_rows.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut(), used.as_mut_ptr())
+        })?;
+        let hits = (0..nq)
+            .map(|q| {
+                (0..found[q] as usize)
+                    .map(|g| {
+                        let o = (q * k + g) * m;
+                        GroupSearchResult {
+                            key: group[q * k + g],
+                            hits: (0..group_rows[q * k + g] as usize)
+                                .map(|i| SearchResult { row_idx: rows[o + i], distance: dist[o + i] })
+                                .collect(),
+                        }
+                    })
+                    .collect()
+            })
+            .collect();
+        Ok((hits, used))
+    }
+
     /// [`Searcher::topk_grouped`] under a per-query filter, as [`Searcher::topk_distinct_filtered`] takes it (`include/pqv.h`:
     /// `pqv_topk_grouped_filtered`).
     pub fn topk_grouped_filtered(&self, group_keys: &RowKeys, filter_keys: &RowKeys, filter: &KeyFilter, mask: Option<&RowMask>,

@@ -643,8 +643,8 @@ int pqv_range_search_filtered(const pqv_searcher *searcher, const pqv_row_keys *
  *   path       the probe ranks P lists per query; a counting pass over the filter's images (1 bit per row of a mask, 4 or 8
  *              bytes per row of a key column) and a select write nprobe_used; ONE exact streaming pass then walks each query's
  *              lists below its own limit.
- *   out of scope  table searchers, PQV_DOT, max_candidates, distinct / grouped expansion, range search, and -- for the host form
- *              too -- k or P beyond the kernels' lists.
+ *   out of scope  table searchers, PQV_DOT, max_candidates, range search, and -- for the host form too -- k or P beyond the kernels'
+ *              lists.  (Expansion with a group column: pqv_topk_distinct_expand below.)
  * Errors, checked in this order, NULL handles before any device use -- PQV_ERR_INVALID: "searcher must not be NULL",
  * "pqv_topk_expand needs a row mask or row keys", "a key filter needs row keys" (filter without keys), "filter must not be NULL"
  * (keys without filter), the filter-descriptor checks of the filtered host form, "max_nprobe must be >= nprobe", then the twin's
@@ -728,8 +728,8 @@ int pqv_topk_distinct_device(const pqv_searcher *searcher, const pqv_row_keys *k
  *   counts           group_size > 1: queries and candidate_rows advance once per query, not once per pass; embeddings_fetched
  *                    advances by the considered rows plus the rows the second pass evaluates, the considered rows of the selected
  *                    groups.  group_size == 1: the distinct call's counts.
- *   out of scope     grouped range search; PQV_DOT; probing further lists when fewer than k groups are found.  (A per-query key
- *                    filter together with grouping: pqv_topk_grouped_filtered below.)
+ *   out of scope     grouped range search; PQV_DOT.  (A per-query key filter together with grouping: pqv_topk_grouped_filtered
+ *                    below.  Probing further lists when fewer than k groups are found: pqv_topk_grouped_expand below.)
  * Errors: pqv_topk_distinct's, in the same order, NULL handles checked before any device use; behind "k must be > 0":
  * "group_size must be > 0".  PQV_DOT: PQV_ERR_UNSUPPORTED "PQV_DOT is not supported by keyed and distinct calls". */
 int pqv_topk_grouped(const pqv_searcher *searcher, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries,
@@ -768,8 +768,8 @@ int pqv_topk_grouped_device(const pqv_searcher *searcher, const pqv_row_keys *ke
  *                    lists) the host forms compute the sorted considered sequence with the filtered range machinery (radius =
  *                    +inf, the group validity AND the shared mask as the image, the per-query filter beside it) and group on the
  *                    host; the device forms report the twins' PQV_ERR_UNSUPPORTED.
- *   out of scope     expansion (max_nprobe) with a group column; PQV_DOT: PQV_ERR_UNSUPPORTED "PQV_DOT is not supported by keyed
- *                    and distinct calls".
+ *   out of scope     PQV_DOT: PQV_ERR_UNSUPPORTED "PQV_DOT is not supported by keyed and distinct calls".  (Expansion (max_nprobe)
+ *                    with a group column: pqv_topk_distinct_expand below.)
  * Errors (PQV_ERR_INVALID), in this order, every NULL and zero check before a handle is dereferenced or a device used: "searcher
  * must not be NULL", "row keys must not be NULL" (group_keys), "a key filter needs row keys" (filter_keys), "filter must not be
  * NULL", the descriptor checks of pqv_topk_filtered, "k must be > 0", "group_size must be > 0" (grouped), "row keys belong to
@@ -793,6 +793,60 @@ int pqv_topk_grouped_filtered_device(const pqv_searcher *searcher, const pqv_row
                                      uint32_t k, uint32_t group_size, uint32_t nprobe, uint64_t max_candidates, int metric,
                                      int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows,
                                      void *d_n_found, void *d_n_candidates, void *hip_stream);
+
+/* Expanding distinct and grouped top-k: every query probes on until k GROUPS are found -- the k nearest documents of a tenant
+ * without raising nprobe for the whole batch and without a round trip per short query.
+ *
+ * Each call is its twin with max_nprobe where max_candidates stands and one more output, nprobe_used (uint32_t [nq]).  The twin is
+ * chosen by the filter arguments: filter_keys == NULL && filter == NULL -- pqv_topk_distinct / pqv_topk_grouped (`mask` optional, so
+ * a plain distinct call expands too); both non-NULL -- pqv_topk_distinct_filtered / pqv_topk_grouped_filtered.
+ *   rule       kc lists, p0 = min(nprobe, kc), P = min(max_nprobe, kc); M_q the twin's row set of query q (the shared mask, ANDed
+ *              with the filter column's validity and the query's test in the filtered forms).  gcnt_q(p) = the DISTINCT i64 group
+ *              values among the rows r of the first p lists of q's probe order whose group key is valid and for which M_q[r]
+ *              holds -- whatever their distance, nothing capped.  nprobe_used[q] = the smallest p in [p0, P] with gcnt_q(p) >= k,
+ *              P where there is none.  group_size plays no part: the target is k groups.
+ *   result     query q returns, bit for bit, what the twin returns for that one query with nprobe = nprobe_used[q] and
+ *              max_candidates = 0: row_idx, dist, group_key, group_rows (grouped) and n_found; n_candidates[q] is the summed
+ *              length of the used lists.  The counters advance as for those nq twin calls; the counting pass reads no embedding
+ *              and counts nothing.  No new result is defined: the probe order is prefix-consistent and positions are prefix sums
+ *              in it, as for pqv_topk_expand.  No tie flags and no heap replay, as the twins; the host and the device form
+ *              return the same thing.  max_nprobe == nprobe is the twin call itself.
+ *   scope      plain searchers, both layouts, PQV_L2SQ_REF4 / PQV_L2SQ_SEQ / PQV_COSINE (through the cosine layout, as the twins),
+ *              I32 and I64 group columns with or without validity, all three filter kinds.  Every output except row_idx and
+ *              dist may be NULL.  The device forms are asynchronous on hip_stream with no host synchronisation; device filter
+ *              arrays are read inside the enqueued work.
+ *   path       the probe ranks P lists per query; ONE counting kernel (a block per query) walks the lists in probe order over
+ *              the stream passes' own windows and keeps the group values seen in an exact hash set until it holds k; the twin's
+ *              stream pass or passes then walk each query's lists below its own limit, and the twin's merge follows.
+ *   out of scope  table searchers, PQV_DOT, max_candidates, range search, and -- for the host forms too -- lists beyond the kernels'.
+ * Errors (PQV_ERR_INVALID), in this order, every NULL and zero check before a handle is read: "searcher must not be NULL", "row
+ * keys must not be NULL" (group_keys), "a key filter needs row keys" (filter without filter_keys), "filter must not be NULL"
+ * (filter_keys without filter), the descriptor checks of pqv_topk_filtered, "max_nprobe must be >= nprobe", "k must be > 0",
+ * "group_size must be > 0" (grouped), "row keys belong to another searcher" (either column), "row mask belongs to another
+ * searcher", and the rest of pqv_topk's.  PQV_ERR_UNSUPPORTED, both forms: "pqv_topk_distinct_expand does not take table searchers"
+ * (grouped: its own name), "PQV_DOT is not supported by keyed and distinct calls", "pqv_topk_distinct_expand takes k <= 1024 and
+ * at most 1024 probed lists per query", "pqv_topk_grouped_expand takes k * group_size <= 1024 and at most 1024 probed lists per
+ * query" (the product in 64 bits; the host forms do not fall back to the range machinery). */
+int pqv_topk_distinct_expand(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                             const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                             uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric, int sqrt_out,
+                             uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates,
+                             uint32_t *nprobe_used);
+int pqv_topk_distinct_expand_device(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                    const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                    uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric, int sqrt_out, void *d_row_idx,
+                                    void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates, void *d_nprobe_used,
+                                    void *hip_stream);
+int pqv_topk_grouped_expand(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                            const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                            uint32_t query_len, uint32_t k, uint32_t group_size, uint32_t nprobe, uint32_t max_nprobe, int metric,
+                            int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows,
+                            uint32_t *n_found, uint64_t *n_candidates, uint32_t *nprobe_used);
+int pqv_topk_grouped_expand_device(const pqv_searcher *searcher, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                   const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                   uint32_t k, uint32_t group_size, uint32_t nprobe, uint32_t max_nprobe, int metric, int sqrt_out,
+                                   void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
+                                   void *d_n_candidates, void *d_nprobe_used, void *hip_stream);
 
 /* Exhaustive top-k of nq queries over EVERY row of the resident column (no index), batched
  * on the matrix cores: what DataFusion's brute-force `ORDER BY array_distance(..) LIMIT k`

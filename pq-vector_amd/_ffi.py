@@ -194,6 +194,14 @@ SIGNATURES = {
                                             C.c_uint32, C.c_uint64, C.c_int, C.c_int, u32p, f32p, i64p, u32p, u32p, u64p]),
     "pqv_topk_grouped_filtered_device": (C.c_int, [vp, vp, vp, C.POINTER(KeyFilter), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                    C.c_uint64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "pqv_topk_distinct_expand": (C.c_int, [vp, vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_int, C.c_int, u32p, f32p, i64p, u32p, u64p, u32p]),
+    "pqv_topk_distinct_expand_device": (C.c_int, [vp, vp, vp, C.POINTER(KeyFilter), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "pqv_topk_grouped_expand": (C.c_int, [vp, vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, f32p, i64p, u32p, u32p, u64p, u32p]),
+    "pqv_topk_grouped_expand_device": (C.c_int, [vp, vp, vp, C.POINTER(KeyFilter), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.c_uint32, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pqv_brute_topk": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, u32p]),
     "pqv_rerank": (C.c_int, [C.c_int, f32p, f32p, u32p, u8p, C.c_uint64, C.c_uint32, C.c_uint32,
                              C.c_int, u32p, f32p, u32p]),

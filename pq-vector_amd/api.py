@@ -907,14 +907,17 @@ class Searcher:
         return rows, dist, nf, nc
 
     def topk_distinct(self, queries, k, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True,
-                      filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None):
+                      filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=None):
         """Distinct top-k (pqv.h: pqv_topk_distinct): per query the nearest row of each of the k nearest groups, a group being the
         considered rows of one value of `keys` (a RowKeys of this searcher; NULL-key rows belong to no group), under `mask` if one
         is given.  Returns (row_idx [nq,k] u32, dist [nq,k] f32, group_keys [nq,k] i64, n_found [nq], n_candidates [nq]), ascending
         by (d2, candidate position); entries past n_found are 0xFFFFFFFF, +inf and 0.
         filter_keys (a RowKeys of this searcher; it may be `keys`) with one of query_keys / query_key_ranges / query_key_sets, as
         topk takes them: query q considers only the rows whose filter key passes ITS test -- the filter applies before a group's
-        representative is chosen (pqv.h: pqv_topk_distinct_filtered)."""
+        representative is chosen (pqv.h: pqv_topk_distinct_filtered).
+        max_nprobe (not with max_candidates): keep probing until k GROUPS are found -- query q probes the fewest lists, at least
+        nprobe and at most max_nprobe, that hold k distinct group values among its considered rows, and gets what the call without
+        max_nprobe returns for that many lists; a sixth array nprobe_used [nq] u32 comes back (pqv.h: pqv_topk_distinct_expand)."""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -925,6 +928,17 @@ class Searcher:
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
         gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if max_nprobe is not None:
+            if max_candidates:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
+            used = np.zeros(nq, dtype=np.uint32)
+            fk, fp = (gf[0], gf[1]) if gf is not None else (None, None)
+            _check(_ffi.lib().pqv_topk_distinct_expand(self._h, _group_handle(keys), fk, fp,
+                                                       _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
+                                                       qlen, k, nprobe, max_nprobe, metric, 1 if sqrt_out else 0,
+                                                       rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), grp.ctypes.data_as(_ffi.i64p),
+                                                       nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p), used.ctypes.data_as(u32p)))
+            return rows, dist, grp, nf, nc, used
         if gf is not None:
             _check(_ffi.lib().pqv_topk_distinct_filtered(self._h, _group_handle(keys), gf[0], gf[1],
                                                          _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
@@ -940,13 +954,25 @@ class Searcher:
 
     def topk_distinct_device(self, d_queries, nq, k, nprobe, keys, d_row_idx, d_dist, d_group_key=0, d_n_found=0, d_n_candidates=0,
                              mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, filter_keys=None,
-                             query_keys=None, query_key_ranges=None, query_key_sets=None):
+                             query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=0, d_nprobe_used=0):
         """Device-pointer form of topk_distinct (pqv.h: pqv_topk_distinct_device), asynchronous on `stream` as topk_device is:
         d_row_idx u32 / d_dist f32 / d_group_key i64 [nq, k], d_n_found u32 / d_n_candidates u64 [nq]; the last three are optional.
         keys and mask must stay alive until the enqueued work has completed.
         filter_keys with query_keys / query_key_ranges / query_key_sets as DEVICE pointers, as topk_device takes them, read on
-        `stream` inside the enqueued work (pqv.h: pqv_topk_distinct_filtered_device)."""
+        `stream` inside the enqueued work (pqv.h: pqv_topk_distinct_filtered_device).
+        max_nprobe (> 0; not with max_candidates): the expanding call, as topk_distinct's; d_nprobe_used (u32 [nq], optional) takes
+        the lists each query probed (pqv.h: pqv_topk_distinct_expand_device)."""
         gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        if max_nprobe:
+            if max_candidates:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
+            fk, fp = (gf[0], gf[1]) if gf is not None else (None, None)
+            _check(_ffi.lib().pqv_topk_distinct_expand_device(self._h, _group_handle(keys), fk, fp,
+                                                              _mask_handle(self, mask) if mask is not None else None, vp(d_queries), nq, k,
+                                                              nprobe, max_nprobe, metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
+                                                              vp(d_group_key or None), vp(d_n_found or None), vp(d_n_candidates or None),
+                                                              vp(d_nprobe_used or None), vp(stream or None)))
+            return
         if gf is not None:
             _check(_ffi.lib().pqv_topk_distinct_filtered_device(self._h, _group_handle(keys), gf[0], gf[1],
                                                                 _mask_handle(self, mask) if mask is not None else None, vp(d_queries), nq, k,
@@ -960,13 +986,15 @@ class Searcher:
                                                    vp(d_n_candidates or None), vp(stream or None)))
 
     def topk_grouped(self, queries, k, group_size, nprobe, keys, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True,
-                     filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None):
+                     filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=None):
         """Grouped top-k (pqv.h: pqv_topk_grouped): per query up to group_size rows of each of the k nearest groups of `keys` (as
         topk_distinct defines groups), under `mask` if one is given.  Returns (row_idx [nq,k,group_size] u32, dist [nq,k,group_size]
         f32, group_keys [nq,k] i64, group_rows [nq,k] u32, n_found [nq], n_candidates [nq]): groups ascending by their nearest row,
         a group's rows ascending by (d2, candidate position); empty row slots are 0xFFFFFFFF / +inf, empty groups key 0, count 0.
         filter_keys with query_keys / query_key_ranges / query_key_sets: a per-query filter, as topk_distinct takes it (pqv.h:
-        pqv_topk_grouped_filtered)."""
+        pqv_topk_grouped_filtered).
+        max_nprobe (not with max_candidates): keep probing until k groups are found, as topk_distinct takes it; a seventh array
+        nprobe_used [nq] u32 comes back (pqv.h: pqv_topk_grouped_expand)."""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -979,6 +1007,18 @@ class Searcher:
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
         gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if max_nprobe is not None:
+            if max_candidates:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
+            used = np.zeros(nq, dtype=np.uint32)
+            fk, fp = (gf[0], gf[1]) if gf is not None else (None, None)
+            _check(_ffi.lib().pqv_topk_grouped_expand(self._h, _group_handle(keys), fk, fp,
+                                                      _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
+                                                      qlen, k, group_size, nprobe, max_nprobe, metric, 1 if sqrt_out else 0,
+                                                      rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), grp.ctypes.data_as(_ffi.i64p),
+                                                      grows.ctypes.data_as(u32p), nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p),
+                                                      used.ctypes.data_as(u32p)))
+            return rows, dist, grp, grows, nf, nc, used
         if gf is not None:
             _check(_ffi.lib().pqv_topk_grouped_filtered(self._h, _group_handle(keys), gf[0], gf[1],
                                                         _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
@@ -995,13 +1035,26 @@ class Searcher:
 
     def topk_grouped_device(self, d_queries, nq, k, group_size, nprobe, keys, d_row_idx, d_dist, d_group_key=0, d_group_rows=0, d_n_found=0,
                             d_n_candidates=0, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0,
-                            filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None):
+                            filter_keys=None, query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=0, d_nprobe_used=0):
         """Device-pointer form of topk_grouped (pqv.h: pqv_topk_grouped_device), asynchronous on `stream` as topk_device is:
         d_row_idx u32 / d_dist f32 [nq, k, group_size], d_group_key i64 / d_group_rows u32 [nq, k], d_n_found u32 / d_n_candidates u64
         [nq]; the last four are optional.  Serves k * group_size <= 1024.  keys and mask must stay alive until the work has completed.
         filter_keys with device-pointer query_keys / query_key_ranges / query_key_sets: as topk_distinct_device (pqv.h:
-        pqv_topk_grouped_filtered_device)."""
+        pqv_topk_grouped_filtered_device).
+        max_nprobe (> 0; not with max_candidates) and d_nprobe_used: the expanding call, as topk_distinct_device's (pqv.h:
+        pqv_topk_grouped_expand_device)."""
         gf = _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        if max_nprobe:
+            if max_candidates:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
+            fk, fp = (gf[0], gf[1]) if gf is not None else (None, None)
+            _check(_ffi.lib().pqv_topk_grouped_expand_device(self._h, _group_handle(keys), fk, fp,
+                                                             _mask_handle(self, mask) if mask is not None else None, vp(d_queries), nq, k,
+                                                             group_size, nprobe, max_nprobe, metric, 1 if sqrt_out else 0, vp(d_row_idx),
+                                                             vp(d_dist), vp(d_group_key or None), vp(d_group_rows or None),
+                                                             vp(d_n_found or None), vp(d_n_candidates or None), vp(d_nprobe_used or None),
+                                                             vp(stream or None)))
+            return
         if gf is not None:
             _check(_ffi.lib().pqv_topk_grouped_filtered_device(self._h, _group_handle(keys), gf[0], gf[1],
                                                                _mask_handle(self, mask) if mask is not None else None, vp(d_queries), nq, k,
@@ -1378,12 +1431,13 @@ class TopkBuilder:
         self._group_size = m
         return self
 
-    def _search_grouped(self, searcher, mask, max_candidates=0):
+    def _search_grouped(self, searcher, mask, max_candidates=0, max_nprobe=None):
         """-> [(key, rows, dist)] of the found groups."""
         keys, owned = self._group_keys(searcher)
         try:
-            rows, dist, grp, grows, nf, _ = searcher.topk_grouped(_f32(self._query).reshape(1, -1), self._k, self._group_size, self._nprobe,
-                                                                  keys, mask=mask, max_candidates=max_candidates, metric=self._metric)
+            rows, dist, grp, grows, nf = searcher.topk_grouped(_f32(self._query).reshape(1, -1), self._k, self._group_size, self._nprobe,
+                                                               keys, mask=mask, max_candidates=max_candidates, metric=self._metric,
+                                                               max_nprobe=max_nprobe)[:5]
         finally:
             if owned:
                 keys.close()
@@ -1401,11 +1455,11 @@ class TopkBuilder:
             _attach_file_columns(searcher, self._path, [self._distinct])
         return searcher.row_keys(self._distinct), True
 
-    def _search_distinct(self, searcher, mask, max_candidates=0):
+    def _search_distinct(self, searcher, mask, max_candidates=0, max_nprobe=None):
         keys, owned = self._group_keys(searcher)
         try:
-            rows, dist, grp, nf, _ = searcher.topk_distinct(_f32(self._query).reshape(1, -1), self._k, self._nprobe, keys, mask=mask,
-                                                            max_candidates=max_candidates, metric=self._metric)
+            rows, dist, grp, nf = searcher.topk_distinct(_f32(self._query).reshape(1, -1), self._k, self._nprobe, keys, mask=mask,
+                                                         max_candidates=max_candidates, metric=self._metric, max_nprobe=max_nprobe)[:4]
         finally:
             if owned:
                 keys.close()
@@ -1439,11 +1493,8 @@ class TopkBuilder:
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         self._check_grouping()
-        if self._max_nprobe is not None:
-            if self._where is None:
-                raise PqvError(_ffi.PQV_ERR_INVALID, "pqv_topk_expand needs a row mask or row keys")
-            if self._distinct is not None:
-                raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "max_nprobe() does not combine with distinct_on()")
+        if self._max_nprobe is not None and self._where is None and self._distinct is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "pqv_topk_expand needs a row mask or row keys")
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
         if self._distinct is not None:
@@ -1451,8 +1502,8 @@ class TopkBuilder:
             try:
                 if self._group_size is not None:
                     return [GroupSearchResult(g, [SearchResult(r, d) for r, d in zip(rows.tolist(), dist.tolist())])
-                            for g, rows, dist in self._search_grouped(self._searcher, mask)]
-                rows, dist, grp = self._search_distinct(self._searcher, mask)
+                            for g, rows, dist in self._search_grouped(self._searcher, mask, max_nprobe=self._max_nprobe)]
+                rows, dist, grp = self._search_distinct(self._searcher, mask, max_nprobe=self._max_nprobe)
             finally:
                 if owned:
                     mask.close()

@@ -715,7 +715,7 @@ static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskVi
         if (mode != pqv::STREAM_TOPK) return hipErrorInvalidValue;
         const pqv_row_keys *gk = mv->group;
         const pqv::DistinctArgs da{mv->bits, stats, n_cand, gk->d_key_pos.p, gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr,
-                                   gk->dtype == PQV_COL_I32 ? 4u : 8u, part_grp};
+                                   gk->dtype == PQV_COL_I32 ? 4u : 8u, part_grp, rank_limit};
         if (mv->keys) return pqv::launch_distinct_filter_stream(ra, da, group_filter_args(mv), stream);
         return pqv::launch_distinct_stream(ra, da, stream);
     }
@@ -3644,7 +3644,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     const uint32_t p0 = probe_count(s, nprobe);
     nprobe = probe_arg(mask, nprobe);
     const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, mask != nullptr);
-    if (expand && (s->n_files || mask->group || p.tile || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
+    if (expand && (s->n_files || p.tile || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
         return fail(PQV_ERR_INVALID, "expanding call on a plan that cannot expand");
     const uint64_t max_pos = max_candidates ? max_candidates : ~0ull;
     // the probe works on the queries as given; everything that meets the (possibly zero-padded) stored rows gets the
@@ -3783,24 +3783,34 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     const uint64_t *pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
     const uint32_t *rank_limit = nullptr;
     if (expand) {
-        HIP_TRY(sc.s_expand_cnt.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
         uint32_t *used = mask->d_nprobe_used;
         if (!used) { HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(nq) * sizeof(uint32_t))); used = sc.s_expand_used.as<uint32_t>(); }
-        ExpandCountArgs ca{};
-        ca.probe = sc.s_probe.as<uint32_t>(); ca.list_off = s->d_list_off.as<uint64_t>(); ca.nq = nq; ca.P = p.np;
-        ca.bits = mask->bits; ca.cnt = sc.s_expand_cnt.as<uint32_t>();
-        if (const pqv_row_keys *kk = mask->keys) {
-            const uint32_t wide = kk->dtype == PQV_COL_I32 ? 0u : 1u;
-            ca.win = 1u + 2u * mask->fkind + wide;
-            ca.key_pos = kk->d_key_pos.p; ca.valid_pos = kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr;
-            ca.a = mask->fkind ? mask->d_fa : mask->d_qkeys; ca.b = mask->fkind ? mask->d_fb : nullptr;
+        // (both forms before the stream pass: that pass adds n_cand[q] to candidate_rows)
+        if (const pqv_row_keys *gk = mask->group) {
+            // a group column (pqv_topk_distinct_expand): DISTINCT group values in probe order, one block per query, one launch
+            const GroupExpandArgs ga{sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(), s->d_list_off.as<uint64_t>(), nq, p.np, p0, k_out,
+                                     mask->bits, gk->d_key_pos.p, gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr,
+                                     gk->dtype == PQV_COL_I32 ? 4u : 8u, used, pm.n_cand};
+            const GroupFilterArgs fa = mask->keys ? group_filter_args(mask) : GroupFilterArgs{};
+            HIP_TRY(launch_group_expand(ga, mask->keys ? &fa : nullptr, stream));
+            s->counters.kernel_launches += 1;
+        } else {
+            HIP_TRY(sc.s_expand_cnt.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
+            ExpandCountArgs ca{};
+            ca.probe = sc.s_probe.as<uint32_t>(); ca.list_off = s->d_list_off.as<uint64_t>(); ca.nq = nq; ca.P = p.np;
+            ca.bits = mask->bits; ca.cnt = sc.s_expand_cnt.as<uint32_t>();
+            if (const pqv_row_keys *kk = mask->keys) {
+                const uint32_t wide = kk->dtype == PQV_COL_I32 ? 0u : 1u;
+                ca.win = 1u + 2u * mask->fkind + wide;
+                ca.key_pos = kk->d_key_pos.p; ca.valid_pos = kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr;
+                ca.a = mask->fkind ? mask->d_fa : mask->d_qkeys; ca.b = mask->fkind ? mask->d_fb : nullptr;
+            }
+            HIP_TRY(launch_filter_count(ca, stream));
+            const ExpandSelectArgs sa{ca.cnt, ca.probe, sc.s_cand_base.as<uint64_t>(), ca.list_off, nq, p.np, p0, k_out, used, pm.n_cand};
+            HIP_TRY(launch_expand_select(sa, stream));
+            s->counters.kernel_launches += 2;
         }
-        HIP_TRY(launch_filter_count(ca, stream));
-        // (before the stream pass: that pass adds n_cand[q] to candidate_rows)
-        const ExpandSelectArgs sa{ca.cnt, ca.probe, sc.s_cand_base.as<uint64_t>(), ca.list_off, nq, p.np, p0, k_out, used, pm.n_cand};
-        HIP_TRY(launch_expand_select(sa, stream));
         rank_limit = used;
-        s->counters.kernel_launches += 2;
     }
 
     // 2. candidate re-rank + per-wave top-k
@@ -4063,6 +4073,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
             ga.k = k; ga.group_size = gm; ga.km = static_cast<uint32_t>(km);
             ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
             ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
+            ga.rank_limit = rank_limit;      // (an expanding call: both passes walk the same ranks)
             if (mask->keys) HIP_TRY(launch_grouped_filter_stream(ra, ga, group_filter_args(mask), stream));
             else HIP_TRY(launch_grouped_stream(ra, ga, stream));
             GroupedMergeArgs gma{};
@@ -5428,14 +5439,15 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
     if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
     Scratch &sc = *lane;
     LaneGuard lane_guard{sc, s->stream};
-    if (grouped_beyond_kernel_lists(s, k, m, nprobe)) {
+    const bool expand = mv->max_nprobe != 0;       // (pqv_topk_distinct_expand: within the kernels' lists, checked by its view)
+    if (!expand && grouped_beyond_kernel_lists(s, k, m, nprobe)) {
         const int rc = distinct_unbounded(s, sc, mv, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, group_key, n_found,
                                           n_candidates, m, group_rows);
         const int rc2 = lane_release(sc, s->stream);
         return rc ? rc : rc2;
     }
     // sub-batches as the keyed form slices them: the per-wave partial lists (20 B per entry here) stay under ~1 GiB
-    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), nprobe, k, metric, true);
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(mv, nprobe), k, metric, true);
     // (a grouped call's second pass: 16 B per entry of k * m, in the same buffers)
     const uint64_t km = static_cast<uint64_t>(k) * m;
     const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * std::max<uint64_t>(k * 20ull, m > 1 ? km * 16 + 4 : 0) +
@@ -5450,7 +5462,9 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
     HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
     if (mv->keys && !mv->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    if (expand) HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     MaskView sub = *mv;
+    if (expand) sub.d_nprobe_used = sc.s_expand_used.as<uint32_t>();
     sub.d_group_out = sc.s_grp_out.as<int64_t>();
     sub.d_group_rows = group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr;
     std::vector<uint64_t> sub_lims;      // (a filtered call: each sub-batch's kernels read its own slice of the filter, IN lims rebased)
@@ -5473,6 +5487,8 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
         if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         if (n_candidates)
             HIP_TRY(hipMemcpyAsync(n_candidates + q0, sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        if (expand && mv->h_nprobe_used)
+            HIP_TRY(hipMemcpyAsync(mv->h_nprobe_used + q0, sc.s_expand_used.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
         s->counters.queries += b;
     }
@@ -5602,6 +5618,95 @@ extern "C" int pqv_topk_grouped_filtered_device(const pqv_searcher *s, const pqv
         mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
+    });
+}
+
+// ---- expanding distinct / grouped top-k (pqv.h: pqv_topk_distinct_expand) ------------------------------------------------------
+// The checks of all four forms up to the view, in the contract's order: every NULL and zero check before a handle is read.
+// group_size: nullptr for the distinct forms.
+static int group_expand_view(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys, const pqv_key_filter *filter,
+                             const pqv_row_mask *mask, uint32_t nq, uint32_t k, const uint32_t *group_size, uint32_t nprobe, uint32_t max_nprobe,
+                             int metric, bool host, MaskView &mv) {
+    const char *name = group_size ? "pqv_topk_grouped_expand" : "pqv_topk_distinct_expand";
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!group_keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
+    if (!filter_keys && filter) return fail(PQV_ERR_INVALID, "a key filter needs row keys");
+    if (filter_keys && !filter) return fail(PQV_ERR_INVALID, "filter must not be NULL");
+    if (filter_keys) { if (int rc = filter_descriptor_checks(filter, nq, host)) return rc; }
+    if (max_nprobe < nprobe) return fail(PQV_ERR_INVALID, "max_nprobe must be >= nprobe");
+    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (group_size && *group_size == 0) return fail(PQV_ERR_INVALID, "group_size must be > 0");
+    if (group_keys->owner != s || group_keys->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
+    if (filter_keys) {      // (the filter column's owner and the mask's: filtered_view)
+        if (int rc = filtered_view(s, filter_keys, filter, nq, mask, host, mv, true)) return rc;
+    } else {
+        mv = MaskView{};
+        if (mask) { if (int rc = mask_view(s, mask, mv)) return rc; }
+    }
+    mv.group = group_keys;
+    mv.group_size = group_size ? *group_size : 0u;
+    if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (s->n_files) return fail(PQV_ERR_UNSUPPORTED, std::string(name) + " does not take table searchers");
+    if (int rc = dot_checks(s, 1, 1, metric, &mv)) return rc;
+    if (static_cast<uint64_t>(k) * std::max<uint32_t>(1, mv.group_size) > 1024 || probe_count(s, max_nprobe) > 1024)
+        return fail(PQV_ERR_UNSUPPORTED, std::string(name) + (group_size ? " takes k * group_size <= 1024" : " takes k <= 1024") +
+                                             " and at most 1024 probed lists per query");
+    mv.max_nprobe = max_nprobe;
+    return PQV_OK;
+}
+extern "C" int pqv_topk_distinct_expand(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                        const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                        uint32_t query_len, uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric, int sqrt_out,
+                                        uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates,
+                                        uint32_t *nprobe_used) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, nprobe, max_nprobe, metric, true, mv)) return rc;
+        mv.h_nprobe_used = nprobe_used;
+        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key, n_found,
+                                      n_candidates);
+    });
+}
+extern "C" int pqv_topk_distinct_expand_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                               const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                               uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric, int sqrt_out, void *d_row_idx,
+                                               void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates, void *d_nprobe_used,
+                                               void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, nprobe, max_nprobe, metric, false, mv)) return rc;
+        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        mv.d_nprobe_used = static_cast<uint32_t *>(d_nprobe_used);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates,
+                                    nullptr, hip_stream, &mv);
+    });
+}
+extern "C" int pqv_topk_grouped_expand(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                       const pqv_key_filter *filter, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                       uint32_t query_len, uint32_t k, uint32_t group_size, uint32_t nprobe, uint32_t max_nprobe, int metric,
+                                       int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found,
+                                       uint64_t *n_candidates, uint32_t *nprobe_used) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, nprobe, max_nprobe, metric, true, mv)) return rc;
+        mv.h_nprobe_used = nprobe_used;
+        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key, n_found,
+                                      n_candidates, group_rows);
+    });
+}
+extern "C" int pqv_topk_grouped_expand_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
+                                              const pqv_key_filter *filter, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                              uint32_t k, uint32_t group_size, uint32_t nprobe, uint32_t max_nprobe, int metric, int sqrt_out,
+                                              void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
+                                              void *d_n_candidates, void *d_nprobe_used, void *hip_stream) {
+    return guard([&] {
+        MaskView mv{};
+        if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, nprobe, max_nprobe, metric, false, mv)) return rc;
+        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
+        mv.d_nprobe_used = static_cast<uint32_t *>(d_nprobe_used);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates,
+                                    nullptr, hip_stream, &mv);
     });
 }
 

@@ -160,6 +160,31 @@ struct ExpandSelectArgs {
 };
 hipError_t launch_expand_select(const ExpandSelectArgs &a, hipStream_t s);
 
+// ---- expanding distinct / grouped top-k (kernels_group_expand.hip; pqv.h: pqv_topk_distinct_expand) ------------------------
+// group_expand_kernel, one block per query: nprobe_used[q] = the smallest p in [p0, P] whose first p lists hold >= k DISTINCT group
+// values among the positions the call's stream pass would walk (group validity AND shared mask AND the query's filter, the stream
+// kernels' windows from the same pieces), P where there is none; n_cand[q] is overwritten with the summed length of those lists.
+// The values are counted exactly in an LDS hash set.  No embedding is read.  1 <= p0 <= P.
+constexpr uint32_t GROUP_SET_SLOTS = 4096;         // the set's i64 slots (32 KiB): at most k + 255 <= 1279 are ever filled
+constexpr uint64_t GROUP_SET_EMPTY = ~0ull;        // an empty slot; the group value -1 is counted by a flag of its own
+// where the set starts to look for (or place) a group value: slot (h + i) % GROUP_SET_SLOTS for i = 0, 1, ... (tests model it)
+constexpr uint32_t group_set_home(uint64_t v) { return (uint32_t)((v * 0x9E3779B97F4A7C15ull) >> 52); }
+struct GroupFilterArgs;
+struct GroupExpandArgs {
+    const uint32_t *probe;       // [nq, P]
+    const uint64_t *cand_base;   // [nq, P]
+    const uint64_t *list_off;
+    uint32_t        nq, P, p0, k;
+    const uint64_t *bits;        // optional: a shared row mask's image
+    const void     *key_pos;     // the group column's position image, i32 / i64
+    const uint64_t *valid_pos;   // optional
+    uint32_t        elem_size;   // 4 or 8
+    uint32_t       *nprobe_used; // [nq]
+    uint64_t       *n_cand;      // [nq]
+};
+// fa == nullptr: no per-query filter
+hipError_t launch_group_expand(const GroupExpandArgs &a, const GroupFilterArgs *fa, hipStream_t s);
+
 // ---- distinct top-k (kernels_distinct.hip; pqv.h: pqv_topk_distinct) -----------------------------------------------------
 // The group column is a key column's position image (launch_key_layout).  launch_distinct_stream is launch_masked_stream's
 // STREAM_TOPK pass over the positions whose key is valid and which the shared mask allows, with per-wave lists that hold at most
@@ -173,6 +198,7 @@ struct DistinctArgs {
     const uint64_t     *valid_pos;  // optional [n_words]: positions whose key is not NULL
     uint32_t            elem_size;  // 4 or 8
     int64_t            *part_grp;
+    const uint32_t     *rank_limit; // as MaskedArgs::rank_limit (pqv_topk_distinct_expand): the lists of a rank at or beyond it go out EMPTY, group 0
 };
 hipError_t launch_distinct_stream(const StreamArgs &a, const DistinctArgs &da, hipStream_t s);
 // the fold of those lists, one wave per query (distinct_merge_kernel): k <= 1024
@@ -213,6 +239,7 @@ struct GroupedArgs {
     uint32_t           *part_vals;
     uint32_t           *part_slot;
     uint32_t           *part_cnt;   // [nq][n_part]
+    const uint32_t     *rank_limit; // as MaskedArgs::rank_limit (pqv_topk_grouped_expand): the lists of a rank at or beyond it go out with part_cnt 0
 };
 // launch_distinct_stream's walk over the positions whose group value is in the query's set, per-wave lists of at most group_size
 // entries per slot (grouped_stream_kernel); StreamArgs::k / part_keys / part_vals are not read

@@ -47,6 +47,11 @@ __global__ __launch_bounds__(256) void distinct_stream_kernel(const StreamArgs a
     float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y;
+    // a rank at or beyond the query's limit (pqv_topk_distinct_expand) walks nothing: that one word is all the block loads
+    if (da.rank_limit && j >= da.rank_limit[q]) {
+        write_empty_distinct_list(a, da.part_grp, partial_base(a, q, j, wave, a.k), lane);
+        return;
+    }
     const WalkRange w = walk_range<true>(a, q, j, wave);
     unsigned long long *st = stats_slot(da.stats, q);
     stats_add_candidates(st, da.n_cand, q, j);

@@ -25,11 +25,7 @@
 
 namespace pqv {
 
-// The query's test (KeyTest, stream_walk.hpp), set up once per block: PQV_KEY_EQ runs as the range [a[q], a[q]].
-__device__ __forceinline__ void group_filter_bounds(const GroupFilterArgs &fa, uint32_t q, KeyTest<1> &kt) {
-    kt.lo = static_cast<const int64_t *>(fa.a)[q];
-    kt.hi = fa.kind == 0 ? kt.lo : static_cast<const int64_t *>(fa.b)[q];
-}
+// group_filter_bounds: stream_walk.hpp
 
 // ------------------------------------------------------------------------------------
 // distinct_filter_stream_kernel
@@ -47,6 +43,11 @@ __global__ __launch_bounds__(256) void distinct_filter_stream_kernel(const Strea
     float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y;
+    // a rank at or beyond the query's limit (pqv_topk_distinct_expand) walks nothing (block-uniform: nobody is left at the barrier)
+    if (da.rank_limit && j >= da.rank_limit[q]) {
+        write_empty_distinct_list(a, da.part_grp, partial_base(a, q, j, wave, a.k), lane);
+        return;
+    }
     // the query's test (block-uniform; IN: every wave of the block passes the barrier before it looks at its range)
     KeyTest<IN ? 2 : 1> kt;
     if constexpr (IN) {
@@ -130,6 +131,11 @@ __global__ __launch_bounds__(256) void grouped_filter_stream_kernel(const Stream
     float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y;
+    // a rank at or beyond the query's limit (pqv_topk_grouped_expand) walks nothing (block-uniform: nobody is left at the barrier)
+    if (ga.rank_limit && j >= ga.rank_limit[q]) {
+        if (lane == 0) ga.part_cnt[partial_base(a, q, j, wave, 1)] = 0;
+        return;
+    }
     // the query's set and test (block-uniform; every wave of the block passes the barrier before it looks at its range)
     GroupSet gs;
     gs.stage(ga, q, set_v, set_s);

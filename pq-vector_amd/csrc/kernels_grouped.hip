@@ -84,6 +84,11 @@ __global__ __launch_bounds__(256) void grouped_stream_kernel(const StreamArgs a,
     float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.z, j = blockIdx.y;
+    // a rank at or beyond the query's limit (pqv_topk_grouped_expand) walks nothing (block-uniform: nobody is left at the barrier)
+    if (ga.rank_limit && j >= ga.rank_limit[q]) {
+        if (lane == 0) ga.part_cnt[partial_base(a, q, j, wave, 1)] = 0;
+        return;
+    }
     // the query's set (block-uniform; every wave of the block passes the barrier before it looks at its range)
     GroupSet gs;
     gs.stage(ga, q, set_v, set_s);

@@ -1,7 +1,7 @@
 // stream_walk.hpp -- the pieces every streaming distance pass is composed of, each ONCE.  stream_kernel (kernels_probe.hip),
 // masked_stream_kernel (kernels_mask.hip), dot_stream_kernel (kernels_dot.hip), distinct_stream_kernel, grouped_stream_kernel and
-// their filtered forms (kernels_distinct.hip, kernels_grouped.hip, kernels_distinct_filter.hip) and filter_count_kernel
-// (kernels_expand.hip) differ only in where a window's bits come from and what a tile's rows are offered to; everything else is here:
+// their filtered forms (kernels_distinct.hip, kernels_grouped.hip, kernels_distinct_filter.hip), filter_count_kernel
+// (kernels_expand.hip) and group_expand_kernel (kernels_group_expand.hip) differ only in where a window's bits come from and what a tile's rows are offered to; everything else is here:
 //
 //   chain_tile / l2_tile / dot_tile   the distance chain of one 64-row tile, in the reference's order of operations
 //   WalkRange / walk_range            the prologue: probed list, candidate base, cap, the wave's position range
@@ -341,6 +341,12 @@ struct KeyTest {
     }
 };
 
+// The test of a distinct / grouped call's filter (GroupFilterArgs), set up once per block: PQV_KEY_EQ runs as the range [a[q], a[q]].
+__device__ __forceinline__ void group_filter_bounds(const GroupFilterArgs &fa, uint32_t q, KeyTest<1> &kt) {
+    kt.lo = static_cast<const int64_t *>(fa.a)[q];
+    kt.hi = fa.kind == 0 ? kt.lo : static_cast<const int64_t *>(fa.b)[q];
+}
+
 // ------------------------------------------------------------------------------------
 // The k groups pass 1 of a grouped call named (launch_group_set's outputs), staged once per block in LDS beside the tile area:
 // 5 KB, GROUPED_SET_MAX i64 values ascending and their u16 slots.  stage() ends WITHOUT a barrier: the caller passes one before
@@ -460,6 +466,15 @@ __device__ __forceinline__ void write_distinct_lists(const StreamArgs &a, int64_
         if constexpr (GW == 1) part_grp[o] = (int64_t)(int32_t)tk.grp[s][0];
         else part_grp[o] = (int64_t)(((uint64_t)tk.grp[s][1] << 32) | (uint64_t)tk.grp[s][0]);
     });
+}
+
+// a rank at or beyond the query's limit (DistinctArgs::rank_limit): the wave's list goes out EMPTY, as init() leaves it
+__device__ __forceinline__ void write_empty_distinct_list(const StreamArgs &a, int64_t *part_grp, uint64_t base, int lane) {
+    for (uint32_t e = (uint32_t)lane; e < a.k; e += 64) {
+        a.part_keys[base + e] = KEY_EMPTY;
+        a.part_vals[base + e] = 0xFFFFFFFFu;
+        part_grp[base + e] = 0;
+    }
 }
 
 // grouped: MEMBERSHIP of a window's positions in the query's k groups -- lane l reads key_pos[p + l] (one coalesced window, as

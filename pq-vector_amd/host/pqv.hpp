@@ -281,6 +281,43 @@ public:
                                         group_size, nprobe, 0, PQV_L2SQ_REF4, 1, rows.data(), dist.data(), group_keys.data(), group_rows.data(),
                                         found.data(), nullptr));
     }
+    // topk_distinct / topk_grouped probing on until k GROUPS are found (pqv.h: pqv_topk_distinct_expand, pqv_topk_grouped_expand): every
+    // query walks the fewest lists in [nprobe, max_nprobe] that hold k distinct values of this column; used[q] = that many.
+    // filter_keys / filter: both or neither (nullptr: the unfiltered twins)
+    void topk_distinct_expand(const Searcher &s, const RowKeys *filter_keys, const KeyFilter *filter, const std::vector<float> &queries,
+                              uint32_t k, uint32_t nprobe, uint32_t max_nprobe, std::vector<uint32_t> &rows, std::vector<float> &dist,
+                              std::vector<int64_t> &group_keys, std::vector<uint32_t> &found, std::vector<uint32_t> &used,
+                              const RowMask *mask = nullptr) const {
+        const uint32_t nq = s.dim() ? static_cast<uint32_t>(queries.size() / s.dim()) : 0;
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, 0.0f);
+        group_keys.assign(static_cast<size_t>(nq) * k, 0);
+        found.assign(nq, 0);
+        used.assign(nq, 0);
+        pqv_key_filter d{};
+        if (filter) d = filter->descriptor();
+        check(pqv_topk_distinct_expand(s.get(), h_.get(), filter_keys ? filter_keys->get() : nullptr, filter ? &d : nullptr,
+                                       mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, nprobe, max_nprobe, PQV_L2SQ_REF4, 1,
+                                       rows.data(), dist.data(), group_keys.data(), found.data(), nullptr, used.data()));
+    }
+    void topk_grouped_expand(const Searcher &s, const RowKeys *filter_keys, const KeyFilter *filter, const std::vector<float> &queries,
+                             uint32_t k, uint32_t group_size, uint32_t nprobe, uint32_t max_nprobe, std::vector<uint32_t> &rows,
+                             std::vector<float> &dist, std::vector<int64_t> &group_keys, std::vector<uint32_t> &group_rows,
+                             std::vector<uint32_t> &found, std::vector<uint32_t> &used, const RowMask *mask = nullptr) const {
+        const uint32_t nq = s.dim() ? static_cast<uint32_t>(queries.size() / s.dim()) : 0;
+        rows.assign(static_cast<size_t>(nq) * k * group_size, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k * group_size, std::numeric_limits<float>::infinity());
+        group_keys.assign(static_cast<size_t>(nq) * k, 0);
+        group_rows.assign(static_cast<size_t>(nq) * k, 0);
+        found.assign(nq, 0);
+        used.assign(nq, 0);
+        pqv_key_filter d{};
+        if (filter) d = filter->descriptor();
+        check(pqv_topk_grouped_expand(s.get(), h_.get(), filter_keys ? filter_keys->get() : nullptr, filter ? &d : nullptr,
+                                      mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, group_size, nprobe, max_nprobe,
+                                      PQV_L2SQ_REF4, 1, rows.data(), dist.data(), group_keys.data(), group_rows.data(), found.data(), nullptr,
+                                      used.data()));
+    }
 private:
     struct Del { void operator()(pqv_row_keys *p) const { pqv_row_keys_free(p); } };
     std::unique_ptr<pqv_row_keys, Del> h_;
