@@ -203,6 +203,24 @@ impl Index {
         let rows = unsafe { std::slice::from_raw_parts(sys::pqv_index_list_rows(self.raw), sys::pqv_index_n_rows(self.raw) as usize) };
         &rows[off[cluster] as usize..off[cluster + 1] as usize]
     }
+
+    /// `nearest_centroid` (`src/ivf/index.rs:244-257`) of corpus rows `[first_row, first_row + n_rows)` under this index'
+    /// centroids: the lowest index wins a tie, a row no centroid is below +inf from goes to 0.
+    pub fn assign(&self, corpus: &Corpus, first_row: usize, n_rows: usize) -> Result<Vec<u32>> {
+        let mut out = vec![0u32; n_rows];
+        check(unsafe { sys::pqv_index_assign(self.raw, corpus.raw, first_row as u64, n_rows as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// A new index with these centroids whose list `c` is this index' list `c` followed by the rows of
+    /// `[first_row, first_row + n_rows)` assigned to `c`, ascending (`src/ivf/index.rs:189-206` for these centroids over the longer
+    /// column; no k-means).  `first_row` must be at least the largest indexed row id + 1.  `self` is not modified; a searcher over
+    /// the grown corpus is made from the result.
+    pub fn append(&self, corpus: &Corpus, first_row: usize, n_rows: usize) -> Result<Index> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_index_append(self.raw, corpus.raw, first_row as u64, n_rows as u64, &mut raw) })?;
+        Ok(Index { raw })
+    }
 }
 
 impl Drop for Index {

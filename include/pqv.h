@@ -206,6 +206,27 @@ void pqv_corpus_free(pqv_corpus *corpus);
  *                       0 => this host's online CPU count. */
 int pqv_index_build(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
                     uint64_t seed, uint32_t workers, pqv_index **out);
+/* ---- index append: rows that arrived after the build -----------------------------------
+ * The build's last stage (the final assignment of every row to its nearest centroid and the stable per-cluster sort,
+ * src/ivf/index.rs:189-206 + :244-257) depends on the centroids and the rows alone, so it can run for new rows under the centroids an
+ * index already has: no k-means, the partition stays.  Grow the column with pqv_corpus_create(capacity) + pqv_corpus_append, then
+ * append the new range.  Appending onto an index with empty lists (pqv_index_from_parts) indexes a column under a given codebook.
+ * Both calls work on the corpus' stream, like pqv_index_build, and return PQV_ERR_INVALID before any device work for a NULL
+ * argument, a dimension mismatch, a range that ends past pqv_corpus_rows(corpus) or past 2^32, or a released row-order copy.
+ * A searcher is bound to the rows its index covers: pqv_searcher_create still requires a BUILT index to cover exactly the corpus'
+ * rows, so after the corpus grew the old index makes no new searcher (searchers made before keep working on the rows they have);
+ * make the new searcher from the appended index. */
+
+/* nearest_centroid (src/ivf/index.rs:244-257) of corpus rows [first_row, first_row + n_rows) under the index' centroids:
+ * cluster_out[i] = argmin_j squared_l2_distance(row, centroid j), strict '<' from +inf in ascending j (lowest index wins a tie,
+ * a row no centroid is < +inf from goes to 0).  Host output [n_rows]. */
+int pqv_index_assign(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, uint32_t *cluster_out);
+/* A NEW index: the centroids of `index` bit for bit, list c = list c of `index` followed by the rows of
+ * [first_row, first_row + n_rows) assigned to c, ascending -- what index.rs:189-206 leaves for these centroids.  `index` is
+ * not modified and stays valid (it may be shared with live searchers).  first_row must be at least the index' row bound (largest
+ * indexed row id + 1), which keeps every list ascending; rows between the bound and first_row are simply not indexed.
+ * n_rows == 0 yields a copy. */
+int pqv_index_append(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out);
 /* Phase wall times of the calling thread's last pqv_index_build / pqv_index_build_host / pqv_kmeans (bench records):
  * out[0] k-means++ seconds, [1] Lloyd seconds, [2] Lloyd iterations run, [3] final assignment seconds (device work +
  * download), [4] host inverted-list build seconds, [5] 1 if the final assignment ran through the MFMA screen, [6] same for

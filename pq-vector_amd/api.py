@@ -170,8 +170,9 @@ class Corpus:
 class Index:
     """IvfIndex{dim, n_clusters, centroids, inverted_lists} (src/ivf/index.rs:9-14)."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, row_bound=None):
         self._h = handle
+        self._row_bound = row_bound      # largest indexed row id + 1 where it is known by construction (a build, an append)
 
     @classmethod
     def from_bytes(cls, blob):
@@ -239,6 +240,35 @@ class Index:
         off, rows = self.list_offsets, self.list_rows
         return [rows[int(off[i]):int(off[i + 1])] for i in range(self.n_clusters)]
 
+    @property
+    def row_bound(self):
+        """Largest indexed row id + 1 (0 for empty lists): the first row an append may start at."""
+        if self._row_bound is None:
+            rows = self.list_rows
+            self._row_bound = int(rows.max()) + 1 if rows.size else 0
+        return self._row_bound
+
+    def assign(self, corpus, first_row=0, n_rows=None):
+        """Nearest centroid (src/ivf/index.rs:244-257) of corpus rows [first_row, first_row + n_rows) under this index'
+        centroids; n_rows None = to the end of the corpus.  -> uint32 [n_rows]."""
+        if n_rows is None:
+            n_rows = max(corpus.rows - first_row, 0)
+        out = np.empty(n_rows, dtype=np.uint32)
+        _check(_ffi.lib().pqv_index_assign(self._h, corpus._h, first_row, n_rows, out.ctypes.data_as(u32p)))
+        return out
+
+    def append(self, corpus, first_row=None, n_rows=None):
+        """A new Index: these centroids, every list followed by the rows of [first_row, first_row + n_rows) assigned to it,
+        ascending (pqv_index_append).  first_row None = this index' row bound, n_rows None = to the end of the corpus, so
+        `corpus.append(batch); index = index.append(corpus)` is the whole ingest step.  This index is not modified."""
+        if first_row is None:
+            first_row = self.row_bound
+        if n_rows is None:
+            n_rows = max(corpus.rows - first_row, 0)
+        h = vp()
+        _check(_ffi.lib().pqv_index_append(self._h, corpus._h, first_row, n_rows, C.byref(h)))
+        return Index(h, row_bound=first_row + n_rows)
+
     def close(self):
         if self._h:
             _ffi.lib().pqv_index_free(self._h)
@@ -265,6 +295,18 @@ class IndexBuilder:
         self._max_iters = 20
         self._seed = 42
         self._workers = 0
+        self._centroids = None
+
+    def with_centroids(self, index_or_array):
+        """Index the source under a given codebook: the centroids of an Index, or a [k, dim] array.  build(), build_inplace() and
+        build_new() then skip k-means (max_iters, seed and workers are ignored; there is no n_clusters <= rows rule, which
+        is k-means') and return Index.from_parts(dim, centroids, empty lists).append(corpus, 0, n): several files of a
+        table, or several shards, can share one partition."""
+        cent = index_or_array.centroids if isinstance(index_or_array, Index) else np.asarray(index_or_array)
+        if cent.ndim != 2 or cent.shape[0] == 0 or cent.shape[1] == 0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "centroids must be a [k, dim] array with k > 0 and dim > 0")
+        self._centroids = _f32(cent)
+        return self
 
     def n_clusters(self, n_clusters):
         self._n_clusters = n_clusters
@@ -285,8 +327,10 @@ class IndexBuilder:
 
     def _config(self):
         # build_config, src/ivf/parquet.rs:88-102
-        if self._max_iters == 0:
+        if self._max_iters == 0 and self._centroids is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "max_iters must be > 0")
+        if self._centroids is not None and self._n_clusters not in (None, len(self._centroids)):
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"n_clusters {self._n_clusters} does not match the {len(self._centroids)} given centroids")
         if self._n_clusters is not None and self._n_clusters == 0:
             raise PqvError(_ffi.PQV_ERR_INVALID, "n_clusters must be > 0")
         if self._embedding_column is not None and not str(self._embedding_column).strip():
@@ -305,9 +349,13 @@ class IndexBuilder:
 
     def _build_on(self, corpus):
         nc, mi, seed, workers = self._config()
+        if self._centroids is not None:
+            k, dim = self._centroids.shape
+            empty = Index.from_parts(dim, self._centroids, [np.zeros(0, np.uint32)] * k)
+            return empty.append(corpus, 0, corpus.rows)
         h = vp()
         _check(_ffi.lib().pqv_index_build(corpus._h, nc, mi, seed, workers, C.byref(h)))
-        return Index(h)
+        return Index(h, row_bound=corpus.rows)
 
     def _load_parquet(self):
         from . import parquet_io
@@ -351,6 +399,8 @@ class IndexBuilder:
         data = np.asarray(self._source)
         if data.ndim != 2:
             raise PqvError(_ffi.PQV_ERR_INVALID, "Embedding data length must be a multiple of dimension")
+        if self._centroids is not None:
+            return self._build_on(Corpus.upload(data, device=self._device))
         dim = data.shape[1]
         flat = _f32(data).reshape(-1)
         h = vp()

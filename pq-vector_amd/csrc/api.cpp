@@ -260,6 +260,24 @@ struct pqv_index {
     std::vector<uint32_t> &list_rows{rows->host};
     uint64_t n_rows() const { return rows->pending ? rows->n : rows->host.size(); }
     uint64_t permutation_of = 0;      // != 0: the lists are a permutation of [0, permutation_of) by construction (a build's result)
+    // largest indexed row id + 1 (pqv_index_append: new rows start at or above it, so a list extended at its end stays ascending):
+    // set by a build (n) and by an append (first_row + n_rows); an index made from parts or bytes finds it by one host scan on first need
+    mutable std::mutex bound_mu;
+    mutable uint64_t bound = 0;
+    mutable bool bound_known = false;
+    void set_row_bound(uint64_t b) { bound = b; bound_known = true; }
+    bool row_bound(uint64_t *out) const {      // false + fail() if the lists could not be read
+        std::lock_guard<std::mutex> lock(bound_mu);
+        if (!bound_known) {
+            const std::vector<uint32_t> *rv = rows->get();
+            if (!rv) return false;
+            uint64_t b = 0;
+            for (uint32_t r : *rv) b = std::max<uint64_t>(b, static_cast<uint64_t>(r) + 1);
+            bound = b; bound_known = true;
+        }
+        *out = bound;
+        return true;
+    }
     pqv_index() = default;
     pqv_index(const pqv_index &) = delete;
     pqv_index &operator=(const pqv_index &) = delete;
@@ -2377,6 +2395,50 @@ int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uin
     return PQV_OK;
 }
 
+// The final-assignment stage (index.rs:189-201 + :244-257): d_cluster[i] = nearest_centroid of row i of d_rows [n, dim] under
+// d_centroids [k, dim], i in [0, n) -- the f16 contraction where it applies, then the MFMA screen where rows (or centroids) were
+// flagged non-finite, then the exact kernel.  Depends on the centroids and these rows alone: the build calls it over the whole
+// column, pqv_index_assign / pqv_index_append over a row range (d_rows = the range's first row: the three forms index rows and
+// outputs from the base they are given and ask no more alignment of it than a row start has -- 16 bytes where dim % 4 == 0,
+// the scalar loads of the exact kernel otherwise; the non-finite checks read the norms of these n rows only).
+// time_kernels: the build's HIP-event bracket of the contraction kernel (g_build_stats[8], [9]).  t0: the caller's clock origin of
+// the PQV_VERBOSE lines.  *exact: the exact kernel ran; *form: 2.0 where the f16 contraction decided.
+int assign_rows(const float *d_rows, uint64_t n, uint32_t dim, const float *d_centroids, uint32_t k, uint32_t *d_cluster,
+                hipStream_t stream, bool time_kernels, double t0, bool *exact, double *form) {
+    using namespace pqv;
+    bool exact_assign = true;
+    if (GemmAssign::applicable(dim, k)) {
+        GemmAssign gemm;
+        bool bad_c = false, bad_r = false;
+        if (int rc = gemm.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
+        if (verbose()) std::fprintf(stderr, "[pqv] final assignment: centroids set at %.1f ms\n", (now_s() - t0) * 1e3);
+        if (!bad_c) {
+            // (chunk-wise downloads behind the next chunk's kernels were measured and dropped: a device-to-pageable copy on a
+            //  second stream stalls the compute stream's queue -- 53 ms for the loop against 34 ms of kernels on C3)
+            gemm.time_kernels = time_kernels;
+            if (int rc = gemm.run(d_rows, n, d_cluster, stream, &bad_r, nullptr)) return rc;
+            exact_assign = bad_r;
+        }
+        HIP_TRY(hipStreamSynchronize(stream));     // the context's buffers are released at scope exit
+        if (!exact_assign) *form = 2.0;
+        if (verbose()) std::fprintf(stderr, "[pqv] final assignment: f16 path done at %.1f ms\n", (now_s() - t0) * 1e3);
+    }
+    if (exact_assign && ScreenedAssign::applicable(dim, k)) {
+        ScreenedAssign screen;
+        bool bad_c = false, bad_r = false;
+        if (int rc = screen.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
+        if (!bad_c) {
+            if (int rc = screen.run(d_rows, n, d_cluster, stream, &bad_r)) return rc;
+            exact_assign = bad_r;
+        }
+        HIP_TRY(hipStreamSynchronize(stream));     // the context's buffers are released at scope exit
+    }
+    if (exact_assign)
+        HIP_TRY(launch_assign(d_rows, n, dim, d_centroids, k, d_cluster, nullptr, nullptr, nullptr, stream));
+    *exact = exact_assign;
+    return PQV_OK;
+}
+
 int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
                      uint64_t seed, uint32_t workers, pqv_index **out) {
     using namespace pqv;
@@ -2438,38 +2500,12 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
             });
         } catch (const std::system_error &) { }
     }
-    bool exact_assign = true, downloaded = false;
+    bool exact_assign = true;
+    const bool downloaded = false;
     double assign_form = 0.0;
-    if (GemmAssign::applicable(dim, static_cast<uint32_t>(k))) {
-        GemmAssign gemm;
-        bool bad_c = false, bad_r = false;
-        if (int rc = gemm.set_centroids(d_centroids.as<float>(), static_cast<uint32_t>(k), dim, stream, &bad_c)) return rc;
-        if (verbose()) std::fprintf(stderr, "[pqv] final assignment: centroids set at %.1f ms\n", (now_s() - t_fa0) * 1e3);
-        if (!bad_c) {
-            // (chunk-wise downloads behind the next chunk's kernels were measured and dropped: a device-to-pageable copy on a
-            //  second stream stalls the compute stream's queue -- 53 ms for the loop against 34 ms of kernels on C3)
-            gemm.time_kernels = true;
-            if (int rc = gemm.run(corpus->d_rows, n, d_cluster.as<uint32_t>(), stream, &bad_r, nullptr)) return rc;
-            exact_assign = bad_r;
-            downloaded = false;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));     // the context's buffers are released at scope exit
-        if (!exact_assign) assign_form = 2.0;
-        if (verbose()) std::fprintf(stderr, "[pqv] final assignment: f16 path done at %.1f ms\n", (now_s() - t_fa0) * 1e3);
-    }
-    if (exact_assign && ScreenedAssign::applicable(dim, static_cast<uint32_t>(k))) {
-        ScreenedAssign screen;
-        bool bad_c = false, bad_r = false;
-        if (int rc = screen.set_centroids(d_centroids.as<float>(), static_cast<uint32_t>(k), dim, stream, &bad_c)) return rc;
-        if (!bad_c) {
-            if (int rc = screen.run(corpus->d_rows, n, d_cluster.as<uint32_t>(), stream, &bad_r)) return rc;
-            exact_assign = bad_r;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));     // the context's buffers are released at scope exit
-    }
-    if (exact_assign)
-        HIP_TRY(launch_assign(corpus->d_rows, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k),
-                              d_cluster.as<uint32_t>(), nullptr, nullptr, nullptr, stream));
+    if (int rc = assign_rows(corpus->d_rows, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(), stream,
+                             true, t_fa0, &exact_assign, &assign_form))
+        return rc;
     // the lists: sorted on the device (the rows of a list ascending, index.rs:193-206), then ONE download of the sorted row ids
     // in place of the assignment's download + the host threads' counting sort
     DeviceLists dlists;
@@ -2528,6 +2564,7 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
         idx->rows->pending = true;
     }
     idx->permutation_of = n;                        // every row was assigned exactly once
+    idx->set_row_bound(n);
     g_build_stats[3] = t_fa1 - t_fa0; g_build_stats[4] = now_s() - t_fa1; g_build_stats[5] = assign_form > 0.0 ? assign_form : exact_assign ? 0.0 : 1.0;
     g_build_stats[7] = static_cast<double>(sample_size);
     if (verbose()) std::fprintf(stderr, "[pqv] final assignment: %llu rows in %.3f s (+ %.3f s host list build)\n",
@@ -2553,6 +2590,201 @@ static int pqv_index_build_impl(const pqv_corpus *corpus, uint32_t n_clusters, u
 extern "C" int pqv_index_build(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
                                uint64_t seed, uint32_t workers, pqv_index **out) {
     return guard([&] { return pqv_index_build_impl(corpus, n_clusters, max_iters, seed, workers, out); });
+}
+
+// ---------------------------------------------------------------------------------------
+// pqv_index_assign / pqv_index_append: rows that arrived after the build join the index under its centroids
+// (index.rs:189-206 + :244-257 for those centroids over the longer column; no k-means)
+// ---------------------------------------------------------------------------------------
+namespace {
+
+// the checks the two calls share, before any device work
+int check_row_range(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows) {
+    if (index->dim != corpus->dim)
+        return fail(PQV_ERR_INVALID, "index dimension " + std::to_string(index->dim) +
+                                         " does not match corpus dimension " + std::to_string(corpus->dim));
+    if (n_rows > corpus->n || first_row > corpus->n - n_rows)
+        return fail(PQV_ERR_INVALID, "rows [" + std::to_string(first_row) + ", " + std::to_string(first_row) + " + " + std::to_string(n_rows) +
+                                         ") are out of range for a corpus of " + std::to_string(corpus->n) + " rows");
+    if (first_row + n_rows > (1ull << 32)) return fail(PQV_ERR_INVALID, "row ids must fit in u32");
+    if (!corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
+    return PQV_OK;
+}
+
+// the index' centroids on the corpus' device + the assignment of the range: d_cluster[i] = cluster of row first_row + i
+int assign_range(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, DevBuf &d_centroids,
+                 DevBuf &d_cluster) {
+    hipStream_t stream = corpus->stream;
+    HIP_TRY(d_centroids.alloc(index->centroids.size() * sizeof(float)));
+    HIP_TRY(d_cluster.alloc(n_rows * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpyAsync(d_centroids.p, index->centroids.data(), index->centroids.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    bool exact = false;
+    double form = 0.0;
+    return assign_rows(corpus->d_rows + first_row * corpus->dim, n_rows, corpus->dim, d_centroids.as<float>(), index->n_clusters,
+                       d_cluster.as<uint32_t>(), stream, false, now_s(), &exact, &form);
+}
+
+int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, uint32_t *cluster_out) {
+    if (!index || !corpus) return fail(PQV_ERR_INVALID, "index/corpus must not be NULL");
+    if (!cluster_out) return fail(PQV_ERR_INVALID, "cluster_out must not be NULL");
+    if (int rc = check_row_range(index, corpus, first_row, n_rows)) return rc;
+    if (n_rows == 0) return PQV_OK;
+    if (int rc = use_device(corpus->device)) return rc;
+    DevBuf d_centroids, d_cluster;
+    if (int rc = assign_range(index, corpus, first_row, n_rows, d_centroids, d_cluster)) return rc;
+    HIP_TRY(hipMemcpyAsync(cluster_out, d_cluster.p, n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, corpus->stream));
+    HIP_TRY(hipStreamSynchronize(corpus->stream));
+    return PQV_OK;
+}
+
+int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out) {
+    using namespace pqv;
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!index || !corpus) return fail(PQV_ERR_INVALID, "index/corpus must not be NULL");
+    if (int rc = check_row_range(index, corpus, first_row, n_rows)) return rc;
+    uint64_t bound = 0;
+    if (!index->row_bound(&bound)) return PQV_ERR_HIP;
+    if (first_row < bound)
+        return fail(PQV_ERR_INVALID, "first_row " + std::to_string(first_row) + " is below the index' row bound " + std::to_string(bound) +
+                                         " (largest indexed row id + 1): appended rows must follow every indexed row");
+    const uint32_t k = index->n_clusters;
+    const uint64_t n_old = index->n_rows(), total = n_old + n_rows;
+    std::unique_ptr<pqv_index> idx(new pqv_index());
+    idx->dim = index->dim; idx->n_clusters = k;
+    idx->centroids = index->centroids;              // bit for bit
+    idx->set_row_bound(first_row + n_rows);
+    idx->permutation_of = index->permutation_of == first_row ? first_row + n_rows : 0;
+    if (n_rows == 0) {                              // a copy
+        const std::vector<uint32_t> *rv = index->rows->get();
+        if (!rv) return PQV_ERR_HIP;
+        idx->list_off = index->list_off;
+        idx->list_rows = *rv;
+        *out = idx.release();
+        return PQV_OK;
+    }
+    if (int rc = use_device(corpus->device)) return rc;
+    hipStream_t stream = corpus->stream;
+    // PQV_APPEND_STATS=1 (diagnostic, read per call): the wall time of the two phases (the stream is drained between them), the splice
+    // kernel between two HIP events and a plain device-to-device copy of the same bytes behind it, on stderr
+    const bool stats = std::getenv("PQV_APPEND_STATS") != nullptr;
+    const double t0 = now_s();
+    DevBuf d_centroids, d_cluster;
+    if (int rc = assign_range(index, corpus, first_row, n_rows, d_centroids, d_cluster)) return rc;
+    if (stats) HIP_TRY(hipStreamSynchronize(stream));
+    const double t1 = now_s();
+
+    if (!DeviceLists::applicable(n_rows, k)) {
+        // more than 4096 clusters (or PQV_DEVICE_LISTS=0): the range's assignment comes to the host, and every list is its old rows
+        // followed by its new ones in ascending order -- lists_from_assignment's rule over the range, behind the old lists
+        std::vector<uint32_t> cluster_of(n_rows);
+        HIP_TRY(hipMemcpyAsync(cluster_of.data(), d_cluster.p, n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        std::vector<uint64_t> add_off;
+        std::vector<uint32_t> add_rows;
+        if (!lists_from_assignment(cluster_of.data(), n_rows, k, add_off, add_rows))
+            return fail(PQV_ERR_HIP, "internal error: final assignment out of range");
+        const std::vector<uint32_t> *rv = index->rows->get();
+        if (!rv) return PQV_ERR_HIP;
+        idx->list_off.resize(static_cast<size_t>(k) + 1);
+        idx->list_rows.resize(total);
+        uint32_t *dst = idx->list_rows.data();
+        for (uint32_t c = 0; c < k; ++c) {
+            const uint64_t ob = index->list_off[c], ol = index->list_off[c + 1] - ob, ab = add_off[c], al = add_off[c + 1] - ab;
+            idx->list_off[c] = ob + ab;
+            if (ol) std::memcpy(dst + ob + ab, rv->data() + ob, ol * sizeof(uint32_t));
+            for (uint64_t i = 0; i < al; ++i) dst[ob + ab + ol + i] = static_cast<uint32_t>(first_row + add_rows[ab + i]);
+        }
+        idx->list_off[k] = total;
+        *out = idx.release();
+        return PQV_OK;
+    }
+
+    // the range's rows sorted by cluster on the device (ids local to the range), then ONE pass writes the extended lists
+    DeviceLists dlists;
+    DevBuf d_add_rows, d_add_off, d_old_off, d_old_up, d_out_rows, d_out_off;
+    if (int rc = dlists.prepare(n_rows, k)) return rc;
+    HIP_TRY(d_add_rows.alloc(n_rows * sizeof(uint32_t)));
+    HIP_TRY(d_add_off.alloc((static_cast<size_t>(k) + 1) * sizeof(uint64_t)));
+    if (int rc = dlists.run(d_cluster.as<uint32_t>(), n_rows, k, d_add_off.as<uint64_t>(), d_add_rows.as<uint32_t>(), stream)) return rc;
+    HIP_TRY(d_old_off.alloc((static_cast<size_t>(k) + 1) * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpyAsync(d_old_off.p, index->list_off.data(), (static_cast<size_t>(k) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    // the old lists: the index' device copy where it lives on this device (a build's or an append's result), else one upload
+    const uint32_t *d_old = nullptr;
+    std::shared_ptr<DevRows> old_dev = index->rows->dev;          // (kept alive over the kernel)
+    if (n_old) {
+        if (old_dev && old_dev->p && old_dev->device == corpus->device && old_dev->n == n_old) {
+            d_old = static_cast<const uint32_t *>(old_dev->p);
+        } else {
+            const std::vector<uint32_t> *rv = index->rows->get();
+            if (!rv) return PQV_ERR_HIP;
+            HIP_TRY(d_old_up.alloc(n_old * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpyAsync(d_old_up.p, rv->data(), n_old * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            d_old = d_old_up.as<uint32_t>();
+        }
+    }
+    HIP_TRY(d_out_rows.alloc(total * sizeof(uint32_t)));
+    HIP_TRY(d_out_off.alloc((static_cast<size_t>(k) + 1) * sizeof(uint64_t)));
+    struct Events { hipEvent_t e[4] = {}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
+    DevBuf d_copy;
+    if (stats) {
+        for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(d_copy.alloc(total * sizeof(uint32_t)));
+        HIP_TRY(hipEventRecord(ev.e[0], stream));
+    }
+    HIP_TRY(launch_list_splice(d_old_off.as<uint64_t>(), d_old, d_add_off.as<uint64_t>(), d_add_rows.as<uint32_t>(), k,
+                               static_cast<uint32_t>(first_row), total, d_out_off.as<uint64_t>(), d_out_rows.as<uint32_t>(), stream));
+    if (stats) {
+        HIP_TRY(hipEventRecord(ev.e[1], stream));
+        HIP_TRY(hipEventRecord(ev.e[2], stream));
+        HIP_TRY(hipMemcpyAsync(d_copy.p, d_out_rows.p, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipEventRecord(ev.e[3], stream));
+    }
+    uint32_t h_bad = 0;
+    static const bool keep_dev = [] { const char *e = std::getenv("PQV_KEEP_DEVICE_LISTS"); return !(e && *e == '0'); }();
+    idx->list_off.resize(static_cast<size_t>(k) + 1);
+    if (!keep_dev) {
+        idx->list_rows.resize(total);
+        HIP_TRY(hipMemcpyAsync(idx->list_rows.data(), d_out_rows.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipMemcpyAsync(idx->list_off.data(), d_out_off.p, (static_cast<size_t>(k) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_bad, dlists.bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (h_bad != 0) return fail(PQV_ERR_HIP, "internal error: final assignment out of range");
+    if (keep_dev) {
+        // as a build leaves them: the lists stay on the device (a searcher here takes them device to device), the host copy is
+        // made by the first call that reads it
+        auto dr = std::make_shared<DevRows>();
+        dr->p = d_out_rows.p; dr->device = corpus->device; dr->n = total;
+        d_out_rows.p = nullptr; d_out_rows.bytes = 0;
+        idx->rows->dev = std::move(dr);
+        idx->rows->n = total;
+        idx->rows->host.clear();
+        idx->rows->pending = true;
+    }
+    if (stats) {
+        float ms_splice = 0.0f, ms_copy = 0.0f;
+        (void)hipEventElapsedTime(&ms_splice, ev.e[0], ev.e[1]);
+        (void)hipEventElapsedTime(&ms_copy, ev.e[2], ev.e[3]);
+        const double bytes = static_cast<double>(total) * sizeof(uint32_t);
+        std::fprintf(stderr, "pqv_index_append: %llu rows onto %llu: assignment %.3f ms, lists %.3f ms; splice kernel %.4f ms for %.0f list bytes "
+                             "(%.1f GB/s written), device-to-device copy of the same bytes %.4f ms\n",
+                     (unsigned long long)n_rows, (unsigned long long)n_old, (t1 - t0) * 1e3, (now_s() - t1) * 1e3, ms_splice, bytes,
+                     ms_splice > 0.0f ? bytes / (ms_splice * 1e6) : 0.0, ms_copy);
+    }
+    *out = idx.release();
+    return PQV_OK;
+}
+
+}  // namespace
+
+extern "C" int pqv_index_assign(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows,
+                                uint32_t *cluster_out) {
+    return guard([&] { return index_assign_impl(index, corpus, first_row, n_rows, cluster_out); });
+}
+extern "C" int pqv_index_append(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows,
+                                pqv_index **out) {
+    return guard([&] { return index_append_impl(index, corpus, first_row, n_rows, out); });
 }
 
 static int pqv_kpp_pick_impl(int device, const float *minima, uint32_t n, uint32_t workers, float draw, uint64_t *pick, float *total,

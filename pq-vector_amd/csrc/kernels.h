@@ -816,6 +816,12 @@ hipError_t launch_nonfinite_flag(const float *v, uint64_t n, uint32_t *flag, hip
 // rows_per_block a multiple of 256.
 hipError_t launch_list_sort(const uint32_t *assign, uint64_t n, uint32_t k, uint32_t *cnt, uint32_t rows_per_block,
                             unsigned long long *tot, uint64_t *list_off, uint32_t *list_rows, uint32_t *bad, hipStream_t s);
+// The lists of an index extended by a sorted range of new rows (kernels_append.hip: list_splice_kernel; pqv_index_append):
+// out_off[c] = old_off[c] + add_off[c] for c in [0, k], out_rows[out_off[c] ..) = old list c verbatim, then first_row + add_rows[add_off[c] ..)
+// (add_off / add_rows: launch_list_sort over the range, ids local to it).  total = old_off[k] + add_off[k] entries of out_rows (16-byte
+// aligned); old_rows may be NULL where the old lists are empty.  k <= 4096.
+hipError_t launch_list_splice(const uint64_t *old_off, const uint32_t *old_rows, const uint64_t *add_off, const uint32_t *add_rows,
+                              uint32_t k, uint32_t first_row, uint64_t total, uint64_t *out_off, uint32_t *out_rows, hipStream_t s);
 hipError_t launch_count_changed(const uint32_t *cur, const uint32_t *prev, uint64_t n, unsigned long long *changed, hipStream_t s);
 
 // pqv_rerank's running state <-> merge lists (see kernels_layout.hip)
