@@ -563,28 +563,46 @@ struct pqv_row_keys {
     mutable std::vector<int64_t> host_vals;      // [n_rows], widened
     mutable std::vector<uint8_t> host_valid;     // [n_rows] (has_valid)
     mutable std::atomic<bool> host_ready{false};
+    uint32_t elem_size() const { return dtype == PQV_COL_I32 ? 4u : 8u; }
+    const uint64_t *valid_image() const { return has_valid ? d_valid_pos.as<uint64_t>() : nullptr; }
 };
-// what a masked or keyed call hands down (nullptr: the unfiltered call)
-struct MaskView {
-    const uint64_t *bits;              // device image of the call's row mask (a keyed call: of its shared mask, or nullptr)
+// What a search call carries beside its queries (nullptr: the plain call), in three independent parts.  The *_view functions fill
+// it; the host bodies point a copy at each sub-batch's device arguments.
+struct RowSelection {                  // which rows a query may return
+    const uint64_t *bits;              // device image of the call's shared row mask, or nullptr
     const pqv_row_mask *mask;          // (the row-order bytes are fetched at the replay site: mask_host_bytes)
-    const pqv_row_keys *keys;          // a keyed call's key column, else nullptr
-    const int64_t *h_qkeys;            // host forms: [nq] query keys, indexed like the call's queries
-    const int64_t *d_qkeys;            // device: the keys of the queries the kernels see (the current sub-batch's)
-    uint32_t fkind;                    // a filtered call (pqv_key_filter) of kind PQV_KEY_RANGE / PQV_KEY_IN, else 0 (PQV_KEY_EQ travels as h_qkeys / d_qkeys)
-    const void *h_fa, *h_fb;           // its host a / b, indexed like the call's queries (IN: lims [nq + 1] and the values)
-    const void *d_fa, *d_fb;           // device: a / b of the queries the kernels see (IN: lims rebased to the current sub-batch)
-    const pqv_row_keys *group;         // a distinct call's group column, else nullptr (bits / mask: its shared mask, or nullptr)
-    int64_t *d_group_out;              // distinct: where the fold writes the group values [nq * k] (device), or nullptr
-    uint32_t group_size;               // a grouped call (pqv_topk_grouped; `group` set): rows per group, >= 1; 0: not grouped.  The call's row_idx / dist are
-                                       // [nq, k, group_size]
-    uint32_t *d_group_rows;            // grouped: where the rows per group go [nq * k] (device), or nullptr
-    uint32_t max_nprobe;               // an expanding call (pqv_topk_expand): the lists the probe ranks per query, >= the call's nprobe; 0: not expanding
-    uint32_t *d_nprobe_used;           // expanding: where the lists each query used go [nq] (device), or nullptr (the lane's scratch)
-    uint32_t *h_nprobe_used;           // expanding host form: the caller's [nq], or nullptr
+    const pqv_row_keys *keys;          // the key column of a per-query key filter, else nullptr
+    uint32_t kind;                     // PQV_KEY_RANGE / PQV_KEY_IN; 0: PQV_KEY_EQ, which travels as the query-key arrays below, not as a / b
+    const int64_t *h_qkeys;            // EQ, host form: [nq] query keys, indexed like the call's queries
+    const int64_t *d_qkeys;            // EQ, device: the keys of the queries the kernels see (the current sub-batch's)
+    const void *h_a, *h_b;             // RANGE / IN, host a / b, indexed like the call's queries (IN: lims [nq + 1] and the values)
+    const void *d_a, *d_b;             // device: a / b of the queries the kernels see (IN: lims rebased to the current sub-batch)
+};
+struct Grouping {                      // a distinct / grouped call
+    const pqv_row_keys *col;           // the group column, else nullptr
+    uint32_t size;                     // pqv_topk_grouped: rows per group, >= 1 (the call's row_idx / dist are [nq, k, size]); 0: not grouped
+    int64_t *d_keys;                   // where the fold writes the group values [nq * k] (device), or nullptr
+    uint32_t *d_rows;                  // grouped: where the rows per group go [nq * k] (device), or nullptr
+};
+struct Expansion {                     // an expanding call (pqv_topk_expand)
+    uint32_t max_nprobe;               // the lists the probe ranks per query, >= the call's nprobe; 0: not expanding
+    uint32_t *d_used;                  // where the lists each query used go [nq] (device), or nullptr (the lane's scratch)
+    uint32_t *h_used;                  // host form: the caller's [nq], or nullptr
+};
+struct SearchRequest {
+    RowSelection rows;
+    Grouping groups;
+    Expansion expand;
+    bool filtered() const { return rows.keys != nullptr; }                 // a per-query key filter of any kind ...
+    bool eq_keys() const { return rows.keys && !rows.kind; }               // ... of kind PQV_KEY_EQ
+    bool distinct() const { return groups.col != nullptr; }
+    bool expanding() const { return expand.max_nprobe != 0; }
+    // a filtered call's per-query arguments as the kernels read them
+    const void *d_filter_a() const { return rows.kind ? rows.d_a : rows.d_qkeys; }
+    const void *d_filter_b() const { return rows.kind ? rows.d_b : nullptr; }
 };
 // the lists the probe of a call ranks per query: an expanding call's max_nprobe, else its nprobe
-static inline uint32_t probe_arg(const MaskView *mv, uint32_t nprobe) { return mv && mv->max_nprobe ? mv->max_nprobe : nprobe; }
+static inline uint32_t probe_arg(const SearchRequest *mv, uint32_t nprobe) { return mv && mv->expanding() ? mv->expand.max_nprobe : nprobe; }
 // a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
 static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
     const uint64_t n_words = (m->n_rows + 63) / 64;
@@ -598,10 +616,10 @@ static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
 // The row-order allow bytes of a masked call's mask (nullptr for an unmasked call).  A predicate mask downloads its row image
 // (n_rows / 8 bytes) once and expands it on the host; threads that arrive together wait for the first.  The row image was complete
 // when the mask's creation returned, so the copy orders behind nothing.
-static int mask_host_bytes(const MaskView *mv, const uint8_t **out) {
+static int mask_host_bytes(const SearchRequest *mv, const uint8_t **out) {
     *out = nullptr;
-    if (!mv || !mv->mask) return PQV_OK;
-    const pqv_row_mask *m = mv->mask;
+    if (!mv || !mv->rows.mask) return PQV_OK;
+    const pqv_row_mask *m = mv->rows.mask;
     if (!m->host_ready.load(std::memory_order_acquire)) {
         std::lock_guard<std::mutex> lock(m->host_mu);
         if (!m->host_ready.load(std::memory_order_relaxed)) {
@@ -623,7 +641,7 @@ static int keys_host_rows(const pqv_searcher *s, const pqv_row_keys *kk) {
     const std::vector<uint32_t> *h_rows = s->h_rows->get();
     if (!h_rows) return PQV_ERR_HIP;
     const uint64_t n_pos = std::min<uint64_t>(kk->n_pos, h_rows->size());
-    const size_t es = kk->dtype == PQV_COL_I32 ? 4 : 8;
+    const size_t es = kk->elem_size();
     std::vector<uint8_t> pos_vals;
     std::vector<uint64_t> pos_valid;
     try {
@@ -668,41 +686,41 @@ struct RowFilter {
         return true;
     }
 };
-static int row_filter(const pqv_searcher *s, const MaskView *mv, uint64_t q, RowFilter &f) {
+static int row_filter(const pqv_searcher *s, const SearchRequest *mv, uint64_t q, RowFilter &f) {
     f = RowFilter{};
     if (!mv) return PQV_OK;
     if (int rc = mask_host_bytes(mv, &f.allow)) return rc;
-    if (mv->keys) {
-        if (int rc = keys_host_rows(s, mv->keys)) return rc;
-        f.key_vals = mv->keys->host_vals.data();
-        f.key_valid = mv->keys->has_valid ? mv->keys->host_valid.data() : nullptr;
-        f.kind = mv->fkind;
-        if (mv->fkind == PQV_KEY_RANGE) {
-            f.qkey = static_cast<const int64_t *>(mv->h_fa)[q];
-            f.qhi = static_cast<const int64_t *>(mv->h_fb)[q];
-        } else if (mv->fkind == PQV_KEY_IN) {
-            const uint64_t *lims = static_cast<const uint64_t *>(mv->h_fa);
-            f.set_beg = static_cast<const int64_t *>(mv->h_fb) + lims[q];
-            f.set_end = static_cast<const int64_t *>(mv->h_fb) + lims[q + 1];
+    if (mv->rows.keys) {
+        if (int rc = keys_host_rows(s, mv->rows.keys)) return rc;
+        f.key_vals = mv->rows.keys->host_vals.data();
+        f.key_valid = mv->rows.keys->has_valid ? mv->rows.keys->host_valid.data() : nullptr;
+        f.kind = mv->rows.kind;
+        if (mv->rows.kind == PQV_KEY_RANGE) {
+            f.qkey = static_cast<const int64_t *>(mv->rows.h_a)[q];
+            f.qhi = static_cast<const int64_t *>(mv->rows.h_b)[q];
+        } else if (mv->rows.kind == PQV_KEY_IN) {
+            const uint64_t *lims = static_cast<const uint64_t *>(mv->rows.h_a);
+            f.set_beg = static_cast<const int64_t *>(mv->rows.h_b) + lims[q];
+            f.set_end = static_cast<const int64_t *>(mv->rows.h_b) + lims[q + 1];
         } else {
-            f.qkey = mv->h_qkeys[q];
+            f.qkey = mv->rows.h_qkeys[q];
         }
     }
     return PQV_OK;
 }
 // A keyed or filtered host call's per-query arguments for the sub-batch [q0, q0 + b): uploaded on `st` into the lane's scratch,
 // `sub` pointed at them.  `lims` keeps an IN filter's rebased offsets alive until the sub-batch's synchronisation.
-static int upload_query_filter(Scratch &sc, const MaskView *mask, MaskView &sub, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
+static int upload_query_filter(Scratch &sc, const SearchRequest *rq, SearchRequest &sub, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
                                hipStream_t st) {
-    if (!mask || !mask->keys) return PQV_OK;
-    if (mask->fkind == PQV_KEY_RANGE) {
+    if (!rq || !rq->filtered()) return PQV_OK;
+    if (rq->rows.kind == PQV_KEY_RANGE) {
         HIP_TRY(sc.s_qfilt_a.ensure(static_cast<size_t>(b) * sizeof(int64_t)));
         HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(b) * sizeof(int64_t)));
-        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, static_cast<const int64_t *>(mask->h_fa) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(mask->h_fb) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        sub.d_fa = sc.s_qfilt_a.p; sub.d_fb = sc.s_qfilt_b.p;
-    } else if (mask->fkind == PQV_KEY_IN) {
-        const uint64_t *hl = static_cast<const uint64_t *>(mask->h_fa);
+        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, static_cast<const int64_t *>(rq->rows.h_a) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(rq->rows.h_b) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        sub.rows.d_a = sc.s_qfilt_a.p; sub.rows.d_b = sc.s_qfilt_b.p;
+    } else if (rq->rows.kind == PQV_KEY_IN) {
+        const uint64_t *hl = static_cast<const uint64_t *>(rq->rows.h_a);
         const uint64_t base = hl[q0], n_vals = hl[q0 + b] - base;
         try { lims.resize(static_cast<size_t>(b) + 1); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
         for (uint32_t i = 0; i <= b; ++i) lims[i] = hl[q0 + i] - base;
@@ -710,46 +728,44 @@ static int upload_query_filter(Scratch &sc, const MaskView *mask, MaskView &sub,
         HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(n_vals) * sizeof(int64_t)));
         HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, lims.data(), (static_cast<size_t>(b) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         if (n_vals)
-            HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(mask->h_fb) + base, static_cast<size_t>(n_vals) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        sub.d_fa = sc.s_qfilt_a.p; sub.d_fb = sc.s_qfilt_b.p;
+            HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(rq->rows.h_b) + base, static_cast<size_t>(n_vals) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        sub.rows.d_a = sc.s_qfilt_a.p; sub.rows.d_b = sc.s_qfilt_b.p;
     } else {
-        HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, mask->h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        sub.d_qkeys = sc.s_qkeys.as<int64_t>();
+        HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, rq->rows.h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        sub.rows.d_qkeys = sc.s_qkeys.as<int64_t>();
     }
     return PQV_OK;
 }
-// the per-query filter of a distinct / grouped call that has one (mv->keys beside mv->group), as its kernels read it
-static pqv::GroupFilterArgs group_filter_args(const MaskView *mv) {
-    const pqv_row_keys *kk = mv->keys;
-    return pqv::GroupFilterArgs{kk->d_key_pos.p, kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr, kk->dtype == PQV_COL_I32 ? 4u : 8u,
-                                mv->fkind, mv->fkind ? mv->d_fa : mv->d_qkeys, mv->fkind ? mv->d_fb : nullptr};
+// the per-query filter of a distinct / grouped call that has one (mv->filtered() beside mv->distinct()), as its kernels read it
+static pqv::GroupFilterArgs group_filter_args(const SearchRequest *mv) {
+    const pqv_row_keys *kk = mv->rows.keys;
+    return pqv::GroupFilterArgs{kk->d_key_pos.p, kk->valid_image(), kk->elem_size(), mv->rows.kind, mv->d_filter_a(), mv->d_filter_b()};
 }
-// the STREAM_TOPK / STREAM_RANGE pass of a masked or keyed call
-// (a distinct call: STREAM_TOPK only, the per-wave lists' group values go to part_grp)
-static hipError_t launch_filtered_stream(const pqv::StreamArgs &ra, const MaskView *mv, unsigned long long *stats, const uint64_t *n_cand,
-                                         pqv::StreamMode mode, hipStream_t stream, int64_t *part_grp = nullptr,
-                                         const uint32_t *rank_limit = nullptr) {
-    if (mv->group) {
+// The STREAM_TOPK / STREAM_RANGE pass of any call: the plain one (rq == nullptr; stats and n_cand unused: the probe merge counts),
+// PQV_DOT, masked, keyed / filtered, and distinct (STREAM_TOPK only, the per-wave lists' group values go to part_grp)
+static hipError_t launch_stream_pass(const pqv::StreamArgs &ra, const SearchRequest *rq, unsigned long long *stats, const uint64_t *n_cand,
+                                     pqv::StreamMode mode, hipStream_t stream, int64_t *part_grp = nullptr,
+                                     const uint32_t *rank_limit = nullptr) {
+    if (!rq) return ra.metric == PQV_DOT ? pqv::launch_dot_stream(ra, nullptr, mode, stream) : pqv::launch_stream(ra, mode, stream);
+    if (rq->distinct()) {
         if (mode != pqv::STREAM_TOPK) return hipErrorInvalidValue;
-        const pqv_row_keys *gk = mv->group;
-        const pqv::DistinctArgs da{mv->bits, stats, n_cand, gk->d_key_pos.p, gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr,
-                                   gk->dtype == PQV_COL_I32 ? 4u : 8u, part_grp, rank_limit};
-        if (mv->keys) return pqv::launch_distinct_filter_stream(ra, da, group_filter_args(mv), stream);
+        const pqv_row_keys *gk = rq->groups.col;
+        const pqv::DistinctArgs da{rq->rows.bits, stats, n_cand, gk->d_key_pos.p, gk->valid_image(), gk->elem_size(), part_grp, rank_limit};
+        if (rq->filtered()) return pqv::launch_distinct_filter_stream(ra, da, group_filter_args(rq), stream);
         return pqv::launch_distinct_stream(ra, da, stream);
     }
-    if (mv->keys) {
-        const pqv_row_keys *kk = mv->keys;
-        const pqv::KeyedArgs ka{mv->bits, stats, n_cand, kk->d_key_pos.p, kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr,
-                                mv->d_qkeys, kk->dtype == PQV_COL_I32 ? 4u : 8u, rank_limit};
-        if (mv->fkind) {
+    if (rq->filtered()) {
+        const pqv_row_keys *kk = rq->rows.keys;
+        const pqv::KeyedArgs ka{rq->rows.bits, stats, n_cand, kk->d_key_pos.p, kk->valid_image(), rq->rows.d_qkeys, kk->elem_size(), rank_limit};
+        if (rq->rows.kind) {
             pqv::KeyFilterArgs fa{};
             static_cast<pqv::KeyedArgs &>(fa) = ka;
-            fa.kind = mv->fkind; fa.a = mv->d_fa; fa.b = mv->d_fb;
+            fa.kind = rq->rows.kind; fa.a = rq->rows.d_a; fa.b = rq->rows.d_b;
             return pqv::launch_key_filter_stream(ra, fa, mode, stream);
         }
         return pqv::launch_keyed_stream(ra, ka, mode, stream);
     }
-    const pqv::MaskedArgs ma{mv->bits, stats, n_cand, rank_limit};
+    const pqv::MaskedArgs ma{rq->rows.bits, stats, n_cand, rank_limit};
     if (ra.metric == PQV_DOT) return pqv::launch_dot_stream(ra, &ma, mode, stream);
     return pqv::launch_masked_stream(ra, ma, mode, stream);
 }
@@ -3576,6 +3592,10 @@ static bool defer_on(const pqv_searcher *s, uint32_t nq, uint32_t k, const TopkP
     if (s->opt.defer != 2 && mean_len > 1536 && prefer_regular(s)) return false;
     return nq >= 8 && p.i8 && p.block_waves == 4 && p.quad_width == 96 && s->sdim >= 512 && (s->opt.defer == 2 || mean_len <= 3072);
 }
+// ... on the wide screened path, where a query's candidate buffer has room for the bounds
+static bool defer_route(const pqv_searcher *s, uint32_t nq, uint32_t k, const TopkPlan &p) {
+    return defer_on(s, nq, k, p) && cand_cap_for(s, k) <= 8192;
+}
 static bool seed_refine_on(const pqv_searcher *s, uint32_t nq, uint32_t k) {
     (void)nq;
     return s->opt.seed_refine && (!s->d_row_of || s->images_only) && (s->sdim % 32) == 0 && k <= 16 && (s->opt.seed_refine > 1 || s->sdim >= 256);
@@ -3720,7 +3740,7 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
                 // streamed past them, so a list is read ONCE however many queries probe it (clustered query loads: hundreds).  Not with
                 // the deferred form (its survivors carry the wide_filter_kernel queue's raw scores).
                 if (p.i8 && p.block_waves == 4 && p.quad_width == 96 && o.wide_quads && o.item_grid >= 1 && pairs >= 16ull * s->n_clusters) {
-                    const bool deferred = defer_on(s, nq, k, p) && cand_cap_for(s, k) <= 8192;
+                    const bool deferred = defer_route(s, nq, k, p);
                     if (o.list_once && o.wide_quads != 2 && !deferred && (s->sdim % 256) == 0 && s->sdim <= 768 && k <= 256) {
                         p.list_once = true;
                         p.wide_width = std::min<uint32_t>(1024u, std::max<uint32_t>(192u, (nq + 63u) / 64u * 64u));
@@ -3862,50 +3882,83 @@ int timing_events(const pqv_searcher *s, hipEvent_t (&e)[4]) {
     return PQV_OK;
 }
 
-// Enqueue probe -> probe-merge -> re-rank -> final merge for one batch on `stream`.
-// `k` is the list length the kernels work with; the first k_out entries are written out.
-// With k == k_out + 1 the merge can also flag queries whose output distances tie (d_tie).
-int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uint32_t k,
-                 uint32_t k_out, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
-                 uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand,
-                 uint32_t *d_tie, hipStream_t stream, Scratch &sc, const MaskView *mask = nullptr) {
-    using namespace pqv;
-    // an expanding call (pqv_topk_expand): the probe ranks P = min(max_nprobe, n_clusters) lists per query, a counting pass and a
-    // select decide per query how many of them it walks (>= p0), and the stream pass below runs under those rank limits
-    const bool expand = mask && mask->max_nprobe;
-    const uint32_t p0 = probe_count(s, nprobe);
-    nprobe = probe_arg(mask, nprobe);
-    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, mask != nullptr);
-    if (expand && (s->n_files || p.tile || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
-        return fail(PQV_ERR_INVALID, "expanding call on a plan that cannot expand");
-    const uint64_t max_pos = max_candidates ? max_candidates : ~0ull;
-    // the probe works on the queries as given; everything that meets the (possibly zero-padded) stored rows gets the
-    // batch's queries padded the same way
-    const float *d_queries_s = d_queries;
-    if (s->sdim != s->dim) {
-        HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(nq) * s->sdim * sizeof(float)));
-        HIP_TRY(launch_pad_rows(d_queries, nullptr, nq, s->dim, s->sdim, sc.s_qpad.as<float>(), stream));
-        d_queries_s = sc.s_qpad.as<float>();
-    }
+// The routing decisions of one top-k batch, derived once from (searcher, plan, nq, k): what the stages of enqueue_topk branch on
+// and what pqv_searcher_describe prints.  Everything below `screened` is false / 0 off the wide screened path.
+struct TopkRoute {
+    bool screened;          // the wide screen (p.tile && p.filter && p.quad): wide_seed_kernel, seed select, wide_filter_kernel
+    int operand;            // its operands, as the index of the blocked copy it reads: 0 f32, 1 f16, 2 int8
+    bool fused_probe;       // one query, no table: probe, probe merge, bucketing and quantisation in ONE block (probe_single_kernel)
+    bool single_bucket;     // one query: the probe merge writes the bucketing itself (MergeArgs::sq_*), no pair sort
+    bool items;             // work-item tables (quad x row chunk that exists) instead of the 2-D grid (which tables of > 2^24 entries keep)
+    bool wide;              // the wide-quad instance beside the regular quads, with an item table of its own
+    uint32_t max_items, wide_max_items;
+    bool q_global;          // rows too long to stage a quad's queries in LDS: blocked copy per quad in global memory
+    bool seed_tail;         // one query: the seed kernel's last block selects (SeedTail); otherwise a launch of its own
+    bool deferred;          // deferred exact evaluation: survivors appended with their bounds, resolved by launch_resolve
+};
+static TopkRoute topk_route(const pqv_searcher *s, const TopkPlan &p, uint32_t nq, uint32_t k) {
+    TopkRoute r{};
+    r.screened = p.tile && p.filter && p.quad;
+    if (!r.screened) return r;
+    r.operand = p.i8 ? 2 : p.f16 ? 1 : 0;
+    r.single_bucket = nq == 1 && p.np <= 64 && s->opt.single_bucket && !s->n_files;
+    r.fused_probe = r.single_bucket && s->opt.single_bucket > 0 && s->opt.single_bucket != 2 && s->kc_pad != 0 && s->kc_pad <= 4096;
+    r.items = (s->opt.item_grid > 1 || (s->opt.item_grid == 1 && p.block_waves == 4)) &&
+              static_cast<uint64_t>(p.max_quads) * p.filter_bpl <= (1ull << 24);
+    r.max_items = r.items ? p.max_quads * p.filter_bpl : 0;
+    r.wide = r.items && p.wide_width != 0 && !r.single_bucket;
+    r.wide_max_items = r.wide ? p.max_quads * p.wide_bpl : 0;
+    r.q_global = !p.f16 && !p.i8 && static_cast<uint64_t>(p.quad_width) * s->sdim * sizeof(float) > 32768;
+    r.seed_tail = nq == 1 && k <= 256 && s->opt.single_bucket > 0;
+    r.deferred = defer_route(s, nq, k, p);
+    return r;
+}
 
-    // 1. centroid probe (its scratch first: the arguments below point into it)
-    MergeArgs pm{};
-    if (int rc = probe_merge_args(s, sc, p, nq, max_candidates, pm)) return rc;
-    if (d_n_cand) pm.n_cand = d_n_cand;
-    // (a masked call: candidate_rows and embeddings_fetched -- the considered rows -- are counted by masked_stream_kernel)
-    pm.stats = mask ? nullptr : s->d_stats.as<unsigned long long>();
+// One enqueue_topk call as its stages see it: the caller's arguments, the plan, route and request they follow, and what earlier
+// stages leave for later ones.  Handed on by reference, never copied.
+struct TopkCall {
+    const pqv_searcher *s; Scratch &sc; hipStream_t stream;
+    const TopkPlan &p; const TopkRoute &rt; const SearchRequest *rq;
+    uint32_t nq, k, k_out, p0;                  // p0: an expanding call's own nprobe (the probe ranks p.np lists)
+    uint64_t max_candidates, max_pos; int metric, sqrt_out;
+    const float *d_queries, *d_queries_s;       // as given (the probe), and padded like the stored rows (pad_queries)
+    uint32_t *d_row_idx; float *d_dist; uint32_t *d_n_found, *d_tie;
+    hipEvent_t ev[4];
+    pqv::MergeArgs pm;                          // the probe merge's arguments (probe_merge_args, enqueue_probe_stage)
+    uint32_t *pair_u32;                         // tile paths: the pair sort's u32 scratch
+    pqv::PairQuantArgs pq_args; bool quant_done;       // int8 screen: the query images' arguments; done inside the fused probe
+    const uint64_t *pair_end;                   // round-robin capped table: every probed list's end of candidates
+    const uint32_t *rank_limit;                 // expanding call: the lists each query walks (expand_depth)
+    // a distinct / grouped call (group_buffers): rows per group (0: distinct), gm > 1 (pass 2 behind the fold fills the caller's
+    // [nq, k, gm] blocks), k * max(1, gm), and where pass 1's n_found and group values go (the caller's blocks, or the lane's)
+    uint32_t gm; bool two_pass; size_t km; uint32_t *g_n_found; int64_t *g_keys;
+};
+// stage: the probe works on the queries as given; everything that meets the (possibly zero-padded) stored rows gets the batch's
+// queries padded the same way
+static int pad_queries(TopkCall &c) {
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc;
+    if (s->sdim == s->dim) return PQV_OK;
+    HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(c.nq) * s->sdim * sizeof(float)));
+    HIP_TRY(pqv::launch_pad_rows(c.d_queries, nullptr, c.nq, s->dim, s->sdim, sc.s_qpad.as<float>(), c.stream));
+    c.d_queries_s = sc.s_qpad.as<float>();
+    return PQV_OK;
+}
+// stage: the per-wave partial lists, and for a distinct / grouped call (pqv.h: pqv_topk_grouped) the buffers of both passes.  With
+// more than one row per group, pass 1 is the distinct call with its rows and distances going to the lane, and pass 2 behind its fold
+// fills the caller's [nq, k, group_size] blocks.  Every buffer of both passes is sized here, before the first kernel: the partial
+// lists of pass 2 take over those of pass 1.
+static int group_buffers(TopkCall &c) {
+    Scratch &sc = c.sc; const TopkPlan &p = c.p; const SearchRequest *rq = c.rq;
+    const uint32_t nq = c.nq, k = c.k;
     HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint32_t)));
-    const bool distinct = mask && mask->group;
+    const bool distinct = rq && rq->distinct();
     if (distinct) HIP_TRY(sc.s_part_grp.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(int64_t)));
-    // a grouped call (pqv.h: pqv_topk_grouped) with more than one row per group: pass 1 below is the distinct call with its rows and
-    // distances going to the lane, pass 2 behind its fold fills the caller's [nq, k, group_size] blocks.  Every buffer of both passes is
-    // sized here, before the first kernel: the partial lists of pass 2 take over those of pass 1.
-    const uint32_t gm = distinct ? mask->group_size : 0u;
+    const uint32_t gm = distinct ? rq->groups.size : 0u;
     const bool two_pass = gm > 1;
     const size_t km = static_cast<size_t>(k) * std::max<uint32_t>(1, gm);
-    uint32_t *g_n_found = d_n_found;          // pass 1's n_found: the caller's block, or the lane's where pass 2 / group_rows need one
-    int64_t *g_keys = distinct ? mask->d_group_out : nullptr;
+    uint32_t *g_n_found = c.d_n_found;
+    int64_t *g_keys = distinct ? rq->groups.d_keys : nullptr;
     if (two_pass) {
         if (km > 1024 || k > pqv::GROUPED_SET_MAX) return fail(PQV_ERR_INVALID, "grouped call beyond the kernels' lists");
         const size_t n_lists = static_cast<size_t>(nq) * p.n_part_rr;
@@ -3919,15 +3972,19 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         HIP_TRY(sc.s_gset_slot.ensure(static_cast<size_t>(nq) * k * sizeof(uint32_t)));
         if (!g_keys) { HIP_TRY(sc.s_g1_keys.ensure(static_cast<size_t>(nq) * k * sizeof(int64_t))); g_keys = sc.s_g1_keys.as<int64_t>(); }
     }
-    if ((two_pass || (gm == 1 && mask->d_group_rows)) && !g_n_found) {
+    if ((two_pass || (gm == 1 && rq->groups.d_rows)) && !g_n_found) {
         HIP_TRY(sc.s_g1_nfound.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
         g_n_found = sc.s_g1_nfound.as<uint32_t>();
     }
-
-    hipEvent_t ev[4];
-    if (int rc = timing_events(s, ev)) return rc;
-    if (ev[0]) HIP_TRY(hipEventRecord(ev[0], stream));
-
+    c.gm = gm; c.two_pass = two_pass; c.km = km; c.g_n_found = g_n_found; c.g_keys = g_keys;
+    return PQV_OK;
+}
+// stage 1: the centroid probe with everything the probe merge presets or writes on the way -- the tile paths' histogram and empty
+// partial lists, the one-query bucketing, and the int8 screen's query images (made inside the fused one-query probe)
+static int enqueue_probe_stage(TopkCall &c, uint32_t nprobe) {
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const TopkRoute &rt = c.rt; hipStream_t stream = c.stream;
+    const uint32_t nq = c.nq, k = c.k; const float *d_queries = c.d_queries, *d_queries_s = c.d_queries_s;
+    pqv::MergeArgs &pm = c.pm; pqv::PairQuantArgs &pq_args = c.pq_args;
     const uint32_t kc_pairs = s->n_clusters;
     uint32_t *pair_u32 = nullptr, zero_n = 0;
     if (p.tile) {
@@ -3939,15 +3996,9 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
         zero_n = static_cast<uint32_t>(R * kc_pairs);
         HIP_TRY(sc.s_gthr.ensure(static_cast<size_t>(nq) * sizeof(unsigned long long)));
         if (p.filter) { HIP_TRY(sc.s_qnorm.ensure(static_cast<size_t>(nq) * sizeof(float))); HIP_TRY(sc.s_qmax.ensure(static_cast<size_t>(nq) * sizeof(float))); }
-    }
-    // one query on the wide screened path: probe, probe merge, bucketing and quantisation in ONE block (probe_single_kernel)
-    // (table searchers: never -- the batched probe and the pair sort)
-    const bool fused_probe = nq == 1 && p.np <= 64 && p.tile && p.filter && p.quad && s->opt.single_bucket > 0 &&
-                             s->opt.single_bucket != 2 && s->kc_pad != 0 && s->kc_pad <= 4096 && !s->n_files;
-    if (p.tile) {
         pm.hist = pair_u32; pm.hist_stride = kc_pairs; pm.gthr_init = sc.s_gthr.as<unsigned long long>();
         // every partial list of the re-rank starts EMPTY: preset by the probe merge (one wave per query)
-        if (p.filter && p.quad) {       // wide path: one "written" byte per list (see MergeArgs::preset_flags)
+        if (rt.screened) {              // wide path: one "written" byte per list (see MergeArgs::preset_flags)
             const uint32_t nflag = (p.n_part_rr + 3) / 4 * 4;
             HIP_TRY(sc.s_part_flags.ensure(static_cast<size_t>(nq) * nflag));
             pm.preset_flags = sc.s_part_flags.as<uint8_t>(); pm.preset_flag_n = nflag;
@@ -3956,33 +4007,21 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
             pm.preset_n = p.n_part_rr * k;
         }
         if (p.filter) { pm.qnorm_out = sc.s_qnorm.as<float>(); pm.qmax_out = sc.s_qmax.as<float>(); pm.queries = d_queries; pm.dim = s->dim; }
-    }
-    // one query: the probe merge writes the bucketing itself (MergeArgs::sq_*), no pair sort
-    const bool single_bucket = nq == 1 && p.np <= 64 && p.tile && p.filter && p.quad && s->opt.single_bucket && !s->n_files;
-    // (a work-item table of more than 2^24 entries -- batches of hundreds of thousands of queries -- keeps the 2-D grid)
-    const bool items = p.tile && p.filter && p.quad && (s->opt.item_grid > 1 || (s->opt.item_grid == 1 && p.block_waves == 4)) &&
-                       static_cast<uint64_t>(p.max_quads) * p.filter_bpl <= (1ull << 24);
-    const uint32_t max_items = items ? p.max_quads * p.filter_bpl : 0;
-    const bool wide = items && p.wide_width != 0 && !single_bucket;
-    const uint32_t wide_max_items = wide ? p.max_quads * p.wide_bpl : 0;
-    if (p.tile) {
         HIP_TRY(sc.s_quads.ensure(static_cast<size_t>(p.max_quads) * sizeof(uint4)));
         HIP_TRY(sc.s_pairs.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
         HIP_TRY(sc.s_groups.ensure(static_cast<size_t>(p.max_groups) * sizeof(uint4)));
-        if (items) HIP_TRY(sc.s_items.ensure(2 * (static_cast<size_t>(max_items) + wide_max_items) * sizeof(uint32_t)));
+        if (rt.items) HIP_TRY(sc.s_items.ensure(2 * (static_cast<size_t>(rt.max_items) + rt.wide_max_items) * sizeof(uint32_t)));
     }
-    if (single_bucket) {
+    if (rt.single_bucket) {
         uint32_t *v = pair_u32 + 2 * (pqv::HIST_REPLICAS - 1) * static_cast<uint64_t>(kc_pairs);
         pm.sq_quads = sc.s_quads.as<uint4>(); pm.sq_pairs = sc.s_pairs.as<uint32_t>(); pm.sq_n_quads = v + 5ull * kc_pairs + 4;
-        if (items) {
+        if (rt.items) {
             pm.sq_item_quad = sc.s_items.as<uint32_t>(); pm.sq_n_items = v + 6ull * kc_pairs + 6;
-            pm.sq_item_rows = p.filter_rows_per_block; pm.sq_max_items = max_items;
+            pm.sq_item_rows = p.filter_rows_per_block; pm.sq_max_items = rt.max_items;
         }
     }
     // int8 screen: the query images (one per query, or one per probed pair in the residual form) -- see step 2
-    pqv::PairQuantArgs pq_args{};
-    bool quant_done = false;
-    if (p.tile && p.filter && p.quad && p.i8) {
+    if (rt.operand == 2) {
         if (int rc = ensure_blocked_copy(s, 2, stream)) return rc;     // centres and scales (built at creation; here only after an option change)
         const bool per_pair = s->i8_residual;
         const size_t n_img = per_pair ? static_cast<size_t>(nq) * p.np : nq;
@@ -3996,7 +4035,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
                                      static_cast<uint32_t>(n_img), per_pair ? p.np : 1u, s->sdim, static_cast<int8_t *>(sc.s_qi8.p),
                                      sc.s_qn2i.as<int>(), sc.s_qres.as<float>(), sc.s_qresu.as<float>(), sc.s_pair_lb.as<float>()};
     }
-    if (fused_probe) {
+    if (rt.fused_probe) {
         pqv::ProbeRowsArgs pr{};
         pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_queries;
         pr.nq = 1; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
@@ -4007,340 +4046,411 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
             HIP_TRY(hipMemsetAsync(sc.s_ticket.p, 0, sizeof(uint32_t), stream));
         }
         // (the image(s) of a one-query call are made inside the probe launch)
-        quant_done = pq_args.n_pairs != 0;
-        HIP_TRY(pqv::launch_probe_single(pr, pm, sc.s_ticket.as<uint32_t>(), quant_done ? &pq_args : nullptr, stream));
+        c.quant_done = pq_args.n_pairs != 0;
+        HIP_TRY(pqv::launch_probe_single(pr, pm, sc.s_ticket.as<uint32_t>(), c.quant_done ? &pq_args : nullptr, stream));
     } else {
-        if (int rc = enqueue_probe(s, sc, p, d_queries, nq, nprobe, max_candidates, pm, pair_u32, zero_n, stream, metric)) return rc;
+        if (int rc = enqueue_probe(s, sc, p, d_queries, nq, nprobe, c.max_candidates, pm, pair_u32, zero_n, stream, c.metric)) return rc;
     }
-    const uint64_t *pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
-    const uint32_t *rank_limit = nullptr;
-    if (expand) {
-        uint32_t *used = mask->d_nprobe_used;
-        if (!used) { HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(nq) * sizeof(uint32_t))); used = sc.s_expand_used.as<uint32_t>(); }
-        // (both forms before the stream pass: that pass adds n_cand[q] to candidate_rows)
-        if (const pqv_row_keys *gk = mask->group) {
-            // a group column (pqv_topk_distinct_expand): DISTINCT group values in probe order, one block per query, one launch
-            const GroupExpandArgs ga{sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(), s->d_list_off.as<uint64_t>(), nq, p.np, p0, k_out,
-                                     mask->bits, gk->d_key_pos.p, gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr,
-                                     gk->dtype == PQV_COL_I32 ? 4u : 8u, used, pm.n_cand};
-            const GroupFilterArgs fa = mask->keys ? group_filter_args(mask) : GroupFilterArgs{};
-            HIP_TRY(launch_group_expand(ga, mask->keys ? &fa : nullptr, stream));
-            s->counters.kernel_launches += 1;
-        } else {
-            HIP_TRY(sc.s_expand_cnt.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
-            ExpandCountArgs ca{};
-            ca.probe = sc.s_probe.as<uint32_t>(); ca.list_off = s->d_list_off.as<uint64_t>(); ca.nq = nq; ca.P = p.np;
-            ca.bits = mask->bits; ca.cnt = sc.s_expand_cnt.as<uint32_t>();
-            if (const pqv_row_keys *kk = mask->keys) {
-                const uint32_t wide = kk->dtype == PQV_COL_I32 ? 0u : 1u;
-                ca.win = 1u + 2u * mask->fkind + wide;
-                ca.key_pos = kk->d_key_pos.p; ca.valid_pos = kk->has_valid ? kk->d_valid_pos.as<uint64_t>() : nullptr;
-                ca.a = mask->fkind ? mask->d_fa : mask->d_qkeys; ca.b = mask->fkind ? mask->d_fb : nullptr;
-            }
-            HIP_TRY(launch_filter_count(ca, stream));
-            const ExpandSelectArgs sa{ca.cnt, ca.probe, sc.s_cand_base.as<uint64_t>(), ca.list_off, nq, p.np, p0, k_out, used, pm.n_cand};
-            HIP_TRY(launch_expand_select(sa, stream));
-            s->counters.kernel_launches += 2;
+    c.pair_u32 = pair_u32;
+    c.pair_end = table_rr(s, c.max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
+    return PQV_OK;
+}
+// stage: an expanding call (pqv_topk_expand).  The probe ranked P = min(max_nprobe, n_clusters) lists per query; a counting pass and
+// a select -- with a group column, one kernel over the distinct group values -- decide per query how many of them it walks
+// (>= p0), and the stream pass runs under those rank limits (c.rank_limit).
+static int expand_depth(TopkCall &c) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const SearchRequest *rq = c.rq; hipStream_t stream = c.stream;
+    const uint32_t nq = c.nq, k_out = c.k_out, p0 = c.p0; const MergeArgs &pm = c.pm;
+    uint32_t *used = rq->expand.d_used;
+    if (!used) { HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(nq) * sizeof(uint32_t))); used = sc.s_expand_used.as<uint32_t>(); }
+    // (both forms before the stream pass: that pass adds n_cand[q] to candidate_rows)
+    if (const pqv_row_keys *gk = rq->groups.col) {
+        // a group column (pqv_topk_distinct_expand): DISTINCT group values in probe order, one block per query, one launch
+        const GroupExpandArgs ga{sc.s_probe.as<uint32_t>(), sc.s_cand_base.as<uint64_t>(), s->d_list_off.as<uint64_t>(), nq, p.np, p0, k_out,
+                                 rq->rows.bits, gk->d_key_pos.p, gk->valid_image(),
+                                 gk->elem_size(), used, pm.n_cand};
+        const GroupFilterArgs fa = rq->filtered() ? group_filter_args(rq) : GroupFilterArgs{};
+        HIP_TRY(launch_group_expand(ga, rq->filtered() ? &fa : nullptr, stream));
+        s->counters.kernel_launches += 1;
+    } else {
+        HIP_TRY(sc.s_expand_cnt.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
+        ExpandCountArgs ca{};
+        ca.probe = sc.s_probe.as<uint32_t>(); ca.list_off = s->d_list_off.as<uint64_t>(); ca.nq = nq; ca.P = p.np;
+        ca.bits = rq->rows.bits; ca.cnt = sc.s_expand_cnt.as<uint32_t>();
+        if (const pqv_row_keys *kk = rq->rows.keys) {
+            const uint32_t wide = kk->dtype == PQV_COL_I32 ? 0u : 1u;
+            ca.win = 1u + 2u * rq->rows.kind + wide;
+            ca.key_pos = kk->d_key_pos.p; ca.valid_pos = kk->valid_image();
+            ca.a = rq->d_filter_a(); ca.b = rq->d_filter_b();
         }
-        rank_limit = used;
+        HIP_TRY(launch_filter_count(ca, stream));
+        const ExpandSelectArgs sa{ca.cnt, ca.probe, sc.s_cand_base.as<uint64_t>(), ca.list_off, nq, p.np, p0, k_out, used, pm.n_cand};
+        HIP_TRY(launch_expand_select(sa, stream));
+        s->counters.kernel_launches += 2;
     }
-
-    // 2. candidate re-rank + per-wave top-k
-    bool use_cand = false;     // wide screened path: the final merge also reads the candidate buffers
-    bool use_defer = false;    // ... whose entries carried bounds (deferred evaluation), resolved by launch_resolve
-    if (p.tile) {
-        const uint32_t n_pairs = nq * p.np, kc = s->n_clusters;
-        uint32_t *u = pair_u32;
-        PairSortArgs ps{};
-        ps.probe = sc.s_probe.as<uint32_t>(); ps.n_pairs = n_pairs; ps.n_clusters = kc; ps.hist_done = 1;
-        uint32_t *v = u + 2 * (pqv::HIST_REPLICAS - 1) * static_cast<uint64_t>(kc);    // past the extra histogram / cursor copies
-        ps.hist = u; ps.hist_stride = kc; ps.nprobe = p.np; ps.cursor = u + pqv::HIST_REPLICAS * static_cast<uint64_t>(kc);
-        ps.pair_off = v + 2ull * kc; ps.group_off = v + 3ull * kc + 1;
-        ps.n_groups = v + 4ull * kc + 2;
-        ps.quad_off = v + 4ull * kc + 3; ps.n_quads = v + 5ull * kc + 4; ps.quad_width = wide ? p.wide_width : p.quad_width ? p.quad_width : 64;
-        ps.pairs = sc.s_pairs.as<uint32_t>(); ps.groups = sc.s_groups.as<uint4>(); ps.quads = sc.s_quads.as<uint4>();
-        // work items of the wide filter kernel (quad x row chunk that exists): its grid then has no holes
-        // (the 8-wave blocks keep the 2-D grid with its quad-to-XCD affinity: C2 7.25 against 7.13 M QPS)
-        if (items) {
-            ps.list_off = s->d_list_off.as<uint64_t>(); ps.item_rows = p.filter_rows_per_block;
-            ps.item_off = v + 5ull * kc + 5; ps.n_items = v + 6ull * kc + 6;
-            ps.item_quad = sc.s_items.as<uint32_t>(); ps.max_items = max_items;
-            if (s->opt.chunk_major && !single_bucket) {
-                ps.item_chunk = ps.item_quad + max_items + wide_max_items; ps.wide_item_chunk = ps.item_chunk + max_items;
-            }
-            if (wide && ps.item_chunk) {         // pair_scan_kernel writes the two counts straight into pinned host memory
-                if (!s->h_wide_stats.p) {
-                    HIP_TRY(s->h_wide_stats.ensure(4 * sizeof(uint32_t)));
-                    std::memset(s->h_wide_stats.p, 0, 4 * sizeof(uint32_t));
-                }
-                ps.wide_stats = s->h_wide_stats.as<uint32_t>();
-            }
-            if (p.i8 && p.block_waves == 4 && p.quad_width == 96 && ps.item_chunk && s->opt.wide_quads == 1) {
-                // the batch's shape for the NEXT batch's choice between the wide-quad instance and regular quads only (prefer_regular)
-                if (!s->h_wide_stats.p) {
-                    HIP_TRY(s->h_wide_stats.ensure(4 * sizeof(uint32_t)));
-                    std::memset(s->h_wide_stats.p, 0, 4 * sizeof(uint32_t));
-                }
-                ps.shape_stats = s->h_wide_stats.as<uint32_t>() + 2; ps.shape_wide = 160; ps.shape_narrow = p.quad_width;
-            }
-            // XCD-aware slots: in the wide table always (lists of several wide quads); in the regular table where it has lists of
-            // several quads too -- no wide-quad instance, or option 3 (every table)
-            ps.xcd_items = !s->opt.xcd_items ? 0u : s->opt.xcd_items >= 3 ? 3u : wide ? 2u : 1u;
-            if (wide) {
-                ps.wide_list_major = p.list_once ? 1u : 0u;
-                ps.wide_min = p.quad_width + 1; ps.wide_item_rows = p.wide_rows_per_block;
-                ps.wide_item_off = v + 6ull * kc + 7; ps.wide_n_items = v + 7ull * kc + 8;
-                ps.wide_item_quad = sc.s_items.as<uint32_t>() + max_items; ps.wide_max_items = wide_max_items;
-            }
+    c.rank_limit = used;
+    return PQV_OK;
+}
+// stage 2a: the probed (query, list) pairs bucketed by list into groups and quads (pair sort; one query: done by the probe merge),
+// and the work-item tables of the wide screen.  ps: filled for the re-rank stages that read its tables.
+static int enqueue_pair_sort(TopkCall &c, pqv::PairSortArgs &ps) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const TopkRoute &rt = c.rt; hipStream_t stream = c.stream;
+    const uint32_t nq = c.nq;
+    const uint32_t n_pairs = nq * p.np, kc = s->n_clusters;
+    uint32_t *u = c.pair_u32;
+    ps.probe = sc.s_probe.as<uint32_t>(); ps.n_pairs = n_pairs; ps.n_clusters = kc; ps.hist_done = 1;
+    uint32_t *v = u + 2 * (pqv::HIST_REPLICAS - 1) * static_cast<uint64_t>(kc);    // past the extra histogram / cursor copies
+    ps.hist = u; ps.hist_stride = kc; ps.nprobe = p.np; ps.cursor = u + pqv::HIST_REPLICAS * static_cast<uint64_t>(kc);
+    ps.pair_off = v + 2ull * kc; ps.group_off = v + 3ull * kc + 1;
+    ps.n_groups = v + 4ull * kc + 2;
+    ps.quad_off = v + 4ull * kc + 3; ps.n_quads = v + 5ull * kc + 4; ps.quad_width = rt.wide ? p.wide_width : p.quad_width ? p.quad_width : 64;
+    ps.pairs = sc.s_pairs.as<uint32_t>(); ps.groups = sc.s_groups.as<uint4>(); ps.quads = sc.s_quads.as<uint4>();
+    // work items of the wide filter kernel (quad x row chunk that exists): its grid then has no holes
+    // (the 8-wave blocks keep the 2-D grid with its quad-to-XCD affinity: C2 7.25 against 7.13 M QPS)
+    if (rt.items) {
+        ps.list_off = s->d_list_off.as<uint64_t>(); ps.item_rows = p.filter_rows_per_block;
+        ps.item_off = v + 5ull * kc + 5; ps.n_items = v + 6ull * kc + 6;
+        ps.item_quad = sc.s_items.as<uint32_t>(); ps.max_items = rt.max_items;
+        if (s->opt.chunk_major && !rt.single_bucket) {
+            ps.item_chunk = ps.item_quad + rt.max_items + rt.wide_max_items; ps.wide_item_chunk = ps.item_chunk + rt.max_items;
         }
-        if (!single_bucket) HIP_TRY(launch_pair_sort(ps, stream));
-        TileArgs ta{};
-        ta.mat = s->d_mat; ta.row_of = s->d_row_of; ta.list_off = s->d_list_off.as<uint64_t>();
-        ta.queries = d_queries_s; ta.cand_base = sc.s_cand_base.as<uint64_t>();
-        ta.pairs = ps.pairs; ta.groups = ps.groups; ta.n_groups = ps.n_groups; ta.max_groups = p.max_groups;
-        ta.nq = nq; ta.nprobe = p.np; ta.dim = s->sdim; ta.k = k;
-        ta.quads = ps.quads; ta.n_quads = ps.n_quads; ta.max_quads = p.max_quads; ta.quad_width = p.quad_width;
-        ta.rows_per_block = p.rr_rows_per_block; ta.blocks_per_list = p.rr_bpl; ta.max_pos = max_pos; ta.pair_end = pair_end;
-        ta.slots_per_pair = p.slots_per_pair; ta.slot_base = 0; ta.n_part = p.n_part_rr;
-        ta.gthr = sc.s_gthr.as<unsigned long long>();
-        ta.part_keys = sc.s_part_keys.as<uint64_t>(); ta.part_vals = sc.s_part_vals.as<uint32_t>();
-        if (p.filter && !(p.quad && p.i8)) { if (int rc = ensure_row_norms(s, stream)) return rc; }    // (the f32 / f16 screens read the rows' norms)
-        ta.row_norm2 = s->d_row_norm2.as<float>(); ta.norm_by_pos = s->images_only ? 1 : 0;
-        ta.stats = s->d_stats.as<unsigned long long>();
-        ta.xcd_swizzle = 0;
-        if (p.filter && p.quad) {
-            if (int rc = ensure_blocked_copy(s, p.i8 ? 2 : p.f16 ? 1 : 0, stream)) return rc;     // built at creation; here only after an option change
-            ta.mat_blk = static_cast<const float4 *>(s->d_mat_blk_op[p.i8 ? 2 : p.f16 ? 1 : 0].p);
-            ta.blk_off = s->d_blk_off.as<uint64_t>();
-            ta.block_waves = p.block_waves;
-            if (p.f16) {
-                ta.f16 = 1; ta.scale = s->f16_scale; ta.scale2 = s->f16_scale * s->f16_scale;
-                ta.query_maxabs = sc.s_qmax.as<float>();
-            }
-            if (p.i8) {
-                // residual form: one image per (query, probed list) pair -- the query's residual against that list's centre at
-                // that list's scale -- + the pair's lower bound from the triangle inequality on the centre (pair_lb);
-                // one-centre form: one image per query (every list shares centre and scale)
-                const bool per_pair = s->i8_residual;
-                if (!quant_done) {
-                    HIP_TRY(launch_quantize_pairs_i8(pq_args.queries, pq_args.probe, pq_args.center, pq_args.scale, pq_args.half, pq_args.radius,
-                                                     pq_args.n_pairs, pq_args.nprobe, pq_args.dim, pq_args.q_i8, pq_args.q_n2i, pq_args.q_res,
-                                                     pq_args.q_resu, pq_args.pair_lb, stream));
-                    s->counters.kernel_launches += 1;
-                }
-                ta.i8 = 1; ta.i8_pair_images = per_pair ? 1 : 0;
-                ta.q_i8 = static_cast<const int8_t *>(sc.s_qi8.p); ta.q_n2i = sc.s_qn2i.as<int>(); ta.q_res = sc.s_qres.as<float>();
-                ta.q_resu = sc.s_qresu.as<float>(); ta.pair_lb = (per_pair && s->opt.pair_prune) ? sc.s_pair_lb.as<float>() : nullptr;
-                ta.list_scale = s->d_list_scale.as<float>();
-                ta.row_n2i = s->d_row_n2i.as<int>(); ta.row_res = s->d_row_res.as<float>();
-            }
-            // quad-to-XCD affinity: on by default for the global-query variant, whose per-quad operand copies
-            // must stay L2-resident
-            const bool q_global = !p.f16 && !p.i8 && static_cast<uint64_t>(p.quad_width) * s->sdim * sizeof(float) > 32768;
-            // (8-wave blocks: the quads of one cluster on one XCD, so a list's second pass finds rows in that L2: C3 2.51 -> 2.44 ms)
-            ta.xcd_swizzle = s->opt.quad_xcd >= 0 ? s->opt.quad_xcd : (q_global ? 1 : p.block_waves == 8 ? 2 : 0);
-            if (q_global) {
-                // rows too long to stage a quad's queries in LDS: blocked copy per quad in global memory
-                HIP_TRY(sc.s_qblk.ensure(static_cast<size_t>(p.max_quads) * p.quad_width * s->sdim * sizeof(float)));
-                HIP_TRY(launch_pack_queries(d_queries_s, ps.pairs, ps.quads, ps.n_quads, p.max_quads, p.np, s->sdim,
-                                            p.quad_width / 16, sc.s_qblk.p, stream));
-                ta.q_blk = static_cast<const float4 *>(sc.s_qblk.p);
-            }
+        // the batch's shape for the NEXT batch's choice between the wide-quad instance and regular quads only (prefer_regular)
+        const bool shape_hint = p.i8 && p.block_waves == 4 && p.quad_width == 96 && ps.item_chunk && s->opt.wide_quads == 1;
+        if (((rt.wide && ps.item_chunk) || shape_hint) && !s->h_wide_stats.p) {
+            HIP_TRY(s->h_wide_stats.ensure(4 * sizeof(uint32_t)));
+            std::memset(s->h_wide_stats.p, 0, 4 * sizeof(uint32_t));
         }
-        if (p.filter) ta.query_norm2 = sc.s_qnorm.as<float>();     // filled by the probe merge
-        if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
-        if (p.filter && p.quad) {
-            const uint32_t ccap = cand_cap_for(s, k);
-            HIP_TRY(sc.s_cand_keys.ensure(static_cast<size_t>(nq) * ccap * sizeof(uint64_t)));
-            HIP_TRY(sc.s_cand_vals.ensure(static_cast<size_t>(nq) * ccap * sizeof(uint32_t)));
-            HIP_TRY(sc.s_cand_cnt.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
-            HIP_TRY(sc.s_spilled.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
-            ta.cand_keys = sc.s_cand_keys.as<uint64_t>(); ta.cand_vals = sc.s_cand_vals.as<uint32_t>();
-            ta.cand_cnt = sc.s_cand_cnt.as<uint32_t>(); ta.cand_cap = ccap; ta.spilled = sc.s_spilled.as<uint32_t>();
-            if (defer_on(s, nq, k, p) && ccap <= 8192) {
-                // deferred exact evaluation: bounds per appended pair, and the queues' raw scores (a strip per wave of every block)
-                HIP_TRY(sc.s_cand_lb.ensure(static_cast<size_t>(nq) * ccap * sizeof(float)));
-                const size_t blocks_r = items ? max_items : static_cast<size_t>(p.filter_bpl | 1u) * p.max_quads;
-                const size_t words_r = blocks_r * p.block_waves * pqv::wide_filter_pend(p.quad_width, p.block_waves, p.f16);
-                const size_t words_w = wide ? static_cast<size_t>(wide_max_items) * 8 * pqv::wide_filter_pend(p.wide_width, 8, false) : 0;
-                HIP_TRY(sc.s_pendv.ensure((words_r + words_w) * sizeof(uint32_t)));
-                ta.cand_lb = sc.s_cand_lb.as<float>();
-                ta.pendv = sc.s_pendv.as<uint32_t>(); ta.pendv_wide = ta.pendv + words_r;
-                use_defer = true;
+        if (rt.wide && ps.item_chunk) ps.wide_stats = s->h_wide_stats.as<uint32_t>();    // pair_scan_kernel writes the two counts straight into pinned host memory
+        if (shape_hint) { ps.shape_stats = s->h_wide_stats.as<uint32_t>() + 2; ps.shape_wide = 160; ps.shape_narrow = p.quad_width; }
+        // XCD-aware slots: in the wide table always (lists of several wide quads); in the regular table where it has lists of
+        // several quads too -- no wide-quad instance, or option 3 (every table)
+        ps.xcd_items = !s->opt.xcd_items ? 0u : s->opt.xcd_items >= 3 ? 3u : rt.wide ? 2u : 1u;
+        if (rt.wide) {
+            ps.wide_list_major = p.list_once ? 1u : 0u;
+            ps.wide_min = p.quad_width + 1; ps.wide_item_rows = p.wide_rows_per_block;
+            ps.wide_item_off = v + 6ull * kc + 7; ps.wide_n_items = v + 7ull * kc + 8;
+            ps.wide_item_quad = sc.s_items.as<uint32_t>() + rt.max_items; ps.wide_max_items = rt.wide_max_items;
+        }
+    }
+    if (!rt.single_bucket) HIP_TRY(launch_pair_sort(ps, stream));
+    return PQV_OK;
+}
+// stage 2b, the wide screen: upper bounds of the first seed_rows rows of every probed list (seed), the k-th smallest of them per query
+// as the first threshold (select; one query: inside the seed launch), the screen over the whole lists with exact evaluation of what
+// passes (filter), and -- deferred form -- the evaluation of the survivors left by their bounds (resolve)
+static int enqueue_wide_screen(TopkCall &c, const pqv::PairSortArgs &ps, pqv::TileArgs &ta) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const TopkRoute &rt = c.rt; hipStream_t stream = c.stream;
+    const uint32_t nq = c.nq, k = c.k; const float *d_queries_s = c.d_queries_s; const uint64_t max_pos = c.max_pos, *pair_end = c.pair_end;
+    const uint32_t ccap = cand_cap_for(s, k);
+    HIP_TRY(sc.s_cand_keys.ensure(static_cast<size_t>(nq) * ccap * sizeof(uint64_t)));
+    HIP_TRY(sc.s_cand_vals.ensure(static_cast<size_t>(nq) * ccap * sizeof(uint32_t)));
+    HIP_TRY(sc.s_cand_cnt.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_spilled.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
+    ta.cand_keys = sc.s_cand_keys.as<uint64_t>(); ta.cand_vals = sc.s_cand_vals.as<uint32_t>();
+    ta.cand_cnt = sc.s_cand_cnt.as<uint32_t>(); ta.cand_cap = ccap; ta.spilled = sc.s_spilled.as<uint32_t>();
+    if (rt.deferred) {
+        // deferred exact evaluation: bounds per appended pair, and the queues' raw scores (a strip per wave of every block)
+        HIP_TRY(sc.s_cand_lb.ensure(static_cast<size_t>(nq) * ccap * sizeof(float)));
+        const size_t blocks_r = rt.items ? rt.max_items : static_cast<size_t>(p.filter_bpl | 1u) * p.max_quads;
+        const size_t words_r = blocks_r * p.block_waves * pqv::wide_filter_pend(p.quad_width, p.block_waves, p.f16);
+        const size_t words_w = rt.wide ? static_cast<size_t>(rt.wide_max_items) * 8 * pqv::wide_filter_pend(p.wide_width, 8, false) : 0;
+        HIP_TRY(sc.s_pendv.ensure((words_r + words_w) * sizeof(uint32_t)));
+        ta.cand_lb = sc.s_cand_lb.as<float>();
+        ta.pendv = sc.s_pendv.as<uint32_t>(); ta.pendv_wide = ta.pendv + words_r;
+    }
+    // thresholds: upper bounds of the first seed_rows rows of every probed list
+    TileArgs seed = ta;
+    if (rt.wide) seed.quad_width = p.wide_width;      // (the seed kernel samples a quad in slices of its own 64 queries)
+    seed.row_offset = 0; seed.row_end = p.seed_rows; seed.rows_per_block = 256;
+    seed.grid_x = (p.seed_rows + 255) / 256; seed.seed_sw = 4 * seed.grid_x;
+    const uint32_t n_vals = p.np * seed.seed_sw * 16;
+    HIP_TRY(sc.s_seed_ub.ensure(static_cast<size_t>(nq) * n_vals * sizeof(float)));
+    seed.seed_ub = sc.s_seed_ub.as<float>();
+    // running thresholds: see TileArgs::thr_hist
+    if (s->opt.running_thr && k > 1) {
+        HIP_TRY(sc.s_thr_hist.ensure(static_cast<size_t>(nq) * 16 * sizeof(uint32_t)));
+        HIP_TRY(sc.s_thr_bins.ensure(static_cast<size_t>(nq) * sizeof(float4)));
+        ta.thr_hist = sc.s_thr_hist.as<uint32_t>(); ta.thr_bins = static_cast<const float4 *>(sc.s_thr_bins.p);
+    }
+    pqv::SeedRefine rf{};
+    if (seed_refine_on(s, nq, k)) {
+        rf.mat = s->d_mat; rf.row_of = s->d_row_of; rf.queries = d_queries_s; rf.list_off = s->d_list_off.as<uint64_t>();
+        rf.probe = sc.s_probe.as<uint32_t>(); rf.cand_base = sc.s_cand_base.as<uint64_t>();
+        rf.dim = s->sdim; rf.nprobe = p.np; rf.seed_sw = seed.seed_sw; rf.seed_rows = p.seed_rows; rf.max_pos = max_pos;
+        rf.pair_end = pair_end;
+    }
+    // one query: the seed kernel's last block selects (SeedTail); otherwise a launch of its own
+    if (rt.seed_tail) {
+        if (!sc.s_ticket2.p) {
+            HIP_TRY(sc.s_ticket2.ensure(sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(sc.s_ticket2.p, 0, sizeof(uint32_t), stream));
+        }
+        seed.seed_tail.enable = 1; seed.seed_tail.n_vals = n_vals; seed.seed_tail.k = k;
+        seed.seed_tail.gthr = ta.gthr; seed.seed_tail.cand_cnt = ta.cand_cnt; seed.seed_tail.spilled = ta.spilled;
+        seed.seed_tail.thr_hist = ta.thr_hist; seed.seed_tail.thr_bins = static_cast<float4 *>(sc.s_thr_bins.p);
+        seed.seed_tail.ticket = sc.s_ticket2.as<uint32_t>();
+        seed.seed_tail.rf = rf;
+    }
+    HIP_TRY(launch_wide_seed(seed, stream));
+    if (!rt.seed_tail)
+        HIP_TRY(launch_seed_select(seed.seed_ub, nq, n_vals, k, ta.gthr, ta.cand_cnt, ta.spilled, stream,
+                                   ta.thr_hist, static_cast<float4 *>(sc.s_thr_bins.p), &rf));
+    ta.row_offset = 0; ta.slot_base = 0; ta.grid_x = p.filter_bpl;
+    ta.rows_per_block = p.filter_rows_per_block; ta.filter_variant = 0;
+    ta.part_flags = sc.s_part_flags.as<uint8_t>();
+    if (rt.items) { ta.item_quad = ps.item_quad; ta.item_chunk = ps.item_chunk; ta.wide_item_chunk = ps.wide_item_chunk; ta.n_items = ps.n_items; ta.max_items = rt.max_items; }
+    ta.drain_min = static_cast<uint32_t>(std::max(0, s->opt.drain_min)); // (whole-tile prefetch in the 96-query f16 form: 1000-row lists of 128 dims 5.96 -> 6.14 M q/s, C2's 10 k-row lists 7.68 -> 7.14 M)
+    ta.opt_pf96 = (s->opt.pf96 >= 2 || (s->opt.pf96 == 1 && s->n / std::max<uint32_t>(1, s->n_clusters) <= 2048)) ? 1u : 0u;
+    if (rt.wide) {
+        ta.wide_width = p.wide_width; ta.wide_item_quad = ps.wide_item_quad; ta.wide_n_items = ps.wide_n_items;
+        ta.wide_max_items = rt.wide_max_items; ta.wide_rows_per_block = p.wide_rows_per_block;
+        ta.wide_nt = wide_rows_nt(s) ? 1u : 0u;
+        ta.list_once = p.list_once ? 1u : 0u;
+        if (s->opt.fork_wide) {
+            if (!sc.side) {
+                HIP_TRY(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
+                HIP_TRY(hipEventCreateWithFlags(&sc.ev_fork, hipEventDisableTiming));
+                HIP_TRY(hipEventCreateWithFlags(&sc.ev_join, hipEventDisableTiming));
             }
-            // thresholds: upper bounds of the first seed_rows rows of every probed list
-            TileArgs seed = ta;
-            if (wide) seed.quad_width = p.wide_width;      // (the seed kernel samples a quad in slices of its own 64 queries)
-            seed.row_offset = 0; seed.row_end = p.seed_rows; seed.rows_per_block = 256;
-            seed.grid_x = (p.seed_rows + 255) / 256; seed.seed_sw = 4 * seed.grid_x;
-            const uint32_t n_vals = p.np * seed.seed_sw * 16;
-            HIP_TRY(sc.s_seed_ub.ensure(static_cast<size_t>(nq) * n_vals * sizeof(float)));
-            seed.seed_ub = sc.s_seed_ub.as<float>();
-            // running thresholds: see TileArgs::thr_hist
-            if (s->opt.running_thr && k > 1) {
-                HIP_TRY(sc.s_thr_hist.ensure(static_cast<size_t>(nq) * 16 * sizeof(uint32_t)));
-                HIP_TRY(sc.s_thr_bins.ensure(static_cast<size_t>(nq) * sizeof(float4)));
-                ta.thr_hist = sc.s_thr_hist.as<uint32_t>(); ta.thr_bins = static_cast<const float4 *>(sc.s_thr_bins.p);
-            }
-            pqv::SeedRefine rf{};
-            if (seed_refine_on(s, nq, k)) {
-                rf.mat = s->d_mat; rf.row_of = s->d_row_of; rf.queries = d_queries_s; rf.list_off = s->d_list_off.as<uint64_t>();
-                rf.probe = sc.s_probe.as<uint32_t>(); rf.cand_base = sc.s_cand_base.as<uint64_t>();
-                rf.dim = s->sdim; rf.nprobe = p.np; rf.seed_sw = seed.seed_sw; rf.seed_rows = p.seed_rows; rf.max_pos = max_pos;
-                rf.pair_end = pair_end;
-            }
-            // one query: the seed kernel's last block selects (SeedTail); otherwise a launch of its own
-            const bool seed_tail = nq == 1 && k <= 256 && s->opt.single_bucket > 0;
-            if (seed_tail) {
-                if (!sc.s_ticket2.p) {
-                    HIP_TRY(sc.s_ticket2.ensure(sizeof(uint32_t)));
-                    HIP_TRY(hipMemsetAsync(sc.s_ticket2.p, 0, sizeof(uint32_t), stream));
-                }
-                seed.seed_tail.enable = 1; seed.seed_tail.n_vals = n_vals; seed.seed_tail.k = k;
-                seed.seed_tail.gthr = ta.gthr; seed.seed_tail.cand_cnt = ta.cand_cnt; seed.seed_tail.spilled = ta.spilled;
-                seed.seed_tail.thr_hist = ta.thr_hist; seed.seed_tail.thr_bins = static_cast<float4 *>(sc.s_thr_bins.p);
-                seed.seed_tail.ticket = sc.s_ticket2.as<uint32_t>();
-                seed.seed_tail.rf = rf;
-            }
-            HIP_TRY(launch_wide_seed(seed, stream));
-            if (!seed_tail)
-                HIP_TRY(launch_seed_select(seed.seed_ub, nq, n_vals, k, ta.gthr, ta.cand_cnt, ta.spilled, stream,
-                                           ta.thr_hist, static_cast<float4 *>(sc.s_thr_bins.p), &rf));
-            ta.row_offset = 0; ta.slot_base = 0; ta.grid_x = p.filter_bpl;
-            ta.rows_per_block = p.filter_rows_per_block; ta.filter_variant = 0;
-            ta.part_flags = sc.s_part_flags.as<uint8_t>();
-            if (items) { ta.item_quad = ps.item_quad; ta.item_chunk = ps.item_chunk; ta.wide_item_chunk = ps.wide_item_chunk; ta.n_items = ps.n_items; ta.max_items = max_items; }
-            ta.drain_min = static_cast<uint32_t>(std::max(0, s->opt.drain_min)); // (whole-tile prefetch in the 96-query f16 form: 1000-row lists of 128 dims 5.96 -> 6.14 M q/s, C2's 10 k-row lists 7.68 -> 7.14 M)
-            ta.opt_pf96 = (s->opt.pf96 >= 2 || (s->opt.pf96 == 1 && s->n / std::max<uint32_t>(1, s->n_clusters) <= 2048)) ? 1u : 0u;
-            if (wide) {
-                ta.wide_width = p.wide_width; ta.wide_item_quad = ps.wide_item_quad; ta.wide_n_items = ps.wide_n_items;
-                ta.wide_max_items = wide_max_items; ta.wide_rows_per_block = p.wide_rows_per_block;
-                ta.wide_nt = wide_rows_nt(s) ? 1u : 0u;
-                ta.list_once = p.list_once ? 1u : 0u;
-                if (s->opt.fork_wide) {
-                    if (!sc.side) {
-                        HIP_TRY(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
-                        HIP_TRY(hipEventCreateWithFlags(&sc.ev_fork, hipEventDisableTiming));
-                        HIP_TRY(hipEventCreateWithFlags(&sc.ev_join, hipEventDisableTiming));
-                    }
-                    ta.side_stream = sc.side; ta.ev_fork = sc.ev_fork; ta.ev_join = sc.ev_join; ta.fork_wide_first = s->opt.fork_wide >= 2 ? 1u : 0u;
-                }
+            ta.side_stream = sc.side; ta.ev_fork = sc.ev_fork; ta.ev_join = sc.ev_join; ta.fork_wide_first = s->opt.fork_wide >= 2 ? 1u : 0u;
+        }
+        s->counters.kernel_launches += 1;
+    }
+    HIP_TRY(launch_tile_filter(ta, stream));
+    s->counters.kernel_launches += 3;
+    if (rt.deferred) {
+        // the k-th smallest upper bound per query, then every band entry of the call on the whole chip (also for ONE query:
+        // a single block evaluating K = 100 rows of 4 KB took 224 us inside the merge, 490 -> 390 us per call); the merge
+        // then sees exact keys only.  (Part of the re-rank group: inside its timing events.)
+        pqv::MergeArgs rm{};
+        rm.nq = nq; rm.k = k; rm.cand_keys = ta.cand_keys; rm.cand_keys_rw = ta.cand_keys; rm.cand_vals = ta.cand_vals;
+        rm.cand_cnt = ta.cand_cnt; rm.cand_cap = ccap; rm.cand_lb = ta.cand_lb;
+        rm.mat = s->d_mat; rm.queries = d_queries_s; rm.dim = s->sdim; rm.resolve_stats = s->d_stats.as<unsigned long long>();
+        // (one query, K = 100: the block evaluating its 100 defining rows alone is 50 of resolve_select's 81 us; the whole
+        //  chip evaluates the 380-row band of the single cut in 13)
+        rm.resolve_two_cuts = nq >= 32 ? 1 : 0;
+        HIP_TRY(sc.s_work.ensure(static_cast<size_t>(nq) * ccap * sizeof(uint32_t) * 2));
+        const bool counter_clean = sc.s_nwork.p != nullptr;       // (cleared by the previous call's final merge on this lane)
+        HIP_TRY(sc.s_nwork.ensure(sizeof(uint32_t)));
+        HIP_TRY(launch_resolve(rm, sc.s_work.p, sc.s_nwork.as<uint32_t>(), counter_clean, stream));
+        s->counters.kernel_launches += 2;
+    }
+    return PQV_OK;
+}
+// stage 2b, the two older forms: the f32 tile filter behind an exact seed window, and the exact tile re-rank
+static int enqueue_tile_forms(TopkCall &c, pqv::TileArgs &ta) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; const TopkPlan &p = c.p; hipStream_t stream = c.stream; const uint32_t nq = c.nq, k = c.k;
+    if (p.filter) {
+        TileArgs seed = ta;          // exact on rows [0, seed_rows) of every list: slot chunk 0
+        seed.row_offset = 0; seed.slot_base = 0; seed.grid_x = 1; seed.row_end = p.seed_rows;
+        seed.rows_per_block = std::max<uint32_t>(256, p.seed_rows);     // one 64-row tile per wave at least
+        HIP_TRY(launch_tile_rerank(seed, stream));
+        ta.row_offset = p.seed_rows; ta.slot_base = 4; ta.grid_x = p.filter_bpl;
+        ta.rows_per_block = p.filter_rows_per_block; ta.filter_variant = 1;
+        HIP_TRY(launch_seed_threshold(ta.part_keys, nq, p.np, p.slots_per_pair, k, ta.gthr, stream));
+        HIP_TRY(launch_tile_filter(ta, stream));
+        s->counters.kernel_launches += 2;
+    } else {
+        ta.row_offset = 0; ta.slot_base = 0; ta.grid_x = p.rr_bpl;
+        HIP_TRY(launch_tile_rerank(ta, stream));
+    }
+    return PQV_OK;
+}
+// stage 2, the tile paths: the pair sort, the arguments every tile kernel shares, then the wide screen or one of the older forms
+static int enqueue_tile_rerank(TopkCall &c) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const TopkRoute &rt = c.rt; hipStream_t stream = c.stream;
+    const uint32_t nq = c.nq, k = c.k; const float *d_queries_s = c.d_queries_s; const uint64_t max_pos = c.max_pos, *pair_end = c.pair_end;
+    const PairQuantArgs &pq_args = c.pq_args; hipEvent_t *ev = c.ev;
+    PairSortArgs ps{};
+    if (int rc = enqueue_pair_sort(c, ps)) return rc;
+    TileArgs ta{};
+    ta.mat = s->d_mat; ta.row_of = s->d_row_of; ta.list_off = s->d_list_off.as<uint64_t>();
+    ta.queries = d_queries_s; ta.cand_base = sc.s_cand_base.as<uint64_t>();
+    ta.pairs = ps.pairs; ta.groups = ps.groups; ta.n_groups = ps.n_groups; ta.max_groups = p.max_groups;
+    ta.nq = nq; ta.nprobe = p.np; ta.dim = s->sdim; ta.k = k;
+    ta.quads = ps.quads; ta.n_quads = ps.n_quads; ta.max_quads = p.max_quads; ta.quad_width = p.quad_width;
+    ta.rows_per_block = p.rr_rows_per_block; ta.blocks_per_list = p.rr_bpl; ta.max_pos = max_pos; ta.pair_end = pair_end;
+    ta.slots_per_pair = p.slots_per_pair; ta.slot_base = 0; ta.n_part = p.n_part_rr;
+    ta.gthr = sc.s_gthr.as<unsigned long long>();
+    ta.part_keys = sc.s_part_keys.as<uint64_t>(); ta.part_vals = sc.s_part_vals.as<uint32_t>();
+    if (p.filter && !(p.quad && p.i8)) { if (int rc = ensure_row_norms(s, stream)) return rc; }    // (the f32 / f16 screens read the rows' norms)
+    ta.row_norm2 = s->d_row_norm2.as<float>(); ta.norm_by_pos = s->images_only ? 1 : 0;
+    ta.stats = s->d_stats.as<unsigned long long>();
+    ta.xcd_swizzle = 0;
+    if (rt.screened) {
+        if (int rc = ensure_blocked_copy(s, rt.operand, stream)) return rc;     // built at creation; here only after an option change
+        ta.mat_blk = static_cast<const float4 *>(s->d_mat_blk_op[rt.operand].p);
+        ta.blk_off = s->d_blk_off.as<uint64_t>();
+        ta.block_waves = p.block_waves;
+        if (p.f16) {
+            ta.f16 = 1; ta.scale = s->f16_scale; ta.scale2 = s->f16_scale * s->f16_scale;
+            ta.query_maxabs = sc.s_qmax.as<float>();
+        }
+        if (p.i8) {
+            // residual form: one image per (query, probed list) pair -- the query's residual against that list's centre at
+            // that list's scale -- + the pair's lower bound from the triangle inequality on the centre (pair_lb);
+            // one-centre form: one image per query (every list shares centre and scale)
+            const bool per_pair = s->i8_residual;
+            if (!c.quant_done) {
+                HIP_TRY(launch_quantize_pairs_i8(pq_args.queries, pq_args.probe, pq_args.center, pq_args.scale, pq_args.half, pq_args.radius,
+                                                 pq_args.n_pairs, pq_args.nprobe, pq_args.dim, pq_args.q_i8, pq_args.q_n2i, pq_args.q_res,
+                                                 pq_args.q_resu, pq_args.pair_lb, stream));
                 s->counters.kernel_launches += 1;
             }
-            HIP_TRY(launch_tile_filter(ta, stream));
-            use_cand = true;
-            s->counters.kernel_launches += 3;
-            if (use_defer) {
-                // the k-th smallest upper bound per query, then every band entry of the call on the whole chip (also for ONE query:
-                // a single block evaluating K = 100 rows of 4 KB took 224 us inside the merge, 490 -> 390 us per call); the merge
-                // then sees exact keys only.  (Part of the re-rank group: inside its timing events.)
-                pqv::MergeArgs rm{};
-                rm.nq = nq; rm.k = k; rm.cand_keys = ta.cand_keys; rm.cand_keys_rw = ta.cand_keys; rm.cand_vals = ta.cand_vals;
-                rm.cand_cnt = ta.cand_cnt; rm.cand_cap = ccap; rm.cand_lb = ta.cand_lb;
-                rm.mat = s->d_mat; rm.queries = d_queries_s; rm.dim = s->sdim; rm.resolve_stats = s->d_stats.as<unsigned long long>();
-                // (one query, K = 100: the block evaluating its 100 defining rows alone is 50 of resolve_select's 81 us; the whole
-                //  chip evaluates the 380-row band of the single cut in 13)
-                rm.resolve_two_cuts = nq >= 32 ? 1 : 0;
-                HIP_TRY(sc.s_work.ensure(static_cast<size_t>(nq) * ccap * sizeof(uint32_t) * 2));
-                const bool counter_clean = sc.s_nwork.p != nullptr;       // (cleared by the previous call's final merge on this lane)
-                HIP_TRY(sc.s_nwork.ensure(sizeof(uint32_t)));
-                HIP_TRY(launch_resolve(rm, sc.s_work.p, sc.s_nwork.as<uint32_t>(), counter_clean, stream));
-                s->counters.kernel_launches += 2;
-            }
-        } else if (p.filter) {
-            TileArgs seed = ta;          // exact on rows [0, seed_rows) of every list: slot chunk 0
-            seed.row_offset = 0; seed.slot_base = 0; seed.grid_x = 1; seed.row_end = p.seed_rows;
-            seed.rows_per_block = std::max<uint32_t>(256, p.seed_rows);     // one 64-row tile per wave at least
-            HIP_TRY(launch_tile_rerank(seed, stream));
-            ta.row_offset = p.seed_rows; ta.slot_base = 4; ta.grid_x = p.filter_bpl;
-            ta.rows_per_block = p.filter_rows_per_block; ta.filter_variant = 1;
-            HIP_TRY(launch_seed_threshold(ta.part_keys, nq, p.np, p.slots_per_pair, k, ta.gthr, stream));
-            HIP_TRY(launch_tile_filter(ta, stream));
-            s->counters.kernel_launches += 2;
-        } else {
-            ta.row_offset = 0; ta.slot_base = 0; ta.grid_x = p.rr_bpl;
-            HIP_TRY(launch_tile_rerank(ta, stream));
+            ta.i8 = 1; ta.i8_pair_images = per_pair ? 1 : 0;
+            ta.q_i8 = static_cast<const int8_t *>(sc.s_qi8.p); ta.q_n2i = sc.s_qn2i.as<int>(); ta.q_res = sc.s_qres.as<float>();
+            ta.q_resu = sc.s_qresu.as<float>(); ta.pair_lb = (per_pair && s->opt.pair_prune) ? sc.s_pair_lb.as<float>() : nullptr;
+            ta.list_scale = s->d_list_scale.as<float>();
+            ta.row_n2i = s->d_row_n2i.as<int>(); ta.row_res = s->d_row_res.as<float>();
         }
-        if (ev[2]) HIP_TRY(hipEventRecord(ev[2], stream));
-        s->counters.kernel_launches += 3;
+        // quad-to-XCD affinity: on by default for the global-query variant, whose per-quad operand copies
+        // must stay L2-resident
+        // (8-wave blocks: the quads of one cluster on one XCD, so a list's second pass finds rows in that L2: C3 2.51 -> 2.44 ms)
+        ta.xcd_swizzle = s->opt.quad_xcd >= 0 ? s->opt.quad_xcd : (rt.q_global ? 1 : p.block_waves == 8 ? 2 : 0);
+        if (rt.q_global) {
+            // rows too long to stage a quad's queries in LDS: blocked copy per quad in global memory
+            HIP_TRY(sc.s_qblk.ensure(static_cast<size_t>(p.max_quads) * p.quad_width * s->sdim * sizeof(float)));
+            HIP_TRY(launch_pack_queries(d_queries_s, ps.pairs, ps.quads, ps.n_quads, p.max_quads, p.np, s->sdim,
+                                        p.quad_width / 16, sc.s_qblk.p, stream));
+            ta.q_blk = static_cast<const float4 *>(sc.s_qblk.p);
+        }
     }
-    StreamArgs ra{};
+    if (p.filter) ta.query_norm2 = sc.s_qnorm.as<float>();     // filled by the probe merge
+    if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
+    if (int rc = rt.screened ? enqueue_wide_screen(c, ps, ta) : enqueue_tile_forms(c, ta)) return rc;
+    if (ev[2]) HIP_TRY(hipEventRecord(ev[2], stream));
+    s->counters.kernel_launches += 3;
+    return PQV_OK;
+}
+// The arguments every candidate stream pass shares (top-k and range; after the probe: a capped table's pair ends are its output).  The
+// caller adds its split (rows_per_block, blocks_per_list) and its outputs: the per-wave lists, or the range segments.
+static pqv::StreamArgs stream_args(const pqv_searcher *s, Scratch &sc, const float *d_queries_s, uint32_t nq, uint32_t np, uint32_t k,
+                                   uint64_t max_candidates, int metric) {
+    pqv::StreamArgs ra{};
     ra.mat = s->d_mat; ra.row_of = s->d_row_of; ra.list_off = s->d_list_off.as<uint64_t>();
     ra.probe = sc.s_probe.as<uint32_t>(); ra.cand_base = sc.s_cand_base.as<uint64_t>();
-    ra.queries = d_queries_s; ra.nq = nq; ra.nprobe = p.np; ra.dim = s->sdim; ra.k = k;
-    ra.rows_per_block = p.rr_rows_per_block; ra.blocks_per_list = p.rr_bpl;
-    ra.max_pos = max_pos; ra.pair_end = pair_end; ra.metric = metric;
-    ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
-    if (!p.tile) {
-        if (ev[1]) HIP_TRY(hipEventRecord(ev[1], stream));
-        if (mask) {
-            HIP_TRY(launch_filtered_stream(ra, mask, s->d_stats.as<unsigned long long>(), pm.n_cand, STREAM_TOPK, stream,
-                                           distinct ? sc.s_part_grp.as<int64_t>() : nullptr, rank_limit));
-        } else if (metric == PQV_DOT) {
-            HIP_TRY(launch_dot_stream(ra, nullptr, STREAM_TOPK, stream));
-        } else {
-            HIP_TRY(launch_stream(ra, STREAM_TOPK, stream));
-        }
-        if (ev[2]) HIP_TRY(hipEventRecord(ev[2], stream));
+    ra.queries = d_queries_s; ra.nq = nq; ra.nprobe = np; ra.dim = s->sdim; ra.k = k;
+    ra.max_pos = max_candidates ? max_candidates : ~0ull; ra.metric = metric;
+    ra.pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
+    return ra;
+}
+// stage 3 of a distinct / grouped call: the fold with at most one entry per group (distinct_merge_kernel -- no tie flag, k_out == k),
+// then a grouped call's second pass, or the rows-per-group fill of a one-row-per-group call
+static int enqueue_group_fold(TopkCall &c, const pqv::StreamArgs &ra) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const SearchRequest *rq = c.rq; hipStream_t stream = c.stream;
+    const uint32_t nq = c.nq, k = c.k, k_out = c.k_out;
+    if (p.tile || k_out != k || c.d_tie) return fail(PQV_ERR_INVALID, "distinct call on a non-distinct plan");
+    DistinctMergeArgs dm{};
+    dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = sc.s_part_grp.as<int64_t>();
+    dm.nq = nq; dm.n_part = p.n_part_rr; dm.k = k; dm.elem_size = rq->groups.col->elem_size();
+    dm.ids = s->d_final_ids; dm.row_idx = c.d_row_idx; dm.dist = c.d_dist; dm.group_key = c.g_keys; dm.n_found = c.g_n_found;
+    dm.sqrt_out = c.sqrt_out;
+    if (c.two_pass) { dm.row_idx = sc.s_g1_rows.as<uint32_t>(); dm.dist = sc.s_g1_dist.as<float>(); }
+    HIP_TRY(launch_distinct_merge(dm, stream));
+    if (c.two_pass) {
+        // pass 2: the k groups as a sorted set per query, the walk again over their rows only, and the fold (no host step between)
+        const pqv_row_keys *gk = rq->groups.col;
+        HIP_TRY(launch_group_set(c.g_keys, c.g_n_found, nq, k, sc.s_gset_keys.as<int64_t>(), sc.s_gset_slot.as<uint32_t>(), stream));
+        GroupedArgs ga{};
+        ga.bits = rq->rows.bits; ga.stats = s->d_stats.as<unsigned long long>(); ga.key_pos = gk->d_key_pos.p;
+        ga.valid_pos = gk->valid_image(); ga.elem_size = dm.elem_size;
+        ga.set_keys = sc.s_gset_keys.as<int64_t>(); ga.set_slot = sc.s_gset_slot.as<uint32_t>(); ga.n_found = c.g_n_found;
+        ga.k = k; ga.group_size = c.gm; ga.km = static_cast<uint32_t>(c.km);
+        ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
+        ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
+        ga.rank_limit = c.rank_limit;      // (an expanding call: both passes walk the same ranks)
+        if (rq->filtered()) HIP_TRY(launch_grouped_filter_stream(ra, ga, group_filter_args(rq), stream));
+        else HIP_TRY(launch_grouped_stream(ra, ga, stream));
+        GroupedMergeArgs gma{};
+        gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
+        gma.nq = nq; gma.n_part = p.n_part_rr; gma.k = k; gma.group_size = c.gm; gma.km = ga.km;
+        gma.ids = s->d_final_ids; gma.row_idx = c.d_row_idx; gma.dist = c.d_dist; gma.group_rows = rq->groups.d_rows; gma.sqrt_out = c.sqrt_out;
+        HIP_TRY(launch_grouped_merge(gma, stream));
+        s->counters.kernel_launches += 3;
+    } else if (c.gm == 1 && rq->groups.d_rows) {
+        HIP_TRY(launch_group_rows_fill(c.g_n_found, nq, k, rq->groups.d_rows, stream));
+        s->counters.kernel_launches += 1;
     }
-
-    // 3. fold the per-wave lists
-    if (distinct) {      // (at most one entry per group: distinct_merge_kernel -- no tie flag, k_out == k)
-        if (p.tile || k_out != k || d_tie) return fail(PQV_ERR_INVALID, "distinct call on a non-distinct plan");
-        DistinctMergeArgs dm{};
-        dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = sc.s_part_grp.as<int64_t>();
-        dm.nq = nq; dm.n_part = p.n_part_rr; dm.k = k; dm.elem_size = mask->group->dtype == PQV_COL_I32 ? 4u : 8u;
-        dm.ids = s->d_final_ids; dm.row_idx = d_row_idx; dm.dist = d_dist; dm.group_key = g_keys; dm.n_found = g_n_found;
-        dm.sqrt_out = sqrt_out;
-        if (two_pass) { dm.row_idx = sc.s_g1_rows.as<uint32_t>(); dm.dist = sc.s_g1_dist.as<float>(); }
-        HIP_TRY(launch_distinct_merge(dm, stream));
-        if (two_pass) {
-            // pass 2: the k groups as a sorted set per query, the walk again over their rows only, and the fold (no host step between)
-            const pqv_row_keys *gk = mask->group;
-            HIP_TRY(launch_group_set(g_keys, g_n_found, nq, k, sc.s_gset_keys.as<int64_t>(), sc.s_gset_slot.as<uint32_t>(), stream));
-            GroupedArgs ga{};
-            ga.bits = mask->bits; ga.stats = s->d_stats.as<unsigned long long>(); ga.key_pos = gk->d_key_pos.p;
-            ga.valid_pos = gk->has_valid ? gk->d_valid_pos.as<uint64_t>() : nullptr; ga.elem_size = dm.elem_size;
-            ga.set_keys = sc.s_gset_keys.as<int64_t>(); ga.set_slot = sc.s_gset_slot.as<uint32_t>(); ga.n_found = g_n_found;
-            ga.k = k; ga.group_size = gm; ga.km = static_cast<uint32_t>(km);
-            ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
-            ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
-            ga.rank_limit = rank_limit;      // (an expanding call: both passes walk the same ranks)
-            if (mask->keys) HIP_TRY(launch_grouped_filter_stream(ra, ga, group_filter_args(mask), stream));
-            else HIP_TRY(launch_grouped_stream(ra, ga, stream));
-            GroupedMergeArgs gma{};
-            gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
-            gma.nq = nq; gma.n_part = p.n_part_rr; gma.k = k; gma.group_size = gm; gma.km = ga.km;
-            gma.ids = s->d_final_ids; gma.row_idx = d_row_idx; gma.dist = d_dist; gma.group_rows = mask->d_group_rows; gma.sqrt_out = sqrt_out;
-            HIP_TRY(launch_grouped_merge(gma, stream));
-            s->counters.kernel_launches += 3;
-        } else if (gm == 1 && mask->d_group_rows) {
-            HIP_TRY(launch_group_rows_fill(g_n_found, nq, k, mask->d_group_rows, stream));
-            s->counters.kernel_launches += 1;
-        }
-        if (ev[3]) HIP_TRY(hipEventRecord(ev[3], stream));
-        if (int rc = lane_release(sc, stream)) return rc;
-        s->counters.kernel_launches += 4;
-        return PQV_OK;
-    }
+    return PQV_OK;
+}
+// stage 3 of every other call: the final merge of the per-wave lists (and the wide screen's candidate buffers)
+static int enqueue_plain_fold(TopkCall &c, const pqv::StreamArgs &ra) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const TopkRoute &rt = c.rt; hipStream_t stream = c.stream;
+    const uint32_t nq = c.nq, k = c.k;
     MergeArgs fm{};
     fm.part_keys = ra.part_keys; fm.part_vals = ra.part_vals;
     fm.nq = nq; fm.n_part = p.n_part_rr; fm.k_part = k; fm.k = k;
-    fm.ids = s->d_final_ids; fm.row_idx = d_row_idx; fm.dist = d_dist; fm.n_found = d_n_found;
-    fm.sqrt_out = sqrt_out; fm.k_out = k_out; fm.tie_flag = d_tie;
-    if (use_cand) {
+    fm.ids = s->d_final_ids; fm.row_idx = c.d_row_idx; fm.dist = c.d_dist; fm.n_found = c.d_n_found;
+    fm.sqrt_out = c.sqrt_out; fm.k_out = c.k_out; fm.tie_flag = c.d_tie;
+    if (rt.screened) {        // wide screened path: the final merge also reads the candidate buffers
         fm.cand_keys = sc.s_cand_keys.as<uint64_t>(); fm.cand_vals = sc.s_cand_vals.as<uint32_t>();
         fm.cand_cnt = sc.s_cand_cnt.as<uint32_t>(); fm.cand_cap = cand_cap_for(s, k);
         fm.spilled = sc.s_spilled.as<uint32_t>();
         fm.part_flags = sc.s_part_flags.as<uint8_t>();       // row stride: (n_part + 3) / 4 * 4 == n_part (a multiple of 4 waves)
     }
-    if (use_defer) fm.zero_after = sc.s_nwork.as<uint32_t>();
-    if (metric == PQV_DOT) {     // (keys carry ord(dist): dot_merge_kernel undoes it; no tie flags to raise)
+    if (rt.deferred) fm.zero_after = sc.s_nwork.as<uint32_t>();
+    if (c.metric == PQV_DOT) {     // (keys carry ord(dist): dot_merge_kernel undoes it; no tie flags to raise)
         if (p.tile) return fail(PQV_ERR_INVALID, "PQV_DOT call on a screened plan");
         HIP_TRY(launch_dot_merge(fm, stream));
     } else
     HIP_TRY(launch_merge_final(fm, stream));
-    if (ev[3]) HIP_TRY(hipEventRecord(ev[3], stream));
+    return PQV_OK;
+}
+
+// Enqueue probe -> probe-merge -> re-rank -> final merge for one batch on `stream`: the stages above, in order.
+// `k` is the list length the kernels work with; the first k_out entries are written out.
+// With k == k_out + 1 the merge can also flag queries whose output distances tie (d_tie).
+// Every buffer of both passes of a grouped call is sized (group_buffers) before the first kernel behind the query padding.
+int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uint32_t k,
+                 uint32_t k_out, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                 uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand,
+                 uint32_t *d_tie, hipStream_t stream, Scratch &sc, const SearchRequest *rq = nullptr) {
+    using namespace pqv;
+    // an expanding call (pqv_topk_expand): the probe ranks P = min(max_nprobe, n_clusters) lists per query (expand_depth)
+    const bool expand = rq && rq->expanding(), distinct = rq && rq->distinct();
+    const uint32_t p0 = probe_count(s, nprobe);
+    nprobe = probe_arg(rq, nprobe);
+    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, rq != nullptr);
+    if (expand && (s->n_files || p.tile || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
+        return fail(PQV_ERR_INVALID, "expanding call on a plan that cannot expand");
+    const TopkRoute rt = topk_route(s, p, nq, k);
+    TopkCall c{s, sc, stream, p, rt, rq, nq, k, k_out, p0, max_candidates, max_candidates ? max_candidates : ~0ull, metric, sqrt_out,
+               d_queries, d_queries, d_row_idx, d_dist, d_n_found, d_tie};
+    if (int rc = pad_queries(c)) return rc;
+
+    // 1. centroid probe (its scratch first: the arguments below point into it)
+    if (int rc = probe_merge_args(s, sc, p, nq, max_candidates, c.pm)) return rc;
+    if (d_n_cand) c.pm.n_cand = d_n_cand;
+    // (a request: candidate_rows and embeddings_fetched -- the considered rows -- are counted by the stream kernel)
+    c.pm.stats = rq ? nullptr : s->d_stats.as<unsigned long long>();
+    if (int rc = group_buffers(c)) return rc;
+    if (int rc = timing_events(s, c.ev)) return rc;
+    if (c.ev[0]) HIP_TRY(hipEventRecord(c.ev[0], stream));
+    if (int rc = enqueue_probe_stage(c, nprobe)) return rc;
+    if (expand) { if (int rc = expand_depth(c)) return rc; }
+
+    // 2. candidate re-rank + per-wave top-k
+    if (p.tile) { if (int rc = enqueue_tile_rerank(c)) return rc; }
+    StreamArgs ra = stream_args(s, sc, c.d_queries_s, nq, p.np, k, max_candidates, metric);
+    ra.rows_per_block = p.rr_rows_per_block; ra.blocks_per_list = p.rr_bpl;
+    ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
+    if (!p.tile) {
+        if (c.ev[1]) HIP_TRY(hipEventRecord(c.ev[1], stream));
+        HIP_TRY(launch_stream_pass(ra, rq, s->d_stats.as<unsigned long long>(), c.pm.n_cand, STREAM_TOPK, stream,
+                                   distinct ? sc.s_part_grp.as<int64_t>() : nullptr, c.rank_limit));
+        if (c.ev[2]) HIP_TRY(hipEventRecord(c.ev[2], stream));
+    }
+
+    // 3. fold the per-wave lists, and the epilogue
+    if (int rc = distinct ? enqueue_group_fold(c, ra) : enqueue_plain_fold(c, ra)) return rc;
+    if (c.ev[3]) HIP_TRY(hipEventRecord(c.ev[3], stream));
     if (int rc = lane_release(sc, stream)) return rc;
     s->counters.kernel_launches += 4;
     return PQV_OK;
@@ -4374,9 +4484,9 @@ bool grouped_beyond_kernel_lists(const pqv_searcher *s, uint32_t k, uint32_t gro
 }
 // PQV_DOT (pqv.h): every entry point works within the kernels' lists, and keyed / distinct calls do not take it.  Checked behind
 // validate_topk, before any device work.
-int dot_checks(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric, const MaskView *mask) {
+int dot_checks(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric, const SearchRequest *rq) {
     if (metric != PQV_DOT) return PQV_OK;
-    if (mask && (mask->keys || mask->group)) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
+    if (rq && (rq->filtered() || rq->distinct())) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
     if (beyond_kernel_lists(s, k, nprobe)) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT takes k <= 1024 and at most 1024 probed lists per query");
     return PQV_OK;
 }
@@ -4590,13 +4700,13 @@ int host_probe(const pqv_searcher *s, Scratch &sc, const float *d_queries, uint3
 // candidate distance on the GPU, the reference's heap on the host.  Correct for any k / nprobe; not a fast path.
 int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                    uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found,
-                   uint64_t *n_candidates, const MaskView *mask = nullptr) {
+                   uint64_t *n_candidates, const SearchRequest *rq = nullptr) {
     using namespace pqv;
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
     std::vector<uint32_t> clusters;
     RowFilter allow;
     for (uint32_t q = 0; q < nq; ++q) {
-        if (int rc = row_filter(s, mask, q, allow)) return rc;
+        if (int rc = row_filter(s, rq, q, allow)) return rc;
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q) * s->dim, static_cast<size_t>(s->dim) * sizeof(float),
                                hipMemcpyHostToDevice, s->stream));
         uint64_t total = 0;
@@ -4648,12 +4758,12 @@ static int cosine_queries_host(const pqv_searcher *s, const float *queries, uint
 static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, uint32_t nq, uint32_t k,
                                uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
-                               void *d_tie_flags, void *hip_stream, const MaskView *mask = nullptr) {
+                               void *d_tie_flags, void *hip_stream, const SearchRequest *rq = nullptr) {
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
-    if (int rc = dot_checks(s, k, nprobe, metric, mask)) return rc;
+    if (int rc = dot_checks(s, k, nprobe, metric, rq)) return rc;
     if (int rc = table_max_candidates(s, max_candidates)) return rc;
     if (d_tie_flags && k > 1023) return fail(PQV_ERR_UNSUPPORTED, "tie flags need a runner-up entry: k <= 1023");
-    if (mask && mask->group_size && grouped_beyond_kernel_lists(s, k, mask->group_size, nprobe))
+    if (rq && rq->groups.size && grouped_beyond_kernel_lists(s, k, rq->groups.size, nprobe))
         return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_grouped_device takes k * group_size <= 1024 and at most 1024 probed lists per query");
     if (beyond_kernel_lists(s, k, nprobe))
         return fail(PQV_ERR_UNSUPPORTED, s->n_files ? "the device entry points take k <= 1024 and at most 1024 probed lists per query (the sum of "
@@ -4674,7 +4784,7 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
         HIP_TRY(lane->s_qcos.ensure(static_cast<size_t>(nq) * s->dim * sizeof(float)));
         HIP_TRY(pqv::launch_normalize_rows(static_cast<const float *>(d_queries), s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), stream));
         if (int rc = pqv_topk_device_impl(s->cos.get(), lane->s_qcos.p, nq, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
-                                          d_n_found, d_n_candidates, d_tie_flags, stream, mask))
+                                          d_n_found, d_n_candidates, d_tie_flags, stream, rq))
             return rc;
         return lane_release(*lane, stream);
     }
@@ -4685,7 +4795,7 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
     const int rc = enqueue_topk(s, static_cast<const float *>(d_queries), nq, (d_tie_flags && metric != PQV_DOT) ? k + 1 : k, k, nprobe, max_candidates,
                                 metric, sqrt_out, static_cast<uint32_t *>(d_row_idx),
                                 static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
-                                static_cast<uint64_t *>(d_n_candidates), static_cast<uint32_t *>(d_tie_flags), stream, *lane, mask);
+                                static_cast<uint64_t *>(d_n_candidates), static_cast<uint32_t *>(d_tie_flags), stream, *lane, rq);
     if (rc == PQV_OK) s->counters.queries += nq;
     return rc;
 }
@@ -4705,9 +4815,9 @@ extern "C" int pqv_topk_device_flags(const pqv_searcher *s, const void *d_querie
 
 static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len,
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
-                        uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates, const MaskView *mask = nullptr) {
+                        uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates, const SearchRequest *rq = nullptr) {
     if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
-    if (int rc = dot_checks(s, k, nprobe, metric, mask)) return rc;
+    if (int rc = dot_checks(s, k, nprobe, metric, rq)) return rc;
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
     if (int rc = use_device(s->device)) return rc;
@@ -4715,7 +4825,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         std::vector<float> nq_host;
         if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
         return pqv_topk_impl(s->cos.get(), nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist, n_found,
-                             n_candidates, mask);
+                             n_candidates, rq);
     }
     std::lock_guard<std::mutex> lock(s->mu);
     // One extra merged entry (the runner-up) lets the merge kernel see ties at the k-th
@@ -4729,13 +4839,13 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     Scratch &sc = *lane;
     LaneGuard lane_guard{sc, s->stream};
     if (!dot && (k >= 1024u || beyond_kernel_lists(s, k_int, nprobe))) {
-        const int rc = topk_unbounded(s, sc, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates, mask);
+        const int rc = topk_unbounded(s, sc, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates, rq);
         const int rc2 = lane_release(sc, s->stream);
         return rc ? rc : rc2;
     }
     // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
     // (per query: partial lists, probe partial lists, candidate buffer, the int8 images of its probed pairs)
-    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(mask, nprobe), k_int, metric, mask != nullptr);
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(rq, nprobe), k_int, metric, rq != nullptr);
     const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * k_int * 12 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
                                static_cast<uint64_t>(cand_cap_for(s, k_int)) * 12 + static_cast<uint64_t>(p1.np) * (s->sdim + 32) +
                                static_cast<uint64_t>(s->sdim) * 4 + 1;
@@ -4748,17 +4858,17 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     HIP_TRY(sc.s_tie.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     std::vector<uint64_t> h_ncand(batch);
     std::vector<uint32_t> h_tie(batch), h_nf(batch);
-    const uint32_t np = probe_count(s, probe_arg(mask, nprobe));
+    const uint32_t np = probe_count(s, probe_arg(rq, nprobe));
     // an expanding call: the lists each query of the sub-batch used come back with its results
-    const bool expand = mask && mask->max_nprobe;
+    const bool expand = rq && rq->expand.max_nprobe;
     std::vector<uint32_t> h_used(expand ? batch : 0);
     if (expand) HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     // a keyed call: the kernels of a sub-batch read its own slice of the query keys (the same q0 as its queries)
-    MaskView sub{};
-    if (mask) sub = *mask;
-    if (expand) sub.d_nprobe_used = sc.s_expand_used.as<uint32_t>();
-    const MaskView *bmask = mask ? &sub : nullptr;
-    if (mask && mask->keys && !mask->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    SearchRequest sub{};
+    if (rq) sub = *rq;
+    if (expand) sub.expand.d_used = sc.s_expand_used.as<uint32_t>();
+    const SearchRequest *brq = rq ? &sub : nullptr;
+    if (rq && rq->eq_keys()) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     std::vector<uint64_t> sub_lims;
     // A call of a few queries (TopkBuilder::search is ONE) is six small pageable copies otherwise -- the query in, rows, distances,
     // counts and tie flags out, each staged and waited for by the runtime: 60-80 us around 180 us of kernels.  Small calls go
@@ -4781,7 +4891,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         // (round 5: the result block of a small call is WRITTEN by the kernels straight into the pinned buffer -- host memory the
         //  device can address -- so there is no device-to-host copy behind them, only the synchronise: PQV_SMALL_IO_DIRECT=0 keeps the copy)
         static const bool direct_out = [] { const char *e = std::getenv("PQV_SMALL_IO_DIRECT"); return !(e && *e == '0'); }();
-        if (int rc = upload_query_filter(sc, mask, sub, q0, b, sub_lims, s->stream)) return rc;
+        if (int rc = upload_query_filter(sc, rq, sub, q0, b, sub_lims, s->stream)) return rc;
         if (small_io) {
             char *ob = direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p);           // (laid out for THIS sub-batch's b)
             o_rows = reinterpret_cast<uint32_t *>(ob + 8ull * b);
@@ -4797,7 +4907,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
         if (int rc = enqueue_topk(s, sc.s_queries.as<float>(), b, k_int, k, nprobe, max_candidates, metric,
                                   sqrt_out, o_rows, o_dist, o_nf,
                                   small_io ? reinterpret_cast<uint64_t *>(direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p)) : nullptr,
-                                  o_tie, s->stream, sc, bmask))
+                                  o_tie, s->stream, sc, brq))
             return rc;
         if (expand) HIP_TRY(hipMemcpyAsync(h_used.data(), sc.s_expand_used.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         if (small_io) {
@@ -4828,7 +4938,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
             if (h_tie[i]) {
                 // tied output distances: survivors / order follow Rust's heap mechanics exactly
                 RowFilter allow;
-                if (int rc = row_filter(s, mask, static_cast<uint64_t>(q0) + i, allow)) return rc;
+                if (int rc = row_filter(s, rq, static_cast<uint64_t>(q0) + i, allow)) return rc;
                 if (int rc = replay_query_exact(s, sc, s->sdim != s->dim ? sc.s_qpad.as<float>() + static_cast<size_t>(i) * s->sdim
                                                                           : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i,
                                                 expand ? std::min<uint32_t>(std::max<uint32_t>(1, h_used[i]), np) : np,
@@ -4839,7 +4949,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
                 s->counters.exact_replays++;
             }
             if (n_found) n_found[q0 + i] = h_nf[i];
-            if (expand && mask->h_nprobe_used) mask->h_nprobe_used[q0 + i] = h_used[i];
+            if (expand && rq->expand.h_used) rq->expand.h_used[q0 + i] = h_used[i];
         }
         s->counters.queries += b;
     }
@@ -4874,12 +4984,11 @@ int grow_host(std::unique_ptr<T, HostFree> &buf, uint64_t &cap, uint64_t need) {
 int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, float radius, uint32_t nprobe,
                uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t *lims,
                std::unique_ptr<uint32_t, HostFree> &rows, std::unique_ptr<float, HostFree> &dist, uint64_t *n_within,
-               uint64_t *n_candidates, const MaskView *mask = nullptr) {
+               uint64_t *n_candidates, const SearchRequest *rq = nullptr) {
     using namespace pqv;
     hipStream_t st = s->stream;
     const uint32_t kc = s->n_clusters, np = probe_count(s, nprobe);
     const bool wide_probe = np > 1024;              // (merge_kernel's lists hold up to 1024 probed clusters)
-    const uint64_t max_pos = max_candidates ? max_candidates : ~0ull;
     // a query's segment holds its capped candidates: at most the np longest lists, at most max_candidates
     uint64_t bound = 0;
     {
@@ -4903,9 +5012,9 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
     HIP_TRY(sc.s_hit_keys.ensure(static_cast<size_t>(batch) * stride * sizeof(uint64_t)));
     HIP_TRY(sc.s_hit_vals.ensure(static_cast<size_t>(batch) * stride * sizeof(uint32_t)));
     HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
-    MaskView sub{};      // (a keyed call: each sub-batch's kernels read its own slice of the query keys)
-    if (mask) sub = *mask;
-    if (mask && mask->keys && !mask->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    SearchRequest sub{};      // (a keyed call: each sub-batch's kernels read its own slice of the query keys)
+    if (rq) sub = *rq;
+    if (rq && rq->eq_keys()) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     std::vector<uint64_t> sub_lims;
     std::vector<uint32_t> h_cnt(batch), h_probe;
     std::vector<uint64_t> h_ncand(batch), h_off(batch);
@@ -4919,7 +5028,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
         if (int rc = timing_events(s, e)) return rc;
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
                                hipMemcpyHostToDevice, st));
-        if (int rc = upload_query_filter(sc, mask, sub, q0, b, sub_lims, st)) return rc;
+        if (int rc = upload_query_filter(sc, rq, sub, q0, b, sub_lims, st)) return rc;
         if (e[0]) HIP_TRY(hipEventRecord(e[0], st));
         const float *d_q = sc.s_queries.as<float>(), *d_q_s = d_q;
         if (s->sdim != s->dim) {
@@ -4931,7 +5040,7 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             const TopkPlan p = plan_topk(s, b, nprobe, 1, metric);
             MergeArgs pm{};
             if (int rc = probe_merge_args(s, sc, p, b, max_candidates, pm)) return rc;
-            pm.stats = mask ? nullptr : s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
+            pm.stats = rq ? nullptr : s->d_stats.as<unsigned long long>();      // candidate_rows / embeddings_fetched, as a top-k call counts them
             if (int rc = enqueue_probe(s, sc, p, d_q, b, nprobe, max_candidates, pm, nullptr, 0, st, metric)) return rc;
             launches += 2;
         } else {
@@ -4939,32 +5048,23 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             if (int rc = host_probe(s, sc, d_q, b, nprobe, max_candidates, true, h_probe, h_ncand.data())) return rc;
             for (uint32_t i = 0; i < b; ++i) {
                 s->counters.candidate_rows += h_ncand[i];                         // index_exec.rs:289-299
-                if (!mask) s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(h_ncand[i], max_candidates) : h_ncand[i];
+                if (!rq) s->counters.embeddings_fetched += max_candidates ? std::min<uint64_t>(h_ncand[i], max_candidates) : h_ncand[i];
             }
         }
 
         // the hits: one pass over every (query, probed list), rows through d_mat / d_row_of (every layout)
         HIP_TRY(hipMemsetAsync(sc.s_hit_cnt.p, 0, static_cast<size_t>(b) * sizeof(uint32_t), st));
-        StreamArgs ra{};
-        ra.mat = s->d_mat; ra.row_of = s->d_row_of; ra.list_off = s->d_list_off.as<uint64_t>();
-        ra.probe = sc.s_probe.as<uint32_t>(); ra.cand_base = sc.s_cand_base.as<uint64_t>();
-        ra.queries = d_q_s; ra.nq = b; ra.nprobe = np; ra.dim = s->sdim; ra.k = 1;
+        StreamArgs ra = stream_args(s, sc, d_q_s, b, np, 1, max_candidates, metric);
         stream_split(max_len, std::max<uint64_t>(1, static_cast<uint64_t>(b) * np), ra.rows_per_block, ra.blocks_per_list);   // (as the top-k form)
-        ra.max_pos = max_pos; ra.metric = metric;
-        ra.pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
         ra.radius = radius; ra.sqrt_out = sqrt_out;
         ra.hit_cnt = sc.s_hit_cnt.as<uint32_t>(); ra.hit_keys = sc.s_hit_keys.as<uint64_t>(); ra.hit_vals = sc.s_hit_vals.as<uint32_t>();
         ra.seg_stride = stride;
         if (e[1]) HIP_TRY(hipEventRecord(e[1], st));
         for (uint32_t j0 = 0; j0 < np; j0 += 32768) {                    // gridDim.y <= 65535
             ra.j0 = j0; ra.nj = std::min<uint32_t>(32768, np - j0);
-            if (mask) {      // (the considered rows are counted by the kernel; candidate_rows too unless the host probe counted it above)
-                HIP_TRY(launch_filtered_stream(ra, &sub, s->d_stats.as<unsigned long long>(), wide_probe ? nullptr : sc.s_ncand.as<uint64_t>(),
-                                               STREAM_RANGE, st));
-            } else if (metric == PQV_DOT) {
-                HIP_TRY(launch_dot_stream(ra, nullptr, STREAM_RANGE, st));
-            } else
-            HIP_TRY(launch_stream(ra, STREAM_RANGE, st));
+            // (a request: the considered rows are counted by the kernel; candidate_rows too unless the host probe counted it above)
+            HIP_TRY(launch_stream_pass(ra, rq ? &sub : nullptr, s->d_stats.as<unsigned long long>(), wide_probe ? nullptr : sc.s_ncand.as<uint64_t>(),
+                                       STREAM_RANGE, st));
             ++launches;
         }
         if (e[2]) HIP_TRY(hipEventRecord(e[2], st));
@@ -5035,9 +5135,9 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
 static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len, float radius,
                                  uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                                  uint64_t **lims_out, uint32_t **rows_out, float **dist_out, uint64_t *n_within,
-                                 uint64_t *n_candidates, const MaskView *mask = nullptr) {
+                                 uint64_t *n_candidates, const SearchRequest *rq = nullptr) {
     if (int rc = validate_query(s, 1, nprobe, metric, max_candidates, query_len)) return rc;
-    if (int rc = dot_checks(s, 1, nprobe, metric, mask)) return rc;
+    if (int rc = dot_checks(s, 1, nprobe, metric, rq)) return rc;
     if (metric == PQV_DOT) sqrt_out = 0;      // (ignored: the range_* kernels run as order-only machinery)
     if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
     if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
@@ -5063,7 +5163,7 @@ static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, ui
         if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
         LaneGuard lane_guard{*lane, s->stream};
         if (int rc = range_body(s, *lane, queries, nq, radius, nprobe, max_candidates, max_results, metric, sqrt_out, lims.get(), rows,
-                                dist, n_within, n_candidates, mask))
+                                dist, n_within, n_candidates, rq))
             return rc;
         if (int rc = lane_release(*lane, s->stream)) return rc;
     }
@@ -5316,19 +5416,19 @@ extern "C" int pqv_row_mask_from_predicates(const pqv_searcher *s, uint32_t n_le
 }
 
 // the checks every masked entry point makes before anything else (after the searcher's own NULL check)
-static int mask_view(const pqv_searcher *s, const pqv_row_mask *mask, MaskView &mv) {
+static int mask_view(const pqv_searcher *s, const pqv_row_mask *mask, SearchRequest &mv) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!mask) return fail(PQV_ERR_INVALID, "row mask must not be NULL");
     if (mask->owner != s || mask->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
-    mv = MaskView{};
-    mv.bits = mask->d_bits.as<uint64_t>(); mv.mask = mask;
+    mv = SearchRequest{};
+    mv.rows.bits = mask->d_bits.as<uint64_t>(); mv.rows.mask = mask;
     return PQV_OK;
 }
 extern "C" int pqv_topk_masked(const pqv_searcher *s, const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len,
                                uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
@@ -5338,7 +5438,7 @@ extern "C" int pqv_topk_masked_device(const pqv_searcher *s, const pqv_row_mask 
                                       void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                       void *d_tie_flags, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
@@ -5348,7 +5448,7 @@ extern "C" int pqv_range_search_masked(const pqv_searcher *s, const pqv_row_mask
                                        float radius, uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
                                        uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
@@ -5396,25 +5496,25 @@ extern "C" void pqv_row_keys_free(pqv_row_keys *k) {
 }
 
 // the checks every keyed entry point makes before anything else: NULL handles first, nothing dereferenced before them
-static int keyed_view(const pqv_searcher *s, const pqv_row_keys *keys, const void *qkeys, uint32_t nq, const pqv_row_mask *mask, MaskView &mv) {
+static int keyed_view(const pqv_searcher *s, const pqv_row_keys *keys, const void *qkeys, uint32_t nq, const pqv_row_mask *mask, SearchRequest &mv) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
     if (nq && !qkeys) return fail(PQV_ERR_INVALID, "query keys must not be NULL");
     if (keys->owner != s || keys->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
-    mv = MaskView{};
+    mv = SearchRequest{};
     if (mask) {
         if (int rc = mask_view(s, mask, mv)) return rc;
     }
-    mv.keys = keys;
+    mv.rows.keys = keys;
     return PQV_OK;
 }
 extern "C" int pqv_topk_keyed(const pqv_searcher *s, const pqv_row_keys *keys, const int64_t *qkeys, const pqv_row_mask *mask,
                               const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates,
                               int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = keyed_view(s, keys, qkeys, nq, mask, mv)) return rc;
-        mv.h_qkeys = qkeys;
+        mv.rows.h_qkeys = qkeys;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
 }
@@ -5423,9 +5523,9 @@ extern "C" int pqv_topk_keyed_device(const pqv_searcher *s, const pqv_row_keys *
                                      int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                      void *d_tie_flags, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = keyed_view(s, keys, d_qkeys, nq, mask, mv)) return rc;
-        mv.d_qkeys = static_cast<const int64_t *>(d_qkeys);
+        mv.rows.d_qkeys = static_cast<const int64_t *>(d_qkeys);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
     });
@@ -5435,9 +5535,9 @@ extern "C" int pqv_range_search_keyed(const pqv_searcher *s, const pqv_row_keys 
                                       uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t **lims,
                                       uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = keyed_view(s, keys, qkeys, nq, mask, mv)) return rc;
-        mv.h_qkeys = qkeys;
+        mv.rows.h_qkeys = qkeys;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
     });
@@ -5467,15 +5567,15 @@ static int filter_descriptor_checks(const pqv_key_filter *f, uint32_t nq, bool h
 }
 // (descriptor_checked: the caller made filter_descriptor_checks itself, with checks of its own behind them)
 static int filtered_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *f, uint32_t nq, const pqv_row_mask *mask,
-                         bool host, MaskView &mv, bool descriptor_checked = false) {
+                         bool host, SearchRequest &mv, bool descriptor_checked = false) {
     if (!descriptor_checked) { if (int rc = filter_descriptor_checks(f, nq, host)) return rc; }
     if (int rc = keyed_view(s, keys, f->a, nq, mask, mv)) return rc;
     if (f->kind == PQV_KEY_EQ) {
-        (host ? mv.h_qkeys : mv.d_qkeys) = static_cast<const int64_t *>(f->a);
+        (host ? mv.rows.h_qkeys : mv.rows.d_qkeys) = static_cast<const int64_t *>(f->a);
     } else {
-        mv.fkind = f->kind;
-        if (host) { mv.h_fa = f->a; mv.h_fb = f->b; }
-        else { mv.d_fa = f->a; mv.d_fb = f->b; }
+        mv.rows.kind = f->kind;
+        if (host) { mv.rows.h_a = f->a; mv.rows.h_b = f->b; }
+        else { mv.rows.d_a = f->a; mv.rows.d_b = f->b; }
     }
     return PQV_OK;
 }
@@ -5483,7 +5583,7 @@ extern "C" int pqv_topk_filtered(const pqv_searcher *s, const pqv_row_keys *keys
                                  const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates,
                                  int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = filtered_view(s, keys, filter, nq, mask, true, mv)) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
@@ -5493,7 +5593,7 @@ extern "C" int pqv_topk_filtered_device(const pqv_searcher *s, const pqv_row_key
                                         int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                         void *d_tie_flags, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = filtered_view(s, keys, filter, nq, mask, false, mv)) return rc;
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
@@ -5502,7 +5602,7 @@ extern "C" int pqv_topk_filtered_device(const pqv_searcher *s, const pqv_row_key
 // ---- expanding filtered top-k (pqv.h: pqv_topk_expand) ---------------------------------------------------------------------
 // The checks of both forms up to the view, in the contract's order; nothing is dereferenced before the NULL checks.
 static int expand_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask, uint32_t nq,
-                       uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric, bool host, bool flags, MaskView &mv) {
+                       uint32_t k, uint32_t nprobe, uint32_t max_nprobe, int metric, bool host, bool flags, SearchRequest &mv) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!keys && !mask) return fail(PQV_ERR_INVALID, "pqv_topk_expand needs a row mask or row keys");
     if (!keys && filter) return fail(PQV_ERR_INVALID, "a key filter needs row keys");
@@ -5517,7 +5617,7 @@ static int expand_view(const pqv_searcher *s, const pqv_row_keys *keys, const pq
     // (the host form always carries the runner-up entry its tie replay needs)
     if (k > (flags ? 1023u : 1024u) || probe_count(s, max_nprobe) > 1024)
         return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_expand takes k <= 1024 (1023 with tie flags) and at most 1024 probed lists per query");
-    mv.max_nprobe = max_nprobe;
+    mv.expand.max_nprobe = max_nprobe;
     return PQV_OK;
 }
 extern "C" int pqv_topk_expand(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_key_filter *filter, const pqv_row_mask *mask,
@@ -5525,9 +5625,9 @@ extern "C" int pqv_topk_expand(const pqv_searcher *s, const pqv_row_keys *keys, 
                                int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates,
                                uint32_t *nprobe_used) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = expand_view(s, keys, filter, mask, nq, k, nprobe, max_nprobe, metric, true, true, mv)) return rc;
-        mv.h_nprobe_used = nprobe_used;
+        mv.expand.h_used = nprobe_used;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
 }
@@ -5536,9 +5636,9 @@ extern "C" int pqv_topk_expand_device(const pqv_searcher *s, const pqv_row_keys 
                                       int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
                                       void *d_nprobe_used, void *d_tie_flags, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = expand_view(s, keys, filter, mask, nq, k, nprobe, max_nprobe, metric, false, d_tie_flags != nullptr, mv)) return rc;
-        mv.d_nprobe_used = static_cast<uint32_t *>(d_nprobe_used);
+        mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
     });
@@ -5548,7 +5648,7 @@ extern "C" int pqv_range_search_filtered(const pqv_searcher *s, const pqv_row_ke
                                          uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t **lims,
                                          uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = filtered_view(s, keys, filter, nq, mask, true, mv)) return rc;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
@@ -5557,16 +5657,16 @@ extern "C" int pqv_range_search_filtered(const pqv_searcher *s, const pqv_row_ke
 
 // ---- distinct top-k (pqv.h: pqv_topk_distinct) -----------------------------------------------------------------------------
 // the checks both entry points make before anything else: NULL handles first, nothing dereferenced before them
-static int distinct_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, MaskView &mv) {
+static int distinct_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, SearchRequest &mv) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
     if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");       // (validate_topk's, ahead of everything that reads a handle)
     if (keys->owner != s || keys->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
-    mv = MaskView{};
+    mv = SearchRequest{};
     if (mask) {
         if (int rc = mask_view(s, mask, mv)) return rc;
     }
-    mv.group = keys;
+    mv.groups.col = keys;
     return PQV_OK;
 }
 namespace {
@@ -5574,16 +5674,16 @@ namespace {
 // the masked range machinery -- radius +inf, d2 out, under the position image (key validity AND shared mask) -- and the first row
 // of every key value kept on the host.  Correct for any k / nprobe; not a fast path.
 // m (a grouped call, pqv.h: pqv_topk_grouped): the first m rows of each of those key values, row_idx / dist [nq, k, m], group_rows [nq, k].
-int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const MaskView *mv, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const SearchRequest *mv, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                        uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key,
                        uint32_t *n_found, uint64_t *n_candidates, uint32_t m = 1, uint32_t *group_rows = nullptr) {
-    const pqv_row_keys *gk = mv->group;
+    const pqv_row_keys *gk = mv->groups.col;
     if (int rc = keys_host_rows(s, gk)) return rc;
     // the image of the considered positions, made on the host from the two images (n / 8 bytes each)
     const uint64_t n_words = (s->n + 63) / 64 + 1;
     std::vector<uint64_t> img, other;
     try { img.assign(n_words, ~0ull); other.resize(n_words); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
-    for (const void *src : {gk->has_valid ? gk->d_valid_pos.p : nullptr, static_cast<void *>(const_cast<uint64_t *>(mv->bits))}) {
+    for (const void *src : {gk->has_valid ? gk->d_valid_pos.p : nullptr, static_cast<void *>(const_cast<uint64_t *>(mv->rows.bits))}) {
         if (!src) continue;
         HIP_TRY(hipMemcpy(other.data(), src, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
         for (uint64_t w = 0; w < n_words; ++w) img[w] &= other[w];
@@ -5592,10 +5692,10 @@ int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const MaskView *mv, c
     DevBuf d_img;
     HIP_TRY(d_img.alloc(n_words * sizeof(uint64_t)));
     HIP_TRY(hipMemcpy(d_img.p, img.data(), n_words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    MaskView rv{};
-    rv.bits = d_img.as<uint64_t>();
+    SearchRequest rv{};
+    rv.rows.bits = d_img.as<uint64_t>();
     // (a filtered call: the per-query filter travels beside the image, as in pqv_range_search_filtered)
-    rv.keys = mv->keys; rv.h_qkeys = mv->h_qkeys; rv.fkind = mv->fkind; rv.h_fa = mv->h_fa; rv.h_fb = mv->h_fb;
+    rv.rows.keys = mv->rows.keys; rv.rows.h_qkeys = mv->rows.h_qkeys; rv.rows.kind = mv->rows.kind; rv.rows.h_a = mv->rows.h_a; rv.rows.h_b = mv->rows.h_b;
     std::unique_ptr<uint64_t, HostFree> lims(static_cast<uint64_t *>(std::malloc((static_cast<size_t>(nq) + 1) * sizeof(uint64_t))));
     std::unique_ptr<uint32_t, HostFree> rows(static_cast<uint32_t *>(std::malloc(sizeof(uint32_t))));
     std::unique_ptr<float, HostFree> d2(static_cast<float *>(std::malloc(sizeof(float))));
@@ -5650,8 +5750,8 @@ int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const MaskView *mv, c
     return PQV_OK;
 }
 }  // namespace
-// (a grouped call: mv->group_size = m >= 1, row_idx / dist [nq, k, m] and group_rows [nq, k]; m == 1 is the distinct call plus group_rows)
-static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
+// (a grouped call: mv->groups.size = m >= 1, row_idx / dist [nq, k, m] and group_rows [nq, k]; m == 1 is the distinct call plus group_rows)
+static int pqv_topk_distinct_impl(const pqv_searcher *s, const SearchRequest *mv, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
                                   uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
                                   int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates, uint32_t *group_rows = nullptr) {
     if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
@@ -5665,13 +5765,13 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
         return pqv_topk_distinct_impl(s->cos.get(), mv, nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist,
                                       group_key, n_found, n_candidates, group_rows);
     }
-    const uint32_t m = std::max<uint32_t>(1, mv->group_size);
+    const uint32_t m = std::max<uint32_t>(1, mv->groups.size);
     std::lock_guard<std::mutex> lock(s->mu);
     Scratch *lane = nullptr;
     if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
     Scratch &sc = *lane;
     LaneGuard lane_guard{sc, s->stream};
-    const bool expand = mv->max_nprobe != 0;       // (pqv_topk_distinct_expand: within the kernels' lists, checked by its view)
+    const bool expand = mv->expanding();       // (pqv_topk_distinct_expand: within the kernels' lists, checked by its view)
     if (!expand && grouped_beyond_kernel_lists(s, k, m, nprobe)) {
         const int rc = distinct_unbounded(s, sc, mv, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, group_key, n_found,
                                           n_candidates, m, group_rows);
@@ -5693,12 +5793,12 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
     if (group_rows) HIP_TRY(sc.s_grows_out.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
     HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
     HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
-    if (mv->keys && !mv->fkind) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    if (mv->eq_keys()) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     if (expand) HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
-    MaskView sub = *mv;
-    if (expand) sub.d_nprobe_used = sc.s_expand_used.as<uint32_t>();
-    sub.d_group_out = sc.s_grp_out.as<int64_t>();
-    sub.d_group_rows = group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr;
+    SearchRequest sub = *mv;
+    if (expand) sub.expand.d_used = sc.s_expand_used.as<uint32_t>();
+    sub.groups.d_keys = sc.s_grp_out.as<int64_t>();
+    sub.groups.d_rows = group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr;
     std::vector<uint64_t> sub_lims;      // (a filtered call: each sub-batch's kernels read its own slice of the filter, IN lims rebased)
     for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
         const uint32_t b = std::min<uint32_t>(batch, nq - q0);
@@ -5719,8 +5819,8 @@ static int pqv_topk_distinct_impl(const pqv_searcher *s, const MaskView *mv, con
         if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         if (n_candidates)
             HIP_TRY(hipMemcpyAsync(n_candidates + q0, sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-        if (expand && mv->h_nprobe_used)
-            HIP_TRY(hipMemcpyAsync(mv->h_nprobe_used + q0, sc.s_expand_used.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        if (expand && mv->expand.h_used)
+            HIP_TRY(hipMemcpyAsync(mv->expand.h_used + q0, sc.s_expand_used.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
         s->counters.queries += b;
     }
@@ -5730,7 +5830,7 @@ extern "C" int pqv_topk_distinct(const pqv_searcher *s, const pqv_row_keys *keys
                                  uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                  uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
         return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
                                       n_found, n_candidates);
@@ -5740,9 +5840,9 @@ extern "C" int pqv_topk_distinct_device(const pqv_searcher *s, const pqv_row_key
                                         uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                         void *d_row_idx, void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
-        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
     });
@@ -5750,13 +5850,13 @@ extern "C" int pqv_topk_distinct_device(const pqv_searcher *s, const pqv_row_key
 
 // ---- grouped top-k (pqv.h: pqv_topk_grouped) ---------------------------------------------------------------------------------
 // distinct_view's checks with "group_size must be > 0" behind "k must be > 0" (both ahead of everything that reads a handle)
-static int grouped_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, uint32_t group_size, MaskView &mv) {
+static int grouped_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, uint32_t group_size, SearchRequest &mv) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
     if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
     if (group_size == 0) return fail(PQV_ERR_INVALID, "group_size must be > 0");
     if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
-    mv.group_size = group_size;
+    mv.groups.size = group_size;
     return PQV_OK;
 }
 extern "C" int pqv_topk_grouped(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries, uint32_t nq,
@@ -5764,7 +5864,7 @@ extern "C" int pqv_topk_grouped(const pqv_searcher *s, const pqv_row_keys *keys,
                                 int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found,
                                 uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
         return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
                                       n_found, n_candidates, group_rows);
@@ -5775,10 +5875,10 @@ extern "C" int pqv_topk_grouped_device(const pqv_searcher *s, const pqv_row_keys
                                        int sqrt_out, void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
                                        void *d_n_candidates, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
-        mv.d_group_out = static_cast<int64_t *>(d_group_key);
-        mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
+        mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
+        mv.groups.d_rows = static_cast<uint32_t *>(d_group_rows);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
     });
@@ -5788,7 +5888,7 @@ extern "C" int pqv_topk_grouped_device(const pqv_searcher *s, const pqv_row_keys
 // Both halves of the view in the contract's order: every NULL and zero check, the descriptor's included, before a handle is read.
 // group_size: nullptr for the distinct forms.
 static int group_filtered_view(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys, const pqv_key_filter *filter,
-                               const pqv_row_mask *mask, uint32_t nq, uint32_t k, const uint32_t *group_size, bool host, MaskView &mv) {
+                               const pqv_row_mask *mask, uint32_t nq, uint32_t k, const uint32_t *group_size, bool host, SearchRequest &mv) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!group_keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
     if (!filter_keys) return fail(PQV_ERR_INVALID, "a key filter needs row keys");
@@ -5799,8 +5899,8 @@ static int group_filtered_view(const pqv_searcher *s, const pqv_row_keys *group_
     if (group_keys->owner != s || group_keys->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
     // (the filter column's owner and the mask's: filtered_view)
     if (int rc = filtered_view(s, filter_keys, filter, nq, mask, host, mv, true)) return rc;
-    mv.group = group_keys;
-    mv.group_size = group_size ? *group_size : 0u;
+    mv.groups.col = group_keys;
+    mv.groups.size = group_size ? *group_size : 0u;
     return PQV_OK;
 }
 extern "C" int pqv_topk_distinct_filtered(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
@@ -5808,7 +5908,7 @@ extern "C" int pqv_topk_distinct_filtered(const pqv_searcher *s, const pqv_row_k
                                           uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                           uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, true, mv)) return rc;
         return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
                                       n_found, n_candidates);
@@ -5819,9 +5919,9 @@ extern "C" int pqv_topk_distinct_filtered_device(const pqv_searcher *s, const pq
                                                  uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, void *d_row_idx,
                                                  void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, false, mv)) return rc;
-        mv.d_group_out = static_cast<int64_t *>(d_group_key);
+        mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
     });
@@ -5832,7 +5932,7 @@ extern "C" int pqv_topk_grouped_filtered(const pqv_searcher *s, const pqv_row_ke
                                          int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found,
                                          uint64_t *n_candidates) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, true, mv)) return rc;
         return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
                                       n_found, n_candidates, group_rows);
@@ -5844,10 +5944,10 @@ extern "C" int pqv_topk_grouped_filtered_device(const pqv_searcher *s, const pqv
                                                 void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
                                                 void *d_n_candidates, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, false, mv)) return rc;
-        mv.d_group_out = static_cast<int64_t *>(d_group_key);
-        mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
+        mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
+        mv.groups.d_rows = static_cast<uint32_t *>(d_group_rows);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
     });
@@ -5858,7 +5958,7 @@ extern "C" int pqv_topk_grouped_filtered_device(const pqv_searcher *s, const pqv
 // group_size: nullptr for the distinct forms.
 static int group_expand_view(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys, const pqv_key_filter *filter,
                              const pqv_row_mask *mask, uint32_t nq, uint32_t k, const uint32_t *group_size, uint32_t nprobe, uint32_t max_nprobe,
-                             int metric, bool host, MaskView &mv) {
+                             int metric, bool host, SearchRequest &mv) {
     const char *name = group_size ? "pqv_topk_grouped_expand" : "pqv_topk_distinct_expand";
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!group_keys) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
@@ -5872,18 +5972,18 @@ static int group_expand_view(const pqv_searcher *s, const pqv_row_keys *group_ke
     if (filter_keys) {      // (the filter column's owner and the mask's: filtered_view)
         if (int rc = filtered_view(s, filter_keys, filter, nq, mask, host, mv, true)) return rc;
     } else {
-        mv = MaskView{};
+        mv = SearchRequest{};
         if (mask) { if (int rc = mask_view(s, mask, mv)) return rc; }
     }
-    mv.group = group_keys;
-    mv.group_size = group_size ? *group_size : 0u;
+    mv.groups.col = group_keys;
+    mv.groups.size = group_size ? *group_size : 0u;
     if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
     if (s->n_files) return fail(PQV_ERR_UNSUPPORTED, std::string(name) + " does not take table searchers");
     if (int rc = dot_checks(s, 1, 1, metric, &mv)) return rc;
-    if (static_cast<uint64_t>(k) * std::max<uint32_t>(1, mv.group_size) > 1024 || probe_count(s, max_nprobe) > 1024)
+    if (static_cast<uint64_t>(k) * std::max<uint32_t>(1, mv.groups.size) > 1024 || probe_count(s, max_nprobe) > 1024)
         return fail(PQV_ERR_UNSUPPORTED, std::string(name) + (group_size ? " takes k * group_size <= 1024" : " takes k <= 1024") +
                                              " and at most 1024 probed lists per query");
-    mv.max_nprobe = max_nprobe;
+    mv.expand.max_nprobe = max_nprobe;
     return PQV_OK;
 }
 extern "C" int pqv_topk_distinct_expand(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
@@ -5892,9 +5992,9 @@ extern "C" int pqv_topk_distinct_expand(const pqv_searcher *s, const pqv_row_key
                                         uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates,
                                         uint32_t *nprobe_used) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, nprobe, max_nprobe, metric, true, mv)) return rc;
-        mv.h_nprobe_used = nprobe_used;
+        mv.expand.h_used = nprobe_used;
         return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key, n_found,
                                       n_candidates);
     });
@@ -5905,10 +6005,10 @@ extern "C" int pqv_topk_distinct_expand_device(const pqv_searcher *s, const pqv_
                                                void *d_dist, void *d_group_key, void *d_n_found, void *d_n_candidates, void *d_nprobe_used,
                                                void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, nprobe, max_nprobe, metric, false, mv)) return rc;
-        mv.d_group_out = static_cast<int64_t *>(d_group_key);
-        mv.d_nprobe_used = static_cast<uint32_t *>(d_nprobe_used);
+        mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
+        mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates,
                                     nullptr, hip_stream, &mv);
     });
@@ -5919,9 +6019,9 @@ extern "C" int pqv_topk_grouped_expand(const pqv_searcher *s, const pqv_row_keys
                                        int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found,
                                        uint64_t *n_candidates, uint32_t *nprobe_used) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, nprobe, max_nprobe, metric, true, mv)) return rc;
-        mv.h_nprobe_used = nprobe_used;
+        mv.expand.h_used = nprobe_used;
         return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key, n_found,
                                       n_candidates, group_rows);
     });
@@ -5932,11 +6032,11 @@ extern "C" int pqv_topk_grouped_expand_device(const pqv_searcher *s, const pqv_r
                                               void *d_row_idx, void *d_dist, void *d_group_key, void *d_group_rows, void *d_n_found,
                                               void *d_n_candidates, void *d_nprobe_used, void *hip_stream) {
     return guard([&] {
-        MaskView mv{};
+        SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, nprobe, max_nprobe, metric, false, mv)) return rc;
-        mv.d_group_out = static_cast<int64_t *>(d_group_key);
-        mv.d_group_rows = static_cast<uint32_t *>(d_group_rows);
-        mv.d_nprobe_used = static_cast<uint32_t *>(d_nprobe_used);
+        mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
+        mv.groups.d_rows = static_cast<uint32_t *>(d_group_rows);
+        mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates,
                                     nullptr, hip_stream, &mv);
     });
@@ -6025,12 +6125,13 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
         return PQV_OK;
     }
     const TopkPlan p = plan_topk(s, std::max<uint32_t>(1, nq), nprobe, k, metric);
+    const TopkRoute rt = topk_route(s, p, std::max<uint32_t>(1, nq), k);      // the decisions enqueue_topk follows
     char t[768];
-    if (p.tile && p.filter && p.quad)
+    if (rt.screened)
         std::snprintf(t, sizeof t, "wide_seed_kernel + seed_select_kernel + wide_filter_kernel: %s screen operands, quads of %u queries "
                       "staged %s, %u waves per block, %u rows per block, threshold sample %u rows per list%s%s",
-                      p.i8 ? "int8" : p.f16 ? "f16" : "f32", p.quad_width,
-                      (p.i8 || p.f16 || static_cast<uint64_t>(p.quad_width) * s->sdim * 4 <= 32768) ? "in LDS" : "as a blocked copy in global memory",
+                      rt.operand == 2 ? "int8" : rt.operand == 1 ? "f16" : "f32", p.quad_width,
+                      !rt.q_global ? "in LDS" : "as a blocked copy in global memory",
                       p.block_waves, p.filter_rows_per_block, p.seed_rows,
                       seed_refine_on(s, std::max<uint32_t>(1, nq), k) ? " + exact refinement" : "",
                       !p.i8 ? "" : !s->d_mat_blk_op[2].p ? "" : s->i8_residual ? "; int8 images of the per-list residual (one per probed pair)" : "; int8 images about one centre (one per query)");
@@ -6045,7 +6146,7 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
                       "range_* sort kernels + dot_finish_kernel)", p.rr_rows_per_block);
     else
         std::snprintf(t, sizeof t, "stream_kernel: one candidate stream per (query, probed list), %u rows per block", p.rr_rows_per_block);
-    if (p.tile && p.filter && p.quad && p.wide_width) {
+    if (rt.screened && p.wide_width) {
         const size_t l = std::strlen(t);
         if (p.list_once)
             std::snprintf(t + l, sizeof t - l, "; lists probed by more than %u queries: list_filter_kernel -- 32 rows per wave stationary in registers, all the list's pairs "
@@ -6054,7 +6155,7 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
         std::snprintf(t + l, sizeof t - l, "; lists probed by %u..%u queries: one quad, 8 waves per block on 32-row tiles, %u rows per block",
                       p.quad_width + 1, p.wide_width, p.wide_rows_per_block);
     }
-    if (p.tile && p.filter && p.quad && defer_on(s, std::max<uint32_t>(1, nq), k, p) && cand_cap_for(s, k) <= 8192) {
+    if (rt.deferred) {
         const size_t l = std::strlen(t);
         std::snprintf(t + l, sizeof t - l, "; exact evaluations deferred: survivors appended with their bounds, resolve_select_kernel + "
                                            "resolve_exact_kernel evaluate what the k-th smallest upper bound leaves");
@@ -6065,17 +6166,17 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
     }
     // exact instantiations (as rocprofv3 prints them), so that a profile line can be matched to this dispatch
     char kn[384] = "";
-    if (p.tile && p.filter && p.quad) {
+    if (rt.screened) {
         const int S = k <= 64 ? 1 : 4;
-        const bool qlds = p.i8 || p.f16 || static_cast<uint64_t>(p.quad_width) * s->sdim * 4 <= 32768;
+        const bool qlds = !rt.q_global;
         const bool pf = p.f16 && s->sdim <= 128 && p.block_waves == 4 && p.quad_width != 96;
-        const int op = p.i8 ? 2 : p.f16 ? 1 : 0;
+        const int op = rt.operand;
         const int seed_ng = p.i8 ? (64ull * s->sdim <= 49152 ? 4 : 2) : p.f16 ? ((64ull * s->sdim * 2 <= 32768 && p.quad_width % 64 == 0) ? 4 : 2) : static_cast<int>(p.quad_width / 16);
-        const bool defp = S == 1 && defer_on(s, std::max<uint32_t>(1, nq), k, p) && cand_cap_for(s, k) <= 8192;
+        const bool defp = S == 1 && rt.deferred;
         std::snprintf(kn, sizeof kn, " | kernels: wide_filter_kernel<%u, %u, %d, %s, %d, %s, %s, 4, %s>; wide_seed_kernel<%d, %s, %d, %d>; seed_select_kernel<%d>@%u",
                       p.quad_width / 16, p.block_waves, S, qlds ? "true" : "false", op, pf ? "true" : "false",
                       ((p.i8 && p.block_waves == 4 && p.quad_width == 64 && std::max<uint32_t>(1, nq) <= 64u) || p.wide_width) ? "true" : "false",
-                      defp ? "true" : "false", seed_ng, qlds ? "true" : "false", op, (std::max<uint32_t>(1, nq) == 1 && k <= 256 && s->opt.single_bucket > 0) ? 12 : 1, S,
+                      defp ? "true" : "false", seed_ng, qlds ? "true" : "false", op, rt.seed_tail ? 12 : 1, S,
                       std::max<uint32_t>(1, nq) * (seed_refine_on(s, std::max<uint32_t>(1, nq), k) ? 256u : 64u));
         if (p.wide_width) {
             const size_t l = std::strlen(kn);

@@ -79,10 +79,7 @@ static hipError_t launch_distinct_s(const StreamArgs &a, const DistinctArgs &da,
 
 template <int GW>
 static hipError_t launch_distinct_w(const StreamArgs &a, const DistinctArgs &da, hipStream_t s) {
-    if (a.k <= 64) return launch_distinct_s<1, GW>(a, da, s);
-    if (a.k <= 256) return launch_distinct_s<4, GW>(a, da, s);
-    if (a.k <= 1024) return launch_distinct_s<16, GW>(a, da, s);
-    return hipErrorInvalidValue;
+    return dispatch_list_slots(a.k, [&](auto S) { return launch_distinct_s<S.value, GW>(a, da, s); });
 }
 
 hipError_t launch_distinct_stream(const StreamArgs &a, const DistinctArgs &da, hipStream_t s) {
@@ -165,19 +162,11 @@ hipError_t launch_distinct_merge(const DistinctMergeArgs &a, hipStream_t s) {
     if (a.nq == 0) return hipSuccess;
     const dim3 grid(a.nq), block(64);
     const bool w = a.elem_size == 8;
-    if (a.k <= 64) {
-        if (w) hipLaunchKernelGGL((distinct_merge_kernel<1, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((distinct_merge_kernel<1, 1>), grid, block, 0, s, a);
-    } else if (a.k <= 256) {
-        if (w) hipLaunchKernelGGL((distinct_merge_kernel<4, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((distinct_merge_kernel<4, 1>), grid, block, 0, s, a);
-    } else if (a.k <= 1024) {
-        if (w) hipLaunchKernelGGL((distinct_merge_kernel<16, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((distinct_merge_kernel<16, 1>), grid, block, 0, s, a);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_list_slots(a.k, [&](auto S) {
+        if (w) hipLaunchKernelGGL((distinct_merge_kernel<S.value, 2>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((distinct_merge_kernel<S.value, 1>), grid, block, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace pqv

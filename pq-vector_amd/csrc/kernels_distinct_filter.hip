@@ -90,10 +90,7 @@ static hipError_t launch_distinct_filter_s(const StreamArgs &a, const DistinctAr
 
 template <int GW>
 static hipError_t launch_distinct_filter_w(const StreamArgs &a, const DistinctArgs &da, const GroupFilterArgs &fa, hipStream_t s) {
-    if (a.k <= 64) return launch_distinct_filter_s<1, GW>(a, da, fa, s);
-    if (a.k <= 256) return launch_distinct_filter_s<4, GW>(a, da, fa, s);
-    if (a.k <= 1024) return launch_distinct_filter_s<16, GW>(a, da, fa, s);
-    return hipErrorInvalidValue;
+    return dispatch_list_slots(a.k, [&](auto S) { return launch_distinct_filter_s<S.value, GW>(a, da, fa, s); });
 }
 
 static bool group_filter_args_ok(const GroupFilterArgs &fa) {
@@ -189,9 +186,7 @@ hipError_t launch_grouped_filter_stream(const StreamArgs &a, const GroupedArgs &
     if (ga.elem_size != 4 && ga.elem_size != 8) return hipErrorInvalidValue;
     if (!group_filter_args_ok(fa)) return hipErrorInvalidValue;
     if (a.nq == 0 || a.blocks_per_list == 0 || a.nprobe == 0) return hipSuccess;
-    if (ga.km <= 64) return launch_grouped_filter_s<1>(a, ga, fa, s);
-    if (ga.km <= 256) return launch_grouped_filter_s<4>(a, ga, fa, s);
-    return launch_grouped_filter_s<16>(a, ga, fa, s);
+    return dispatch_list_slots(ga.km, [&](auto S) { return launch_grouped_filter_s<S.value>(a, ga, fa, s); });
 }
 
 }  // namespace pqv

@@ -112,10 +112,7 @@ static hipError_t launch_dot_w(const StreamArgs &a, const MaskedArgs &ma, Stream
     }
     if (mode != STREAM_TOPK) return hipErrorInvalidValue;
     if (a.probe && a.nprobe == 0) return hipSuccess;
-    if (a.k <= 64) return launch_dot_s<1, STREAM_TOPK, WIN>(a, ma, s);
-    if (a.k <= 256) return launch_dot_s<4, STREAM_TOPK, WIN>(a, ma, s);
-    if (a.k <= 1024) return launch_dot_s<16, STREAM_TOPK, WIN>(a, ma, s);
-    return hipErrorInvalidValue;
+    return dispatch_list_slots(a.k, [&](auto S) { return launch_dot_s<S.value, STREAM_TOPK, WIN>(a, ma, s); });
 }
 
 hipError_t launch_dot_stream(const StreamArgs &a, const MaskedArgs *ma, StreamMode mode, hipStream_t s) {
@@ -183,11 +180,10 @@ __global__ __launch_bounds__(64) void dot_merge_kernel(const MergeArgs a) {
 hipError_t launch_dot_merge(const MergeArgs &a, hipStream_t s) {
     if (a.nq == 0) return hipSuccess;
     if (a.cand_keys || a.cand_lb || a.part_flags || a.k == 0 || (a.k_out ? a.k_out : a.k) > a.k) return hipErrorInvalidValue;
-    if (a.k <= 64) hipLaunchKernelGGL(dot_merge_kernel<1>, dim3(a.nq), dim3(64), 0, s, a);
-    else if (a.k <= 256) hipLaunchKernelGGL(dot_merge_kernel<4>, dim3(a.nq), dim3(64), 0, s, a);
-    else if (a.k <= 1024) hipLaunchKernelGGL(dot_merge_kernel<16>, dim3(a.nq), dim3(64), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_list_slots(a.k, [&](auto S) {
+        hipLaunchKernelGGL(dot_merge_kernel<S.value>, dim3(a.nq), dim3(64), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // dist[i] = the distance whose ord bits dist[i] holds (range search write-out), i < n

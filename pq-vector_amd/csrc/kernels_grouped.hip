@@ -125,9 +125,7 @@ static hipError_t launch_grouped_s(const StreamArgs &a, const GroupedArgs &ga, h
 
 template <int GW>
 static hipError_t launch_grouped_w(const StreamArgs &a, const GroupedArgs &ga, hipStream_t s) {
-    if (ga.km <= 64) return launch_grouped_s<1, GW>(a, ga, s);
-    if (ga.km <= 256) return launch_grouped_s<4, GW>(a, ga, s);
-    return launch_grouped_s<16, GW>(a, ga, s);
+    return dispatch_list_slots(ga.km, [&](auto S) { return launch_grouped_s<S.value, GW>(a, ga, s); });     // (km <= 1024: grouped_shape_ok)
 }
 
 // k * group_size <= 1024 with group_size >= 2 (one row per group is the distinct call), hence k <= GROUPED_SET_MAX
@@ -236,10 +234,10 @@ hipError_t launch_grouped_merge(const GroupedMergeArgs &a, hipStream_t s) {
     if (!grouped_shape_ok(a.k, a.group_size, a.km)) return hipErrorInvalidValue;
     if (a.nq == 0) return hipSuccess;
     const dim3 grid(a.nq), block(64);
-    if (a.km <= 64) hipLaunchKernelGGL((grouped_merge_kernel<1>), grid, block, 0, s, a);
-    else if (a.km <= 256) hipLaunchKernelGGL((grouped_merge_kernel<4>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((grouped_merge_kernel<16>), grid, block, 0, s, a);
-    return hipGetLastError();
+    return dispatch_list_slots(a.km, [&](auto S) {
+        hipLaunchKernelGGL((grouped_merge_kernel<S.value>), grid, block, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------------------------

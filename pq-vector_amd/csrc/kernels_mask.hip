@@ -204,10 +204,7 @@ static hipError_t launch_masked_w(const StreamArgs &a, const typename WinArgs<WI
     if (mode == STREAM_RANGE) return a.nj == 0 ? hipSuccess : launch_masked_s<1, STREAM_RANGE, WIN>(a, ma, s);
     if (mode != STREAM_TOPK) return hipErrorInvalidValue;
     if (a.nprobe == 0) return hipSuccess;
-    if (a.k <= 64) return launch_masked_s<1, STREAM_TOPK, WIN>(a, ma, s);
-    if (a.k <= 256) return launch_masked_s<4, STREAM_TOPK, WIN>(a, ma, s);
-    if (a.k <= 1024) return launch_masked_s<16, STREAM_TOPK, WIN>(a, ma, s);
-    return hipErrorInvalidValue;
+    return dispatch_list_slots(a.k, [&](auto S) { return launch_masked_s<S.value, STREAM_TOPK, WIN>(a, ma, s); });
 }
 
 hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s) {

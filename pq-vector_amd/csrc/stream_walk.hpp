@@ -11,6 +11,7 @@
 //   distinct_tile / grouped_tile ...  what a distinct / grouped kernel shares with its filtered twin: images, tile, list write-out
 //   stats_slot, l2_key, emit_range_hit, write_partial_lists     the statistics slot, a candidate's key, the two output formats
 //   dispatch_chunk (host)             the chunk choice (CG, SEQ, ALIGNED) of every launcher
+//   dispatch_list_slots (host)        the list length choice (S) of every launcher
 //
 // The forms promise results bit-identical to each other and the tests compare form against form: a change to the chain, the
 // clamps or the barrier placement belongs here, where every form gets it.
@@ -522,6 +523,16 @@ static inline hipError_t dispatch_chunk(uint32_t dim, int metric, F &&f) {
         if (G >= 64 && G % 64 == 0) return f(std::integral_constant<int, 64>{}, false_type{}, true_type{});
     }
     return f(std::integral_constant<int, 32>{}, false_type{}, true_type{});
+}
+
+// Host: the list length choice of every launcher.  f(S) gets the 64-entry slots a lane's sorted list takes as an integral_constant:
+// k <= 64 -> 1, <= 256 -> 4, <= 1024 -> 16; the kernels hold no longer list.
+template <class F>
+static inline hipError_t dispatch_list_slots(uint32_t k, F &&f) {
+    if (k <= 64) return f(std::integral_constant<int, 1>{});
+    if (k <= 256) return f(std::integral_constant<int, 4>{});
+    if (k <= 1024) return f(std::integral_constant<int, 16>{});
+    return hipErrorInvalidValue;
 }
 
 }  // namespace pqv
