@@ -221,6 +221,36 @@ impl Index {
         check(unsafe { sys::pqv_index_append(self.raw, corpus.raw, first_row as u64, n_rows as u64, &mut raw) })?;
         Ok(Index { raw })
     }
+
+    /// A new index with these centroids whose lists no longer hold the rows `r < remove.len()` with `remove[r] != 0`; order is
+    /// kept, row ids stay what they were and the row bound is carried over.  Runs on `device` where there is one, else on the
+    /// host with the same result.  `self` is not modified: searchers made from it keep answering as before.
+    pub fn remove(&self, device: usize, remove: &[u8]) -> Result<Index> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_index_remove(self.raw, device as c_int, remove.as_ptr(), remove.len() as u64, &mut raw) })?;
+        Ok(Index { raw })
+    }
+
+    /// `remove` by row id: any order, duplicates allowed, ids that are not indexed ignored.
+    pub fn remove_rows(&self, device: usize, rows: &[u32]) -> Result<Index> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_index_remove_rows(self.raw, device as c_int, rows.as_ptr(), rows.len() as u64, &mut raw) })?;
+        Ok(Index { raw })
+    }
+
+    /// The vacuum: a dense corpus of the rows this index still holds (ascending old id, bit for bit, room for
+    /// `max(capacity_rows, kept)` rows), the index renumbered onto it (new id = rank of the old id among the kept rows), and
+    /// `old_row[j]` = the old id of new row `j` -- attached columns are re-made as `column[old_row]`.
+    pub fn compact(&self, corpus: &Corpus, capacity_rows: usize) -> Result<(Corpus, Index, Vec<u32>)> {
+        let (mut c_raw, mut i_raw) = (ptr::null_mut(), ptr::null_mut());
+        let mut old_row = vec![0u32; unsafe { sys::pqv_index_n_rows(self.raw) } as usize];
+        check(unsafe {
+            sys::pqv_index_compact(self.raw, corpus.raw, capacity_rows as u64, &mut c_raw, &mut i_raw, old_row.as_mut_ptr())
+        })?;
+        let (c, i) = (Corpus { raw: c_raw }, Index { raw: i_raw });
+        old_row.truncate(c.rows());
+        Ok((c, i, old_row))
+    }
 }
 
 impl Drop for Index {

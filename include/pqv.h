@@ -227,6 +227,34 @@ int pqv_index_assign(const pqv_index *index, const pqv_corpus *corpus, uint64_t 
  * indexed row id + 1), which keeps every list ascending; rows between the bound and first_row are simply not indexed.
  * n_rows == 0 yields a copy. */
 int pqv_index_append(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out);
+/* ---- index remove and compact: deleted rows leave the lists, then HBM ---------------------
+ * pqv_index_remove* is the logical delete.  A NEW index: the centroids of `index` bit for bit, n_clusters unchanged, list c =
+ * list c of `index` without the removed rows, order kept (a list that loses every row stays, empty).  Row ids stay what they
+ * were and the row bound (largest indexed row id + 1, as append defines it) is carried over, not lowered: ids are never reused
+ * and a later pqv_index_append continues where it would have.  `index` is not modified and stays valid (it may be shared with
+ * live searchers; their masks and keys remain what they were).  Where nothing is removed the result is a copy.  An unmasked
+ * search of the result returns what a search of `index` under the equivalent pqv_row_mask returns -- through every fast path.
+ * The three forms differ in how the rows are named:
+ *   pqv_index_remove          host bytes, one per row id in [0, n_flags): non-zero removes the row; ids >= n_flags stay.  n_flags
+ *                             may be 0 and may exceed every indexed id.  Runs on `device` where it is usable, else on the host
+ *                             with the identical result (also under PQV_DEVICE_LISTS=0).
+ *   pqv_index_remove_device   the same bytes in device memory of `device` (required); runs on hip_stream and synchronises it.
+ *   pqv_index_remove_rows     the row ids themselves: any order, duplicates allowed, ids that are not indexed ignored.
+ * PQV_ERR_INVALID before any device work: a NULL index or out, NULL flags / rows with a non-zero count, n_flags above 2^32.
+ *
+ * pqv_index_compact is the vacuum.  With M = the rows in the lists of `index` (each below pqv_corpus_rows(corpus) and indexed
+ * at most once, else PQV_ERR_INVALID), the new id of row r is its rank in M.  *corpus_out is made like
+ * pqv_corpus_create(device of corpus, max(capacity_rows, |M|), dim) and holds the |M| rows of M in ascending old id, bit for
+ * bit; *index_out has the centroids bit for bit and every list with the rank applied element by element (monotone: positions
+ * and order are preserved), row bound |M|, and is a permutation of the new corpus' rows by construction.  old_row[j] (host,
+ * [|M|] -- pqv_index_n_rows(index) entries suffice --, may be NULL) is the old id of new row j: attached columns are re-made as
+ * column[old_row].  Works on the corpus' stream; validation as for append (NULLs, dimension mismatch, a released row-order
+ * copy).  Neither input is modified. */
+int pqv_index_remove(const pqv_index *index, int device, const uint8_t *remove, uint64_t n_flags, pqv_index **out);
+int pqv_index_remove_device(const pqv_index *index, int device, const void *d_remove, uint64_t n_flags, void *hip_stream, pqv_index **out);
+int pqv_index_remove_rows(const pqv_index *index, int device, const uint32_t *rows, uint64_t m, pqv_index **out);
+int pqv_index_compact(const pqv_index *index, const pqv_corpus *corpus, uint64_t capacity_rows,
+                      pqv_corpus **corpus_out, pqv_index **index_out, uint32_t *old_row /* host [kept rows], may be NULL */);
 /* Phase wall times of the calling thread's last pqv_index_build / pqv_index_build_host / pqv_kmeans (bench records):
  * out[0] k-means++ seconds, [1] Lloyd seconds, [2] Lloyd iterations run, [3] final assignment seconds (device work +
  * download), [4] host inverted-list build seconds, [5] 1 if the final assignment ran through the MFMA screen, [6] same for

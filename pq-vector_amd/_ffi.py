@@ -107,6 +107,10 @@ SIGNATURES = {
     "pqv_index_build": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
     "pqv_index_assign": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u32p]),
     "pqv_index_append": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "pqv_index_remove": (C.c_int, [vp, C.c_int, u8p, C.c_uint64, C.POINTER(vp)]),
+    "pqv_index_remove_device": (C.c_int, [vp, C.c_int, vp, C.c_uint64, vp, C.POINTER(vp)]),
+    "pqv_index_remove_rows": (C.c_int, [vp, C.c_int, u32p, C.c_uint64, C.POINTER(vp)]),
+    "pqv_index_compact": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(vp), C.POINTER(vp), u32p]),
     "pqv_index_build_stats": (C.c_int, [C.POINTER(C.c_double), C.c_uint32]),
     "pqv_kpp_pick": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_uint64),
                                C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),

@@ -269,6 +269,56 @@ class Index:
         _check(_ffi.lib().pqv_index_append(self._h, corpus._h, first_row, n_rows, C.byref(h)))
         return Index(h, row_bound=first_row + n_rows)
 
+    def remove(self, rows=None, *, flags=None, where=None, device=0, stream=0):
+        """A new Index: these centroids, every list without the removed rows, order kept (pqv_index_remove*).  Row ids stay what
+        they were and the row bound is carried over, so a later append continues where it would have; an unmasked search of the
+        result answers what a search of this index under the equivalent mask answers, through every fast path.  Exactly one of:
+          rows   row ids to remove -- any order, duplicates allowed, ids that are not indexed ignored;
+          flags  one byte (or bool) per row id from 0, non-zero REMOVES the row, ids beyond the array stay: a numpy array, a
+                 torch tensor (on the GPU: read in place), or (device pointer, count) as row_mask_device takes them;
+          where  a RowMask: the rows the mask ALLOWS are removed -- DELETE WHERE predicate, the opposite sense of passing the
+                 mask to a search (read through to_bytes()).
+        Runs on `device` where there is one (flags on the GPU need it), else on the host with the same result.  This index is
+        not modified: searchers made from it, and their masks and keys, stay as they were."""
+        if (rows is not None) + (flags is not None) + (where is not None) != 1:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "remove() takes exactly one of rows, flags and where")
+        lib, h = _ffi.lib(), vp()
+        bound = self.row_bound               # carried over, not lowered (known by construction, else one scan of the host lists)
+        if rows is not None:
+            r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.uint32)
+            _check(lib.pqv_index_remove_rows(self._h, device, r.ctypes.data_as(u32p), r.size, C.byref(h)))
+            return Index(h, row_bound=bound)
+        if where is not None:
+            flags = where.to_bytes()
+        ptr = count = None
+        if isinstance(flags, tuple):
+            ptr, count = int(flags[0]), int(flags[1])
+        elif hasattr(flags, "data_ptr") and getattr(flags, "is_cuda", False):
+            if flags.element_size() != 1 or not flags.is_contiguous():
+                raise PqvError(_ffi.PQV_ERR_INVALID, "remove flags on the device must be contiguous bytes or bools")
+            ptr, count = int(flags.data_ptr()), int(flags.numel())
+        if ptr is not None:
+            _check(lib.pqv_index_remove_device(self._h, device, vp(ptr or None), count, vp(stream or None), C.byref(h)))
+            return Index(h, row_bound=bound)
+        a = flags.numpy() if hasattr(flags, "data_ptr") else np.asarray(flags)
+        if a.dtype != np.bool_ and a.dtype != np.uint8:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "remove flags must be bool or uint8, one entry per row id")
+        a = np.ascontiguousarray(a.reshape(-1)).view(np.uint8)
+        _check(lib.pqv_index_remove(self._h, device, a.ctypes.data_as(u8p), a.size, C.byref(h)))
+        return Index(h, row_bound=bound)
+
+    def compact(self, corpus, capacity=None):
+        """-> (Corpus, Index, old_row): a dense corpus of the rows this index still holds (ascending old id, bit for bit, room for
+        max(capacity, kept) rows), this index renumbered onto it (new id = rank of the old id among the kept rows; lists keep their
+        order), and old_row uint32 [kept] = the old id of every new row -- attached columns, masks and keys are re-made from
+        column[old_row].  Neither this index nor `corpus` is modified (pqv_index_compact)."""
+        old_row = np.zeros(max(self.n_rows, 1), dtype=np.uint32)
+        ch, ih = vp(), vp()
+        _check(_ffi.lib().pqv_index_compact(self._h, corpus._h, int(capacity or 0), C.byref(ch), C.byref(ih), old_row.ctypes.data_as(u32p)))
+        dense = Corpus(ch)
+        dense._capacity = max(int(capacity or 0), dense.rows)
+        return dense, Index(ih, row_bound=dense.rows), old_row[:dense.rows].copy()
+
     def close(self):
         if self._h:
             _ffi.lib().pqv_index_free(self._h)

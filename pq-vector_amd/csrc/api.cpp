@@ -278,6 +278,11 @@ struct pqv_index {
         *out = bound;
         return true;
     }
+    bool known_row_bound(uint64_t *out) const {      // the bound where it is known already (no read of the lists)
+        std::lock_guard<std::mutex> lock(bound_mu);
+        if (bound_known) *out = bound;
+        return bound_known;
+    }
     pqv_index() = default;
     pqv_index(const pqv_index &) = delete;
     pqv_index &operator=(const pqv_index &) = delete;
@@ -2653,6 +2658,13 @@ int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
     return PQV_OK;
 }
 
+// PQV_KEEP_DEVICE_LISTS=0: a derived index' lists are downloaded at once instead of staying on the device
+bool keep_device_lists() {
+    static const bool keep = [] { const char *e = std::getenv("PQV_KEEP_DEVICE_LISTS"); return !(e && *e == '0'); }();
+    return keep;
+}
+struct EventSet { hipEvent_t e[4] = {}; ~EventSet() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
+
 int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out) {
     using namespace pqv;
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
@@ -2741,7 +2753,7 @@ int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
     }
     HIP_TRY(d_out_rows.alloc(total * sizeof(uint32_t)));
     HIP_TRY(d_out_off.alloc((static_cast<size_t>(k) + 1) * sizeof(uint64_t)));
-    struct Events { hipEvent_t e[4] = {}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
+    EventSet ev;
     DevBuf d_copy;
     if (stats) {
         for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
@@ -2757,7 +2769,7 @@ int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
         HIP_TRY(hipEventRecord(ev.e[3], stream));
     }
     uint32_t h_bad = 0;
-    static const bool keep_dev = [] { const char *e = std::getenv("PQV_KEEP_DEVICE_LISTS"); return !(e && *e == '0'); }();
+    const bool keep_dev = keep_device_lists();
     idx->list_off.resize(static_cast<size_t>(k) + 1);
     if (!keep_dev) {
         idx->list_rows.resize(total);
@@ -2792,7 +2804,352 @@ int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
     return PQV_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// pqv_index_remove* / pqv_index_compact: rows leave the lists (remove), then the corpus (compact).  Both rank over a bitset on
+// the device (kernels_remove.hip); a host path leaves the identical result where the device path is not taken.
+// ---------------------------------------------------------------------------------------
+bool device_lists_on() { return DeviceLists::applicable(1, 1); }       // (PQV_DEVICE_LISTS alone: these paths have no cluster limit)
+bool device_usable(int device) {      // (no error text: the caller falls back to the host)
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return device >= 0 && device < count;
+}
+struct PooledStream {
+    int device = -1;
+    hipStream_t s = nullptr;
+    ~PooledStream() { if (s) pool_put(device, s); }
+};
+
+// the parts every derived index shares with its source: dimension, centroids bit for bit
+std::unique_ptr<pqv_index> derive_index(const pqv_index *index) {
+    std::unique_ptr<pqv_index> idx(new pqv_index());
+    idx->dim = index->dim; idx->n_clusters = index->n_clusters;
+    idx->centroids = index->centroids;
+    return idx;
+}
+int copy_lists(const pqv_index *index, pqv_index *idx) {
+    const std::vector<uint32_t> *rv = index->rows->get();
+    if (!rv) return PQV_ERR_HIP;
+    idx->list_off = index->list_off;
+    idx->list_rows = *rv;
+    idx->permutation_of = index->permutation_of;
+    return PQV_OK;
+}
+// as a build leaves them: the lists stay on the device, the host copy is made by the first call that reads it
+void adopt_device_lists(pqv_index *idx, DevBuf &rows, int device, uint64_t n) {
+    auto dr = std::make_shared<DevRows>();
+    dr->p = rows.p; dr->device = device; dr->n = n;
+    rows.p = nullptr; rows.bytes = 0;
+    idx->rows->dev = std::move(dr);
+    idx->rows->n = n;
+    idx->rows->host.clear();
+    idx->rows->pending = true;
+}
+// the index' lists on `device`: its device copy where it lives there, else one upload (up keeps it)
+int device_lists_of(const pqv_index *index, int device, uint64_t n_pos, hipStream_t stream, std::shared_ptr<DevRows> &keep, DevBuf &up,
+                    const uint32_t **d_ids) {
+    keep = index->rows->dev;
+    if (keep && keep->p && keep->device == device && keep->n == n_pos) { *d_ids = static_cast<const uint32_t *>(keep->p); return PQV_OK; }
+    const std::vector<uint32_t> *rv = index->rows->get();
+    if (!rv) return PQV_ERR_HIP;
+    HIP_TRY(up.alloc(n_pos * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpyAsync(up.p, rv->data(), n_pos * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    *d_ids = up.as<uint32_t>();
+    return PQV_OK;
+}
+
+// flags: host bytes (h_flags) or device bytes (d_flags, from_device); validated by the callers
+int index_remove_common(const pqv_index *index, int device, const uint8_t *h_flags, const void *d_flags, bool from_device, uint64_t n_flags,
+                        hipStream_t user_stream, pqv_index **out) {
+    using namespace pqv;
+    if (from_device) if (int rc = use_device(device)) return rc;
+    uint64_t bound = 0;
+    if (!index->row_bound(&bound)) return PQV_ERR_HIP;
+    std::unique_ptr<pqv_index> idx = derive_index(index);
+    idx->set_row_bound(bound);                       // carried over, not lowered: ids are never reused
+    const uint32_t k = index->n_clusters;
+    const uint64_t n_pos = index->n_rows();
+    const uint64_t nf = std::min(n_flags, bound);    // (no row at or above the bound is indexed)
+    if (n_pos == 0 || nf == 0) {                     // nothing can leave: a copy
+        if (int rc = copy_lists(index, idx.get())) return rc;
+        *out = idx.release();
+        return PQV_OK;
+    }
+    const bool on_device = device_lists_on() && (from_device || device_usable(device));
+    if (!on_device) {
+        // PQV_DEVICE_LISTS=0, or host flags and no usable device: list c = its rows whose flag byte is zero, order kept
+        std::vector<uint8_t> down;
+        if (from_device) {
+            hipStream_t stream = user_stream;
+            down.resize(nf);
+            HIP_TRY(hipMemcpyAsync(down.data(), d_flags, nf, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            h_flags = down.data();
+        }
+        const std::vector<uint32_t> *rv = index->rows->get();
+        if (!rv) return PQV_ERR_HIP;
+        idx->list_off.assign(static_cast<size_t>(k) + 1, 0);
+        idx->list_rows.reserve(n_pos);
+        for (uint32_t c = 0; c < k; ++c) {
+            for (uint64_t p = index->list_off[c]; p < index->list_off[c + 1]; ++p) {
+                const uint32_t r = (*rv)[p];
+                if (r >= nf || h_flags[r] == 0) idx->list_rows.push_back(r);
+            }
+            idx->list_off[c + 1] = idx->list_rows.size();
+        }
+        if (idx->list_rows.size() == n_pos) idx->permutation_of = index->permutation_of;
+        idx->list_rows.shrink_to_fit();
+        *out = idx.release();
+        return PQV_OK;
+    }
+
+    if (!from_device) if (int rc = use_device(device)) return rc;
+    PooledStream pooled;
+    hipStream_t stream = user_stream;
+    if (!from_device) {
+        pooled.device = device;
+        HIP_TRY(pool_get(device, &pooled.s));
+        stream = pooled.s;
+    }
+    // PQV_REMOVE_STATS=1 (diagnostic, read per call): the compaction kernel between two HIP events and a plain device-to-device
+    // copy of the same list bytes behind it, on stderr
+    const bool stats = std::getenv("PQV_REMOVE_STATS") != nullptr;
+    const double t0 = now_s();
+    std::shared_ptr<DevRows> old_dev;
+    DevBuf d_up_ids, d_up_flags, d_bits, d_rank, d_tmp, d_old_off, d_new_off, d_out, d_copy;
+    const uint32_t *d_ids = nullptr;
+    if (int rc = device_lists_of(index, device, n_pos, stream, old_dev, d_up_ids, &d_ids)) return rc;
+    const uint8_t *d_f = static_cast<const uint8_t *>(d_flags);
+    if (!from_device) {
+        HIP_TRY(d_up_flags.alloc(nf));
+        HIP_TRY(hipMemcpyAsync(d_up_flags.p, h_flags, nf, hipMemcpyHostToDevice, stream));
+        d_f = d_up_flags.as<uint8_t>();
+    }
+    // bit p of the image = "the row at list position p is flagged" (launch_mask_layout as it is); the kernels behind it read the
+    // image inverted: a set bit leaves
+    const uint64_t n_words = (n_pos + 63) / 64, n_words_image = n_words + 1;
+    HIP_TRY(d_bits.alloc((n_words_image + 1) * sizeof(uint64_t)));
+    unsigned long long *d_count = d_bits.as<unsigned long long>() + n_words_image;
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
+    HIP_TRY(launch_mask_layout(d_f, nf, d_ids, n_pos, d_bits.as<uint64_t>(), n_words_image, d_count, stream));
+    HIP_TRY(d_rank.alloc((n_words + 1) * sizeof(uint64_t)));
+    HIP_TRY(d_tmp.alloc((bit_rank_blocks(n_pos) + 1) * sizeof(uint64_t)));
+    HIP_TRY(launch_bit_rank(d_bits.as<uint64_t>(), n_pos, true, d_rank.as<uint64_t>(), d_tmp.as<uint64_t>(), stream));
+    uint64_t kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, d_rank.as<uint64_t>() + n_words, sizeof kept, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (kept > n_pos) return fail(PQV_ERR_HIP, "internal error: more rows kept than indexed");
+    if (kept == n_pos) {                             // nothing was removed: a copy
+        if (int rc = copy_lists(index, idx.get())) return rc;
+        *out = idx.release();
+        return PQV_OK;
+    }
+    const double t1 = now_s();
+    HIP_TRY(d_out.alloc(kept * sizeof(uint32_t)));
+    HIP_TRY(d_old_off.alloc((static_cast<size_t>(k) + 1) * sizeof(uint64_t)));
+    HIP_TRY(d_new_off.alloc((static_cast<size_t>(k) + 1) * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpyAsync(d_old_off.p, index->list_off.data(), (static_cast<size_t>(k) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    EventSet ev;
+    if (stats) {
+        for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(d_copy.alloc(n_pos * sizeof(uint32_t)));
+        HIP_TRY(hipEventRecord(ev.e[0], stream));
+    }
+    HIP_TRY(launch_list_compact(d_ids, n_pos, d_bits.as<uint64_t>(), true, d_rank.as<uint64_t>(), d_out.as<uint32_t>(), stream));
+    if (stats) {
+        HIP_TRY(hipEventRecord(ev.e[1], stream));
+        HIP_TRY(hipEventRecord(ev.e[2], stream));
+        HIP_TRY(hipMemcpyAsync(d_copy.p, d_ids, n_pos * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipEventRecord(ev.e[3], stream));
+    }
+    HIP_TRY(launch_offsets_rank(d_old_off.as<uint64_t>(), k + 1, d_bits.as<uint64_t>(), n_pos, true, d_rank.as<uint64_t>(),
+                                d_new_off.as<uint64_t>(), stream));
+    idx->list_off.resize(static_cast<size_t>(k) + 1);
+    const bool keep_dev = keep_device_lists();
+    if (!keep_dev) {
+        idx->list_rows.resize(kept);
+        if (kept) HIP_TRY(hipMemcpyAsync(idx->list_rows.data(), d_out.p, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipMemcpyAsync(idx->list_off.data(), d_new_off.p, (static_cast<size_t>(k) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (idx->list_off[0] != 0 || idx->list_off[k] != kept) return fail(PQV_ERR_HIP, "internal error: list offsets do not add up");
+    if (keep_dev) adopt_device_lists(idx.get(), d_out, device, kept);
+    if (stats) {
+        float ms_k = 0.0f, ms_copy = 0.0f;
+        (void)hipEventElapsedTime(&ms_k, ev.e[0], ev.e[1]);
+        (void)hipEventElapsedTime(&ms_copy, ev.e[2], ev.e[3]);
+        const double bytes = static_cast<double>(n_pos) * sizeof(uint32_t);
+        std::fprintf(stderr, "pqv_index_remove: %llu of %llu rows leave: keep bits + rank %.3f ms, lists %.3f ms; compaction kernel %.4f ms for %.0f "
+                             "list bytes read (%.1f GB/s), device-to-device copy of the same bytes %.4f ms\n",
+                     (unsigned long long)(n_pos - kept), (unsigned long long)n_pos, (t1 - t0) * 1e3, (now_s() - t1) * 1e3, ms_k, bytes,
+                     ms_k > 0.0f ? bytes / (ms_k * 1e6) : 0.0, ms_copy);
+    }
+    *out = idx.release();
+    return PQV_OK;
+}
+
+int index_remove_impl(const pqv_index *index, int device, const uint8_t *h_flags, const void *d_flags, bool from_device, uint64_t n_flags,
+                      void *hip_stream, pqv_index **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!index) return fail(PQV_ERR_INVALID, "index must not be NULL");
+    if (n_flags && !(from_device ? d_flags != nullptr : h_flags != nullptr)) return fail(PQV_ERR_INVALID, "remove must not be NULL");
+    if (n_flags > (1ull << 32)) return fail(PQV_ERR_INVALID, "row ids must fit in u32: n_flags must not exceed 2^32");
+    return index_remove_common(index, device, h_flags, d_flags, from_device, n_flags, static_cast<hipStream_t>(hip_stream), out);
+}
+
+int index_remove_rows_impl(const pqv_index *index, int device, const uint32_t *rows, uint64_t m, pqv_index **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!index) return fail(PQV_ERR_INVALID, "index must not be NULL");
+    if (m && !rows) return fail(PQV_ERR_INVALID, "rows must not be NULL");
+    // the byte form over max id + 1 flags, cut at the row bound (no row at or above it is indexed)
+    uint64_t bound = 0, n_flags = 0;
+    if (!index->row_bound(&bound)) return PQV_ERR_HIP;
+    for (uint64_t i = 0; i < m; ++i)
+        if (rows[i] < bound) n_flags = std::max<uint64_t>(n_flags, static_cast<uint64_t>(rows[i]) + 1);
+    std::vector<uint8_t> flags(n_flags, 0);
+    for (uint64_t i = 0; i < m; ++i)
+        if (rows[i] < n_flags) flags[rows[i]] = 1;
+    return index_remove_common(index, device, flags.data(), nullptr, false, n_flags, nullptr, out);
+}
+
+int index_compact_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t capacity_rows, pqv_corpus **corpus_out,
+                       pqv_index **index_out, uint32_t *old_row) {
+    using namespace pqv;
+    if (corpus_out) *corpus_out = nullptr;
+    if (index_out) *index_out = nullptr;
+    if (!corpus_out || !index_out) return fail(PQV_ERR_INVALID, "corpus_out/index_out must not be NULL");
+    if (!index || !corpus) return fail(PQV_ERR_INVALID, "index/corpus must not be NULL");
+    if (index->dim != corpus->dim)
+        return fail(PQV_ERR_INVALID, "index dimension " + std::to_string(index->dim) +
+                                         " does not match corpus dimension " + std::to_string(corpus->dim));
+    if (!corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
+    const uint64_t n = corpus->n, n_pos = index->n_rows();
+    const uint32_t dim = corpus->dim;
+    if (n_pos > (1ull << 32)) return fail(PQV_ERR_INVALID, "row ids must fit in u32");
+    if (int rc = use_device(corpus->device)) return rc;
+    hipStream_t stream = corpus->stream;
+    // PQV_REMOVE_STATS=1: the gather kernel between two HIP events and a plain device-to-device copy of the same row bytes
+    const bool stats = std::getenv("PQV_REMOVE_STATS") != nullptr;
+    const double t0 = now_s();
+    std::unique_ptr<pqv_index> idx = derive_index(index);
+    idx->list_off = index->list_off;                 // (the rank is applied element by element: every list keeps its length)
+    DevBuf d_old_row, d_new_rows;
+    uint64_t total = 0;
+    const char *const dup_text = "index holds a row more than once: it cannot be compacted";
+    const char *const range_text = "index row id out of range for this corpus";
+    if (n_pos == 0) {
+        HIP_TRY(d_old_row.alloc(16));
+    } else if (!device_lists_on()) {
+        // PQV_DEVICE_LISTS=0: membership, rank and the renumbered lists on the host; only the rows are gathered on the device
+        const std::vector<uint32_t> *rv = index->rows->get();
+        if (!rv) return PQV_ERR_HIP;
+        std::vector<uint8_t> member(n, 0);
+        for (uint32_t r : *rv) {
+            if (r >= n) return fail(PQV_ERR_INVALID, range_text);
+            member[r] = 1;
+        }
+        std::vector<uint32_t> new_id(n), h_old;
+        h_old.reserve(n_pos);
+        for (uint64_t r = 0; r < n; ++r) {
+            new_id[r] = static_cast<uint32_t>(h_old.size());
+            if (member[r]) h_old.push_back(static_cast<uint32_t>(r));
+        }
+        total = h_old.size();
+        if (total != n_pos) return fail(PQV_ERR_INVALID, dup_text);
+        idx->list_rows.resize(n_pos);
+        for (uint64_t p = 0; p < n_pos; ++p) idx->list_rows[p] = new_id[(*rv)[p]];
+        HIP_TRY(d_old_row.alloc(total * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpyAsync(d_old_row.p, h_old.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));       // (h_old leaves scope)
+    } else {
+        std::shared_ptr<DevRows> old_dev;
+        DevBuf d_up_ids, d_member, d_rowbits, d_rank, d_tmp, d_bad;
+        const uint32_t *d_ids = nullptr;
+        if (int rc = device_lists_of(index, corpus->device, n_pos, stream, old_dev, d_up_ids, &d_ids)) return rc;
+        const uint64_t n_words = (n + 63) / 64;
+        HIP_TRY(d_member.alloc(n));
+        HIP_TRY(d_bad.alloc(sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(d_member.p, 0, n, stream));
+        HIP_TRY(hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), stream));
+        HIP_TRY(launch_member_bytes(d_ids, n_pos, n, d_member.as<uint8_t>(), d_bad.as<uint32_t>(), stream));
+        HIP_TRY(d_rowbits.alloc((n_words + 1) * sizeof(uint64_t)));
+        HIP_TRY(launch_mask_pack(d_member.as<uint8_t>(), n, d_rowbits.as<uint64_t>(), n_words, stream));
+        HIP_TRY(d_rank.alloc((n_words + 1) * sizeof(uint64_t)));
+        HIP_TRY(d_tmp.alloc((bit_rank_blocks(n) + 1) * sizeof(uint64_t)));
+        HIP_TRY(launch_bit_rank(d_rowbits.as<uint64_t>(), n, false, d_rank.as<uint64_t>(), d_tmp.as<uint64_t>(), stream));
+        uint32_t h_bad = 0;
+        HIP_TRY(hipMemcpyAsync(&total, d_rank.as<uint64_t>() + n_words, sizeof total, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&h_bad, d_bad.p, sizeof h_bad, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (h_bad != 0) return fail(PQV_ERR_INVALID, range_text);
+        if (total != n_pos) return fail(PQV_ERR_INVALID, dup_text);       // (the member count: a repeated row collapsed)
+        HIP_TRY(d_old_row.alloc(total * sizeof(uint32_t)));
+        HIP_TRY(d_new_rows.alloc(n_pos * sizeof(uint32_t)));
+        HIP_TRY(launch_list_compact(nullptr, n, d_rowbits.as<uint64_t>(), false, d_rank.as<uint64_t>(), d_old_row.as<uint32_t>(), stream));
+        HIP_TRY(launch_lists_remap(d_ids, n_pos, d_rowbits.as<uint64_t>(), n, d_rank.as<uint64_t>(), d_new_rows.as<uint32_t>(), stream));
+        if (!keep_device_lists()) {
+            idx->list_rows.resize(n_pos);
+            HIP_TRY(hipMemcpyAsync(idx->list_rows.data(), d_new_rows.p, n_pos * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        }
+        HIP_TRY(hipStreamSynchronize(stream));       // (the work buffers leave scope)
+        if (keep_device_lists()) adopt_device_lists(idx.get(), d_new_rows, corpus->device, n_pos);
+    }
+    const double t1 = now_s();
+    pqv_corpus *made = nullptr;
+    if (int rc = pqv_corpus_create_impl(corpus->device, std::max(capacity_rows, total), dim, &made)) return rc;
+    std::unique_ptr<pqv_corpus> dense(made);
+    EventSet ev;
+    DevBuf d_copy;
+    const size_t row_bytes = static_cast<size_t>(total) * dim * sizeof(float);
+    if (stats) {
+        for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(d_copy.alloc(row_bytes));
+        HIP_TRY(hipEventRecord(ev.e[0], stream));
+    }
+    HIP_TRY(launch_rows_gather(corpus->d_rows, d_old_row.as<uint32_t>(), total, dim, dense->d_rows, stream));
+    if (stats) {
+        HIP_TRY(hipEventRecord(ev.e[1], stream));
+        HIP_TRY(hipEventRecord(ev.e[2], stream));
+        if (row_bytes) HIP_TRY(hipMemcpyAsync(d_copy.p, dense->d_rows, row_bytes, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipEventRecord(ev.e[3], stream));
+    }
+    if (old_row && total) HIP_TRY(hipMemcpyAsync(old_row, d_old_row.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    dense->n = total;
+    idx->set_row_bound(total);
+    idx->permutation_of = total;                     // every new row is in exactly one list
+    if (stats) {
+        float ms_g = 0.0f, ms_copy = 0.0f;
+        (void)hipEventElapsedTime(&ms_g, ev.e[0], ev.e[1]);
+        (void)hipEventElapsedTime(&ms_copy, ev.e[2], ev.e[3]);
+        std::fprintf(stderr, "pqv_index_compact: %llu of %llu rows stay: members + rank + lists %.3f ms, rows %.3f ms; gather kernel %.4f ms for "
+                             "%.0f row bytes (%.1f GB/s written), device-to-device copy of the same bytes %.4f ms\n",
+                     (unsigned long long)total, (unsigned long long)n, (t1 - t0) * 1e3, (now_s() - t1) * 1e3, ms_g, (double)row_bytes,
+                     ms_g > 0.0f ? row_bytes / (ms_g * 1e6) : 0.0, ms_copy);
+    }
+    *corpus_out = dense.release();
+    *index_out = idx.release();
+    return PQV_OK;
+}
+
 }  // namespace
+
+extern "C" int pqv_index_remove(const pqv_index *index, int device, const uint8_t *remove, uint64_t n_flags, pqv_index **out) {
+    return guard([&] { return index_remove_impl(index, device, remove, nullptr, false, n_flags, nullptr, out); });
+}
+extern "C" int pqv_index_remove_device(const pqv_index *index, int device, const void *d_remove, uint64_t n_flags, void *hip_stream,
+                                       pqv_index **out) {
+    return guard([&] { return index_remove_impl(index, device, nullptr, d_remove, true, n_flags, hip_stream, out); });
+}
+extern "C" int pqv_index_remove_rows(const pqv_index *index, int device, const uint32_t *rows, uint64_t m, pqv_index **out) {
+    return guard([&] { return index_remove_rows_impl(index, device, rows, m, out); });
+}
+extern "C" int pqv_index_compact(const pqv_index *index, const pqv_corpus *corpus, uint64_t capacity_rows, pqv_corpus **corpus_out,
+                                 pqv_index **index_out, uint32_t *old_row) {
+    return guard([&] { return index_compact_impl(index, corpus, capacity_rows, corpus_out, index_out, old_row); });
+}
 
 extern "C" int pqv_index_assign(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows,
                                 uint32_t *cluster_out) {
@@ -3149,7 +3506,10 @@ static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, 
                                          " does not match corpus dimension " + std::to_string(corpus->dim));
     if (index->permutation_of != 0 ? index->permutation_of != corpus->n : false)
         return fail(PQV_ERR_INVALID, "index row id out of range for this corpus");
-    if (index->permutation_of == 0) {     // (a build's lists are a permutation of the corpus' rows; anything else is checked)
+    // (a build's lists are a permutation of the corpus' rows; anything else is checked: by the row bound where the index knows one
+    //  that fits -- an appended or a removed index, whose lists may still be on the device -- else row by row)
+    uint64_t known_bound = 0;
+    if (index->permutation_of == 0 && !(index->known_row_bound(&known_bound) && known_bound <= corpus->n)) {
         const std::vector<uint32_t> *rv = index->rows->get();
         if (!rv) return PQV_ERR_HIP;
         for (uint32_t r : *rv)

@@ -822,6 +822,25 @@ hipError_t launch_list_sort(const uint32_t *assign, uint64_t n, uint32_t k, uint
 // aligned); old_rows may be NULL where the old lists are empty.  k <= 4096.
 hipError_t launch_list_splice(const uint64_t *old_off, const uint32_t *old_rows, const uint64_t *add_off, const uint32_t *add_rows,
                               uint32_t k, uint32_t first_row, uint64_t total, uint64_t *out_off, uint32_t *out_rows, hipStream_t s);
+// Ranking over a bitset (kernels_remove.hip; pqv_index_remove / pqv_index_compact).  A bitset of n_bits bits is ceil(n_bits / 64)
+// words; `invert` reads the stored bits as "leaves" (launch_mask_layout's image of the remove flags), bits at or beyond n_bits never
+// count.  launch_bit_rank: rank[w] = set bits of the words before w, rank[ceil(n_bits / 64)] = the total (rank holds one entry more
+// than the words); block_tmp holds bit_rank_blocks(n_bits) + 1 u64.
+uint64_t bit_rank_blocks(uint64_t n_bits);
+hipError_t launch_bit_rank(const uint64_t *bits, uint64_t n_bits, bool invert, uint64_t *rank, uint64_t *block_tmp, hipStream_t s);
+// out[set bits below p] = ids ? ids[p] : p for every set position p < n_pos (<= 2^32), order kept; out holds the total
+hipError_t launch_list_compact(const uint32_t *ids, uint64_t n_pos, const uint64_t *bits, bool invert, const uint64_t *rank, uint32_t *out,
+                               hipStream_t s);
+// new_off[c] = set bits below position old_off[c] (old_off[c] <= n_pos), c in [0, n_entries)
+hipError_t launch_offsets_rank(const uint64_t *old_off, uint32_t n_entries, const uint64_t *bits, uint64_t n_pos, bool invert,
+                               const uint64_t *rank, uint64_t *new_off, hipStream_t s);
+// member[ids[p]] = 1 (member: n_rows zeroed bytes); *bad |= 1 where an id is >= n_rows (nothing is written for it)
+hipError_t launch_member_bytes(const uint32_t *ids, uint64_t n_pos, uint64_t n_rows, uint8_t *member, uint32_t *bad, hipStream_t s);
+// out[p] = set bits of rowbits below ids[p] (rowbits / rank over n_rows row ids; out 16-byte aligned)
+hipError_t launch_lists_remap(const uint32_t *ids, uint64_t n_pos, const uint64_t *rowbits, uint64_t n_rows, const uint64_t *rank,
+                              uint32_t *out, hipStream_t s);
+// dst[j, :] = src[old_row[j], :] for j < m, bit for bit (every old_row[j] is a row of src)
+hipError_t launch_rows_gather(const float *src, const uint32_t *old_row, uint64_t m, uint32_t dim, float *dst, hipStream_t s);
 hipError_t launch_count_changed(const uint32_t *cur, const uint32_t *prev, uint64_t n, unsigned long long *changed, hipStream_t s);
 
 // pqv_rerank's running state <-> merge lists (see kernels_layout.hip)
