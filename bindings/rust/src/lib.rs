@@ -956,7 +956,7 @@ impl Drop for RowKeys {
 pub struct TableSearcher<'c> {
     inner: Searcher<'c>,
     row_base: Vec<u64>,
-    n_rows: Vec<u64>,
+    extent: Vec<u64>,
 }
 
 impl<'c> TableSearcher<'c> {
@@ -975,8 +975,9 @@ impl<'c> TableSearcher<'c> {
         check(unsafe {
             sys::pqv_table_searcher_create(ptrs.as_mut_ptr(), ptrs.len() as u32, row_base.as_ptr(), corpus.raw, flags, &mut raw)
         })?;
-        let n_rows = indexes.iter().map(|i| unsafe { sys::pqv_index_n_rows(i.raw) }).collect();
-        Ok(Self { inner: Searcher { raw, _corpus: std::marker::PhantomData }, row_base: row_base.to_vec(), n_rows })
+        // a file's extent is its index' row bound: after a remove the ids run past the count of list rows
+        let extent = indexes.iter().map(|i| unsafe { sys::pqv_index_row_bound(i.raw) }).collect();
+        Ok(Self { inner: Searcher { raw, _corpus: std::marker::PhantomData }, row_base: row_base.to_vec(), extent })
     }
 
     /// A corpus row of this table -> (file, row in that file); `None` outside every file.
@@ -984,7 +985,7 @@ impl<'c> TableSearcher<'c> {
         let r = row as u64;
         let f = self.row_base.partition_point(|&b| b <= r).checked_sub(1)?;
         let local = r - self.row_base[f];
-        if row == u32::MAX || local >= self.n_rows[f] { None } else { Some((f, local as u32)) }
+        if row == u32::MAX || local >= self.extent[f] { None } else { Some((f, local as u32)) }
     }
 }
 

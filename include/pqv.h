@@ -215,7 +215,11 @@ int pqv_index_build(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_
  * argument, a dimension mismatch, a range that ends past pqv_corpus_rows(corpus) or past 2^32, or a released row-order copy.
  * A searcher is bound to the rows its index covers: pqv_searcher_create still requires a BUILT index to cover exactly the corpus'
  * rows, so after the corpus grew the old index makes no new searcher (searchers made before keep working on the rows they have);
- * make the new searcher from the appended index. */
+ * make the new searcher from the appended index.  What an old searcher already holds -- its masks, row keys and results -- stays
+ * bit for bit what it was however often the corpus grows and whatever is removed or compacted on descendants of its index.  A
+ * row mask or row keys MADE on it after the growth are sized by the corpus' CURRENT row count (pqv_corpus_rows now, not at the
+ * searcher's creation; the old length is refused); the rows past the searcher's lists are in no list, so their entries are
+ * carried and never read.  A first PQV_COSINE call after the growth normalises the rows the searcher has. */
 
 /* nearest_centroid (src/ivf/index.rs:244-257) of corpus rows [first_row, first_row + n_rows) under the index' centroids:
  * cluster_out[i] = argmin_j squared_l2_distance(row, centroid j), strict '<' from +inf in ascending j (lowest index wins a tie,
@@ -290,6 +294,10 @@ int  pqv_index_from_parts(uint32_t dim, uint32_t n_clusters, const float *centro
 uint32_t pqv_index_dim(const pqv_index *index);              /* IvfIndex::dim() :53 */
 uint32_t pqv_index_n_clusters(const pqv_index *index);
 uint64_t pqv_index_n_rows(const pqv_index *index);           /* sum of list lengths   */
+/* The row bound: largest indexed row id + 1 as a build, an append, a remove (which carries it over, never lowers it) or a compact
+ * left it; for an index from bytes or parts the largest id its lists hold + 1 (one host scan on first use); 0 for empty lists or
+ * where the lists could not be read (pqv_last_error).  What pqv_index_append starts at and what a table spaces its files by. */
+uint64_t pqv_index_row_bound(const pqv_index *index);
 const float    *pqv_index_centroids(const pqv_index *index); /* [n_clusters*dim]      */
 const uint64_t *pqv_index_list_offsets(const pqv_index *index); /* [n_clusters+1]     */
 const uint32_t *pqv_index_list_rows(const pqv_index *index); /* lists, concatenated   */
@@ -303,12 +311,15 @@ int  pqv_searcher_create(const pqv_index *index, pqv_corpus *corpus, uint32_t fl
                          pqv_searcher **out);
 void pqv_searcher_free(pqv_searcher *searcher);
 /* A table of indexed files on one GPU (src/df_vector/index_exec.rs:85-164 on one device): file f's rows are corpus rows
- * [row_base[f], row_base[f] + pqv_index_n_rows(indexes[f])), its index' row ids are local to the file.  Returns an ordinary
+ * [row_base[f], row_base[f] + bound_f), bound_f = pqv_index_row_bound(indexes[f]) (largest indexed row id + 1, carried over by
+ * pqv_index_remove: pqv_index_n_rows for a built or appended index, more after a remove, whose surviving rows keep their ids --
+ * a file that had a DELETE stays in its table, the removed rows' slots are never candidates); its index' row ids are local to
+ * the file and below bound_f.  Returns an ordinary
  * pqv_searcher on which nprobe means "per file": a query probes the first min(nprobe, kc_f) centroids of each file's
  * find_closest_centroids, reported as global list ids cluster_base[f] + c, file after file (P = the sum of those counts).  The
  * candidate sequence is file 0's candidate_rows, then file 1's, ... with rows shifted by row_base; top-k orders by (distance,
  * position in that sequence), as per-file searches merged with pqv_merge_topk.  Row ranges must increase without overlapping
- * and lie inside the corpus; all dims are equal.  P > 1024: as min(nprobe, n_clusters) > 1024 today.
+ * (row_base[f + 1] >= row_base[f] + bound_f) and lie inside the corpus; all dims are equal.  P > 1024: as min(nprobe, n_clusters) > 1024 today.
  * max_candidates > 0 returns PQV_ERR_UNSUPPORTED on a table created without PQV_TABLE_CAP_ROUND_ROBIN.  With that flag the cap is
  * the reference's (exec.rs:207-245): file f of a query considers the first t_f of its c_f candidates, t_f being what
  * CandidateCursor::next_batch(max_candidates) of a fresh cursor over the files (access.rs:214-242, file 0 first) takes from it --

@@ -124,6 +124,7 @@ SIGNATURES = {
     "pqv_index_dim": (C.c_uint32, [vp]),
     "pqv_index_n_clusters": (C.c_uint32, [vp]),
     "pqv_index_n_rows": (C.c_uint64, [vp]),
+    "pqv_index_row_bound": (C.c_uint64, [vp]),
     "pqv_index_centroids": (f32p, [vp]),
     "pqv_index_list_offsets": (u64p, [vp]),
     "pqv_index_list_rows": (u32p, [vp]),

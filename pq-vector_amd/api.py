@@ -1428,7 +1428,8 @@ def _attach_table_columns(searcher, paths, names):
             continue
         values = valid = None
         dtype0 = None
-        for f, (p, b, n) in enumerate(zip(paths, searcher.row_base.tolist(), searcher.n_rows.tolist())):
+        # (a file's rows are its extent, not its index' list rows: a file that had rows removed keeps every row's column value)
+        for f, (p, b, n) in enumerate(zip(paths, searcher.row_base.tolist(), searcher.extents.tolist())):
             a, v, dtype = parquet_io.read_scalar_column(p, name)
             if a.size != int(n):
                 raise PqvError(_ffi.PQV_ERR_INVALID, f"column {name!r} of file {f} has {a.size} rows, its index has {int(n)}")
@@ -1467,7 +1468,7 @@ def _resolve_table_where(per_file, paths, searcher):
         _attach_table_columns(searcher, paths, per_file.columns())
         return searcher.row_mask_predicate(per_file)
     allowed = np.zeros(searcher._corpus.rows, dtype=np.uint8)
-    for xf, p, b, n in zip(per_file, paths, searcher.row_base.tolist(), searcher.n_rows.tolist()):
+    for xf, p, b, n in zip(per_file, paths, searcher.row_base.tolist(), searcher.extents.tolist()):
         a = parquet_io.row_mask_from_expression(p, xf) if _is_expression(xf) else xf
         a = _allow_array(a, int(n), "where()")
         allowed[int(b):int(b) + int(n)] = a
@@ -1724,7 +1725,7 @@ def _table_args(indexes, corpus, row_base):
             raise PqvError(_ffi.PQV_ERR_INVALID, f"index dimension {ix.dim} of file {f} does not match dimension {dim0} of file 0")
         if ix.dim != corpus.dim:
             raise PqvError(_ffi.PQV_ERR_INVALID, f"index dimension {ix.dim} of file {f} does not match corpus dimension {corpus.dim}")
-        b, n = int(rb[f]), ix.n_rows
+        b, n = int(rb[f]), ix.row_bound          # the file's extent: ids a remove left free stay the file's
         if f > 0 and b < end:
             raise PqvError(_ffi.PQV_ERR_INVALID, f"row range of file {f} starts at {b}, inside the rows of the files before it "
                                                  "(ranges must be increasing and disjoint)")
@@ -1738,8 +1739,10 @@ def _table_args(indexes, corpus, row_base):
 
 class TableSearcher(Searcher):
     """Several indexed files searched as ONE table on one GPU: file f's rows are corpus rows [row_base[f], row_base[f] + its
-    rows).  nprobe counts per file; probe() returns the P = sum_f min(nprobe, kc_f) global list ids, file after file; rows
-    come back as corpus rows (split_rows maps them to (file, local row)).  max_candidates > 0 needs
+    extent), the extent being its index' row bound: its row count until a remove, after which the ids run on up to the bound
+    (n_rows keeps the files' list rows, extents their bounds).  nprobe counts per file; probe() returns the P = sum_f
+    min(nprobe, kc_f) global list ids, file after file; rows come back as corpus rows (split_rows maps them to (file, local
+    row), by the extents).  max_candidates > 0 needs
     flags |= PQV_TABLE_CAP_ROUND_ROBIN: file f then considers the first round_robin_quota(its candidate counts, max_candidates)[f]
     of its candidates, as the reference's CandidateCursor deals them; without the flag it is refused (PQV_ERR_UNSUPPORTED)."""
 
@@ -1756,8 +1759,22 @@ class TableSearcher(Searcher):
         self.n_clusters = sum(ix.n_clusters for ix in indexes)
         self.n_files = len(indexes)
         self.row_base = rb.copy()
-        self.n_rows = np.array([ix.n_rows for ix in indexes], dtype=np.uint64)
+        self.n_rows = np.array([ix.n_rows for ix in indexes], dtype=np.uint64)          # list rows of each file
+        self.extents = np.array([ix.row_bound for ix in indexes], dtype=np.uint64)      # the files' local ids run below these
         self.cluster_base = np.concatenate([[0], np.cumsum([ix.n_clusters for ix in indexes])]).astype(np.uint32)
+
+    _extents = None
+
+    @property
+    def extents(self):
+        """u64 [n_files]: the rows of each file as the table sees them -- its index' row bound; for files read from Parquet
+        (searcher_for_parquet_files) the file's row count, which is at least that.  n_rows where none were given: the two are
+        equal until rows are removed."""
+        return self.n_rows if self._extents is None else self._extents
+
+    @extents.setter
+    def extents(self, value):
+        self._extents = np.asarray(value, dtype=np.uint64).reshape(-1)
 
     def probe_count(self, nprobe):
         """P: the lists one query probes (the sum over the files of min(nprobe, kc_f))."""
@@ -1773,12 +1790,13 @@ class TableSearcher(Searcher):
 
     def split_rows(self, rows):
         """Corpus rows -> (file, local row) arrays (0xFFFFFFFF, an empty slot, maps to file -1)."""
-        return split_table_rows(rows, self.row_base, self.n_rows)
+        return split_table_rows(rows, self.row_base, self.extents)
 
 
 def split_table_rows(rows, row_base, n_rows=None):
     """Corpus rows of a table -> (file index int64, row in that file u32); rows outside every file (and 0xFFFFFFFF) give file
-    -1.  row_base: increasing first rows of the files; n_rows: their row counts (default: up to the next file's base)."""
+    -1.  row_base: increasing first rows of the files; n_rows: their extents -- the row counts, or the row bounds where rows were
+    removed (default: up to the next file's base)."""
     rows = np.asarray(rows, dtype=np.uint64)
     rb = np.asarray(row_base, dtype=np.uint64).reshape(-1)
     f = np.searchsorted(rb, rows, side="right").astype(np.int64) - 1
@@ -1853,6 +1871,7 @@ def searcher_for_parquet_files(paths, device=0, round_robin_cap=False):
             if round_robin_cap:
                 flags |= _ffi.PQV_TABLE_CAP_ROUND_ROBIN
             hit = TableSearcher(indexes, corpus, row_base, flags)
+            hit.extents = counts          # (a file's rows: at least its index' row bound, more where its newest rows were removed)
         except Exception:
             corpus.close()
             raise

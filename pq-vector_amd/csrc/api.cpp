@@ -1451,6 +1451,10 @@ extern "C" int pqv_index_from_parts(uint32_t dim, uint32_t n_clusters, const flo
 extern "C" uint32_t pqv_index_dim(const pqv_index *i) { return i ? i->dim : 0; }
 extern "C" uint32_t pqv_index_n_clusters(const pqv_index *i) { return i ? i->n_clusters : 0; }
 extern "C" uint64_t pqv_index_n_rows(const pqv_index *i) { return i ? i->n_rows() : 0; }
+extern "C" uint64_t pqv_index_row_bound(const pqv_index *i) {
+    uint64_t b = 0;
+    return i && i->row_bound(&b) ? b : 0;
+}
 extern "C" const float *pqv_index_centroids(const pqv_index *i) { return i ? i->centroids.data() : nullptr; }
 extern "C" const uint64_t *pqv_index_list_offsets(const pqv_index *i) { return i ? i->list_off.data() : nullptr; }
 extern "C" const uint32_t *pqv_index_list_rows(const pqv_index *i) {
@@ -3695,7 +3699,8 @@ static int pqv_table_searcher_create_impl(const pqv_index *const *indexes, uint3
         if (ix->dim != corpus->dim)
             return fail(PQV_ERR_INVALID, "index dimension " + std::to_string(ix->dim) + " of file " + fs +
                                              " does not match corpus dimension " + std::to_string(corpus->dim));
-        const uint64_t n_f = ix->n_rows();
+        uint64_t n_f = 0;                              // the file's extent: its row bound (ids a remove left free stay the file's)
+        if (!ix->row_bound(&n_f)) return PQV_ERR_HIP;
         if (f > 0 && row_base[f] < rows_end)
             return fail(PQV_ERR_INVALID, "row range of file " + fs + " starts at " + std::to_string(row_base[f]) +
                                              ", inside the rows of the files before it (ranges must be increasing and disjoint)");
@@ -3718,12 +3723,14 @@ static int pqv_table_searcher_create_impl(const pqv_index *const *indexes, uint3
         const pqv_index *ix = indexes[f];
         const std::vector<uint32_t> *rv = ix->rows->get();
         if (!rv) return PQV_ERR_HIP;
-        const uint64_t n_f = ix->n_rows(), o = all.list_off.back();
+        uint64_t bound_f = 0;
+        if (!ix->row_bound(&bound_f)) return PQV_ERR_HIP;
+        const uint64_t o = all.list_off.back();
         all.centroids.insert(all.centroids.end(), ix->centroids.begin(), ix->centroids.end());
         for (uint32_t c = 0; c < ix->n_clusters; ++c) all.list_off.push_back(o + ix->list_off[c + 1]);
         const uint32_t rb = static_cast<uint32_t>(row_base[f]);
         for (uint32_t r : *rv) {
-            if (r >= n_f) return fail(PQV_ERR_INVALID, "index row id out of range for file " + std::to_string(f));
+            if (r >= bound_f) return fail(PQV_ERR_INVALID, "index row id out of range for file " + std::to_string(f));
             all.list_rows.push_back(rb + r);
         }
         seg_off[f + 1] = seg_off[f] + ix->n_clusters;
