@@ -369,6 +369,11 @@ int pqv_round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max
  *                   thresholds have seen a piece of each of its lists before the bulk is screened; 0 = list by list
  *   "probe_rows"    batched centroid probe (a lane per centroid): 1 for batches of >= 8 queries (default), 2 always,
  *                   0 = the per-query stream over the centroid table
+ *   "probe_screen"  that batched probe screened on the matrix cores (probe_screen_kernel + probe_resolve_kernel: an f16 contraction
+ *                   against centroid images, exact chains only for the centroids its bounds cannot exclude; same results): 1 by
+ *                   rule (default: >= 128 queries, >= 256 centroids, nprobe <= n_clusters / 4, no table, not PQV_DOT), 2 for every
+ *                   batch the kernels support, 0 off.  The centroid images are made when the searcher is created, or by the
+ *                   first non-zero setting of this option where PQV_PROBE_SCREEN=0 kept creation from making them
  *   "wide_quads"    int8 path, batches: lists probed by 97..160 queries in ONE quad of the wide-quad instance (32-row tiles, one
  *                   8-wave block per CU) instead of two regular quads.  1 (default): by the PREVIOUS batch's shape -- regular quads
  *                   only while most rows of the popular lists sit in lists of > 160 pairs (clustered query loads); 2 always; 0 never

@@ -352,7 +352,8 @@ struct Scratch {
         // takes none, the sorted sets [nq][k], the partial lists' slots [nq][n_part][k * group_size] and lengths [nq][n_part], and the
         // host form's group_rows block
         s_g1_rows, s_g1_dist, s_g1_keys, s_g1_nfound, s_gset_keys, s_gset_slot, s_gpart_slot, s_gpart_cnt, s_grows_out,
-        s_expand_cnt, s_expand_used;    // pqv_topk_expand: the passing rows per probed list u32 [nq][P]; nprobe_used u32 [nq] where the caller takes none
+        s_expand_cnt, s_expand_used,    // pqv_topk_expand: the passing rows per probed list u32 [nq][P]; nprobe_used u32 [nq] where the caller takes none
+        s_ps_q16, s_ps_qn2, s_ps_score; // screened probe: the batch's query images f16 [nq][dim_p], |q - mean|^2 [nq], the scores f32 [nq][kc_pad]
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -368,7 +369,7 @@ struct Scratch {
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
                 &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
                 &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out,
-                &s_expand_cnt, &s_expand_used};
+                &s_expand_cnt, &s_expand_used, &s_ps_q16, &s_ps_qn2, &s_ps_score};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -394,6 +395,12 @@ struct pqv_searcher {
     std::shared_ptr<ListRows> h_rows;      // the index' lists (shared, not copied; the host copy is made by the first call that reads it)
     DevBuf d_cent_t;                   // [dim/4][kc_pad] float4 transpose of the centroids (probe_rows_kernel), dim % 4 == 0
     uint32_t kc_pad = 0;
+    // the screened batched probe (probe_screen_kernel + probe_resolve_kernel): the centroid mean, f16 images of (centroid - mean) at
+    // ONE table-wide scale padded to a multiple of 64 values, |centroid - mean|^2, and the bound's constants; ps.ok: the table is
+    // finite and its scale representable
+    DevBuf d_ps_mu, d_ps_c16, d_ps_cn2;
+    mutable DevBuf d_ps_stats;             // PQV_PROBE_SCREEN_STATS=1 (diagnostic): {queries, exact evaluations, all-exact queries}, printed by destroy
+    struct ProbeScreen { bool ok = false, tried = false; uint32_t dim_p = 0; float inv_cs = 0, fn = 0, e1 = 0, e2s = 0, kS = 0, lo_f = 0, hi_f = 0; } ps;
     DevBuf d_centroids, d_list_off, d_ids, d_mat_ivf, d_stats;
     mutable DevBuf d_row_norm2;            // |x|^2 per storage row (f32 / f16 MFMA screens; see norms_done)
     const float *d_mat = nullptr;          // row storage the re-rank reads
@@ -460,6 +467,8 @@ struct pqv_searcher {
         int chunk_major = 1;               // ... numbered chunk-major (row chunk 0 of every quad first)
         int wide_waves = 0;                // waves per block of the wide kernel: 0 by rule, 4 or 8
         int probe_rows = 1;                // batched centroid probe (probe_rows_kernel) when dim % 4 == 0; 0 = stream_kernel
+        int probe_screen = 1;              // ... screened on the matrix cores (probe_screen_kernel + probe_resolve_kernel): 1 by rule, 0 off,
+                                           // 2 = every batch the kernels support
         uint32_t quad_width = 0;           // queries per quad of the wide kernel (0 = by rule)
         uint32_t min_blocks = 0;           // wide kernel: blocks a launch should at least have before rows per block shrink (0 = by rule)
         int pair_prune = 1;                // int8 path: drop (query, list) pairs whose centre-distance bound exceeds the query's threshold
@@ -498,6 +507,12 @@ struct pqv_searcher {
     ~pqv_searcher();
 };
 pqv_searcher::~pqv_searcher() {
+    if (d_ps_stats.p) {       // PQV_PROBE_SCREEN_STATS=1: what the screened probe left to the exact chains, over the searcher's life
+        unsigned long long h[3] = {0, 0, 0};
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d_ps_stats.p, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
+            std::fprintf(stderr, "[pqv] screened probe: %llu queries, %.2f exact evaluations per query of %u centroids, %llu all-exact queries\n",
+                         h[0], h[0] ? static_cast<double>(h[1]) / static_cast<double>(h[0]) : 0.0, n_clusters, h[2]);
+    }
     for (auto e : ev) (void)hipEventDestroy(e);
     pool_put(device, stream);          // (back to the device's pool: see StreamPool)
 }
@@ -3302,6 +3317,7 @@ void opts_from_env(pqv_searcher::Opts &o) {
     o.seed_refine = static_cast<int>(num("PQV_SEED_REFINE", o.seed_refine));
     o.single_bucket = static_cast<int>(num("PQV_SINGLE_BUCKET", o.single_bucket));
     o.probe_rows = static_cast<int>(num("PQV_PROBE_ROWS", o.probe_rows));
+    o.probe_screen = static_cast<int>(num("PQV_PROBE_SCREEN", o.probe_screen));
     o.quad_width = static_cast<uint32_t>(num("PQV_QUAD_WIDTH", o.quad_width));
     o.min_blocks = static_cast<uint32_t>(num("PQV_MIN_BLOCKS", o.min_blocks));
     o.wide_quads = static_cast<int>(num("PQV_WIDE_QUADS", o.wide_quads));
@@ -3497,6 +3513,57 @@ int ensure_blocked_copy(const pqv_searcher *s, int op, hipStream_t stream) {
     return PQV_OK;
 }
 
+// The screened probe's centroid side, made once per searcher: mu = the centroid mean (any fixed vector serves the bound; the mean
+// shrinks |q - mu| |c - mu|, which scales its slack), f16 images of (c - mu) at ONE scale 2^8 / max |c - mu|, |c - mu|^2, and the
+// constants of probe_bound (kernels_probe_screen.hip; derivation in DESIGN 5.1), in units of 2^-24 = u and 2^-11 = h:
+//   e1  per |a||b|: 2 h' + h'^2 (h' = h + u + h u: both images rounded to f16 after an f32 product), the contraction's f32
+//       accumulation in any order (2.02 dim_p u), the query image's subnormal components, the roundings of the estimate
+//   e2s per |a|: sqrt(dim) 2^-25 / cscale -- components of a centroid image below 2^-14 carry an ABSOLUTE rounding error
+//   kS  per |a|^2 + |b|^2: the norms' summation (center_normalize_f16_sum_depth), the roundings of q - mu and c - mu, of the sum
+//   cm  = (dim / 4 + 8) u: the reference chain rounds each term six times and the running sum once per group, all terms >= 0
+// ps.ok stays false -- the plan keeps probe_rows_kernel -- for a table with a non-finite norm or a scale f32 cannot hold.
+hipError_t probe_screen_images(pqv_searcher *s) {
+    using namespace pqv;
+    const uint32_t kc = s->n_clusters, dim = s->dim, dim_p = (dim + 63) / 64 * 64;
+    s->ps.tried = true;
+#define PS_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
+    PS_TRY(s->d_ps_mu.alloc(static_cast<size_t>(dim) * sizeof(float)));
+    PS_TRY(s->d_ps_c16.alloc(static_cast<size_t>(s->kc_pad) * dim_p * sizeof(uint16_t)));
+    PS_TRY(s->d_ps_cn2.alloc(static_cast<size_t>(s->kc_pad) * sizeof(float)));
+    const float *d_c = s->d_centroids.as<float>();
+    PS_TRY(launch_col_mean(d_c, kc, dim, s->d_ps_mu.as<float>(), s->stream));
+    // the norms first (the images of this pass are overwritten below), then the images at the scale the norms give
+    PS_TRY(launch_center_normalize_f16(d_c, s->d_ps_mu.as<float>(), kc, s->kc_pad, dim, dim_p, s->d_ps_cn2.as<float>(), s->d_ps_c16.p, s->stream));
+    std::vector<float> h_cn2(kc);
+    PS_TRY(hipMemcpyAsync(h_cn2.data(), s->d_ps_cn2.p, static_cast<size_t>(kc) * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    PS_TRY(hipStreamSynchronize(s->stream));
+    double mx = 0.0;
+    for (float v : h_cn2) { if (!(v <= 3.0e38f)) return hipSuccess; mx = std::max<double>(mx, v); }
+    const float cscale = mx > 0.0 ? static_cast<float>(256.0 / (std::sqrt(mx) * 1.000001)) : 1.0f;
+    const float inv_cs = static_cast<float>(1.000001 / static_cast<double>(cscale));
+    if (!(cscale > 0.0f && cscale < 3.0e38f && inv_cs > 0.0f && inv_cs < 3.0e38f)) return hipSuccess;
+    PS_TRY(launch_center_normalize_f16(d_c, s->d_ps_mu.as<float>(), kc, s->kc_pad, dim, dim_p, s->d_ps_cn2.as<float>(), s->d_ps_c16.p, s->stream, cscale));
+#undef PS_TRY
+    const double u = 5.9604644775390625e-08, h = 4.8828125e-04, hp = h + u + h * u;
+    const double sub = std::sqrt(static_cast<double>(dim)) * 2.98023223876953125e-08;
+    const double g = (center_normalize_f16_sum_depth(dim) + 2) * u * 1.01;
+    const double cm = (dim / 4 + 8) * u;
+    auto up = [](double v) { return std::nextafter(static_cast<float>(v), INFINITY); };
+    pqv_searcher::ProbeScreen &ps = s->ps;
+    ps.dim_p = dim_p; ps.inv_cs = inv_cs;
+    ps.fn = up((1.0 + g) * 1.000001);
+    ps.e1 = up((2.0 * hp + hp * hp + 1.01 * 2.02 * dim_p * u + 1.01 * sub / 256.0 + 2.0e-6) * 1.001);
+    ps.e2s = up(static_cast<double>(inv_cs) * sub * 1.02);
+    ps.kS = up(1.01 * g + 16.0 * u);
+    ps.lo_f = std::nextafter(static_cast<float>(1.0 - cm - 1.0e-6), 0.0f);
+    ps.hi_f = up(1.0 + cm + 1.0e-6);
+    ps.ok = ps.e2s < 3.0e38f;
+    if (const char *e = std::getenv("PQV_PROBE_SCREEN_STATS"); e && *e && *e != '0') {
+        if (s->d_ps_stats.alloc(3 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemsetAsync(s->d_ps_stats.p, 0, 3 * sizeof(unsigned long long), s->stream);
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, uint32_t flags,
@@ -3572,6 +3639,9 @@ static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, 
         s->kc_pad = (s->n_clusters + 255) / 256 * 256;
         S_TRY(s->d_cent_t.alloc(static_cast<size_t>(s->kc_pad) * s->dim * sizeof(float)));
         S_TRY(pqv::launch_transpose_rows4(s->d_centroids.as<float>(), s->n_clusters, s->kc_pad, s->dim, s->d_cent_t.p, s->stream));
+        if (s->opt.probe_screen) {
+            if (hipError_t e = probe_screen_images(s)) S_TRY(e);
+        }
     }
     mark("centroid tables");
     if (s->n) {
@@ -3912,6 +3982,7 @@ struct TopkPlan {
     uint32_t probe_bpl;     // blocks over the centroid matrix
     uint32_t probe_kpart;   // entries per partial list of the probe pass (np, or 64 unsorted from probe_rows_kernel)
     bool probe_rows;        // batched probe_rows_kernel instead of the per-query stream_kernel
+    bool probe_screen;      // ... screened: probe_screen_kernel + probe_resolve_kernel write the same partial lists
     uint32_t rr_rows_per_block, rr_bpl;
     uint32_t n_part_probe, n_part_rr;
     bool tile;              // batched cluster-major tiles instead of one stream per (query, list)
@@ -3983,6 +4054,15 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     p.probe_rows = s->opt.probe_rows && s->kc_pad != 0 && (nq >= 8 || s->opt.probe_rows > 1) &&
                    static_cast<uint64_t>(nq) * s->kc_pad * 12 <= (2ull << 30);
     if (metric == PQV_DOT) p.probe_rows = false;    // (probe_rows_kernel is L2 arithmetic: dot_stream_kernel over the centroid matrix)
+    // the screened form: where the contraction pays.  Measured on MI355X, 768 dims, nprobe 32, kernel time per batch in us
+    // (rocprofv3 kernel trace, 4 calls each): probe_rows_kernel at 32 / 64 / 128 / 256 queries -- 1024 centroids 31.8 / 32.8 / 38.5 /
+    // 40.4, 256 centroids 36.3 / 35.5 / 36.6 / 36.2 (a chain of 192 row loads whatever the batch); the screened route at all eight
+    // shapes -- query images 4-6 + probe_screen_kernel 6.9-7.6 + probe_resolve_kernel 16.0-16.6 = 27-31.  From 128 queries on the
+    // gain (8-12 us) is worth two more launches; below, it is 2-8 us of kernel time against them and the exact kernel stays.
+    // Fewer than 256 centroids were not measured: they leave the 64 x 64 tiles a handful of blocks, and keep the exact kernel.
+    // With np beyond kc / 4 (every-list parity runs, expanding searches that probe far) most centroids are contenders.
+    p.probe_screen = p.probe_rows && s->ps.ok && o.probe_screen && !s->n_files && p.np >= 1 && p.np <= s->n_clusters / 4 &&
+                     (o.probe_screen > 1 || (nq >= 128 && s->n_clusters >= 256));
     p.probe_kpart = p.probe_rows ? 64u : p.np;
     if (s->n_files && !p.probe_rows) {
         // table, stream_kernel probe: one list per file (no block straddles two files), the nprobe nearest of a file kept per partial list
@@ -4192,7 +4272,23 @@ int enqueue_probe(const pqv_searcher *s, Scratch &sc, const TopkPlan &p, const f
     using namespace pqv;
     uint64_t *keys = const_cast<uint64_t *>(pm.part_keys);
     uint32_t *vals = const_cast<uint32_t *>(pm.part_vals);
-    if (p.probe_rows) {     // a batch: a lane per centroid, the chains of up to 8 queries in registers
+    if (p.probe_screen) {   // a batch, screened: f16 images of the queries, the contraction, exact chains for the contenders
+        const pqv_searcher::ProbeScreen &ps = s->ps;
+        HIP_TRY(sc.s_ps_q16.ensure(static_cast<size_t>(nq) * ps.dim_p * sizeof(uint16_t)));
+        HIP_TRY(sc.s_ps_qn2.ensure(static_cast<size_t>(nq) * sizeof(float)));
+        HIP_TRY(sc.s_ps_score.ensure(static_cast<size_t>(nq) * s->kc_pad * sizeof(float)));
+        HIP_TRY(launch_center_normalize_f16(d_queries, s->d_ps_mu.as<float>(), nq, nq, s->dim, ps.dim_p, sc.s_ps_qn2.as<float>(), sc.s_ps_q16.p, stream));
+        ProbeScreenArgs pr{};
+        pr.q16 = sc.s_ps_q16.as<uint16_t>(); pr.c16 = s->d_ps_c16.as<uint16_t>(); pr.qn2 = sc.s_ps_qn2.as<float>(); pr.cn2 = s->d_ps_cn2.as<float>();
+        pr.score = sc.s_ps_score.as<float>(); pr.queries = d_queries; pr.centroids = s->d_centroids.as<float>();
+        pr.nq = nq; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim; pr.dim_p = ps.dim_p; pr.np = p.np;
+        pr.inv_cs = ps.inv_cs; pr.fn = ps.fn; pr.e1 = ps.e1; pr.e2s = ps.e2s; pr.kS = ps.kS; pr.lo_f = ps.lo_f; pr.hi_f = ps.hi_f;
+        pr.part_keys = keys; pr.part_vals = vals;
+        pr.zero_u32 = zero_u32; pr.zero_n = zero_n;
+        pr.stats = s->d_ps_stats.as<unsigned long long>();
+        HIP_TRY(launch_probe_screen(pr, stream));
+        s->counters.kernel_launches += 2;       // (the callers count ONE distance pass and the merge: this route enqueues three launches in its place)
+    } else if (p.probe_rows) {     // a batch: a lane per centroid, the chains of up to 8 queries in registers
         ProbeRowsArgs pr{};
         pr.cent_t = s->d_cent_t.as<float4>(); pr.queries = d_queries;
         pr.nq = nq; pr.kc = s->n_clusters; pr.kc_pad = s->kc_pad; pr.dim = s->dim;
@@ -6432,6 +6528,14 @@ static int pqv_searcher_set_option_impl(pqv_searcher *s, const char *name, int64
     else if (n == "item_grid") o.item_grid = static_cast<int>(value);          // 2 = also for the 8-wave blocks
     else if (n == "chunk_major") o.chunk_major = value != 0;
     else if (n == "probe_rows") o.probe_rows = static_cast<int>(value);       // 2 = for any batch size
+    else if (n == "probe_screen") {       // 0 = off, 2 = every batch the kernels support
+        o.probe_screen = static_cast<int>(value);
+        // a searcher created with the option off (PQV_PROBE_SCREEN=0) has no images yet: made here, once
+        if (value != 0 && !s->ps.tried && s->kc_pad != 0 && !s->n_files) {
+            const hipError_t e = probe_screen_images(s);
+            if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PQV_ERR_OOM : PQV_ERR_HIP, std::string("probe_screen_images: ") + hipGetErrorString(e));
+        }
+    }
     else if (n == "quad_width") o.quad_width = static_cast<uint32_t>(std::max<int64_t>(0, value));
     else if (n == "min_blocks") o.min_blocks = static_cast<uint32_t>(std::max<int64_t>(0, value));
     else if (n == "pair_prune") o.pair_prune = value != 0;
@@ -6558,7 +6662,8 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
         std::snprintf(kn, sizeof kn, " | kernels: dot_stream_kernel<%d, %d, 0, %s, 0>; dot_merge_kernel<%d>",
                       (al && (s->sdim / 4) % 64 == 0) ? 64 : 32, k <= 64 ? 1 : k <= 256 ? 4 : 16, al ? "true" : "false", k <= 64 ? 1 : k <= 256 ? 4 : 16);
     }
-    std::snprintf(buf, len, "%s%s; centroid probe: %s%s", tb, t, p.probe_rows ? "probe_rows_kernel (a lane per centroid)" : metric == PQV_DOT ? "dot_stream_kernel" : "stream_kernel", kn);
+    std::snprintf(buf, len, "%s%s; centroid probe: %s%s", tb, t, p.probe_screen ? "probe_screen_kernel + probe_resolve_kernel (f16 contraction, probe_rows_kernel's exact chains for the contenders)"
+                  : p.probe_rows ? "probe_rows_kernel (a lane per centroid)" : metric == PQV_DOT ? "dot_stream_kernel" : "stream_kernel", kn);
     return PQV_OK;
 }
 extern "C" int pqv_searcher_describe(const pqv_searcher *s, uint32_t nq, uint32_t k, uint32_t nprobe, int metric,
@@ -6574,7 +6679,7 @@ static int pqv_searcher_footprint_impl(const pqv_searcher *s, uint64_t *row_orde
     if (ivf_rows_bytes) *ivf_rows_bytes = s->d_mat_ivf.p ? s->d_mat_ivf.bytes : 0;
     if (blocked_bytes) *blocked_bytes = (s->d_mat_blk_op[0].p ? s->d_mat_blk_op[0].bytes : 0) + (s->d_mat_blk_op[1].p ? s->d_mat_blk_op[1].bytes : 0) +
                                         (s->d_mat_blk_op[2].p ? s->d_mat_blk_op[2].bytes : 0);
-    uint64_t other = s->d_centroids.bytes + s->d_cent_t.bytes + s->d_list_off.bytes + s->d_ids.bytes + s->d_stats.bytes + s->d_row_norm2.bytes + s->d_blk_off.bytes +
+    uint64_t other = s->d_centroids.bytes + s->d_cent_t.bytes + s->d_ps_mu.bytes + s->d_ps_c16.bytes + s->d_ps_cn2.bytes + s->d_ps_stats.bytes + s->d_list_off.bytes + s->d_ids.bytes + s->d_stats.bytes + s->d_row_norm2.bytes + s->d_blk_off.bytes +
                      s->d_center.bytes + s->d_list_scale.bytes + s->d_list_half.bytes + s->d_list_radius.bytes + s->d_row_n2i.bytes + s->d_row_res.bytes;
     for (const Scratch &l : s->lanes)
         for (const DevBuf *b : l.bufs()) other += b->p ? b->bytes : 0;

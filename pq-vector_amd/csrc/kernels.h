@@ -319,6 +319,31 @@ struct ProbeRowsArgs {
     uint32_t        zero_n;
 };
 hipError_t launch_probe_rows(const ProbeRowsArgs &a, hipStream_t s);
+// The same probe, screened (kernels_probe_screen.hip): an f16 contraction of query images against centroid images, bounds of the
+// reference distance from every score, exact chains only for the centroids that can be among a query's np nearest.  Writes
+// probe_rows_kernel's partial lists, KEY_EMPTY where the bounds exclude a centroid.  The images are launch_center_normalize_f16's
+// about ONE vector mu: queries at 2^8 / |q - mu| each, centroids at one table-wide scale cscale.
+struct ProbeScreenArgs {
+    const uint16_t *q16;         // [nq][dim_p]      f16 images of (q - mu) 2^8 / |q - mu|, dim_p a multiple of 64
+    const uint16_t *c16;         // [kc_pad][dim_p]  f16 images of (c - mu) cscale; rows >= kc are zero
+    const float    *qn2;         // [nq]  |q - mu|^2 as the image kernel summed it
+    const float    *cn2;         // [kc]  |c - mu|^2
+    float          *score;       // [nq][kc_pad] scratch
+    const float    *queries;     // [nq, dim]
+    const float    *centroids;   // [kc, dim] row-major
+    uint32_t        nq, kc, kc_pad, dim, dim_p, np;
+    // the bound's constants (api.cpp: probe_screen_images)
+    float           inv_cs;      // >= 1 / cscale
+    float           fn;          // a computed norm times fn is >= the true norm
+    float           e1, e2s, kS; // per unit of |a||b|; per unit of |a| (subnormal image components, / cscale); per unit of |a|^2 + |b|^2
+    float           lo_f, hi_f;  // 1 -+ the reference chain's margin, rounded outwards
+    uint64_t       *part_keys;   // [nq][kc_pad / 64][64], entry c = centroid c
+    uint32_t       *part_vals;
+    uint32_t       *zero_u32;    // optional scratch to zero (as StreamArgs::zero_u32)
+    uint32_t        zero_n;
+    unsigned long long *stats;   // diagnostic, optional [3]: += queries, += exact evaluations, += all-exact queries
+};
+hipError_t launch_probe_screen(const ProbeScreenArgs &a, hipStream_t s);
 struct MergeArgs;
 // one query: probe + probe merge in one launch (kc_pad <= 4096, nprobe <= 64); the last block to finish merges
 // (pr.part_keys: kc_pad keys of scratch; ticket: one zero-initialised u32 that the kernel leaves at zero)
@@ -762,6 +787,9 @@ hipError_t launch_assign_rescore(const float *rows, const float *centroids, uint
 // idx != nullptr: output row r is made from rows[idx[r]]
 hipError_t launch_center_normalize_f16(const float *rows, const float *mu, uint64_t n, uint64_t n_pad, uint32_t dim, uint32_t dim_p,
                                        float *out_n2, void *out, hipStream_t s, float fixed_scale = 0.0f, const uint32_t *idx = nullptr);
+// the longest chain of f32 roundings behind an out_n2 value of that kernel (fused multiply-adds of a lane, then the wave's tree):
+// a sum of non-negative terms is within that many units of 2^-24, relatively, of the exact one
+uint32_t center_normalize_f16_sum_depth(uint32_t dim);
 hipError_t launch_col_mean(const float *m, uint32_t k, uint32_t dim, float *mu, hipStream_t s);
 hipError_t launch_normalize_f16(const float *rows, const float *rnorm, uint64_t n, uint32_t dim, uint32_t dim_p, void *out, hipStream_t s);
 hipError_t launch_normalize_i8(const float *rows, const float *rnorm, uint64_t n, uint32_t dim, uint32_t dim_p, void *out, void *sr, float *nrm,

@@ -838,6 +838,11 @@ hipError_t launch_center_normalize_f16(const float *rows, const float *mu, uint6
                        static_cast<uint16_t *>(out), fixed_scale, idx);
     return hipGetLastError();
 }
+// (follows center_normalize_f16_kernel's two summation loops: change them together)
+uint32_t center_normalize_f16_sum_depth(uint32_t dim) {
+    const uint32_t per_lane = ((dim & 7u) == 0 && dim <= 2048) ? 8u * ((dim / 8u + 63u) / 64u) : (dim + 63u) / 64u;
+    return per_lane + 6u;
+}
 // mu[d] = mean over the k rows of m[., d]: one block per 64 columns, SIXTEEN row slices per column (four loads in flight each)
 // reduced through LDS.  (mu only centres the f16 images of the assignment -- the bounds hold for any mu --, so the order of this
 // sum is free; with four slices of 256 dependent loads it was 80 us of every Lloyd iteration.)
