@@ -559,6 +559,34 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// A posting list per key value of an integer column over this searcher's rows (`include/pqv.h`: `pqv_key_partition`).
+    pub fn key_partition(&self, column: &Column) -> Result<KeyPartition> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_key_partition_create(self.raw, column.raw, ptr::null_mut(), &mut raw) })?;
+        Ok(KeyPartition { raw })
+    }
+
+    /// The exact top-k over the rows of `part` whose key passes the query's filter -- nothing is probed (`include/pqv.h`:
+    /// `pqv_topk_partition`).  Sets are sorted and de-duplicated here, as for [`Searcher::topk_filtered`].
+    pub fn topk_partition(&self, part: &KeyPartition, filter: &KeyFilter, mask: Option<&RowMask>, queries: &[f32], dim: usize,
+                          k: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        // (the arrays the descriptor points at live until the call has returned)
+        let (desc, _lims, _vals) = key_filter_desc(filter, nq)?;
+        let k = k.get();
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_partition(self.raw, part.raw, &desc, mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(),
+                                    nq as u32, dim as u32, k as u32, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(), dist.as_mut_ptr(),
+                                    found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
     /// Keep probing until `k` rows pass the filter (`include/pqv.h`: `pqv_topk_expand`): every query probes the fewest lists, at
     /// least `nprobe` and at most `max_nprobe`, whose passing rows number `k`, and gets what [`Searcher::topk_masked`] (`filter`
     /// `None`: `mask` is required) or [`Searcher::topk_filtered`] returns for that many lists.  Returns the hits and the lists
@@ -933,6 +961,37 @@ impl RowKeys {
     pub fn rows(&self) -> u64 { unsafe { sys::pqv_row_keys_rows(self.raw) } }
     /// `PQV_COL_I32` or `PQV_COL_I64`
     pub fn dtype(&self) -> i32 { unsafe { sys::pqv_row_keys_dtype(self.raw) } }
+}
+
+/// A posting list per key value over one searcher's rows ([`Searcher::key_partition`]): what [`Searcher::topk_partition`] answers
+/// from.  Immutable, usable from any thread, and safe to drop before or after its searcher.
+pub struct KeyPartition {
+    raw: *mut sys::PqvKeyPartition,
+}
+unsafe impl Send for KeyPartition {}
+unsafe impl Sync for KeyPartition {}
+
+impl KeyPartition {
+    /// indexed rows with a valid key
+    pub fn rows(&self) -> u64 { unsafe { sys::pqv_key_partition_rows(self.raw) } }
+    /// distinct key values among them
+    pub fn n_keys(&self) -> u64 { unsafe { sys::pqv_key_partition_n_keys(self.raw) } }
+    /// `PQV_COL_I32` or `PQV_COL_I64`
+    pub fn dtype(&self) -> i32 { unsafe { sys::pqv_key_partition_dtype(self.raw) } }
+    /// the distinct key values ascending and their row counts
+    pub fn keys(&self) -> Result<(Vec<i64>, Vec<u64>)> {
+        let n = self.n_keys();
+        let mut keys = vec![0i64; n as usize];
+        let mut counts = vec![0u64; n as usize];
+        check(unsafe { sys::pqv_key_partition_keys(self.raw, keys.as_mut_ptr(), counts.as_mut_ptr(), n) })?;
+        Ok((keys, counts))
+    }
+}
+
+impl Drop for KeyPartition {
+    fn drop(&mut self) {
+        unsafe { sys::pqv_key_partition_free(self.raw) }
+    }
 }
 
 /// One filter per query of a [`Searcher::topk_filtered`] call, compared in i64 against the key column (`include/pqv.h`:

@@ -388,6 +388,8 @@ int pqv_round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max
  *   "pf96"          f16 96-query form on rows of <= 128 dims: all of the next tile's operands are requested behind the current tile's
  *                   MFMAs (1 = for lists of <= 2048 rows on average (default), 2 always, 0 never)
  *   "drain_min"     queued survivors that start a batch of exact evaluations before a wave's last tile (0 = 64)
+ *   "partition_blocks" pqv_topk_partition: blocks per query of partition_stream_kernel (0 = by rule, from nq, k and the partition's
+ *                   rows; at most 4096)
  * The same names, upper-cased with a PQV_ prefix, are read from the environment ONCE when a searcher is created
  * (profiling scripts). */
 int pqv_searcher_set_option(pqv_searcher *searcher, const char *name, int64_t value);
@@ -724,6 +726,71 @@ int pqv_topk_expand_device(const pqv_searcher *searcher, const pqv_row_keys *key
                            const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                            uint32_t max_nprobe, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found,
                            void *d_n_candidates, void *d_nprobe_used, void *d_tie_flags, void *hip_stream);
+
+/* Key partitions: exact per-key top-k over a key's own rows.  The keyed, filtered and expanding calls above answer a per-query
+ * filter THROUGH the IVF lists: approximate (only the probed lists are seen), at a cost that follows the probed lists' length.  For
+ * many small tenants that is the wrong end of the trade.  A key partition is a second set of lists over the same rows, keyed by the
+ * filter column instead of the centroids: a posting list per key value.  Nothing is probed, and the cost follows the rows that pass.
+ *
+ * A pqv_key_partition is made for ONE plain searcher from an integer pqv_column (PQV_COL_I32 / PQV_COL_I64, optional validity), as a
+ * pqv_row_keys is.  It holds, all on the device: the searcher's list positions whose row has a valid (non-NULL) key, sorted by (key
+ * as i64 ascending, row id ascending) -- an I32 column is widened, never truncated --, the distinct values ascending and the offsets
+ * of each value's run.  Rows in no list (those pqv_index_remove took out) are not in it, as masks ignore them.  Positions are stored,
+ * so one partition serves both layouts, a released row-order copy and the cosine layout.  pqv_key_partition_create runs on hip_stream
+ * (NULL: the searcher's) and is complete on return; nothing of size O(n_rows) crosses PCIe; the result is immutable, usable from any
+ * thread, and may be freed before or after its searcher.  _rows: m, the indexed rows with a valid key; _n_keys: the distinct values
+ * among them; _keys: a host download for planners and tests, the first min(n, n_keys) distinct values ascending and their row counts
+ * (either array may be NULL).
+ * Errors of _create, in this order, NULL checks before any device use: pqv_row_keys_create's texts ("out must not be NULL", "searcher
+ * must not be NULL", "column must not be NULL", "key column must be PQV_COL_I32 or PQV_COL_I64", "column has N rows, the corpus has
+ * M", "column is on device D, the searcher on device E"); PQV_ERR_UNSUPPORTED "pqv_key_partition_create does not take table
+ * searchers" (behind the NULL checks).
+ *
+ * pqv_topk_partition / pqv_topk_partition_device: no nprobe and no max_candidates.  F_q is the test of `filter` for query q
+ * (PQV_KEY_EQ, PQV_KEY_RANGE, PQV_KEY_IN), read exactly as pqv_topk_filtered* reads it: host arrays in the host form; in the device
+ * form device arrays read on hip_stream inside the enqueued work.
+ *   candidates   query q's sequence is every partition row r with F_q(key[r]), ordered by (key[r], r): ONE contiguous span of the
+ *                partition for EQ and RANGE, up to PQV_KEY_SET_MAX spans in the slice's ascending order for IN.  A candidate's
+ *                position is its index in that sequence; n_candidates[q] is the sequence's length, taken before the mask.
+ *   considered   the candidates the optional shared `mask` allows (NULL: all), at their unmasked positions; a row the mask excludes
+ *                is never loaded.
+ *   result       the k considered rows with the smallest (distance key, position), ascending.  The distance is bit for bit that of
+ *                the metric's chain: PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE (through the cosine layout, with the halving) and
+ *                PQV_DOT (ord() keys, dist = 0.0f - s(q, x)); sqrt_out as in pqv_topk.  There is no reference heap to replay and
+ *                there are no tie flags: the host and the device form return the same thing.  Slots past n_found[q] hold
+ *                0xFFFFFFFF / +inf.  NaN follows the key's bit order, unpinned, as everywhere.
+ *   exactness    with mask == NULL the result is the exact top-k over ALL indexed rows whose key passes.  No searcher option
+ *                changes a result (partition_blocks fixes the blocks per query, 0 = by rule).
+ *   equivalence  let S1 be a searcher over pqv_index_from_parts(dim, 1, any centroid, one list = all indexed rows ascending) on the
+ *                same corpus.  For PQV_KEY_EQ the call returns rows, distances and n_found bit for bit equal to
+ *                pqv_topk_filtered_device on S1 with nprobe = 1 and max_candidates = 0; for RANGE and IN the same holds whenever no two
+ *                considered rows of DIFFERENT keys tie in distance at or inside the k-th place; for PQV_DOT (which the keyed calls
+ *                refuse) the twin is pqv_topk_masked_device on S1, per query under the mask M_q.
+ *   counts       queries advances by nq, candidate_rows by the sum of n_candidates, embeddings_fetched by the considered rows;
+ *                screened_pairs and screen_survivors do not move.
+ *   limits       k <= 1024 in both forms (PQV_ERR_UNSUPPORTED "pqv_topk_partition takes k <= 1024"): there is no host fallback.
+ *                n_found, n_candidates and their device forms may be NULL.  The device form is asynchronous on hip_stream with no
+ *                host synchronisation; for an unvalidated IN slice that query's result is unspecified and every access is in
+ *                bounds, as pqv_topk_filtered_device documents.
+ *   out of scope table searchers; range search, distinct and grouped over a partition; k > 1024; mutable partitions (after an
+ *                append or a remove, make the new searcher's partition); the screened kernels on long runs; choosing between the
+ *                IVF and the partition path automatically (pqv_key_partition_keys gives a planner the run lengths for that choice).
+ * Errors, in this order (PQV_ERR_INVALID): "searcher must not be NULL", "key partition must not be NULL", "filter must not be
+ * NULL", the descriptor checks of pqv_topk_filtered (host form), "k must be > 0", "key partition belongs to another searcher", "row
+ * mask belongs to another searcher", then pqv_topk's own (query length, metric). */
+typedef struct pqv_key_partition pqv_key_partition;
+int      pqv_key_partition_create(const pqv_searcher *searcher, const pqv_column *column, void *hip_stream, pqv_key_partition **out);
+uint64_t pqv_key_partition_rows(const pqv_key_partition *part);
+uint64_t pqv_key_partition_n_keys(const pqv_key_partition *part);
+int      pqv_key_partition_dtype(const pqv_key_partition *part);
+int      pqv_key_partition_keys(const pqv_key_partition *part, int64_t *keys, uint64_t *counts, uint64_t n);
+void     pqv_key_partition_free(pqv_key_partition *part);
+int pqv_topk_partition(const pqv_searcher *searcher, const pqv_key_partition *part, const pqv_key_filter *filter,
+                       const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, int metric,
+                       int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_partition_device(const pqv_searcher *searcher, const pqv_key_partition *part, const pqv_key_filter *filter,
+                              const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
+                              void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates, void *hip_stream);
 
 /* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
  * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.

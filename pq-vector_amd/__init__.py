@@ -32,7 +32,7 @@ Host-side mirror of the reference's Rust API over the C ABI of include/pqv.h:
 (src/ivf/parquet.rs:23-103, src/ivf/search.rs:41-81).  All compute runs in the HIP kernels
 behind libpqv_hip.so; importing this package without the built library fails loudly.
 """
-from .api import (CandidateCursor, Column, Corpus, DistinctSearchResult, GroupSearchResult, TableDistinctSearchResult, Index, IndexBuilder, PqvError, RangeBuilder, RowKeys, RowMask, Searcher, SearchResult, TopkBuilder,
+from .api import (CandidateCursor, Column, Corpus, DistinctSearchResult, GroupSearchResult, TableDistinctSearchResult, Index, IndexBuilder, PqvError, RangeBuilder, KeyPartition, RowKeys, RowMask, Searcher, SearchResult, TopkBuilder,
                   TableRangeBuilder, TableSearcher, TableSearchResult, TableTopkBuilder, device_count, merge_topk, rerank_batch,
                   rerank_finish, round_robin_quota, searcher_for_parquet, searcher_for_parquet_files, split_table_rows)
 from .parquet_io import has_pq_vector_index, load_scalar_column, read_index_from_parquet, row_mask_from_expression
@@ -41,7 +41,7 @@ from ._ffi import (PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE, PQV_L2SQ_MFMA, PQV_D
                    PQV_RELEASE_ROW_ORDER, PQV_RELEASE_IF_COPIED, PQV_TABLE_CAP_ROUND_ROBIN, PQV_PREPARE_COSINE, PQV_KEY_EQ, PQV_KEY_RANGE, PQV_KEY_IN,
                    PQV_KEY_SET_MAX, LIB_PATH)
 
-__all__ = ["RowMask", "RowKeys", "DistinctSearchResult", "GroupSearchResult", "TableDistinctSearchResult", "Column", "col", "allowed", "load_scalar_column", "row_mask_from_expression", "CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
+__all__ = ["RowMask", "RowKeys", "KeyPartition", "DistinctSearchResult", "GroupSearchResult", "TableDistinctSearchResult", "Column", "col", "allowed", "load_scalar_column", "row_mask_from_expression", "CandidateCursor", "Corpus", "Index", "IndexBuilder", "PqvError", "RangeBuilder", "Searcher", "SearchResult",
            "TopkBuilder", "TableRangeBuilder", "TableSearcher", "TableSearchResult", "TableTopkBuilder", "searcher_for_parquet_files",
            "split_table_rows", "device_count", "merge_topk", "rerank_batch", "rerank_finish", "searcher_for_parquet", "PQV_COSINE", "PQV_L2SQ_MFMA", "PQV_DOT",
            "has_pq_vector_index", "read_index_from_parquet", "PQV_L2SQ_REF4",

@@ -183,6 +183,16 @@ SIGNATURES = {
                                   C.c_int, C.c_int, u32p, f32p, u32p, u64p, u32p]),
     "pqv_topk_expand_device": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                          C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "pqv_key_partition_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
+    "pqv_key_partition_rows": (C.c_uint64, [vp]),
+    "pqv_key_partition_n_keys": (C.c_uint64, [vp]),
+    "pqv_key_partition_dtype": (C.c_int, [vp]),
+    "pqv_key_partition_keys": (C.c_int, [vp, i64p, u64p, C.c_uint64]),
+    "pqv_key_partition_free": (None, [vp]),
+    "pqv_topk_partition": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                     u32p, f32p, u32p, u64p]),
+    "pqv_topk_partition_device": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                            vp, vp, vp, vp, vp]),
     "pqv_range_search_filtered": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64,
                                             C.c_uint64, C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_topk_distinct": (C.c_int, [vp, vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,

@@ -812,6 +812,89 @@ def _group_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq,
     return _expand_filter(_key_filter(filter_keys, query_keys, query_key_ranges, query_key_sets, nq, device=device), device=device)
 
 
+class KeyPartition:
+    """A posting list per key value over one searcher's rows (pqv.h: pqv_key_partition): made by Searcher.key_partition, passed to
+    that searcher's topk_partition / topk_partition_device -- the exact top-k over a key's own rows, nothing probed.  Immutable;
+    close() releases it."""
+
+    def __init__(self, handle, searcher):
+        self._h = handle
+        self._searcher = searcher
+
+    @property
+    def rows(self):
+        """indexed rows with a valid key"""
+        return int(_ffi.lib().pqv_key_partition_rows(self._h)) if self._h else 0
+
+    @property
+    def n_keys(self):
+        """distinct key values among them"""
+        return int(_ffi.lib().pqv_key_partition_n_keys(self._h)) if self._h else 0
+
+    @property
+    def dtype(self):
+        """PQV_COL_I32 or PQV_COL_I64"""
+        return int(_ffi.lib().pqv_key_partition_dtype(self._h)) if self._h else -1
+
+    def keys(self, n=None):
+        """(values int64, counts uint64): the first min(n, n_keys) distinct key values ascending and their row counts."""
+        if self._h is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "key partition must not be NULL")
+        n = self.n_keys if n is None else min(int(n), self.n_keys)
+        vals = np.zeros(n, dtype=np.int64)
+        counts = np.zeros(n, dtype=np.uint64)
+        _check(_ffi.lib().pqv_key_partition_keys(self._h, vals.ctypes.data_as(_ffi.i64p), counts.ctypes.data_as(u64p), n))
+        return vals, counts
+
+    def close(self):
+        if self._h:
+            _ffi.lib().pqv_key_partition_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _partition_filter(part, query_keys, query_key_ranges, query_key_sets, nq, device=False):
+    """A partition call's (partition handle, KeyFilter, what must stay alive): exactly one of the three query keywords, read as
+    _key_filter reads them (query_keys= travels as a PQV_KEY_EQ descriptor)."""
+    if not isinstance(part, KeyPartition):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"part must be a KeyPartition, got {type(part).__name__}")
+    if part._h is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "key partition must not be NULL")
+    given = [n for n, v in (("query_keys", query_keys), ("query_key_ranges", query_key_ranges), ("query_key_sets", query_key_sets))
+             if v is not None]
+    if not given:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "query keys must not be NULL")
+    if len(given) > 1:
+        raise PqvError(_ffi.PQV_ERR_INVALID, " and ".join(given) + " are mutually exclusive")
+    if query_keys is not None:
+        if device:
+            return part._h, _ffi.KeyFilter(_ffi.PQV_KEY_EQ, 0, int(query_keys) or None, None), ()
+        qk = _query_keys(query_keys, nq)
+        return part._h, _ffi.KeyFilter(_ffi.PQV_KEY_EQ, 0, qk.ctypes.data, None), (qk,)
+    if query_key_ranges is not None:
+        try:
+            lo, hi = query_key_ranges
+        except (TypeError, ValueError):
+            raise PqvError(_ffi.PQV_ERR_INVALID, "query_key_ranges must be a pair (lo, hi)") from None
+        if device:
+            return part._h, _ffi.KeyFilter(_ffi.PQV_KEY_RANGE, 0, int(lo) or None, int(hi) or None), ()
+        lo, hi = _query_keys(lo, nq), _query_keys(hi, nq)
+        return part._h, _ffi.KeyFilter(_ffi.PQV_KEY_RANGE, 0, lo.ctypes.data, hi.ctypes.data), (lo, hi)
+    if device:
+        try:
+            d_lims, d_vals = query_key_sets
+        except (TypeError, ValueError):
+            raise PqvError(_ffi.PQV_ERR_INVALID, "query_key_sets of a device call must be a pair (ptr_lims, ptr_vals)") from None
+        return part._h, _ffi.KeyFilter(_ffi.PQV_KEY_IN, 0, int(d_lims) or None, int(d_vals) or None), ()
+    lims, vals = key_sets_to_csr(query_key_sets, nq)
+    return part._h, _ffi.KeyFilter(_ffi.PQV_KEY_IN, 0, lims.ctypes.data, vals.ctypes.data), (lims, vals)
+
+
 def _allow_array(allowed, n_rows, what="row mask"):
     """A caller's allow array -> contiguous uint8 [n_rows]: bool or uint8, one entry per row; anything else is refused."""
     if allowed is None:
@@ -950,6 +1033,50 @@ class Searcher:
         h = vp()
         _check(_ffi.lib().pqv_row_keys_create(self._h, column._h, vp(stream or None), C.byref(h)))
         return RowKeys(h, self)
+
+    def key_partition(self, column, stream=0):
+        """KeyPartition of an integer column (a Column, or the name of an attached one): pqv.h: pqv_key_partition_create.  Built on
+        the device; the column may be closed afterwards.  Complete on return."""
+        if isinstance(column, str):
+            if column not in self._columns:
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"no column named {column!r} is attached to this searcher")
+            column = self._columns[column]
+        if not isinstance(column, Column) or column._h is None:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "column must not be NULL")
+        h = vp()
+        _check(_ffi.lib().pqv_key_partition_create(self._h, column._h, vp(stream or None), C.byref(h)))
+        return KeyPartition(h, self)
+
+    def topk_partition(self, queries, k, part, query_keys=None, query_key_ranges=None, query_key_sets=None, mask=None,
+                       metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """Exact top-k over the rows of `part` (a KeyPartition of this searcher) whose key passes the query's filter -- exactly one
+        of query_keys (int [nq]), query_key_ranges=(lo, hi) or query_key_sets, read as topk reads them -- within mask if one is
+        given; nothing is probed (pqv.h: pqv_topk_partition).  Returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq],
+        n_candidates [nq])."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        ph, f, _alive = _partition_filter(part, query_keys, query_key_ranges, query_key_sets, nq)
+        rows = np.full((nq, max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        nf = np.zeros(nq, dtype=np.uint32)
+        nc = np.zeros(nq, dtype=np.uint64)
+        _check(_ffi.lib().pqv_topk_partition(self._h, ph, C.byref(f), _mask_handle(self, mask) if mask is not None else None,
+                                             q.ctypes.data_as(f32p), nq, qlen, k, metric, 1 if sqrt_out else 0,
+                                             rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
+                                             nc.ctypes.data_as(u64p)))
+        return rows, dist, nf, nc
+
+    def topk_partition_device(self, d_queries, nq, k, part, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0, query_keys=None,
+                              query_key_ranges=None, query_key_sets=None, mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of topk_partition, shaped like topk_device: asynchronous on `stream`; the query keywords take device
+        pointers (int64 [nq]; (ptr_lo, ptr_hi); (ptr_lims, ptr_vals)) read on `stream` inside the enqueued work (pqv.h:
+        pqv_topk_partition_device)."""
+        ph, f, _alive = _partition_filter(part, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        _check(_ffi.lib().pqv_topk_partition_device(self._h, ph, C.byref(f), _mask_handle(self, mask) if mask is not None else None,
+                                                    vp(d_queries), nq, k, metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
+                                                    vp(d_n_found or None), vp(d_n_candidates or None), vp(stream or None)))
 
     def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None, keys=None,
              query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=None):

@@ -353,7 +353,8 @@ struct Scratch {
         // host form's group_rows block
         s_g1_rows, s_g1_dist, s_g1_keys, s_g1_nfound, s_gset_keys, s_gset_slot, s_gpart_slot, s_gpart_cnt, s_grows_out,
         s_expand_cnt, s_expand_used,    // pqv_topk_expand: the passing rows per probed list u32 [nq][P]; nprobe_used u32 [nq] where the caller takes none
-        s_ps_q16, s_ps_qn2, s_ps_score; // screened probe: the batch's query images f16 [nq][dim_p], |q - mean|^2 [nq], the scores f32 [nq][kc_pad]
+        s_ps_q16, s_ps_qn2, s_ps_score, // screened probe: the batch's query images f16 [nq][dim_p], |q - mean|^2 [nq], the scores f32 [nq][kc_pad]
+        s_pt_beg, s_pt_end, s_pt_nspan; // pqv_topk_partition: the spans' first entries u32 [nq] (IN: [nq][1024]), IN: their prefix sums and counts
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -369,7 +370,7 @@ struct Scratch {
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
                 &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
                 &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out,
-                &s_expand_cnt, &s_expand_used, &s_ps_q16, &s_ps_qn2, &s_ps_score};
+                &s_expand_cnt, &s_expand_used, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_pt_beg, &s_pt_end, &s_pt_nspan};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -480,6 +481,7 @@ struct pqv_searcher {
         int wide_quads = 1;                // int8, 96-query quads: lists probed by 97..160 queries of the batch take ONE 160-query quad
                                            // (8-wave blocks on 32-row tiles) instead of two passes; 0 = off
         uint32_t wide_quad_rows = 0;       // rows per block of that instance (0 = by rule: 6144)
+        uint32_t partition_blocks = 0;     // pqv_topk_partition: blocks per query of partition_stream_kernel (0 = by rule; PQV_PARTITION_BLOCKS)
         int list_once = 0;                 // round 6: 1 = lists probed by more than 96 queries of the batch go to list_filter_kernel (rows stationary in
                                            // registers, ALL the list's pairs streamed past them: every such list is read once -- and measured SLOWER than
                                            // the wide-quad instance / regular quads sharing an L2: C3 2.18 against 1.87 ms of kernels, the mixture 3.7
@@ -728,19 +730,17 @@ static int row_filter(const pqv_searcher *s, const SearchRequest *mv, uint64_t q
     }
     return PQV_OK;
 }
-// A keyed or filtered host call's per-query arguments for the sub-batch [q0, q0 + b): uploaded on `st` into the lane's scratch,
-// `sub` pointed at them.  `lims` keeps an IN filter's rebased offsets alive until the sub-batch's synchronisation.
-static int upload_query_filter(Scratch &sc, const SearchRequest *rq, SearchRequest &sub, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
-                               hipStream_t st) {
-    if (!rq || !rq->filtered()) return PQV_OK;
-    if (rq->rows.kind == PQV_KEY_RANGE) {
+// The RANGE / IN arrays of a filter descriptor for the sub-batch [q0, q0 + b): uploaded on `st` into the lane's scratch, *d_a / *d_b
+// pointed at them.  `lims` keeps an IN filter's rebased offsets alive until the sub-batch's synchronisation.
+static int upload_filter_arrays(Scratch &sc, uint32_t kind, const void *h_a, const void *h_b, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
+                                hipStream_t st, const void **d_a, const void **d_b) {
+    if (kind == PQV_KEY_RANGE) {
         HIP_TRY(sc.s_qfilt_a.ensure(static_cast<size_t>(b) * sizeof(int64_t)));
         HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(b) * sizeof(int64_t)));
-        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, static_cast<const int64_t *>(rq->rows.h_a) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(rq->rows.h_b) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        sub.rows.d_a = sc.s_qfilt_a.p; sub.rows.d_b = sc.s_qfilt_b.p;
-    } else if (rq->rows.kind == PQV_KEY_IN) {
-        const uint64_t *hl = static_cast<const uint64_t *>(rq->rows.h_a);
+        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, static_cast<const int64_t *>(h_a) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(h_b) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    } else {
+        const uint64_t *hl = static_cast<const uint64_t *>(h_a);
         const uint64_t base = hl[q0], n_vals = hl[q0 + b] - base;
         try { lims.resize(static_cast<size_t>(b) + 1); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
         for (uint32_t i = 0; i <= b; ++i) lims[i] = hl[q0 + i] - base;
@@ -748,12 +748,19 @@ static int upload_query_filter(Scratch &sc, const SearchRequest *rq, SearchReque
         HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(n_vals) * sizeof(int64_t)));
         HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, lims.data(), (static_cast<size_t>(b) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         if (n_vals)
-            HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(rq->rows.h_b) + base, static_cast<size_t>(n_vals) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        sub.rows.d_a = sc.s_qfilt_a.p; sub.rows.d_b = sc.s_qfilt_b.p;
-    } else {
-        HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, rq->rows.h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        sub.rows.d_qkeys = sc.s_qkeys.as<int64_t>();
+            HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(h_b) + base, static_cast<size_t>(n_vals) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     }
+    *d_a = sc.s_qfilt_a.p; *d_b = sc.s_qfilt_b.p;
+    return PQV_OK;
+}
+// A keyed or filtered host call's per-query arguments for the sub-batch [q0, q0 + b): uploaded on `st` into the lane's scratch,
+// `sub` pointed at them.
+static int upload_query_filter(Scratch &sc, const SearchRequest *rq, SearchRequest &sub, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
+                               hipStream_t st) {
+    if (!rq || !rq->filtered()) return PQV_OK;
+    if (rq->rows.kind) return upload_filter_arrays(sc, rq->rows.kind, rq->rows.h_a, rq->rows.h_b, q0, b, lims, st, &sub.rows.d_a, &sub.rows.d_b);
+    HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, rq->rows.h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    sub.rows.d_qkeys = sc.s_qkeys.as<int64_t>();
     return PQV_OK;
 }
 // the per-query filter of a distinct / grouped call that has one (mv->filtered() beside mv->distinct()), as its kernels read it
@@ -3327,6 +3334,7 @@ void opts_from_env(pqv_searcher::Opts &o) {
     o.xcd_items = static_cast<int>(num("PQV_XCD_ITEMS", o.xcd_items));
     o.wide_quad_rows = static_cast<uint32_t>(num("PQV_WIDE_QUAD_ROWS", o.wide_quad_rows));
     o.list_once = static_cast<int>(num("PQV_LIST_ONCE", o.list_once));
+    o.partition_blocks = static_cast<uint32_t>(std::max<long long>(0, num("PQV_PARTITION_BLOCKS", o.partition_blocks)));
     o.pair_prune = static_cast<int>(num("PQV_PAIR_PRUNE", o.pair_prune));
     o.i8_form = static_cast<int>(num("PQV_I8_FORM", o.i8_form));
 }
@@ -6118,6 +6126,311 @@ extern "C" int pqv_range_search_filtered(const pqv_searcher *s, const pqv_row_ke
     });
 }
 
+// ---- key partitions (pqv.h: pqv_key_partition) ----------------------------------------------------------------------------
+// The searcher's list positions with a valid key in (key as i64, row id) order, the distinct values and their runs' offsets
+// (kernels.h: launch_partition_*).  Positions index d_ids like a mask's image, so one partition serves every layout and the cosine
+// searcher.  Immutable; owner / owner_uid are compared, never read through.
+struct pqv_key_partition {
+    const pqv_searcher *owner = nullptr;
+    uint64_t owner_uid = 0;
+    int device = 0;
+    int dtype = 0;                     // PQV_COL_I32 / PQV_COL_I64
+    uint64_t m = 0, n_keys = 0;
+    DevBuf d_pos;                      // [m] u32
+    DevBuf d_keys;                     // [n_keys] i64, ascending
+    DevBuf d_off;                      // [n_keys + 1] u64
+};
+// Creation: the gather through d_ids, a sort by row (the positions without a key go behind the m that have one), the keys of those m,
+// a stable sort by key, the run boundaries.  Two 8-byte counts come back to the host: m between the sorts, n_keys at the end.
+static int key_partition_create_impl(const pqv_searcher *s, const pqv_column *c, void *hip_stream, pqv_key_partition **out) {
+    if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
+    *out = nullptr;
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!c) return fail(PQV_ERR_INVALID, "column must not be NULL");
+    if (s->n_files) return fail(PQV_ERR_UNSUPPORTED, "pqv_key_partition_create does not take table searchers");
+    if (c->dtype != PQV_COL_I32 && c->dtype != PQV_COL_I64) return fail(PQV_ERR_INVALID, "key column must be PQV_COL_I32 or PQV_COL_I64");
+    const uint64_t corpus_rows = s->corpus ? s->corpus->n : 0;
+    if (c->n != corpus_rows)
+        return fail(PQV_ERR_INVALID, "column has " + std::to_string(c->n) + " rows, the corpus has " + std::to_string(corpus_rows));
+    if (c->device != s->device)
+        return fail(PQV_ERR_INVALID, "column is on device " + std::to_string(c->device) + ", the searcher on device " + std::to_string(s->device));
+    if (int rc = use_device(s->device)) return rc;
+    std::unique_ptr<pqv_key_partition> kp(new (std::nothrow) pqv_key_partition());
+    if (!kp) return fail(PQV_ERR_OOM, "host allocation failed");
+    kp->owner = s; kp->owner_uid = s->uid; kp->device = s->device; kp->dtype = c->dtype;
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+    const uint64_t n = s->n;
+    size_t tmp_bytes = 0;
+    HIP_TRY(pqv::launch_partition_tmp_bytes(n, &tmp_bytes));
+    DevBuf d_tmp, d_row[2], d_p[2], d_cnt;
+    HIP_TRY(d_tmp.alloc(tmp_bytes));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(d_row[i].alloc(n * sizeof(uint32_t)));
+        HIP_TRY(d_p[i].alloc(n * sizeof(uint32_t)));
+    }
+    HIP_TRY(d_cnt.alloc(2 * sizeof(unsigned long long)));         // {m, n_keys}
+    HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), stream));
+    HIP_TRY(pqv::launch_partition_gather(c->d_valid, corpus_rows, s->d_ids.as<uint32_t>(), n, d_row[0].as<uint32_t>(), d_p[0].as<uint32_t>(),
+                                         d_cnt.as<unsigned long long>(), stream));
+    HIP_TRY(pqv::launch_partition_sort_rows(d_row[0].as<uint32_t>(), d_p[0].as<uint32_t>(), d_row[1].as<uint32_t>(), d_p[1].as<uint32_t>(), n,
+                                            d_tmp.p, tmp_bytes, stream));
+    unsigned long long h_cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&h_cnt[0], d_cnt.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint64_t m = h_cnt[0];
+    if (m > n) return fail(PQV_ERR_HIP, "key partition build: more keyed positions than positions");
+    kp->m = m;
+    HIP_TRY(kp->d_pos.alloc(m * sizeof(uint32_t)));
+    if (m) {
+        DevBuf d_key[2], d_vals, d_run, d_off;
+        for (int i = 0; i < 2; ++i) HIP_TRY(d_key[i].alloc(m * sizeof(int64_t)));
+        HIP_TRY(d_vals.alloc(m * sizeof(int64_t)));
+        HIP_TRY(d_run.alloc(m * sizeof(uint64_t)));
+        HIP_TRY(d_off.alloc((m + 1) * sizeof(uint64_t)));
+        HIP_TRY(pqv::launch_partition_keys(c->d_values, static_cast<uint32_t>(column_value_size(c->dtype)), d_row[1].as<uint32_t>(), m,
+                                           d_key[0].as<int64_t>(), stream));
+        HIP_TRY(pqv::launch_partition_sort_keys(d_key[0].as<int64_t>(), d_p[1].as<uint32_t>(), d_key[1].as<int64_t>(), kp->d_pos.as<uint32_t>(), m,
+                                                d_tmp.p, tmp_bytes, stream));
+        HIP_TRY(hipMemsetAsync(d_run.p, 0, m * sizeof(uint64_t), stream));
+        HIP_TRY(pqv::launch_partition_runs(d_key[1].as<int64_t>(), m, d_vals.as<int64_t>(), d_run.as<uint64_t>(), d_off.as<uint64_t>(),
+                                           d_cnt.as<unsigned long long>() + 1, d_tmp.p, tmp_bytes, stream));
+        HIP_TRY(hipMemcpyAsync(&h_cnt[1], d_cnt.as<unsigned long long>() + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t nk = h_cnt[1];
+        if (nk == 0 || nk > m) return fail(PQV_ERR_HIP, "key partition build: run count out of range");
+        kp->n_keys = nk;
+        HIP_TRY(kp->d_keys.alloc(nk * sizeof(int64_t)));
+        HIP_TRY(kp->d_off.alloc((nk + 1) * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpyAsync(kp->d_keys.p, d_vals.p, nk * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(kp->d_off.p, d_off.p, (nk + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));      // (the scratch is released at scope exit)
+    } else {
+        HIP_TRY(kp->d_keys.alloc(0));
+        HIP_TRY(kp->d_off.alloc(sizeof(uint64_t)));
+        HIP_TRY(hipMemsetAsync(kp->d_off.p, 0, sizeof(uint64_t), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    *out = kp.release();
+    return PQV_OK;
+}
+extern "C" int pqv_key_partition_create(const pqv_searcher *s, const pqv_column *column, void *hip_stream, pqv_key_partition **out) {
+    return guard([&] { return key_partition_create_impl(s, column, hip_stream, out); });
+}
+extern "C" uint64_t pqv_key_partition_rows(const pqv_key_partition *p) { return p ? p->m : 0; }
+extern "C" uint64_t pqv_key_partition_n_keys(const pqv_key_partition *p) { return p ? p->n_keys : 0; }
+extern "C" int pqv_key_partition_dtype(const pqv_key_partition *p) { return p ? p->dtype : -1; }
+static int key_partition_keys_impl(const pqv_key_partition *p, int64_t *keys, uint64_t *counts, uint64_t n) {
+    if (!p) return fail(PQV_ERR_INVALID, "key partition must not be NULL");
+    n = std::min<uint64_t>(n, p->n_keys);
+    if (n == 0 || (!keys && !counts)) return PQV_OK;
+    if (int rc = use_device(p->device)) return rc;
+    if (keys) HIP_TRY(hipMemcpy(keys, p->d_keys.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (counts) {
+        std::vector<uint64_t> off;
+        try { off.resize(n + 1); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
+        HIP_TRY(hipMemcpy(off.data(), p->d_off.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; ++i) counts[i] = off[i + 1] - off[i];
+    }
+    return PQV_OK;
+}
+extern "C" int pqv_key_partition_keys(const pqv_key_partition *p, int64_t *keys, uint64_t *counts, uint64_t n) {
+    return guard([&] { return key_partition_keys_impl(p, keys, counts, n); });
+}
+extern "C" void pqv_key_partition_free(pqv_key_partition *p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    delete p;
+}
+
+// The checks of both forms, in the contract's order; nothing is dereferenced before the NULL checks.  query_len: the host form's.
+static int partition_checks(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask, uint32_t nq,
+                            uint32_t k, int metric, bool host, uint32_t query_len) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!part) return fail(PQV_ERR_INVALID, "key partition must not be NULL");
+    if (int rc = filter_descriptor_checks(f, nq, host)) return rc;
+    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (part->owner != s || part->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "key partition belongs to another searcher");
+    if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+    if (int rc = validate_topk(s, k, 1, metric)) return rc;
+    if (host && query_len != s->dim)
+        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) + ", got " + std::to_string(query_len));
+    if (k > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_partition takes k <= 1024");
+    return PQV_OK;
+}
+// blocks per query of partition_stream_kernel: the grid cannot follow span lengths only the device knows, so it comes from the batch
+// (about 2048 blocks fill the chip), the partition (a block's turn covers 256 positions: no more blocks than turns over ALL of it)
+// and k (the fold reads B * 4 * k entries per query)
+static uint32_t partition_blocks(const pqv_searcher *s, uint32_t nq, uint32_t k, uint64_t m) {
+    if (s->opt.partition_blocks) return s->opt.partition_blocks;
+    uint64_t b = (2048 + static_cast<uint64_t>(nq) - 1) / std::max<uint32_t>(1, nq);
+    b = std::min<uint64_t>(b, (m + 255) / 256);
+    b = std::min<uint64_t>(b, std::max<uint32_t>(1, 4096 / k));
+    return static_cast<uint32_t>(std::max<uint64_t>(1, b));
+}
+// Enqueue span -> stream -> fold for the queries [0, nq) on `stream`, in pieces of at most PARTITION_GRID_Q queries (the grid's y).
+// `s`: the searcher whose rows are read (the call's, or its cosine searcher); a / b: the descriptor's DEVICE arrays.
+constexpr uint32_t PARTITION_GRID_Q = 32768;
+static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
+                             const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
+                             uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+    using namespace pqv;
+    const uint32_t piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
+    const uint32_t B = partition_blocks(s, piece, k, part->m);
+    const uint32_t n_part = B * waves_per_block();
+    const size_t span_slots = static_cast<size_t>(piece) * (kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u);
+    HIP_TRY(sc.s_pt_beg.ensure(span_slots * sizeof(uint32_t)));
+    if (kind == PQV_KEY_IN) {
+        HIP_TRY(sc.s_pt_end.ensure(span_slots * sizeof(uint32_t)));
+        HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+    }
+    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(piece) * n_part * k + 4) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(piece) * n_part * k + 4) * sizeof(uint32_t)));
+    if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
+    for (uint32_t q0 = 0; q0 < nq; q0 += piece) {
+        const uint32_t b = std::min<uint32_t>(piece, nq - q0);
+        const float *dq = d_queries + static_cast<size_t>(q0) * s->dim;
+        if (s->sdim != s->dim) {      // (the stored rows are zero-padded: the queries that meet them too)
+            HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), stream));
+            dq = sc.s_qpad.as<float>();
+        }
+        PartitionSpanArgs sp{};
+        sp.keys = part->d_keys.as<int64_t>(); sp.key_off = part->d_off.as<uint64_t>(); sp.n_keys = part->n_keys;
+        sp.nq = b; sp.kind = kind;
+        // (every kind's a is indexed by query -- an IN filter's lims hold offsets into ALL of b, so a piece takes a + q0 and b as it is)
+        sp.a = static_cast<const char *>(d_a) + static_cast<size_t>(q0) * 8;
+        sp.b = kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + static_cast<size_t>(q0) * 8) : d_b;
+        sp.span_beg = sc.s_pt_beg.as<uint32_t>(); sp.span_end = sc.s_pt_end.as<uint32_t>(); sp.n_span = sc.s_pt_nspan.as<uint32_t>();
+        sp.n_cand = sc.s_ncand.as<uint64_t>(); sp.n_cand_out = d_n_cand ? d_n_cand + q0 : nullptr;
+        sp.stats = s->d_stats.as<unsigned long long>();
+        HIP_TRY(launch_partition_span(sp, stream));
+
+        StreamArgs ra{};
+        ra.mat = s->d_mat; ra.row_of = s->d_row_of;
+        ra.queries = dq; ra.nq = b; ra.nprobe = 1; ra.dim = s->sdim; ra.k = k;
+        ra.rows_per_block = 256; ra.blocks_per_list = B; ra.max_pos = ~0ull; ra.metric = metric;
+        ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
+        PartitionArgs pa{};
+        pa.pos = part->d_pos.as<uint32_t>(); pa.span_beg = sp.span_beg; pa.span_end = sp.span_end; pa.n_span = sp.n_span;
+        pa.n_cand = sp.n_cand; pa.kind = kind; pa.bits = bits; pa.stats = s->d_stats.as<unsigned long long>();
+        HIP_TRY(launch_partition_stream(ra, pa, stream));
+
+        MergeArgs fm{};
+        fm.part_keys = ra.part_keys; fm.part_vals = ra.part_vals;
+        fm.nq = b; fm.n_part = n_part; fm.k_part = k; fm.k = k;
+        fm.ids = s->d_final_ids; fm.row_idx = d_row_idx + static_cast<size_t>(q0) * k; fm.dist = d_dist + static_cast<size_t>(q0) * k;
+        fm.n_found = d_n_found ? d_n_found + q0 : nullptr;
+        fm.sqrt_out = sqrt_out; fm.k_out = k;
+        if (metric == PQV_DOT) HIP_TRY(launch_dot_merge(fm, stream));
+        else HIP_TRY(launch_merge_final(fm, stream));
+        s->counters.kernel_launches += 3;
+    }
+    s->counters.queries += nq;
+    return PQV_OK;
+}
+// the device form behind its checks; PQV_COSINE: n(q) into this searcher's lane, then the L2 body on the cosine searcher (sqrt_out 2)
+static int topk_partition_device_impl(const pqv_searcher *s, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
+                                      const pqv_row_mask *mask, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
+                                      uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+    std::lock_guard<std::mutex> lock(s->mu);
+    Scratch *lane = nullptr;
+    if (metric == PQV_COSINE) {
+        if (int rc = ensure_cosine(s)) return rc;
+        if (int rc = lane_acquire(s, stream, &lane)) return rc;
+        LaneGuard lane_guard{*lane, stream};
+        HIP_TRY(lane->s_qcos.ensure(static_cast<size_t>(nq) * s->dim * sizeof(float)));
+        HIP_TRY(pqv::launch_normalize_rows(d_queries, s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), stream));
+        const pqv_searcher *cs = s->cos.get();
+        std::lock_guard<std::mutex> cos_lock(cs->mu);
+        Scratch *cl = nullptr;
+        if (int rc = lane_acquire(cs, stream, &cl)) return rc;
+        LaneGuard cos_guard{*cl, stream};
+        if (int rc = enqueue_partition(cs, *cl, part, kind, d_a, d_b, bits, lane->s_qcos.as<float>(), nq, k, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
+                                       d_n_found, d_n_cand, stream))
+            return rc;
+        if (int rc = lane_release(*cl, stream)) return rc;
+        return lane_release(*lane, stream);
+    }
+    if (int rc = lane_acquire(s, stream, &lane)) return rc;
+    LaneGuard lane_guard{*lane, stream};
+    if (int rc = enqueue_partition(s, *lane, part, kind, d_a, d_b, bits, d_queries, nq, k, metric, sqrt_out, d_row_idx, d_dist, d_n_found, d_n_cand,
+                                   stream))
+        return rc;
+    return lane_release(*lane, stream);
+}
+extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
+                                         const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
+                                         void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        if (int rc = partition_checks(s, part, filter, mask, nq, k, metric, false, 0)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+        return topk_partition_device_impl(s, part, filter->kind, filter->a, filter->b, mask, static_cast<const float *>(d_queries), nq, k, metric,
+                                          sqrt_out ? 1 : 0, static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist),
+                                          static_cast<uint32_t *>(d_n_found), static_cast<uint64_t *>(d_n_candidates), stream);
+    });
+}
+// The host form: sub-batches of queries through the lane (their filter slices uploaded as pqv_topk_filtered uploads them), the
+// device body, and the results back.
+static int topk_partition_host_impl(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask,
+                                    const float *queries, uint32_t nq, uint32_t k, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
+                                    uint32_t *n_found, uint64_t *n_candidates) {
+    if (metric == PQV_COSINE) {
+        std::vector<float> nq_host;
+        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
+        return topk_partition_host_impl(s->cos.get(), part, f, mask, nq_host.data(), nq, k, PQV_L2SQ_REF4, 2, row_idx, dist, n_found, n_candidates);
+    }
+    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+    std::lock_guard<std::mutex> lock(s->mu);
+    Scratch *lane = nullptr;
+    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
+    Scratch &sc = *lane;
+    LaneGuard lane_guard{sc, s->stream};
+    // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
+    const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), k, part->m);
+    const uint64_t per_query = static_cast<uint64_t>(B) * 4 * k * 12 + static_cast<uint64_t>(s->sdim) * 8 + 12ull * k + 8 * PQV_KEY_SET_MAX;
+    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
+    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
+    HIP_TRY(sc.s_rows.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
+    HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(batch) * k * sizeof(float)));
+    HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_out.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
+    std::vector<uint64_t> sub_lims;
+    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
+        const uint32_t b = std::min<uint32_t>(batch, nq - q0);
+        const void *d_a = sc.s_qkeys.p, *d_b = nullptr;
+        if (f->kind == PQV_KEY_EQ)
+            HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, static_cast<const int64_t *>(f->a) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+        else if (int rc = upload_filter_arrays(sc, f->kind, f->a, f->b, q0, b, sub_lims, s->stream, &d_a, &d_b)) return rc;
+        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
+                               hipMemcpyHostToDevice, s->stream));
+        if (int rc = enqueue_partition(s, sc, part, f->kind, d_a, d_b, bits, sc.s_queries.as<float>(), b, k, metric, sqrt_out, sc.s_rows.as<uint32_t>(),
+                                       sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(), s->stream))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(row_idx + static_cast<uint64_t>(q0) * k, sc.s_rows.p, static_cast<size_t>(b) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(dist + static_cast<uint64_t>(q0) * k, sc.s_dist.p, static_cast<size_t>(b) * k * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        if (n_candidates) HIP_TRY(hipMemcpyAsync(n_candidates + q0, sc.s_out.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    return lane_release(sc, s->stream);
+}
+extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter, const pqv_row_mask *mask,
+                                  const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, int metric, int sqrt_out,
+                                  uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        if (int rc = partition_checks(s, part, filter, mask, nq, k, metric, true, query_len)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        return topk_partition_host_impl(s, part, filter, mask, queries, nq, k, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates);
+    });
+}
+
 // ---- distinct top-k (pqv.h: pqv_topk_distinct) -----------------------------------------------------------------------------
 // the checks both entry points make before anything else: NULL handles first, nothing dereferenced before them
 static int distinct_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, SearchRequest &mv) {
@@ -6546,6 +6859,7 @@ static int pqv_searcher_set_option_impl(pqv_searcher *s, const char *name, int64
     else if (n == "xcd_items") o.xcd_items = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(3, value)));
     else if (n == "wide_quad_rows") o.wide_quad_rows = static_cast<uint32_t>(std::max<int64_t>(0, value));
     else if (n == "list_once") o.list_once = static_cast<int>(value);
+    else if (n == "partition_blocks") o.partition_blocks = static_cast<uint32_t>(std::max<int64_t>(0, std::min<int64_t>(4096, value)));
     else if (n == "i8_form") {        // takes effect when the int8 copy is (re)built
         o.i8_form = static_cast<int>(std::min<int64_t>(2, std::max<int64_t>(0, value)));
         (void)hipSetDevice(s->device);

@@ -129,6 +129,64 @@ struct KeyFilterArgs : KeyedArgs {
 };
 hipError_t launch_key_filter_stream(const StreamArgs &a, const KeyFilterArgs &fa, StreamMode mode, hipStream_t s);
 
+// ---- key partitions (kernels_partition.hip; pqv.h: pqv_key_partition) -----------------------------------------------------
+// A key partition on the device: the searcher's list positions whose row has a valid key, sorted by (key as i64, row id) -- pos
+// [m] --, the distinct key values ascending -- keys [n_keys] -- and the first entry of every value's run -- key_off [n_keys + 1].
+// The build, in the order the host enqueues it (every step on `s`; `tmp` / tmp_bytes: launch_partition_tmp_bytes(n_pos) of scratch):
+//   launch_partition_gather    row_key[p] = the row list position p reports where it has a valid key, 0xFFFFFFFF where it has none;
+//                              pos[p] = p; *count += the positions with a key (zeroed by the caller)
+//   launch_partition_sort_rows (row_key, pos) sorted by row: the m positions with a key come first, in row order
+//   launch_partition_keys      key[i] = the column's value of row_key[i], widened, i < m
+//   launch_partition_sort_keys (key, pos) sorted STABLY by key as a signed 64-bit value: the (key, row) order
+//   launch_partition_runs      the distinct values, each value's run length and *n_keys; then key_off = the lengths' prefix sums
+// The two sorts, the run-length pass and the scan are rocPRIM's (header-only, from the ROCm tree; stable LSD radix sorts).
+hipError_t launch_partition_tmp_bytes(uint64_t n_pos, size_t *bytes);
+hipError_t launch_partition_gather(const uint8_t *valid, uint64_t n_rows, const uint32_t *ids, uint64_t n_pos, uint32_t *row_key, uint32_t *pos,
+                                   unsigned long long *count, hipStream_t s);
+hipError_t launch_partition_sort_rows(const uint32_t *row_key, const uint32_t *pos, uint32_t *row_key_out, uint32_t *pos_out, uint64_t n_pos,
+                                      void *tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_partition_keys(const void *values, uint32_t elem_size, const uint32_t *row_key, uint64_t m, int64_t *key, hipStream_t s);
+hipError_t launch_partition_sort_keys(const int64_t *key, const uint32_t *pos, int64_t *key_out, uint32_t *pos_out, uint64_t m, void *tmp,
+                                      size_t tmp_bytes, hipStream_t s);
+// cnt: [m] u64 scratch (the run lengths); key_off[n_keys] = m is written too (key_off has m + 1 entries of room)
+hipError_t launch_partition_runs(const int64_t *key, uint64_t m, int64_t *keys, uint64_t *cnt, uint64_t *key_off, unsigned long long *n_keys,
+                                 void *tmp, size_t tmp_bytes, hipStream_t s);
+// partition_span_kernel: query q's candidate sequence as spans of the partition.  kind 0 (PQV_KEY_EQ, a = i64 [nq]) and 1
+// (PQV_KEY_RANGE, a / b = i64 [nq] inclusive bounds): ONE span, span_beg[q] its first entry.  kind 2 (PQV_KEY_IN, a = u64 lims [nq + 1],
+// b = i64 values, at most KEY_SET_MAX of a slice are read): a span per slice value, span_beg[q * KEY_SET_MAX + i] and the inclusive
+// prefix sums of the span lengths span_end[q * KEY_SET_MAX + i], n_span[q] = the values read.  n_cand[q] (and n_cand_out[q], where
+// given) = the sequence's length, saturated at 2^32 - 1 like the prefix sums (a sequence position is a u32); with stats, added to
+// candidate_rows.  An empty or inverted range, an absent key and a value no key of the column can take give an empty span.
+struct PartitionSpanArgs {
+    const int64_t      *keys;       // [n_keys] ascending
+    const uint64_t     *key_off;    // [n_keys + 1]
+    uint64_t            n_keys;
+    uint32_t            nq, kind;
+    const void         *a, *b;
+    uint32_t           *span_beg;   // [nq] / [nq * KEY_SET_MAX]
+    uint32_t           *span_end;   // kind 2: [nq * KEY_SET_MAX]
+    uint32_t           *n_span;     // kind 2: [nq]
+    uint64_t           *n_cand;     // [nq]
+    uint64_t           *n_cand_out; // optional [nq]
+    unsigned long long *stats;      // optional: the searcher's statistics block
+};
+hipError_t launch_partition_span(const PartitionSpanArgs &a, hipStream_t s);
+// partition_stream_kernel: launch_masked_stream's STREAM_TOPK pass over a query's candidate sequence instead of probed lists.  grid
+// (blocks_per_list = B, nq); wave w of block x takes the 64-position windows (turn * B + x) * 4 + w of its query's sequence, maps
+// each sequence position to its partition entry (one span: an add; kind 2: a search in span_end), loads the entry's list position
+// and -- with a mask -- keeps the positions whose image bit is set.  Keys are (distance key << 32) | sequence position, the L2 forms'
+// (l2_key) or PQV_DOT's (dot_key); the per-wave lists go out in StreamArgs' format with nprobe = 1.  a.probe / list_off / cand_base
+// are not read; a.nprobe must be 1.  Every wave adds the rows it evaluated to embeddings_fetched.
+struct PartitionArgs {
+    const uint32_t     *pos;        // [m] the partition's list positions
+    const uint32_t     *span_beg, *span_end, *n_span;       // launch_partition_span's outputs
+    const uint64_t     *n_cand;
+    uint32_t            kind;       // the span kernel's
+    const uint64_t     *bits;       // optional: a shared row mask's image (MaskedArgs::bits)
+    unsigned long long *stats;      // as MaskedArgs::stats
+};
+hipError_t launch_partition_stream(const StreamArgs &a, const PartitionArgs &pa, hipStream_t s);
+
 // ---- expanding filtered top-k (kernels_expand.hip; pqv.h: pqv_topk_expand) ------------------------------------------------
 // filter_count_kernel: cnt[q * P + j] = the positions of list probe[q * P + j] that pass the call's filter -- the set bits of
 // the windows masked_stream_kernel forms for the same `win` (0: the mask image `bits`; 1 / 2: key_pos == a[q], i32 / i64; 3 / 4:

@@ -19,18 +19,6 @@
 
 namespace pqv {
 
-namespace {
-
-__device__ __forceinline__ uint32_t dot_ord(float d) {
-    const uint32_t b = __float_as_uint(d);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float dot_unord(uint32_t o) {
-    return __uint_as_float((o >> 31) ? o ^ 0x80000000u : ~o);
-}
-
-}  // namespace
-
 // ------------------------------------------------------------------------------------
 // dot_stream_kernel
 //
@@ -62,7 +50,7 @@ __global__ __launch_bounds__(256) void dot_stream_kernel(const StreamArgs a, con
     // what a tile's rows become: lane `lane` holds row my_srow at candidate position pos
     auto emit = [&](float sum, bool valid, uint64_t pos, uint32_t my_srow) {
         const float dist = 0.0f - sum;
-        const uint64_t key = ((uint64_t)dot_ord(dist) << 32) | (uint64_t)(uint32_t)pos;
+        const uint64_t key = dot_key(sum, pos);
         if constexpr (MODE == STREAM_TOPK) tk.offer(valid ? key : KEY_EMPTY, my_srow, a.k, lane);
         else emit_range_hit(a, q, valid && dist <= a.radius, key, my_srow, lane);     // (a NaN distance never compares true)
     };

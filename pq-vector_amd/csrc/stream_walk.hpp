@@ -139,6 +139,16 @@ __device__ __forceinline__ float dot_tile(const StreamArgs &a, float *lds, const
 
 // a candidate's key: ascending keys = ascending (d2, candidate position)
 __device__ __forceinline__ uint64_t l2_key(float d2, uint64_t pos) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint64_t)(uint32_t)pos; }
+// PQV_DOT (kernels_dot.hip): distances are signed, so a key carries ord(dist), the order-preserving map of f32 bits to u32
+// (negative: all bits flipped; else: the sign bit set); dot_key: the key of the products chain `sum`, dist = 0.0f - sum
+__device__ __forceinline__ uint32_t dot_ord(float d) {
+    const uint32_t b = __float_as_uint(d);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float dot_unord(uint32_t o) {
+    return __uint_as_float((o >> 31) ? o ^ 0x80000000u : ~o);
+}
+__device__ __forceinline__ uint64_t dot_key(float sum, uint64_t pos) { return ((uint64_t)dot_ord(0.0f - sum) << 32) | (uint64_t)(uint32_t)pos; }
 
 // ------------------------------------------------------------------------------------
 // The walk range: block (row block x, probe rank j, query q), wave `wave` of 4.  The list of rank j (probe == nullptr, unclamped

@@ -323,6 +323,42 @@ private:
     std::unique_ptr<pqv_row_keys, Del> h_;
 };
 
+// A posting list per key value over one searcher's rows (pqv.h: pqv_key_partition): the exact top-k over a key's own rows, nothing
+// probed.  The column is read once; a partition may outlive its searcher or be released before it.
+class KeyPartition {
+public:
+    KeyPartition(const Searcher &s, const Column &column) {
+        pqv_key_partition *h = nullptr;
+        check(pqv_key_partition_create(s.get(), column.get(), nullptr, &h));
+        h_.reset(h);
+    }
+    const pqv_key_partition *get() const { return h_.get(); }
+    uint64_t rows() const { return pqv_key_partition_rows(h_.get()); }
+    uint64_t n_keys() const { return pqv_key_partition_n_keys(h_.get()); }
+    int dtype() const { return pqv_key_partition_dtype(h_.get()); }
+    // the distinct key values ascending and their row counts
+    void keys(std::vector<int64_t> &values, std::vector<uint64_t> &counts) const {
+        values.assign(n_keys(), 0);
+        counts.assign(n_keys(), 0);
+        check(pqv_key_partition_keys(h_.get(), values.data(), counts.data(), values.size()));
+    }
+    // exact top-k of nq = filter.queries() queries over the partition rows whose key passes the query's filter -- and, with `mask`,
+    // that the mask allows (pqv.h: pqv_topk_partition); found[q] results per query, k slots each
+    void topk(const Searcher &s, const KeyFilter &filter, const std::vector<float> &queries, uint32_t k, std::vector<uint32_t> &rows,
+              std::vector<float> &dist, std::vector<uint32_t> &found, const RowMask *mask = nullptr) const {
+        const uint32_t nq = filter.queries();
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, 0.0f);
+        found.assign(nq, 0);
+        const pqv_key_filter d = filter.descriptor();
+        check(pqv_topk_partition(s.get(), h_.get(), &d, mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, PQV_L2SQ_REF4, 1,
+                                 rows.data(), dist.data(), found.data(), nullptr));
+    }
+private:
+    struct Del { void operator()(pqv_key_partition *p) const { pqv_key_partition_free(p); } };
+    std::unique_ptr<pqv_key_partition, Del> h_;
+};
+
 class TopkBuilder {
 public:
     TopkBuilder(const Searcher &s, const std::vector<float> &query) : s_(s), query_(query) {}
