@@ -55,8 +55,11 @@ SHAPES = {
     "padded72": dict(dim=72, kc=24, n0=3000, n1=3800, n2=4200, integer=False, nprobe_f=2, max_nprobe=8, mid_f=0.025, seed=72),
     "int8_256": dict(dim=256, kc=8, n0=3072, n1=4096, n2=4608, integer=False, nprobe_f=1, max_nprobe=4, mid_f=0.012, seed=256),
     "ties": dict(dim=64, kc=16, n0=6144, n1=8192, n2=9216, integer=True, nprobe_f=2, max_nprobe=6, mid_f=0.008, seed=65),
+    # every depth the modes use (1, 2, 4 and max_nprobe) is <= kc / 4: the screened centroid probe is eligible in every call, the
+    # expanding ones included (tests/test_gpu_probe_screen_modes.py; not one of CASES)
+    "probe32": dict(dim=64, kc=32, n0=12288, n1=16384, n2=18432, integer=False, nprobe_f=2, max_nprobe=8, mid_f=0.004, seed=66),
 }
-CASES = list(SHAPES)
+CASES = ["screened", "exact30", "padded72", "int8_256", "ties"]          # what test_gpu_mutated_search.py / _table.py run
 N_MID, N_TINY, TINY_ROWS = 8, 4, 6
 MID0, TINY0 = 2, 2 + N_MID           # tenants 0, 1: common; 2 .. 9: mid; 10 .. 13: tiny
 

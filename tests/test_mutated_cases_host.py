@@ -14,7 +14,7 @@ EMPTY_STATES = ["removed", "chained", "compacted"]          # the states in whic
 FILTERED = {"mask": dict(mask="sparse"), "key equality": dict(filt="eq"), "key set": dict(filt="in"), "key range": dict(filt="range")}
 
 
-@pytest.fixture(scope="module", params=mc.CASES)
+@pytest.fixture(scope="module", params=mc.CASES + ["probe32"])
 def case(request, oracle):
     return mc.case(oracle, request.param)
 

@@ -8,6 +8,8 @@ import math
 import numpy as np
 import pytest
 
+import probe_screen_cases as psc
+
 F = np.float32
 U = 2.0 ** -24
 H = 2.0 ** -11
@@ -148,7 +150,9 @@ def _sets(dim, rng):
     yield "norms next to FLT_MAX", hq, np.concatenate([half, -half])
 
 
-@pytest.mark.parametrize("dim", [4, 36, 100, 768])
+# 772 .. 3072: rows beyond one 768-dim slab of probe_resolve_kernel; 2048 is the last dim of center_normalize_f16_kernel's register
+# path, 2052 (dim % 8 != 0) and 3072 take sum_depth's other branch
+@pytest.mark.parametrize("dim", [4, 36, 100, 768, 772, 1536, 2048, 2052, 3072])
 def test_bounds_enclose_the_reference_chain(dim):
     rng = np.random.default_rng(1000 + dim)
     for name, q, c in _sets(dim, rng):
@@ -190,3 +194,65 @@ def test_bounds_are_tight_on_uniform_data():
     d_ref = reference_chain(q, c)
     assert (an2[:, None] + bn2[None, :] <= 2.2 * d_ref).all()
     assert ((ub - lb) <= 6e-3 * d_ref).all(), float(((ub - lb) / d_ref).max())
+
+
+def contenders(queries, cent, n_probe):
+    """per query the centroids probe_resolve_kernel keeps: lb <= T, T the n_probe-th smallest upper bound (the f64 score)"""
+    an2, bn2, q16, c16, inv_cs = images(queries, cent)
+    k = constants(queries.shape[1], inv_cs)
+    s = (q16.astype(np.float64) @ c16.astype(np.float64).T).astype(F)
+    lb, ub = probe_bound(k, an2[:, None], bn2[None, :], s)
+    T = np.sort(ub, axis=1)[:, n_probe - 1]
+    return (lb <= T[:, None]).sum(axis=1)
+
+
+def test_sum_depth_takes_both_branches():
+    assert sum_depth(2048) == 8 * 4 + 6 and sum_depth(2052) == 33 + 6 and sum_depth(3072) == 48 + 6 and sum_depth(772) == 13 + 6
+    assert sum_depth(1536) == 8 * 3 + 6
+
+
+@pytest.mark.parametrize("kc", psc.ALL_EQUAL_KC)
+def test_all_equal_tables_leave_every_query_above_the_cap(kc):
+    """The premise of tests/test_gpu_probe_screen.py::test_screened_probe_all_equal_table: every centroid is a contender of every
+    query, more than PR_CAP of them."""
+    _, cent, queries = psc.all_equal(kc)
+    assert kc > psc.PR_CAP and (2 * kc <= 32 * 196) == (kc == 2304)          # parked / not parked (PR_R * PR_TW words of LDS)
+    for n_probe in (1, 7, kc // 4):
+        assert (contenders(queries, cent, n_probe) == kc).all(), n_probe
+
+
+def test_split_table_leaves_2040_contenders():
+    """The premise of test_screened_probe_2040_contenders: at nprobe 1 and 7 every query but FAR keeps exactly the 2040 copies --
+    below the cap, 64 rounds of 32 with a last round of 24 --, FAR keeps a handful; nobody goes all-exact."""
+    _, cent, queries = psc.split_2040()
+    assert len(cent) == 2304 and len(np.unique(cent, axis=0)) == psc.N_FAR + 1
+    near = np.arange(psc.NQ) != psc.FAR
+    for n_probe in (1, 7):
+        n = contenders(queries, cent, n_probe)
+        assert (n[near] == psc.N_COPIES).all() and psc.N_COPIES <= psc.PR_CAP, (n_probe, n)
+        assert n_probe <= n[psc.FAR] < psc.N_COPIES, (n_probe, n)
+    assert contenders(queries, cent, len(cent) // 4)[psc.FAR] == len(cent) > psc.PR_CAP          # deeper, it is above the cap
+    # psc.FAR_MAX: centroids no farther from FAR than the n_probe-th nearest + twice the widest interval (2 % to spare)
+    an2, bn2, q16, c16, inv_cs = images(queries, cent)
+    lb, ub = probe_bound(constants(psc.DIM, inv_cs), an2[:, None], bn2[None, :], (q16.astype(np.float64) @ c16.astype(np.float64).T).astype(F))
+    d_far = reference_chain(queries, cent)[psc.FAR]
+    width = float((ub - lb)[psc.FAR].max())
+    for n_probe in (1, 7):
+        assert (d_far <= np.sort(d_far)[n_probe - 1] + 2.02 * width).sum() <= psc.FAR_MAX[n_probe] < psc.N_COPIES - 1
+    # the far query's nearest centroid is the one it was placed beside, 0.01 away
+    d = np.sqrt(((cent.astype(np.float64) - queries[psc.FAR].astype(np.float64)) ** 2).sum(1))
+    assert 0.009 < d.min() < 0.011 and (d < 1.0).sum() < psc.N_FAR
+
+
+def test_refused_tables_have_a_norm_the_screen_cannot_hold():
+    """The premise of test_screened_probe_refuses_the_table: probe_screen_images gives up where a centred norm is not <= 3e38 --
+    the first table's is finite in every component and row norm of the centroids themselves, the second's is not a number."""
+    tables = psc.refused_tables()
+    for name, (_, cent) in tables.items():
+        mu = (cent.astype(np.float64).sum(0) / len(cent)).astype(F)
+        with np.errstate(over="ignore", invalid="ignore"):
+            bn2 = norms_like_kernel((cent - mu).astype(F))
+        assert not (bn2 <= F(3.0e38)).all(), name
+    cent = tables["norm above 3e38"][1]
+    assert np.isfinite(cent).all() and np.isfinite((cent.astype(np.float64) ** 2).sum(1).astype(F)).all()
+    assert not np.isfinite(tables["inf component"][1]).all()
