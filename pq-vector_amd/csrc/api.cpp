@@ -522,29 +522,37 @@ pqv_searcher::~pqv_searcher() {
 // The scratch lane of a call on `stream`: the lane that stream used last, else a free one, else the least
 // recently assigned one.  Resolved ONCE per public entry point (under s->mu) and handed down: a lane taken
 // over from another stream is first ordered behind that stream's last call (its `done` event), and
-// lane_release() records the new owner when the call's last kernel has been enqueued.
-static int lane_acquire(const pqv_searcher *s, hipStream_t stream, Scratch **out) {
+// release() records the new owner when the call's last kernel has been enqueued.  The destructor records `done` on EVERY other
+// way out of an entry point: an error return half-way through a call has enqueued work on `stream` that the lane's next owner
+// must still be ordered behind.
+struct Lane {
     Scratch *sc = nullptr;
-    for (auto &l : s->lanes) if (l.used && l.stream == stream) { sc = &l; break; }
-    if (!sc) for (auto &l : s->lanes) if (!l.used) { sc = &l; break; }
-    if (!sc) sc = &s->lanes[s->lane_rr++ % PQV_LANES];     // only an eviction advances the cursor
-    if (!sc->done) HIP_TRY(hipEventCreateWithFlags(&sc->done, hipEventDisableTiming));
-    if (sc->used && sc->stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sc->done, 0));
-    // owned by `stream` from here on, also if the call fails half-way: whatever it enqueued runs on `stream`
-    sc->stream = stream; sc->used = true;
-    *out = sc;
-    return PQV_OK;
-}
-static int lane_release(Scratch &sc, hipStream_t stream) {
-    HIP_TRY(hipEventRecord(sc.done, stream));
-    return PQV_OK;
-}
-// Records the lane's `done` event on EVERY way out of an entry point (an error return half-way through a call has enqueued
-// work on `stream` that the lane's next owner must still be ordered behind); recording again after a successful
-// lane_release() is harmless.
-struct LaneGuard {
-    Scratch &sc; hipStream_t stream;
-    ~LaneGuard() { if (sc.done) (void)hipEventRecord(sc.done, stream); }
+    hipStream_t stream = nullptr;
+    Lane() = default;
+    Lane(const Lane &) = delete;
+    Lane &operator=(const Lane &) = delete;
+    ~Lane() { if (sc && sc->done) (void)hipEventRecord(sc->done, stream); }
+    int acquire(const pqv_searcher *s, hipStream_t st) {
+        Scratch *l = nullptr;
+        for (auto &c : s->lanes) if (c.used && c.stream == st) { l = &c; break; }
+        if (!l) for (auto &c : s->lanes) if (!c.used) { l = &c; break; }
+        if (!l) l = &s->lanes[s->lane_rr++ % PQV_LANES];     // only an eviction advances the cursor
+        if (!l->done) HIP_TRY(hipEventCreateWithFlags(&l->done, hipEventDisableTiming));
+        if (l->used && l->stream != st) HIP_TRY(hipStreamWaitEvent(st, l->done, 0));
+        // owned by `st` from here on, also if the call fails half-way: whatever it enqueued runs on `st`
+        l->stream = st; l->used = true;
+        sc = l; stream = st;
+        return PQV_OK;
+    }
+    // the success path's last step: the same record, checked
+    int release() {
+        Scratch *l = sc;
+        sc = nullptr;
+        HIP_TRY(hipEventRecord(l->done, stream));
+        return PQV_OK;
+    }
+    Scratch &operator*() const { return *sc; }
+    Scratch *operator->() const { return sc; }
 };
 
 // A row mask (pqv.h: pqv_row_mask): one allow bit per row of the searcher's corpus, kept as the device bitset over LIST POSITIONS
@@ -753,12 +761,14 @@ static int upload_filter_arrays(Scratch &sc, uint32_t kind, const void *h_a, con
     *d_a = sc.s_qfilt_a.p; *d_b = sc.s_qfilt_b.p;
     return PQV_OK;
 }
-// A keyed or filtered host call's per-query arguments for the sub-batch [q0, q0 + b): uploaded on `st` into the lane's scratch,
-// `sub` pointed at them.
+// A host call's per-query filter arguments (rq's host arrays; a call without them: nothing to do) for the sub-batch [q0, q0 + b):
+// uploaded on `st` into the lane's scratch, `sub` pointed at them.
 static int upload_query_filter(Scratch &sc, const SearchRequest *rq, SearchRequest &sub, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
                                hipStream_t st) {
-    if (!rq || !rq->filtered()) return PQV_OK;
+    if (!rq) return PQV_OK;
     if (rq->rows.kind) return upload_filter_arrays(sc, rq->rows.kind, rq->rows.h_a, rq->rows.h_b, q0, b, lims, st, &sub.rows.d_a, &sub.rows.d_b);
+    if (!rq->rows.h_qkeys) return PQV_OK;
+    HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(b) * sizeof(int64_t)));
     HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, rq->rows.h_qkeys + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     sub.rows.d_qkeys = sc.s_qkeys.as<int64_t>();
     return PQV_OK;
@@ -4922,7 +4932,6 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     // 3. fold the per-wave lists, and the epilogue
     if (int rc = distinct ? enqueue_group_fold(c, ra) : enqueue_plain_fold(c, ra)) return rc;
     if (c.ev[3]) HIP_TRY(hipEventRecord(c.ev[3], stream));
-    if (int rc = lane_release(sc, stream)) return rc;
     s->counters.kernel_launches += 4;
     return PQV_OK;
 }
@@ -5208,22 +5217,35 @@ int topk_unbounded(const pqv_searcher *s, Scratch &sc, const float *queries, uin
 }  // namespace
 
 // The host entry points' PQV_COSINE queries: the cosine layout (ensure_cosine), then n(q) of host queries [nq, dim] computed on the device
-// (one normalize_rows_kernel launch on the searcher's stream) and brought back for the cosine searcher's own host entry point.
-static int cosine_queries_host(const pqv_searcher *s, const float *queries, uint32_t nq, std::vector<float> &out) {
+// (one normalize_rows_kernel launch on the searcher's stream) and brought back into `out`; then the call's arguments are pointed at
+// the cosine searcher's own L2 search over them, its write-out halving d2 (sqrt_out 2).  Any other metric: nothing happens.
+static int cosine_queries_host(const pqv_searcher *&s, const float *&queries, uint32_t nq, int &metric, int &sqrt_out, std::vector<float> &out) {
+    if (metric != PQV_COSINE) return PQV_OK;
     std::lock_guard<std::mutex> lock(s->mu);
     if (int rc = ensure_cosine(s)) return rc;
     const size_t n = static_cast<size_t>(nq) * s->dim;
     try { out.resize(n); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
-    Scratch *lane = nullptr;
-    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
-    LaneGuard lane_guard{*lane, s->stream};
+    Lane lane;
+    if (int rc = lane.acquire(s, s->stream)) return rc;
     HIP_TRY(lane->s_queries.ensure(n * sizeof(float)));
     HIP_TRY(lane->s_qcos.ensure(n * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(lane->s_queries.p, queries, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(pqv::launch_normalize_rows(lane->s_queries.as<float>(), s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), s->stream));
     HIP_TRY(hipMemcpyAsync(out.data(), lane->s_qcos.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    return lane_release(*lane, s->stream);
+    if (int rc = lane.release()) return rc;
+    queries = out.data(); s = s->cos.get(); metric = PQV_L2SQ_REF4; sqrt_out = 2;
+    return PQV_OK;
+}
+// The device entry points' PQV_COSINE queries: the cosine layout, then n(q) of the device queries into `lane` -- THIS searcher's, taken
+// here on the caller's stream -- as s_qcos.  The caller runs the cosine searcher's L2 body on the same stream (sqrt_out 2) and
+// releases the lane behind it: its `done` event follows that call's kernels.
+static int cosine_queries_device(const pqv_searcher *s, const float *d_queries, uint32_t nq, hipStream_t stream, Lane &lane) {
+    if (int rc = ensure_cosine(s)) return rc;
+    if (int rc = lane.acquire(s, stream)) return rc;
+    HIP_TRY(lane->s_qcos.ensure(static_cast<size_t>(nq) * s->dim * sizeof(float)));
+    HIP_TRY(pqv::launch_normalize_rows(d_queries, s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), stream));
+    return PQV_OK;
 }
 
 static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, uint32_t nq, uint32_t k,
@@ -5245,30 +5267,25 @@ static int pqv_topk_device_impl(const pqv_searcher *s, const void *d_queries, ui
     if (int rc = use_device(s->device)) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
-    Scratch *lane = nullptr;
+    Lane lane;
     if (metric == PQV_COSINE) {
-        // n(q) into this searcher's lane on the caller's stream, then the L2 call of the cosine searcher on the same stream, its
-        // write-out halving d2 (sqrt_out 2); the lane's `done` event follows that call's kernels
-        if (int rc = ensure_cosine(s)) return rc;
-        if (int rc = lane_acquire(s, stream, &lane)) return rc;
-        LaneGuard lane_guard{*lane, stream};
-        HIP_TRY(lane->s_qcos.ensure(static_cast<size_t>(nq) * s->dim * sizeof(float)));
-        HIP_TRY(pqv::launch_normalize_rows(static_cast<const float *>(d_queries), s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), stream));
+        // n(q), then the L2 call of the cosine searcher on the same stream
+        if (int rc = cosine_queries_device(s, static_cast<const float *>(d_queries), nq, stream, lane)) return rc;
         if (int rc = pqv_topk_device_impl(s->cos.get(), lane->s_qcos.p, nq, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
                                           d_n_found, d_n_candidates, d_tie_flags, stream, rq))
             return rc;
-        return lane_release(*lane, stream);
+        return lane.release();
     }
-    if (int rc = lane_acquire(s, stream, &lane)) return rc;
-    LaneGuard lane_guard{*lane, stream};
+    if (int rc = lane.acquire(s, stream)) return rc;
     // with flags the kernels carry one extra merged entry (the runner-up), exactly as pqv_topk does
     // (PQV_DOT: no runner-up -- dot_merge_kernel writes the flags with zeros)
-    const int rc = enqueue_topk(s, static_cast<const float *>(d_queries), nq, (d_tie_flags && metric != PQV_DOT) ? k + 1 : k, k, nprobe, max_candidates,
-                                metric, sqrt_out, static_cast<uint32_t *>(d_row_idx),
-                                static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
-                                static_cast<uint64_t *>(d_n_candidates), static_cast<uint32_t *>(d_tie_flags), stream, *lane, rq);
-    if (rc == PQV_OK) s->counters.queries += nq;
-    return rc;
+    if (int rc = enqueue_topk(s, static_cast<const float *>(d_queries), nq, (d_tie_flags && metric != PQV_DOT) ? k + 1 : k, k, nprobe, max_candidates,
+                              metric, sqrt_out, static_cast<uint32_t *>(d_row_idx),
+                              static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
+                              static_cast<uint64_t *>(d_n_candidates), static_cast<uint32_t *>(d_tie_flags), stream, *lane, rq))
+        return rc;
+    s->counters.queries += nq;
+    return lane.release();
 }
 extern "C" int pqv_topk_device(const pqv_searcher *s, const void *d_queries, uint32_t nq, uint32_t k,
                                uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
@@ -5284,147 +5301,176 @@ extern "C" int pqv_topk_device_flags(const pqv_searcher *s, const void *d_querie
     return guard([&] { return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates, d_tie_flags, hip_stream); });
 }
 
+// ---- host sub-batches ------------------------------------------------------------------------------------------------
+// One per-query output of a host top-k call: `bytes` per query, written by a sub-batch's kernels to `buf` and copied from there to
+// the caller's array at the sub-batch's offset (dst NULL: the buffer is sized, nothing is copied).
+struct BatchOut { DevBuf *buf; size_t bytes; void *dst; };
+// The loop of every host top-k entry point: the queries go through the lane in sub-batches of at most `batch` (the caller's bound
+// on its scratch).  Per sub-batch [q0, q0 + b): the queries uploaded to s_queries (through the pinned `h_stage` where the caller
+// has one), the slice of a per-query filter uploaded and the sub-batch's copy of the request pointed at it (upload_query_filter:
+// IN lims rebased), enqueue(b, brq) -- brq: that copy, for the caller to add its device outputs to, or nullptr for a call without a
+// request --, every output copied back, ONE synchronise, after(q0, b) on the host, and the queries counted.  s_queries and the
+// outputs' buffers are sized here, for `batch`, before the first enqueue.
+template <class Enqueue, class After>
+static int host_batches(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, uint32_t batch, const SearchRequest *rq,
+                        void *h_stage, const std::vector<BatchOut> &outs, Enqueue enqueue, After after) {
+    const size_t q_row = static_cast<size_t>(s->dim) * sizeof(float);
+    HIP_TRY(sc.s_queries.ensure(batch * q_row));
+    for (const BatchOut &o : outs) HIP_TRY(o.buf->ensure(batch * o.bytes));
+    SearchRequest sub{};
+    if (rq) sub = *rq;
+    std::vector<uint64_t> sub_lims;      // (an IN filter's rebased lims stay alive until the sub-batch's synchronisation)
+    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
+        const uint32_t b = std::min<uint32_t>(batch, nq - q0);
+        if (int rc = upload_query_filter(sc, rq, sub, q0, b, sub_lims, s->stream)) return rc;
+        const void *src = queries + static_cast<uint64_t>(q0) * s->dim;
+        if (h_stage) src = std::memcpy(h_stage, src, b * q_row);
+        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, src, b * q_row, hipMemcpyHostToDevice, s->stream));
+        if (int rc = enqueue(b, rq ? &sub : nullptr)) return rc;
+        for (const BatchOut &o : outs)
+            if (o.dst) HIP_TRY(hipMemcpyAsync(static_cast<char *>(o.dst) + q0 * o.bytes, o.buf->p, b * o.bytes, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (int rc = after(q0, b)) return rc;
+        s->counters.queries += b;
+    }
+    return PQV_OK;
+}
+
+namespace {
+int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const SearchRequest *mv, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
+                       uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key,
+                       uint32_t *n_found, uint64_t *n_candidates, uint32_t m, uint32_t *group_rows);
+}
+// The body of every host top-k entry point.  A grouping (rq->distinct(): pqv_topk_distinct / pqv_topk_grouped and their filtered and
+// expanding forms) changes what is read from the request below: rows per query k * m (row_idx / dist [nq, k, m]; m = groups.size,
+// 1 for a distinct call), the group_key / group_rows outputs [nq, k], no runner-up entry and no tie replay, and distinct_unbounded
+// beyond the kernels' lists.
 static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len,
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
-                        uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates, const SearchRequest *rq = nullptr) {
+                        uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates, const SearchRequest *rq = nullptr,
+                        int64_t *group_key = nullptr, uint32_t *group_rows = nullptr) {
     if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
     if (int rc = dot_checks(s, k, nprobe, metric, rq)) return rc;
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
     if (int rc = use_device(s->device)) return rc;
-    if (metric == PQV_COSINE) {
-        std::vector<float> nq_host;
-        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
-        return pqv_topk_impl(s->cos.get(), nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist, n_found,
-                             n_candidates, rq);
-    }
+    std::vector<float> nq_host;
+    if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     // One extra merged entry (the runner-up) lets the merge kernel see ties at the k-th
     // distance; queries it flags are replayed through the exact heap (replay_query_exact).
     // (k == UINT32_MAX -- "keep everything": the reference takes any NonZeroUsize -- must not wrap to a plan with k = 0)
     // (PQV_DOT: no runner-up, no replay -- the order is (dist, position) and the flags come back zero; its limits were checked above)
-    const bool dot = metric == PQV_DOT;
-    const uint32_t k_int = (dot || k >= 1024u) ? k : k + 1;
-    Scratch *lane = nullptr;
-    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
+    const bool dot = metric == PQV_DOT, grouped = rq && rq->distinct();
+    const bool expand = rq && rq->expanding();      // (the expanding forms stay within the kernels' lists: checked by their views)
+    const uint32_t m = grouped ? std::max<uint32_t>(1, rq->groups.size) : 1;
+    const uint32_t k_int = (dot || grouped || k >= 1024u) ? k : k + 1;
+    Lane lane;
+    if (int rc = lane.acquire(s, s->stream)) return rc;
     Scratch &sc = *lane;
-    LaneGuard lane_guard{sc, s->stream};
-    if (!dot && (k >= 1024u || beyond_kernel_lists(s, k_int, nprobe))) {
-        const int rc = topk_unbounded(s, sc, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates, rq);
-        const int rc2 = lane_release(sc, s->stream);
-        return rc ? rc : rc2;
+    if (grouped ? !expand && grouped_beyond_kernel_lists(s, k, m, nprobe) : !dot && (k >= 1024u || beyond_kernel_lists(s, k_int, nprobe))) {
+        if (int rc = grouped ? distinct_unbounded(s, sc, rq, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, group_key,
+                                                  n_found, n_candidates, m, group_rows)
+                             : topk_unbounded(s, sc, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, n_found, n_candidates, rq))
+            return rc;
+        return lane.release();
     }
     // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
-    // (per query: partial lists, probe partial lists, candidate buffer, the int8 images of its probed pairs)
+    // (per query: partial lists, probe partial lists, candidate buffer, the int8 images of its probed pairs; a grouping: 20 B per
+    //  entry of the partial lists, and a grouped call's second pass 16 B per entry of k * m in the same buffers)
     const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(rq, nprobe), k_int, metric, rq != nullptr);
-    const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * k_int * 12 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
-                               static_cast<uint64_t>(cand_cap_for(s, k_int)) * 12 + static_cast<uint64_t>(p1.np) * (s->sdim + 32) +
-                               static_cast<uint64_t>(s->sdim) * 4 + 1;
-    uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 30) / per_query)));
-    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
-    HIP_TRY(sc.s_rows.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
-    HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(batch) * k * sizeof(float)));
-    HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
-    HIP_TRY(sc.s_tie.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
-    std::vector<uint64_t> h_ncand(batch);
-    std::vector<uint32_t> h_tie(batch), h_nf(batch);
-    const uint32_t np = probe_count(s, probe_arg(rq, nprobe));
-    // an expanding call: the lists each query of the sub-batch used come back with its results
-    const bool expand = rq && rq->expand.max_nprobe;
-    std::vector<uint32_t> h_used(expand ? batch : 0);
-    if (expand) HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
-    // a keyed call: the kernels of a sub-batch read its own slice of the query keys (the same q0 as its queries)
-    SearchRequest sub{};
-    if (rq) sub = *rq;
-    if (expand) sub.expand.d_used = sc.s_expand_used.as<uint32_t>();
-    const SearchRequest *brq = rq ? &sub : nullptr;
-    if (rq && rq->eq_keys()) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
-    std::vector<uint64_t> sub_lims;
-    // A call of a few queries (TopkBuilder::search is ONE) is six small pageable copies otherwise -- the query in, rows, distances,
-    // counts and tie flags out, each staged and waited for by the runtime: 60-80 us around 180 us of kernels.  Small calls go
-    // through ONE pinned buffer instead: the results are laid out as one device block {candidates u64 | rows | dist | found |
-    // tie} and come back in one copy.
+    const uint64_t km = static_cast<uint64_t>(k) * m;
+    const uint64_t per_query =
+        grouped ? static_cast<uint64_t>(p1.n_part_rr) * std::max<uint64_t>(k * 20ull, m > 1 ? km * 16 + 4 : 0) +
+                      static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
+                      static_cast<uint64_t>(p1.np) * 32 + static_cast<uint64_t>(s->sdim + s->dim) * 4 + 20ull * k + (m > 1 ? 8ull * km : 0) + 16
+                : static_cast<uint64_t>(p1.n_part_rr) * k_int * 12 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
+                      static_cast<uint64_t>(cand_cap_for(s, k_int)) * 12 + static_cast<uint64_t>(p1.np) * (s->sdim + 32) +
+                      static_cast<uint64_t>(s->sdim) * 4 + 1;
+    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 30) / per_query)));
+    // the tie replay reads the flags, n_found (which it corrects) and an expanding call's lists used: the caller's arrays, or the call's
+    uint32_t *nf = n_found, *used = expand ? rq->expand.h_used : nullptr;
+    std::vector<uint32_t> h_tie, h_nf, h_used;
+    if (!grouped) {
+        h_tie.resize(nq);
+        if (!nf) { h_nf.resize(nq); nf = h_nf.data(); }
+        if (expand && !used) { h_used.resize(nq); used = h_used.data(); }
+    }
+    // A plain call of a few queries (TopkBuilder::search is ONE) is six small pageable copies otherwise -- the query in, rows,
+    // distances, counts and tie flags out, each staged and waited for by the runtime: 60-80 us around 180 us of kernels.  Small calls
+    // go through ONE pinned buffer instead -- host memory the device can address: the queries are staged in it, and the kernels WRITE
+    // the results straight into it as one block {candidates u64 | rows | dist | found | tie}, so there is no device-to-host copy
+    // behind them, only the synchronise.
     const size_t q_bytes = static_cast<size_t>(batch) * s->dim * sizeof(float);
     const size_t out_bytes = static_cast<size_t>(batch) * (16 + 8 * static_cast<size_t>(k));
     // (the result block starts with the u64 candidate counts: its offset behind the queries is rounded up to 64 bytes -- batch * dim
     //  may be odd, and the kernels store 64-bit values there)
     const size_t out_off = (q_bytes + 63) & ~static_cast<size_t>(63);
-    const bool small_io = out_off + out_bytes <= (256u << 10);
-    uint32_t *o_rows = sc.s_rows.as<uint32_t>(), *o_nf = sc.s_nfound.as<uint32_t>(), *o_tie = sc.s_tie.as<uint32_t>();
-    float *o_dist = sc.s_dist.as<float>();
-    if (small_io) {
-        HIP_TRY(sc.s_out.ensure(out_bytes));
-        HIP_TRY(sc.h_io.ensure(out_off + out_bytes));
+    const bool small_io = !grouped && out_off + out_bytes <= (256u << 10);
+    if (small_io) HIP_TRY(sc.h_io.ensure(out_off + out_bytes));
+    std::vector<BatchOut> outs;
+    if (!small_io)
+        outs = {{&sc.s_rows, km * sizeof(uint32_t), row_idx}, {&sc.s_dist, km * sizeof(float), dist}, {&sc.s_nfound, sizeof(uint32_t), nf},
+                {&sc.s_ncand, sizeof(uint64_t), n_candidates}};
+    if (grouped) {
+        outs.push_back({&sc.s_grp_out, k * sizeof(int64_t), group_key});
+        if (group_rows) outs.push_back({&sc.s_grows_out, k * sizeof(uint32_t), group_rows});
+    } else if (!small_io) {
+        outs.push_back({&sc.s_tie, sizeof(uint32_t), h_tie.data()});
     }
-    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
-        const uint32_t b = std::min<uint32_t>(batch, nq - q0);
-        // (round 5: the result block of a small call is WRITTEN by the kernels straight into the pinned buffer -- host memory the
-        //  device can address -- so there is no device-to-host copy behind them, only the synchronise: PQV_SMALL_IO_DIRECT=0 keeps the copy)
-        static const bool direct_out = [] { const char *e = std::getenv("PQV_SMALL_IO_DIRECT"); return !(e && *e == '0'); }();
-        if (int rc = upload_query_filter(sc, rq, sub, q0, b, sub_lims, s->stream)) return rc;
-        if (small_io) {
-            char *ob = direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p);           // (laid out for THIS sub-batch's b)
-            o_rows = reinterpret_cast<uint32_t *>(ob + 8ull * b);
-            o_dist = reinterpret_cast<float *>(ob + 8ull * b + 4ull * b * k);
-            o_nf = reinterpret_cast<uint32_t *>(ob + 8ull * b + 8ull * b * k);
-            o_tie = o_nf + b;
-            std::memcpy(sc.h_io.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float));
-            HIP_TRY(hipMemcpyAsync(sc.s_queries.p, sc.h_io.p, static_cast<size_t>(b) * s->dim * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim,
-                                   static_cast<size_t>(b) * s->dim * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        }
-        if (int rc = enqueue_topk(s, sc.s_queries.as<float>(), b, k_int, k, nprobe, max_candidates, metric,
-                                  sqrt_out, o_rows, o_dist, o_nf,
-                                  small_io ? reinterpret_cast<uint64_t *>(direct_out ? static_cast<char *>(sc.h_io.p) + out_off : static_cast<char *>(sc.s_out.p)) : nullptr,
-                                  o_tie, s->stream, sc, brq))
-            return rc;
-        if (expand) HIP_TRY(hipMemcpyAsync(h_used.data(), sc.s_expand_used.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        if (small_io) {
-            char *hb = static_cast<char *>(sc.h_io.p) + out_off;
-            const size_t ob_bytes = static_cast<size_t>(b) * (16 + 8 * static_cast<size_t>(k));
-            if (!direct_out) HIP_TRY(hipMemcpyAsync(hb, sc.s_out.p, ob_bytes, hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            std::memcpy(h_ncand.data(), hb, static_cast<size_t>(b) * sizeof(uint64_t));
-            std::memcpy(row_idx + static_cast<uint64_t>(q0) * k, hb + 8ull * b, static_cast<size_t>(b) * k * sizeof(uint32_t));
-            std::memcpy(dist + static_cast<uint64_t>(q0) * k, hb + 8ull * b + 4ull * b * k, static_cast<size_t>(b) * k * sizeof(float));
-            std::memcpy(h_nf.data(), hb + 8ull * b + 8ull * b * k, static_cast<size_t>(b) * sizeof(uint32_t));
-            std::memcpy(h_tie.data(), hb + 8ull * b + 8ull * b * k + 4ull * b, static_cast<size_t>(b) * sizeof(uint32_t));
-        } else {
-        HIP_TRY(hipMemcpyAsync(row_idx + static_cast<uint64_t>(q0) * k, sc.s_rows.p,
-                               static_cast<size_t>(b) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(dist + static_cast<uint64_t>(q0) * k, sc.s_dist.p,
-                               static_cast<size_t>(b) * k * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(h_nf.data(), sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(h_tie.data(), sc.s_tie.p, static_cast<size_t>(b) * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(h_ncand.data(), sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t),
-                               hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        }
-        for (uint32_t i = 0; i < b; ++i) {      // (candidate_rows / embeddings_fetched are counted on the device)
-            if (n_candidates) n_candidates[q0 + i] = h_ncand[i];
-            if (h_tie[i]) {
-                // tied output distances: survivors / order follow Rust's heap mechanics exactly
-                RowFilter allow;
-                if (int rc = row_filter(s, rq, static_cast<uint64_t>(q0) + i, allow)) return rc;
-                if (int rc = replay_query_exact(s, sc, s->sdim != s->dim ? sc.s_qpad.as<float>() + static_cast<size_t>(i) * s->sdim
-                                                                          : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i,
-                                                expand ? std::min<uint32_t>(std::max<uint32_t>(1, h_used[i]), np) : np,
-                                                k, max_candidates, metric, sqrt_out,
-                                                row_idx + static_cast<uint64_t>(q0 + i) * k,
-                                                dist + static_cast<uint64_t>(q0 + i) * k, &h_nf[i], nprobe, allow.active() ? &allow : nullptr, np))
-                    return rc;
-                s->counters.exact_replays++;
-            }
-            if (n_found) n_found[q0 + i] = h_nf[i];
-            if (expand && rq->expand.h_used) rq->expand.h_used[q0 + i] = h_used[i];
-        }
-        s->counters.queries += b;
-    }
-    return PQV_OK;
+    // (an expanding call: the lists each query used come back with its results)
+    if (expand) outs.push_back({&sc.s_expand_used, sizeof(uint32_t), used});
+    // the pinned block's arrays, laid out for a sub-batch of b queries
+    struct Block { uint64_t *ncand; uint32_t *rows; float *dist; uint32_t *nf, *tie; };
+    auto block = [&](uint32_t b) {
+        char *ob = static_cast<char *>(sc.h_io.p) + out_off;
+        uint32_t *f = reinterpret_cast<uint32_t *>(ob + 8ull * b + 8ull * b * k);
+        return Block{reinterpret_cast<uint64_t *>(ob), reinterpret_cast<uint32_t *>(ob + 8ull * b), reinterpret_cast<float *>(ob + 8ull * b + 4ull * b * k),
+                     f, f + b};
+    };
+    const uint32_t np = probe_count(s, probe_arg(rq, nprobe));
+    if (int rc = host_batches(
+            s, sc, queries, nq, batch, rq, small_io ? sc.h_io.p : nullptr, outs,
+            [&](uint32_t b, SearchRequest *brq) {
+                if (expand) brq->expand.d_used = sc.s_expand_used.as<uint32_t>();
+                if (grouped) {
+                    brq->groups.d_keys = sc.s_grp_out.as<int64_t>();
+                    brq->groups.d_rows = group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr;
+                }
+                const Block o = small_io ? block(b)
+                                         : Block{sc.s_ncand.as<uint64_t>(), sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(),
+                                                 grouped ? nullptr : sc.s_tie.as<uint32_t>()};
+                return enqueue_topk(s, sc.s_queries.as<float>(), b, k_int, k, nprobe, max_candidates, metric, sqrt_out, o.rows, o.dist, o.nf, o.ncand,
+                                    o.tie, s->stream, sc, brq);
+            },
+            [&](uint32_t q0, uint32_t b) -> int {
+                if (grouped) return PQV_OK;
+                if (small_io) {
+                    const Block o = block(b);
+                    if (n_candidates) std::memcpy(n_candidates + q0, o.ncand, static_cast<size_t>(b) * sizeof(uint64_t));
+                    std::memcpy(row_idx + static_cast<uint64_t>(q0) * k, o.rows, static_cast<size_t>(b) * k * sizeof(uint32_t));
+                    std::memcpy(dist + static_cast<uint64_t>(q0) * k, o.dist, static_cast<size_t>(b) * k * sizeof(float));
+                    std::memcpy(nf + q0, o.nf, static_cast<size_t>(b) * sizeof(uint32_t));
+                    std::memcpy(h_tie.data() + q0, o.tie, static_cast<size_t>(b) * sizeof(uint32_t));
+                }
+                for (uint32_t i = 0; i < b; ++i) {      // (candidate_rows / embeddings_fetched are counted on the device)
+                    const uint64_t q = static_cast<uint64_t>(q0) + i;
+                    if (!h_tie[q]) continue;
+                    // tied output distances: survivors / order follow Rust's heap mechanics exactly
+                    RowFilter allow;
+                    if (int rc = row_filter(s, rq, q, allow)) return rc;
+                    if (int rc = replay_query_exact(s, sc, s->sdim != s->dim ? sc.s_qpad.as<float>() + static_cast<size_t>(i) * s->sdim
+                                                                              : sc.s_queries.as<float>() + static_cast<size_t>(i) * s->dim, i,
+                                                    expand ? std::min<uint32_t>(std::max<uint32_t>(1, used[q]), np) : np,
+                                                    k, max_candidates, metric, sqrt_out, row_idx + q * k, dist + q * k, &nf[q], nprobe,
+                                                    allow.active() ? &allow : nullptr, np))
+                        return rc;
+                    s->counters.exact_replays++;
+                }
+                return PQV_OK;
+            }))
+        return rc;
+    return lane.release();
 }
 extern "C" int pqv_topk(const pqv_searcher *s, const float *queries, uint32_t nq, uint32_t query_len,
                         uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
@@ -5485,7 +5531,6 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
     HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
     SearchRequest sub{};      // (a keyed call: each sub-batch's kernels read its own slice of the query keys)
     if (rq) sub = *rq;
-    if (rq && rq->eq_keys()) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
     std::vector<uint64_t> sub_lims;
     std::vector<uint32_t> h_cnt(batch), h_probe;
     std::vector<uint64_t> h_ncand(batch), h_off(batch);
@@ -5620,23 +5665,17 @@ static int pqv_range_search_impl(const pqv_searcher *s, const float *queries, ui
     if (!lims || !rows || !dist) return fail(PQV_ERR_OOM, "host allocation failed");
     lims.get()[0] = 0;
     std::vector<float> nq_host;
-    if (nq && metric == PQV_COSINE) {
-        // the cosine searcher's range search over n(q): hits 0.5 d2 <= radius, written out halved (sqrt_out 2)
-        if (int rc = use_device(s->device)) return rc;
-        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
-        queries = nq_host.data();
-        s = s->cos.get(); metric = PQV_L2SQ_REF4; sqrt_out = 2;
-    }
     if (nq) {
         if (int rc = use_device(s->device)) return rc;
+        // (PQV_COSINE: the cosine searcher's range search over n(q): hits 0.5 d2 <= radius, written out halved)
+        if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
         std::lock_guard<std::mutex> lock(s->mu);
-        Scratch *lane = nullptr;
-        if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
-        LaneGuard lane_guard{*lane, s->stream};
+        Lane lane;
+        if (int rc = lane.acquire(s, s->stream)) return rc;
         if (int rc = range_body(s, *lane, queries, nq, radius, nprobe, max_candidates, max_results, metric, sqrt_out, lims.get(), rows,
                                 dist, n_within, n_candidates, rq))
             return rc;
-        if (int rc = lane_release(*lane, s->stream)) return rc;
+        if (int rc = lane.release()) return rc;
     }
     *lims_out = lims.release(); *rows_out = rows.release(); *dist_out = dist.release();
     return PQV_OK;
@@ -6325,7 +6364,6 @@ static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_p
         else HIP_TRY(launch_merge_final(fm, stream));
         s->counters.kernel_launches += 3;
     }
-    s->counters.queries += nq;
     return PQV_OK;
 }
 // the device form behind its checks; PQV_COSINE: n(q) into this searcher's lane, then the L2 body on the cosine searcher (sqrt_out 2)
@@ -6334,30 +6372,26 @@ static int topk_partition_device_impl(const pqv_searcher *s, const pqv_key_parti
                                       uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
     const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
     std::lock_guard<std::mutex> lock(s->mu);
-    Scratch *lane = nullptr;
+    Lane lane;
     if (metric == PQV_COSINE) {
-        if (int rc = ensure_cosine(s)) return rc;
-        if (int rc = lane_acquire(s, stream, &lane)) return rc;
-        LaneGuard lane_guard{*lane, stream};
-        HIP_TRY(lane->s_qcos.ensure(static_cast<size_t>(nq) * s->dim * sizeof(float)));
-        HIP_TRY(pqv::launch_normalize_rows(d_queries, s->dim, nullptr, nq, s->dim, lane->s_qcos.as<float>(), stream));
+        if (int rc = cosine_queries_device(s, d_queries, nq, stream, lane)) return rc;
         const pqv_searcher *cs = s->cos.get();
         std::lock_guard<std::mutex> cos_lock(cs->mu);
-        Scratch *cl = nullptr;
-        if (int rc = lane_acquire(cs, stream, &cl)) return rc;
-        LaneGuard cos_guard{*cl, stream};
-        if (int rc = enqueue_partition(cs, *cl, part, kind, d_a, d_b, bits, lane->s_qcos.as<float>(), nq, k, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
+        Lane cos_lane;
+        if (int rc = cos_lane.acquire(cs, stream)) return rc;
+        if (int rc = enqueue_partition(cs, *cos_lane, part, kind, d_a, d_b, bits, lane->s_qcos.as<float>(), nq, k, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
                                        d_n_found, d_n_cand, stream))
             return rc;
-        if (int rc = lane_release(*cl, stream)) return rc;
-        return lane_release(*lane, stream);
+        cs->counters.queries += nq;
+        if (int rc = cos_lane.release()) return rc;
+        return lane.release();
     }
-    if (int rc = lane_acquire(s, stream, &lane)) return rc;
-    LaneGuard lane_guard{*lane, stream};
+    if (int rc = lane.acquire(s, stream)) return rc;
     if (int rc = enqueue_partition(s, *lane, part, kind, d_a, d_b, bits, d_queries, nq, k, metric, sqrt_out, d_row_idx, d_dist, d_n_found, d_n_cand,
                                    stream))
         return rc;
-    return lane_release(*lane, stream);
+    s->counters.queries += nq;
+    return lane.release();
 }
 extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
                                          const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
@@ -6378,46 +6412,33 @@ extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_pa
 static int topk_partition_host_impl(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask,
                                     const float *queries, uint32_t nq, uint32_t k, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
                                     uint32_t *n_found, uint64_t *n_candidates) {
-    if (metric == PQV_COSINE) {
-        std::vector<float> nq_host;
-        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
-        return topk_partition_host_impl(s->cos.get(), part, f, mask, nq_host.data(), nq, k, PQV_L2SQ_REF4, 2, row_idx, dist, n_found, n_candidates);
-    }
+    std::vector<float> nq_host;
+    if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
     const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
     std::lock_guard<std::mutex> lock(s->mu);
-    Scratch *lane = nullptr;
-    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
+    Lane lane;
+    if (int rc = lane.acquire(s, s->stream)) return rc;
     Scratch &sc = *lane;
-    LaneGuard lane_guard{sc, s->stream};
     // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
     const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), k, part->m);
     const uint64_t per_query = static_cast<uint64_t>(B) * 4 * k * 12 + static_cast<uint64_t>(s->sdim) * 8 + 12ull * k + 8 * PQV_KEY_SET_MAX;
     const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
-    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
-    HIP_TRY(sc.s_rows.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
-    HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(batch) * k * sizeof(float)));
-    HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_out.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
-    HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
-    std::vector<uint64_t> sub_lims;
-    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
-        const uint32_t b = std::min<uint32_t>(batch, nq - q0);
-        const void *d_a = sc.s_qkeys.p, *d_b = nullptr;
-        if (f->kind == PQV_KEY_EQ)
-            HIP_TRY(hipMemcpyAsync(sc.s_qkeys.p, static_cast<const int64_t *>(f->a) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
-        else if (int rc = upload_filter_arrays(sc, f->kind, f->a, f->b, q0, b, sub_lims, s->stream, &d_a, &d_b)) return rc;
-        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
-                               hipMemcpyHostToDevice, s->stream));
-        if (int rc = enqueue_partition(s, sc, part, f->kind, d_a, d_b, bits, sc.s_queries.as<float>(), b, k, metric, sqrt_out, sc.s_rows.as<uint32_t>(),
-                                       sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(), s->stream))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(row_idx + static_cast<uint64_t>(q0) * k, sc.s_rows.p, static_cast<size_t>(b) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(dist + static_cast<uint64_t>(q0) * k, sc.s_dist.p, static_cast<size_t>(b) * k * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        if (n_candidates) HIP_TRY(hipMemcpyAsync(n_candidates + q0, sc.s_out.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    return lane_release(sc, s->stream);
+    SearchRequest rq{};      // the descriptor's host arrays, for the sub-batches' slices
+    rq.rows.kind = f->kind;
+    if (f->kind == PQV_KEY_EQ) rq.rows.h_qkeys = static_cast<const int64_t *>(f->a);
+    else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
+    if (int rc = host_batches(
+            s, sc, queries, nq, batch, &rq, nullptr,
+            {{&sc.s_rows, k * sizeof(uint32_t), row_idx}, {&sc.s_dist, k * sizeof(float), dist}, {&sc.s_nfound, sizeof(uint32_t), n_found},
+             {&sc.s_out, sizeof(uint64_t), n_candidates}},
+            [&](uint32_t b, SearchRequest *brq) {
+                return enqueue_partition(s, sc, part, f->kind, brq->d_filter_a(), brq->d_filter_b(), bits, sc.s_queries.as<float>(), b, k, metric,
+                                         sqrt_out, sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(),
+                                         sc.s_out.as<uint64_t>(), s->stream);
+            },
+            [](uint32_t, uint32_t) { return static_cast<int>(PQV_OK); }))      // (no host step)
+        return rc;
+    return lane.release();
 }
 extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter, const pqv_row_mask *mask,
                                   const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, int metric, int sqrt_out,
@@ -6452,7 +6473,7 @@ namespace {
 // m (a grouped call, pqv.h: pqv_topk_grouped): the first m rows of each of those key values, row_idx / dist [nq, k, m], group_rows [nq, k].
 int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const SearchRequest *mv, const float *queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                        uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key,
-                       uint32_t *n_found, uint64_t *n_candidates, uint32_t m = 1, uint32_t *group_rows = nullptr) {
+                       uint32_t *n_found, uint64_t *n_candidates, uint32_t m, uint32_t *group_rows) {
     const pqv_row_keys *gk = mv->groups.col;
     if (int rc = keys_host_rows(s, gk)) return rc;
     // the image of the considered positions, made on the host from the two images (n / 8 bytes each)
@@ -6526,90 +6547,14 @@ int distinct_unbounded(const pqv_searcher *s, Scratch &sc, const SearchRequest *
     return PQV_OK;
 }
 }  // namespace
-// (a grouped call: mv->groups.size = m >= 1, row_idx / dist [nq, k, m] and group_rows [nq, k]; m == 1 is the distinct call plus group_rows)
-static int pqv_topk_distinct_impl(const pqv_searcher *s, const SearchRequest *mv, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
-                                  uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                                  int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates, uint32_t *group_rows = nullptr) {
-    if (int rc = validate_query(s, k, nprobe, metric, max_candidates, query_len)) return rc;
-    if (int rc = dot_checks(s, k, nprobe, metric, mv)) return rc;
-    if (nq == 0) return PQV_OK;
-    if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
-    if (int rc = use_device(s->device)) return rc;
-    if (metric == PQV_COSINE) {
-        std::vector<float> nq_host;
-        if (int rc = cosine_queries_host(s, queries, nq, nq_host)) return rc;
-        return pqv_topk_distinct_impl(s->cos.get(), mv, nq_host.data(), nq, query_len, k, nprobe, max_candidates, PQV_L2SQ_REF4, 2, row_idx, dist,
-                                      group_key, n_found, n_candidates, group_rows);
-    }
-    const uint32_t m = std::max<uint32_t>(1, mv->groups.size);
-    std::lock_guard<std::mutex> lock(s->mu);
-    Scratch *lane = nullptr;
-    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
-    Scratch &sc = *lane;
-    LaneGuard lane_guard{sc, s->stream};
-    const bool expand = mv->expanding();       // (pqv_topk_distinct_expand: within the kernels' lists, checked by its view)
-    if (!expand && grouped_beyond_kernel_lists(s, k, m, nprobe)) {
-        const int rc = distinct_unbounded(s, sc, mv, queries, nq, k, nprobe, max_candidates, metric, sqrt_out, row_idx, dist, group_key, n_found,
-                                          n_candidates, m, group_rows);
-        const int rc2 = lane_release(sc, s->stream);
-        return rc ? rc : rc2;
-    }
-    // sub-batches as the keyed form slices them: the per-wave partial lists (20 B per entry here) stay under ~1 GiB
-    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(mv, nprobe), k, metric, true);
-    // (a grouped call's second pass: 16 B per entry of k * m, in the same buffers)
-    const uint64_t km = static_cast<uint64_t>(k) * m;
-    const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * std::max<uint64_t>(k * 20ull, m > 1 ? km * 16 + 4 : 0) +
-                               static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
-                               static_cast<uint64_t>(p1.np) * 32 + static_cast<uint64_t>(s->sdim + s->dim) * 4 + 20ull * k + (m > 1 ? 8ull * km : 0) + 16;
-    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 30) / per_query)));
-    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(batch) * s->dim * sizeof(float)));
-    HIP_TRY(sc.s_rows.ensure(static_cast<size_t>(batch) * km * sizeof(uint32_t)));
-    HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(batch) * km * sizeof(float)));
-    HIP_TRY(sc.s_grp_out.ensure(static_cast<size_t>(batch) * k * sizeof(int64_t)));
-    if (group_rows) HIP_TRY(sc.s_grows_out.ensure(static_cast<size_t>(batch) * k * sizeof(uint32_t)));
-    HIP_TRY(sc.s_nfound.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(batch) * sizeof(uint64_t)));
-    if (mv->eq_keys()) HIP_TRY(sc.s_qkeys.ensure(static_cast<size_t>(batch) * sizeof(int64_t)));
-    if (expand) HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(batch) * sizeof(uint32_t)));
-    SearchRequest sub = *mv;
-    if (expand) sub.expand.d_used = sc.s_expand_used.as<uint32_t>();
-    sub.groups.d_keys = sc.s_grp_out.as<int64_t>();
-    sub.groups.d_rows = group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr;
-    std::vector<uint64_t> sub_lims;      // (a filtered call: each sub-batch's kernels read its own slice of the filter, IN lims rebased)
-    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
-        const uint32_t b = std::min<uint32_t>(batch, nq - q0);
-        const uint64_t o = static_cast<uint64_t>(q0) * k;
-        if (int rc = upload_query_filter(sc, mv, sub, q0, b, sub_lims, s->stream)) return rc;
-        const size_t nk = static_cast<size_t>(b) * k;
-        const uint64_t om = o * m;
-        const size_t nkm = nk * m;
-        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
-                               hipMemcpyHostToDevice, s->stream));
-        if (int rc = enqueue_topk(s, sc.s_queries.as<float>(), b, k, k, nprobe, max_candidates, metric, sqrt_out, sc.s_rows.as<uint32_t>(),
-                                  sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_ncand.as<uint64_t>(), nullptr, s->stream, sc, &sub))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(row_idx + om, sc.s_rows.p, nkm * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(dist + om, sc.s_dist.p, nkm * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        if (group_key) HIP_TRY(hipMemcpyAsync(group_key + o, sc.s_grp_out.p, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
-        if (group_rows) HIP_TRY(hipMemcpyAsync(group_rows + o, sc.s_grows_out.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        if (n_candidates)
-            HIP_TRY(hipMemcpyAsync(n_candidates + q0, sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-        if (expand && mv->expand.h_used)
-            HIP_TRY(hipMemcpyAsync(mv->expand.h_used + q0, sc.s_expand_used.p, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        s->counters.queries += b;
-    }
-    return PQV_OK;
-}
 extern "C" int pqv_topk_distinct(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const float *queries, uint32_t nq,
                                  uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
                                  uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
         SearchRequest mv{};
         if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
-        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
-                                      n_found, n_candidates);
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
+                             &mv, group_key);
     });
 }
 extern "C" int pqv_topk_distinct_device(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const void *d_queries,
@@ -6642,8 +6587,8 @@ extern "C" int pqv_topk_grouped(const pqv_searcher *s, const pqv_row_keys *keys,
     return guard([&] {
         SearchRequest mv{};
         if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
-        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
-                                      n_found, n_candidates, group_rows);
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
+                             &mv, group_key, group_rows);
     });
 }
 extern "C" int pqv_topk_grouped_device(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, const void *d_queries,
@@ -6686,8 +6631,8 @@ extern "C" int pqv_topk_distinct_filtered(const pqv_searcher *s, const pqv_row_k
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, true, mv)) return rc;
-        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
-                                      n_found, n_candidates);
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
+                             &mv, group_key);
     });
 }
 extern "C" int pqv_topk_distinct_filtered_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
@@ -6710,8 +6655,8 @@ extern "C" int pqv_topk_grouped_filtered(const pqv_searcher *s, const pqv_row_ke
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, true, mv)) return rc;
-        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key,
-                                      n_found, n_candidates, group_rows);
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
+                             &mv, group_key, group_rows);
     });
 }
 extern "C" int pqv_topk_grouped_filtered_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
@@ -6771,8 +6716,8 @@ extern "C" int pqv_topk_distinct_expand(const pqv_searcher *s, const pqv_row_key
         SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, nprobe, max_nprobe, metric, true, mv)) return rc;
         mv.expand.h_used = nprobe_used;
-        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key, n_found,
-                                      n_candidates);
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
+                             &mv, group_key);
     });
 }
 extern "C" int pqv_topk_distinct_expand_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
@@ -6798,8 +6743,8 @@ extern "C" int pqv_topk_grouped_expand(const pqv_searcher *s, const pqv_row_keys
         SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, nprobe, max_nprobe, metric, true, mv)) return rc;
         mv.expand.h_used = nprobe_used;
-        return pqv_topk_distinct_impl(s, &mv, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, group_key, n_found,
-                                      n_candidates, group_rows);
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
+                             &mv, group_key, group_rows);
     });
 }
 extern "C" int pqv_topk_grouped_expand_device(const pqv_searcher *s, const pqv_row_keys *group_keys, const pqv_row_keys *filter_keys,
@@ -7020,10 +6965,9 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
     const uint32_t np = probe_count(s, nprobe);
     if (int rc = use_device(s->device)) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
-    Scratch *lane = nullptr;
-    if (int rc = lane_acquire(s, s->stream, &lane)) return rc;
+    Lane lane;
+    if (int rc = lane.acquire(s, s->stream)) return rc;
     Scratch &sc = *lane;
-    LaneGuard lane_guard{sc, s->stream};
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(s->dim) * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(sc.s_queries.p, query, static_cast<size_t>(s->dim) * sizeof(float), hipMemcpyHostToDevice, s->stream));
     if (np > 1024) {            // beyond the kernels' sorted lists: distances on the GPU, the stable sort on the host
@@ -7032,7 +6976,7 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
         if (int rc = host_probe(s, sc, sc.s_queries.as<float>(), 1, nprobe, 0, false, clusters, &total)) return rc;
         std::memcpy(clusters_out, clusters.data(), static_cast<size_t>(np) * sizeof(uint32_t));
         if (n_out) *n_out = np;
-        return lane_release(sc, s->stream);
+        return lane.release();
     }
     const TopkPlan p = plan_topk(s, 1, nprobe);
     pqv::MergeArgs pm{};        // (no pm.stats: a probe counts no candidates)
@@ -7040,7 +6984,7 @@ static int pqv_probe_impl(const pqv_searcher *s, const float *query, uint32_t qu
     if (int rc = enqueue_probe(s, sc, p, sc.s_queries.as<float>(), 1, nprobe, 0, pm, nullptr, 0, s->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(clusters_out, sc.s_probe.p, static_cast<size_t>(np) * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, s->stream));
-    if (int rc = lane_release(sc, s->stream)) return rc;
+    if (int rc = lane.release()) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (n_out) *n_out = np;
     s->counters.kernel_launches += 2;

@@ -461,3 +461,118 @@ def test_builders(pqv, tmp_path):
         assert [x.path for x in res] == [paths[int(i)] for i in f] and [x.row_idx for x in res] == local.tolist()
         assert [x.key for x in res] == g.tolist() and [np.float32(x.distance) for x in res] == dd.tolist()
         assert len(set(x.key for x in res)) == len(res) == 9
+
+
+# ---- host sub-batches: one call of more queries than the lane's scratch bound lets one pass hold ---------------------------------
+def host_batch(kc, dim, k, m):
+    """The queries one sub-batch of a host distinct (m = 1) / grouped call holds at 4096 x 128 over all kc = 8 lists: the per-query
+    scratch of the grouped branch of pqv_topk_impl (csrc/api.cpp) against its 1 GiB bound, restated from the code."""
+    n_part_rr = kc * 1 * 4                  # exact stream, >= 8192 (query, list) pairs: one block of four waves per list
+    n_part_probe, probe_kpart = 4, 64       # 8 centroids: one probe block of four waves; probe_rows_kernel's 64 unsorted entries
+    km = k * m
+    per_query = (n_part_rr * max(k * 20, km * 16 + 4 if m > 1 else 0) + n_part_probe * probe_kpart * 12 + kc * 32 + (dim + dim) * 4 +
+                 20 * k + (8 * km if m > 1 else 0) + 16)
+    return (1 << 30) // per_query
+
+
+# the per-query filters of the filtered runs: six patterns cycle over the queries, so the second sub-batch is right only if it got
+# its own slice of the arrays and IN lims rebased to it (sets of 300, 0, 1, 2, 65 and 7 values)
+SUB_FILTERS = {
+    "eq": [3, 0, 99, 63, 17, 40],                                                         # (99: no row's key)
+    "range": ([0, 2, 5, 63, -100, -(2 ** 63)], [7, 40, 4, 63, 0, 2 ** 63 - 1]),           # (5 > 4: nothing; the last: every key)
+    "in": [list(range(-150, 150)), [], [5], [-3, 17], list(range(0, 130, 2)), [1, 2, 3, 60, 61, 62, 1000]],
+}
+
+
+def check_host_sub_batches(pqv, oracle, m, filt):
+    """m None: topk_distinct, else topk_grouped with group_size m; filt: None or a key of SUB_FILTERS.  The call of
+    nq = batch + batch // 2 queries is compared (a) with the deduplicated range search -- the yardstick of this file, under the
+    mask M_q of the query's filter pattern -- for the first 64 queries, the 64 on each side of q0 = batch and the last 64, and (b)
+    for every query with the concatenation of calls of at most 1000 queries, every output bit for bit."""
+    import distinct_filter_ref as fref
+    import grouped_ref
+    c = SHAPES["4096x128"]
+    st = Setup(pqv, oracle, c["n"], c["dim"], c["kc"], seed=71)
+    k, nprobe = 300, st.kc
+    batch = host_batch(st.kc, c["dim"], k, m or 1)
+    assert 1000 < batch < 8000
+    nq = batch + batch // 2                 # (the second sub-batch starts in the middle of the call)
+    rng = np.random.default_rng(72)
+    q = rng.random((nq, c["dim"]), dtype=np.float32)
+    values = rng.integers(0, 1024, st.n).astype(np.int64)
+    valid = (rng.random(st.n) >= 0.1).astype(np.uint8)
+    fvalues = rng.integers(0, 64, st.n).astype(np.int32)
+    fvalid = (rng.random(st.n) >= 0.1).astype(np.uint8)
+    col = pqv.Column.upload(values, valid, device=0)
+    gkeys = st.s.row_keys(col)
+    col.close()
+    col = pqv.Column.upload(fvalues, fvalid, device=0)
+    fkeys = st.s.row_keys(col)
+    col.close()
+    which = np.arange(nq) % 6
+    kind, pat = (getattr(fref, filt.upper()), SUB_FILTERS[filt]) if filt else (None, None)
+
+    def spec(idx):      # the filter of the queries idx, as distinct_filter_ref states one
+        if kind == fref.RANGE:
+            return [pat[0][which[i]] for i in idx], [pat[1][which[i]] for i in idx]
+        return [pat[which[i]] for i in idx]
+
+    def call(a, b):
+        kw = dict(sqrt_out=False)
+        if filt:
+            kw.update(filter_keys=fkeys, **fref.call_kw(kind, spec(range(a, b))))
+        if m is None:
+            return st.s.topk_distinct(q[a:b], k, nprobe, gkeys, **kw)
+        return st.s.topk_grouped(q[a:b], k, m, nprobe, gkeys, **kw)
+
+    got = call(0, nq)
+    names = ("rows", "dist", "group_key") + (() if m is None else ("group_rows",)) + ("n_found", "n_candidates")
+    assert len(got) == len(names)
+    # (b) the same queries in calls of at most 1000
+    small = [call(a, min(a + 1000, nq)) for a in range(0, nq, 1000)]
+    for j, name in enumerate(names):
+        whole, parts = np.ascontiguousarray(got[j]), np.concatenate([p[j] for p in small])
+        assert whole.shape == parts.shape and (whole.view(np.uint8) == parts.view(np.uint8)).all(), f"{name}: one call != smaller calls"
+    # (a) the yardstick around both ends and the cut
+    sel = np.concatenate([np.arange(0, 64), np.arange(batch - 64, batch + 64), np.arange(nq - 64, nq)])
+    n_full = n_some = 0
+    for w in range(6 if filt else 1):
+        idx = sel[which[sel] == w] if filt else sel
+        allowed = distinct_ref.considered_mask(st.n, valid)
+        if filt:
+            allowed = allowed & fref.allowed(fvalues, fvalid, kind, spec([w]), 0)
+        ymask = st.s.row_mask(allowed)
+        lims, rows, dist, _, nc = st.s.range_search(q[idx], np.inf, nprobe, sqrt_out=False, mask=ymask)
+        ymask.close()
+        for j, i in enumerate(idx):
+            a, b = int(lims[j]), int(lims[j + 1])
+            what = f"query {i} (filter pattern {w})"
+            if m is None:
+                r, d, g = distinct_ref.dedup_sorted(rows[a:b], dist[a:b], values, k)
+                n = len(r)
+                assert got[3][i] == n, "n_found of " + what
+                assert (got[0][i, :n] == r).all() and (got[0][i, n:] == EMPTY).all(), "rows of " + what
+                assert (_bits(got[1][i, :n]) == _bits(d)).all() and np.isposinf(got[1][i, n:]).all(), "distance bits of " + what
+                assert (got[2][i, :n] == g).all() and (got[2][i, n:] == 0).all(), "group keys of " + what
+            else:
+                r, d, g, cnt, n = grouped_ref.group_sorted(rows[a:b], dist[a:b], values, k, m)
+                assert got[4][i] == n, "n_found of " + what
+                assert (got[0][i] == r).all() and (_bits(got[1][i]) == _bits(d)).all(), "rows / distance bits of " + what
+                assert (got[2][i] == g).all() and (got[3][i] == cnt).all(), "group keys / group_rows of " + what
+            assert got[-1][i] == nc[j], "n_candidates of " + what
+            n_full += n == k
+            n_some += n > 0
+    if not filt:
+        assert n_full == len(sel)           # (about a thousand valid key values in the probed lists: every query finds k groups)
+    elif filt != "eq":
+        assert n_full > 0                   # (the full range and the 300-value set pass every filter key)
+    assert n_some > len(sel) // 2
+    fkeys.close()
+    gkeys.close()
+
+
+@pytest.mark.parametrize("filt", [None, "eq", "range", "in"])
+def test_host_sub_batches(pqv, oracle, filt):
+    """One host call of more queries than one sub-batch holds (k = 300, 4096 x 128, all 8 lists): the second sub-batch's results,
+    group keys and counts land at their offsets, and its filter slice is its own."""
+    check_host_sub_batches(pqv, oracle, None, filt)

@@ -475,3 +475,11 @@ def test_builders(pqv, tmp_path):
             assert [np.float32(h.distance) for h in x.hits] == dd[i, :c[i]].tolist()
     with pytest.raises(pqv.PqvError, match=r"group_size\(\) needs distinct_on\(\)"):
         pqv.TopkBuilder(s, query).k(3).nprobe(1).group_size(2).search()
+
+
+@pytest.mark.parametrize("filt", [None, "eq", "range", "in"])
+def test_host_sub_batches(pqv, oracle, filt):
+    """One host call of more queries than one sub-batch holds (k = 300, m = 3, 4096 x 128, all 8 lists): rows and distances land at
+    q0 * k * m, group keys and group_rows at q0 * k, and the second sub-batch's filter slice is its own."""
+    from test_gpu_distinct import check_host_sub_batches
+    check_host_sub_batches(pqv, oracle, 3, filt)

@@ -438,3 +438,55 @@ def test_lifetime_refusals_and_limits(pqv, oracle):
     assert (got[2] == 0).all() and (got[3] == 0).all() and (got[0] == EMPTY).all() and np.isposinf(got[1]).all()
     empty.close()
     s.close()
+
+
+@pytest.mark.parametrize("masked", [False, True], ids=["unmasked", "masked"])
+def test_host_sub_batches(pqv, oracle, masked):
+    """One host call of more queries than one sub-batch of pqv_topk_partition holds (1500 x 30, partition_blocks 16, k = 256: the
+    per-query scratch against the 1 GiB bound, restated from csrc/api.cpp), for EQ, RANGE and IN filters that cycle over five
+    patterns (sets of 1, 2, 0, 3 and 5 values): the second sub-batch is right only if it got its own slice of the filter arrays,
+    IN lims rebased, and wrote at its offsets.  Compared with the restatement for the first 64 queries, the 64 on each side of
+    q0 = batch and the last 64, and for every query with the concatenation of calls of at most 1000 queries."""
+    name, k, blocks = "1500x30", 256, 16
+    c = pc.SHAPES[name]
+    sdim = c["dim"]                          # (30 dims: stored as they are)
+    per_query = blocks * 4 * k * 12 + sdim * 8 + 12 * k + 8 * 1024          # (1024: PQV_KEY_SET_MAX)
+    batch = min(32768, (1 << 30) // per_query)
+    assert 1000 < batch < 8000
+    nq = batch + batch // 2                  # (the second sub-batch starts in the middle of the call)
+    st = Setup(pqv, oracle, name, nq=1)
+    data = st.case.data
+    q = np.random.default_rng(91).random((nq, c["dim"]), dtype=np.float32)
+    sel = np.concatenate([np.arange(0, 64), np.arange(batch - 64, batch + 64), np.arange(nq - 64, nq)])
+    d_sel = pr.distances("l2", c["metric"], data, q[sel])
+    allow = np.random.default_rng(92).random(c["n"]) < 0.5 if masked else None
+    mask = st.s.row_mask(allow) if masked else None
+    col = "t3"
+    prows, pkeys = st.ref[col]
+    st.s.set_option("partition_blocks", blocks)
+    try:
+        for flt in pc.filters(col, nq, 93):
+            _, kind, a, b = flt
+
+            def sub(lo, hi):                 # the filter of the queries [lo, hi)
+                if kind == kf.IN:
+                    return (flt[0], kind, [x - a[lo] for x in a[lo:hi + 1]], b[a[lo]:a[hi]])
+                return (flt[0], kind, a[lo:hi], b[lo:hi] if b is not None else None)
+
+            def call(lo, hi):
+                return st.s.topk_partition(q[lo:hi], k, st.parts[col], mask=mask, metric=c["metric"], sqrt_out=False, **_host_filter(sub(lo, hi)))
+
+            got = call(0, nq)
+            small = [call(lo, min(lo + 1000, nq)) for lo in range(0, nq, 1000)]
+            _same(got, [np.concatenate([p[j] for p in small]) for j in range(4)], f"{flt[0]}: one call vs smaller calls")
+            for j, i in enumerate(sel):
+                exp = pr.topk(prows, pkeys, kind, a, b, int(i), d_sel[j], k, "l2", False, allow)
+                _same([x[i:i + 1] for x in got], [exp[0][None], exp[1][None], np.array([exp[2]], np.uint32), np.array([exp[3]], np.uint64)],
+                      f"{flt[0]}: query {i} vs the restatement")
+            assert (got[2][batch:] > 0).any()
+            if kind == kf.RANGE:             # (the full range: more than k rows also under the mask)
+                assert (got[2][batch:] == k).any()
+    finally:
+        st.s.set_option("partition_blocks", 0)
+        if mask is not None:
+            mask.close()
