@@ -493,7 +493,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void brute_
         float lb;
         if (a.metric == BRUTE_COSINE) lb = (1.0f - sc) - eps;
         else {
-            const float qv = sqrtf(qaux_s[ml] * vaux) * 1.000001f;     // |q| |v|
+            const float qv = sqrtf(qaux_s[ml]) * sqrtf(vaux) * 1.000001f;     // |q| |v| (|q|^2 |v|^2 leaves f32's range where |q|^2 + |v|^2 does not)
             lb = (qaux_s[ml] + vaux - 2.0f * qv * sc) - 2.0f * qv * eps - 1.0e-6f * (qaux_s[ml] + vaux);
             lb = lb < 0.0f ? 0.0f : lb;
         }
