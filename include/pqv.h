@@ -387,6 +387,9 @@ int pqv_round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max
  *   "fork_wide"     the wide-quad launch on a side stream of the call's lane: 0 off (default), 1 regular instance first, 2 wide first
  *   "pf96"          f16 96-query form on rows of <= 128 dims: all of the next tile's operands are requested behind the current tile's
  *                   MFMAs (1 = for lists of <= 2048 rows on average (default), 2 always, 0 never)
+ *   "static_dim"    int8 path, batches, k <= 64: 1 (default) = rows of 768 dims run the screen instances that have the row length compiled
+ *                   in (K loops unrolled, every A-operand read at a lane address + immediate; same results); 0 = the run-time row length
+ *                   everywhere (A/B runs)
  *   "drain_min"     queued survivors that start a batch of exact evaluations before a wave's last tile (0 = 64)
  *   "partition_blocks" pqv_topk_partition: blocks per query of partition_stream_kernel (0 = by rule, from nq, k and the partition's
  *                   rows; at most 4096)

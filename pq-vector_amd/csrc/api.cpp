@@ -476,6 +476,7 @@ struct pqv_searcher {
         int i8_form = 0;                   // int8 images: 0 by rule (per-list residual where the lists are tight), 1 one centre, 2 residual
         int xcd_items = 1;                 // PairSortArgs::xcd_items (PQV_XCD_ITEMS)
         int pf96 = 1;                      // TileArgs::opt_pf96 (PQV_PF96)
+        int static_dim = 1;                // TileArgs::static_dim (PQV_STATIC_DIM): 0 = the run-time row length in every screen instance
         int drain_min = 0;                 // TileArgs::drain_min (PQV_DRAIN_MIN)
         int fork_wide = 0;                 // the wide-quad launch on the lane's side stream, beside the regular instance (PQV_FORK_WIDE)
         int wide_quads = 1;                // int8, 96-query quads: lists probed by 97..160 queries of the batch take ONE 160-query quad
@@ -3341,6 +3342,7 @@ void opts_from_env(pqv_searcher::Opts &o) {
     o.fork_wide = static_cast<int>(num("PQV_FORK_WIDE", o.fork_wide));
     o.drain_min = static_cast<int>(num("PQV_DRAIN_MIN", o.drain_min));
     o.pf96 = static_cast<int>(num("PQV_PF96", o.pf96));
+    o.static_dim = num("PQV_STATIC_DIM", o.static_dim) != 0 ? 1 : 0;
     o.xcd_items = static_cast<int>(num("PQV_XCD_ITEMS", o.xcd_items));
     o.wide_quad_rows = static_cast<uint32_t>(num("PQV_WIDE_QUAD_ROWS", o.wide_quad_rows));
     o.list_once = static_cast<int>(num("PQV_LIST_ONCE", o.list_once));
@@ -4642,6 +4644,7 @@ static int enqueue_wide_screen(TopkCall &c, const pqv::PairSortArgs &ps, pqv::Ti
         ta.cand_lb = sc.s_cand_lb.as<float>();
         ta.pendv = sc.s_pendv.as<uint32_t>(); ta.pendv_wide = ta.pendv + words_r;
     }
+    ta.static_dim = s->opt.static_dim ? 1u : 0u;       // (the seed kernel and the two filter instances)
     // thresholds: upper bounds of the first seed_rows rows of every probed list
     TileArgs seed = ta;
     if (rt.wide) seed.quad_width = p.wide_width;      // (the seed kernel samples a quad in slices of its own 64 queries)
@@ -6800,6 +6803,7 @@ static int pqv_searcher_set_option_impl(pqv_searcher *s, const char *name, int64
     else if (n == "wide_quads") o.wide_quads = value <= 0 ? 0 : value >= 2 ? 2 : 1;       // 1: by the previous batch's shape; 2: always
     else if (n == "fork_wide") o.fork_wide = value <= 0 ? 0 : value >= 2 ? 2 : 1;
     else if (n == "pf96") o.pf96 = value <= 0 ? 0 : value >= 2 ? 2 : 1;
+    else if (n == "static_dim") o.static_dim = value != 0 ? 1 : 0;
     else if (n == "drain_min") o.drain_min = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(64, value)));
     else if (n == "xcd_items") o.xcd_items = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(3, value)));
     else if (n == "wide_quad_rows") o.wide_quad_rows = static_cast<uint32_t>(std::max<int64_t>(0, value));
@@ -6856,7 +6860,7 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
     }
     const TopkPlan p = plan_topk(s, std::max<uint32_t>(1, nq), nprobe, k, metric);
     const TopkRoute rt = topk_route(s, p, std::max<uint32_t>(1, nq), k);      // the decisions enqueue_topk follows
-    char t[768];
+    char t[1024];
     if (rt.screened)
         std::snprintf(t, sizeof t, "wide_seed_kernel + seed_select_kernel + wide_filter_kernel: %s screen operands, quads of %u queries "
                       "staged %s, %u waves per block, %u rows per block, threshold sample %u rows per list%s%s",
@@ -6884,6 +6888,13 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
         else
         std::snprintf(t + l, sizeof t - l, "; lists probed by %u..%u queries: one quad, 8 waves per block on 32-row tiles, %u rows per block",
                       p.quad_width + 1, p.wide_width, p.wide_rows_per_block);
+    }
+    if (rt.screened && rt.operand == 2) {
+        // (launch_wide's rule: the regular and the wide-quad int8 instance, k <= 64, exact evaluation in the kernel, 768 dims)
+        const bool sd = s->opt.static_dim && s->sdim == 768 && k <= 64 && !rt.deferred && !rt.q_global && p.quad_width == 96 && p.block_waves == 4;
+        const size_t l = std::strlen(t);
+        if (sd) std::snprintf(t + l, sizeof t - l, "; row length compiled in (%u dims: unrolled K loops, A operands at four lane addresses + immediates)", s->sdim);
+        else std::snprintf(t + l, sizeof t - l, "; row length read at run time");
     }
     if (rt.deferred) {
         const size_t l = std::strlen(t);

@@ -111,7 +111,8 @@ __device__ __forceinline__ uint32_t buf_ld4(__amdgpu_buffer_rsrc_t r, uint32_t l
 #endif
 #ifndef PQV_NA_REG
 #define PQV_NA_REG 0           // regular int8 instance: branch-free K loop bodies for quads of 3 / 4 / 5 groups too (spilled 124 bytes while every
-                               // accumulator had two register homes; fits since -- 245 VGPRs, no scratch -- and is not measured yet: off)
+                               // accumulator had two register homes; the run-time form fits since -- 245 VGPRs, no scratch -- but the
+                               // DIM = 768 instance, already at 256 VGPRs, takes 20 bytes of scratch with them: off)
 #endif
 #ifndef PQV_THR_EVERY
 #define PQV_THR_EVERY 1        // 64-row-tile instances: thresholds re-read behind every n-th tile

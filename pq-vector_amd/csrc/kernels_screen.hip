@@ -531,10 +531,15 @@ __device__ __forceinline__ void seed_tail_finish(const TileArgs &a) {
 // tile per wave and nothing else on the CU, so its 48 KB are requested 12 stages at a time.  Only the U > 1 instances
 // carry the one-query tail (select + refinement by the last block): its register needs (16 row chunks + 16 query chunks
 // in flight per lane) would otherwise set the allocation -- and halve the occupancy -- of the batched instances.
-template <int NG, bool QLDS, int OP, int U = 1>
+// DIM: the row length compiled in (the batched int8 instance; 0 = TileArgs::dim): the K steps in line, the staged image read at four
+// lane addresses plus immediates -- wide_filter_kernel's form of the same image.
+template <int NG, bool QLDS, int OP, int U = 1, int DIM = 0>
 __global__ __launch_bounds__(256) void wide_seed_kernel(const TileArgs a) {
     constexpr bool F16 = OP == OP_F16, I8 = OP == OP_I8;
     static_assert(!I8 || QLDS, "int8 operands: queries staged in LDS");
+    static_assert(DIM == 0 || (I8 && QLDS && U == 1 && DIM % 256 == 0 && 256 * (DIM / 16) * (NG - 1) + 256 * (DIM / 256 - 1) <= 65535),
+                  "compiled-in row length: the batched int8 instance, every group within the 16-bit immediate");
+    constexpr bool SD = DIM != 0;
     constexpr uint32_t NQ = 16 * NG;
     // One-query instance (U > 1; launched only for nq == 1, so a quad holds ONE query): a block takes one 64-row tile and
     // each of its waves ONE 16-row sub-tile of it (TS = 1) -- four times the blocks, because a CU takes in ~25-40 GB/s
@@ -577,7 +582,7 @@ __global__ __launch_bounds__(256) void wide_seed_kernel(const TileArgs a) {
     if (a.row_end && r1 > a.row_end) r1 = a.row_end;
     if (r0 > r1) r0 = r1;
 
-    const uint32_t dim = a.dim;
+    const uint32_t dim = SD ? (uint32_t)DIM : a.dim;
     const uint32_t G = I8 ? dim >> 4 : F16 ? dim >> 3 : dim >> 2;    // 16-byte operand columns per row
     const float cmargin = (float)(dim + 16) * 2.384185791015625e-07f;   // (dim + 16) * 2^-22
     const float c16 = F16 ? 1.25f * 9.765625e-04f : 0.0f;               // f16 operands: see wide_filter_kernel
@@ -638,6 +643,15 @@ __global__ __launch_bounds__(256) void wide_seed_kernel(const TileArgs a) {
     const float4 *qblk = a.q_blk + (uint64_t)by * NG * G * 16;
     const __amdgpu_buffer_rsrc_t qr = operand_rsrc(QLDS ? (const void *)a.queries : (const void *)qblk);
 
+    // SD: the four lane addresses of the staged image, one per ks & 3 (wide_filter_kernel: `qa`), made once per wave
+    typedef const __attribute__((address_space(3))) f32x4_acc lds_f4;
+    [[maybe_unused]] uint32_t qa[SD ? 4 : 1];
+    if constexpr (SD) {
+        const uint32_t q0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)qs + (uint32_t)l15 * (16u * (DIM / 16))
+                            + (((uint32_t)kk ^ ((uint32_t)l15 & 3u)) << 4);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { qa[b] = q0 + (((uint32_t)b ^ ((uint32_t)l15 >> 2)) << 6); asm volatile("" : "+v"(qa[b])); }
+    }
     float mins[NGE][4];
     // I8: the largest dot - ceil(Nx / 2) a lane sees per query bounds the smallest |qi - xi|^2 from above
     [[maybe_unused]] int maxs[NGE][4];
@@ -682,6 +696,22 @@ __global__ __launch_bounds__(256) void wide_seed_kernel(const TileArgs a) {
                 else acc[g][t] = (f32x4_acc){0.f, 0.f, 0.f, 0.f};
             }
         const uint32_t nks = G >> 2;
+        if constexpr (SD) {
+            static_for<DIM / 64>([&](auto ksc) {
+                constexpr uint32_t KS = (uint32_t)decltype(ksc)::value;
+                float4 x[TS];
+#pragma unroll
+                for (int t = 0; t < TS; ++t) x[t] = buf_ld16(xr, lane_off * 16u, xso[t] + KS * 1024);
+#pragma unroll
+                for (int g = 0; g < NGE; ++g) {
+                    if ((uint32_t)g < ng) {
+                        const float4 qc = __builtin_bit_cast(float4, *(lds_f4 *)(uintptr_t)(qa[KS & 3u] + (uint32_t)g * (256u * (DIM / 16)) + 256u * (KS >> 2)));
+#pragma unroll
+                        for (int t = 0; t < TS; ++t) mfma_step<OP>(acc[g][t], qc, x[t]);
+                    }
+                }
+            });
+        } else
         for (uint32_t ks0 = 0; ks0 < nks; ks0 += U) {
             float4 x[U][TS];
             if (ONE && ks0 == 0) {          // (one branch around the whole stage set, not a select per load)
@@ -1168,7 +1198,11 @@ hipError_t launch_wide_seed(const TileArgs &a, hipStream_t s) {
             32ull * a.dim > 65536) return hipErrorInvalidValue;
         // 64 queries per pass where they fit 48 KB (a 96-query quad is then sampled in two slices instead of three:
         // the sample rows are re-read once per slice)
-        if (64ull * a.dim <= 49152)
+        if (a.static_dim && a.dim == 768 && !deep) {        // batches of 768-dim rows: the row length compiled in
+            TileArgs b = a;
+            b.seed_tail.lds_floats = (uint32_t)(64ull * a.dim / 4);
+            hipLaunchKernelGGL((wide_seed_kernel<4, true, OP_I8, 1, 768>), dim3(a.grid_x, a.max_quads, (a.quad_width + 63) / 64), dim3(256), 64ull * a.dim, s, b);
+        } else if (64ull * a.dim <= 49152)
             SEED_LAUNCH(4, OP_I8, dim3(a.grid_x, a.max_quads, (a.quad_width + 63) / 64), 64ull * a.dim)
         else
             SEED_LAUNCH(2, OP_I8, dim3(a.grid_x, a.max_quads, a.quad_width / 32), 32ull * a.dim)
@@ -1277,7 +1311,10 @@ __device__ __forceinline__ uint64_t qread_u64(const uint64_t (&v)[QS], uint32_t 
 // halve the accumulator registers per query group, so ONE block holds a quad of 160 queries (120 KB of int8 images) and a
 // list that 97..160 queries of the batch probe is streamed once instead of twice (launch_tile_filter, TileArgs::wide_*).
 // DEFP: the deferred-evaluation form (5.4b) also in a k <= 64 instance (the k > 64 instances always carry it)
-template <int NG, int NW, int S, bool QLDS, int OP, bool PF, bool ONCE, int TS, bool DEFP>
+// DIM: the row length compiled in (int8 instances of the flagship dispatch; 0 = TileArgs::dim at run time).  G, the K step count and
+// the group stride of the staged images are constants then: the K loop is unrolled over all its steps and every A-operand read is
+// ds_read_b128 at one of four per-lane addresses plus an immediate (see `qa` below) -- no address arithmetic inside the loop.
+template <int NG, int NW, int S, bool QLDS, int OP, bool PF, bool ONCE, int TS, bool DEFP, int DIM = 0>
 __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS && OP != OP_F32)) ? 2 : 3) void wide_filter_kernel(const TileArgs a) {
     constexpr int ROW_AUX = ONCE ? 2 : PQV_ROW_AUX;
     constexpr bool F16 = OP == OP_F16, I8 = OP == OP_I8;
@@ -1285,6 +1322,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
     static_assert(!I8 || QLDS, "int8 operands: queries staged in LDS");
     static_assert(TILE_QB == 16 && NG >= 2 && NG <= 12 && (NG % 2) == 0 && (NW == 4 || NW == 8), "16-row MFMA tiles, 2..12 groups, 4 or 8 waves");
     static_assert(TS == 4 || (TS == 2 && QLDS && !PF && OP != OP_F32), "32-row tiles: staged queries, int8 / f16 operands");
+    static_assert(DIM == 0 || (I8 && QLDS && DIM % 256 == 0), "compiled-in row length: int8 images staged in LDS, K steps in fours");
+    constexpr bool SD = DIM != 0;
     constexpr uint32_t TROWS = 16 * TS;            // rows per wave tile
     constexpr uint32_t FW = 4 * TS, GPW = 32 / FW; // keep-bits per lane and group; groups per 32-bit word
     constexpr int NWD = (NG + (int)GPW - 1) / (int)GPW;
@@ -1389,7 +1428,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
     if (a.row_end && r1 > a.row_end) r1 = a.row_end;     // window of this launch
     if (r0 > len) r0 = len;
 
-    const uint32_t dim = a.dim;
+    const uint32_t dim = SD ? (uint32_t)DIM : a.dim;     // (SD: everything derived from it below is a constant)
     // 16-byte operand columns per row: 4 f32, 8 f16 or 16 int8 values each; a K step is 4 columns
     const uint32_t G = I8 ? dim >> 4 : F16 ? dim >> 3 : dim >> 2;
     const uint32_t Gx = dim >> 2;                    // 16-byte chunks of a row-major f32 row (exact evaluation)
@@ -2013,13 +2052,47 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
         // group g + APD is issued before the MFMAs of group g (rotating register quads; group indices past the quad's last
         // group are clamped to it, the staged part of the LDS).
         constexpr int APD = TS == 2 ? PQV_APD_TS2 : PQV_APD;
+        // SD: column (4 ks + kk) ^ l15 = 16 (ks >> 2) + 4 ((ks & 3) ^ (l15 >> 2)) + (kk ^ (l15 & 3)) -- within four K steps a lane
+        // visits the same four 64-byte column blocks, in an order fixed by l15 >> 2.  FOUR per-lane LDS byte addresses qa[ks & 3]
+        // (the staged image's own address included), made once per tile; group g at K step ks is qa[ks & 3] + g * 256 G +
+        // 256 (ks >> 2), an immediate of the read.  The field has 16 bits: groups from QSPLIT on take a second set, qa2.  Both sets
+        // are opaque to the compiler, which otherwise folds the second into the first and adds the constant again at every read.
+        constexpr uint32_t NKS = SD ? DIM / 64 : 4, GSB = SD ? 256u * (DIM / 16) : 1u;
+        constexpr uint32_t QSPLIT = (65535u - 256u * (NKS / 4 - 1)) / GSB + 1u;
+        static_assert(!SD || (uint32_t)NG <= 2 * QSPLIT, "two address sets reach every group");
+        constexpr bool QA2 = SD && (uint32_t)NG > QSPLIT;
+        typedef const __attribute__((address_space(3))) f32x4_acc lds_f4;      // (a built-in vector: loads through the LDS address space)
+        [[maybe_unused]] uint32_t qa[SD ? 4 : 1], qa2[QA2 ? 4 : 1];
+        if constexpr (SD) {
+            const uint32_t q0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)qs + (uint32_t)l15 * (16u * (DIM / 16))
+                                + (((uint32_t)kk ^ ((uint32_t)l15 & 3u)) << 4);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                qa[b] = q0 + ((((uint32_t)b ^ ((uint32_t)l15 >> 2))) << 6);
+                asm volatile("" : "+v"(qa[b]));
+                if constexpr (QA2) { qa2[b] = qa[b] + QSPLIT * GSB; asm volatile("" : "+v"(qa2[b])); }
+            }
+        }
+        // `ksv`: the K step -- a run-time uint32_t, or (SD) std::integral_constant<int, ks> of the unrolled loop
         // `full`: std::integral_constant<int, NA> -- NA > 0: exactly the first NA groups, branch-free (NA = NG: a full quad);
         // NA = 0: the quad's ng groups behind per-group branches
         // `first`: std::bool_constant -- the accumulators' first K step: they START here, from c0 (groups that are not
         // contracted still get the start value: the screen reads every accumulator and masks what does not count)
-        auto mma = [&](const float4 (&x)[TS], uint32_t ks, auto full, auto first) {
+        auto mma = [&](const float4 (&x)[TS], auto ksv, auto full, auto first) {
             constexpr int NA = decltype(full)::value, NGL = NA ? NA : NG;
             constexpr bool FIRST = decltype(first)::value;
+            constexpr bool KSC = !std::is_integral_v<decltype(ksv)>;
+            static_assert(KSC == SD, "a compiled-in row length, and only that, unrolls the K loop");
+            const uint32_t ks = (uint32_t)ksv;
+            // SD: the A operand of group gi (a constant wherever the group loops are unrolled over live groups)
+            auto qread = [&](uint32_t gi) -> float4 {
+                if constexpr (KSC) {
+                    constexpr uint32_t KS = (uint32_t)decltype(ksv)::value;
+                    const bool hi = QA2 && gi >= QSPLIT;
+                    const uint32_t base = hi ? qa2[QA2 ? (KS & 3u) : 0u] : qa[KS & 3u];
+                    return __builtin_bit_cast(float4, *(lds_f4 *)(uintptr_t)(base + (hi ? gi - QSPLIT : gi) * GSB + 256u * (KS >> 2)));
+                } else return make_float4(0.f, 0.f, 0.f, 0.f);
+            };
             auto step = [&](int g, const float4 qc) {
 #pragma unroll
                 for (int t = 0; t < TS; ++t) {
@@ -2037,8 +2110,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
             if constexpr (APD == 0) {
 #pragma unroll
                 for (int g = 0; g < NGL; ++g) {
-                    if (NA || (uint32_t)g < ng) step(g, qs[(16 * g + l15) * G + (chq ^ (uint32_t)l15)]);
-                    else idle(g);
+                    if (NA || (uint32_t)g < ng) {
+                        if constexpr (KSC) step(g, qread((uint32_t)g));
+                        else step(g, qs[(16 * g + l15) * G + (chq ^ (uint32_t)l15)]);
+                    } else idle(g);
                 }
             } else {
                 const float4 *qb0 = qs + (uint32_t)l15 * G + (chq ^ (uint32_t)l15);
@@ -2047,14 +2122,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
 #pragma unroll
                 for (int g = 0; g < APD && g < NGL; ++g) {
                     const uint32_t gi = NA || (uint32_t)g < ng ? (uint32_t)g : ng - 1u;
-                    qb[g] = qb0[gi * gstride];
+                    if constexpr (KSC) qb[g] = qread(gi); else qb[g] = qb0[gi * gstride];
                 }
 #pragma unroll
                 for (int g = 0; g < NGL; ++g) {
                     if (NA || (uint32_t)g < ng) {
                         if (g + APD < NGL) {
                             const uint32_t gi = NA || (uint32_t)(g + APD) < ng ? (uint32_t)(g + APD) : ng - 1u;
-                            qb[(g + APD) % (APD + 1)] = qb0[gi * gstride];
+                            if constexpr (KSC) qb[(g + APD) % (APD + 1)] = qread(gi); else qb[(g + APD) % (APD + 1)] = qb0[gi * gstride];
                         }
                         step(g, qb[g % (APD + 1)]);
                         // (the machine scheduler otherwise sinks every read back in front of its use to save the registers)
@@ -2081,6 +2156,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
 #pragma unroll
                 for (int t = 0; t < TS; ++t) xs[j][t] = buf_ld16<ROW_AUX>(xr, lane_b, xso[t] + (ks + NS) * 1024);
             };
+            if constexpr (SD) {
+                // every K step in line, in the order of the loop below: the step's MFMAs, then the refill of its operand stage
+                static_assert(C0 && NKS % NS == 0, "the unrolled loop starts the accumulators in its first step");
+                static_for<(int)NKS>([&](auto ksc) {
+                    constexpr int KS = decltype(ksc)::value, j = KS % NS;
+                    mma(xs[j], ksc, full, std::bool_constant<KS == 0>{});
+                    if constexpr (KS + NS < (int)NKS) refill(j, (uint32_t)KS);
+                });
+            } else {
             uint32_t ks = 0;
             if constexpr (C0) {
                 const bool more = (uint32_t)NS < nks;       // wave-uniform
@@ -2103,6 +2187,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (NG == 4 && !QLDS) || (QLDS &&
             }
 #pragma unroll
             for (int j = 0; j < NS; ++j) mma(xs[j], ks + j, full, std::false_type{});
+            }
         };
         // !QLDS: both operands stream from global memory through THREE rotating register stages, so the
         // loads of K step s + 2 are issued before the MFMAs of step s (HBM latency is ~2 K steps of a
@@ -2555,9 +2640,14 @@ hipError_t launch_seed_threshold(const uint64_t *part_keys, uint32_t nq, uint32_
 }
 
 // dynamic LDS beyond 64 KB has to be allowed per kernel once
-template <int NG, int NW, int S, bool QLDS, int OP, bool PF = false, bool ONCE = false, int TS = 4, bool DEFP = false>
+template <int NG, int NW, int S, bool QLDS, int OP, bool PF = false, bool ONCE = false, int TS = 4, bool DEFP = false, int DIM = 0>
 static hipError_t launch_wide(const TileArgs &a, size_t lds, hipStream_t s) {
-    auto kern = wide_filter_kernel<NG, NW, S, QLDS, OP, PF, ONCE, TS, DEFP>;
+    // the row length compiled in: the two int8 instances of the flagship dispatch (k <= 64, exact evaluation in the kernel) at 768 dims
+    if constexpr (DIM == 0 && OP == OP_I8 && S == 1 && !DEFP && ((NG == 6 && NW == 4 && TS == 4) || (NG == 10 && NW == 8 && TS == 2))) {
+        if (a.static_dim && a.dim == 768) return launch_wide<NG, NW, S, QLDS, OP, PF, ONCE, TS, DEFP, 768>(a, lds, s);
+    }
+    if (DIM != 0 && a.dim != (uint32_t)DIM) return hipErrorInvalidValue;
+    auto kern = wide_filter_kernel<NG, NW, S, QLDS, OP, PF, ONCE, TS, DEFP, DIM>;
     if (a.cand_lb && !(S > 1 || DEFP)) return hipErrorInvalidValue;      // this instance would ignore the request
     if (a.rows_per_block / NW + 64u >= (1u << 23)) return hipErrorInvalidValue;       // queue entries: 23 bits of row offset per wave
     if (lds > 65536) {          // raise the kernel's dynamic-LDS ceiling to what this launch needs (static + dynamic <= 160 KB)
