@@ -587,6 +587,44 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// Up to `group_size` rows of each of the `k` nearest groups of `group_keys` among the rows of `part` whose key passes the
+    /// query's filter -- exact, nothing is probed; `group_size` 1 is the distinct call (`include/pqv.h`:
+    /// `pqv_topk_partition_grouped`).  `k * group_size <= 1024`.
+    pub fn topk_partition_grouped(&self, part: &KeyPartition, filter: &KeyFilter, group_keys: &RowKeys, mask: Option<&RowMask>,
+                                  queries: &[f32], dim: usize, k: NonZeroUsize, group_size: NonZeroUsize)
+                                  -> Result<Vec<Vec<GroupSearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        // (the arrays the descriptor points at live until the call has returned)
+        let (desc, _lims, _vals) = key_filter_desc(filter, nq)?;
+        let (k, m) = (k.get(), group_size.get());
+        let mut rows = vec![0u32; nq * k * m];
+        let mut dist = vec![0f32; nq * k * m];
+        let mut group = vec![0i64; nq * k];
+        let mut group_rows = vec![0u32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_partition_grouped(self.raw, part.raw, &desc, group_keys.raw, mask.map_or(ptr::null(), |x| x.raw as *const _),
+                                            queries.as_ptr(), nq as u32, dim as u32, k as u32, m as u32, sys::PQV_L2SQ_REF4, 1,
+                                            rows.as_mut_ptr(), dist.as_mut_ptr(), group.as_mut_ptr(), group_rows.as_mut_ptr(),
+                                            found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| {
+                (0..found[q] as usize)
+                    .map(|g| {
+                        let o = (q * k + g) * m;
+                        GroupSearchResult {
+                            key: group[q * k + g],
+                            hits: (0..group_rows[q * k + g] as usize)
+                                .map(|i| SearchResult { row_idx: rows[o + i], distance: dist[o + i] })
+                                .collect(),
+                        }
+                    })
+                    .collect()
+            })
+            .collect())
+    }
+
     /// Keep probing until `k` rows pass the filter (`include/pqv.h`: `pqv_topk_expand`): every query probes the fewest lists, at
     /// least `nprobe` and at most `max_nprobe`, whose passing rows number `k`, and gets what [`Searcher::topk_masked`] (`filter`
     /// `None`: `mask` is required) or [`Searcher::topk_filtered`] returns for that many lists.  Returns the hits and the lists

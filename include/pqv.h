@@ -775,12 +775,55 @@ int pqv_topk_expand_device(const pqv_searcher *searcher, const pqv_row_keys *key
  *                n_found, n_candidates and their device forms may be NULL.  The device form is asynchronous on hip_stream with no
  *                host synchronisation; for an unvalidated IN slice that query's result is unspecified and every access is in
  *                bounds, as pqv_topk_filtered_device documents.
- *   out of scope table searchers; range search, distinct and grouped over a partition; k > 1024; mutable partitions (after an
- *                append or a remove, make the new searcher's partition); the screened kernels on long runs; choosing between the
- *                IVF and the partition path automatically (pqv_key_partition_keys gives a planner the run lengths for that choice).
+ *   out of scope table searchers; range search over a partition (distinct and grouped: pqv_topk_partition_grouped below); k > 1024;
+ *                mutable partitions (after an append or a remove, make the new searcher's partition); the screened kernels on long
+ *                runs; choosing between the IVF and the partition path automatically (pqv_key_partition_keys gives a planner the run
+ *                lengths for that choice).
  * Errors, in this order (PQV_ERR_INVALID): "searcher must not be NULL", "key partition must not be NULL", "filter must not be
  * NULL", the descriptor checks of pqv_topk_filtered (host form), "k must be > 0", "key partition belongs to another searcher", "row
- * mask belongs to another searcher", then pqv_topk's own (query length, metric). */
+ * mask belongs to another searcher", then pqv_topk's own (query length, metric).
+ *
+ * pqv_topk_partition_grouped / pqv_topk_partition_grouped_device: "the k nearest documents of tenant T, group_size chunks each" --
+ * pqv_topk_grouped's result over pqv_topk_partition's candidates.  `group_keys` is a pqv_row_keys of this searcher (I32 or I64,
+ * optional validity): the group column.  group_size == 1 is the distinct call: one pass, outputs [nq, k]; there is no separate
+ * _distinct symbol, as pqv_topk_grouped has none for it either.
+ *   candidates   exactly pqv_topk_partition's sequence for `filter` (EQ and RANGE: one span; IN: up to PQV_KEY_SET_MAX spans in the
+ *                slice's ascending order); a candidate's position is its index in that sequence; n_candidates[q] is the sequence's
+ *                length, taken before the mask and the group validity.  Host filter arrays in the host form; device arrays read on
+ *                hip_stream in the device form, with pqv_topk_partition_device's unspecified-but-in-bounds rule for an unvalidated
+ *                IN slice.
+ *   considered   the candidates `mask` allows (NULL: all) AND whose group_keys value is valid, at their unmasked positions.  A row
+ *                that fails either test is never loaded; a NULL-group row belongs to no group.
+ *   result       as pqv_topk_grouped: let S be the considered rows sorted by (distance key, position).  Groups are compared in i64
+ *                and ranked by their first row in S; the first k groups are kept, each with its first min(group_size, rows it has)
+ *                rows in S order.  No heap replay, no tie flags: the host and the device form return the same thing.
+ *   outputs      as pqv_topk_grouped: row_idx / dist [nq, k, group_size], group_key [nq, k], group_rows [nq, k], n_found [nq] (the
+ *                groups found) and n_candidates [nq]; padding 0xFFFFFFFF / +inf / key 0 / count 0.  Everything but row_idx and
+ *                dist may be NULL.  sqrt_out and the cosine halving as in pqv_topk_partition.
+ *   metrics      PQV_L2SQ_REF4, PQV_L2SQ_SEQ, and PQV_COSINE through the cosine layout as pqv_topk_partition does it.  PQV_DOT:
+ *                PQV_ERR_UNSUPPORTED "PQV_DOT is not supported by keyed and distinct calls" (the distinct lists and folds carry
+ *                L2 keys).
+ *   equivalence  1. on S1 (above), with row keys made from the same two columns on S1: for PQV_KEY_EQ the call equals
+ *                pqv_topk_grouped_filtered_device on S1 with nprobe = 1 and max_candidates = 0, n_candidates excepted, bit for bit;
+ *                for RANGE and IN the same holds whenever no two considered rows of different filter keys tie in distance.
+ *                2. with every group value distinct and valid, slot i = 0 holds pqv_topk_partition_device's rows, distances and
+ *                n_found, and group_rows is 1 there.  3. group_size == 1 against group_size == m: the [.., 0] slots, group_key and
+ *                n_found agree.
+ *   exactness    with mask == NULL the answer is exact over ALL indexed rows whose filter key passes.  No searcher option changes a
+ *                result; partition_blocks fixes the blocks per query of both passes.
+ *   counts       queries advances by nq, once per call (not per pass); candidate_rows by the sum of n_candidates, once;
+ *                embeddings_fetched by the considered rows plus, for group_size > 1, the rows pass 2 evaluates: the considered rows
+ *                of the selected groups.  screened_pairs and screen_survivors do not move.
+ *   limits       k * group_size <= 1024 (the product taken in 64 bits) in both forms: PQV_ERR_UNSUPPORTED
+ *                "pqv_topk_partition_grouped takes k * group_size <= 1024"; there is no host fallback.  The device form is
+ *                asynchronous on hip_stream with no host synchronisation.
+ *   out of scope table searchers (pqv_key_partition_create refuses them); range search over a partition; PQV_DOT; max_nprobe (nothing
+ *                is probed); the path-taking builders; choosing between the IVF and the partition path automatically.
+ * Errors, in this order (PQV_ERR_INVALID), every NULL and zero check before a handle is dereferenced or a device used: "searcher
+ * must not be NULL", "key partition must not be NULL", "row keys must not be NULL", "filter must not be NULL" and the descriptor
+ * checks of pqv_topk_filtered (host form), "k must be > 0", "group_size must be > 0", "key partition belongs to another searcher",
+ * "row keys belong to another searcher", "row mask belongs to another searcher", then pqv_topk's own (metric, query length), then the
+ * two PQV_ERR_UNSUPPORTED texts above (PQV_DOT first). */
 typedef struct pqv_key_partition pqv_key_partition;
 int      pqv_key_partition_create(const pqv_searcher *searcher, const pqv_column *column, void *hip_stream, pqv_key_partition **out);
 uint64_t pqv_key_partition_rows(const pqv_key_partition *part);
@@ -794,6 +837,15 @@ int pqv_topk_partition(const pqv_searcher *searcher, const pqv_key_partition *pa
 int pqv_topk_partition_device(const pqv_searcher *searcher, const pqv_key_partition *part, const pqv_key_filter *filter,
                               const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
                               void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates, void *hip_stream);
+int pqv_topk_partition_grouped(const pqv_searcher *searcher, const pqv_key_partition *part, const pqv_key_filter *filter,
+                               const pqv_row_keys *group_keys, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                               uint32_t query_len, uint32_t k, uint32_t group_size, int metric, int sqrt_out,
+                               uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows,
+                               uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_partition_grouped_device(const pqv_searcher *searcher, const pqv_key_partition *part, const pqv_key_filter *filter,
+                                      const pqv_row_keys *group_keys, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                      uint32_t k, uint32_t group_size, int metric, int sqrt_out, void *d_row_idx, void *d_dist,
+                                      void *d_group_key, void *d_group_rows, void *d_n_found, void *d_n_candidates, void *hip_stream);
 
 /* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
  * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.

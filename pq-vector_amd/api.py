@@ -1078,6 +1078,65 @@ class Searcher:
                                                     vp(d_queries), nq, k, metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
                                                     vp(d_n_found or None), vp(d_n_candidates or None), vp(stream or None)))
 
+    def topk_partition_grouped(self, queries, k, group_size, part, keys, query_keys=None, query_key_ranges=None, query_key_sets=None,
+                               mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """Exact grouped top-k over the rows of `part` whose key passes the query's filter (the keywords of topk_partition): up
+        to group_size rows of each of the k nearest groups of `keys` -- a RowKeys of this searcher, or the name of an attached
+        column -- within mask if one is given; nothing is probed (pqv.h: pqv_topk_partition_grouped).  Returns (row_idx
+        [nq,k,group_size] u32, dist [nq,k,group_size] f32, group_keys [nq,k] i64, group_rows [nq,k] u32, n_found [nq],
+        n_candidates [nq]), laid out and padded as topk_grouped's."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        ph, f, _alive = _partition_filter(part, query_keys, query_key_ranges, query_key_sets, nq)
+        shape = (nq, max(k, 1), max(group_size, 1))
+        rows = np.full(shape, 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full(shape, np.inf, dtype=np.float32)
+        grp = np.zeros(shape[:2], dtype=np.int64)
+        grows = np.zeros(shape[:2], dtype=np.uint32)
+        nf = np.zeros(nq, dtype=np.uint32)
+        nc = np.zeros(nq, dtype=np.uint64)
+        owned = isinstance(keys, str)
+        if owned:
+            keys = self.row_keys(keys)
+        try:
+            kh = _group_handle(keys)
+            _check(_ffi.lib().pqv_topk_partition_grouped(self._h, ph, C.byref(f), kh,
+                                                         _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq,
+                                                         qlen, k, group_size, metric, 1 if sqrt_out else 0, rows.ctypes.data_as(u32p),
+                                                         dist.ctypes.data_as(f32p), grp.ctypes.data_as(_ffi.i64p), grows.ctypes.data_as(u32p),
+                                                         nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p)))
+        finally:
+            if owned:
+                keys.close()
+        return rows, dist, grp, grows, nf, nc
+
+    def topk_partition_distinct(self, queries, k, part, keys, query_keys=None, query_key_ranges=None, query_key_sets=None, mask=None,
+                                metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """Exact distinct top-k over a partition: topk_partition_grouped with group_size = 1.  Returns (row_idx [nq,k] u32, dist
+        [nq,k] f32, group_keys [nq,k] i64, n_found [nq], n_candidates [nq])."""
+        rows, dist, grp, _grows, nf, nc = self.topk_partition_grouped(queries, k, 1, part, keys, query_keys=query_keys,
+                                                                      query_key_ranges=query_key_ranges, query_key_sets=query_key_sets,
+                                                                      mask=mask, metric=metric, sqrt_out=sqrt_out)
+        return rows.reshape(rows.shape[:2]), dist.reshape(dist.shape[:2]), grp, nf, nc
+
+    def topk_partition_grouped_device(self, d_queries, nq, k, group_size, part, keys, d_row_idx, d_dist, d_group_key=0, d_group_rows=0,
+                                      d_n_found=0, d_n_candidates=0, query_keys=None, query_key_ranges=None, query_key_sets=None,
+                                      mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of topk_partition_grouped, shaped like topk_partition_device plus the two group outputs: d_row_idx
+        u32 / d_dist f32 [nq, k, group_size], d_group_key i64 / d_group_rows u32 [nq, k], d_n_found u32 / d_n_candidates u64 [nq];
+        the last four are optional.  Asynchronous on `stream`; the query keywords take device pointers read on `stream` inside
+        the enqueued work.  `keys` (a RowKeys), `part` and `mask` must stay alive until the work has completed (pqv.h:
+        pqv_topk_partition_grouped_device)."""
+        ph, f, _alive = _partition_filter(part, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        kh = _group_handle(keys)
+        _check(_ffi.lib().pqv_topk_partition_grouped_device(self._h, ph, C.byref(f), kh,
+                                                            _mask_handle(self, mask) if mask is not None else None, vp(d_queries), nq, k,
+                                                            group_size, metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
+                                                            vp(d_group_key or None), vp(d_group_rows or None), vp(d_n_found or None),
+                                                            vp(d_n_candidates or None), vp(stream or None)))
+
     def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None, keys=None,
              query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=None):
         """Batched topk(); returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq], n_candidates [nq]).

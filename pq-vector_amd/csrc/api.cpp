@@ -6455,6 +6455,228 @@ extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition
     });
 }
 
+// ---- distinct / grouped top-k over a key partition (pqv.h: pqv_topk_partition_grouped) ------------------------------------------
+// The checks of both forms, in the contract's order: every NULL and zero check before a handle is read.  query_len: the host form's.
+static int partition_group_checks(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_keys *gk,
+                                  const pqv_row_mask *mask, uint32_t nq, uint32_t k, uint32_t group_size, int metric, bool host,
+                                  uint32_t query_len) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!part) return fail(PQV_ERR_INVALID, "key partition must not be NULL");
+    if (!gk) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
+    if (int rc = filter_descriptor_checks(f, nq, host)) return rc;
+    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (group_size == 0) return fail(PQV_ERR_INVALID, "group_size must be > 0");
+    if (part->owner != s || part->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "key partition belongs to another searcher");
+    if (gk->owner != s || gk->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
+    if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+    if (int rc = validate_topk(s, k, 1, metric)) return rc;
+    if (host && query_len != s->dim)
+        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) + ", got " + std::to_string(query_len));
+    if (metric == PQV_DOT) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
+    if (static_cast<uint64_t>(k) * group_size > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_partition_grouped takes k * group_size <= 1024");
+    return PQV_OK;
+}
+// Enqueue both passes for the queries [0, nq) on `stream`, in enqueue_partition's pieces: the span kernel (once per piece), the
+// distinct stream and its fold, then for m > 1 the group set, the grouped stream and its fold -- or, for m == 1, the rows-per-group
+// fill where d_group_rows is asked for.  One B for both passes; every buffer of a piece is sized before its first kernel (the partial
+// lists of pass 2 take over those of pass 1).  `s`: the searcher whose rows are read; a / b: the descriptor's DEVICE arrays.
+static int enqueue_partition_grouped(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, uint32_t kind, const void *d_a,
+                                     const void *d_b, const pqv_row_keys *gk, const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k,
+                                     uint32_t m, int metric, int sqrt_out, uint32_t *d_row_idx, float *d_dist, int64_t *d_group_key,
+                                     uint32_t *d_group_rows, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+    using namespace pqv;
+    const uint32_t piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
+    const uint32_t km = k * m;                                              // (<= 1024: partition_group_checks)
+    const bool two_pass = m > 1;
+    const uint32_t B = partition_blocks(s, piece, km, part->m);
+    const uint32_t n_part = B * waves_per_block();
+    const size_t n_lists = static_cast<size_t>(piece) * n_part;
+    const size_t span_slots = static_cast<size_t>(piece) * (kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u);
+    HIP_TRY(sc.s_pt_beg.ensure(span_slots * sizeof(uint32_t)));
+    if (kind == PQV_KEY_IN) {
+        HIP_TRY(sc.s_pt_end.ensure(span_slots * sizeof(uint32_t)));
+        HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+    }
+    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_part_keys.ensure((n_lists * km + 4) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_part_vals.ensure((n_lists * km + 4) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_part_grp.ensure((n_lists * k + 4) * sizeof(int64_t)));
+    if (two_pass) {
+        HIP_TRY(sc.s_gpart_slot.ensure((n_lists * km + 4) * sizeof(uint32_t)));
+        HIP_TRY(sc.s_gpart_cnt.ensure((n_lists + 4) * sizeof(uint32_t)));
+        HIP_TRY(sc.s_g1_rows.ensure(static_cast<size_t>(piece) * k * sizeof(uint32_t)));
+        HIP_TRY(sc.s_g1_dist.ensure(static_cast<size_t>(piece) * k * sizeof(float)));
+        HIP_TRY(sc.s_gset_keys.ensure(static_cast<size_t>(piece) * k * sizeof(int64_t)));
+        HIP_TRY(sc.s_gset_slot.ensure(static_cast<size_t>(piece) * k * sizeof(uint32_t)));
+        if (!d_group_key) HIP_TRY(sc.s_g1_keys.ensure(static_cast<size_t>(piece) * k * sizeof(int64_t)));
+    }
+    const bool need_found = two_pass || d_group_rows;                       // (read by the group set / the rows-per-group fill)
+    if (need_found && !d_n_found) HIP_TRY(sc.s_g1_nfound.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+    if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
+    for (uint32_t q0 = 0; q0 < nq; q0 += piece) {
+        const uint32_t b = std::min<uint32_t>(piece, nq - q0);
+        const float *dq = d_queries + static_cast<size_t>(q0) * s->dim;
+        if (s->sdim != s->dim) {      // (the stored rows are zero-padded: the queries that meet them too)
+            HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), stream));
+            dq = sc.s_qpad.as<float>();
+        }
+        // the piece's outputs: keys, counts and n_found at q0 * k / q0, rows and distances at q0 * k * m
+        uint32_t *o_rows = d_row_idx + static_cast<size_t>(q0) * km;
+        float *o_dist = d_dist + static_cast<size_t>(q0) * km;
+        int64_t *o_keys = d_group_key ? d_group_key + static_cast<size_t>(q0) * k : two_pass ? sc.s_g1_keys.as<int64_t>() : nullptr;
+        uint32_t *o_found = d_n_found ? d_n_found + q0 : need_found ? sc.s_g1_nfound.as<uint32_t>() : nullptr;
+        uint32_t *o_grows = d_group_rows ? d_group_rows + static_cast<size_t>(q0) * k : nullptr;
+
+        PartitionSpanArgs sp{};
+        sp.keys = part->d_keys.as<int64_t>(); sp.key_off = part->d_off.as<uint64_t>(); sp.n_keys = part->n_keys;
+        sp.nq = b; sp.kind = kind;
+        // (every kind's a is indexed by query -- an IN filter's lims hold offsets into ALL of b, so a piece takes a + q0 and b as it is)
+        sp.a = static_cast<const char *>(d_a) + static_cast<size_t>(q0) * 8;
+        sp.b = kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + static_cast<size_t>(q0) * 8) : d_b;
+        sp.span_beg = sc.s_pt_beg.as<uint32_t>(); sp.span_end = sc.s_pt_end.as<uint32_t>(); sp.n_span = sc.s_pt_nspan.as<uint32_t>();
+        sp.n_cand = sc.s_ncand.as<uint64_t>(); sp.n_cand_out = d_n_cand ? d_n_cand + q0 : nullptr;
+        sp.stats = s->d_stats.as<unsigned long long>();
+        HIP_TRY(launch_partition_span(sp, stream));
+
+        StreamArgs ra{};
+        ra.mat = s->d_mat; ra.row_of = s->d_row_of;
+        ra.queries = dq; ra.nq = b; ra.nprobe = 1; ra.dim = s->sdim; ra.k = k;
+        ra.rows_per_block = 256; ra.blocks_per_list = B; ra.max_pos = ~0ull; ra.metric = metric;
+        ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
+        PartitionArgs pa{};
+        pa.pos = part->d_pos.as<uint32_t>(); pa.span_beg = sp.span_beg; pa.span_end = sp.span_end; pa.n_span = sp.n_span;
+        pa.n_cand = sp.n_cand; pa.kind = kind; pa.bits = bits; pa.stats = s->d_stats.as<unsigned long long>();
+        DistinctArgs da{};
+        da.key_pos = gk->d_key_pos.p; da.valid_pos = gk->valid_image(); da.elem_size = gk->elem_size();
+        da.part_grp = sc.s_part_grp.as<int64_t>();
+        HIP_TRY(launch_partition_distinct_stream(ra, pa, da, stream));
+
+        DistinctMergeArgs dm{};
+        dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = da.part_grp;
+        dm.nq = b; dm.n_part = n_part; dm.k = k; dm.elem_size = da.elem_size;
+        dm.ids = s->d_final_ids; dm.row_idx = two_pass ? sc.s_g1_rows.as<uint32_t>() : o_rows; dm.dist = two_pass ? sc.s_g1_dist.as<float>() : o_dist;
+        dm.group_key = o_keys; dm.n_found = o_found; dm.sqrt_out = sqrt_out;
+        HIP_TRY(launch_distinct_merge(dm, stream));
+        s->counters.kernel_launches += 3;
+        if (two_pass) {
+            HIP_TRY(launch_group_set(o_keys, o_found, b, k, sc.s_gset_keys.as<int64_t>(), sc.s_gset_slot.as<uint32_t>(), stream));
+            GroupedArgs ga{};
+            ga.key_pos = da.key_pos; ga.valid_pos = da.valid_pos; ga.elem_size = da.elem_size;
+            ga.set_keys = sc.s_gset_keys.as<int64_t>(); ga.set_slot = sc.s_gset_slot.as<uint32_t>(); ga.n_found = o_found;
+            ga.k = k; ga.group_size = m; ga.km = km;
+            ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
+            ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
+            HIP_TRY(launch_partition_grouped_stream(ra, pa, ga, stream));
+            GroupedMergeArgs gma{};
+            gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
+            gma.nq = b; gma.n_part = n_part; gma.k = k; gma.group_size = m; gma.km = km;
+            gma.ids = s->d_final_ids; gma.row_idx = o_rows; gma.dist = o_dist; gma.group_rows = o_grows; gma.sqrt_out = sqrt_out;
+            HIP_TRY(launch_grouped_merge(gma, stream));
+            s->counters.kernel_launches += 3;
+        } else if (o_grows) {
+            HIP_TRY(launch_group_rows_fill(o_found, b, k, o_grows, stream));
+            s->counters.kernel_launches += 1;
+        }
+    }
+    return PQV_OK;
+}
+// the device form behind its checks; PQV_COSINE as topk_partition_device_impl takes it, the lock order included
+static int topk_partition_grouped_device_impl(const pqv_searcher *s, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
+                                              const pqv_row_keys *gk, const pqv_row_mask *mask, const float *d_queries, uint32_t nq, uint32_t k,
+                                              uint32_t m, int metric, int sqrt_out, uint32_t *d_row_idx, float *d_dist, int64_t *d_group_key,
+                                              uint32_t *d_group_rows, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+    std::lock_guard<std::mutex> lock(s->mu);
+    Lane lane;
+    if (metric == PQV_COSINE) {
+        if (int rc = cosine_queries_device(s, d_queries, nq, stream, lane)) return rc;
+        const pqv_searcher *cs = s->cos.get();
+        std::lock_guard<std::mutex> cos_lock(cs->mu);
+        Lane cos_lane;
+        if (int rc = cos_lane.acquire(cs, stream)) return rc;
+        if (int rc = enqueue_partition_grouped(cs, *cos_lane, part, kind, d_a, d_b, gk, bits, lane->s_qcos.as<float>(), nq, k, m, PQV_L2SQ_REF4, 2,
+                                               d_row_idx, d_dist, d_group_key, d_group_rows, d_n_found, d_n_cand, stream))
+            return rc;
+        cs->counters.queries += nq;
+        if (int rc = cos_lane.release()) return rc;
+        return lane.release();
+    }
+    if (int rc = lane.acquire(s, stream)) return rc;
+    if (int rc = enqueue_partition_grouped(s, *lane, part, kind, d_a, d_b, gk, bits, d_queries, nq, k, m, metric, sqrt_out, d_row_idx, d_dist,
+                                           d_group_key, d_group_rows, d_n_found, d_n_cand, stream))
+        return rc;
+    s->counters.queries += nq;
+    return lane.release();
+}
+extern "C" int pqv_topk_partition_grouped_device(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
+                                                 const pqv_row_keys *group_keys, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                                                 uint32_t k, uint32_t group_size, int metric, int sqrt_out, void *d_row_idx, void *d_dist,
+                                                 void *d_group_key, void *d_group_rows, void *d_n_found, void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        if (int rc = partition_group_checks(s, part, filter, group_keys, mask, nq, k, group_size, metric, false, 0)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+        return topk_partition_grouped_device_impl(s, part, filter->kind, filter->a, filter->b, group_keys, mask, static_cast<const float *>(d_queries),
+                                                  nq, k, group_size, metric, sqrt_out ? 1 : 0, static_cast<uint32_t *>(d_row_idx),
+                                                  static_cast<float *>(d_dist), static_cast<int64_t *>(d_group_key),
+                                                  static_cast<uint32_t *>(d_group_rows), static_cast<uint32_t *>(d_n_found),
+                                                  static_cast<uint64_t *>(d_n_candidates), stream);
+    });
+}
+// The host form: topk_partition_host_impl's sub-batches with the group outputs beside the rows; the sub-batch size is bounded from
+// the per-query scratch of BOTH passes (20 B per entry of pass 1's lists, 16 B per entry of k * m and a count in pass 2's).
+static int topk_partition_grouped_host_impl(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_keys *gk,
+                                            const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t k, uint32_t m, int metric,
+                                            int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows,
+                                            uint32_t *n_found, uint64_t *n_candidates) {
+    std::vector<float> nq_host;
+    if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
+    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+    std::lock_guard<std::mutex> lock(s->mu);
+    Lane lane;
+    if (int rc = lane.acquire(s, s->stream)) return rc;
+    Scratch &sc = *lane;
+    const uint64_t km = static_cast<uint64_t>(k) * m;
+    const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), static_cast<uint32_t>(km), part->m);
+    const uint64_t per_query = static_cast<uint64_t>(B) * 4 * std::max<uint64_t>(std::max<uint64_t>(k * 20ull, km * 12), m > 1 ? km * 16 + 4 : 0) +
+                               static_cast<uint64_t>(s->sdim) * 8 + 32ull * k + 8 * km + 8 * PQV_KEY_SET_MAX + 16;
+    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
+    SearchRequest rq{};      // the descriptor's host arrays, for the sub-batches' slices
+    rq.rows.kind = f->kind;
+    if (f->kind == PQV_KEY_EQ) rq.rows.h_qkeys = static_cast<const int64_t *>(f->a);
+    else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
+    std::vector<BatchOut> outs = {{&sc.s_rows, km * sizeof(uint32_t), row_idx}, {&sc.s_dist, km * sizeof(float), dist},
+                                  {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates},
+                                  {&sc.s_grp_out, k * sizeof(int64_t), group_key}};
+    if (group_rows) outs.push_back({&sc.s_grows_out, k * sizeof(uint32_t), group_rows});
+    if (int rc = host_batches(
+            s, sc, queries, nq, batch, &rq, nullptr, outs,
+            [&](uint32_t b, SearchRequest *brq) {
+                return enqueue_partition_grouped(s, sc, part, f->kind, brq->d_filter_a(), brq->d_filter_b(), gk, bits, sc.s_queries.as<float>(), b, k, m,
+                                                 metric, sqrt_out, sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_grp_out.as<int64_t>(),
+                                                 group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr, sc.s_nfound.as<uint32_t>(),
+                                                 sc.s_out.as<uint64_t>(), s->stream);
+            },
+            [](uint32_t, uint32_t) { return static_cast<int>(PQV_OK); }))      // (no host step)
+        return rc;
+    return lane.release();
+}
+extern "C" int pqv_topk_partition_grouped(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
+                                          const pqv_row_keys *group_keys, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                          uint32_t query_len, uint32_t k, uint32_t group_size, int metric, int sqrt_out, uint32_t *row_idx,
+                                          float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        if (int rc = partition_group_checks(s, part, filter, group_keys, mask, nq, k, group_size, metric, true, query_len)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        return topk_partition_grouped_host_impl(s, part, filter, group_keys, mask, queries, nq, k, group_size, metric, sqrt_out ? 1 : 0, row_idx,
+                                                dist, group_key, group_rows, n_found, n_candidates);
+    });
+}
+
 // ---- distinct top-k (pqv.h: pqv_topk_distinct) -----------------------------------------------------------------------------
 // the checks both entry points make before anything else: NULL handles first, nothing dereferenced before them
 static int distinct_view(const pqv_searcher *s, const pqv_row_keys *keys, const pqv_row_mask *mask, uint32_t k, SearchRequest &mv) {

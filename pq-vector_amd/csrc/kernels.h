@@ -186,6 +186,18 @@ struct PartitionArgs {
     unsigned long long *stats;      // as MaskedArgs::stats
 };
 hipError_t launch_partition_stream(const StreamArgs &a, const PartitionArgs &pa, hipStream_t s);
+// Distinct / grouped top-k over a partition (kernels_partition_group.hip; pqv.h: pqv_topk_partition_grouped): the two passes of
+// launch_distinct_stream / launch_grouped_stream over launch_partition_stream's grid and sequence walk, PQV_DOT excepted.  A
+// position is walked iff pa.bits allows it AND the group column's valid_pos does (both gathered per list position; either may be
+// nullptr); keys are l2_key(sum, sequence position).  Pass 1 (partition_distinct_stream_kernel) writes a.part_keys / a.part_vals /
+// da.part_grp [nq][B * 4][k] for launch_distinct_merge with n_part = B * 4.  Pass 2 (partition_grouped_stream_kernel; behind
+// launch_group_set) walks the members of the query's set only and writes ga.part_keys / part_vals / part_slot [nq][B * 4][km] and
+// ga.part_cnt [nq][B * 4] for launch_grouped_merge.  The mask and the statistics block are pa's: da / ga .bits, .stats, .n_cand
+// and .rank_limit are not read.
+struct DistinctArgs;
+struct GroupedArgs;
+hipError_t launch_partition_distinct_stream(const StreamArgs &a, const PartitionArgs &pa, const DistinctArgs &da, hipStream_t s);
+hipError_t launch_partition_grouped_stream(const StreamArgs &a, const PartitionArgs &pa, const GroupedArgs &ga, hipStream_t s);
 
 // ---- expanding filtered top-k (kernels_expand.hip; pqv.h: pqv_topk_expand) ------------------------------------------------
 // filter_count_kernel: cnt[q * P + j] = the positions of list probe[q * P + j] that pass the call's filter -- the set bits of

@@ -238,7 +238,8 @@ hipError_t launch_partition_span(const PartitionSpanArgs &a, hipStream_t s) {
 //
 // grid = (B, nq); block = 256 threads = 4 independent waves with masked_stream_kernel's tile area and nothing beside it.  The
 // query's sequence has n_cand[q] positions, known on the device only, so the grid cannot follow it: wave w of block x takes the
-// 64-position windows (turn * B + x) * 4 + w for turn = 0, 1, ... while they begin inside the sequence.  A window's position
+// 64-position windows (turn * B + x) * 4 + w for turn = 0, 1, ... while they begin inside the sequence (PartitionSeq,
+// stream_walk.hpp: the distinct / grouped passes of kernels_partition_group.hip walk the same way).  A window's position
 // `seq` is mapped to its partition entry -- one span (EQ / RANGE): span_beg[q] + seq; IN: the first span whose inclusive prefix
 // sum exceeds seq, found by a halving search over the query's n_span[q] <= KEY_SET_MAX sums (read through the caches: no LDS
 // beside the tile, the occupancy of the masked twin) -- and the entry's list position is loaded: one coalesced 256-byte read per
@@ -259,27 +260,8 @@ __global__ __launch_bounds__(256) void partition_stream_kernel(const StreamArgs 
     float *lds = lds_all + wave * tile_words<CG, SEQ>();
 
     const uint32_t q = blockIdx.y;
-    const uint32_t total = (uint32_t)uniform_word(pa.n_cand + q);       // (saturated below 2^32 by the span kernel)
-    const bool in_set = pa.kind == 2;
-    const uint32_t n_span = in_set ? uniform_word(pa.n_span + q) : 1u;
-    const uint32_t *sbeg = pa.span_beg + (in_set ? (uint64_t)q * KEY_SET_MAX : (uint64_t)q);
-    const uint32_t *send = in_set ? pa.span_end + (uint64_t)q * KEY_SET_MAX : nullptr;
-    const uint32_t beg0 = total ? uniform_word(sbeg) : 0u;
-
-    // the list position of sequence position seq < total
-    auto entry = [&](uint32_t seq) -> uint32_t {
-        uint32_t at = beg0 + seq;
-        if (in_set) {
-            uint32_t i = 0;
-            for (uint32_t span = n_span; span > 1;) {       // (wave-uniform trip count; i + half - 1 < n_span)
-                const uint32_t half = span >> 1;
-                if (send[i + half - 1] <= seq) i += half;
-                span -= half;
-            }
-            at = sbeg[i] + (seq - (i ? send[i - 1] : 0u));
-        }
-        return pa.pos[at];
-    };
+    PartitionSeq ps;
+    ps.setup(pa, q);
 
     const float *qv = a.queries + (uint64_t)q * a.dim;
     WaveTopk<S> tk;
@@ -300,12 +282,7 @@ __global__ __launch_bounds__(256) void partition_stream_kernel(const StreamArgs 
 
     WindowQueue<true> wq;
     wq.cq = reinterpret_cast<uint32_t *>(lds);
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wave) * 64; w0 < total; w0 += stride) {
-        const uint32_t nvalid = total - w0 < 64 ? (uint32_t)(total - w0) : 64u;
-        const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
-        const uint32_t seq = (uint32_t)w0 + lrow;
-        const uint32_t lpos = entry(seq);
+    ps.windows(ps.total, wave, lane, [&](uint64_t w0, uint32_t nvalid, uint32_t seq, uint32_t lpos) {
         if constexpr (!MASKED) {
             tile(lpos, seq, nvalid);
         } else {
@@ -313,7 +290,7 @@ __global__ __launch_bounds__(256) void partition_stream_kernel(const StreamArgs 
             const QueueTile t = wq.push(__ballot(on), w0, lpos, lane);
             if (t.nvalid) tile(t.my_x, t.my_r, t.nvalid);
         }
-    }
+    });
     if constexpr (MASKED) {
         const QueueTile t = wq.flush(lane);
         if (t.nvalid) {

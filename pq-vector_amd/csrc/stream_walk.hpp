@@ -6,6 +6,7 @@
 //   chain_tile / l2_tile / dot_tile   the distance chain of one 64-row tile, in the reference's order of operations
 //   WalkRange / walk_range            the prologue: probed list, candidate base, cap, the wave's position range
 //   WindowQueue / filtered_walk       the walk over 64-position windows: compaction into a queue, a tile per 64 queued rows
+//   PartitionSeq                      a key partition's candidate sequence: position -> list position, a wave's windows
 //   KeyTest                           a query's key test (EQ / RANGE / IN): setup once per block, one window per call
 //   GroupSet                          the k groups of a grouped call's pass 2: staged in LDS, membership and slot per key
 //   distinct_tile / grouped_tile ...  what a distinct / grouped kernel shares with its filtered twin: images, tile, list write-out
@@ -299,6 +300,85 @@ __device__ __forceinline__ uint32_t filtered_walk(uint64_t lbeg, uint64_t r0, ui
     }
     return n_eval;
 }
+
+// ------------------------------------------------------------------------------------
+// A key partition's candidate sequence (kernels_partition.hip, kernels_partition_group.hip; launch_partition_span's outputs): query
+// q's sequence has `total` positions, known on the device only.  entry(seq) maps a position to its partition entry -- one span (EQ /
+// RANGE): span_beg[q] + seq; IN: the first span whose inclusive prefix sum exceeds seq, found by a halving search over the query's
+// n_span[q] <= KEY_SET_MAX sums (read through the caches: no LDS beside the tile) -- and loads the entry's list position.
+// windows(wave, lane, f): wave w of block x takes the 64-position windows (turn * gridDim.x + x) * 4 + w for turn = 0, 1, ... while
+// they begin below `limit`; f(w0, nvalid, seq, lpos) gets the window's first position, its positions inside the sequence, and lane
+// l's sequence position and list position, both clamped to the window's last one.
+// ------------------------------------------------------------------------------------
+struct PartitionSeq {
+    uint32_t total, n_span, beg0;
+    bool in_set;
+    const uint32_t *sbeg, *send, *pos;
+
+    __device__ __forceinline__ void setup(const PartitionArgs &pa, uint32_t q) {
+        total = (uint32_t)uniform_word(pa.n_cand + q);       // (saturated below 2^32 by the span kernel)
+        in_set = pa.kind == 2;
+        n_span = in_set ? uniform_word(pa.n_span + q) : 1u;
+        sbeg = pa.span_beg + (in_set ? (uint64_t)q * KEY_SET_MAX : (uint64_t)q);
+        send = in_set ? pa.span_end + (uint64_t)q * KEY_SET_MAX : nullptr;
+        beg0 = total ? uniform_word(sbeg) : 0u;
+        pos = pa.pos;
+    }
+    // the list position of sequence position seq < total
+    __device__ __forceinline__ uint32_t entry(uint32_t seq) const {
+        uint32_t at = beg0 + seq;
+        if (in_set) {
+            uint32_t i = 0;
+            for (uint32_t span = n_span; span > 1;) {       // (wave-uniform trip count; i + half - 1 < n_span)
+                const uint32_t half = span >> 1;
+                if (send[i + half - 1] <= seq) i += half;
+                span -= half;
+            }
+            at = sbeg[i] + (seq - (i ? send[i - 1] : 0u));
+        }
+        return pos[at];
+    }
+    template <class F>
+    __device__ __forceinline__ void windows(uint32_t limit, int wave, int lane, F &&f) const {
+        const uint64_t stride = (uint64_t)gridDim.x * 256;
+        for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wave) * 64; w0 < limit; w0 += stride) {
+            const uint32_t nvalid = limit - w0 < 64 ? (uint32_t)(limit - w0) : 64u;
+            const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
+            const uint32_t seq = (uint32_t)w0 + lrow;
+            f(w0, nvalid, seq, entry(seq));
+        }
+    }
+    // The same windows under a per-position test: bit(lpos) of the window's positions is balloted and the set ones are compacted
+    // through a WindowQueue with lpos as payload; tile(lpos, seq, nvalid) runs whenever 64 are queued and once more behind the
+    // wave's last window (ONE call site, as in filtered_walk: the chain and the list's offer are instantiated once), so a position
+    // that fails the test is never loaded.  The lanes behind a last tile's end follow its last entry, payload included.
+    template <class B, class T>
+    __device__ __forceinline__ void filtered_windows(uint32_t limit, float *lds, int wave, int lane, B &&bit, T &&tile) const {
+        WindowQueue<true> wq;
+        wq.cq = reinterpret_cast<uint32_t *>(lds);
+        const uint64_t stride = (uint64_t)gridDim.x * 256;
+        for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wave) * 64;; w0 += stride) {
+            const bool last = w0 >= limit;
+            QueueTile t;
+            if (!last) {
+                const uint32_t nvalid = limit - w0 < 64 ? (uint32_t)(limit - w0) : 64u;
+                const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
+                const uint32_t lpos = entry((uint32_t)w0 + lrow);
+                const bool on = (uint32_t)lane < nvalid && bit(lpos);
+                t = wq.push(__ballot(on), w0, lpos, lane);
+            } else {
+                t = wq.flush(lane);
+            }
+            if (t.nvalid) {
+                const uint32_t lp = (uint32_t)__shfl((int)t.my_x, (int)((uint32_t)lane < t.nvalid ? (uint32_t)lane : t.nvalid - 1), 64);
+                tile(lp, t.my_r, t.nvalid);
+            }
+            if (last) break;
+        }
+    }
+};
+// bit p of a position image (a mask's or a key column's validity): a gathered 8-byte load; nullptr: set
+__device__ __forceinline__ bool image_bit(const uint64_t *img, uint32_t p) { return !img || ((img[p >> 6] >> (p & 63u)) & 1ull); }
 
 // ------------------------------------------------------------------------------------
 // The per-query key test (pqv.h: pqv_key_filter).  KIND 0 (PQV_KEY_EQ): key == lo.  KIND 1 (PQV_KEY_RANGE): lo <= key && key <=
