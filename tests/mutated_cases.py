@@ -38,7 +38,7 @@ import mask_ref
 import range_oracle
 import remove_ref
 from key_filter_ref import EQ, IN, RANGE
-from range_oracle import REF4, l2_chain
+from range_oracle import REF4, SEQ, l2_chain
 
 EMPTY = 0xFFFFFFFF
 K, NPROBE, M = 10, 4, 3
@@ -58,6 +58,14 @@ SHAPES = {
     # every depth the modes use (1, 2, 4 and max_nprobe) is <= kc / 4: the screened centroid probe is eligible in every call, the
     # expanding ones included (tests/test_gpu_probe_screen_modes.py; not one of CASES)
     "probe32": dict(dim=64, kc=32, n0=12288, n1=16384, n2=18432, integer=False, nprobe_f=2, max_nprobe=8, mid_f=0.004, seed=66),
+    # the workload's row length, and the cases tests/far_rows_cases.py relocates onto rows beyond 2^31 / 2^32 bytes and elements of a
+    # 16 GiB corpus (tests/test_gpu_far_rows.py; not among CASES): a multiple of 64 dims and a mean list of >= 192 rows in every
+    # state -- the images-only layout --, the full mode set; far768i: the same sizes with distances that tie.  (radius_cuts_all:
+    # pick_radius)
+    "far768": dict(dim=768, kc=8, n0=3072, n1=4096, n2=4608, integer=False, nprobe_f=1, max_nprobe=4, mid_f=0.012, seed=768,
+                   radius_cuts_all=False),
+    "far768i": dict(dim=768, kc=8, n0=3072, n1=4096, n2=4608, integer=True, nprobe_f=1, max_nprobe=4, mid_f=0.012, seed=769,
+                    radius_cuts_all=False),
 }
 CASES = ["screened", "exact30", "padded72", "int8_256", "ties"]          # what test_gpu_mutated_search.py / _table.py run
 N_MID, N_TINY, TINY_ROWS = 8, 4, 6
@@ -102,6 +110,7 @@ class Case:
         self.name = name
         self.dim, self.kc, self.n0, self.n1, self.n2 = sh["dim"], sh["kc"], sh["n0"], sh["n1"], sh["n2"]
         self.nprobe_f, self.max_nprobe = sh["nprobe_f"], sh["max_nprobe"]
+        self.integer = sh["integer"]         # small integers: distances tie, and every chain of partial sums is exact
         rng = np.random.default_rng(sh["seed"])
         draw = (lambda n: rng.integers(0, 3, (n, self.dim)).astype(np.float32)) if sh["integer"] else \
                (lambda n: rng.random((n, self.dim), dtype=np.float32))
@@ -239,11 +248,13 @@ def _of(a, q, n):
     return a[q] if a.ndim == 2 else a
 
 
-def pick_radius(lo_hi):
+def pick_radius(lo_hi, cuts_all=True):
     """a radius with hits for every query that cuts candidates for every query: between the largest per-query minimum and the
-    smallest per-query maximum of the candidate distances"""
+    smallest per-query maximum of the candidate distances.  cuts_all False (768 uniform dims: distances concentrate, every row is
+    nearer to query 0, a centroid, than any row is to a uniform query, and no such radius exists): the same midpoint, which then
+    leaves query 0 every candidate, the uniform queries none and the queries beside a corpus row some"""
     lo, hi = max(x[0] for x in lo_hi), min(x[1] for x in lo_hi)
-    assert lo < hi, (lo, hi)
+    assert lo < hi or not cuts_all, (lo, hi)
     return float(np.float32((np.float64(lo) + np.float64(hi)) / 2))
 
 
@@ -267,7 +278,8 @@ def radius_for(oracle, model, sp, Q):
     d = candidate_distances(oracle, model, sp, Q)
     if sp["metric"] == "l2":
         d = [np.sqrt(x) for x in d]
-    return pick_radius([(float(x.min()), float(x.max())) for x in d if len(x)])          # (nprobe 1 on the emptied list: no candidates)
+    return pick_radius([(float(x.min()), float(x.max())) for x in d if len(x)],          # (nprobe 1 on the emptied list: no candidates)
+                       cuts_all=SHAPES[model.case.name].get("radius_cuts_all", True))
 
 
 def _pad(rows, d, k):
@@ -275,6 +287,12 @@ def _pad(rows, d, k):
     o = np.full(k, np.inf, np.float32)
     r[:len(rows)], o[:len(rows)] = rows, d
     return r, o
+
+
+def _chains_agree(X, rows, qv):
+    """the element-by-element chain and the 4-grouped chain of every one of `rows`, bit for bit"""
+    x = X[rows.astype(np.int64)].reshape(len(rows), X.shape[1])
+    return bool((l2_chain(x, qv, SEQ).view(np.uint32) == l2_chain(x, qv, REF4).view(np.uint32)).all())
 
 
 def expect(oracle, model, sp):
@@ -347,13 +365,19 @@ def expect(oracle, model, sp):
                 assert hnc[q] == len(cand)
                 r, d = hrows[q, :hnf[q]], hdist[q, :hnf[q]]
                 assert (np.sqrt(l2_chain(X[r.astype(np.int64)].reshape(len(r), model.dim), qv, REF4)).view(np.uint32) == d.view(np.uint32)).all()
-            elif heap and model.case.name == "ties":
+            elif heap and model.case.integer and _chains_agree(X, mask_ref.considered(cand, a_q, sp["maxc"])[0], qv):
                 # the heap over the considered rows: the oracle's is exec.rs' (the element-by-element chain), which on these small
                 # integers is the 4-grouped chain bit for bit (every partial sum is an exact integer)
                 r, d = oracle.topk_df(X, mask_ref.considered(cand, a_q, sp["maxc"])[0], qv, k)
                 assert (d.view(np.uint32) == l2_chain(X[r.astype(np.int64)].reshape(len(r), model.dim), qv, REF4).view(np.uint32)).all()
             else:
                 r, d, _, _ = mask_ref.masked_topk(cand, a_q, X, qv, k, max_candidates=sp["maxc"])
+                if heap and model.case.integer:
+                    # query 0, a centroid, is no vector of small integers: where its two chains round differently (long rows) the
+                    # oracle's heap states nothing about the 4-grouped one.  Its k + 1 nearest considered rows are then all at
+                    # different distances, and there the heap's order is (d2, position)
+                    near = np.sort(l2_chain(X[mask_ref.considered(cand, a_q, sp["maxc"])[0].astype(np.int64)].reshape(-1, model.dim), qv, REF4))[:k + 1]
+                    assert q == 0 and len(np.unique(near)) == len(near), (q, near)
                 if sp["sqrt"]:
                     d = np.sqrt(d)
             if metric == "cos":
@@ -408,13 +432,13 @@ def modes(case_name):
         m[f"{call}_nq1"] = spec(call, nq=1)
         for cap, n in (("below", CAP), ("at", None), ("above", 1 << 20)):
             m[f"{call}_cap_{cap}"] = spec(call, maxc=n)               # "at": the first query's candidate count, filled in per state
-        if call == "topk_device" or case_name != "ties":
+        if call == "topk_device" or not sh["integer"]:
             # (pqv_topk's cosine is the d2-sorted heap of the normalised rows: where d2 ties, as on `ties`, no reference here states
             #  it -- the oracle's heaps sort by sqrt(d2) or run the element-by-element chain; the device form's (d2, position) stays)
             m[f"{call}_cosine"] = spec(call, metric="cos")
         m[f"{call}_masked"] = spec(call, mask="dense")
         m[f"{call}_masked_sparse"] = spec(call, mask="sparse", nprobe=nf)
-    if case_name != "ties":
+    if not sh["integer"]:
         m["cosine_cap"] = spec("topk", metric="cos", maxc=CAP)
     m["masked_cap"] = spec("topk", mask="dense", maxc=CAP)
     m["distinct"] = spec("distinct")
@@ -434,7 +458,7 @@ def modes(case_name):
     m["range_cap"] = spec("range", maxc=CAP)
     m["range_cosine"] = spec("range", metric="cos")
     m["range_masked_cap"] = spec("range", mask="dense", maxc=CAP, maxr=7)
-    if case_name in ("exact30", "screened"):
+    if case_name in ("exact30", "screened", "far768"):
         m["dot"] = spec("topk", metric="dot")
         m["dot_device"] = spec("topk_device", metric="dot")
         m["dot_range"] = spec("range", metric="dot")
