@@ -587,6 +587,40 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// Every row of `part` whose key passes the query's filter within `radius` of the query -- exact, nothing is probed, ascending by
+    /// (distance, sequence position); `max_results > 0` keeps the first `max_results` of each query (`include/pqv.h`:
+    /// `pqv_range_search_partition`).
+    pub fn range_search_partition(&self, part: &KeyPartition, filter: &KeyFilter, mask: Option<&RowMask>, queries: &[f32], dim: usize,
+                                  radius: f32, max_results: u64) -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        // (the arrays the descriptor points at live until the call has returned)
+        let (desc, _lims, _vals) = key_filter_desc(filter, nq)?;
+        let (mut lims, mut rows, mut dist) = (ptr::null_mut::<u64>(), ptr::null_mut::<u32>(), ptr::null_mut::<f32>());
+        check(unsafe {
+            sys::pqv_range_search_partition(self.raw, part.raw, &desc, mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(),
+                                            nq as u32, dim as u32, radius, max_results, sys::PQV_L2SQ_REF4, 1, &mut lims, &mut rows,
+                                            &mut dist, ptr::null_mut(), ptr::null_mut())
+        })?;
+        if lims.is_null() || rows.is_null() || dist.is_null() {
+            unsafe { sys::pqv_range_free(lims, rows, dist) };
+            return Err("pqv_range_search_partition returned a NULL buffer".into());
+        }
+        let out = {
+            let l = unsafe { std::slice::from_raw_parts(lims, nq + 1) };
+            let total = l[nq] as usize;
+            let (r, d) = if total == 0 {
+                (&[][..], &[][..])
+            } else {
+                unsafe { (std::slice::from_raw_parts(rows, total), std::slice::from_raw_parts(dist, total)) }
+            };
+            (0..nq)
+                .map(|q| (l[q] as usize..l[q + 1] as usize).map(|i| SearchResult { row_idx: r[i], distance: d[i] }).collect())
+                .collect()
+        };
+        unsafe { sys::pqv_range_free(lims, rows, dist) };
+        Ok(out)
+    }
+
     /// Up to `group_size` rows of each of the `k` nearest groups of `group_keys` among the rows of `part` whose key passes the
     /// query's filter -- exact, nothing is probed; `group_size` 1 is the distinct call (`include/pqv.h`:
     /// `pqv_topk_partition_grouped`).  `k * group_size <= 1024`.

@@ -392,7 +392,8 @@ int pqv_round_robin_quota(const uint64_t *counts, uint32_t n_files, uint64_t max
  *                   everywhere (A/B runs)
  *   "drain_min"     queued survivors that start a batch of exact evaluations before a wave's last tile (0 = 64)
  *   "partition_blocks" pqv_topk_partition: blocks per query of partition_stream_kernel (0 = by rule, from nq, k and the partition's
- *                   rows; at most 4096)
+ *                   rows; at most 4096).  pqv_range_search_partition: the same, by rule from the group and its longest sequence
+ *   "partition_range_bytes" pqv_range_search_partition: the byte budget of one group's hit segments (0 = 1 GiB)
  * The same names, upper-cased with a PQV_ prefix, are read from the environment ONCE when a searcher is created
  * (profiling scripts). */
 int pqv_searcher_set_option(pqv_searcher *searcher, const char *name, int64_t value);
@@ -775,7 +776,8 @@ int pqv_topk_expand_device(const pqv_searcher *searcher, const pqv_row_keys *key
  *                n_found, n_candidates and their device forms may be NULL.  The device form is asynchronous on hip_stream with no
  *                host synchronisation; for an unvalidated IN slice that query's result is unspecified and every access is in
  *                bounds, as pqv_topk_filtered_device documents.
- *   out of scope table searchers; range search over a partition (distinct and grouped: pqv_topk_partition_grouped below); k > 1024;
+ *   out of scope table searchers; k > 1024 (distinct and grouped: pqv_topk_partition_grouped below; every row within a radius:
+ *                pqv_range_search_partition below);
  *                mutable partitions (after an append or a remove, make the new searcher's partition); the screened kernels on long
  *                runs; choosing between the IVF and the partition path automatically (pqv_key_partition_keys gives a planner the run
  *                lengths for that choice).
@@ -817,13 +819,56 @@ int pqv_topk_expand_device(const pqv_searcher *searcher, const pqv_row_keys *key
  *   limits       k * group_size <= 1024 (the product taken in 64 bits) in both forms: PQV_ERR_UNSUPPORTED
  *                "pqv_topk_partition_grouped takes k * group_size <= 1024"; there is no host fallback.  The device form is
  *                asynchronous on hip_stream with no host synchronisation.
- *   out of scope table searchers (pqv_key_partition_create refuses them); range search over a partition; PQV_DOT; max_nprobe (nothing
- *                is probed); the path-taking builders; choosing between the IVF and the partition path automatically.
+ *   out of scope table searchers (pqv_key_partition_create refuses them); PQV_DOT; max_nprobe (nothing is probed); the path-taking
+ *                builders; choosing between the IVF and the partition path automatically.
  * Errors, in this order (PQV_ERR_INVALID), every NULL and zero check before a handle is dereferenced or a device used: "searcher
  * must not be NULL", "key partition must not be NULL", "row keys must not be NULL", "filter must not be NULL" and the descriptor
  * checks of pqv_topk_filtered (host form), "k must be > 0", "group_size must be > 0", "key partition belongs to another searcher",
  * "row keys belong to another searcher", "row mask belongs to another searcher", then pqv_topk's own (metric, query length), then the
- * two PQV_ERR_UNSUPPORTED texts above (PQV_DOT first). */
+ * two PQV_ERR_UNSUPPORTED texts above (PQV_DOT first).
+ *
+ * pqv_range_search_partition: "every document of tenant T within 0.3 of this vector" -- pqv_range_search's answer over
+ * pqv_topk_partition's candidates, exact because nothing is probed.  The host form only: range search has no device form anywhere,
+ * the output is sized from counts.  No nprobe and no max_candidates.
+ *   candidates   exactly pqv_topk_partition's: query q's sequence is every partition row r with F_q(key[r]), ordered by (key[r], r);
+ *                a candidate's position is its index in that sequence; n_candidates[q] is the sequence's length, taken before the
+ *                mask.  The filter arrays are host arrays, read as pqv_topk_filtered reads them.
+ *   considered   the candidates the optional shared `mask` allows (NULL: all), at their unmasked positions; a row the mask excludes
+ *                is never loaded.
+ *   distance     exactly pqv_range_search's: the bit-identical chains of PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE (through the cosine
+ *                layout, out = 0.5f * d2 whatever sqrt_out) and PQV_DOT (dist = 0.0f - s(q, x); sqrt_out is ignored and a hit is dist
+ *                <= radius); out = sqrt_out ? sqrt(d2) (correctly rounded) : d2 for the L2 forms.
+ *   hit          out <= radius, inclusive, on the output scale.  A NaN distance is never a hit; radius = +inf keeps every other
+ *                considered row; a negative radius keeps none, except for PQV_DOT, whose distances are signed; a NaN radius is
+ *                PQV_ERR_INVALID "radius must not be NaN".
+ *   order        ascending by (distance key, sequence position): unique per query, independent of scheduling and of
+ *                partition_blocks.  max_results > 0 keeps the first max_results hits in that order.
+ *   exactness    with mask == NULL the answer is EVERY indexed row of the passing keys within the radius.  No searcher option
+ *                changes a result.
+ *   equivalence  (a) for any input, ties included: with radius = +inf, max_results = k <= 1024 and no NaN distance, query q's hits
+ *                are pqv_topk_partition's first n_found[q] rows and distances, bit for bit -- both calls order by (distance key,
+ *                position) and neither replays a heap.  (b) on S1 (above) the call equals pqv_range_search_masked under the per-query
+ *                mask M_q (the rows whose key passes F_q, ANDed with `mask`) with nprobe = 1: always for PQV_KEY_EQ; for RANGE and IN
+ *                whenever no two considered rows of different keys tie in distance.
+ *   output       CSR library buffers as pqv_range_search: query q's hits are row_idx / dist [lims[q], lims[q + 1]); *lims [nq + 1]
+ *                is allocated also for nq = 0; release with pqv_range_free.  n_within host [nq]: the hit count before max_results;
+ *                n_candidates host [nq]; both may be NULL.
+ *   counts       queries advances by nq, candidate_rows by the sum of n_candidates, embeddings_fetched by the considered rows;
+ *                screened_pairs and screen_survivors do not move.  pqv_set_timing / pqv_timing_read see the distance pass as the
+ *                "re-rank" (one timed call per group, below).
+ *   path         per piece of at most 32768 queries: the span kernel, then the candidate counts come back to the host -- ONE
+ *                synchronisation more than pqv_range_search has, because the hit segments are packed (query q's holds
+ *                n_candidates[q] entries, not the longest tenant's) and the grid follows the longest sequence.  The piece runs in
+ *                groups of consecutive queries whose segments (12 bytes a candidate) fit a byte budget ("partition_range_bytes", 0 =
+ *                1 GiB; a query whose own segment exceeds it runs alone): per group ONE exact streaming pass, the hit counts back,
+ *                pqv_range_search's sort and write-out.  A group without a candidate launches nothing.
+ *   limits       none on the number of hits; a sequence holds at most 2^32 - 1 candidates.
+ *   out of scope table searchers; a device form; range search over the distinct or grouped forms; a per-query radius; the screened
+ *                kernels on long runs.
+ * Errors, in this order (PQV_ERR_INVALID), every NULL check before a handle is read or a device used: "searcher must not be NULL",
+ * "key partition must not be NULL", "filter must not be NULL" and the host descriptor checks of pqv_topk_filtered, "key partition
+ * belongs to another searcher", "row mask belongs to another searcher", then pqv_range_search's own: metric, query length, "radius
+ * must not be NaN", "lims/row_idx/dist must not be NULL", "queries must not be NULL". */
 typedef struct pqv_key_partition pqv_key_partition;
 int      pqv_key_partition_create(const pqv_searcher *searcher, const pqv_column *column, void *hip_stream, pqv_key_partition **out);
 uint64_t pqv_key_partition_rows(const pqv_key_partition *part);
@@ -846,6 +891,10 @@ int pqv_topk_partition_grouped_device(const pqv_searcher *searcher, const pqv_ke
                                       const pqv_row_keys *group_keys, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
                                       uint32_t k, uint32_t group_size, int metric, int sqrt_out, void *d_row_idx, void *d_dist,
                                       void *d_group_key, void *d_group_rows, void *d_n_found, void *d_n_candidates, void *hip_stream);
+int pqv_range_search_partition(const pqv_searcher *searcher, const pqv_key_partition *part, const pqv_key_filter *filter,
+                               const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len, float radius,
+                               uint64_t max_results, int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
+                               uint64_t *n_within, uint64_t *n_candidates);
 
 /* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
  * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.

@@ -197,6 +197,8 @@ SIGNATURES = {
                                              C.c_int, C.c_int, u32p, f32p, i64p, u32p, u32p, u64p]),
     "pqv_topk_partition_grouped_device": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "pqv_range_search_partition": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint64,
+                                             C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_range_search_filtered": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64,
                                             C.c_uint64, C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_topk_distinct": (C.c_int, [vp, vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,

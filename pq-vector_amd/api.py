@@ -909,6 +909,18 @@ def _allow_array(allowed, n_rows, what="row mask"):
     return np.ascontiguousarray(a).view(np.uint8) if a.dtype == np.bool_ else np.ascontiguousarray(a)
 
 
+def _take_range_buffers(nq, lims_p, rows_p, dist_p):
+    """(lims, rows, dist) copied out of a range call's library buffers, which are released"""
+    try:
+        lims = np.ctypeslib.as_array(lims_p, shape=(nq + 1,)).copy()
+        total = int(lims[-1])
+        rows = (np.ctypeslib.as_array(rows_p, shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32))
+        dist = (np.ctypeslib.as_array(dist_p, shape=(total,)).copy() if total else np.zeros(0, dtype=np.float32))
+    finally:
+        _ffi.lib().pqv_range_free(lims_p, rows_p, dist_p)
+    return lims, rows, dist
+
+
 def _mask_handle(searcher, mask):
     if not isinstance(mask, RowMask):
         raise PqvError(_ffi.PQV_ERR_INVALID, f"mask must be a RowMask, got {type(mask).__name__}")
@@ -1396,13 +1408,34 @@ class Searcher:
             _check(_ffi.lib().pqv_range_search(self._h, q.ctypes.data_as(f32p), nq, qlen, radius, nprobe, max_candidates,
                                                max_results, metric, 1 if sqrt_out else 0, C.byref(lims_p), C.byref(rows_p),
                                                C.byref(dist_p), nw.ctypes.data_as(u64p), nc.ctypes.data_as(u64p)))
-        try:
-            lims = np.ctypeslib.as_array(lims_p, shape=(nq + 1,)).copy()
-            total = int(lims[-1])
-            rows = (np.ctypeslib.as_array(rows_p, shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32))
-            dist = (np.ctypeslib.as_array(dist_p, shape=(total,)).copy() if total else np.zeros(0, dtype=np.float32))
-        finally:
-            _ffi.lib().pqv_range_free(lims_p, rows_p, dist_p)
+        lims, rows, dist = _take_range_buffers(nq, lims_p, rows_p, dist_p)
+        return lims, rows, dist, nw, nc
+
+    def range_search_partition(self, queries, radius, part, query_keys=None, query_key_ranges=None, query_key_sets=None, mask=None,
+                               max_results=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """Every row of `part` (a KeyPartition of this searcher) whose key passes the query's filter -- the keywords of
+        topk_partition -- within `radius` of the query and within mask if one is given, ascending by (distance, sequence position);
+        exact, nothing is probed (pqv.h: pqv_range_search_partition).  Returns (lims u64 [nq+1], rows u32, dist f32, n_within u64
+        [nq], n_candidates u64 [nq]) laid out as range_search's."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        ph, f, _alive = _partition_filter(part, query_keys, query_key_ranges, query_key_sets, nq)
+        mh = _mask_handle(self, mask) if mask is not None else None
+        radius = float(radius)
+        if radius != radius:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "radius must not be NaN")
+        max_results = int(max_results)
+        if max_results < 0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "max_results must be >= 0")
+        nw = np.zeros(nq, dtype=np.uint64)
+        nc = np.zeros(nq, dtype=np.uint64)
+        lims_p, rows_p, dist_p = u64p(), u32p(), f32p()
+        _check(_ffi.lib().pqv_range_search_partition(self._h, ph, C.byref(f), mh, q.ctypes.data_as(f32p), nq, qlen, radius, max_results,
+                                                     metric, 1 if sqrt_out else 0, C.byref(lims_p), C.byref(rows_p), C.byref(dist_p),
+                                                     nw.ctypes.data_as(u64p), nc.ctypes.data_as(u64p)))
+        lims, rows, dist = _take_range_buffers(nq, lims_p, rows_p, dist_p)
         return lims, rows, dist, nw, nc
 
     def topk_device(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0,

@@ -114,6 +114,7 @@ int use_device(int device) {
         std::call_once(warmed[device], [] {
             (void)pqv::touch_probe(nullptr); (void)pqv::touch_screen(nullptr); (void)pqv::touch_brute(nullptr); (void)pqv::touch_build(nullptr);
             (void)pqv::touch_layout(nullptr); (void)pqv::touch_list(nullptr); (void)pqv::touch_kpp(nullptr); (void)pqv::touch_range(nullptr); (void)pqv::touch_mask(nullptr); (void)pqv::touch_predicate(nullptr);
+            (void)pqv::touch_partition_range(nullptr);
             (void)hipStreamSynchronize(nullptr);
             // ... and the runtime's staging buffers for copies from / to pageable host memory are made by the first such copies
             void *d = nullptr;
@@ -354,6 +355,7 @@ struct Scratch {
         s_g1_rows, s_g1_dist, s_g1_keys, s_g1_nfound, s_gset_keys, s_gset_slot, s_gpart_slot, s_gpart_cnt, s_grows_out,
         s_expand_cnt, s_expand_used,    // pqv_topk_expand: the passing rows per probed list u32 [nq][P]; nprobe_used u32 [nq] where the caller takes none
         s_ps_q16, s_ps_qn2, s_ps_score, // screened probe: the batch's query images f16 [nq][dim_p], |q - mean|^2 [nq], the scores f32 [nq][kc_pad]
+        s_seg_off,                      // pqv_range_search_partition: the group's packed segment offsets u64 [b]
         s_pt_beg, s_pt_end, s_pt_nspan; // pqv_topk_partition: the spans' first entries u32 [nq] (IN: [nq][1024]), IN: their prefix sums and counts
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
@@ -370,7 +372,7 @@ struct Scratch {
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
                 &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
                 &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out,
-                &s_expand_cnt, &s_expand_used, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_pt_beg, &s_pt_end, &s_pt_nspan};
+                &s_expand_cnt, &s_expand_used, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_seg_off, &s_pt_beg, &s_pt_end, &s_pt_nspan};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -483,6 +485,7 @@ struct pqv_searcher {
                                            // (8-wave blocks on 32-row tiles) instead of two passes; 0 = off
         uint32_t wide_quad_rows = 0;       // rows per block of that instance (0 = by rule: 6144)
         uint32_t partition_blocks = 0;     // pqv_topk_partition: blocks per query of partition_stream_kernel (0 = by rule; PQV_PARTITION_BLOCKS)
+        uint64_t partition_range_bytes = 0;    // pqv_range_search_partition: the hit segments' byte budget of one group (0 = 1 GiB; PQV_PARTITION_RANGE_BYTES)
         int list_once = 0;                 // round 6: 1 = lists probed by more than 96 queries of the batch go to list_filter_kernel (rows stationary in
                                            // registers, ALL the list's pairs streamed past them: every such list is read once -- and measured SLOWER than
                                            // the wide-quad instance / regular quads sharing an L2: C3 2.18 against 1.87 ms of kernels, the mixture 3.7
@@ -3347,6 +3350,7 @@ void opts_from_env(pqv_searcher::Opts &o) {
     o.wide_quad_rows = static_cast<uint32_t>(num("PQV_WIDE_QUAD_ROWS", o.wide_quad_rows));
     o.list_once = static_cast<int>(num("PQV_LIST_ONCE", o.list_once));
     o.partition_blocks = static_cast<uint32_t>(std::max<long long>(0, num("PQV_PARTITION_BLOCKS", o.partition_blocks)));
+    o.partition_range_bytes = static_cast<uint64_t>(std::max<long long>(0, num("PQV_PARTITION_RANGE_BYTES", static_cast<long long>(o.partition_range_bytes))));
     o.pair_prune = static_cast<int>(num("PQV_PAIR_PRUNE", o.pair_prune));
     o.i8_form = static_cast<int>(num("PQV_I8_FORM", o.i8_form));
 }
@@ -5501,6 +5505,79 @@ int grow_host(std::unique_ptr<T, HostFree> &buf, uint64_t &cap, uint64_t need) {
     return PQV_OK;
 }
 
+// What follows a hit pass's synchronisation, for the b queries from q0 whose hit counts h_cnt came back: the output offsets from
+// the counts (lims[q0 + 1 ..] from lims[q0]; n_within), the library buffers grown, the segments sorted by (distance key, position)
+// and written out on the device -- one block each up to RANGE_SMALL hits, the multi-pass path beyond --, PQV_DOT's ord halves
+// turned back into distances, and the results copied behind lims[q0] and waited for.  Segments: uniform (q * stride) or packed
+// (d_seg_off, with the host's per-query room).  e_end: the timing event recorded behind the write-out, or nullptr.
+struct RangeWriteOut {
+    const uint32_t *d_hit_cnt;    // [b] on the device
+    const uint32_t *h_cnt;        // [b] the same counts on the host
+    const uint64_t *h_room;       // [b] entries each segment holds, or nullptr: `stride` each
+    uint64_t stride;
+    const uint64_t *d_seg_off;    // [b] on the device, or nullptr (RangeSortArgs::seg_off)
+    uint64_t max_results;
+    int metric, sqrt_out;
+};
+int range_write_out(const pqv_searcher *s, Scratch &sc, const RangeWriteOut &w, uint32_t q0, uint32_t b, uint64_t *lims,
+                    std::unique_ptr<uint32_t, HostFree> &rows, std::unique_ptr<float, HostFree> &dist, uint64_t &cap_rows, uint64_t &cap_dist,
+                    uint64_t *n_within, std::vector<uint64_t> &h_off, std::vector<pqv::RangeSeg> &segs, hipEvent_t e_end, uint32_t &launches) {
+    using namespace pqv;
+    hipStream_t st = s->stream;
+    // output offsets from the counts; segments longer than one block's sort go to the multi-pass path
+    segs.clear();
+    uint64_t tot = 0, alt = 0;
+    uint32_t max_n = 0;
+    bool any_small = false;
+    for (uint32_t i = 0; i < b; ++i) {
+        const uint32_t n = w.h_cnt[i];
+        if (n > (w.h_room ? w.h_room[i] : w.stride)) return fail(PQV_ERR_HIP, "range search: a segment overflowed");     // (cannot happen: n <= capped candidates)
+        const uint64_t kept = w.max_results ? std::min<uint64_t>(n, w.max_results) : n;
+        h_off[i] = tot;
+        tot += kept;
+        lims[q0 + i + 1] = lims[q0 + i] + kept;
+        if (n_within) n_within[q0 + i] = n;
+        if (n > RANGE_SMALL) { segs.push_back(RangeSeg{i, n, alt}); alt += n; max_n = std::max(max_n, n); }
+        else if (n) any_small = true;
+    }
+    if (int rc = grow_host(rows, cap_rows, lims[q0 + b])) return rc;
+    if (int rc = grow_host(dist, cap_dist, lims[q0 + b])) return rc;
+    if (tot) {
+        HIP_TRY(sc.s_rout_rows.ensure(tot * sizeof(uint32_t)));
+        HIP_TRY(sc.s_rout_dist.ensure(tot * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(sc.s_rout_off.p, h_off.data(), static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        RangeSortArgs sa{};
+        sa.nq = b; sa.hit_cnt = w.d_hit_cnt;
+        sa.keys = sc.s_hit_keys.as<uint64_t>(); sa.vals = sc.s_hit_vals.as<uint32_t>(); sa.seg_stride = w.stride; sa.seg_off = w.d_seg_off;
+        sa.max_results = w.max_results; sa.out_off = sc.s_rout_off.as<uint64_t>();
+        sa.ids = s->d_final_ids; sa.sqrt_out = w.sqrt_out;
+        sa.out_rows = sc.s_rout_rows.as<uint32_t>(); sa.out_dist = sc.s_rout_dist.as<float>();
+        if (any_small) { HIP_TRY(launch_range_sort_small(sa, st)); ++launches; }
+        if (!segs.empty()) {
+            HIP_TRY(sc.s_alt_keys.ensure(alt * sizeof(uint64_t)));
+            HIP_TRY(sc.s_alt_vals.ensure(alt * sizeof(uint32_t)));
+            HIP_TRY(sc.s_rsegs.ensure(segs.size() * sizeof(RangeSeg)));
+            HIP_TRY(hipMemcpyAsync(sc.s_rsegs.p, segs.data(), segs.size() * sizeof(RangeSeg), hipMemcpyHostToDevice, st));
+            sa.alt_keys = sc.s_alt_keys.as<uint64_t>(); sa.alt_vals = sc.s_alt_vals.as<uint32_t>();
+            sa.segs = sc.s_rsegs.as<RangeSeg>(); sa.n_segs = static_cast<uint32_t>(segs.size());
+            uint32_t nl = 0;
+            HIP_TRY(launch_range_sort_large(sa, max_n, &nl, st));
+            launches += nl;
+        }
+        if (w.metric == PQV_DOT) {     // (the sort kernels wrote the keys' ord halves: back to dist in place)
+            HIP_TRY(launch_dot_finish(sc.s_rout_dist.as<float>(), tot, st));
+            ++launches;
+        }
+        if (e_end) HIP_TRY(hipEventRecord(e_end, st));
+        HIP_TRY(hipMemcpyAsync(rows.get() + lims[q0], sc.s_rout_rows.p, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(dist.get() + lims[q0], sc.s_rout_dist.p, tot * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else if (e_end) {
+        HIP_TRY(hipEventRecord(e_end, st));
+    }
+    return PQV_OK;
+}
+
 int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_t nq, float radius, uint32_t nprobe,
                uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out, uint64_t *lims,
                std::unique_ptr<uint32_t, HostFree> &rows, std::unique_ptr<float, HostFree> &dist, uint64_t *n_within,
@@ -5592,58 +5669,9 @@ int range_body(const pqv_searcher *s, Scratch &sc, const float *queries, uint32_
             HIP_TRY(hipMemcpyAsync(h_ncand.data(), sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
 
-        // output offsets from the counts; segments longer than one block's sort go to the multi-pass path
-        segs.clear();
-        uint64_t tot = 0, alt = 0;
-        uint32_t max_n = 0;
-        bool any_small = false;
-        for (uint32_t i = 0; i < b; ++i) {
-            const uint32_t n = h_cnt[i];
-            if (n > stride) return fail(PQV_ERR_HIP, "range search: a segment overflowed");     // (cannot happen: n <= capped candidates)
-            const uint64_t kept = max_results ? std::min<uint64_t>(n, max_results) : n;
-            h_off[i] = tot;
-            tot += kept;
-            lims[q0 + i + 1] = lims[q0 + i] + kept;
-            if (n_within) n_within[q0 + i] = n;
-            if (n_candidates) n_candidates[q0 + i] = h_ncand[i];
-            if (n > RANGE_SMALL) { segs.push_back(RangeSeg{i, n, alt}); alt += n; max_n = std::max(max_n, n); }
-            else if (n) any_small = true;
-        }
-        if (int rc = grow_host(rows, cap_rows, lims[q0 + b])) return rc;
-        if (int rc = grow_host(dist, cap_dist, lims[q0 + b])) return rc;
-        if (tot) {
-            HIP_TRY(sc.s_rout_rows.ensure(tot * sizeof(uint32_t)));
-            HIP_TRY(sc.s_rout_dist.ensure(tot * sizeof(float)));
-            HIP_TRY(hipMemcpyAsync(sc.s_rout_off.p, h_off.data(), static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            RangeSortArgs sa{};
-            sa.nq = b; sa.hit_cnt = sc.s_hit_cnt.as<uint32_t>();
-            sa.keys = sc.s_hit_keys.as<uint64_t>(); sa.vals = sc.s_hit_vals.as<uint32_t>(); sa.seg_stride = stride;
-            sa.max_results = max_results; sa.out_off = sc.s_rout_off.as<uint64_t>();
-            sa.ids = s->d_final_ids; sa.sqrt_out = sqrt_out;
-            sa.out_rows = sc.s_rout_rows.as<uint32_t>(); sa.out_dist = sc.s_rout_dist.as<float>();
-            if (any_small) { HIP_TRY(launch_range_sort_small(sa, st)); ++launches; }
-            if (!segs.empty()) {
-                HIP_TRY(sc.s_alt_keys.ensure(alt * sizeof(uint64_t)));
-                HIP_TRY(sc.s_alt_vals.ensure(alt * sizeof(uint32_t)));
-                HIP_TRY(sc.s_rsegs.ensure(segs.size() * sizeof(RangeSeg)));
-                HIP_TRY(hipMemcpyAsync(sc.s_rsegs.p, segs.data(), segs.size() * sizeof(RangeSeg), hipMemcpyHostToDevice, st));
-                sa.alt_keys = sc.s_alt_keys.as<uint64_t>(); sa.alt_vals = sc.s_alt_vals.as<uint32_t>();
-                sa.segs = sc.s_rsegs.as<RangeSeg>(); sa.n_segs = static_cast<uint32_t>(segs.size());
-                uint32_t nl = 0;
-                HIP_TRY(launch_range_sort_large(sa, max_n, &nl, st));
-                launches += nl;
-            }
-            if (metric == PQV_DOT) {     // (the sort kernels wrote the keys' ord halves: back to dist in place)
-                HIP_TRY(launch_dot_finish(sc.s_rout_dist.as<float>(), tot, st));
-                ++launches;
-            }
-            if (e[3]) HIP_TRY(hipEventRecord(e[3], st));
-            HIP_TRY(hipMemcpyAsync(rows.get() + lims[q0], sc.s_rout_rows.p, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(dist.get() + lims[q0], sc.s_rout_dist.p, tot * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        } else if (e[3]) {
-            HIP_TRY(hipEventRecord(e[3], st));
-        }
+        if (n_candidates) std::copy(h_ncand.begin(), h_ncand.begin() + b, n_candidates + q0);
+        RangeWriteOut wo{sc.s_hit_cnt.as<uint32_t>(), h_cnt.data(), nullptr, stride, nullptr, max_results, metric, sqrt_out};
+        if (int rc = range_write_out(s, sc, wo, q0, b, lims, rows, dist, cap_rows, cap_dist, n_within, h_off, segs, e[3], launches)) return rc;
         s->counters.queries += b;
         s->counters.kernel_launches += launches;
     }
@@ -6455,6 +6483,182 @@ extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition
     });
 }
 
+// ---- range search over a key partition (pqv.h: pqv_range_search_partition) --------------------------------------------------------
+// Per piece of at most PARTITION_GRID_Q queries: the queries and the filter slice uploaded as topk_partition_host_impl uploads them,
+// ONE span launch, and n_cand [b] brought back -- the one synchronisation this call has over range_body: the hit segments are
+// PACKED, query q's holds n_cand[q] entries, and the grid follows the longest sequence.  The piece is then cut into groups of
+// consecutive queries whose segments fit the byte budget (12 B an entry; partition_range_bytes, 0 = 1 GiB; a query whose own segment
+// exceeds it runs alone).  Per group: hit_cnt zeroed, partition_range_kernel on the group's slice of the span arrays, the counts
+// back, and range_body's write-out (range_write_out) over the packed segments.  A group without a candidate launches nothing.
+// Timing: one event set per group that launches (the first of a piece begins ahead of the span launch); the range kernel is the
+// "re-rank".
+static int range_partition_body(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, const pqv_key_filter *f, const uint64_t *bits,
+                                const float *queries, uint32_t nq, float radius, uint64_t max_results, int metric, int sqrt_out, uint64_t *lims,
+                                std::unique_ptr<uint32_t, HostFree> &rows, std::unique_ptr<float, HostFree> &dist, uint64_t *n_within,
+                                uint64_t *n_candidates) {
+    using namespace pqv;
+    hipStream_t st = s->stream;
+    const uint32_t kind = f->kind;
+    const uint64_t budget = s->opt.partition_range_bytes ? s->opt.partition_range_bytes : (1ull << 30);
+    const uint32_t piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
+    const uint32_t span_w = kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u;      // span slots per query
+    HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(piece) * s->dim * sizeof(float)));
+    if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
+    HIP_TRY(sc.s_pt_beg.ensure(static_cast<size_t>(piece) * span_w * sizeof(uint32_t)));
+    if (kind == PQV_KEY_IN) {
+        HIP_TRY(sc.s_pt_end.ensure(static_cast<size_t>(piece) * span_w * sizeof(uint32_t)));
+        HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+    }
+    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_hit_cnt.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_seg_off.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
+    SearchRequest rq{}, sub{};      // the descriptor's host arrays, for the pieces' slices
+    rq.rows.kind = kind;
+    if (kind == PQV_KEY_EQ) rq.rows.h_qkeys = static_cast<const int64_t *>(f->a);
+    else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
+    sub = rq;
+    std::vector<uint64_t> sub_lims, h_ncand(piece), h_off(piece), h_seg(piece);
+    std::vector<uint32_t> h_cnt(piece);
+    std::vector<RangeSeg> segs;
+    uint64_t cap_rows = 1, cap_dist = 1;      // entries the library buffers have room for
+    for (uint32_t q0 = 0; q0 < nq; q0 += piece) {
+        const uint32_t b = std::min<uint32_t>(piece, nq - q0);
+        uint32_t launches = 0;
+        hipEvent_t e[4];
+        if (int rc = timing_events(s, e)) return rc;
+        bool e_open = e[0] != nullptr;      // a set whose first event is recorded and whose others wait for a group
+        HIP_TRY(hipMemcpyAsync(sc.s_queries.p, queries + static_cast<uint64_t>(q0) * s->dim, static_cast<size_t>(b) * s->dim * sizeof(float),
+                               hipMemcpyHostToDevice, st));
+        if (int rc = upload_query_filter(sc, &rq, sub, q0, b, sub_lims, st)) return rc;
+        if (e[0]) HIP_TRY(hipEventRecord(e[0], st));
+        const float *dq = sc.s_queries.as<float>();
+        if (s->sdim != s->dim) {      // (the stored rows are zero-padded: the queries that meet them too)
+            HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), st));
+            dq = sc.s_qpad.as<float>();
+            ++launches;
+        }
+        PartitionSpanArgs sp{};
+        sp.keys = part->d_keys.as<int64_t>(); sp.key_off = part->d_off.as<uint64_t>(); sp.n_keys = part->n_keys;
+        sp.nq = b; sp.kind = kind;
+        sp.a = sub.d_filter_a(); sp.b = sub.d_filter_b();       // (the piece's own slice: an IN filter's lims are rebased)
+        sp.span_beg = sc.s_pt_beg.as<uint32_t>(); sp.span_end = sc.s_pt_end.as<uint32_t>(); sp.n_span = sc.s_pt_nspan.as<uint32_t>();
+        sp.n_cand = sc.s_ncand.as<uint64_t>();
+        sp.stats = s->d_stats.as<unsigned long long>();
+        HIP_TRY(launch_partition_span(sp, st));
+        ++launches;
+        HIP_TRY(hipMemcpyAsync(h_ncand.data(), sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_candidates) std::copy(h_ncand.begin(), h_ncand.begin() + b, n_candidates + q0);
+
+        for (uint32_t g0 = 0; g0 < b;) {
+            // the group [g0, g1): consecutive queries while their segments fit the budget; never empty
+            uint64_t entries = 0, longest = 0;
+            uint32_t g1 = g0;
+            while (g1 < b && (g1 == g0 || (entries + h_ncand[g1]) * 12 <= budget)) {
+                h_seg[g1 - g0] = entries;
+                entries += h_ncand[g1];
+                longest = std::max(longest, h_ncand[g1]);
+                ++g1;
+            }
+            const uint32_t gb = g1 - g0;
+            if (entries == 0) {         // nobody has a candidate: nothing is launched
+                for (uint32_t i = g0; i < g1; ++i) {
+                    lims[q0 + i + 1] = lims[q0 + i];
+                    if (n_within) n_within[q0 + i] = 0;
+                }
+                g0 = g1;
+                continue;
+            }
+            if (!e_open) {
+                if (int rc = timing_events(s, e)) return rc;
+                if (e[0]) HIP_TRY(hipEventRecord(e[0], st));
+            }
+            e_open = false;
+            HIP_TRY(sc.s_hit_keys.ensure(static_cast<size_t>(entries) * sizeof(uint64_t)));
+            HIP_TRY(sc.s_hit_vals.ensure(static_cast<size_t>(entries) * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(sc.s_hit_cnt.p, 0, static_cast<size_t>(gb) * sizeof(uint32_t), st));
+            HIP_TRY(hipMemcpyAsync(sc.s_seg_off.p, h_seg.data(), static_cast<size_t>(gb) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            // blocks per query: the option, or by rule about 2048 blocks for the group and no more than the longest sequence's turns
+            uint64_t B = s->opt.partition_blocks;
+            if (!B) B = std::min<uint64_t>((2048 + static_cast<uint64_t>(gb) - 1) / gb, (longest + 255) / 256);
+            StreamArgs ra{};
+            ra.mat = s->d_mat; ra.row_of = s->d_row_of;
+            ra.queries = dq + static_cast<size_t>(g0) * s->sdim; ra.nq = gb; ra.nprobe = 1; ra.dim = s->sdim; ra.k = 1;
+            ra.rows_per_block = 256; ra.blocks_per_list = static_cast<uint32_t>(std::max<uint64_t>(1, B)); ra.max_pos = ~0ull; ra.metric = metric;
+            ra.radius = radius; ra.sqrt_out = sqrt_out;
+            ra.hit_cnt = sc.s_hit_cnt.as<uint32_t>(); ra.hit_keys = sc.s_hit_keys.as<uint64_t>(); ra.hit_vals = sc.s_hit_vals.as<uint32_t>();
+            ra.seg_stride = 0; ra.seg_off = sc.s_seg_off.as<uint64_t>();
+            PartitionArgs pa{};
+            pa.pos = part->d_pos.as<uint32_t>();
+            // (the span arrays are indexed by the piece's query: IN keeps KEY_SET_MAX slots a query)
+            pa.span_beg = sp.span_beg + static_cast<size_t>(g0) * span_w;
+            if (kind == PQV_KEY_IN) { pa.span_end = sp.span_end + static_cast<size_t>(g0) * span_w; pa.n_span = sp.n_span + g0; }
+            pa.n_cand = sp.n_cand + g0; pa.kind = kind; pa.bits = bits; pa.stats = s->d_stats.as<unsigned long long>();
+            if (e[1]) HIP_TRY(hipEventRecord(e[1], st));
+            HIP_TRY(launch_partition_range(ra, pa, st));
+            ++launches;
+            if (e[2]) HIP_TRY(hipEventRecord(e[2], st));
+            HIP_TRY(hipMemcpyAsync(h_cnt.data(), sc.s_hit_cnt.p, static_cast<size_t>(gb) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            RangeWriteOut wo{sc.s_hit_cnt.as<uint32_t>(), h_cnt.data(), h_ncand.data() + g0, 0, sc.s_seg_off.as<uint64_t>(), max_results, metric, sqrt_out};
+            if (int rc = range_write_out(s, sc, wo, q0 + g0, gb, lims, rows, dist, cap_rows, cap_dist, n_within, h_off, segs, e[3], launches)) return rc;
+            g0 = g1;
+        }
+        if (e_open) for (int i = 1; i < 4; ++i) HIP_TRY(hipEventRecord(e[i], st));     // (a piece without a candidate)
+        s->counters.queries += b;
+        s->counters.kernel_launches += launches;
+    }
+    return PQV_OK;
+}
+// The checks in the contract's order: every NULL check before a handle is read or a device used, then pqv_range_search's own.
+static int range_search_partition_impl(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask,
+                                       const float *queries, uint32_t nq, uint32_t query_len, float radius, uint64_t max_results, int metric,
+                                       int sqrt_out, uint64_t **lims_out, uint32_t **rows_out, float **dist_out, uint64_t *n_within,
+                                       uint64_t *n_candidates) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!part) return fail(PQV_ERR_INVALID, "key partition must not be NULL");
+    if (int rc = filter_descriptor_checks(f, nq, true)) return rc;
+    if (part->owner != s || part->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "key partition belongs to another searcher");
+    if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+    if (int rc = validate_query(s, 1, 1, metric, 0, query_len)) return rc;
+    if (metric == PQV_DOT) sqrt_out = 0;      // (ignored: the range_* kernels run as order-only machinery)
+    if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
+    if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
+    if (nq && !queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
+    *lims_out = nullptr; *rows_out = nullptr; *dist_out = nullptr;
+    std::unique_ptr<uint64_t, HostFree> lims(static_cast<uint64_t *>(std::malloc((static_cast<size_t>(nq) + 1) * sizeof(uint64_t))));
+    std::unique_ptr<uint32_t, HostFree> rows(static_cast<uint32_t *>(std::malloc(sizeof(uint32_t))));
+    std::unique_ptr<float, HostFree> dist(static_cast<float *>(std::malloc(sizeof(float))));
+    if (!lims || !rows || !dist) return fail(PQV_ERR_OOM, "host allocation failed");
+    lims.get()[0] = 0;
+    std::vector<float> nq_host;
+    if (nq) {
+        if (int rc = use_device(s->device)) return rc;
+        // (PQV_COSINE: the L2 body on the cosine searcher over n(q): hits 0.5 d2 <= radius, written out halved)
+        if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
+        const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+        std::lock_guard<std::mutex> lock(s->mu);
+        Lane lane;
+        if (int rc = lane.acquire(s, s->stream)) return rc;
+        if (int rc = range_partition_body(s, *lane, part, f, bits, queries, nq, radius, max_results, metric, sqrt_out, lims.get(), rows, dist,
+                                          n_within, n_candidates))
+            return rc;
+        if (int rc = lane.release()) return rc;
+    }
+    *lims_out = lims.release(); *rows_out = rows.release(); *dist_out = dist.release();
+    return PQV_OK;
+}
+extern "C" int pqv_range_search_partition(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
+                                          const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len, float radius,
+                                          uint64_t max_results, int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
+                                          uint64_t *n_within, uint64_t *n_candidates) {
+    return guard([&] {
+        return range_search_partition_impl(s, part, filter, mask, queries, nq, query_len, radius, max_results, metric, sqrt_out ? 1 : 0, lims,
+                                           row_idx, dist, n_within, n_candidates);
+    });
+}
+
 // ---- distinct / grouped top-k over a key partition (pqv.h: pqv_topk_partition_grouped) ------------------------------------------
 // The checks of both forms, in the contract's order: every NULL and zero check before a handle is read.  query_len: the host form's.
 static int partition_group_checks(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_keys *gk,
@@ -7031,6 +7235,7 @@ static int pqv_searcher_set_option_impl(pqv_searcher *s, const char *name, int64
     else if (n == "wide_quad_rows") o.wide_quad_rows = static_cast<uint32_t>(std::max<int64_t>(0, value));
     else if (n == "list_once") o.list_once = static_cast<int>(value);
     else if (n == "partition_blocks") o.partition_blocks = static_cast<uint32_t>(std::max<int64_t>(0, std::min<int64_t>(4096, value)));
+    else if (n == "partition_range_bytes") o.partition_range_bytes = static_cast<uint64_t>(std::max<int64_t>(0, value));
     else if (n == "i8_form") {        // takes effect when the int8 copy is (re)built
         o.i8_form = static_cast<int>(std::min<int64_t>(2, std::max<int64_t>(0, value)));
         (void)hipSetDevice(s->device);

@@ -62,7 +62,14 @@ struct StreamArgs {
     uint64_t       *hit_keys;    // (d2 bits << 32) | candidate position
     uint32_t       *hit_vals;    // storage row
     uint64_t        seg_stride;
+    // optional [nq]: PACKED segments -- query q's begins at seg_off[q] instead of q * seg_stride (range_seg_base; the partition
+    // range search, whose segment lengths are its per-query candidate counts).  nullptr: the uniform stride.
+    const uint64_t *seg_off;
 };
+// the first entry of query q's hit segment, for the kernel that appends (emit_range_hit) and the ones that sort and write out
+__host__ __device__ __forceinline__ uint64_t range_seg_base(const uint64_t *seg_off, uint64_t seg_stride, uint32_t q) {
+    return seg_off ? seg_off[q] : (uint64_t)q * seg_stride;
+}
 
 // Streaming exact-order squared-L2 pass (the re-rank kernel).  Returns hipError_t.
 hipError_t launch_stream(const StreamArgs &a, StreamMode mode, hipStream_t s);
@@ -198,6 +205,13 @@ struct DistinctArgs;
 struct GroupedArgs;
 hipError_t launch_partition_distinct_stream(const StreamArgs &a, const PartitionArgs &pa, const DistinctArgs &da, hipStream_t s);
 hipError_t launch_partition_grouped_stream(const StreamArgs &a, const PartitionArgs &pa, const GroupedArgs &ga, hipStream_t s);
+// Range search over a partition (kernels_partition_range.hip; pqv.h: pqv_range_search_partition): launch_partition_stream's grid
+// and sequence walk with STREAM_RANGE's output -- every considered row whose output-scale distance is <= a.radius (a.sqrt_out as
+// StreamArgs documents it; PQV_DOT: dist <= radius) is appended, as (l2_key / dot_key of the sequence position, storage row), to
+// query q's segment of a.hit_keys / a.hit_vals at range_seg_base(a.seg_off, a.seg_stride, q), slot from one atomicAdd per wave and
+// tile on a.hit_cnt[q] (zeroed by the caller).  A segment must hold n_cand[q] entries.  a.k / part_keys / part_vals are not read;
+// a.nprobe must be 1.  Every wave adds the rows it evaluated to embeddings_fetched.  The segments go to launch_range_sort_*.
+hipError_t launch_partition_range(const StreamArgs &a, const PartitionArgs &pa, hipStream_t s);
 
 // ---- expanding filtered top-k (kernels_expand.hip; pqv.h: pqv_topk_expand) ------------------------------------------------
 // filter_count_kernel: cnt[q * P + j] = the positions of list probe[q * P + j] that pass the call's filter -- the set bits of
@@ -1063,6 +1077,7 @@ struct RangeSortArgs {
     uint64_t       *keys;         // [nq * seg_stride] (StreamArgs::hit_keys)
     uint32_t       *vals;
     uint64_t        seg_stride;
+    const uint64_t *seg_off;      // optional [nq]: packed segments (StreamArgs::seg_off); nullptr: q * seg_stride
     uint64_t       *alt_keys;     // second buffer of the long segments, RangeSeg::alt_off
     uint32_t       *alt_vals;
     const RangeSeg *segs;         // [n_segs] long segments
@@ -1097,5 +1112,6 @@ hipError_t touch_kpp(hipStream_t s);
 hipError_t touch_range(hipStream_t s);
 hipError_t touch_mask(hipStream_t s);
 hipError_t touch_predicate(hipStream_t s);
+hipError_t touch_partition_range(hipStream_t s);
 
 }  // namespace pqv

@@ -6,6 +6,8 @@
 //   range_merge_kernel        ... then sorted runs of width w merged pairwise into runs of 2w (merge path, 8 outputs a
 //                             thread), ping-pong between the segment buffer and a compact second buffer
 //   range_write_kernel        ... and the first min(n, max_results) entries written out
+// A segment begins at range_seg_base(seg_off, seg_stride, q): q * seg_stride, or -- the partition range search's packed segments --
+// seg_off[q].
 #include "device_common.hpp"
 
 namespace pqv {
@@ -60,8 +62,9 @@ __global__ __launch_bounds__(RS_THREADS) void range_sort_small_kernel(const Rang
     const uint32_t n = a.hit_cnt[q];
     if (n == 0 || n > RANGE_SMALL) return;
     const uint32_t n2 = pow2_at_least(n);
-    const uint64_t *gk = a.keys + (uint64_t)q * a.seg_stride;
-    const uint32_t *gv = a.vals + (uint64_t)q * a.seg_stride;
+    const uint64_t seg = range_seg_base(a.seg_off, a.seg_stride, q);
+    const uint64_t *gk = a.keys + seg;
+    const uint32_t *gv = a.vals + seg;
     for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
         sk[i] = i < n ? gk[i] : KEY_EMPTY;
         sv[i] = i < n ? gv[i] : 0xFFFFFFFFu;
@@ -80,8 +83,9 @@ __global__ __launch_bounds__(RS_THREADS) void range_tile_sort_kernel(const Range
     const uint64_t t0 = (uint64_t)blockIdx.x * RANGE_SMALL;
     if (t0 >= sg.n) return;
     const uint32_t m = (uint32_t)((sg.n - t0 < RANGE_SMALL) ? sg.n - t0 : RANGE_SMALL);
-    uint64_t *gk = a.keys + (uint64_t)sg.q * a.seg_stride + t0;
-    uint32_t *gv = a.vals + (uint64_t)sg.q * a.seg_stride + t0;
+    const uint64_t seg = range_seg_base(a.seg_off, a.seg_stride, sg.q);
+    uint64_t *gk = a.keys + seg + t0;
+    uint32_t *gv = a.vals + seg + t0;
     const uint32_t n2 = pow2_at_least(m);
     for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
         sk[i] = i < m ? gk[i] : KEY_EMPTY;
@@ -99,8 +103,9 @@ __global__ __launch_bounds__(RS_THREADS) void range_merge_kernel(const RangeSort
     const uint64_t n = sg.n;
     const uint64_t o0 = ((uint64_t)blockIdx.x * RS_THREADS + threadIdx.x) * RS_ITEMS;
     if (o0 >= n) return;
-    uint64_t *mk = a.keys + (uint64_t)sg.q * a.seg_stride;
-    uint32_t *mv = a.vals + (uint64_t)sg.q * a.seg_stride;
+    const uint64_t seg = range_seg_base(a.seg_off, a.seg_stride, sg.q);
+    uint64_t *mk = a.keys + seg;
+    uint32_t *mv = a.vals + seg;
     uint64_t *xk = a.alt_keys + sg.alt_off;
     uint32_t *xv = a.alt_vals + sg.alt_off;
     const uint64_t *sk = to_alt ? mk : xk;
@@ -133,7 +138,7 @@ __global__ __launch_bounds__(RS_THREADS) void range_write_kernel(const RangeSort
     const RangeSeg sg = a.segs[blockIdx.y];
     const uint64_t i = (uint64_t)blockIdx.x * RS_THREADS + threadIdx.x;
     if (i >= kept_of(a, sg.n)) return;
-    const uint64_t src = from_alt ? sg.alt_off + i : (uint64_t)sg.q * a.seg_stride + i;
+    const uint64_t src = from_alt ? sg.alt_off + i : range_seg_base(a.seg_off, a.seg_stride, sg.q) + i;
     write_hit(a, a.out_off[sg.q] + i, from_alt ? a.alt_keys[src] : a.keys[src], from_alt ? a.alt_vals[src] : a.vals[src]);
 }
 

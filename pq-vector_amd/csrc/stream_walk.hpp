@@ -482,7 +482,7 @@ __device__ __forceinline__ void emit_range_hit(const StreamArgs &a, uint32_t q, 
         base = (uint32_t)__shfl((int)base, 0, 64);
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         if (hit) {
-            const uint64_t o = (uint64_t)q * a.seg_stride + base + rank;
+            const uint64_t o = range_seg_base(a.seg_off, a.seg_stride, q) + base + rank;
             a.hit_keys[o] = key;
             a.hit_vals[o] = my_srow;
         }

@@ -354,6 +354,23 @@ public:
         check(pqv_topk_partition(s.get(), h_.get(), &d, mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), k, PQV_L2SQ_REF4, 1,
                                  rows.data(), dist.data(), found.data(), nullptr));
     }
+    // every partition row whose key passes the query's filter within `radius` of the query -- and, with `mask`, that the mask allows
+    // (pqv.h: pqv_range_search_partition): exact, ascending by (distance, sequence position); query q's hits are rows / dist
+    // [lims[q], lims[q + 1]); max_results > 0 keeps the first max_results of each query
+    void range_search(const Searcher &s, const KeyFilter &filter, const std::vector<float> &queries, float radius, std::vector<uint64_t> &lims,
+                      std::vector<uint32_t> &rows, std::vector<float> &dist, const RowMask *mask = nullptr, uint64_t max_results = 0) const {
+        const uint32_t nq = filter.queries();
+        const pqv_key_filter d = filter.descriptor();
+        uint64_t *l = nullptr;
+        uint32_t *r = nullptr;
+        float *x = nullptr;
+        check(pqv_range_search_partition(s.get(), h_.get(), &d, mask ? mask->get() : nullptr, queries.data(), nq, s.dim(), radius, max_results,
+                                         PQV_L2SQ_REF4, 1, &l, &r, &x, nullptr, nullptr));
+        lims.assign(l, l + nq + 1);
+        rows.assign(r, r + lims[nq]);
+        dist.assign(x, x + lims[nq]);
+        pqv_range_free(l, r, x);
+    }
 private:
     struct Del { void operator()(pqv_key_partition *p) const { pqv_key_partition_free(p); } };
     std::unique_ptr<pqv_key_partition, Del> h_;
