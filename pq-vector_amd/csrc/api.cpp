@@ -6312,19 +6312,26 @@ extern "C" void pqv_key_partition_free(pqv_key_partition *p) {
     delete p;
 }
 
-// The checks of both forms, in the contract's order; nothing is dereferenced before the NULL checks.  query_len: the host form's.
-static int partition_checks(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask, uint32_t nq,
-                            uint32_t k, int metric, bool host, uint32_t query_len) {
+// The checks of every partition entry point, in the contract's order: every NULL and zero check before a handle is read.
+// group_size: a grouped call's (gk is then one of its handles), else nullptr; query_len: a host form's; limit: the entry's own bound
+// on its lists, k (* group_size) <= 1024 -- nullptr for the range call, which has no k and passes 1.
+static int partition_checks(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_keys *gk,
+                            const uint32_t *group_size, const pqv_row_mask *mask, uint32_t nq, uint32_t k, int metric, bool host,
+                            uint32_t query_len, const char *limit) {
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     if (!part) return fail(PQV_ERR_INVALID, "key partition must not be NULL");
+    if (group_size && !gk) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
     if (int rc = filter_descriptor_checks(f, nq, host)) return rc;
     if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (group_size && *group_size == 0) return fail(PQV_ERR_INVALID, "group_size must be > 0");
     if (part->owner != s || part->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "key partition belongs to another searcher");
+    if (group_size && (gk->owner != s || gk->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
     if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
     if (int rc = validate_topk(s, k, 1, metric)) return rc;
     if (host && query_len != s->dim)
         return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) + ", got " + std::to_string(query_len));
-    if (k > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_partition takes k <= 1024");
+    if (group_size && metric == PQV_DOT) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
+    if (limit && static_cast<uint64_t>(k) * (group_size ? *group_size : 1u) > 1024) return fail(PQV_ERR_UNSUPPORTED, limit);
     return PQV_OK;
 }
 // blocks per query of partition_stream_kernel: the grid cannot follow span lengths only the device knows, so it comes from the batch
@@ -6337,52 +6344,146 @@ static uint32_t partition_blocks(const pqv_searcher *s, uint32_t nq, uint32_t k,
     b = std::min<uint64_t>(b, std::max<uint32_t>(1, 4096 / k));
     return static_cast<uint32_t>(std::max<uint64_t>(1, b));
 }
-// Enqueue span -> stream -> fold for the queries [0, nq) on `stream`, in pieces of at most PARTITION_GRID_Q queries (the grid's y).
-// `s`: the searcher whose rows are read (the call's, or its cosine searcher); a / b: the descriptor's DEVICE arrays.
+// The walk stage of every partition body.  A call runs in pieces of at most PARTITION_GRID_Q queries (the grid's y): size() sizes,
+// once, the scratch that does not depend on the piece; launch() pads a piece's queries where the stored rows are padded, launches
+// the span kernel and fills the arguments of the walk that follows -- StreamArgs' common fields (the caller adds k,
+// blocks_per_list and its outputs) and all of PartitionArgs.  `s`: the searcher whose rows are read (the call's, or its cosine
+// searcher).  Nothing is counted here: launch() is one launch, two where padded().
 constexpr uint32_t PARTITION_GRID_Q = 32768;
-static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
-                             const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
-                             uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
-    using namespace pqv;
-    const uint32_t piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
-    const uint32_t B = partition_blocks(s, piece, k, part->m);
-    const uint32_t n_part = B * waves_per_block();
-    const size_t span_slots = static_cast<size_t>(piece) * (kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u);
-    HIP_TRY(sc.s_pt_beg.ensure(span_slots * sizeof(uint32_t)));
-    if (kind == PQV_KEY_IN) {
-        HIP_TRY(sc.s_pt_end.ensure(span_slots * sizeof(uint32_t)));
-        HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+struct PartitionWalk {
+    const pqv_searcher *s;
+    Scratch &sc;
+    const pqv_key_partition *part;
+    uint32_t kind;
+    const uint64_t *bits;
+    int metric;
+    hipStream_t stream;
+    uint32_t piece = 0;
+
+    uint32_t span_w() const { return kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u; }      // span slots per query
+    bool padded() const { return s->sdim != s->dim; }
+    int size(uint32_t nq) {
+        piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
+        HIP_TRY(sc.s_pt_beg.ensure(static_cast<size_t>(piece) * span_w() * sizeof(uint32_t)));
+        if (kind == PQV_KEY_IN) {
+            HIP_TRY(sc.s_pt_end.ensure(static_cast<size_t>(piece) * span_w() * sizeof(uint32_t)));
+            HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+        }
+        HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
+        if (padded()) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
+        return PQV_OK;
     }
-    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
-    HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(piece) * n_part * k + 4) * sizeof(uint64_t)));
-    HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(piece) * n_part * k + 4) * sizeof(uint32_t)));
-    if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
-    for (uint32_t q0 = 0; q0 < nq; q0 += piece) {
-        const uint32_t b = std::min<uint32_t>(piece, nq - q0);
-        const float *dq = d_queries + static_cast<size_t>(q0) * s->dim;
-        if (s->sdim != s->dim) {      // (the stored rows are zero-padded: the queries that meet them too)
+    // the b queries at dq, with d_a / d_b as the span kernel indexes them from this piece's first query
+    int launch(const float *dq, uint32_t b, const void *d_a, const void *d_b, uint64_t *d_n_cand_out, pqv::StreamArgs &ra,
+               pqv::PartitionArgs &pa) const {
+        using namespace pqv;
+        if (padded()) {      // (the stored rows are zero-padded: the queries that meet them too)
             HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), stream));
             dq = sc.s_qpad.as<float>();
         }
         PartitionSpanArgs sp{};
         sp.keys = part->d_keys.as<int64_t>(); sp.key_off = part->d_off.as<uint64_t>(); sp.n_keys = part->n_keys;
-        sp.nq = b; sp.kind = kind;
-        // (every kind's a is indexed by query -- an IN filter's lims hold offsets into ALL of b, so a piece takes a + q0 and b as it is)
-        sp.a = static_cast<const char *>(d_a) + static_cast<size_t>(q0) * 8;
-        sp.b = kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + static_cast<size_t>(q0) * 8) : d_b;
+        sp.nq = b; sp.kind = kind; sp.a = d_a; sp.b = d_b;
         sp.span_beg = sc.s_pt_beg.as<uint32_t>(); sp.span_end = sc.s_pt_end.as<uint32_t>(); sp.n_span = sc.s_pt_nspan.as<uint32_t>();
-        sp.n_cand = sc.s_ncand.as<uint64_t>(); sp.n_cand_out = d_n_cand ? d_n_cand + q0 : nullptr;
+        sp.n_cand = sc.s_ncand.as<uint64_t>(); sp.n_cand_out = d_n_cand_out;
         sp.stats = s->d_stats.as<unsigned long long>();
         HIP_TRY(launch_partition_span(sp, stream));
-
-        StreamArgs ra{};
+        ra = StreamArgs{};
         ra.mat = s->d_mat; ra.row_of = s->d_row_of;
-        ra.queries = dq; ra.nq = b; ra.nprobe = 1; ra.dim = s->sdim; ra.k = k;
-        ra.rows_per_block = 256; ra.blocks_per_list = B; ra.max_pos = ~0ull; ra.metric = metric;
-        ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
-        PartitionArgs pa{};
+        ra.queries = dq; ra.nq = b; ra.nprobe = 1; ra.dim = s->sdim;
+        ra.rows_per_block = 256; ra.max_pos = ~0ull; ra.metric = metric;
+        pa = PartitionArgs{};
         pa.pos = part->d_pos.as<uint32_t>(); pa.span_beg = sp.span_beg; pa.span_end = sp.span_end; pa.n_span = sp.n_span;
-        pa.n_cand = sp.n_cand; pa.kind = kind; pa.bits = bits; pa.stats = s->d_stats.as<unsigned long long>();
+        pa.n_cand = sp.n_cand; pa.kind = kind; pa.bits = bits; pa.stats = sp.stats;
+        return PQV_OK;
+    }
+    // the piece [q0, q0 + b) of a call whose queries, a / b and n_cand are whole DEVICE arrays: every kind's a is indexed by query --
+    // an IN filter's lims hold offsets into ALL of b -- so a piece takes a + q0 and, but for a RANGE filter's, b as it is
+    int launch_at(uint32_t q0, uint32_t b, const float *d_queries, const void *d_a, const void *d_b, uint64_t *d_n_cand, pqv::StreamArgs &ra,
+                  pqv::PartitionArgs &pa) const {
+        const size_t off = static_cast<size_t>(q0) * 8;
+        return launch(d_queries + static_cast<size_t>(q0) * s->dim, b, static_cast<const char *>(d_a) + off,
+                      kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + off) : d_b,
+                      d_n_cand ? d_n_cand + q0 : nullptr, ra, pa);
+    }
+};
+// A device form behind its checks: the lock, the lane, body(searcher, scratch, queries, metric, sqrt_out) and the queries counted.
+// PQV_COSINE: n(q) into this searcher's lane, then the L2 body on the cosine searcher (sqrt_out 2) under ITS lock and lane, taken
+// second and released first.
+template <class Body>
+static int partition_device_call(const pqv_searcher *s, const float *d_queries, uint32_t nq, int metric, int sqrt_out, hipStream_t stream, Body body) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    Lane lane;
+    if (metric == PQV_COSINE) {
+        if (int rc = cosine_queries_device(s, d_queries, nq, stream, lane)) return rc;
+        const pqv_searcher *cs = s->cos.get();
+        std::lock_guard<std::mutex> cos_lock(cs->mu);
+        Lane cos_lane;
+        if (int rc = cos_lane.acquire(cs, stream)) return rc;
+        if (int rc = body(cs, *cos_lane, lane->s_qcos.as<float>(), PQV_L2SQ_REF4, 2)) return rc;
+        cs->counters.queries += nq;
+        if (int rc = cos_lane.release()) return rc;
+        return lane.release();
+    }
+    if (int rc = lane.acquire(s, stream)) return rc;
+    if (int rc = body(s, *lane, d_queries, metric, sqrt_out)) return rc;
+    s->counters.queries += nq;
+    return lane.release();
+}
+// the descriptor's host arrays as a request, for the sub-batches' (pieces') slices: upload_query_filter
+static SearchRequest partition_request(const pqv_key_filter *f) {
+    SearchRequest rq{};
+    rq.rows.kind = f->kind;
+    if (f->kind == PQV_KEY_EQ) rq.rows.h_qkeys = static_cast<const int64_t *>(f->a);
+    else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
+    return rq;
+}
+// The host form of both top-k calls: PQV_COSINE's n(q), the lane, sub-batches of queries through it (their filter slices uploaded
+// as pqv_topk_filtered uploads them), enqueue(s, sc, bits, d_a, d_b, b, metric, sqrt_out) -- the device body on a sub-batch's
+// scratch -- and outs(sc) back.  The sub-batch is bounded so the scratch stays under ~1 GiB: per query the B * 4 per-wave lists of
+// k_lists entries, list_bytes in all passes' widest, the padded query, and out_bytes of outputs and filter slice.
+template <class Outs, class Enqueue>
+static int topk_partition_host_body(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask,
+                                    const float *queries, uint32_t nq, uint32_t k_lists, int metric, int sqrt_out, uint64_t list_bytes,
+                                    uint64_t out_bytes, Outs outs, Enqueue enqueue) {
+    std::vector<float> nq_host;
+    if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
+    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+    std::lock_guard<std::mutex> lock(s->mu);
+    Lane lane;
+    if (int rc = lane.acquire(s, s->stream)) return rc;
+    Scratch &sc = *lane;
+    const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), k_lists, part->m);
+    const uint64_t per_query = static_cast<uint64_t>(B) * 4 * list_bytes + static_cast<uint64_t>(s->sdim) * 8 + out_bytes;
+    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
+    const SearchRequest rq = partition_request(f);
+    if (int rc = host_batches(
+            s, sc, queries, nq, batch, &rq, nullptr, outs(sc),
+            [&](uint32_t b, SearchRequest *brq) { return enqueue(s, sc, bits, brq->d_filter_a(), brq->d_filter_b(), b, metric, sqrt_out); },
+            [](uint32_t, uint32_t) { return static_cast<int>(PQV_OK); }))      // (no host step)
+        return rc;
+    return lane.release();
+}
+
+// ---- top-k over a key partition (pqv.h: pqv_topk_partition) ----------------------------------------------------------------------
+// Enqueue span -> stream -> fold for the queries [0, nq) on `stream`, in PartitionWalk's pieces.  a / b: the descriptor's DEVICE arrays.
+static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
+                             const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
+                             uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+    using namespace pqv;
+    PartitionWalk w{s, sc, part, kind, bits, metric, stream};
+    if (int rc = w.size(nq)) return rc;
+    const uint32_t B = partition_blocks(s, w.piece, k, part->m);
+    const uint32_t n_part = B * waves_per_block();
+    HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(w.piece) * n_part * k + 4) * sizeof(uint64_t)));
+    HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(w.piece) * n_part * k + 4) * sizeof(uint32_t)));
+    for (uint32_t q0 = 0; q0 < nq; q0 += w.piece) {
+        const uint32_t b = std::min<uint32_t>(w.piece, nq - q0);
+        StreamArgs ra;
+        PartitionArgs pa;
+        if (int rc = w.launch_at(q0, b, d_queries, d_a, d_b, d_n_cand, ra, pa)) return rc;
+        ra.k = k; ra.blocks_per_list = B;
+        ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
         HIP_TRY(launch_partition_stream(ra, pa, stream));
 
         MergeArgs fm{};
@@ -6397,38 +6498,20 @@ static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_p
     }
     return PQV_OK;
 }
-// the device form behind its checks; PQV_COSINE: n(q) into this searcher's lane, then the L2 body on the cosine searcher (sqrt_out 2)
+// the device form behind its checks
 static int topk_partition_device_impl(const pqv_searcher *s, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
                                       const pqv_row_mask *mask, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
                                       uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
     const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
-    std::lock_guard<std::mutex> lock(s->mu);
-    Lane lane;
-    if (metric == PQV_COSINE) {
-        if (int rc = cosine_queries_device(s, d_queries, nq, stream, lane)) return rc;
-        const pqv_searcher *cs = s->cos.get();
-        std::lock_guard<std::mutex> cos_lock(cs->mu);
-        Lane cos_lane;
-        if (int rc = cos_lane.acquire(cs, stream)) return rc;
-        if (int rc = enqueue_partition(cs, *cos_lane, part, kind, d_a, d_b, bits, lane->s_qcos.as<float>(), nq, k, PQV_L2SQ_REF4, 2, d_row_idx, d_dist,
-                                       d_n_found, d_n_cand, stream))
-            return rc;
-        cs->counters.queries += nq;
-        if (int rc = cos_lane.release()) return rc;
-        return lane.release();
-    }
-    if (int rc = lane.acquire(s, stream)) return rc;
-    if (int rc = enqueue_partition(s, *lane, part, kind, d_a, d_b, bits, d_queries, nq, k, metric, sqrt_out, d_row_idx, d_dist, d_n_found, d_n_cand,
-                                   stream))
-        return rc;
-    s->counters.queries += nq;
-    return lane.release();
+    return partition_device_call(s, d_queries, nq, metric, sqrt_out, stream, [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
+        return enqueue_partition(bs, sc, part, kind, d_a, d_b, bits, q, nq, k, mt, so, d_row_idx, d_dist, d_n_found, d_n_cand, stream);
+    });
 }
 extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
                                          const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
                                          void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates, void *hip_stream) {
     return guard([&] {
-        if (int rc = partition_checks(s, part, filter, mask, nq, k, metric, false, 0)) return rc;
+        if (int rc = partition_checks(s, part, filter, nullptr, nullptr, mask, nq, k, metric, false, 0, "pqv_topk_partition takes k <= 1024")) return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
         if (int rc = use_device(s->device)) return rc;
@@ -6438,54 +6521,31 @@ extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_pa
                                           static_cast<uint32_t *>(d_n_found), static_cast<uint64_t *>(d_n_candidates), stream);
     });
 }
-// The host form: sub-batches of queries through the lane (their filter slices uploaded as pqv_topk_filtered uploads them), the
-// device body, and the results back.
-static int topk_partition_host_impl(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask,
-                                    const float *queries, uint32_t nq, uint32_t k, int metric, int sqrt_out, uint32_t *row_idx, float *dist,
-                                    uint32_t *n_found, uint64_t *n_candidates) {
-    std::vector<float> nq_host;
-    if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
-    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
-    std::lock_guard<std::mutex> lock(s->mu);
-    Lane lane;
-    if (int rc = lane.acquire(s, s->stream)) return rc;
-    Scratch &sc = *lane;
-    // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
-    const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), k, part->m);
-    const uint64_t per_query = static_cast<uint64_t>(B) * 4 * k * 12 + static_cast<uint64_t>(s->sdim) * 8 + 12ull * k + 8 * PQV_KEY_SET_MAX;
-    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
-    SearchRequest rq{};      // the descriptor's host arrays, for the sub-batches' slices
-    rq.rows.kind = f->kind;
-    if (f->kind == PQV_KEY_EQ) rq.rows.h_qkeys = static_cast<const int64_t *>(f->a);
-    else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
-    if (int rc = host_batches(
-            s, sc, queries, nq, batch, &rq, nullptr,
-            {{&sc.s_rows, k * sizeof(uint32_t), row_idx}, {&sc.s_dist, k * sizeof(float), dist}, {&sc.s_nfound, sizeof(uint32_t), n_found},
-             {&sc.s_out, sizeof(uint64_t), n_candidates}},
-            [&](uint32_t b, SearchRequest *brq) {
-                return enqueue_partition(s, sc, part, f->kind, brq->d_filter_a(), brq->d_filter_b(), bits, sc.s_queries.as<float>(), b, k, metric,
-                                         sqrt_out, sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(),
-                                         sc.s_out.as<uint64_t>(), s->stream);
-            },
-            [](uint32_t, uint32_t) { return static_cast<int>(PQV_OK); }))      // (no host step)
-        return rc;
-    return lane.release();
-}
 extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter, const pqv_row_mask *mask,
                                   const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, int metric, int sqrt_out,
                                   uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
-        if (int rc = partition_checks(s, part, filter, mask, nq, k, metric, true, query_len)) return rc;
+        if (int rc = partition_checks(s, part, filter, nullptr, nullptr, mask, nq, k, metric, true, query_len, "pqv_topk_partition takes k <= 1024")) return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
         if (int rc = use_device(s->device)) return rc;
-        return topk_partition_host_impl(s, part, filter, mask, queries, nq, k, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates);
+        // (per list entry 12 B; beside the lists the rows, distances and n_found / n_candidates, and an IN slice)
+        return topk_partition_host_body(
+            s, part, filter, mask, queries, nq, k, metric, sqrt_out ? 1 : 0, 12ull * k, 12ull * k + 8 * PQV_KEY_SET_MAX,
+            [&](Scratch &sc) {
+                return std::vector<BatchOut>{{&sc.s_rows, k * sizeof(uint32_t), row_idx}, {&sc.s_dist, k * sizeof(float), dist},
+                                             {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates}};
+            },
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
+                return enqueue_partition(bs, sc, part, filter->kind, d_a, d_b, bits, sc.s_queries.as<float>(), b, k, mt, so, sc.s_rows.as<uint32_t>(),
+                                         sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(), bs->stream);
+            });
     });
 }
 
 // ---- range search over a key partition (pqv.h: pqv_range_search_partition) --------------------------------------------------------
-// Per piece of at most PARTITION_GRID_Q queries: the queries and the filter slice uploaded as topk_partition_host_impl uploads them,
-// ONE span launch, and n_cand [b] brought back -- the one synchronisation this call has over range_body: the hit segments are
+// Per piece of PartitionWalk: the queries and the filter slice uploaded as the top-k host form uploads them, the walk stage's ONE
+// span launch, and n_cand [b] brought back -- the one synchronisation this call has over range_body: the hit segments are
 // PACKED, query q's holds n_cand[q] entries, and the grid follows the longest sequence.  The piece is then cut into groups of
 // consecutive queries whose segments fit the byte budget (12 B an entry; partition_range_bytes, 0 = 1 GiB; a query whose own segment
 // exceeds it runs alone).  Per group: hit_cnt zeroed, partition_range_kernel on the group's slice of the span arrays, the counts
@@ -6498,26 +6558,16 @@ static int range_partition_body(const pqv_searcher *s, Scratch &sc, const pqv_ke
                                 uint64_t *n_candidates) {
     using namespace pqv;
     hipStream_t st = s->stream;
-    const uint32_t kind = f->kind;
     const uint64_t budget = s->opt.partition_range_bytes ? s->opt.partition_range_bytes : (1ull << 30);
-    const uint32_t piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
-    const uint32_t span_w = kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u;      // span slots per query
+    PartitionWalk w{s, sc, part, f->kind, bits, metric, st};
+    if (int rc = w.size(nq)) return rc;
+    const uint32_t piece = w.piece, span_w = w.span_w();
     HIP_TRY(sc.s_queries.ensure(static_cast<size_t>(piece) * s->dim * sizeof(float)));
-    if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
-    HIP_TRY(sc.s_pt_beg.ensure(static_cast<size_t>(piece) * span_w * sizeof(uint32_t)));
-    if (kind == PQV_KEY_IN) {
-        HIP_TRY(sc.s_pt_end.ensure(static_cast<size_t>(piece) * span_w * sizeof(uint32_t)));
-        HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
-    }
-    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
     HIP_TRY(sc.s_hit_cnt.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
     HIP_TRY(sc.s_rout_off.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
     HIP_TRY(sc.s_seg_off.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
-    SearchRequest rq{}, sub{};      // the descriptor's host arrays, for the pieces' slices
-    rq.rows.kind = kind;
-    if (kind == PQV_KEY_EQ) rq.rows.h_qkeys = static_cast<const int64_t *>(f->a);
-    else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
-    sub = rq;
+    const SearchRequest rq = partition_request(f);
+    SearchRequest sub = rq;
     std::vector<uint64_t> sub_lims, h_ncand(piece), h_off(piece), h_seg(piece);
     std::vector<uint32_t> h_cnt(piece);
     std::vector<RangeSeg> segs;
@@ -6532,21 +6582,11 @@ static int range_partition_body(const pqv_searcher *s, Scratch &sc, const pqv_ke
                                hipMemcpyHostToDevice, st));
         if (int rc = upload_query_filter(sc, &rq, sub, q0, b, sub_lims, st)) return rc;
         if (e[0]) HIP_TRY(hipEventRecord(e[0], st));
-        const float *dq = sc.s_queries.as<float>();
-        if (s->sdim != s->dim) {      // (the stored rows are zero-padded: the queries that meet them too)
-            HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), st));
-            dq = sc.s_qpad.as<float>();
-            ++launches;
-        }
-        PartitionSpanArgs sp{};
-        sp.keys = part->d_keys.as<int64_t>(); sp.key_off = part->d_off.as<uint64_t>(); sp.n_keys = part->n_keys;
-        sp.nq = b; sp.kind = kind;
-        sp.a = sub.d_filter_a(); sp.b = sub.d_filter_b();       // (the piece's own slice: an IN filter's lims are rebased)
-        sp.span_beg = sc.s_pt_beg.as<uint32_t>(); sp.span_end = sc.s_pt_end.as<uint32_t>(); sp.n_span = sc.s_pt_nspan.as<uint32_t>();
-        sp.n_cand = sc.s_ncand.as<uint64_t>();
-        sp.stats = s->d_stats.as<unsigned long long>();
-        HIP_TRY(launch_partition_span(sp, st));
-        ++launches;
+        StreamArgs pra;      // the piece's walk: every group runs on a slice of it
+        PartitionArgs ppa;
+        // (the piece's own filter slice: an IN filter's lims are rebased)
+        if (int rc = w.launch(sc.s_queries.as<float>(), b, sub.d_filter_a(), sub.d_filter_b(), nullptr, pra, ppa)) return rc;
+        launches += w.padded() ? 2 : 1;
         HIP_TRY(hipMemcpyAsync(h_ncand.data(), sc.s_ncand.p, static_cast<size_t>(b) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (n_candidates) std::copy(h_ncand.begin(), h_ncand.begin() + b, n_candidates + q0);
@@ -6582,19 +6622,17 @@ static int range_partition_body(const pqv_searcher *s, Scratch &sc, const pqv_ke
             // blocks per query: the option, or by rule about 2048 blocks for the group and no more than the longest sequence's turns
             uint64_t B = s->opt.partition_blocks;
             if (!B) B = std::min<uint64_t>((2048 + static_cast<uint64_t>(gb) - 1) / gb, (longest + 255) / 256);
-            StreamArgs ra{};
-            ra.mat = s->d_mat; ra.row_of = s->d_row_of;
-            ra.queries = dq + static_cast<size_t>(g0) * s->sdim; ra.nq = gb; ra.nprobe = 1; ra.dim = s->sdim; ra.k = 1;
-            ra.rows_per_block = 256; ra.blocks_per_list = static_cast<uint32_t>(std::max<uint64_t>(1, B)); ra.max_pos = ~0ull; ra.metric = metric;
+            StreamArgs ra = pra;
+            ra.queries = pra.queries + static_cast<size_t>(g0) * s->sdim; ra.nq = gb; ra.k = 1;
+            ra.blocks_per_list = static_cast<uint32_t>(std::max<uint64_t>(1, B));
             ra.radius = radius; ra.sqrt_out = sqrt_out;
             ra.hit_cnt = sc.s_hit_cnt.as<uint32_t>(); ra.hit_keys = sc.s_hit_keys.as<uint64_t>(); ra.hit_vals = sc.s_hit_vals.as<uint32_t>();
             ra.seg_stride = 0; ra.seg_off = sc.s_seg_off.as<uint64_t>();
-            PartitionArgs pa{};
-            pa.pos = part->d_pos.as<uint32_t>();
+            PartitionArgs pa = ppa;
             // (the span arrays are indexed by the piece's query: IN keeps KEY_SET_MAX slots a query)
-            pa.span_beg = sp.span_beg + static_cast<size_t>(g0) * span_w;
-            if (kind == PQV_KEY_IN) { pa.span_end = sp.span_end + static_cast<size_t>(g0) * span_w; pa.n_span = sp.n_span + g0; }
-            pa.n_cand = sp.n_cand + g0; pa.kind = kind; pa.bits = bits; pa.stats = s->d_stats.as<unsigned long long>();
+            pa.span_beg = ppa.span_beg + static_cast<size_t>(g0) * span_w;
+            if (w.kind == PQV_KEY_IN) { pa.span_end = ppa.span_end + static_cast<size_t>(g0) * span_w; pa.n_span = ppa.n_span + g0; }
+            pa.n_cand = ppa.n_cand + g0;
             if (e[1]) HIP_TRY(hipEventRecord(e[1], st));
             HIP_TRY(launch_partition_range(ra, pa, st));
             ++launches;
@@ -6611,17 +6649,12 @@ static int range_partition_body(const pqv_searcher *s, Scratch &sc, const pqv_ke
     }
     return PQV_OK;
 }
-// The checks in the contract's order: every NULL check before a handle is read or a device used, then pqv_range_search's own.
+// The family's checks (no k, no limit of its own), then pqv_range_search's own.
 static int range_search_partition_impl(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask,
                                        const float *queries, uint32_t nq, uint32_t query_len, float radius, uint64_t max_results, int metric,
                                        int sqrt_out, uint64_t **lims_out, uint32_t **rows_out, float **dist_out, uint64_t *n_within,
                                        uint64_t *n_candidates) {
-    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
-    if (!part) return fail(PQV_ERR_INVALID, "key partition must not be NULL");
-    if (int rc = filter_descriptor_checks(f, nq, true)) return rc;
-    if (part->owner != s || part->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "key partition belongs to another searcher");
-    if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
-    if (int rc = validate_query(s, 1, 1, metric, 0, query_len)) return rc;
+    if (int rc = partition_checks(s, part, f, nullptr, nullptr, mask, nq, 1, metric, true, query_len, nullptr)) return rc;
     if (metric == PQV_DOT) sqrt_out = 0;      // (ignored: the range_* kernels run as order-only machinery)
     if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
     if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
@@ -6660,27 +6693,7 @@ extern "C" int pqv_range_search_partition(const pqv_searcher *s, const pqv_key_p
 }
 
 // ---- distinct / grouped top-k over a key partition (pqv.h: pqv_topk_partition_grouped) ------------------------------------------
-// The checks of both forms, in the contract's order: every NULL and zero check before a handle is read.  query_len: the host form's.
-static int partition_group_checks(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_keys *gk,
-                                  const pqv_row_mask *mask, uint32_t nq, uint32_t k, uint32_t group_size, int metric, bool host,
-                                  uint32_t query_len) {
-    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
-    if (!part) return fail(PQV_ERR_INVALID, "key partition must not be NULL");
-    if (!gk) return fail(PQV_ERR_INVALID, "row keys must not be NULL");
-    if (int rc = filter_descriptor_checks(f, nq, host)) return rc;
-    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
-    if (group_size == 0) return fail(PQV_ERR_INVALID, "group_size must be > 0");
-    if (part->owner != s || part->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "key partition belongs to another searcher");
-    if (gk->owner != s || gk->owner_uid != s->uid) return fail(PQV_ERR_INVALID, "row keys belong to another searcher");
-    if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
-    if (int rc = validate_topk(s, k, 1, metric)) return rc;
-    if (host && query_len != s->dim)
-        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) + ", got " + std::to_string(query_len));
-    if (metric == PQV_DOT) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
-    if (static_cast<uint64_t>(k) * group_size > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_partition_grouped takes k * group_size <= 1024");
-    return PQV_OK;
-}
-// Enqueue both passes for the queries [0, nq) on `stream`, in enqueue_partition's pieces: the span kernel (once per piece), the
+// Enqueue both passes for the queries [0, nq) on `stream`, in PartitionWalk's pieces: the span kernel (once per piece), the
 // distinct stream and its fold, then for m > 1 the group set, the grouped stream and its fold -- or, for m == 1, the rows-per-group
 // fill where d_group_rows is asked for.  One B for both passes; every buffer of a piece is sized before its first kernel (the partial
 // lists of pass 2 take over those of pass 1).  `s`: the searcher whose rows are read; a / b: the descriptor's DEVICE arrays.
@@ -6689,19 +6702,14 @@ static int enqueue_partition_grouped(const pqv_searcher *s, Scratch &sc, const p
                                      uint32_t m, int metric, int sqrt_out, uint32_t *d_row_idx, float *d_dist, int64_t *d_group_key,
                                      uint32_t *d_group_rows, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
     using namespace pqv;
-    const uint32_t piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
-    const uint32_t km = k * m;                                              // (<= 1024: partition_group_checks)
+    PartitionWalk w{s, sc, part, kind, bits, metric, stream};
+    if (int rc = w.size(nq)) return rc;
+    const uint32_t piece = w.piece;
+    const uint32_t km = k * m;                                              // (<= 1024: partition_checks)
     const bool two_pass = m > 1;
     const uint32_t B = partition_blocks(s, piece, km, part->m);
     const uint32_t n_part = B * waves_per_block();
     const size_t n_lists = static_cast<size_t>(piece) * n_part;
-    const size_t span_slots = static_cast<size_t>(piece) * (kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u);
-    HIP_TRY(sc.s_pt_beg.ensure(span_slots * sizeof(uint32_t)));
-    if (kind == PQV_KEY_IN) {
-        HIP_TRY(sc.s_pt_end.ensure(span_slots * sizeof(uint32_t)));
-        HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
-    }
-    HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_keys.ensure((n_lists * km + 4) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_vals.ensure((n_lists * km + 4) * sizeof(uint32_t)));
     HIP_TRY(sc.s_part_grp.ensure((n_lists * k + 4) * sizeof(int64_t)));
@@ -6716,14 +6724,8 @@ static int enqueue_partition_grouped(const pqv_searcher *s, Scratch &sc, const p
     }
     const bool need_found = two_pass || d_group_rows;                       // (read by the group set / the rows-per-group fill)
     if (need_found && !d_n_found) HIP_TRY(sc.s_g1_nfound.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
-    if (s->sdim != s->dim) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
     for (uint32_t q0 = 0; q0 < nq; q0 += piece) {
         const uint32_t b = std::min<uint32_t>(piece, nq - q0);
-        const float *dq = d_queries + static_cast<size_t>(q0) * s->dim;
-        if (s->sdim != s->dim) {      // (the stored rows are zero-padded: the queries that meet them too)
-            HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), stream));
-            dq = sc.s_qpad.as<float>();
-        }
         // the piece's outputs: keys, counts and n_found at q0 * k / q0, rows and distances at q0 * k * m
         uint32_t *o_rows = d_row_idx + static_cast<size_t>(q0) * km;
         float *o_dist = d_dist + static_cast<size_t>(q0) * km;
@@ -6731,25 +6733,11 @@ static int enqueue_partition_grouped(const pqv_searcher *s, Scratch &sc, const p
         uint32_t *o_found = d_n_found ? d_n_found + q0 : need_found ? sc.s_g1_nfound.as<uint32_t>() : nullptr;
         uint32_t *o_grows = d_group_rows ? d_group_rows + static_cast<size_t>(q0) * k : nullptr;
 
-        PartitionSpanArgs sp{};
-        sp.keys = part->d_keys.as<int64_t>(); sp.key_off = part->d_off.as<uint64_t>(); sp.n_keys = part->n_keys;
-        sp.nq = b; sp.kind = kind;
-        // (every kind's a is indexed by query -- an IN filter's lims hold offsets into ALL of b, so a piece takes a + q0 and b as it is)
-        sp.a = static_cast<const char *>(d_a) + static_cast<size_t>(q0) * 8;
-        sp.b = kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + static_cast<size_t>(q0) * 8) : d_b;
-        sp.span_beg = sc.s_pt_beg.as<uint32_t>(); sp.span_end = sc.s_pt_end.as<uint32_t>(); sp.n_span = sc.s_pt_nspan.as<uint32_t>();
-        sp.n_cand = sc.s_ncand.as<uint64_t>(); sp.n_cand_out = d_n_cand ? d_n_cand + q0 : nullptr;
-        sp.stats = s->d_stats.as<unsigned long long>();
-        HIP_TRY(launch_partition_span(sp, stream));
-
-        StreamArgs ra{};
-        ra.mat = s->d_mat; ra.row_of = s->d_row_of;
-        ra.queries = dq; ra.nq = b; ra.nprobe = 1; ra.dim = s->sdim; ra.k = k;
-        ra.rows_per_block = 256; ra.blocks_per_list = B; ra.max_pos = ~0ull; ra.metric = metric;
+        StreamArgs ra;
+        PartitionArgs pa;
+        if (int rc = w.launch_at(q0, b, d_queries, d_a, d_b, d_n_cand, ra, pa)) return rc;
+        ra.k = k; ra.blocks_per_list = B;
         ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
-        PartitionArgs pa{};
-        pa.pos = part->d_pos.as<uint32_t>(); pa.span_beg = sp.span_beg; pa.span_end = sp.span_end; pa.n_span = sp.n_span;
-        pa.n_cand = sp.n_cand; pa.kind = kind; pa.bits = bits; pa.stats = s->d_stats.as<unsigned long long>();
         DistinctArgs da{};
         da.key_pos = gk->d_key_pos.p; da.valid_pos = gk->valid_image(); da.elem_size = gk->elem_size();
         da.part_grp = sc.s_part_grp.as<int64_t>();
@@ -6784,40 +6772,25 @@ static int enqueue_partition_grouped(const pqv_searcher *s, Scratch &sc, const p
     }
     return PQV_OK;
 }
-// the device form behind its checks; PQV_COSINE as topk_partition_device_impl takes it, the lock order included
+// the device form behind its checks
 static int topk_partition_grouped_device_impl(const pqv_searcher *s, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
                                               const pqv_row_keys *gk, const pqv_row_mask *mask, const float *d_queries, uint32_t nq, uint32_t k,
                                               uint32_t m, int metric, int sqrt_out, uint32_t *d_row_idx, float *d_dist, int64_t *d_group_key,
                                               uint32_t *d_group_rows, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
     const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
-    std::lock_guard<std::mutex> lock(s->mu);
-    Lane lane;
-    if (metric == PQV_COSINE) {
-        if (int rc = cosine_queries_device(s, d_queries, nq, stream, lane)) return rc;
-        const pqv_searcher *cs = s->cos.get();
-        std::lock_guard<std::mutex> cos_lock(cs->mu);
-        Lane cos_lane;
-        if (int rc = cos_lane.acquire(cs, stream)) return rc;
-        if (int rc = enqueue_partition_grouped(cs, *cos_lane, part, kind, d_a, d_b, gk, bits, lane->s_qcos.as<float>(), nq, k, m, PQV_L2SQ_REF4, 2,
-                                               d_row_idx, d_dist, d_group_key, d_group_rows, d_n_found, d_n_cand, stream))
-            return rc;
-        cs->counters.queries += nq;
-        if (int rc = cos_lane.release()) return rc;
-        return lane.release();
-    }
-    if (int rc = lane.acquire(s, stream)) return rc;
-    if (int rc = enqueue_partition_grouped(s, *lane, part, kind, d_a, d_b, gk, bits, d_queries, nq, k, m, metric, sqrt_out, d_row_idx, d_dist,
-                                           d_group_key, d_group_rows, d_n_found, d_n_cand, stream))
-        return rc;
-    s->counters.queries += nq;
-    return lane.release();
+    return partition_device_call(s, d_queries, nq, metric, sqrt_out, stream, [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
+        return enqueue_partition_grouped(bs, sc, part, kind, d_a, d_b, gk, bits, q, nq, k, m, mt, so, d_row_idx, d_dist, d_group_key, d_group_rows,
+                                         d_n_found, d_n_cand, stream);
+    });
 }
 extern "C" int pqv_topk_partition_grouped_device(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
                                                  const pqv_row_keys *group_keys, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
                                                  uint32_t k, uint32_t group_size, int metric, int sqrt_out, void *d_row_idx, void *d_dist,
                                                  void *d_group_key, void *d_group_rows, void *d_n_found, void *d_n_candidates, void *hip_stream) {
     return guard([&] {
-        if (int rc = partition_group_checks(s, part, filter, group_keys, mask, nq, k, group_size, metric, false, 0)) return rc;
+        if (int rc = partition_checks(s, part, filter, group_keys, &group_size, mask, nq, k, metric, false, 0,
+                                      "pqv_topk_partition_grouped takes k * group_size <= 1024"))
+            return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
         if (int rc = use_device(s->device)) return rc;
@@ -6829,55 +6802,37 @@ extern "C" int pqv_topk_partition_grouped_device(const pqv_searcher *s, const pq
                                                   static_cast<uint64_t *>(d_n_candidates), stream);
     });
 }
-// The host form: topk_partition_host_impl's sub-batches with the group outputs beside the rows; the sub-batch size is bounded from
-// the per-query scratch of BOTH passes (20 B per entry of pass 1's lists, 16 B per entry of k * m and a count in pass 2's).
-static int topk_partition_grouped_host_impl(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_keys *gk,
-                                            const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t k, uint32_t m, int metric,
-                                            int sqrt_out, uint32_t *row_idx, float *dist, int64_t *group_key, uint32_t *group_rows,
-                                            uint32_t *n_found, uint64_t *n_candidates) {
-    std::vector<float> nq_host;
-    if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
-    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
-    std::lock_guard<std::mutex> lock(s->mu);
-    Lane lane;
-    if (int rc = lane.acquire(s, s->stream)) return rc;
-    Scratch &sc = *lane;
-    const uint64_t km = static_cast<uint64_t>(k) * m;
-    const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), static_cast<uint32_t>(km), part->m);
-    const uint64_t per_query = static_cast<uint64_t>(B) * 4 * std::max<uint64_t>(std::max<uint64_t>(k * 20ull, km * 12), m > 1 ? km * 16 + 4 : 0) +
-                               static_cast<uint64_t>(s->sdim) * 8 + 32ull * k + 8 * km + 8 * PQV_KEY_SET_MAX + 16;
-    const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
-    SearchRequest rq{};      // the descriptor's host arrays, for the sub-batches' slices
-    rq.rows.kind = f->kind;
-    if (f->kind == PQV_KEY_EQ) rq.rows.h_qkeys = static_cast<const int64_t *>(f->a);
-    else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
-    std::vector<BatchOut> outs = {{&sc.s_rows, km * sizeof(uint32_t), row_idx}, {&sc.s_dist, km * sizeof(float), dist},
-                                  {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates},
-                                  {&sc.s_grp_out, k * sizeof(int64_t), group_key}};
-    if (group_rows) outs.push_back({&sc.s_grows_out, k * sizeof(uint32_t), group_rows});
-    if (int rc = host_batches(
-            s, sc, queries, nq, batch, &rq, nullptr, outs,
-            [&](uint32_t b, SearchRequest *brq) {
-                return enqueue_partition_grouped(s, sc, part, f->kind, brq->d_filter_a(), brq->d_filter_b(), gk, bits, sc.s_queries.as<float>(), b, k, m,
-                                                 metric, sqrt_out, sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_grp_out.as<int64_t>(),
-                                                 group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr, sc.s_nfound.as<uint32_t>(),
-                                                 sc.s_out.as<uint64_t>(), s->stream);
-            },
-            [](uint32_t, uint32_t) { return static_cast<int>(PQV_OK); }))      // (no host step)
-        return rc;
-    return lane.release();
-}
 extern "C" int pqv_topk_partition_grouped(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
                                           const pqv_row_keys *group_keys, const pqv_row_mask *mask, const float *queries, uint32_t nq,
                                           uint32_t query_len, uint32_t k, uint32_t group_size, int metric, int sqrt_out, uint32_t *row_idx,
                                           float *dist, int64_t *group_key, uint32_t *group_rows, uint32_t *n_found, uint64_t *n_candidates) {
     return guard([&] {
-        if (int rc = partition_group_checks(s, part, filter, group_keys, mask, nq, k, group_size, metric, true, query_len)) return rc;
+        if (int rc = partition_checks(s, part, filter, group_keys, &group_size, mask, nq, k, metric, true, query_len,
+                                      "pqv_topk_partition_grouped takes k * group_size <= 1024"))
+            return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
         if (int rc = use_device(s->device)) return rc;
-        return topk_partition_grouped_host_impl(s, part, filter, group_keys, mask, queries, nq, k, group_size, metric, sqrt_out ? 1 : 0, row_idx,
-                                                dist, group_key, group_rows, n_found, n_candidates);
+        // (the scratch of BOTH passes: 20 B per entry of pass 1's lists, 16 B per entry of k * m and a count in pass 2's; the group
+        // outputs beside the rows)
+        const uint32_t m = group_size;
+        const uint64_t km = static_cast<uint64_t>(k) * m;
+        return topk_partition_host_body(
+            s, part, filter, mask, queries, nq, static_cast<uint32_t>(km), metric, sqrt_out ? 1 : 0,
+            std::max<uint64_t>(std::max<uint64_t>(k * 20ull, km * 12), m > 1 ? km * 16 + 4 : 0), 32ull * k + 8 * km + 8 * PQV_KEY_SET_MAX + 16,
+            [&](Scratch &sc) {
+                std::vector<BatchOut> outs = {{&sc.s_rows, km * sizeof(uint32_t), row_idx}, {&sc.s_dist, km * sizeof(float), dist},
+                                              {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates},
+                                              {&sc.s_grp_out, k * sizeof(int64_t), group_key}};
+                if (group_rows) outs.push_back({&sc.s_grows_out, k * sizeof(uint32_t), group_rows});
+                return outs;
+            },
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
+                return enqueue_partition_grouped(bs, sc, part, filter->kind, d_a, d_b, group_keys, bits, sc.s_queries.as<float>(), b, k, m, mt, so,
+                                                 sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_grp_out.as<int64_t>(),
+                                                 group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr, sc.s_nfound.as<uint32_t>(),
+                                                 sc.s_out.as<uint64_t>(), bs->stream);
+            });
     });
 }
 

@@ -181,7 +181,8 @@ hipError_t launch_partition_span(const PartitionSpanArgs &a, hipStream_t s);
 // partition_stream_kernel: launch_masked_stream's STREAM_TOPK pass over a query's candidate sequence instead of probed lists.  grid
 // (blocks_per_list = B, nq); wave w of block x takes the 64-position windows (turn * B + x) * 4 + w of its query's sequence, maps
 // each sequence position to its partition entry (one span: an add; kind 2: a search in span_end), loads the entry's list position
-// and -- with a mask -- keeps the positions whose image bit is set.  Keys are (distance key << 32) | sequence position, the L2 forms'
+// and -- with a mask -- keeps the positions whose image bit is set (PartitionSeq::windows / filtered_windows, stream_walk.hpp: the
+// one walk of every launch_partition_* pass; partition_walk_ok is what all of them ask of a and pa).  Keys are (distance key << 32) | sequence position, the L2 forms'
 // (l2_key) or PQV_DOT's (dot_key); the per-wave lists go out in StreamArgs' format with nprobe = 1.  a.probe / list_off / cand_base
 // are not read; a.nprobe must be 1.  Every wave adds the rows it evaluated to embeddings_fetched.
 struct PartitionArgs {

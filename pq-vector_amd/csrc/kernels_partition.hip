@@ -5,8 +5,8 @@
 //                            run-length pass and a scan -- rocPRIM's, header-only from the ROCm tree (kernels.h has the order)
 //   partition_span_kernel    a query's filter (PQV_KEY_EQ / RANGE / IN) -> spans of the partition: lower / upper bound searches in
 //                            the distinct-value table, for IN one per slice value and the prefix sums of the span lengths
-//   partition_stream_kernel  the exact distance pass over a query's candidate sequence: masked_stream_kernel's tile, queue and list
-//                            (stream_walk.hpp), a grid that does not depend on the span lengths
+//   partition_stream_kernel  the exact distance pass over a query's candidate sequence: masked_stream_kernel's tile and list over
+//                            PartitionSeq's walk (stream_walk.hpp), a grid that does not depend on the span lengths
 // Nothing is probed: with no mask the answer is the exact top-k over ALL indexed rows whose key passes.
 #include "stream_walk.hpp"
 
@@ -239,20 +239,23 @@ hipError_t launch_partition_span(const PartitionSpanArgs &a, hipStream_t s) {
 // grid = (B, nq); block = 256 threads = 4 independent waves with masked_stream_kernel's tile area and nothing beside it.  The
 // query's sequence has n_cand[q] positions, known on the device only, so the grid cannot follow it: wave w of block x takes the
 // 64-position windows (turn * B + x) * 4 + w for turn = 0, 1, ... while they begin inside the sequence (PartitionSeq,
-// stream_walk.hpp: the distinct / grouped passes of kernels_partition_group.hip walk the same way).  A window's position
-// `seq` is mapped to its partition entry -- one span (EQ / RANGE): span_beg[q] + seq; IN: the first span whose inclusive prefix
+// stream_walk.hpp: the distinct / grouped passes of kernels_partition_group.hip and the range pass walk the same way).  A window's
+// position `seq` is mapped to its partition entry -- one span (EQ / RANGE): span_beg[q] + seq; IN: the first span whose inclusive prefix
 // sum exceeds seq, found by a halving search over the query's n_span[q] <= KEY_SET_MAX sums (read through the caches: no LDS
 // beside the tile, the occupancy of the masked twin) -- and the entry's list position is loaded: one coalesced 256-byte read per
 // span a window touches.
-// MASKED = false: the window IS the tile.  MASKED: the lanes ballot their positions' bits of the mask's image and the set ones are
-// compacted through WindowQueue, each with its list position as payload; a tile runs whenever 64 are queued and once more behind
-// the wave's last window, so a row the mask excludes is never loaded.  Sequence positions stay the unmasked ones.
+// MASKED = false: the window IS the tile (PartitionSeq::windows).  MASKED: PartitionSeq::filtered_windows under image_bit of the
+// mask's image -- the set positions are compacted through a WindowQueue, each with its list position as payload; a tile runs
+// whenever 64 are queued and once more behind the wave's last window, from ONE call site, so a row the mask excludes is never
+// loaded and the list's offer is instantiated once (the 1024-entry lists stay in registers).  Sequence positions stay the unmasked
+// ones.
 // Keys: (d2 bits << 32) | seq (l2_key) or (ord(dist) << 32) | seq (dot_key); storage rows through storage_row.  The per-wave lists
 // go out in StreamArgs' format (nprobe = 1, blocks_per_list = B) for merge_kernel / dot_merge_kernel; a wave without a window
 // writes its EMPTY list.  One statistics add per wave: the rows evaluated, to embeddings_fetched.
 // ------------------------------------------------------------------------------------
+// (CG 32's tile area lets 5 blocks share a CU: the masked forms of the lists up to 256 entries are held to 5 waves' registers)
 template <int CG, int S, bool SEQ, bool ALIGNED, bool DOT, bool MASKED>
-__global__ __launch_bounds__(256) void partition_stream_kernel(const StreamArgs a, const PartitionArgs pa) {
+__global__ __launch_bounds__(256, (MASKED && CG == 32 && S <= 4) ? 5 : 1) void partition_stream_kernel(const StreamArgs a, const PartitionArgs pa) {
     static_assert(tile_words<CG, SEQ>() >= WindowQueue<true>::SCRATCH, "the compaction needs 256 words of the tile area");
     __shared__ float lds_all[4 * tile_words<CG, SEQ>()];
     const int lane = threadIdx.x & 63;
@@ -280,29 +283,15 @@ __global__ __launch_bounds__(256) void partition_stream_kernel(const StreamArgs 
         n_eval += nvalid;
     };
 
-    WindowQueue<true> wq;
-    wq.cq = reinterpret_cast<uint32_t *>(lds);
-    ps.windows(ps.total, wave, lane, [&](uint64_t w0, uint32_t nvalid, uint32_t seq, uint32_t lpos) {
-        if constexpr (!MASKED) {
-            tile(lpos, seq, nvalid);
-        } else {
-            const bool on = (uint32_t)lane < nvalid && ((pa.bits[lpos >> 6] >> (lpos & 63u)) & 1ull);
-            const QueueTile t = wq.push(__ballot(on), w0, lpos, lane);
-            if (t.nvalid) tile(t.my_x, t.my_r, t.nvalid);
-        }
-    });
-    if constexpr (MASKED) {
-        const QueueTile t = wq.flush(lane);
-        if (t.nvalid) {
-            // (flush clamps the sequence position of the lanes behind the queue's end; their payload follows it)
-            const uint32_t lp = (uint32_t)__shfl((int)t.my_x, (int)((uint32_t)lane < t.nvalid ? (uint32_t)lane : t.nvalid - 1), 64);
-            tile(lp, t.my_r, t.nvalid);
-        }
+    if constexpr (!MASKED) {
+        ps.windows(ps.total, wave, lane, [&](uint64_t, uint32_t nvalid, uint32_t seq, uint32_t lpos) { tile(lpos, seq, nvalid); });
+    } else {
+        ps.filtered_windows(ps.total, lds, wave, lane, [&](uint32_t lpos) { return image_bit(pa.bits, lpos); }, tile);
     }
     unsigned long long *st = stats_slot(pa.stats, q);
     if (st && n_eval && lane == 0) atomicAdd(&st[3], (unsigned long long)n_eval);
 
-    write_partial_lists<S>(a.part_keys, a.part_vals, ((uint64_t)q * (gridDim.x * 4) + blockIdx.x * 4 + wave) * a.k, a.k, lane, tk.key, tk.val);
+    write_partial_lists<S>(a.part_keys, a.part_vals, partial_base(a, q, 0, wave, a.k), a.k, lane, tk.key, tk.val);
 }
 
 template <int S, bool DOT, bool MASKED>
@@ -316,8 +305,7 @@ static hipError_t launch_partition_s(const StreamArgs &a, const PartitionArgs &p
 
 hipError_t launch_partition_stream(const StreamArgs &a, const PartitionArgs &pa, hipStream_t s) {
     if (a.nq == 0) return hipSuccess;
-    if (!pa.span_beg || !pa.n_cand || (pa.kind == 2 && (!pa.span_end || !pa.n_span)) || pa.kind > 2) return hipErrorInvalidValue;
-    if (a.nprobe != 1 || a.blocks_per_list == 0 || a.blocks_per_list > 0xFFFFu || a.nq > 0xFFFFu || !a.part_keys || !a.part_vals) return hipErrorInvalidValue;
+    if (!partition_walk_ok(a, pa) || !a.part_keys || !a.part_vals) return hipErrorInvalidValue;
     const bool dot = a.metric == 4;     // PQV_DOT
     return dispatch_list_slots(a.k, [&](auto S) {
         if (dot) return pa.bits ? launch_partition_s<S.value, true, true>(a, pa, s) : launch_partition_s<S.value, true, false>(a, pa, s);

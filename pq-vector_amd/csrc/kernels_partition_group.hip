@@ -87,11 +87,9 @@ static hipError_t launch_partition_distinct_s(const StreamArgs &a, const Partiti
     });
 }
 
-// what both passes ask of the walk's arguments (launch_partition_stream's checks; the lists carry L2 keys: no PQV_DOT)
+// what both passes ask beside the walk's arguments (the lists carry L2 keys: no PQV_DOT)
 static bool partition_group_walk_ok(const StreamArgs &a, const PartitionArgs &pa) {
-    if (!pa.pos || !pa.span_beg || !pa.n_cand || (pa.kind == 2 && (!pa.span_end || !pa.n_span)) || pa.kind > 2) return false;
-    if (a.nprobe != 1 || a.blocks_per_list == 0 || a.blocks_per_list > 0xFFFFu || a.nq > 0xFFFFu) return false;
-    return a.metric != 4 && a.mat && a.queries;
+    return partition_walk_ok(a, pa) && a.metric != 4 && a.mat && a.queries;
 }
 
 hipError_t launch_partition_distinct_stream(const StreamArgs &a, const PartitionArgs &pa, const DistinctArgs &da, hipStream_t s) {

@@ -73,8 +73,7 @@ static hipError_t launch_partition_range_m(const StreamArgs &a, const PartitionA
 
 hipError_t launch_partition_range(const StreamArgs &a, const PartitionArgs &pa, hipStream_t s) {
     if (a.nq == 0) return hipSuccess;
-    if (!pa.pos || !pa.span_beg || !pa.n_cand || (pa.kind == 2 && (!pa.span_end || !pa.n_span)) || pa.kind > 2) return hipErrorInvalidValue;
-    if (a.nprobe != 1 || a.blocks_per_list == 0 || a.blocks_per_list > 0xFFFFu || a.nq > 0xFFFFu) return hipErrorInvalidValue;
+    if (!partition_walk_ok(a, pa)) return hipErrorInvalidValue;
     if (!a.hit_cnt || !a.hit_keys || !a.hit_vals || (!a.seg_off && a.seg_stride == 0)) return hipErrorInvalidValue;
     if (a.metric == 4) return pa.bits ? launch_partition_range_m<true, true>(a, pa, s) : launch_partition_range_m<true, false>(a, pa, s);     // PQV_DOT
     return pa.bits ? launch_partition_range_m<false, true>(a, pa, s) : launch_partition_range_m<false, false>(a, pa, s);

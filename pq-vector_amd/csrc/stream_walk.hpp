@@ -615,6 +615,13 @@ static inline hipError_t dispatch_chunk(uint32_t dim, int metric, F &&f) {
     return f(std::integral_constant<int, 32>{}, false_type{}, true_type{});
 }
 
+// Host: what every walk of a key partition's candidate sequences (PartitionSeq) asks of its arguments: the partition's positions, the
+// span kernel's outputs for the filter's kind, and a (B, nq) grid; each launcher adds the checks of its own outputs.
+static inline bool partition_walk_ok(const StreamArgs &a, const PartitionArgs &pa) {
+    if (!pa.pos || !pa.span_beg || !pa.n_cand || (pa.kind == 2 && (!pa.span_end || !pa.n_span)) || pa.kind > 2) return false;
+    return a.nprobe == 1 && a.blocks_per_list != 0 && a.blocks_per_list <= 0xFFFFu && a.nq <= 0xFFFFu;
+}
+
 // Host: the list length choice of every launcher.  f(S) gets the 64-entry slots a lane's sorted list takes as an integral_constant:
 // k <= 64 -> 1, <= 256 -> 4, <= 1024 -> 16; the kernels hold no longer list.
 template <class F>

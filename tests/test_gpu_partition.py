@@ -250,6 +250,67 @@ def test_same_call_twice_and_counters(shape):
         m.close()
 
 
+def test_masked_flush_edges(pqv, oracle):
+    """The masked walk's last tile, with one block per query (wave w takes the windows 4 t + w) over a run of about 1365 positions:
+    the mask allows exactly the rows at the run's sequence positions (i) 0 .. 63 -- wave 0 emits one full tile and flushes nothing;
+    (ii) 0 .. 63 and 256 -- wave 0's second window leaves one queued; (iii) 0 alone; (iv) 64 .. 126 -- 63 rows, all in wave 1."""
+    st = Setup(pqv, oracle, "4096x128")
+    c, k = st.case, 10
+    flt = ("eq", kf.EQ, [7] * c.nq, None)
+    prows, pkeys = st.ref["t3"]
+    run = prows[pr.sequence(pkeys, kf.EQ, flt[2], None, 0)]          # the rows at the sequence's positions
+    assert 1200 < len(run) < 1500
+    st.s.set_option("partition_blocks", 1)
+    try:
+        for label, positions, n_found in (("i", range(64), 10), ("ii", [*range(64), 256], 10), ("iii", [0], 1), ("iv", range(64, 127), 10)):
+            allow = np.zeros(c.n, bool)
+            allow[run[list(positions)]] = True
+            assert allow.sum() == len(positions)
+            m = st.s.row_mask(allow)
+            try:
+                got = part_device(st.s, st.parts["t3"], c.queries, k, flt, mask=m, metric=c.metric)
+            finally:
+                m.close()
+            _same(got, c.topk(st.ref["t3"], flt, k, allow=allow)[:4], f"mask ({label})")
+            assert (got[2] == n_found).all(), label
+    finally:
+        st.s.set_option("partition_blocks", 0)
+
+
+def test_piece_boundary(pqv):
+    """one device call of PARTITION_GRID_Q + 5 queries (32768: the grid's y, restated from csrc/api.cpp) on the smallest rows: 5
+    distinct queries and filters, cycled, so the reference is computed for 5 and tiled.  32768 is no multiple of 5: the queries past
+    the boundary continue the cycle at its fourth pattern, so each of them has another IN set than the query 32768 places ahead of it
+    -- a second piece that read the filter arrays (or IN lims) from the call's start would answer for other keys.  Every output is
+    compared whole, and its part past the boundary on its own."""
+    piece, n, dim, k = 32768, 300, 8, 3
+    nq = piece + 5
+    rng = np.random.default_rng(77)
+    data, q5 = rng.random((n, dim), dtype=np.float32), rng.random((5, dim), dtype=np.float32)
+    tenant = rng.integers(0, 3, n).astype(np.int32)
+    corpus = pqv.Corpus.upload(data)
+    lists = [np.arange(i, n, 2, dtype=np.uint32) for i in range(2)]
+    s = pqv.Searcher(pqv.Index.from_parts(dim, np.zeros((2, dim), np.float32), lists), corpus)
+    part = s.key_partition(pqv.Column.upload(tenant))
+    prows, pkeys = pr.build(tenant, None, np.arange(n))
+    d5 = pr.distances("l2", pr.REF4, data, q5)
+    reps = (nq + 4) // 5
+    tile = lambda x: np.concatenate([x] * reps)[:nq]        # noqa: E731
+    queries = tile(q5)
+    sets5 = [[0], [1, 2], [], [0, 2, 5], [2]]
+    assert all(sets5[(piece + i) % 5] != sets5[i] for i in range(5))
+    lims5, vals5 = kf.sets_to_csr(sets5)
+    lims, vals = kf.sets_to_csr((sets5 * reps)[:nq])
+    for f5, f in ((("eq", kf.EQ, [0, 1, 2, 7, 1], None), ("eq", kf.EQ, ([0, 1, 2, 7, 1] * reps)[:nq], None)),
+                  (("range", kf.RANGE, [0, 1, 2, 0, 1], [1, 2, 0, 2, 1]), ("range", kf.RANGE, ([0, 1, 2, 0, 1] * reps)[:nq], ([1, 2, 0, 2, 1] * reps)[:nq])),
+                  (("in", kf.IN, [int(x) for x in lims5], [int(x) for x in vals5]), ("in", kf.IN, [int(x) for x in lims], [int(x) for x in vals]))):
+        exp = [tile(x) for x in pr.topk_batch(prows, pkeys, f5[1], f5[2], f5[3], d5, k, "l2", False)[:4]]
+        assert exp[2][piece:].max() > 0 and (exp[0][piece:] != EMPTY).any()
+        got = part_device(s, part, queries, k, f)
+        _same(got, exp, f"{f[0]}: {nq} queries in one device call")
+        _same([x[piece:] for x in got], [x[piece:] for x in exp], f"{f[0]}: past the piece boundary")
+
+
 @pytest.mark.parametrize("nq", [1, 70])
 def test_batch_sizes(pqv, oracle, nq):
     st = Setup(pqv, oracle, "1500x30", nq=nq)

@@ -13,6 +13,8 @@ import pytest
 import key_filter_ref as kf
 import partition_cases as pc
 import partition_range_cases as prc
+import partition_range_ref as prr
+import partition_ref as pr
 from test_gpu_partition import Setup, _host_filter, _same
 
 pytestmark = pytest.mark.gpu
@@ -114,6 +116,49 @@ def test_seventy_queries(pqv, oracle):
     for col in ("t3", "t64"):           # (t64's IN filter holds the 1024-value set)
         for flt in c.filters(col):
             check_radii(st.s, st.parts[col], c, st.ref[col], flt, c.metric, sqrt_out=True, blocks=prc.BLOCKS)
+
+
+def test_piece_boundary(pqv):
+    """one call of PARTITION_GRID_Q + 5 queries (32768: the grid's y, restated from csrc/api.cpp) on the smallest rows: 5 distinct
+    queries and filters, cycled, so the reference is computed for 5 and tiled.  32768 is no multiple of 5: the queries past the
+    boundary continue the cycle at its fourth pattern, so each of them has another IN set than the query 32768 places ahead of it --
+    a second piece that kept the first one's filter slice or lims would answer for other keys.  The radius is the 75th smallest of
+    the 1500 distances: about 15 rows a query ahead of the filter, at most 15 hits.  Every output is compared whole, and its part past the boundary on its own."""
+    piece, n, dim = 32768, 300, 8
+    nq = piece + 5
+    rng = np.random.default_rng(77)
+    data, q5 = rng.random((n, dim), dtype=np.float32), rng.random((5, dim), dtype=np.float32)
+    tenant = rng.integers(0, 3, n).astype(np.int32)
+    corpus = pqv.Corpus.upload(data)
+    lists = [np.arange(i, n, 2, dtype=np.uint32) for i in range(2)]
+    s = pqv.Searcher(pqv.Index.from_parts(dim, np.zeros((2, dim), np.float32), lists), corpus)
+    part = s.key_partition(pqv.Column.upload(tenant))
+    prows, pkeys = pr.build(tenant, None, np.arange(n))
+    d5 = pr.distances("l2", pr.REF4, data, q5)
+    radius = np.sort(d5.ravel())[5 * 15 - 1]
+    reps = (nq + 4) // 5
+    tile = lambda x: np.concatenate([x] * reps)[:nq]        # noqa: E731
+    queries = tile(q5)
+    sets5 = [[0], [1, 2], [], [0, 2, 5], [2]]
+    assert all(sets5[(piece + i) % 5] != sets5[i] for i in range(5))
+    lims5, vals5 = kf.sets_to_csr(sets5)
+    lims, vals = kf.sets_to_csr((sets5 * reps)[:nq])
+    for f5, f in ((("eq", kf.EQ, [0, 1, 2, 7, 1], None), ("eq", kf.EQ, ([0, 1, 2, 7, 1] * reps)[:nq], None)),
+                  (("range", kf.RANGE, [0, 1, 2, 0, 1], [1, 2, 0, 2, 1]), ("range", kf.RANGE, ([0, 1, 2, 0, 1] * reps)[:nq], ([1, 2, 0, 2, 1] * reps)[:nq])),
+                  (("in", kf.IN, [int(x) for x in lims5], [int(x) for x in vals5]), ("in", kf.IN, [int(x) for x in lims], [int(x) for x in vals]))):
+        res5 = [prr.range_query(prows, pkeys, f5[1], f5[2], f5[3], q, d5[q], radius) for q in range(5)]
+        assert max(r[2] for r in res5) <= 15
+        exp_lims = np.zeros(nq + 1, np.uint64)
+        exp_lims[1:] = np.cumsum(tile(np.array([len(r[0]) for r in res5], np.uint64)))
+        exp = (exp_lims, np.concatenate([res5[i % 5][0] for i in range(nq)]), np.concatenate([res5[i % 5][1] for i in range(nq)]),
+               tile(np.array([r[2] for r in res5], np.uint64)), tile(np.array([r[3] for r in res5], np.uint64)))
+        got = search(s, part, queries, radius, f)
+        _same_range(got, exp, f"{f[0]}: {nq} queries in one call")
+        lo = int(exp_lims[piece])
+        assert int(exp_lims[nq]) > lo, "the part past the boundary is not empty"
+        _same_range((got[0][piece:] - got[0][piece], got[1][int(got[0][piece]):], got[2][int(got[0][piece]):], got[3][piece:], got[4][piece:]),
+                    (exp_lims[piece:] - exp_lims[piece], exp[1][lo:], exp[2][lo:], exp[3][piece:], exp[4][piece:]),
+                    f"{f[0]}: past the piece boundary")
 
 
 def _groups(n_cand, budget):

@@ -12,8 +12,10 @@ or other rows than (a), and each side's bytes per call, computed from what the k
   (a) considered rows x 4 dim (the embeddings_fetched counter) + candidate positions x 4 (the partition's list positions);
   (b) considered rows x 4 dim + the key column of every list the counting pass and the stream pass walk: the counting pass all
       P = max_nprobe = n_clusters lists (n positions per query), the stream pass the used ones (n_candidates[q] positions), x 4.
+--mask FRACTION runs (a) under a shared row mask that allows that fraction of the rows (uniform, seed 3000): the masked walk of
+partition_stream_kernel.  (b) stays unmasked, so the comparisons between the sides mean nothing then; the line carries "mask".
 Writes one JSON line (profiles/partition_bench.json holds those lines).
-usage: python tools/bench_partition.py [--workload c3s|c3] [--reps N]"""
+usage: python tools/bench_partition.py [--workload c3s|c3] [--reps N] [--mask FRACTION]"""
 import argparse
 import json
 import os
@@ -46,6 +48,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="c3s", choices=["c3s", "c3"])
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--mask", type=float, default=None, metavar="FRACTION")
     args = ap.parse_args()
     import torch
     import bench
@@ -59,6 +62,7 @@ def main():
     index = pqv.IndexBuilder(corpus).n_clusters(kc).max_iters(20).seed(42).workers(min(16, os.cpu_count() or 1)).build()
     s = pqv.Searcher(index, corpus)
     list_len = np.diff(index.list_offsets.astype(np.int64))
+    mask = s.row_mask(np.random.default_rng(3000).random(n) < args.mask) if args.mask is not None else None
 
     def outputs():
         return (torch.zeros((NQ, K), dtype=torch.int32, device=dev), torch.zeros((NQ, K), dtype=torch.float32, device=dev),
@@ -72,6 +76,8 @@ def main():
 
     out = {"workload": args.workload, "rows": n, "dim": dim, "n_clusters": kc, "nprobe": nprobe, "max_nprobe": kc, "k": K, "nq": NQ,
            "reps": args.reps, "tenants": []}
+    if mask is not None:
+        out["mask"] = args.mask
     for t in TENANTS:
         col = pqv.Column.upload(tenant_column(n, t))
         t0 = time.perf_counter()
@@ -87,7 +93,7 @@ def main():
 
         def partition_call():
             s.topk_partition_device(q_t.data_ptr(), NQ, K, part, pa[0].data_ptr(), pa[1].data_ptr(), pa[2].data_ptr(), pa[3].data_ptr(),
-                                    query_keys=qk_t.data_ptr())
+                                    query_keys=qk_t.data_ptr(), mask=mask)
 
         def expand_call():
             s.topk_device(q_t.data_ptr(), NQ, K, nprobe, ex[0].data_ptr(), ex[1].data_ptr(), ex[2].data_ptr(), ex[3].data_ptr(),
