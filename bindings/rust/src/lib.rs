@@ -587,6 +587,39 @@ impl<'c> Searcher<'c> {
             .collect())
     }
 
+    /// The exact top-k among the rows the caller names per query -- `candidates[q]` in any order, duplicates allowed, rows that are
+    /// not indexed skipped -- within `mask` if one is given; nothing is probed (`include/pqv.h`: `pqv_topk_rows`).
+    pub fn topk_rows(&self, candidates: &[Vec<u32>], mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize)
+                     -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (lims, cand) = candidate_lists(candidates, nq)?;
+        let k = k.get();
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_rows(self.raw, lims.as_ptr(), cand.as_ptr(), mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(),
+                               nq as u32, dim as u32, k as u32, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(), dist.as_mut_ptr(),
+                               found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
+    /// The exact distance of every candidate to its query, in the order given; `+inf` for a row that is not indexed or that `mask`
+    /// excludes (`include/pqv.h`: `pqv_score_rows`).
+    pub fn score_rows(&self, candidates: &[Vec<u32>], mask: Option<&RowMask>, queries: &[f32], dim: usize) -> Result<Vec<Vec<f32>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (lims, cand) = candidate_lists(candidates, nq)?;
+        let mut dist = vec![f32::INFINITY; cand.len().max(1)];
+        check(unsafe {
+            sys::pqv_score_rows(self.raw, lims.as_ptr(), cand.as_ptr(), mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(),
+                                nq as u32, dim as u32, sys::PQV_L2SQ_REF4, 1, dist.as_mut_ptr())
+        })?;
+        Ok((0..nq).map(|q| dist[lims[q] as usize..lims[q + 1] as usize].to_vec()).collect())
+    }
+
     /// Every row of `part` whose key passes the query's filter within `radius` of the query -- exact, nothing is probed, ascending by
     /// (distance, sequence position); `max_results > 0` keeps the first `max_results` of each query (`include/pqv.h`:
     /// `pqv_range_search_partition`).
@@ -1294,6 +1327,21 @@ impl Drop for CandidateCursor {
     fn drop(&mut self) {
         unsafe { sys::pqv_candidate_cursor_free(self.raw) }
     }
+}
+
+/// The `(lims, rows)` arrays of a candidate-list call: one list per query, concatenated in order.
+fn candidate_lists(candidates: &[Vec<u32>], nq: usize) -> Result<(Vec<u64>, Vec<u32>)> {
+    if candidates.len() != nq {
+        return Err("one candidate list per query".into());
+    }
+    let mut lims = Vec::with_capacity(nq + 1);
+    lims.push(0u64);
+    let mut rows = Vec::with_capacity(candidates.iter().map(Vec::len).sum());
+    for c in candidates {
+        rows.extend_from_slice(c);
+        lims.push(rows.len() as u64);
+    }
+    Ok((lims, rows))
 }
 
 /// The C descriptor of a [`KeyFilter`] for `nq` queries, with the arrays it points at (a set filter's offsets and sorted,

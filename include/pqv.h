@@ -896,6 +896,65 @@ int pqv_range_search_partition(const pqv_searcher *searcher, const pqv_key_parti
                                uint64_t max_results, int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
                                uint64_t *n_within, uint64_t *n_candidates);
 
+/* Candidate lists: "the nearest 10 of exactly THESE rows" / "the distance of each of these rows" -- the second stage of hybrid
+ * retrieval, where a lexical engine, a SQL sub-query, a graph walk or a coarse pass hands over a few hundred to a few thousand row
+ * ids per query, different for every query.  The rows are resident: nothing crosses the bus but the ids.
+ *
+ * pqv_topk_rows / pqv_topk_rows_device / pqv_score_rows / pqv_score_rows_device: no nprobe and no max_candidates.  `lims` is u64
+ * [nq + 1] and need not start at 0; `cand_rows` u32 row ids.  Host arrays in the host forms; in the device forms device arrays read
+ * on hip_stream inside the enqueued work.
+ *   candidates   query q's sequence is cand_rows[lims[q] .. lims[q + 1]) exactly as given, in any order.  A candidate's position is
+ *                its index in the slice; n_candidates[q] is the slice's length, taken before any test below.  A row listed twice
+ *                is two candidates and can be returned twice.
+ *   considered   the candidates whose row is in one of the searcher's lists and which the optional shared `mask` allows (NULL:
+ *                all), at their unmasked positions.  A row id at or above the corpus' row count, 0xFFFFFFFF, and a row
+ *                pqv_index_remove* took out are not indexed.  A candidate that is not considered is never loaded.
+ *   result       top-k: the k considered candidates with the smallest (distance key, position), ascending.  The distance is bit for
+ *                bit that of the metric's chain: PQV_L2SQ_REF4, PQV_L2SQ_SEQ, PQV_COSINE (through the cosine layout, with the
+ *                halving) and PQV_DOT (ord() keys, dist = 0.0f - s(q, x)); sqrt_out as in pqv_topk_partition.  There is no reference
+ *                heap to replay and there are no tie flags: the host and the device form return the same bytes.  Slots past
+ *                n_found[q] hold 0xFFFFFFFF / +inf.  n_found and n_candidates may be NULL.
+ *                scores: dist[i - lims[0]] for candidate i of cand_rows is its distance on the output scale, bit-equal to what
+ *                pqv_topk_rows reports for that candidate; +inf for a candidate that is not considered.  dist holds lims[nq] -
+ *                lims[0] values.
+ *   equivalence  with every slice ascending and unique: on S1 (pqv_topk_partition, above) rows, distances and n_found equal
+ *                pqv_topk_masked_device with nprobe = 1 under the per-query mask M_q = the slice, for every metric, whenever no two
+ *                considered rows tie in distance at or inside the k-th place.  With slice q = the rows of one key of a partition,
+ *                ascending, the call equals pqv_topk_partition with PQV_KEY_EQ for any input, ties included: both order by
+ *                (distance key, position).
+ *   exactness    no searcher option changes a result (partition_blocks fixes the blocks per query, 0 = by rule, as for the
+ *                partition calls).
+ *   counts       queries advances by nq, candidate_rows by the sum of the slice lengths, embeddings_fetched by the considered
+ *                candidates; screened_pairs and screen_survivors do not move.
+ *   row map      the calls need the way back from a row id to its list position: a u32 per corpus row (4 bytes x the corpus' row
+ *                count of device memory, reported with the searcher's other buffers by pqv_searcher_footprint), built by the first
+ *                candidate-list call on a searcher -- one fill and one scatter kernel -- and freed with it.  It serves every layout
+ *                (flags 0, PQV_LAYOUT_ROW_ORDER, PQV_RELEASE_ROW_ORDER) and the cosine layout.
+ *   limits       k <= 1024 in both top-k forms (PQV_ERR_UNSUPPORTED "pqv_topk_rows takes k <= 1024"): there is no host fallback.  A
+ *                slice holds at most 2^32 - 1 candidates: the host forms refuse a longer one, the device forms read its first 2^32 -
+ *                1.  An inverted slice (lims[q + 1] < lims[q]) is PQV_ERR_INVALID "lims must not decrease" in the host forms and an
+ *                empty sequence in the device forms.  The device forms are asynchronous on hip_stream (NULL: the searcher's stream)
+ *                with no host synchronisation -- except the first candidate-list call on a searcher, which builds the row map and
+ *                waits for it, as the first cosine call builds its layout.  Every access stays in bounds whatever the arrays hold,
+ *                given that the slices lie inside cand_rows: a row id indexes the map only behind a compare against its length.
+ *   out of scope table searchers (PQV_ERR_UNSUPPORTED "pqv_topk_rows does not take table searchers" / "pqv_score_rows does not take
+ *                table searchers", behind the NULL checks); distinct, grouped and range forms over candidate lists; the
+ *                path-taking builders; the screened kernels.
+ * Errors, in this order, all before any device use (PQV_ERR_INVALID unless noted): "searcher must not be NULL", "lims must not be
+ * NULL", "cand_rows must not be NULL" (host forms: only where some slice is non-empty), top-k: "k must be > 0", host forms: "lims
+ * must not decrease" then "a candidate list holds at most 2^32 - 1 rows", "row mask belongs to another searcher", the table refusal,
+ * pqv_topk's own metric and query-length texts, "row_idx/dist must not be NULL" (scores: "dist must not be NULL"), the k limit. */
+int pqv_topk_rows(const pqv_searcher *searcher, const uint64_t *lims, const uint32_t *cand_rows, const pqv_row_mask *mask,
+                  const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, int metric, int sqrt_out,
+                  uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_rows_device(const pqv_searcher *searcher, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
+                         const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
+                         void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates, void *hip_stream);
+int pqv_score_rows(const pqv_searcher *searcher, const uint64_t *lims, const uint32_t *cand_rows, const pqv_row_mask *mask,
+                   const float *queries, uint32_t nq, uint32_t query_len, int metric, int sqrt_out, float *dist /* [lims[nq] - lims[0]] */);
+int pqv_score_rows_device(const pqv_searcher *searcher, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
+                          const void *d_queries, uint32_t nq, int metric, int sqrt_out, void *d_dist, void *hip_stream);
+
 /* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
  * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.
  *

@@ -27,6 +27,8 @@ Host-side mirror of the reference's Rust API over the C ABI of include/pqv.h:
       ORDER BY distance) <= m, k docs          rows of each of the k nearest groups; Searcher.topk_grouped / topk_grouped_device
     (no counterpart: a posting list per      Searcher.key_partition(column) + topk_partition / topk_partition_grouped (exact top-k over a
       tenant, nothing probed)                  tenant's own rows) / range_search_partition (every row of the tenant within a radius)
+    WHERE id IN (rows another engine named,  Searcher.topk_rows(queries, k, candidates) (the exact top-k among exactly those rows, a list per
+      per query: hybrid retrieval)             query) / score_rows (every candidate's exact distance); topk_rows_device / score_rows_device
     (no counterpart: rows that arrive after  corpus.append(batch); index = index.append(corpus) -> a new Index, same centroids, every
       the build; indexing under a given        list extended (no k-means); Index.assign(corpus, first_row, n_rows);
       codebook)                                IndexBuilder(source).with_centroids(index_or_array).build()

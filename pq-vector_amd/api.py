@@ -895,6 +895,48 @@ def _partition_filter(part, query_keys, query_key_ranges, query_key_sets, nq, de
     return part._h, _ffi.KeyFilter(_ffi.PQV_KEY_IN, 0, lims.ctypes.data, vals.ctypes.data), (lims, vals)
 
 
+def _row_ids_u32(ids, what="row ids"):
+    """Row ids -> contiguous uint32: integers in [0, 2^32), checked as row_mask_from_rows checks its ids (a candidate list may name
+    rows the corpus does not have: they are skipped by the call, not refused here)."""
+    a = np.asarray(ids)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} must be integers, got {a.dtype}")
+    a = a.reshape(-1)
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"{what} must be in [0, 2^32)")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _candidate_lists(candidates, nq):
+    """A candidate-list call's (lims uint64 [nq + 1], rows uint32): a TUPLE is a (lims, rows) pair passed on as given -- lims need not
+    start at 0 --, any other sequence holds one integer array per query."""
+    if candidates is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "candidates must not be None")
+    if isinstance(candidates, tuple):
+        if len(candidates) != 2:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "candidates given as a tuple must be a pair (lims, rows)")
+        lims = np.asarray(candidates[0])
+        if lims.ndim != 1 or lims.size != nq + 1:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"lims must have nq + 1 = {nq + 1} entries, got shape {lims.shape}")
+        if not np.issubdtype(lims.dtype, np.integer) or (lims.size and int(lims.min()) < 0):
+            raise PqvError(_ffi.PQV_ERR_INVALID, "lims must be non-negative integers")
+        rows = _row_ids_u32(candidates[1], "candidate row ids")
+        if int(lims.max()) > rows.size:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"lims reach {int(lims.max())}, the candidate rows hold {rows.size} ids")
+        return np.ascontiguousarray(lims, dtype=np.uint64), rows
+    try:
+        per_query = [_row_ids_u32(c, "candidate row ids") for c in candidates]
+    except TypeError:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "candidates must be a sequence of per-query integer arrays or a (lims, rows) tuple") from None
+    if len(per_query) != nq:
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"candidates has {len(per_query)} lists, the call has {nq} queries")
+    lims = np.zeros(nq + 1, dtype=np.uint64)
+    if nq:
+        lims[1:] = np.cumsum([c.size for c in per_query], dtype=np.uint64)
+    rows = np.concatenate(per_query) if per_query else np.zeros(0, dtype=np.uint32)
+    return lims, np.ascontiguousarray(rows, dtype=np.uint32)
+
+
 def _allow_array(allowed, n_rows, what="row mask"):
     """A caller's allow array -> contiguous uint8 [n_rows]: bool or uint8, one entry per row; anything else is refused."""
     if allowed is None:
@@ -1089,6 +1131,59 @@ class Searcher:
         _check(_ffi.lib().pqv_topk_partition_device(self._h, ph, C.byref(f), _mask_handle(self, mask) if mask is not None else None,
                                                     vp(d_queries), nq, k, metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
                                                     vp(d_n_found or None), vp(d_n_candidates or None), vp(stream or None)))
+
+    def topk_rows(self, queries, k, candidates, mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """Exact top-k among the rows the caller names per query -- `candidates`: a list of per-query integer arrays, or a
+        (lims, rows) TUPLE (lims int [nq + 1], need not start at 0; rows the ids, query q's are rows[lims[q]:lims[q + 1]]) -- in any
+        order, duplicates allowed, within mask if one is given; nothing is probed (pqv.h: pqv_topk_rows).  Returns (row_idx [nq,k]
+        u32, dist [nq,k] f32, n_found [nq], n_candidates [nq])."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        lims, cand = _candidate_lists(candidates, nq)
+        rows = np.full((nq, max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        nf = np.zeros(nq, dtype=np.uint32)
+        nc = np.zeros(nq, dtype=np.uint64)
+        _check(_ffi.lib().pqv_topk_rows(self._h, lims.ctypes.data_as(u64p), cand.ctypes.data_as(u32p),
+                                        _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq, qlen, k, metric,
+                                        1 if sqrt_out else 0, rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p),
+                                        nc.ctypes.data_as(u64p)))
+        return rows, dist, nf, nc
+
+    def score_rows(self, queries, candidates, mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """The exact distance of every candidate (`candidates` as topk_rows takes them) to its query, +inf for a row that is not
+        indexed or that mask excludes (pqv.h: pqv_score_rows).  Returns (lims u64 [nq + 1] rebased to start at 0, dist f32
+        [lims[nq]]): query q's distances are dist[lims[q]:lims[q + 1]], in the order its candidates were given."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        lims, cand = _candidate_lists(candidates, nq)
+        total = int(lims[nq] - lims[0]) if lims[nq] >= lims[0] else 0
+        dist = np.full(max(total, 1), np.inf, dtype=np.float32)
+        _check(_ffi.lib().pqv_score_rows(self._h, lims.ctypes.data_as(u64p), cand.ctypes.data_as(u32p),
+                                         _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq, qlen, metric,
+                                         1 if sqrt_out else 0, dist.ctypes.data_as(f32p)))
+        return lims - lims[0], dist[:total]
+
+    def topk_rows_device(self, d_queries, nq, k, d_lims, d_cand_rows, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0, mask=None,
+                         metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of topk_rows, shaped like topk_device: asynchronous on `stream`; d_lims (u64 [nq + 1]) and d_cand_rows
+        (u32) are device pointers read on `stream` inside the enqueued work (pqv.h: pqv_topk_rows_device).  The first candidate-list
+        call on a searcher builds its row map and waits for it."""
+        _check(_ffi.lib().pqv_topk_rows_device(self._h, vp(d_lims or None), vp(d_cand_rows or None),
+                                               _mask_handle(self, mask) if mask is not None else None, vp(d_queries or None), nq, k, metric,
+                                               1 if sqrt_out else 0, vp(d_row_idx or None), vp(d_dist or None), vp(d_n_found or None),
+                                               vp(d_n_candidates or None), vp(stream or None)))
+
+    def score_rows_device(self, d_queries, nq, d_lims, d_cand_rows, d_dist, mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of score_rows: d_dist f32 [lims[nq] - lims[0]], candidate i's distance at i - lims[0]; asynchronous on
+        `stream` (pqv.h: pqv_score_rows_device)."""
+        _check(_ffi.lib().pqv_score_rows_device(self._h, vp(d_lims or None), vp(d_cand_rows or None),
+                                                _mask_handle(self, mask) if mask is not None else None, vp(d_queries or None), nq, metric,
+                                                1 if sqrt_out else 0, vp(d_dist or None), vp(stream or None)))
 
     def topk_partition_grouped(self, queries, k, group_size, part, keys, query_keys=None, query_key_ranges=None, query_key_sets=None,
                                mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):

@@ -510,6 +510,11 @@ struct pqv_searcher {
     // searcher goes before the corpus it borrows.
     mutable std::unique_ptr<pqv_corpus> cos_corpus;    // row-order n(x) (its rows released where `cos` keeps an IVF-ordered copy)
     mutable std::unique_ptr<pqv_searcher> cos;
+    // pqv_topk_rows / pqv_score_rows: row -> list position, u32 [corpus rows], 0xFFFFFFFF for a row of no list -- made under `mu` by
+    // the first candidate-list call (ensure_row_map).  List positions are the same in every layout and in `cos`: one map serves all.
+    mutable DevBuf d_row_map;
+    mutable uint64_t row_map_len = 0;
+    mutable bool row_map_done = false;
     ~pqv_searcher();
 };
 pqv_searcher::~pqv_searcher() {
@@ -744,6 +749,8 @@ static int row_filter(const pqv_searcher *s, const SearchRequest *mv, uint64_t q
 }
 // The RANGE / IN arrays of a filter descriptor for the sub-batch [q0, q0 + b): uploaded on `st` into the lane's scratch, *d_a / *d_b
 // pointed at them.  `lims` keeps an IN filter's rebased offsets alive until the sub-batch's synchronisation.
+// SLICE_ROWS: RowSelection::kind of a candidate-list call (pqv_topk_rows), beside pqv.h's PQV_KEY_* -- a = lims, b = u32 row ids.
+constexpr uint32_t SLICE_ROWS = 3;
 static int upload_filter_arrays(Scratch &sc, uint32_t kind, const void *h_a, const void *h_b, uint32_t q0, uint32_t b, std::vector<uint64_t> &lims,
                                 hipStream_t st, const void **d_a, const void **d_b) {
     if (kind == PQV_KEY_RANGE) {
@@ -752,15 +759,17 @@ static int upload_filter_arrays(Scratch &sc, uint32_t kind, const void *h_a, con
         HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, static_cast<const int64_t *>(h_a) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(h_b) + q0, static_cast<size_t>(b) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     } else {
+        // (PQV_KEY_IN's i64 values, or -- SLICE_ROWS -- a candidate-list call's u32 row ids: lims + slices either way)
+        const size_t vs = kind == SLICE_ROWS ? sizeof(uint32_t) : sizeof(int64_t);
         const uint64_t *hl = static_cast<const uint64_t *>(h_a);
         const uint64_t base = hl[q0], n_vals = hl[q0 + b] - base;
         try { lims.resize(static_cast<size_t>(b) + 1); } catch (const std::bad_alloc &) { return fail(PQV_ERR_OOM, "host allocation failed"); }
         for (uint32_t i = 0; i <= b; ++i) lims[i] = hl[q0 + i] - base;
         HIP_TRY(sc.s_qfilt_a.ensure((static_cast<size_t>(b) + 1) * sizeof(uint64_t)));
-        HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(n_vals) * sizeof(int64_t)));
+        HIP_TRY(sc.s_qfilt_b.ensure(static_cast<size_t>(n_vals) * vs));
         HIP_TRY(hipMemcpyAsync(sc.s_qfilt_a.p, lims.data(), (static_cast<size_t>(b) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         if (n_vals)
-            HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const int64_t *>(h_b) + base, static_cast<size_t>(n_vals) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(sc.s_qfilt_b.p, static_cast<const char *>(h_b) + base * vs, static_cast<size_t>(n_vals) * vs, hipMemcpyHostToDevice, st));
     }
     *d_a = sc.s_qfilt_a.p; *d_b = sc.s_qfilt_b.p;
     return PQV_OK;
@@ -6350,6 +6359,7 @@ static uint32_t partition_blocks(const pqv_searcher *s, uint32_t nq, uint32_t k,
 // blocks_per_list and its outputs) and all of PartitionArgs.  `s`: the searcher whose rows are read (the call's, or its cosine
 // searcher).  Nothing is counted here: launch() is one launch, two where padded().
 constexpr uint32_t PARTITION_GRID_Q = 32768;
+struct RowMap { const uint32_t *map; uint64_t len; };      // a searcher's row -> list position map (ensure_row_map)
 struct PartitionWalk {
     const pqv_searcher *s;
     Scratch &sc;
@@ -6359,28 +6369,43 @@ struct PartitionWalk {
     int metric;
     hipStream_t stream;
     uint32_t piece = 0;
+    // kind SLICE_ROWS (part nullptr): the sequences are a candidate-list call's own slices -- no span kernel, launch_rows_at
+    RowMap map{};
+    const uint64_t *lims0 = nullptr;    // ... its score form: the lims word of the call's first query (RowsArgs::lims0)
 
     uint32_t span_w() const { return kind == PQV_KEY_IN ? PQV_KEY_SET_MAX : 1u; }      // span slots per query
     bool padded() const { return s->sdim != s->dim; }
     int size(uint32_t nq) {
         piece = std::min<uint32_t>(nq, PARTITION_GRID_Q);
-        HIP_TRY(sc.s_pt_beg.ensure(static_cast<size_t>(piece) * span_w() * sizeof(uint32_t)));
-        if (kind == PQV_KEY_IN) {
-            HIP_TRY(sc.s_pt_end.ensure(static_cast<size_t>(piece) * span_w() * sizeof(uint32_t)));
-            HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+        if (kind != SLICE_ROWS) {
+            HIP_TRY(sc.s_pt_beg.ensure(static_cast<size_t>(piece) * span_w() * sizeof(uint32_t)));
+            if (kind == PQV_KEY_IN) {
+                HIP_TRY(sc.s_pt_end.ensure(static_cast<size_t>(piece) * span_w() * sizeof(uint32_t)));
+                HIP_TRY(sc.s_pt_nspan.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
+            }
+            HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
         }
-        HIP_TRY(sc.s_ncand.ensure(static_cast<size_t>(piece) * sizeof(uint64_t)));
         if (padded()) HIP_TRY(sc.s_qpad.ensure(static_cast<size_t>(piece) * s->sdim * sizeof(float)));
+        return PQV_OK;
+    }
+    // the b queries at dq, padded where the stored rows are, and StreamArgs' common fields
+    int stream_args(const float *dq, uint32_t b, pqv::StreamArgs &ra) const {
+        using namespace pqv;
+        if (padded()) {      // (the stored rows are zero-padded: the queries that meet them too)
+            HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), stream));
+            dq = sc.s_qpad.as<float>();
+        }
+        ra = StreamArgs{};
+        ra.mat = s->d_mat; ra.row_of = s->d_row_of;
+        ra.queries = dq; ra.nq = b; ra.nprobe = 1; ra.dim = s->sdim;
+        ra.rows_per_block = 256; ra.max_pos = ~0ull; ra.metric = metric;
         return PQV_OK;
     }
     // the b queries at dq, with d_a / d_b as the span kernel indexes them from this piece's first query
     int launch(const float *dq, uint32_t b, const void *d_a, const void *d_b, uint64_t *d_n_cand_out, pqv::StreamArgs &ra,
                pqv::PartitionArgs &pa) const {
         using namespace pqv;
-        if (padded()) {      // (the stored rows are zero-padded: the queries that meet them too)
-            HIP_TRY(launch_pad_rows(dq, nullptr, b, s->dim, s->sdim, sc.s_qpad.as<float>(), stream));
-            dq = sc.s_qpad.as<float>();
-        }
+        if (int rc = stream_args(dq, b, ra)) return rc;
         PartitionSpanArgs sp{};
         sp.keys = part->d_keys.as<int64_t>(); sp.key_off = part->d_off.as<uint64_t>(); sp.n_keys = part->n_keys;
         sp.nq = b; sp.kind = kind; sp.a = d_a; sp.b = d_b;
@@ -6388,10 +6413,6 @@ struct PartitionWalk {
         sp.n_cand = sc.s_ncand.as<uint64_t>(); sp.n_cand_out = d_n_cand_out;
         sp.stats = s->d_stats.as<unsigned long long>();
         HIP_TRY(launch_partition_span(sp, stream));
-        ra = StreamArgs{};
-        ra.mat = s->d_mat; ra.row_of = s->d_row_of;
-        ra.queries = dq; ra.nq = b; ra.nprobe = 1; ra.dim = s->sdim;
-        ra.rows_per_block = 256; ra.max_pos = ~0ull; ra.metric = metric;
         pa = PartitionArgs{};
         pa.pos = part->d_pos.as<uint32_t>(); pa.span_beg = sp.span_beg; pa.span_end = sp.span_end; pa.n_span = sp.n_span;
         pa.n_cand = sp.n_cand; pa.kind = kind; pa.bits = bits; pa.stats = sp.stats;
@@ -6405,6 +6426,17 @@ struct PartitionWalk {
         return launch(d_queries + static_cast<size_t>(q0) * s->dim, b, static_cast<const char *>(d_a) + off,
                       kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + off) : d_b,
                       d_n_cand ? d_n_cand + q0 : nullptr, ra, pa);
+    }
+    // SLICE_ROWS: the same piece of a candidate-list call -- d_lims indexed from the piece's first query, d_rows whole (lims hold
+    // offsets into all of it); nothing is launched beside the padding, the walk's kernel reads the slices itself
+    int launch_rows_at(uint32_t q0, uint32_t b, const float *d_queries, const void *d_lims, const void *d_rows, uint64_t *d_n_cand,
+                       pqv::StreamArgs &ra, pqv::RowsArgs &wa) const {
+        if (int rc = stream_args(d_queries + static_cast<size_t>(q0) * s->dim, b, ra)) return rc;
+        wa = pqv::RowsArgs{};
+        wa.lims = static_cast<const uint64_t *>(d_lims) + q0; wa.cand_rows = static_cast<const uint32_t *>(d_rows);
+        wa.map = map.map; wa.map_len = map.len; wa.bits = bits; wa.stats = s->d_stats.as<unsigned long long>();
+        wa.n_cand_out = d_n_cand ? d_n_cand + q0 : nullptr; wa.lims0 = lims0;
+        return PQV_OK;
     }
 };
 // A device form behind its checks: the lock, the lane, body(searcher, scratch, queries, metric, sqrt_out) and the queries counted.
@@ -6438,12 +6470,13 @@ static SearchRequest partition_request(const pqv_key_filter *f) {
     else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
     return rq;
 }
-// The host form of both top-k calls: PQV_COSINE's n(q), the lane, sub-batches of queries through it (their filter slices uploaded
-// as pqv_topk_filtered uploads them), enqueue(s, sc, bits, d_a, d_b, b, metric, sqrt_out) -- the device body on a sub-batch's
+// The host form of the partition top-k calls and the candidate-list calls: PQV_COSINE's n(q), the lane, sub-batches of queries
+// through it (rq's per-query slices -- a filter's, or the candidate lists -- uploaded as pqv_topk_filtered uploads a filter's; m:
+// the positions partition_blocks sizes the grid by), enqueue(s, sc, bits, d_a, d_b, b, metric, sqrt_out) -- the device body on a sub-batch's
 // scratch -- and outs(sc) back.  The sub-batch is bounded so the scratch stays under ~1 GiB: per query the B * 4 per-wave lists of
 // k_lists entries, list_bytes in all passes' widest, the padded query, and out_bytes of outputs and filter slice.
 template <class Outs, class Enqueue>
-static int topk_partition_host_body(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *f, const pqv_row_mask *mask,
+static int topk_partition_host_body(const pqv_searcher *s, uint64_t m, const SearchRequest &rq, const pqv_row_mask *mask,
                                     const float *queries, uint32_t nq, uint32_t k_lists, int metric, int sqrt_out, uint64_t list_bytes,
                                     uint64_t out_bytes, Outs outs, Enqueue enqueue) {
     std::vector<float> nq_host;
@@ -6453,10 +6486,9 @@ static int topk_partition_host_body(const pqv_searcher *s, const pqv_key_partiti
     Lane lane;
     if (int rc = lane.acquire(s, s->stream)) return rc;
     Scratch &sc = *lane;
-    const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), k_lists, part->m);
+    const uint32_t B = partition_blocks(s, std::min<uint32_t>(nq, 1024), k_lists, m);
     const uint64_t per_query = static_cast<uint64_t>(B) * 4 * list_bytes + static_cast<uint64_t>(s->sdim) * 8 + out_bytes;
     const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
-    const SearchRequest rq = partition_request(f);
     if (int rc = host_batches(
             s, sc, queries, nq, batch, &rq, nullptr, outs(sc),
             [&](uint32_t b, SearchRequest *brq) { return enqueue(s, sc, bits, brq->d_filter_a(), brq->d_filter_b(), b, metric, sqrt_out); },
@@ -6466,6 +6498,22 @@ static int topk_partition_host_body(const pqv_searcher *s, const pqv_key_partiti
 }
 
 // ---- top-k over a key partition (pqv.h: pqv_topk_partition) ----------------------------------------------------------------------
+// The fold of a piece's per-wave lists (ra: the walk's arguments, n_part lists of ra.k entries per query) into the call's outputs
+// from query q0 on: merge_kernel, PQV_DOT: dot_merge_kernel.
+static int partition_fold(const pqv_searcher *s, const pqv::StreamArgs &ra, uint32_t n_part, uint32_t q0, int metric, int sqrt_out,
+                          uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, hipStream_t stream) {
+    using namespace pqv;
+    const uint32_t k = ra.k;
+    MergeArgs fm{};
+    fm.part_keys = ra.part_keys; fm.part_vals = ra.part_vals;
+    fm.nq = ra.nq; fm.n_part = n_part; fm.k_part = k; fm.k = k;
+    fm.ids = s->d_final_ids; fm.row_idx = d_row_idx + static_cast<size_t>(q0) * k; fm.dist = d_dist + static_cast<size_t>(q0) * k;
+    fm.n_found = d_n_found ? d_n_found + q0 : nullptr;
+    fm.sqrt_out = sqrt_out; fm.k_out = k;
+    if (metric == PQV_DOT) HIP_TRY(launch_dot_merge(fm, stream));
+    else HIP_TRY(launch_merge_final(fm, stream));
+    return PQV_OK;
+}
 // Enqueue span -> stream -> fold for the queries [0, nq) on `stream`, in PartitionWalk's pieces.  a / b: the descriptor's DEVICE arrays.
 static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
                              const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
@@ -6485,15 +6533,7 @@ static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_p
         ra.k = k; ra.blocks_per_list = B;
         ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
         HIP_TRY(launch_partition_stream(ra, pa, stream));
-
-        MergeArgs fm{};
-        fm.part_keys = ra.part_keys; fm.part_vals = ra.part_vals;
-        fm.nq = b; fm.n_part = n_part; fm.k_part = k; fm.k = k;
-        fm.ids = s->d_final_ids; fm.row_idx = d_row_idx + static_cast<size_t>(q0) * k; fm.dist = d_dist + static_cast<size_t>(q0) * k;
-        fm.n_found = d_n_found ? d_n_found + q0 : nullptr;
-        fm.sqrt_out = sqrt_out; fm.k_out = k;
-        if (metric == PQV_DOT) HIP_TRY(launch_dot_merge(fm, stream));
-        else HIP_TRY(launch_merge_final(fm, stream));
+        if (int rc = partition_fold(s, ra, n_part, q0, metric, sqrt_out, d_row_idx, d_dist, d_n_found, stream)) return rc;
         s->counters.kernel_launches += 3;
     }
     return PQV_OK;
@@ -6531,7 +6571,7 @@ extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition
         if (int rc = use_device(s->device)) return rc;
         // (per list entry 12 B; beside the lists the rows, distances and n_found / n_candidates, and an IN slice)
         return topk_partition_host_body(
-            s, part, filter, mask, queries, nq, k, metric, sqrt_out ? 1 : 0, 12ull * k, 12ull * k + 8 * PQV_KEY_SET_MAX,
+            s, part->m, partition_request(filter), mask, queries, nq, k, metric, sqrt_out ? 1 : 0, 12ull * k, 12ull * k + 8 * PQV_KEY_SET_MAX,
             [&](Scratch &sc) {
                 return std::vector<BatchOut>{{&sc.s_rows, k * sizeof(uint32_t), row_idx}, {&sc.s_dist, k * sizeof(float), dist},
                                              {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates}};
@@ -6539,6 +6579,184 @@ extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition
             [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
                 return enqueue_partition(bs, sc, part, filter->kind, d_a, d_b, bits, sc.s_queries.as<float>(), b, k, mt, so, sc.s_rows.as<uint32_t>(),
                                          sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(), bs->stream);
+            });
+    });
+}
+
+// ---- candidate lists (pqv.h: pqv_topk_rows, pqv_score_rows) ------------------------------------------------------------------------
+// The partition walk stage over sequences the caller wrote: query q's is cand_rows[lims[q] .. lims[q + 1]), a position's list
+// position comes from the searcher's row map.  One body for the four entry points: k == 0 is the score form, whose d_dist takes a
+// distance per candidate instead of the fold's k per query.
+// The row map of `s`, made by its first candidate-list call under s->mu: 4 bytes per corpus row, one fill and one scatter over
+// d_ids on the searcher's stream, waited for -- later calls run on any stream.
+static int ensure_row_map(const pqv_searcher *s, RowMap &out) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->row_map_done) {
+        const uint64_t rows = s->corpus ? s->corpus->n : 0;
+        HIP_TRY(s->d_row_map.alloc(rows * sizeof(uint32_t)));
+        HIP_TRY(pqv::launch_row_map(s->d_ids.as<uint32_t>(), s->n, s->d_row_map.as<uint32_t>(), rows, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        s->row_map_len = rows;
+        s->row_map_done = true;
+        s->counters.kernel_launches += 1;
+    }
+    out = RowMap{s->d_row_map.as<uint32_t>(), s->row_map_len};
+    return PQV_OK;
+}
+// The checks of the four entry points up to the query length, in the contract's order, all before any device use.  k: a top-k
+// form's, else nullptr; host: lims / cand_rows are host arrays -- cand_rows may then be NULL where every slice is empty, and the
+// slices are checked; who: the entry point's name for the table refusal.
+static int rows_checks(const pqv_searcher *s, const void *lims, const void *cand_rows, const pqv_row_mask *mask, uint32_t nq, const uint32_t *k,
+                       int metric, bool host, uint32_t query_len, const char *who) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!lims) return fail(PQV_ERR_INVALID, "lims must not be NULL");
+    const uint64_t *hl = host ? static_cast<const uint64_t *>(lims) : nullptr;
+    bool any = !host;
+    for (uint32_t q = 0; q < nq && !any; ++q) any = hl[q + 1] != hl[q];
+    if (any && !cand_rows) return fail(PQV_ERR_INVALID, "cand_rows must not be NULL");
+    if (k && *k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (host) {
+        for (uint32_t q = 0; q < nq; ++q)
+            if (hl[q + 1] < hl[q]) return fail(PQV_ERR_INVALID, "lims must not decrease");
+        for (uint32_t q = 0; q < nq; ++q)
+            if (hl[q + 1] - hl[q] > 0xFFFFFFFFull) return fail(PQV_ERR_INVALID, "a candidate list holds at most 2^32 - 1 rows");
+    }
+    if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+    if (s->n_files) return fail(PQV_ERR_UNSUPPORTED, std::string(who) + " does not take table searchers");
+    if (int rc = validate_topk(s, 1, 1, metric)) return rc;
+    if (host && query_len != s->dim)
+        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) + ", got " + std::to_string(query_len));
+    return PQV_OK;
+}
+// Enqueue walk (-> fold) for the queries [0, nq) on `stream`, in PartitionWalk's pieces.  d_lims / d_rows: DEVICE arrays; lims0: the
+// device word the score form's output offsets are taken from.
+static int enqueue_rows(const pqv_searcher *s, Scratch &sc, const RowMap &map, const void *d_lims, const void *d_rows, const uint64_t *lims0,
+                        const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out, uint32_t *d_row_idx,
+                        float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+    using namespace pqv;
+    PartitionWalk w{s, sc, nullptr, SLICE_ROWS, bits, metric, stream};
+    w.map = map; w.lims0 = lims0;
+    if (int rc = w.size(nq)) return rc;
+    const uint32_t B = partition_blocks(s, w.piece, std::max<uint32_t>(1, k), s->n);
+    const uint32_t n_part = B * waves_per_block();
+    if (k) {
+        HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(w.piece) * n_part * k + 4) * sizeof(uint64_t)));
+        HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(w.piece) * n_part * k + 4) * sizeof(uint32_t)));
+    }
+    for (uint32_t q0 = 0; q0 < nq; q0 += w.piece) {
+        const uint32_t b = std::min<uint32_t>(w.piece, nq - q0);
+        StreamArgs ra;
+        RowsArgs wa;
+        if (int rc = w.launch_rows_at(q0, b, d_queries, d_lims, d_rows, d_n_cand, ra, wa)) return rc;
+        ra.k = k; ra.blocks_per_list = B;
+        if (k) {
+            ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
+            HIP_TRY(launch_rows_stream(ra, wa, stream));
+            if (int rc = partition_fold(s, ra, n_part, q0, metric, sqrt_out, d_row_idx, d_dist, d_n_found, stream)) return rc;
+            s->counters.kernel_launches += 2;
+        } else {
+            ra.out_f32 = d_dist; ra.sqrt_out = sqrt_out;
+            HIP_TRY(launch_rows_score(ra, wa, stream));
+            s->counters.kernel_launches += 1;
+        }
+    }
+    return PQV_OK;
+}
+// the device forms behind their checks (k == 0: scores)
+static int rows_device_impl(const pqv_searcher *s, const void *d_lims, const void *d_rows, const pqv_row_mask *mask, const void *d_queries,
+                            uint32_t nq, uint32_t k, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_cand,
+                            void *hip_stream) {
+    if (nq == 0) return PQV_OK;
+    if (!d_queries) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+    if (int rc = use_device(s->device)) return rc;
+    RowMap map{};
+    if (int rc = ensure_row_map(s, map)) return rc;
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+    return partition_device_call(s, static_cast<const float *>(d_queries), nq, metric, sqrt_out ? 1 : 0, stream,
+                                 [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
+                                     return enqueue_rows(bs, sc, map, d_lims, d_rows, static_cast<const uint64_t *>(d_lims), bits, q, nq, k, mt, so,
+                                                         static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist),
+                                                         static_cast<uint32_t *>(d_n_found), static_cast<uint64_t *>(d_n_cand), stream);
+                                 });
+}
+extern "C" int pqv_topk_rows_device(const pqv_searcher *s, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
+                                    const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out, void *d_row_idx, void *d_dist,
+                                    void *d_n_found, void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        if (int rc = rows_checks(s, d_lims, d_cand_rows, mask, nq, &k, metric, false, 0, "pqv_topk_rows")) return rc;
+        if (nq && (!d_row_idx || !d_dist)) return fail(PQV_ERR_INVALID, "row_idx/dist must not be NULL");
+        if (k > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_rows takes k <= 1024");
+        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, k, metric, sqrt_out, d_row_idx, d_dist, d_n_found, d_n_candidates,
+                                hip_stream);
+    });
+}
+extern "C" int pqv_score_rows_device(const pqv_searcher *s, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
+                                     const void *d_queries, uint32_t nq, int metric, int sqrt_out, void *d_dist, void *hip_stream) {
+    return guard([&] {
+        if (int rc = rows_checks(s, d_lims, d_cand_rows, mask, nq, nullptr, metric, false, 0, "pqv_score_rows")) return rc;
+        if (nq && !d_dist) return fail(PQV_ERR_INVALID, "dist must not be NULL");
+        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, 0, metric, sqrt_out, nullptr, d_dist, nullptr, nullptr, hip_stream);
+    });
+}
+// the host forms' request: the slices travel through host_batches as an IN filter's do
+static SearchRequest rows_request(const uint64_t *lims, const uint32_t *cand_rows) {
+    SearchRequest rq{};
+    rq.rows.kind = SLICE_ROWS; rq.rows.h_a = lims; rq.rows.h_b = cand_rows;
+    return rq;
+}
+extern "C" int pqv_topk_rows(const pqv_searcher *s, const uint64_t *lims, const uint32_t *cand_rows, const pqv_row_mask *mask,
+                             const float *queries, uint32_t nq, uint32_t query_len, uint32_t k, int metric, int sqrt_out, uint32_t *row_idx,
+                             float *dist, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        if (int rc = rows_checks(s, lims, cand_rows, mask, nq, &k, metric, true, query_len, "pqv_topk_rows")) return rc;
+        if (nq && (!row_idx || !dist)) return fail(PQV_ERR_INVALID, "row_idx/dist must not be NULL");
+        if (k > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_rows takes k <= 1024");
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        RowMap map{};
+        if (int rc = ensure_row_map(s, map)) return rc;
+        // (per list entry 12 B; beside the lists the rows, distances and n_found / n_candidates; the slices are as long as the caller made them)
+        return topk_partition_host_body(
+            s, s->n, rows_request(lims, cand_rows), mask, queries, nq, k, metric, sqrt_out ? 1 : 0, 12ull * k, 12ull * k + 12,
+            [&](Scratch &sc) {
+                return std::vector<BatchOut>{{&sc.s_rows, k * sizeof(uint32_t), row_idx}, {&sc.s_dist, k * sizeof(float), dist},
+                                             {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates}};
+            },
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
+                return enqueue_rows(bs, sc, map, d_a, d_b, nullptr, bits, sc.s_queries.as<float>(), b, k, mt, so, sc.s_rows.as<uint32_t>(),
+                                    sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(), bs->stream);
+            });
+    });
+}
+extern "C" int pqv_score_rows(const pqv_searcher *s, const uint64_t *lims, const uint32_t *cand_rows, const pqv_row_mask *mask,
+                              const float *queries, uint32_t nq, uint32_t query_len, int metric, int sqrt_out, float *dist) {
+    return guard([&] {
+        if (int rc = rows_checks(s, lims, cand_rows, mask, nq, nullptr, metric, true, query_len, "pqv_score_rows")) return rc;
+        if (nq && lims[nq] != lims[0] && !dist) return fail(PQV_ERR_INVALID, "dist must not be NULL");
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        RowMap map{};
+        if (int rc = ensure_row_map(s, map)) return rc;
+        // a sub-batch's distances come back from s_dist as one run of the caller's array: its slices are consecutive there (the
+        // sub-batches arrive in order: q_done is the first query of the one being enqueued)
+        uint32_t q_done = 0;
+        return topk_partition_host_body(
+            s, s->n, rows_request(lims, cand_rows), mask, queries, nq, 1, metric, sqrt_out ? 1 : 0, 0, 8,
+            [&](Scratch &) { return std::vector<BatchOut>{}; },
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
+                const uint64_t first = lims[q_done], n_vals = lims[q_done + b] - first;
+                q_done += b;
+                HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(n_vals) * sizeof(float)));
+                if (int rc = enqueue_rows(bs, sc, map, d_a, d_b, static_cast<const uint64_t *>(d_a), bits, sc.s_queries.as<float>(), b, 0, mt, so,
+                                          nullptr, sc.s_dist.as<float>(), nullptr, nullptr, bs->stream))
+                    return rc;
+                if (n_vals)
+                    HIP_TRY(hipMemcpyAsync(dist + (first - lims[0]), sc.s_dist.p, static_cast<size_t>(n_vals) * sizeof(float), hipMemcpyDeviceToHost,
+                                           bs->stream));
+                return static_cast<int>(PQV_OK);
             });
     });
 }
@@ -6818,7 +7036,7 @@ extern "C" int pqv_topk_partition_grouped(const pqv_searcher *s, const pqv_key_p
         const uint32_t m = group_size;
         const uint64_t km = static_cast<uint64_t>(k) * m;
         return topk_partition_host_body(
-            s, part, filter, mask, queries, nq, static_cast<uint32_t>(km), metric, sqrt_out ? 1 : 0,
+            s, part->m, partition_request(filter), mask, queries, nq, static_cast<uint32_t>(km), metric, sqrt_out ? 1 : 0,
             std::max<uint64_t>(std::max<uint64_t>(k * 20ull, km * 12), m > 1 ? km * 16 + 4 : 0), 32ull * k + 8 * km + 8 * PQV_KEY_SET_MAX + 16,
             [&](Scratch &sc) {
                 std::vector<BatchOut> outs = {{&sc.s_rows, km * sizeof(uint32_t), row_idx}, {&sc.s_dist, km * sizeof(float), dist},
@@ -7331,7 +7549,7 @@ static int pqv_searcher_footprint_impl(const pqv_searcher *s, uint64_t *row_orde
     if (ivf_rows_bytes) *ivf_rows_bytes = s->d_mat_ivf.p ? s->d_mat_ivf.bytes : 0;
     if (blocked_bytes) *blocked_bytes = (s->d_mat_blk_op[0].p ? s->d_mat_blk_op[0].bytes : 0) + (s->d_mat_blk_op[1].p ? s->d_mat_blk_op[1].bytes : 0) +
                                         (s->d_mat_blk_op[2].p ? s->d_mat_blk_op[2].bytes : 0);
-    uint64_t other = s->d_centroids.bytes + s->d_cent_t.bytes + s->d_ps_mu.bytes + s->d_ps_c16.bytes + s->d_ps_cn2.bytes + s->d_ps_stats.bytes + s->d_list_off.bytes + s->d_ids.bytes + s->d_stats.bytes + s->d_row_norm2.bytes + s->d_blk_off.bytes +
+    uint64_t other = s->d_centroids.bytes + s->d_cent_t.bytes + s->d_ps_mu.bytes + s->d_ps_c16.bytes + s->d_ps_cn2.bytes + s->d_ps_stats.bytes + s->d_list_off.bytes + s->d_ids.bytes + s->d_row_map.bytes + s->d_stats.bytes + s->d_row_norm2.bytes + s->d_blk_off.bytes +
                      s->d_center.bytes + s->d_list_scale.bytes + s->d_list_half.bytes + s->d_list_radius.bytes + s->d_row_n2i.bytes + s->d_row_res.bytes;
     for (const Scratch &l : s->lanes)
         for (const DevBuf *b : l.bufs()) other += b->p ? b->bytes : 0;

@@ -214,6 +214,31 @@ hipError_t launch_partition_grouped_stream(const StreamArgs &a, const PartitionA
 // a.nprobe must be 1.  Every wave adds the rows it evaluated to embeddings_fetched.  The segments go to launch_range_sort_*.
 hipError_t launch_partition_range(const StreamArgs &a, const PartitionArgs &pa, hipStream_t s);
 
+// ---- candidate lists (kernels_rows.hip; pqv.h: pqv_topk_rows, pqv_score_rows) -----------------------------------------------
+// The searcher's row -> list position map: map[r] = the list position that reports row r (ids[p] == r), 0xFFFFFFFF where no list
+// holds r; map_len = the corpus' rows, an id at or beyond it is dropped.  A fill and one scatter over the n_pos positions, on `s`.
+hipError_t launch_row_map(const uint32_t *ids, uint64_t n_pos, uint32_t *map, uint64_t map_len, hipStream_t s);
+// rows_stream_kernel: launch_partition_stream's grid, tile, keys and output format over caller-given sequences -- query q's is
+// cand_rows[lims[q] .. lims[q + 1]) as given (at most 2^32 - 1 positions of it; none where the slice is inverted), a position's
+// list position map[row] behind a compare of the row against map_len.  A position is walked iff that entry is a list position and
+// `bits` allows it; the walk is always the filtered one (walk_seq_windows, stream_walk.hpp).  Block 0 of a query writes
+// n_cand_out[q] = the sequence's length and adds it to candidate_rows; every wave adds the rows it evaluated to embeddings_fetched.
+struct RowsArgs {
+    const uint64_t     *lims;       // [nq + 1] offsets into cand_rows
+    const uint32_t     *cand_rows;
+    const uint32_t     *map;        // launch_row_map's
+    uint64_t            map_len;
+    const uint64_t     *bits;       // optional: a shared row mask's image (MaskedArgs::bits)
+    unsigned long long *stats;      // as MaskedArgs::stats
+    uint64_t           *n_cand_out; // optional [nq]
+    const uint64_t     *lims0;      // launch_rows_score: the word the output offsets are taken from (the lims word of the CALL's first
+                                    // query, which a piece's lims + q0 no longer begins with)
+};
+hipError_t launch_rows_stream(const StreamArgs &a, const RowsArgs &ra, hipStream_t s);
+// ... with every candidate's distance written instead of offered: a.out_f32[lims[q] - *lims0 + seq] on the output scale (a.sqrt_out
+// as StreamArgs documents it; PQV_DOT: 0.0f - s), +inf for a candidate that is not walked.  a.k / part_keys / part_vals are not read.
+hipError_t launch_rows_score(const StreamArgs &a, const RowsArgs &ra, hipStream_t s);
+
 // ---- expanding filtered top-k (kernels_expand.hip; pqv.h: pqv_topk_expand) ------------------------------------------------
 // filter_count_kernel: cnt[q * P + j] = the positions of list probe[q * P + j] that pass the call's filter -- the set bits of
 // the windows masked_stream_kernel forms for the same `win` (0: the mask image `bits`; 1 / 2: key_pos == a[q], i32 / i64; 3 / 4:

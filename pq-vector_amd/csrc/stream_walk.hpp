@@ -6,7 +6,8 @@
 //   chain_tile / l2_tile / dot_tile   the distance chain of one 64-row tile, in the reference's order of operations
 //   WalkRange / walk_range            the prologue: probed list, candidate base, cap, the wave's position range
 //   WindowQueue / filtered_walk       the walk over 64-position windows: compaction into a queue, a tile per 64 queued rows
-//   PartitionSeq                      a key partition's candidate sequence: position -> list position, a wave's windows
+//   PartitionSeq / walk_seq_windows   a key partition's candidate sequence: position -> list position, a wave's windows; the filtered
+//                                     walk of any such sequence (a caller's candidate list: RowsSeq, kernels_rows.hip)
 //   KeyTest                           a query's key test (EQ / RANGE / IN): setup once per block, one window per call
 //   GroupSet                          the k groups of a grouped call's pass 2: staged in LDS, membership and slot per key
 //   distinct_tile / grouped_tile ...  what a distinct / grouped kernel shares with its filtered twin: images, tile, list write-out
@@ -348,35 +349,46 @@ struct PartitionSeq {
             f(w0, nvalid, seq, entry(seq));
         }
     }
-    // The same windows under a per-position test: bit(lpos) of the window's positions is balloted and the set ones are compacted
-    // through a WindowQueue with lpos as payload; tile(lpos, seq, nvalid) runs whenever 64 are queued and once more behind the
-    // wave's last window (ONE call site, as in filtered_walk: the chain and the list's offer are instantiated once), so a position
-    // that fails the test is never loaded.  The lanes behind a last tile's end follow its last entry, payload included.
+    // The same windows under a per-position test bit(lpos): walk_seq_windows below over this sequence's entries
     template <class B, class T>
-    __device__ __forceinline__ void filtered_windows(uint32_t limit, float *lds, int wave, int lane, B &&bit, T &&tile) const {
-        WindowQueue<true> wq;
-        wq.cq = reinterpret_cast<uint32_t *>(lds);
-        const uint64_t stride = (uint64_t)gridDim.x * 256;
-        for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wave) * 64;; w0 += stride) {
-            const bool last = w0 >= limit;
-            QueueTile t;
-            if (!last) {
-                const uint32_t nvalid = limit - w0 < 64 ? (uint32_t)(limit - w0) : 64u;
-                const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
-                const uint32_t lpos = entry((uint32_t)w0 + lrow);
-                const bool on = (uint32_t)lane < nvalid && bit(lpos);
-                t = wq.push(__ballot(on), w0, lpos, lane);
-            } else {
-                t = wq.flush(lane);
-            }
-            if (t.nvalid) {
-                const uint32_t lp = (uint32_t)__shfl((int)t.my_x, (int)((uint32_t)lane < t.nvalid ? (uint32_t)lane : t.nvalid - 1), 64);
-                tile(lp, t.my_r, t.nvalid);
-            }
-            if (last) break;
-        }
-    }
+    __device__ __forceinline__ void filtered_windows(uint32_t limit, float *lds, int wave, int lane, B &&bit, T &&tile) const;
 };
+// The windows of a candidate sequence under a per-position test (PartitionSeq::filtered_windows; RowsSeq, kernels_rows.hip): wave
+// w of block x takes the 64-position windows (turn * gridDim.x + x) * 4 + w while they begin below `limit`; lane l's position gets
+// lpos = entry(seq) and, where it is inside the sequence, bit(lpos, seq) -- called for exactly those positions, once each.  The
+// set ones are balloted and compacted through a WindowQueue with lpos as payload; tile(lpos, seq, nvalid) runs whenever 64 are
+// queued and once more behind the wave's last window (ONE call site, as in filtered_walk: the chain and the list's offer are
+// instantiated once), so a position that fails the test is never loaded.  The lanes behind a last tile's end follow its last
+// entry, payload included.
+template <class E, class B, class T>
+__device__ __forceinline__ void walk_seq_windows(uint32_t limit, float *lds, int wave, int lane, E &&entry, B &&bit, T &&tile) {
+    WindowQueue<true> wq;
+    wq.cq = reinterpret_cast<uint32_t *>(lds);
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wave) * 64;; w0 += stride) {
+        const bool last = w0 >= limit;
+        QueueTile t;
+        if (!last) {
+            const uint32_t nvalid = limit - w0 < 64 ? (uint32_t)(limit - w0) : 64u;
+            const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
+            const uint32_t seq = (uint32_t)w0 + lrow;
+            const uint32_t lpos = entry(seq);
+            const bool on = (uint32_t)lane < nvalid && bit(lpos, seq);
+            t = wq.push(__ballot(on), w0, lpos, lane);
+        } else {
+            t = wq.flush(lane);
+        }
+        if (t.nvalid) {
+            const uint32_t lp = (uint32_t)__shfl((int)t.my_x, (int)((uint32_t)lane < t.nvalid ? (uint32_t)lane : t.nvalid - 1), 64);
+            tile(lp, t.my_r, t.nvalid);
+        }
+        if (last) break;
+    }
+}
+template <class B, class T>
+__device__ __forceinline__ void PartitionSeq::filtered_windows(uint32_t limit, float *lds, int wave, int lane, B &&bit, T &&tile) const {
+    walk_seq_windows(limit, lds, wave, lane, [&](uint32_t seq) { return entry(seq); }, [&](uint32_t lpos, uint32_t) { return bit(lpos); }, tile);
+}
 // bit p of a position image (a mask's or a key column's validity): a gathered 8-byte load; nullptr: set
 __device__ __forceinline__ bool image_bit(const uint64_t *img, uint32_t p) { return !img || ((img[p >> 6] >> (p & 63u)) & 1ull); }
 

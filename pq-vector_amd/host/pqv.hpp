@@ -95,6 +95,27 @@ public:
     }
     pqv_searcher *get() const { return h_.get(); }
     uint32_t dim() const { return dim_; }
+    // exact top-k among the rows the caller names per query -- query q's candidates are cand_rows[lims[q] .. lims[q + 1]) in any
+    // order, lims [nq + 1]; rows that are not indexed are skipped -- and, with `mask` (a RowMask's get()), that the mask allows
+    // (pqv.h: pqv_topk_rows); found[q] results per query, k slots each
+    void topk_rows(const std::vector<uint64_t> &lims, const std::vector<uint32_t> &cand_rows, const std::vector<float> &queries, uint32_t k,
+                   std::vector<uint32_t> &rows, std::vector<float> &dist, std::vector<uint32_t> &found,
+                   const pqv_row_mask *mask = nullptr) const {
+        const uint32_t nq = lims.empty() ? 0 : static_cast<uint32_t>(lims.size() - 1);
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, std::numeric_limits<float>::infinity());
+        found.assign(nq, 0);
+        check(pqv_topk_rows(h_.get(), lims.data(), cand_rows.data(), mask, queries.data(), nq, dim_, k, PQV_L2SQ_REF4, 1, rows.data(),
+                            dist.data(), found.data(), nullptr));
+    }
+    // ... and every candidate's exact distance instead: dist[i - lims[0]] for candidate i, +inf where it is not considered (pqv.h:
+    // pqv_score_rows)
+    void score_rows(const std::vector<uint64_t> &lims, const std::vector<uint32_t> &cand_rows, const std::vector<float> &queries,
+                    std::vector<float> &dist, const pqv_row_mask *mask = nullptr) const {
+        const uint32_t nq = lims.empty() ? 0 : static_cast<uint32_t>(lims.size() - 1);
+        dist.assign(nq && lims[nq] > lims[0] ? static_cast<size_t>(lims[nq] - lims[0]) : 0, std::numeric_limits<float>::infinity());
+        check(pqv_score_rows(h_.get(), lims.data(), cand_rows.data(), mask, queries.data(), nq, dim_, PQV_L2SQ_REF4, 1, dist.data()));
+    }
 private:
     struct Del { void operator()(pqv_searcher *p) const { pqv_searcher_free(p); } };
     std::unique_ptr<pqv_searcher, Del> h_;
