@@ -4410,6 +4410,94 @@ static TopkRoute topk_route(const pqv_searcher *s, const TopkPlan &p, uint32_t n
     return r;
 }
 
+// A top-k call's device outputs, the optional ones nullptr where the caller takes none: rows and dist [nq, k * m] (m: rows per group,
+// 1 off the grouped calls), n_found and n_cand [nq], group_key and group_rows [nq, k].  The host forms of the partition family
+// carry the caller's HOST arrays in one too (PartitionHostOuts).
+struct TopkOut {
+    uint32_t *rows; float *dist; uint32_t *n_found; uint64_t *n_cand; int64_t *group_key; uint32_t *group_rows;
+    // the block of the piece that starts at query q0 (km: k * m; the score form of the candidate-list calls, whose dist is indexed
+    // by candidate, passes k = km = 0)
+    TopkOut at(uint32_t q0, uint32_t k, size_t km) const {
+        const size_t q = q0;
+        return TopkOut{rows ? rows + q * km : nullptr, dist ? dist + q * km : nullptr, n_found ? n_found + q : nullptr,
+                       n_cand ? n_cand + q : nullptr, group_key ? group_key + q * k : nullptr, group_rows ? group_rows + q * k : nullptr};
+    }
+};
+
+// The two-pass fold of a distinct / grouped call (pqv.h: pqv_topk_grouped), probed (enqueue_topk) or over a key partition
+// (enqueue_partition_grouped): n_part per-wave lists per query, group_size rows per group (0: a distinct call; 1: one row per group,
+// its group_rows filled from n_found) of the k nearest groups of column col.  With more than one row per group, pass 1 is the distinct
+// call with its rows and distances going to the lane, and pass 2 behind its fold fills the caller's [nq, k, group_size] blocks.
+struct GroupFold {
+    uint32_t k, group_size, n_part; const pqv_row_keys *col; int sqrt_out;
+    bool two_pass() const { return group_size > 1; }
+    size_t km() const { return static_cast<size_t>(k) * std::max<uint32_t>(1, group_size); }      // (64-bit: no wrap)
+    bool fill(const TopkOut &o) const { return group_size == 1 && o.group_rows; }
+    // Every buffer of both passes, for nq queries: called before the first kernel of the batch or piece (DevBuf::ensure may move a
+    // buffer enqueued work still reads) -- the partial lists of pass 2 take over those of pass 1.  out: the caller's outputs.
+    int size(Scratch &sc, uint32_t nq, const TopkOut &out) const {
+        const size_t n_lists = static_cast<size_t>(nq) * n_part, km = this->km();
+        HIP_TRY(sc.s_part_keys.ensure((n_lists * km + 4) * sizeof(uint64_t)));
+        HIP_TRY(sc.s_part_vals.ensure((n_lists * km + 4) * sizeof(uint32_t)));
+        HIP_TRY(sc.s_part_grp.ensure((n_lists * k + 4) * sizeof(int64_t)));
+        if (two_pass()) {
+            HIP_TRY(sc.s_gpart_slot.ensure((n_lists * km + 4) * sizeof(uint32_t)));
+            HIP_TRY(sc.s_gpart_cnt.ensure((n_lists + 4) * sizeof(uint32_t)));
+            HIP_TRY(sc.s_g1_rows.ensure(static_cast<size_t>(nq) * k * sizeof(uint32_t)));
+            HIP_TRY(sc.s_g1_dist.ensure(static_cast<size_t>(nq) * k * sizeof(float)));
+            HIP_TRY(sc.s_gset_keys.ensure(static_cast<size_t>(nq) * k * sizeof(int64_t)));
+            HIP_TRY(sc.s_gset_slot.ensure(static_cast<size_t>(nq) * k * sizeof(uint32_t)));
+            if (!out.group_key) HIP_TRY(sc.s_g1_keys.ensure(static_cast<size_t>(nq) * k * sizeof(int64_t)));
+        }
+        if ((two_pass() || fill(out)) && !out.n_found) HIP_TRY(sc.s_g1_nfound.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
+        return PQV_OK;
+    }
+    // o (a batch's or a piece's block) with what the caller does not take but the fold reads going to the lane: pass 1's group values
+    // (read by the group set) and n_found (the group set, the rows-per-group fill).  The lane's buffers hold one batch or piece.
+    TopkOut on_lane(Scratch &sc, TopkOut o) const {
+        if (two_pass() && !o.group_key) o.group_key = sc.s_g1_keys.as<int64_t>();
+        if ((two_pass() || fill(o)) && !o.n_found) o.n_found = sc.s_g1_nfound.as<uint32_t>();
+        return o;
+    }
+    // The fold with at most one entry per group (distinct_merge_kernel) of the ra.nq queries' lists behind pass 1's walk, then a
+    // grouped call's pass 2 -- the k groups as a sorted set per query, walk(ga) over their rows only, and the fold (no host step
+    // between) -- or the rows-per-group fill.  s: the searcher whose rows are read; ra: pass 1's walk; out: on_lane's block.
+    // walk gets GroupedArgs with the column, the set, the sizes and the partial lists filled, adds what only its path has and
+    // launches its kernel.  Counted here: what is launched beyond the distinct merge.
+    template <class Walk>
+    int enqueue(const pqv_searcher *s, Scratch &sc, hipStream_t stream, const pqv::StreamArgs &ra, const TopkOut &out, Walk walk) const {
+        using namespace pqv;
+        const uint32_t nq = ra.nq, km = static_cast<uint32_t>(this->km());
+        DistinctMergeArgs dm{};
+        dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = sc.s_part_grp.as<int64_t>();
+        dm.nq = nq; dm.n_part = n_part; dm.k = k; dm.elem_size = col->elem_size();
+        dm.ids = s->d_final_ids; dm.row_idx = two_pass() ? sc.s_g1_rows.as<uint32_t>() : out.rows;
+        dm.dist = two_pass() ? sc.s_g1_dist.as<float>() : out.dist;
+        dm.group_key = out.group_key; dm.n_found = out.n_found; dm.sqrt_out = sqrt_out;
+        HIP_TRY(launch_distinct_merge(dm, stream));
+        if (two_pass()) {
+            HIP_TRY(launch_group_set(out.group_key, out.n_found, nq, k, sc.s_gset_keys.as<int64_t>(), sc.s_gset_slot.as<uint32_t>(), stream));
+            GroupedArgs ga{};
+            ga.key_pos = col->d_key_pos.p; ga.valid_pos = col->valid_image(); ga.elem_size = dm.elem_size;
+            ga.set_keys = sc.s_gset_keys.as<int64_t>(); ga.set_slot = sc.s_gset_slot.as<uint32_t>(); ga.n_found = out.n_found;
+            ga.k = k; ga.group_size = group_size; ga.km = km;
+            ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
+            ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
+            if (int rc = walk(ga)) return rc;
+            GroupedMergeArgs gma{};
+            gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
+            gma.nq = nq; gma.n_part = n_part; gma.k = k; gma.group_size = group_size; gma.km = km;
+            gma.ids = s->d_final_ids; gma.row_idx = out.rows; gma.dist = out.dist; gma.group_rows = out.group_rows; gma.sqrt_out = sqrt_out;
+            HIP_TRY(launch_grouped_merge(gma, stream));
+            s->counters.kernel_launches += 3;
+        } else if (fill(out)) {
+            HIP_TRY(launch_group_rows_fill(out.n_found, nq, k, out.group_rows, stream));
+            s->counters.kernel_launches += 1;
+        }
+        return PQV_OK;
+    }
+};
+
 // One enqueue_topk call as its stages see it: the caller's arguments, the plan, route and request they follow, and what earlier
 // stages leave for later ones.  Handed on by reference, never copied.
 struct TopkCall {
@@ -4425,9 +4513,8 @@ struct TopkCall {
     pqv::PairQuantArgs pq_args; bool quant_done;       // int8 screen: the query images' arguments; done inside the fused probe
     const uint64_t *pair_end;                   // round-robin capped table: every probed list's end of candidates
     const uint32_t *rank_limit;                 // expanding call: the lists each query walks (expand_depth)
-    // a distinct / grouped call (group_buffers): rows per group (0: distinct), gm > 1 (pass 2 behind the fold fills the caller's
-    // [nq, k, gm] blocks), k * max(1, gm), and where pass 1's n_found and group values go (the caller's blocks, or the lane's)
-    uint32_t gm; bool two_pass; size_t km; uint32_t *g_n_found; int64_t *g_keys;
+    // a distinct / grouped call (group_buffers): its fold, and the outputs the fold writes (the caller's blocks, or the lane's)
+    GroupFold gf; TopkOut g_out;
 };
 // stage: the probe works on the queries as given; everything that meets the (possibly zero-padded) stored rows gets the batch's
 // queries padded the same way
@@ -4439,40 +4526,19 @@ static int pad_queries(TopkCall &c) {
     c.d_queries_s = sc.s_qpad.as<float>();
     return PQV_OK;
 }
-// stage: the per-wave partial lists, and for a distinct / grouped call (pqv.h: pqv_topk_grouped) the buffers of both passes.  With
-// more than one row per group, pass 1 is the distinct call with its rows and distances going to the lane, and pass 2 behind its fold
-// fills the caller's [nq, k, group_size] blocks.  Every buffer of both passes is sized here, before the first kernel: the partial
-// lists of pass 2 take over those of pass 1.
+// stage: the per-wave partial lists, and for a distinct / grouped call every buffer of both passes of its fold (GroupFold::size),
+// before the first kernel
 static int group_buffers(TopkCall &c) {
     Scratch &sc = c.sc; const TopkPlan &p = c.p; const SearchRequest *rq = c.rq;
     const uint32_t nq = c.nq, k = c.k;
     HIP_TRY(sc.s_part_keys.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint64_t)));
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(uint32_t)));
-    const bool distinct = rq && rq->distinct();
-    if (distinct) HIP_TRY(sc.s_part_grp.ensure((static_cast<size_t>(nq) * p.n_part_rr * k + 4) * sizeof(int64_t)));
-    const uint32_t gm = distinct ? rq->groups.size : 0u;
-    const bool two_pass = gm > 1;
-    const size_t km = static_cast<size_t>(k) * std::max<uint32_t>(1, gm);
-    uint32_t *g_n_found = c.d_n_found;
-    int64_t *g_keys = distinct ? rq->groups.d_keys : nullptr;
-    if (two_pass) {
-        if (km > 1024 || k > pqv::GROUPED_SET_MAX) return fail(PQV_ERR_INVALID, "grouped call beyond the kernels' lists");
-        const size_t n_lists = static_cast<size_t>(nq) * p.n_part_rr;
-        HIP_TRY(sc.s_part_keys.ensure((n_lists * km + 4) * sizeof(uint64_t)));
-        HIP_TRY(sc.s_part_vals.ensure((n_lists * km + 4) * sizeof(uint32_t)));
-        HIP_TRY(sc.s_gpart_slot.ensure((n_lists * km + 4) * sizeof(uint32_t)));
-        HIP_TRY(sc.s_gpart_cnt.ensure((n_lists + 4) * sizeof(uint32_t)));
-        HIP_TRY(sc.s_g1_rows.ensure(static_cast<size_t>(nq) * k * sizeof(uint32_t)));
-        HIP_TRY(sc.s_g1_dist.ensure(static_cast<size_t>(nq) * k * sizeof(float)));
-        HIP_TRY(sc.s_gset_keys.ensure(static_cast<size_t>(nq) * k * sizeof(int64_t)));
-        HIP_TRY(sc.s_gset_slot.ensure(static_cast<size_t>(nq) * k * sizeof(uint32_t)));
-        if (!g_keys) { HIP_TRY(sc.s_g1_keys.ensure(static_cast<size_t>(nq) * k * sizeof(int64_t))); g_keys = sc.s_g1_keys.as<int64_t>(); }
-    }
-    if ((two_pass || (gm == 1 && rq->groups.d_rows)) && !g_n_found) {
-        HIP_TRY(sc.s_g1_nfound.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
-        g_n_found = sc.s_g1_nfound.as<uint32_t>();
-    }
-    c.gm = gm; c.two_pass = two_pass; c.km = km; c.g_n_found = g_n_found; c.g_keys = g_keys;
+    if (!rq || !rq->distinct()) return PQV_OK;
+    c.gf = GroupFold{k, rq->groups.size, p.n_part_rr, rq->groups.col, c.sqrt_out};
+    if (c.gf.two_pass() && (c.gf.km() > 1024 || k > pqv::GROUPED_SET_MAX)) return fail(PQV_ERR_INVALID, "grouped call beyond the kernels' lists");
+    const TopkOut out{c.d_row_idx, c.d_dist, c.d_n_found, nullptr, rq->groups.d_keys, rq->groups.d_rows};
+    if (int rc = c.gf.size(sc, nq, out)) return rc;
+    c.g_out = c.gf.on_lane(sc, out);
     return PQV_OK;
 }
 // stage 1: the centroid probe with everything the probe merge presets or writes on the way -- the tile paths' histogram and empty
@@ -4836,45 +4902,19 @@ static pqv::StreamArgs stream_args(const pqv_searcher *s, Scratch &sc, const flo
     ra.pair_end = table_rr(s, max_candidates) ? sc.s_pair_end.as<uint64_t>() : nullptr;   // (round-robin capped table)
     return ra;
 }
-// stage 3 of a distinct / grouped call: the fold with at most one entry per group (distinct_merge_kernel -- no tie flag, k_out == k),
-// then a grouped call's second pass, or the rows-per-group fill of a one-row-per-group call
+// stage 3 of a distinct / grouped call: GroupFold's fold (no tie flag, k_out == k); pass 2 walks the probed lists again, under the
+// call's row mask and per-query filter
 static int enqueue_group_fold(TopkCall &c, const pqv::StreamArgs &ra) {
     using namespace pqv;
-    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const TopkPlan &p = c.p; const SearchRequest *rq = c.rq; hipStream_t stream = c.stream;
-    const uint32_t nq = c.nq, k = c.k, k_out = c.k_out;
-    if (p.tile || k_out != k || c.d_tie) return fail(PQV_ERR_INVALID, "distinct call on a non-distinct plan");
-    DistinctMergeArgs dm{};
-    dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = sc.s_part_grp.as<int64_t>();
-    dm.nq = nq; dm.n_part = p.n_part_rr; dm.k = k; dm.elem_size = rq->groups.col->elem_size();
-    dm.ids = s->d_final_ids; dm.row_idx = c.d_row_idx; dm.dist = c.d_dist; dm.group_key = c.g_keys; dm.n_found = c.g_n_found;
-    dm.sqrt_out = c.sqrt_out;
-    if (c.two_pass) { dm.row_idx = sc.s_g1_rows.as<uint32_t>(); dm.dist = sc.s_g1_dist.as<float>(); }
-    HIP_TRY(launch_distinct_merge(dm, stream));
-    if (c.two_pass) {
-        // pass 2: the k groups as a sorted set per query, the walk again over their rows only, and the fold (no host step between)
-        const pqv_row_keys *gk = rq->groups.col;
-        HIP_TRY(launch_group_set(c.g_keys, c.g_n_found, nq, k, sc.s_gset_keys.as<int64_t>(), sc.s_gset_slot.as<uint32_t>(), stream));
-        GroupedArgs ga{};
-        ga.bits = rq->rows.bits; ga.stats = s->d_stats.as<unsigned long long>(); ga.key_pos = gk->d_key_pos.p;
-        ga.valid_pos = gk->valid_image(); ga.elem_size = dm.elem_size;
-        ga.set_keys = sc.s_gset_keys.as<int64_t>(); ga.set_slot = sc.s_gset_slot.as<uint32_t>(); ga.n_found = c.g_n_found;
-        ga.k = k; ga.group_size = c.gm; ga.km = static_cast<uint32_t>(c.km);
-        ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
-        ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
+    const pqv_searcher *s = c.s; const SearchRequest *rq = c.rq; hipStream_t stream = c.stream;
+    if (c.p.tile || c.k_out != c.k || c.d_tie) return fail(PQV_ERR_INVALID, "distinct call on a non-distinct plan");
+    return c.gf.enqueue(s, c.sc, stream, ra, c.g_out, [&](GroupedArgs &ga) {
+        ga.bits = rq->rows.bits; ga.stats = s->d_stats.as<unsigned long long>();
         ga.rank_limit = c.rank_limit;      // (an expanding call: both passes walk the same ranks)
         if (rq->filtered()) HIP_TRY(launch_grouped_filter_stream(ra, ga, group_filter_args(rq), stream));
         else HIP_TRY(launch_grouped_stream(ra, ga, stream));
-        GroupedMergeArgs gma{};
-        gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
-        gma.nq = nq; gma.n_part = p.n_part_rr; gma.k = k; gma.group_size = c.gm; gma.km = ga.km;
-        gma.ids = s->d_final_ids; gma.row_idx = c.d_row_idx; gma.dist = c.d_dist; gma.group_rows = rq->groups.d_rows; gma.sqrt_out = c.sqrt_out;
-        HIP_TRY(launch_grouped_merge(gma, stream));
-        s->counters.kernel_launches += 3;
-    } else if (c.gm == 1 && rq->groups.d_rows) {
-        HIP_TRY(launch_group_rows_fill(c.g_n_found, nq, k, rq->groups.d_rows, stream));
-        s->counters.kernel_launches += 1;
-    }
-    return PQV_OK;
+        return static_cast<int>(PQV_OK);
+    });
 }
 // stage 3 of every other call: the final merge of the per-wave lists (and the wide screen's candidate buffers)
 static int enqueue_plain_fold(TopkCall &c, const pqv::StreamArgs &ra) {
@@ -6418,24 +6458,24 @@ struct PartitionWalk {
         pa.n_cand = sp.n_cand; pa.kind = kind; pa.bits = bits; pa.stats = sp.stats;
         return PQV_OK;
     }
-    // the piece [q0, q0 + b) of a call whose queries, a / b and n_cand are whole DEVICE arrays: every kind's a is indexed by query --
-    // an IN filter's lims hold offsets into ALL of b -- so a piece takes a + q0 and, but for a RANGE filter's, b as it is
-    int launch_at(uint32_t q0, uint32_t b, const float *d_queries, const void *d_a, const void *d_b, uint64_t *d_n_cand, pqv::StreamArgs &ra,
+    // the piece [q0, q0 + b) of a call whose queries and a / b are whole DEVICE arrays: every kind's a is indexed by query -- an IN
+    // filter's lims hold offsets into ALL of b -- so a piece takes a + q0 and, but for a RANGE filter's, b as it is.  o: the
+    // piece's output block (TopkOut::at), whose n_cand the span kernel writes.
+    int launch_at(uint32_t q0, uint32_t b, const float *d_queries, const void *d_a, const void *d_b, const TopkOut &o, pqv::StreamArgs &ra,
                   pqv::PartitionArgs &pa) const {
         const size_t off = static_cast<size_t>(q0) * 8;
         return launch(d_queries + static_cast<size_t>(q0) * s->dim, b, static_cast<const char *>(d_a) + off,
-                      kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + off) : d_b,
-                      d_n_cand ? d_n_cand + q0 : nullptr, ra, pa);
+                      kind == PQV_KEY_RANGE ? static_cast<const void *>(static_cast<const char *>(d_b) + off) : d_b, o.n_cand, ra, pa);
     }
     // SLICE_ROWS: the same piece of a candidate-list call -- d_lims indexed from the piece's first query, d_rows whole (lims hold
     // offsets into all of it); nothing is launched beside the padding, the walk's kernel reads the slices itself
-    int launch_rows_at(uint32_t q0, uint32_t b, const float *d_queries, const void *d_lims, const void *d_rows, uint64_t *d_n_cand,
+    int launch_rows_at(uint32_t q0, uint32_t b, const float *d_queries, const void *d_lims, const void *d_rows, const TopkOut &o,
                        pqv::StreamArgs &ra, pqv::RowsArgs &wa) const {
         if (int rc = stream_args(d_queries + static_cast<size_t>(q0) * s->dim, b, ra)) return rc;
         wa = pqv::RowsArgs{};
         wa.lims = static_cast<const uint64_t *>(d_lims) + q0; wa.cand_rows = static_cast<const uint32_t *>(d_rows);
         wa.map = map.map; wa.map_len = map.len; wa.bits = bits; wa.stats = s->d_stats.as<unsigned long long>();
-        wa.n_cand_out = d_n_cand ? d_n_cand + q0 : nullptr; wa.lims0 = lims0;
+        wa.n_cand_out = o.n_cand; wa.lims0 = lims0;
         return PQV_OK;
     }
 };
@@ -6470,15 +6510,38 @@ static SearchRequest partition_request(const pqv_key_filter *f) {
     else { rq.rows.h_a = f->a; rq.rows.h_b = f->b; }
     return rq;
 }
+// The outputs of a host form of the partition family (topk_partition_host_body) on a lane: `host`, the caller's arrays (rows and
+// dist k * m per query; none at all: the score form, which brings its distances back itself), as the list host_batches sizes and
+// copies back, and as the block over the same scratch buffers that a sub-batch's kernels write.  n_candidates comes back through
+// s_out: the walk stage uses s_ncand itself.  A grouped call's keys are always written (group_key NULL: sized, not copied), its rows
+// per group where the caller takes them.
+struct PartitionHostOuts {
+    TopkOut host; uint32_t k; uint64_t km; bool grouped;
+    bool rows_per_group() const { return grouped && host.group_rows; }
+    std::vector<BatchOut> batch(Scratch &sc) const {
+        if (!host.dist) return {};
+        std::vector<BatchOut> outs = {{&sc.s_rows, km * sizeof(uint32_t), host.rows}, {&sc.s_dist, km * sizeof(float), host.dist},
+                                      {&sc.s_nfound, sizeof(uint32_t), host.n_found}, {&sc.s_out, sizeof(uint64_t), host.n_cand}};
+        if (grouped) outs.push_back({&sc.s_grp_out, k * sizeof(int64_t), host.group_key});
+        if (rows_per_group()) outs.push_back({&sc.s_grows_out, k * sizeof(uint32_t), host.group_rows});
+        return outs;
+    }
+    TopkOut dev(Scratch &sc) const {      // (once host_batches has sized them)
+        if (!host.dist) return TopkOut{};
+        return TopkOut{sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(),
+                       grouped ? sc.s_grp_out.as<int64_t>() : nullptr, rows_per_group() ? sc.s_grows_out.as<uint32_t>() : nullptr};
+    }
+};
 // The host form of the partition top-k calls and the candidate-list calls: PQV_COSINE's n(q), the lane, sub-batches of queries
 // through it (rq's per-query slices -- a filter's, or the candidate lists -- uploaded as pqv_topk_filtered uploads a filter's; m:
-// the positions partition_blocks sizes the grid by), enqueue(s, sc, bits, d_a, d_b, b, metric, sqrt_out) -- the device body on a sub-batch's
-// scratch -- and outs(sc) back.  The sub-batch is bounded so the scratch stays under ~1 GiB: per query the B * 4 per-wave lists of
-// k_lists entries, list_bytes in all passes' widest, the padded query, and out_bytes of outputs and filter slice.
-template <class Outs, class Enqueue>
+// the positions partition_blocks sizes the grid by), enqueue(s, sc, bits, d_a, d_b, b, metric, sqrt_out, out) -- the device body on a
+// sub-batch's scratch, out: outs.dev(sc) -- and outs.batch(sc) back.  The sub-batch is bounded so the scratch stays under ~1 GiB: per
+// query the B * 4 per-wave lists of k_lists entries, list_bytes in all passes' widest, the padded query, and out_bytes of outputs and
+// filter slice.
+template <class Enqueue>
 static int topk_partition_host_body(const pqv_searcher *s, uint64_t m, const SearchRequest &rq, const pqv_row_mask *mask,
                                     const float *queries, uint32_t nq, uint32_t k_lists, int metric, int sqrt_out, uint64_t list_bytes,
-                                    uint64_t out_bytes, Outs outs, Enqueue enqueue) {
+                                    uint64_t out_bytes, const PartitionHostOuts &outs, Enqueue enqueue) {
     std::vector<float> nq_host;
     if (int rc = cosine_queries_host(s, queries, nq, metric, sqrt_out, nq_host)) return rc;
     const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
@@ -6490,34 +6553,36 @@ static int topk_partition_host_body(const pqv_searcher *s, uint64_t m, const Sea
     const uint64_t per_query = static_cast<uint64_t>(B) * 4 * list_bytes + static_cast<uint64_t>(s->sdim) * 8 + out_bytes;
     const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(nq, PARTITION_GRID_Q), (1ull << 30) / per_query)));
     if (int rc = host_batches(
-            s, sc, queries, nq, batch, &rq, nullptr, outs(sc),
-            [&](uint32_t b, SearchRequest *brq) { return enqueue(s, sc, bits, brq->d_filter_a(), brq->d_filter_b(), b, metric, sqrt_out); },
+            s, sc, queries, nq, batch, &rq, nullptr, outs.batch(sc),
+            [&](uint32_t b, SearchRequest *brq) {
+                return enqueue(s, sc, bits, brq->d_filter_a(), brq->d_filter_b(), b, metric, sqrt_out, outs.dev(sc));
+            },
             [](uint32_t, uint32_t) { return static_cast<int>(PQV_OK); }))      // (no host step)
         return rc;
     return lane.release();
 }
 
 // ---- top-k over a key partition (pqv.h: pqv_topk_partition) ----------------------------------------------------------------------
-// The fold of a piece's per-wave lists (ra: the walk's arguments, n_part lists of ra.k entries per query) into the call's outputs
-// from query q0 on: merge_kernel, PQV_DOT: dot_merge_kernel.
-static int partition_fold(const pqv_searcher *s, const pqv::StreamArgs &ra, uint32_t n_part, uint32_t q0, int metric, int sqrt_out,
-                          uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, hipStream_t stream) {
+// The fold of a piece's per-wave lists (ra: the walk's arguments, n_part lists of ra.k entries per query) into the piece's output
+// block o: merge_kernel, PQV_DOT: dot_merge_kernel.
+static int partition_fold(const pqv_searcher *s, const pqv::StreamArgs &ra, uint32_t n_part, int metric, int sqrt_out, const TopkOut &o,
+                          hipStream_t stream) {
     using namespace pqv;
     const uint32_t k = ra.k;
     MergeArgs fm{};
     fm.part_keys = ra.part_keys; fm.part_vals = ra.part_vals;
     fm.nq = ra.nq; fm.n_part = n_part; fm.k_part = k; fm.k = k;
-    fm.ids = s->d_final_ids; fm.row_idx = d_row_idx + static_cast<size_t>(q0) * k; fm.dist = d_dist + static_cast<size_t>(q0) * k;
-    fm.n_found = d_n_found ? d_n_found + q0 : nullptr;
+    fm.ids = s->d_final_ids; fm.row_idx = o.rows; fm.dist = o.dist; fm.n_found = o.n_found;
     fm.sqrt_out = sqrt_out; fm.k_out = k;
     if (metric == PQV_DOT) HIP_TRY(launch_dot_merge(fm, stream));
     else HIP_TRY(launch_merge_final(fm, stream));
     return PQV_OK;
 }
-// Enqueue span -> stream -> fold for the queries [0, nq) on `stream`, in PartitionWalk's pieces.  a / b: the descriptor's DEVICE arrays.
+// Enqueue span -> stream -> fold for the queries [0, nq) on `stream`, in PartitionWalk's pieces.  a / b: the descriptor's DEVICE arrays;
+// out: the call's outputs.
 static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
                              const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
-                             uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+                             const TopkOut &out, hipStream_t stream) {
     using namespace pqv;
     PartitionWalk w{s, sc, part, kind, bits, metric, stream};
     if (int rc = w.size(nq)) return rc;
@@ -6527,25 +6592,17 @@ static int enqueue_partition(const pqv_searcher *s, Scratch &sc, const pqv_key_p
     HIP_TRY(sc.s_part_vals.ensure((static_cast<size_t>(w.piece) * n_part * k + 4) * sizeof(uint32_t)));
     for (uint32_t q0 = 0; q0 < nq; q0 += w.piece) {
         const uint32_t b = std::min<uint32_t>(w.piece, nq - q0);
+        const TopkOut o = out.at(q0, k, k);
         StreamArgs ra;
         PartitionArgs pa;
-        if (int rc = w.launch_at(q0, b, d_queries, d_a, d_b, d_n_cand, ra, pa)) return rc;
+        if (int rc = w.launch_at(q0, b, d_queries, d_a, d_b, o, ra, pa)) return rc;
         ra.k = k; ra.blocks_per_list = B;
         ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
         HIP_TRY(launch_partition_stream(ra, pa, stream));
-        if (int rc = partition_fold(s, ra, n_part, q0, metric, sqrt_out, d_row_idx, d_dist, d_n_found, stream)) return rc;
+        if (int rc = partition_fold(s, ra, n_part, metric, sqrt_out, o, stream)) return rc;
         s->counters.kernel_launches += 3;
     }
     return PQV_OK;
-}
-// the device form behind its checks
-static int topk_partition_device_impl(const pqv_searcher *s, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
-                                      const pqv_row_mask *mask, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
-                                      uint32_t *d_row_idx, float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
-    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
-    return partition_device_call(s, d_queries, nq, metric, sqrt_out, stream, [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
-        return enqueue_partition(bs, sc, part, kind, d_a, d_b, bits, q, nq, k, mt, so, d_row_idx, d_dist, d_n_found, d_n_cand, stream);
-    });
 }
 extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
                                          const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out,
@@ -6556,9 +6613,13 @@ extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_pa
         if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
         if (int rc = use_device(s->device)) return rc;
         hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
-        return topk_partition_device_impl(s, part, filter->kind, filter->a, filter->b, mask, static_cast<const float *>(d_queries), nq, k, metric,
-                                          sqrt_out ? 1 : 0, static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist),
-                                          static_cast<uint32_t *>(d_n_found), static_cast<uint64_t *>(d_n_candidates), stream);
+        const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+        const TopkOut out{static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
+                          static_cast<uint64_t *>(d_n_candidates)};
+        return partition_device_call(s, static_cast<const float *>(d_queries), nq, metric, sqrt_out ? 1 : 0, stream,
+                                     [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
+                                         return enqueue_partition(bs, sc, part, filter->kind, filter->a, filter->b, bits, q, nq, k, mt, so, out, stream);
+                                     });
     });
 }
 extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter, const pqv_row_mask *mask,
@@ -6572,13 +6633,10 @@ extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition
         // (per list entry 12 B; beside the lists the rows, distances and n_found / n_candidates, and an IN slice)
         return topk_partition_host_body(
             s, part->m, partition_request(filter), mask, queries, nq, k, metric, sqrt_out ? 1 : 0, 12ull * k, 12ull * k + 8 * PQV_KEY_SET_MAX,
-            [&](Scratch &sc) {
-                return std::vector<BatchOut>{{&sc.s_rows, k * sizeof(uint32_t), row_idx}, {&sc.s_dist, k * sizeof(float), dist},
-                                             {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates}};
-            },
-            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
-                return enqueue_partition(bs, sc, part, filter->kind, d_a, d_b, bits, sc.s_queries.as<float>(), b, k, mt, so, sc.s_rows.as<uint32_t>(),
-                                         sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(), bs->stream);
+            PartitionHostOuts{{row_idx, dist, n_found, n_candidates}, k, k, false},
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so,
+                const TopkOut &out) {
+                return enqueue_partition(bs, sc, part, filter->kind, d_a, d_b, bits, sc.s_queries.as<float>(), b, k, mt, so, out, bs->stream);
             });
     });
 }
@@ -6629,10 +6687,10 @@ static int rows_checks(const pqv_searcher *s, const void *lims, const void *cand
     return PQV_OK;
 }
 // Enqueue walk (-> fold) for the queries [0, nq) on `stream`, in PartitionWalk's pieces.  d_lims / d_rows: DEVICE arrays; lims0: the
-// device word the score form's output offsets are taken from.
+// device word the score form's output offsets are taken from; out: the call's outputs (k == 0: dist alone, a distance per candidate).
 static int enqueue_rows(const pqv_searcher *s, Scratch &sc, const RowMap &map, const void *d_lims, const void *d_rows, const uint64_t *lims0,
-                        const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out, uint32_t *d_row_idx,
-                        float *d_dist, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+                        const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k, int metric, int sqrt_out, const TopkOut &out,
+                        hipStream_t stream) {
     using namespace pqv;
     PartitionWalk w{s, sc, nullptr, SLICE_ROWS, bits, metric, stream};
     w.map = map; w.lims0 = lims0;
@@ -6645,17 +6703,18 @@ static int enqueue_rows(const pqv_searcher *s, Scratch &sc, const RowMap &map, c
     }
     for (uint32_t q0 = 0; q0 < nq; q0 += w.piece) {
         const uint32_t b = std::min<uint32_t>(w.piece, nq - q0);
+        const TopkOut o = out.at(q0, k, k);
         StreamArgs ra;
         RowsArgs wa;
-        if (int rc = w.launch_rows_at(q0, b, d_queries, d_lims, d_rows, d_n_cand, ra, wa)) return rc;
+        if (int rc = w.launch_rows_at(q0, b, d_queries, d_lims, d_rows, o, ra, wa)) return rc;
         ra.k = k; ra.blocks_per_list = B;
         if (k) {
             ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
             HIP_TRY(launch_rows_stream(ra, wa, stream));
-            if (int rc = partition_fold(s, ra, n_part, q0, metric, sqrt_out, d_row_idx, d_dist, d_n_found, stream)) return rc;
+            if (int rc = partition_fold(s, ra, n_part, metric, sqrt_out, o, stream)) return rc;
             s->counters.kernel_launches += 2;
         } else {
-            ra.out_f32 = d_dist; ra.sqrt_out = sqrt_out;
+            ra.out_f32 = o.dist; ra.sqrt_out = sqrt_out;
             HIP_TRY(launch_rows_score(ra, wa, stream));
             s->counters.kernel_launches += 1;
         }
@@ -6664,8 +6723,7 @@ static int enqueue_rows(const pqv_searcher *s, Scratch &sc, const RowMap &map, c
 }
 // the device forms behind their checks (k == 0: scores)
 static int rows_device_impl(const pqv_searcher *s, const void *d_lims, const void *d_rows, const pqv_row_mask *mask, const void *d_queries,
-                            uint32_t nq, uint32_t k, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_cand,
-                            void *hip_stream) {
+                            uint32_t nq, uint32_t k, int metric, int sqrt_out, const TopkOut &out, void *hip_stream) {
     if (nq == 0) return PQV_OK;
     if (!d_queries) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
     if (int rc = use_device(s->device)) return rc;
@@ -6676,8 +6734,7 @@ static int rows_device_impl(const pqv_searcher *s, const void *d_lims, const voi
     return partition_device_call(s, static_cast<const float *>(d_queries), nq, metric, sqrt_out ? 1 : 0, stream,
                                  [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
                                      return enqueue_rows(bs, sc, map, d_lims, d_rows, static_cast<const uint64_t *>(d_lims), bits, q, nq, k, mt, so,
-                                                         static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist),
-                                                         static_cast<uint32_t *>(d_n_found), static_cast<uint64_t *>(d_n_cand), stream);
+                                                         out, stream);
                                  });
 }
 extern "C" int pqv_topk_rows_device(const pqv_searcher *s, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
@@ -6687,8 +6744,9 @@ extern "C" int pqv_topk_rows_device(const pqv_searcher *s, const void *d_lims, c
         if (int rc = rows_checks(s, d_lims, d_cand_rows, mask, nq, &k, metric, false, 0, "pqv_topk_rows")) return rc;
         if (nq && (!d_row_idx || !d_dist)) return fail(PQV_ERR_INVALID, "row_idx/dist must not be NULL");
         if (k > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_rows takes k <= 1024");
-        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, k, metric, sqrt_out, d_row_idx, d_dist, d_n_found, d_n_candidates,
-                                hip_stream);
+        const TopkOut out{static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
+                          static_cast<uint64_t *>(d_n_candidates)};
+        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, k, metric, sqrt_out, out, hip_stream);
     });
 }
 extern "C" int pqv_score_rows_device(const pqv_searcher *s, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
@@ -6696,7 +6754,8 @@ extern "C" int pqv_score_rows_device(const pqv_searcher *s, const void *d_lims, 
     return guard([&] {
         if (int rc = rows_checks(s, d_lims, d_cand_rows, mask, nq, nullptr, metric, false, 0, "pqv_score_rows")) return rc;
         if (nq && !d_dist) return fail(PQV_ERR_INVALID, "dist must not be NULL");
-        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, 0, metric, sqrt_out, nullptr, d_dist, nullptr, nullptr, hip_stream);
+        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, 0, metric, sqrt_out, TopkOut{nullptr, static_cast<float *>(d_dist)},
+                                hip_stream);
     });
 }
 // the host forms' request: the slices travel through host_batches as an IN filter's do
@@ -6720,13 +6779,10 @@ extern "C" int pqv_topk_rows(const pqv_searcher *s, const uint64_t *lims, const 
         // (per list entry 12 B; beside the lists the rows, distances and n_found / n_candidates; the slices are as long as the caller made them)
         return topk_partition_host_body(
             s, s->n, rows_request(lims, cand_rows), mask, queries, nq, k, metric, sqrt_out ? 1 : 0, 12ull * k, 12ull * k + 12,
-            [&](Scratch &sc) {
-                return std::vector<BatchOut>{{&sc.s_rows, k * sizeof(uint32_t), row_idx}, {&sc.s_dist, k * sizeof(float), dist},
-                                             {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates}};
-            },
-            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
-                return enqueue_rows(bs, sc, map, d_a, d_b, nullptr, bits, sc.s_queries.as<float>(), b, k, mt, so, sc.s_rows.as<uint32_t>(),
-                                    sc.s_dist.as<float>(), sc.s_nfound.as<uint32_t>(), sc.s_out.as<uint64_t>(), bs->stream);
+            PartitionHostOuts{{row_idx, dist, n_found, n_candidates}, k, k, false},
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so,
+                const TopkOut &out) {
+                return enqueue_rows(bs, sc, map, d_a, d_b, nullptr, bits, sc.s_queries.as<float>(), b, k, mt, so, out, bs->stream);
             });
     });
 }
@@ -6745,13 +6801,14 @@ extern "C" int pqv_score_rows(const pqv_searcher *s, const uint64_t *lims, const
         uint32_t q_done = 0;
         return topk_partition_host_body(
             s, s->n, rows_request(lims, cand_rows), mask, queries, nq, 1, metric, sqrt_out ? 1 : 0, 0, 8,
-            [&](Scratch &) { return std::vector<BatchOut>{}; },
-            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
+            PartitionHostOuts{},
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so,
+                const TopkOut &) {
                 const uint64_t first = lims[q_done], n_vals = lims[q_done + b] - first;
                 q_done += b;
                 HIP_TRY(sc.s_dist.ensure(static_cast<size_t>(n_vals) * sizeof(float)));
                 if (int rc = enqueue_rows(bs, sc, map, d_a, d_b, static_cast<const uint64_t *>(d_a), bits, sc.s_queries.as<float>(), b, 0, mt, so,
-                                          nullptr, sc.s_dist.as<float>(), nullptr, nullptr, bs->stream))
+                                          TopkOut{nullptr, sc.s_dist.as<float>()}, bs->stream))
                     return rc;
                 if (n_vals)
                     HIP_TRY(hipMemcpyAsync(dist + (first - lims[0]), sc.s_dist.p, static_cast<size_t>(n_vals) * sizeof(float), hipMemcpyDeviceToHost,
@@ -6912,94 +6969,39 @@ extern "C" int pqv_range_search_partition(const pqv_searcher *s, const pqv_key_p
 
 // ---- distinct / grouped top-k over a key partition (pqv.h: pqv_topk_partition_grouped) ------------------------------------------
 // Enqueue both passes for the queries [0, nq) on `stream`, in PartitionWalk's pieces: the span kernel (once per piece), the
-// distinct stream and its fold, then for m > 1 the group set, the grouped stream and its fold -- or, for m == 1, the rows-per-group
-// fill where d_group_rows is asked for.  One B for both passes; every buffer of a piece is sized before its first kernel (the partial
-// lists of pass 2 take over those of pass 1).  `s`: the searcher whose rows are read; a / b: the descriptor's DEVICE arrays.
+// distinct stream, and GroupFold's fold with the grouped stream over the same spans as its pass-2 walk.  One B for both passes;
+// every buffer of a piece is sized before its first kernel.  `s`: the searcher whose rows are read; a / b: the descriptor's DEVICE
+// arrays; out: the call's outputs.
 static int enqueue_partition_grouped(const pqv_searcher *s, Scratch &sc, const pqv_key_partition *part, uint32_t kind, const void *d_a,
                                      const void *d_b, const pqv_row_keys *gk, const uint64_t *bits, const float *d_queries, uint32_t nq, uint32_t k,
-                                     uint32_t m, int metric, int sqrt_out, uint32_t *d_row_idx, float *d_dist, int64_t *d_group_key,
-                                     uint32_t *d_group_rows, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
+                                     uint32_t m, int metric, int sqrt_out, const TopkOut &out, hipStream_t stream) {
     using namespace pqv;
     PartitionWalk w{s, sc, part, kind, bits, metric, stream};
     if (int rc = w.size(nq)) return rc;
-    const uint32_t piece = w.piece;
     const uint32_t km = k * m;                                              // (<= 1024: partition_checks)
-    const bool two_pass = m > 1;
-    const uint32_t B = partition_blocks(s, piece, km, part->m);
-    const uint32_t n_part = B * waves_per_block();
-    const size_t n_lists = static_cast<size_t>(piece) * n_part;
-    HIP_TRY(sc.s_part_keys.ensure((n_lists * km + 4) * sizeof(uint64_t)));
-    HIP_TRY(sc.s_part_vals.ensure((n_lists * km + 4) * sizeof(uint32_t)));
-    HIP_TRY(sc.s_part_grp.ensure((n_lists * k + 4) * sizeof(int64_t)));
-    if (two_pass) {
-        HIP_TRY(sc.s_gpart_slot.ensure((n_lists * km + 4) * sizeof(uint32_t)));
-        HIP_TRY(sc.s_gpart_cnt.ensure((n_lists + 4) * sizeof(uint32_t)));
-        HIP_TRY(sc.s_g1_rows.ensure(static_cast<size_t>(piece) * k * sizeof(uint32_t)));
-        HIP_TRY(sc.s_g1_dist.ensure(static_cast<size_t>(piece) * k * sizeof(float)));
-        HIP_TRY(sc.s_gset_keys.ensure(static_cast<size_t>(piece) * k * sizeof(int64_t)));
-        HIP_TRY(sc.s_gset_slot.ensure(static_cast<size_t>(piece) * k * sizeof(uint32_t)));
-        if (!d_group_key) HIP_TRY(sc.s_g1_keys.ensure(static_cast<size_t>(piece) * k * sizeof(int64_t)));
-    }
-    const bool need_found = two_pass || d_group_rows;                       // (read by the group set / the rows-per-group fill)
-    if (need_found && !d_n_found) HIP_TRY(sc.s_g1_nfound.ensure(static_cast<size_t>(piece) * sizeof(uint32_t)));
-    for (uint32_t q0 = 0; q0 < nq; q0 += piece) {
-        const uint32_t b = std::min<uint32_t>(piece, nq - q0);
-        // the piece's outputs: keys, counts and n_found at q0 * k / q0, rows and distances at q0 * k * m
-        uint32_t *o_rows = d_row_idx + static_cast<size_t>(q0) * km;
-        float *o_dist = d_dist + static_cast<size_t>(q0) * km;
-        int64_t *o_keys = d_group_key ? d_group_key + static_cast<size_t>(q0) * k : two_pass ? sc.s_g1_keys.as<int64_t>() : nullptr;
-        uint32_t *o_found = d_n_found ? d_n_found + q0 : need_found ? sc.s_g1_nfound.as<uint32_t>() : nullptr;
-        uint32_t *o_grows = d_group_rows ? d_group_rows + static_cast<size_t>(q0) * k : nullptr;
-
+    const uint32_t B = partition_blocks(s, w.piece, km, part->m);
+    const GroupFold fold{k, m, B * waves_per_block(), gk, sqrt_out};
+    if (int rc = fold.size(sc, w.piece, out)) return rc;
+    for (uint32_t q0 = 0; q0 < nq; q0 += w.piece) {
+        const uint32_t b = std::min<uint32_t>(w.piece, nq - q0);
+        const TopkOut o = fold.on_lane(sc, out.at(q0, k, km));
         StreamArgs ra;
         PartitionArgs pa;
-        if (int rc = w.launch_at(q0, b, d_queries, d_a, d_b, d_n_cand, ra, pa)) return rc;
+        if (int rc = w.launch_at(q0, b, d_queries, d_a, d_b, o, ra, pa)) return rc;
         ra.k = k; ra.blocks_per_list = B;
         ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
         DistinctArgs da{};
         da.key_pos = gk->d_key_pos.p; da.valid_pos = gk->valid_image(); da.elem_size = gk->elem_size();
         da.part_grp = sc.s_part_grp.as<int64_t>();
         HIP_TRY(launch_partition_distinct_stream(ra, pa, da, stream));
-
-        DistinctMergeArgs dm{};
-        dm.part_keys = ra.part_keys; dm.part_vals = ra.part_vals; dm.part_grp = da.part_grp;
-        dm.nq = b; dm.n_part = n_part; dm.k = k; dm.elem_size = da.elem_size;
-        dm.ids = s->d_final_ids; dm.row_idx = two_pass ? sc.s_g1_rows.as<uint32_t>() : o_rows; dm.dist = two_pass ? sc.s_g1_dist.as<float>() : o_dist;
-        dm.group_key = o_keys; dm.n_found = o_found; dm.sqrt_out = sqrt_out;
-        HIP_TRY(launch_distinct_merge(dm, stream));
         s->counters.kernel_launches += 3;
-        if (two_pass) {
-            HIP_TRY(launch_group_set(o_keys, o_found, b, k, sc.s_gset_keys.as<int64_t>(), sc.s_gset_slot.as<uint32_t>(), stream));
-            GroupedArgs ga{};
-            ga.key_pos = da.key_pos; ga.valid_pos = da.valid_pos; ga.elem_size = da.elem_size;
-            ga.set_keys = sc.s_gset_keys.as<int64_t>(); ga.set_slot = sc.s_gset_slot.as<uint32_t>(); ga.n_found = o_found;
-            ga.k = k; ga.group_size = m; ga.km = km;
-            ga.part_keys = sc.s_part_keys.as<uint64_t>(); ga.part_vals = sc.s_part_vals.as<uint32_t>();
-            ga.part_slot = sc.s_gpart_slot.as<uint32_t>(); ga.part_cnt = sc.s_gpart_cnt.as<uint32_t>();
-            HIP_TRY(launch_partition_grouped_stream(ra, pa, ga, stream));
-            GroupedMergeArgs gma{};
-            gma.part_keys = ga.part_keys; gma.part_vals = ga.part_vals; gma.part_slot = ga.part_slot; gma.part_cnt = ga.part_cnt;
-            gma.nq = b; gma.n_part = n_part; gma.k = k; gma.group_size = m; gma.km = km;
-            gma.ids = s->d_final_ids; gma.row_idx = o_rows; gma.dist = o_dist; gma.group_rows = o_grows; gma.sqrt_out = sqrt_out;
-            HIP_TRY(launch_grouped_merge(gma, stream));
-            s->counters.kernel_launches += 3;
-        } else if (o_grows) {
-            HIP_TRY(launch_group_rows_fill(o_found, b, k, o_grows, stream));
-            s->counters.kernel_launches += 1;
-        }
+        if (int rc = fold.enqueue(s, sc, stream, ra, o, [&](GroupedArgs &ga) {
+                HIP_TRY(launch_partition_grouped_stream(ra, pa, ga, stream));
+                return static_cast<int>(PQV_OK);
+            }))
+            return rc;
     }
     return PQV_OK;
-}
-// the device form behind its checks
-static int topk_partition_grouped_device_impl(const pqv_searcher *s, const pqv_key_partition *part, uint32_t kind, const void *d_a, const void *d_b,
-                                              const pqv_row_keys *gk, const pqv_row_mask *mask, const float *d_queries, uint32_t nq, uint32_t k,
-                                              uint32_t m, int metric, int sqrt_out, uint32_t *d_row_idx, float *d_dist, int64_t *d_group_key,
-                                              uint32_t *d_group_rows, uint32_t *d_n_found, uint64_t *d_n_cand, hipStream_t stream) {
-    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
-    return partition_device_call(s, d_queries, nq, metric, sqrt_out, stream, [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
-        return enqueue_partition_grouped(bs, sc, part, kind, d_a, d_b, gk, bits, q, nq, k, m, mt, so, d_row_idx, d_dist, d_group_key, d_group_rows,
-                                         d_n_found, d_n_cand, stream);
-    });
 }
 extern "C" int pqv_topk_partition_grouped_device(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
                                                  const pqv_row_keys *group_keys, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
@@ -7013,11 +7015,14 @@ extern "C" int pqv_topk_partition_grouped_device(const pqv_searcher *s, const pq
         if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
         if (int rc = use_device(s->device)) return rc;
         hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
-        return topk_partition_grouped_device_impl(s, part, filter->kind, filter->a, filter->b, group_keys, mask, static_cast<const float *>(d_queries),
-                                                  nq, k, group_size, metric, sqrt_out ? 1 : 0, static_cast<uint32_t *>(d_row_idx),
-                                                  static_cast<float *>(d_dist), static_cast<int64_t *>(d_group_key),
-                                                  static_cast<uint32_t *>(d_group_rows), static_cast<uint32_t *>(d_n_found),
-                                                  static_cast<uint64_t *>(d_n_candidates), stream);
+        const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+        const TopkOut out{static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
+                          static_cast<uint64_t *>(d_n_candidates), static_cast<int64_t *>(d_group_key), static_cast<uint32_t *>(d_group_rows)};
+        return partition_device_call(s, static_cast<const float *>(d_queries), nq, metric, sqrt_out ? 1 : 0, stream,
+                                     [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
+                                         return enqueue_partition_grouped(bs, sc, part, filter->kind, filter->a, filter->b, group_keys, bits, q, nq, k,
+                                                                          group_size, mt, so, out, stream);
+                                     });
     });
 }
 extern "C" int pqv_topk_partition_grouped(const pqv_searcher *s, const pqv_key_partition *part, const pqv_key_filter *filter,
@@ -7038,18 +7043,11 @@ extern "C" int pqv_topk_partition_grouped(const pqv_searcher *s, const pqv_key_p
         return topk_partition_host_body(
             s, part->m, partition_request(filter), mask, queries, nq, static_cast<uint32_t>(km), metric, sqrt_out ? 1 : 0,
             std::max<uint64_t>(std::max<uint64_t>(k * 20ull, km * 12), m > 1 ? km * 16 + 4 : 0), 32ull * k + 8 * km + 8 * PQV_KEY_SET_MAX + 16,
-            [&](Scratch &sc) {
-                std::vector<BatchOut> outs = {{&sc.s_rows, km * sizeof(uint32_t), row_idx}, {&sc.s_dist, km * sizeof(float), dist},
-                                              {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_out, sizeof(uint64_t), n_candidates},
-                                              {&sc.s_grp_out, k * sizeof(int64_t), group_key}};
-                if (group_rows) outs.push_back({&sc.s_grows_out, k * sizeof(uint32_t), group_rows});
-                return outs;
-            },
-            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so) {
+            PartitionHostOuts{{row_idx, dist, n_found, n_candidates, group_key, group_rows}, k, km, true},
+            [&](const pqv_searcher *bs, Scratch &sc, const uint64_t *bits, const void *d_a, const void *d_b, uint32_t b, int mt, int so,
+                const TopkOut &out) {
                 return enqueue_partition_grouped(bs, sc, part, filter->kind, d_a, d_b, group_keys, bits, sc.s_queries.as<float>(), b, k, m, mt, so,
-                                                 sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_grp_out.as<int64_t>(),
-                                                 group_rows ? sc.s_grows_out.as<uint32_t>() : nullptr, sc.s_nfound.as<uint32_t>(),
-                                                 sc.s_out.as<uint64_t>(), bs->stream);
+                                                 out, bs->stream);
             });
     });
 }

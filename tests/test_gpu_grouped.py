@@ -421,6 +421,72 @@ def test_second_submission_and_optional_outputs(pqv, oracle):
         d.close()
 
 
+@pytest.fixture(scope="module")
+def small(pqv, oracle):
+    """Case 14's set-up (1500 x 30, 6 lists), for the two tests below."""
+    st = Setup(pqv, oracle, 1500, 30, 6, seed=19)
+    d = Grouped(pqv, st.s, st.n, st.rng.integers(0, st.n // 16, st.n).astype(np.int64), (st.rng.random(st.n) >= 0.3).astype(np.uint8))
+    yield st, d
+    d.close()
+
+
+def _outputs_alone(call, nq, k, m, full, given):
+    """call(r, d, g, c, nf) with fresh garbage blocks, 0 in place of every optional output that `given` does not name; what it writes
+    must equal, byte for byte, the same outputs of the all-outputs call `full` (_device's tuple), and the withheld ones are not missed."""
+    import torch
+    dev = torch.device("cuda", 0)
+    r_t = torch.full((nq, k, m), 5, dtype=torch.int32, device=dev)
+    d_t = torch.full((nq, k, m), -1.0, dtype=torch.float32, device=dev)
+    opt = {"group_key": (torch.full((nq, k), 77, dtype=torch.int64, device=dev), 2),
+           "group_rows": (torch.full((nq, k), 99, dtype=torch.int32, device=dev), 3),
+           "n_found": (torch.full((nq,), 9, dtype=torch.int32, device=dev), 4)}
+    torch.cuda.synchronize()
+    call(r_t.data_ptr(), d_t.data_ptr(), *(opt[name][0].data_ptr() if name in given else 0 for name in ("group_key", "group_rows", "n_found")))
+    torch.cuda.synchronize()
+    what = f"m={m} given={given}"
+    assert r_t.cpu().numpy().tobytes() == full[0].tobytes(), "rows " + what
+    assert d_t.cpu().numpy().tobytes() == full[1].tobytes(), "distances " + what
+    for name in given:
+        t, i = opt[name]
+        assert t.cpu().numpy().tobytes() == full[i].tobytes(), name + " " + what
+
+
+@pytest.mark.parametrize("m", [1, 5])
+def test_each_optional_output_alone(small, m):
+    """The lane stands in for the group keys and n_found that a caller does not take but the fold reads (group keys: pass 2's
+    set; n_found: the set and the rows-per-group fill): each of d_group_key, d_group_rows and d_n_found given alone."""
+    st, d = small
+    nq, k, nprobe = len(st.queries), 13, 3
+    full = d.device(st.queries, k, m, nprobe)
+    import torch
+    q_t = torch.from_numpy(st.queries).to(torch.device("cuda", 0))
+    for name in ("group_key", "group_rows", "n_found"):
+        _outputs_alone(lambda r, dd, g, c, nf: st.s.topk_grouped_device(q_t.data_ptr(), nq, k, m, nprobe, d.keys, r, dd, g, c, nf,
+                                                                        mask=d.shared_mask, sqrt_out=False),
+                       nq, k, m, full, (name,))
+
+
+def test_distinct_device_without_group_key_or_n_found(small):
+    """topk_distinct_device with d_group_key = 0, and again with d_n_found = 0: the other outputs equal the all-outputs call's."""
+    st, d = small
+    nq, k, nprobe = len(st.queries), 13, 3
+    import torch
+    dev = torch.device("cuda", 0)
+    q_t = torch.from_numpy(st.queries).to(dev)
+    r_t = torch.full((nq, k, 1), 5, dtype=torch.int32, device=dev); d_t = torch.full((nq, k, 1), -1.0, dtype=torch.float32, device=dev)
+    g_t = torch.full((nq, k), 77, dtype=torch.int64, device=dev); nf_t = torch.full((nq,), 9, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    st.s.topk_distinct_device(q_t.data_ptr(), nq, k, nprobe, d.keys, r_t.data_ptr(), d_t.data_ptr(), g_t.data_ptr(), nf_t.data_ptr(),
+                              mask=d.shared_mask, sqrt_out=False)
+    torch.cuda.synchronize()
+    full = (r_t.cpu().numpy(), d_t.cpu().numpy(), g_t.cpu().numpy(), None, nf_t.cpu().numpy())
+    assert (full[4] > 0).any() and (full[0] != 5).any()                     # (the call wrote something to compare with)
+    for given in (("n_found",), ("group_key",)):
+        _outputs_alone(lambda r, dd, g, c, nf: st.s.topk_distinct_device(q_t.data_ptr(), nq, k, nprobe, d.keys, r, dd, g, nf,
+                                                                         mask=d.shared_mask, sqrt_out=False),
+                       nq, k, 1, full, given)
+
+
 def test_builders(pqv, tmp_path):
     """Case 15: .distinct_on("doc").group_size(3) on a written Parquet file with an int64 doc column, with and without .where(),
     and on a two-file table; against the yardstick on the same resident searcher."""
