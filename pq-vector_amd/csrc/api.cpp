@@ -186,8 +186,12 @@ struct PinnedBuf {
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
-// phase wall times of this thread's last index build (pqv_index_build_stats)
-thread_local double g_build_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // [8]: assign_wide_kernel seconds of the final assignment (HIP events), [9]: its launches
+// phase wall times of this thread's last index build (pqv_index_build_stats; bench.py's build_record unpacks the slots by position)
+// FORM: an AssignLadder::Tier -- the one that decided the final assignment, the one Lloyd chose.  WIDE: assign_wide_kernel in the
+// final assignment -- seconds between HIP events, launches.
+enum BuildStat { BS_KPP_S, BS_LLOYD_S, BS_ITERS, BS_FINAL_ASSIGN_S, BS_HOST_LISTS_S, BS_FINAL_FORM, BS_LLOYD_FORM, BS_SAMPLE_ROWS,
+                 BS_WIDE_KERNEL_S, BS_WIDE_LAUNCHES, BS_COUNT };
+thread_local double g_build_stats[BS_COUNT] = {};
 
 // PQV_VERBOSE=1: phase timings of the build on stderr
 bool verbose() {
@@ -1514,6 +1518,21 @@ extern "C" void pqv_index_free(pqv_index *i) { delete i; }
 // ---------------------------------------------------------------------------------------
 namespace {
 
+// an on/off switch of the build: on unless the variable is set and starts with '0'
+bool env_on(const char *name) { const char *e = std::getenv(name); return !(e && *e == '0'); }
+
+// *nonfinite = some v[0 .. n) is inf / NaN: one flag round trip on the stream (flag: the caller's 4 bytes of device scratch)
+int any_nonfinite(const float *v, uint64_t n, DevBuf &flag, hipStream_t stream, bool *nonfinite) {
+    uint32_t h = 0;
+    HIP_TRY(flag.ensure(sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), stream));
+    HIP_TRY(pqv::launch_nonfinite_flag(v, n, flag.as<uint32_t>(), stream));
+    HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *nonfinite = h != 0;
+    return PQV_OK;
+}
+
 // Stable counting sort of rows by cluster == the reference's "ascending row ids per
 // cluster" (index.rs:193-206).
 // false if an assignment is out of range (a kernel bug must surface as an error, not as host memory corruption)
@@ -1588,12 +1607,10 @@ bool lists_from_assignment(const uint32_t *cluster_of, uint64_t n, uint32_t k,
 // centroids with a non-finite norm (NaN ordering is the reference's `<`, not the key order).
 // ---------------------------------------------------------------------------------------
 struct ScreenedAssign {
-    uint32_t dim = 0, kc = 0, width = 0, chunk_q = 0, rpb = 0, bpl = 0, max_quads = 0, ccap = 32;
+    static constexpr uint32_t width = 64;          // 64-row quads halve the re-streaming of the centroids
+    static constexpr uint32_t rpb = 1024, seed_rows = 256;
+    uint32_t dim = 0, kc = 0, chunk_q = 0, bpl = 0, max_quads = 0, ccap = 32;
     const float *d_centroids = nullptr;
-    // f16 operands (PQV_ASSIGN_F16=1; dim % 128 == 0, dim <= 1024): the 8-wave kernel with the chunk's rows staged in LDS
-    bool f16 = false;
-    float f16_scale = 1.0f;
-    DevBuf qmax, dmax;
     DevBuf cblk, cnorm, list_off, blk_off, flag;
     DevBuf qnorm, pairs, quads, nq_u32, cand_base, gthr, part_keys, part_vals, cand_keys, cand_vals, cand_cnt, spilled,
         seed_ub, qblk, dist_out, nfound;
@@ -1608,13 +1625,8 @@ struct ScreenedAssign {
     int set_centroids(const float *d_c, uint32_t k, uint32_t d, hipStream_t stream, bool *nonfinite) {
         using namespace pqv;
         dim = d; kc = k; d_centroids = d_c;
-        static const uint32_t wide_env = [] { const char *e = std::getenv("PQV_ASSIGN_WIDTH"); return e ? static_cast<uint32_t>(std::strtoul(e, nullptr, 10)) : 0u; }();
-        width = wide_env == 32 && dim > 128 ? 32 : 64;     // 64-row quads halve the re-streaming of the centroids
-        static const bool f16_env = [] { const char *e = std::getenv("PQV_ASSIGN_F16"); return e && *e == '1'; }();
-        f16 = f16_env && (dim % 128) == 0 && dim <= 1024;
-        if (f16) width = static_cast<uint32_t>(std::min<uint64_t>(128, 147456ull / (static_cast<uint64_t>(dim) * (dim <= 128 ? 6 : 2)) / 32 * 32));
         chunk_q = 65536;          // (131072 / 262144 rows per chunk measured the same build time: the per-chunk launches are not what bounds it)
-        rpb = f16 ? 2048 : 1024; bpl = (kc + rpb - 1) / rpb;
+        bpl = (kc + rpb - 1) / rpb;
         max_quads = (chunk_q / width + 7) / 8 * 8;
         const uint64_t tiles = (static_cast<uint64_t>(kc) + 15) / 16;
         const uint64_t h_off[2] = {0, kc}, h_blk[2] = {0, tiles};
@@ -1625,34 +1637,8 @@ struct ScreenedAssign {
         HIP_TRY(cblk.ensure(tiles * 16 * dim * sizeof(float)));
         HIP_TRY(cnorm.ensure(static_cast<size_t>(kc) * sizeof(float)));
         HIP_TRY(launch_row_norms(d_c, kc, dim, 1, cnorm.as<float>(), stream));
-        if (int rc = check_finite(cnorm.as<float>(), kc, stream, nonfinite)) return rc;
-        if (f16 && !*nonfinite) {
-            // scale: the centroids' maximum lands below 2^14 (rows beyond the f16 range are never skipped by the kernel)
-            uint32_t bits = 0;
-            HIP_TRY(dmax.ensure(sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(dmax.p, 0, sizeof(uint32_t), stream));
-            HIP_TRY(launch_maxabs(d_c, static_cast<uint64_t>(kc) * dim, dmax.as<uint32_t>(), stream));
-            HIP_TRY(hipMemcpyAsync(&bits, dmax.p, sizeof bits, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            float m; std::memcpy(&m, &bits, sizeof m);
-            int e = 0;
-            if (m > 0.0f) (void)std::frexp(m, &e);
-            const int se = m > 0.0f ? 14 - e : 0;
-            if (se < -60 || se > 60) f16 = false; else f16_scale = std::ldexp(1.0f, se);
-        }
-        if (f16 && !*nonfinite)
-            HIP_TRY(launch_block_rows_f16(d_c, list_off.as<uint64_t>(), blk_off.as<uint64_t>(), 1, tiles, dim, f16_scale, cblk.p, stream));
-        else
-            HIP_TRY(launch_block_rows(d_c, list_off.as<uint64_t>(), blk_off.as<uint64_t>(), 1, tiles, dim, cblk.p, stream));
-        return PQV_OK;
-    }
-    int check_finite(const float *v, uint64_t n, hipStream_t stream, bool *nonfinite) {
-        uint32_t h = 0;
-        HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), stream));
-        HIP_TRY(pqv::launch_nonfinite_flag(v, n, flag.as<uint32_t>(), stream));
-        HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        *nonfinite = h != 0;
+        if (int rc = any_nonfinite(cnorm.as<float>(), kc, flag, stream, nonfinite)) return rc;
+        HIP_TRY(launch_block_rows(d_c, list_off.as<uint64_t>(), blk_off.as<uint64_t>(), 1, tiles, dim, cblk.p, stream));
         return PQV_OK;
     }
     // cluster[0 .. n) for rows d_rows[0 .. n); *fallback = true if a row norm is not finite (nothing written)
@@ -1662,10 +1648,9 @@ struct ScreenedAssign {
         HIP_TRY(qnorm.ensure(static_cast<size_t>(n) * sizeof(float)));
         HIP_TRY(launch_row_norms(d_rows, n, dim, 1, qnorm.as<float>(), stream));
         bool bad = false;
-        if (int rc = check_finite(qnorm.as<float>(), n, stream, &bad)) return rc;
+        if (int rc = any_nonfinite(qnorm.as<float>(), n, flag, stream, &bad)) return rc;
         if (bad) { *fallback = true; return PQV_OK; }
-        static const uint32_t seed_env = [] { const char *e = std::getenv("PQV_ASSIGN_SEED"); return e ? static_cast<uint32_t>(std::strtoul(e, nullptr, 10)) : 256u; }();
-        const uint32_t k = 1, slots = (f16 ? 8u : 4u) * bpl, seed_rows = std::max<uint32_t>(64, seed_env / 64 * 64), seed_sw = 4;
+        const uint32_t k = 1, slots = 4 * bpl, seed_sw = 4;
         HIP_TRY(pairs.ensure(static_cast<size_t>(chunk_q) * 4)); HIP_TRY(quads.ensure(static_cast<size_t>(max_quads) * sizeof(uint4)));
         HIP_TRY(nq_u32.ensure(16)); HIP_TRY(cand_base.ensure(static_cast<size_t>(chunk_q) * 8));
         HIP_TRY(gthr.ensure(static_cast<size_t>(chunk_q) * 8));
@@ -1675,12 +1660,8 @@ struct ScreenedAssign {
         HIP_TRY(cand_cnt.ensure(static_cast<size_t>(chunk_q) * 4)); HIP_TRY(spilled.ensure(static_cast<size_t>(chunk_q) * 4));
         HIP_TRY(seed_ub.ensure(static_cast<size_t>(chunk_q) * seed_sw * 16 * 4));
         HIP_TRY(dist_out.ensure(static_cast<size_t>(chunk_q) * 4)); HIP_TRY(nfound.ensure(static_cast<size_t>(chunk_q) * 4));
-        const bool qlds = f16 || static_cast<uint64_t>(width) * dim * sizeof(float) <= 32768;
+        const bool qlds = static_cast<uint64_t>(width) * dim * sizeof(float) <= 32768;
         if (!qlds) HIP_TRY(qblk.ensure(static_cast<size_t>(max_quads) * width * dim * sizeof(float)));
-        if (f16) {
-            HIP_TRY(qmax.ensure(static_cast<size_t>(n) * sizeof(float)));
-            HIP_TRY(launch_row_norms(d_rows, n, dim, 2, qmax.as<float>(), stream));
-        }
         for (uint64_t r0 = 0; r0 < n; r0 += chunk_q) {
             const uint32_t nq = static_cast<uint32_t>(std::min<uint64_t>(chunk_q, n - r0));
             const float *q = d_rows + r0 * dim;
@@ -1702,10 +1683,6 @@ struct ScreenedAssign {
             ta.cand_keys = cand_keys.as<uint64_t>(); ta.cand_vals = cand_vals.as<uint32_t>();
             ta.cand_cnt = cand_cnt.as<uint32_t>(); ta.cand_cap = ccap; ta.spilled = spilled.as<uint32_t>();
             ta.xcd_swizzle = qlds ? 0 : 1;
-            if (f16) {
-                ta.f16 = 1; ta.scale = f16_scale; ta.scale2 = f16_scale * f16_scale; ta.block_waves = 8;
-                ta.query_maxabs = qmax.as<float>() + r0;
-            }
             if (!qlds) {
                 HIP_TRY(launch_pack_queries(q, ta.pairs, ta.quads, ta.n_quads, max_quads, 1, dim, width / 16, qblk.p, stream));
                 ta.q_blk = static_cast<const float4 *>(qblk.p);
@@ -1760,16 +1737,6 @@ struct GemmAssign {
         const long v = e ? std::strtol(e, nullptr, 10) : 128L;
         return v != 0 && (dim % 4) == 0 && kc >= static_cast<uint32_t>(v > 1 ? v : 128) && static_cast<uint64_t>((dim + 31) / 32 * 32) * 2 * 320 < 0x7FFFFFFFull;
     }
-    int finite(const float *v, uint64_t n, hipStream_t stream, bool *bad) {
-        uint32_t h = 0;
-        HIP_TRY(flag.ensure(sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), stream));
-        HIP_TRY(pqv::launch_nonfinite_flag(v, n, flag.as<uint32_t>(), stream));
-        HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        *bad = h != 0;
-        return PQV_OK;
-    }
     int set_centroids(const float *d_c, uint32_t k, uint32_t d, hipStream_t stream, bool *nonfinite) {
         using namespace pqv;
         {
@@ -1782,7 +1749,7 @@ struct GemmAssign {
         HIP_TRY(cn2.ensure(static_cast<size_t>(kc_pad) * sizeof(float)));
         if (!(keep_mu && mu_set)) { HIP_TRY(launch_col_mean(d_c, kc, dim, mu.as<float>(), stream)); mu_set = true; img_rows = nullptr; }
         HIP_TRY(launch_center_normalize_f16(d_c, mu.as<float>(), kc, kc_pad, dim, dim_p, cn2.as<float>(), c16.p, stream));
-        if (!wide) return finite(cn2.as<float>(), kc, stream, nonfinite);
+        if (!wide) return any_nonfinite(cn2.as<float>(), kc, flag, stream, nonfinite);
         // one global scale for the centroid images: 2^8 / max |c - mu| (the norms come back anyway: this is the call's one host check)
         h_cn2.resize(kc);
         HIP_TRY(hipMemcpyAsync(h_cn2.data(), cn2.p, static_cast<size_t>(kc) * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -1819,29 +1786,13 @@ struct GemmAssign {
         return PQV_OK;          // (perm / grp are members: a later call rewrites them only after its own synchronisation on the norms)
     }
     // cluster[0 .. n) for rows d_rows[0 .. n); *fallback = true if a row norm is not finite (the caller re-runs its old path)
-    // h_out (optional): the assignment is also copied to this host array, chunk by chunk on a second stream, each copy behind
-    // the NEXT chunk's kernels (a pageable destination blocks the calling thread, not the GPU: the copies hide behind the compute)
-    int run(const float *d_rows, uint64_t n, uint32_t *d_cluster, hipStream_t stream, bool *fallback, uint32_t *h_out = nullptr) {
+    // (Measured and dropped: the assignment copied to the host chunk by chunk on a second stream behind the next chunk's kernels -- a
+    //  device-to-pageable copy there stalls the compute stream's queue, 53 ms for the loop against 34 ms of kernels on C3.)
+    int run(const float *d_rows, uint64_t n, uint32_t *d_cluster, hipStream_t stream, bool *fallback) {
         using namespace pqv;
         *fallback = false;
         const double t_run0 = now_s();
         const uint64_t ch = std::min<uint64_t>(chunk, std::max<uint64_t>(1, n));
-        struct CopyLane {
-            hipStream_t s = nullptr; hipEvent_t ev[2] = {nullptr, nullptr};
-            ~CopyLane() { if (s) (void)hipStreamDestroy(s); for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-        } cl;
-        if (h_out) {
-            HIP_TRY(hipStreamCreateWithFlags(&cl.s, hipStreamNonBlocking));
-            for (auto &e : cl.ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        uint64_t pend_r0 = 0, pend_m = 0; int pend_ev = -1, n_chunk = 0;
-        auto flush_copy = [&]() -> int {
-            if (pend_ev < 0) return PQV_OK;
-            HIP_TRY(hipStreamWaitEvent(cl.s, cl.ev[pend_ev], 0));
-            HIP_TRY(hipMemcpyAsync(h_out + pend_r0, d_cluster + pend_r0, pend_m * sizeof(uint32_t), hipMemcpyDeviceToHost, cl.s));
-            pend_ev = -1;
-            return PQV_OK;
-        };
         HIP_TRY(x16.ensure(ch * dim_p * sizeof(uint16_t)));
         HIP_TRY(xn2.ensure(ch * sizeof(float)));
         HIP_TRY(cand.ensure(ch * cap * sizeof(uint32_t)));
@@ -1894,12 +1845,6 @@ struct GemmAssign {
             HIP_TRY(launch_assign_f16(a, stream));
             HIP_TRY(launch_assign_rescore(rows, d_centroids, m, dim, kc, cand.as<uint32_t>(), cnt.as<uint32_t>(), cap, d_cluster + r0, stream));
             }
-            if (h_out) {
-                const int evi = n_chunk++ & 1;
-                if (int rc = flush_copy()) return rc;                   // the previous chunk: its kernels are done or running, this chunk's are queued
-                HIP_TRY(hipEventRecord(cl.ev[evi], stream));
-                pend_r0 = r0; pend_m = m; pend_ev = evi;
-            }
             if (verbose() && r0 == 0 && n >= 65536) {      // candidates the screen left per row (first chunk)
                 std::vector<uint32_t> hc(m);
                 HIP_TRY(hipMemcpyAsync(hc.data(), cnt.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -1910,12 +1855,11 @@ struct GemmAssign {
                              static_cast<double>(sum) / static_cast<double>(m), mx, (unsigned long long)over, cap, kc);
             }
         }
-        if (h_out) { if (int rc = flush_copy()) return rc; HIP_TRY(hipStreamSynchronize(cl.s)); }
         const double t_run1 = now_s();
         uint32_t h = 0;
         HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
-        if (verbose() && n >= (1u << 20)) std::fprintf(stderr, "[pqv] f16 assignment: %llu rows enqueued%s in %.1f ms\n", (unsigned long long)n,
-                                                       h_out ? " and downloaded" : "", (t_run1 - t_run0) * 1e3);
+        if (verbose() && n >= (1u << 20)) std::fprintf(stderr, "[pqv] f16 assignment: %llu rows enqueued in %.1f ms\n", (unsigned long long)n,
+                                                       (t_run1 - t_run0) * 1e3);
         if (wide && verbose()) {
             unsigned long long hs[2] = {0, 0};
             HIP_TRY(hipMemcpyAsync(hs, rstats.p, sizeof hs, hipMemcpyDeviceToHost, stream));
@@ -1932,7 +1876,7 @@ struct GemmAssign {
                 float ms = 0.0f;
                 if (hipEventElapsedTime(&ms, kernel_ev[i], kernel_ev[i + 1]) == hipSuccess) ms_sum += ms;
             }
-            g_build_stats[8] = ms_sum * 1e-3; g_build_stats[9] = static_cast<double>(kernel_ev.size() / 2);
+            g_build_stats[BS_WIDE_KERNEL_S] = ms_sum * 1e-3; g_build_stats[BS_WIDE_LAUNCHES] = static_cast<double>(kernel_ev.size() / 2);
             for (hipEvent_t e : kernel_ev) (void)hipEventDestroy(e);
             kernel_ev.clear();
         }
@@ -2054,7 +1998,7 @@ struct DeviceLists {
     DevBuf cnt, tot, bad;
     uint32_t rpb = 4096;
     static bool applicable(uint64_t n, uint32_t k) {
-        static const bool on = [] { const char *e = std::getenv("PQV_DEVICE_LISTS"); return !(e && e[0] == '0'); }();
+        static const bool on = env_on("PQV_DEVICE_LISTS");
         return on && n > 0 && n <= 0xFFFFFFFFull && k > 0 && k <= 4096;
     }
     int prepare(uint64_t n, uint32_t k) {
@@ -2075,220 +2019,320 @@ struct DeviceLists {
     }
 };
 
-// d_data [n, dim] resident; writes d_centroids [k, dim] (device) and optionally the final
-// assignment (host).
-int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iters,
-                  uint64_t seed, uint32_t workers, hipStream_t stream, float *d_centroids,
-                  std::vector<uint32_t> *assign_out, uint32_t *iters_run) {
-    using namespace pqv;
-    if (workers == 0) workers = host_workers();
-    StdRng rng = StdRng::seed_from_u64(seed);                                          // :327
-    HIP_TRY(hipMemsetAsync(d_centroids, 0, static_cast<size_t>(k) * dim * sizeof(float), stream)); // :330
+// The assignment ladder (index.rs:395-430 in Lloyd; :189-206 + :244-257 in assign_rows): cluster[r] = the nearest centroid of row r
+// by the f16 contraction (GemmAssign), else by the f32 MFMA screen (ScreenedAssign), else by the exact kernel.  A tier steps down
+// where a centroid norm (its set_centroids) or a row norm (its run) is not finite: NaN ordering is the reference's `<`, which only
+// the exact kernel keeps.  The caller chooses the tiers to try once; Lloyd keeps one ladder over its iterations, so the
+// contraction's centring vector and row images carry over (GemmAssign::keep_mu).
+struct AssignLadder {
+    enum Tier { EXACT = 0, SCREEN = 1, GEMM = 2 };         // (the values of BS_FINAL_FORM / BS_LLOYD_FORM)
+    GemmAssign gemm;
+    ScreenedAssign screen;
+    bool try_gemm = false, try_screen = false;
+    // one call on a local ladder (assign_rows): the stream is drained behind each tier, before the next one starts and before the
+    // scope exit releases the tiers' buffers; t0 is the clock origin of that call's PQV_VERBOSE lines
+    bool one_shot = false;
+    double t0 = 0.0;
+    // d_cluster[i] = nearest centroid of row i of d_rows [n, dim], i in [0, n); *decided = the tier that wrote it.  With d_prev and
+    // d_changed (Lloyd, :417-427) *d_changed counts the rows whose cluster differs from d_prev's: the exact kernel counts as it
+    // assigns, a tier above it is followed by count_changed_kernel.
+    int run(const float *d_rows, uint64_t n, const float *d_centroids, uint32_t k, uint32_t dim, uint32_t *d_cluster, hipStream_t stream,
+            Tier *decided, const uint32_t *d_prev = nullptr, unsigned long long *d_changed = nullptr) {
+        using namespace pqv;
+        *decided = EXACT;
+        auto attempt = [&](auto &tier, Tier t, bool trace) -> int {
+            bool bad_c = false, bad_r = false;
+            if (int rc = tier.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
+            if (trace) std::fprintf(stderr, "[pqv] final assignment: centroids set at %.1f ms\n", (now_s() - t0) * 1e3);
+            if (!bad_c) { if (int rc = tier.run(d_rows, n, d_cluster, stream, &bad_r)) return rc; }
+            if (one_shot) HIP_TRY(hipStreamSynchronize(stream));
+            if (trace) std::fprintf(stderr, "[pqv] final assignment: f16 path done at %.1f ms\n", (now_s() - t0) * 1e3);
+            if (!bad_c && !bad_r) *decided = t;
+            return PQV_OK;
+        };
+        if (try_gemm) { if (int rc = attempt(gemm, GEMM, one_shot && verbose())) return rc; }
+        if (*decided == EXACT && try_screen) { if (int rc = attempt(screen, SCREEN, false)) return rc; }
+        if (*decided == EXACT) HIP_TRY(launch_assign(d_rows, n, dim, d_centroids, k, d_cluster, d_prev, d_changed, nullptr, stream));
+        else if (d_changed) HIP_TRY(launch_count_changed(d_cluster, d_prev, n, d_changed, stream));
+        return PQV_OK;
+    }
+};
 
-    // k-means++ subset (:332-338)
-    uint64_t init_n = std::max<uint64_t>(std::min<uint64_t>(n, 50000), k);
-    DevBuf d_init_own, d_idx;
-    const float *d_init = d_data;
-    std::vector<uint64_t> init_indices;
-    if (init_n != n) {
-        init_indices = index_sample(rng, n, init_n);
+// k-means++ (index.rs:332-390) in stages, each owning its buffers; kmeans_device below strings them together.
+
+// The subset the rounds run over (:332-338): every row up to 50 000 of them, else an index_sample gathered into a buffer of its own.
+struct KppSubset {
+    uint64_t init_n = 0;
+    uint32_t dim = 0;
+    const float *d_init = nullptr;
+    std::vector<uint64_t> indices;
+    DevBuf d_own, d_idx;
+    int draw(pqv::StdRng &rng, const float *d_data, uint64_t n, uint32_t row_dim, uint32_t k, hipStream_t stream) {
+        init_n = std::max<uint64_t>(std::min<uint64_t>(n, 50000), k); dim = row_dim; d_init = d_data;
+        if (init_n == n) return PQV_OK;
+        indices = index_sample(rng, n, init_n);
         HIP_TRY(d_idx.alloc(init_n * sizeof(uint64_t)));
-        HIP_TRY(d_init_own.alloc(init_n * dim * sizeof(float)));
-        HIP_TRY(hipMemcpyAsync(d_idx.p, init_indices.data(), init_n * sizeof(uint64_t),
-                               hipMemcpyHostToDevice, stream));
-        HIP_TRY(launch_gather_rows(d_data, nullptr, d_idx.as<uint64_t>(), init_n, dim,
-                                   d_init_own.as<float>(), stream));
-        d_init = d_init_own.as<float>();
+        HIP_TRY(d_own.alloc(init_n * dim * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(d_idx.p, indices.data(), init_n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(pqv::launch_gather_rows(d_data, nullptr, d_idx.as<uint64_t>(), init_n, dim, d_own.as<float>(), stream));
+        d_init = d_own.as<float>();
+        return PQV_OK;
     }
-    // Centroid i is row picks[i] of the subset (~0: none, the centroid keeps its zero fill).  A round measures against that
-    // row where it lies and the rows are copied into the table once, after the last round, so that a round is ONE command
-    // on the stream: no device-to-device copy before its kernel, no download after it (the kernel mirrors the minima into
-    // pinned host memory): 83 -> 64 us per round on C3's 50 000 x 768 subset (kernel 26 us, the host scans about 20).
-    std::vector<uint64_t> picks(k, ~0ull);
-    picks[0] = rng.range_usize(0, init_n);                                             // :340-342
-    auto centroid_row = [&](uint32_t j) -> const float * {
-        return picks[j] != ~0ull ? d_init + picks[j] * dim : d_centroids + static_cast<uint64_t>(j) * dim;
-    };
+    const float *row(uint64_t pick) const { return d_init + pick * dim; }
+    void release() { d_own.release(); d_idx.release(); }
+};
 
-    // min_distances (:344-352), then one streaming pass per round (:354-369)
+// min_distances (:344-352): the minima on the device, mirrored by the update kernels into pinned host memory where the host sums
+// and walks them, and the worker chunking of their sum (:259-265, :305-306).
+// With many chunks (a 256-core host: 256 chunks of 196 minima) the independent chunk chains are added as vector lanes: the kernels
+// keep a second mirror in chunk-transposed order [position in chunk][chunk] (padding stays +0.0: x + 0.0 == x for the non-negative
+// sums), and step t adds row t of it to the running sums -- every chain still in its own order.
+struct KppMinima {
+    uint64_t n = 0, chunk = 0, n_chunks = 0, wpad = 0;
+    bool use_t = false;
+    uint32_t mirror_chunk = 0, mirror_stride = 0;      // what the kernels' arguments of those names take (0 without the transposed mirror)
     DevBuf d_min;
-    HIP_TRY(d_min.alloc(init_n * sizeof(float)));
-    {
-        std::vector<float> inf(init_n, INFINITY);
-        HIP_TRY(hipMemcpyAsync(d_min.p, inf.data(), init_n * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    PinnedBuf h_min;
-    HIP_TRY(h_min.ensure(init_n * sizeof(float)));
-    for (uint64_t t = 0; t < init_n; ++t) h_min.as<float>()[t] = INFINITY;     // the mirror starts equal to d_min
-    StreamArgs sa{};
-    sa.mat = d_init; sa.row_of = nullptr; sa.list_off = nullptr; sa.probe = nullptr; sa.cand_base = nullptr;
-    sa.single_begin = 0; sa.single_end = init_n;
-    sa.nq = 1; sa.nprobe = 1; sa.dim = dim; sa.k = 1;
-    sa.rows_per_block = 256;
-    sa.blocks_per_list = static_cast<uint32_t>((init_n + 255) / 256);
-    sa.max_pos = ~0ull; sa.metric = PQV_L2SQ_REF4;
-    sa.out_f32 = d_min.as<float>();
-    sa.mirror_f32 = h_min.as<float>();
-
-    // chunking of the partial sums (:259-265,:305-306)
-    const uint64_t w = std::max<uint64_t>(1, std::min<uint64_t>(workers, init_n));
-    const uint64_t chunk = (init_n + w - 1) / w;
-    // With many chunks (a 256-core host: 256 chunks of 196 minima) the w independent chunk chains are added as vector lanes:
-    // the kernels keep a second mirror in chunk-transposed order [position in chunk][chunk] (padding stays +0.0: x + 0.0 == x
-    // for the non-negative sums), and step t adds row t of it to the w running sums -- every chain still in its own order.
-    const uint64_t n_chunks = (init_n + chunk - 1) / chunk;
-    const uint64_t wpad = (n_chunks + 15) / 16 * 16;
-    const bool use_t = n_chunks >= 16 && chunk * wpad <= (64ull << 20);
-    PinnedBuf h_min_t;
+    PinnedBuf h_min, h_min_t;
     std::vector<float> chain_acc;
-    if (use_t) {
-        HIP_TRY(h_min_t.ensure(chunk * wpad * sizeof(float)));
-        float *mt = h_min_t.as<float>();
-        for (uint64_t t = 0; t < chunk * wpad; ++t) mt[t] = 0.0f;
-        for (uint64_t pos = 0; pos < init_n; ++pos) mt[(pos % chunk) * wpad + pos / chunk] = INFINITY;
-        sa.mirror_t = mt; sa.mirror_chunk = static_cast<uint32_t>(chunk); sa.mirror_stride = static_cast<uint32_t>(wpad);
-        chain_acc.resize(wpad);
-    }
 
-    const double t_pp0 = now_s();
-    // Round 4: from the second measured centroid on, a round first screens the rows with int8 images (minupd_screen_kernel): a row
-    // whose distance to the new centroid provably is not below its current minimum is not evaluated (after a dozen rounds: most).
-    // Rows of a multiple of 64 dims, finite data; PQV_KPP_SCREEN=0 keeps the plain streaming pass (A/B, tests).
-    DevBuf d_kimg, d_kn2i, d_kres, d_kaux, d_kmm;
-    MinUpdScreenArgs ms{};
-    bool kpp_screen = false;
-    {
-        const char *e = std::getenv("PQV_KPP_SCREEN");
-        if (!(e && *e == '0') && (dim % 64) == 0 && dim >= 128 && dim <= 8192 && init_n >= 1024 && k > 8) {
-            const uint64_t n_tiles = (init_n + 15) / 16;
-            // one "list" holding the whole subset: {list_off[2], blk_off[2]} u64, then centre[dim], half, scale, radius floats
-            HIP_TRY(d_kaux.alloc(4 * sizeof(uint64_t) + (static_cast<size_t>(dim) + 3) * sizeof(float)));
-            const uint64_t h_off[4] = {0, init_n, 0, n_tiles};
-            HIP_TRY(hipMemcpyAsync(d_kaux.p, h_off, sizeof h_off, hipMemcpyHostToDevice, stream));
-            const uint64_t *d_loff = d_kaux.as<uint64_t>(), *d_boff = d_loff + 2;
-            float *d_ctr = reinterpret_cast<float *>(d_kaux.as<uint64_t>() + 4), *d_half = d_ctr + dim, *d_scale = d_half + 1, *d_rad = d_scale + 1;
-            HIP_TRY(d_kmm.alloc(2 * static_cast<size_t>(dim) * sizeof(uint32_t)));
-            uint32_t *kmin = d_kmm.as<uint32_t>(), *kmax = kmin + dim;
-            HIP_TRY(hipMemsetAsync(kmin, 0xFF, static_cast<size_t>(dim) * sizeof(uint32_t), stream));
-            HIP_TRY(hipMemsetAsync(kmax, 0, static_cast<size_t>(dim) * sizeof(uint32_t), stream));
-            HIP_TRY(d_kimg.alloc(n_tiles * 16 * dim));
-            HIP_TRY(d_kn2i.alloc(init_n * sizeof(int)));
-            HIP_TRY(d_kres.alloc(init_n * sizeof(float)));
-            HIP_TRY(launch_list_minmax(d_init, d_loff, 1, init_n, dim, kmin, kmax, stream));
-            HIP_TRY(launch_list_center(kmin, kmax, 1, dim, d_loff, d_ctr, d_half, d_scale, d_rad, stream));
-            HIP_TRY(launch_block_rows_i8(d_init, d_loff, d_boff, 1, n_tiles, dim, d_ctr, d_scale, d_half, d_rad, d_kimg.p, d_kn2i.as<int>(),
-                                         d_kres.as<float>(), stream));
-            float h_hs[2] = {0.0f, 0.0f};       // {half range, scale}
-            HIP_TRY(hipMemcpyAsync(h_hs, d_half, sizeof h_hs, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            // (a non-finite value anywhere in the subset shows in the half range; a degenerate scale -- all rows equal -- has nothing to screen)
-            if (h_hs[0] > 0.0f && h_hs[0] < 1.0e30f && h_hs[1] > 1.0e-30f && h_hs[1] < 1.0e15f) {
-                ms.rows = d_init; ms.img = static_cast<const float4 *>(d_kimg.p); ms.n2i = d_kn2i.as<int>(); ms.res = d_kres.as<float>();
-                ms.n = init_n; ms.dim = dim; ms.inv_s = 1.0f / h_hs[1];
-                ms.cm = static_cast<float>(dim + 16) * 2.384185791015625e-07f;
-                ms.min_d = d_min.as<float>(); ms.mirror = h_min.as<float>();
-                ms.mirror_t = sa.mirror_t; ms.mirror_chunk = sa.mirror_chunk; ms.mirror_stride = sa.mirror_stride;
-                kpp_screen = true;
-            }
-        }
-    }
-    // (Measured and dropped: the screened rounds as ONE resident kernel fed through pinned memory -- commands polled with relaxed
-    //  system-scope loads, minima mirrored with system-scope stores, a ticket per block -- 45 us a round against 24 for a launch per
-    //  round: the PCIe round trips of the hand-shake cost more than a kernel launch and its completion.  Likewise a completion flag
-    //  written by the last block of a per-round launch: the per-block system-scope release costs the kernel 20 us.)
-    // Round 6: the rounds enqueued ahead with the pick on the device (kernels_kpp.hip: the reference's sequential f32 sums evaluated
-    // exactly by composing the additions' integer images) -- no host round trip per centroid.  The draws of :373 are taken from a copy
-    // of the generator (one per round while every total is positive); a round the device cannot decide the reference's way stops the
-    // chain and the host walk below takes over from that round.  PQV_KPP_DEVICE=0 keeps the host walk for every round (A/B, tests).
-    uint32_t i_start = 1;
-    bool resume_after_update = false;
-    sa.queries = centroid_row(0);  // distances to centroid 0
-    bool kpp_dev = false;
-    {
-        const char *e = std::getenv("PQV_KPP_DEVICE");
-        kpp_dev = !(e && *e == '0') && kpp_screen && k >= 3 && init_n <= 57344 && n_chunks <= 1024 && chunk <= 0xFFFFFFFFull;
-    }
-    if (kpp_dev) {
-        const double t_d0 = now_s();
-        // picks [k] | chunk sums [n_chunks] | block sums [64] | quarter-run pairs [4096] | block flags [64] | head [72] (u64 each), draws [k] f32, state [4] u32
-        const size_t n64 = static_cast<size_t>(k) + n_chunks + 64 + 4096 + 64 + 72;
-        const size_t bytes = n64 * 8 + (static_cast<size_t>(k) + 4) * 4;
-        DevBuf d_kpp;
-        HIP_TRY(d_kpp.alloc(bytes));
-        HIP_TRY(hipMemsetAsync(d_kpp.p, 0, bytes, stream));
-        unsigned long long *d_picks = d_kpp.as<unsigned long long>();
-        float *d_u = reinterpret_cast<float *>(d_picks + n64);
-        uint32_t *d_state = reinterpret_cast<uint32_t *>(d_u + k);
-        StdRng ahead = rng;
-        std::vector<float> draws(k, 0.0f);
-        for (uint32_t i = 1; i < k; ++i) draws[i] = ahead.unit_f32();
-        const unsigned long long pick0 = picks[0];
-        HIP_TRY(hipMemcpyAsync(d_picks, &pick0, sizeof pick0, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_u, draws.data(), static_cast<size_t>(k) * sizeof(float), hipMemcpyHostToDevice, stream));
-        StreamArgs sd = sa;
-        sd.mirror_f32 = nullptr; sd.mirror_t = nullptr;
-        HIP_TRY(launch_stream(sd, STREAM_MINUPD, stream));
-        MinUpdScreenArgs md_args = ms;
-        md_args.mirror = nullptr; md_args.mirror_t = nullptr; md_args.stop = d_state;
-        KppPickArgs pa{};
-        pa.md = d_min.as<float>(); pa.n = static_cast<uint32_t>(init_n);
-        pa.chunk = static_cast<uint32_t>(chunk); pa.n_chunks = static_cast<uint32_t>(n_chunks);
-        pa.chunk_sum = d_picks + k; pa.blk_sum = pa.chunk_sum + n_chunks; pa.run_sum = pa.blk_sum + 64; pa.blk_done = pa.run_sum + 4096; pa.head = pa.blk_done + 64;
-        pa.u = d_u; pa.picks = d_picks; pa.state = d_state;
-        for (uint32_t i = 1; i < k; ++i) {
-            if (i > 1) {                                   // (round 1 would re-measure centroid 0)
-                md_args.pick_dev = d_picks + (i - 1);
-                HIP_TRY(launch_minupd_screen(md_args, stream));
-            }
-            pa.round = i;
-            HIP_TRY(launch_kpp_pick(pa, stream));
-        }
-        uint32_t h_state[4] = {0, 0, 0, 0};
-        std::vector<unsigned long long> h_picks(k, ~0ull);
-        HIP_TRY(hipMemcpyAsync(h_picks.data(), d_picks, static_cast<size_t>(k) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(h_state, d_state, sizeof h_state, hipMemcpyDeviceToHost, stream));
+    int init(uint64_t init_n, uint32_t workers, hipStream_t stream) {
+        n = init_n;
+        const uint64_t w = std::max<uint64_t>(1, std::min<uint64_t>(workers, n));
+        chunk = (n + w - 1) / w;
+        n_chunks = (n + chunk - 1) / chunk;
+        wpad = (n_chunks + 15) / 16 * 16;
+        use_t = n_chunks >= 16 && chunk * wpad <= (64ull << 20);
+        HIP_TRY(d_min.alloc(n * sizeof(float)));
+        std::vector<float> inf(n, INFINITY);
+        HIP_TRY(hipMemcpyAsync(d_min.p, inf.data(), n * sizeof(float), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        const uint32_t decided = h_state[0] ? std::min<uint32_t>(std::max<uint32_t>(h_state[1], 1), k) : k;   // rounds 1 .. decided - 1
-        for (uint32_t i = 1; i < decided; ++i) picks[i] = h_picks[i];
-        for (uint32_t i = 1; i < decided; ++i) (void)rng.unit_f32();     // the generator follows the rounds that were decided
-        if (verbose()) std::fprintf(stderr, "[pqv] k-means++ on the device: rounds 1..%u of %u in %.1f ms%s\n", decided - 1, k - 1,
-                                    (now_s() - t_d0) * 1e3, h_state[0] ? " (the host walk takes over)" : "");
-        if (decided < k) {
-            if (verbose()) std::fprintf(stderr, "[pqv] k-means++: round %u back to the host (reason %u)\n", decided, h_state[2]);
-            // the host walk needs its mirrors of the minima as the device left them (round `decided`'s update has run)
-            HIP_TRY(hipMemcpyAsync(h_min.as<float>(), d_min.p, init_n * sizeof(float), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (use_t) {
-                float *mt = h_min_t.as<float>();
-                const float *hm = h_min.as<float>();
-                for (uint64_t pos = 0; pos < init_n; ++pos) mt[(pos % chunk) * wpad + pos / chunk] = hm[pos];
-            }
-            resume_after_update = decided > 1;
+        HIP_TRY(h_min.ensure(n * sizeof(float)));
+        if (use_t) {
+            HIP_TRY(h_min_t.ensure(chunk * wpad * sizeof(float)));
+            float *mt = h_min_t.as<float>();
+            for (uint64_t t = 0; t < chunk * wpad; ++t) mt[t] = 0.0f;
+            mirror_chunk = static_cast<uint32_t>(chunk); mirror_stride = static_cast<uint32_t>(wpad);
+            chain_acc.resize(wpad);
         }
-        i_start = decided;
-    } else {
-        HIP_TRY(launch_stream(sa, STREAM_MINUPD, stream));
+        fill_mirrors(inf.data());                      // the mirrors start equal to d_min
+        return PQV_OK;
     }
+    float *mirror() const { return h_min.as<float>(); }
+    float *mirror_t() const { return use_t ? h_min_t.as<float>() : nullptr; }
+    // both mirrors from the minima in slot order (md may be the plain mirror itself)
+    void fill_mirrors(const float *md) {
+        if (md != mirror()) std::memcpy(mirror(), md, n * sizeof(float));
+        if (!use_t) return;
+        float *mt = h_min_t.as<float>();
+        for (uint64_t pos = 0; pos < n; ++pos) mt[(pos % chunk) * wpad + pos / chunk] = md[pos];
+    }
+    // the mirrors as the device holds the minima now (behind updates that ran without them)
+    int reload(hipStream_t stream) {
+        HIP_TRY(hipMemcpyAsync(h_min.p, d_min.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        fill_mirrors(mirror());
+        return PQV_OK;
+    }
+    // total = sum over worker chunks of the chunk's sequential f32 sum (:356-370).  Each chunk's sum is its own sequential f32
+    // chain and the chains are independent of each other: they run side by side -- one per vector lane over the transposed mirror,
+    // else eight full chunks at a time, else one by one; the chunk sums still join `total` in ascending chunk order.
+    float total() {
+        const float *md = mirror();
+        float total = 0.0f;
+        uint64_t s = 0;
+        if (use_t) {
+            float *acc = chain_acc.data();
+            for (uint64_t c = 0; c < wpad; ++c) acc[c] = 0.0f;
+            chain_sums(h_min_t.as<float>(), chunk, wpad, acc);
+            for (uint64_t c = 0; c < n_chunks; ++c) total = total + acc[c];
+            s = n;
+        } else if (chunk < n) {
+            for (; s + 8 * chunk <= n; s += 8 * chunk) {
+                const float *p = md + s;
+                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f, a6 = 0.0f, a7 = 0.0f;
+                for (uint64_t t = 0; t < chunk; ++t) {
+                    a0 = a0 + p[t];             a1 = a1 + p[chunk + t];     a2 = a2 + p[2 * chunk + t]; a3 = a3 + p[3 * chunk + t];
+                    a4 = a4 + p[4 * chunk + t]; a5 = a5 + p[5 * chunk + t]; a6 = a6 + p[6 * chunk + t]; a7 = a7 + p[7 * chunk + t];
+                }
+                total = total + a0; total = total + a1; total = total + a2; total = total + a3;
+                total = total + a4; total = total + a5; total = total + a6; total = total + a7;
+            }
+        }
+        for (; s < n; s += chunk) {
+            const uint64_t e = std::min(n, s + chunk);
+            float local = 0.0f;
+            for (uint64_t t = s; t < e; ++t) local = local + md[t];
+            total = total + local;
+        }
+        return total;
+    }
+};
+
+// The plain update of the minima (stream_kernel, STREAM_MINUPD): the subset's distances to the row `queries` (set per launch) are
+// folded into d_min and both mirrors.
+pqv::StreamArgs kpp_minupd_pass(const KppSubset &subset, const KppMinima &minima) {
+    pqv::StreamArgs sa{};
+    sa.mat = subset.d_init; sa.row_of = nullptr; sa.list_off = nullptr; sa.probe = nullptr; sa.cand_base = nullptr;
+    sa.single_begin = 0; sa.single_end = subset.init_n;
+    sa.nq = 1; sa.nprobe = 1; sa.dim = subset.dim; sa.k = 1;
+    sa.rows_per_block = 256;
+    sa.blocks_per_list = static_cast<uint32_t>((subset.init_n + 255) / 256);
+    sa.max_pos = ~0ull; sa.metric = PQV_L2SQ_REF4;
+    sa.out_f32 = minima.d_min.as<float>();
+    sa.mirror_f32 = minima.mirror();
+    sa.mirror_t = minima.mirror_t(); sa.mirror_chunk = minima.mirror_chunk; sa.mirror_stride = minima.mirror_stride;
+    return sa;
+}
+
+// Round 4: from the second measured centroid on, a round first screens the rows with int8 images (minupd_screen_kernel): a row
+// whose distance to the new centroid provably is not below its current minimum is not evaluated (after a dozen rounds: most).
+// Rows of a multiple of 64 dims, finite data; PQV_KPP_SCREEN=0 keeps the plain streaming pass (A/B, tests).
+struct KppRoundScreen {
+    DevBuf d_kimg, d_kn2i, d_kres, d_kaux, d_kmm;
+    pqv::MinUpdScreenArgs ms{};
+    bool applies = false;
+    // images the subset; applies = the screen serves these rows, ms is filled
+    int init(const KppSubset &subset, const KppMinima &minima, uint32_t k, hipStream_t stream) {
+        using namespace pqv;
+        const uint64_t init_n = subset.init_n; const uint32_t dim = subset.dim; const float *d_init = subset.d_init;
+        if (!(env_on("PQV_KPP_SCREEN") && (dim % 64) == 0 && dim >= 128 && dim <= 8192 && init_n >= 1024 && k > 8)) return PQV_OK;
+        const uint64_t n_tiles = (init_n + 15) / 16;
+        // one "list" holding the whole subset: {list_off[2], blk_off[2]} u64, then centre[dim], half, scale, radius floats
+        HIP_TRY(d_kaux.alloc(4 * sizeof(uint64_t) + (static_cast<size_t>(dim) + 3) * sizeof(float)));
+        const uint64_t h_off[4] = {0, init_n, 0, n_tiles};
+        HIP_TRY(hipMemcpyAsync(d_kaux.p, h_off, sizeof h_off, hipMemcpyHostToDevice, stream));
+        const uint64_t *d_loff = d_kaux.as<uint64_t>(), *d_boff = d_loff + 2;
+        float *d_ctr = reinterpret_cast<float *>(d_kaux.as<uint64_t>() + 4), *d_half = d_ctr + dim, *d_scale = d_half + 1, *d_rad = d_scale + 1;
+        HIP_TRY(d_kmm.alloc(2 * static_cast<size_t>(dim) * sizeof(uint32_t)));
+        uint32_t *kmin = d_kmm.as<uint32_t>(), *kmax = kmin + dim;
+        HIP_TRY(hipMemsetAsync(kmin, 0xFF, static_cast<size_t>(dim) * sizeof(uint32_t), stream));
+        HIP_TRY(hipMemsetAsync(kmax, 0, static_cast<size_t>(dim) * sizeof(uint32_t), stream));
+        HIP_TRY(d_kimg.alloc(n_tiles * 16 * dim));
+        HIP_TRY(d_kn2i.alloc(init_n * sizeof(int)));
+        HIP_TRY(d_kres.alloc(init_n * sizeof(float)));
+        HIP_TRY(launch_list_minmax(d_init, d_loff, 1, init_n, dim, kmin, kmax, stream));
+        HIP_TRY(launch_list_center(kmin, kmax, 1, dim, d_loff, d_ctr, d_half, d_scale, d_rad, stream));
+        HIP_TRY(launch_block_rows_i8(d_init, d_loff, d_boff, 1, n_tiles, dim, d_ctr, d_scale, d_half, d_rad, d_kimg.p, d_kn2i.as<int>(),
+                                     d_kres.as<float>(), stream));
+        float h_hs[2] = {0.0f, 0.0f};       // {half range, scale}
+        HIP_TRY(hipMemcpyAsync(h_hs, d_half, sizeof h_hs, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        // (a non-finite value anywhere in the subset shows in the half range; a degenerate scale -- all rows equal -- has nothing to screen)
+        if (!(h_hs[0] > 0.0f && h_hs[0] < 1.0e30f && h_hs[1] > 1.0e-30f && h_hs[1] < 1.0e15f)) return PQV_OK;
+        ms.rows = d_init; ms.img = static_cast<const float4 *>(d_kimg.p); ms.n2i = d_kn2i.as<int>(); ms.res = d_kres.as<float>();
+        ms.n = init_n; ms.dim = dim; ms.inv_s = 1.0f / h_hs[1];
+        ms.cm = static_cast<float>(dim + 16) * 2.384185791015625e-07f;
+        ms.min_d = minima.d_min.as<float>(); ms.mirror = minima.mirror();
+        ms.mirror_t = minima.mirror_t(); ms.mirror_chunk = minima.mirror_chunk; ms.mirror_stride = minima.mirror_stride;
+        applies = true;
+        return PQV_OK;
+    }
+    void release() { d_kimg.release(); d_kn2i.release(); d_kres.release(); d_kaux.release(); d_kmm.release(); }
+};
+
+// The scratch of kpp_pick_kernel, one zeroed block: picks [n_picks] | chunk sums [n_chunks] | block sums [64] | quarter-run pairs
+// [4096] | block flags [64] | head [72] (u64 each), then draws [n_draws] f32, state [4] u32 and, where asked for, 16-byte aligned
+// minima [n_minima] f32 (pqv_kpp_pick's copy of them: aligned as the build's d_min is).
+struct KppScratch {
+    DevBuf buf;
+    float *draws = nullptr, *minima = nullptr;
+    pqv::KppPickArgs pa{};         // picks, state, draws (u) and the sums' pointers over the block; md, n, chunk and round are the caller's
+    // stream: where the zero fill is enqueued; nullptr: the blocking hipMemset (pqv_kpp_pick has no stream of its own)
+    int init(size_t n_picks, size_t n_draws, uint64_t n_chunks, size_t n_minima, const hipStream_t *stream) {
+        const size_t n64 = n_picks + n_chunks + 64 + 4096 + 64 + 72;
+        const size_t bytes = n64 * 8 + (n_draws + 4) * 4 + (n_minima ? 16 + n_minima * 4 : 0);
+        HIP_TRY(buf.alloc(bytes));
+        if (stream) HIP_TRY(hipMemsetAsync(buf.p, 0, bytes, *stream));
+        else HIP_TRY(hipMemset(buf.p, 0, bytes));
+        pa.picks = buf.as<unsigned long long>(); pa.n_chunks = static_cast<uint32_t>(n_chunks);
+        pa.chunk_sum = pa.picks + n_picks; pa.blk_sum = pa.chunk_sum + n_chunks; pa.run_sum = pa.blk_sum + 64; pa.blk_done = pa.run_sum + 4096;
+        pa.head = pa.blk_done + 64;
+        pa.u = draws = reinterpret_cast<float *>(pa.picks + n64);
+        pa.state = reinterpret_cast<uint32_t *>(draws + n_draws);
+        if (n_minima) minima = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(pa.state + 4) + 15) & ~static_cast<uintptr_t>(15));
+        return PQV_OK;
+    }
+};
+
+// (Measured and dropped: the screened rounds as ONE resident kernel fed through pinned memory -- commands polled with relaxed
+//  system-scope loads, minima mirrored with system-scope stores, a ticket per block -- 45 us a round against 24 for a launch per
+//  round: the PCIe round trips of the hand-shake cost more than a kernel launch and its completion.  Likewise a completion flag
+//  written by the last block of a per-round launch: the per-block system-scope release costs the kernel 20 us.)
+// Round 6: the rounds enqueued ahead with the pick on the device (kernels_kpp.hip: the reference's sequential f32 sums evaluated
+// exactly by composing the additions' integer images) -- no host round trip per centroid.  The draws of :373 are taken from a copy
+// of the generator (one per round while every total is positive); a round the device cannot decide the reference's way stops the
+// chain and the host walk takes over from that round.  PQV_KPP_DEVICE=0 keeps the host walk for every round (A/B, tests).
+// sa: the plain pass against centroid 0 (round 1's update).  *decided = the first round left to the host (k: none): picks[1 ..
+// decided) are set, rng has made their draws and, where rounds are left, the minima's mirrors are the device's state behind round
+// `decided`'s update (the chain ran without them).
+int kpp_device_rounds(pqv::StdRng &rng, const pqv::StreamArgs &sa, const pqv::MinUpdScreenArgs &ms, KppMinima &minima, uint32_t k,
+                      std::vector<uint64_t> &picks, hipStream_t stream, uint32_t *decided_out) {
+    using namespace pqv;
+    const double t_d0 = now_s();
+    KppScratch scratch;
+    if (int rc = scratch.init(k, k, minima.n_chunks, 0, &stream)) return rc;
+    StdRng ahead = rng;
+    std::vector<float> draws(k, 0.0f);
+    for (uint32_t i = 1; i < k; ++i) draws[i] = ahead.unit_f32();
+    const unsigned long long pick0 = picks[0];
+    HIP_TRY(hipMemcpyAsync(scratch.pa.picks, &pick0, sizeof pick0, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(scratch.draws, draws.data(), static_cast<size_t>(k) * sizeof(float), hipMemcpyHostToDevice, stream));
+    StreamArgs sd = sa;
+    sd.mirror_f32 = nullptr; sd.mirror_t = nullptr;
+    HIP_TRY(launch_stream(sd, STREAM_MINUPD, stream));
+    MinUpdScreenArgs md_args = ms;
+    md_args.mirror = nullptr; md_args.mirror_t = nullptr; md_args.stop = scratch.pa.state;
+    KppPickArgs pa = scratch.pa;
+    pa.md = minima.d_min.as<float>(); pa.n = static_cast<uint32_t>(minima.n); pa.chunk = static_cast<uint32_t>(minima.chunk);
+    for (uint32_t i = 1; i < k; ++i) {
+        if (i > 1) {                                   // (round 1 would re-measure centroid 0)
+            md_args.pick_dev = scratch.pa.picks + (i - 1);
+            HIP_TRY(launch_minupd_screen(md_args, stream));
+        }
+        pa.round = i;
+        HIP_TRY(launch_kpp_pick(pa, stream));
+    }
+    uint32_t h_state[4] = {0, 0, 0, 0};
+    std::vector<unsigned long long> h_picks(k, ~0ull);
+    HIP_TRY(hipMemcpyAsync(h_picks.data(), scratch.pa.picks, static_cast<size_t>(k) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(h_state, scratch.pa.state, sizeof h_state, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint32_t decided = h_state[0] ? std::min<uint32_t>(std::max<uint32_t>(h_state[1], 1), k) : k;   // rounds 1 .. decided - 1
+    for (uint32_t i = 1; i < decided; ++i) picks[i] = h_picks[i];
+    for (uint32_t i = 1; i < decided; ++i) (void)rng.unit_f32();     // the generator follows the rounds that were decided
+    if (verbose()) std::fprintf(stderr, "[pqv] k-means++ on the device: rounds 1..%u of %u in %.1f ms%s\n", decided - 1, k - 1,
+                                (now_s() - t_d0) * 1e3, h_state[0] ? " (the host walk takes over)" : "");
+    if (decided < k) {
+        if (verbose()) std::fprintf(stderr, "[pqv] k-means++: round %u back to the host (reason %u)\n", decided, h_state[2]);
+        if (int rc = minima.reload(stream)) return rc;
+    }
+    *decided_out = decided;
+    return PQV_OK;
+}
+
+// Rounds i_start .. k - 1 on the host (:354-390): a round's one command updates the minima against centroid i - 1, the host adds
+// the chunk sums off the mirror and walks to the pick.  Round i_start's update has run before the call -- round 1's is the plain
+// pass against centroid 0, a later one the device chain's last -- so the first round here launches nothing.
+int kpp_host_rounds(pqv::StdRng &rng, uint32_t i_start, uint32_t k, const KppSubset &subset, KppMinima &minima, pqv::StreamArgs sa,
+                    KppRoundScreen &screen, const float *d_centroids, std::vector<uint64_t> &picks, hipStream_t stream) {
+    using namespace pqv;
+    const uint64_t init_n = subset.init_n;
     double tt_gpu = 0.0, tt_sum = 0.0, tt_pick = 0.0;       // PQV_VERBOSE: where a round's time goes
     const bool vb = verbose();
     // round 6: the pick's walk starts on a second host thread while this one adds the chunk sums (PrefixScout; PQV_KPP_SCOUT=0: one thread)
     std::unique_ptr<PrefixScout> scout;
-    {
-        const char *e = std::getenv("PQV_KPP_SCOUT");
-        if (!(e && *e == '0') && std::thread::hardware_concurrency() >= 2 && k > 2 && init_n >= 4096 && i_start < k) {
-            scout.reset(new (std::nothrow) PrefixScout());
-            if (scout) scout->start(h_min.as<float>(), init_n);
-        }
+    if (env_on("PQV_KPP_SCOUT") && std::thread::hardware_concurrency() >= 2 && k > 2 && init_n >= 4096 && i_start < k) {
+        scout.reset(new (std::nothrow) PrefixScout());
+        if (scout) scout->start(minima.mirror(), init_n);
     }
     for (uint32_t i = i_start; i < k; ++i) {
         const double tr0 = vb ? now_s() : 0.0;
-        if (i > 1 && !(resume_after_update && i == i_start)) {  // round 1 would re-measure centroid 0: min-update is the identity
-            if (kpp_screen && picks[i - 1] != ~0ull) {
-                ms.pick = picks[i - 1];
-                HIP_TRY(launch_minupd_screen(ms, stream));
+        if (i > i_start) {
+            if (screen.applies && picks[i - 1] != ~0ull) {
+                screen.ms.pick = picks[i - 1];
+                HIP_TRY(launch_minupd_screen(screen.ms, stream));
             } else {                                                // (a centroid that is no subset row -- the zero fill -- takes the plain pass)
-                sa.queries = centroid_row(i - 1);
+                sa.queries = picks[i - 1] != ~0ull ? subset.row(picks[i - 1]) : d_centroids + static_cast<uint64_t>(i - 1) * subset.dim;
                 HIP_TRY(launch_stream(sa, STREAM_MINUPD, stream));
             }
         }
@@ -2301,37 +2345,8 @@ int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uin
         }
         const double tr1 = vb ? now_s() : 0.0;
         if (scout) scout->begin(i);
-        const float *md = h_min.as<float>();
-        // total = sum over worker chunks of the chunk's sequential f32 sum (:356-370)
-        // Each chunk's sum is its own sequential f32 chain and the chains are independent of each other, so eight
-        // full chunks run side by side; the chunk sums still join `total` in ascending chunk order.
-        float total = 0.0f;
-        uint64_t s = 0;
-        if (use_t) {
-            const float *mt = h_min_t.as<float>();
-            float *acc = chain_acc.data();
-            for (uint64_t c = 0; c < wpad; ++c) acc[c] = 0.0f;
-            chain_sums(mt, chunk, wpad, acc);                                          // w independent chains, one per vector lane
-            for (uint64_t c = 0; c < n_chunks; ++c) total = total + acc[c];            // joined in ascending chunk order
-            s = init_n;
-        } else if (chunk < init_n) {
-            for (; s + 8 * chunk <= init_n; s += 8 * chunk) {
-                const float *p = md + s;
-                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f, a5 = 0.0f, a6 = 0.0f, a7 = 0.0f;
-                for (uint64_t t = 0; t < chunk; ++t) {
-                    a0 = a0 + p[t];             a1 = a1 + p[chunk + t];     a2 = a2 + p[2 * chunk + t]; a3 = a3 + p[3 * chunk + t];
-                    a4 = a4 + p[4 * chunk + t]; a5 = a5 + p[5 * chunk + t]; a6 = a6 + p[6 * chunk + t]; a7 = a7 + p[7 * chunk + t];
-                }
-                total = total + a0; total = total + a1; total = total + a2; total = total + a3;
-                total = total + a4; total = total + a5; total = total + a6; total = total + a7;
-            }
-        }
-        for (; s < init_n; s += chunk) {
-            const uint64_t e = std::min(init_n, s + chunk);
-            float local = 0.0f;
-            for (uint64_t t = s; t < e; ++t) local = local + md[t];
-            total = total + local;
-        }
+        const float *md = minima.mirror();
+        const float total = minima.total();
         const double tr2 = vb ? now_s() : 0.0;
         if (total > 0.0f) {
             const float threshold = rng.unit_f32() * total;                            // :373
@@ -2351,33 +2366,35 @@ int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uin
         if (vb) { const double tr3 = now_s(); tt_gpu += tr1 - tr0; tt_sum += tr2 - tr1; tt_pick += tr3 - tr2; }
     }
     if (vb) std::fprintf(stderr, "[pqv] k-means++ rounds: launch + wait %.1f ms, chunk sums %.1f ms, pick scan %.1f ms\n", tt_gpu * 1e3, tt_sum * 1e3, tt_pick * 1e3);
-    // the chosen rows -> the centroid table (a centroid without a pick keeps its zero fill, as in the reference)
-    {
-        bool all = true;
-        for (uint32_t i = 0; i < k; ++i) all = all && picks[i] != ~0ull;
-        if (all) {
-            DevBuf d_picks;
-            HIP_TRY(d_picks.alloc(static_cast<size_t>(k) * sizeof(uint64_t)));
-            HIP_TRY(hipMemcpyAsync(d_picks.p, picks.data(), static_cast<size_t>(k) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            HIP_TRY(launch_gather_rows(d_init, nullptr, d_picks.as<uint64_t>(), k, dim, d_centroids, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-        } else {
-            for (uint32_t i = 0; i < k; ++i)
-                if (picks[i] != ~0ull)
-                    HIP_TRY(hipMemcpyAsync(d_centroids + static_cast<uint64_t>(i) * dim, d_init + picks[i] * dim,
-                                           dim * sizeof(float), hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    d_min.release(); d_init_own.release(); d_idx.release(); d_kimg.release(); d_kn2i.release(); d_kres.release(); d_kaux.release(); d_kmm.release();
-    HIP_TRY(hipStreamSynchronize(stream));
-    const double t_pp1 = now_s();
-    g_build_stats[0] = t_pp1 - t_pp0; g_build_stats[8] = 0.0; g_build_stats[9] = 0.0;
-    if (verbose()) std::fprintf(stderr, "[pqv] k-means++: %u rounds over %llu rows in %.3f s\n", k,
-                                (unsigned long long)init_n, t_pp1 - t_pp0);
+    return PQV_OK;
+}
 
-    // Lloyd iterations (:392-454)
+// the chosen rows -> the centroid table (a centroid without a pick keeps its zero fill, as in the reference)
+int kpp_commit(const std::vector<uint64_t> &picks, const KppSubset &subset, float *d_centroids, hipStream_t stream) {
+    const uint32_t k = static_cast<uint32_t>(picks.size()), dim = subset.dim;
+    bool all = true;
+    for (uint32_t i = 0; i < k; ++i) all = all && picks[i] != ~0ull;
+    if (all) {
+        DevBuf d_picks;
+        HIP_TRY(d_picks.alloc(static_cast<size_t>(k) * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpyAsync(d_picks.p, picks.data(), static_cast<size_t>(k) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(pqv::launch_gather_rows(subset.d_init, nullptr, d_picks.as<uint64_t>(), k, dim, d_centroids, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    } else {
+        for (uint32_t i = 0; i < k; ++i)
+            if (picks[i] != ~0ull)
+                HIP_TRY(hipMemcpyAsync(d_centroids + static_cast<uint64_t>(i) * dim, subset.row(picks[i]), dim * sizeof(float),
+                                       hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    return PQV_OK;
+}
+
+// Lloyd iterations (:392-454) over d_data [n, dim] from the centroids k-means++ left in d_centroids.  t0: the clock origin of the
+// phase (the end of k-means++).
+int lloyd_iterations(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iters, hipStream_t stream, float *d_centroids,
+                     double t0, std::vector<uint32_t> *assign_out, uint32_t *iters_run) {
+    using namespace pqv;
     DevBuf d_assign_a, d_assign_b, d_counts, d_list_rows, d_list_off;
     HIP_TRY(d_assign_a.alloc(n * sizeof(uint32_t)));
     HIP_TRY(d_assign_b.alloc(n * sizeof(uint32_t)));
@@ -2391,14 +2408,14 @@ int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uin
     std::vector<uint64_t> off;
     std::vector<uint32_t> rows;
     uint32_t iters = 0;
-    ScreenedAssign screen;
-    GemmAssign gemm;
-    const bool use_gemm = GemmAssign::applicable(dim, k);
-    const bool use_screen = !use_gemm && ScreenedAssign::applicable(dim, k);
-    {
-        const char *e = std::getenv("PQV_LLOYD_KEEP_IMAGES");
-        gemm.keep_mu = !(e && *e == '0');
-    }
+    // Lloyd tries ONE tier above the exact kernel: the contraction where it applies, else the screen, never the screen behind a
+    // contraction that stepped down.  What makes a tier step down -- a non-finite row, a centroid that is one -- is there again in
+    // the next iteration, and a second tier would spend its norm passes and its synchronisation on it every time; assign_rows
+    // runs once and does try both.
+    AssignLadder ladder;
+    ladder.try_gemm = GemmAssign::applicable(dim, k);
+    ladder.try_screen = !ladder.try_gemm && ScreenedAssign::applicable(dim, k);
+    ladder.gemm.keep_mu = env_on("PQV_LLOYD_KEEP_IMAGES");
     const bool dev_lists = DeviceLists::applicable(n, k);
     DeviceLists dlists;
     uint32_t h_bad = 0;
@@ -2409,27 +2426,8 @@ int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uin
     for (uint32_t iter = 0; iter < max_iters; ++iter) {
         HIP_TRY(hipMemsetAsync(d_counts.p, 0, (static_cast<size_t>(k) + 1) * sizeof(unsigned long long), stream));
         unsigned long long *d_changed = d_counts.as<unsigned long long>() + k;
-        bool exact_assign = !use_screen;
-        if (use_gemm) {
-            bool bad_c = false, bad_r = false;
-            if (int rc = gemm.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
-            if (!bad_c) {
-                if (int rc = gemm.run(d_data, n, d_cur, stream, &bad_r)) return rc;
-                if (!bad_r) HIP_TRY(launch_count_changed(d_cur, d_prev, n, d_changed, stream));
-            }
-            exact_assign = bad_c || bad_r;
-        }
-        if (use_screen) {
-            bool bad_c = false, bad_r = false;
-            if (int rc = screen.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
-            if (!bad_c) {
-                if (int rc = screen.run(d_data, n, d_cur, stream, &bad_r)) return rc;
-                if (!bad_r) HIP_TRY(launch_count_changed(d_cur, d_prev, n, d_changed, stream));
-            }
-            exact_assign = bad_c || bad_r;
-        }
-        if (exact_assign)
-            HIP_TRY(launch_assign(d_data, n, dim, d_centroids, k, d_cur, d_prev, d_changed, nullptr, stream));
+        AssignLadder::Tier tier;
+        if (int rc = ladder.run(d_data, n, d_centroids, k, dim, d_cur, stream, &tier, d_prev, d_changed)) return rc;
         HIP_TRY(hipMemcpyAsync(h_counts.data(), d_counts.p, h_counts.size() * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, stream));
         if (!dev_lists) HIP_TRY(hipMemcpyAsync(h_assign.data(), d_cur, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -2457,56 +2455,93 @@ int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uin
     }
     HIP_TRY(hipStreamSynchronize(stream));
     if (h_bad) return fail(PQV_ERR_HIP, "internal error: Lloyd assignment out of range");
-    g_build_stats[1] = now_s() - t_pp1; g_build_stats[2] = iters; g_build_stats[6] = use_gemm ? 2.0 : use_screen ? 1.0 : 0.0;
+    g_build_stats[BS_LLOYD_S] = now_s() - t0; g_build_stats[BS_ITERS] = iters;
+    g_build_stats[BS_LLOYD_FORM] = ladder.try_gemm ? AssignLadder::GEMM : ladder.try_screen ? AssignLadder::SCREEN : AssignLadder::EXACT;
     if (verbose()) std::fprintf(stderr, "[pqv] Lloyd: %u iterations over %llu rows in %.3f s\n", iters,
-                                (unsigned long long)n, now_s() - t_pp1);
+                                (unsigned long long)n, now_s() - t0);
     if (iters_run) *iters_run = iters;
     if (assign_out) *assign_out = std::move(h_assign);
     return PQV_OK;
 }
 
-// The final-assignment stage (index.rs:189-201 + :244-257): d_cluster[i] = nearest_centroid of row i of d_rows [n, dim] under
-// d_centroids [k, dim], i in [0, n) -- the f16 contraction where it applies, then the MFMA screen where rows (or centroids) were
-// flagged non-finite, then the exact kernel.  Depends on the centroids and these rows alone: the build calls it over the whole
-// column, pqv_index_assign / pqv_index_append over a row range (d_rows = the range's first row: the three forms index rows and
-// outputs from the base they are given and ask no more alignment of it than a row start has -- 16 bytes where dim % 4 == 0,
-// the scalar loads of the exact kernel otherwise; the non-finite checks read the norms of these n rows only).
-// time_kernels: the build's HIP-event bracket of the contraction kernel (g_build_stats[8], [9]).  t0: the caller's clock origin of
-// the PQV_VERBOSE lines.  *exact: the exact kernel ran; *form: 2.0 where the f16 contraction decided.
-int assign_rows(const float *d_rows, uint64_t n, uint32_t dim, const float *d_centroids, uint32_t k, uint32_t *d_cluster,
-                hipStream_t stream, bool time_kernels, double t0, bool *exact, double *form) {
+// d_data [n, dim] resident; writes d_centroids [k, dim] (device) and optionally the final
+// assignment (host).
+int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iters,
+                  uint64_t seed, uint32_t workers, hipStream_t stream, float *d_centroids,
+                  std::vector<uint32_t> *assign_out, uint32_t *iters_run) {
     using namespace pqv;
-    bool exact_assign = true;
-    if (GemmAssign::applicable(dim, k)) {
-        GemmAssign gemm;
-        bool bad_c = false, bad_r = false;
-        if (int rc = gemm.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
-        if (verbose()) std::fprintf(stderr, "[pqv] final assignment: centroids set at %.1f ms\n", (now_s() - t0) * 1e3);
-        if (!bad_c) {
-            // (chunk-wise downloads behind the next chunk's kernels were measured and dropped: a device-to-pageable copy on a
-            //  second stream stalls the compute stream's queue -- 53 ms for the loop against 34 ms of kernels on C3)
-            gemm.time_kernels = time_kernels;
-            if (int rc = gemm.run(d_rows, n, d_cluster, stream, &bad_r, nullptr)) return rc;
-            exact_assign = bad_r;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));     // the context's buffers are released at scope exit
-        if (!exact_assign) *form = 2.0;
-        if (verbose()) std::fprintf(stderr, "[pqv] final assignment: f16 path done at %.1f ms\n", (now_s() - t0) * 1e3);
+    if (workers == 0) workers = host_workers();
+    StdRng rng = StdRng::seed_from_u64(seed);                                          // :327
+    HIP_TRY(hipMemsetAsync(d_centroids, 0, static_cast<size_t>(k) * dim * sizeof(float), stream)); // :330
+
+    // k-means++ (:332-390).  Centroid i is row picks[i] of the subset (~0: none, the centroid keeps its zero fill).  A round measures
+    // against that row where it lies and the rows are copied into the table once, after the last round, so that a round is ONE command
+    // on the stream: no device-to-device copy before its kernel, no download after it (the kernel mirrors the minima into pinned host
+    // memory): 83 -> 64 us per round on C3's 50 000 x 768 subset (kernel 26 us, the host scans about 20).
+    KppSubset subset;
+    if (int rc = subset.draw(rng, d_data, n, dim, k, stream)) return rc;
+    std::vector<uint64_t> picks(k, ~0ull);
+    picks[0] = rng.range_usize(0, subset.init_n);                                      // :340-342
+    KppMinima minima;
+    if (int rc = minima.init(subset.init_n, workers, stream)) return rc;
+    StreamArgs sa = kpp_minupd_pass(subset, minima);
+    const double t_pp0 = now_s();
+    KppRoundScreen screen;
+    if (int rc = screen.init(subset, minima, k, stream)) return rc;
+    sa.queries = subset.row(picks[0]);             // distances to centroid 0
+    uint32_t i_start = 1;
+    if (env_on("PQV_KPP_DEVICE") && screen.applies && k >= 3 && minima.n <= 57344 && minima.n_chunks <= 1024 && minima.chunk <= 0xFFFFFFFFull) {
+        if (int rc = kpp_device_rounds(rng, sa, screen.ms, minima, k, picks, stream, &i_start)) return rc;
+    } else {
+        HIP_TRY(launch_stream(sa, STREAM_MINUPD, stream));
     }
-    if (exact_assign && ScreenedAssign::applicable(dim, k)) {
-        ScreenedAssign screen;
-        bool bad_c = false, bad_r = false;
-        if (int rc = screen.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
-        if (!bad_c) {
-            if (int rc = screen.run(d_rows, n, d_cluster, stream, &bad_r)) return rc;
-            exact_assign = bad_r;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));     // the context's buffers are released at scope exit
-    }
-    if (exact_assign)
-        HIP_TRY(launch_assign(d_rows, n, dim, d_centroids, k, d_cluster, nullptr, nullptr, nullptr, stream));
-    *exact = exact_assign;
-    return PQV_OK;
+    if (int rc = kpp_host_rounds(rng, i_start, k, subset, minima, sa, screen, d_centroids, picks, stream)) return rc;
+    if (int rc = kpp_commit(picks, subset, d_centroids, stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+    minima.d_min.release(); subset.release(); screen.release();
+    HIP_TRY(hipStreamSynchronize(stream));
+    const double t_pp1 = now_s();
+    g_build_stats[BS_KPP_S] = t_pp1 - t_pp0; g_build_stats[BS_WIDE_KERNEL_S] = 0.0; g_build_stats[BS_WIDE_LAUNCHES] = 0.0;
+    if (verbose()) std::fprintf(stderr, "[pqv] k-means++: %u rounds over %llu rows in %.3f s\n", k,
+                                (unsigned long long)subset.init_n, t_pp1 - t_pp0);
+
+    return lloyd_iterations(d_data, n, dim, k, max_iters, stream, d_centroids, t_pp1, assign_out, iters_run);
+}
+
+// The final-assignment stage (index.rs:189-201 + :244-257): d_cluster[i] = nearest_centroid of row i of d_rows [n, dim] under
+// d_centroids [k, dim], i in [0, n), by the ladder with both tiers above the exact kernel where they apply: one call over all the
+// rows, so the screen behind a contraction that stepped down is one more pass, paid once (Lloyd chooses differently: see there).
+// Depends on the centroids and these rows alone: the build calls it over the whole column, pqv_index_assign / pqv_index_append
+// over a row range (d_rows = the range's first row: the three forms index rows and outputs from the base they are given and ask
+// no more alignment of it than a row start has -- 16 bytes where dim % 4 == 0, the scalar loads of the exact kernel otherwise;
+// the non-finite checks read the norms of these n rows only).
+// time_kernels: the build's HIP-event bracket of the contraction kernel (BS_WIDE_KERNEL_S, BS_WIDE_LAUNCHES).  t0: the caller's
+// clock origin of the PQV_VERBOSE lines.  *decided: the tier that wrote d_cluster.
+int assign_rows(const float *d_rows, uint64_t n, uint32_t dim, const float *d_centroids, uint32_t k, uint32_t *d_cluster,
+                hipStream_t stream, bool time_kernels, double t0, AssignLadder::Tier *decided) {
+    AssignLadder ladder;
+    ladder.try_gemm = GemmAssign::applicable(dim, k);
+    ladder.try_screen = ScreenedAssign::applicable(dim, k);
+    ladder.one_shot = true; ladder.t0 = t0;
+    ladder.gemm.time_kernels = time_kernels;
+    return ladder.run(d_rows, n, d_centroids, k, dim, d_cluster, stream, decided);
+}
+
+// PQV_KEEP_DEVICE_LISTS=0: a built or derived index' lists are downloaded at once instead of staying on the device
+bool keep_device_lists() {
+    static const bool keep = env_on("PQV_KEEP_DEVICE_LISTS");
+    return keep;
+}
+// The sorted row ids stay where they are: a searcher on this device copies them device to device, and the host copy (40 MB per
+// 10 M rows: 3.5 ms of download) is made by the first call that reads it (ListRows::get).
+void adopt_device_lists(pqv_index *idx, DevBuf &rows, int device, uint64_t n) {
+    auto dr = std::make_shared<DevRows>();
+    dr->p = rows.p; dr->device = device; dr->n = n;
+    rows.p = nullptr; rows.bytes = 0;
+    idx->rows->dev = std::move(dr);
+    idx->rows->n = n;
+    idx->rows->host.clear();
+    idx->rows->pending = true;
 }
 
 int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
@@ -2523,7 +2558,7 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
     if (!corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
     if (int rc = use_device(corpus->device)) return rc;
     hipStream_t stream = corpus->stream;
-    g_build_stats[8] = 0.0; g_build_stats[9] = 0.0;      // (kernel seconds / launches of THIS build's final assignment, whichever path it takes)
+    g_build_stats[BS_WIDE_KERNEL_S] = 0.0; g_build_stats[BS_WIDE_LAUNCHES] = 0.0;      // (kernel seconds / launches of THIS build's final assignment, whichever path it takes)
 
     uint64_t sample_size = std::max<uint64_t>(n / 20, 1);                              // :172
     sample_size = std::min<uint64_t>(sample_size, 100000);                             // :173
@@ -2552,7 +2587,7 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
     const double t_b2 = now_s();
     d_sample.release(); d_idx.release();
     if (verbose()) std::fprintf(stderr, "[pqv] build: training sample %.3f s, k-means call %.3f s (k-means++ %.3f + Lloyd %.3f inside)\n",
-                                t_b1 - t_b0, t_b2 - t_b1, g_build_stats[0], g_build_stats[1]);
+                                t_b1 - t_b0, t_b2 - t_b1, g_build_stats[BS_KPP_S], g_build_stats[BS_LLOYD_S]);
 
     // final assignment of every row (:189-206)
     const double t_fa0 = now_s();
@@ -2570,11 +2605,9 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
             });
         } catch (const std::system_error &) { }
     }
-    bool exact_assign = true;
-    const bool downloaded = false;
-    double assign_form = 0.0;
+    AssignLadder::Tier assign_tier = AssignLadder::EXACT;
     if (int rc = assign_rows(corpus->d_rows, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(), stream,
-                             true, t_fa0, &exact_assign, &assign_form))
+                             true, t_fa0, &assign_tier))
         return rc;
     // the lists: sorted on the device (the rows of a list ascending, index.rs:193-206), then ONE download of the sorted row ids
     // in place of the assignment's download + the host threads' counting sort
@@ -2598,7 +2631,7 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
     idx->centroids.resize(k * dim);
     uint32_t h_bad = 0;
     hipError_t e = hipSuccess;
-    static const bool keep_dev = [] { const char *e = std::getenv("PQV_KEEP_DEVICE_LISTS"); return !(e && *e == '0'); }();
+    const bool keep_dev = keep_device_lists();
     if (dev_lists) {
         idx->list_off.resize(k + 1);
         if (!keep_dev) {                            // (the lists are not left on the device: downloaded here)
@@ -2607,7 +2640,7 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
         }
         if (e == hipSuccess) e = hipMemcpyAsync(idx->list_off.data(), d_off.p, (k + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, dlists.bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    } else if (!downloaded) {
+    } else {
         e = hipMemcpyAsync(cluster_of.data(), d_cluster.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
     }
     if (e == hipSuccess)
@@ -2622,21 +2655,11 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
         delete idx;
         return fail(PQV_ERR_HIP, "internal error: final assignment out of range");
     }
-    if (dev_lists && keep_dev && d_rows_sorted.p) {
-        // The sorted row ids stay where they are: a searcher on this device copies them device to device, and the host copy (40 MB per
-        // 10 M rows: 3.5 ms of download) is made by the first call that reads it (ListRows::get).  PQV_KEEP_DEVICE_LISTS=0: downloaded above.
-        auto dr = std::make_shared<DevRows>();
-        dr->p = d_rows_sorted.p; dr->device = corpus->device; dr->n = n;
-        d_rows_sorted.p = nullptr; d_rows_sorted.bytes = 0;
-        idx->rows->dev = std::move(dr);
-        idx->rows->n = n;
-        idx->rows->host.clear();
-        idx->rows->pending = true;
-    }
+    if (dev_lists && keep_dev && d_rows_sorted.p) adopt_device_lists(idx, d_rows_sorted, corpus->device, n);   // (PQV_KEEP_DEVICE_LISTS=0: downloaded above)
     idx->permutation_of = n;                        // every row was assigned exactly once
     idx->set_row_bound(n);
-    g_build_stats[3] = t_fa1 - t_fa0; g_build_stats[4] = now_s() - t_fa1; g_build_stats[5] = assign_form > 0.0 ? assign_form : exact_assign ? 0.0 : 1.0;
-    g_build_stats[7] = static_cast<double>(sample_size);
+    g_build_stats[BS_FINAL_ASSIGN_S] = t_fa1 - t_fa0; g_build_stats[BS_HOST_LISTS_S] = now_s() - t_fa1; g_build_stats[BS_FINAL_FORM] = assign_tier;
+    g_build_stats[BS_SAMPLE_ROWS] = static_cast<double>(sample_size);
     if (verbose()) std::fprintf(stderr, "[pqv] final assignment: %llu rows in %.3f s (+ %.3f s host list build)\n",
                                 (unsigned long long)n, t_fa1 - t_fa0, now_s() - t_fa1);
     if (verbose()) {
@@ -2688,10 +2711,9 @@ int assign_range(const pqv_index *index, const pqv_corpus *corpus, uint64_t firs
     HIP_TRY(d_centroids.alloc(index->centroids.size() * sizeof(float)));
     HIP_TRY(d_cluster.alloc(n_rows * sizeof(uint32_t)));
     HIP_TRY(hipMemcpyAsync(d_centroids.p, index->centroids.data(), index->centroids.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    bool exact = false;
-    double form = 0.0;
+    AssignLadder::Tier tier;
     return assign_rows(corpus->d_rows + first_row * corpus->dim, n_rows, corpus->dim, d_centroids.as<float>(), index->n_clusters,
-                       d_cluster.as<uint32_t>(), stream, false, now_s(), &exact, &form);
+                       d_cluster.as<uint32_t>(), stream, false, now_s(), &tier);
 }
 
 int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, uint32_t *cluster_out) {
@@ -2707,11 +2729,6 @@ int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
     return PQV_OK;
 }
 
-// PQV_KEEP_DEVICE_LISTS=0: a derived index' lists are downloaded at once instead of staying on the device
-bool keep_device_lists() {
-    static const bool keep = [] { const char *e = std::getenv("PQV_KEEP_DEVICE_LISTS"); return !(e && *e == '0'); }();
-    return keep;
-}
 struct EventSet { hipEvent_t e[4] = {}; ~EventSet() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
 
 int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out) {
@@ -2828,17 +2845,7 @@ int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
     HIP_TRY(hipMemcpyAsync(&h_bad, dlists.bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (h_bad != 0) return fail(PQV_ERR_HIP, "internal error: final assignment out of range");
-    if (keep_dev) {
-        // as a build leaves them: the lists stay on the device (a searcher here takes them device to device), the host copy is
-        // made by the first call that reads it
-        auto dr = std::make_shared<DevRows>();
-        dr->p = d_out_rows.p; dr->device = corpus->device; dr->n = total;
-        d_out_rows.p = nullptr; d_out_rows.bytes = 0;
-        idx->rows->dev = std::move(dr);
-        idx->rows->n = total;
-        idx->rows->host.clear();
-        idx->rows->pending = true;
-    }
+    if (keep_dev) adopt_device_lists(idx.get(), d_out_rows, corpus->device, total);      // as a build leaves them
     if (stats) {
         float ms_splice = 0.0f, ms_copy = 0.0f;
         (void)hipEventElapsedTime(&ms_splice, ev.e[0], ev.e[1]);
@@ -2883,16 +2890,6 @@ int copy_lists(const pqv_index *index, pqv_index *idx) {
     idx->list_rows = *rv;
     idx->permutation_of = index->permutation_of;
     return PQV_OK;
-}
-// as a build leaves them: the lists stay on the device, the host copy is made by the first call that reads it
-void adopt_device_lists(pqv_index *idx, DevBuf &rows, int device, uint64_t n) {
-    auto dr = std::make_shared<DevRows>();
-    dr->p = rows.p; dr->device = device; dr->n = n;
-    rows.p = nullptr; rows.bytes = 0;
-    idx->rows->dev = std::move(dr);
-    idx->rows->n = n;
-    idx->rows->host.clear();
-    idx->rows->pending = true;
 }
 // the index' lists on `device`: its device copy where it lives there, else one upload (up keeps it)
 int device_lists_of(const pqv_index *index, int device, uint64_t n_pos, hipStream_t stream, std::shared_ptr<DevRows> &keep, DevBuf &up,
@@ -3219,22 +3216,13 @@ static int pqv_kpp_pick_impl(int device, const float *minima, uint32_t n, uint32
     const uint64_t w = std::max<uint64_t>(1, std::min<uint64_t>(workers, n));          // index.rs:259-265
     const uint64_t chunk = (n + w - 1) / w, n_chunks = (n + chunk - 1) / chunk;
     if (n_chunks > 1024) return fail(PQV_ERR_INVALID, "more than 1024 worker chunks");
-    const size_t n64 = 2 + n_chunks + 64 + 4096 + 64 + 72;
-    const size_t bytes = n64 * 8 + 4 * 4 + 4 * 4 + 16 + static_cast<size_t>(n) * 4;
-    DevBuf buf;
-    HIP_TRY(buf.alloc(bytes));
-    HIP_TRY(hipMemset(buf.p, 0, bytes));
-    unsigned long long *d_picks = buf.as<unsigned long long>();
-    float *d_u = reinterpret_cast<float *>(d_picks + n64);
-    uint32_t *d_state = reinterpret_cast<uint32_t *>(d_u + 4);
-    float *d_md = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(d_state + 4) + 15) & ~static_cast<uintptr_t>(15));   // 16-byte aligned, as the build's minima are
+    KppScratch scratch;                                // two pick slots (round 1 writes the second), four draws, the minima behind them
+    if (int rc = scratch.init(2, 4, n_chunks, n, nullptr)) return rc;
     const float u2[2] = {0.0f, draw};
-    HIP_TRY(hipMemcpy(d_u, u2, sizeof u2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_md, minima, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
-    KppPickArgs pa{};
-    pa.md = d_md; pa.n = n; pa.chunk = static_cast<uint32_t>(chunk); pa.n_chunks = static_cast<uint32_t>(n_chunks);
-    pa.chunk_sum = d_picks + 2; pa.blk_sum = pa.chunk_sum + n_chunks; pa.run_sum = pa.blk_sum + 64; pa.blk_done = pa.run_sum + 4096; pa.head = pa.blk_done + 64;
-    pa.u = d_u; pa.round = 1; pa.picks = d_picks; pa.state = d_state;
+    HIP_TRY(hipMemcpy(scratch.draws, u2, sizeof u2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(scratch.minima, minima, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
+    KppPickArgs pa = scratch.pa;
+    pa.md = scratch.minima; pa.n = n; pa.chunk = static_cast<uint32_t>(chunk); pa.round = 1;
     DevBuf d_stamps;
     const char *want_stamps = std::getenv("PQV_KPP_STAMPS");
     if (want_stamps && *want_stamps == '1') {
@@ -3256,8 +3244,8 @@ static int pqv_kpp_pick_impl(int device, const float *minima, uint32_t n, uint32
     }
     uint32_t h_state[4];
     unsigned long long h_pick[2];
-    HIP_TRY(hipMemcpy(h_state, d_state, sizeof h_state, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h_pick, d_picks, sizeof h_pick, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_state, pa.state, sizeof h_state, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_pick, pa.picks, sizeof h_pick, hipMemcpyDeviceToHost));
     *status = h_state[0] ? h_state[2] : 0;
     std::memcpy(total, &h_state[3], 4);
     if (!h_state[0]) *pick = h_pick[1];
@@ -3270,7 +3258,7 @@ extern "C" int pqv_kpp_pick(int device, const float *minima, uint32_t n, uint32_
 
 extern "C" int pqv_index_build_stats(double *out, uint32_t n) {
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
-    for (uint32_t i = 0; i < n; ++i) out[i] = i < 10 ? g_build_stats[i] : 0.0;
+    for (uint32_t i = 0; i < n; ++i) out[i] = i < BS_COUNT ? g_build_stats[i] : 0.0;
     return PQV_OK;
 }
 

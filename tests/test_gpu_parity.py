@@ -336,6 +336,95 @@ def test_kmeans_matches_oracle_with_subset_sampling(pqv, oracle):
     assert (assign == oassign.astype(np.uint32)).all()
 
 
+def _gpu_kmeans(pqv, data, k, max_iters, seed, workers):
+    """pqv_kmeans over all rows of `data` (no training sample between the rows and k_means) -> centroids, assignments, iterations."""
+    import ctypes as C
+    from pq_vector_amd import _ffi
+    corpus = pqv.Corpus.upload(data)
+    cent = np.zeros((k, data.shape[1]), np.float32)
+    assign = np.zeros(len(data), np.uint32)
+    iters = C.c_uint32(0)
+    rc = _ffi.lib().pqv_kmeans(corpus._h, k, max_iters, seed, workers, cent.ctypes.data_as(_ffi.f32p),
+                               assign.ctypes.data_as(_ffi.u32p), C.byref(iters))
+    assert rc == 0, _ffi.lib().pqv_last_error()
+    return cent, assign, iters.value
+
+
+def _kmeans_hash(cent, assign, iters):
+    import hashlib
+    h = hashlib.sha256(np.uint32(iters).tobytes())
+    h.update(_bits(cent).tobytes())
+    h.update(np.ascontiguousarray(assign, dtype=np.uint32).tobytes())
+    return h.hexdigest()
+
+
+_HANDOVER_SCRIPT = r"""
+import sys, os, hashlib, ctypes as C
+sys.path.insert(0, os.getcwd())
+import numpy as np
+import pq_vector_amd as pqv
+from pq_vector_amd import _ffi
+data = np.load(sys.argv[1])
+k, max_iters, seed, workers = (int(x) for x in sys.argv[2:6])
+corpus = pqv.Corpus.upload(data)
+cent = np.zeros((k, data.shape[1]), np.float32)
+assign = np.zeros(len(data), np.uint32)
+iters = C.c_uint32(0)
+rc = _ffi.lib().pqv_kmeans(corpus._h, k, max_iters, seed, workers, cent.ctypes.data_as(_ffi.f32p),
+                           assign.ctypes.data_as(_ffi.u32p), C.byref(iters))
+assert rc == 0, _ffi.lib().pqv_last_error()
+h = hashlib.sha256(np.uint32(iters.value).tobytes()); h.update(cent.view(np.uint32).tobytes()); h.update(assign.tobytes())
+print("HASH", h.hexdigest())
+"""
+
+
+@pytest.mark.parametrize("workers", [2, 64])
+def test_kmeanspp_device_chain_hands_over_midway(oracle, tmp_path, workers):
+    """index.rs:354-390 with 24 distinct rows under 2 048 and k = 40: the device decides the rounds while `total` is positive, then
+    its pick reports total == 0 and the host draws gen_range for the rest -- the host rounds resume BEHIND an update the device
+    ran, from mirrors reloaded off the device (workers = 2: the plain mirror; 64: 64 chunks, the chunk-transposed one).  Iterations,
+    centroid bits and every assignment are the oracle's, with the device chain and with the host walk alone (PQV_KPP_DEVICE=0).
+    PQV_VERBOSE is read once per process: each case is a child process."""
+    import os, subprocess, sys
+    rng = np.random.default_rng(24 + 2048 + 40)
+    base = rng.random((24, 128), dtype=np.float32)
+    data = np.ascontiguousarray(base[rng.integers(0, 24, 2048)])
+    k, max_iters, seed = 40, 4, 11
+    ocent, oassign, oiters = oracle.kmeans(data, k, max_iters=max_iters, seed=seed, workers=workers)
+    assert oiters == 2 and len(set(oassign.tolist())) == 24
+    want = _kmeans_hash(ocent, oassign, oiters)
+    path = str(tmp_path / "rows.npy")
+    np.save(path, data)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for device, handed_over in (("1", True), ("0", False)):
+        env = dict(os.environ, PQV_VERBOSE="1", PQV_KPP_DEVICE=device)
+        p = subprocess.run([sys.executable, "-c", _HANDOVER_SCRIPT, path, str(k), str(max_iters), str(seed), str(workers)], cwd=root, env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        got = [l for l in p.stdout.splitlines() if l.startswith("HASH")][0].split()[1]
+        assert got == want, (device, p.stderr[-2000:])
+        assert ("the host walk takes over" in p.stderr) == handed_over, p.stderr[-2000:]
+
+
+@pytest.mark.parametrize("n,dim,k,gemm", [(3000, 128, 130, None), (6000, 64, 520, "0")])
+def test_lloyd_steps_down_a_tier_on_a_nonfinite_centroid_norm(pqv, oracle, monkeypatch, n, dim, k, gemm):
+    """Row 789 is 1e25 in every dimension: finite values whose squared norm overflows.  Its k-means++ minimum is +inf, so a device
+    chain (the 128-dim shape) stops at its first round and the host walks every round; the row then becomes a centroid, alone in its
+    cluster, so the assignment tier Lloyd chose -- the f16 contraction, or with PQV_ASSIGN_GEMM=0 and 520 centroids the MFMA
+    screen -- meets a non-finite centroid norm in every iteration and the exact kernel assigns and counts the changes."""
+    if gemm is not None:
+        monkeypatch.setenv("PQV_ASSIGN_GEMM", gemm)
+    rng = np.random.default_rng(n + dim + k)
+    data = rng.random((n, dim), dtype=np.float32)
+    data[789] = np.float32(1e25)
+    ocent, oassign, oiters = oracle.kmeans(data, k, max_iters=3, seed=11, workers=3)
+    assert np.isfinite(ocent).all() and oassign[789] == 1 and (oassign == 1).sum() == 1
+    cent, assign, iters = _gpu_kmeans(pqv, data, k, 3, 11, 3)
+    assert iters == oiters
+    assert (_bits(cent) == _bits(ocent)).all()
+    assert (assign == oassign.astype(np.uint32)).all()
+
+
 def test_empty_cluster_and_duplicate_rows(pqv, oracle):
     """Duplicate vectors: k-means++ total reaches 0 -> uniform pick (index.rs:384-389);
     clusters that end up empty keep all-zero centroids (index.rs:436,446-453)."""
