@@ -722,6 +722,39 @@ impl<'c> Searcher<'c> {
         Ok((hits, used))
     }
 
+    /// The plain top-k call with a probe depth per query (`include/pqv.h`: `pqv_topk_depth`): query `q` walks
+    /// `min(max(r, nprobe), max_nprobe)` lists -- `r` its entry of [`ProbeDepth::Given`], or with [`ProbeDepth::Ratio`] the lists whose
+    /// centroid lies within that factor (squared scale, `>= 1`) of the nearest centroid's distance -- and gets what
+    /// [`Searcher::topk`] returns at that `nprobe`.  Returns the hits and the lists each query probed.
+    pub fn topk_depth(&self, depth: &ProbeDepth, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize,
+                      max_nprobe: NonZeroUsize) -> Result<(Vec<Vec<SearchResult>>, Vec<u32>)> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (k, np, max_np) = (k.get(), nprobe.get(), max_nprobe.get());
+        // (the array the descriptor points at lives until the call has returned)
+        let desc = match depth {
+            ProbeDepth::Given(d) => {
+                if d.len() != nq {
+                    return Err("one probe depth per query".into());
+                }
+                sys::PqvProbeDepth { kind: sys::PQV_DEPTH_GIVEN, max_nprobe: max_np as u32, d2_ratio: 0.0, depths: d.as_ptr() as *const c_void }
+            }
+            ProbeDepth::Ratio(r) => sys::PqvProbeDepth { kind: sys::PQV_DEPTH_RATIO, max_nprobe: max_np as u32, d2_ratio: *r, depths: ptr::null() },
+        };
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        let mut used = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_depth(self.raw, &desc as *const sys::PqvProbeDepth, queries.as_ptr(), nq as u32, dim as u32, k as u32, np as u32,
+                                sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(), dist.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut(),
+                                used.as_mut_ptr())
+        })?;
+        let hits = (0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect();
+        Ok((hits, used))
+    }
+
     /// The nearest row of each of the `k` nearest groups -- a group is the considered rows of one value of `keys` (NULL-key rows
     /// belong to none), under `mask` where one is given (`include/pqv.h`: `pqv_topk_distinct`).  Ascending by (distance, position).
     pub fn topk_distinct(&self, keys: &RowKeys, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize,
@@ -1097,6 +1130,14 @@ impl Drop for KeyPartition {
     fn drop(&mut self) {
         unsafe { sys::pqv_key_partition_free(self.raw) }
     }
+}
+
+/// Where the probe depths of a [`Searcher::topk_depth`] call come from (`include/pqv.h`: `pqv_probe_depth`).
+pub enum ProbeDepth {
+    /// one depth per query; clamped into `[nprobe, max_nprobe]`
+    Given(Vec<u32>),
+    /// the lists whose centroid distance is at most this factor (squared scale, `>= 1`, may be infinite) times the nearest one's
+    Ratio(f32),
 }
 
 /// One filter per query of a [`Searcher::topk_filtered`] call, compared in i64 against the key column (`include/pqv.h`:

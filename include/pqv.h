@@ -731,6 +731,53 @@ int pqv_topk_expand_device(const pqv_searcher *searcher, const pqv_row_keys *key
                            uint32_t max_nprobe, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found,
                            void *d_n_candidates, void *d_nprobe_used, void *d_tie_flags, void *hip_stream);
 
+/* Per-query probe depths for the PLAIN top-k call: every query of a batch walks its own number of lists -- given by the caller (a
+ * frontend that batches requests with different nprobe values), or decided on the device from the centroid distances (a query
+ * inside a cluster needs its home list and little else; one between clusters needs more).  The call keeps the plain call's
+ * screened kernels; a rank nobody walks makes no work item, no seed sample and no pair image.
+ *
+ * With kc = n_clusters, p0 = min(nprobe, kc), P = min(max_nprobe, kc), c_0 .. c_{P-1} the query's probe order (the P nearest
+ * centroids by (d2, id)) and d2_j their probe distances -- the reference chain PQV_L2SQ_REF4 whatever `metric` is; PQV_COSINE: that
+ * chain of the normalised query against the normalised centroids, as the cosine probe -- the raw depth r_q is
+ *   PQV_DEPTH_GIVEN   depths[q];
+ *   PQV_DEPTH_RATIO   the number of j < P with d2_j <= t, t the single f32 product d2_ratio * d2_0 (no contraction).  d2_ratio is on
+ *                     the SQUARED scale.  A NaN on either side compares false: d2_0 == 0 with d2_ratio == +inf gives t = NaN and
+ *                     r_q = 0.  The distances ascend, so the counted ranks are a prefix.
+ * and nprobe_used[q] = min(max(r_q, p0), P): nprobe is the floor and max_nprobe the ceiling in both kinds; a given depth of 0 or
+ * above P is clamped, not refused (the device form cannot read the array).
+ * Query q's row_idx, dist, n_found and tie flag are, bit for bit, what pqv_topk / pqv_topk_device / pqv_topk_device_flags returns
+ * for that one query at nprobe = nprobe_used[q] and max_candidates = 0 (no new result is defined: the probe order is
+ * prefix-consistent and candidate positions are prefix sums in it).  The host form replays flagged queries through the reference
+ * heap over the query's first nprobe_used[q] lists.  n_candidates[q] is the summed length of those lists.  No searcher option changes
+ * a result.
+ *   counts     as for those nq single calls: queries advances by nq, candidate_rows and embeddings_fetched by the sum of
+ *              n_candidates.
+ *   scope      plain searchers, both layouts; PQV_L2SQ_REF4, PQV_L2SQ_SEQ and PQV_COSINE; k <= 1024 (1023 for the host form and for
+ *              the device form with tie flags); P <= 1024.  nprobe_used / d_nprobe_used, n_found, n_candidates and d_tie_flags may be
+ *              NULL.  GIVEN: depths is a host array in the host form and a device array, read inside the enqueued work, in the device
+ *              form.  The device form is asynchronous on hip_stream, with no host synchronisation.
+ *   out of scope  a depth combined with a mask, keys, a distinct or grouped call (those expand by counting: pqv_topk_expand,
+ *              pqv_topk_distinct_expand); range search; max_candidates; table searchers; PQV_DOT.
+ * Errors, NULL handles before any device use -- PQV_ERR_INVALID: "searcher must not be NULL", "depth must not be NULL",
+ * "max_nprobe must be >= nprobe", "unknown depth kind", "depths must not be NULL" (GIVEN), "d2_ratio must be >= 1 and not NaN"
+ * (RATIO), then the plain call's own ("k must be > 0", ...).  PQV_ERR_UNSUPPORTED: "pqv_topk_depth does not take table searchers",
+ * "PQV_DOT is not supported by pqv_topk_depth", "pqv_topk_depth takes k <= 1024 (1023 with tie flags) and at most 1024 probed lists
+ * per query". */
+#define PQV_DEPTH_GIVEN 0
+#define PQV_DEPTH_RATIO 1
+typedef struct pqv_probe_depth {
+    uint32_t    kind;        /* PQV_DEPTH_GIVEN | PQV_DEPTH_RATIO */
+    uint32_t    max_nprobe;  /* >= nprobe; the lists the probe ranks per query */
+    float       d2_ratio;    /* RATIO: >= 1, may be +inf, not NaN; on the SQUARED scale */
+    const void *depths;      /* GIVEN: u32 [nq], host (host form) / device (device form) */
+} pqv_probe_depth;
+int pqv_topk_depth(const pqv_searcher *searcher, const pqv_probe_depth *depth, const float *queries, uint32_t nq, uint32_t query_len,
+                   uint32_t k, uint32_t nprobe, int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found,
+                   uint64_t *n_candidates, uint32_t *nprobe_used);
+int pqv_topk_depth_device(const pqv_searcher *searcher, const pqv_probe_depth *depth, const void *d_queries, uint32_t nq, uint32_t k,
+                          uint32_t nprobe, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found,
+                          void *d_n_candidates, void *d_nprobe_used, void *d_tie_flags, void *hip_stream);
+
 /* Key partitions: exact per-key top-k over a key's own rows.  The keyed, filtered and expanding calls above answer a per-query
  * filter THROUGH the IVF lists: approximate (only the probed lists are seen), at a cost that follows the probed lists' length.  For
  * many small tenants that is the wrong end of the trade.  A key partition is a second set of lists over the same rows, keyed by the

@@ -21,6 +21,8 @@ Host-side mirror of the reference's Rust API over the C ABI of include/pqv.h:
                                                predicates (col("id") >= 2, & | ~) run on the GPU over resident Columns
     (no counterpart: probe on until k rows   topk / topk_device (mask= or keys=..., max_nprobe=P) -> also nprobe_used [nq];
       pass the filter)                         TopkBuilder(...).where(...).max_nprobe(P)
+    (no counterpart: a probe depth per       topk / topk_device (probe_depths=... | d2_ratio=r, max_nprobe=P) -> also nprobe_used [nq];
+      query of the plain call)                 TopkBuilder(...).d2_ratio(r).max_nprobe(P)
     SELECT DISTINCT ON (doc) .. LIMIT k      TopkBuilder / TableTopkBuilder: .distinct_on("doc") -> [DistinctSearchResult(row_idx,
       (no counterpart: grouping)               distance, key)]; Searcher.topk_distinct / topk_distinct_device (keys=RowKeys)
     ROW_NUMBER() OVER (PARTITION BY doc      .distinct_on("doc").group_size(m) -> [GroupSearchResult(key, hits=[SearchResult])]: up to m

@@ -55,6 +55,14 @@ class KeyFilter(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("a", C.c_void_p), ("b", C.c_void_p)]
 
 
+# per-query probe depths (pqv.h: pqv_probe_depth)
+PQV_DEPTH_GIVEN, PQV_DEPTH_RATIO = 0, 1
+
+
+class ProbeDepth(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("max_nprobe", C.c_uint32), ("d2_ratio", C.c_float), ("depths", C.c_void_p)]
+
+
 class Counters(C.Structure):
     _fields_ = [("queries", C.c_uint64), ("candidate_rows", C.c_uint64),
                 ("embeddings_fetched", C.c_uint64), ("kernel_launches", C.c_uint64),
@@ -181,6 +189,10 @@ SIGNATURES = {
                                            C.c_int, vp, vp, vp, vp, vp, vp]),
     "pqv_topk_expand": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_int, C.c_int, u32p, f32p, u32p, u64p, u32p]),
+    "pqv_topk_depth": (C.c_int, [vp, C.POINTER(ProbeDepth), f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                 u32p, f32p, u32p, u64p, u32p]),
+    "pqv_topk_depth_device": (C.c_int, [vp, C.POINTER(ProbeDepth), vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                        vp, vp, vp, vp, vp, vp, vp]),
     "pqv_topk_expand_device": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                          C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "pqv_key_partition_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),

@@ -786,6 +786,28 @@ def _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq, device=F
     return ("filtered", kh, _ffi.KeyFilter(_ffi.PQV_KEY_IN, 0, lims.ctypes.data, vals.ctypes.data), (lims, vals))
 
 
+def _probe_depth(probe_depths, d2_ratio, max_nprobe, max_candidates, mask, kf, nq, device=False):
+    """The pqv_probe_depth descriptor of a topk / topk_device call with probe_depths= or d2_ratio= (pqv.h: pqv_topk_depth), and
+    what must stay alive behind it.  Exactly one of the two, max_nprobe with it, and neither filter nor max_candidates."""
+    if probe_depths is not None and d2_ratio is not None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "probe_depths and d2_ratio are mutually exclusive")
+    if max_nprobe is None:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "probe_depths / d2_ratio need max_nprobe")
+    if max_candidates:
+        raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
+    if mask is not None or kf is not None:
+        raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "probe_depths / d2_ratio do not combine with mask= or keys= (pqv.h: pqv_topk_depth)")
+    if d2_ratio is not None:
+        return _ffi.ProbeDepth(_ffi.PQV_DEPTH_RATIO, max_nprobe, float(d2_ratio), None), None
+    if device:
+        return _ffi.ProbeDepth(_ffi.PQV_DEPTH_GIVEN, max_nprobe, 0.0, int(probe_depths) or None), None
+    arr = np.asarray(probe_depths)
+    if arr.shape != (nq,) or arr.dtype.kind not in "iu" or (arr.size and (arr.min() < 0 or arr.max() > 0xFFFFFFFF)):
+        raise PqvError(_ffi.PQV_ERR_INVALID, f"probe_depths must be {nq} integers in [0, 2^32)")
+    arr = np.ascontiguousarray(arr, dtype=np.uint32)
+    return _ffi.ProbeDepth(_ffi.PQV_DEPTH_GIVEN, max_nprobe, 0.0, arr.ctypes.data), arr
+
+
 def _expand_filter(kf, device=False):
     """An expanding call's (keys handle, KeyFilter pointer, what must stay alive) from _key_filter's answer: query_keys= travels as a
     PQV_KEY_EQ descriptor (pqv.h: pqv_topk_expand); no keys= gives (None, None, ())."""
@@ -1245,8 +1267,12 @@ class Searcher:
                                                             vp(d_n_candidates or None), vp(stream or None)))
 
     def topk(self, queries, k, nprobe, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, mask=None, keys=None,
-             query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=None):
+             query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=None, probe_depths=None, d2_ratio=None):
         """Batched topk(); returns (row_idx [nq,k] u32, dist [nq,k] f32, n_found [nq], n_candidates [nq]).
+        probe_depths (int [nq]) or d2_ratio (float >= 1), with max_nprobe and no filter: per-query probe depths -- query q walks
+        min(max(r, nprobe), max_nprobe) lists, r its given depth or the lists whose centroid is within d2_ratio (squared scale) of
+        the nearest one, and gets what the plain call returns at that nprobe; a fifth array nprobe_used [nq] u32 comes back
+        (pqv.h: pqv_topk_depth).
         max_nprobe (with mask= or keys=; not with max_candidates): keep probing until k rows pass the filter -- query q probes the
         fewest lists, at least nprobe and at most max_nprobe, whose passing rows number k, and gets what the call without
         max_nprobe returns for that many lists; a fifth array nprobe_used [nq] u32 comes back (pqv.h: pqv_topk_expand).
@@ -1265,6 +1291,13 @@ class Searcher:
         nf = np.zeros(nq, dtype=np.uint32)
         nc = np.zeros(nq, dtype=np.uint64)
         kf = _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq)
+        if probe_depths is not None or d2_ratio is not None:
+            d, _alive = _probe_depth(probe_depths, d2_ratio, max_nprobe, max_candidates, mask, kf, nq)
+            used = np.zeros(nq, dtype=np.uint32)
+            _check(_ffi.lib().pqv_topk_depth(self._h, C.byref(d), q.ctypes.data_as(f32p), nq, qlen, k, nprobe, metric,
+                                             1 if sqrt_out else 0, rows.ctypes.data_as(u32p), dist.ctypes.data_as(f32p),
+                                             nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p), used.ctypes.data_as(u32p)))
+            return rows, dist, nf, nc, used
         if max_nprobe is not None:
             if max_candidates:
                 raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
@@ -1535,7 +1568,8 @@ class Searcher:
 
     def topk_device(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0,
                     max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0, mask=None, keys=None,
-                    query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=0, d_nprobe_used=0):
+                    query_keys=None, query_key_ranges=None, query_key_sets=None, max_nprobe=0, d_nprobe_used=0, probe_depths=None,
+                    d2_ratio=None):
         """Device-pointer form (ints from tensor.data_ptr()); asynchronous on `stream` -- a hipStream_t handle; 0 means the
         searcher's OWN non-blocking stream, not HIP's / torch's default stream (whose handle is 0 too): work that must follow
         the call on the default stream is NOT ordered behind it, so pass an explicit stream (1 = hipStreamLegacy names the default
@@ -1548,8 +1582,16 @@ class Searcher:
         int64 values, every query's slice strictly ascending and at most PQV_KEY_SET_MAX long -- not validated, the call stays
         asynchronous (pqv.h: pqv_topk_filtered_device).
         max_nprobe (> 0, with mask= or keys=; not with max_candidates): the expanding call, as topk's; d_nprobe_used (u32 [nq],
-        optional) takes the lists each query probed (pqv.h: pqv_topk_expand_device)."""
+        optional) takes the lists each query probed (pqv.h: pqv_topk_expand_device).
+        probe_depths (the device pointer of uint32 [nq], read on `stream` inside the enqueued work) or d2_ratio (float >= 1), with
+        max_nprobe and no filter: per-query probe depths, as topk's; d_nprobe_used as above (pqv.h: pqv_topk_depth_device)."""
         kf = _key_filter(keys, query_keys, query_key_ranges, query_key_sets, nq, device=True)
+        if probe_depths is not None or d2_ratio is not None:
+            d, _alive = _probe_depth(probe_depths, d2_ratio, max_nprobe or None, max_candidates, mask, kf, nq, device=True)
+            _check(_ffi.lib().pqv_topk_depth_device(self._h, C.byref(d), vp(d_queries), nq, k, nprobe, metric, 1 if sqrt_out else 0,
+                                                    vp(d_row_idx), vp(d_dist), vp(d_n_found or None), vp(d_n_candidates or None),
+                                                    vp(d_nprobe_used or None), vp(d_tie_flags or None), vp(stream or None)))
+            return
         if max_nprobe:
             if max_candidates:
                 raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe and max_candidates are mutually exclusive")
@@ -1810,13 +1852,22 @@ class TopkBuilder:
         self._distinct = None
         self._group_size = None
         self._max_nprobe = None
+        self._d2_ratio = None
 
     def max_nprobe(self, n):
         """With where(): keep probing, up to n lists, until k rows pass the filter (pqv.h: pqv_topk_expand); nprobe() stays the
-        fewest lists probed.  Not with distinct_on(); table builders do not take it."""
+        fewest lists probed.  Not with distinct_on(); table builders do not take it.  With d2_ratio(): the ceiling of the depth."""
         if n == 0:
             raise PqvError(_ffi.PQV_ERR_INVALID, "max_nprobe must be > 0")
         self._max_nprobe = n
+        return self
+
+    def d2_ratio(self, r):
+        """With max_nprobe(n) and no where() / distinct_on(): probe the lists whose centroid is within r (>= 1, squared scale) of the
+        nearest centroid's distance, at least nprobe() and at most n of them (pqv.h: pqv_topk_depth)."""
+        if not r >= 1.0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "d2_ratio must be >= 1 and not NaN")
+        self._d2_ratio = float(r)
         return self
 
     def metric(self, m):
@@ -1908,7 +1959,12 @@ class TopkBuilder:
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         self._check_grouping()
-        if self._max_nprobe is not None and self._where is None and self._distinct is None:
+        if self._d2_ratio is not None:
+            if self._max_nprobe is None:
+                raise PqvError(_ffi.PQV_ERR_INVALID, "probe_depths / d2_ratio need max_nprobe")
+            if self._where is not None or self._distinct is not None:
+                raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "d2_ratio() does not combine with where() or distinct_on() (pqv.h: pqv_topk_depth)")
+        elif self._max_nprobe is not None and self._where is None and self._distinct is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "pqv_topk_expand needs a row mask or row keys")
         if self._searcher is None:
             self._searcher = searcher_for_parquet(self._path, self._device)
@@ -1931,6 +1987,9 @@ class TopkBuilder:
             finally:
                 if owned:
                     mask.close()
+        elif self._d2_ratio is not None:
+            rows, dist, nf = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric,
+                                                 max_nprobe=self._max_nprobe, d2_ratio=self._d2_ratio)[:3]
         else:
             rows, dist, nf, _ = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric)
         n = int(nf[0])

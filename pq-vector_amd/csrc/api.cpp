@@ -358,6 +358,7 @@ struct Scratch {
         // host form's group_rows block
         s_g1_rows, s_g1_dist, s_g1_keys, s_g1_nfound, s_gset_keys, s_gset_slot, s_gpart_slot, s_gpart_cnt, s_grows_out,
         s_expand_cnt, s_expand_used,    // pqv_topk_expand: the passing rows per probed list u32 [nq][P]; nprobe_used u32 [nq] where the caller takes none
+        s_depths, s_depth_d2, s_depth_end,  // pqv_topk_depth: a host call's given depths u32 [b]; the probe distances' bits u32 [nq][P]; the pairs' candidate ends u64 [nq][P]
         s_ps_q16, s_ps_qn2, s_ps_score, // screened probe: the batch's query images f16 [nq][dim_p], |q - mean|^2 [nq], the scores f32 [nq][kc_pad]
         s_seg_off,                      // pqv_range_search_partition: the group's packed segment offsets u64 [b]
         s_pt_beg, s_pt_end, s_pt_nspan; // pqv_topk_partition: the spans' first entries u32 [nq] (IN: [nq][1024]), IN: their prefix sums and counts
@@ -376,7 +377,7 @@ struct Scratch {
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
                 &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
                 &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out,
-                &s_expand_cnt, &s_expand_used, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_seg_off, &s_pt_beg, &s_pt_end, &s_pt_nspan};
+                &s_expand_cnt, &s_expand_used, &s_depths, &s_depth_d2, &s_depth_end, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_seg_off, &s_pt_beg, &s_pt_end, &s_pt_nspan};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -627,8 +628,15 @@ struct Grouping {                      // a distinct / grouped call
     int64_t *d_keys;                   // where the fold writes the group values [nq * k] (device), or nullptr
     uint32_t *d_rows;                  // grouped: where the rows per group go [nq * k] (device), or nullptr
 };
-struct Expansion {                     // an expanding call (pqv_topk_expand)
+enum DepthSource : uint32_t { DEPTH_COUNTED = 0, DEPTH_GIVEN, DEPTH_RATIO };
+struct Expansion {                     // a call with per-query probe depths (pqv_topk_expand, pqv_topk_depth)
     uint32_t max_nprobe;               // the lists the probe ranks per query, >= the call's nprobe; 0: not expanding
+    // where a query's depth comes from: the passing rows or groups counted on the way (pqv_topk_expand and its grouped forms), the
+    // caller's array, or the probe distances against d2_ratio times the nearest one (pqv_topk_depth: no filter, the plain call's plan)
+    uint32_t source;
+    float d2_ratio;
+    const uint32_t *h_depths;          // GIVEN, host form: [nq], indexed like the call's queries
+    const uint32_t *d_depths;          // GIVEN, device: the depths of the queries the kernels see (the current sub-batch's)
     uint32_t *d_used;                  // where the lists each query used go [nq] (device), or nullptr (the lane's scratch)
     uint32_t *h_used;                  // host form: the caller's [nq], or nullptr
 };
@@ -640,12 +648,16 @@ struct SearchRequest {
     bool eq_keys() const { return rows.keys && !rows.kind; }               // ... of kind PQV_KEY_EQ
     bool distinct() const { return groups.col != nullptr; }
     bool expanding() const { return expand.max_nprobe != 0; }
+    // pqv_topk_depth: nothing but depths -- the plain call's kernels under per-query rank limits, not the filtered stream
+    bool depth_only() const { return expanding() && expand.source != DEPTH_COUNTED; }
     // a filtered call's per-query arguments as the kernels read them
     const void *d_filter_a() const { return rows.kind ? rows.d_a : rows.d_qkeys; }
     const void *d_filter_b() const { return rows.kind ? rows.d_b : nullptr; }
 };
 // the lists the probe of a call ranks per query: an expanding call's max_nprobe, else its nprobe
 static inline uint32_t probe_arg(const SearchRequest *mv, uint32_t nprobe) { return mv && mv->expanding() ? mv->expand.max_nprobe : nprobe; }
+// a request whose rows are filtered or grouped takes the exact stream (plan_topk); one that only carries depths keeps the plain plan
+static inline bool stream_request(const SearchRequest *mv) { return mv && !mv->depth_only(); }
 // a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
 static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
     const uint64_t n_words = (m->n_rows + 63) / 64;
@@ -4380,12 +4392,14 @@ struct TopkRoute {
     bool seed_tail;         // one query: the seed kernel's last block selects (SeedTail); otherwise a launch of its own
     bool deferred;          // deferred exact evaluation: survivors appended with their bounds, resolved by launch_resolve
 };
-static TopkRoute topk_route(const pqv_searcher *s, const TopkPlan &p, uint32_t nq, uint32_t k) {
+// rank_limits: a call under per-query probe depths (pqv_topk_depth) -- its one-query form goes through the general pair sort, which
+// leaves the cut ranks out (the probe merge's own bucketing makes a quad of every rank)
+static TopkRoute topk_route(const pqv_searcher *s, const TopkPlan &p, uint32_t nq, uint32_t k, bool rank_limits = false) {
     TopkRoute r{};
     r.screened = p.tile && p.filter && p.quad;
     if (!r.screened) return r;
     r.operand = p.i8 ? 2 : p.f16 ? 1 : 0;
-    r.single_bucket = nq == 1 && p.np <= 64 && s->opt.single_bucket && !s->n_files;
+    r.single_bucket = nq == 1 && p.np <= 64 && s->opt.single_bucket && !s->n_files && !rank_limits;
     r.fused_probe = r.single_bucket && s->opt.single_bucket > 0 && s->opt.single_bucket != 2 && s->kc_pad != 0 && s->kc_pad <= 4096;
     r.items = (s->opt.item_grid > 1 || (s->opt.item_grid == 1 && p.block_waves == 4)) &&
               static_cast<uint64_t>(p.max_quads) * p.filter_bpl <= (1ull << 24);
@@ -4547,6 +4561,8 @@ static int enqueue_probe_stage(TopkCall &c, uint32_t nprobe) {
         HIP_TRY(sc.s_gthr.ensure(static_cast<size_t>(nq) * sizeof(unsigned long long)));
         if (p.filter) { HIP_TRY(sc.s_qnorm.ensure(static_cast<size_t>(nq) * sizeof(float))); HIP_TRY(sc.s_qmax.ensure(static_cast<size_t>(nq) * sizeof(float))); }
         pm.hist = pair_u32; pm.hist_stride = kc_pairs; pm.gthr_init = sc.s_gthr.as<unsigned long long>();
+        // (per-query depths are decided behind the merge: probe_depth fills the histogram, below the limits)
+        if (c.rq && c.rq->depth_only()) pm.hist = nullptr;
         // every partial list of the re-rank starts EMPTY: preset by the probe merge (one wave per query)
         if (rt.screened) {              // wide path: one "written" byte per list (see MergeArgs::preset_flags)
             const uint32_t nflag = (p.n_part_rr + 3) / 4 * 4;
@@ -4584,6 +4600,10 @@ static int enqueue_probe_stage(TopkCall &c, uint32_t nprobe) {
                                      s->d_list_scale.as<float>(), s->d_list_half.as<float>(), s->d_list_radius.as<float>(),
                                      static_cast<uint32_t>(n_img), per_pair ? p.np : 1u, s->sdim, static_cast<int8_t *>(sc.s_qi8.p),
                                      sc.s_qn2i.as<int>(), sc.s_qres.as<float>(), sc.s_qresu.as<float>(), sc.s_pair_lb.as<float>()};
+    }
+    if (c.rq && c.rq->depth_only() && c.rq->expand.source == DEPTH_RATIO) {     // the depth stage reads the ranks' probe distances
+        HIP_TRY(sc.s_depth_d2.ensure(static_cast<size_t>(nq) * p.np * sizeof(uint32_t)));
+        pm.probe_d2 = sc.s_depth_d2.as<uint32_t>();
     }
     if (rt.fused_probe) {
         pqv::ProbeRowsArgs pr{};
@@ -4642,6 +4662,28 @@ static int expand_depth(TopkCall &c) {
     c.rank_limit = used;
     return PQV_OK;
 }
+// stage: a call with depths of its own (pqv_topk_depth).  The probe ranked P lists per query; one wave per query clamps the caller's
+// depth, or counts the ranks within d2_ratio of the nearest centroid, into [p0, P].  Everything behind it runs under those limits:
+// the pair sort leaves the cut pairs out (c.rank_limit), the kernels that walk by (query, rank) find no candidate in them
+// (c.pair_end), and the candidate totals are those of the used lists -- counted here, the request's probe merge counts nothing.
+static int probe_depth(TopkCall &c) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const SearchRequest *rq = c.rq;
+    const uint32_t nq = c.nq, P = c.p.np;
+    uint32_t *used = rq->expand.d_used;
+    if (!used) { HIP_TRY(sc.s_expand_used.ensure(static_cast<size_t>(nq) * sizeof(uint32_t))); used = sc.s_expand_used.as<uint32_t>(); }
+    HIP_TRY(sc.s_depth_end.ensure(static_cast<size_t>(nq) * P * sizeof(uint64_t)));
+    const bool given = rq->expand.source == DEPTH_GIVEN;
+    if (given && !rq->expand.d_depths) return fail(PQV_ERR_INVALID, "depths must not be NULL");
+    const ProbeDepthArgs da{given ? rq->expand.d_depths : nullptr, given ? nullptr : c.pm.probe_d2, rq->expand.d2_ratio, sc.s_probe.as<uint32_t>(),
+                            sc.s_cand_base.as<uint64_t>(), s->d_list_off.as<uint64_t>(), nq, P, c.p0, used, c.pm.n_cand,
+                            sc.s_depth_end.as<uint64_t>(), s->d_stats.as<unsigned long long>(), c.p.tile ? c.pair_u32 : nullptr, s->n_clusters};
+    HIP_TRY(launch_probe_depth(da, c.stream));
+    s->counters.kernel_launches += 1;
+    c.rank_limit = used;
+    c.pair_end = sc.s_depth_end.as<uint64_t>();
+    return PQV_OK;
+}
 // stage 2a: the probed (query, list) pairs bucketed by list into groups and quads (pair sort; one query: done by the probe merge),
 // and the work-item tables of the wide screen.  ps: filled for the re-rank stages that read its tables.
 static int enqueue_pair_sort(TopkCall &c, pqv::PairSortArgs &ps) {
@@ -4651,6 +4693,7 @@ static int enqueue_pair_sort(TopkCall &c, pqv::PairSortArgs &ps) {
     const uint32_t n_pairs = nq * p.np, kc = s->n_clusters;
     uint32_t *u = c.pair_u32;
     ps.probe = sc.s_probe.as<uint32_t>(); ps.n_pairs = n_pairs; ps.n_clusters = kc; ps.hist_done = 1;
+    ps.rank_limit = c.rank_limit;          // (per-query depths: the histogram holds the pairs below them, see probe_depth)
     uint32_t *v = u + 2 * (pqv::HIST_REPLICAS - 1) * static_cast<uint64_t>(kc);    // past the extra histogram / cursor copies
     ps.hist = u; ps.hist_stride = kc; ps.nprobe = p.np; ps.cursor = u + pqv::HIST_REPLICAS * static_cast<uint64_t>(kc);
     ps.pair_off = v + 2ull * kc; ps.group_off = v + 3ull * kc + 1;
@@ -4720,6 +4763,12 @@ static int enqueue_wide_screen(TopkCall &c, const pqv::PairSortArgs &ps, pqv::Ti
     const uint32_t n_vals = p.np * seed.seed_sw * 16;
     HIP_TRY(sc.s_seed_ub.ensure(static_cast<size_t>(nq) * n_vals * sizeof(float)));
     seed.seed_ub = sc.s_seed_ub.as<float>();
+    // (per-query depths: no quad holds a cut rank.  A batch's selection reads the bounds below the limits only; the one-query call
+    //  selects inside the seed launch over all P ranks, so the cut ranks' bounds are preset to "none")
+    if (c.rank_limit && rt.seed_tail) {
+        HIP_TRY(launch_depth_seed_clear(seed.seed_ub, c.rank_limit, nq, p.np, seed.seed_sw * 16, stream));
+        s->counters.kernel_launches += 1;
+    }
     // running thresholds: see TileArgs::thr_hist
     if (s->opt.running_thr && k > 1) {
         HIP_TRY(sc.s_thr_hist.ensure(static_cast<size_t>(nq) * 16 * sizeof(uint32_t)));
@@ -4748,7 +4797,7 @@ static int enqueue_wide_screen(TopkCall &c, const pqv::PairSortArgs &ps, pqv::Ti
     HIP_TRY(launch_wide_seed(seed, stream));
     if (!rt.seed_tail)
         HIP_TRY(launch_seed_select(seed.seed_ub, nq, n_vals, k, ta.gthr, ta.cand_cnt, ta.spilled, stream,
-                                   ta.thr_hist, static_cast<float4 *>(sc.s_thr_bins.p), &rf));
+                                   ta.thr_hist, static_cast<float4 *>(sc.s_thr_bins.p), &rf, c.rank_limit, seed.seed_sw * 16));
     ta.row_offset = 0; ta.slot_base = 0; ta.grid_x = p.filter_bpl;
     ta.rows_per_block = p.filter_rows_per_block; ta.filter_variant = 0;
     ta.part_flags = sc.s_part_flags.as<uint8_t>();
@@ -4850,7 +4899,7 @@ static int enqueue_tile_rerank(TopkCall &c) {
             if (!c.quant_done) {
                 HIP_TRY(launch_quantize_pairs_i8(pq_args.queries, pq_args.probe, pq_args.center, pq_args.scale, pq_args.half, pq_args.radius,
                                                  pq_args.n_pairs, pq_args.nprobe, pq_args.dim, pq_args.q_i8, pq_args.q_n2i, pq_args.q_res,
-                                                 pq_args.q_resu, pq_args.pair_lb, stream));
+                                                 pq_args.q_resu, pq_args.pair_lb, stream, c.rank_limit));
                 s->counters.kernel_launches += 1;
             }
             ta.i8 = 1; ta.i8_pair_images = per_pair ? 1 : 0;
@@ -4939,13 +4988,15 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
                  uint32_t *d_tie, hipStream_t stream, Scratch &sc, const SearchRequest *rq = nullptr) {
     using namespace pqv;
     // an expanding call (pqv_topk_expand): the probe ranks P = min(max_nprobe, n_clusters) lists per query (expand_depth)
-    const bool expand = rq && rq->expanding(), distinct = rq && rq->distinct();
+    // a call with depths of its own (pqv_topk_depth) keeps the plain call's plan for P lists (probe_depth)
+    const bool expand = rq && rq->expanding(), distinct = rq && rq->distinct(), depth = rq && rq->depth_only();
     const uint32_t p0 = probe_count(s, nprobe);
     nprobe = probe_arg(rq, nprobe);
-    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, rq != nullptr);
-    if (expand && (s->n_files || p.tile || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
+    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, stream_request(rq));
+    if (depth && (distinct || rq->filtered() || rq->rows.bits)) return fail(PQV_ERR_INVALID, "a depth call takes no filter and no grouping");
+    if (expand && (s->n_files || (p.tile && !depth) || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
         return fail(PQV_ERR_INVALID, "expanding call on a plan that cannot expand");
-    const TopkRoute rt = topk_route(s, p, nq, k);
+    const TopkRoute rt = topk_route(s, p, nq, k, depth);
     TopkCall c{s, sc, stream, p, rt, rq, nq, k, k_out, p0, max_candidates, max_candidates ? max_candidates : ~0ull, metric, sqrt_out,
                d_queries, d_queries, d_row_idx, d_dist, d_n_found, d_tie};
     if (int rc = pad_queries(c)) return rc;
@@ -4959,7 +5010,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     if (int rc = timing_events(s, c.ev)) return rc;
     if (c.ev[0]) HIP_TRY(hipEventRecord(c.ev[0], stream));
     if (int rc = enqueue_probe_stage(c, nprobe)) return rc;
-    if (expand) { if (int rc = expand_depth(c)) return rc; }
+    if (expand) { if (int rc = depth ? probe_depth(c) : expand_depth(c)) return rc; }
 
     // 2. candidate re-rank + per-wave top-k
     if (p.tile) { if (int rc = enqueue_tile_rerank(c)) return rc; }
@@ -4968,6 +5019,9 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
     if (!p.tile) {
         if (c.ev[1]) HIP_TRY(hipEventRecord(c.ev[1], stream));
+        if (depth) {       // (no filter: the plain walk, a cut rank's blocks storing empty lists; probe_depth has counted the candidates)
+            HIP_TRY(launch_limited_stream(ra, MaskedArgs{nullptr, nullptr, nullptr, c.rank_limit}, stream));
+        } else
         HIP_TRY(launch_stream_pass(ra, rq, s->d_stats.as<unsigned long long>(), c.pm.n_cand, STREAM_TOPK, stream,
                                    distinct ? sc.s_part_grp.as<int64_t>() : nullptr, c.rank_limit));
         if (c.ev[2]) HIP_TRY(hipEventRecord(c.ev[2], stream));
@@ -5367,6 +5421,11 @@ static int host_batches(const pqv_searcher *s, Scratch &sc, const float *queries
     for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
         const uint32_t b = std::min<uint32_t>(batch, nq - q0);
         if (int rc = upload_query_filter(sc, rq, sub, q0, b, sub_lims, s->stream)) return rc;
+        if (rq && rq->expand.h_depths) {       // (pqv_topk_depth: the sub-batch's given depths)
+            HIP_TRY(sc.s_depths.ensure(static_cast<size_t>(b) * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpyAsync(sc.s_depths.p, rq->expand.h_depths + q0, static_cast<size_t>(b) * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+            sub.expand.d_depths = sc.s_depths.as<uint32_t>();
+        }
         const void *src = queries + static_cast<uint64_t>(q0) * s->dim;
         if (h_stage) src = std::memcpy(h_stage, src, b * q_row);
         HIP_TRY(hipMemcpyAsync(sc.s_queries.p, src, b * q_row, hipMemcpyHostToDevice, s->stream));
@@ -5422,7 +5481,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
     // (per query: partial lists, probe partial lists, candidate buffer, the int8 images of its probed pairs; a grouping: 20 B per
     //  entry of the partial lists, and a grouped call's second pass 16 B per entry of k * m in the same buffers)
-    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(rq, nprobe), k_int, metric, rq != nullptr);
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(rq, nprobe), k_int, metric, stream_request(rq));
     const uint64_t km = static_cast<uint64_t>(k) * m;
     const uint64_t per_query =
         grouped ? static_cast<uint64_t>(p1.n_part_rr) * std::max<uint64_t>(k * 20ull, m > 1 ? km * 16 + 4 : 0) +
@@ -6216,6 +6275,50 @@ extern "C" int pqv_topk_expand_device(const pqv_searcher *s, const pqv_row_keys 
     return guard([&] {
         SearchRequest mv{};
         if (int rc = expand_view(s, keys, filter, mask, nq, k, nprobe, max_nprobe, metric, false, d_tie_flags != nullptr, mv)) return rc;
+        mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, d_tie_flags, hip_stream, &mv);
+    });
+}
+// ---- per-query probe depths (pqv.h: pqv_topk_depth) ------------------------------------------------------------------------
+// The checks of both forms up to the view, in the contract's order; nothing is dereferenced before the NULL checks.
+static int depth_view(const pqv_searcher *s, const pqv_probe_depth *d, uint32_t nq, uint32_t k, uint32_t nprobe, int metric, bool flags,
+                      SearchRequest &mv) {
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (!d) return fail(PQV_ERR_INVALID, "depth must not be NULL");
+    if (d->max_nprobe < nprobe) return fail(PQV_ERR_INVALID, "max_nprobe must be >= nprobe");
+    if (d->kind != PQV_DEPTH_GIVEN && d->kind != PQV_DEPTH_RATIO) return fail(PQV_ERR_INVALID, "unknown depth kind " + std::to_string(d->kind));
+    if (d->kind == PQV_DEPTH_GIVEN && nq && !d->depths) return fail(PQV_ERR_INVALID, "depths must not be NULL");
+    if (d->kind == PQV_DEPTH_RATIO && !(d->d2_ratio >= 1.0f)) return fail(PQV_ERR_INVALID, "d2_ratio must be >= 1 and not NaN");
+    if (int rc = validate_topk(s, k, nprobe, metric)) return rc;
+    if (s->n_files) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_depth does not take table searchers");
+    if (metric == PQV_DOT) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by pqv_topk_depth");
+    // (the host form always carries the runner-up entry its tie replay needs)
+    if (k > (flags ? 1023u : 1024u) || probe_count(s, d->max_nprobe) > 1024)
+        return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_depth takes k <= 1024 (1023 with tie flags) and at most 1024 probed lists per query");
+    mv.expand.max_nprobe = d->max_nprobe;
+    mv.expand.source = d->kind == PQV_DEPTH_GIVEN ? DEPTH_GIVEN : DEPTH_RATIO;
+    mv.expand.d2_ratio = d->d2_ratio;
+    return PQV_OK;
+}
+extern "C" int pqv_topk_depth(const pqv_searcher *s, const pqv_probe_depth *depth, const float *queries, uint32_t nq, uint32_t query_len,
+                              uint32_t k, uint32_t nprobe, int metric, int sqrt_out, uint32_t *row_idx, float *dist, uint32_t *n_found,
+                              uint64_t *n_candidates, uint32_t *nprobe_used) {
+    return guard([&] {
+        SearchRequest mv{};
+        if (int rc = depth_view(s, depth, nq, k, nprobe, metric, true, mv)) return rc;
+        if (depth->kind == PQV_DEPTH_GIVEN) mv.expand.h_depths = static_cast<const uint32_t *>(depth->depths);
+        mv.expand.h_used = nprobe_used;
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
+    });
+}
+extern "C" int pqv_topk_depth_device(const pqv_searcher *s, const pqv_probe_depth *depth, const void *d_queries, uint32_t nq, uint32_t k,
+                                     uint32_t nprobe, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_n_found,
+                                     void *d_n_candidates, void *d_nprobe_used, void *d_tie_flags, void *hip_stream) {
+    return guard([&] {
+        SearchRequest mv{};
+        if (int rc = depth_view(s, depth, nq, k, nprobe, metric, d_tie_flags != nullptr, mv)) return rc;
+        if (depth->kind == PQV_DEPTH_GIVEN) mv.expand.d_depths = static_cast<const uint32_t *>(depth->depths);
         mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);

@@ -91,6 +91,8 @@ struct MaskedArgs {
 // launch_stream's STREAM_TOPK / STREAM_RANGE pass over the allowed positions only (masked_stream_kernel): the same grid, chain
 // arithmetic, keys and output formats; a.probe / a.list_off / a.cand_base are required.
 hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s);
+// the same walk with no mask (bits == nullptr) under MaskedArgs::rank_limit, STREAM_TOPK: the plain call's keys, a cut rank's lists EMPTY
+hipError_t launch_limited_stream(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s);
 
 // ---- inner-product search (kernels_dot.hip; pqv.h: PQV_DOT) ----------------------------------------------------------------
 // launch_stream's / launch_masked_stream's STREAM_TOPK / STREAM_RANGE pass with dist = 0.0f - s(q, x), s the 4-grouped chain over
@@ -269,6 +271,32 @@ struct ExpandSelectArgs {
     uint64_t       *n_cand;      // [nq]
 };
 hipError_t launch_expand_select(const ExpandSelectArgs &a, hipStream_t s);
+// probe_depth_kernel (pqv.h: pqv_topk_depth), one wave per query behind the probe merge: the raw depth r -- depths[q] (given), or
+// the number of ranks j < P whose probe distance d2[q * P + j] is <= the ONE f32 product ratio * d2[q * P] (a NaN on either side
+// compares false) -- clamped: nprobe_used[q] = min(max(r, p0), P).  n_cand[q] is overwritten with the summed length of those lists
+// and, with `stats`, added to the query's candidate_rows and embeddings_fetched words (the request's probe merge counts nothing).
+// pair_end[q * P + j] = ~0 below the depth and 0 from it on: the candidate end of every pair for the kernels that walk by
+// (query, rank) -- a cut rank holds no candidate.  1 <= p0 <= P.
+struct ProbeDepthArgs {
+    const uint32_t *depths;      // [nq] given depths, or nullptr: by ratio
+    const uint32_t *d2;          // [nq, P] the probe distances' bits in probe order (MergeArgs::probe_d2); ratio only
+    float           ratio;
+    const uint32_t *probe;       // [nq, P]
+    const uint64_t *cand_base;   // [nq, P]
+    const uint64_t *list_off;
+    uint32_t        nq, P, p0;
+    uint32_t       *nprobe_used; // [nq]
+    uint64_t       *n_cand;      // [nq]
+    uint64_t       *pair_end;    // [nq, P]
+    unsigned long long *stats;   // optional: the searcher's statistics block
+    uint32_t       *hist;        // optional (the tile paths' pair sort): the cluster histogram of the pairs BELOW the depths, as the
+    uint32_t        hist_stride; // probe merge fills it for a call without depths (MergeArgs::hist: HIST_REPLICAS copies, zeroed)
+};
+hipError_t launch_probe_depth(const ProbeDepthArgs &a, hipStream_t s);
+// the wide screen's seed bounds [nq][P][per_rank] of the ranks at or beyond rank_limit[q] set to +inf ("no bound": the seed kernel
+// never visits them, and what an earlier call left there must not be selected) -- for the one-query call, whose selection runs
+// inside the seed launch over all P ranks; a batch's selection reads the ranks below the limit only (launch_seed_select)
+hipError_t launch_depth_seed_clear(float *seed_ub, const uint32_t *rank_limit, uint32_t nq, uint32_t P, uint32_t per_rank, hipStream_t s);
 
 // ---- expanding distinct / grouped top-k (kernels_group_expand.hip; pqv.h: pqv_topk_distinct_expand) ------------------------
 // group_expand_kernel, one block per query: nprobe_used[q] = the smallest p in [p0, P] whose first p lists hold >= k DISTINCT group
@@ -545,6 +573,7 @@ struct MergeArgs {
     float          *qmax_out;    // max |q_i| per query (f16 screen)
     const float    *queries;
     uint32_t        dim;
+    uint32_t       *probe_d2;    // probe mode, optional [nq, k]: the probe distance's bits of every rank, beside `probe` (pqv_topk_depth)
 };
 hipError_t launch_merge_final(const MergeArgs &a, hipStream_t s);
 // deferred evaluations of a BATCH, ahead of launch_merge_final (which then gets cand_lb = nullptr): work = nq * cand_cap uint2 of scratch
@@ -631,6 +660,9 @@ struct PairSortArgs {
     uint32_t       *wide_n_items;   // [1]
     uint32_t       *wide_item_quad; // [wide_max_items]
     uint32_t        wide_max_items;
+    // optional [n_pairs / nprobe] (pqv_topk_depth): pair (q, j) with j >= rank_limit[q] is left out of the scatter, as
+    // probe_depth_kernel left it out of the histogram -- no group, quad or work item exists for a rank nobody walks
+    const uint32_t *rank_limit;
 };
 // hist -> scan -> scatter; three tiny launches
 hipError_t launch_pair_sort(const PairSortArgs &a, hipStream_t s);
@@ -794,7 +826,10 @@ hipError_t launch_seed_threshold(const uint64_t *part_keys, uint32_t nq, uint32_
 hipError_t launch_wide_seed(const TileArgs &a, hipStream_t s);
 hipError_t launch_seed_select(const float *seed_ub, uint32_t nq, uint32_t n_vals, uint32_t k, unsigned long long *gthr,
                               uint32_t *cand_cnt, uint32_t *spilled, hipStream_t s,
-                              uint32_t *thr_hist = nullptr, float4 *thr_bins = nullptr, const SeedRefine *refine = nullptr);
+                              uint32_t *thr_hist = nullptr, float4 *thr_bins = nullptr, const SeedRefine *refine = nullptr,
+                              const uint32_t *rank_limit = nullptr, uint32_t per_rank = 0);
+// (rank_limit, optional [nq] with per_rank = the bounds per probe rank, pqv_topk_depth: query q selects among the bounds of its
+//  ranks below rank_limit[q] only -- the first rank_limit[q] * per_rank of its n_vals)
 
 // ---- batched brute force as a dense Q.V^T contraction on f32 MFMA (BASELINE config 5) -------
 // score s[i][j] = q_i . v_j over ALL rows j of a row range; distance by `metric`:
@@ -1016,7 +1051,8 @@ hipError_t launch_block_rows_i8(const float *src, const uint64_t *list_off, cons
                                 float *list_radius, void *out, int *row_n2i, float *row_res, hipStream_t s, const uint32_t *row_of = nullptr);
 hipError_t launch_quantize_pairs_i8(const float *queries, const uint32_t *probe, const float *center, const float *scale, const float *half,
                                     const float *radius, uint32_t n_pairs, uint32_t nprobe, uint32_t dim, void *q_i8, int *q_n2i,
-                                    float *q_res, float *q_resu, float *pair_lb, hipStream_t s);
+                                    float *q_res, float *q_resu, float *pair_lb, hipStream_t s, const uint32_t *rank_limit = nullptr);
+// (rank_limit, with `probe`: optional [n_pairs / nprobe] -- no image for a pair at or beyond its query's limit, pqv_topk_depth)
 
 // k-means++ round with an int8 screen (kernels_build.hip: minupd_screen_kernel; index.rs:354-369): min_d[r] = min(min_d[r],
 // d2(row r, row `pick`)) in the reference's order -- but a row's exact distance is evaluated only if a rigorous lower bound

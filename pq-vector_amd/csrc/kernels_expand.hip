@@ -2,6 +2,7 @@
 // positions of each probed list pass the call's filter -- no embedding is read) and expand_select_kernel (per query: the prefix
 // sums of those counts in probe order, the first rank at which k rows have passed, the candidate total of the lists up to it).
 // masked_stream_kernel (kernels_mask.hip) then walks each query's lists below its own rank limit.
+// Also the depth stage of the plain call under per-query depths (pqv.h: pqv_topk_depth): probe_depth_kernel, depth_seed_clear_kernel.
 #include "stream_walk.hpp"
 
 namespace pqv {
@@ -123,6 +124,72 @@ hipError_t launch_expand_select(const ExpandSelectArgs &a, hipStream_t s) {
     if (a.nq == 0) return hipSuccess;
     if (a.P == 0 || a.p0 == 0 || a.p0 > a.P) return hipErrorInvalidValue;
     hipLaunchKernelGGL(expand_select_kernel, dim3(a.nq), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// probe_depth_kernel (pqv.h: pqv_topk_depth): one wave per query.  The raw depth is the caller's, or the ranks whose probe
+// distance is at most t = ratio * d2_0 -- ONE f32 multiplication (the unit is built without contraction) and an ordered <=, so a
+// NaN threshold (inf * 0) or a NaN distance counts nothing; the distances ascend, so the counted ranks are a prefix.  Clamped into
+// [p0, P].  Lane 0 writes nprobe_used[q], OVERWRITES n_cand[q] as expand_select_kernel does and counts it; the wave writes every
+// pair's candidate end (ProbeDepthArgs::pair_end) and adds the pairs below the depth to the pair sort's cluster histogram, which the
+// probe merge of such a call leaves empty.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void probe_depth_kernel(const ProbeDepthArgs a) {
+    const int lane = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    const uint64_t row = (uint64_t)q * a.P;
+    uint32_t r = 0;
+    if (a.depths) {
+        r = a.depths[q];
+    } else {
+        const float t = a.ratio * __uint_as_float(a.d2[row]);
+        for (uint32_t c0 = 0; c0 < a.P; c0 += 64) {
+            const uint32_t j = c0 + (uint32_t)lane;
+            const bool in = j < a.P && __uint_as_float(a.d2[row + (j < a.P ? j : 0u)]) <= t;
+            r += (uint32_t)__popcll(__ballot(in));
+        }
+    }
+    uint32_t used = r < a.p0 ? a.p0 : r;
+    if (used > a.P) used = a.P;
+    for (uint32_t j = (uint32_t)lane; j < a.P; j += 64) {
+        a.pair_end[row + j] = j < used ? ~0ull : 0ull;
+        if (a.hist && j < used) atomicAdd(&a.hist[(uint64_t)(q % HIST_REPLICAS) * a.hist_stride + a.probe[row + j]], 1u);
+    }
+    if (lane == 0) {
+        a.nprobe_used[q] = used;
+        const uint64_t at = row + (used - 1);
+        const uint32_t c = a.probe[at];
+        const uint64_t total = a.cand_base[at] + (a.list_off[c + 1] - a.list_off[c]);
+        a.n_cand[q] = total;
+        if (unsigned long long *st = stats_slot(a.stats, q)) {
+            atomicAdd(&st[2], (unsigned long long)total);
+            atomicAdd(&st[3], (unsigned long long)total);
+        }
+    }
+}
+
+hipError_t launch_probe_depth(const ProbeDepthArgs &a, hipStream_t s) {
+    if (!(a.depths || a.d2) || !a.probe || !a.cand_base || !a.list_off || !a.nprobe_used || !a.n_cand || !a.pair_end) return hipErrorInvalidValue;
+    if (a.nq == 0) return hipSuccess;
+    if (a.P == 0 || a.p0 == 0 || a.p0 > a.P) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(probe_depth_kernel, dim3(a.nq), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// one block per query: the seed bounds of its ranks [rank_limit[q], P) are one contiguous run of (P - limit) * per_rank floats
+__global__ __launch_bounds__(256) void depth_seed_clear_kernel(float *seed_ub, const uint32_t *rank_limit, uint32_t P, uint32_t per_rank) {
+    const uint32_t q = blockIdx.x;
+    const uint32_t lim = rank_limit[q] < P ? rank_limit[q] : P;
+    float *dst = seed_ub + ((uint64_t)q * P + lim) * per_rank;
+    const uint64_t n = (uint64_t)(P - lim) * per_rank;
+    for (uint64_t i = threadIdx.x; i < n; i += 256) dst[i] = INFINITY;
+}
+
+hipError_t launch_depth_seed_clear(float *seed_ub, const uint32_t *rank_limit, uint32_t nq, uint32_t P, uint32_t per_rank, hipStream_t s) {
+    if (!seed_ub || !rank_limit) return hipErrorInvalidValue;
+    if (nq == 0 || P == 0 || per_rank == 0) return hipSuccess;
+    hipLaunchKernelGGL(depth_seed_clear_kernel, dim3(nq), dim3(256), 0, s, seed_ub, rank_limit, P, per_rank);
     return hipGetLastError();
 }
 

@@ -122,6 +122,7 @@ template <int WIN> struct WinArgs { using type = KeyFilterArgs; };
 template <> struct WinArgs<0> { using type = MaskedArgs; };
 template <> struct WinArgs<1> { using type = KeyedArgs; };
 template <> struct WinArgs<2> { using type = KeyedArgs; };
+template <> struct WinArgs<7> { using type = MaskedArgs; };      // WIN 7: no filter at all -- every window is all ones (launch_limited_stream)
 
 template <int CG, int S, int MODE, bool SEQ, bool ALIGNED, int WIN = 0>
 __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, const typename WinArgs<WIN>::type ma) {
@@ -148,13 +149,13 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
     unsigned long long *st = stats_slot(ma.stats, q);
     stats_add_candidates(st, ma.n_cand, q, j);
 
-    KeyTest<WIN == 0 ? 0 : (WIN - 1) / 2> kt;       // WIN 1 / 2: EQ, 3 / 4: RANGE, 5 / 6: IN
+    KeyTest<(WIN == 0 || WIN == 7) ? 0 : (WIN - 1) / 2> kt;       // WIN 1 / 2: EQ, 3 / 4: RANGE, 5 / 6: IN
     if constexpr (WIN == 1 || WIN == 2) kt.lo = ma.qkeys[q];
     if constexpr (WIN == 3 || WIN == 4) {
         kt.lo = static_cast<const int64_t *>(ma.a)[q];
         kt.hi = static_cast<const int64_t *>(ma.b)[q];
     }
-    if constexpr (WIN >= 5) {
+    if constexpr (WIN == 5 || WIN == 6) {
         __shared__ int64_t set_lds[KEY_SET_MAX];
         kt.setup_in(ma.a, ma.b, q, set_lds);
         if (kt.empty()) w.r1 = w.r0;      // (nothing matches: no window is read)
@@ -169,6 +170,8 @@ __global__ __launch_bounds__(256) void masked_stream_kernel(const StreamArgs a, 
         [&](uint64_t p, uint64_t, uint64_t, uint32_t &) {
             if constexpr (WIN == 0) {
                 return image_window(ma.bits, p);
+            } else if constexpr (WIN == 7) {
+                return ~0ull;
             } else {
                 uint64_t win = kt.window(ma.key_pos, (WIN & 1) != 0, ma.valid_pos, p, lane);
                 if (ma.bits) win &= image_window(ma.bits, p);
@@ -210,6 +213,13 @@ static hipError_t launch_masked_w(const StreamArgs &a, const typename WinArgs<WI
 hipError_t launch_masked_stream(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s) {
     if (!ma.bits) return hipErrorInvalidValue;
     return launch_masked_w<0>(a, ma, mode, s);
+}
+
+// The plain walk under per-query rank limits (pqv_topk_depth on the exact stream): no mask, every position of a walked list is a
+// candidate and its key is stream_kernel's; the blocks of a rank at or beyond rank_limit[q] store empty lists and end.
+hipError_t launch_limited_stream(const StreamArgs &a, const MaskedArgs &ma, hipStream_t s) {
+    if (ma.bits || !ma.rank_limit) return hipErrorInvalidValue;
+    return launch_masked_w<7>(a, ma, STREAM_TOPK, s);
 }
 
 hipError_t launch_keyed_stream(const StreamArgs &a, const KeyedArgs &ka, StreamMode mode, hipStream_t s) {

@@ -245,17 +245,21 @@ __device__ __forceinline__ void quantize_pair_i8_wave(const PairQuantArgs &a, ui
         }
     }
 }
-__global__ __launch_bounds__(256) void quantize_pairs_i8_kernel(const PairQuantArgs a) {
+// LIMIT (pqv_topk_depth, one image per pair): no image for a pair at or beyond its query's rank limit
+template <bool LIMIT>
+__global__ __launch_bounds__(256) void quantize_pairs_i8_kernel(const PairQuantArgs a, const uint32_t *rank_limit) {
     const uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if constexpr (LIMIT) { if (p < a.n_pairs && p % a.nprobe >= rank_limit[p / a.nprobe]) return; }
     if (p < a.n_pairs) quantize_pair_i8_wave(a, p, (int)(threadIdx.x & 63));
 }
 hipError_t launch_quantize_pairs_i8(const float *queries, const uint32_t *probe, const float *center, const float *scale, const float *half,
                                     const float *radius, uint32_t n_pairs, uint32_t nprobe, uint32_t dim, void *q_i8, int *q_n2i,
-                                    float *q_res, float *q_resu, float *pair_lb, hipStream_t s) {
+                                    float *q_res, float *q_resu, float *pair_lb, hipStream_t s, const uint32_t *rank_limit) {
     if (n_pairs == 0) return hipSuccess;
     if (dim % 4 || nprobe == 0 || (probe && !pair_lb)) return hipErrorInvalidValue;
     PairQuantArgs a{queries, probe, center, scale, half, radius, n_pairs, nprobe, dim, static_cast<int8_t *>(q_i8), q_n2i, q_res, q_resu, pair_lb};
-    hipLaunchKernelGGL(quantize_pairs_i8_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, s, a);
+    if (rank_limit && probe) hipLaunchKernelGGL(quantize_pairs_i8_kernel<true>, dim3((n_pairs + 3) / 4), dim3(256), 0, s, a, rank_limit);
+    else hipLaunchKernelGGL(quantize_pairs_i8_kernel<false>, dim3((n_pairs + 3) / 4), dim3(256), 0, s, a, nullptr);
     return hipGetLastError();
 }
 
@@ -328,6 +332,7 @@ __device__ __forceinline__ void probe_merge_tail(const MergeArgs &a, uint32_t q,
         if (e < a.k) {
             a.probe[(uint64_t)q * a.k + e] = c;
             a.cand_base[(uint64_t)q * a.k + e] = carry + incl - len;
+            if (a.probe_d2) a.probe_d2[(uint64_t)q * a.k + e] = have ? (uint32_t)(tk.key[s] >> 32) : 0x7FC00000u;
             if (a.hist && have && !a.sq_quads) atomicAdd(&a.hist[(uint64_t)(q % HIST_REPLICAS) * a.hist_stride + c], 1u);   // pair bucketing: cluster histogram
         }
         if (a.sq_quads && s == 0) {          // single query (q == 0, a.k <= 64): quad e = pair e = probe rank e
@@ -1330,9 +1335,13 @@ __global__ __launch_bounds__(1024) void pair_scan_kernel(const PairSortArgs a) {
     }
 }
 
+// LIMIT (pqv_topk_depth): a pair at or beyond its query's rank limit takes no part (PairSortArgs::rank_limit; the histogram
+// was filled below the limits, by probe_depth_kernel); the <false> instance is the code of a call without limits.
+template <bool LIMIT>
 __global__ __launch_bounds__(256) void pair_scatter_kernel(const PairSortArgs a) {
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
     if (p >= a.n_pairs) return;
+    if constexpr (LIMIT) { if (p % a.nprobe >= a.rank_limit[p / a.nprobe]) return; }
     const uint32_t c = a.probe[p];
     const uint32_t i = atomicAdd(&a.cursor[(uint64_t)(a.hist_stride ? (p / a.nprobe) % HIST_REPLICAS : 0u) * a.hist_stride + c], 1u);
     const uint32_t slot = a.pair_off[c] + i;
@@ -1369,9 +1378,15 @@ __global__ __launch_bounds__(256) void pair_scatter_kernel(const PairSortArgs a)
 hipError_t launch_pair_sort(const PairSortArgs &a, hipStream_t s) {
     if (a.n_pairs == 0) return hipSuccess;
     const uint32_t blocks = (a.n_pairs + 255) / 256;
+    if (a.rank_limit) {
+        if (!a.hist_done || a.nprobe == 0) return hipErrorInvalidValue;     // (the histogram below the limits: probe_depth_kernel's)
+        hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL(pair_scatter_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
     if (!a.hist_done) hipLaunchKernelGGL(pair_hist_kernel, dim3(blocks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(pair_scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pair_scatter_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

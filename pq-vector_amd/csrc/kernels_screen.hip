@@ -1180,6 +1180,18 @@ __global__ __launch_bounds__(256) void seed_select_kernel(const float *seed_ub, 
                                                         uint32_t *thr_hist, float4 *thr_bins, const SeedRefine rf) {
     seed_select_body<S>(blockIdx.x, seed_ub, n_vals, k, gthr, cand_cnt, spilled, thr_hist, thr_bins, rf);
 }
+// the same selection over the ranks below the query's limit only (pqv_topk_depth): a query's bounds are rank-major, so its first
+// rank_limit[q] * per_rank values are those of the ranks it walks -- what lies behind them (an earlier call's) is never read
+template <int S>
+__global__ __launch_bounds__(256) void seed_select_limit_kernel(const float *seed_ub, uint32_t n_vals, const uint32_t *rank_limit, uint32_t per_rank,
+                                                              uint32_t k, unsigned long long *gthr, uint32_t *cand_cnt, uint32_t *spilled,
+                                                              uint32_t *thr_hist, float4 *thr_bins, const SeedRefine rf) {
+    const uint32_t q = blockIdx.x;
+    const uint64_t n_lim = (uint64_t)rank_limit[q] * per_rank;
+    const uint32_t n_q = n_lim < n_vals ? (uint32_t)n_lim : n_vals;
+    // (the body reads seed_ub[q * n + idx]: the base is moved so that this is the query's row of n_vals values)
+    seed_select_body<S>(q, seed_ub + (uint64_t)q * (n_vals - n_q), n_q, k, gthr, cand_cnt, spilled, thr_hist, thr_bins, rf);
+}
 // QLDS forms: a one-query call (seed_tail) takes the deep-prefetch instance and tells the tail how much dynamic LDS it has
 #define SEED_LAUNCH(NG_, OP_, GRID_, LDS_)                                                                              \
     {                                                                                                                   \
@@ -1234,11 +1246,18 @@ hipError_t launch_wide_seed(const TileArgs &a, hipStream_t s) {
 #undef SEED_LAUNCH
 hipError_t launch_seed_select(const float *seed_ub, uint32_t nq, uint32_t n_vals, uint32_t k, unsigned long long *gthr,
                               uint32_t *cand_cnt, uint32_t *spilled, hipStream_t s,
-                              uint32_t *thr_hist, float4 *thr_bins, const SeedRefine *refine) {
+                              uint32_t *thr_hist, float4 *thr_bins, const SeedRefine *refine, const uint32_t *rank_limit, uint32_t per_rank) {
     if (nq == 0) return hipSuccess;
     SeedRefine rf{};
     if (refine && refine->mat && (refine->dim % 32) == 0 && k <= 16) rf = *refine;
     const dim3 block(rf.mat ? 256 : 64);
+    if (rank_limit) {
+        if (per_rank == 0 || n_vals % per_rank) return hipErrorInvalidValue;
+        if (k <= 64) hipLaunchKernelGGL(seed_select_limit_kernel<1>, dim3(nq), block, 0, s, seed_ub, n_vals, rank_limit, per_rank, k, gthr, cand_cnt, spilled, thr_hist, thr_bins, rf);
+        else if (k <= 256) hipLaunchKernelGGL(seed_select_limit_kernel<4>, dim3(nq), dim3(256), 0, s, seed_ub, n_vals, rank_limit, per_rank, k, gthr, cand_cnt, spilled, thr_hist, thr_bins, rf);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     if (k <= 64) hipLaunchKernelGGL(seed_select_kernel<1>, dim3(nq), block, 0, s, seed_ub, n_vals, k, gthr, cand_cnt, spilled, thr_hist, thr_bins, rf);
     else if (k <= 256) hipLaunchKernelGGL(seed_select_kernel<4>, dim3(nq), dim3(256), 0, s, seed_ub, n_vals, k, gthr, cand_cnt, spilled, thr_hist, thr_bins, rf);
     else return hipErrorInvalidValue;
