@@ -6,14 +6,17 @@ import numpy as np
 
 import distinct_filter_ref
 from key_filter_ref import EQ, RANGE
+from mutated_cases import is_depth
 
 METRIC = {"l2": 0, "cos": 2, "dot": 4}
-GROUPS = ["plain", "range", "metrics", "masks", "keys", "expand", "distinct"]
+GROUPS = ["plain", "range", "metrics", "masks", "keys", "expand", "distinct", "depth"]
 
 
 def group_of(sp):
     if sp["call"].startswith(("distinct", "grouped")):
         return "distinct"
+    if is_depth(sp):          # (a depth spec carries maxp too)
+        return "depth"
     if sp["maxp"]:
         return "expand"
     if sp["metric"] != "l2":
@@ -90,7 +93,14 @@ def run(H, sp, mask=None):
     if call.endswith("_device"):
         return _run_device(H, sp, Q, mask)
     keys, fkw = _filter_kw(H, sp, nq)
-    if call == "topk":
+    if call == "topk" and is_depth(sp):
+        # a uniform call at nprobe = P first, on the same searcher and stream: the scratch of the ranks a query does not walk then
+        # holds valid-looking entries (tests/test_gpu_depth.py)
+        s.topk(Q, k, sp["maxp"], metric=metric, sqrt_out=False)
+        dkw = dict(probe_depths=sp["depths"]) if sp["depths"] is not None else dict(d2_ratio=sp["ratio"])
+        out = s.topk(Q, k, sp["nprobe"], metric=metric, sqrt_out=sp["sqrt"], max_nprobe=sp["maxp"], **dkw)
+        names = ["rows", "d", "nf", "nc", "used"]
+    elif call == "topk":
         out = s.topk(Q, k, sp["nprobe"], max_candidates=sp["maxc"], metric=metric, sqrt_out=sp["sqrt"], mask=mask, keys=keys, max_nprobe=sp["maxp"], **fkw)
         names = ["rows", "d", "nf", "nc", "used"]
     elif call == "range":
@@ -129,6 +139,18 @@ def _run_device(H, sp, Q, mask):
         kw = dict(mask=mask, max_candidates=sp["maxc"], metric=METRIC[sp["metric"]], sqrt_out=False, stream=side.cuda_stream, **fkw)
         if sp["maxp"]:
             kw.update(max_nprobe=sp["maxp"], d_nprobe_used=u_t.data_ptr())
+        if is_depth(sp):
+            # (the uniform call at nprobe = P first, as in run(); its outputs go to buffers of their own)
+            p_r, p_d = torch.empty_like(r_t), torch.empty_like(d_t)
+            s.topk_device(q_t.data_ptr(), nq, k, sp["maxp"], p_r.data_ptr(), p_d.data_ptr(), metric=METRIC[sp["metric"]], sqrt_out=False,
+                          stream=side.cuda_stream)
+            if sp["depths"] is not None:          # the depths uploaded on the side stream, alive until the synchronise
+                dep_t = torch.from_numpy(np.ascontiguousarray(sp["depths"], dtype=np.uint32).view(np.int32).copy()).to(dev, non_blocking=True)
+                alive = alive + (dep_t, p_r, p_d)
+                kw["probe_depths"] = dep_t.data_ptr()
+            else:
+                alive = alive + (p_r, p_d)
+                kw["d2_ratio"] = sp["ratio"]
         if call == "topk_device":
             s.topk_device(q_t.data_ptr(), nq, k, sp["nprobe"], r_t.data_ptr(), d_t.data_ptr(), nf_t.data_ptr(), nc_t.data_ptr(), keys=keys, **kw)
         elif grouped:

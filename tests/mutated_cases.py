@@ -21,13 +21,14 @@ allowed rows depends on where it lies).  32 queries, most of them beside a corpu
 centroid of the emptied list, query 1 a copy of a removed row.
 
 expect(model, spec) is the numpy answer of one call, put together from the references the project has: the oracle's top-k and
-candidate order, range_oracle, cosine_ref, dot_ref, mask_ref, key_filter_ref, expand_ref, distinct_ref, grouped_ref,
+candidate order, range_oracle, cosine_ref, dot_ref, mask_ref, key_filter_ref, expand_ref, depth_ref, distinct_ref, grouped_ref,
 distinct_filter_ref and distinct_expand_ref."""
 import numpy as np
 
 import append_ref
 import assign_exact  # noqa: F401  (append_ref's assignment: the exact nearest centroid)
 import cosine_ref
+import depth_ref
 import distinct_expand_ref
 import distinct_filter_ref
 import distinct_ref
@@ -223,12 +224,27 @@ def case(oracle, name):
 # A spec names one call: call (topk | topk_device | range | distinct | grouped | distinct_device | grouped_device), k, nprobe,
 # metric (l2 | cos | dot), mask (a mask's name, or a bool array over the rows), filt (a filter's name), maxc (max_candidates), maxr (max_results), maxp (max_nprobe),
 # nq (the first nq queries), q160 (the 160-query batch), radius (filled in by expect()).
+# A DEPTH spec (pqv_topk_depth: the plain call under per-query probe depths) carries maxp and one of depths (uint32 [nq], the given
+# depths) and ratio (a float, or RESOLVE until resolve() fills it in per state: ratio_for).
+RESOLVE = "to be resolved"
+
+
+def is_depth(sp):
+    return sp.get("depths") is not None or sp.get("ratio") is not None
+
+
 def spec(call, **kw):
-    s = dict(call=call, k=K, nprobe=NPROBE, metric="l2", mask=None, filt=None, maxc=0, maxr=0, maxp=None, nq=None, q160=False, m=M)
+    s = dict(call=call, k=K, nprobe=NPROBE, metric="l2", mask=None, filt=None, maxc=0, maxr=0, maxp=None, nq=None, q160=False, m=M,
+             depths=None, ratio=None)
     s.update(kw)
+    if is_depth(s):
+        assert s["maxp"] and (s["depths"] is None or s["ratio"] is None) and s["mask"] is None and not s["filt"] and not s["maxc"]
+        assert call in ("topk", "topk_device")
     # pqv_topk as the reference runs it: sqrt_out, whose final stable sort is by sqrt(d2) -- two d2 that round to one sqrt keep
-    # the heap's order (the oracle's topk_batch); every other call returns d2 (cosine / dot: the output distance)
-    s["sqrt"] = call == "topk" and s["metric"] == "l2" and not (s["mask"] is not None or s["filt"] or s["maxc"] is None or s["maxc"] or s["maxp"])
+    # the heap's order (the oracle's topk_batch); every other call returns d2 (cosine / dot: the output distance).  A depth call
+    # follows the plain call: query q's answer is the uniform call's at nprobe_used[q] (pqv.h)
+    s["sqrt"] = call == "topk" and s["metric"] == "l2" and not (s["mask"] is not None or s["filt"] or s["maxc"] is None or s["maxc"]
+                                                                 or (s["maxp"] and not is_depth(s)))
     return s
 
 
@@ -282,6 +298,37 @@ def radius_for(oracle, model, sp, Q):
                        cuts_all=SHAPES[model.case.name].get("radius_cuts_all", True))
 
 
+def _depth_probe(oracle, model, sp):
+    """what a depth call's probe ranks: the metric's oracle index and the queries as it sees them (cosine: both normalised, as
+    depth_ref.cosine_index_and_queries makes them)"""
+    Q = model.case.queries(sp)
+    return model.oidx(oracle, sp["metric"]), (cosine_ref.normalise(Q) if sp["metric"] == "cos" else Q)
+
+
+def ratio_for(oracle, model, sp):
+    """the d2_ratio of a RATIO depth spec: the float32 median, over the queries with d2_0 > 0, of d2_[(p0 + P) // 2] / d2_0 -- half
+    of those queries then reach the middle rank and half do not (the distances come from depth_ref.probe_d2 on the oracle)"""
+    oidx, Q = _depth_probe(oracle, model, sp)
+    kc = int(oidx.n_clusters)
+    p0, P = min(sp["nprobe"], kc), min(sp["maxp"], kc)
+    assert p0 < P
+    d2 = np.stack([depth_ref.probe_d2(oracle, oidx, q, P) for q in Q])
+    ok = d2[:, 0] > 0
+    assert ok.any() and d2.dtype == np.float32
+    return float(np.float32(np.median(d2[ok, (p0 + P) // 2] / d2[ok, 0])))
+
+
+def depth_used(oracle, model, sp):
+    """uint32 [nq]: nprobe_used of a depth spec, from tests/depth_ref.py"""
+    oidx, Q = _depth_probe(oracle, model, sp)
+    if sp["depths"] is not None:
+        assert len(sp["depths"]) == len(Q)
+        return depth_ref.used_given(sp["depths"], sp["nprobe"], sp["maxp"], int(oidx.n_clusters))
+    if not isinstance(sp["ratio"], float):
+        raise ValueError("a ratio depth spec needs its ratio (resolve)")
+    return depth_ref.used_ratio(oracle, oidx, Q, sp["ratio"], sp["nprobe"], sp["maxp"])
+
+
 def _pad(rows, d, k):
     r = np.full(k, EMPTY, np.uint32)
     o = np.full(k, np.inf, np.float32)
@@ -315,9 +362,19 @@ def expect(oracle, model, sp):
     # the host forms of top-k follow the reference's heap where distances tie (pqv.h: the masked, keyed and expanding forms replay it
     # over the considered rows in arrival order); everything else orders by (d2, position)
     heap = call == "topk" and metric == "l2"
-    plain_heap = heap and allow is None and not sp["maxp"] and not sp["maxc"]
+    depth = is_depth(sp)
+    plain_heap = heap and allow is None and (depth or not sp["maxp"]) and not sp["maxc"]
     assert plain_heap == bool(sp["sqrt"])
-    if plain_heap:
+    used_q = depth_used(oracle, model, sp) if depth else None
+    if plain_heap and depth:
+        # the host form "replays flagged queries through the reference heap over the query's first nprobe_used[q] lists": the
+        # oracle's top-k at each distinct depth u, for the queries whose depth is u
+        hrows, hdist = np.full((nq, k), EMPTY, np.uint32), np.full((nq, k), np.inf, np.float32)
+        hnf, hnc = np.zeros(nq, np.uint32), np.zeros(nq, np.uint64)
+        for u in sorted(set(used_q.tolist())):
+            sel = used_q == u
+            hrows[sel], hdist[sel], hnf[sel], hnc[sel] = model.oidx(oracle).topk_batch(X, Q[sel], k, u)
+    elif plain_heap:
         hrows, hdist, hnf, hnc = model.oidx(oracle).topk_batch(X, Q, k, sp["nprobe"])
     lims = [0]
     for q in range(nq):
@@ -335,7 +392,10 @@ def expect(oracle, model, sp):
             continue
         oidx = model.oidx(oracle, metric)
         used = sp["nprobe"]
-        if sp["maxp"]:
+        if depth:
+            used = int(used_q[q])
+            put("used", q, used)
+        elif sp["maxp"]:
             if group is None:
                 used = expand_ref.nprobe_used(oidx, model.lists, a_q, qv, k, sp["nprobe"], sp["maxp"])
             else:
@@ -419,8 +479,14 @@ def same(got, want, skip=(), what=""):
 
 
 # ---- the calls every (case, state) is held to ---------------------------------------------------------------------------------------
+def given_depths(nq, p0, P):
+    """the given depths of a batch: below, at and above the floor p0 and the ceiling P, cycled (query 0 gets 0)"""
+    vals = [0, 1, p0, (p0 + P) // 2, P, P + 1, 2 ** 32 - 1, p0 + 1]
+    return np.array([vals[i % len(vals)] for i in range(nq)], np.uint32)
+
+
 def modes(case_name):
-    """name -> spec: what tests/test_gpu_mutated_search.py runs on every state of a case (int8_256: plain, cosine, masked and distinct)"""
+    """name -> spec: what tests/test_gpu_mutated_search.py runs on every state of a case (int8_256: plain, per-query depths, cosine, masked and distinct)"""
     sh = SHAPES[case_name]
     nf, mp = sh["nprobe_f"], sh["max_nprobe"]
     full = case_name != "int8_256"
@@ -450,6 +516,24 @@ def modes(case_name):
         m["topk_160"] = spec("topk", q160=True)
         m["topk_device_160"] = spec("topk_device", q160=True)
         m["topk_masked_160"] = spec("topk", q160=True, mask="dense")
+    # per-query probe depths (plain calls: int8_256 has them all).  Given: the cycle of `given_depths` -- query 0, the emptied
+    # list's centroid, gets 0 and so walks nprobe_f lists --; ratio: ratio_for, filled in by resolve()
+    dkw = dict(nprobe=nf, maxp=mp)
+    m["depth_given"] = spec("topk", depths=given_depths(32, nf, mp), **dkw)
+    m["depth_given_device"] = spec("topk_device", depths=given_depths(32, nf, mp), **dkw)
+    m["depth_ratio"] = spec("topk", ratio=RESOLVE, **dkw)
+    m["depth_ratio_device"] = spec("topk_device", ratio=RESOLVE, **dkw)
+    m["depth_ratio_k1"] = spec("topk", k=1, ratio=RESOLVE, **dkw)
+    # k above one list's rows: the answer of a query at depth 1 is every candidate
+    m["depth_given_device_k1000"] = spec("topk_device", k=1000, nprobe=1, maxp=2, depths=np.array([1, 2] * 16, np.uint32))
+    # one query: the uniform call is the fused probe with its own bucketing, the depth call goes through the general pair sort
+    m["depth_given_device_nq1"] = spec("topk_device", nq=1, depths=np.array([(nf + mp) // 2], np.uint32), **dkw)
+    if not sh["integer"]:          # (the host cosine form: as topk_cosine above)
+        m["depth_ratio_cosine"] = spec("topk", metric="cos", ratio=RESOLVE, **dkw)
+    m["depth_ratio_device_cosine"] = spec("topk_device", metric="cos", ratio=RESOLVE, **dkw)
+    if case_name == "screened":
+        m["depth_ratio_160"] = spec("topk", q160=True, ratio=RESOLVE, **dkw)
+        m["depth_given_device_160"] = spec("topk_device", q160=True, depths=given_depths(160, nf, mp), **dkw)
     if not full:
         return m
     m["range"] = spec("range")
@@ -487,8 +571,11 @@ def modes(case_name):
 
 
 def resolve(oracle, model, sp):
-    """a spec with what depends on the state filled in: the cap "at" the candidate count, a range call's radius"""
+    """a spec with what depends on the state filled in: the cap "at" the candidate count, a range call's radius, a ratio depth
+    call's ratio"""
     sp = dict(sp)
+    if sp["ratio"] == RESOLVE:
+        sp["ratio"] = ratio_for(oracle, model, sp)
     if sp["maxc"] is None:
         sp["maxc"] = len(model.oidx(oracle, sp["metric"]).candidate_rows(
             cosine_ref.normalise(model.case.Q[0]) if sp["metric"] == "cos" else model.case.Q[0], sp["nprobe"]))

@@ -50,7 +50,8 @@ def test_the_shapes(far):
     for s in mc.STATES:
         assert sum(len(l) for l in c.models[s].lists) // c.kc >= 192, s
     specs = mc.modes(far.name)
-    groups = {g: [n for n, sp in specs.items() if _group(sp) == g] for g in ("plain", "masks", "metrics", "keys", "expand", "distinct", "range")}
+    groups = {g: [n for n, sp in specs.items() if _group(sp) == g] for g in ("plain", "masks", "metrics", "keys", "expand", "distinct", "range", "depth")}
+    assert set(groups) == set(_groups())
     assert all(groups.values())
     if far.name == "far768":
         assert {"dot", "dot_device", "dot_range", "dot_masked", "dot_range_masked"} <= set(specs)
@@ -60,6 +61,24 @@ def test_the_shapes(far):
 def _group(sp):
     import mode_calls
     return mode_calls.group_of(sp)
+
+
+def _groups():
+    import mode_calls
+    return mode_calls.GROUPS
+
+
+def test_the_depth_draws_are_not_vacuous(far, oracle):
+    """the premises of the per-query depth modes (tests/test_mutated_cases_host.py), on the states the far tests search"""
+    from test_mutated_cases_host import depth_premises
+    depth_premises(oracle, far.case, mc.STATES)
+    dense = far.case.models["chained"]
+    for name in ("depth_ratio_device", "depth_given_device"):
+        e = mc.expect(oracle, dense, mc.resolve(oracle, dense, mc.modes(far.name)[name]))
+        moved = far.relocate(e)
+        found = e["rows"] != mc.EMPTY
+        assert (moved["rows"][found] == far.R[e["rows"][found].astype(np.int64)]).all() and (moved["rows"][~found] == mc.EMPTY).all()
+        assert (moved["used"] == e["used"]).all() and (moved["rows"][found] > far.breaks[-1]).any()
 
 
 @pytest.mark.parametrize("state", STATES)

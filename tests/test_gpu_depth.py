@@ -4,7 +4,9 @@ topk_device(..., d_nprobe_used=); TopkBuilder.d2_ratio).
 The yardstick is never the code under test.  nprobe_used comes from tests/depth_ref.py (numpy over the ORACLE's probe order and its
 l2_ref4).  For each distinct expected depth u ONE existing uniform call runs on the whole batch at nprobe = u, and the queries whose
 expected depth is u must equal it byte for byte: rows, distance bits, n_found, tie flags, n_candidates.  Host form, device form,
-device form with tie flags.
+device form with tie flags.  The screened centroid probe by plan_topk's default rule is held to the oracle's topk_batch per
+distinct depth instead, and so is every depth mode of tests/mutated_cases.py on mutated indexes, under the forced screen, at far
+rows and under every searcher option (test_gpu_mutated_search.py, test_gpu_probe_screen_modes.py, test_gpu_far_rows.py).
 
 Every depth call is preceded by a uniform call at nprobe = P on the same searcher and stream: the scratch slots of the ranks beyond
 a query's depth then hold valid-looking entries of the same shape, and a kernel that reads them gives a wrong answer.
@@ -262,12 +264,188 @@ def test_one_query(f16, i8, shape):
         check(st, 10, 1, 8, ratio=RATIO[shape], queries=st.queries[qi:qi + 1], what=f"one query ratio, expected {u}")
 
 
+def test_one_query_whose_cut_ranks_hold_nearer_seed_rows(pqv, oracle):
+    """One query selects its first threshold inside the seed launch, over the bounds of all P ranks: those of the ranks it does not
+    walk must read "none" (launch_depth_seed_clear).  The query's nearest list is cut down to its 12 FARTHEST rows -- fewer than
+    the seed sample, so the true k-th distance is among the sampled bounds -- and the rows taken out head the second list: after the
+    uniform call at nprobe = P the scratch holds bounds of k nearer rows at a rank the depth call cuts."""
+    d = shape_data(oracle, **F16)
+    k, P, q = 10, 8, d["queries"][:1]
+    order = depth_ref.probe_order(d["oidx"], q[0], P)
+    c0, c1 = int(order[0]), int(order[1])
+    mine = np.asarray(d["lists"][c0], np.int64)
+    by_d = mine[np.argsort(((d["data"][mine].astype(np.float64) - q[0]) ** 2).sum(axis=1))]
+    far, near = by_d[-12:], by_d[:-12]
+    lists = [np.asarray(l, np.uint32) for l in d["lists"]]
+    lists[c0] = np.sort(far).astype(np.uint32)
+    lists[c1] = np.concatenate([near.astype(np.uint32), lists[c1]])
+    d2 = lambda rows: ((d["data"][np.asarray(rows, np.int64)].astype(np.float64) - q[0]) ** 2).sum(axis=1)       # noqa: E731
+    assert len(near) >= 64 and np.sort(d2(lists[c1][:64]))[k - 1] < 0.8 * d2(far).min()          # premise: k nearer rows in the cut rank's sample
+    st = Dep.__new__(Dep)
+    st.pqv, st.oracle, st.kc, st.data, st.lists, st.dim, st.n, st.queries = pqv, oracle, len(lists), d["data"], lists, d["dim"], d["n"], q
+    cents = np.asarray(d["oidx"].centroids, np.float32).reshape(-1, d["dim"])
+    st.oidx = oracle.index_from_parts(d["dim"], cents, lists)
+    st.corpus = pqv.Corpus.upload(d["data"])
+    st.s = pqv.Searcher(pqv.Index.from_parts(d["dim"], cents, lists), st.corpus)
+    assert "wide_filter_kernel" in st.s.describe(1, k, P)
+    _, host = check(st, k, 1, P, depths=np.array([1], np.uint32), premise=lambda u: u[0] == 1, what="one query, short nearest list, given")
+    want = st.oidx.topk_batch(d["data"], q, k, 1)
+    assert host[2][0] == k == want[2][0] and host[3][0] == 12 and sorted(host[0][0].tolist()) == sorted(want[0][0].tolist())
+    check(st, k, 1, P, ratio=1.0, premise=lambda u: u[0] == 1, what="one query, short nearest list, ratio 1")
+    st.s.close()
+
+
 def test_beyond_one_chunk_of_64_ranks(pqv, oracle):
     st = Dep(pqv, oracle, 4096, 32, 200, 77)
     depths = np.array([0, 1, 4, 63, 64, 65, 100, 128, 129, 149, 150, 151, 1000, 2 ** 32 - 1, 70, 5], np.uint32)
     check(st, 20, 4, 150, depths=depths, premise=lambda u: (u < 64).any() and (u > 64).any() and (u > 128).any() and (u == 150).any(), what="200 lists")
     check(st, 20, 4, 150, ratio=RATIO["far"], premise=lambda u: _mixed(u) and (u > 64).any() and (u < 64).any(), what="200 lists ratio")
     check(st, 20, 4, 1000, ratio=INF, premise=lambda u: (u == 200).all(), what="200 lists, every list")
+    st.s.close()
+
+
+# ---- the screened centroid probe by the DEFAULT rule, two probe blocks --------------------------------------------------------------
+SCREENED = "probe_screen_kernel + probe_resolve_kernel"
+# ratio: the median of d2_40 / d2_0 over the draw's queries, from the reference on the CPU -- 8 queries stay at p0, 92 end below rank
+# 64, 18 between 64 and 80, 17 at 80
+RULE = dict(n=4096, dim=32, kc=320, nq=128, seed=320, k=10, p0=2, P=80, ratio=1.578)
+
+
+def rule_data(oracle):
+    """320 centroids (two probe blocks of 256; P = 80 = kc / 4, 128 queries: plan_topk's own rule takes the screen), no GPU: uniform
+    rows, 320 of them the centroids, the lists by the f64 nearest centroid; three of four queries beside a row, the fourth uniform,
+    query 0 IS a centroid."""
+    if "rule" not in _SHAPES:
+        n, dim, kc, nq = RULE["n"], RULE["dim"], RULE["kc"], RULE["nq"]
+        rng = np.random.default_rng(RULE["seed"])
+        data = rng.random((n, dim), dtype=np.float32)
+        cents = np.ascontiguousarray(data[np.sort(rng.choice(n, kc, replace=False))])
+        x, c = data.astype(np.float64), cents.astype(np.float64)
+        owner = ((x * x).sum(1)[:, None] - 2.0 * (x @ c.T) + (c * c).sum(1)[None, :]).argmin(axis=1)
+        lists = [np.flatnonzero(owner == j).astype(np.uint32) for j in range(kc)]
+        queries = rng.random((nq, dim), dtype=np.float32)
+        for i in range(nq):
+            if i % 4 != 3:
+                queries[i] = data[(37 * i) % n] + np.float32(0.05) * (rng.random(dim, dtype=np.float32) - np.float32(0.5))
+        queries[0] = cents[kc // 2]
+        _SHAPES["rule"] = dict(n=n, dim=dim, data=data, queries=np.ascontiguousarray(queries), cents=cents, lists=lists,
+                               oidx=oracle.index_from_parts(dim, cents, lists))
+    return _SHAPES["rule"]
+
+
+def _oracle_answer(d, used, k):
+    """the oracle's topk_batch (the heap, sqrt_out) at each distinct depth u for the queries whose depth is u, padded as the library pads"""
+    nq = len(used)
+    rows, dist = np.full((nq, k), 0xFFFFFFFF, np.uint32), np.full((nq, k), np.inf, np.float32)
+    nf, nc = np.zeros(nq, np.uint32), np.zeros(nq, np.uint64)
+    for u in sorted(set(used.tolist())):
+        for q in np.flatnonzero(used == u):
+            r, x, f, c = d["oidx"].topk_batch(d["data"], d["queries"][q:q + 1], k, u)
+            rows[q, :f[0]], dist[q, :f[0]], nf[q], nc[q] = r[0, :f[0]], x[0, :f[0]], f[0], c[0]
+    return rows, dist, nf, nc
+
+
+@pytest.mark.parametrize("kind", ["given", "ratio"])
+def test_screened_probe_by_the_default_rule(pqv, oracle, monkeypatch, kind):
+    """No set_option and no PQV_PROBE_SCREEN: 128 queries, 320 centroids and P = kc / 4 take the screened probe by plan_topk's own
+    rule (two probe blocks), and the probe merge behind it hands out the ranks' d2 (MergeArgs::probe_d2).  nprobe_used from
+    depth_ref; rows, distance bits, n_found and n_candidates from the oracle's topk_batch per distinct depth; a second searcher
+    at probe_screen = 0 agrees byte for byte."""
+    monkeypatch.delenv("PQV_PROBE_SCREEN", raising=False)
+    d = rule_data(oracle)
+    nq, k, p0, P, kc = RULE["nq"], RULE["k"], RULE["p0"], RULE["P"], RULE["kc"]
+    q = d["queries"]
+    assert P == kc // 4 and kc > 256 and min(len(l) for l in d["lists"]) < k
+    if kind == "given":
+        vals = [0, 1, 2, 3, 40, 63, 64, 65, 79, 80, 81, 1000, 2 ** 32 - 1, 70, 5, 64]
+        depths, ratio = np.array([vals[i % len(vals)] for i in range(nq)], np.uint32), None
+        used = depth_ref.used_given(depths, p0, P, kc)
+        assert {2, 3, 63, 64, 65, 79, 80} <= set(used.tolist())
+    else:
+        depths, ratio = None, RULE["ratio"]
+        used = depth_ref.used_ratio(oracle, d["oidx"], q, ratio, p0, P)
+        at = [int((used == p0).sum()), int((used < 64).sum()), int(((used > 64) & (used < P)).sum()), int((used == P).sum())]
+        assert at[0] >= 4 and at[1] >= 32 and at[2] >= 8 and at[3] >= 8 and used[0] == p0, (at, used.tolist())
+    want = _oracle_answer(d, used, k)
+    assert (want[2] < k).any() and (want[2] == k).any()
+    corpus = pqv.Corpus.upload(d["data"])
+    dkw = dict(probe_depths=depths) if depths is not None else dict(d2_ratio=ratio)
+    got = []
+    for option in (None, 0):
+        s = pqv.Searcher(pqv.Index.from_parts(d["dim"], d["cents"], d["lists"]), corpus)
+        if option is not None:
+            s.set_option("probe_screen", option)
+        plan = s.describe(nq, k, P)
+        assert (SCREENED in plan) == (option is None), plan
+        what = f"default rule {kind} probe_screen={option}"
+        s.topk(q, k, P, sqrt_out=False)                                                   # poison the lane's scratch
+        host = s.topk(q, k, p0, max_nprobe=P, **dkw)
+        assert (host[4] == used).all(), f"host nprobe_used {host[4].tolist()}, expected {used.tolist()}: {what}"
+        _same(host, want, slice(None), what + ": host form against the oracle")
+        _device(s, q, k, P, False)                                                        # poison
+        dev = _device(s, q, k, p0, False, max_nprobe=P, depths=depths, ratio=ratio)
+        assert (dev[5] == used).all() and (dev[3] == want[3]).all() and (dev[2] == want[2]).all(), what + ": device form"
+        got.append((host, dev))
+        s.close()
+    for a, b in zip(got[0], got[1]):
+        for x, y in zip(a, b):
+            assert (x is None and y is None) or (np.asarray(x).view(np.uint8) == np.asarray(y).view(np.uint8)).all()
+    corpus.close()
+
+
+# ---- 2 to 7 queries: the per-query stream probe (probe_rows is off below 8 queries), then the general pair sort ------------------------
+@pytest.mark.parametrize("nq", [2, 7])
+@pytest.mark.parametrize("shape", ["f16", "i8"])
+def test_small_batches(f16, i8, shape, nq):
+    st = f16 if shape == "f16" else i8
+    p0, P = 2, 8
+    plan = st.s.describe(nq, 10, P)
+    assert "centroid probe: stream_kernel" in plan and "probe_rows_kernel" not in plan and "wide_filter_kernel" in plan, plan
+    few = lambda u: len(set(u.tolist())) >= min(nq, 3)                                     # noqa: E731
+    depths = np.array([1, 5, 8, 9, 3, 2 ** 32 - 1, 0][:nq], np.uint32)
+    check(st, 10, p0, P, depths=depths, premise=few, queries=st.queries[:nq], what=f"{nq} queries given")
+    # the ratio draw: the queries ordered so that the first ones have depths of their own
+    us = expected(st, p0, P, ratio=RATIO[shape], queries=st.queries).tolist()
+    order = [us.index(u) for u in sorted(set(us))]
+    order += [i for i in range(NQ) if i not in order]
+    check(st, 10, p0, P, ratio=RATIO[shape], premise=few, queries=np.ascontiguousarray(st.queries[order[:nq]]), what=f"{nq} queries ratio")
+
+
+# ---- clamping to the lists there are ----------------------------------------------------------------------------------------------------
+def test_depths_clamp_to_the_lists(pqv, oracle):
+    st = Dep(pqv, oracle, 4096, 32, 200, 77)
+    every = lambda u: (u == 200).all()                                                     # noqa: E731
+    # nprobe above the lists: floor and ceiling are both the 200 lists
+    check(st, 20, 300, 1000, depths=given_depths(NQ, 300, 1000), premise=every, what="nprobe > kc, given")
+    check(st, 20, 300, 1000, ratio=1.0, premise=every, what="nprobe > kc, ratio")
+    # max_nprobe == kc + 1: the ceiling is kc, a given depth of kc + 1 or 2^32 - 1 walks every list
+    depths = np.array([(199, 200, 201, 2 ** 32 - 1, 0, 64)[i % 6] for i in range(NQ)], np.uint32)
+    check(st, 20, 4, 201, depths=depths, premise=lambda u: set(u.tolist()) == {4, 64, 199, 200}, what="max_nprobe == kc + 1, given")
+    check(st, 20, 4, 201, ratio=INF, premise=every, what="max_nprobe == kc + 1, ratio inf")
+    st.s.close()
+
+
+# ---- the rule on special values -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("screen", [None, 0])
+def test_ratio_on_nan_and_overflowing_queries(pqv, oracle, screen):
+    """an all-NaN query: every comparison is false, so it walks p0 lists; a query of 1e30 components: every d2 is +inf and so is
+    t, so it walks all P.  nprobe_used from depth_ref, n_candidates the summed lengths of the lists, rows and distances the
+    uniform call's.  probe_screen at its default and at 0."""
+    st = Dep(pqv, oracle, **F16)
+    if screen is not None:
+        st.s.set_option("probe_screen", screen)
+    p0, P = 2, 8
+    q = st.queries.copy()
+    q[5], q[10] = np.nan, np.float32(1e30)
+    d2 = depth_ref.probe_d2(oracle, st.oidx, q[10], P)
+    assert np.isinf(d2).all() and np.isnan(depth_ref.probe_d2(oracle, st.oidx, q[5], P)).all()
+    u, host = check(st, 10, p0, P, ratio=RATIO["f16"], premise=lambda u: u[5] == p0 and u[10] == P and _mixed(np.delete(u, [5, 10])),
+                    queries=q, what=f"special values probe_screen={screen}")
+    lens = np.array([len(l) for l in st.lists], np.uint64)
+    for i in (5, 10):                          # (all distances equal, NaN or +inf: the probe order (d2, id) is by centroid id)
+        assert depth_ref.probe_order(st.oidx, q[i], P).tolist() == list(range(P))
+    for i in range(NQ):
+        assert host[3][i] == lens[depth_ref.probe_order(st.oidx, q[i], int(u[i]))].sum(), i
     st.s.close()
 
 

@@ -206,7 +206,8 @@ def test_row_masks_keep_the_callers_bytes_and_count_list_rows(zoo, pqv, name, st
 
 
 # ---- layouts and creation flags -----------------------------------------------------------------------------------------------------------
-LAYOUT_MODES = ["topk", "topk_device", "topk_cosine", "topk_device_cosine", "topk_masked", "distinct", "keyed_eq", "range", "expand_masked"]
+LAYOUT_MODES = ["topk", "topk_device", "topk_cosine", "topk_device_cosine", "topk_masked", "distinct", "keyed_eq", "range", "expand_masked",
+                "depth_ratio", "depth_given_device", "depth_ratio_device_cosine"]
 
 
 @pytest.mark.parametrize("layout", ["row_order", "prepare_cosine", "release_row_order"])
@@ -252,18 +253,20 @@ def test_removed_answers_under_every_searcher_option(zoo, pqv, option, value):
         s.set_option(option, value)
     h = Handles(pqv, model, s, masks=("dense",))
     try:
-        for mode in ("topk", "topk_device", "topk_160", "topk_masked", "topk_device_masked", "topk_masked_160"):
+        for mode in ("topk", "topk_device", "topk_160", "topk_masked", "topk_device_masked", "topk_masked_160", "depth_given_device", "depth_ratio",
+                     "depth_ratio_160"):
             mc.same(run(h, z.modes("removed")[mode]), z.expect("removed", mode), what=f"{option}={value} {mode}")
     finally:
         h.close()
 
 
 # ---- relation 1: removed == appended under row_mask(~flags) ----------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,group", CASE_GROUPS)
+@pytest.mark.parametrize("name,group", [(n, g) for n, g in CASE_GROUPS if g != "depth"])
 def test_removed_equals_appended_under_the_keep_mask(zoo, name, group):
     """... n_candidates excepted; a filter on the removed side is the same filter combined with the mask on the old side.  With
     max_candidates the two differ by contract (the cap counts candidate positions, and the removed rows hold positions of the old
-    lists only); so do pqv_topk's heap order and the masked call's (d2, position) order where distances tie."""
+    lists only); so do pqv_topk's heap order and the masked call's (d2, position) order where distances tie.  The `depth` group has
+    no part in this relation: pqv_topk_depth takes no mask, and every call on the old side is made under the keep mask."""
     z = zoo(name)
     assert np.array_equal(z.under.masks[None].to_bytes(), z.keep.astype(np.uint8))
     compared = 0

@@ -1,6 +1,6 @@
 """Every search mode under the screened centroid probe (probe_screen_kernel + probe_resolve_kernel).  enqueue_probe sits
-behind every entry point -- plain, capped, masked, keyed (EQ / IN / RANGE), expanding, distinct, grouped, their device forms, range
-and cosine -- and each hands it another request (an expanding call ranks max_nprobe lists, cosine goes through the lazily made inner
+behind every entry point -- plain, capped, per-query depths (whose ratio rule reads the probe distances the merge hands out: MergeArgs::
+probe_d2), masked, keyed (EQ / IN / RANGE), expanding, distinct, grouped, their device forms, range and cosine -- and each hands it another request (an expanding call ranks max_nprobe lists, cosine goes through the lazily made inner
 searcher, which copies the options) and other scratch to zero on the way.
 
 The shape `probe32` of tests/mutated_cases.py has 32 centroids and no depth above 8 = kc / 4, so the screen is eligible in every call
@@ -66,7 +66,7 @@ def pairs(pqv, oracle):
 def test_the_shape_keeps_every_depth_eligible():
     sh = mc.SHAPES[NAME]
     specs = mc.modes(NAME)
-    assert len(specs) == 69 and not any(sp["metric"] == "dot" for sp in specs.values())
+    assert len(specs) == 78 and not any(sp["metric"] == "dot" for sp in specs.values())
     assert {sp["maxp"] or sp["nprobe"] for sp in specs.values()} == {1, 2, 4, 8} and sh["max_nprobe"] == 8 == sh["kc"] // 4
     assert {group_of(sp) for sp in specs.values()} == set(GROUPS)
     assert NAME not in mc.CASES

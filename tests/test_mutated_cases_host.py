@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import append_ref
+import depth_ref
 import distinct_expand_ref
 import expand_ref
 import mutated_cases as mc
@@ -80,6 +81,79 @@ def test_the_distinct_depths_differ_too(case, oracle, state):
                                                   case.max_nprobe)
         assert (used == case.nprobe_f).any() and ((used > case.nprobe_f) & (used < case.max_nprobe)).any() and (used == case.max_nprobe).any(), used
         assert (mc.expect(oracle, model, sp)["used"] == used).all()
+
+
+def depth_premises(oracle, case, states):
+    """The per-query depth modes of one case are not vacuous, on the REFERENCE's depths alone (tests/depth_ref.py over the oracle):
+    the ratio draw has at least three distinct depths, the floor p0 among them and, for L2, the ceiling P; query 0 -- the emptied
+    list's centroid, d2_0 == 0 -- counts one rank and walks p0 lists, so that in the states where that list is empty it gets
+    nothing (p0 == 1) or its second list alone (p0 == 2)."""
+    p0, P = case.nprobe_f, case.max_nprobe
+    modes = mc.modes(case.name)
+    assert 1 <= p0 <= 2 and p0 + 1 < P <= case.kc
+    for state in states:
+        model = case.models[state]
+        for name, metric in (("depth_ratio_device", "l2"), ("depth_ratio_device_cosine", "cos")):
+            sp = mc.resolve(oracle, model, modes[name])
+            assert sp["metric"] == metric and (sp["nprobe"], sp["maxp"]) == (p0, P) and isinstance(sp["ratio"], float) and sp["ratio"] > 1
+            used = mc.depth_used(oracle, model, sp)
+            depths = set(used.tolist())
+            print(f"{case.name} {state} {metric}: p0 {p0} P {P} ratio {sp['ratio']:.4f} at p0 {int((used == p0).sum())} at P {int((used == P).sum())} "
+                  f"distinct {len(depths)}")
+            assert len(depths) >= 3 and p0 in depths and (metric != "l2" or P in depths), (name, state, used)
+            for other in [n for n, o in modes.items() if o["ratio"] is not None and o["metric"] == metric and not o["q160"]]:
+                assert mc.resolve(oracle, model, modes[other])["ratio"] == sp["ratio"], other          # (one draw per metric)
+        # query 0 under L2
+        sp = mc.resolve(oracle, model, modes["depth_ratio_device"])
+        oidx = model.oidx(oracle)
+        d2 = depth_ref.probe_d2(oracle, oidx, case.Q[0], P)
+        assert d2[0] == 0 and depth_ref.ratio_count(d2, sp["ratio"]) == 1 and mc.depth_used(oracle, model, sp)[0] == p0
+        assert int(depth_ref.probe_order(oidx, case.Q[0], P)[0]) == case.emptied
+        given = modes["depth_given_device"]
+        assert given["depths"][0] == 0 and mc.depth_used(oracle, model, given)[0] == p0
+        assert {p0, (p0 + P) // 2, P} <= set(mc.depth_used(oracle, model, given).tolist()) and{0, P + 1, 2 ** 32 - 1} <= set(given["depths"].tolist())
+        if state in EMPTY_STATES:
+            second = len(model.lists[int(depth_ref.probe_order(oidx, case.Q[0], 2)[1])])
+            for name in ("depth_ratio", "depth_ratio_device", "depth_given", "depth_given_device"):
+                e = mc.expect(oracle, model, mc.resolve(oracle, model, modes[name]))
+                assert e["used"][0] == p0
+                if p0 == 1:
+                    assert e["nf"][0] == 0 and e["nc"][0] == 0 and (e["rows"][0] == mc.EMPTY).all(), (name, state)
+                else:
+                    assert e["nc"][0] == second > 0 and e["nf"][0] == min(mc.K, second), (name, state)
+                assert (e["nf"][1:] > 0).any() and len(set(e["nc"].tolist())) > 3
+
+
+def test_the_depth_draws_are_not_vacuous(case, oracle):
+    depth_premises(oracle, case, mc.STATES)
+    # the depths depend on the centroids alone: one draw for all five states
+    for name in ("depth_ratio", "depth_ratio_cosine", "depth_given_device"):
+        if name in mc.modes(case.name):
+            used = [mc.depth_used(oracle, case.models[s], mc.resolve(oracle, case.models[s], mc.modes(case.name)[name])) for s in mc.STATES]
+            assert all((u == used[0]).all() for u in used)
+
+
+def test_the_depth_modes(oracle):
+    """which depth modes a case has: all of them on int8_256, the host cosine form off the integer cases, the 160-query batch on
+    `screened` alone; k = 1000 is above one list's rows, so a query at depth 1 gets every candidate"""
+    names = {"depth_given", "depth_given_device", "depth_ratio", "depth_ratio_device", "depth_ratio_k1", "depth_given_device_k1000",
+             "depth_given_device_nq1", "depth_ratio_cosine", "depth_ratio_device_cosine"}
+    for case_name in mc.CASES + ["probe32", "far768", "far768i"]:
+        have = {n for n, sp in mc.modes(case_name).items() if mc.is_depth(sp)}
+        want = names - ({"depth_ratio_cosine"} if mc.SHAPES[case_name]["integer"] else set())
+        if case_name == "screened":
+            want |= {"depth_ratio_160", "depth_given_device_160"}
+        assert have == want, case_name
+        for n in have:
+            sp = mc.modes(case_name)[n]
+            assert sp["sqrt"] == (sp["call"] == "topk" and sp["metric"] == "l2") and sp["maxp"] > sp["nprobe"], n
+    case = mc.case(oracle, "screened")
+    for state in mc.MUTATED:
+        model = case.models[state]
+        e = mc.expect(oracle, model, mc.modes("screened")["depth_given_device_k1000"])
+        assert e["used"].tolist() == [1, 2] * 16
+        short = (e["used"] == 1) & (e["nc"] < 1000)
+        assert short.sum() >= 8 and (e["nf"][short] == e["nc"][short]).all() and (e["nc"][e["used"] == 2] > 1000).any(), (e["used"], e["nc"])
 
 
 def test_masks_allow_removed_rows_and_keys_match_them(case):
