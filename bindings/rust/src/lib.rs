@@ -620,6 +620,49 @@ impl<'c> Searcher<'c> {
         Ok((0..nq).map(|q| dist[lims[q] as usize..lims[q + 1] as usize].to_vec()).collect())
     }
 
+    /// MMR top-k: the `fetch_k` nearest rows of the probed lists (within `mask` if one is given), then `k` of them picked greedily by
+    /// `lambda * distance - (1 - lambda) * distance to the nearest pick so far`, smallest first; the results come in pick order
+    /// (`include/pqv.h`: `pqv_topk_mmr`).
+    pub fn topk_mmr(&self, mask: Option<&RowMask>, queries: &[f32], dim: usize, k: NonZeroUsize, fetch_k: NonZeroUsize, lambda: f32,
+                    nprobe: NonZeroUsize) -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let k = k.get();
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_mmr(self.raw, mask.map_or(ptr::null(), |m| m.raw as *const _), queries.as_ptr(), nq as u32, dim as u32, k as u32,
+                              fetch_k.get() as u32, lambda, nprobe.get() as u32, 0, sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(),
+                              dist.as_mut_ptr(), ptr::null_mut(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
+    /// The MMR selection alone over `candidates[q]`, the results of any top-k call of this searcher (all of one length), in pick
+    /// order (`include/pqv.h`: `pqv_mmr_select`).
+    pub fn mmr_select(&self, candidates: &[Vec<SearchResult>], k: NonZeroUsize, lambda: f32) -> Result<Vec<Vec<SearchResult>>> {
+        let nq = candidates.len();
+        let n = candidates.first().map_or(0, |c| c.len());
+        if candidates.iter().any(|c| c.len() != n) {
+            return Err("mmr_select needs candidate lists of one length".into());
+        }
+        let k = k.get();
+        let cand: Vec<u32> = candidates.iter().flat_map(|c| c.iter().map(|r| r.row_idx)).collect();
+        let rel: Vec<f32> = candidates.iter().flat_map(|c| c.iter().map(|r| r.distance)).collect();
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_mmr_select(self.raw, cand.as_ptr(), rel.as_ptr(), ptr::null(), nq as u32, n as u32, k as u32, lambda,
+                                sys::PQV_L2SQ_REF4, 1, rows.as_mut_ptr(), dist.as_mut_ptr(), ptr::null_mut(), found.as_mut_ptr())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
     /// Every row of `part` whose key passes the query's filter within `radius` of the query -- exact, nothing is probed, ascending by
     /// (distance, sequence position); `max_results > 0` keeps the first `max_results` of each query (`include/pqv.h`:
     /// `pqv_range_search_partition`).

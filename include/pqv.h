@@ -1002,6 +1002,69 @@ int pqv_score_rows(const pqv_searcher *searcher, const uint64_t *lims, const uin
 int pqv_score_rows_device(const pqv_searcher *searcher, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
                           const void *d_queries, uint32_t nq, int metric, int sqrt_out, void *d_dist, void *hip_stream);
 
+/* MMR top-k: diversity by geometry -- fetch the fetch_k nearest rows, then pick k of them by maximal marginal relevance, so that
+ * five paraphrases of one passage do not fill a context window.  The rows are resident: the pairwise distances are taken on the
+ * device by the metric's own chain, nothing crosses the bus but the picks.
+ *
+ * pqv_mmr_select / pqv_mmr_select_device: the selection stage alone, over candidates the caller has -- the [nq, n] row_idx / dist
+ * outputs of ANY top-k call (keyed, partition, candidate list, expanding, per-query depth) and optionally its n_found: no queries,
+ * no probing.  pqv_topk_mmr / pqv_topk_mmr_device: probe + the fetch_k nearest (under `mask` where one is given) + selection.
+ *   notation     one query has n candidates at positions 0 .. n-1 with rows r_i and rel_i, their distances to the query as f32 on the
+ *                call's output scale (d2, sqrt(d2) with sqrt_out, 0.5f * d2 of the normalised vectors for PQV_COSINE, 0.0f - s for
+ *                PQV_DOT).  lambda in [0, 1]; om = 1.0f - lambda, one f32 subtraction.
+ *   considered   a candidate whose row is in one of the searcher's lists (below the corpus' row count, not 0xFFFFFFFF, not removed:
+ *                pqv_topk_rows' rule) and whose position is below n_found_in[q] (NULL: n).  A candidate that is not considered is
+ *                never loaded and never picked.  A row listed twice is two candidates.
+ *   pd(a, b)     the metric's chain with row a in the query's place and row b as the row, put on the output scale exactly as a
+ *                query distance is: PQV_L2SQ_REF4 / PQV_L2SQ_SEQ d2, or correctly rounded sqrtf(d2) with sqrt_out; PQV_COSINE the
+ *                REF4 chain over the cosine layout's normalised rows, times 0.5f; PQV_DOT 0.0f - s(a, b).
+ *   selection    step t = 0, 1, ... with S_t the candidates picked so far: red_t[i] = +0.0f while S_t is empty, else the f32 minimum
+ *                over s in S_t of pd(r_s, r_i) -- a running minimum that starts at +inf with the first pick and takes a value only
+ *                where it compares smaller, so a NaN pd leaves it as it is (the fminf rule; pd is never -0).  score_t[i] =
+ *                (lambda * rel_i) - (om * red_t[i]): two f32 products and one f32 subtraction, each rounded on its own, no FMA.
+ *                The pick is the considered, not yet picked candidate with the smallest (ord(score_t[i]), i), ord() as for PQV_DOT
+ *                on the score's bits: a total order, NaN and +-0 included, the lowest position winning a tie.  Selection ends after
+ *                min(k, considered) picks; that count is n_found[q].
+ *   outputs      in PICK order, not by distance: row_idx[q, j] the j-th pick's row, dist[q, j] its rel bit for bit, score[q, j] its
+ *                score_t at the time of the pick; past n_found 0xFFFFFFFF / +inf / +inf.  score and n_found may be NULL.
+ *   lambda       1: om is +0.0f and for finite rel the picks are the first k considered candidates by (ord(rel), i) -- with
+ *                candidates in ascending rel, the input order.  The first pick is always the considered candidate with the smallest
+ *                (ord(lambda * rel), i).
+ *   stage 1      of pqv_topk_mmr*: exactly pqv_topk_device with k = fetch_k, or pqv_topk_masked_device where mask is not NULL, on
+ *                whatever route the searcher's dispatch picks, the screened kernels included; its result is in (d2, position) order
+ *                -- in both forms no reference heap is replayed and there are no tie flags -- and stays in the call's scratch lane,
+ *                the selection running over it on the same stream.  n_candidates is stage 1's.  The fused call equals
+ *                pqv_mmr_select_device over the outputs of that stage-1 call, bit for bit.
+ *   exactness    no searcher option changes a result.
+ *   counts       as for the stage-1 call of the same shape; pqv_mmr_select* advances queries by nq.  The selection itself moves
+ *                kernel_launches only.
+ *   limits       n, fetch_k <= 1024 and at most 1024 probed lists per query (PQV_ERR_UNSUPPORTED): there is no host fallback.
+ *                PQV_DOT keeps its own limits.  The device forms are asynchronous on hip_stream (NULL: the searcher's stream) with
+ *                no host synchronisation -- except the first call on a searcher that needs the row map (pqv_topk_rows: row map),
+ *                and the first cosine call.  Every access stays in bounds whatever cand_rows holds: a row id indexes the map only
+ *                behind a compare against its length.
+ *   work         (picks - 1) x considered row reads per query, served from the caches behind the first pass.
+ *   out of scope table searchers; keyed, distinct and grouped stage 1 inside the fused call (pqv_mmr_select* takes their outputs);
+ *                n above 1024; a screened redundancy pass.
+ * Errors, in this order, all before any device use (PQV_ERR_INVALID unless noted): "searcher must not be NULL", "k must be > 0",
+ * fused: "fetch_k must be >= k" (n < k is fine for the selection: fewer picks), "lambda must be in [0, 1]" (a NaN too),
+ * PQV_ERR_UNSUPPORTED "pqv_topk_mmr takes fetch_k <= 1024" / "pqv_mmr_select takes n <= 1024", "row mask belongs to another
+ * searcher", PQV_ERR_UNSUPPORTED "pqv_topk_mmr does not take table searchers" / "pqv_mmr_select does not take table searchers",
+ * pqv_topk's own nprobe and metric texts, PQV_DOT's limits, PQV_ERR_UNSUPPORTED "pqv_topk_mmr takes min(nprobe, n_clusters) <= 1024",
+ * the query-length text, then the NULL pointers ("cand_rows/cand_dist must not be NULL", "row_idx/dist must not be NULL"). */
+int pqv_mmr_select(const pqv_searcher *searcher, const uint32_t *cand_rows /* [nq, n] */, const float *cand_dist /* [nq, n] */,
+                   const uint32_t *n_found_in /* [nq], may be NULL: n for every query */, uint32_t nq, uint32_t n, uint32_t k,
+                   float lambda, int metric, int sqrt_out, uint32_t *row_idx, float *dist, float *score, uint32_t *n_found);
+int pqv_mmr_select_device(const pqv_searcher *searcher, const void *d_cand_rows, const void *d_cand_dist, const void *d_n_found_in,
+                          uint32_t nq, uint32_t n, uint32_t k, float lambda, int metric, int sqrt_out, void *d_row_idx, void *d_dist,
+                          void *d_score, void *d_n_found, void *hip_stream);
+int pqv_topk_mmr(const pqv_searcher *searcher, const pqv_row_mask *mask /* may be NULL */, const float *queries, uint32_t nq,
+                 uint32_t query_len, uint32_t k, uint32_t fetch_k, float lambda, uint32_t nprobe, uint64_t max_candidates, int metric,
+                 int sqrt_out, uint32_t *row_idx, float *dist, float *score, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_mmr_device(const pqv_searcher *searcher, const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k,
+                        uint32_t fetch_k, float lambda, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                        void *d_row_idx, void *d_dist, void *d_score, void *d_n_found, void *d_n_candidates, void *hip_stream);
+
 /* Distinct top-k: the nearest row of each of the k nearest GROUPS -- `SELECT DISTINCT ON (doc_id) .. ORDER BY array_distance(col, q)
  * LIMIT k` over chunked embeddings (several rows per document, product, user); elsewhere called grouping or collapse.
  *

@@ -31,6 +31,8 @@ Host-side mirror of the reference's Rust API over the C ABI of include/pqv.h:
       tenant, nothing probed)                  tenant's own rows) / range_search_partition (every row of the tenant within a radius)
     WHERE id IN (rows another engine named,  Searcher.topk_rows(queries, k, candidates) (the exact top-k among exactly those rows, a list per
       per query: hybrid retrieval)             query) / score_rows (every candidate's exact distance); topk_rows_device / score_rows_device
+    (no counterpart: MMR, k diverse rows     Searcher.topk_mmr(queries, k, fetch_k, nprobe, lambda_) / TopkBuilder(...).mmr(fetch_k, lambda_);
+      out of the fetch_k nearest)              Searcher.mmr_select(rows, dist, k) over any call's [nq, n] result; the _device forms
     (no counterpart: rows that arrive after  corpus.append(batch); index = index.append(corpus) -> a new Index, same centroids, every
       the build; indexing under a given        list extended (no k-means); Index.assign(corpus, first_row, n_rows);
       codebook)                                IndexBuilder(source).with_centroids(index_or_array).build()

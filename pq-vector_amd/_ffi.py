@@ -215,6 +215,12 @@ SIGNATURES = {
     "pqv_topk_rows_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "pqv_score_rows": (C.c_int, [vp, u64p, u32p, vp, f32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, f32p]),
     "pqv_score_rows_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp]),
+    "pqv_mmr_select": (C.c_int, [vp, u32p, f32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_int, u32p, f32p, f32p, u32p]),
+    "pqv_mmr_select_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "pqv_topk_mmr": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                               u32p, f32p, f32p, u32p, u64p]),
+    "pqv_topk_mmr_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                      vp, vp, vp, vp, vp, vp]),
     "pqv_range_search_filtered": (C.c_int, [vp, vp, C.POINTER(KeyFilter), vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64,
                                             C.c_uint64, C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_topk_distinct": (C.c_int, [vp, vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,

@@ -1207,6 +1207,70 @@ class Searcher:
                                                 _mask_handle(self, mask) if mask is not None else None, vp(d_queries or None), nq, metric,
                                                 1 if sqrt_out else 0, vp(d_dist or None), vp(stream or None)))
 
+    def topk_mmr(self, queries, k, fetch_k, nprobe, lambda_=0.5, mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """MMR top-k: the fetch_k nearest rows of the probed lists (within mask if one is given), then k of them picked greedily by
+        (lambda_ * distance) - ((1 - lambda_) * distance to the nearest row picked so far), smallest first -- lambda_ = 1 is the plain
+        top-k, smaller values trade relevance for diversity (pqv.h: pqv_topk_mmr).  Returns (row_idx [nq,k] u32, dist [nq,k] f32,
+        score [nq,k] f32, n_found [nq], n_candidates [nq]) in PICK order."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        rows = np.full((nq, max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        score = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        nf = np.zeros(nq, dtype=np.uint32)
+        nc = np.zeros(nq, dtype=np.uint64)
+        _check(_ffi.lib().pqv_topk_mmr(self._h, _mask_handle(self, mask) if mask is not None else None, q.ctypes.data_as(f32p), nq, qlen, k,
+                                       fetch_k, float(lambda_), nprobe, max_candidates, metric, 1 if sqrt_out else 0, rows.ctypes.data_as(u32p),
+                                       dist.ctypes.data_as(f32p), score.ctypes.data_as(f32p), nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p)))
+        return rows, dist, score, nf, nc
+
+    def mmr_select(self, rows, dist, k, lambda_=0.5, n_found=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """The MMR selection alone over candidates the caller has: rows u32 [nq, n] and dist f32 [nq, n], the outputs of ANY top-k
+        call of this searcher with the same metric and sqrt_out, and optionally its n_found [nq] (pqv.h: pqv_mmr_select).  Returns
+        (row_idx [nq,k] u32, dist [nq,k] f32, score [nq,k] f32, n_found [nq]) in PICK order."""
+        cand = np.ascontiguousarray(rows, dtype=np.uint32)
+        rel = _f32(dist)
+        if cand.ndim == 1:
+            cand = cand.reshape(1, -1)
+        if rel.ndim == 1:
+            rel = rel.reshape(1, -1)
+        if cand.ndim != 2 or cand.shape != rel.shape:
+            raise PqvError(_ffi.PQV_ERR_INVALID, f"mmr_select needs rows and dist of one [nq, n] shape, got {cand.shape} and {rel.shape}")
+        nq, n = cand.shape
+        nf_in = None
+        if n_found is not None:
+            nf_in = np.ascontiguousarray(n_found, dtype=np.uint32).reshape(-1)
+            if nf_in.shape[0] != nq:
+                raise PqvError(_ffi.PQV_ERR_INVALID, f"mmr_select needs n_found of length {nq}, got {nf_in.shape[0]}")
+        out_rows = np.full((nq, max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        out_dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        score = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        nf = np.zeros(nq, dtype=np.uint32)
+        _check(_ffi.lib().pqv_mmr_select(self._h, cand.ctypes.data_as(u32p), rel.ctypes.data_as(f32p),
+                                         nf_in.ctypes.data_as(u32p) if nf_in is not None else None, nq, n, k, float(lambda_), metric,
+                                         1 if sqrt_out else 0, out_rows.ctypes.data_as(u32p), out_dist.ctypes.data_as(f32p),
+                                         score.ctypes.data_as(f32p), nf.ctypes.data_as(u32p)))
+        return out_rows, out_dist, score, nf
+
+    def topk_mmr_device(self, d_queries, nq, k, fetch_k, nprobe, d_row_idx, d_dist, d_score=0, d_n_found=0, d_n_candidates=0, lambda_=0.5,
+                        mask=None, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of topk_mmr, shaped like topk_device: asynchronous on `stream` (pqv.h: pqv_topk_mmr_device).  The first
+        call on a searcher that needs its row map builds it and waits for it."""
+        _check(_ffi.lib().pqv_topk_mmr_device(self._h, _mask_handle(self, mask) if mask is not None else None, vp(d_queries or None), nq, k,
+                                              fetch_k, float(lambda_), nprobe, max_candidates, metric, 1 if sqrt_out else 0,
+                                              vp(d_row_idx or None), vp(d_dist or None), vp(d_score or None), vp(d_n_found or None),
+                                              vp(d_n_candidates or None), vp(stream or None)))
+
+    def mmr_select_device(self, d_cand_rows, d_cand_dist, nq, n, k, d_row_idx, d_dist, d_score=0, d_n_found=0, d_n_found_in=0, lambda_=0.5,
+                          metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0):
+        """Device-pointer form of mmr_select: d_cand_rows u32 / d_cand_dist f32 [nq, n] and the optional d_n_found_in u32 [nq] are read
+        on `stream` inside the enqueued work (pqv.h: pqv_mmr_select_device)."""
+        _check(_ffi.lib().pqv_mmr_select_device(self._h, vp(d_cand_rows or None), vp(d_cand_dist or None), vp(d_n_found_in or None), nq, n, k,
+                                                float(lambda_), metric, 1 if sqrt_out else 0, vp(d_row_idx or None), vp(d_dist or None),
+                                                vp(d_score or None), vp(d_n_found or None), vp(stream or None)))
+
     def topk_partition_grouped(self, queries, k, group_size, part, keys, query_keys=None, query_key_ranges=None, query_key_sets=None,
                                mask=None, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
         """Exact grouped top-k over the rows of `part` whose key passes the query's filter (the keywords of topk_partition): up
@@ -1853,6 +1917,29 @@ class TopkBuilder:
         self._group_size = None
         self._max_nprobe = None
         self._d2_ratio = None
+        self._mmr = None
+
+    def mmr(self, fetch_k, lambda_=0.5):
+        """Diversify the result: fetch the fetch_k (>= k) nearest rows, then pick k of them by maximal marginal relevance with weight
+        lambda_ in [0, 1] on the distance to the query (pqv.h: pqv_topk_mmr).  search() returns the picks in pick order.  Composes
+        with where() and metric(); not with distinct_on(), max_nprobe() or d2_ratio(): diversify their results with
+        Searcher.mmr_select."""
+        if fetch_k == 0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "fetch_k must be > 0")
+        if not 0.0 <= lambda_ <= 1.0:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "lambda must be in [0, 1]")
+        self._mmr = (fetch_k, float(lambda_))
+        return self
+
+    def _check_mmr(self):
+        if self._mmr is None:
+            return
+        if self._distinct is not None:
+            raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "mmr() does not combine with distinct_on(): pick among a distinct call's rows with "
+                                                     "Searcher.mmr_select (pqv.h: pqv_mmr_select)")
+        if self._max_nprobe is not None or self._d2_ratio is not None:
+            raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "mmr() does not combine with max_nprobe() or d2_ratio(): pick among their rows with "
+                                                     "Searcher.mmr_select (pqv.h: pqv_mmr_select)")
 
     def max_nprobe(self, n):
         """With where(): keep probing, up to n lists, until k rows pass the filter (pqv.h: pqv_topk_expand); nprobe() stays the
@@ -1959,6 +2046,7 @@ class TopkBuilder:
         if self._nprobe is None:
             raise PqvError(_ffi.PQV_ERR_INVALID, "nprobe must be set")
         self._check_grouping()
+        self._check_mmr()
         if self._d2_ratio is not None:
             if self._max_nprobe is None:
                 raise PqvError(_ffi.PQV_ERR_INVALID, "probe_depths / d2_ratio need max_nprobe")
@@ -1979,7 +2067,15 @@ class TopkBuilder:
                 if owned:
                     mask.close()
             return [DistinctSearchResult(r, d, g) for r, d, g in zip(rows.tolist(), dist.tolist(), grp.tolist())]
-        if self._where is not None:
+        if self._mmr is not None:
+            mask, owned = _resolve_where(self._where, self._path, self._searcher) if self._where is not None else (None, False)
+            try:
+                rows, dist, _, nf, _ = self._searcher.topk_mmr(_f32(self._query).reshape(1, -1), self._k, self._mmr[0], self._nprobe,
+                                                               lambda_=self._mmr[1], mask=mask, metric=self._metric)
+            finally:
+                if owned:
+                    mask.close()
+        elif self._where is not None:
             mask, owned = _resolve_where(self._where, self._path, self._searcher)
             try:
                 rows, dist, nf = self._searcher.topk(_f32(self._query).reshape(1, -1), self._k, self._nprobe, metric=self._metric,
@@ -2310,6 +2406,8 @@ class TableTopkBuilder(TopkBuilder):
         self._check_grouping()
         if self._max_nprobe is not None:
             raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "pqv_topk_expand does not take table searchers")
+        if self._mmr is not None:
+            raise PqvError(_ffi.PQV_ERR_UNSUPPORTED, "pqv_topk_mmr does not take table searchers")
         s = searcher_for_parquet_files(self._paths, self._device, round_robin_cap=self._max_candidates > 0)
         if self._distinct is not None:
             mask = _resolve_table_where(self._where, self._paths, s) if self._where is not None else None

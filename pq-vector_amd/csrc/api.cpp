@@ -361,7 +361,8 @@ struct Scratch {
         s_depths, s_depth_d2, s_depth_end,  // pqv_topk_depth: a host call's given depths u32 [b]; the probe distances' bits u32 [nq][P]; the pairs' candidate ends u64 [nq][P]
         s_ps_q16, s_ps_qn2, s_ps_score, // screened probe: the batch's query images f16 [nq][dim_p], |q - mean|^2 [nq], the scores f32 [nq][kc_pad]
         s_seg_off,                      // pqv_range_search_partition: the group's packed segment offsets u64 [b]
-        s_pt_beg, s_pt_end, s_pt_nspan; // pqv_topk_partition: the spans' first entries u32 [nq] (IN: [nq][1024]), IN: their prefix sums and counts
+        s_pt_beg, s_pt_end, s_pt_nspan, // pqv_topk_partition: the spans' first entries u32 [nq] (IN: [nq][1024]), IN: their prefix sums and counts
+        s_mmr_rows, s_mmr_dist, s_mmr_nf;   // pqv_topk_mmr: stage 1's rows u32 / distances f32 [nq][fetch_k] and n_found u32 [nq]; pqv_mmr_select's host form: the candidates
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
     hipStream_t stream = nullptr;   // the stream of that call
@@ -377,7 +378,8 @@ struct Scratch {
                 &s_hit_cnt, &s_hit_keys, &s_hit_vals, &s_alt_keys, &s_alt_vals, &s_rsegs, &s_rout_off, &s_rout_rows, &s_rout_dist,
                 &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
                 &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out,
-                &s_expand_cnt, &s_expand_used, &s_depths, &s_depth_d2, &s_depth_end, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_seg_off, &s_pt_beg, &s_pt_end, &s_pt_nspan};
+                &s_expand_cnt, &s_expand_used, &s_depths, &s_depth_d2, &s_depth_end, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_seg_off, &s_pt_beg, &s_pt_end, &s_pt_nspan,
+                &s_mmr_rows, &s_mmr_dist, &s_mmr_nf};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -6906,6 +6908,219 @@ extern "C" int pqv_score_rows(const pqv_searcher *s, const uint64_t *lims, const
                                            bs->stream));
                 return static_cast<int>(PQV_OK);
             });
+    });
+}
+
+// ---- MMR selection (pqv.h: pqv_mmr_select, pqv_topk_mmr) ---------------------------------------------------------------------------
+// One kernel (mmr_select_kernel) over [nq, n] candidates: the caller's (pqv_mmr_select*), or stage 1's in the lane
+// (pqv_topk_mmr*: enqueue_topk with k = fetch_k, a mask as pqv_topk_masked carries it, then the selection on the same stream).
+// The checks of the four entry points, in the contract's order, all before any device use.  n: the candidates per query (fetch_k);
+// fused: pqv_topk_mmr*, which probes; host: the form that takes its queries from the host.
+static int mmr_checks(const pqv_searcher *s, const pqv_row_mask *mask, uint32_t k, uint32_t n, float lambda, bool fused, uint32_t nprobe,
+                      int metric, bool host, uint32_t query_len) {
+    const char *who = fused ? "pqv_topk_mmr" : "pqv_mmr_select";
+    if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
+    if (k == 0) return fail(PQV_ERR_INVALID, "k must be > 0");
+    if (fused && n < k) return fail(PQV_ERR_INVALID, "fetch_k must be >= k");
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(PQV_ERR_INVALID, "lambda must be in [0, 1]");
+    if (n > 1024) return fail(PQV_ERR_UNSUPPORTED, fused ? "pqv_topk_mmr takes fetch_k <= 1024" : "pqv_mmr_select takes n <= 1024");
+    if (mask && (mask->owner != s || mask->owner_uid != s->uid)) return fail(PQV_ERR_INVALID, "row mask belongs to another searcher");
+    if (s->n_files) return fail(PQV_ERR_UNSUPPORTED, std::string(who) + " does not take table searchers");
+    if (int rc = validate_topk(s, k, fused ? nprobe : 1, metric)) return rc;
+    if (fused) {
+        if (int rc = dot_checks(s, n, nprobe, metric, nullptr)) return rc;
+        if (beyond_kernel_lists(s, n, nprobe)) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_mmr takes min(nprobe, n_clusters) <= 1024");
+    }
+    if (host && query_len != s->dim)
+        return fail(PQV_ERR_INVALID, "Query dimension mismatch: expected " + std::to_string(s->dim) + ", got " + std::to_string(query_len));
+    return PQV_OK;
+}
+// a selection's device arrays: the candidates [nq, n] (nf_in: optional [nq]) and the picks [nq, k] (score, nf: optional)
+struct MmrIo {
+    const uint32_t *rows; const float *dist; const uint32_t *nf_in;
+    uint32_t *o_rows; float *o_dist; float *o_score; uint32_t *o_nf;
+};
+// the selection launch over the rows of `s` (the call's searcher, or its cosine searcher with sqrt_out 2)
+static int enqueue_mmr(const pqv_searcher *s, const RowMap &map, const MmrIo &io, uint32_t nq, uint32_t n, uint32_t k, float lambda, int metric,
+                       int sqrt_out, hipStream_t stream) {
+    using namespace pqv;
+    StreamArgs a{};
+    a.mat = s->d_mat; a.row_of = s->d_row_of; a.nq = nq; a.dim = s->sdim; a.metric = metric; a.sqrt_out = sqrt_out;
+    MmrArgs ma{};
+    ma.cand_rows = io.rows; ma.cand_dist = io.dist; ma.n_found_in = io.nf_in; ma.map = map.map; ma.map_len = map.len;
+    ma.n = n; ma.k = k; ma.lambda = lambda;
+    ma.row_idx = io.o_rows; ma.dist = io.o_dist; ma.score = io.o_score; ma.n_found = io.o_nf;
+    HIP_TRY(launch_mmr_select(a, ma, stream));
+    s->counters.kernel_launches += 1;
+    return PQV_OK;
+}
+// The searcher whose rows a selection without queries reads: `s`, or -- PQV_COSINE -- its cosine searcher, made here where this is
+// the first cosine call, with the L2 chain over its normalised rows and the halving write-out.
+static int mmr_rows_searcher(const pqv_searcher *s, int &metric, int &sqrt_out, const pqv_searcher *&rows) {
+    rows = s;
+    if (metric != PQV_COSINE) return PQV_OK;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = ensure_cosine(s)) return rc;
+    rows = s->cos.get(); metric = PQV_L2SQ_REF4; sqrt_out = 2;
+    return PQV_OK;
+}
+extern "C" int pqv_mmr_select_device(const pqv_searcher *s, const void *d_cand_rows, const void *d_cand_dist, const void *d_n_found_in, uint32_t nq,
+                                     uint32_t n, uint32_t k, float lambda, int metric, int sqrt_out, void *d_row_idx, void *d_dist, void *d_score,
+                                     void *d_n_found, void *hip_stream) {
+    return guard([&] {
+        if (int rc = mmr_checks(s, nullptr, k, n, lambda, false, 1, metric, false, 0)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (n && (!d_cand_rows || !d_cand_dist)) return fail(PQV_ERR_INVALID, "cand_rows/cand_dist must not be NULL");
+        if (!d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "row_idx/dist must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        RowMap map{};
+        if (int rc = ensure_row_map(s, map)) return rc;
+        hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+        int mt = metric, so = sqrt_out ? 1 : 0;
+        const pqv_searcher *rs = nullptr;
+        if (int rc = mmr_rows_searcher(s, mt, so, rs)) return rc;
+        const MmrIo io{static_cast<const uint32_t *>(d_cand_rows), static_cast<const float *>(d_cand_dist), static_cast<const uint32_t *>(d_n_found_in),
+                       static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist), static_cast<float *>(d_score), static_cast<uint32_t *>(d_n_found)};
+        std::lock_guard<std::mutex> lock(rs->mu);
+        if (int rc = enqueue_mmr(rs, map, io, nq, n, k, lambda, mt, so, stream)) return rc;
+        rs->counters.queries += nq;
+        return static_cast<int>(PQV_OK);
+    });
+}
+extern "C" int pqv_mmr_select(const pqv_searcher *s, const uint32_t *cand_rows, const float *cand_dist, const uint32_t *n_found_in, uint32_t nq, uint32_t n,
+                              uint32_t k, float lambda, int metric, int sqrt_out, uint32_t *row_idx, float *dist, float *score, uint32_t *n_found) {
+    return guard([&] {
+        if (int rc = mmr_checks(s, nullptr, k, n, lambda, false, 1, metric, false, 0)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (n && (!cand_rows || !cand_dist)) return fail(PQV_ERR_INVALID, "cand_rows/cand_dist must not be NULL");
+        if (!row_idx || !dist) return fail(PQV_ERR_INVALID, "row_idx/dist must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        RowMap map{};
+        if (int rc = ensure_row_map(s, map)) return rc;
+        int mt = metric, so = sqrt_out ? 1 : 0;
+        const pqv_searcher *rs = nullptr;
+        if (int rc = mmr_rows_searcher(s, mt, so, rs)) return rc;
+        std::lock_guard<std::mutex> lock(rs->mu);
+        Lane lane;
+        if (int rc = lane.acquire(rs, rs->stream)) return rc;
+        Scratch &sc = *lane;
+        // sub-batches of queries through the lane: per query the candidates in and the picks out and nothing else, so 64 MiB of
+        // them already amortise a sub-batch's synchronisation
+        const uint64_t per_query = 8ull * n + 12ull * k + 8;
+        const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 26) / per_query)));
+        const size_t in_w = static_cast<size_t>(n) * sizeof(uint32_t), out_w = static_cast<size_t>(k) * sizeof(uint32_t);
+        HIP_TRY(sc.s_mmr_rows.ensure(std::max<size_t>(1, batch * in_w)));
+        HIP_TRY(sc.s_mmr_dist.ensure(std::max<size_t>(1, batch * in_w)));
+        HIP_TRY(sc.s_mmr_nf.ensure(batch * sizeof(uint32_t)));
+        HIP_TRY(sc.s_rows.ensure(batch * out_w));
+        HIP_TRY(sc.s_dist.ensure(batch * out_w));
+        HIP_TRY(sc.s_out.ensure(batch * out_w));
+        HIP_TRY(sc.s_nfound.ensure(batch * sizeof(uint32_t)));
+        const MmrIo io{sc.s_mmr_rows.as<uint32_t>(), sc.s_mmr_dist.as<float>(), n_found_in ? sc.s_mmr_nf.as<uint32_t>() : nullptr,
+                       sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_out.as<float>(), sc.s_nfound.as<uint32_t>()};
+        for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
+            const uint32_t b = std::min<uint32_t>(batch, nq - q0);
+            const size_t qi = static_cast<size_t>(q0) * n, qo = static_cast<size_t>(q0) * k;
+            if (n) {
+                HIP_TRY(hipMemcpyAsync(sc.s_mmr_rows.p, cand_rows + qi, b * in_w, hipMemcpyHostToDevice, rs->stream));
+                HIP_TRY(hipMemcpyAsync(sc.s_mmr_dist.p, cand_dist + qi, b * in_w, hipMemcpyHostToDevice, rs->stream));
+            }
+            if (n_found_in) HIP_TRY(hipMemcpyAsync(sc.s_mmr_nf.p, n_found_in + q0, b * sizeof(uint32_t), hipMemcpyHostToDevice, rs->stream));
+            if (int rc = enqueue_mmr(rs, map, io, b, n, k, lambda, mt, so, rs->stream)) return rc;
+            HIP_TRY(hipMemcpyAsync(row_idx + qo, sc.s_rows.p, b * out_w, hipMemcpyDeviceToHost, rs->stream));
+            HIP_TRY(hipMemcpyAsync(dist + qo, sc.s_dist.p, b * out_w, hipMemcpyDeviceToHost, rs->stream));
+            if (score) HIP_TRY(hipMemcpyAsync(score + qo, sc.s_out.p, b * out_w, hipMemcpyDeviceToHost, rs->stream));
+            if (n_found) HIP_TRY(hipMemcpyAsync(n_found + q0, sc.s_nfound.p, b * sizeof(uint32_t), hipMemcpyDeviceToHost, rs->stream));
+            HIP_TRY(hipStreamSynchronize(rs->stream));
+            rs->counters.queries += b;
+        }
+        return lane.release();
+    });
+}
+// Stage 1 into the lane, then the selection over it: for the queries d_queries [nq] of `s` (the searcher whose rows are read) on
+// `stream`.  rq: a masked call's request, else nullptr; the picks go to io's outputs, stage 1's candidate totals to d_n_cand.
+static int enqueue_topk_mmr(const pqv_searcher *s, Scratch &sc, const RowMap &map, const SearchRequest *rq, const float *d_queries, uint32_t nq,
+                            uint32_t k, uint32_t fetch_k, float lambda, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, MmrIo io,
+                            uint64_t *d_n_cand, hipStream_t stream) {
+    const size_t cells = static_cast<size_t>(nq) * fetch_k;
+    HIP_TRY(sc.s_mmr_rows.ensure(cells * sizeof(uint32_t)));
+    HIP_TRY(sc.s_mmr_dist.ensure(cells * sizeof(float)));
+    HIP_TRY(sc.s_mmr_nf.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
+    if (int rc = enqueue_topk(s, d_queries, nq, fetch_k, fetch_k, nprobe, max_candidates, metric, sqrt_out, sc.s_mmr_rows.as<uint32_t>(),
+                              sc.s_mmr_dist.as<float>(), sc.s_mmr_nf.as<uint32_t>(), d_n_cand, nullptr, stream, sc, rq))
+        return rc;
+    io.rows = sc.s_mmr_rows.as<uint32_t>(); io.dist = sc.s_mmr_dist.as<float>(); io.nf_in = sc.s_mmr_nf.as<uint32_t>();
+    return enqueue_mmr(s, map, io, nq, fetch_k, k, lambda, metric, sqrt_out, stream);
+}
+// a masked call's request (mask NULL: none)
+static const SearchRequest *mmr_request(const pqv_row_mask *mask, SearchRequest &mv) {
+    if (!mask) return nullptr;
+    mv = SearchRequest{};
+    mv.rows.bits = mask->d_bits.as<uint64_t>(); mv.rows.mask = mask;
+    return &mv;
+}
+extern "C" int pqv_topk_mmr_device(const pqv_searcher *s, const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                   float lambda, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, void *d_row_idx, void *d_dist,
+                                   void *d_score, void *d_n_found, void *d_n_candidates, void *hip_stream) {
+    return guard([&] {
+        if (int rc = mmr_checks(s, mask, k, fetch_k, lambda, true, nprobe, metric, false, 0)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        RowMap map{};
+        if (int rc = ensure_row_map(s, map)) return rc;
+        hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+        SearchRequest mv{};
+        const SearchRequest *rq = mmr_request(mask, mv);
+        const MmrIo io{nullptr, nullptr, nullptr, static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist), static_cast<float *>(d_score),
+                       static_cast<uint32_t *>(d_n_found)};
+        return partition_device_call(s, static_cast<const float *>(d_queries), nq, metric, sqrt_out ? 1 : 0, stream,
+                                     [&](const pqv_searcher *bs, Scratch &sc, const float *q, int mt, int so) {
+                                         return enqueue_topk_mmr(bs, sc, map, rq, q, nq, k, fetch_k, lambda, nprobe, max_candidates, mt, so, io,
+                                                                 static_cast<uint64_t *>(d_n_candidates), stream);
+                                     });
+    });
+}
+extern "C" int pqv_topk_mmr(const pqv_searcher *s, const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len, uint32_t k,
+                            uint32_t fetch_k, float lambda, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, uint32_t *row_idx,
+                            float *dist, float *score, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        if (int rc = mmr_checks(s, mask, k, fetch_k, lambda, true, nprobe, metric, true, query_len)) return rc;
+        if (nq == 0) return static_cast<int>(PQV_OK);
+        if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+        if (int rc = use_device(s->device)) return rc;
+        RowMap map{};
+        if (int rc = ensure_row_map(s, map)) return rc;
+        SearchRequest mv{};
+        const SearchRequest *rq = mmr_request(mask, mv);
+        const pqv_searcher *bs = s;
+        const float *qs = queries;
+        int mt = metric, so = sqrt_out ? 1 : 0;
+        std::vector<float> nq_host;
+        if (int rc = cosine_queries_host(bs, qs, nq, mt, so, nq_host)) return rc;
+        std::lock_guard<std::mutex> lock(bs->mu);
+        Lane lane;
+        if (int rc = lane.acquire(bs, bs->stream)) return rc;
+        Scratch &sc = *lane;
+        // the sub-batch bound of the plain host top-k at k = fetch_k, and stage 1's block and the picks beside it
+        const TopkPlan p1 = plan_topk(bs, std::min<uint32_t>(nq, 1024), nprobe, fetch_k, mt, stream_request(rq));
+        const uint64_t per_query = static_cast<uint64_t>(p1.n_part_rr) * fetch_k * 12 + static_cast<uint64_t>(p1.n_part_probe) * p1.probe_kpart * 12 +
+                                   static_cast<uint64_t>(cand_cap_for(bs, fetch_k)) * 12 + static_cast<uint64_t>(p1.np) * (bs->sdim + 32) +
+                                   static_cast<uint64_t>(bs->sdim) * 4 + 8ull * fetch_k + 12ull * k + 17;
+        const uint32_t batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 30) / per_query)));
+        const size_t out_w = static_cast<size_t>(k) * sizeof(uint32_t);
+        const std::vector<BatchOut> outs = {{&sc.s_rows, out_w, row_idx}, {&sc.s_dist, out_w, dist}, {&sc.s_out, out_w, score},
+                                            {&sc.s_nfound, sizeof(uint32_t), n_found}, {&sc.s_ncand, sizeof(uint64_t), n_candidates}};
+        if (int rc = host_batches(
+                bs, sc, qs, nq, batch, rq, nullptr, outs,
+                [&](uint32_t b, SearchRequest *brq) {
+                    const MmrIo io{nullptr, nullptr, nullptr, sc.s_rows.as<uint32_t>(), sc.s_dist.as<float>(), sc.s_out.as<float>(), sc.s_nfound.as<uint32_t>()};
+                    return enqueue_topk_mmr(bs, sc, map, brq, sc.s_queries.as<float>(), b, k, fetch_k, lambda, nprobe, max_candidates, mt, so, io,
+                                            sc.s_ncand.as<uint64_t>(), bs->stream);
+                },
+                [](uint32_t, uint32_t) { return static_cast<int>(PQV_OK); }))      // (no host step: stage 1 replays nothing)
+            return rc;
+        return lane.release();
     });
 }
 

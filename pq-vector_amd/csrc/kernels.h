@@ -241,6 +241,26 @@ hipError_t launch_rows_stream(const StreamArgs &a, const RowsArgs &ra, hipStream
 // as StreamArgs documents it; PQV_DOT: 0.0f - s), +inf for a candidate that is not walked.  a.k / part_keys / part_vals are not read.
 hipError_t launch_rows_score(const StreamArgs &a, const RowsArgs &ra, hipStream_t s);
 
+// ---- MMR selection (kernels_mmr.hip; pqv.h: pqv_mmr_select, pqv_topk_mmr) ----------------------------------------------------
+// mmr_select_kernel, one block per query: the greedy selection of pqv.h's MMR section over query q's candidates cand_rows /
+// cand_dist [q * n .. + n), of which the first min(n, n_found_in[q]) whose row the map places in a list are considered.  Of `a` the
+// kernel reads mat, row_of, dim, nq, metric (the chain: 1 = SEQ, 4 = PQV_DOT's products) and sqrt_out (how a pairwise d2 is put on
+// the output scale, as StreamArgs documents it).  The picks go out in pick order, padded to k with 0xFFFFFFFF / +inf / +inf.
+struct MmrArgs {
+    const uint32_t *cand_rows;   // [nq, n] row ids, anything
+    const float    *cand_dist;   // [nq, n] rel on the output scale
+    const uint32_t *n_found_in;  // optional [nq]
+    const uint32_t *map;         // launch_row_map's
+    uint64_t        map_len;
+    uint32_t        n, k;        // n <= 1024, k >= 1
+    float           lambda;
+    uint32_t       *row_idx;     // [nq, k]
+    float          *dist;        // [nq, k]
+    float          *score;       // optional [nq, k]
+    uint32_t       *n_found;     // optional [nq]
+};
+hipError_t launch_mmr_select(const StreamArgs &a, const MmrArgs &ma, hipStream_t s);
+
 // ---- expanding filtered top-k (kernels_expand.hip; pqv.h: pqv_topk_expand) ------------------------------------------------
 // filter_count_kernel: cnt[q * P + j] = the positions of list probe[q * P + j] that pass the call's filter -- the set bits of
 // the windows masked_stream_kernel forms for the same `win` (0: the mask image `bits`; 1 / 2: key_pos == a[q], i32 / i64; 3 / 4:

@@ -116,6 +116,30 @@ public:
         dist.assign(nq && lims[nq] > lims[0] ? static_cast<size_t>(lims[nq] - lims[0]) : 0, std::numeric_limits<float>::infinity());
         check(pqv_score_rows(h_.get(), lims.data(), cand_rows.data(), mask, queries.data(), nq, dim_, PQV_L2SQ_REF4, 1, dist.data()));
     }
+    // MMR top-k: the fetch_k nearest rows of the probed lists (under `mask` where one is given), then k of them picked by maximal
+    // marginal relevance with weight lambda on the distance to the query; rows / dist / score in pick order, found[q] picks per
+    // query, k slots each (pqv.h: pqv_topk_mmr)
+    void topk_mmr(const std::vector<float> &queries, uint32_t k, uint32_t fetch_k, float lambda, uint32_t nprobe, std::vector<uint32_t> &rows,
+                  std::vector<float> &dist, std::vector<float> &score, std::vector<uint32_t> &found, const pqv_row_mask *mask = nullptr) const {
+        const uint32_t nq = dim_ ? static_cast<uint32_t>(queries.size() / dim_) : 0;
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, std::numeric_limits<float>::infinity());
+        score.assign(static_cast<size_t>(nq) * k, std::numeric_limits<float>::infinity());
+        found.assign(nq, 0);
+        check(pqv_topk_mmr(h_.get(), mask, queries.data(), nq, dim_, k, fetch_k, lambda, nprobe, 0, PQV_L2SQ_REF4, 1, rows.data(), dist.data(),
+                           score.data(), found.data(), nullptr));
+    }
+    // ... and the selection alone over the [nq, n] rows and distances of any top-k call (pqv.h: pqv_mmr_select)
+    void mmr_select(const std::vector<uint32_t> &cand_rows, const std::vector<float> &cand_dist, uint32_t nq, uint32_t k, float lambda,
+                    std::vector<uint32_t> &rows, std::vector<float> &dist, std::vector<float> &score, std::vector<uint32_t> &found) const {
+        const uint32_t n = nq ? static_cast<uint32_t>(cand_rows.size() / nq) : 0;
+        rows.assign(static_cast<size_t>(nq) * k, 0xFFFFFFFFu);
+        dist.assign(static_cast<size_t>(nq) * k, std::numeric_limits<float>::infinity());
+        score.assign(static_cast<size_t>(nq) * k, std::numeric_limits<float>::infinity());
+        found.assign(nq, 0);
+        check(pqv_mmr_select(h_.get(), cand_rows.data(), cand_dist.data(), nullptr, nq, n, k, lambda, PQV_L2SQ_REF4, 1, rows.data(), dist.data(),
+                             score.data(), found.data()));
+    }
 private:
     struct Del { void operator()(pqv_searcher *p) const { pqv_searcher_free(p); } };
     std::unique_ptr<pqv_searcher, Del> h_;
