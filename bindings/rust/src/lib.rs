@@ -75,6 +75,26 @@ impl Corpus {
         Ok(Self { raw })
     }
 
+    /// An f16 corpus (`pqv.h`: half-precision corpora): `rows` are IEEE binary16 bit patterns, row-major `[n, dim]`, kept as given.
+    pub fn upload_f16(device: usize, rows: &[u16], dim: usize) -> Result<Self> {
+        if dim == 0 {
+            return Err("Embedding dimension must be > 0".into());
+        }
+        if rows.len() % dim != 0 {
+            return Err("Embedding data length must be a multiple of dimension".into());
+        }
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            sys::pqv_corpus_upload_f16(device as c_int, rows.as_ptr(), (rows.len() / dim) as u64, dim as u32, &mut raw)
+        })?;
+        Ok(Self { raw })
+    }
+
+    /// `true` for an f16 corpus.
+    pub fn is_f16(&self) -> bool {
+        unsafe { sys::pqv_corpus_dtype(self.raw) == sys::PQV_ROWS_F16 }
+    }
+
     pub fn append(&mut self, rows: &[f32]) -> Result<()> {
         let dim = self.dim();
         if rows.len() % dim != 0 {

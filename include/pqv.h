@@ -196,6 +196,44 @@ int pqv_corpus_fetch_rows(const pqv_corpus *corpus, const uint32_t *rows, uint64
                           float *out);
 void pqv_corpus_free(pqv_corpus *corpus);
 
+/* ---- half-precision corpora: f16 rows in HBM, exact top-k and range search -------------------------------------------------
+ * An embedding column stored as Float16 is uploaded AS GIVEN: [n, dim] IEEE binary16 values, 2 bytes each, no padding -- half
+ * the HBM of the f32 corpus (10 M x 768: 15.4 GB instead of 30.7 GB; 100 M x 768: 154 GB, which fits one 288 GB device where
+ * 307 GB of f32 does not) and half the bytes of every exact pass.  f16 -> f32 widening is exact, so the distance of a query to an
+ * f16 row is DEFINED as the reference chain (PQV_L2SQ_REF4 / PQV_L2SQ_SEQ) over the widened row: every result is bit-identical
+ * to what the same call returns on an f32 corpus holding the widened values.  Inf / NaN halves are accepted and unpinned.
+ *
+ *   rows        `const uint16_t *`: the binary16 bit patterns.  The f32 / f64 write calls (pqv_corpus_append, _append_f64,
+ *               _write_rows, _write_rows_f64, _write_plain_pages) on an f16 corpus return PQV_ERR_INVALID "corpus rows are f16",
+ *               the f16 ones on an f32 corpus "corpus rows are f32": nothing is rounded silently.  pqv_corpus_finish is shared.
+ *               pqv_corpus_from_device_f16 borrows the buffer like pqv_corpus_from_device; d_rows must be 16-byte aligned
+ *               (PQV_ERR_INVALID "d_rows must be 16-byte aligned").  No kernel reads behind a row's last byte.
+ *   fetch       pqv_corpus_fetch_rows returns the widened f32 values.
+ *   searcher    pqv_searcher_create(index, f16 corpus, flags, &out) makes a searcher that keeps NO row-derived layout -- no
+ *               list-ordered copy, screen images, norms or cosine layout; flags other than PQV_PREPARE_COSINE (refused) change
+ *               nothing, nor do the options of pqv_searcher_set_option.  Centroids stay f32.  Every search runs the exact stream
+ *               (stream_h_kernel: 16-byte loads of eight halves, widened by the hardware conversion, both 4-group partials of a
+ *               load parked in the chain tile), as rerank_mode = 1 does on f32.  pqv_searcher_footprint counts 2 bytes per value.
+ *   served      pqv_topk (tie replay and k / nprobe beyond 1024 included), pqv_topk_device, pqv_topk_device_flags and
+ *               pqv_range_search with PQV_L2SQ_REF4 / PQV_L2SQ_SEQ; max_candidates, sqrt_out, max_results as on f32.  pqv_probe,
+ *               pqv_candidate_rows, the counters (screened_pairs / screen_survivors do not advance) and the timing calls work.
+ *   refused     everything else that would read row values returns PQV_ERR_UNSUPPORTED "<entry point> does not take f16
+ *               corpora" before any device work, behind the entry point's own handle checks: PQV_COSINE and PQV_DOT on the served
+ *               calls (the text names the metric: "PQV_DOT does not take f16 corpora"), the masked, keyed, filtered, expanding,
+ *               depth, distinct, grouped, partition, candidate-list and MMR calls, pqv_table_searcher_create, pqv_brute_topk, pqv_kmeans, pqv_index_build,
+ *               pqv_index_assign, pqv_index_append and pqv_index_compact.  pqv_index_remove* reads no rows and is unchanged.
+ *   index       comes from pqv_index_build_host (on widened rows), pqv_index_from_bytes or pqv_index_from_parts: building from
+ *               f16 rows on the device is out of scope, so a column that only fits as f16 needs centroids trained elsewhere. */
+#define PQV_ROWS_F32 0
+#define PQV_ROWS_F16 1
+int pqv_corpus_create_f16(int device, uint64_t capacity_rows, uint32_t dim, pqv_corpus **out);
+int pqv_corpus_append_f16(pqv_corpus *corpus, const uint16_t *rows, uint64_t n_rows);
+int pqv_corpus_write_rows_f16(pqv_corpus *corpus, uint64_t row_offset, const uint16_t *rows, uint64_t n_rows);
+int pqv_corpus_upload_f16(int device, const uint16_t *rows, uint64_t n, uint32_t dim, pqv_corpus **out);
+int pqv_corpus_from_device_f16(int device, const void *d_rows, uint64_t n, uint32_t dim, pqv_corpus **out);
+/* PQV_ROWS_F32 or PQV_ROWS_F16 (-1 for NULL) */
+int pqv_corpus_dtype(const pqv_corpus *corpus);
+
 /* ---- index build ---------------------------------------------------------------------
  * Replaces build_ivf_index(&Embeddings, IvfBuildConfig{n_clusters, max_iters, seed})
  * (src/ivf/index.rs:152-214) including k_means (:323-457), sample_embeddings (:222-242)

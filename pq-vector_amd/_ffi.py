@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PQV_LIB_PATH") or os.path.join(_HERE, "libpqv_hip.so")
 
 u8p = C.POINTER(C.c_uint8)
+u16p = C.POINTER(C.c_uint16)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
 i64p = C.POINTER(C.c_int64)
@@ -31,6 +32,8 @@ PQV_L2SQ_SEQ = 1
 PQV_COSINE = 2
 PQV_L2SQ_MFMA = 3
 PQV_DOT = 4                           # inner product through the index: dist = -(q.x) (pqv.h: PQV_DOT)
+
+PQV_ROWS_F32, PQV_ROWS_F16 = 0, 1      # pqv_corpus_dtype (pqv.h: half-precision corpora)
 
 PQV_LAYOUT_IVF_ORDERED = 0x0
 PQV_LAYOUT_ROW_ORDER = 0x1
@@ -112,6 +115,12 @@ SIGNATURES = {
     "pqv_corpus_device": (C.c_int, [vp]),
     "pqv_corpus_fetch_rows": (C.c_int, [vp, u32p, C.c_uint64, f32p]),
     "pqv_corpus_free": (None, [vp]),
+    "pqv_corpus_create_f16": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
+    "pqv_corpus_append_f16": (C.c_int, [vp, u16p, C.c_uint64]),
+    "pqv_corpus_write_rows_f16": (C.c_int, [vp, C.c_uint64, u16p, C.c_uint64]),
+    "pqv_corpus_upload_f16": (C.c_int, [C.c_int, u16p, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
+    "pqv_corpus_from_device_f16": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
+    "pqv_corpus_dtype": (C.c_int, [vp]),
     "pqv_index_build": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
     "pqv_index_assign": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u32p]),
     "pqv_index_append": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]),

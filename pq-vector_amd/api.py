@@ -9,7 +9,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi, predicate
-from ._ffi import f32p, f64p, u8p, u32p, u64p, vp
+from ._ffi import f32p, f64p, u8p, u16p, u32p, u64p, vp
 
 
 class PqvError(Exception):
@@ -30,13 +30,19 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _h16(a):
+    """a float16 array's IEEE binary16 bit patterns, contiguous (pqv.h: half-precision corpora)"""
+    return np.ascontiguousarray(a).view(np.uint16)
+
+
 def device_count():
     return _ffi.lib().pqv_device_count()
 
 
 # ---------------------------------------------------------------------------------------
 class Corpus:
-    """The embedding column resident in one GPU's HBM (row-major [n, dim] f32)."""
+    """The embedding column resident in one GPU's HBM: row-major [n, dim] f32, or -- from float16 input -- f16 rows as given (`dtype`;
+    pqv.h: half-precision corpora).  A float16 array never goes into an f32 corpus or the reverse: the library refuses the call."""
 
     def __init__(self, handle, keepalive=None):
         self._h = handle
@@ -49,6 +55,10 @@ class Corpus:
             raise PqvError(_ffi.PQV_ERR_INVALID, "Embedding data length must be a multiple of dimension")
         n, dim = rows.shape
         h = vp()
+        if rows.dtype == np.float16:
+            r = _h16(rows)
+            _check(_ffi.lib().pqv_corpus_upload_f16(device, r.ctypes.data_as(u16p), n, dim, C.byref(h)))
+            return cls(h)
         if rows.dtype == np.float64:  # narrowed like src/ivf/parquet.rs:246-256
             _check(_ffi.lib().pqv_corpus_create(device, n, dim, C.byref(h)))
             c = cls(h)
@@ -60,9 +70,12 @@ class Corpus:
         return cls(h)
 
     @classmethod
-    def create(cls, capacity_rows, dim, device=0):
+    def create(cls, capacity_rows, dim, device=0, dtype=np.float32):
         h = vp()
-        _check(_ffi.lib().pqv_corpus_create(device, capacity_rows, dim, C.byref(h)))
+        if np.dtype(dtype) == np.float16:
+            _check(_ffi.lib().pqv_corpus_create_f16(device, capacity_rows, dim, C.byref(h)))
+        else:
+            _check(_ffi.lib().pqv_corpus_create(device, capacity_rows, dim, C.byref(h)))
         c = cls(h)
         c._capacity = int(capacity_rows)
         return c
@@ -74,7 +87,10 @@ class Corpus:
 
     def append(self, rows):
         rows = np.asarray(rows)
-        if rows.dtype == np.float64:
+        if rows.dtype == np.float16:
+            r = _h16(rows)
+            _check(_ffi.lib().pqv_corpus_append_f16(self._h, r.ctypes.data_as(u16p), r.shape[0]))
+        elif rows.dtype == np.float64:
             r = np.ascontiguousarray(rows)
             _check(_ffi.lib().pqv_corpus_append_f64(self._h, r.ctypes.data_as(f64p), r.shape[0]))
         else:
@@ -82,10 +98,13 @@ class Corpus:
             _check(_ffi.lib().pqv_corpus_append(self._h, r.ctypes.data_as(f32p), r.shape[0]))
 
     def write_rows(self, row_offset, rows):
-        """Streaming upload (pqv_corpus_write_rows): rows [row_offset, row_offset + len(rows)) from a [m, dim] f32 / f64 array,
+        """Streaming upload (pqv_corpus_write_rows): rows [row_offset, row_offset + len(rows)) from a [m, dim] f32 / f64 array (float16 into an f16 corpus),
         staged in pinned memory and DMA'd asynchronously.  Thread-safe; batches may arrive in any order.  finish() completes."""
         rows = np.asarray(rows)
-        if rows.dtype == np.float64:
+        if rows.dtype == np.float16:
+            r = _h16(rows)
+            _check(_ffi.lib().pqv_corpus_write_rows_f16(self._h, row_offset, r.ctypes.data_as(u16p), r.shape[0]))
+        elif rows.dtype == np.float64:
             r = np.ascontiguousarray(rows)
             _check(_ffi.lib().pqv_corpus_write_rows_f64(self._h, row_offset, r.ctypes.data_as(f64p), r.shape[0]))
         else:
@@ -113,11 +132,26 @@ class Corpus:
         _check(_ffi.lib().pqv_corpus_finish(self._h, n_rows))
 
     @classmethod
-    def from_device_ptr(cls, ptr, n, dim, device=0, keepalive=None):
-        """Adopt a device buffer (e.g. a torch tensor's data_ptr()); `keepalive` pins its owner."""
+    def from_device_ptr(cls, ptr, n, dim, device=0, keepalive=None, dtype=np.float32):
+        """Adopt a device buffer (e.g. a torch tensor's data_ptr()); `keepalive` pins its owner.  dtype=np.float16: f16 rows."""
         h = vp()
-        _check(_ffi.lib().pqv_corpus_from_device(device, vp(ptr), n, dim, C.byref(h)))
+        fn = _ffi.lib().pqv_corpus_from_device_f16 if np.dtype(dtype) == np.float16 else _ffi.lib().pqv_corpus_from_device
+        _check(fn(device, vp(ptr), n, dim, C.byref(h)))
         return cls(h, keepalive)
+
+    @classmethod
+    def from_device(cls, tensor):
+        """Adopt a contiguous [n, dim] torch tensor on a GPU, float32 or float16 (half), and keep it alive."""
+        import torch
+        if not tensor.is_cuda or tensor.dim() != 2 or not tensor.is_contiguous() or tensor.dtype not in (torch.float32, torch.float16):
+            raise PqvError(_ffi.PQV_ERR_INVALID, "from_device takes a contiguous [n, dim] float32 or float16 tensor on a GPU")
+        return cls.from_device_ptr(tensor.data_ptr(), tensor.shape[0], tensor.shape[1], device=tensor.device.index or 0, keepalive=tensor,
+                                   dtype=np.float16 if tensor.dtype == torch.float16 else np.float32)
+
+    @property
+    def dtype(self):
+        """np.float32, or np.float16 for an f16 corpus"""
+        return np.dtype(np.float16 if _ffi.lib().pqv_corpus_dtype(self._h) == _ffi.PQV_ROWS_F16 else np.float32)
 
     @property
     def rows(self):

@@ -323,6 +323,10 @@ struct pqv_corpus {
     uint64_t n = 0;
     uint64_t capacity = 0;
     float *d_rows = nullptr;  // [capacity, dim]
+    // an f16 corpus (pqv.h: half-precision corpora; dtype PQV_ROWS_F16): the rows as given, [capacity, dim] binary16 bits -- d_rows stays NULL
+    int dtype = PQV_ROWS_F32;
+    uint16_t *d_rows_h = nullptr;
+    bool half() const { return dtype == PQV_ROWS_F16; }
     bool owned = true;
     hipStream_t stream = nullptr;
     std::unique_ptr<UploadStage> upload;       // made by the first pqv_corpus_write_rows
@@ -336,6 +340,7 @@ struct pqv_corpus {
     mutable uint64_t aux_v8_rows = 0;
     ~pqv_corpus() {
         if (d_rows && owned) (void)hipFree(d_rows);
+        if (d_rows_h && owned) (void)hipFree(d_rows_h);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -414,6 +419,9 @@ struct pqv_searcher {
     DevBuf d_centroids, d_list_off, d_ids, d_mat_ivf, d_stats;
     mutable DevBuf d_row_norm2;            // |x|^2 per storage row (f32 / f16 MFMA screens; see norms_done)
     const float *d_mat = nullptr;          // row storage the re-rank reads
+    const uint16_t *d_mat_h = nullptr;     // a searcher over an f16 corpus: its rows (row order, through d_row_of); d_mat stays NULL and no
+                                           // row-derived layout exists -- every search is the exact stream over launch_stream_h
+    bool half() const { return d_mat_h != nullptr; }
     const uint32_t *d_row_of = nullptr;    // list position -> storage row (ROW_ORDER layout, and the images-only IVF layout)
     const uint32_t *d_final_ids = nullptr; // storage row -> file row id (IVF layout with its own f32 copy)
     // IVF-ordered layout WITHOUT a second f32 copy of the corpus (round 4): everything the screen streams -- the blocked operand
@@ -814,6 +822,7 @@ static pqv::GroupFilterArgs group_filter_args(const SearchRequest *mv) {
 static hipError_t launch_stream_pass(const pqv::StreamArgs &ra, const SearchRequest *rq, unsigned long long *stats, const uint64_t *n_cand,
                                      pqv::StreamMode mode, hipStream_t stream, int64_t *part_grp = nullptr,
                                      const uint32_t *rank_limit = nullptr) {
+    if (ra.mat_h) return rq ? hipErrorInvalidValue : pqv::launch_stream_h(ra, mode, stream);     // (f16 rows: the plain L2 call only)
     if (!rq) return ra.metric == PQV_DOT ? pqv::launch_dot_stream(ra, nullptr, mode, stream) : pqv::launch_stream(ra, mode, stream);
     if (rq->distinct()) {
         if (mode != pqv::STREAM_TOPK) return hipErrorInvalidValue;
@@ -875,8 +884,21 @@ extern "C" int pqv_diag_rng(const uint8_t *seed32, uint64_t seed64, int mode, ui
 // ---------------------------------------------------------------------------------------
 // corpus
 // ---------------------------------------------------------------------------------------
+// The one refusal of everything that would read the values of f16 rows (pqv.h: half-precision corpora), called where each entry point
+// validates its arguments: behind its own handle checks, before any device work.  A NULL handle is left to those checks.
+static int refuse_f16(const pqv_corpus *c, const char *entry) {
+    if (c && c->half()) return fail(PQV_ERR_UNSUPPORTED, std::string(entry) + " does not take f16 corpora");
+    return PQV_OK;
+}
+static int refuse_f16(const pqv_searcher *s, const char *entry) { return s ? refuse_f16(s->corpus, entry) : PQV_OK; }
+// the write calls: rows of one element type into a corpus of the other
+static int rows_dtype_check(const pqv_corpus *c, int dtype) {
+    if (c->dtype != dtype) return fail(PQV_ERR_INVALID, c->half() ? "corpus rows are f16" : "corpus rows are f32");
+    return PQV_OK;
+}
+
 static int pqv_corpus_create_impl(int device, uint64_t capacity_rows, uint32_t dim,
-                                 pqv_corpus **out) {
+                                 pqv_corpus **out, int dtype = PQV_ROWS_F32) {
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
     *out = nullptr;
     if (dim == 0) return fail(PQV_ERR_INVALID, "Embedding dimension must be > 0");  // mod.rs:59
@@ -888,8 +910,9 @@ static int pqv_corpus_create_impl(int device, uint64_t capacity_rows, uint32_t d
     c->device = device;
     c->dim = dim;
     c->capacity = capacity_rows;
-    const size_t bytes = std::max<size_t>(16, static_cast<size_t>(capacity_rows) * dim * sizeof(float));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_rows), bytes);
+    c->dtype = dtype;
+    const size_t bytes = std::max<size_t>(16, static_cast<size_t>(capacity_rows) * dim * (c->half() ? sizeof(uint16_t) : sizeof(float)));
+    hipError_t e = hipMalloc(c->half() ? reinterpret_cast<void **>(&c->d_rows_h) : reinterpret_cast<void **>(&c->d_rows), bytes);
     if (e != hipSuccess) {
         delete c;
         return fail(PQV_ERR_OOM, std::string("hipMalloc(corpus): ") + hipGetErrorString(e));
@@ -911,6 +934,7 @@ extern "C" int pqv_corpus_create(int device, uint64_t capacity_rows, uint32_t di
 
 static int pqv_corpus_append_impl(pqv_corpus *c, const float *rows, uint64_t n_rows) {
     if (!c) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
+    if (int rc = rows_dtype_check(c, PQV_ROWS_F32)) return rc;
     if (!c->owned) return fail(PQV_ERR_INVALID, "cannot append to a borrowed device buffer");
     if (n_rows == 0) return PQV_OK;
     if (!rows) return fail(PQV_ERR_INVALID, "rows must not be NULL");
@@ -924,9 +948,24 @@ static int pqv_corpus_append_impl(pqv_corpus *c, const float *rows, uint64_t n_r
 extern "C" int pqv_corpus_append(pqv_corpus *c, const float *rows, uint64_t n_rows) {
     return guard([&] { return pqv_corpus_append_impl(c, rows, n_rows); });
 }
+extern "C" int pqv_corpus_append_f16(pqv_corpus *c, const uint16_t *rows, uint64_t n_rows) {
+    return guard([&]() -> int {
+        if (!c) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
+        if (int rc = rows_dtype_check(c, PQV_ROWS_F16)) return rc;
+        if (!c->owned) return fail(PQV_ERR_INVALID, "cannot append to a borrowed device buffer");
+        if (n_rows == 0) return PQV_OK;
+        if (!rows) return fail(PQV_ERR_INVALID, "rows must not be NULL");
+        if (c->n + n_rows > c->capacity) return fail(PQV_ERR_INVALID, "corpus capacity exceeded");
+        if (int rc = use_device(c->device)) return rc;
+        HIP_TRY(hipMemcpy(c->d_rows_h + c->n * c->dim, rows, static_cast<size_t>(n_rows) * c->dim * sizeof(uint16_t), hipMemcpyHostToDevice));
+        c->n += n_rows;
+        return PQV_OK;
+    });
+}
 
 static int pqv_corpus_append_f64_impl(pqv_corpus *c, const double *rows, uint64_t n_rows) {
     if (!c) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
+    if (int rc = rows_dtype_check(c, PQV_ROWS_F32)) return rc;
     if (!c->owned) return fail(PQV_ERR_INVALID, "cannot append to a borrowed device buffer");
     if (n_rows == 0) return PQV_OK;
     if (!rows) return fail(PQV_ERR_INVALID, "rows must not be NULL");
@@ -985,6 +1024,7 @@ void upload_release(UploadStage *u, int slot, bool in_flight) {
 template <class T>
 int corpus_write_rows(pqv_corpus *c, uint64_t row_offset, const T *rows, uint64_t n_rows) {
     if (!c) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
+    if (int rc = rows_dtype_check(c, std::is_same<T, uint16_t>::value ? PQV_ROWS_F16 : PQV_ROWS_F32)) return rc;
     if (!c->owned) return fail(PQV_ERR_INVALID, "cannot write into a borrowed device buffer");
     if (n_rows == 0) return PQV_OK;
     if (!rows) return fail(PQV_ERR_INVALID, "rows must not be NULL");
@@ -1001,9 +1041,11 @@ int corpus_write_rows(pqv_corpus *c, uint64_t row_offset, const T *rows, uint64_
         if (int rc = upload_claim(u, &slot)) return rc;
         std::memcpy(u->pin[slot], rows + r0 * c->dim, m * row_bytes);
         hipStream_t cs = u->copy_stream[slot % UploadStage::NS];
-        float *dst = c->d_rows + (row_offset + r0) * c->dim;
+        float *dst = c->d_rows ? c->d_rows + (row_offset + r0) * c->dim : nullptr;
         hipError_t e = hipSuccess;
-        if (std::is_same<T, float>::value) {
+        if (std::is_same<T, uint16_t>::value) {       // (f16 rows go in as given)
+            e = hipMemcpyAsync(c->d_rows_h + (row_offset + r0) * c->dim, u->pin[slot], m * row_bytes, hipMemcpyHostToDevice, cs);
+        } else if (std::is_same<T, float>::value) {
             e = hipMemcpyAsync(dst, u->pin[slot], m * row_bytes, hipMemcpyHostToDevice, cs);
         } else {
             if (!u->dev64[slot]) e = hipMalloc(&u->dev64[slot], UploadStage::BYTES);
@@ -1022,6 +1064,9 @@ extern "C" int pqv_corpus_write_rows(pqv_corpus *c, uint64_t row_offset, const f
 }
 extern "C" int pqv_corpus_write_rows_f64(pqv_corpus *c, uint64_t row_offset, const double *rows, uint64_t n_rows) {
     return guard([&] { return corpus_write_rows<double>(c, row_offset, rows, n_rows); });
+}
+extern "C" int pqv_corpus_write_rows_f16(pqv_corpus *c, uint64_t row_offset, const uint16_t *rows, uint64_t n_rows) {
+    return guard([&] { return corpus_write_rows<uint16_t>(c, row_offset, rows, n_rows); });
 }
 extern "C" int pqv_corpus_finish(pqv_corpus *c, uint64_t n_rows) {
     return guard([&]() -> int {
@@ -1154,6 +1199,7 @@ extern "C" int pqv_corpus_write_plain_pages(pqv_corpus *c, const uint8_t *file_b
                                             uint32_t max_def, int f64, uint32_t *bad_page) {
     return guard([&]() -> int {
         if (!c) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
+        if (int rc = rows_dtype_check(c, PQV_ROWS_F32)) return rc;
         if (!file_base || !body_off || !body_len || !first_value || !n_values) return fail(PQV_ERR_INVALID, "page tables must not be NULL");
         if (dim == 0 || dim != c->dim) return fail(PQV_ERR_INVALID, "list length does not match the corpus");
         uint32_t def_bw = 0;
@@ -1331,18 +1377,34 @@ extern "C" int pqv_corpus_upload(int device, const float *rows, uint64_t n, uint
     return guard([&] { return pqv_corpus_upload_impl(device, rows, n, dim, out); });
 }
 
+extern "C" int pqv_corpus_upload_f16(int device, const uint16_t *rows, uint64_t n, uint32_t dim, pqv_corpus **out) {
+    return guard([&]() -> int {
+        if (int rc = pqv_corpus_create_impl(device, n, dim, out, PQV_ROWS_F16)) return rc;
+        if (int rc = pqv_corpus_append_f16(*out, rows, n)) {
+            delete *out;
+            *out = nullptr;
+            return rc;
+        }
+        return PQV_OK;
+    });
+}
+
 static int pqv_corpus_from_device_impl(int device, const void *d_rows, uint64_t n, uint32_t dim,
-                                      pqv_corpus **out) {
+                                      pqv_corpus **out, int dtype = PQV_ROWS_F32) {
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
     *out = nullptr;
     if (dim == 0) return fail(PQV_ERR_INVALID, "Embedding dimension must be > 0");
     if (n > 0xFFFFFFFFull)
         return fail(PQV_ERR_UNSUPPORTED, "row ids are u32: at most 4294967295 rows per corpus");
     if (n && !d_rows) return fail(PQV_ERR_INVALID, "d_rows must not be NULL");
+    // (the f16 loads are 16 bytes wide where dim % 8 == 0, dwords where dim is even: the buffer's own alignment is the caller's)
+    if (dtype == PQV_ROWS_F16 && (reinterpret_cast<uintptr_t>(d_rows) & 15u)) return fail(PQV_ERR_INVALID, "d_rows must be 16-byte aligned");
     if (int rc = use_device(device)) return rc;
     pqv_corpus *c = new (std::nothrow) pqv_corpus();
     if (!c) return fail(PQV_ERR_OOM, "host allocation failed");
-    c->device = device; c->dim = dim; c->n = n; c->capacity = n;
+    c->device = device; c->dim = dim; c->n = n; c->capacity = n; c->dtype = dtype;
+    if (dtype == PQV_ROWS_F16) c->d_rows_h = const_cast<uint16_t *>(static_cast<const uint16_t *>(d_rows));
+    else
     c->d_rows = const_cast<float *>(static_cast<const float *>(d_rows));
     c->owned = false;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -1360,6 +1422,14 @@ extern "C" int pqv_corpus_from_device(int device, const void *d_rows, uint64_t n
     return guard([&] { return pqv_corpus_from_device_impl(device, d_rows, n, dim, out); });
 }
 
+extern "C" int pqv_corpus_from_device_f16(int device, const void *d_rows, uint64_t n, uint32_t dim, pqv_corpus **out) {
+    return guard([&] { return pqv_corpus_from_device_impl(device, d_rows, n, dim, out, PQV_ROWS_F16); });
+}
+extern "C" int pqv_corpus_create_f16(int device, uint64_t capacity_rows, uint32_t dim, pqv_corpus **out) {
+    return guard([&] { return pqv_corpus_create_impl(device, capacity_rows, dim, out, PQV_ROWS_F16); });
+}
+extern "C" int pqv_corpus_dtype(const pqv_corpus *c) { return c ? c->dtype : -1; }
+
 extern "C" uint64_t pqv_corpus_rows(const pqv_corpus *c) { return c ? c->n : 0; }
 extern "C" uint32_t pqv_corpus_dim(const pqv_corpus *c) { return c ? c->dim : 0; }
 extern "C" int pqv_corpus_device(const pqv_corpus *c) { return c ? c->device : -1; }
@@ -1369,7 +1439,7 @@ static int pqv_corpus_fetch_rows_impl(const pqv_corpus *c, const uint32_t *rows,
     if (!c) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
     if (m == 0) return PQV_OK;
     if (!rows || !out) return fail(PQV_ERR_INVALID, "rows/out must not be NULL");
-    if (!c->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
+    if (!c->d_rows && !c->half()) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
     for (uint64_t i = 0; i < m; ++i)
         if (rows[i] >= c->n) return fail(PQV_ERR_INVALID, "row id out of range");
     if (int rc = use_device(c->device)) return rc;
@@ -1377,6 +1447,8 @@ static int pqv_corpus_fetch_rows_impl(const pqv_corpus *c, const uint32_t *rows,
     HIP_TRY(d_idx.alloc(m * sizeof(uint32_t)));
     HIP_TRY(d_out.alloc(m * c->dim * sizeof(float)));
     HIP_TRY(hipMemcpy(d_idx.p, rows, m * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (c->half()) HIP_TRY(pqv::launch_widen_rows_h(c->d_rows_h, d_idx.as<uint32_t>(), m, c->dim, d_out.as<float>(), c->stream));
+    else
     HIP_TRY(pqv::launch_gather_rows(c->d_rows, d_idx.as<uint32_t>(), nullptr, m, c->dim,
                                     d_out.as<float>(), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2692,6 +2764,7 @@ static int pqv_index_build_impl(const pqv_corpus *corpus, uint32_t n_clusters, u
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
     *out = nullptr;
     if (!corpus) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
+    if (int rc = refuse_f16(corpus, "pqv_index_build")) return rc;
     return build_index_impl(corpus, n_clusters, max_iters, seed, workers, out);
 }
 extern "C" int pqv_index_build(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
@@ -2733,6 +2806,7 @@ int assign_range(const pqv_index *index, const pqv_corpus *corpus, uint64_t firs
 int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, uint32_t *cluster_out) {
     if (!index || !corpus) return fail(PQV_ERR_INVALID, "index/corpus must not be NULL");
     if (!cluster_out) return fail(PQV_ERR_INVALID, "cluster_out must not be NULL");
+    if (int rc = refuse_f16(corpus, "pqv_index_assign")) return rc;
     if (int rc = check_row_range(index, corpus, first_row, n_rows)) return rc;
     if (n_rows == 0) return PQV_OK;
     if (int rc = use_device(corpus->device)) return rc;
@@ -2750,6 +2824,7 @@ int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
     *out = nullptr;
     if (!index || !corpus) return fail(PQV_ERR_INVALID, "index/corpus must not be NULL");
+    if (int rc = refuse_f16(corpus, "pqv_index_append")) return rc;
     if (int rc = check_row_range(index, corpus, first_row, n_rows)) return rc;
     uint64_t bound = 0;
     if (!index->row_bound(&bound)) return PQV_ERR_HIP;
@@ -3084,6 +3159,7 @@ int index_compact_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_
     if (index->dim != corpus->dim)
         return fail(PQV_ERR_INVALID, "index dimension " + std::to_string(index->dim) +
                                          " does not match corpus dimension " + std::to_string(corpus->dim));
+    if (int rc = refuse_f16(corpus, "pqv_index_compact")) return rc;
     if (!corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
     const uint64_t n = corpus->n, n_pos = index->n_rows();
     const uint32_t dim = corpus->dim;
@@ -3305,6 +3381,7 @@ static int pqv_kmeans_impl(const pqv_corpus *sample, uint32_t k, uint32_t max_it
     if (!sample || !centroids) return fail(PQV_ERR_INVALID, "sample/centroids must not be NULL");
     if (k == 0) return fail(PQV_ERR_INVALID, "Cluster count must be > 0");
     if (sample->n == 0 || k > sample->n) return fail(PQV_ERR_INVALID, "n_clusters cannot exceed number of vectors");
+    if (int rc = refuse_f16(sample, "pqv_kmeans")) return rc;
     if (!sample->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
     if (int rc = use_device(sample->device)) return rc;
     DevBuf d_centroids;
@@ -3621,13 +3698,15 @@ static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, 
         for (uint32_t r : *rv)
             if (r >= corpus->n) return fail(PQV_ERR_INVALID, "index row id out of range for this corpus");
     }
-    if (!corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
+    const bool half = corpus->half();      // (pqv.h: half-precision corpora -- the rows as they are, no row-derived layout)
+    if (!corpus->d_rows && !half) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
+    if (half && (flags & PQV_PREPARE_COSINE)) return refuse_f16(corpus, "PQV_PREPARE_COSINE");
     if (int rc = use_device(corpus->device)) return rc;
     pqv_searcher *s = new (std::nothrow) pqv_searcher();
     if (!s) return fail(PQV_ERR_OOM, "host allocation failed");
     { static std::atomic<uint64_t> next_uid{1}; s->uid = next_uid.fetch_add(1, std::memory_order_relaxed); }
     s->device = corpus->device; s->dim = index->dim; s->sdim = index->dim; s->n_clusters = index->n_clusters;
-    if (!(flags & PQV_LAYOUT_ROW_ORDER) && (s->dim % 4) == 0 && (s->dim % 64) != 0) {
+    if (!half && !(flags & PQV_LAYOUT_ROW_ORDER) && (s->dim % 4) == 0 && (s->dim % 64) != 0) {
         // zero-padded storage: the cheapest tiling whose padding stays within a third of the row -- int8 images (a multiple
         // of 256 dims), else f16 (128), else f32 (64); rows of fewer than 48 dims stay as they are (exact kernels)
         auto up = [&](uint32_t m) { return (s->dim + m - 1) / m * m; };
@@ -3695,10 +3774,14 @@ static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, 
     {
         const char *e = std::getenv("PQV_IVF_COPY");
         const bool want_copy = e && *e && *e != '0';
-        s->images_only = !(flags & PQV_LAYOUT_ROW_ORDER) && !((flags & PQV_RELEASE_ROW_ORDER) && corpus->owned) && !want_copy && s->sdim == s->dim &&
+        s->images_only = !half && !(flags & PQV_LAYOUT_ROW_ORDER) && !((flags & PQV_RELEASE_ROW_ORDER) && corpus->owned) && !want_copy && s->sdim == s->dim &&
                          (s->dim % 64) == 0 && s->n > 0 && s->n / std::max<uint32_t>(1, s->n_clusters) >= 192;
     }
-    if ((flags & PQV_LAYOUT_ROW_ORDER) || s->images_only) {
+    if (half) {
+        s->d_mat_h = corpus->d_rows_h;
+        s->d_row_of = s->d_ids.as<uint32_t>();
+        s->d_final_ids = nullptr;
+    } else if ((flags & PQV_LAYOUT_ROW_ORDER) || s->images_only) {
         s->d_mat = corpus->d_rows;
         s->d_row_of = s->d_ids.as<uint32_t>();
         s->d_final_ids = nullptr;
@@ -3722,7 +3805,12 @@ static int pqv_searcher_create_impl(const pqv_index *index, pqv_corpus *corpus, 
     S_TRY(s->d_stats.alloc((8 + 16 * pqv::STATS_SLOTS) * sizeof(unsigned long long)));
     S_TRY(hipMemsetAsync(s->d_stats.p, 0, (8 + 16 * pqv::STATS_SLOTS) * sizeof(unsigned long long), s->stream));
 #endif
-    s->n_storage = (flags & PQV_LAYOUT_ROW_ORDER) ? corpus->n : s->n;
+    s->n_storage = ((flags & PQV_LAYOUT_ROW_ORDER) || half) ? corpus->n : s->n;
+    if (half) {      // no norms, no operand images: every search is the exact stream
+        S_TRY(hipStreamSynchronize(s->stream));
+        *out = s;
+        return PQV_OK;
+    }
     // The blocked MFMA-operand copy of the lists is built here, not inside the first query, whenever the wide screened path can apply
     // to this searcher (ensure_blocked_copy rebuilds it if an option changes its form).  int8 form: rows of a multiple of 256 dims,
     // IVF-ordered rows, finite data.  Where that copy is built right away, ITS first pass (the per-dimension extremes) vouches for the
@@ -3793,6 +3881,7 @@ static int pqv_table_searcher_create_impl(const pqv_index *const *indexes, uint3
     *out = nullptr;
     if (!indexes || !row_base || !corpus) return fail(PQV_ERR_INVALID, "indexes/row_base/corpus must not be NULL");
     if (n_files == 0) return fail(PQV_ERR_INVALID, "a table needs at least one indexed file");
+    if (int rc = refuse_f16(corpus, "pqv_table_searcher_create")) return rc;
     uint64_t kc_total = 0, rows_end = 0;
     for (uint32_t f = 0; f < n_files; ++f) {
         const pqv_index *ix = indexes[f];
@@ -4079,6 +4168,7 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     TopkPlan p{};
     const pqv_searcher::Opts &o = s->opt;
     if (metric == PQV_DOT) exact_stream = true;     // (pqv.h: always the exact stream, whatever the options say)
+    if (s->half()) exact_stream = true;             // (f16 rows: no screen images exist)
     p.np = probe_count(s, nprobe);
     // probe pass: every block scans 256 centroids (64 per wave)
     p.probe_bpl = (s->n_clusters + 255) / 256;
@@ -4934,7 +5024,7 @@ static int enqueue_tile_rerank(TopkCall &c) {
 static pqv::StreamArgs stream_args(const pqv_searcher *s, Scratch &sc, const float *d_queries_s, uint32_t nq, uint32_t np, uint32_t k,
                                    uint64_t max_candidates, int metric) {
     pqv::StreamArgs ra{};
-    ra.mat = s->d_mat; ra.row_of = s->d_row_of; ra.list_off = s->d_list_off.as<uint64_t>();
+    ra.mat = s->d_mat; ra.mat_h = s->d_mat_h; ra.row_of = s->d_row_of; ra.list_off = s->d_list_off.as<uint64_t>();
     ra.probe = sc.s_probe.as<uint32_t>(); ra.cand_base = sc.s_cand_base.as<uint64_t>();
     ra.queries = d_queries_s; ra.nq = nq; ra.nprobe = np; ra.dim = s->sdim; ra.k = k;
     ra.max_pos = max_candidates ? max_candidates : ~0ull; ra.metric = metric;
@@ -5065,6 +5155,8 @@ bool grouped_beyond_kernel_lists(const pqv_searcher *s, uint32_t k, uint32_t gro
 // PQV_DOT (pqv.h): every entry point works within the kernels' lists, and keyed / distinct calls do not take it.  Checked behind
 // validate_topk, before any device work.
 int dot_checks(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric, const SearchRequest *rq) {
+    // (f16 rows, pqv.h: the served calls take REF4 / SEQ only; every call with a request was refused by its entry point, by name)
+    if (metric == PQV_DOT || metric == PQV_COSINE) { if (int rc = refuse_f16(s, metric == PQV_DOT ? "PQV_DOT" : "PQV_COSINE")) return rc; }
     if (metric != PQV_DOT) return PQV_OK;
     if (rq && (rq->filtered() || rq->distinct())) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
     if (beyond_kernel_lists(s, k, nprobe)) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT takes k <= 1024 and at most 1024 probed lists per query");
@@ -5147,7 +5239,8 @@ int replay_with_clusters(const pqv_searcher *s, Scratch &sc, const float *d_quer
             ra.rows_per_block = 1024;
             ra.blocks_per_list = static_cast<uint32_t>((std::max<uint64_t>(1, s->max_list_len) + 1023) / 1024);
             ra.max_pos = ~0ull; ra.metric = metric; ra.out_f32 = sc.s_replay.as<float>();
-            HIP_TRY(launch_stream(ra, STREAM_DIST, s->stream));
+            ra.mat_h = s->d_mat_h;
+            HIP_TRY(s->half() ? launch_stream_h(ra, STREAM_DIST, s->stream) : launch_stream(ra, STREAM_DIST, s->stream));
             s->counters.kernel_launches += 1;
         }
         HIP_TRY(hipMemcpyAsync(d.data(), sc.s_replay.p, total * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -6069,6 +6162,7 @@ extern "C" int pqv_topk_masked(const pqv_searcher *s, const pqv_row_mask *mask, 
     return guard([&] {
         SearchRequest mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_masked")) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
 }
@@ -6079,6 +6173,7 @@ extern "C" int pqv_topk_masked_device(const pqv_searcher *s, const pqv_row_mask 
     return guard([&] {
         SearchRequest mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_masked_device")) return rc;
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
     });
@@ -6089,6 +6184,7 @@ extern "C" int pqv_range_search_masked(const pqv_searcher *s, const pqv_row_mask
     return guard([&] {
         SearchRequest mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_range_search_masked")) return rc;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
     });
@@ -6153,6 +6249,7 @@ extern "C" int pqv_topk_keyed(const pqv_searcher *s, const pqv_row_keys *keys, c
     return guard([&] {
         SearchRequest mv{};
         if (int rc = keyed_view(s, keys, qkeys, nq, mask, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_keyed")) return rc;
         mv.rows.h_qkeys = qkeys;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
@@ -6164,6 +6261,7 @@ extern "C" int pqv_topk_keyed_device(const pqv_searcher *s, const pqv_row_keys *
     return guard([&] {
         SearchRequest mv{};
         if (int rc = keyed_view(s, keys, d_qkeys, nq, mask, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_keyed_device")) return rc;
         mv.rows.d_qkeys = static_cast<const int64_t *>(d_qkeys);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
@@ -6176,6 +6274,7 @@ extern "C" int pqv_range_search_keyed(const pqv_searcher *s, const pqv_row_keys 
     return guard([&] {
         SearchRequest mv{};
         if (int rc = keyed_view(s, keys, qkeys, nq, mask, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_range_search_keyed")) return rc;
         mv.rows.h_qkeys = qkeys;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
@@ -6224,6 +6323,7 @@ extern "C" int pqv_topk_filtered(const pqv_searcher *s, const pqv_row_keys *keys
     return guard([&] {
         SearchRequest mv{};
         if (int rc = filtered_view(s, keys, filter, nq, mask, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_filtered")) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
 }
@@ -6234,6 +6334,7 @@ extern "C" int pqv_topk_filtered_device(const pqv_searcher *s, const pqv_row_key
     return guard([&] {
         SearchRequest mv{};
         if (int rc = filtered_view(s, keys, filter, nq, mask, false, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_filtered_device")) return rc;
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
     });
@@ -6266,6 +6367,7 @@ extern "C" int pqv_topk_expand(const pqv_searcher *s, const pqv_row_keys *keys, 
     return guard([&] {
         SearchRequest mv{};
         if (int rc = expand_view(s, keys, filter, mask, nq, k, nprobe, max_nprobe, metric, true, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_expand")) return rc;
         mv.expand.h_used = nprobe_used;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
     });
@@ -6277,6 +6379,7 @@ extern "C" int pqv_topk_expand_device(const pqv_searcher *s, const pqv_row_keys 
     return guard([&] {
         SearchRequest mv{};
         if (int rc = expand_view(s, keys, filter, mask, nq, k, nprobe, max_nprobe, metric, false, d_tie_flags != nullptr, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_expand_device")) return rc;
         mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, d_tie_flags, hip_stream, &mv);
@@ -6309,6 +6412,7 @@ extern "C" int pqv_topk_depth(const pqv_searcher *s, const pqv_probe_depth *dept
     return guard([&] {
         SearchRequest mv{};
         if (int rc = depth_view(s, depth, nq, k, nprobe, metric, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_depth")) return rc;
         if (depth->kind == PQV_DEPTH_GIVEN) mv.expand.h_depths = static_cast<const uint32_t *>(depth->depths);
         mv.expand.h_used = nprobe_used;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
@@ -6320,6 +6424,7 @@ extern "C" int pqv_topk_depth_device(const pqv_searcher *s, const pqv_probe_dept
     return guard([&] {
         SearchRequest mv{};
         if (int rc = depth_view(s, depth, nq, k, nprobe, metric, d_tie_flags != nullptr, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_depth_device")) return rc;
         if (depth->kind == PQV_DEPTH_GIVEN) mv.expand.d_depths = static_cast<const uint32_t *>(depth->depths);
         mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
@@ -6333,6 +6438,7 @@ extern "C" int pqv_range_search_filtered(const pqv_searcher *s, const pqv_row_ke
     return guard([&] {
         SearchRequest mv{};
         if (int rc = filtered_view(s, keys, filter, nq, mask, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_range_search_filtered")) return rc;
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
     });
@@ -6704,6 +6810,7 @@ extern "C" int pqv_topk_partition_device(const pqv_searcher *s, const pqv_key_pa
         if (int rc = partition_checks(s, part, filter, nullptr, nullptr, mask, nq, k, metric, false, 0, "pqv_topk_partition takes k <= 1024")) return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_topk_partition_device")) return rc;
         if (int rc = use_device(s->device)) return rc;
         hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
         const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
@@ -6722,6 +6829,7 @@ extern "C" int pqv_topk_partition(const pqv_searcher *s, const pqv_key_partition
         if (int rc = partition_checks(s, part, filter, nullptr, nullptr, mask, nq, k, metric, true, query_len, "pqv_topk_partition takes k <= 1024")) return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_topk_partition")) return rc;
         if (int rc = use_device(s->device)) return rc;
         // (per list entry 12 B; beside the lists the rows, distances and n_found / n_candidates, and an IN slice)
         return topk_partition_host_body(
@@ -6816,9 +6924,10 @@ static int enqueue_rows(const pqv_searcher *s, Scratch &sc, const RowMap &map, c
 }
 // the device forms behind their checks (k == 0: scores)
 static int rows_device_impl(const pqv_searcher *s, const void *d_lims, const void *d_rows, const pqv_row_mask *mask, const void *d_queries,
-                            uint32_t nq, uint32_t k, int metric, int sqrt_out, const TopkOut &out, void *hip_stream) {
+                            uint32_t nq, uint32_t k, int metric, int sqrt_out, const TopkOut &out, void *hip_stream, const char *entry) {
     if (nq == 0) return PQV_OK;
     if (!d_queries) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+    if (int rc = refuse_f16(s, entry)) return rc;
     if (int rc = use_device(s->device)) return rc;
     RowMap map{};
     if (int rc = ensure_row_map(s, map)) return rc;
@@ -6839,7 +6948,7 @@ extern "C" int pqv_topk_rows_device(const pqv_searcher *s, const void *d_lims, c
         if (k > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_rows takes k <= 1024");
         const TopkOut out{static_cast<uint32_t *>(d_row_idx), static_cast<float *>(d_dist), static_cast<uint32_t *>(d_n_found),
                           static_cast<uint64_t *>(d_n_candidates)};
-        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, k, metric, sqrt_out, out, hip_stream);
+        return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, k, metric, sqrt_out, out, hip_stream, "pqv_topk_rows_device");
     });
 }
 extern "C" int pqv_score_rows_device(const pqv_searcher *s, const void *d_lims, const void *d_cand_rows, const pqv_row_mask *mask,
@@ -6848,7 +6957,7 @@ extern "C" int pqv_score_rows_device(const pqv_searcher *s, const void *d_lims, 
         if (int rc = rows_checks(s, d_lims, d_cand_rows, mask, nq, nullptr, metric, false, 0, "pqv_score_rows")) return rc;
         if (nq && !d_dist) return fail(PQV_ERR_INVALID, "dist must not be NULL");
         return rows_device_impl(s, d_lims, d_cand_rows, mask, d_queries, nq, 0, metric, sqrt_out, TopkOut{nullptr, static_cast<float *>(d_dist)},
-                                hip_stream);
+                                hip_stream, "pqv_score_rows_device");
     });
 }
 // the host forms' request: the slices travel through host_batches as an IN filter's do
@@ -6866,6 +6975,7 @@ extern "C" int pqv_topk_rows(const pqv_searcher *s, const uint64_t *lims, const 
         if (k > 1024) return fail(PQV_ERR_UNSUPPORTED, "pqv_topk_rows takes k <= 1024");
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_topk_rows")) return rc;
         if (int rc = use_device(s->device)) return rc;
         RowMap map{};
         if (int rc = ensure_row_map(s, map)) return rc;
@@ -6886,6 +6996,7 @@ extern "C" int pqv_score_rows(const pqv_searcher *s, const uint64_t *lims, const
         if (nq && lims[nq] != lims[0] && !dist) return fail(PQV_ERR_INVALID, "dist must not be NULL");
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_score_rows")) return rc;
         if (int rc = use_device(s->device)) return rc;
         RowMap map{};
         if (int rc = ensure_row_map(s, map)) return rc;
@@ -6972,6 +7083,7 @@ extern "C" int pqv_mmr_select_device(const pqv_searcher *s, const void *d_cand_r
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (n && (!d_cand_rows || !d_cand_dist)) return fail(PQV_ERR_INVALID, "cand_rows/cand_dist must not be NULL");
         if (!d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "row_idx/dist must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_mmr_select_device")) return rc;
         if (int rc = use_device(s->device)) return rc;
         RowMap map{};
         if (int rc = ensure_row_map(s, map)) return rc;
@@ -6994,6 +7106,7 @@ extern "C" int pqv_mmr_select(const pqv_searcher *s, const uint32_t *cand_rows, 
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (n && (!cand_rows || !cand_dist)) return fail(PQV_ERR_INVALID, "cand_rows/cand_dist must not be NULL");
         if (!row_idx || !dist) return fail(PQV_ERR_INVALID, "row_idx/dist must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_mmr_select")) return rc;
         if (int rc = use_device(s->device)) return rc;
         RowMap map{};
         if (int rc = ensure_row_map(s, map)) return rc;
@@ -7066,6 +7179,7 @@ extern "C" int pqv_topk_mmr_device(const pqv_searcher *s, const pqv_row_mask *ma
         if (int rc = mmr_checks(s, mask, k, fetch_k, lambda, true, nprobe, metric, false, 0)) return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_topk_mmr_device")) return rc;
         if (int rc = use_device(s->device)) return rc;
         RowMap map{};
         if (int rc = ensure_row_map(s, map)) return rc;
@@ -7088,6 +7202,7 @@ extern "C" int pqv_topk_mmr(const pqv_searcher *s, const pqv_row_mask *mask, con
         if (int rc = mmr_checks(s, mask, k, fetch_k, lambda, true, nprobe, metric, true, query_len)) return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_topk_mmr")) return rc;
         if (int rc = use_device(s->device)) return rc;
         RowMap map{};
         if (int rc = ensure_row_map(s, map)) return rc;
@@ -7240,6 +7355,7 @@ static int range_search_partition_impl(const pqv_searcher *s, const pqv_key_part
     if (std::isnan(radius)) return fail(PQV_ERR_INVALID, "radius must not be NaN");
     if (!lims_out || !rows_out || !dist_out) return fail(PQV_ERR_INVALID, "lims/row_idx/dist must not be NULL");
     if (nq && !queries) return fail(PQV_ERR_INVALID, "queries must not be NULL");
+    if (int rc = refuse_f16(s, "pqv_range_search_partition")) return rc;
     *lims_out = nullptr; *rows_out = nullptr; *dist_out = nullptr;
     std::unique_ptr<uint64_t, HostFree> lims(static_cast<uint64_t *>(std::malloc((static_cast<size_t>(nq) + 1) * sizeof(uint64_t))));
     std::unique_ptr<uint32_t, HostFree> rows(static_cast<uint32_t *>(std::malloc(sizeof(uint32_t))));
@@ -7319,6 +7435,7 @@ extern "C" int pqv_topk_partition_grouped_device(const pqv_searcher *s, const pq
             return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!d_queries || !d_row_idx || !d_dist) return fail(PQV_ERR_INVALID, "device pointers must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_topk_partition_grouped_device")) return rc;
         if (int rc = use_device(s->device)) return rc;
         hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
         const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
@@ -7341,6 +7458,7 @@ extern "C" int pqv_topk_partition_grouped(const pqv_searcher *s, const pqv_key_p
             return rc;
         if (nq == 0) return static_cast<int>(PQV_OK);
         if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+        if (int rc = refuse_f16(s, "pqv_topk_partition_grouped")) return rc;
         if (int rc = use_device(s->device)) return rc;
         // (the scratch of BOTH passes: 20 B per entry of pass 1's lists, 16 B per entry of k * m and a count in pass 2's; the group
         // outputs beside the rows)
@@ -7459,6 +7577,7 @@ extern "C" int pqv_topk_distinct(const pqv_searcher *s, const pqv_row_keys *keys
     return guard([&] {
         SearchRequest mv{};
         if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_distinct")) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
                              &mv, group_key);
     });
@@ -7469,6 +7588,7 @@ extern "C" int pqv_topk_distinct_device(const pqv_searcher *s, const pqv_row_key
     return guard([&] {
         SearchRequest mv{};
         if (int rc = distinct_view(s, keys, mask, k, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_distinct_device")) return rc;
         mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
@@ -7493,6 +7613,7 @@ extern "C" int pqv_topk_grouped(const pqv_searcher *s, const pqv_row_keys *keys,
     return guard([&] {
         SearchRequest mv{};
         if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_grouped")) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
                              &mv, group_key, group_rows);
     });
@@ -7504,6 +7625,7 @@ extern "C" int pqv_topk_grouped_device(const pqv_searcher *s, const pqv_row_keys
     return guard([&] {
         SearchRequest mv{};
         if (int rc = grouped_view(s, keys, mask, k, group_size, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_grouped_device")) return rc;
         mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         mv.groups.d_rows = static_cast<uint32_t *>(d_group_rows);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
@@ -7537,6 +7659,7 @@ extern "C" int pqv_topk_distinct_filtered(const pqv_searcher *s, const pqv_row_k
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_distinct_filtered")) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
                              &mv, group_key);
     });
@@ -7548,6 +7671,7 @@ extern "C" int pqv_topk_distinct_filtered_device(const pqv_searcher *s, const pq
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, false, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_distinct_filtered_device")) return rc;
         mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
                                     d_n_candidates, nullptr, hip_stream, &mv);
@@ -7561,6 +7685,7 @@ extern "C" int pqv_topk_grouped_filtered(const pqv_searcher *s, const pqv_row_ke
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_grouped_filtered")) return rc;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
                              &mv, group_key, group_rows);
     });
@@ -7573,6 +7698,7 @@ extern "C" int pqv_topk_grouped_filtered_device(const pqv_searcher *s, const pqv
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_filtered_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, false, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_grouped_filtered_device")) return rc;
         mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         mv.groups.d_rows = static_cast<uint32_t *>(d_group_rows);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
@@ -7621,6 +7747,7 @@ extern "C" int pqv_topk_distinct_expand(const pqv_searcher *s, const pqv_row_key
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, nprobe, max_nprobe, metric, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_distinct_expand")) return rc;
         mv.expand.h_used = nprobe_used;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
                              &mv, group_key);
@@ -7634,6 +7761,7 @@ extern "C" int pqv_topk_distinct_expand_device(const pqv_searcher *s, const pqv_
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, nullptr, nprobe, max_nprobe, metric, false, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_distinct_expand_device")) return rc;
         mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
         return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, 0, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found, d_n_candidates,
@@ -7648,6 +7776,7 @@ extern "C" int pqv_topk_grouped_expand(const pqv_searcher *s, const pqv_row_keys
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, nprobe, max_nprobe, metric, true, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_grouped_expand")) return rc;
         mv.expand.h_used = nprobe_used;
         return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, 0, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates,
                              &mv, group_key, group_rows);
@@ -7661,6 +7790,7 @@ extern "C" int pqv_topk_grouped_expand_device(const pqv_searcher *s, const pqv_r
     return guard([&] {
         SearchRequest mv{};
         if (int rc = group_expand_view(s, group_keys, filter_keys, filter, mask, nq, k, &group_size, nprobe, max_nprobe, metric, false, mv)) return rc;
+        if (int rc = refuse_f16(s, "pqv_topk_grouped_expand_device")) return rc;
         mv.groups.d_keys = static_cast<int64_t *>(d_group_key);
         mv.groups.d_rows = static_cast<uint32_t *>(d_group_rows);
         mv.expand.d_used = static_cast<uint32_t *>(d_nprobe_used);
@@ -7745,6 +7875,12 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
         if (int rc = pqv_searcher_describe_impl(c, nq, k, nprobe, PQV_L2SQ_REF4, buf + used, len - used)) return rc;
         const size_t end = std::strlen(buf);
         std::snprintf(buf + end, len - end, "; distances halved in the final write-out (merge_kernel / range write-out)");
+        return PQV_OK;
+    }
+    if (s->half()) {       // (pqv.h: half-precision corpora -- one route, whatever the options say)
+        std::snprintf(buf, len, "f16 rows: %s, then stream_h_kernel (kernels_half.hip: the exact stream over 2-byte rows, widened per load; %s) + merge_kernel",
+                      beyond_kernel_lists(s, k, nprobe) ? "host probe" : "the centroid probe over the f32 centroids",
+                      beyond_kernel_lists(s, k, nprobe) ? "STREAM_DIST, selection by the reference's heap on the host" : "STREAM_TOPK; STREAM_DIST for tie replays");
         return PQV_OK;
     }
     std::lock_guard<std::mutex> lock(s->mu);
@@ -7850,6 +7986,7 @@ static int pqv_searcher_footprint_impl(const pqv_searcher *s, uint64_t *row_orde
     if (!s) return fail(PQV_ERR_INVALID, "searcher must not be NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     if (row_order_bytes) *row_order_bytes = s->corpus && s->corpus->d_rows ? s->corpus->capacity * s->corpus->dim * sizeof(float) : 0;
+    if (row_order_bytes && s->half()) *row_order_bytes = s->corpus->capacity * s->corpus->dim * sizeof(uint16_t);      // (f16 rows: 2 bytes per value)
     if (ivf_rows_bytes) *ivf_rows_bytes = s->d_mat_ivf.p ? s->d_mat_ivf.bytes : 0;
     if (blocked_bytes) *blocked_bytes = (s->d_mat_blk_op[0].p ? s->d_mat_blk_op[0].bytes : 0) + (s->d_mat_blk_op[1].p ? s->d_mat_blk_op[1].bytes : 0) +
                                         (s->d_mat_blk_op[2].p ? s->d_mat_blk_op[2].bytes : 0);
@@ -8044,6 +8181,7 @@ static int pqv_brute_topk_impl(const pqv_corpus *c, const float *queries, uint32
                                          ", got " + std::to_string(query_len));
     if (nq == 0) return PQV_OK;
     if (!queries || !row_idx || !dist) return fail(PQV_ERR_INVALID, "queries/row_idx/dist must not be NULL");
+    if (int rc = refuse_f16(c, "pqv_brute_topk")) return rc;
     if (!c->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
     if (int rc = use_device(c->device)) return rc;
     hipStream_t stream = c->stream;

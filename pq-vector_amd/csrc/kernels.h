@@ -65,6 +65,8 @@ struct StreamArgs {
     // optional [nq]: PACKED segments -- query q's begins at seg_off[q] instead of q * seg_stride (range_seg_base; the partition
     // range search, whose segment lengths are its per-query candidate counts).  nullptr: the uniform stride.
     const uint64_t *seg_off;
+    // launch_stream_h only (a searcher over an f16 corpus): the row storage [*, dim] as IEEE binary16 bits, in place of `mat`
+    const uint16_t *mat_h;
 };
 // the first entry of query q's hit segment, for the kernel that appends (emit_range_hit) and the ones that sort and write out
 __host__ __device__ __forceinline__ uint64_t range_seg_base(const uint64_t *seg_off, uint64_t seg_stride, uint32_t q) {
@@ -73,6 +75,14 @@ __host__ __device__ __forceinline__ uint64_t range_seg_base(const uint64_t *seg_
 
 // Streaming exact-order squared-L2 pass (the re-rank kernel).  Returns hipError_t.
 hipError_t launch_stream(const StreamArgs &a, StreamMode mode, hipStream_t s);
+
+// ---- half-precision corpora (kernels_half.hip; pqv.h: pqv_corpus_create_f16) -------------------------------------------------
+// launch_stream's STREAM_TOPK / STREAM_DIST / STREAM_RANGE pass over 2-byte rows a.mat_h (stream_h_kernel): the same grid, walk,
+// keys and output formats, the distance the reference chain over the row widened to f32 (exact) -- bit-identical to launch_stream
+// over the widened rows.  metric PQV_L2SQ_REF4 / PQV_L2SQ_SEQ; a.mat is not read.  No load reaches behind a row's last byte.
+hipError_t launch_stream_h(const StreamArgs &a, StreamMode mode, hipStream_t s);
+// out[i, :] = rows[idx[i], :] widened to f32, i < m
+hipError_t launch_widen_rows_h(const uint16_t *rows, const uint32_t *idx, uint64_t m, uint32_t dim, float *out, hipStream_t s);
 
 // ---- row-masked searches (kernels_mask.hip) ------------------------------------------------------------------------------
 // A row mask on the device is a bitset over LIST POSITIONS: bit p = the caller's allow byte of the row position p reports.

@@ -32,7 +32,14 @@ public:
         check(pqv_corpus_upload(device, rows, n, dim, &h));
         h_.reset(h);
     }
+    // f16 rows as given: IEEE binary16 bit patterns (pqv.h: half-precision corpora)
+    Corpus(int device, const uint16_t *rows_f16, uint64_t n, uint32_t dim) {
+        pqv_corpus *h = nullptr;
+        check(pqv_corpus_upload_f16(device, rows_f16, n, dim, &h));
+        h_.reset(h);
+    }
     pqv_corpus *get() const { return h_.get(); }
+    bool is_f16() const { return pqv_corpus_dtype(h_.get()) == PQV_ROWS_F16; }
     uint64_t rows() const { return pqv_corpus_rows(h_.get()); }
     uint32_t dim() const { return pqv_corpus_dim(h_.get()); }
 private:
