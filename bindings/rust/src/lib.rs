@@ -242,6 +242,20 @@ impl Index {
         Ok(Index { raw })
     }
 
+    /// [`Index::assign`] over an f16 corpus (`pqv_index_assign_f16`): the nearest centroid of every row widened to f32.
+    pub fn assign_f16(&self, corpus: &Corpus, first_row: usize, n_rows: usize) -> Result<Vec<u32>> {
+        let mut out = vec![0u32; n_rows];
+        check(unsafe { sys::pqv_index_assign_f16(self.raw, corpus.raw, first_row as u64, n_rows as u64, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// [`Index::append`] over an f16 corpus (`pqv_index_append_f16`): the result equals the f32 call's on the widened column.
+    pub fn append_f16(&self, corpus: &Corpus, first_row: usize, n_rows: usize) -> Result<Index> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { sys::pqv_index_append_f16(self.raw, corpus.raw, first_row as u64, n_rows as u64, &mut raw) })?;
+        Ok(Index { raw })
+    }
+
     /// A new index with these centroids whose lists no longer hold the rows `r < remove.len()` with `remove[r] != 0`; order is
     /// kept, row ids stay what they were and the row bound is carried over.  Runs on `device` where there is one, else on the
     /// host with the same result.  `self` is not modified: searchers made from it keep answering as before.
@@ -333,6 +347,24 @@ impl IndexBuilder {
         let mut raw = ptr::null_mut();
         check(unsafe {
             sys::pqv_index_build(corpus.raw, n_clusters, u32::try_from(self.max_iters)?, self.seed, self.workers as u32, &mut raw)
+        })?;
+        Ok(Index { raw })
+    }
+
+    /// The same build over an f16 corpus (`pqv_index_build_f16`): the index of the widened column, byte for byte, from the
+    /// 2-byte rows as they lie in device memory.
+    pub fn build_f16(&self, corpus: &Corpus) -> Result<Index> {
+        if self.max_iters == 0 {
+            return Err("max_iters must be > 0".into());
+        }
+        let n_clusters = match self.n_clusters {
+            Some(0) => return Err("n_clusters must be > 0".into()),
+            Some(v) => u32::try_from(v)?,
+            None => 0,
+        };
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            sys::pqv_index_build_f16(corpus.raw, n_clusters, u32::try_from(self.max_iters)?, self.seed, self.workers as u32, &mut raw)
         })?;
         Ok(Index { raw })
     }

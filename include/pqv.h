@@ -222,8 +222,10 @@ void pqv_corpus_free(pqv_corpus *corpus);
  *               calls (the text names the metric: "PQV_DOT does not take f16 corpora"), the masked, keyed, filtered, expanding,
  *               depth, distinct, grouped, partition, candidate-list and MMR calls, pqv_table_searcher_create, pqv_brute_topk, pqv_kmeans, pqv_index_build,
  *               pqv_index_assign, pqv_index_append and pqv_index_compact.  pqv_index_remove* reads no rows and is unchanged.
- *   index       comes from pqv_index_build_host (on widened rows), pqv_index_from_bytes or pqv_index_from_parts: building from
- *               f16 rows on the device is out of scope, so a column that only fits as f16 needs centroids trained elsewhere. */
+ *               (The unsuffixed build / assign / append calls keep refusing: their f16 forms are the _f16 calls below.)
+ *   index       pqv_index_build_f16, pqv_index_assign_f16 and pqv_index_append_f16 (below, behind their f32 siblings) build,
+ *               assign and append straight from the 2-byte rows; the result is what the f32 call gives on the widened column,
+ *               byte for byte.  pqv_index_build_host (on widened rows), pqv_index_from_bytes and pqv_index_from_parts serve too. */
 #define PQV_ROWS_F32 0
 #define PQV_ROWS_F16 1
 int pqv_corpus_create_f16(int device, uint64_t capacity_rows, uint32_t dim, pqv_corpus **out);
@@ -269,6 +271,17 @@ int pqv_index_assign(const pqv_index *index, const pqv_corpus *corpus, uint64_t 
  * indexed row id + 1), which keeps every list ascending; rows between the bound and first_row are simply not indexed.
  * n_rows == 0 yields a copy. */
 int pqv_index_append(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out);
+/* The three calls above over an f16 corpus (half-precision corpora): arguments, checks, error texts and results are their
+ * siblings'; the result is DEFINED as the sibling's on the rows widened to f32 (an exact conversion) -- the index blob and every
+ * assignment equal, byte for byte.  The training sample is widened as it is gathered and k-means runs on it unchanged; the
+ * final assignment reads the 2-byte rows as they are stored (assign_h_wide_kernel: the rows are the matrix instruction's
+ * operand, no image of the column is written; assign_h_kernel where dim % 8 != 0, below 128 centroids or with a non-finite
+ * value).  They REQUIRE an f16 corpus: an f32 one is PQV_ERR_INVALID "corpus rows are f32".  The index goes straight into
+ * pqv_searcher_create(index, the f16 corpus): upload, build, search, append rows, append to the index, search. */
+int pqv_index_build_f16(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
+                        uint64_t seed, uint32_t workers, pqv_index **out);
+int pqv_index_assign_f16(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, uint32_t *cluster_out);
+int pqv_index_append_f16(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out);
 /* ---- index remove and compact: deleted rows leave the lists, then HBM ---------------------
  * pqv_index_remove* is the logical delete.  A NEW index: the centroids of `index` bit for bit, n_clusters unchanged, list c =
  * list c of `index` without the removed rows, order kept (a list that loses every row stays, empty).  Row ids stay what they

@@ -124,6 +124,9 @@ SIGNATURES = {
     "pqv_index_build": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
     "pqv_index_assign": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u32p]),
     "pqv_index_append": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "pqv_index_build_f16": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
+    "pqv_index_assign_f16": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u32p]),
+    "pqv_index_append_f16": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "pqv_index_remove": (C.c_int, [vp, C.c_int, u8p, C.c_uint64, C.POINTER(vp)]),
     "pqv_index_remove_device": (C.c_int, [vp, C.c_int, vp, C.c_uint64, vp, C.POINTER(vp)]),
     "pqv_index_remove_rows": (C.c_int, [vp, C.c_int, u32p, C.c_uint64, C.POINTER(vp)]),

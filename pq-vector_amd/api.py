@@ -282,16 +282,20 @@ class Index:
             self._row_bound = int(rows.max()) + 1 if rows.size else 0
         return self._row_bound
 
-    def assign(self, corpus, first_row=0, n_rows=None):
+    def assign(self, corpus, first_row=0, n_rows=None, _call="pqv_index_assign"):
         """Nearest centroid (src/ivf/index.rs:244-257) of corpus rows [first_row, first_row + n_rows) under this index'
         centroids; n_rows None = to the end of the corpus.  -> uint32 [n_rows]."""
         if n_rows is None:
             n_rows = max(corpus.rows - first_row, 0)
         out = np.empty(n_rows, dtype=np.uint32)
-        _check(_ffi.lib().pqv_index_assign(self._h, corpus._h, first_row, n_rows, out.ctypes.data_as(u32p)))
+        _check(getattr(_ffi.lib(), _call)(self._h, corpus._h, first_row, n_rows, out.ctypes.data_as(u32p)))
         return out
 
-    def append(self, corpus, first_row=None, n_rows=None):
+    def assign_f16(self, corpus, first_row=0, n_rows=None):
+        """assign() over an f16 corpus (pqv_index_assign_f16): the nearest centroid of each row widened to f32."""
+        return self.assign(corpus, first_row, n_rows, _call="pqv_index_assign_f16")
+
+    def append(self, corpus, first_row=None, n_rows=None, _call="pqv_index_append"):
         """A new Index: these centroids, every list followed by the rows of [first_row, first_row + n_rows) assigned to it,
         ascending (pqv_index_append).  first_row None = this index' row bound, n_rows None = to the end of the corpus, so
         `corpus.append(batch); index = index.append(corpus)` is the whole ingest step.  This index is not modified."""
@@ -300,8 +304,12 @@ class Index:
         if n_rows is None:
             n_rows = max(corpus.rows - first_row, 0)
         h = vp()
-        _check(_ffi.lib().pqv_index_append(self._h, corpus._h, first_row, n_rows, C.byref(h)))
+        _check(getattr(_ffi.lib(), _call)(self._h, corpus._h, first_row, n_rows, C.byref(h)))
         return Index(h, row_bound=first_row + n_rows)
+
+    def append_f16(self, corpus, first_row=None, n_rows=None):
+        """append() over an f16 corpus (pqv_index_append_f16): `corpus.append(halves); index = index.append_f16(corpus)`."""
+        return self.append(corpus, first_row, n_rows, _call="pqv_index_append_f16")
 
     def remove(self, rows=None, *, flags=None, where=None, device=0, stream=0):
         """A new Index: these centroids, every list without the removed rows, order kept (pqv_index_remove*).  Row ids stay what
@@ -431,14 +439,14 @@ class IndexBuilder:
         if self._embedding_column is None or not str(self._embedding_column).strip():
             raise PqvError(_ffi.PQV_ERR_INVALID, "Embedding column name cannot be empty")   # mod.rs:25
 
-    def _build_on(self, corpus):
+    def _build_on(self, corpus, half=False):
         nc, mi, seed, workers = self._config()
         if self._centroids is not None:
             k, dim = self._centroids.shape
             empty = Index.from_parts(dim, self._centroids, [np.zeros(0, np.uint32)] * k)
-            return empty.append(corpus, 0, corpus.rows)
+            return empty.append_f16(corpus, 0, corpus.rows) if half else empty.append(corpus, 0, corpus.rows)
         h = vp()
-        _check(_ffi.lib().pqv_index_build(corpus._h, nc, mi, seed, workers, C.byref(h)))
+        _check((_ffi.lib().pqv_index_build_f16 if half else _ffi.lib().pqv_index_build)(corpus._h, nc, mi, seed, workers, C.byref(h)))
         return Index(h, row_bound=corpus.rows)
 
     def _load_parquet(self):
@@ -491,6 +499,13 @@ class IndexBuilder:
         _check(_ffi.lib().pqv_index_build_host(self._device, flat.ctypes.data_as(f32p), flat.size,
                                                dim, nc, mi, seed, workers, C.byref(h)))
         return Index(h)
+
+    def build_f16(self):
+        """build() over an f16 Corpus (pqv_index_build_f16; with_centroids: pqv_index_append_f16): the index of the widened column,
+        byte for byte, made from the 2-byte rows as they lie in HBM.  It goes straight into Searcher(index, corpus)."""
+        if not isinstance(self._source, Corpus):
+            raise PqvError(_ffi.PQV_ERR_INVALID, "build_f16 needs an f16 Corpus as source")
+        return self._build_on(self._source, half=True)
 
 
 # ---------------------------------------------------------------------------------------

@@ -2613,6 +2613,145 @@ int assign_rows(const float *d_rows, uint64_t n, uint32_t dim, const float *d_ce
     return ladder.run(d_rows, n, d_centroids, k, dim, d_cluster, stream, decided);
 }
 
+// ---------------------------------------------------------------------------------------
+// The same stage over 2-byte rows (pqv_index_build_f16 / _assign_f16 / _append_f16; kernels_half_build.hip): the
+// result is the reference's nearest_centroid on the rows widened to f32.  Two tiers: the screen on the f16 matrix pipe with the
+// rows AS STORED for the row-side operand -- no image of the rows, no second pass over the column; scratch is the candidate
+// buffers alone --, where dim % 8 == 0, GemmAssign::applicable holds (PQV_ASSIGN_GEMM=0: off) and every norm is finite; else the
+// exact kernel.  With  |x - c|^2 = |x - mu|^2 + s_c,  s_c = b_c - 2 x.(c - mu),  b_c = |c - mu|^2 + 2 mu.(c - mu)  the kernel's
+// score  t_c = fl(b_c) - kA acc  (acc: the f32 contraction of the row with GemmAssign's image of (c - mu) cscale, kA = 2 / cscale)
+// is within  E = xs gA + gB  of s_c per 32-centroid group, xs >= |x|:
+//   gA = 2 gcs eps + kA c1      eps = 1.01 2^-11 (the image's rounding, the f32 subtraction and scaling before it)
+//                                     + (2 dim_p + 16) 2^-24 (f32 accumulation over dim_p exact products; kA; the score's roundings)
+//                               c1  = 1.01 sqrt(dim) (2^-25 + 2^-14): image elements rounded in the subnormal range; subnormal
+//                                     image elements, should the matrix pipe flush them
+//   gB = c2 gcs + c3 gcn + c4   c2  = 2.02 sqrt(dim) 2^-14 (subnormal ROW elements, should the pipe flush them) + 2 c3 |mu|
+//                               c3  = 2^-21: b_c summed in f64 and rounded once, the score's roundings; |b_c| <= gcn + 2 |mu| gcs
+//                               c4  = the product of the two subnormal allowances
+// gcs >= max |c - mu| and gcn >= max |c - mu|^2 of the group (GemmAssign's, raised by their own summation margin).  The row
+// operand carries no rounding at all.  |x| stands where the f32 form has |x - mu|: rows far from the origin screen worse.
+// ---------------------------------------------------------------------------------------
+struct HalfAssign {
+    GemmAssign gemm;          // set_centroids alone: the centring vector, the sorted centroid images, perm, the group maxima, the scale
+    DevBuf bias, grp, cand, cand_t, cnt, best_t, pub, flag, rstats;
+    std::vector<float> h_mu, h_grp;
+    std::vector<hipEvent_t> kernel_ev;
+    bool time_kernels = false;
+    double t0 = 0.0;
+    ~HalfAssign() { for (hipEvent_t e : kernel_ev) (void)hipEventDestroy(e); }
+
+    static bool screen_applicable(uint32_t dim, uint32_t k) {
+        return (dim % 8) == 0 && GemmAssign::applicable(dim, k) && static_cast<uint64_t>((dim + 63) / 64 * 64) * 2 * 512 < 0x7FFFFFFFull;
+    }
+    // the screen + resolve over d_rows_h [n, dim]; *fallback = true where it does not decide (a non-finite row, a degenerate table)
+    int screen(const uint16_t *d_rows_h, uint64_t n, const float *d_centroids, uint32_t k, uint32_t dim, uint32_t *d_cluster, hipStream_t stream,
+               bool *fallback) {
+        using namespace pqv;
+        *fallback = true;
+        bool bad_c = false;
+        if (int rc = gemm.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
+        if (bad_c || !gemm.wide) return PQV_OK;
+        const uint32_t dim_p = gemm.dim_p, kc_pad = gemm.kc_pad, ngrp = kc_pad / 32, cap = gemm.cap;
+        const float cscale = 256.0f / gemm.cmaxs, kA = 2.0f / cscale;
+        h_mu.resize(dim);
+        HIP_TRY(hipMemcpyAsync(h_mu.data(), gemm.mu.p, static_cast<size_t>(dim) * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        double mu2 = 0.0;
+        for (float v : h_mu) mu2 += static_cast<double>(v) * v;
+        const double mun = std::sqrt(mu2) * 1.000001;
+        if (!(mun < 1.0e18) || !(kA > 0.0f && kA < 3.0e38f)) return PQV_OK;
+        const double u = 5.9604644775390625e-08, sd = std::sqrt(static_cast<double>(dim));
+        const double up = 1.0 + (center_normalize_f16_sum_depth(dim) + 4) * u;
+        const double eps = 1.01 * 4.8828125e-04 + (2.0 * dim_p + 16.0) * u;
+        const double A0 = sd * 2.98023223876953125e-08, F = sd * 6.103515625e-05;
+        const double c1 = 1.01 * (A0 + F), c3 = 4.76837158203125e-07, c2 = 2.02 * F + 2.0 * c3 * mun, c4 = 1.01 * kA * F * A0 + 1.0e-30;
+        auto upf = [](double v) { return std::nextafter(static_cast<float>(v * 1.00001), INFINITY); };
+        h_grp.resize(2 * static_cast<size_t>(ngrp));
+        for (uint32_t g = 0; g < ngrp; ++g) {
+            const double gcs = gemm.h_grp[g] * up, gcn = gemm.h_grp[ngrp + g] * up;
+            h_grp[g] = upf(2.0 * gcs * eps + kA * c1); h_grp[ngrp + g] = upf(c2 * gcs + c3 * gcn + c4);
+        }
+        HIP_TRY(grp.ensure(h_grp.size() * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(grp.p, h_grp.data(), h_grp.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(bias.ensure(static_cast<size_t>(kc_pad) * sizeof(float)));
+        HIP_TRY(launch_half_bias(d_centroids, gemm.mu.as<float>(), gemm.d_perm.as<uint32_t>(), k, kc_pad, dim, bias.as<float>(), stream));
+        const uint64_t ch = std::min<uint64_t>(gemm.chunk, std::max<uint64_t>(1, n));
+        HIP_TRY(cand.ensure(ch * cap * sizeof(uint32_t))); HIP_TRY(cand_t.ensure(ch * cap * sizeof(float)));
+        HIP_TRY(cnt.ensure(ch * sizeof(uint32_t))); HIP_TRY(best_t.ensure(ch * sizeof(float))); HIP_TRY(pub.ensure(ch * sizeof(float)));
+        HIP_TRY(flag.ensure(sizeof(uint32_t))); HIP_TRY(rstats.ensure(2 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), stream));
+        HIP_TRY(hipMemsetAsync(rstats.p, 0, 2 * sizeof(unsigned long long), stream));
+        AssignHalfArgs w{};
+        w.c16 = gemm.c16.as<uint16_t>(); w.bias = bias.as<float>(); w.perm = gemm.d_perm.as<uint32_t>();
+        w.grp_a = grp.as<float>(); w.grp_b = grp.as<float>() + ngrp;
+        w.kc = k; w.kc_pad = kc_pad; w.dim = dim; w.dim_p = dim_p; w.kA = kA;
+        w.cm = static_cast<float>(dim / 4 + 16) * 1.1920928955078125e-07f;          // GemmAssign::run's margin of the reference chain
+        w.mun = upf(mun);
+        // the kernel's |x|^2: dim_p / 4 two-term dot instructions and one add per lane, each taken as three roundings, twice over;
+        // a subnormal half squares to less than 2^-28
+        w.xn_up = static_cast<float>(1.0 + (dim_p + 16.0) * 2.0 * u); w.xn_add = upf(dim * 3.7252902984619140625e-09);
+        w.cand = cand.as<uint32_t>(); w.cand_t = cand_t.as<float>(); w.cand_cnt = cnt.as<uint32_t>(); w.best_t = best_t.as<float>();
+        w.pub = pub.as<float>(); w.flag = flag.as<uint32_t>(); w.cap = cap;
+        for (uint64_t r0 = 0; r0 < n; r0 += ch) {
+            w.m = std::min<uint64_t>(ch, n - r0);
+            w.rows_h = d_rows_h + r0 * dim;
+            HIP_TRY(hipMemsetAsync(cnt.p, 0, w.m * sizeof(uint32_t), stream));
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (time_kernels) {
+                HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+                kernel_ev.push_back(e0); kernel_ev.push_back(e1);
+                HIP_TRY(hipEventRecord(e0, stream));
+            }
+            HIP_TRY(launch_assign_h_wide(w, stream));
+            if (time_kernels) HIP_TRY(hipEventRecord(e1, stream));
+            HIP_TRY(launch_assign_h_resolve(w, d_centroids, d_cluster + r0, verbose() ? rstats.as<unsigned long long>() : nullptr, stream));
+        }
+        uint32_t h = 0;
+        unsigned long long hs[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
+        if (verbose()) HIP_TRY(hipMemcpyAsync(hs, rstats.p, sizeof hs, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (verbose() && n >= 65536)
+            std::fprintf(stderr, "[pqv] f16-row assignment (256 x 256 tiles, rows as stored): %.1f %% of %llu rows evaluated exactly, %.2f evaluations per such row\n",
+                         100.0 * static_cast<double>(hs[0]) / static_cast<double>(n), (unsigned long long)n,
+                         hs[0] ? static_cast<double>(hs[1]) / static_cast<double>(hs[0]) : 0.0);
+        if (!kernel_ev.empty()) {
+            double ms_sum = 0.0;
+            for (size_t i = 0; i + 1 < kernel_ev.size(); i += 2) {
+                float ms = 0.0f;
+                if (hipEventElapsedTime(&ms, kernel_ev[i], kernel_ev[i + 1]) == hipSuccess) ms_sum += ms;
+            }
+            g_build_stats[BS_WIDE_KERNEL_S] = ms_sum * 1e-3; g_build_stats[BS_WIDE_LAUNCHES] = static_cast<double>(kernel_ev.size() / 2);
+            for (hipEvent_t e : kernel_ev) (void)hipEventDestroy(e);
+            kernel_ev.clear();
+        }
+        *fallback = h != 0;
+        return PQV_OK;
+    }
+    // d_cluster[i] = nearest centroid of row i of d_rows_h [n, dim]; *decided = the tier that wrote it (GEMM: the screen).  The stream
+    // is drained before the scope exit releases the buffers.
+    int run(const uint16_t *d_rows_h, uint64_t n, const float *d_centroids, uint32_t k, uint32_t dim, uint32_t *d_cluster, hipStream_t stream,
+            AssignLadder::Tier *decided) {
+        using namespace pqv;
+        *decided = AssignLadder::EXACT;
+        if (screen_applicable(dim, k)) {
+            bool fallback = true;
+            if (int rc = screen(d_rows_h, n, d_centroids, k, dim, d_cluster, stream, &fallback)) return rc;
+            if (verbose()) std::fprintf(stderr, "[pqv] final assignment: f16-row screen %s at %.1f ms\n", fallback ? "stepped down" : "done", (now_s() - t0) * 1e3);
+            if (!fallback) *decided = AssignLadder::GEMM;
+        }
+        if (*decided == AssignLadder::EXACT) HIP_TRY(launch_assign_h(d_rows_h, n, dim, d_centroids, k, d_cluster, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return PQV_OK;
+    }
+};
+int assign_rows_h(const uint16_t *d_rows_h, uint64_t n, uint32_t dim, const float *d_centroids, uint32_t k, uint32_t *d_cluster,
+                  hipStream_t stream, bool time_kernels, double t0, AssignLadder::Tier *decided) {
+    HalfAssign ladder;
+    ladder.time_kernels = time_kernels; ladder.t0 = t0;
+    return ladder.run(d_rows_h, n, d_centroids, k, dim, d_cluster, stream, decided);
+}
+
 // PQV_KEEP_DEVICE_LISTS=0: a built or derived index' lists are downloaded at once instead of staying on the device
 bool keep_device_lists() {
     static const bool keep = env_on("PQV_KEEP_DEVICE_LISTS");
@@ -2641,7 +2780,8 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
     if (k == 0) k = static_cast<uint64_t>(std::ceil(std::sqrt(static_cast<double>(n)))); // :164
     if (k > n) return fail(PQV_ERR_INVALID, "n_clusters cannot exceed number of vectors"); // :169
     if (k > 0xFFFFFFFFull) return fail(PQV_ERR_INVALID, "Cluster count must fit in u32");
-    if (!corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
+    const bool half = corpus->half();              // (pqv_index_build_f16: the two places that read the column take their f16 forms)
+    if (half ? !corpus->d_rows_h : !corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
     if (int rc = use_device(corpus->device)) return rc;
     hipStream_t stream = corpus->stream;
     g_build_stats[BS_WIDE_KERNEL_S] = 0.0; g_build_stats[BS_WIDE_LAUNCHES] = 0.0;      // (kernel seconds / launches of THIS build's final assignment, whichever path it takes)
@@ -2661,8 +2801,14 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
         HIP_TRY(d_idx.alloc(sample_size * sizeof(uint64_t)));
         HIP_TRY(d_sample.alloc(sample_size * dim * sizeof(float)));
         HIP_TRY(hipMemcpyAsync(d_idx.p, idx.data(), sample_size * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        HIP_TRY(launch_gather_rows(corpus->d_rows, nullptr, d_idx.as<uint64_t>(), sample_size, dim,
+        if (half) HIP_TRY(launch_gather_widen_h(corpus->d_rows_h, d_idx.as<uint64_t>(), sample_size, dim, d_sample.as<float>(), stream));
+        else HIP_TRY(launch_gather_rows(corpus->d_rows, nullptr, d_idx.as<uint64_t>(), sample_size, dim,
                                    d_sample.as<float>(), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        d_train = d_sample.as<float>();
+    } else if (half) {                                                                 // the sample is the column: widened whole
+        HIP_TRY(d_sample.alloc(n * dim * sizeof(float)));
+        HIP_TRY(launch_gather_widen_h(corpus->d_rows_h, nullptr, n, dim, d_sample.as<float>(), stream));
         HIP_TRY(hipStreamSynchronize(stream));
         d_train = d_sample.as<float>();
     }
@@ -2692,8 +2838,10 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
         } catch (const std::system_error &) { }
     }
     AssignLadder::Tier assign_tier = AssignLadder::EXACT;
-    if (int rc = assign_rows(corpus->d_rows, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(), stream,
-                             true, t_fa0, &assign_tier))
+    if (int rc = half ? assign_rows_h(corpus->d_rows_h, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(),
+                                      stream, true, t_fa0, &assign_tier)
+                      : assign_rows(corpus->d_rows, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(), stream,
+                                    true, t_fa0, &assign_tier))
         return rc;
     // the lists: sorted on the device (the rows of a list ascending, index.rs:193-206), then ONE download of the sorted row ids
     // in place of the assignment's download + the host threads' counting sort
@@ -2759,13 +2907,18 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
 
 }  // namespace
 
+// (half: the _f16 entry point -- an f16 corpus is required there and refused by the unsuffixed call)
 static int pqv_index_build_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
-                               uint64_t seed, uint32_t workers, pqv_index **out) {
+                               uint64_t seed, uint32_t workers, pqv_index **out, bool half = false) {
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
     *out = nullptr;
     if (!corpus) return fail(PQV_ERR_INVALID, "corpus must not be NULL");
-    if (int rc = refuse_f16(corpus, "pqv_index_build")) return rc;
+    if (int rc = half ? rows_dtype_check(corpus, PQV_ROWS_F16) : refuse_f16(corpus, "pqv_index_build")) return rc;
     return build_index_impl(corpus, n_clusters, max_iters, seed, workers, out);
+}
+extern "C" int pqv_index_build_f16(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
+                                   uint64_t seed, uint32_t workers, pqv_index **out) {
+    return guard([&] { return pqv_index_build_impl(corpus, n_clusters, max_iters, seed, workers, out, true); });
 }
 extern "C" int pqv_index_build(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max_iters,
                                uint64_t seed, uint32_t workers, pqv_index **out) {
@@ -2787,7 +2940,7 @@ int check_row_range(const pqv_index *index, const pqv_corpus *corpus, uint64_t f
         return fail(PQV_ERR_INVALID, "rows [" + std::to_string(first_row) + ", " + std::to_string(first_row) + " + " + std::to_string(n_rows) +
                                          ") are out of range for a corpus of " + std::to_string(corpus->n) + " rows");
     if (first_row + n_rows > (1ull << 32)) return fail(PQV_ERR_INVALID, "row ids must fit in u32");
-    if (!corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
+    if (corpus->half() ? !corpus->d_rows_h : !corpus->d_rows) return fail(PQV_ERR_INVALID, "corpus row-order copy was released");
     return PQV_OK;
 }
 
@@ -2799,14 +2952,19 @@ int assign_range(const pqv_index *index, const pqv_corpus *corpus, uint64_t firs
     HIP_TRY(d_cluster.alloc(n_rows * sizeof(uint32_t)));
     HIP_TRY(hipMemcpyAsync(d_centroids.p, index->centroids.data(), index->centroids.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     AssignLadder::Tier tier;
+    if (corpus->half())
+        return assign_rows_h(corpus->d_rows_h + first_row * corpus->dim, n_rows, corpus->dim, d_centroids.as<float>(), index->n_clusters,
+                             d_cluster.as<uint32_t>(), stream, false, now_s(), &tier);
     return assign_rows(corpus->d_rows + first_row * corpus->dim, n_rows, corpus->dim, d_centroids.as<float>(), index->n_clusters,
                        d_cluster.as<uint32_t>(), stream, false, now_s(), &tier);
 }
 
-int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, uint32_t *cluster_out) {
+// (half, here and in index_append_impl: the _f16 entry point -- an f16 corpus is required there and refused by the unsuffixed call)
+int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, uint32_t *cluster_out,
+                      bool half = false) {
     if (!index || !corpus) return fail(PQV_ERR_INVALID, "index/corpus must not be NULL");
     if (!cluster_out) return fail(PQV_ERR_INVALID, "cluster_out must not be NULL");
-    if (int rc = refuse_f16(corpus, "pqv_index_assign")) return rc;
+    if (int rc = half ? rows_dtype_check(corpus, PQV_ROWS_F16) : refuse_f16(corpus, "pqv_index_assign")) return rc;
     if (int rc = check_row_range(index, corpus, first_row, n_rows)) return rc;
     if (n_rows == 0) return PQV_OK;
     if (int rc = use_device(corpus->device)) return rc;
@@ -2819,12 +2977,13 @@ int index_assign_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t
 
 struct EventSet { hipEvent_t e[4] = {}; ~EventSet() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
 
-int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out) {
+int index_append_impl(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows, pqv_index **out,
+                      bool half = false) {
     using namespace pqv;
     if (!out) return fail(PQV_ERR_INVALID, "out must not be NULL");
     *out = nullptr;
     if (!index || !corpus) return fail(PQV_ERR_INVALID, "index/corpus must not be NULL");
-    if (int rc = refuse_f16(corpus, "pqv_index_append")) return rc;
+    if (int rc = half ? rows_dtype_check(corpus, PQV_ROWS_F16) : refuse_f16(corpus, "pqv_index_append")) return rc;
     if (int rc = check_row_range(index, corpus, first_row, n_rows)) return rc;
     uint64_t bound = 0;
     if (!index->row_bound(&bound)) return PQV_ERR_HIP;
@@ -3294,6 +3453,14 @@ extern "C" int pqv_index_assign(const pqv_index *index, const pqv_corpus *corpus
 extern "C" int pqv_index_append(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows,
                                 pqv_index **out) {
     return guard([&] { return index_append_impl(index, corpus, first_row, n_rows, out); });
+}
+extern "C" int pqv_index_assign_f16(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows,
+                                    uint32_t *cluster_out) {
+    return guard([&] { return index_assign_impl(index, corpus, first_row, n_rows, cluster_out, true); });
+}
+extern "C" int pqv_index_append_f16(const pqv_index *index, const pqv_corpus *corpus, uint64_t first_row, uint64_t n_rows,
+                                    pqv_index **out) {
+    return guard([&] { return index_append_impl(index, corpus, first_row, n_rows, out, true); });
 }
 
 static int pqv_kpp_pick_impl(int device, const float *minima, uint32_t n, uint32_t workers, float draw, uint64_t *pick, float *total,

@@ -84,6 +84,43 @@ hipError_t launch_stream_h(const StreamArgs &a, StreamMode mode, hipStream_t s);
 // out[i, :] = rows[idx[i], :] widened to f32, i < m
 hipError_t launch_widen_rows_h(const uint16_t *rows, const uint32_t *idx, uint64_t m, uint32_t dim, float *out, hipStream_t s);
 
+// ---- the index build over 2-byte rows (kernels_half_build.hip; pqv_index_build_f16 / _assign_f16 / _append_f16) -----------------
+// out[i, :] = f32(rows_h[idx ? idx[i] : i, :]), i < m: the training sample widened as it is gathered (idx == nullptr: the column)
+hipError_t launch_gather_widen_h(const uint16_t *rows_h, const uint64_t *idx, uint64_t m, uint32_t dim, float *out, hipStream_t s);
+// cluster[r] = the reference's nearest_centroid of row r widened to f32 (assign_h_kernel: the exact tier, any dim; rows_h needs no
+// more alignment than a row start has: 16 bytes where dim % 8 == 0, 4 where dim is even, else 2)
+hipError_t launch_assign_h(const uint16_t *rows_h, uint64_t n, uint32_t dim, const float *centroids, uint32_t k, uint32_t *cluster, hipStream_t s);
+// The screen of the same assignment on the f16 matrix pipe with the rows AS STORED for the row-side operand (assign_h_wide_kernel):
+//   |x - c|^2 = |x - mu|^2 + s_c,   s_c = bias[c] - 2 x.(c - mu),   bias[c] = |c - mu|^2 + 2 mu.(c - mu)
+// the centroid images, their order and groups are GemmAssign::set_centroids' (AssignWideArgs: c16, perm); the kernel forms |x|^2
+// from the operands it stages, flags non-finite rows and leaves candidates in AssignWideArgs' shape for launch_assign_h_resolve.
+struct AssignHalfArgs {
+    const uint16_t *rows_h;  // [m, dim] the rows, 2 dim bytes apart (dim % 8 == 0); nothing is read behind row m - 1
+    const uint16_t *c16;     // [kc_pad, dim_p] images of (centroid - mu) * cscale in ascending-norm order; rows >= kc are zero
+    const float    *bias;    // [kc_pad] in the same order (launch_half_bias); +inf in the slots >= kc
+    const uint32_t *perm;    // [kc] the centroid in sorted slot s
+    const float    *grp_a;   // [kc_pad / 32] per group of 32 sorted centroids: |t_c - s_c| <= xs grp_a + grp_b, xs >= |x| ...
+    const float    *grp_b;   // [kc_pad / 32] ...
+    uint64_t        m;
+    uint32_t        kc, kc_pad, dim, dim_p;      // dim_p = dim rounded up to 64: the images' row length
+    float           kA;      // 2 / cscale: t_c = bias[c] - kA acc
+    float           cm;      // the reference chain's summation margin
+    float           mun;     // >= |mu|
+    float           xn_up, xn_add;      // the kernel's own |x|^2 is taken as sum * xn_up + xn_add (summation margin; flushed subnormals)
+    uint32_t       *cand;     // [m][cap] candidate slots
+    float          *cand_t;   // [m][cap] their lower-bound scores t - E
+    uint32_t       *cand_cnt; // [m] zeroed by the caller; may exceed cap (the row is then compared with every centroid)
+    float          *best_t;   // [m] smallest upper-bound score t + E of the row over all centroids
+    float          *pub;      // [m] >= |x - mu|^2 (from xs and mun): what turns a score into a distance for the margin
+    uint32_t       *flag;     // [1] |= 1 where a row holds Inf / NaN (zeroed by the caller; checked once per call)
+    uint32_t        cap;
+};
+hipError_t launch_half_bias(const float *centroids, const float *mu, const uint32_t *perm, uint32_t kc, uint32_t kc_pad, uint32_t dim, float *bias,
+                            hipStream_t s);
+hipError_t launch_assign_h_wide(const AssignHalfArgs &a, hipStream_t s);
+hipError_t launch_assign_h_resolve(const AssignHalfArgs &a, const float *centroids, uint32_t *cluster,
+                                   unsigned long long *stats /* optional [2]: += rows evaluated exactly, += exact evaluations */, hipStream_t s);
+
 // ---- row-masked searches (kernels_mask.hip) ------------------------------------------------------------------------------
 // A row mask on the device is a bitset over LIST POSITIONS: bit p = the caller's allow byte of the row position p reports.
 // launch_mask_layout writes it from allow bytes in row order (ids: list position -> reported row, a searcher's d_ids) -- all

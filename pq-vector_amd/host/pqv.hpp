@@ -84,6 +84,14 @@ public:
         check(pqv_index_build(corpus_.get(), n_clusters_.value_or(0), max_iters_, seed_, workers_, &h));
         return Index(h);
     }
+    // the same build over an f16 corpus (pqv_index_build_f16): the index of the widened column, byte for byte
+    Index build_f16() const {
+        if (max_iters_ == 0) throw Error(PQV_ERR_INVALID, "max_iters must be > 0");
+        if (n_clusters_ && *n_clusters_ == 0) throw Error(PQV_ERR_INVALID, "n_clusters must be > 0");
+        pqv_index *h = nullptr;
+        check(pqv_index_build_f16(corpus_.get(), n_clusters_.value_or(0), max_iters_, seed_, workers_, &h));
+        return Index(h);
+    }
 private:
     const Corpus &corpus_;
     std::optional<uint32_t> n_clusters_;
