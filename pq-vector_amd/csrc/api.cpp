@@ -1793,49 +1793,91 @@ struct ScreenedAssign {
     }
 };
 
+// The HIP-event bracket of the contraction kernels (BS_WIDE_KERNEL_S, BS_WIDE_LAUNCHES; the build's final assignment turns it on:
+// the roofline of bench.py's index_build record divides by KERNEL time, not by the phase's wall time).  The events live here, so
+// every way out of a tier -- an early error return included -- destroys them.
+struct KernelTimer {
+    bool on = false;
+    std::vector<hipEvent_t> ev;
+    template <class Launch> int around(hipStream_t stream, Launch &&launch) {
+        if (!on) { HIP_TRY(launch()); return PQV_OK; }
+        for (int i = 0; i < 2; ++i) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreate(&e)); ev.push_back(e); }
+        HIP_TRY(hipEventRecord(ev[ev.size() - 2], stream));
+        HIP_TRY(launch());
+        HIP_TRY(hipEventRecord(ev.back(), stream));
+        return PQV_OK;
+    }
+    // behind a synchronisation of the stream: the pairs' elapsed times into the build's stats
+    void report() {
+        if (ev.empty()) return;
+        double ms_sum = 0.0;
+        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) ms_sum += ms;
+        }
+        g_build_stats[BS_WIDE_KERNEL_S] = ms_sum * 1e-3; g_build_stats[BS_WIDE_LAUNCHES] = static_cast<double>(ev.size() / 2);
+        release();
+    }
+    void release() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); ev.clear(); }
+    ~KernelTimer() { release(); }
+};
+
+// The resolve kernels' two counters -- rows evaluated exactly, exact evaluations -- and their PQV_VERBOSE line.  (They are
+// same-address atomics from every wave: the kernels get them in diagnostic runs only.)
+struct ResolveStats {
+    DevBuf buf;
+    int reset(hipStream_t stream) {
+        HIP_TRY(buf.ensure(2 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(buf.p, 0, 2 * sizeof(unsigned long long), stream));
+        return PQV_OK;
+    }
+    unsigned long long *counters() const { return verbose() ? buf.as<unsigned long long>() : nullptr; }
+    // PQV_VERBOSE: downloads them (a synchronisation of the stream) and prints the line of the tier `what` over its n rows
+    int report(const char *what, uint64_t n, hipStream_t stream) {
+        if (!verbose()) return PQV_OK;
+        unsigned long long hs[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(hs, buf.p, sizeof hs, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (n >= 65536) std::fprintf(stderr, "[pqv] %s: %.1f %% of %llu rows evaluated exactly, %.2f evaluations per such row\n", what,
+                                     100.0 * static_cast<double>(hs[0]) / static_cast<double>(n), (unsigned long long)n,
+                                     hs[0] ? static_cast<double>(hs[1]) / static_cast<double>(hs[0]) : 0.0);
+        return PQV_OK;
+    }
+};
+
 // ---------------------------------------------------------------------------------------
-// Round 3: the assignment as a dense f16 contraction + exact re-scoring (kernels_build.hip: assign_f16_kernel,
-// assign_rescore_kernel).  Rows and centroids are imaged as unit vectors about a common centre mu (the column mean of
-// the centroids: the distance is translation invariant, and |x - mu| |c - mu| is what scales the bound's slack); the
-// screen leaves a handful of candidate centroids per row, the exact pass evaluates those in the reference's order and
-// takes the argmin by (distance bits, index) -- index.rs:408-415's strict '<' in ascending order.  Needs dim % 4 == 0
-// and finite norms (NaN ordering is the reference's `<`, not the key order): otherwise the callers keep their old path.
+// The assignment as a dense f16 contraction + exact evaluation of the rows it leaves open (kernels_build.hip: assign_wide_kernel,
+// assign_resolve_kernel).  Rows and centroids are imaged about a common centre mu (the column mean of the centroids: the distance
+// is translation invariant, and |x - mu| |c - mu| is what scales the bound's slack); the screen leaves a handful of candidate
+// centroids per row, the exact pass evaluates those in the reference's order and takes the argmin by (distance bits, index) --
+// index.rs:408-415's strict '<' in ascending order.  Needs dim % 4 == 0 and finite norms (NaN ordering is the reference's `<`,
+// not the key order): otherwise the callers keep their old path.  CentroidImages: the centroid side, shared by the f32-row tier
+// (GemmAssign) and the f16-row tier (HalfAssign).
 // ---------------------------------------------------------------------------------------
-struct GemmAssign {
-    uint32_t dim = 0, dim_p = 0, kc = 0, kc_pad = 0, cap = 32;
-    uint64_t chunk = [] { const char *e = std::getenv("PQV_ASSIGN_CHUNK"); const long v = e ? std::atol(e) : 0; return v >= 4096 ? static_cast<uint64_t>(v) : (1ull << 18); }();
+struct CentroidImages {
+    static constexpr uint32_t cap = 32;          // a row's candidate list (a row that overflows it is compared with every centroid)
+    uint32_t dim = 0, dim_p = 0, kc = 0, kc_pad = 0;
     const float *d_centroids = nullptr;
-    DevBuf mu, c16, cn2, x16, xn2, cand, cnt, flag, cand_t, best_t, rstats, d_perm, d_grp;
-    // round 4: 256 x 256 tiles with the rows on the lane-owned side and centroid images at one global scale (assign_wide_kernel +
-    // assign_resolve_kernel); PQV_ASSIGN_TILE=128 keeps round 3's 128 x 256 kernel with its own exact pass (A/B, tests)
-    bool wide = true;
+    DevBuf mu, c16, cn2, d_perm, d_grp;
+    std::vector<uint32_t> h_perm; std::vector<float> h_grp, h_cn2;
     // The Lloyd iterations assign the SAME rows again and again: with the centring vector kept from the first iteration (any fixed
     // vector serves the bounds; the first centroid mean is as good as the current one) the rows' images and norms are made once.
-    std::vector<uint32_t> h_perm; std::vector<float> h_grp;
-    bool keep_mu = false, mu_set = false;
-    const float *img_rows = nullptr; uint64_t img_n = 0; uint32_t img_dim_p = 0;       // what x16 / xn2 currently hold (single-chunk runs)
-    float cmaxs = 0.0f, cn_max = 0.0f, kA = 0.0f;
-    std::vector<float> h_cn2;
-    unsigned long long exact_rows = 0, exact_evals = 0, rows_total = 0;
+    bool keep_mu = false;
+    uint32_t mu_gen = 0;          // counts the centring vectors made (0: none yet): what a row image was centred on
+    float cmaxs = 0.0f, cscale = 0.0f;          // >= max |c - mu|; the images' scale 2^8 / cmaxs
 
-    static bool applicable(uint32_t dim, uint32_t kc) {
-        const char *e = std::getenv("PQV_ASSIGN_GEMM");          // 0 = off, n > 1 = smallest centroid count that takes this path
-        const long v = e ? std::strtol(e, nullptr, 10) : 128L;
-        return v != 0 && (dim % 4) == 0 && kc >= static_cast<uint32_t>(v > 1 ? v : 128) && static_cast<uint64_t>((dim + 31) / 32 * 32) * 2 * 320 < 0x7FFFFFFFull;
-    }
-    int set_centroids(const float *d_c, uint32_t k, uint32_t d, hipStream_t stream, bool *nonfinite) {
+    // rows per pass of the tiers' chunk loops (PQV_ASSIGN_CHUNK)
+    static uint64_t chunk_rows() { const char *e = std::getenv("PQV_ASSIGN_CHUNK"); const long v = e ? std::atol(e) : 0; return v >= 4096 ? static_cast<uint64_t>(v) : (1ull << 18); }
+    // *undecided = true where the tier cannot decide under this table: a centroid norm that is not finite, or all centroids at mu
+    // (a degenerate scale) -- the ladder steps down
+    int set(const float *d_c, uint32_t k, uint32_t d, hipStream_t stream, bool *undecided) {
         using namespace pqv;
-        {
-            const char *e = std::getenv("PQV_ASSIGN_TILE");
-            wide = !(e && std::atoi(e) == 128) && static_cast<uint64_t>((d + 63) / 64 * 64) * 2 * 512 < 0x7FFFFFFFull;
-        }
-        dim = d; dim_p = wide ? (d + 63) / 64 * 64 : (d + 31) / 32 * 32; kc = k; kc_pad = (k + 255) / 256 * 256; d_centroids = d_c;
+        dim = d; dim_p = (d + 63) / 64 * 64; kc = k; kc_pad = (k + 255) / 256 * 256; d_centroids = d_c;
         HIP_TRY(mu.ensure(static_cast<size_t>(dim) * sizeof(float)));
         HIP_TRY(c16.ensure(static_cast<size_t>(kc_pad) * dim_p * sizeof(uint16_t)));
         HIP_TRY(cn2.ensure(static_cast<size_t>(kc_pad) * sizeof(float)));
-        if (!(keep_mu && mu_set)) { HIP_TRY(launch_col_mean(d_c, kc, dim, mu.as<float>(), stream)); mu_set = true; img_rows = nullptr; }
+        if (!(keep_mu && mu_gen)) { HIP_TRY(launch_col_mean(d_c, kc, dim, mu.as<float>(), stream)); ++mu_gen; }
         HIP_TRY(launch_center_normalize_f16(d_c, mu.as<float>(), kc, kc_pad, dim, dim_p, cn2.as<float>(), c16.p, stream));
-        if (!wide) return any_nonfinite(cn2.as<float>(), kc, flag, stream, nonfinite);
         // one global scale for the centroid images: 2^8 / max |c - mu| (the norms come back anyway: this is the call's one host check)
         h_cn2.resize(kc);
         HIP_TRY(hipMemcpyAsync(h_cn2.data(), cn2.p, static_cast<size_t>(kc) * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -1843,13 +1885,10 @@ struct GemmAssign {
         float mx = 0.0f;
         bool bad = false;
         for (float v : h_cn2) { if (!(v <= 3.0e38f)) bad = true; else mx = std::max(mx, v); }
-        *nonfinite = bad;
-        if (bad) return PQV_OK;
-        cn_max = mx * 1.000001f;
         cmaxs = std::sqrt(mx) * 1.000001f;
-        const float cscale = cmaxs > 0.0f ? 256.0f / cmaxs : 0.0f;
-        if (!(cscale > 0.0f && cscale < 3.0e38f)) { wide = false; return PQV_OK; }      // all centroids at mu / degenerate scale: round 3's kernel (images already written)
-        kA = 2.0f / (256.0f * cscale);
+        cscale = cmaxs > 0.0f ? 256.0f / cmaxs : 0.0f;
+        *undecided = bad || !(cscale > 0.0f && cscale < 3.0e38f);
+        if (*undecided) return PQV_OK;
         // images in ascending-norm order: a 32-centroid group's own largest norm scales its error bound (a table trained on a
         // sample has a few far-out centroids -- clusters of one or two points -- and the table-wide maximum would loosen every bound)
         std::vector<uint32_t> &perm = h_perm;          // (members: the uploads below need no synchronisation to outlive)
@@ -1871,66 +1910,64 @@ struct GemmAssign {
         HIP_TRY(launch_center_normalize_f16(d_c, mu.as<float>(), kc, kc_pad, dim, dim_p, cn2.as<float>(), c16.p, stream, cscale, d_perm.as<uint32_t>()));
         return PQV_OK;          // (perm / grp are members: a later call rewrites them only after its own synchronisation on the norms)
     }
+};
+
+// The f32-row side of the contraction: 256 x 256 tiles with the rows on the lane-owned side (assign_wide_kernel +
+// assign_resolve_kernel) over f16 images of the rows, made chunk by chunk.
+struct GemmAssign {
+    CentroidImages cen;
+    DevBuf x16, xn2, cand, cnt, flag, cand_t, best_t;
+    ResolveStats rstats;
+    KernelTimer timer;
+    const float *img_rows = nullptr; uint64_t img_n = 0; uint32_t img_dim_p = 0, img_mu_gen = 0;       // what x16 / xn2 currently hold (single-chunk runs)
+
+    static bool applicable(uint32_t dim, uint32_t kc) {
+        const char *e = std::getenv("PQV_ASSIGN_GEMM");          // 0 = off, n > 1 = smallest centroid count that takes this path
+        const long v = e ? std::strtol(e, nullptr, 10) : 128L;
+        // (the last term: the kernels address a 512-row stage of images with 32-bit byte offsets)
+        return v != 0 && (dim % 4) == 0 && kc >= static_cast<uint32_t>(v > 1 ? v : 128) && static_cast<uint64_t>((dim + 63) / 64 * 64) * 2 * 512 < 0x7FFFFFFFull;
+    }
+    int set_centroids(const float *d_c, uint32_t k, uint32_t d, hipStream_t stream, bool *undecided) { return cen.set(d_c, k, d, stream, undecided); }
     // cluster[0 .. n) for rows d_rows[0 .. n); *fallback = true if a row norm is not finite (the caller re-runs its old path)
     // (Measured and dropped: the assignment copied to the host chunk by chunk on a second stream behind the next chunk's kernels -- a
     //  device-to-pageable copy there stalls the compute stream's queue, 53 ms for the loop against 34 ms of kernels on C3.)
     int run(const float *d_rows, uint64_t n, uint32_t *d_cluster, hipStream_t stream, bool *fallback) {
         using namespace pqv;
         *fallback = false;
+        const uint32_t dim = cen.dim, dim_p = cen.dim_p, cap = cen.cap;
         const double t_run0 = now_s();
-        const uint64_t ch = std::min<uint64_t>(chunk, std::max<uint64_t>(1, n));
+        const uint64_t ch = std::min<uint64_t>(cen.chunk_rows(), std::max<uint64_t>(1, n));
         HIP_TRY(x16.ensure(ch * dim_p * sizeof(uint16_t)));
         HIP_TRY(xn2.ensure(ch * sizeof(float)));
         HIP_TRY(cand.ensure(ch * cap * sizeof(uint32_t)));
         HIP_TRY(cnt.ensure(ch * sizeof(uint32_t)));
-        if (wide) {
-            HIP_TRY(cand_t.ensure(ch * cap * sizeof(float)));
-            HIP_TRY(best_t.ensure(ch * sizeof(float)));
-            HIP_TRY(rstats.ensure(2 * sizeof(unsigned long long)));
-            HIP_TRY(hipMemsetAsync(rstats.p, 0, 2 * sizeof(unsigned long long), stream));
-        }
-        const float eps = 1.01f * 9.765625e-04f + 2.0f * static_cast<float>(dim_p) * 5.9604645e-08f + 2.0e-6f;
-        const float cm = static_cast<float>(dim + 16) * 2.384185791015625e-07f;
+        HIP_TRY(cand_t.ensure(ch * cap * sizeof(float)));
+        HIP_TRY(best_t.ensure(ch * sizeof(float)));
+        if (int rc = rstats.reset(stream)) return rc;
         // (one host check of the row norms after all chunks: a non-finite one sends the whole call to the caller's old path)
         HIP_TRY(flag.ensure(sizeof(uint32_t)));
         HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), stream));
+        AssignWideArgs w{};
+        w.x16 = x16.as<uint16_t>(); w.c16 = cen.c16.as<uint16_t>(); w.xn2 = xn2.as<float>(); w.cn2 = cen.cn2.as<float>();
+        w.perm = cen.d_perm.as<uint32_t>(); w.grp_cs = cen.d_grp.as<float>(); w.grp_cn = cen.d_grp.as<float>() + cen.kc_pad / 32;
+        w.kc = cen.kc; w.kc_pad = cen.kc_pad; w.dim_p = dim_p;
+        w.kA = 2.0f / (256.0f * cen.cscale);
+        w.eps = 1.01f * 9.765625e-04f + 2.0f * static_cast<float>(dim_p) * 5.9604645e-08f + 2.0e-6f;
+        // the reference's summation margin, tight: a squared difference carries <= 3 roundings, the 4-group <= 3 more, the
+        // running sum one per group (index.rs:461-480; all terms non-negative) -- (dim / 4 + 6) 2^-24, taken twice over
+        w.cm = static_cast<float>(dim / 4 + 16) * 1.1920928955078125e-07f;
+        w.cand = cand.as<uint32_t>(); w.cand_t = cand_t.as<float>(); w.cand_cnt = cnt.as<uint32_t>(); w.best_t = best_t.as<float>(); w.cap = cap;
         for (uint64_t r0 = 0; r0 < n; r0 += ch) {
             const uint64_t m = std::min<uint64_t>(ch, n - r0);
             const float *rows = d_rows + r0 * dim;
-            const bool have_img = keep_mu && n <= ch && img_rows == d_rows && img_n == n && img_dim_p == dim_p;
-            if (!have_img) HIP_TRY(launch_center_normalize_f16(rows, mu.as<float>(), m, m, dim, dim_p, xn2.as<float>(), x16.p, stream));
+            const bool have_img = cen.keep_mu && n <= ch && img_rows == d_rows && img_n == n && img_dim_p == dim_p && img_mu_gen == cen.mu_gen;
+            if (!have_img) HIP_TRY(launch_center_normalize_f16(rows, cen.mu.as<float>(), m, m, dim, dim_p, xn2.as<float>(), x16.p, stream));
             HIP_TRY(launch_nonfinite_flag(xn2.as<float>(), m, flag.as<uint32_t>(), stream));
-            img_rows = n <= ch ? d_rows : nullptr; img_n = n; img_dim_p = dim_p;
+            img_rows = n <= ch ? d_rows : nullptr; img_n = n; img_dim_p = dim_p; img_mu_gen = cen.mu_gen;
             HIP_TRY(hipMemsetAsync(cnt.p, 0, m * sizeof(uint32_t), stream));
-            if (wide) {
-                AssignWideArgs w{};
-                w.x16 = x16.as<uint16_t>(); w.c16 = c16.as<uint16_t>(); w.xn2 = xn2.as<float>(); w.cn2 = cn2.as<float>();
-                w.perm = d_perm.as<uint32_t>(); w.grp_cs = d_grp.as<float>(); w.grp_cn = d_grp.as<float>() + kc_pad / 32;
-                w.m = m; w.kc = kc; w.kc_pad = kc_pad; w.dim_p = dim_p; w.kA = kA; w.eps = eps;
-                // the reference's summation margin, tight: a squared difference carries <= 3 roundings, the 4-group <= 3 more, the
-                // running sum one per group (index.rs:461-480; all terms non-negative) -- (dim / 4 + 6) 2^-24, taken twice over
-                w.cm = static_cast<float>(dim / 4 + 16) * 1.1920928955078125e-07f;
-                w.cand = cand.as<uint32_t>(); w.cand_t = cand_t.as<float>(); w.cand_cnt = cnt.as<uint32_t>(); w.best_t = best_t.as<float>(); w.cap = cap;
-                // (the final assignment brackets the contraction kernel with HIP events -- time_kernels: the roofline of bench.py's
-                //  index_build record divides by KERNEL time, not by the phase's wall time)
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (time_kernels) {
-                    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-                    kernel_ev.push_back(e0); kernel_ev.push_back(e1);
-                    HIP_TRY(hipEventRecord(e0, stream));
-                }
-                HIP_TRY(launch_assign_wide(w, stream));
-                if (time_kernels) HIP_TRY(hipEventRecord(e1, stream));
-                // (the two counters are same-address atomics from every wave: diagnostic runs only)
-                HIP_TRY(launch_assign_resolve(w, rows, d_centroids, dim, d_cluster + r0, verbose() ? rstats.as<unsigned long long>() : nullptr, stream));
-            } else {
-            AssignF16Args a{};
-            a.x16 = x16.as<uint16_t>(); a.c16 = c16.as<uint16_t>(); a.xn2 = xn2.as<float>(); a.cn2 = cn2.as<float>();
-            a.m = m; a.kc = kc; a.kc_pad = kc_pad; a.dim_p = dim_p; a.eps = eps; a.cm = cm;
-            a.cand = cand.as<uint32_t>(); a.cand_cnt = cnt.as<uint32_t>(); a.cap = cap;
-            HIP_TRY(launch_assign_f16(a, stream));
-            HIP_TRY(launch_assign_rescore(rows, d_centroids, m, dim, kc, cand.as<uint32_t>(), cnt.as<uint32_t>(), cap, d_cluster + r0, stream));
-            }
+            w.m = m;
+            if (int rc = timer.around(stream, [&] { return launch_assign_wide(w, stream); })) return rc;
+            HIP_TRY(launch_assign_resolve(w, rows, cen.d_centroids, dim, d_cluster + r0, rstats.counters(), stream));
             if (verbose() && r0 == 0 && n >= 65536) {      // candidates the screen left per row (first chunk)
                 std::vector<uint32_t> hc(m);
                 HIP_TRY(hipMemcpyAsync(hc.data(), cnt.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -1938,7 +1975,7 @@ struct GemmAssign {
                 uint64_t sum = 0, over = 0; uint32_t mx = 0;
                 for (uint32_t c : hc) { sum += c; mx = std::max(mx, c); over += c > cap; }
                 std::fprintf(stderr, "[pqv] f16 assignment: %.2f candidates per row (max %u, %llu rows over the %u-entry list) of %u centroids\n",
-                             static_cast<double>(sum) / static_cast<double>(m), mx, (unsigned long long)over, cap, kc);
+                             static_cast<double>(sum) / static_cast<double>(m), mx, (unsigned long long)over, cap, cen.kc);
             }
         }
         const double t_run1 = now_s();
@@ -1946,33 +1983,12 @@ struct GemmAssign {
         HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
         if (verbose() && n >= (1u << 20)) std::fprintf(stderr, "[pqv] f16 assignment: %llu rows enqueued in %.1f ms\n", (unsigned long long)n,
                                                        (t_run1 - t_run0) * 1e3);
-        if (wide && verbose()) {
-            unsigned long long hs[2] = {0, 0};
-            HIP_TRY(hipMemcpyAsync(hs, rstats.p, sizeof hs, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            exact_rows += hs[0]; exact_evals += hs[1]; rows_total += n;
-            if (n >= 65536) std::fprintf(stderr, "[pqv] f16 assignment (256 x 256 tiles): %.1f %% of %llu rows evaluated exactly, %.2f evaluations per such row\n",
-                                         100.0 * static_cast<double>(hs[0]) / static_cast<double>(n), (unsigned long long)n,
-                                         hs[0] ? static_cast<double>(hs[1]) / static_cast<double>(hs[0]) : 0.0);
-        }
+        if (int rc = rstats.report("f16 assignment (256 x 256 tiles)", n, stream)) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
-        if (!kernel_ev.empty()) {
-            double ms_sum = 0.0;
-            for (size_t i = 0; i + 1 < kernel_ev.size(); i += 2) {
-                float ms = 0.0f;
-                if (hipEventElapsedTime(&ms, kernel_ev[i], kernel_ev[i + 1]) == hipSuccess) ms_sum += ms;
-            }
-            g_build_stats[BS_WIDE_KERNEL_S] = ms_sum * 1e-3; g_build_stats[BS_WIDE_LAUNCHES] = static_cast<double>(kernel_ev.size() / 2);
-            for (hipEvent_t e : kernel_ev) (void)hipEventDestroy(e);
-            kernel_ev.clear();
-        }
+        timer.report();
         *fallback = h != 0;
         return PQV_OK;
     }
-    std::vector<hipEvent_t> kernel_ev;
-    bool time_kernels = false;
-    // (an early error return of run() leaves its events here)
-    ~GemmAssign() { for (hipEvent_t e : kernel_ev) (void)hipEventDestroy(e); }
 };
 
 // acc[c] = ((0 + m[0][c]) + m[1][c]) + ... + m[rows - 1][c] for c in [0, width), width a multiple of 16: `width` independent f32
@@ -2105,28 +2121,137 @@ struct DeviceLists {
     }
 };
 
+// ---------------------------------------------------------------------------------------
+// The ladder's tier over 2-byte rows (pqv_index_build_f16 / _assign_f16 / _append_f16; kernels_half_build.hip): the
+// result is the reference's nearest_centroid on the rows widened to f32.  Two tiers: the screen on the f16 matrix pipe with the
+// rows AS STORED for the row-side operand -- no image of the rows, no second pass over the column; scratch is the candidate
+// buffers alone --, where dim % 8 == 0, GemmAssign::applicable holds (PQV_ASSIGN_GEMM=0: off) and every norm is finite; else the
+// exact kernel.  With  |x - c|^2 = |x - mu|^2 + s_c,  s_c = b_c - 2 x.(c - mu),  b_c = |c - mu|^2 + 2 mu.(c - mu)  the kernel's
+// score  t_c = fl(b_c) - kA acc  (acc: the f32 contraction of the row with CentroidImages' image of (c - mu) cscale, kA = 2 / cscale)
+// is within  E = xs gA + gB  of s_c per 32-centroid group, xs >= |x|:
+//   gA = 2 gcs eps + kA c1      eps = 1.01 2^-11 (the image's rounding, the f32 subtraction and scaling before it)
+//                                     + (2 dim_p + 16) 2^-24 (f32 accumulation over dim_p exact products; kA; the score's roundings)
+//                               c1  = 1.01 sqrt(dim) (2^-25 + 2^-14): image elements rounded in the subnormal range; subnormal
+//                                     image elements, should the matrix pipe flush them
+//   gB = c2 gcs + c3 gcn + c4   c2  = 2.02 sqrt(dim) 2^-14 (subnormal ROW elements, should the pipe flush them) + 2 c3 |mu|
+//                               c3  = 2^-21: b_c summed in f64 and rounded once, the score's roundings; |b_c| <= gcn + 2 |mu| gcs
+//                               c4  = the product of the two subnormal allowances
+// gcs >= max |c - mu| and gcn >= max |c - mu|^2 of the group (CentroidImages', raised by their own summation margin).  The row
+// operand carries no rounding at all.  |x| stands where the f32 form has |x - mu|: rows far from the origin screen worse.
+// ---------------------------------------------------------------------------------------
+struct HalfAssign {
+    CentroidImages cen;
+    DevBuf bias, grp, cand, cand_t, cnt, best_t, pub, flag;
+    ResolveStats rstats;
+    KernelTimer timer;
+    std::vector<float> h_mu, h_grp;
+    pqv::AssignHalfArgs w{};          // set_centroids fills the table's side, run the rows'
+
+    static bool applicable(uint32_t dim, uint32_t k) { return (dim % 8) == 0 && GemmAssign::applicable(dim, k); }
+    // the centroid images, the bias b_c and the groups' bound vectors; *undecided as CentroidImages::set's, and where |mu| or kA leaves
+    // the range the bounds are derived for
+    int set_centroids(const float *d_centroids, uint32_t k, uint32_t dim, hipStream_t stream, bool *undecided) {
+        using namespace pqv;
+        if (int rc = cen.set(d_centroids, k, dim, stream, undecided)) return rc;
+        if (*undecided) return PQV_OK;
+        *undecided = true;
+        const uint32_t dim_p = cen.dim_p, kc_pad = cen.kc_pad, ngrp = kc_pad / 32;
+        const float kA = 2.0f / cen.cscale;
+        h_mu.resize(dim);
+        HIP_TRY(hipMemcpyAsync(h_mu.data(), cen.mu.p, static_cast<size_t>(dim) * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        double mu2 = 0.0;
+        for (float v : h_mu) mu2 += static_cast<double>(v) * v;
+        const double mun = std::sqrt(mu2) * 1.000001;
+        if (!(mun < 1.0e18) || !(kA > 0.0f && kA < 3.0e38f)) return PQV_OK;
+        const double u = 5.9604644775390625e-08, sd = std::sqrt(static_cast<double>(dim));
+        const double up = 1.0 + (center_normalize_f16_sum_depth(dim) + 4) * u;
+        const double eps = 1.01 * 4.8828125e-04 + (2.0 * dim_p + 16.0) * u;
+        const double A0 = sd * 2.98023223876953125e-08, F = sd * 6.103515625e-05;
+        const double c1 = 1.01 * (A0 + F), c3 = 4.76837158203125e-07, c2 = 2.02 * F + 2.0 * c3 * mun, c4 = 1.01 * kA * F * A0 + 1.0e-30;
+        auto upf = [](double v) { return std::nextafter(static_cast<float>(v * 1.00001), INFINITY); };
+        h_grp.resize(2 * static_cast<size_t>(ngrp));
+        for (uint32_t g = 0; g < ngrp; ++g) {
+            const double gcs = cen.h_grp[g] * up, gcn = cen.h_grp[ngrp + g] * up;
+            h_grp[g] = upf(2.0 * gcs * eps + kA * c1); h_grp[ngrp + g] = upf(c2 * gcs + c3 * gcn + c4);
+        }
+        HIP_TRY(grp.ensure(h_grp.size() * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(grp.p, h_grp.data(), h_grp.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(bias.ensure(static_cast<size_t>(kc_pad) * sizeof(float)));
+        HIP_TRY(launch_half_bias(d_centroids, cen.mu.as<float>(), cen.d_perm.as<uint32_t>(), k, kc_pad, dim, bias.as<float>(), stream));
+        w = AssignHalfArgs{};
+        w.c16 = cen.c16.as<uint16_t>(); w.bias = bias.as<float>(); w.perm = cen.d_perm.as<uint32_t>();
+        w.grp_a = grp.as<float>(); w.grp_b = grp.as<float>() + ngrp;
+        w.kc = k; w.kc_pad = kc_pad; w.dim = dim; w.dim_p = dim_p; w.kA = kA;
+        w.cm = static_cast<float>(dim / 4 + 16) * 1.1920928955078125e-07f;          // GemmAssign::run's margin of the reference chain
+        w.mun = upf(mun);
+        // the kernel's |x|^2: dim_p / 4 two-term dot instructions and one add per lane, each taken as three roundings, twice over;
+        // a subnormal half squares to less than 2^-28
+        w.xn_up = static_cast<float>(1.0 + (dim_p + 16.0) * 2.0 * u); w.xn_add = upf(dim * 3.7252902984619140625e-09);
+        w.cap = cen.cap;
+        *undecided = false;
+        return PQV_OK;
+    }
+    // the screen + resolve over d_rows_h [n, dim]; *fallback = true where a row norm is not finite (nothing the caller may keep)
+    int run(const uint16_t *d_rows_h, uint64_t n, uint32_t *d_cluster, hipStream_t stream, bool *fallback) {
+        using namespace pqv;
+        *fallback = true;
+        const uint64_t ch = std::min<uint64_t>(cen.chunk_rows(), std::max<uint64_t>(1, n));
+        HIP_TRY(cand.ensure(ch * w.cap * sizeof(uint32_t))); HIP_TRY(cand_t.ensure(ch * w.cap * sizeof(float)));
+        HIP_TRY(cnt.ensure(ch * sizeof(uint32_t))); HIP_TRY(best_t.ensure(ch * sizeof(float))); HIP_TRY(pub.ensure(ch * sizeof(float)));
+        HIP_TRY(flag.ensure(sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), stream));
+        if (int rc = rstats.reset(stream)) return rc;
+        w.cand = cand.as<uint32_t>(); w.cand_t = cand_t.as<float>(); w.cand_cnt = cnt.as<uint32_t>(); w.best_t = best_t.as<float>();
+        w.pub = pub.as<float>(); w.flag = flag.as<uint32_t>();
+        for (uint64_t r0 = 0; r0 < n; r0 += ch) {
+            w.m = std::min<uint64_t>(ch, n - r0);
+            w.rows_h = d_rows_h + r0 * w.dim;
+            HIP_TRY(hipMemsetAsync(cnt.p, 0, w.m * sizeof(uint32_t), stream));
+            if (int rc = timer.around(stream, [&] { return launch_assign_h_wide(w, stream); })) return rc;
+            HIP_TRY(launch_assign_h_resolve(w, cen.d_centroids, d_cluster + r0, rstats.counters(), stream));
+        }
+        uint32_t h = 0;
+        HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
+        if (int rc = rstats.report("f16-row assignment (256 x 256 tiles, rows as stored)", n, stream)) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));
+        timer.report();
+        *fallback = h != 0;
+        return PQV_OK;
+    }
+};
+
+// The rows an assignment reads: an f32 column or an f16 one (a corpus has one of the two), from the row the view stands at
+struct RowView {
+    const float *f;
+    const uint16_t *h;
+    RowView advance(uint64_t first_row, uint32_t dim) const { return {f ? f + first_row * dim : nullptr, h ? h + first_row * dim : nullptr}; }
+};
+
 // The assignment ladder (index.rs:395-430 in Lloyd; :189-206 + :244-257 in assign_rows): cluster[r] = the nearest centroid of row r
-// by the f16 contraction (GemmAssign), else by the f32 MFMA screen (ScreenedAssign), else by the exact kernel.  A tier steps down
-// where a centroid norm (its set_centroids) or a row norm (its run) is not finite: NaN ordering is the reference's `<`, which only
-// the exact kernel keeps.  The caller chooses the tiers to try once; Lloyd keeps one ladder over its iterations, so the
-// contraction's centring vector and row images carry over (GemmAssign::keep_mu).
+// by the f16 contraction (GemmAssign; over f16 rows HalfAssign), else -- f32 rows -- by the f32 MFMA screen (ScreenedAssign), else by
+// the exact kernel.  A tier steps down where its set_centroids does not decide (a centroid norm that is not finite, a degenerate
+// table) or a row norm (its run) is not finite: NaN ordering is the reference's `<`, which only the exact kernel keeps.  The
+// caller chooses the tiers to try once; Lloyd keeps one ladder over its iterations, so the contraction's centring vector and row
+// images carry over (CentroidImages::keep_mu).
 struct AssignLadder {
-    enum Tier { EXACT = 0, SCREEN = 1, GEMM = 2 };         // (the values of BS_FINAL_FORM / BS_LLOYD_FORM)
+    enum Tier { EXACT = 0, SCREEN = 1, GEMM = 2 };         // (the values of BS_FINAL_FORM / BS_LLOYD_FORM; the f16-row screen reports GEMM)
     GemmAssign gemm;
+    HalfAssign half;
     ScreenedAssign screen;
     bool try_gemm = false, try_screen = false;
     // one call on a local ladder (assign_rows): the stream is drained behind each tier, before the next one starts and before the
     // scope exit releases the tiers' buffers; t0 is the clock origin of that call's PQV_VERBOSE lines
     bool one_shot = false;
     double t0 = 0.0;
-    // d_cluster[i] = nearest centroid of row i of d_rows [n, dim], i in [0, n); *decided = the tier that wrote it.  With d_prev and
-    // d_changed (Lloyd, :417-427) *d_changed counts the rows whose cluster differs from d_prev's: the exact kernel counts as it
-    // assigns, a tier above it is followed by count_changed_kernel.
-    int run(const float *d_rows, uint64_t n, const float *d_centroids, uint32_t k, uint32_t dim, uint32_t *d_cluster, hipStream_t stream,
+    // d_cluster[i] = nearest centroid of row i of rows [n, dim], i in [0, n); *decided = the tier that wrote it.  With d_prev and
+    // d_changed (Lloyd, :417-427; f32 rows -- Lloyd trains on an f32 sample) *d_changed counts the rows whose cluster differs from
+    // d_prev's: the exact kernel counts as it assigns, a tier above it is followed by count_changed_kernel.
+    int run(RowView rows, uint64_t n, const float *d_centroids, uint32_t k, uint32_t dim, uint32_t *d_cluster, hipStream_t stream,
             Tier *decided, const uint32_t *d_prev = nullptr, unsigned long long *d_changed = nullptr) {
         using namespace pqv;
         *decided = EXACT;
-        auto attempt = [&](auto &tier, Tier t, bool trace) -> int {
+        auto attempt = [&](auto &tier, auto *d_rows, Tier t, bool trace) -> int {
             bool bad_c = false, bad_r = false;
             if (int rc = tier.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
             if (trace) std::fprintf(stderr, "[pqv] final assignment: centroids set at %.1f ms\n", (now_s() - t0) * 1e3);
@@ -2136,9 +2261,18 @@ struct AssignLadder {
             if (!bad_c && !bad_r) *decided = t;
             return PQV_OK;
         };
-        if (try_gemm) { if (int rc = attempt(gemm, GEMM, one_shot && verbose())) return rc; }
-        if (*decided == EXACT && try_screen) { if (int rc = attempt(screen, SCREEN, false)) return rc; }
-        if (*decided == EXACT) HIP_TRY(launch_assign(d_rows, n, dim, d_centroids, k, d_cluster, d_prev, d_changed, nullptr, stream));
+        if (rows.h) {          // f16 rows: their screen, then their exact kernel; the stream is drained before the scope exit releases the buffers
+            if (try_gemm) {
+                if (int rc = attempt(half, rows.h, GEMM, false)) return rc;
+                if (verbose()) std::fprintf(stderr, "[pqv] final assignment: f16-row screen %s at %.1f ms\n", *decided == EXACT ? "stepped down" : "done", (now_s() - t0) * 1e3);
+            }
+            if (*decided == EXACT) HIP_TRY(launch_assign_h(rows.h, n, dim, d_centroids, k, d_cluster, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            return PQV_OK;
+        }
+        if (try_gemm) { if (int rc = attempt(gemm, rows.f, GEMM, one_shot && verbose())) return rc; }
+        if (*decided == EXACT && try_screen) { if (int rc = attempt(screen, rows.f, SCREEN, false)) return rc; }
+        if (*decided == EXACT) HIP_TRY(launch_assign(rows.f, n, dim, d_centroids, k, d_cluster, d_prev, d_changed, nullptr, stream));
         else if (d_changed) HIP_TRY(launch_count_changed(d_cluster, d_prev, n, d_changed, stream));
         return PQV_OK;
     }
@@ -2501,7 +2635,7 @@ int lloyd_iterations(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, 
     AssignLadder ladder;
     ladder.try_gemm = GemmAssign::applicable(dim, k);
     ladder.try_screen = !ladder.try_gemm && ScreenedAssign::applicable(dim, k);
-    ladder.gemm.keep_mu = env_on("PQV_LLOYD_KEEP_IMAGES");
+    ladder.gemm.cen.keep_mu = env_on("PQV_LLOYD_KEEP_IMAGES");
     const bool dev_lists = DeviceLists::applicable(n, k);
     DeviceLists dlists;
     uint32_t h_bad = 0;
@@ -2513,7 +2647,7 @@ int lloyd_iterations(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, 
         HIP_TRY(hipMemsetAsync(d_counts.p, 0, (static_cast<size_t>(k) + 1) * sizeof(unsigned long long), stream));
         unsigned long long *d_changed = d_counts.as<unsigned long long>() + k;
         AssignLadder::Tier tier;
-        if (int rc = ladder.run(d_data, n, d_centroids, k, dim, d_cur, stream, &tier, d_prev, d_changed)) return rc;
+        if (int rc = ladder.run(RowView{d_data, nullptr}, n, d_centroids, k, dim, d_cur, stream, &tier, d_prev, d_changed)) return rc;
         HIP_TRY(hipMemcpyAsync(h_counts.data(), d_counts.p, h_counts.size() * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, stream));
         if (!dev_lists) HIP_TRY(hipMemcpyAsync(h_assign.data(), d_cur, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -2594,162 +2728,24 @@ int kmeans_device(const float *d_data, uint64_t n, uint32_t dim, uint32_t k, uin
     return lloyd_iterations(d_data, n, dim, k, max_iters, stream, d_centroids, t_pp1, assign_out, iters_run);
 }
 
-// The final-assignment stage (index.rs:189-201 + :244-257): d_cluster[i] = nearest_centroid of row i of d_rows [n, dim] under
+// The final-assignment stage (index.rs:189-201 + :244-257): d_cluster[i] = nearest_centroid of row i of rows [n, dim] under
 // d_centroids [k, dim], i in [0, n), by the ladder with both tiers above the exact kernel where they apply: one call over all the
 // rows, so the screen behind a contraction that stepped down is one more pass, paid once (Lloyd chooses differently: see there).
+// f16 rows (the result is the reference's on the rows widened to f32) have their own screen above their exact kernel and no second tier.
 // Depends on the centroids and these rows alone: the build calls it over the whole column, pqv_index_assign / pqv_index_append
-// over a row range (d_rows = the range's first row: the three forms index rows and outputs from the base they are given and ask
+// over a row range (rows = the view at the range's first row: the forms index rows and outputs from the base they are given and ask
 // no more alignment of it than a row start has -- 16 bytes where dim % 4 == 0, the scalar loads of the exact kernel otherwise;
 // the non-finite checks read the norms of these n rows only).
 // time_kernels: the build's HIP-event bracket of the contraction kernel (BS_WIDE_KERNEL_S, BS_WIDE_LAUNCHES).  t0: the caller's
 // clock origin of the PQV_VERBOSE lines.  *decided: the tier that wrote d_cluster.
-int assign_rows(const float *d_rows, uint64_t n, uint32_t dim, const float *d_centroids, uint32_t k, uint32_t *d_cluster,
+int assign_rows(RowView rows, uint64_t n, uint32_t dim, const float *d_centroids, uint32_t k, uint32_t *d_cluster,
                 hipStream_t stream, bool time_kernels, double t0, AssignLadder::Tier *decided) {
     AssignLadder ladder;
-    ladder.try_gemm = GemmAssign::applicable(dim, k);
-    ladder.try_screen = ScreenedAssign::applicable(dim, k);
+    ladder.try_gemm = rows.h ? HalfAssign::applicable(dim, k) : GemmAssign::applicable(dim, k);
+    ladder.try_screen = ScreenedAssign::applicable(dim, k);          // (f32 rows)
     ladder.one_shot = true; ladder.t0 = t0;
-    ladder.gemm.time_kernels = time_kernels;
-    return ladder.run(d_rows, n, d_centroids, k, dim, d_cluster, stream, decided);
-}
-
-// ---------------------------------------------------------------------------------------
-// The same stage over 2-byte rows (pqv_index_build_f16 / _assign_f16 / _append_f16; kernels_half_build.hip): the
-// result is the reference's nearest_centroid on the rows widened to f32.  Two tiers: the screen on the f16 matrix pipe with the
-// rows AS STORED for the row-side operand -- no image of the rows, no second pass over the column; scratch is the candidate
-// buffers alone --, where dim % 8 == 0, GemmAssign::applicable holds (PQV_ASSIGN_GEMM=0: off) and every norm is finite; else the
-// exact kernel.  With  |x - c|^2 = |x - mu|^2 + s_c,  s_c = b_c - 2 x.(c - mu),  b_c = |c - mu|^2 + 2 mu.(c - mu)  the kernel's
-// score  t_c = fl(b_c) - kA acc  (acc: the f32 contraction of the row with GemmAssign's image of (c - mu) cscale, kA = 2 / cscale)
-// is within  E = xs gA + gB  of s_c per 32-centroid group, xs >= |x|:
-//   gA = 2 gcs eps + kA c1      eps = 1.01 2^-11 (the image's rounding, the f32 subtraction and scaling before it)
-//                                     + (2 dim_p + 16) 2^-24 (f32 accumulation over dim_p exact products; kA; the score's roundings)
-//                               c1  = 1.01 sqrt(dim) (2^-25 + 2^-14): image elements rounded in the subnormal range; subnormal
-//                                     image elements, should the matrix pipe flush them
-//   gB = c2 gcs + c3 gcn + c4   c2  = 2.02 sqrt(dim) 2^-14 (subnormal ROW elements, should the pipe flush them) + 2 c3 |mu|
-//                               c3  = 2^-21: b_c summed in f64 and rounded once, the score's roundings; |b_c| <= gcn + 2 |mu| gcs
-//                               c4  = the product of the two subnormal allowances
-// gcs >= max |c - mu| and gcn >= max |c - mu|^2 of the group (GemmAssign's, raised by their own summation margin).  The row
-// operand carries no rounding at all.  |x| stands where the f32 form has |x - mu|: rows far from the origin screen worse.
-// ---------------------------------------------------------------------------------------
-struct HalfAssign {
-    GemmAssign gemm;          // set_centroids alone: the centring vector, the sorted centroid images, perm, the group maxima, the scale
-    DevBuf bias, grp, cand, cand_t, cnt, best_t, pub, flag, rstats;
-    std::vector<float> h_mu, h_grp;
-    std::vector<hipEvent_t> kernel_ev;
-    bool time_kernels = false;
-    double t0 = 0.0;
-    ~HalfAssign() { for (hipEvent_t e : kernel_ev) (void)hipEventDestroy(e); }
-
-    static bool screen_applicable(uint32_t dim, uint32_t k) {
-        return (dim % 8) == 0 && GemmAssign::applicable(dim, k) && static_cast<uint64_t>((dim + 63) / 64 * 64) * 2 * 512 < 0x7FFFFFFFull;
-    }
-    // the screen + resolve over d_rows_h [n, dim]; *fallback = true where it does not decide (a non-finite row, a degenerate table)
-    int screen(const uint16_t *d_rows_h, uint64_t n, const float *d_centroids, uint32_t k, uint32_t dim, uint32_t *d_cluster, hipStream_t stream,
-               bool *fallback) {
-        using namespace pqv;
-        *fallback = true;
-        bool bad_c = false;
-        if (int rc = gemm.set_centroids(d_centroids, k, dim, stream, &bad_c)) return rc;
-        if (bad_c || !gemm.wide) return PQV_OK;
-        const uint32_t dim_p = gemm.dim_p, kc_pad = gemm.kc_pad, ngrp = kc_pad / 32, cap = gemm.cap;
-        const float cscale = 256.0f / gemm.cmaxs, kA = 2.0f / cscale;
-        h_mu.resize(dim);
-        HIP_TRY(hipMemcpyAsync(h_mu.data(), gemm.mu.p, static_cast<size_t>(dim) * sizeof(float), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        double mu2 = 0.0;
-        for (float v : h_mu) mu2 += static_cast<double>(v) * v;
-        const double mun = std::sqrt(mu2) * 1.000001;
-        if (!(mun < 1.0e18) || !(kA > 0.0f && kA < 3.0e38f)) return PQV_OK;
-        const double u = 5.9604644775390625e-08, sd = std::sqrt(static_cast<double>(dim));
-        const double up = 1.0 + (center_normalize_f16_sum_depth(dim) + 4) * u;
-        const double eps = 1.01 * 4.8828125e-04 + (2.0 * dim_p + 16.0) * u;
-        const double A0 = sd * 2.98023223876953125e-08, F = sd * 6.103515625e-05;
-        const double c1 = 1.01 * (A0 + F), c3 = 4.76837158203125e-07, c2 = 2.02 * F + 2.0 * c3 * mun, c4 = 1.01 * kA * F * A0 + 1.0e-30;
-        auto upf = [](double v) { return std::nextafter(static_cast<float>(v * 1.00001), INFINITY); };
-        h_grp.resize(2 * static_cast<size_t>(ngrp));
-        for (uint32_t g = 0; g < ngrp; ++g) {
-            const double gcs = gemm.h_grp[g] * up, gcn = gemm.h_grp[ngrp + g] * up;
-            h_grp[g] = upf(2.0 * gcs * eps + kA * c1); h_grp[ngrp + g] = upf(c2 * gcs + c3 * gcn + c4);
-        }
-        HIP_TRY(grp.ensure(h_grp.size() * sizeof(float)));
-        HIP_TRY(hipMemcpyAsync(grp.p, h_grp.data(), h_grp.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(bias.ensure(static_cast<size_t>(kc_pad) * sizeof(float)));
-        HIP_TRY(launch_half_bias(d_centroids, gemm.mu.as<float>(), gemm.d_perm.as<uint32_t>(), k, kc_pad, dim, bias.as<float>(), stream));
-        const uint64_t ch = std::min<uint64_t>(gemm.chunk, std::max<uint64_t>(1, n));
-        HIP_TRY(cand.ensure(ch * cap * sizeof(uint32_t))); HIP_TRY(cand_t.ensure(ch * cap * sizeof(float)));
-        HIP_TRY(cnt.ensure(ch * sizeof(uint32_t))); HIP_TRY(best_t.ensure(ch * sizeof(float))); HIP_TRY(pub.ensure(ch * sizeof(float)));
-        HIP_TRY(flag.ensure(sizeof(uint32_t))); HIP_TRY(rstats.ensure(2 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(uint32_t), stream));
-        HIP_TRY(hipMemsetAsync(rstats.p, 0, 2 * sizeof(unsigned long long), stream));
-        AssignHalfArgs w{};
-        w.c16 = gemm.c16.as<uint16_t>(); w.bias = bias.as<float>(); w.perm = gemm.d_perm.as<uint32_t>();
-        w.grp_a = grp.as<float>(); w.grp_b = grp.as<float>() + ngrp;
-        w.kc = k; w.kc_pad = kc_pad; w.dim = dim; w.dim_p = dim_p; w.kA = kA;
-        w.cm = static_cast<float>(dim / 4 + 16) * 1.1920928955078125e-07f;          // GemmAssign::run's margin of the reference chain
-        w.mun = upf(mun);
-        // the kernel's |x|^2: dim_p / 4 two-term dot instructions and one add per lane, each taken as three roundings, twice over;
-        // a subnormal half squares to less than 2^-28
-        w.xn_up = static_cast<float>(1.0 + (dim_p + 16.0) * 2.0 * u); w.xn_add = upf(dim * 3.7252902984619140625e-09);
-        w.cand = cand.as<uint32_t>(); w.cand_t = cand_t.as<float>(); w.cand_cnt = cnt.as<uint32_t>(); w.best_t = best_t.as<float>();
-        w.pub = pub.as<float>(); w.flag = flag.as<uint32_t>(); w.cap = cap;
-        for (uint64_t r0 = 0; r0 < n; r0 += ch) {
-            w.m = std::min<uint64_t>(ch, n - r0);
-            w.rows_h = d_rows_h + r0 * dim;
-            HIP_TRY(hipMemsetAsync(cnt.p, 0, w.m * sizeof(uint32_t), stream));
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (time_kernels) {
-                HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-                kernel_ev.push_back(e0); kernel_ev.push_back(e1);
-                HIP_TRY(hipEventRecord(e0, stream));
-            }
-            HIP_TRY(launch_assign_h_wide(w, stream));
-            if (time_kernels) HIP_TRY(hipEventRecord(e1, stream));
-            HIP_TRY(launch_assign_h_resolve(w, d_centroids, d_cluster + r0, verbose() ? rstats.as<unsigned long long>() : nullptr, stream));
-        }
-        uint32_t h = 0;
-        unsigned long long hs[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, stream));
-        if (verbose()) HIP_TRY(hipMemcpyAsync(hs, rstats.p, sizeof hs, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (verbose() && n >= 65536)
-            std::fprintf(stderr, "[pqv] f16-row assignment (256 x 256 tiles, rows as stored): %.1f %% of %llu rows evaluated exactly, %.2f evaluations per such row\n",
-                         100.0 * static_cast<double>(hs[0]) / static_cast<double>(n), (unsigned long long)n,
-                         hs[0] ? static_cast<double>(hs[1]) / static_cast<double>(hs[0]) : 0.0);
-        if (!kernel_ev.empty()) {
-            double ms_sum = 0.0;
-            for (size_t i = 0; i + 1 < kernel_ev.size(); i += 2) {
-                float ms = 0.0f;
-                if (hipEventElapsedTime(&ms, kernel_ev[i], kernel_ev[i + 1]) == hipSuccess) ms_sum += ms;
-            }
-            g_build_stats[BS_WIDE_KERNEL_S] = ms_sum * 1e-3; g_build_stats[BS_WIDE_LAUNCHES] = static_cast<double>(kernel_ev.size() / 2);
-            for (hipEvent_t e : kernel_ev) (void)hipEventDestroy(e);
-            kernel_ev.clear();
-        }
-        *fallback = h != 0;
-        return PQV_OK;
-    }
-    // d_cluster[i] = nearest centroid of row i of d_rows_h [n, dim]; *decided = the tier that wrote it (GEMM: the screen).  The stream
-    // is drained before the scope exit releases the buffers.
-    int run(const uint16_t *d_rows_h, uint64_t n, const float *d_centroids, uint32_t k, uint32_t dim, uint32_t *d_cluster, hipStream_t stream,
-            AssignLadder::Tier *decided) {
-        using namespace pqv;
-        *decided = AssignLadder::EXACT;
-        if (screen_applicable(dim, k)) {
-            bool fallback = true;
-            if (int rc = screen(d_rows_h, n, d_centroids, k, dim, d_cluster, stream, &fallback)) return rc;
-            if (verbose()) std::fprintf(stderr, "[pqv] final assignment: f16-row screen %s at %.1f ms\n", fallback ? "stepped down" : "done", (now_s() - t0) * 1e3);
-            if (!fallback) *decided = AssignLadder::GEMM;
-        }
-        if (*decided == AssignLadder::EXACT) HIP_TRY(launch_assign_h(d_rows_h, n, dim, d_centroids, k, d_cluster, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return PQV_OK;
-    }
-};
-int assign_rows_h(const uint16_t *d_rows_h, uint64_t n, uint32_t dim, const float *d_centroids, uint32_t k, uint32_t *d_cluster,
-                  hipStream_t stream, bool time_kernels, double t0, AssignLadder::Tier *decided) {
-    HalfAssign ladder;
-    ladder.time_kernels = time_kernels; ladder.t0 = t0;
-    return ladder.run(d_rows_h, n, d_centroids, k, dim, d_cluster, stream, decided);
+    ladder.gemm.timer.on = ladder.half.timer.on = time_kernels;
+    return ladder.run(rows, n, d_centroids, k, dim, d_cluster, stream, decided);
 }
 
 // PQV_KEEP_DEVICE_LISTS=0: a built or derived index' lists are downloaded at once instead of staying on the device
@@ -2838,10 +2834,8 @@ int build_index_impl(const pqv_corpus *corpus, uint32_t n_clusters, uint32_t max
         } catch (const std::system_error &) { }
     }
     AssignLadder::Tier assign_tier = AssignLadder::EXACT;
-    if (int rc = half ? assign_rows_h(corpus->d_rows_h, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(),
-                                      stream, true, t_fa0, &assign_tier)
-                      : assign_rows(corpus->d_rows, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(), stream,
-                                    true, t_fa0, &assign_tier))
+    if (int rc = assign_rows(RowView{corpus->d_rows, corpus->d_rows_h}, n, dim, d_centroids.as<float>(), static_cast<uint32_t>(k), d_cluster.as<uint32_t>(), stream,
+                             true, t_fa0, &assign_tier))
         return rc;
     // the lists: sorted on the device (the rows of a list ascending, index.rs:193-206), then ONE download of the sorted row ids
     // in place of the assignment's download + the host threads' counting sort
@@ -2952,10 +2946,7 @@ int assign_range(const pqv_index *index, const pqv_corpus *corpus, uint64_t firs
     HIP_TRY(d_cluster.alloc(n_rows * sizeof(uint32_t)));
     HIP_TRY(hipMemcpyAsync(d_centroids.p, index->centroids.data(), index->centroids.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     AssignLadder::Tier tier;
-    if (corpus->half())
-        return assign_rows_h(corpus->d_rows_h + first_row * corpus->dim, n_rows, corpus->dim, d_centroids.as<float>(), index->n_clusters,
-                             d_cluster.as<uint32_t>(), stream, false, now_s(), &tier);
-    return assign_rows(corpus->d_rows + first_row * corpus->dim, n_rows, corpus->dim, d_centroids.as<float>(), index->n_clusters,
+    return assign_rows(RowView{corpus->d_rows, corpus->d_rows_h}.advance(first_row, corpus->dim), n_rows, corpus->dim, d_centroids.as<float>(), index->n_clusters,
                        d_cluster.as<uint32_t>(), stream, false, now_s(), &tier);
 }
 

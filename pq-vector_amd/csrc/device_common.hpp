@@ -583,7 +583,7 @@ __device__ __forceinline__ float unsortable_bits(uint32_t u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
 }
 
-constexpr int BH_BM = 128, BH_BN = 256, BH_BK = 32;       // assign_f16_kernel's tile (and the 4-wave form of brute_f16_kernel)
+constexpr int BH_BK = 32;       // the K granule launch_brute_f16 asks of dim_p
 typedef int i32x16_t __attribute__((ext_vector_type(16)));
 typedef float f32x4_raw_t __attribute__((ext_vector_type(4)));
 

@@ -92,7 +92,7 @@ hipError_t launch_gather_widen_h(const uint16_t *rows_h, const uint64_t *idx, ui
 hipError_t launch_assign_h(const uint16_t *rows_h, uint64_t n, uint32_t dim, const float *centroids, uint32_t k, uint32_t *cluster, hipStream_t s);
 // The screen of the same assignment on the f16 matrix pipe with the rows AS STORED for the row-side operand (assign_h_wide_kernel):
 //   |x - c|^2 = |x - mu|^2 + s_c,   s_c = bias[c] - 2 x.(c - mu),   bias[c] = |c - mu|^2 + 2 mu.(c - mu)
-// the centroid images, their order and groups are GemmAssign::set_centroids' (AssignWideArgs: c16, perm); the kernel forms |x|^2
+// the centroid images, their order and groups are CentroidImages::set's (api.cpp; AssignWideArgs: c16, perm); the kernel forms |x|^2
 // from the operands it stages, flags non-finite rows and leaves candidates in AssignWideArgs' shape for launch_assign_h_resolve.
 struct AssignHalfArgs {
     const uint16_t *rows_h;  // [m, dim] the rows, 2 dim bytes apart (dim % 8 == 0); nothing is read behind row m - 1
@@ -950,26 +950,11 @@ struct BruteF16Args {
     uint32_t     cap;
 };
 hipError_t launch_brute_f16(const BruteF16Args &a, hipStream_t s);
-// The k-means assignment on the f16 matrix pipe (kernels_build.hip: assign_f16_kernel): images of (row - mu) / |row - mu| * 2^8
-// for rows and centroids (launch_center_normalize_f16; the centroid table padded to kc_pad rows, a multiple of 256),
-// candidate lists per row, then launch_assign_rescore picks the exact argmin among them.
-struct AssignF16Args {
-    const uint16_t *x16;     // [m, dim_p]
-    const uint16_t *c16;     // [kc_pad, dim_p]
-    const float    *xn2;     // [m]  |row - mu|^2
-    const float    *cn2;     // [kc] |centroid - mu|^2
-    uint64_t        m;
-    uint32_t        kc, kc_pad, dim_p;
-    float           eps, cm;  // image dot-product bound (cosine scale); the reference summation margin
-    uint32_t       *cand;     // [m][cap] candidate centroid ids
-    uint32_t       *cand_cnt; // [m] (zeroed by the caller; may exceed cap: the row is then compared with every centroid)
-    uint32_t        cap;
-};
-hipError_t launch_assign_f16(const AssignF16Args &a, hipStream_t s);
-// Round 4 form of the same screen (kernels_build.hip: assign_wide_kernel): block tile 256 rows x 256 centroids (8 waves, 128-byte K
-// stages), the data rows on the LANE-owned side of the MFMA so that a row's running best needs no cross-lane reduction, centroid
-// images at ONE global scale (cscale = 2^8 / max |c - mu|) so that the whole epilogue of a pair is  t = cn2[c] - kA xs acc  (one
-// FMA + one min; d~ = |x - mu|^2 + t).  Candidates carry their t; launch_assign_resolve filters them against the row's FINAL
+// The k-means assignment on the f16 matrix pipe (kernels_build.hip: assign_wide_kernel): images of the rows and centroids about a
+// common centre mu (launch_center_normalize_f16; the centroid table padded to kc_pad rows, a multiple of 256), block tile 256 rows
+// x 256 centroids (8 waves, 128-byte K stages), the data rows on the LANE-owned side of the MFMA so that a row's running best
+// needs no cross-lane reduction, centroid images at ONE global scale (cscale = 2^8 / max |c - mu|) so that the whole epilogue of a
+// pair is  t = cn2[c] - kA xs acc  (one FMA + one min; d~ = |x - mu|^2 + t).  Candidates carry their t; launch_assign_resolve filters them against the row's FINAL
 // best (the kernel's own test only sees the best so far), returns the survivor where one is left and evaluates exactly --
 // reference order, argmin by (distance bits, index) -- only the rows that keep two or more.
 struct AssignWideArgs {
@@ -994,9 +979,7 @@ struct AssignWideArgs {
 hipError_t launch_assign_wide(const AssignWideArgs &a, hipStream_t s);
 hipError_t launch_assign_resolve(const AssignWideArgs &a, const float *rows, const float *centroids, uint32_t dim, uint32_t *cluster,
                                  unsigned long long *stats /* optional [2]: += rows evaluated exactly, += exact evaluations */, hipStream_t s);
-hipError_t launch_assign_rescore(const float *rows, const float *centroids, uint64_t m, uint32_t dim, uint32_t kc, const uint32_t *cand,
-                                 const uint32_t *cand_cnt, uint32_t cap, uint32_t *cluster, hipStream_t s);
-// fixed_scale > 0: every row is multiplied by that one scale instead of 2^8 / its own norm (the centroid images of the round-4 form)
+// fixed_scale > 0: every row is multiplied by that one scale instead of 2^8 / its own norm (the centroid images)
 // idx != nullptr: output row r is made from rows[idx[r]]
 hipError_t launch_center_normalize_f16(const float *rows, const float *mu, uint64_t n, uint64_t n_pad, uint32_t dim, uint32_t dim_p,
                                        float *out_n2, void *out, hipStream_t s, float fixed_scale = 0.0f, const uint32_t *idx = nullptr);

@@ -1,324 +1,16 @@
-// kernels_build.hip -- index build (src/ivf/index.rs:323-457, :189-206): assign_f16_kernel + assign_rescore(_wave)_kernel (the k-means
-// assignment as an f16 contraction + exact re-scoring), assign_kernel (exact VALU form), lloyd_update_kernel, and the helpers of
-// the f32-screened assignment.
+// kernels_build.hip -- index build (src/ivf/index.rs:323-457, :189-206): assign_wide_kernel + assign_resolve_kernel (the k-means
+// assignment as an f16 contraction + exact evaluation of the rows it leaves undecided), assign_kernel (exact VALU form),
+// lloyd_update_kernel, and the helpers of the f32-screened assignment.
 #include "device_common.hpp"
 
 namespace pqv {
 
 // ------------------------------------------------------------------------------------
-// Round 3: the k-means assignment (index.rs:395-430 Lloyd, :189-206 + :244-257 final) as a dense contraction on the f16
-// matrix pipe + exact re-scoring -- the brute-force design with the roles swapped: every ROW keeps a threshold and a
-// candidate list, the CENTROIDS are the streamed side.
-//
-//   images      x^ = (x - mu) / |x - mu| * 2^8 in f16 for rows and centroids alike (mu: any fixed vector -- the distance is
-//               translation invariant; centring shrinks |x - mu| |c - mu| and with it the bound's slack)
-//   assign_f16_kernel   one block = 128 rows against ALL centroids, 256 at a time (4 waves as 2 x 2, 64 rows x 128
-//               centroids each, v_mfma_f32_32x32x16_f16, K in 32-value stages through double-buffered LDS).  With s~ the image
-//               dot product / 2^16:  d~ = |a|^2 + |b|^2 - 2 |a||b| s~,  |d~ - d| <= err = 2 |a||b| eps + 4e-6 (|a|^2 + |b|^2)
-//               (eps as in brute_f16_kernel), and the reference's computed distance lies within (1 +- cm) of d.  Per row the
-//               smallest UPPER bound seen so far is a running threshold (LDS); every centroid whose LOWER bound does not
-//               exceed it is appended to the row's candidate list.  The true argmin is never dropped: its lower bound is
-//               below its own upper bound, which is below every threshold the row ever had.
-//   assign_rescore_kernel   exact reference-order distances (index.rs:461-480) of a row's candidates, four lanes per row,
-//               argmin by (distance bits, centroid index) = strict '<' in ascending index order; a row whose list
-//               overflowed is compared with every centroid.
-// ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void assign_f16_kernel(const AssignF16Args a) {
-    __shared__ float4 As4[2][BH_BM * 4];
-    __shared__ float4 Bs4[2][BH_BN * 4];
-    __shared__ uint32_t thr_s[BH_BM];        // running threshold per row: bits of a non-negative float
-    __shared__ float xn2_s[BH_BM];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const uint64_t m0 = (uint64_t)blockIdx.x * BH_BM;
-    const uint32_t dp = a.dim_p;
-    const int ld_r = tid >> 2, ld_ch = tid & 3;
-    float4 ra[2], rb[4];
-    const uint64_t qleft = (a.m - m0) * dp * 2;
-    const __amdgpu_buffer_rsrc_t qres = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint16_t *>(a.x16 + m0 * dp), 0, (int)(qleft > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)qleft), 0x00020000);
-    const uint32_t lane_b = (uint32_t)ld_r * dp * 2 + (uint32_t)ld_ch * 16, r64_b = 64u * dp * 2;
-    __shared__ float xs_s[BH_BM];            // |row - mu| (the square roots are taken once per row / centroid, not per pair)
-    if (tid < BH_BM) {
-        thr_s[tid] = 0x7F800000u;            // +inf
-        const float xn = m0 + tid < a.m ? a.xn2[m0 + tid] : 0.0f;
-        xn2_s[tid] = xn;
-        xs_s[tid] = sqrtf(xn) * 1.000001f;
-    }
-    const int l31 = lane & 31, lk = lane >> 5;
-    int rowa[2], rowb[4], swa[2], swb[4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) { rowa[t] = wm * 64 + t * 32 + l31; swa[t] = (rowa[t] >> 2) & 3; }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { rowb[t] = wn * 128 + t * 32 + l31; swb[t] = (rowb[t] >> 2) & 3; }
-    const uint32_t nk = dp / BH_BK;
-    const float inv = 1.52587890625e-05f;    // 2^-16
-
-    for (uint32_t c0 = 0; c0 < a.kc; c0 += BH_BN) {
-        const uint64_t vleft = (uint64_t)(a.kc_pad - c0) * dp * 2;
-        const __amdgpu_buffer_rsrc_t vres = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint16_t *>(a.c16 + (uint64_t)c0 * dp), 0, (int)(vleft > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)vleft), 0x00020000);
-        auto fetch = [&](uint32_t k0) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) ra[h] = buf_ld16(qres, lane_b, k0 * 2 + h * r64_b);
-#pragma unroll
-            for (int h = 0; h < 4; ++h) rb[h] = buf_ld16(vres, lane_b, k0 * 2 + h * r64_b);
-        };
-        auto stash = [&](int buf) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { const int r = ld_r + 64 * h; As4[buf][r * 4 + (ld_ch ^ ((r >> 2) & 3))] = ra[h]; }
-#pragma unroll
-            for (int h = 0; h < 4; ++h) { const int r = ld_r + 64 * h; Bs4[buf][r * 4 + (ld_ch ^ ((r >> 2) & 3))] = rb[h]; }
-        };
-        f32x16_t acc[2][4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-        fetch(0);
-        stash(0);
-        __syncthreads();
-        for (uint32_t kt = 0; kt < nk; ++kt) {
-            const int buf = (int)(kt & 1u);
-            if (kt + 1 < nk) fetch((kt + 1) * BH_BK);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                f16x8_t av[2], bv[4];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) av[t] = __builtin_bit_cast(f16x8_t, As4[buf][rowa[t] * 4 + ((2 * j + lk) ^ swa[t])]);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) bv[t] = __builtin_bit_cast(f16x8_t, Bs4[buf][rowb[t] * 4 + ((2 * j + lk) ^ swb[t])]);
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-                        acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[jj], acc[i][jj], 0, 0, 0);
-            }
-            if (kt + 1 < nk) stash(buf ^ 1);
-            __syncthreads();
-        }
-        // ---- bounds of this centroid tile.  C/D layout: col = lane & 31 (centroid), row = (r & 3) + 8 (r >> 2) + 4 lk
-        float cn2[4], cs[4];
-        bool cv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t vj = c0 + wn * 128 + j * 32 + l31;
-            cv[j] = vj < a.kc;
-            cn2[j] = cv[j] ? a.cn2[vj] : 0.0f;
-            cs[j] = sqrtf(cn2[j]) * 1.000001f;
-        }
-        auto bounds = [&](int i, int j, int r, float &lb, float &ub) {
-            const int ml = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-            const float xn = xn2_s[ml], nn = xn + cn2[j];
-            const float qv = xs_s[ml] * cs[j];                      // >= |a| |b|
-            const float dt = nn - 2.0f * qv * (acc[i][j][r] * inv);
-            const float err = 2.0f * qv * a.eps + 4.0e-6f * nn;
-            ub = fmaxf(dt + err, 0.0f) * (1.0f + a.cm) + 1.0e-30f;
-            lb = fmaxf(dt - err, 0.0f) * (1.0f - a.cm);
-        };
-        // (1) the rows' running thresholds: smallest upper bound of this tile, reduced over the 32 centroid lanes
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float mn = INFINITY;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float lb, ub;
-                    bounds(i, j, r, lb, ub);
-                    if (cv[j] && ub < mn) mn = ub;                  // (a NaN bound never lowers a threshold)
-                }
-#pragma unroll
-                for (int off = 16; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
-                if (l31 == 0 && mn < INFINITY)
-                    atomicMin(&thr_s[wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk], __float_as_uint(mn));
-            }
-        }
-        __syncthreads();
-        // (2) candidates: every centroid whose lower bound does not exceed its row's threshold (NaN bounds are kept)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ml = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                const float thr = __uint_as_float(thr_s[ml]);
-                const uint64_t row = m0 + ml;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float lb, ub;
-                    bounds(i, j, r, lb, ub);
-                    if (cv[j] && row < a.m && !(lb > thr)) {
-                        const uint32_t slot = atomicAdd(&a.cand_cnt[row], 1u);
-                        if (slot < a.cap) a.cand[row * a.cap + slot] = c0 + wn * 128 + j * 32 + l31;
-                    }
-                }
-            }
-        }
-        __syncthreads();          // the LDS stages are reused by the next centroid tile
-    }
-}
-hipError_t launch_assign_f16(const AssignF16Args &a, hipStream_t s) {
-    if (a.m == 0 || a.kc == 0) return hipSuccess;
-    if ((a.dim_p % BH_BK) != 0 || (uint64_t)a.dim_p * 2 * 320 >= 0x7FFFFFFFull || (a.kc_pad % BH_BN) != 0 || a.kc_pad < a.kc)
-        return hipErrorInvalidValue;
-    const uint64_t blocks = (a.m + BH_BM - 1) / BH_BM;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(assign_f16_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// exact pass: four lanes per row, each walking candidates 4 t + (lane & 3) of its row in the reference's order
-__global__ __launch_bounds__(256) void assign_rescore_kernel(const float *__restrict__ rows, const float *__restrict__ centroids, uint64_t m,
-                                                            uint32_t dim, uint32_t kc, const uint32_t *__restrict__ cand,
-                                                            const uint32_t *__restrict__ cand_cnt, uint32_t cap, uint32_t *__restrict__ cluster) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t row = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (uint32_t)(lane >> 2);
-    const uint32_t cl = (uint32_t)lane & 3u;
-    const bool live = row < m;
-    uint32_t cnt = live ? cand_cnt[row] : 0u;
-    const bool all = cnt > cap;                       // list overflowed: every centroid is a candidate
-    if (all) cnt = kc;
-    const float *x = rows + (live ? row : 0) * dim;
-    const uint32_t G = dim >> 2;
-    uint64_t best = KEY_EMPTY;
-    uint32_t rounds = (cnt + 3) >> 2;
-    // (the loop count differs per lane: no cross-lane operation inside)
-    for (uint32_t t = 0; t < rounds; ++t) {
-        const uint32_t ci = 4 * t + cl;
-        if (ci >= cnt) break;
-        const uint32_t j = all ? ci : cand[row * cap + ci];
-        const float *c = centroids + (uint64_t)j * dim;
-        float sum = 0.0f;
-        uint32_t g = 0;
-        for (; g + 8 <= G; g += 8) {
-            float4 xv[8], cvv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { xv[u] = load4<true>(x + (g + u) * 4); cvv[u] = load4<true>(c + (g + u) * 4); }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float d0 = xv[u].x - cvv[u].x, d1 = xv[u].y - cvv[u].y, d2 = xv[u].z - cvv[u].z, d3 = xv[u].w - cvv[u].w;
-                float tt = d0 * d0 + d1 * d1;
-                tt = tt + d2 * d2;
-                sum = sum + (tt + d3 * d3);
-            }
-        }
-        for (; g < G; ++g) {
-            const float4 xv = load4<true>(x + g * 4), cv = load4<true>(c + g * 4);
-            const float d0 = xv.x - cv.x, d1 = xv.y - cv.y, d2 = xv.z - cv.z, d3 = xv.w - cv.w;
-            float tt = d0 * d0 + d1 * d1;
-            tt = tt + d2 * d2;
-            sum = sum + (tt + d3 * d3);
-        }
-        const uint64_t key = ((uint64_t)__float_as_uint(sum) << 32) | j;
-        best = key < best ? key : best;
-    }
-    // the row's four lanes: smallest (distance bits, index) = strict '<' in ascending centroid order (index.rs:408-415)
-#pragma unroll
-    for (int off = 1; off < 4; off <<= 1) {
-        const uint64_t o = shfl_u64(best, lane ^ off);
-        best = o < best ? o : best;
-    }
-    if (live && cl == 0) cluster[row] = best == KEY_EMPTY ? 0u : (uint32_t)best;
-}
-// The same result with coalesced reads: a wave still owns 16 rows x 4 candidate slots per round, but the 64 lanes read one
-// row (and each of its candidates' centroids) 1 KB at a time -- lane g computes the 4-group term of group g -- and park the
-// terms in LDS [group][slot] (stride 65: conflict-free both ways); lane `slot` then adds its 64 terms in ascending group order,
-// which is the reference's chain (index.rs:461-480).  A row is read once for its four slots.
-__global__ __launch_bounds__(128) void assign_rescore_wave_kernel(const float *__restrict__ rows, const float *__restrict__ centroids, uint64_t m,
-                                                                 uint32_t dim, uint32_t kc, const uint32_t *__restrict__ cand,
-                                                                 const uint32_t *__restrict__ cand_cnt, uint32_t cap, uint32_t *__restrict__ cluster) {
-    __shared__ float lds_all[2][64 * 65];
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    float *lds = lds_all[wv];
-    const uint64_t wave_row0 = ((uint64_t)blockIdx.x * 2 + (uint32_t)wv) * 16;
-    const uint64_t row = wave_row0 + (uint32_t)(lane >> 2);
-    const uint32_t cl = (uint32_t)lane & 3u;
-    const bool live = row < m;
-    uint32_t cnt = live ? cand_cnt[row] : 0u;
-    const bool all = cnt > cap;                       // list overflowed: every centroid is a candidate
-    if (all) cnt = kc;
-    const uint32_t G = dim >> 2;
-    uint64_t best = KEY_EMPTY;
-    for (uint32_t t = 0;; ++t) {
-        const uint32_t ci = 4 * t + cl;
-        const bool act = ci < cnt;
-        const uint64_t mask = __ballot(act);
-        if (mask == 0) break;
-        const uint32_t j = act ? (all ? ci : cand[row * cap + ci]) : 0u;
-        float sum = 0.0f;
-        for (uint32_t g0 = 0; g0 < G; g0 += 64) {
-            const uint32_t ng = (G - g0 < 64u) ? (G - g0) : 64u;
-            const bool gv = (uint32_t)lane < ng;
-            const uint32_t goff = (g0 + (gv ? (uint32_t)lane : 0u)) * 4;
-#pragma unroll 1
-            for (int r = 0; r < 16; ++r) {
-                const uint32_t m4 = (uint32_t)(mask >> (4 * r)) & 0xFu;     // wave-uniform
-                if (m4 == 0) continue;
-                const float4 xv = load4<true>(rows + (wave_row0 + (uint32_t)r) * dim + goff);
-                float4 cv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const uint32_t jp = readlane_u32(j, 4 * r + u);
-                    cv[u] = load4<true>(centroids + (uint64_t)jp * dim + goff);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float d0 = xv.x - cv[u].x, d1 = xv.y - cv[u].y, d2 = xv.z - cv[u].z, d3 = xv.w - cv[u].w;
-                    float tt = d0 * d0 + d1 * d1;
-                    tt = tt + d2 * d2;
-                    tt = tt + d3 * d3;
-                    if (gv) lds[lane * 65 + 4 * r + u] = tt;
-                }
-            }
-            wave_lds_fence();
-            uint32_t e = 0;
-            for (; e + 8 <= ng; e += 8) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = lds[(e + u) * 65 + lane];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) sum = sum + v[u];
-            }
-            for (; e < ng; ++e) sum = sum + lds[e * 65 + lane];
-            wave_lds_fence();
-        }
-        if (act) {
-            const uint64_t key = ((uint64_t)__float_as_uint(sum) << 32) | j;
-            best = key < best ? key : best;
-        }
-    }
-    // the row's four lanes: smallest (distance bits, index) = strict '<' in ascending centroid order (index.rs:408-415)
-#pragma unroll
-    for (int off = 1; off < 4; off <<= 1) {
-        const uint64_t o = shfl_u64(best, lane ^ off);
-        best = o < best ? o : best;
-    }
-    if (live && cl == 0) cluster[row] = best == KEY_EMPTY ? 0u : (uint32_t)best;
-}
-hipError_t launch_assign_rescore(const float *rows, const float *centroids, uint64_t m, uint32_t dim, uint32_t kc, const uint32_t *cand,
-                                 const uint32_t *cand_cnt, uint32_t cap, uint32_t *cluster, hipStream_t s) {
-    if (m == 0) return hipSuccess;
-    if ((dim % 4) != 0) return hipErrorInvalidValue;
-    // PQV_RESCORE_WAVE=0: the lane-per-(row, candidate) form above (A/B)
-    static const bool wave_form = [] { const char *e = getenv("PQV_RESCORE_WAVE"); return !(e && *e == '0'); }();
-    if (wave_form && dim >= 64) {
-        const uint64_t wblocks = (m + 31) / 32;
-        if (wblocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(assign_rescore_wave_kernel, dim3((uint32_t)wblocks), dim3(128), 0, s, rows, centroids, m, dim, kc, cand, cand_cnt, cap, cluster);
-        return hipGetLastError();
-    }
-    const uint64_t blocks = (m + 63) / 64;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(assign_rescore_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, rows, centroids, m, dim, kc, cand, cand_cnt, cap, cluster);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// Round 4: assign_wide_kernel + assign_resolve_kernel (see kernels.h: AssignWideArgs).
+// The k-means assignment (index.rs:395-430 Lloyd, :189-206 + :244-257 final) as a dense contraction on the f16 matrix pipe + exact
+// evaluation of what it leaves open: assign_wide_kernel + assign_resolve_kernel (see kernels.h: AssignWideArgs) -- the brute-force
+// design with the roles swapped: every ROW keeps a running best and a candidate list, the CENTROIDS are the streamed side.  Rows and
+// centroids are imaged about a common centre mu (any fixed vector: the distance is translation invariant; centring shrinks
+// |x - mu| |c - mu| and with it the bound's slack).
 //
 // Block = 256 rows against ALL centroids, 256 at a time; 8 waves as 2 (centroid side, M) x 4 (row side, N), each 128 centroids
 // x 64 rows = 4 x 2 tiles of v_mfma_f32_32x32x16_f16; K in 128-byte stages through double-buffered, chunk-swizzled LDS
@@ -523,7 +215,10 @@ hipError_t launch_assign_wide(const AssignWideArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// The second half: a wave owns 16 rows x 4 candidate slots per round (assign_rescore_wave_kernel's tiling).  A row's candidates
+// The second half: a wave owns 16 rows x 4 candidate slots per round.  The exact chains read coalesced: the 64 lanes read one row
+// (and each of its candidates' centroids) 1 KB at a time -- lane g computes the 4-group term of group g -- and park the terms in LDS
+// [group][slot] (stride 65: conflict-free both ways); lane `slot` then adds its 64 terms in ascending group order, which is the
+// reference's chain (index.rs:461-480).  A row is read once for its four slots.  A row's candidates
 // are first filtered against the row's FINAL best; a row left with one survivor is done -- its f32 row is never read -- and
 // only rows with two or more (or an overflowed list: every centroid) go through the exact chains.
 __global__ __launch_bounds__(128) void assign_resolve_kernel(const AssignWideArgs a, const float *__restrict__ rows, const float *__restrict__ centroids,

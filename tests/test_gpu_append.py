@@ -195,6 +195,19 @@ def test_ties_go_to_the_lower_index(pqv, oracle, dim, k):
     _check_index(oracle, index.append(corpus, n0, m), dim, C, append_ref.splice([[]] * k, want, n0))
 
 
+@pytest.mark.parametrize("value", [0.0, 3.0])
+def test_identical_centroids_leave_every_row_in_cluster_0(pqv, value):
+    """130 copies of one centroid: every one lies at their mean, the contraction's image scale is degenerate and the tier does not
+    decide -- the ladder steps down.  300 rows: one full 256-row tile and a part-filled one; value 3: the mean is not the origin."""
+    dim, k, n = 8, 130, 300
+    X = np.random.default_rng(130).standard_normal((n, dim)).astype(np.float32)
+    C = np.full((k, dim), value, np.float32)
+    want = assign_exact.nearest(X, C)[0]
+    assert (want == 0).all()                  # the reference's strict `<`
+    index = pqv.Index.from_parts(dim, C, [np.zeros(0, np.uint32)] * k)
+    assert (index.assign(pqv.Corpus.upload(X)) == want).all()
+
+
 @pytest.mark.parametrize("name", ["exact_d30_k7", "gemm_d72_k128"])
 def test_non_finite_rows(cases, pqv, oracle, name):
     c = cases(name)

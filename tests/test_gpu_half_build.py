@@ -59,6 +59,19 @@ def test_assign_where_the_screen_can_go_wrong(pqv, dim, kind):
     assert (index.assign_f16(borrowed, 257, 1000) == want[257:1257]).all()
 
 
+@pytest.mark.parametrize("value", [0.0, 3.0])
+def test_identical_centroids_leave_every_row_in_cluster_0(pqv, value):
+    """130 copies of one centroid: every one lies at their mean, the centroid images' scale is degenerate and the screen does not
+    decide -- the exact kernel does.  300 rows: one full 256-row tile and a part-filled one; value 3: the mean is not the origin."""
+    dim, k, n = 8, 130, 300
+    h = _halves("normal", n, dim)
+    C = np.full((k, dim), value, np.float32)
+    want = assign_exact.nearest(h.astype(np.float32), C)[0]
+    assert (want == 0).all()                  # the reference's strict `<`
+    index = pqv.Index.from_parts(dim, C, [np.zeros(0, np.uint32)] * k)
+    assert (index.assign_f16(pqv.Corpus.upload(h)) == want).all()
+
+
 def test_append_and_search(pqv, oracle):
     dim, k, n0 = 72, 130, 2000
     h = _halves("normal", N, dim)

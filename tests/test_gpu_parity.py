@@ -1171,7 +1171,7 @@ def test_running_thresholds_with_hundreds_of_tied_candidates(pqv, oracle, monkey
     (40000, 16, 257, 2),         # one centroid past a 256-tile; short rows
 ])
 def test_screened_assignment_builds_identical_index(pqv, oracle, monkeypatch, n, dim, kc, min_k):
-    """Index build with the f16 contraction + exact re-scoring (round 3: assign_f16_kernel), with the f32 MFMA-screened
+    """Index build with the f16 contraction + exact evaluation (assign_wide_kernel), with the f32 MFMA-screened
     assignment and with the exact VALU assignment (Lloyd iterations and final assignment alike) must produce the
     oracle's blob byte for byte."""
     rng = np.random.default_rng(n + dim + kc)

@@ -7,7 +7,7 @@ import conftest
 from oracle_binding import Oracle
 import pq_vector_amd as pqv
 oracle = Oracle()
-os.environ.setdefault("PQV_ASSIGN_SCREEN", "1")          # PQV_ASSIGN_GEMM=2 (the round-3 f16 contraction, forced) / 0 (the f32 screen)
+os.environ.setdefault("PQV_ASSIGN_SCREEN", "1")          # PQV_ASSIGN_GEMM=2 (the f16 contraction, forced) / 0 (the f32 screen)
 bad = 0; t = time.time()
 for seed in range(int(os.environ.get("FZ_LO", 100)), int(os.environ.get("FZ_HI", 130))):
     rng = np.random.default_rng(seed)

@@ -11,7 +11,9 @@ one warm-up build.  Per build: the whole call (host clock), the final-assignment
 digest, so a wrong build cannot be timed.  One more process per side runs under PQV_VERBOSE=1 (not timed) for the line that
 reports the share of rows resolved exactly.  Prints one JSON line and writes it to --out (default
 profiles/half_build_timing.json).  The condition it records: the f16 final assignment is not slower than the parent's f32 one
-beyond the parent's own run-to-run range (max - min over its builds)."""
+beyond the parent's own run-to-run range (max - min over its builds).
+--parent-side f16 times the parent's pqv_index_build_f16 over the same f16 column instead (a parent that has the call): the same
+build on both libraries, for a change that must leave it as fast as it was; the record then says so in its keys."""
 import argparse
 import hashlib
 import json
@@ -29,7 +31,7 @@ def worker(a):
     import torch
     sys.path.insert(0, ROOT)
     from pq_vector_amd import _ffi
-    if a.side == "f32":      # the parent's library has none of the _f16 build entry points: bind what it exports
+    if os.environ.get("PQV_LIB_PATH"):      # a parent's library may lack the _f16 build entry points: bind what it exports
         have = ctypes.CDLL(_ffi.LIB_PATH)
         for name in [n for n in _ffi.SIGNATURES if not hasattr(have, n)]:
             del _ffi.SIGNATURES[name]
@@ -66,6 +68,8 @@ def main():
     ap.add_argument("--builds", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "half_build_timing.json"))
+    ap.add_argument("--parent-side", choices=["f32", "f16"], default="f32",
+                    help="what the parent's library builds: the widened f32 column (default) or the f16 column itself")
     ap.add_argument("--side", choices=["f16", "f32"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.side:
@@ -74,9 +78,10 @@ def main():
         sys.exit("--parent-lib must name the parent commit's libpqv_hip.so")
     shape = [f"--{n}={getattr(a, n)}" for n in ("rows", "dim", "clusters", "workers", "builds")]
 
-    def run(side, verbose):
+    def run(who, verbose):
         env = dict(os.environ)
-        if side == "f32":
+        side = "f16" if who == "f16" else a.parent_side
+        if who == "f32":
             env["PQV_LIB_PATH"] = os.path.abspath(a.parent_lib)
         else:
             env.pop("PQV_LIB_PATH", None)
@@ -94,7 +99,7 @@ def main():
             runs[side].append(rec["builds"])
             digests.add(rec["digest"])
     if len(digests) != 1:
-        sys.exit("the f16 build and the parent's f32 build of the widened column gave different index blobs")
+        sys.exit("the f16 build and the parent's build gave different index blobs")
     lines = {}
     for side in ("f16", "f32"):
         rec, err = run(side, True)
@@ -120,8 +125,10 @@ def main():
            "timing": {"builds_per_process": a.builds, "rounds": a.rounds, "warmup_builds": 1,
                       "clock": "pqv_index_build_stats of each build (host clock of the phase; HIP events around the contraction kernel); "
                                "host clock around the whole call; sides alternate, one process each"},
-           "f16_this_tree_build_f16": f16, "f32_parent_build_of_widened_column": f32,
-           "final_assign_ratio_f32_over_f16": round(f32["final_assign"]["median_ms"] / f16["final_assign"]["median_ms"], 4),
+           "f16_this_tree_build_f16": f16,
+           "f32_parent_build_of_widened_column" if a.parent_side == "f32" else "f16_parent_build_f16": f32,
+           "final_assign_ratio_f32_over_f16" if a.parent_side == "f32" else "final_assign_ratio_parent_over_this_tree":
+               round(f32["final_assign"]["median_ms"] / f16["final_assign"]["median_ms"], 4),
            "parent_final_assign_range_ms": round(parent_range, 3),
            "f16_final_assign_not_slower_beyond_parent_range": f16["final_assign"]["median_ms"] <= f32["final_assign"]["median_ms"] + parent_range,
            "verbose_exact_share": lines, "blobs_identical": True}
