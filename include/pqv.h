@@ -211,12 +211,29 @@ void pqv_corpus_free(pqv_corpus *corpus);
  *   fetch       pqv_corpus_fetch_rows returns the widened f32 values.
  *   searcher    pqv_searcher_create(index, f16 corpus, flags, &out) makes a searcher that keeps NO row-derived layout -- no
  *               list-ordered copy, screen images, norms or cosine layout; flags other than PQV_PREPARE_COSINE (refused) change
- *               nothing, nor do the options of pqv_searcher_set_option.  Centroids stay f32.  Every search runs the exact stream
- *               (stream_h_kernel: 16-byte loads of eight halves, widened by the hardware conversion, both 4-group partials of a
- *               load parked in the chain tile), as rerank_mode = 1 does on f32.  pqv_searcher_footprint counts 2 bytes per value.
+ *               nothing, nor do the options of pqv_searcher_set_option other than rerank_mode = 2 (below).  Centroids stay f32.
+ *               By default every search runs the exact stream (stream_h_kernel: 16-byte loads of eight halves, widened by the
+ *               hardware conversion, both 4-group partials of a load parked in the chain tile), as rerank_mode = 1 does on f32.
+ *               pqv_searcher_footprint counts 2 bytes per value.
+ *   screened    opt-in: pqv_searcher_set_option(s, "rerank_mode", 2), or PQV_RERANK_MODE=tile at creation.  pqv_topk,
+ *               pqv_topk_device and pqv_topk_device_flags then screen the candidates on the matrix cores with the STORED rows as the
+ *               operand (screen_h_kernel) and spend the exact chain on the survivors only (survivor_h_kernel).  Results are the
+ *               default route's by definition -- row ids, distance bits, n_found, n_candidates and tie flags identical; options
+ *               never change results.  The route applies to PQV_L2SQ_REF4 with dim % 8 == 0, dim <= 2240, k <= 127 (128 for a
+ *               device call that takes no tie flags: the lists of the other forms carry the runner-up) and min(nprobe, n_clusters)
+ *               <= 1024, batches of at most 65535 queries per device call; everything else (PQV_L2SQ_SEQ, range search, other dims,
+ *               larger k or nprobe) stays on stream_h_kernel silently, and rerank_mode 0 and 1 are the default route.
+ *               pqv_searcher_describe names the route that will run.  The first screened call makes the searcher's one row-derived
+ *               buffer -- an upper bound of |x| per row, 4 bytes a row (0.26 % of a 768-dim column), counted by
+ *               pqv_searcher_footprint under other_bytes -- and waits for it once; no later call gains a host synchronisation.
+ *               Counters: queries, candidate_rows and embeddings_fetched advance as on the default route (embeddings_fetched by
+ *               the capped candidates, as the f32 screened route counts it, not by the rows evaluated); screened_pairs by the
+ *               (row, query) pairs put through the bound; screen_survivors by the rows evaluated exactly behind it, the full walks
+ *               of queries that fall back (non-finite, all-zero, fewer than k candidates, survivor list overflow) included.
  *   served      pqv_topk (tie replay and k / nprobe beyond 1024 included), pqv_topk_device, pqv_topk_device_flags and
  *               pqv_range_search with PQV_L2SQ_REF4 / PQV_L2SQ_SEQ; max_candidates, sqrt_out, max_results as on f32.  pqv_probe,
- *               pqv_candidate_rows, the counters (screened_pairs / screen_survivors do not advance) and the timing calls work.
+ *               pqv_candidate_rows, the counters (screened_pairs / screen_survivors advance on the screened route only) and the
+ *               timing calls work.
  *   refused     everything else that would read row values returns PQV_ERR_UNSUPPORTED "<entry point> does not take f16
  *               corpora" before any device work, behind the entry point's own handle checks: PQV_COSINE and PQV_DOT on the served
  *               calls (the text names the metric: "PQV_DOT does not take f16 corpora"), the masked, keyed, filtered, expanding,

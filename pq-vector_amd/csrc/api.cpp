@@ -367,6 +367,8 @@ struct Scratch {
         s_ps_q16, s_ps_qn2, s_ps_score, // screened probe: the batch's query images f16 [nq][dim_p], |q - mean|^2 [nq], the scores f32 [nq][kc_pad]
         s_seg_off,                      // pqv_range_search_partition: the group's packed segment offsets u64 [b]
         s_pt_beg, s_pt_end, s_pt_nspan, // pqv_topk_partition: the spans' first entries u32 [nq] (IN: [nq][1024]), IN: their prefix sums and counts
+        s_hs_q16, s_hs_qinfo, s_hs_qflag, s_hs_sort, s_hs_surv, s_hs_cnt,   // the screened f16 route (HalfScreenArgs): query images, {|q|^2, scale, qs, tau},
+                                            // exact flags, the pair bucketing's u32 tables, the survivor lists and their counts
         s_mmr_rows, s_mmr_dist, s_mmr_nf;   // pqv_topk_mmr: stage 1's rows u32 / distances f32 [nq][fetch_k] and n_found u32 [nq]; pqv_mmr_select's host form: the candidates
     PinnedBuf h_io;                 // small host calls: queries in, one block of results out, through pinned memory
     hipEvent_t done = nullptr;      // recorded after the last kernel of the call that used this lane
@@ -384,7 +386,7 @@ struct Scratch {
                 &s_pair_end, &s_file_cnt, &s_qcos, &s_qkeys, &s_qfilt_a, &s_qfilt_b, &s_part_grp, &s_grp_out,
                 &s_g1_rows, &s_g1_dist, &s_g1_keys, &s_g1_nfound, &s_gset_keys, &s_gset_slot, &s_gpart_slot, &s_gpart_cnt, &s_grows_out,
                 &s_expand_cnt, &s_expand_used, &s_depths, &s_depth_d2, &s_depth_end, &s_ps_q16, &s_ps_qn2, &s_ps_score, &s_seg_off, &s_pt_beg, &s_pt_end, &s_pt_nspan,
-                &s_mmr_rows, &s_mmr_dist, &s_mmr_nf};
+                &s_hs_q16, &s_hs_qinfo, &s_hs_qflag, &s_hs_sort, &s_hs_surv, &s_hs_cnt, &s_mmr_rows, &s_mmr_dist, &s_mmr_nf};
     }
     ~Scratch() {
         if (done) (void)hipEventDestroy(done);
@@ -422,6 +424,8 @@ struct pqv_searcher {
     const uint16_t *d_mat_h = nullptr;     // a searcher over an f16 corpus: its rows (row order, through d_row_of); d_mat stays NULL and no
                                            // row-derived layout exists -- every search is the exact stream over launch_stream_h
     bool half() const { return d_mat_h != nullptr; }
+    mutable DevBuf d_half_xs;              // ... its one row-derived buffer: xs >= |x| per storage row, f32, made by the first screened call
+                                           // (rerank_mode 2: ensure_half_xs, under norms_mu)
     const uint32_t *d_row_of = nullptr;    // list position -> storage row (ROW_ORDER layout, and the images-only IVF layout)
     const uint32_t *d_final_ids = nullptr; // storage row -> file row id (IVF layout with its own f32 copy)
     // IVF-ordered layout WITHOUT a second f32 copy of the corpus (round 4): everything the screen streams -- the blocked operand
@@ -4279,6 +4283,7 @@ struct TopkPlan {
     uint32_t slots_per_pair;   // partial lists per (query, probe rank)
     uint32_t wide_width;    // > 0: quads of 97..wide_width pairs go to the wide-quad instance (its own item table)
     uint32_t wide_rows_per_block, wide_bpl;
+    bool half_screen;       // f16 rows under rerank_mode 2: screen_h_kernel + survivor_h_kernel instead of stream_h_kernel (half_screen_applies)
     bool list_once;         // the wide table's quads hold up to wide_width (<= 1024) pairs of ONE list and run in list_filter_kernel
 };
 
@@ -4325,7 +4330,8 @@ static bool seed_refine_on(const pqv_searcher *s, uint32_t nq, uint32_t k) {
 TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t k = 1, int metric = 0, bool exact_stream = false) {
     TopkPlan p{};
     const pqv_searcher::Opts &o = s->opt;
-    if (metric == PQV_DOT) exact_stream = true;     // (pqv.h: always the exact stream, whatever the options say)
+    const bool stream_req = exact_stream;           // (as asked for by the call: a request's walk)
+    if (metric == PQV_DOT) exact_stream = true;    // (pqv.h: always the exact stream, whatever the options say)
     if (s->half()) exact_stream = true;             // (f16 rows: no screen images exist)
     p.np = probe_count(s, nprobe);
     // probe pass: every block scans 256 centroids (64 per wave)
@@ -4504,6 +4510,14 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     }
     stream_split(max_len, pairs, p.rr_rows_per_block, p.rr_bpl);
     p.n_part_rr = p.np * p.rr_bpl * pqv::waves_per_block();
+    // f16 rows, rerank_mode 2 (pqv.h: half-precision corpora): the screened route where it applies -- a plain REF4 call,
+    // rows of whole 16-byte chunks whose query tile fits LDS, lists of at most 128 entries (k <= 127 where the list carries the
+    // runner-up for the tie flag), the probe within the kernels' lists.  Everything else stays on stream_h_kernel: options never
+    // change results.  The survivor pass writes HS_PARTS lists per query.
+    p.half_screen = s->half() && o.rerank_mode == 2 && metric == PQV_L2SQ_REF4 && !stream_req && (s->dim % 8) == 0 && k <= 128 &&
+                    p.np >= 1 && p.np <= 1024 && nq <= 0xFFFFu && static_cast<uint64_t>(nq) * p.np <= 0x7FFFFFFFull &&
+                    32ull * ((s->dim + 63) / 64 * 8 + 1) * 16 <= pqv::half_screen_lds_max();
+    if (p.half_screen) p.n_part_rr = pqv::HS_PARTS;
     return p;
 }
 
@@ -5228,6 +5242,49 @@ static int enqueue_plain_fold(TopkCall &c, const pqv::StreamArgs &ra) {
     return PQV_OK;
 }
 
+// The one row-derived buffer of an f16 searcher (pqv.h: half-precision corpora, rerank_mode 2): xs >= |x| per storage row, 4 bytes a
+// row.  Made by the first screened call, once per searcher (that call waits for it: later calls on other streams read it).
+static int ensure_half_xs(const pqv_searcher *s, hipStream_t stream) {
+    std::lock_guard<std::mutex> lock(s->norms_mu);
+    if (s->d_half_xs.p) return PQV_OK;
+    const uint64_t rows = s->corpus->n;
+    DevBuf xs;
+    HIP_TRY(xs.alloc(std::max<uint64_t>(1, rows) * sizeof(float)));
+    HIP_TRY(pqv::launch_half_xs(s->d_mat_h, rows, s->dim, xs.as<float>(), stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    std::swap(s->d_half_xs.p, xs.p); std::swap(s->d_half_xs.bytes, xs.bytes);
+    s->counters.kernel_launches += 1;
+    return PQV_OK;
+}
+// survivor entries per query of the screened f16 route: 4096, fewer for very large batches (a list that overflows is walked exactly)
+static uint32_t half_surv_cap(uint32_t nq) { return static_cast<uint32_t>(std::max<uint64_t>(512, std::min<uint64_t>(4096, (1ull << 26) / std::max<uint32_t>(1, nq)))); }
+// stage 2 of an f16 searcher under rerank_mode 2 (TopkPlan::half_screen): query images, seed thresholds, the pairs bucketed by list,
+// screen_h_kernel and survivor_h_kernel -- the per-wave lists the final merge reads, keys as stream_h_kernel writes them
+static int enqueue_half_screen(TopkCall &c, const pqv::StreamArgs &ra) {
+    using namespace pqv;
+    const pqv_searcher *s = c.s; Scratch &sc = c.sc; const uint32_t nq = c.nq, kc = s->n_clusters, np = c.p.np;
+    if (int rc = ensure_half_xs(s, c.stream)) return rc;
+    const uint32_t dim_p = (s->dim + 63) / 64 * 64;
+    HalfScreenArgs a{};
+    a.st = ra; a.xs = s->d_half_xs.as<float>(); a.n_clusters = kc;
+    a.qt = 64ull * (dim_p / 8 + 1) * 16 <= half_screen_lds_max() ? 64u : 32u;
+    a.surv_cap = half_surv_cap(nq);
+    HIP_TRY(sc.s_hs_q16.ensure(static_cast<size_t>(nq) * dim_p * sizeof(uint16_t)));
+    HIP_TRY(sc.s_hs_qinfo.ensure(static_cast<size_t>(nq) * sizeof(float4)));
+    HIP_TRY(sc.s_hs_qflag.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_hs_sort.ensure((4 * static_cast<size_t>(kc) + 2 + static_cast<size_t>(nq) * np) * sizeof(uint32_t)));
+    HIP_TRY(sc.s_hs_surv.ensure(static_cast<size_t>(nq) * a.surv_cap * sizeof(uint2)));
+    HIP_TRY(sc.s_hs_cnt.ensure(static_cast<size_t>(nq) * sizeof(uint32_t)));
+    a.q16 = sc.s_hs_q16.as<uint16_t>(); a.qinfo = sc.s_hs_qinfo.as<float4>(); a.qflag = sc.s_hs_qflag.as<uint32_t>();
+    uint32_t *u = sc.s_hs_sort.as<uint32_t>();
+    a.hist = u; a.pair_off = u + 2ull * kc; a.item_off = u + 3ull * kc + 1; a.pairs = u + 4ull * kc + 2;
+    a.surv = sc.s_hs_surv.as<uint2>(); a.surv_cnt = sc.s_hs_cnt.as<uint32_t>();
+    a.stats = s->d_stats.as<unsigned long long>();
+    HIP_TRY(launch_half_screen(a, c.stream));
+    s->counters.kernel_launches += 5;       // (six launches for the stream pass's one)
+    return PQV_OK;
+}
+
 // Enqueue probe -> probe-merge -> re-rank -> final merge for one batch on `stream`: the stages above, in order.
 // `k` is the list length the kernels work with; the first k_out entries are written out.
 // With k == k_out + 1 the merge can also flag queries whose output distances tie (d_tie).
@@ -5267,9 +5324,13 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     StreamArgs ra = stream_args(s, sc, c.d_queries_s, nq, p.np, k, max_candidates, metric);
     ra.rows_per_block = p.rr_rows_per_block; ra.blocks_per_list = p.rr_bpl;
     ra.part_keys = sc.s_part_keys.as<uint64_t>(); ra.part_vals = sc.s_part_vals.as<uint32_t>();
-    if (!p.tile) {
+    if (p.half_screen) {
         if (c.ev[1]) HIP_TRY(hipEventRecord(c.ev[1], stream));
-        if (depth) {       // (no filter: the plain walk, a cut rank's blocks storing empty lists; probe_depth has counted the candidates)
+        if (int rc = enqueue_half_screen(c, ra)) return rc;
+        if (c.ev[2]) HIP_TRY(hipEventRecord(c.ev[2], stream));
+    } else if (!p.tile) {
+        if (c.ev[1]) HIP_TRY(hipEventRecord(c.ev[1], stream));
+        if (depth) {      // (no filter: the plain walk, a cut rank's blocks storing empty lists; probe_depth has counted the candidates)
             HIP_TRY(launch_limited_stream(ra, MaskedArgs{nullptr, nullptr, nullptr, c.rank_limit}, stream));
         } else
         HIP_TRY(launch_stream_pass(ra, rq, s->d_stats.as<unsigned long long>(), c.pm.n_cand, STREAM_TOPK, stream,
@@ -8035,7 +8096,16 @@ static int pqv_searcher_describe_impl(const pqv_searcher *s, uint32_t nq, uint32
         std::snprintf(buf + end, len - end, "; distances halved in the final write-out (merge_kernel / range write-out)");
         return PQV_OK;
     }
-    if (s->half()) {       // (pqv.h: half-precision corpora -- one route, whatever the options say)
+    if (s->half()) {       // (pqv.h: half-precision corpora -- the exact stream, or under rerank_mode 2 the screened route where it applies)
+        // (k + 1: the list of the host form and of a device call that takes tie flags carries the runner-up)
+        if (!beyond_kernel_lists(s, k, nprobe) && plan_topk(s, std::max<uint32_t>(1, nq), nprobe, k + 1, metric).half_screen) {
+            std::snprintf(buf, len, "f16 rows, rerank_mode 2: the centroid probe over the f32 centroids, then half_query_kernel + half_seed_kernel "
+                          "(tau: k-th exact distance among the first ~sqrt(candidates k) candidates in probe order) + screen_h_kernel (kernels_half_screen.hip: "
+                          "v_mfma_f32_32x32x16_f16, the stored rows as the operand, tiles of %u queries in LDS) + survivor_h_kernel (the exact "
+                          "chain on the survivors; flagged queries walk their lists) + merge_kernel; STREAM_DIST for tie replays",
+                          64ull * ((s->dim + 63) / 64 * 8 + 1) * 16 <= pqv::half_screen_lds_max() ? 64u : 32u);
+            return PQV_OK;
+        }
         std::snprintf(buf, len, "f16 rows: %s, then stream_h_kernel (kernels_half.hip: the exact stream over 2-byte rows, widened per load; %s) + merge_kernel",
                       beyond_kernel_lists(s, k, nprobe) ? "host probe" : "the centroid probe over the f32 centroids",
                       beyond_kernel_lists(s, k, nprobe) ? "STREAM_DIST, selection by the reference's heap on the host" : "STREAM_TOPK; STREAM_DIST for tie replays");
@@ -8148,7 +8218,7 @@ static int pqv_searcher_footprint_impl(const pqv_searcher *s, uint64_t *row_orde
     if (ivf_rows_bytes) *ivf_rows_bytes = s->d_mat_ivf.p ? s->d_mat_ivf.bytes : 0;
     if (blocked_bytes) *blocked_bytes = (s->d_mat_blk_op[0].p ? s->d_mat_blk_op[0].bytes : 0) + (s->d_mat_blk_op[1].p ? s->d_mat_blk_op[1].bytes : 0) +
                                         (s->d_mat_blk_op[2].p ? s->d_mat_blk_op[2].bytes : 0);
-    uint64_t other = s->d_centroids.bytes + s->d_cent_t.bytes + s->d_ps_mu.bytes + s->d_ps_c16.bytes + s->d_ps_cn2.bytes + s->d_ps_stats.bytes + s->d_list_off.bytes + s->d_ids.bytes + s->d_row_map.bytes + s->d_stats.bytes + s->d_row_norm2.bytes + s->d_blk_off.bytes +
+    uint64_t other = s->d_centroids.bytes + s->d_cent_t.bytes + s->d_ps_mu.bytes + s->d_ps_c16.bytes + s->d_ps_cn2.bytes + s->d_ps_stats.bytes + s->d_list_off.bytes + s->d_ids.bytes + s->d_row_map.bytes + s->d_stats.bytes + s->d_row_norm2.bytes + s->d_half_xs.bytes + s->d_blk_off.bytes +
                      s->d_center.bytes + s->d_list_scale.bytes + s->d_list_half.bytes + s->d_list_radius.bytes + s->d_row_n2i.bytes + s->d_row_res.bytes;
     for (const Scratch &l : s->lanes)
         for (const DevBuf *b : l.bufs()) other += b->p ? b->bytes : 0;

@@ -81,6 +81,29 @@ hipError_t launch_stream(const StreamArgs &a, StreamMode mode, hipStream_t s);
 // keys and output formats, the distance the reference chain over the row widened to f32 (exact) -- bit-identical to launch_stream
 // over the widened rows.  metric PQV_L2SQ_REF4 / PQV_L2SQ_SEQ; a.mat is not read.  No load reaches behind a row's last byte.
 hipError_t launch_stream_h(const StreamArgs &a, StreamMode mode, hipStream_t s);
+// The screened top-k route over 2-byte rows (kernels_half_screen.hip; pqv.h: rerank_mode 2 on an f16 searcher).
+// launch_half_xs: xs[r] >= |row r| for the n rows of the column (dim % 8 == 0), +inf where a row holds Inf / NaN.
+hipError_t launch_half_xs(const uint16_t *rows, uint64_t n, uint32_t dim, float *xs, hipStream_t s);
+constexpr uint32_t HS_PARTS = 8;           // per-wave partial lists per query that survivor_h_kernel writes: [nq][HS_PARTS][k]
+constexpr size_t half_screen_lds_max() { return 147456; }     // the query tile's images: qt (dim_p / 8 + 1) 16 bytes
+struct HalfScreenArgs {
+    StreamArgs st;             // launch_stream_h's arguments behind the probe (mat_h, row_of, list_off, probe, cand_base, queries, nq, nprobe,
+                               // dim, k, max_pos) and the per-wave lists part_keys / part_vals [nq][HS_PARTS][k]
+    const float *xs;           // launch_half_xs's output, by storage row
+    uint32_t n_clusters, qt;   // qt: queries per tile of the screen, 64 or 32 (what fits half_screen_lds_max)
+    uint16_t *q16;             // [nq][dim_p] query images, dim_p = dim rounded up to 64
+    float4   *qinfo;           // [nq] {|q|^2, 2^-e_q, qs >= |q|, tau}
+    uint32_t *qflag;           // [nq] != 0: the query is walked exactly
+    uint32_t *hist;            // [2 n_clusters] pairs per list, and the scatter's cursors
+    uint32_t *pair_off, *item_off;     // [n_clusters + 1] each
+    uint32_t *pairs;           // [nq nprobe] pair ids q nprobe + j bucketed by list
+    uint2    *surv;            // [nq][surv_cap] (candidate position, storage row)
+    uint32_t *surv_cnt;        // [nq]; may exceed surv_cap: the query is then walked exactly
+    uint32_t  surv_cap;
+    unsigned long long *stats; // optional: the statistics block (word 0 += screened pairs, word 1 += rows evaluated exactly)
+};
+// Everything behind the probe of one batch, up to the per-wave lists the final merge reads; k <= 256, nprobe <= 1024, nq <= 65535.
+hipError_t launch_half_screen(const HalfScreenArgs &a, hipStream_t s);
 // out[i, :] = rows[idx[i], :] widened to f32, i < m
 hipError_t launch_widen_rows_h(const uint16_t *rows, const uint32_t *idx, uint64_t m, uint32_t dim, float *out, hipStream_t s);
 
