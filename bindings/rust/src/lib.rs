@@ -561,6 +561,53 @@ impl<'c> Searcher<'c> {
         Ok(out)
     }
 
+    /// [`Searcher::topk_masked`] on a searcher over an f16 corpus (`pqv_topk_masked_f16`): the result equals the f32 call's on the
+    /// widened rows under the same mask.
+    pub fn topk_masked_f16(&self, mask: &RowMask, queries: &[f32], dim: usize, k: NonZeroUsize, nprobe: NonZeroUsize)
+        -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (k, np) = (k.get(), nprobe.get());
+        let mut rows = vec![0u32; nq * k];
+        let mut dist = vec![0f32; nq * k];
+        let mut found = vec![0u32; nq];
+        check(unsafe {
+            sys::pqv_topk_masked_f16(self.raw, mask.raw, queries.as_ptr(), nq as u32, dim as u32, k as u32, np as u32, 0, sys::PQV_L2SQ_REF4, 1,
+                                     rows.as_mut_ptr(), dist.as_mut_ptr(), found.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((0..nq)
+            .map(|q| (0..found[q] as usize).map(|i| SearchResult { row_idx: rows[q * k + i], distance: dist[q * k + i] }).collect())
+            .collect())
+    }
+
+    /// [`Searcher::range_search_masked`] on a searcher over an f16 corpus (`pqv_range_search_masked_f16`).
+    pub fn range_search_masked_f16(&self, mask: &RowMask, queries: &[f32], dim: usize, radius: f32, nprobe: NonZeroUsize, max_results: u64)
+        -> Result<Vec<Vec<SearchResult>>> {
+        let nq = if dim == 0 { 0 } else { queries.len() / dim };
+        let (mut lims, mut rows, mut dist) = (ptr::null_mut::<u64>(), ptr::null_mut::<u32>(), ptr::null_mut::<f32>());
+        check(unsafe {
+            sys::pqv_range_search_masked_f16(self.raw, mask.raw, queries.as_ptr(), nq as u32, dim as u32, radius, nprobe.get() as u32, 0,
+                                             max_results, sys::PQV_L2SQ_REF4, 1, &mut lims, &mut rows, &mut dist, ptr::null_mut(), ptr::null_mut())
+        })?;
+        if lims.is_null() || rows.is_null() || dist.is_null() {
+            unsafe { sys::pqv_range_free(lims, rows, dist) };
+            return Err("pqv_range_search_masked_f16 returned a NULL buffer".into());
+        }
+        let out = {
+            let l = unsafe { std::slice::from_raw_parts(lims, nq + 1) };
+            let total = l[nq] as usize;
+            let (r, d) = if total == 0 {
+                (&[][..], &[][..])
+            } else {
+                unsafe { (std::slice::from_raw_parts(rows, total), std::slice::from_raw_parts(dist, total)) }
+            };
+            (0..nq)
+                .map(|q| (l[q] as usize..l[q + 1] as usize).map(|i| SearchResult { row_idx: r[i], distance: d[i] }).collect())
+                .collect()
+        };
+        unsafe { sys::pqv_range_free(lims, rows, dist) };
+        Ok(out)
+    }
+
     /// The keys of an integer column laid out for this searcher (`include/pqv.h`: `pqv_row_keys`); the column is copied.
     pub fn row_keys(&self, column: &Column) -> Result<RowKeys> {
         let mut raw = ptr::null_mut();

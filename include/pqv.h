@@ -236,10 +236,28 @@ void pqv_corpus_free(pqv_corpus *corpus);
  *               timing calls work.
  *   refused     everything else that would read row values returns PQV_ERR_UNSUPPORTED "<entry point> does not take f16
  *               corpora" before any device work, behind the entry point's own handle checks: PQV_COSINE and PQV_DOT on the served
- *               calls (the text names the metric: "PQV_DOT does not take f16 corpora"), the masked, keyed, filtered, expanding,
+ *               calls (the text names the metric: "PQV_DOT does not take f16 corpora"), the unsuffixed masked, keyed, filtered, expanding,
  *               depth, distinct, grouped, partition, candidate-list and MMR calls, pqv_table_searcher_create, pqv_brute_topk, pqv_kmeans, pqv_index_build,
  *               pqv_index_assign, pqv_index_append and pqv_index_compact.  pqv_index_remove* reads no rows and is unchanged.
- *               (The unsuffixed build / assign / append calls keep refusing: their f16 forms are the _f16 calls below.)
+ *               (The unsuffixed build / assign / append calls keep refusing: their f16 forms are the _f16 calls below.  The
+ *               unsuffixed masked calls pqv_topk_masked, pqv_topk_masked_device and pqv_range_search_masked keep refusing too:
+ *               their f16 forms are pqv_topk_masked_f16, pqv_topk_masked_device_f16 and pqv_range_search_masked_f16.)
+ *   masked      pqv_topk_masked_f16, pqv_topk_masked_device_f16 and pqv_range_search_masked_f16 (below, behind their f32 siblings)
+ *               search under a pqv_row_mask of the f16 searcher -- pqv_row_mask_create, _from_device and _from_predicates read no
+ *               row values and work on it as they are.  Results are what the sibling returns on an f32 searcher over the widened
+ *               rows under the same mask, bit for bit: row ids, distances, n_found, n_candidates, tie flags, lims and n_within;
+ *               max_candidates caps positions before the mask.  PQV_L2SQ_REF4 / PQV_L2SQ_SEQ, every dim.  Two routes:
+ *               exact     the default, and range search always: masked_stream_h_kernel, masked_stream_kernel's walk over the
+ *                         mask's position bitset with stream_h_kernel's chain tile; rows the mask excludes are never read.
+ *               screened  the two top-k forms under rerank_mode = 2, within the limits of "screened" above (PQV_L2SQ_REF4,
+ *                         dim % 8 == 0, dim <= 2240, k <= 127, or 128 for the device call without tie flags, min(nprobe,
+ *                         n_clusters) <= 1024, at most 65535 queries per device call); everything else takes the exact route
+ *                         silently.  The seed threshold comes from allowed rows only (so it bounds the masked k-th distance),
+ *                         the screen tests each row's own mask bit and skips 32-row tiles without an allowed row, and a query
+ *                         with fewer than k allowed candidates is walked exactly.  Results are the exact route's.
+ *               Counters: queries, candidate_rows and embeddings_fetched advance as pqv_topk_masked advances them on f32
+ *               (embeddings_fetched by the allowed rows among the capped candidates); screened_pairs (allowed (row, query)
+ *               pairs put through the bound) and screen_survivors advance on the screened route only.
  *   index       pqv_index_build_f16, pqv_index_assign_f16 and pqv_index_append_f16 (below, behind their f32 siblings) build,
  *               assign and append straight from the 2-byte rows; the result is what the f32 call gives on the widened column,
  *               byte for byte.  pqv_index_build_host (on widened rows), pqv_index_from_bytes and pqv_index_from_parts serve too. */
@@ -601,6 +619,20 @@ int pqv_range_search_masked(const pqv_searcher *searcher, const pqv_row_mask *ma
                             uint32_t query_len, float radius, uint32_t nprobe, uint64_t max_candidates, uint64_t max_results,
                             int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
                             uint64_t *n_within, uint64_t *n_candidates);
+/* The three calls above over an f16 searcher (half-precision corpora, "masked"): arguments, checks, error texts and results are
+ * their siblings'; the result is DEFINED as the sibling's on an f32 searcher over the rows widened to f32 under the same allow
+ * bytes.  They REQUIRE an f16 searcher: an f32 one is PQV_ERR_INVALID "corpus rows are f32".  PQV_COSINE and PQV_DOT are
+ * PQV_ERR_UNSUPPORTED "PQV_COSINE does not take f16 corpora" / "PQV_DOT does not take f16 corpora". */
+int pqv_topk_masked_f16(const pqv_searcher *searcher, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                        uint32_t query_len, uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                        uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates);
+int pqv_topk_masked_device_f16(const pqv_searcher *searcher, const pqv_row_mask *mask, const void *d_queries, uint32_t nq,
+                               uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out, void *d_row_idx,
+                               void *d_dist, void *d_n_found, void *d_n_candidates, void *d_tie_flags, void *hip_stream);
+int pqv_range_search_masked_f16(const pqv_searcher *searcher, const pqv_row_mask *mask, const float *queries, uint32_t nq,
+                                uint32_t query_len, float radius, uint32_t nprobe, uint64_t max_candidates, uint64_t max_results,
+                                int metric, int sqrt_out, uint64_t **lims, uint32_t **row_idx, float **dist,
+                                uint64_t *n_within, uint64_t *n_candidates);
 
 /* Predicate masks: the WHERE clause evaluated on the GPU.  A pqv_column is one scalar column resident on one GPU beside the
  * embedding column: one value per corpus row (PQV_COL_*), optionally validity bytes (u8 [n_rows], 0 = NULL).

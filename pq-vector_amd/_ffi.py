@@ -185,6 +185,12 @@ SIGNATURES = {
                                          vp, vp, vp, vp, vp, vp]),
     "pqv_range_search_masked": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64,
                                           C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
+    "pqv_topk_masked_f16": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                      C.c_int, C.c_int, u32p, f32p, u32p, u64p]),
+    "pqv_topk_masked_device_f16": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                             vp, vp, vp, vp, vp, vp]),
+    "pqv_range_search_masked_f16": (C.c_int, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64,
+                                              C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(f32p), u64p, u64p]),
     "pqv_row_keys_create": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "pqv_row_keys_rows": (C.c_uint64, [vp]),
     "pqv_row_keys_dtype": (C.c_int, [vp]),

@@ -1744,6 +1744,53 @@ class Searcher:
                                           vp(d_n_found or None), vp(d_n_candidates or None),
                                           vp(stream or None)))
 
+    def topk_f16(self, queries, k, nprobe, *, mask, max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True):
+        """topk(..., mask=) on a searcher over an f16 Corpus (pqv.h: pqv_topk_masked_f16): what topk(mask=) returns on an f32
+        searcher over the widened rows under the same allow bytes, bit for bit.  mask: a RowMask of this searcher (row_mask()).
+        Under set_option("rerank_mode", 2) the screened route runs where it applies; results do not change."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, qlen = q.shape
+        rows = np.full((nq, max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        nf = np.zeros(nq, dtype=np.uint32)
+        nc = np.zeros(nq, dtype=np.uint64)
+        _check(_ffi.lib().pqv_topk_masked_f16(self._h, _mask_handle(self, mask), q.ctypes.data_as(f32p), nq, qlen, k, nprobe,
+                                              max_candidates, metric, 1 if sqrt_out else 0, rows.ctypes.data_as(u32p),
+                                              dist.ctypes.data_as(f32p), nf.ctypes.data_as(u32p), nc.ctypes.data_as(u64p)))
+        return rows, dist, nf, nc
+
+    def topk_device_f16(self, d_queries, nq, k, nprobe, d_row_idx, d_dist, d_n_found=0, d_n_candidates=0, *, mask,
+                        max_candidates=0, metric=_ffi.PQV_L2SQ_REF4, sqrt_out=True, stream=0, d_tie_flags=0):
+        """topk_device(..., mask=) on a searcher over an f16 Corpus (pqv.h: pqv_topk_masked_device_f16); pointers, stream and
+        d_tie_flags as topk_device takes them."""
+        _check(_ffi.lib().pqv_topk_masked_device_f16(self._h, _mask_handle(self, mask), vp(d_queries), nq, k, nprobe, max_candidates,
+                                                     metric, 1 if sqrt_out else 0, vp(d_row_idx), vp(d_dist),
+                                                     vp(d_n_found or None), vp(d_n_candidates or None), vp(d_tie_flags or None),
+                                                     vp(stream or None)))
+
+    def range_search_f16(self, queries, radius, nprobe, *, mask, max_candidates=0, max_results=0, metric=_ffi.PQV_L2SQ_REF4,
+                         sqrt_out=True):
+        """range_search(..., mask=) on a searcher over an f16 Corpus (pqv.h: pqv_range_search_masked_f16): the f32 call's
+        (lims, rows, dist, n_within, n_candidates) over the widened rows under the same allow bytes, bit for bit."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        radius = float(radius)
+        if radius != radius:
+            raise PqvError(_ffi.PQV_ERR_INVALID, "radius must not be NaN")
+        nq, qlen = q.shape
+        nw = np.zeros(nq, dtype=np.uint64)
+        nc = np.zeros(nq, dtype=np.uint64)
+        lims_p, rows_p, dist_p = u64p(), u32p(), f32p()
+        _check(_ffi.lib().pqv_range_search_masked_f16(self._h, _mask_handle(self, mask), q.ctypes.data_as(f32p), nq, qlen, radius,
+                                                      nprobe, max_candidates, max_results, metric, 1 if sqrt_out else 0,
+                                                      C.byref(lims_p), C.byref(rows_p), C.byref(dist_p), nw.ctypes.data_as(u64p),
+                                                      nc.ctypes.data_as(u64p)))
+        lims, rows, dist = _take_range_buffers(nq, lims_p, rows_p, dist_p)
+        return lims, rows, dist, nw, nc
+
     def counters(self):
         c = _ffi.Counters()
         _check(_ffi.lib().pqv_counters(self._h, C.byref(c)))

@@ -672,6 +672,11 @@ struct SearchRequest {
 static inline uint32_t probe_arg(const SearchRequest *mv, uint32_t nprobe) { return mv && mv->expanding() ? mv->expand.max_nprobe : nprobe; }
 // a request whose rows are filtered or grouped takes the exact stream (plan_topk); one that only carries depths keeps the plain plan
 static inline bool stream_request(const SearchRequest *mv) { return mv && !mv->depth_only(); }
+// a request that is a shared row mask and nothing else (pqv_topk_masked* and their _f16 forms): what an f16 searcher serves, and
+// what its screened route runs under (plan_topk)
+static inline bool mask_only_request(const SearchRequest *mv) {
+    return mv && mv->rows.bits && !mv->filtered() && !mv->distinct() && !mv->expanding();
+}
 // a mask's row image, downloaded (n_rows / 8 bytes) and expanded to one 0 / 1 byte per row
 static int row_image_to_bytes(const pqv_row_mask *m, uint8_t *dst) {
     const uint64_t n_words = (m->n_rows + 63) / 64;
@@ -826,7 +831,11 @@ static pqv::GroupFilterArgs group_filter_args(const SearchRequest *mv) {
 static hipError_t launch_stream_pass(const pqv::StreamArgs &ra, const SearchRequest *rq, unsigned long long *stats, const uint64_t *n_cand,
                                      pqv::StreamMode mode, hipStream_t stream, int64_t *part_grp = nullptr,
                                      const uint32_t *rank_limit = nullptr) {
-    if (ra.mat_h) return rq ? hipErrorInvalidValue : pqv::launch_stream_h(ra, mode, stream);     // (f16 rows: the plain L2 call only)
+    if (ra.mat_h) {       // (f16 rows: the plain L2 call, or the L2 call under a row mask and nothing else -- the _f16 masked entry points)
+        if (!rq) return pqv::launch_stream_h(ra, mode, stream);
+        if (!mask_only_request(rq) || rank_limit) return hipErrorInvalidValue;
+        return pqv::launch_masked_stream_h(ra, pqv::MaskedArgs{rq->rows.bits, stats, n_cand, nullptr}, mode, stream);
+    }
     if (!rq) return ra.metric == PQV_DOT ? pqv::launch_dot_stream(ra, nullptr, mode, stream) : pqv::launch_stream(ra, mode, stream);
     if (rq->distinct()) {
         if (mode != pqv::STREAM_TOPK) return hipErrorInvalidValue;
@@ -4326,8 +4335,10 @@ static bool seed_refine_on(const pqv_searcher *s, uint32_t nq, uint32_t k) {
     return s->opt.seed_refine && (!s->d_row_of || s->images_only) && (s->sdim % 32) == 0 && k <= 16 && (s->opt.seed_refine > 1 || s->sdim >= 256);
 }
 // exact_stream: a masked call -- the per-(query, list) stream whatever the options say (the screened paths' thresholds come from
-// sampled rows the mask may exclude)
-TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t k = 1, int metric = 0, bool exact_stream = false) {
+// sampled rows the mask may exclude).  mask_only: the request is one shared row mask (mask_only_request) -- on f16 rows under
+// rerank_mode 2 the screened route still applies, its threshold taken from allowed rows only (half_seed_masked_kernel)
+TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t k = 1, int metric = 0, bool exact_stream = false,
+                   bool mask_only = false) {
     TopkPlan p{};
     const pqv_searcher::Opts &o = s->opt;
     const bool stream_req = exact_stream;           // (as asked for by the call: a request's walk)
@@ -4514,7 +4525,7 @@ TopkPlan plan_topk(const pqv_searcher *s, uint32_t nq, uint32_t nprobe, uint32_t
     // rows of whole 16-byte chunks whose query tile fits LDS, lists of at most 128 entries (k <= 127 where the list carries the
     // runner-up for the tie flag), the probe within the kernels' lists.  Everything else stays on stream_h_kernel: options never
     // change results.  The survivor pass writes HS_PARTS lists per query.
-    p.half_screen = s->half() && o.rerank_mode == 2 && metric == PQV_L2SQ_REF4 && !stream_req && (s->dim % 8) == 0 && k <= 128 &&
+    p.half_screen = s->half() && o.rerank_mode == 2 && metric == PQV_L2SQ_REF4 && (!stream_req || mask_only) && (s->dim % 8) == 0 && k <= 128 &&
                     p.np >= 1 && p.np <= 1024 && nq <= 0xFFFFu && static_cast<uint64_t>(nq) * p.np <= 0x7FFFFFFFull &&
                     32ull * ((s->dim + 63) / 64 * 8 + 1) * 16 <= pqv::half_screen_lds_max();
     if (p.half_screen) p.n_part_rr = pqv::HS_PARTS;
@@ -5259,7 +5270,9 @@ static int ensure_half_xs(const pqv_searcher *s, hipStream_t stream) {
 // survivor entries per query of the screened f16 route: 4096, fewer for very large batches (a list that overflows is walked exactly)
 static uint32_t half_surv_cap(uint32_t nq) { return static_cast<uint32_t>(std::max<uint64_t>(512, std::min<uint64_t>(4096, (1ull << 26) / std::max<uint32_t>(1, nq)))); }
 // stage 2 of an f16 searcher under rerank_mode 2 (TopkPlan::half_screen): query images, seed thresholds, the pairs bucketed by list,
-// screen_h_kernel and survivor_h_kernel -- the per-wave lists the final merge reads, keys as stream_h_kernel writes them
+// screen_h_kernel and survivor_h_kernel -- the per-wave lists the final merge reads, keys as stream_h_kernel writes them.  Under a
+// row mask (c.rq: mask_only_request) the same buffers and launches with the mask's image and allowed fraction: the keys are
+// masked_stream_h_kernel's, and the kernels count candidate_rows and the considered rows (the probe merge of a request counts nothing)
 static int enqueue_half_screen(TopkCall &c, const pqv::StreamArgs &ra) {
     using namespace pqv;
     const pqv_searcher *s = c.s; Scratch &sc = c.sc; const uint32_t nq = c.nq, kc = s->n_clusters, np = c.p.np;
@@ -5280,6 +5293,11 @@ static int enqueue_half_screen(TopkCall &c, const pqv::StreamArgs &ra) {
     a.hist = u; a.pair_off = u + 2ull * kc; a.item_off = u + 3ull * kc + 1; a.pairs = u + 4ull * kc + 2;
     a.surv = sc.s_hs_surv.as<uint2>(); a.surv_cnt = sc.s_hs_cnt.as<uint32_t>();
     a.stats = s->d_stats.as<unsigned long long>();
+    if (c.rq) {
+        a.mask_bits = c.rq->rows.bits; a.n_cand = c.pm.n_cand;
+        a.allowed_frac = static_cast<float>(std::min(1.0, static_cast<double>(c.rq->rows.mask->count) / static_cast<double>(std::max<uint64_t>(1, s->n))));
+        HIP_TRY(launch_half_screen_masked(a, c.stream));
+    } else
     HIP_TRY(launch_half_screen(a, c.stream));
     s->counters.kernel_launches += 5;       // (six launches for the stream pass's one)
     return PQV_OK;
@@ -5299,7 +5317,7 @@ int enqueue_topk(const pqv_searcher *s, const float *d_queries, uint32_t nq, uin
     const bool expand = rq && rq->expanding(), distinct = rq && rq->distinct(), depth = rq && rq->depth_only();
     const uint32_t p0 = probe_count(s, nprobe);
     nprobe = probe_arg(rq, nprobe);
-    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, stream_request(rq));
+    const TopkPlan p = plan_topk(s, nq, nprobe, k, metric, stream_request(rq), mask_only_request(rq));
     if (depth && (distinct || rq->filtered() || rq->rows.bits)) return fail(PQV_ERR_INVALID, "a depth call takes no filter and no grouping");
     if (expand && (s->n_files || (p.tile && !depth) || metric == PQV_DOT || max_candidates || p0 == 0 || p0 > p.np))
         return fail(PQV_ERR_INVALID, "expanding call on a plan that cannot expand");
@@ -5374,7 +5392,8 @@ bool grouped_beyond_kernel_lists(const pqv_searcher *s, uint32_t k, uint32_t gro
 // PQV_DOT (pqv.h): every entry point works within the kernels' lists, and keyed / distinct calls do not take it.  Checked behind
 // validate_topk, before any device work.
 int dot_checks(const pqv_searcher *s, uint32_t k, uint32_t nprobe, int metric, const SearchRequest *rq) {
-    // (f16 rows, pqv.h: the served calls take REF4 / SEQ only; every call with a request was refused by its entry point, by name)
+    // (f16 rows, pqv.h: the served calls, the masked _f16 forms among them, take REF4 / SEQ only; every other call with a request was
+    //  refused by its entry point, by name)
     if (metric == PQV_DOT || metric == PQV_COSINE) { if (int rc = refuse_f16(s, metric == PQV_DOT ? "PQV_DOT" : "PQV_COSINE")) return rc; }
     if (metric != PQV_DOT) return PQV_OK;
     if (rq && (rq->filtered() || rq->distinct())) return fail(PQV_ERR_UNSUPPORTED, "PQV_DOT is not supported by keyed and distinct calls");
@@ -5795,7 +5814,7 @@ static int pqv_topk_impl(const pqv_searcher *s, const float *queries, uint32_t n
     // bound the scratch: sub-batch so the per-wave partial lists stay under ~1 GiB
     // (per query: partial lists, probe partial lists, candidate buffer, the int8 images of its probed pairs; a grouping: 20 B per
     //  entry of the partial lists, and a grouped call's second pass 16 B per entry of k * m in the same buffers)
-    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(rq, nprobe), k_int, metric, stream_request(rq));
+    const TopkPlan p1 = plan_topk(s, std::min<uint32_t>(nq, 1024), probe_arg(rq, nprobe), k_int, metric, stream_request(rq), mask_only_request(rq));
     const uint64_t km = static_cast<uint64_t>(k) * m;
     const uint64_t per_query =
         grouped ? static_cast<uint64_t>(p1.n_part_rr) * std::max<uint64_t>(k * 20ull, m > 1 ? km * 16 + 4 : 0) +
@@ -6404,6 +6423,43 @@ extern "C" int pqv_range_search_masked(const pqv_searcher *s, const pqv_row_mask
         SearchRequest mv{};
         if (int rc = mask_view(s, mask, mv)) return rc;
         if (int rc = refuse_f16(s, "pqv_range_search_masked")) return rc;
+        return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
+                                     row_idx, dist, n_within, n_candidates, &mv);
+    });
+}
+
+// The three calls above over an f16 searcher (pqv.h: half-precision corpora, "masked"): the same bodies with the same request -- the
+// exact walk is masked_stream_h_kernel (launch_stream_pass), and under rerank_mode 2 the top-k forms take the screened route where
+// it applies (plan_topk: half_screen).  They require f16 rows; PQV_COSINE / PQV_DOT are refused by dot_checks, by the metric's name.
+extern "C" int pqv_topk_masked_f16(const pqv_searcher *s, const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len,
+                                   uint32_t k, uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                   uint32_t *row_idx, float *dist, uint32_t *n_found, uint64_t *n_candidates) {
+    return guard([&] {
+        SearchRequest mv{};
+        if (int rc = mask_view(s, mask, mv)) return rc;
+        if (!s->half()) return fail(PQV_ERR_INVALID, "corpus rows are f32");      // (as the _f16 index calls: rows_dtype_check)
+        return pqv_topk_impl(s, queries, nq, query_len, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, row_idx, dist, n_found, n_candidates, &mv);
+    });
+}
+extern "C" int pqv_topk_masked_device_f16(const pqv_searcher *s, const pqv_row_mask *mask, const void *d_queries, uint32_t nq, uint32_t k,
+                                          uint32_t nprobe, uint64_t max_candidates, int metric, int sqrt_out,
+                                          void *d_row_idx, void *d_dist, void *d_n_found, void *d_n_candidates,
+                                          void *d_tie_flags, void *hip_stream) {
+    return guard([&] {
+        SearchRequest mv{};
+        if (int rc = mask_view(s, mask, mv)) return rc;
+        if (!s->half()) return fail(PQV_ERR_INVALID, "corpus rows are f32");      // (as the _f16 index calls: rows_dtype_check)
+        return pqv_topk_device_impl(s, d_queries, nq, k, nprobe, max_candidates, metric, sqrt_out ? 1 : 0, d_row_idx, d_dist, d_n_found,
+                                    d_n_candidates, d_tie_flags, hip_stream, &mv);
+    });
+}
+extern "C" int pqv_range_search_masked_f16(const pqv_searcher *s, const pqv_row_mask *mask, const float *queries, uint32_t nq, uint32_t query_len,
+                                           float radius, uint32_t nprobe, uint64_t max_candidates, uint64_t max_results, int metric, int sqrt_out,
+                                           uint64_t **lims, uint32_t **row_idx, float **dist, uint64_t *n_within, uint64_t *n_candidates) {
+    return guard([&] {
+        SearchRequest mv{};
+        if (int rc = mask_view(s, mask, mv)) return rc;
+        if (!s->half()) return fail(PQV_ERR_INVALID, "corpus rows are f32");      // (as the _f16 index calls: rows_dtype_check)
         return pqv_range_search_impl(s, queries, nq, query_len, radius, nprobe, max_candidates, max_results, metric, sqrt_out ? 1 : 0, lims,
                                      row_idx, dist, n_within, n_candidates, &mv);
     });

@@ -101,9 +101,23 @@ struct HalfScreenArgs {
     uint32_t *surv_cnt;        // [nq]; may exceed surv_cap: the query is then walked exactly
     uint32_t  surv_cap;
     unsigned long long *stats; // optional: the statistics block (word 0 += screened pairs, word 1 += rows evaluated exactly)
+    // launch_half_screen_masked only (launch_half_screen: all unset)
+    const uint64_t *mask_bits; // the row mask's image over list positions (MaskedArgs::bits)
+    float allowed_frac;        // the mask's allowed count over the searcher's list positions, in [0, 1]: sizes the seed
+    const uint64_t *n_cand;    // optional [nq] (with stats): the probe merge's uncapped totals, added to candidate_rows once per query;
+                               // embeddings_fetched (word 3) += the allowed candidates below the cap
 };
 // Everything behind the probe of one batch, up to the per-wave lists the final merge reads; k <= 256, nprobe <= 1024, nq <= 65535.
 hipError_t launch_half_screen(const HalfScreenArgs &a, hipStream_t s);
+// The same route under a row mask (pqv_topk_masked_f16 under rerank_mode 2): the seed threshold from allowed rows only
+// (half_seed_masked_kernel), the lane's own mask bit in the screen's epilogue and tiles without a set bit skipped, the fallback walk
+// under the mask.  The per-wave lists hold launch_masked_stream_h's keys.
+hipError_t launch_half_screen_masked(const HalfScreenArgs &a, hipStream_t s);
+// launch_masked_stream's STREAM_TOPK / STREAM_RANGE pass over 2-byte rows a.mat_h (masked_stream_h_kernel, kernels_half_mask.hip): the
+// filtered walk over ma.bits with launch_stream_h's chain tile -- bit-identical to launch_masked_stream over the widened rows.
+// metric PQV_L2SQ_REF4 / PQV_L2SQ_SEQ, any dim; ma.rank_limit must be unset; no load reaches behind a row's last byte.
+struct MaskedArgs;
+hipError_t launch_masked_stream_h(const StreamArgs &a, const MaskedArgs &ma, StreamMode mode, hipStream_t s);
 // out[i, :] = rows[idx[i], :] widened to f32, i < m
 hipError_t launch_widen_rows_h(const uint16_t *rows, const uint32_t *idx, uint64_t m, uint32_t dim, float *out, hipStream_t s);
 

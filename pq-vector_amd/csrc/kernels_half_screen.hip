@@ -11,6 +11,11 @@
 //                         lane-owned side straight from global memory in operand layout, query images in LDS; survivors appended
 //   survivor_h_kernel     per query: 64 survivors per wave and tile through chain_tile_h into WaveTopk; an "exact" query (or one
 //                         whose survivor list overflowed) walks its probed lists as stream_h_kernel does
+//
+// Under a row mask (pqv_topk_masked_f16 / pqv_topk_masked_device_f16) the answer is masked_stream_h_kernel's and the
+// same launches run with three differences: half_seed_masked_kernel takes tau from ALLOWED rows only, screen_h_kernel<.., true>
+// tests the lane's own row against the mask image and skips a tile no bit of which is set, and survivor_h_kernel<.., true> walks
+// an "exact" query's lists under the mask.
 #include "half_tile.hpp"
 
 namespace pqv {
@@ -142,6 +147,80 @@ __global__ __launch_bounds__(256) void half_seed_kernel(const HalfScreenArgs a) 
 }
 
 // ------------------------------------------------------------------------------------
+// half_seed_masked_kernel: half_seed_kernel under a row mask -- one wave per query, 4 per block.  The seed rows are the first
+// n_seed ALLOWED candidates in probe order: the wave walks its probed lists rank by rank in 64-position windows of the mask image
+// (two words, funnel-shifted: a list does not begin at a multiple of 64), drops the bits at or beyond the candidate cap, and
+// compacts the set positions -- rank from mbcnt, through the first 256 words of the idle chain tile -- into a queue whose entries
+// carry the LIST position (-> storage row) and the CANDIDATE position (-> key).  Whenever 64 are queued one chain tile runs; the
+// walk stops at n_seed evaluated rows, or at the end of the capped walk, where what is left in the queue is the last tile.
+// n_seed is half_seed_kernel's with the allowed candidates ESTIMATED as total x allowed_frac (the mask's allowed count over the
+// searcher's positions: no second pass over the words); an estimate that is off costs survivors, never correctness.
+//
+// tau, the k-th smallest seed key's distance, is the distance of an allowed candidate below the cap with at least k - 1 allowed
+// candidates at or below it: an UPPER BOUND OF THE MASKED k-th DISTANCE.  That is the property a threshold from sampled rows
+// lacks on f32 (kernels_mask.hip: "a threshold from a row the mask excludes is no bound on the masked answer") and what lets the
+// screen run under a mask here.  Fewer than k allowed candidates in the whole capped walk: the query is "exact" -- the survivor
+// kernel walks it under the mask and finds n_found < k.
+// Also adds the probe merge's uncapped total n_cand[q] to candidate_rows (a masked call's merge counts nothing itself).
+// ------------------------------------------------------------------------------------
+template <int CGH, int S>
+__global__ __launch_bounds__(256) void half_seed_masked_kernel(const HalfScreenArgs a) {
+    static_assert(tile_words_h<CGH, false>() >= WindowQueue<true>::SCRATCH, "the compaction needs 256 words of the tile area");
+    __shared__ float lds_all[4 * tile_words_h<CGH, false>()];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float *lds = lds_all + wave * tile_words_h<CGH, false>();
+    const uint32_t q = blockIdx.x * 4 + wave, np = a.st.nprobe, k = a.st.k;
+    if (q >= a.st.nq) return;
+    const uint32_t *probe = a.st.probe + (uint64_t)q * np;
+    const uint64_t *cbase = a.st.cand_base + (uint64_t)q * np;
+    unsigned long long *st = stats_slot(a.stats, q);
+    if (st && a.n_cand && lane == 0) atomicAdd(&st[2], (unsigned long long)a.n_cand[q]);
+    const uint32_t c_last = probe[np - 1];
+    uint64_t total = cbase[np - 1] + (a.st.list_off[c_last + 1] - a.st.list_off[c_last]);
+    if (total > a.st.max_pos) total = a.st.max_pos;
+    bool exact = a.qflag[q] != 0u || total < (uint64_t)k;
+    if (!exact) {
+        const uint32_t least = k > 64u ? k : 64u;
+        const uint32_t ideal = ((uint32_t)fminf(sqrtf((float)total * a.allowed_frac * (float)k), 2048.0f) + 63u) & ~63u;
+        const uint32_t n_seed = ideal > least ? ideal : least;
+        const float *qv = a.st.queries + (uint64_t)q * a.st.dim;
+        WaveTopk<S> tk;
+        tk.init();
+        WindowQueue<true> wq;
+        wq.cq = reinterpret_cast<uint32_t *>(lds);
+        uint32_t n_have = 0;
+        auto seed_tile = [&](const QueueTile &t) {      // entry: list position (below the searcher's positions), payload: candidate position
+            const uint32_t my_srow = storage_row(a.st, t.my_r);
+            const float sum = chain_tile_h<CGH, false, 16>(a.st, lds, qv, my_srow, t.nvalid, lane);
+            tk.offer((uint32_t)lane < t.nvalid ? l2_key(sum, t.my_x) : KEY_EMPTY, my_srow, k, lane);
+            n_have += t.nvalid;
+        };
+        for (uint32_t j = 0; j < np && n_have < n_seed; ++j) {
+            const uint32_t c = probe[j];
+            const uint64_t lbeg = a.st.list_off[c], cb = cbase[j];
+            uint64_t len = a.st.list_off[c + 1] - lbeg;
+            const uint64_t room = a.st.max_pos > cb ? a.st.max_pos - cb : 0;
+            if (len > room) len = room;
+            for (uint64_t w0 = 0; w0 < len && n_have < n_seed; w0 += 64) {
+                const uint64_t clip = len - w0 < 64 ? (1ull << (len - w0)) - 1ull : ~0ull;
+                const uint64_t win = image_window(a.mask_bits, lbeg + w0) & clip;
+                const QueueTile t = wq.push(win, lbeg + w0, (uint32_t)(cb + w0) + (uint32_t)lane, lane);
+                if (t.nvalid) seed_tile(t);
+            }
+        }
+        if (n_have < n_seed) {          // the capped walk ended first: its last, partial tile
+            const QueueTile t = wq.flush(lane);
+            if (t.nvalid) seed_tile(t);
+        }
+        const uint64_t kk = tk.kth(k);
+        if (kk == KEY_EMPTY) exact = true;
+        else if (lane == 0) a.qinfo[q].w = __uint_as_float((uint32_t)(kk >> 32));
+    }
+    if (exact) { if (lane == 0) a.qflag[q] = 1u; return; }        // (walked exactly under the mask: none of its pairs is screened)
+    for (uint32_t j = lane; j < np; j += 64) atomicAdd(&a.hist[probe[j]], 1u);
+}
+
+// ------------------------------------------------------------------------------------
 // half_scan_kernel (one block): pair_off = exclusive sums of the histogram; item_off = exclusive sums of the lists' work items,
 // ceil(pairs / qt) query tiles x ceil(rows / HS_SEG_ROWS) segments.  Thread t owns a contiguous run of lists.
 // ------------------------------------------------------------------------------------
@@ -187,8 +266,14 @@ __global__ __launch_bounds__(256) void half_scatter_kernel(const HalfScreenArgs 
 //                query 32 t + (i & 3) + 8 (i >> 2) + 4 h.  mid = |q|^2 + xs^2 - 2 acc 2^-e, E = (|q|^2 + xs^2) eN + 2 qs (xs eA + eB),
 //                lb = (mid - E) (1 - cm) where positive; a pair survives unless lb > tau (NaN survives; xs = +inf survives).
 //   append       per register and half-wave one atomicAdd on the query's count, ranks from the ballot.
+//   MASKED       the 32 mask bits of a wave's tile -- list positions lbeg + row0 .. + 31: two words of the image, funnel-shifted,
+//                wave-uniform -- are loaded BEFORE the K loop and are in flight under it.  No bit set: the tile's loads, matrix
+//                instructions and epilogue are skipped (a wave-uniform branch; no barrier lies inside the row loop).  Else the
+//                epilogue's lane-local test gains one term, the lane's own bit: an excluded row survives for no query.
+//                screened_pairs counts allowed rows only; the allowed pairs below the cap are the call's considered rows and go
+//                to embeddings_fetched (a masked call's probe merge counts nothing).
 // ------------------------------------------------------------------------------------
-template <int NQT>
+template <int NQT, bool MASKED = false>
 __global__ __launch_bounds__(256) void screen_h_kernel(const HalfScreenArgs a) {
     constexpr int QT = 32 * NQT;
     extern __shared__ uint4 hs_q[];
@@ -201,6 +286,7 @@ __global__ __launch_bounds__(256) void screen_h_kernel(const HalfScreenArgs a) {
     const HalfBound hb = half_bound(dim);
     const uint32_t n_items = a.item_off[kc];
     unsigned long long n_screened = 0;
+    uint32_t n_considered = 0;              // MASKED: this lane's allowed pairs below the cap (< 2^32: a lane meets 16 NQT pairs per tile)
 
     for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         __syncthreads();                    // the previous item's LDS is read no more
@@ -234,7 +320,12 @@ __global__ __launch_bounds__(256) void screen_h_kernel(const HalfScreenArgs a) {
         const uint64_t s0 = (uint64_t)seg * HS_SEG_ROWS, s1 = s0 + HS_SEG_ROWS < len ? s0 + HS_SEG_ROWS : len;
         for (uint64_t row0 = s0 + (uint64_t)wave * 32; row0 < s1; row0 += 128) {
             const uint64_t lrow = row0 + (uint32_t)r;
-            const bool rvalid = lrow < s1;
+            bool rvalid = lrow < s1;
+            if constexpr (MASKED) {
+                const uint32_t tile_bits = (uint32_t)image_window(a.mask_bits, lbeg + row0);       // (row0 < s1 <= len: a position of the image)
+                if (__builtin_amdgcn_readfirstlane(tile_bits) == 0u) continue;
+                rvalid = rvalid && ((tile_bits >> r) & 1u);
+            }
             const uint32_t srow = storage_row(a.st, lbeg + (rvalid ? lrow : s1 - 1));
             const float xs = a.xs[srow];
             const uint16_t *xrow = a.st.mat_h + (uint64_t)srow * dim + (uint32_t)h * 32u;
@@ -288,6 +379,7 @@ __global__ __launch_bounds__(256) void screen_h_kernel(const HalfScreenArgs a) {
                         const float L = mid - E;
                         const float lb = L > 0.0f ? L * (1.0f - hb.cm) * 0.999999f : L;
                         keep = pos < a.st.max_pos && (xinf || !(lb > qi.w));
+                        if constexpr (MASKED) n_considered += pos < a.st.max_pos ? 1u : 0u;
                     }
                     const uint64_t m = __ballot(keep);
                     if (m) {
@@ -307,6 +399,11 @@ __global__ __launch_bounds__(256) void screen_h_kernel(const HalfScreenArgs a) {
         }
     }
     if (a.stats && lane == 0 && n_screened) atomicAdd(stats_slot(a.stats, blockIdx.x * 4 + wave), n_screened);
+    if constexpr (MASKED) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) n_considered += (uint32_t)__shfl_xor((int)n_considered, off, 64);
+        if (a.stats && lane == 0 && n_considered) atomicAdd(stats_slot(a.stats, blockIdx.x * 4 + wave) + 3, (unsigned long long)n_considered);
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -314,9 +411,14 @@ __global__ __launch_bounds__(256) void screen_h_kernel(const HalfScreenArgs a) {
 // through chain_tile_h, which gathers by storage row, and offers l2_key(sum, position): stream_h_kernel's keys.  A query flagged
 // "exact", or whose count ran past the list, walks its probed lists instead (rank g, g + HS_PARTS, ...), positions below the cap.
 // Every wave writes its list (empty ones too): the merge reads [nq][HS_PARTS][k].
+// MASKED: the survivors are allowed rows already; the walk of an "exact" query is masked_stream_h_kernel's filtered walk over each
+// of its lists (the window queue's compaction through the idle chain tile), so an excluded row is never loaded there either.  The
+// rows such a walk evaluates are the considered rows of a query flagged "exact" -- none of its pairs was screened -- and go to
+// embeddings_fetched; a query walked because its survivor list overflowed was counted by the screen.
 // ------------------------------------------------------------------------------------
-template <int CGH, int S>
+template <int CGH, int S, bool MASKED = false>
 __global__ __launch_bounds__(256) void survivor_h_kernel(const HalfScreenArgs a) {
+    static_assert(tile_words_h<CGH, false>() >= WindowQueue<false>::SCRATCH, "the compaction needs 128 words of the tile area");
     __shared__ float lds_all[4 * tile_words_h<CGH, false>()];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float *lds = lds_all + wave * tile_words_h<CGH, false>();
@@ -343,6 +445,15 @@ __global__ __launch_bounds__(256) void survivor_h_kernel(const HalfScreenArgs a)
             uint64_t len = a.st.list_off[c + 1] - lbeg;
             const uint64_t room = a.st.max_pos > cb ? a.st.max_pos - cb : 0;
             if (len > room) len = room;
+            if constexpr (MASKED) {
+                n_eval += filtered_walk<false>(
+                    lbeg, 0, len, lds, lane, [&](uint64_t p, uint64_t, uint64_t, uint32_t &) { return image_window(a.mask_bits, p); },
+                    [&](const QueueTile &t) {
+                        const uint32_t my_srow = storage_row(a.st, lbeg + t.my_r);
+                        const float sum = chain_tile_h<CGH, false, 16>(a.st, lds, qv, my_srow, t.nvalid, lane);
+                        tk.offer((uint32_t)lane < t.nvalid ? l2_key(sum, cb + t.my_r) : KEY_EMPTY, my_srow, k, lane);
+                    });
+            } else
             for (uint64_t t0 = 0; t0 < len; t0 += 64) {
                 const uint32_t nvalid = len - t0 < 64 ? (uint32_t)(len - t0) : 64u;
                 const uint32_t lrow = (uint32_t)lane < nvalid ? (uint32_t)lane : nvalid - 1;
@@ -355,12 +466,17 @@ __global__ __launch_bounds__(256) void survivor_h_kernel(const HalfScreenArgs a)
     }
     write_partial_lists<S>(a.st.part_keys, a.st.part_vals, ((uint64_t)q * HS_PARTS + g) * k, k, lane, tk.key, tk.val);
     if (a.stats && lane == 0 && n_eval) atomicAdd(stats_slot(a.stats, q) + 1, n_eval);
+    if constexpr (MASKED) {
+        if (a.stats && lane == 0 && n_eval && a.qflag[q] != 0u) atomicAdd(stats_slot(a.stats, q) + 3, n_eval);
+    }
 }
 
-// the whole route behind the probe: images, seeds, bucketing, screen, survivors (six launches on `s`)
-hipError_t launch_half_screen(const HalfScreenArgs &a, hipStream_t s) {
+// the whole route behind the probe: images, seeds, bucketing, screen, survivors (six launches on `s`); MASKED: under a.mask_bits
+template <bool MASKED>
+static hipError_t launch_half_screen_m(const HalfScreenArgs &a, hipStream_t s) {
     const StreamArgs &st = a.st;
     if (st.nq == 0) return hipSuccess;
+    if (MASKED ? !a.mask_bits || !(a.allowed_frac >= 0.0f && a.allowed_frac <= 1.0f) : a.mask_bits != nullptr) return hipErrorInvalidValue;
     if (!st.mat_h || !st.probe || !st.cand_base || !st.list_off || !a.xs || st.dim == 0 || st.dim % 8 != 0 || st.k == 0 || st.k > 256 ||
         st.nprobe == 0 || st.nprobe > 1024 || a.n_clusters == 0 || (a.qt != 32 && a.qt != 64) || a.surv_cap == 0 || st.nq > 0xFFFFu ||
         (uint64_t)st.nq * st.nprobe > 0x7FFFFFFFull)
@@ -370,8 +486,11 @@ hipError_t launch_half_screen(const HalfScreenArgs &a, hipStream_t s) {
     if (lds > half_screen_lds_max()) return hipErrorInvalidValue;
     const uint32_t qblocks = (st.nq + 3) / 4;
     hipLaunchKernelGGL(half_query_kernel, dim3(qblocks), dim3(256), 0, s, a);
-    auto seed = [&](auto cgh, auto slots) { hipLaunchKernelGGL((half_seed_kernel<cgh.value, slots.value>), dim3(qblocks), dim3(256), 0, s, a); };
-    auto surv = [&](auto cgh, auto slots) { hipLaunchKernelGGL((survivor_h_kernel<cgh.value, slots.value>), dim3(HS_PARTS / 4, st.nq), dim3(256), 0, s, a); };
+    auto seed = [&](auto cgh, auto slots) {
+        if constexpr (MASKED) hipLaunchKernelGGL((half_seed_masked_kernel<cgh.value, slots.value>), dim3(qblocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((half_seed_kernel<cgh.value, slots.value>), dim3(qblocks), dim3(256), 0, s, a);
+    };
+    auto surv = [&](auto cgh, auto slots) { hipLaunchKernelGGL((survivor_h_kernel<cgh.value, slots.value, MASKED>), dim3(HS_PARTS / 4, st.nq), dim3(256), 0, s, a); };
     auto by_shape = [&](auto f) {
         using I = std::integral_constant<int, 1>; using IV = std::integral_constant<int, 4>;
         using C16 = std::integral_constant<int, 16>; using C32 = std::integral_constant<int, 32>;
@@ -383,13 +502,16 @@ hipError_t launch_half_screen(const HalfScreenArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(half_scatter_kernel, dim3(std::min<uint32_t>(1024, (st.nq * st.nprobe + 255) / 256)), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const void *kern = a.qt == 64 ? reinterpret_cast<const void *>(screen_h_kernel<2>) : reinterpret_cast<const void *>(screen_h_kernel<1>);
+    const void *kern = a.qt == 64 ? reinterpret_cast<const void *>(screen_h_kernel<2, MASKED>) : reinterpret_cast<const void *>(screen_h_kernel<1, MASKED>);
     e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { (void)hipGetLastError(); return e; }
-    if (a.qt == 64) hipLaunchKernelGGL(screen_h_kernel<2>, dim3(1024), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(screen_h_kernel<1>, dim3(1024), dim3(256), lds, s, a);
+    if (a.qt == 64) hipLaunchKernelGGL((screen_h_kernel<2, MASKED>), dim3(1024), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((screen_h_kernel<1, MASKED>), dim3(1024), dim3(256), lds, s, a);
     by_shape(surv);
     return hipGetLastError();
 }
+hipError_t launch_half_screen(const HalfScreenArgs &a, hipStream_t s) { return launch_half_screen_m<false>(a, s); }
+// ... under a row mask: half_seed_masked_kernel, screen_h_kernel<.., true>, survivor_h_kernel<.., true>
+hipError_t launch_half_screen_masked(const HalfScreenArgs &a, hipStream_t s) { return launch_half_screen_m<true>(a, s); }
 
 }  // namespace pqv
